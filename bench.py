@@ -1,26 +1,38 @@
 #!/usr/bin/env python3
 """Benchmark of the pyramid style-transfer hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one closure evaluation (the reference's `step` counter, neural_style_transfer.py:198)
 of the BASELINE workload - L=2: levels 1536x1024 + 768x512 + 384x256, synthetic 3:2 images,
 seeded synthetic VGG19 weights, content+noise init, L-BFGS as the reference constructs it - run
 through the optimiser driver, i.e. K closures = K/2 `optimizer.step(closure)` turns, each followed
 by the per-step image yield (unprepare + D2H) exactly as NeuralStyleTransfer.process does.
-Everything the step reads is resident in HBM before the timed region starts.
+Everything the step reads is resident in HBM before the timed region starts.  The timed region holds
+exactly K closure evaluations (odd K: the last one is the first evaluation of the next optimiser
+step, a closure at the current image); only a step that takes more evaluations than are left (the
+25-evaluation line search) can overshoot, and `steps` reports what ran.  Sharded modes (levels,
+stripes) time whole optimiser steps: K is rounded down to a multiple of 2 there (L-BFGS, max_eval 1).
+
+--dump-outputs DIR: after the timed region, what its last optimiser step handed its caller, as
+float32 .npy files: image.npy (the yielded H x W x 3 image) and loss_rows.npy (the loss rows of
+that step's closure evaluations, and of the trailing single evaluation for odd K).  The inputs are
+seeded: the same arguments give the same inputs in every run.
 
 N > 1 (launched with torch.distributed.run, one rank per GPU): every rank optimises an independent
 content x style job of the same shape (BASELINE config 5, task_executor throughput mode); there is
 no data-path collective, `value` is the whole-node closure rate, scaling is weak.
 
-Beside the headline (N = 1 only, after the timed region; none of it is inside `value`):
+A plain run does the headline only.  --full adds, as before: HIP events around the dominant kernel's
+launches in the timed region (roofline, kernel_ms_per_closure; --no-kernel-timing leaves them out),
+and after the timed region (N = 1 only; none of it is inside `value`):
   exact_f32        the same job on the exact fp32 MFMA (nst_options.conv_mode = f32), priced against the 157.3 TF fp32 peak;
   sustained        the headline job kept running for >= 5 s whatever --steps says, with the shader clock sampled from sysfs;
   direct_convolution   the same job with nst_options.h2_winograd = 0 (no launch in the Winograd form)
   progressing_job  jobs whose image moves at every step (Adam; L-BFGS with the 25-evaluation line search), so that the
                    optimiser update with a filling curvature history is in a driver-seen number;
-  cpu_baseline     the oracle timed on this box's host cores on a bounded sample of the same job.
+  cpu_baseline     the oracle timed on this box's host cores on a bounded sample of the same job;
+  roofline.traffic two rocprofv3 counter passes over a few closures in a child process (--no-traffic skips them).
 
 Prints ONE JSON line (rank 0)."""
 from __future__ import annotations
@@ -305,6 +317,7 @@ class JobLoop:
         self.eng, self.x, self.opt, self.stream = eng, x, opt, stream
         self.cw, self.sw, self.tvw = weights3
         self.do_yield = do_yield
+        self.split = 0                    # > 0: evaluations one optimiser step takes; fewer left are single closures
         H, W = eng.shape
         self.img_host = [torch.empty((H, W, 3), dtype=torch.float32, pin_memory=True) for _ in range(2)]
         self.copy_stream = torch.cuda.Stream()
@@ -313,6 +326,8 @@ class JobLoop:
         self.opt_steps = 0
         self.accepted = 0
         self.history = 0
+        self.last_yield = None            # index into img_host of the last yielded image
+        self.tail_losses = None           # device loss row of a trailing single closure evaluation, else None
 
     def run(self, closures: int):
         if self.stream is not None:                      # an extra job: its own stream (per-thread current stream)
@@ -326,7 +341,14 @@ class JobLoop:
         done = 0
         last = None
         k = 0
+        self.tail_losses = None
         while done < closures:
+            if closures - done < self.split:
+                # fewer evaluations left than an optimiser step takes: the first evaluation of the next step (a closure at
+                # the current image; x and the optimiser stay as they are) makes the count exact
+                _, self.tail_losses = self.eng.closure(self.x, self.cw, self.sw, self.tvw)
+                done += 1
+                continue
             info, rows = self.opt.step(self.x, self.cw, self.sw, self.tvw, want_losses=True)
             done += info.closures
             self.opt_steps += 1
@@ -346,11 +368,30 @@ class JobLoop:
                     ev = torch.cuda.Event()
                     ev.record()
                 self.copy_done[k] = ev
+                self.last_yield = k
                 k ^= 1
         for ev in self.copy_done:
             if ev is not None:
                 ev.synchronize()
         return done, last
+
+
+def dump_outputs(out_dir: str, job: JobLoop, last_rows):
+    """--dump-outputs: what the last timed optimiser step handed its caller (NeuralStyleTransfer.process yields the image
+    and records the loss rows), float32: image.npy (H, W, 3) and loss_rows.npy (closures, 4 * levels + 1).  The loss row of
+    a trailing single closure evaluation (odd --steps) is the last row."""
+    torch.cuda.synchronize()
+    if job.do_yield and job.last_yield is not None:
+        image = job.img_host[job.last_yield].numpy()
+    else:
+        image = job.eng.unprepare_img(job.x).cpu().numpy()
+    rows = [np.asarray(last_rows, dtype=np.float32).reshape(-1, job.opt.row)] if last_rows is not None else []
+    if job.tail_losses is not None:
+        rows.append(job.tail_losses.cpu().numpy().reshape(1, -1))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "image.npy"), np.ascontiguousarray(image, dtype=np.float32))
+    np.save(os.path.join(out_dir, "loss_rows.npy"),
+            np.concatenate(rows).astype(np.float32) if rows else np.zeros((0, job.opt.row), np.float32))
 
 
 def timed(job: JobLoop, closures: int):
@@ -403,21 +444,26 @@ def ranks_present(dist, device) -> int:
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=40, help="closure evaluations in the timed region (even)")
+    ap.add_argument("--steps", type=int, default=40, help="closure evaluations in the timed region")
     ap.add_argument("--warmup", type=int, default=4)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed optimiser step handed its caller as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: kernel timing and roofline, the side jobs (sustained, exact_f32, "
+                         "progressing_job, direct_convolution), the measured traffic and the CPU baseline")
     ap.add_argument("--levels", type=int, default=3, help="levels_num (3 = BASELINE L=2)")
     ap.add_argument("--optimizer", default="lbfgs", choices=["lbfgs", "adam"])
     ap.add_argument("--lbfgs-max-eval", type=int, default=1,
                     help="1 = the reference's constructor arguments under torch 2.10 (one trial point per step, almost always "
                          "rejected: SURVEY F5); 26 = the line search older torch performed")
     ap.add_argument("--no-yield", action="store_true", help="skip the per-step image yield (unprepare + D2H)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip exact_f32 / sustained / progressing_job")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip exact_f32 / sustained / progressing_job")
     ap.add_argument("--sustained-seconds", type=float, default=5.0)
     ap.add_argument("--cpu-closures", type=int, default=2)
-    ap.add_argument("--no-kernel-timing", action="store_true")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the two rocprofv3 counter passes behind roofline.traffic (~40 s)")
-    ap.add_argument("--time-all-kernels", action="store_true", help="event pairs around every launch (slower)")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="--full: no HIP events in the timed region")
+    ap.add_argument("--no-traffic", action="store_true", help="--full: skip the two rocprofv3 counter passes behind roofline.traffic (~40 s)")
+    ap.add_argument("--time-all-kernels", action="store_true", help="--full: event pairs around every launch (slower)")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL over xGMI) or gloo (rehearsals)")
     ap.add_argument("--comm", default="c-abi", choices=["c-abi", "torch"],
                     help="mode 'levels': the per-closure collective behind the C ABI (nst_comm_*: one ncclAllReduce of the "
@@ -438,6 +484,11 @@ def main():
                          "job, pyramid levels sharded over the ranks, RCCL all-reduce of the pixel gradient per "
                          "closure (BASELINE config 4, strong scaling, capped at 1.33x by the 75/19/5/1 % split)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        # a plain run is the headline only: everything else is behind --full
+        args.no_kernel_timing = args.no_extras = args.no_cpu_baseline = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # Started plainly: launch the N ranks ourselves, as CHILD processes of a parent that has not touched the GPU
@@ -506,6 +557,8 @@ def main():
     cw, sw, tvw = w3
     H, W = eng.shape
     per_step = 2 if (args.optimizer == "lbfgs" and args.lbfgs_max_eval == 1) else 1
+    # a sharded closure is a collective of all ranks: there the timed region stays whole optimiser steps
+    split = 0 if sharded else per_step
 
     jobs = [JobLoop(eng, x, opt, w3, not args.no_yield)]
     extra = []
@@ -538,7 +591,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    steps = max(per_step, (args.steps // per_step) * per_step)
+    steps = args.steps if split else max(per_step, (args.steps // per_step) * per_step)
     # part of the set-up, not of the --warmup steps: one closure evaluation that leaves x and the optimiser untouched, so
     # that the one-off cold launch of the backward kernels (code-object load, ~17 ms) never lands in a timed region
     for j in jobs:
@@ -554,6 +607,7 @@ def main():
         eng.timing_totals(0, reset=True)
     for j in jobs:
         j.opt_steps = j.accepted = 0
+        j.split = split                  # the timed region holds exactly `steps` closure evaluations
     barrier()
     t0 = time.perf_counter()
     done, last_rows = run(steps)
@@ -563,6 +617,8 @@ def main():
     total_done, dt = sharding.aggregate_throughput(done, dt, dist, device="cuda")
     if sharded:
         total_done = done            # every rank counted the same closures of the one shared job
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, jobs[0], last_rows)
 
     if rank == 0:
         px = sum((H >> l) * (W >> l) for l in range(args.levels))

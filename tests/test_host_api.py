@@ -536,7 +536,7 @@ def test_process_closed_early_or_failing_releases_after_the_step(monkeypatch):
 
 # ---------------------------------------------------------------- the bench record's contract
 def test_committed_bench_record_has_the_contract_fields():
-    """profiles/r03_bench_default.json is the line `python bench.py` printed on an MI355X: the fields the driver parses, the
+    """profiles/r03_bench_default.json is the line `python bench.py --full` printed on an MI355X: the fields the driver parses, the
     roofline object (with a measured traffic figure) and the CPU baseline object must be there and consistent."""
     import json
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
