@@ -52,6 +52,7 @@ SYMBOLS = {
     "nst_ctx_create_ex": (C.c_int, [C.c_int, C.POINTER(c_void), C.POINTER(c_void), C.POINTER(Options), C.POINTER(c_void)]),
     "nst_ctx_destroy": (None, [c_void]),
     "nst_job_configure": (C.c_int, [c_void, C.c_int, C.c_int, C.c_int]),
+    "nst_job_set_taps": (C.c_int, [c_void, C.c_int, C.c_uint, C.c_int]),
     "nst_level_set_targets": (C.c_int, [c_void, C.c_int, c_void, c_void, C.c_int, C.c_int, c_void]),
     "nst_closure": (C.c_int, [c_void, c_void, C.c_float, C.c_float, C.c_float, c_void, c_void, c_void]),
     "nst_closure_levels": (C.c_int, [c_void, c_void, C.c_float, C.c_float, C.c_float, C.c_uint, c_void, c_void, c_void]),

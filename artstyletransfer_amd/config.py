@@ -19,6 +19,13 @@ _DEFAULTS = dict(
     noise_levels_peripheral_amplitude=(0.20, 0.30, 0.40, 0.10, 0.00),
     noise_levels_dispersion=(0.20, 0.30, 0.40, 0.60, 0.30),
 )
+# extension, keyword-only: the feature maps the losses read (neural_style_transfer(..., content_layer=, style_layers=,
+# use_relu=)); None = the reference's content 4 / style [0, 1, 2, 3, 5].  Not part of the positional order or the repr.
+_KW_ONLY = dict(
+    content_layer=None,            # index 0..5 or a name of Vgg19.layer_names
+    style_layers=None,             # indices / names
+    use_relu=True,                 # False: the reference's Vgg19(use_relu=False) taps
+)
 
 
 class Config:
@@ -33,10 +40,10 @@ class Config:
             if name in kwargs:
                 raise TypeError(f"Config() got multiple values for argument '{name}'")
             kwargs[name] = value
-        unknown = set(kwargs) - set(_DEFAULTS)
+        unknown = set(kwargs) - set(_DEFAULTS) - set(_KW_ONLY)
         if unknown:
             raise TypeError(f"Config() got unexpected keyword argument(s): {sorted(unknown)}")
-        for name, default in _DEFAULTS.items():
+        for name, default in {**_DEFAULTS, **_KW_ONLY}.items():
             setattr(self, name, kwargs.get(name, default))
 
     def __repr__(self):

@@ -28,10 +28,11 @@ const int kCin[NL] = {3, 64, 64, 128, 128, 256, 256, 256, 256, 512, 512, 512, 51
 const int kCout[NL] = {64, 64, 128, 128, 256, 256, 256, 256, 512, 512, 512, 512, 512};
 const int kScale[NL] = {0, 0, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4};      // log2 of the spatial divisor
 const int kPoolAfter[4] = {1, 3, 7, 11};
-const int kStyleLayer[5] = {0, 2, 4, 8, 12};                          // relu1_1, relu2_1, relu3_1, relu4_1, relu5_1
-constexpr int kContentLayer = 9;                                       // ReLU(conv4_2)
 // reference output index (neural_nets.py:22) -> conv layer
 const int kTapLayer[6] = {0, 2, 4, 8, 9, 12};
+// the reference's default taps (neural_nets.py:25-28): content 4 = ReLU(conv4_2), style 0, 1, 2, 3, 5 =
+// relu1_1, relu2_1, relu3_1, relu4_1, relu5_1; a context's own taps (nst_job_set_taps) live in nst_ctx::taps
+constexpr int kMaxStyle = 6;
 
 thread_local std::string g_err;
 
@@ -45,18 +46,36 @@ struct ActSet {                 // activations of one forward pass, NHWC
     bool bits_valid[NL] = {};    // written by the last forward pass (false when that layer ran split-K / fp32)
     bool pooled[4] = {};         // pool[k] already produced by the conv epilogue of the last forward pass
     // absmax records for the fp16-piece convolutions (conv_h2.hip): AMAX_IDS x NST_AMAX_SLOTS words.
-    // ids: act[l] -> l; the Gram factor S of style layer q -> NL + q; the gradient w.r.t. the pre-ReLU output of
-    // layer l (or a bound of it: the pooled gradient it was un-pooled from) -> NL + 5 + l
+    // ids: act[l] -> l; the Gram factor S of style slot q -> NL + q (6 slots); the gradient w.r.t. the pre-ReLU output
+    // of layer l (or a bound of it: the pooled gradient it was un-pooled from) -> NL + 6 + l
     unsigned* amax = nullptr;
     // arg-max codes of the four max-pools, written by the fused pooling of the f16x2 forward launches and read by
     // the un-pooling loader of the input-gradient launch below each pool: [H/2*W/2][C/32][4] words
     unsigned* pcode[4] = {};
     size_t bytes = 0;
 };
-constexpr int AMAX_IDS = 2 * NST_VGG19_CONVS + 5;
+constexpr int AMAX_IDS = 2 * NST_VGG19_CONVS + kMaxStyle;
 inline unsigned* amax_act(const ActSet& a, int l) { return a.amax + (size_t)l * NST_AMAX_SLOTS; }
 inline unsigned* amax_S(const ActSet& a, int q) { return a.amax + (size_t)(NST_VGG19_CONVS + q) * NST_AMAX_SLOTS; }
-inline unsigned* amax_grad(const ActSet& a, int l) { return a.amax + (size_t)(NST_VGG19_CONVS + 5 + l) * NST_AMAX_SLOTS; }
+inline unsigned* amax_grad(const ActSet& a, int l) { return a.amax + (size_t)(NST_VGG19_CONVS + kMaxStyle + l) * NST_AMAX_SLOTS; }
+
+// The feature maps a job's losses read (nst_job_set_taps), as conv layers.  The reference's LossBuilder keeps the indices
+// of enumerate(features) that are `in` its lists (neural_style_transfer.py:48-64): order and repeats do not matter, the
+// style term is the mean over the distinct maps kept (:104-106).
+struct Taps {
+    int content = 9;                           // conv layer of the content map
+    int style[kMaxStyle] = {0, 2, 4, 8, 12};   // conv layers of the style maps, ascending (style slot q -> style[q])
+    int nstyle = 5;
+    int top = 12;                              // the deepest layer any loss reads: the forward stops, the backward starts there
+    int use_relu = 1;                          // 0: tap 5 is conv5_1 BEFORE its ReLU (neural_nets.py:24-26 with use_relu=False)
+    bool is_default = true;
+    int style_slot(int l) const {
+        for (int q = 0; q < nstyle; ++q) if (style[q] == l) return q;
+        return -1;
+    }
+    // the top layer's gradient goes through its ReLU mask unless it is the pre-ReLU conv5_1
+    bool top_mask() const { return use_relu || top != NST_VGG19_CONVS - 1; }
+};
 
 enum KClass { K_CONV3 = 0, K_GRAM = 1, K_CONV1 = 2, K_OTHER = 3, K_NCLASS = 4 };
 
@@ -71,12 +90,13 @@ struct LevelWs {
     float* gxl = nullptr;       // its gradient (levels >= 1), planar
     float* content_t = nullptr; // NHWC target ReLU(conv4_2)
     size_t content_n = 0;
-    float* gram_t[5] = {};
-    float* S[5] = {};
-    unsigned short* S_bf[5] = {};
+    float* gram_t[kMaxStyle] = {};
+    float* S[kMaxStyle] = {};
+    unsigned short* S_bf[kMaxStyle] = {};
     float* gram_part = nullptr;
     size_t gram_part_floats = 0;
-    double* style_partial[5] = {};
+    double* style_partial[kMaxStyle] = {};
+    int tap_c[kMaxStyle] = {};  // channels of the style map each Gram buffer was sized for
     double* content_partial = nullptr;
     double* tv_partial = nullptr;
     float* tv_means = nullptr;
@@ -130,6 +150,7 @@ struct nst_ctx {
     float* w11k = nullptr;      // [28][64]
     float* w11d = nullptr;      // [9][64][4]
     int levels = 0;
+    Taps taps;                  // nst_job_set_taps
     LevelWs lv[NST_MAX_LEVELS];
     hipEvent_t fork = nullptr;
     size_t bytes = 0;
@@ -471,7 +492,7 @@ int forward(nst_ctx* ctx, ActSet& a, const float* x, int h, int w, hipStream_t s
     for (int l = 0; l < NL; ++l) a.bits_valid[l] = false;
     for (int k = 0; k < 4; ++k) a.pooled[k] = false;
     const bool h2 = ctx->conv_mode == 2;
-    if (h2) HIPCHK(ctx, launch_zero(a.amax, (size_t)(NL + 5) * NST_AMAX_SLOTS, s));     // act + S records
+    if (h2) HIPCHK(ctx, launch_zero(a.amax, (size_t)(NL + kMaxStyle) * NST_AMAX_SLOTS, s));     // act + S records
     {
         Timer t(ctx, s, K_CONV1, conv_flops(h, w, 3, 64, 9));
         unsigned* bits = ctx->conv_mode ? a.bits[0] : nullptr;
@@ -483,7 +504,8 @@ int forward(nst_ctx* ctx, ActSet& a, const float* x, int h, int w, hipStream_t s
         const float* in = (pk >= 0) ? a.pool[pk] : a.act[l - 1];
         ConvParams p{};
         p.in = in; p.wt = ctx->wf[l]; p.bias = ctx->bias[l]; p.addend = nullptr; p.mask = nullptr; p.out = a.act[l];
-        p.H = a.h[l]; p.W = a.w[l]; p.Cin = kCin[l]; p.Cout = kCout[l]; p.relu = 1;
+        p.H = a.h[l]; p.W = a.w[l]; p.Cin = kCin[l]; p.Cout = kCout[l];
+        p.relu = (l == NL - 1 && !ctx->taps.use_relu) ? 0 : 1;      // conv5_1 before its ReLU (use_relu = 0)
         p.partial = a.splitk; p.partial_floats = a.splitk_floats; p.wt_bf = ctx->wf_bf[l];
         if (h2) {
             p.wt_h2 = ctx->wf_h2[l]; p.wt_h2_inv = ctx->wf_h2_inv[l];
@@ -526,32 +548,42 @@ struct Inject {
 struct ContentJob { const float* target; size_t n; float coef; double* partial; };
 
 // Backward through the network down to the planar image gradient gx (overwritten).
-// inj[l] describes what enters at conv layer l; gbuf: two NHWC scratch buffers of the largest size.
+// inj[l] describes what enters at conv layer l; gbuf: two NHWC scratch buffers of the largest size.  The chain starts at
+// layer `top` (nothing above it is read); `top_mask` = false: the top map is pre-ReLU (its gradient passes unmasked).
 int backward(nst_ctx* ctx, ActSet& a, const Inject* inj, const ContentJob* cj, float* gbuf0, float* gbuf1, float* gx,
-             int h, int w, hipStream_t s) {
+             int h, int w, hipStream_t s, int top = NL - 1, bool top_mask = true) {
     float* cur = gbuf0;     // holds the gradient w.r.t. the pre-ReLU output of the layer being processed
     float* oth = gbuf1;
     const bool h2 = ctx->conv_mode == 2;
     if (h2) HIPCHK(ctx, launch_zero(amax_grad(a, 0), (size_t)NL * NST_AMAX_SLOTS, s));
-    // top: layer 12
+    // top of the chain
     {
-        const int l = NL - 1;
+        const int l = top;
         const size_t n = (size_t)a.h[l] * a.w[l] * kCout[l];
+        const bool content = inj[l].content && cj;
+        if (content) {
+            Timer t(ctx, s, K_OTHER, 0);
+            HIPCHK(ctx, launch_mse_grad(a.act[l], cj->target, cj->n, cj->coef, oth, cj->partial, s));
+        }
         if (inj[l].S) {
+            // (the content gradient, if any, as the addend of the 1x1 Gram launch)
             ConvParams p{};
-            p.in = a.act[l]; p.wt = inj[l].S; p.out = cur; p.mask = a.act[l];
+            p.in = a.act[l]; p.wt = inj[l].S; p.out = cur; p.mask = top_mask ? a.act[l] : nullptr;
+            p.addend = content ? oth : nullptr;
             p.H = a.h[l]; p.W = a.w[l]; p.Cin = kCout[l]; p.Cout = kCout[l];
             Timer t(ctx, s, K_GRAM, conv_flops(p.H, p.W, p.Cin, p.Cout, 1));
             HIPCHK(ctx, launch_conv_mfma(p, 1, s));
-        } else if (inj[l].direct) {
+        } else if (content || inj[l].direct) {
+            const float* g = content ? oth : inj[l].direct;
             Timer t(ctx, s, K_OTHER, 0);
-            HIPCHK(ctx, launch_relu_mask(a.act[l], inj[l].direct, n, cur, s));
+            if (top_mask) HIPCHK(ctx, launch_relu_mask(a.act[l], g, n, cur, s));
+            else HIPCHK(ctx, launch_copy(g, cur, n, s));
         } else {
             HIPCHK(ctx, launch_zero(cur, n, s));
         }
         if (h2) HIPCHK(ctx, launch_absmax_slots(cur, n, amax_grad(a, l), s));
     }
-    for (int l = NL - 1; l >= 1; --l) {
+    for (int l = top; l >= 1; --l) {
         // cur = g(pre-ReLU of layer l), dims of layer l, kCout[l] channels.  dgrad -> gradient w.r.t.
         // layer l's input: either pool[k] (then un-pool into act[l-1]'s shape) or act[l-1] directly.
         const int pk = pool_index_after(l - 1);
@@ -579,6 +611,15 @@ int backward(nst_ctx* ctx, ActSet& a, const Inject* inj, const ContentJob* cj, f
             const Inject& in = inj[m];
             const bool fuse = bf3_unsplit(ctx, p);
             double extra_flops = 0;
+            // the content gradient first: a Gram term of the same map then rides on the launch as well (second K source)
+            // or accumulates into the addend (standalone 1x1 launch)
+            if (in.content && cj) {
+                Timer t(ctx, s, K_OTHER, 0);
+                HIPCHK(ctx, launch_mse_grad(a.act[m], cj->target, cj->n, cj->coef, oth, cj->partial, s));
+                p.addend = oth;
+            } else if (in.direct) {
+                p.addend = in.direct;
+            }
             if (in.S && fuse && (h2 ? in.S_amax != nullptr : in.S_bf != nullptr)) {
                 // Gram backward rides on this launch as a second K source: acc += act[m] * S
                 p.in2 = a.act[m]; p.Cin2 = kCout[m]; p.wt2_bf = in.S_bf;
@@ -586,17 +627,11 @@ int backward(nst_ctx* ctx, ActSet& a, const Inject* inj, const ContentJob* cj, f
                 extra_flops = conv_flops(a.h[m], a.w[m], kCout[m], kCout[m], 1);
             } else if (in.S) {
                 ConvParams q{};
-                q.in = a.act[m]; q.wt = in.S; q.out = oth;
+                q.in = a.act[m]; q.wt = in.S; q.out = oth; q.addend = p.addend;
                 q.H = a.h[m]; q.W = a.w[m]; q.Cin = kCout[m]; q.Cout = kCout[m];
                 Timer t(ctx, s, K_GRAM, conv_flops(q.H, q.W, q.Cin, q.Cout, 1));
                 HIPCHK(ctx, launch_conv_mfma(q, 1, s));
                 p.addend = oth;
-            } else if (in.content && cj) {
-                Timer t(ctx, s, K_OTHER, 0);
-                HIPCHK(ctx, launch_mse_grad(a.act[m], cj->target, cj->n, cj->coef, oth, cj->partial, s));
-                p.addend = oth;
-            } else if (in.direct) {
-                p.addend = in.direct;
             }
             if (fuse && a.bits_valid[m]) p.bits_in = a.bits[m];
             else p.mask = a.act[m];
@@ -629,18 +664,18 @@ int gram_of(nst_ctx* ctx, const float* f_nhwc, size_t N, int C, const unsigned* 
     return NST_OK;
 }
 
-// partial-Gram workspace of one image: the five style layers one after the other (the batched launch works on
-// all of them at once); offset of layer k = gram_part_offset(h, w, k), total = gram_part_offset(h, w, 5)
-size_t gram_part_offset(int h, int w, int k) {
+// partial-Gram workspace of one image: the style layers one after the other (the batched launch works on
+// all of them at once); offset of style slot k = gram_part_offset(tp, h, w, k), total = gram_part_offset(tp, h, w, tp.nstyle)
+size_t gram_part_offset(const Taps& tp, int h, int w, int k) {
     size_t off = 0;
     for (int q = 0; q < k; ++q) {
-        const int l = kStyleLayer[q];
+        const int l = tp.style[q];
         const size_t N = (size_t)(h >> kScale[l]) * (w >> kScale[l]);
         off += (size_t)gram_nsplit(kCout[l], N) * kCout[l] * kCout[l];
     }
     return off;
 }
-size_t gram_part_floats_for(int h, int w) { return gram_part_offset(h, w, 5); }
+size_t gram_part_floats_for(const Taps& tp, int h, int w) { return gram_part_offset(tp, h, w, tp.nstyle); }
 
 // ---- closure with every conv layer launched once for all pyramid levels ("batched") ----------------------
 // Layer l has the same weights and channel counts at every level, and layer l of any level depends only on
@@ -670,6 +705,7 @@ constexpr size_t kWinSums = kWinScalarOff + 4;
 int batched_gram(nst_ctx* ctx, const int* lv, int n, float sw, hipStream_t s, unsigned qmask);
 int batched_forward(nst_ctx* ctx, const float* const* xi, const int* lv, int n, hipStream_t s, const Window* win, float fork_sw = -1.f) {
     const bool h2 = ctx->conv_mode == 2;
+    const int top = ctx->taps.top;
     for (int k = 0; k < n; ++k) {
         LevelWs& L = ctx->lv[lv[k]];
         ActSet& a = L.acts;
@@ -685,10 +721,12 @@ int batched_forward(nst_ctx* ctx, const float* const* xi, const int* lv, int n, 
                                        h2 ? amax_act(a, 0) : nullptr, s));
         a.bits_valid[0] = true;
     }
-    for (int l = 1; l < NL; ++l) {
+    for (int l = 1; l <= top; ++l) {
         const int pk = pool_index_after(l - 1), pa = pool_index_after(l);
         ConvBatch b{};
-        b.n = n; b.wt_bf = ctx->wf_bf[l]; b.bias = ctx->bias[l]; b.Cin = kCin[l]; b.Cout = kCout[l]; b.relu = 1;
+        b.n = n; b.wt_bf = ctx->wf_bf[l]; b.bias = ctx->bias[l]; b.Cin = kCin[l]; b.Cout = kCout[l];
+        // conv5_1 before its ReLU (use_relu = 0): the Winograd launch takes its general epilogue (MODE 0), which honours relu = 0
+        b.relu = (l == NL - 1 && !ctx->taps.use_relu) ? 0 : 1;
         b.wt_h2 = ctx->wf_h2[l]; b.wt_h2_inv = ctx->wf_h2_inv[l]; b.mfma16 = ctx->mfma16; b.wg256 = ctx->wg256; b.tile_rows = ctx->tile_rows; b.persist = ctx->persist;
         b.wt_wino = ctx->wf_wino[l]; b.wt_wino_inv = ctx->wf_wino_inv[l];
         double flops = 0;
@@ -725,22 +763,23 @@ int batched_gram(nst_ctx* ctx, const int* lv, int n, float sw, hipStream_t s, un
     const bool h2 = ctx->conv_mode == 2;
     if (h2) {
         // every (level, style layer) pair in two partial launches (one per tile shape) and one finish launch
-        for (int k0 = 0; k0 < n; k0 += 3) {
+        const int per = std::max(1, NST_GRAM_BATCH_MAX / ctx->taps.nstyle);      // levels per launch (3 with five style maps)
+        for (int k0 = 0; k0 < n; k0 += per) {
             GramBatch gb{};
             double flops = 0;
-            for (int k = k0; k < n && k < k0 + 3; ++k) {
+            for (int k = k0; k < n && k < k0 + per; ++k) {
                 LevelWs& L = ctx->lv[lv[k]];
-                for (int q = 0; q < 5; ++q) {
+                for (int q = 0; q < ctx->taps.nstyle; ++q) {
                     if (!((qmask >> q) & 1u)) continue;
-                    const int l = kStyleLayer[q];
+                    const int l = ctx->taps.style[q];
                     const int C = kCout[l];
                     const size_t N = (size_t)L.acts.h[l] * L.acts.w[l];
                     const double chw = (double)C * (double)N;
                     GramItem& it = gb.it[gb.n++];
                     it.f = L.acts.act[l]; it.N = N; it.C = C; it.amax = amax_act(L.acts, l);
-                    it.part = L.gram_part + gram_part_offset(L.h, L.w, q);
+                    it.part = L.gram_part + gram_part_offset(ctx->taps, L.h, L.w, q);
                     it.divisor = (float)chw; it.target = L.gram_t[q];
-                    it.coef = (float)((double)sw * 4.0 / (5.0 * (double)C * C * chw));
+                    it.coef = (float)((double)sw * 4.0 / ((double)ctx->taps.nstyle * (double)C * C * chw));
                     it.gram_out = nullptr; it.S = L.S[q]; it.S_bf = L.S_bf[q]; it.S_amax = amax_S(L.acts, q);
                     it.mse_partial = L.style_partial[q];
                     flops += 2.0 * (double)N * C * C;
@@ -753,12 +792,12 @@ int batched_gram(nst_ctx* ctx, const int* lv, int n, float sw, hipStream_t s, un
     }
     for (int k = 0; k < n && !h2; ++k) {
         LevelWs& L = ctx->lv[lv[k]];
-        for (int q = 0; q < 5; ++q) {
-            const int l = kStyleLayer[q];
+        for (int q = 0; q < ctx->taps.nstyle; ++q) {
+            const int l = ctx->taps.style[q];
             const int C = kCout[l];
             const size_t N = (size_t)L.acts.h[l] * L.acts.w[l];
             const double chw = (double)C * (double)N;
-            const float coef = (float)((double)sw * 4.0 / (5.0 * (double)C * C * chw));
+            const float coef = (float)((double)sw * 4.0 / ((double)ctx->taps.nstyle * (double)C * C * chw));
             NSTCHK(gram_of(ctx, L.acts.act[l], N, C, nullptr, (float)chw, L.gram_part, L.gram_t[q], coef, nullptr, L.S[q],
                            L.S_bf[q], nullptr, L.style_partial[q], s));
         }
@@ -771,10 +810,37 @@ int batched_backward(nst_ctx* ctx, const float* const* xi, float* const* gi, con
     const bool h2 = ctx->conv_mode == 2;
     float* cur[NST_MAX_LEVELS]; float* oth[NST_MAX_LEVELS];
     for (int k = 0; k < n; ++k) { cur[k] = ctx->lv[lv[k]].gbuf[0]; oth[k] = ctx->lv[lv[k]].gbuf[1]; }
-    if (h2) {
-        // top of the chain: g(pre-ReLU of conv5_1) = mask(relu5_1 * S) - the second K source of the fp16 kernel on
-        // its own (no 3x3 part), one launch for all levels; its epilogue applies the ReLU mask and records the absmax
-        const int l = NL - 1;
+    const Taps& tp = ctx->taps;
+    const int top = tp.top;
+    const int top_q = tp.style_slot(top);
+    const bool top_content = tp.content == top;
+    // content gradient of level image k into dst (the content map's own shape), windowed or not
+    auto content_grad = [&](int k, float* dst) -> int {
+        LevelWs& L = ctx->lv[lv[k]];
+        ActSet& a = L.acts;
+        const int m = tp.content;
+        Timer t(ctx, s, K_OTHER, 0);
+        if (win) {
+            // content gradient on the owned rows only (zero elsewhere), normalised by the full image's size
+            const size_t off = (size_t)win_r0(*win, kScale[m]) * a.w[m] * kCout[m];
+            const size_t cnt = (size_t)win_nr(*win, kScale[m]) * a.w[m] * kCout[m];
+            const double n_all = (double)(win->H0 >> kScale[m]) * a.w[m] * kCout[m];
+            HIPCHK(ctx, launch_zero(dst, L.content_n, s));
+            HIPCHK(ctx, launch_mse_grad(a.act[m] + off, L.content_t + off, cnt, (float)((double)cw * 2.0 / n_all),
+                                        dst + off, L.content_partial, s));
+        } else {
+            HIPCHK(ctx, launch_mse_grad(a.act[m], L.content_t, L.content_n,
+                                        (float)((double)cw * 2.0 / (double)L.content_n), dst, L.content_partial, s));
+        }
+        return NST_OK;
+    };
+    if (top_content)
+        for (int k = 0; k < n; ++k) NSTCHK(content_grad(k, oth[k]));
+    if (h2 && top_q >= 0) {
+        // top of the chain: g(pre-ReLU of the top map) = mask(act * S (+ content gradient)) - the second K source of the
+        // fp16 kernel on its own (no 3x3 part), one launch for all levels; its epilogue adds the content gradient (when the
+        // top map is the content map too), applies the ReLU mask (not for the pre-ReLU conv5_1) and records the absmax
+        const int l = top;
         ConvBatch b{};
         b.n = n; b.Cin = 0; b.Cout = kCout[l]; b.Cin2 = kCout[l]; b.relu = 0; b.wt_h2_inv = 1.f; b.mfma16 = ctx->mfma16; b.wg256 = ctx->wg256; b.tile_rows = ctx->tile_rows; b.persist = ctx->persist;
         double flops = 0;
@@ -783,29 +849,39 @@ int batched_backward(nst_ctx* ctx, const float* const* xi, float* const* gi, con
             ActSet& a = L.acts;
             ConvImage& im = b.img[k];
             im.out = cur[k]; im.H = a.h[l]; im.W = a.w[l];
-            im.in2 = a.act[l]; im.wt2_f32 = L.S[4]; im.amax_in2 = amax_act(a, l); im.amax_w2 = amax_S(a, 4);
-            im.bits_in = a.bits[l]; im.amax_out = amax_grad(a, l);
+            im.in2 = a.act[l]; im.wt2_f32 = L.S[top_q]; im.amax_in2 = amax_act(a, l); im.amax_w2 = amax_S(a, top_q);
+            im.bits_in = tp.top_mask() ? a.bits[l] : nullptr; im.amax_out = amax_grad(a, l);
+            im.addend = top_content ? oth[k] : nullptr;
             if (win) { im.in2_row0 = win_r0(*win, kScale[l]); im.in2_rows = win_nr(*win, kScale[l]); }
             flops += conv_flops(im.H, im.W, b.Cin2, b.Cout, 1);
         }
         Timer t(ctx, s, K_GRAM, flops);
         HIPCHK(ctx, launch_conv_h2_batch(b, s));
     }
-    for (int k = 0; k < n && !h2; ++k) {
+    for (int k = 0; k < n && !(h2 && top_q >= 0); ++k) {
         LevelWs& L = ctx->lv[lv[k]];
         ActSet& a = L.acts;
-        const int l = NL - 1;
-        ConvParams p{};
-        p.in = a.act[l]; p.wt = L.S[4]; p.out = cur[k]; p.mask = a.act[l];
-        p.H = a.h[l]; p.W = a.w[l]; p.Cin = kCout[l]; p.Cout = kCout[l];
-        Timer t(ctx, s, K_GRAM, conv_flops(p.H, p.W, p.Cin, p.Cout, 1));
-        HIPCHK(ctx, launch_conv_mfma(p, 1, s));
+        const int l = top;
+        const size_t cnt = (size_t)a.h[l] * a.w[l] * kCout[l];
+        if (top_q >= 0) {
+            ConvParams p{};
+            p.in = a.act[l]; p.wt = L.S[top_q]; p.out = cur[k]; p.mask = tp.top_mask() ? a.act[l] : nullptr;
+            p.addend = top_content ? oth[k] : nullptr;
+            p.H = a.h[l]; p.W = a.w[l]; p.Cin = kCout[l]; p.Cout = kCout[l];
+            Timer t(ctx, s, K_GRAM, conv_flops(p.H, p.W, p.Cin, p.Cout, 1));
+            HIPCHK(ctx, launch_conv_mfma(p, 1, s));
+        } else {
+            // the content map alone at the top: its gradient through the ReLU mask
+            Timer t(ctx, s, K_OTHER, 0);
+            if (tp.top_mask()) HIPCHK(ctx, launch_relu_mask(a.act[l], oth[k], cnt, cur[k], s));
+            else HIPCHK(ctx, launch_copy(oth[k], cur[k], cnt, s));
+        }
+        if (h2) HIPCHK(ctx, launch_absmax_slots(cur[k], cnt, amax_grad(a, l), s));
     }
-    for (int l = NL - 1; l >= 1; --l) {
+    for (int l = top; l >= 1; --l) {
         const int pk = pool_index_after(l - 1);
         const int m = l - 1;
-        int style_q = -1;
-        for (int q = 0; q < 5; ++q) if (kStyleLayer[q] == m) style_q = q;
+        const int style_q = tp.style_slot(m);
         ConvBatch b{};
         b.n = n; b.wt_bf = ctx->wd_bf[l]; b.bias = nullptr; b.Cin = kCout[l]; b.Cout = kCin[l]; b.relu = 0;
         b.wt_h2 = ctx->wd_h2[l]; b.wt_h2_inv = ctx->wd_h2_inv[l]; b.mfma16 = ctx->mfma16; b.wg256 = ctx->wg256; b.tile_rows = ctx->tile_rows; b.persist = ctx->persist;
@@ -825,25 +901,16 @@ int batched_backward(nst_ctx* ctx, const float* const* xi, float* const* gi, con
             im.amax_in = amax_grad(a, l); im.amax_out = amax_grad(a, l - 1);
             flops += conv_flops(im.H, im.W, b.Cin, b.Cout, 9);
             if (pk >= 0) continue;
+            // a map that is both a style and the content map: the Gram term as the second K source AND the content
+            // gradient as the addend of the same launch
             if (style_q >= 0) {
                 im.in2 = a.act[m]; im.wt2_bf = L.S_bf[style_q];
                 im.wt2_f32 = L.S[style_q]; im.amax_in2 = amax_act(a, m); im.amax_w2 = amax_S(a, style_q);
                 if (win) { im.in2_row0 = win_r0(*win, kScale[m]); im.in2_rows = win_nr(*win, kScale[m]); }
                 flops += conv_flops(a.h[m], a.w[m], kCout[m], kCout[m], 1);
-            } else if (m == kContentLayer) {
-                Timer t(ctx, s, K_OTHER, 0);
-                if (win) {
-                    // content gradient on the owned rows only (zero elsewhere), normalised by the full image's size
-                    const size_t off = (size_t)win_r0(*win, kScale[m]) * a.w[m] * kCout[m];
-                    const size_t cnt = (size_t)win_nr(*win, kScale[m]) * a.w[m] * kCout[m];
-                    const double n_all = (double)(win->H0 >> kScale[m]) * a.w[m] * kCout[m];
-                    HIPCHK(ctx, launch_zero(oth[k], L.content_n, s));
-                    HIPCHK(ctx, launch_mse_grad(a.act[m] + off, L.content_t + off, cnt, (float)((double)cw * 2.0 / n_all),
-                                                oth[k] + off, L.content_partial, s));
-                } else {
-                    HIPCHK(ctx, launch_mse_grad(a.act[m], L.content_t, L.content_n,
-                                                (float)((double)cw * 2.0 / (double)L.content_n), oth[k], L.content_partial, s));
-                }
+            }
+            if (m == tp.content) {
+                NSTCHK(content_grad(k, oth[k]));
                 im.addend = oth[k];
             }
             im.bits_in = a.bits[m];
@@ -889,18 +956,49 @@ int closure_batched(nst_ctx* ctx, const float* const* xi, float* const* gi, unsi
     }
     if (n == 0) return NST_OK;
     // (not while a hipGraph is being captured or replayed: the closure then stays on one stream)
-    const bool overlap = ctx->gram_overlap && ctx->conv_mode == 2 && !ctx->use_graph && ctx->side != nullptr;
+    // (the overlap's split of the style maps - relu1_1 .. relu3_1 on the side stream - is the default taps')
+    const bool overlap = ctx->gram_overlap && ctx->conv_mode == 2 && !ctx->use_graph && ctx->side != nullptr && ctx->taps.is_default;
     NSTCHK(batched_forward(ctx, xi, lv, n, s, nullptr, overlap ? sw : -1.f));
-    NSTCHK(batched_gram(ctx, lv, n, sw, s, overlap ? 0x18u : 0x1Fu));
+    NSTCHK(batched_gram(ctx, lv, n, sw, s, overlap ? 0x18u : (1u << ctx->taps.nstyle) - 1u));
     if (overlap) HIPCHK(ctx, hipStreamWaitEvent(s, ctx->side_join, 0));
     return batched_backward(ctx, xi, gi, lv, n, cw, tvw, s, nullptr, nullptr, 0, 0);
 }
 
+// the buffers whose size depends on the taps: content target, Gram targets / factors / partial sums, partial-Gram workspace
+void free_tap_buffers(nst_ctx* ctx, LevelWs& L) {
+    auto drop = [&](void* p, size_t bytes) { if (p) { dev_free(p); if (ctx->bytes >= bytes) ctx->bytes -= bytes; } };
+    drop(L.content_t, L.content_n * 4); L.content_t = nullptr; L.content_n = 0;
+    for (int k = 0; k < kMaxStyle; ++k) {
+        const size_t C = (size_t)L.tap_c[k];
+        drop(L.gram_t[k], C * C * 4); drop(L.S[k], C * C * 4); drop(L.S_bf[k], C * C * 6);
+        drop(L.style_partial[k], (size_t)gram_finish_blocks((int)std::max<size_t>(C, 1)) * 8);
+        L.gram_t[k] = nullptr; L.S[k] = nullptr; L.S_bf[k] = nullptr; L.style_partial[k] = nullptr; L.tap_c[k] = 0;
+    }
+    drop(L.gram_part, L.gram_part_floats * 4); L.gram_part = nullptr; L.gram_part_floats = 0;
+}
+int alloc_tap_buffers(nst_ctx* ctx, LevelWs& L) {
+    const Taps& tp = ctx->taps;
+    const int m = tp.content;
+    L.content_n = (size_t)L.acts.h[m] * L.acts.w[m] * kCout[m];
+    NSTCHK(dev_alloc_t(ctx, &L.content_t, L.content_n));
+    for (int k = 0; k < tp.nstyle; ++k) {
+        const int C = kCout[tp.style[k]];
+        L.tap_c[k] = C;
+        NSTCHK(dev_alloc_t(ctx, &L.gram_t[k], (size_t)C * C));
+        NSTCHK(dev_alloc_t(ctx, &L.S[k], (size_t)C * C));
+        NSTCHK(dev_alloc_t(ctx, &L.S_bf[k], (size_t)C * C * 3));
+        NSTCHK(dev_alloc_t(ctx, &L.style_partial[k], gram_finish_blocks(C)));
+    }
+    L.gram_part_floats = gram_part_floats_for(tp, L.h, L.w);
+    NSTCHK(dev_alloc_t(ctx, &L.gram_part, L.gram_part_floats));
+    return NST_OK;
+}
+
 void free_level(nst_ctx* ctx, LevelWs& L) {
     free_acts(ctx, L.acts);
-    dev_free(L.gbuf[0]); dev_free(L.gbuf[1]); dev_free(L.xl); dev_free(L.gxl); dev_free(L.content_t);
-    for (int k = 0; k < 5; ++k) { dev_free(L.gram_t[k]); dev_free(L.S[k]); dev_free(L.S_bf[k]); dev_free(L.style_partial[k]); }
-    dev_free(L.gram_part); dev_free(L.content_partial); dev_free(L.tv_partial); dev_free(L.tv_means);
+    dev_free(L.gbuf[0]); dev_free(L.gbuf[1]); dev_free(L.xl); dev_free(L.gxl);
+    free_tap_buffers(ctx, L);
+    dev_free(L.content_partial); dev_free(L.tv_partial); dev_free(L.tv_means);
     if (L.stream) (void)hipStreamDestroy(L.stream);
     if (L.done) (void)hipEventDestroy(L.done);
     L = LevelWs();
@@ -1188,23 +1286,43 @@ int nst_job_configure(nst_ctx* ctx, int levels_num, int H0, int W0) {
             NSTCHK(dev_alloc_t(ctx, &L.xl, (size_t)3 * h * w));
             NSTCHK(dev_alloc_t(ctx, &L.gxl, (size_t)3 * h * w));
         }
-        L.content_n = (size_t)L.acts.h[kContentLayer] * L.acts.w[kContentLayer] * kCout[kContentLayer];
-        NSTCHK(dev_alloc_t(ctx, &L.content_t, L.content_n));
-        for (int k = 0; k < 5; ++k) {
-            const int C = kCout[kStyleLayer[k]];
-            NSTCHK(dev_alloc_t(ctx, &L.gram_t[k], (size_t)C * C));
-            NSTCHK(dev_alloc_t(ctx, &L.S[k], (size_t)C * C));
-            NSTCHK(dev_alloc_t(ctx, &L.S_bf[k], (size_t)C * C * 3));
-            NSTCHK(dev_alloc_t(ctx, &L.style_partial[k], gram_finish_blocks(C)));
-        }
-        L.gram_part_floats = gram_part_floats_for(h, w);
-        NSTCHK(dev_alloc_t(ctx, &L.gram_part, L.gram_part_floats));
+        NSTCHK(alloc_tap_buffers(ctx, L));       // sized for the context's current taps
         NSTCHK(dev_alloc_t(ctx, &L.content_partial, MSE_BLOCKS));
         NSTCHK(dev_alloc_t(ctx, &L.tv_partial, 2 * TV_BLOCKS));
         NSTCHK(dev_alloc_t(ctx, &L.tv_means, 2));
         h /= 2; w /= 2;
     }
     ctx->levels = levels_num;
+    return NST_OK;
+}
+
+// LossBuilder(content_feature_maps_index, style_feature_maps_indices, ...) and Vgg19(use_relu=...) of the reference
+// (neural_style_transfer.py:41-82, neural_nets.py:17-28) as a context setting
+int nst_job_set_taps(nst_ctx* ctx, int content_index, unsigned style_mask, int use_relu) {
+    NSTCHK(bind(ctx));
+    if (content_index < 0 || content_index > 5) return fail(ctx, NST_E_ARG, "content_index must be 0 .. 5");
+    if (style_mask == 0u || (style_mask & ~0x3Fu) != 0u)
+        return fail(ctx, NST_E_ARG, "style_mask must be a non-empty set of bits 0 .. 5");
+    if (use_relu != 0 && use_relu != 1) return fail(ctx, NST_E_ARG, "use_relu must be 0 or 1");
+    Taps tp;
+    tp.content = kTapLayer[content_index];
+    tp.nstyle = 0;
+    for (int i = 0; i < 6; ++i)
+        if ((style_mask >> i) & 1u) tp.style[tp.nstyle++] = kTapLayer[i];      // (ascending: kTapLayer increases)
+    tp.top = std::max(tp.content, tp.style[tp.nstyle - 1]);
+    tp.use_relu = use_relu;
+    tp.is_default = content_index == 4 && style_mask == 0x2Fu && use_relu == 1;
+    // every level's targets and the captured closure belong to the old taps; the tap-sized buffers are re-allocated
+    quiesce(ctx);
+    if (ctx->gexec) { (void)hipGraphExecDestroy(ctx->gexec); ctx->gexec = nullptr; }
+    ctx->gkey = {}; ctx->glast = {};
+    ctx->taps = tp;
+    for (int i = 0; i < ctx->levels; ++i) {
+        LevelWs& L = ctx->lv[i];
+        L.targets = false;
+        free_tap_buffers(ctx, L);
+        NSTCHK(alloc_tap_buffers(ctx, L));
+    }
     return NST_OK;
 }
 
@@ -1217,7 +1335,8 @@ int nst_level_set_targets(nst_ctx* ctx, int level, const float* content, const f
     if (hs < 16 || ws < 16) return fail(ctx, NST_E_ARG, "style image must be at least 16x16");
     hipStream_t s = enter(ctx, stream);
     LevelWs& L = ctx->lv[level];
-    // content: ReLU(conv4_2) of the content image, through the level's own activation buffers - by the launches the closure
+    const Taps& tp = ctx->taps;
+    // content: the content map (default ReLU(conv4_2)) of the content image, through the level's own activation buffers - by the launches the closure
     // of this job will use (one launch per layer, Winograd F(2,3) where it applies), so that target and current features
     // carry the same rounding: an image that IS the content image then has a content loss of (all but) exactly zero, as in
     // the reference, whose target and current features come from one and the same forward code
@@ -1227,17 +1346,17 @@ int nst_level_set_targets(nst_ctx* ctx, int level, const float* content, const f
         const int lv1 = level;
         NSTCHK(batched_forward(ctx, xi, &lv1, 1, s, nullptr));
     } else {
-        NSTCHK(forward(ctx, L.acts, content, L.h, L.w, s, kContentLayer));
+        NSTCHK(forward(ctx, L.acts, content, L.h, L.w, s, tp.content));
     }
-    HIPCHK(ctx, hipMemcpyAsync(L.content_t, L.acts.act[kContentLayer], L.content_n * 4, hipMemcpyDeviceToDevice, s));
-    // style: 5 Gram matrices of the style image (its own size)
+    HIPCHK(ctx, hipMemcpyAsync(L.content_t, L.acts.act[tp.content], L.content_n * 4, hipMemcpyDeviceToDevice, s));
+    // style: the Gram matrices of the style image (its own size)
     ActSet sa;
     int r = alloc_acts(ctx, sa, hs, ws);
     float* part = nullptr;
-    if (r == NST_OK) r = dev_alloc_t(ctx, &part, gram_part_floats_for(hs, ws));
-    if (r == NST_OK) r = forward(ctx, sa, style, hs, ws, s);
-    for (int k = 0; k < 5 && r == NST_OK; ++k) {
-        const int l = kStyleLayer[k];
+    if (r == NST_OK) r = dev_alloc_t(ctx, &part, gram_part_floats_for(tp, hs, ws));
+    if (r == NST_OK) r = forward(ctx, sa, style, hs, ws, s, tp.style[tp.nstyle - 1]);
+    for (int k = 0; k < tp.nstyle && r == NST_OK; ++k) {
+        const int l = tp.style[k];
         const int C = kCout[l];
         const size_t N = (size_t)sa.h[l] * sa.w[l];
         r = gram_of(ctx, sa.act[l], N, C, ctx->conv_mode == 2 ? amax_act(sa, l) : nullptr, (float)((double)C * sa.h[l] * sa.w[l]), part, nullptr, 0.f, L.gram_t[k],
@@ -1381,24 +1500,25 @@ static int closure_record(nst_ctx* ctx, const float* x, float cw, float sw, floa
             Timer t(ctx, s, K_OTHER, 0);
             HIPCHK(ctx, launch_tv_partial(xi[i], 3, L.h, L.w, L.tv_partial, s));
         }
-        NSTCHK(forward(ctx, L.acts, xi[i], L.h, L.w, s));
+        const Taps& tp = ctx->taps;
+        NSTCHK(forward(ctx, L.acts, xi[i], L.h, L.w, s, tp.top));
         Inject inj[NL];
-        for (int k = 0; k < 5; ++k) {
-            const int l = kStyleLayer[k];
+        for (int k = 0; k < tp.nstyle; ++k) {
+            const int l = tp.style[k];
             const int C = kCout[l];
             const size_t N = (size_t)L.acts.h[l] * L.acts.w[l];
             const double chw = (double)C * (double)N;
-            // style = mean_k mse(G_k, Gt_k); dL/dG = sw/5 * 2 (G-Gt)/C^2; dF = 2 * dL/dG * F / (C h w)
-            const float coef = (float)((double)sw * 4.0 / (5.0 * (double)C * C * chw));
+            // style = mean_k mse(G_k, Gt_k); dL/dG = sw/nstyle * 2 (G-Gt)/C^2; dF = 2 * dL/dG * F / (C h w)
+            const float coef = (float)((double)sw * 4.0 / ((double)tp.nstyle * (double)C * C * chw));
             NSTCHK(gram_of(ctx, L.acts.act[l], N, C, ctx->conv_mode == 2 ? amax_act(L.acts, l) : nullptr, (float)chw, L.gram_part, L.gram_t[k], coef, nullptr, L.S[k],
                            L.S_bf[k], ctx->conv_mode == 2 ? amax_S(L.acts, k) : nullptr, L.style_partial[k], s));
             inj[l].S = L.S[k];
             inj[l].S_bf = L.S_bf[k];
             inj[l].S_amax = ctx->conv_mode == 2 ? amax_S(L.acts, k) : nullptr;
         }
-        inj[kContentLayer].content = true;
+        inj[tp.content].content = true;
         ContentJob cj{L.content_t, L.content_n, (float)((double)cw * 2.0 / (double)L.content_n), L.content_partial};
-        NSTCHK(backward(ctx, L.acts, inj, &cj, L.gbuf[0], L.gbuf[1], gi[i], L.h, L.w, s));
+        NSTCHK(backward(ctx, L.acts, inj, &cj, L.gbuf[0], L.gbuf[1], gi[i], L.h, L.w, s, tp.top, tp.top_mask()));
         {
             Timer t(ctx, s, K_OTHER, 0);
             HIPCHK(ctx, launch_tv_finish(xi[i], 3, L.h, L.w, L.tv_partial, tvw, gi[i], 1, L.tv_means, s));
@@ -1415,12 +1535,12 @@ static int closure_record(nst_ctx* ctx, const float* x, float cw, float sw, floa
                                             gi[i - 1], 1, main));
     }
     LossAssembly la{};
-    la.levels = ctx->levels; la.cw = cw; la.sw = sw; la.tvw = tvw; la.out = losses;
+    la.levels = ctx->levels; la.nstyle = ctx->taps.nstyle; la.cw = cw; la.sw = sw; la.tvw = tvw; la.out = losses;
     for (int i = 0; i < ctx->levels; ++i) {
         LevelWs& L = ctx->lv[i];
         la.lv[i].content_partial = L.content_partial;
         la.lv[i].content_n = L.content_n;
-        for (int k = 0; k < 5; ++k) { la.lv[i].style_partial[k] = L.style_partial[k]; la.lv[i].style_c[k] = kCout[kStyleLayer[k]]; }
+        for (int k = 0; k < ctx->taps.nstyle; ++k) { la.lv[i].style_partial[k] = L.style_partial[k]; la.lv[i].style_c[k] = kCout[ctx->taps.style[k]]; }
         la.lv[i].tv_means = L.tv_means;
         la.lv[i].owned = (int)((level_mask >> i) & 1u);
     }
@@ -1438,6 +1558,8 @@ int nst_window_sums_count(size_t* count) {
 static int window_check(nst_ctx* ctx, const float* xs, int row0, int rows, int H0) {
     if (ctx->levels != 1) return fail(ctx, NST_E_STATE, "a stripe context is configured with levels_num = 1");
     if (ctx->conv_mode != 2) return fail(ctx, NST_E_STATE, "the stripe closure runs on the f16x2 convolutions (NST_CONV unset)");
+    if (!ctx->taps.is_default)
+        return fail(ctx, NST_E_STATE, "the stripe closure implements the default feature maps only (nst_job_set_taps(ctx, 4, 0x2F, 1))");
     LevelWs& L = ctx->lv[0];
     if (!L.targets) return fail(ctx, NST_E_STATE, "targets of the stripe not set");
     if (!xs) return fail(ctx, NST_E_ARG, "null buffer");
@@ -1463,7 +1585,7 @@ int nst_window_begin(nst_ctx* ctx, const float* xs, int row0, int rows, int H0, 
     NSTCHK(batched_forward(ctx, xi, lv, 1, s, &win));
     // un-normalised Gram sums of the owned rows
     for (int q = 0; q < 5; ++q) {
-        const int l = kStyleLayer[q], C = kCout[l];
+        const int l = ctx->taps.style[q], C = kCout[l];
         const size_t off = (size_t)win_r0(win, kScale[l]) * a.w[l] * C;
         const size_t N = (size_t)win_nr(win, kScale[l]) * a.w[l];
         const int ns = gram_nsplit(C, N);
@@ -1473,7 +1595,7 @@ int nst_window_begin(nst_ctx* ctx, const float* xs, int row0, int rows, int H0, 
     }
     // content: sum of squared differences over the owned rows
     {
-        const int m = kContentLayer;
+        const int m = ctx->taps.content;
         const size_t off = (size_t)win_r0(win, kScale[m]) * a.w[m] * kCout[m];
         const size_t cnt = (size_t)win_nr(win, kScale[m]) * a.w[m] * kCout[m];
         HIPCHK(ctx, launch_mse_grad(a.act[m] + off, L.content_t + off, cnt, 0.f, nullptr, L.content_partial, s));
@@ -1497,7 +1619,7 @@ int nst_window_end(nst_ctx* ctx, const float* xs, int row0, int rows, int H0, fl
     Window win{row0, rows, H0, sums};
     // S = d loss / d G from the Gram sums of ALL stripes, normalised by the full image
     for (int q = 0; q < 5; ++q) {
-        const int l = kStyleLayer[q], C = kCout[l];
+        const int l = ctx->taps.style[q], C = kCout[l];
         const double chw = (double)C * (double)(H0 >> kScale[l]) * a.w[l];
         const float coef = (float)((double)sw * 4.0 / (5.0 * (double)C * C * chw));
         HIPCHK(ctx, launch_gram_finish(sums + kWinGramOff[q], 1, C, (float)chw, L.gram_t[q], coef, nullptr, L.S[q], L.S_bf[q],
@@ -1512,10 +1634,11 @@ int nst_window_end(nst_ctx* ctx, const float* xs, int row0, int rows, int H0, fl
     // the level's loss row from the global sums (the backward's content pass left this stripe's partials behind)
     HIPCHK(ctx, launch_window_scalars(sums + kWinScalarOff, nx, ny, L.tv_means, L.content_partial, MSE_BLOCKS, s));
     LossAssembly la{};
-    la.levels = 1; la.cw = cw; la.sw = sw; la.tvw = tvw; la.out = losses;
+    la.levels = 1; la.nstyle = 5; la.cw = cw; la.sw = sw; la.tvw = tvw; la.out = losses;
     la.lv[0].content_partial = L.content_partial;
-    la.lv[0].content_n = (size_t)(H0 >> kScale[kContentLayer]) * a.w[kContentLayer] * kCout[kContentLayer];
-    for (int k = 0; k < 5; ++k) { la.lv[0].style_partial[k] = L.style_partial[k]; la.lv[0].style_c[k] = kCout[kStyleLayer[k]]; }
+    const int m = ctx->taps.content;
+    la.lv[0].content_n = (size_t)(H0 >> kScale[m]) * a.w[m] * kCout[m];
+    for (int k = 0; k < 5; ++k) { la.lv[0].style_partial[k] = L.style_partial[k]; la.lv[0].style_c[k] = kCout[ctx->taps.style[k]]; }
     la.lv[0].tv_means = L.tv_means;
     la.lv[0].owned = 1;
     HIPCHK(ctx, launch_loss_assemble(la, s));
@@ -1671,7 +1794,7 @@ int nst_vgg_features_backward(nst_ctx* ctx, const float* x, int h, int w, const 
             r = fail(ctx, NST_E_HIP, "chw_to_hwc launch failed");
         inj[l].direct = inj_buf[i];
     }
-    if (r == NST_OK) r = backward(ctx, a, inj, nullptr, g0, g1, gx, h, w, s);
+    if (r == NST_OK) r = backward(ctx, a, inj, nullptr, g0, g1, gx, h, w, s, NL - 1, ctx->taps.use_relu != 0);
     hipError_t e = hipStreamSynchronize(s);
     free_acts(ctx, a);
     dev_free(g0); dev_free(g1);

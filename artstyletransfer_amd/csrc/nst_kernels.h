@@ -186,14 +186,15 @@ hipError_t launch_unprepare_img(const float* chw, int h, int w, float* hwc, hipS
 struct LevelLossInputs {
     const double* content_partial;   // MSE_BLOCKS doubles
     size_t content_n;
-    const double* style_partial[5];  // gram_finish_blocks(C) doubles each: partial sums of (G-Gt)^2
-    int style_c[5];                  // C of each style layer (mse mean over C*C)
+    const double* style_partial[6];  // gram_finish_blocks(C) doubles each: partial sums of (G-Gt)^2
+    int style_c[6];                  // C of each style layer (mse mean over C*C)
     const float* tv_means;           // 2 floats (mean_x, mean_y)
     int owned;                       // 0: level computed by another rank, its row is written as zeros
 };
 struct LossAssembly {
     LevelLossInputs lv[8];
     int levels;
+    int nstyle;                      // style layers in use (1..6): the style term is the mean over them
     float cw, sw, tvw;
     float* out;                      // 4*levels + 1
 };

@@ -504,21 +504,22 @@ hipError_t launch_unprepare_img(const float* chw, int h, int w, float* hwc, hipS
 }
 
 // ------------------------------------------------------------------ loss rows (neural_style_transfer.py:95-110, :179-185)
-// one workgroup per level: the six sums of a level (content + 5 style) go through ONE pair of barriers (each sum
+// one workgroup per level: the sums of a level (content + up to 6 style) go through ONE pair of barriers (each sum
 // keeps its own fixed order: strided per-thread share in index order, wave tree, waves in order)
 __global__ __launch_bounds__(256) void loss_rows_kernel(LossAssembly la) {
 #pragma clang fp contract(off)
-    __shared__ double sh[6][4];
+    __shared__ double sh[7][4];
     const int l = blockIdx.x;
     const LevelLossInputs& in = la.lv[l];
     if (!in.owned) {
         if (threadIdx.x < 4) la.out[4 * l + threadIdx.x] = 0.f;
         return;
     }
-    double v[6];
+    double v[7];
     v[0] = threadIdx.x < MSE_BLOCKS ? in.content_partial[threadIdx.x] : 0.0;
 #pragma unroll
-    for (int k = 0; k < 5; ++k) {
+    for (int k = 0; k < 6; ++k) {
+        if (k >= la.nstyle) { v[k + 1] = 0.0; continue; }
         // C*C / NST_GRAM_FINISH_EPB partials: each thread adds its strided share in index order, then the fixed tree
         const int nb = (in.style_c[k] * in.style_c[k] + NST_GRAM_FINISH_EPB - 1) / NST_GRAM_FINISH_EPB;
         double p[8];
@@ -535,19 +536,19 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(LossAssembly la) {
     }
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
-    for (int q = 0; q < 6; ++q) {
+    for (int q = 0; q < 7; ++q) {
         double x = v[q];
         for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
         if (lane == 0) sh[q][w] = x;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        double r[6];
-        for (int q = 0; q < 6; ++q) { r[q] = 0.0; for (int i = 0; i < 4; ++i) r[q] += sh[q][i]; }
+        double r[7];
+        for (int q = 0; q < 7; ++q) { r[q] = 0.0; for (int i = 0; i < 4; ++i) r[q] += sh[q][i]; }
         const float content = (float)(r[0] / (double)in.content_n);
         float style = 0.f;
-        for (int k = 0; k < 5; ++k) style = style + (float)(r[k + 1] / ((double)in.style_c[k] * in.style_c[k]));
-        style = style / 5.f;
+        for (int k = 0; k < la.nstyle; ++k) style = style + (float)(r[k + 1] / ((double)in.style_c[k] * in.style_c[k]));
+        style = style / (float)la.nstyle;
         const float mx = in.tv_means[0], my = in.tv_means[1];
         const float tv = mx * mx + my * my;
         // cw*content + sw*style + tvw*tv, each product and sum rounded (contraction is off here)

@@ -9,10 +9,12 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import taps as _taps
 from ._lib import NST_LOSS_ROW, NstError, StepInfo
 
 TAP_CHANNELS = (64, 128, 256, 512, 512, 512)
 TAP_SCALE = (0, 1, 2, 3, 3, 4)
+DEFAULT_TAPS = (_taps.DEFAULT_CONTENT_INDEX, _taps.DEFAULT_STYLE_INDICES, True)
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -76,6 +78,7 @@ class StyleEngine:
         self.weights_id = id(weights)          # which weight set this context carries (neural_nets' engine pool)
         self.levels = 0
         self.shape = None
+        self.taps = DEFAULT_TAPS                 # (content index, style indices, use_relu): set_taps
 
     def close(self):
         if getattr(self, "ctx", None):
@@ -93,6 +96,20 @@ class StyleEngine:
         _lib.check(self.ctx, self.lib.nst_job_configure(self.ctx, levels_num, H0, W0), "nst_job_configure")
         self.levels = levels_num
         self.shape = (H0, W0)
+
+    def set_taps(self, content_index, style_indices, use_relu: bool = True) -> None:
+        """The feature maps the losses read (nst_job_set_taps): a content index and style indices of Vgg19.layer_names
+        (0..5, or names of the `use_relu` flavour; order and repeats of the style list do not matter).  Drops the
+        targets of every configured level: call set_targets again.  ValueError for an invalid choice."""
+        content, style = _taps.normalize_taps(content_index, style_indices, use_relu)
+        _lib.check(self.ctx, self.lib.nst_job_set_taps(self.ctx, content, _taps.style_mask(style), int(use_relu)),
+                   "nst_job_set_taps")
+        self.taps = (content, style, bool(use_relu))
+
+    def reset_taps(self) -> None:
+        """Back to the reference's taps (content 4, style 0, 1, 2, 3, 5, post-ReLU), if they were changed."""
+        if self.taps != DEFAULT_TAPS:
+            self.set_taps(*DEFAULT_TAPS)
 
     def release_job(self) -> None:
         """Give the job's pyramid workspace back (4.7 GB at L=2) and keep the context with its uploaded weights: what an

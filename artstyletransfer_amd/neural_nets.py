@@ -22,8 +22,10 @@ import torch
 
 from . import synthetic
 from .engine import StyleEngine
+from .taps import DEFAULT_CONTENT_INDEX, DEFAULT_STYLE_INDICES, LAYER_NAMES
 
 _FEATURE_CONV_INDICES = (0, 2, 5, 7, 10, 12, 14, 16, 19, 21, 23, 25, 28)   # torchvision vgg19.features
+
 _weights_cache = None
 _engines: Dict[int, StyleEngine] = {}
 _lock = threading.Lock()
@@ -112,6 +114,7 @@ def lease_engine(device) -> StyleEngine:
 
 
 def return_engine(eng: StyleEngine) -> None:
+    """Back to the per-GPU pool, with the default taps: the next job must not inherit this one's."""
     if getattr(eng, "ctx", None) is None:
         return
     idx = eng.device.index
@@ -121,6 +124,7 @@ def return_engine(eng: StyleEngine) -> None:
     if keep:
         try:
             eng.release_job()                  # the workspace goes back now, only the weights stay resident
+            eng.reset_taps()
         except Exception:
             keep = False
     if keep:
@@ -143,15 +147,15 @@ def shared_engine(device) -> StyleEngine:
 class Vgg19:
     """Only the layers the original NST paper uses are exposed (relu1_1, relu2_1, relu3_1, relu4_1,
     conv4_2, relu5_1); 'conv4_2' carries ReLU(conv4_2) exactly as the reference's in-place ReLU
-    leaves it."""
+    leaves it.  use_relu=False names them conv1_1 ... conv5_1 as the reference does; torchvision's
+    in-place ReLUs still leave maps 0..4 post-ReLU there, and only map 5 is conv5_1 BEFORE its ReLU."""
 
     def __init__(self, requires_grad=False, show_progress=False, use_relu=True):
         if requires_grad:
             raise NotImplementedError("the feature network is frozen; only the image is optimised")
-        if not use_relu:
-            raise NotImplementedError("use_relu=False (pre-activation taps) is not on the reference's path")
-        self.layer_names = ["relu1_1", "relu2_1", "relu3_1", "relu4_1", "conv4_2", "relu5_1"]
-        self.offset = 1
+        self.use_relu = bool(use_relu)
+        self.layer_names = list(LAYER_NAMES[self.use_relu])
+        self.offset = 1 if self.use_relu else 0
         self.content_feature_maps_index = 4
         self.style_feature_maps_indices = [0, 1, 2, 3, 5]
         self.weights = load_weights()
@@ -170,8 +174,16 @@ class Vgg19:
             yield b
 
     def forward(self, x: torch.Tensor):
-        eng = shared_engine(x.device)
-        outs = eng.vgg_features(x.contiguous())
+        if self.use_relu:
+            outs = shared_engine(x.device).vgg_features(x.contiguous())
+        else:
+            # the pre-ReLU conv5_1 is a setting of the context: a pooled one, handed back with the default taps
+            eng = lease_engine(x.device)
+            try:
+                eng.set_taps(DEFAULT_CONTENT_INDEX, DEFAULT_STYLE_INDICES, use_relu=False)
+                outs = eng.vgg_features(x.contiguous())
+            finally:
+                return_engine(eng)
         return namedtuple("VggOutputs", self.layer_names)(*outs)
 
     __call__ = forward

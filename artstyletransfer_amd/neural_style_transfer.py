@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import device_image, host_image, math_utils
+from . import taps as _taps
 from .engine import PixelOptimizer, StyleEngine
 from .neural_nets import lease_engine, return_engine, shared_engine
 
@@ -78,14 +79,17 @@ class LossBuilder:
 
     def __init__(self, content_feature_maps_index, style_feature_maps_indices, target_content_image,
                  target_style_image, neural_net, content_weight, style_weight, tv_weight):
-        if content_feature_maps_index != 4 or list(style_feature_maps_indices) != [0, 1, 2, 3, 5]:
-            raise ValueError("the HIP closure implements the reference's VGG19 taps (content 4, style [0,1,2,3,5])")
+        # any taps of the reference's six maps (ValueError where the reference would fail or silently ignore an index:
+        # taps.normalize_taps); the flavour (use_relu) is the network's
+        use_relu = bool(getattr(neural_net, "use_relu", True))
+        taps = _taps.normalize_taps(content_feature_maps_index, style_feature_maps_indices, use_relu)
         self.__weights = (float(content_weight), float(style_weight), float(tv_weight))
         c = target_content_image
         # a context from the per-GPU pool (the weights are uploaded once, not per LossBuilder); it goes back when this
         # object is collected
         self.__engine = lease_engine(c.device)
         self.__engine.configure(1, c.shape[-2], c.shape[-1])
+        self.__engine.set_taps(*taps, use_relu=use_relu)
         self.__engine.set_targets(0, c.contiguous(), target_style_image.contiguous())
 
     def __del__(self):
@@ -107,7 +111,7 @@ class _DeviceJob:
     otherwise plain asyncio, so the hand-over and tear-down ordering can be tested with a fake in its place
     (`_make_job`, tests/test_host_api.py)."""
 
-    def __init__(self, device, optimizer_name, style_imgs, content_imgs, init_img, lr_start):
+    def __init__(self, device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, taps=None):
         self.dev = dev = device
         self.optimizer = None
         self.engine = lease_engine(dev)
@@ -130,6 +134,8 @@ class _DeviceJob:
 
             with torch.cuda.stream(self.job_stream):
                 engine.configure(len(content_imgs), h0, w0)
+                if taps is not None:                # (content index, style indices, use_relu), normalised
+                    engine.set_taps(*taps)
                 for lvl, (c_img, s_img) in enumerate(zip(content_imgs, style_imgs)):
                     if tuple(c_img.shape[:2]) != engine.level_shape(lvl):
                         raise ValueError(f"content level {lvl} is {tuple(c_img.shape[:2])}, expected {engine.level_shape(lvl)}")
@@ -179,8 +185,8 @@ class _DeviceJob:
         return_engine(self.engine)             # back to the per-GPU pool: the next job re-uses its uploaded weights
 
 
-def _make_job(device, optimizer_name, style_imgs, content_imgs, init_img, lr_start):
-    return _DeviceJob(device, optimizer_name, style_imgs, content_imgs, init_img, lr_start)
+def _make_job(device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, taps=None):
+    return _DeviceJob(device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, taps)
 
 
 async def _drain(step_future):
@@ -211,6 +217,15 @@ class NeuralStyleTransfer:
         self.__model_name = model_name
         self.__style_imgs = style_imgs
         self.__optimizer_name = optimizer_name
+        self.__taps = None                       # None: the reference's feature maps
+
+    def set_feature_maps(self, content_layer=None, style_layers=None, use_relu=True):
+        """Extension: the feature maps the losses of the next `process` read - a content map and a set of style maps of
+        Vgg19.layer_names, as indices 0..5 or names of the `use_relu` flavour (None: the reference's content 4, style
+        [0, 1, 2, 3, 5]).  ValueError for an empty style set, an index out of range or a content map that is not one
+        index or name."""
+        content, style = _taps.normalize_taps(content_layer, style_layers, use_relu)
+        self.__taps = None if _taps.is_default(content, style, use_relu) else (content, style, use_relu)
 
     async def process(self, content_imgs, init_img, lr_start, iters_num, content_weight, style_weight, tv_weight,
                       init_img_name):
@@ -220,7 +235,11 @@ class NeuralStyleTransfer:
             raise RuntimeError("Unknown optimizer")
         if self.__device.type != "cuda":
             raise RuntimeError("the HIP style-transfer engine needs a GPU; no CPU path exists")
-        job = _make_job(self.__device, self.__optimizer_name, self.__style_imgs, content_imgs, init_img, lr_start)
+        if self.__taps is None:
+            job = _make_job(self.__device, self.__optimizer_name, self.__style_imgs, content_imgs, init_img, lr_start)
+        else:
+            job = _make_job(self.__device, self.__optimizer_name, self.__style_imgs, content_imgs, init_img, lr_start,
+                            taps=self.__taps)
         cw, sw, tvw = float(content_weight), float(style_weight), float(tv_weight)
         loop = asyncio.get_running_loop()
 
@@ -274,9 +293,13 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
                                 content_weight, style_weight, tv_weight,
                                 optimizer, model, init_method,
                                 iters_num, levels_num, noise_factor, noise_levels, noise_levels_central_amplitude,
-                                noise_levels_peripheral_amplitude, noise_levels_dispersion, device=None):
+                                noise_levels_peripheral_amplitude, noise_levels_dispersion, device=None, *,
+                                content_layer=None, style_layers=None, use_relu=True):
     """Async generator yielding (percent, HWC float32 image) after every optimiser step
-    (reference :229-372). `device` (extension): the GPU to run on; default = current."""
+    (reference :229-372). `device` (extension): the GPU to run on; default = current.  `content_layer`,
+    `style_layers`, `use_relu` (extension): the feature maps the losses read, see NeuralStyleTransfer.set_feature_maps
+    (None: the reference's).  They are validated before any GPU work."""
+    taps = _taps.normalize_taps(content_layer, style_layers, use_relu)
     if device is None:
         if not torch.cuda.is_available():
             raise RuntimeError("no GPU visible: the HIP style-transfer engine has no CPU path")
@@ -298,6 +321,7 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
     init_name = {"random": "random", "content": content_n_style.content[0], "style": content_n_style.style[0]}[tag]
 
     nst = NeuralStyleTransfer(device, model, style_levels, optimizer)
+    nst.set_feature_maps(*taps, use_relu=use_relu)
     lr_start = 10.0
     async for img, cur_iter in nst.process(content_levels, init_img, lr_start, iters_num, content_weight,
                                            style_weight, tv_weight, init_name):

@@ -109,9 +109,23 @@ int nst_ctx_create_ex(int device, const float* const* weights, const float* cons
  * (neural_style_transfer.py:170-176).  Allocates the activation workspace of every level. */
 int nst_job_configure(nst_ctx* ctx, int levels_num, int H0, int W0);
 
+/* The feature maps the losses read: LossBuilder(content_feature_maps_index, style_feature_maps_indices, ...) and
+ * Vgg19(use_relu=...) (neural_style_transfer.py:41-82, neural_nets.py:17-28) as a setting of the context.  Indices are
+ * those of Vgg19.layer_names: 0..5 = relu1_1, relu2_1, relu3_1, relu4_1, conv4_2, relu5_1.
+ *   content_index: 0..5;  style_mask: non-empty set of bits 0..5 (bit i = map i; order and repeats of the reference's
+ *   list do not matter, the style term is the mean over the maps in the set);  use_relu: 1, or 0 = the reference's
+ *   use_relu=False - map 5 is then conv5_1 BEFORE its ReLU (torchvision's in-place ReLUs leave maps 0..4 post-ReLU).
+ * NST_E_ARG for anything else.  A new context has the reference's taps: (4, 0x2F, 1).  The forward of a closure stops at
+ * the deepest map in use, its backward starts there.  Setting taps (even the same ones) waits for the context's work,
+ * re-sizes the target buffers of every configured level and drops their targets (a closure returns NST_E_STATE until
+ * nst_level_set_targets has run again) and any captured closure graph.  nst_vgg_features / nst_vgg_activations return
+ * conv5_1 before its ReLU under use_relu = 0.  The stripe closure (nst_window_*) implements the default taps only and
+ * returns NST_E_STATE under any other. */
+int nst_job_set_taps(nst_ctx* ctx, int content_index, unsigned style_mask, int use_relu);
+
 /* LossBuilder.__init__ (neural_style_transfer.py:68-82): target content representation
  * ReLU(conv4_2) of the content image and the 5 target Gram matrices of the style image of one
- * level.  content: device (3,h,w) of that level's size; style: device (3,hs,ws), any size. */
+ * level (of the maps nst_job_set_taps chose, when it was called).  content: device (3,h,w) of that level's size; style: device (3,hs,ws), any size. */
 int nst_level_set_targets(nst_ctx* ctx, int level, const float* content, const float* style,
                           int hs, int ws, void* stream);
 
@@ -273,7 +287,8 @@ int nst_scale(nst_ctx* ctx, const float* src, float alpha, size_t n, float* dst,
  *     runs the backward pass for the loss terms of the owned rows and writes d loss / d xs to gxs (3, ext_rows, W0);
  *     the caller adds the stripes' gradients into the full image (overlap-add, one all-reduce).  losses[0..3] = (total,
  *     content, style, tv) of the level, losses[4] = total - identical on every rank.
- * Nothing else may run on the context between begin and end. */
+ * Nothing else may run on the context between begin and end.  The stripe closure implements the default feature maps
+ * only: after nst_job_set_taps with any other taps both calls return NST_E_STATE. */
 int nst_window_sums_count(size_t* count);
 int nst_window_begin(nst_ctx* ctx, const float* xs, int row0, int rows, int H0, float* sums, void* stream);
 int nst_window_end(nst_ctx* ctx, const float* xs, int row0, int rows, int H0, float content_weight, float style_weight,
