@@ -19,6 +19,8 @@ NST_MAX_LEVELS = 8
 NST_LOSS_ROW = 4
 NST_OPT_ADAM = 0
 NST_OPT_LBFGS = 1
+NST_COLOR_RGB = 0
+NST_COLOR_LUMINANCE = 1
 
 c_float_p = C.POINTER(C.c_float)
 REDUCE_HOOK = C.CFUNCTYPE(None, C.c_void_p)
@@ -53,6 +55,13 @@ SYMBOLS = {
     "nst_ctx_destroy": (None, [c_void]),
     "nst_job_configure": (C.c_int, [c_void, C.c_int, C.c_int, C.c_int]),
     "nst_job_set_taps": (C.c_int, [c_void, C.c_int, C.c_uint, C.c_int]),
+    "nst_job_set_color": (C.c_int, [c_void, C.c_int]),
+    "nst_job_color": (C.c_int, [c_void]),
+    "nst_color_stats": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), c_void]),
+    "nst_color_transfer_matrix": (C.c_int, [C.POINTER(C.c_double)] * 6),
+    "nst_color_affine": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), c_void, c_void]),
+    "nst_luminance": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_double, C.c_double, c_void, c_void]),
+    "nst_luminance_recombine": (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, c_void, c_void]),
     "nst_level_set_targets": (C.c_int, [c_void, C.c_int, c_void, c_void, C.c_int, C.c_int, c_void]),
     "nst_closure": (C.c_int, [c_void, c_void, C.c_float, C.c_float, C.c_float, c_void, c_void, c_void]),
     "nst_closure_levels": (C.c_int, [c_void, c_void, C.c_float, C.c_float, C.c_float, C.c_uint, c_void, c_void, c_void]),

@@ -1,4 +1,5 @@
 """Configuration surface of the reference (config.py:1-31): same names, same defaults."""
+from .color_modes import check_preserve_color
 
 # jobs that may run at once PER GPU (the reference runs everything on device 0; here the
 # scheduler multiplies this by the number of GPUs of the node). Use 1 when levels_num > 2.
@@ -20,11 +21,13 @@ _DEFAULTS = dict(
     noise_levels_dispersion=(0.20, 0.30, 0.40, 0.60, 0.30),
 )
 # extension, keyword-only: the feature maps the losses read (neural_style_transfer(..., content_layer=, style_layers=,
-# use_relu=)); None = the reference's content 4 / style [0, 1, 2, 3, 5].  Not part of the positional order or the repr.
+# use_relu=)); None = the reference's content 4 / style [0, 1, 2, 3, 5]; and colour preservation (preserve_color=).
+# Not part of the positional order or the repr.
 _KW_ONLY = dict(
     content_layer=None,            # index 0..5 or a name of Vgg19.layer_names
     style_layers=None,             # indices / names
     use_relu=True,                 # False: the reference's Vgg19(use_relu=False) taps
+    preserve_color=None,           # None | 'luminance' | 'histogram': keep the content's colours (Gatys et al. 2016)
 )
 
 
@@ -45,6 +48,7 @@ class Config:
             raise TypeError(f"Config() got unexpected keyword argument(s): {sorted(unknown)}")
         for name, default in {**_DEFAULTS, **_KW_ONLY}.items():
             setattr(self, name, kwargs.get(name, default))
+        check_preserve_color(self.preserve_color)
 
     def __repr__(self):
         return "Config(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in _DEFAULTS) + ")"

@@ -6,6 +6,7 @@
 // table lives in registers, the 3-plane halo patch in LDS.
 // Input gradient: conv1_1_dgrad_h2_kernel (two-piece fp16 arithmetic on v_mfma_f32_16x16x32_f16, the default) and
 // conv1_1_dgrad_kernel (fp32 on the VALU, for the paths that record no absmax).
+// Luminance mode (nst_job_set_color): LUM variants of all three read / write ONE plane u, the image being x_c = u - mean_c.
 #include <hip/hip_runtime.h>
 
 #include "nst_kernels.h"
@@ -40,6 +41,13 @@ __host__ __device__ constexpr int tap_off(int k) {
 // tile's MFMAs and written to LDS after its stores.
 constexpr int F_PATCH_PER_T = (3 * F_PLANE + 255) / 256;
 
+// the ImageNet mean (x255) of pixel_ops.hip's prepare_img: the luminance variant forms x_c = u - mean_c in fp32
+__device__ __forceinline__ float mean255(int c) { return c == 0 ? 123.675f : (c == 1 ? 116.28f : 103.53f); }
+
+// LUM (nst_job_set_color luminance): x is ONE plane u (1,H,W) and the patch planes are x_c = u - mean_c inside the image,
+// 0 in the padding - the same LDS contents the RGB form stages from a planar image x_c = fl(u - mean_c), from a third of
+// the bytes.  Weights, MFMAs and epilogue are the RGB form's.
+template <bool LUM>
 __global__ __launch_bounds__(256, 2) void conv1_1_fwd_kernel(const float* __restrict__ x, int H, int W,
                                                           const float* __restrict__ wk,
                                                           const float* __restrict__ bias, float* __restrict__ out,
@@ -66,7 +74,9 @@ __global__ __launch_bounds__(256, 2) void conv1_1_fwd_kernel(const float* __rest
         for (int i = 0; i < F_PATCH_PER_T; ++i) {
             const int pk = pu_off[i];
             const int c = pk >> 16, gy = y0 - 1 + ((pk >> 8) & 255), gx = x0 - 1 + (pk & 255);
-            v[i] = (pk >= 0 && tile < ntiles && gy >= 0 && gy < H && gx >= 0 && gx < W) ? x[((size_t)c * H + gy) * W + gx] : 0.f;
+            const bool inb = pk >= 0 && tile < ntiles && gy >= 0 && gy < H && gx >= 0 && gx < W;
+            if (LUM) v[i] = inb ? x[(size_t)gy * W + gx] - mean255(c) : 0.f;
+            else v[i] = inb ? x[((size_t)c * H + gy) * W + gx] : 0.f;
         }
     };
     auto stash = [&](const float* v) {
@@ -185,10 +195,13 @@ __global__ __launch_bounds__(256, 2) void conv1_1_fwd_kernel(const float* __rest
 }
 
 hipError_t launch_conv1_1_fwd(const float* x, int H, int W, const float* wk, const float* bias, float* out,
-                              unsigned* bits_out, unsigned* amax_out, hipStream_t stream) {
+                              unsigned* bits_out, unsigned* amax_out, hipStream_t stream, int channels) {
     const int ntiles = ((H + F_TH - 1) / F_TH) * ((W + F_TW - 1) / F_TW);
     const int blocks = ntiles < 512 ? ntiles : 512;          // two workgroups per CU, each walking tiles b, b + 512, ...
-    hipLaunchKernelGGL(conv1_1_fwd_kernel, dim3(blocks), dim3(256), 0, stream, x, H, W, wk, bias, out, bits_out, amax_out, ntiles);
+    if (channels == 1)
+        hipLaunchKernelGGL(conv1_1_fwd_kernel<true>, dim3(blocks), dim3(256), 0, stream, x, H, W, wk, bias, out, bits_out, amax_out, ntiles);
+    else
+        hipLaunchKernelGGL(conv1_1_fwd_kernel<false>, dim3(blocks), dim3(256), 0, stream, x, H, W, wk, bias, out, bits_out, amax_out, ntiles);
     return hipGetLastError();
 }
 
@@ -204,6 +217,9 @@ constexpr int D_RS = D_KC + 4;             // LDS row stride (floats)
 constexpr int D_UNITS = D_P * D_P * (D_KC / 4);
 }  // namespace
 
+// LUM (luminance mode): the image is one plane u with x_c = u - mean_c, so d/du = sum_c d/dx_c - the three accumulators
+// are added ((g0 + g1) + g2: the RGB form's three outputs summed in fp32) and one plane is written.
+template <bool LUM>
 __global__ __launch_bounds__(256) void conv1_1_dgrad_kernel(const float* __restrict__ g, int H, int W,
                                                             const float* __restrict__ wd, float* __restrict__ gx) {
     __shared__ __attribute__((aligned(16))) float patch[D_P * D_P * D_RS];
@@ -261,9 +277,13 @@ __global__ __launch_bounds__(256) void conv1_1_dgrad_kernel(const float* __restr
     const int y = y0 + py, x = x0 + px;
     if (y < H && x < W) {
         const size_t HW = (size_t)H * W, i = (size_t)y * W + x;
-        gx[i] = a01[0];
-        gx[HW + i] = a01[1];
-        gx[2 * HW + i] = a2;
+        if (LUM) {
+            gx[i] = (a01[0] + a01[1]) + a2;
+        } else {
+            gx[i] = a01[0];
+            gx[HW + i] = a01[1];
+            gx[2 * HW + i] = a2;
+        }
     }
 }
 
@@ -305,6 +325,10 @@ __device__ __forceinline__ unsigned wave_max(unsigned m) {
 }
 }  // namespace
 
+// LUM: lanes l15 = 0, 1, 2 hold the three channels of a pixel; their values are added across lanes ((c0 + c1) + c2) and
+// lane l15 = 0 writes the one plane.  The MFMAs are the RGB form's (the nine columns ky*3 + c stay: the channel sum comes
+// after the tap-row sum, which needs them apart).
+template <bool LUM>
 __global__ __launch_bounds__(256, 2) void conv1_1_dgrad_h2_kernel(const float* __restrict__ g, int H, int W,
                                                                   const float* __restrict__ wd,
                                                                   const unsigned* __restrict__ amax_g, float* __restrict__ gx,
@@ -438,20 +462,27 @@ __global__ __launch_bounds__(256, 2) void conv1_1_dgrad_h2_kernel(const float* _
                 const float v2 = am[r + 2][i] + ax[r + 2][i] * G_LO_DOWN;
                 const float s = (v0 + __shfl(v1, lane + 3) + __shfl(v2, lane + 6)) * inv;
                 const int x = x0 + kg * 4 + i;
-                if (l15 < 3 && y < H && x < W) gx[l15 * HW + (size_t)y * W + x] = s;
+                if (LUM) {
+                    const float sum = (s + __shfl(s, lane + 1)) + __shfl(s, lane + 2);
+                    if (l15 == 0 && y < H && x < W) gx[(size_t)y * W + x] = sum;
+                } else {
+                    if (l15 < 3 && y < H && x < W) gx[l15 * HW + (size_t)y * W + x] = s;
+                }
             }
         }
     }
 }
 
 hipError_t launch_conv1_1_dgrad(const float* g, int H, int W, const float* wd, const unsigned* amax_g, float* gx,
-                                hipStream_t stream) {
+                                hipStream_t stream, int channels) {
     const int blocks = ((H + D_T - 1) / D_T) * ((W + D_T - 1) / D_T);
+    const bool lum = channels == 1;
     if (amax_g)     // two workgroups per CU, each walking tiles b, b + grid, ...: scales and weight fragments once per workgroup
-        hipLaunchKernelGGL(conv1_1_dgrad_h2_kernel, dim3(blocks < 512 ? blocks : 512), dim3(256), 0, stream, g, H, W, wd, amax_g,
-                           gx, blocks);
+        hipLaunchKernelGGL(lum ? conv1_1_dgrad_h2_kernel<true> : conv1_1_dgrad_h2_kernel<false>, dim3(blocks < 512 ? blocks : 512),
+                           dim3(256), 0, stream, g, H, W, wd, amax_g, gx, blocks);
     else
-        hipLaunchKernelGGL(conv1_1_dgrad_kernel, dim3(blocks), dim3(256), 0, stream, g, H, W, wd, gx);
+        hipLaunchKernelGGL(lum ? conv1_1_dgrad_kernel<true> : conv1_1_dgrad_kernel<false>, dim3(blocks), dim3(256), 0, stream, g, H,
+                           W, wd, gx);
     return hipGetLastError();
 }
 

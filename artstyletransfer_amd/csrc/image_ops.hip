@@ -210,4 +210,115 @@ hipError_t launch_scale(const float* src, float alpha, size_t n, float* dst, hip
     return hipGetLastError();
 }
 
+// ---- colour preservation (nst_job_set_color; Gatys et al., "Preserving Color in Neural Artistic Style Transfer", 2016) ----
+// Set-up only: O(pixels) and HBM-bound, fp64 arithmetic so that the host restatement (host_image.py) holds them to rounding.
+__device__ __forceinline__ double luma(const float* p) { return 0.299 * (double)p[0] + 0.587 * (double)p[1] + 0.114 * (double)p[2]; }
+
+// PASS 0: per-block sums of p_c (3); PASS 1: of (p_c - mean_c)(p_d - mean_d), c <= d (6).  Strided per-thread sums in index
+// order, then a fixed tree: the same result on every run.
+template <int PASS>
+__global__ __launch_bounds__(256) void color_partial_kernel(const float* __restrict__ hwc, size_t pixels,
+                                                            const double* __restrict__ mean3, double* __restrict__ partial) {
+    constexpr int NV = PASS ? 6 : 3;
+    __shared__ double red[NV][256];
+    double acc[NV];
+#pragma unroll
+    for (int k = 0; k < NV; ++k) acc[k] = 0.0;
+    double m0 = 0.0, m1 = 0.0, m2 = 0.0;
+    if constexpr (PASS == 1) { m0 = mean3[0]; m1 = mean3[1]; m2 = mean3[2]; }
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < pixels; i += (size_t)gridDim.x * blockDim.x) {
+        const double r = hwc[i * 3], g = hwc[i * 3 + 1], b = hwc[i * 3 + 2];
+        if constexpr (PASS == 0) {
+            acc[0] += r; acc[1] += g; acc[2] += b;
+        } else {
+            const double dr = r - m0, dg = g - m1, db = b - m2;
+            acc[0] += dr * dr; acc[1] += dr * dg; acc[2] += dr * db;
+            acc[3] += dg * dg; acc[4] += dg * db; acc[5] += db * db;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < NV; ++k) red[k][threadIdx.x] = acc[k];
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off)
+#pragma unroll
+            for (int k = 0; k < NV; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x < NV) partial[(size_t)blockIdx.x * NV + threadIdx.x] = red[threadIdx.x][0];
+}
+// one workgroup: the COLOR_BLOCKS partials in a fixed tree -> mean3 (PASS 0) or the symmetric cov9 (PASS 1)
+template <int PASS>
+__global__ __launch_bounds__(256) void color_finish_kernel(const double* __restrict__ partial, size_t pixels, double* __restrict__ out) {
+    constexpr int NV = PASS ? 6 : 3;
+    __shared__ double red[NV][COLOR_BLOCKS];
+    for (int k = 0; k < NV; ++k) red[k][threadIdx.x] = partial[(size_t)threadIdx.x * NV + k];
+    __syncthreads();
+    for (int off = COLOR_BLOCKS / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off)
+            for (int k = 0; k < NV; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double n = (double)pixels;
+        if (PASS == 0) {
+            for (int k = 0; k < 3; ++k) out[k] = red[k][0] / n;
+        } else {
+            const int ij[6][2] = {{0, 0}, {0, 1}, {0, 2}, {1, 1}, {1, 2}, {2, 2}};
+            for (int k = 0; k < 6; ++k) {
+                const double v = red[k][0] / n;
+                out[ij[k][0] * 3 + ij[k][1]] = v;
+                out[ij[k][1] * 3 + ij[k][0]] = v;
+            }
+        }
+    }
+}
+hipError_t launch_color_stats(const float* hwc, size_t pixels, double* scratch, double* mean3, double* cov9, hipStream_t stream) {
+    static_assert(COLOR_BLOCKS == 256, "the finish kernel gives one partial to each of its 256 threads");
+    hipLaunchKernelGGL(color_partial_kernel<0>, dim3(COLOR_BLOCKS), dim3(256), 0, stream, hwc, pixels, nullptr, scratch);
+    hipLaunchKernelGGL(color_finish_kernel<0>, dim3(1), dim3(COLOR_BLOCKS), 0, stream, scratch, pixels, mean3);
+    hipLaunchKernelGGL(color_partial_kernel<1>, dim3(COLOR_BLOCKS), dim3(256), 0, stream, hwc, pixels, mean3, scratch);
+    hipLaunchKernelGGL(color_finish_kernel<1>, dim3(1), dim3(COLOR_BLOCKS), 0, stream, scratch, pixels, cov9);
+    return hipGetLastError();
+}
+
+__global__ void color_affine_kernel(const float* src, size_t pixels, ColorAffine a, float* dst) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < pixels; i += (size_t)gridDim.x * blockDim.x) {
+        const double p0 = src[i * 3], p1 = src[i * 3 + 1], p2 = src[i * 3 + 2];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) dst[i * 3 + c] = (float)(a.m[c][0] * p0 + a.m[c][1] * p1 + a.m[c][2] * p2 + a.b[c]);
+    }
+}
+hipError_t launch_color_affine(const float* src, size_t pixels, const ColorAffine& a, float* dst, hipStream_t stream) {
+    hipLaunchKernelGGL(color_affine_kernel, dim3(img_blocks(pixels)), dim3(256), 0, stream, src, pixels, a, dst);
+    return hipGetLastError();
+}
+
+__global__ void luminance_kernel(const float* __restrict__ hwc, size_t pixels, double alpha, double beta, float* __restrict__ out) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < pixels; i += (size_t)gridDim.x * blockDim.x)
+        out[i] = (float)(255.0 * (alpha * luma(hwc + i * 3) + beta));
+}
+hipError_t launch_luminance(const float* hwc, size_t pixels, double alpha, double beta, float* out, hipStream_t stream) {
+    hipLaunchKernelGGL(luminance_kernel, dim3(img_blocks(pixels)), dim3(256), 0, stream, hwc, pixels, alpha, beta, out);
+    return hipGetLastError();
+}
+
+__global__ void luminance_recombine_kernel(const float* __restrict__ u, const float* __restrict__ content, size_t pixels,
+                                           ColorAffine inv, float* __restrict__ out) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < pixels; i += (size_t)gridDim.x * blockDim.x) {
+        const double r = content[i * 3], g = content[i * 3 + 1], b = content[i * 3 + 2];
+        const double y = (double)u[i] / 255.0;
+        const double ci = 0.595716 * r - 0.274453 * g - 0.321263 * b;
+        const double cq = 0.211456 * r - 0.522591 * g + 0.311135 * b;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) out[i * 3 + c] = (float)(inv.m[c][0] * y + inv.m[c][1] * ci + inv.m[c][2] * cq);
+    }
+}
+hipError_t launch_luminance_recombine(const float* u, const float* content_hwc, size_t pixels, const ColorAffine& yiq_inv,
+                                      float* out, hipStream_t stream) {
+    hipLaunchKernelGGL(luminance_recombine_kernel, dim3(img_blocks(pixels)), dim3(256), 0, stream, u, content_hwc, pixels, yiq_inv,
+                       out);
+    return hipGetLastError();
+}
+
 }  // namespace nst

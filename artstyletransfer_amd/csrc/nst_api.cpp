@@ -88,6 +88,7 @@ struct LevelWs {
     size_t gbuf_floats = 0;
     float* xl = nullptr;        // level image (levels >= 1), planar
     float* gxl = nullptr;       // its gradient (levels >= 1), planar
+    size_t xl_floats = 0;       // channels (nst_job_set_color) x h x w
     float* content_t = nullptr; // NHWC target ReLU(conv4_2)
     size_t content_n = 0;
     float* gram_t[kMaxStyle] = {};
@@ -151,6 +152,8 @@ struct nst_ctx {
     float* w11d = nullptr;      // [9][64][4]
     int levels = 0;
     Taps taps;                  // nst_job_set_taps
+    int channels = 3;           // nst_job_set_color: 3 = RGB, 1 = luminance (the optimised image is u = 255 Y)
+    double* color_scratch = nullptr;   // nst_color_stats: COLOR_BLOCKS * 9 partials | mean (3) | cov (9), made on first use
     LevelWs lv[NST_MAX_LEVELS];
     hipEvent_t fork = nullptr;
     size_t bytes = 0;
@@ -488,7 +491,8 @@ bool bf3_unsplit(const nst_ctx* ctx, const ConvParams& p) {
 }
 
 // ---- network forward ----------------------------------------------------------------------------
-int forward(nst_ctx* ctx, ActSet& a, const float* x, int h, int w, hipStream_t s, int last_layer = NL - 1) {
+// channels = 1: x is a luminance plane u, conv1_1 sees x_c = u - mean_c (nst_job_set_color)
+int forward(nst_ctx* ctx, ActSet& a, const float* x, int h, int w, hipStream_t s, int last_layer = NL - 1, int channels = 3) {
     for (int l = 0; l < NL; ++l) a.bits_valid[l] = false;
     for (int k = 0; k < 4; ++k) a.pooled[k] = false;
     const bool h2 = ctx->conv_mode == 2;
@@ -496,7 +500,7 @@ int forward(nst_ctx* ctx, ActSet& a, const float* x, int h, int w, hipStream_t s
     {
         Timer t(ctx, s, K_CONV1, conv_flops(h, w, 3, 64, 9));
         unsigned* bits = ctx->conv_mode ? a.bits[0] : nullptr;
-        HIPCHK(ctx, launch_conv1_1_fwd(x, h, w, ctx->w11k, ctx->bias[0], a.act[0], bits, h2 ? amax_act(a, 0) : nullptr, s));
+        HIPCHK(ctx, launch_conv1_1_fwd(x, h, w, ctx->w11k, ctx->bias[0], a.act[0], bits, h2 ? amax_act(a, 0) : nullptr, s, channels));
         a.bits_valid[0] = bits != nullptr;
     }
     for (int l = 1; l <= last_layer; ++l) {
@@ -550,8 +554,9 @@ struct ContentJob { const float* target; size_t n; float coef; double* partial; 
 // Backward through the network down to the planar image gradient gx (overwritten).
 // inj[l] describes what enters at conv layer l; gbuf: two NHWC scratch buffers of the largest size.  The chain starts at
 // layer `top` (nothing above it is read); `top_mask` = false: the top map is pre-ReLU (its gradient passes unmasked).
+// channels = 1: gx is the gradient of a luminance plane (the sum over the three channels)
 int backward(nst_ctx* ctx, ActSet& a, const Inject* inj, const ContentJob* cj, float* gbuf0, float* gbuf1, float* gx,
-             int h, int w, hipStream_t s, int top = NL - 1, bool top_mask = true) {
+             int h, int w, hipStream_t s, int top = NL - 1, bool top_mask = true, int channels = 3) {
     float* cur = gbuf0;     // holds the gradient w.r.t. the pre-ReLU output of the layer being processed
     float* oth = gbuf1;
     const bool h2 = ctx->conv_mode == 2;
@@ -644,7 +649,7 @@ int backward(nst_ctx* ctx, ActSet& a, const Inject* inj, const ContentJob* cj, f
     }
     {
         Timer t(ctx, s, K_CONV1, conv_flops(h, w, 64, 3, 9));
-        HIPCHK(ctx, launch_conv1_1_dgrad(cur, h, w, ctx->w11d, h2 ? amax_grad(a, 0) : nullptr, gx, s));
+        HIPCHK(ctx, launch_conv1_1_dgrad(cur, h, w, ctx->w11d, h2 ? amax_grad(a, 0) : nullptr, gx, s, channels));
     }
     return NST_OK;
 }
@@ -714,11 +719,11 @@ int batched_forward(nst_ctx* ctx, const float* const* xi, const int* lv, int n, 
         if (h2) HIPCHK(ctx, launch_zero(a.amax, (size_t)AMAX_IDS * NST_AMAX_SLOTS, s));
         {
             Timer t(ctx, s, K_OTHER, 0);
-            HIPCHK(ctx, launch_tv_partial(xi[lv[k]], 3, L.h, L.w, L.tv_partial, s, win ? win->row0 : 0, win ? win->rows : 0));
+            HIPCHK(ctx, launch_tv_partial(xi[lv[k]], ctx->channels, L.h, L.w, L.tv_partial, s, win ? win->row0 : 0, win ? win->rows : 0));
         }
         Timer t(ctx, s, K_CONV1, conv_flops(L.h, L.w, 3, 64, 9));
         HIPCHK(ctx, launch_conv1_1_fwd(xi[lv[k]], L.h, L.w, ctx->w11k, ctx->bias[0], a.act[0], a.bits[0],
-                                       h2 ? amax_act(a, 0) : nullptr, s));
+                                       h2 ? amax_act(a, 0) : nullptr, s, ctx->channels));
         a.bits_valid[0] = true;
     }
     for (int l = 1; l <= top; ++l) {
@@ -934,14 +939,15 @@ int batched_backward(nst_ctx* ctx, const float* const* xi, float* const* gi, con
         LevelWs& L = ctx->lv[lv[k]];
         {
             Timer t(ctx, s, K_CONV1, conv_flops(L.h, L.w, 64, 3, 9));
-            HIPCHK(ctx, launch_conv1_1_dgrad(cur[k], L.h, L.w, ctx->w11d, h2 ? amax_grad(L.acts, 0) : nullptr, gi[lv[k]], s));
+            HIPCHK(ctx, launch_conv1_1_dgrad(cur[k], L.h, L.w, ctx->w11d, h2 ? amax_grad(L.acts, 0) : nullptr, gi[lv[k]], s,
+                                             ctx->channels));
         }
         Timer t(ctx, s, K_OTHER, 0);
         if (win)
-            HIPCHK(ctx, launch_tv_finish(xi[lv[k]], 3, L.h, L.w, L.tv_partial, tvw, gi[lv[k]], 1, nullptr, s, win->row0, win->rows,
+            HIPCHK(ctx, launch_tv_finish(xi[lv[k]], ctx->channels, L.h, L.w, L.tv_partial, tvw, gi[lv[k]], 1, nullptr, s, win->row0, win->rows,
                                          win_means, win_nx, win_ny));
         else
-            HIPCHK(ctx, launch_tv_finish(xi[lv[k]], 3, L.h, L.w, L.tv_partial, tvw, gi[lv[k]], 1, L.tv_means, s));
+            HIPCHK(ctx, launch_tv_finish(xi[lv[k]], ctx->channels, L.h, L.w, L.tv_partial, tvw, gi[lv[k]], 1, L.tv_means, s));
     }
     return NST_OK;
 }
@@ -952,7 +958,7 @@ int closure_batched(nst_ctx* ctx, const float* const* xi, float* const* gi, unsi
     int lv[NST_MAX_LEVELS], n = 0;
     for (int i = 0; i < ctx->levels; ++i) {
         if ((level_mask >> i) & 1u) lv[n++] = i;
-        else if ((zero_mask >> i) & 1u) HIPCHK(ctx, launch_zero(gi[i], (size_t)3 * ctx->lv[i].h * ctx->lv[i].w, s));
+        else if ((zero_mask >> i) & 1u) HIPCHK(ctx, launch_zero(gi[i], (size_t)ctx->channels * ctx->lv[i].h * ctx->lv[i].w, s));
     }
     if (n == 0) return NST_OK;
     // (not while a hipGraph is being captured or replayed: the closure then stays on one stream)
@@ -991,6 +997,21 @@ int alloc_tap_buffers(nst_ctx* ctx, LevelWs& L) {
     }
     L.gram_part_floats = gram_part_floats_for(tp, L.h, L.w);
     NSTCHK(dev_alloc_t(ctx, &L.gram_part, L.gram_part_floats));
+    return NST_OK;
+}
+
+// the level image and its gradient (levels >= 1): their size follows the channel count (nst_job_set_color)
+void free_level_image(nst_ctx* ctx, LevelWs& L) {
+    for (float** p : {&L.xl, &L.gxl}) {
+        if (*p) { dev_free(*p); if (ctx->bytes >= L.xl_floats * 4) ctx->bytes -= L.xl_floats * 4; }
+        *p = nullptr;
+    }
+    L.xl_floats = 0;
+}
+int alloc_level_image(nst_ctx* ctx, LevelWs& L) {
+    L.xl_floats = (size_t)ctx->channels * L.h * L.w;
+    NSTCHK(dev_alloc_t(ctx, &L.xl, L.xl_floats));
+    NSTCHK(dev_alloc_t(ctx, &L.gxl, L.xl_floats));
     return NST_OK;
 }
 
@@ -1243,7 +1264,7 @@ void nst_ctx_destroy(nst_ctx* ctx) {
     for (int i = 0; i < NST_MAX_LEVELS; ++i) free_level(ctx, ctx->lv[i]);
     if (ctx->tail) (void)hipEventDestroy(ctx->tail);
     for (int l = 0; l < NL; ++l) { dev_free(ctx->wf[l]); dev_free(ctx->wd[l]); dev_free(ctx->bias[l]); dev_free(ctx->wf_bf[l]); dev_free(ctx->wd_bf[l]); dev_free(ctx->wf_h2[l]); dev_free(ctx->wd_h2[l]); dev_free(ctx->wf_wino[l]); dev_free(ctx->wd_wino[l]); }
-    dev_free(ctx->w11k); dev_free(ctx->w11d);
+    dev_free(ctx->w11k); dev_free(ctx->w11d); dev_free(ctx->color_scratch);
     if (ctx->gexec) (void)hipGraphExecDestroy(ctx->gexec);
     if (ctx->gstream) (void)hipStreamDestroy(ctx->gstream);
     if (ctx->side) (void)hipStreamDestroy(ctx->side);
@@ -1282,10 +1303,7 @@ int nst_job_configure(nst_ctx* ctx, int levels_num, int H0, int W0) {
         L.gbuf_floats = (size_t)h * w * 64;
         NSTCHK(dev_alloc_t(ctx, &L.gbuf[0], L.gbuf_floats));
         NSTCHK(dev_alloc_t(ctx, &L.gbuf[1], L.gbuf_floats));
-        if (i > 0) {
-            NSTCHK(dev_alloc_t(ctx, &L.xl, (size_t)3 * h * w));
-            NSTCHK(dev_alloc_t(ctx, &L.gxl, (size_t)3 * h * w));
-        }
+        if (i > 0) NSTCHK(alloc_level_image(ctx, L));      // sized for the context's current channel count
         NSTCHK(alloc_tap_buffers(ctx, L));       // sized for the context's current taps
         NSTCHK(dev_alloc_t(ctx, &L.content_partial, MSE_BLOCKS));
         NSTCHK(dev_alloc_t(ctx, &L.tv_partial, 2 * TV_BLOCKS));
@@ -1326,6 +1344,47 @@ int nst_job_set_taps(nst_ctx* ctx, int content_index, unsigned style_mask, int u
     return NST_OK;
 }
 
+// Gatys et al. 2016, luminance-only transfer: the optimised image becomes one plane u = 255 Y (channels = 1) that the
+// network sees as x_c = u - mean_c.  Same life cycle as the taps: every level's targets and the captured closure go.
+int nst_job_set_color(nst_ctx* ctx, int mode) {
+    NSTCHK(bind(ctx));
+    if (mode != NST_COLOR_RGB && mode != NST_COLOR_LUMINANCE) return fail(ctx, NST_E_ARG, "mode must be NST_COLOR_RGB or NST_COLOR_LUMINANCE");
+    const int channels = mode == NST_COLOR_LUMINANCE ? 1 : 3;
+    quiesce(ctx);
+    // the level images of the new channel count first: if one cannot be had, the context stays as it was (old mode, old
+    // buffers, targets kept)
+    float* img[NST_MAX_LEVELS][2] = {};
+    int r = NST_OK;
+    for (int i = 1; i < ctx->levels && r == NST_OK; ++i) {
+        const size_t n = (size_t)channels * ctx->lv[i].h * ctx->lv[i].w;
+        r = dev_alloc_t(ctx, &img[i][0], n);
+        if (r == NST_OK) r = dev_alloc_t(ctx, &img[i][1], n);
+    }
+    if (r != NST_OK) {
+        for (int i = 1; i < ctx->levels; ++i) {
+            const size_t bytes = (size_t)channels * ctx->lv[i].h * ctx->lv[i].w * 4;
+            for (float* p : img[i])
+                if (p) { dev_free(p); if (ctx->bytes >= bytes) ctx->bytes -= bytes; }
+        }
+        return r;
+    }
+    if (ctx->gexec) { (void)hipGraphExecDestroy(ctx->gexec); ctx->gexec = nullptr; }
+    ctx->gkey = {}; ctx->glast = {};
+    ctx->channels = channels;
+    for (int i = 0; i < ctx->levels; ++i) {
+        LevelWs& L = ctx->lv[i];
+        L.targets = false;
+        if (i > 0) {
+            free_level_image(ctx, L);
+            L.xl = img[i][0]; L.gxl = img[i][1];
+            L.xl_floats = (size_t)channels * L.h * L.w;
+        }
+    }
+    return NST_OK;
+}
+
+int nst_job_color(const nst_ctx* ctx) { return ctx ? (ctx->channels == 1 ? NST_COLOR_LUMINANCE : NST_COLOR_RGB) : -1; }
+
 static bool batch_eligible(const nst_ctx* ctx);
 int nst_level_set_targets(nst_ctx* ctx, int level, const float* content, const float* style, int hs, int ws,
                           void* stream) {
@@ -1346,7 +1405,7 @@ int nst_level_set_targets(nst_ctx* ctx, int level, const float* content, const f
         const int lv1 = level;
         NSTCHK(batched_forward(ctx, xi, &lv1, 1, s, nullptr));
     } else {
-        NSTCHK(forward(ctx, L.acts, content, L.h, L.w, s, tp.content));
+        NSTCHK(forward(ctx, L.acts, content, L.h, L.w, s, tp.content, ctx->channels));
     }
     HIPCHK(ctx, hipMemcpyAsync(L.content_t, L.acts.act[tp.content], L.content_n * 4, hipMemcpyDeviceToDevice, s));
     // style: the Gram matrices of the style image (its own size)
@@ -1354,7 +1413,7 @@ int nst_level_set_targets(nst_ctx* ctx, int level, const float* content, const f
     int r = alloc_acts(ctx, sa, hs, ws);
     float* part = nullptr;
     if (r == NST_OK) r = dev_alloc_t(ctx, &part, gram_part_floats_for(tp, hs, ws));
-    if (r == NST_OK) r = forward(ctx, sa, style, hs, ws, s, tp.style[tp.nstyle - 1]);
+    if (r == NST_OK) r = forward(ctx, sa, style, hs, ws, s, tp.style[tp.nstyle - 1], ctx->channels);
     for (int k = 0; k < tp.nstyle && r == NST_OK; ++k) {
         const int l = tp.style[k];
         const int C = kCout[l];
@@ -1455,7 +1514,7 @@ static int closure_record(nst_ctx* ctx, const float* x, float cw, float sw, floa
     for (int i = 1; i < ctx->levels; ++i) {
         LevelWs& L = ctx->lv[i];
         Timer t(ctx, main, K_OTHER, 0);
-        HIPCHK(ctx, launch_bicubic_down(xi[i - 1], 3, ctx->lv[i - 1].h, ctx->lv[i - 1].w, L.h, L.w, L.xl, main));
+        HIPCHK(ctx, launch_bicubic_down(xi[i - 1], ctx->channels, ctx->lv[i - 1].h, ctx->lv[i - 1].w, L.h, L.w, L.xl, main));
         xi[i] = L.xl; gi[i] = L.gxl;
     }
     const bool batch = batch_eligible(ctx);
@@ -1492,16 +1551,16 @@ static int closure_record(nst_ctx* ctx, const float* x, float cw, float sw, floa
         if (multi) HIPCHK(ctx, hipStreamWaitEvent(s, ctx->fork, 0));
         if (!((level_mask >> i) & 1u)) {
             // a level another rank owns: it contributes nothing here (its gradient arrives by all-reduce)
-            HIPCHK(ctx, launch_zero(gi[i], (size_t)3 * L.h * L.w, s));
+            HIPCHK(ctx, launch_zero(gi[i], (size_t)ctx->channels * L.h * L.w, s));
             if (multi) HIPCHK(ctx, hipEventRecord(L.done, s));
             continue;
         }
         {
             Timer t(ctx, s, K_OTHER, 0);
-            HIPCHK(ctx, launch_tv_partial(xi[i], 3, L.h, L.w, L.tv_partial, s));
+            HIPCHK(ctx, launch_tv_partial(xi[i], ctx->channels, L.h, L.w, L.tv_partial, s));
         }
         const Taps& tp = ctx->taps;
-        NSTCHK(forward(ctx, L.acts, xi[i], L.h, L.w, s, tp.top));
+        NSTCHK(forward(ctx, L.acts, xi[i], L.h, L.w, s, tp.top, ctx->channels));
         Inject inj[NL];
         for (int k = 0; k < tp.nstyle; ++k) {
             const int l = tp.style[k];
@@ -1518,10 +1577,10 @@ static int closure_record(nst_ctx* ctx, const float* x, float cw, float sw, floa
         }
         inj[tp.content].content = true;
         ContentJob cj{L.content_t, L.content_n, (float)((double)cw * 2.0 / (double)L.content_n), L.content_partial};
-        NSTCHK(backward(ctx, L.acts, inj, &cj, L.gbuf[0], L.gbuf[1], gi[i], L.h, L.w, s, tp.top, tp.top_mask()));
+        NSTCHK(backward(ctx, L.acts, inj, &cj, L.gbuf[0], L.gbuf[1], gi[i], L.h, L.w, s, tp.top, tp.top_mask(), ctx->channels));
         {
             Timer t(ctx, s, K_OTHER, 0);
-            HIPCHK(ctx, launch_tv_finish(xi[i], 3, L.h, L.w, L.tv_partial, tvw, gi[i], 1, L.tv_means, s));
+            HIPCHK(ctx, launch_tv_finish(xi[i], ctx->channels, L.h, L.w, L.tv_partial, tvw, gi[i], 1, L.tv_means, s));
         }
         if (multi) HIPCHK(ctx, hipEventRecord(L.done, s));
     }
@@ -1531,7 +1590,7 @@ static int closure_record(nst_ctx* ctx, const float* x, float cw, float sw, floa
     // pull the coarse-level gradients back up the bicubic chain (autograd of :173-176)
     for (int i = ctx->levels - 1; i >= 1; --i) {
         Timer t(ctx, main, K_OTHER, 0);
-        HIPCHK(ctx, launch_bicubic_down_bwd(gi[i], 3, ctx->lv[i - 1].h, ctx->lv[i - 1].w, ctx->lv[i].h, ctx->lv[i].w,
+        HIPCHK(ctx, launch_bicubic_down_bwd(gi[i], ctx->channels, ctx->lv[i - 1].h, ctx->lv[i - 1].w, ctx->lv[i].h, ctx->lv[i].w,
                                             gi[i - 1], 1, main));
     }
     LossAssembly la{};
@@ -1560,6 +1619,8 @@ static int window_check(nst_ctx* ctx, const float* xs, int row0, int rows, int H
     if (ctx->conv_mode != 2) return fail(ctx, NST_E_STATE, "the stripe closure runs on the f16x2 convolutions (NST_CONV unset)");
     if (!ctx->taps.is_default)
         return fail(ctx, NST_E_STATE, "the stripe closure implements the default feature maps only (nst_job_set_taps(ctx, 4, 0x2F, 1))");
+    if (ctx->channels != 3)
+        return fail(ctx, NST_E_STATE, "the stripe closure implements RGB only (nst_job_set_color(ctx, NST_COLOR_RGB))");
     LevelWs& L = ctx->lv[0];
     if (!L.targets) return fail(ctx, NST_E_STATE, "targets of the stripe not set");
     if (!xs) return fail(ctx, NST_E_ARG, "null buffer");
@@ -1768,7 +1829,7 @@ int nst_level_image(nst_ctx* ctx, int level, float* out, void* stream) {
     if (!out) return fail(ctx, NST_E_ARG, "null argument");
     const LevelWs& L = ctx->lv[level];
     hipStream_t s = enter(ctx, stream);
-    HIPCHK(ctx, hipMemcpyAsync(out, L.xl, (size_t)3 * L.h * L.w * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(out, L.xl, (size_t)ctx->channels * L.h * L.w * sizeof(float), hipMemcpyDeviceToDevice, s));
     mark(ctx, s);
     return NST_OK;
 }
@@ -1925,9 +1986,132 @@ int nst_scale(nst_ctx* ctx, const float* src, float alpha, size_t n, float* dst,
     return NST_OK;
 }
 
+// ---- colour preservation: set-up entry points (Gatys et al. 2016) ------------------------------------------------------
+int nst_color_stats(nst_ctx* ctx, const float* hwc, int h, int w, double* mean, double* cov, void* stream) {
+    NSTCHK(bind(ctx));
+    if (!hwc || !mean || !cov || h < 1 || w < 1) return fail(ctx, NST_E_ARG, "bad argument");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // the context's own scratch (kept: no allocation or free, and so no device-wide synchronisation, per call)
+    if (!ctx->color_scratch) NSTCHK(dev_alloc_t(ctx, &ctx->color_scratch, (size_t)COLOR_BLOCKS * 9 + 12));
+    double* dev = ctx->color_scratch;
+    double host[12];
+    HIPCHK(ctx, launch_color_stats(hwc, (size_t)h * w, dev, dev + (size_t)COLOR_BLOCKS * 9, dev + (size_t)COLOR_BLOCKS * 9 + 3, s));
+    HIPCHK(ctx, hipMemcpyAsync(host, dev + (size_t)COLOR_BLOCKS * 9, sizeof(host), hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));       // synchronous: the scratch is free again when this returns
+    std::memcpy(mean, host, 3 * sizeof(double));
+    std::memcpy(cov, host + 3, 9 * sizeof(double));
+    return NST_OK;
+}
+
+namespace {
+// eigen-decomposition of a symmetric 3x3 matrix by cyclic Jacobi rotations (fp64): a = V diag(e) V^T, columns of V
+void jacobi3(const double* a_in, double* e, double* V) {
+    double a[3][3];
+    for (int i = 0; i < 9; ++i) { a[i / 3][i % 3] = 0.5 * (a_in[i] + a_in[(i % 3) * 3 + i / 3]); V[i] = (i % 4 == 0) ? 1.0 : 0.0; }
+    for (int sweep = 0; sweep < 64; ++sweep) {
+        const double off = a[0][1] * a[0][1] + a[0][2] * a[0][2] + a[1][2] * a[1][2];
+        const double diag = a[0][0] * a[0][0] + a[1][1] * a[1][1] + a[2][2] * a[2][2];
+        if (off <= 1e-300 || off <= 1e-34 * diag) break;
+        for (int p = 0; p < 2; ++p)
+            for (int q = p + 1; q < 3; ++q) {
+                if (a[p][q] == 0.0) continue;
+                const double theta = (a[q][q] - a[p][p]) / (2.0 * a[p][q]);
+                const double t = (theta >= 0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+                const double c = 1.0 / std::sqrt(t * t + 1.0), sn = t * c;
+                for (int k = 0; k < 3; ++k) {           // a <- a J (columns p, q)
+                    const double akp = a[k][p], akq = a[k][q];
+                    a[k][p] = c * akp - sn * akq;
+                    a[k][q] = sn * akp + c * akq;
+                }
+                for (int k = 0; k < 3; ++k) {           // a <- J^T a (rows p, q)
+                    const double apk = a[p][k], aqk = a[q][k];
+                    a[p][k] = c * apk - sn * aqk;
+                    a[q][k] = sn * apk + c * aqk;
+                }
+                for (int k = 0; k < 3; ++k) {           // V <- V J
+                    const double vkp = V[k * 3 + p], vkq = V[k * 3 + q];
+                    V[k * 3 + p] = c * vkp - sn * vkq;
+                    V[k * 3 + q] = sn * vkp + c * vkq;
+                }
+            }
+    }
+    for (int i = 0; i < 3; ++i) e[i] = a[i][i];
+}
+// out = V diag(f(e)) V^T
+void sym_apply(const double* V, const double* fe, double* out) {
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            double acc = 0.0;
+            for (int k = 0; k < 3; ++k) acc += V[i * 3 + k] * fe[k] * V[j * 3 + k];
+            out[i * 3 + j] = acc;
+        }
+}
+// the YIQ (NTSC) matrix of nst_luminance_recombine and its fp64 inverse (adjugate / determinant)
+ColorAffine yiq_inverse() {
+    const double m[3][3] = {{0.299, 0.587, 0.114}, {0.595716, -0.274453, -0.321263}, {0.211456, -0.522591, 0.311135}};
+    ColorAffine r{};
+    const double det = m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]) +
+                       m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            const int a0 = (j + 1) % 3, a1 = (j + 2) % 3, b0 = (i + 1) % 3, b1 = (i + 2) % 3;
+            r.m[i][j] = (m[a0][b0] * m[a1][b1] - m[a0][b1] * m[a1][b0]) / det;
+        }
+    return r;
+}
+}  // namespace
+
+int nst_color_transfer_matrix(const double* mean_c, const double* cov_c, const double* mean_s, const double* cov_s, double* A,
+                              double* b) {
+    if (!mean_c || !cov_c || !mean_s || !cov_s || !A || !b) return fail(nullptr, NST_E_ARG, "null argument");
+    double ec[3], Vc[9], es[3], Vs[9], fc[3], fs[3], Rc[9], Rs[9];
+    jacobi3(cov_c, ec, Vc);
+    jacobi3(cov_s, es, Vs);
+    for (int k = 0; k < 3; ++k) {
+        fc[k] = std::sqrt(std::max(ec[k], 0.0));                  // Sigma_c^{1/2}
+        fs[k] = 1.0 / std::sqrt(std::max(es[k], 1e-10));          // Sigma_s^{-1/2}, eigenvalues clamped below at 1e-10
+    }
+    sym_apply(Vc, fc, Rc);
+    sym_apply(Vs, fs, Rs);
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            double acc = 0.0;
+            for (int k = 0; k < 3; ++k) acc += Rc[i * 3 + k] * Rs[k * 3 + j];
+            A[i * 3 + j] = acc;
+        }
+    for (int i = 0; i < 3; ++i) b[i] = mean_c[i] - (A[i * 3] * mean_s[0] + A[i * 3 + 1] * mean_s[1] + A[i * 3 + 2] * mean_s[2]);
+    return NST_OK;
+}
+
+int nst_color_affine(nst_ctx* ctx, const float* src, int h, int w, const double* A, const double* b, float* dst, void* stream) {
+    NSTCHK(bind(ctx));
+    if (!src || !dst || !A || !b || h < 1 || w < 1) return fail(ctx, NST_E_ARG, "bad argument");
+    ColorAffine a{};
+    for (int i = 0; i < 9; ++i) a.m[i / 3][i % 3] = A[i];
+    for (int i = 0; i < 3; ++i) a.b[i] = b[i];
+    HIPCHK(ctx, launch_color_affine(src, (size_t)h * w, a, dst, static_cast<hipStream_t>(stream)));
+    return NST_OK;
+}
+
+int nst_luminance(nst_ctx* ctx, const float* hwc, int h, int w, double alpha, double beta, float* out, void* stream) {
+    NSTCHK(bind(ctx));
+    if (!hwc || !out || h < 1 || w < 1) return fail(ctx, NST_E_ARG, "bad argument");
+    HIPCHK(ctx, launch_luminance(hwc, (size_t)h * w, alpha, beta, out, static_cast<hipStream_t>(stream)));
+    return NST_OK;
+}
+
+int nst_luminance_recombine(nst_ctx* ctx, const float* u, const float* content, int h, int w, float* out, void* stream) {
+    NSTCHK(bind(ctx));
+    if (!u || !content || !out || h < 1 || w < 1) return fail(ctx, NST_E_ARG, "bad argument");
+    static const ColorAffine inv = yiq_inverse();
+    HIPCHK(ctx, launch_luminance_recombine(u, content, (size_t)h * w, inv, out, static_cast<hipStream_t>(stream)));
+    return NST_OK;
+}
+
 // ---- internal accessors for nst_opt.cpp (not part of the public ABI) --------------------------------
 int nst_internal_device(const nst_ctx* ctx) { return ctx ? ctx->device : 0; }
 int nst_internal_levels(const nst_ctx* ctx) { return ctx ? ctx->levels : 0; }
+int nst_internal_channels(const nst_ctx* ctx) { return ctx ? ctx->channels : 3; }
 size_t nst_internal_pixels(const nst_ctx* ctx) { return (ctx && ctx->levels > 0) ? (size_t)ctx->lv[0].h * ctx->lv[0].w : 0; }
 int nst_internal_fail(nst_ctx* ctx, int code, const char* msg) { return fail(ctx, code, msg ? msg : ""); }
 void nst_internal_poison(void* p, size_t bytes) { poison_if_asked(p, bytes); }

@@ -127,14 +127,16 @@ hipError_t launch_absmax_slots(const float* x, size_t n, unsigned* slots, hipStr
 // conv_first.hip: conv1_1 (3 -> 64) forward from the planar image, and its input gradient
 // wk: [28][64] (k = c*9 + ky*3 + kx, row 27 zero); bias [64]; out NHWC 64, ReLU applied.
 // bits_out (nullable): ReLU bit-mask of the output, [H*W][2] words; amax_out (nullable): NST_AMAX_SLOTS words
-// receiving the absmax of the output (atomic max)
+// receiving the absmax of the output (atomic max).  channels = 1 (luminance mode): x is one plane u (1,H,W) and the
+// convolution sees x_c = u - mean_c (bitwise the channels = 3 result at that planar image)
 hipError_t launch_conv1_1_fwd(const float* x, int H, int W, const float* wk, const float* bias, float* out,
-                              unsigned* bits_out, unsigned* amax_out, hipStream_t stream);
+                              unsigned* bits_out, unsigned* amax_out, hipStream_t stream, int channels = 3);
 // g: [H][W][64] gradient w.r.t. the pre-ReLU conv1_1 output; wd: [9][64][4] flipped taps
 // (wd[t][co][c] = W[co][c][2-ky][2-kx], c = 3 unused 0); gx planar (3,H,W), overwritten.
-// amax_g: the absmax slots of g (the matrix-pipe form), or null (fp32 on the VALU)
+// amax_g: the absmax slots of g (the matrix-pipe form), or null (fp32 on the VALU).  channels = 1 (luminance mode):
+// gx is one plane, the sum over c of the three (added in fp32, (c0 + c1) + c2)
 hipError_t launch_conv1_1_dgrad(const float* g, int H, int W, const float* wd, const unsigned* amax_g, float* gx,
-                                hipStream_t stream);
+                                hipStream_t stream, int channels = 3);
 
 // pixel_ops.hip ---------------------------------------------------------------------------------
 // 2x2/2 max pool (floor) over NHWC, C % 4 == 0
@@ -240,6 +242,18 @@ hipError_t launch_blend_weight(const float* content, int h, int w, int C, double
 hipError_t launch_blend_init(const float* content, const float* noise, const double* weight, size_t n, float* out,
                              hipStream_t stream);
 hipError_t launch_scale(const float* src, float alpha, size_t n, float* dst, hipStream_t stream);
+// colour preservation (nst_job_set_color): fp64 statistics of an HWC RGB image - per-block partial sums, reduced in a
+// fixed order; mean3 / cov9 are DEVICE doubles (population covariance, row-major); scratch: COLOR_BLOCKS * 9 doubles
+constexpr int COLOR_BLOCKS = 256;
+hipError_t launch_color_stats(const float* hwc, size_t pixels, double* scratch, double* mean3, double* cov9, hipStream_t stream);
+struct ColorAffine { double m[3][3]; double b[3]; };
+// out_c = (float)(sum_d m[c][d] p_d + b[c]) per pixel, fp64 arithmetic (HWC -> HWC, in place allowed)
+hipError_t launch_color_affine(const float* src, size_t pixels, const ColorAffine& a, float* dst, hipStream_t stream);
+// out (1,h,w) = (float)(255 (alpha Y(p) + beta)), Y = 0.299 R + 0.587 G + 0.114 B
+hipError_t launch_luminance(const float* hwc, size_t pixels, double alpha, double beta, float* out, hipStream_t stream);
+// out HWC = YIQ^-1 (u / 255, I(content), Q(content)); yiq_inv: the fp64 inverse of the YIQ matrix
+hipError_t launch_luminance_recombine(const float* u, const float* content_hwc, size_t pixels, const ColorAffine& yiq_inv,
+                                      float* out, hipStream_t stream);
 
 // vector_ops.hip: optimiser arithmetic over the n pixel floats ---------------------------------------
 constexpr int RED_BLOCKS = 256;

@@ -22,6 +22,7 @@ using namespace nst;
 extern "C" int nst_internal_device(const nst_ctx* ctx);
 extern "C" int nst_internal_levels(const nst_ctx* ctx);
 extern "C" size_t nst_internal_pixels(const nst_ctx* ctx);
+extern "C" int nst_internal_channels(const nst_ctx* ctx);     // 3, or 1 under NST_COLOR_LUMINANCE
 extern "C" int nst_internal_fail(nst_ctx* ctx, int code, const char* msg);
 extern "C" void nst_internal_poison(void* p, size_t bytes);
 extern "C" int nst_internal_zero_now(void* p, size_t bytes);      // a zero fill that has RUN when it returns (nst_api.cpp)
@@ -31,7 +32,8 @@ extern "C" void nst_internal_mark(nst_ctx* ctx, void* stream);
 struct nst_opt {
     nst_ctx* ctx = nullptr;
     int kind = 0;
-    size_t n = 0;
+    size_t n = 0;                // channels * pixels of level 0
+    int channels = 3;            // the context's channel count when the optimiser was created
     int levels = 0;
     double lr = 10.0;            // python float in the reference
     int total_closures = 0;
@@ -464,7 +466,8 @@ int nst_opt_create(nst_ctx* ctx, int kind, float lr_start, int lbfgs_max_eval, n
     if (!o) return nst_internal_fail(ctx, NST_E_NOMEM, "out of host memory");
     o->ctx = ctx; o->kind = kind; o->lr = (double)lr_start;
     o->levels = nst_internal_levels(ctx);
-    o->n = 3 * nst_internal_pixels(ctx);
+    o->channels = nst_internal_channels(ctx);
+    o->n = (size_t)o->channels * nst_internal_pixels(ctx);
     o->max_eval = lbfgs_max_eval < 1 ? 1 : lbfgs_max_eval;
     const size_t row = (size_t)NST_LOSS_ROW * o->levels + 1;
     // gradient and loss row live in ONE allocation (gradient padded to 64 floats): the sharded closure all-reduces both
@@ -681,6 +684,8 @@ int nst_opt_step(nst_opt* o, float* x, float cw, float sw, float tvw, float* los
                  nst_step_info* info, void* stream) {
     if (!o || !x || !info) return nst_internal_fail(o ? o->ctx : nullptr, NST_E_ARG, "null argument");
     if (hipSetDevice(nst_internal_device(o->ctx)) != hipSuccess) return nst_internal_fail(o->ctx, NST_E_HIP, "hipSetDevice failed");
+    if (o->channels != nst_internal_channels(o->ctx))
+        return nst_internal_fail(o->ctx, NST_E_STATE, "the optimiser was created under the other colour mode (nst_job_set_color)");
     hipStream_t s = static_cast<hipStream_t>(stream);
     // a step issued on another stream than the previous one is ordered behind it (one tail event then covers the optimiser)
     if (o->tail_set && s != o->tail_stream) OHIP(o, hipStreamWaitEvent(s, o->tail, 0));

@@ -55,13 +55,30 @@ def noise_map(eng: StyleEngine, style_top: torch.Tensor, shape: Tuple[int, int, 
 
 def initial_image(eng: StyleEngine, init_method: str, content: torch.Tensor, style: torch.Tensor,
                   content_top: torch.Tensor, style_top: torch.Tensor, top_level: int, noise_factor, noise_levels,
-                  central, peripheral, dispersion):
-    """(device HWC float32 initial image, tag) - reference :265-362."""
+                  central, peripheral, dispersion, style_init=None):
+    """(device HWC float32 initial image, tag) - reference :265-362.  `style_init`: the "style" initial image as given
+    (the recoloured top style level of preserve_color="histogram") instead of `style` resized."""
     noise = noise_map(eng, style_top, tuple(content_top.shape), noise_levels, central, peripheral, dispersion)
     if init_method == "random":
         return eng.scale(noise, 0.5), "random"
     if init_method == "content+noise":
         return eng.noise_blend(content_top, noise, float(noise_factor)), "content"
+    if style_init is not None:
+        return style_init, "style"
     h, w = style.shape[:2]
     nh, nw = host_image.level_size(h, w, top_level)
     return eng.resize(style, nh, nw), "style"
+
+
+# ---- colour preservation (Gatys et al. 2016): statistics always from the top pyramid level, the geometry the job
+# optimises; the same transform then applies to every level
+def recolor_histogram(eng: StyleEngine, content_top: torch.Tensor, style_levels: Sequence[torch.Tensor]) -> List[torch.Tensor]:
+    """preserve_color="histogram": every style level through A p + b, the affine map that gives the top style level the
+    top content level's pixel mean and covariance."""
+    A, b = eng.color_transfer_matrix(eng.color_stats(content_top), eng.color_stats(style_levels[0]))
+    return [eng.color_affine(s, A, b) for s in style_levels]
+
+
+def luminance_params(eng: StyleEngine, content_top: torch.Tensor, style_top: torch.Tensor):
+    """preserve_color="luminance": (alpha, beta) of the style luminance targets 255 (alpha Y + beta)."""
+    return host_image.luminance_params(eng.color_stats(content_top), eng.color_stats(style_top))

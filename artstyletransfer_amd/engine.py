@@ -79,6 +79,7 @@ class StyleEngine:
         self.levels = 0
         self.shape = None
         self.taps = DEFAULT_TAPS                 # (content index, style indices, use_relu): set_taps
+        self.channels = 3                        # 1 under set_color("luminance")
 
     def close(self):
         if getattr(self, "ctx", None):
@@ -111,6 +112,24 @@ class StyleEngine:
         if self.taps != DEFAULT_TAPS:
             self.set_taps(*DEFAULT_TAPS)
 
+    def set_color(self, mode) -> None:
+        """Channel count of the optimised image (nst_job_set_color): "rgb" (or None) = prepared RGB (1,3,H,W), "luminance"
+        = one plane u = 255 Y (1,1,H,W) that the network sees as u - mean_c.  Drops the targets of every configured
+        level: call set_targets again."""
+        if mode not in (None, "rgb", "luminance"):
+            raise ValueError(f"colour mode must be 'rgb' or 'luminance', not {mode!r}")
+        lum = mode == "luminance"
+        try:
+            _lib.check(self.ctx, self.lib.nst_job_set_color(self.ctx, _lib.NST_COLOR_LUMINANCE if lum else _lib.NST_COLOR_RGB),
+                       "nst_job_set_color")
+        finally:                                 # the context's mode, whether the call succeeded or not
+            self.channels = 1 if self.lib.nst_job_color(self.ctx) == _lib.NST_COLOR_LUMINANCE else 3
+
+    def reset_color(self) -> None:
+        """Back to RGB, if the colour mode was changed."""
+        if self.channels != 3:
+            self.set_color("rgb")
+
     def release_job(self) -> None:
         """Give the job's pyramid workspace back (4.7 GB at L=2) and keep the context with its uploaded weights: what an
         engine waiting in neural_nets' pool holds is the smallest job nst_job_configure accepts."""
@@ -122,9 +141,12 @@ class StyleEngine:
 
     def set_targets(self, level: int, content: torch.Tensor, style: torch.Tensor) -> None:
         h, w = self.level_shape(level)
-        content = content.contiguous().reshape(3, h, w)
+        ch = self.channels
+        if content.numel() != ch * h * w or style.numel() != ch * style.shape[-2] * style.shape[-1]:
+            raise NstError(f"targets must have {ch} channel(s) in this colour mode")
+        content = content.contiguous().reshape(ch, h, w)
         _chk_dev(content, self.device)
-        style = style.contiguous().reshape(3, style.shape[-2], style.shape[-1])
+        style = style.contiguous().reshape(ch, style.shape[-2], style.shape[-1])
         _chk_dev(style, self.device)
         _lib.check(self.ctx, self.lib.nst_level_set_targets(self.ctx, level, _ptr(content), _ptr(style),
                                                             style.shape[1], style.shape[2], _stream(self.device)),
@@ -132,13 +154,16 @@ class StyleEngine:
 
     def closure(self, x: torch.Tensor, cw: float, sw: float, tvw: float,
                 grad: Optional[torch.Tensor] = None, losses: Optional[torch.Tensor] = None):
-        """Asynchronous on the current stream. Returns (grad (3,H,W), losses (4*levels+1,)) device tensors."""
+        """Asynchronous on the current stream. Returns (grad (C,H,W), losses (4*levels+1,)) device tensors (C = 3, or 1
+        in luminance mode)."""
         H, W = self.shape
         _chk_dev(x, self.device)
-        if x.numel() != 3 * H * W:
+        if x.numel() != self.channels * H * W:
             raise NstError("x has the wrong number of elements")
         if grad is None:
-            grad = torch.empty((1, 3, H, W), dtype=torch.float32, device=self.device)
+            grad = torch.empty((1, self.channels, H, W), dtype=torch.float32, device=self.device)
+        elif grad.numel() != self.channels * H * W:
+            raise NstError("grad has the wrong number of elements")
         if losses is None:
             losses = torch.empty(NST_LOSS_ROW * self.levels + 1, dtype=torch.float32, device=self.device)
         _lib.check(self.ctx, self.lib.nst_closure(self.ctx, _ptr(x), cw, sw, tvw, _ptr(grad), _ptr(losses),
@@ -150,8 +175,12 @@ class StyleEngine:
         """The closure restricted to the levels in `mask` (level sharding); see nst_closure_levels."""
         H, W = self.shape
         _chk_dev(x, self.device)
+        if x.numel() != self.channels * H * W:
+            raise NstError("x has the wrong number of elements")
         if grad is None:
-            grad = torch.empty((1, 3, H, W), dtype=torch.float32, device=self.device)
+            grad = torch.empty((1, self.channels, H, W), dtype=torch.float32, device=self.device)
+        elif grad.numel() != self.channels * H * W:
+            raise NstError("grad has the wrong number of elements")
         if losses is None:
             losses = torch.empty(NST_LOSS_ROW * self.levels + 1, dtype=torch.float32, device=self.device)
         _lib.check(self.ctx, self.lib.nst_closure_levels(self.ctx, _ptr(x), cw, sw, tvw, mask, _ptr(grad),
@@ -301,9 +330,9 @@ class StyleEngine:
         return t
 
     def level_image(self, level: int) -> torch.Tensor:
-        """The (1,3,h,w) image of pyramid level `level` >= 1 that the last closure evaluated (nst_level_image)."""
+        """The (1,C,h,w) image of pyramid level `level` >= 1 that the last closure evaluated (nst_level_image)."""
         h, w = self.level_shape(level)
-        t = torch.empty((1, 3, h, w), dtype=torch.float32, device=self.device)
+        t = torch.empty((1, self.channels, h, w), dtype=torch.float32, device=self.device)
         _lib.check(self.ctx, self.lib.nst_level_image(self.ctx, level, _ptr(t), _stream(self.device)), "nst_level_image")
         return t
 
@@ -414,6 +443,61 @@ class StyleEngine:
                                                 _stream(self.device)), "nst_scale")
         return out
 
+    # ---- colour preservation set-up (Gatys et al. 2016; host_image.py restates these in fp64) ----
+    def color_stats(self, hwc: torch.Tensor):
+        """(mean (3,), population covariance (3,3)) float64 numpy of an (h,w,3) device image (nst_color_stats; synchronous)."""
+        _chk_dev(hwc, self.device)
+        h, w, c = hwc.shape
+        if c != 3:
+            raise NstError("expected an (h,w,3) image")
+        mean, cov = np.zeros(3), np.zeros(9)
+        _lib.check(self.ctx, self.lib.nst_color_stats(self.ctx, _ptr(hwc), h, w, mean.ctypes.data_as(C.POINTER(C.c_double)),
+                                                      cov.ctypes.data_as(C.POINTER(C.c_double)), _stream(self.device)),
+                   "nst_color_stats")
+        return mean, cov.reshape(3, 3)
+
+    def color_transfer_matrix(self, stats_c, stats_s):
+        """(A (3,3), b (3,)) float64 of nst_color_transfer_matrix: A p + b carries the style statistics to the content's."""
+        dp = C.POINTER(C.c_double)
+        args = [np.ascontiguousarray(a, dtype=np.float64) for a in (stats_c[0], stats_c[1], stats_s[0], stats_s[1])]
+        A, b = np.zeros(9), np.zeros(3)
+        _lib.check(None, self.lib.nst_color_transfer_matrix(*[a.ctypes.data_as(dp) for a in args], A.ctypes.data_as(dp),
+                                                            b.ctypes.data_as(dp)), "nst_color_transfer_matrix")
+        return A.reshape(3, 3), b
+
+    def color_affine(self, hwc: torch.Tensor, A, b) -> torch.Tensor:
+        """A p + b per pixel of an (h,w,3) device image (nst_color_affine)."""
+        _chk_dev(hwc, self.device)
+        h, w, _ = hwc.shape
+        dp = C.POINTER(C.c_double)
+        A = np.ascontiguousarray(A, dtype=np.float64).reshape(9)
+        b = np.ascontiguousarray(b, dtype=np.float64).reshape(3)
+        out = torch.empty_like(hwc)
+        _lib.check(self.ctx, self.lib.nst_color_affine(self.ctx, _ptr(hwc), h, w, A.ctypes.data_as(dp), b.ctypes.data_as(dp),
+                                                       _ptr(out), _stream(self.device)), "nst_color_affine")
+        return out
+
+    def luminance(self, hwc: torch.Tensor, alpha: float = 1.0, beta: float = 0.0) -> torch.Tensor:
+        """(1,1,h,w) 255 (alpha Y + beta) of an (h,w,3) device image (nst_luminance)."""
+        _chk_dev(hwc, self.device)
+        h, w, _ = hwc.shape
+        out = torch.empty((1, 1, h, w), dtype=torch.float32, device=self.device)
+        _lib.check(self.ctx, self.lib.nst_luminance(self.ctx, _ptr(hwc), h, w, float(alpha), float(beta), _ptr(out),
+                                                    _stream(self.device)), "nst_luminance")
+        return out
+
+    def luminance_recombine(self, u: torch.Tensor, content: torch.Tensor) -> torch.Tensor:
+        """(h,w,3) YIQ^-1 (u / 255, I(content), Q(content)) (nst_luminance_recombine)."""
+        _chk_dev(u, self.device)
+        _chk_dev(content, self.device)
+        h, w, _ = content.shape
+        if u.numel() != h * w:
+            raise NstError("u and content differ in size")
+        out = torch.empty((h, w, 3), dtype=torch.float32, device=self.device)
+        _lib.check(self.ctx, self.lib.nst_luminance_recombine(self.ctx, _ptr(u), _ptr(content), h, w, _ptr(out),
+                                                              _stream(self.device)), "nst_luminance_recombine")
+        return out
+
 
 class PixelOptimizer:
     """nst_opt: torch.optim.Adam / LBFGS as the reference constructs them, driving the closure."""
@@ -431,6 +515,7 @@ class PixelOptimizer:
         _lib.check(engine.ctx, engine.lib.nst_opt_create(engine.ctx, kind, lr_start, lbfgs_max_eval, C.byref(h)),
                    "nst_opt_create")
         self.h = h
+        self.channels = engine.channels
         self.row = NST_LOSS_ROW * engine.levels + 1
         self.cap = 32 if name == "lbfgs" else 1
         self._rows = np.zeros((self.cap, self.row), dtype=np.float32)
@@ -456,7 +541,7 @@ class PixelOptimizer:
         from . import sharding
         e = self.engine
         H, W = e.shape
-        self._g = torch.zeros((1, 3, H, W), dtype=torch.float32, device=e.device)
+        self._g = torch.zeros((1, self.channels, H, W), dtype=torch.float32, device=e.device)
         self._l = torch.zeros(self.row, dtype=torch.float32, device=e.device)
 
         def hook(_user):
@@ -490,6 +575,8 @@ class PixelOptimizer:
         contents = list(content_t) if isinstance(content_t, (list, tuple)) else [content_t]
         styles = list(style_t) if isinstance(style_t, (list, tuple)) else [style_t]
         e = self.engine
+        if e.channels != 3:
+            raise NstError("the stripe closure implements RGB only (set_color('rgb'))")
         H, W = e.shape
         nstriped = min(len(contents), len(styles), e.levels)
         plans, stripes = [], []

@@ -18,6 +18,8 @@ import torch
 import torch.nn.functional as F
 from scipy.ndimage import correlate1d
 
+from .color_modes import PRESERVE_COLOR_MODES, check_preserve_color  # noqa: F401  (the job API's choices)
+
 BASE_DIAMETER = 256   # neural_style_transfer.py:213
 
 
@@ -139,3 +141,64 @@ def initial_image(init_method: str, content_img: np.ndarray, style_img: np.ndarr
         base = resize_to_level(content_img, top_level)
         return ((1.0 - weight) * base + weight * noise).astype(np.float32), "content"
     return resize_to_level(style_img, top_level), "style"
+
+
+# ---- colour preservation (Gatys, Bethge, Hertzmann & Shechtman, "Preserving Color in Neural Artistic Style Transfer",
+# 2016): the fp64 restatement of image_ops.hip's set-up kernels (nst_color_stats, nst_color_transfer_matrix,
+# nst_color_affine, nst_luminance, nst_luminance_recombine); images HWC float RGB in [0,1]
+LUMA = np.array([0.299, 0.587, 0.114])
+YIQ = np.array([[0.299, 0.587, 0.114],
+                [0.595716, -0.274453, -0.321263],
+                [0.211456, -0.522591, 0.311135]])
+YIQ_INV = np.linalg.inv(YIQ)
+
+
+def color_stats(img: np.ndarray):
+    """(mean (3,), population covariance (3,3)) of the pixels of an HWC RGB image, fp64."""
+    p = np.asarray(img, dtype=np.float64).reshape(-1, 3)
+    mu = p.mean(axis=0)
+    d = p - mu
+    return mu, d.T @ d / p.shape[0]
+
+
+def color_transfer_matrix(stats_c, stats_s):
+    """(A, b) with A = Sigma_c^{1/2} Sigma_s^{-1/2} (symmetric square roots; style eigenvalues clamped below at 1e-10) and
+    b = mu_c - A mu_s: A p + b has the content's mean and covariance."""
+    (mu_c, cov_c), (mu_s, cov_s) = stats_c, stats_s
+    ec, vc = np.linalg.eigh(np.asarray(cov_c, dtype=np.float64))
+    es, vs = np.linalg.eigh(np.asarray(cov_s, dtype=np.float64))
+    root_c = (vc * np.sqrt(np.maximum(ec, 0.0))) @ vc.T
+    inv_root_s = (vs / np.sqrt(np.maximum(es, 1e-10))) @ vs.T
+    A = root_c @ inv_root_s
+    return A, np.asarray(mu_c, dtype=np.float64) - A @ np.asarray(mu_s, dtype=np.float64)
+
+
+def color_affine(img: np.ndarray, A: np.ndarray, b: np.ndarray) -> np.ndarray:
+    """Every pixel p -> A p + b (fp64, stored float32, not clipped)."""
+    p = np.asarray(img, dtype=np.float64)
+    return (p @ np.asarray(A, dtype=np.float64).T + b).astype(np.float32)
+
+
+def luminance_params(stats_c, stats_s):
+    """(alpha, beta) matching the style's luminance mean and deviation to the content's: alpha = sigma_Yc / sigma_Ys
+    (0 for a flat style, sigma_Ys < 1e-12), beta = mu_Yc - alpha mu_Ys."""
+    (mu_c, cov_c), (mu_s, cov_s) = stats_c, stats_s
+    m_c, m_s = float(LUMA @ mu_c), float(LUMA @ mu_s)
+    s_c = float(np.sqrt(max(LUMA @ cov_c @ LUMA, 0.0)))
+    s_s = float(np.sqrt(max(LUMA @ cov_s @ LUMA, 0.0)))
+    alpha = s_c / s_s if s_s >= 1e-12 else 0.0
+    return alpha, m_c - alpha * m_s
+
+
+def luminance(img: np.ndarray, alpha: float = 1.0, beta: float = 0.0) -> np.ndarray:
+    """(1,h,w) float32 255 (alpha Y + beta), Y = 0.299 R + 0.587 G + 0.114 B."""
+    y = np.asarray(img, dtype=np.float64) @ LUMA
+    return (255.0 * (alpha * y + beta)).astype(np.float32)[None]
+
+
+def luminance_recombine(u: np.ndarray, content: np.ndarray) -> np.ndarray:
+    """HWC float32 YIQ^-1 (u / 255, I(content), Q(content)), not clipped: the RGB image of a luminance job."""
+    c = np.asarray(content, dtype=np.float64)
+    yiq = c @ YIQ.T
+    yiq[..., 0] = np.asarray(u, dtype=np.float64).reshape(c.shape[:2]) / 255.0
+    return (yiq @ YIQ_INV.T).astype(np.float32)

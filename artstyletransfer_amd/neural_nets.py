@@ -114,7 +114,7 @@ def lease_engine(device) -> StyleEngine:
 
 
 def return_engine(eng: StyleEngine) -> None:
-    """Back to the per-GPU pool, with the default taps: the next job must not inherit this one's."""
+    """Back to the per-GPU pool, with the default taps and RGB: the next job must not inherit this one's."""
     if getattr(eng, "ctx", None) is None:
         return
     idx = eng.device.index
@@ -125,6 +125,7 @@ def return_engine(eng: StyleEngine) -> None:
         try:
             eng.release_job()                  # the workspace goes back now, only the weights stay resident
             eng.reset_taps()
+            eng.reset_color()
         except Exception:
             keep = False
     if keep:

@@ -111,9 +111,10 @@ class _DeviceJob:
     otherwise plain asyncio, so the hand-over and tear-down ordering can be tested with a fake in its place
     (`_make_job`, tests/test_host_api.py)."""
 
-    def __init__(self, device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, taps=None):
+    def __init__(self, device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, taps=None, color=None):
         self.dev = dev = device
         self.optimizer = None
+        self.luminance = color == "luminance"   # the optimised image is u = 255 Y; the yield puts the content's I, Q back
         self.engine = lease_engine(dev)
         h0, w0 = init_img.shape[:2]
         # Every job runs on a HIP stream of its own: the jobs that share a GPU (`config.simultaneous_tasks_count`
@@ -132,15 +133,30 @@ class _DeviceJob:
                     return engine.prepare_img(img.to(dev).contiguous())
                 return prepare_img(img, dev)
 
+            def on_device(img):
+                if isinstance(img, torch.Tensor):
+                    return img.to(dev).contiguous()
+                return torch.from_numpy(np.ascontiguousarray(img, dtype=np.float32)).to(dev)
+
             with torch.cuda.stream(self.job_stream):
                 engine.configure(len(content_imgs), h0, w0)
                 if taps is not None:                # (content index, style indices, use_relu), normalised
                     engine.set_taps(*taps)
+                if self.luminance:
+                    # luminance-only transfer: content targets 255 Y(content), style targets 255 (alpha Y(style) + beta)
+                    # with the style luminance matched to the content's (statistics of the top level), u0 = 255 Y(init)
+                    engine.set_color("luminance")
+                    self.content_top = on_device(content_imgs[0])
+                    alpha, beta = device_image.luminance_params(engine, self.content_top, on_device(style_imgs[0]))
+                    content_t = lambda img: engine.luminance(on_device(img))                      # noqa: E731
+                    style_t = lambda img: engine.luminance(on_device(img), alpha, beta)           # noqa: E731
+                else:
+                    content_t = style_t = prepared
                 for lvl, (c_img, s_img) in enumerate(zip(content_imgs, style_imgs)):
                     if tuple(c_img.shape[:2]) != engine.level_shape(lvl):
                         raise ValueError(f"content level {lvl} is {tuple(c_img.shape[:2])}, expected {engine.level_shape(lvl)}")
-                    engine.set_targets(lvl, prepared(c_img), prepared(s_img))
-                self.x = prepared(init_img)
+                    engine.set_targets(lvl, content_t(c_img), style_t(s_img))
+                self.x = content_t(init_img) if self.luminance else prepared(init_img)
                 self.optimizer = PixelOptimizer(engine, optimizer_name, lr_start, LBFGS_MAX_EVAL)
             # Per-step yield (reference :207-208): the image is un-prepared into its own device buffer, copied to
             # pinned host memory on a side stream, and the NEXT optimiser step is started before that copy is
@@ -160,7 +176,10 @@ class _DeviceJob:
         after this returns) and start its D2H into host buffer k on the side stream.  Returns a callable that blocks
         until the copy has landed."""
         with torch.cuda.device(self.dev), torch.cuda.stream(self.job_stream):
-            snap = self.engine.unprepare_img(self.x)
+            if self.luminance:
+                snap = self.engine.luminance_recombine(self.x, self.content_top)
+            else:
+                snap = self.engine.unprepare_img(self.x)
             ready = torch.cuda.Event()
             ready.record()
             with torch.cuda.stream(self.copy_stream):
@@ -185,8 +204,8 @@ class _DeviceJob:
         return_engine(self.engine)             # back to the per-GPU pool: the next job re-uses its uploaded weights
 
 
-def _make_job(device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, taps=None):
-    return _DeviceJob(device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, taps)
+def _make_job(device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, taps=None, color=None):
+    return _DeviceJob(device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, taps, color)
 
 
 async def _drain(step_future):
@@ -218,6 +237,7 @@ class NeuralStyleTransfer:
         self.__style_imgs = style_imgs
         self.__optimizer_name = optimizer_name
         self.__taps = None                       # None: the reference's feature maps
+        self.__color = None                      # set_preserve_color
 
     def set_feature_maps(self, content_layer=None, style_layers=None, use_relu=True):
         """Extension: the feature maps the losses of the next `process` read - a content map and a set of style maps of
@@ -227,6 +247,16 @@ class NeuralStyleTransfer:
         content, style = _taps.normalize_taps(content_layer, style_layers, use_relu)
         self.__taps = None if _taps.is_default(content, style, use_relu) else (content, style, use_relu)
 
+    def set_preserve_color(self, mode=None):
+        """Extension: keep the content image's colours (Gatys, Bethge, Hertzmann & Shechtman 2016) in the next `process`.
+        None: the reference's behaviour.  "luminance": the job optimises the luminance u = 255 Y only, against the content
+        luminance and the style luminance matched to the content's mean and deviation; every yielded image is
+        YIQ^-1 (u / 255, I, Q of content level 0).  "histogram": `process` recolours the style levels with the affine map
+        that gives the top style level the top content level's pixel mean and covariance, then runs the RGB job
+        (neural_style_transfer() recolours before it builds the initial image and hands the recoloured levels over).
+        ValueError for any other value."""
+        self.__color = host_image.check_preserve_color(mode)
+
     async def process(self, content_imgs, init_img, lr_start, iters_num, content_weight, style_weight, tv_weight,
                       init_img_name):
         # validates the model name exactly as the reference does (ValueError for anything but vgg19)
@@ -235,11 +265,18 @@ class NeuralStyleTransfer:
             raise RuntimeError("Unknown optimizer")
         if self.__device.type != "cuda":
             raise RuntimeError("the HIP style-transfer engine needs a GPU; no CPU path exists")
-        if self.__taps is None:
-            job = _make_job(self.__device, self.__optimizer_name, self.__style_imgs, content_imgs, init_img, lr_start)
-        else:
-            job = _make_job(self.__device, self.__optimizer_name, self.__style_imgs, content_imgs, init_img, lr_start,
-                            taps=self.__taps)
+        style_imgs = self.__style_imgs
+        if self.__color == "histogram":
+            setup = shared_engine(self.__device)
+            up = [s if isinstance(s, torch.Tensor) else device_image.upload(setup, s) for s in (content_imgs[0], *style_imgs)]
+            style_imgs = device_image.recolor_histogram(setup, up[0].to(self.__device).contiguous(),
+                                                        [s.to(self.__device).contiguous() for s in up[1:]])
+        extra = {}
+        if self.__taps is not None:
+            extra["taps"] = self.__taps
+        if self.__color == "luminance":
+            extra["color"] = "luminance"
+        job = _make_job(self.__device, self.__optimizer_name, style_imgs, content_imgs, init_img, lr_start, **extra)
         cw, sw, tvw = float(content_weight), float(style_weight), float(tv_weight)
         loop = asyncio.get_running_loop()
 
@@ -294,12 +331,15 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
                                 optimizer, model, init_method,
                                 iters_num, levels_num, noise_factor, noise_levels, noise_levels_central_amplitude,
                                 noise_levels_peripheral_amplitude, noise_levels_dispersion, device=None, *,
-                                content_layer=None, style_layers=None, use_relu=True):
+                                content_layer=None, style_layers=None, use_relu=True, preserve_color=None):
     """Async generator yielding (percent, HWC float32 image) after every optimiser step
     (reference :229-372). `device` (extension): the GPU to run on; default = current.  `content_layer`,
     `style_layers`, `use_relu` (extension): the feature maps the losses read, see NeuralStyleTransfer.set_feature_maps
-    (None: the reference's).  They are validated before any GPU work."""
+    (None: the reference's).  `preserve_color` (extension): None, "luminance" or "histogram", see
+    NeuralStyleTransfer.set_preserve_color; under "histogram" the style levels are recoloured once, here, and the noise
+    map and the "style" initial image are built from the recoloured ones.  They are validated before any GPU work."""
     taps = _taps.normalize_taps(content_layer, style_layers, use_relu)
+    host_image.check_preserve_color(preserve_color)
     if device is None:
         if not torch.cuda.is_available():
             raise RuntimeError("no GPU visible: the HIP style-transfer engine has no CPU path")
@@ -313,15 +353,20 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
     style_dev = device_image.upload(setup, content_n_style.style[1])
     content_levels = device_image.pyramid(setup, content_dev, levels_num)
     style_levels = device_image.pyramid(setup, style_dev, levels_num)
+    style_init = None
+    if preserve_color == "histogram":
+        style_levels = device_image.recolor_histogram(setup, content_levels[0], style_levels)
+        style_init = style_levels[0]
     level = max(levels_num - 1, 0)
     init_img, tag = device_image.initial_image(
         setup, init_method, content_dev, style_dev, content_levels[0], style_levels[0], level,
         noise_factor, noise_levels, noise_levels_central_amplitude, noise_levels_peripheral_amplitude,
-        noise_levels_dispersion)
+        noise_levels_dispersion, style_init=style_init)
     init_name = {"random": "random", "content": content_n_style.content[0], "style": content_n_style.style[0]}[tag]
 
     nst = NeuralStyleTransfer(device, model, style_levels, optimizer)
     nst.set_feature_maps(*taps, use_relu=use_relu)
+    nst.set_preserve_color("luminance" if preserve_color == "luminance" else None)   # (histogram: recoloured above)
     lr_start = 10.0
     async for img, cur_iter in nst.process(content_levels, init_img, lr_start, iters_num, content_weight,
                                            style_weight, tv_weight, init_name):

@@ -62,8 +62,9 @@ class Task:
 
     async def __do_job(self):
         cfg = self.__config
-        # the keyword-only feature-map fields of Config, passed on when set (a config without them is the reference's)
-        taps = {k: getattr(cfg, k) for k, dflt in (("content_layer", None), ("style_layers", None), ("use_relu", True))
+        # the keyword-only feature-map and colour fields of Config, passed on when set (a config without them is the reference's)
+        extensions = {k: getattr(cfg, k) for k, dflt in (("content_layer", None), ("style_layers", None), ("use_relu", True),
+                                                   ("preserve_color", None))
                 if getattr(cfg, k, dflt) is not dflt}
         gpu = await self.__slots.acquire()
         self.gpu = gpu
@@ -72,7 +73,7 @@ class Task:
                     self.__content_n_style, cfg.content_weight, cfg.style_weight, cfg.tv_weight, cfg.optimizer,
                     cfg.model, cfg.init_method, cfg.iters_num, cfg.levels_num, cfg.noise_factor, cfg.noise_levels,
                     cfg.noise_levels_central_amplitude, cfg.noise_levels_peripheral_amplitude,
-                    cfg.noise_levels_dispersion, device=torch.device("cuda", gpu), **taps):
+                    cfg.noise_levels_dispersion, device=torch.device("cuda", gpu), **extensions):
                 await self.__report(self.__task_id, (percent, img.copy()))
         finally:
             self.__slots.release(gpu)

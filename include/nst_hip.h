@@ -123,15 +123,34 @@ int nst_job_configure(nst_ctx* ctx, int levels_num, int H0, int W0);
  * returns NST_E_STATE under any other. */
 int nst_job_set_taps(nst_ctx* ctx, int content_index, unsigned style_mask, int use_relu);
 
+/* Colour preservation, luminance-only transfer (Gatys, Bethge, Hertzmann & Shechtman, "Preserving Color in Neural
+ * Artistic Style Transfer", 2016): the channel count of the optimised image, a setting of the context like the taps.
+ *   NST_COLOR_RGB (a new context's): images are prepared RGB (3,h,w).
+ *   NST_COLOR_LUMINANCE: the optimised image is ONE plane u = 255 Y (1,H0,W0) that the network sees as the prepared
+ *     image E(u)_c = u - mean_c (mean = IMAGENET_MEAN_255).  The loss is the RGB closure at E(u) (the bicubic 1/2 chain of
+ *     u, then E, per level; TV taken on u, which equals TV(E(u))), the gradient is the sum over c of d loss / d x_c.
+ *     nst_level_set_targets takes (1,h,w) / (1,hs,ws) prepared luminance images, nst_closure(_levels) a (1,H0,W0) x and
+ *     grad, nst_level_image writes (1,h_l,w_l); nst_opt_create sizes its vectors by the channel count, and a step of an
+ *     optimiser created under the other mode returns NST_E_STATE.  The stripe closure (nst_window_*) returns
+ *     NST_E_STATE; nst_vgg_features* stay RGB.
+ * Setting the mode (even the same one) waits for the context's work, re-sizes the level image buffers and drops every
+ * level's targets and any captured closure graph.  It composes with any taps, every conv mode and schedule.
+ * nst_job_color returns the current mode. */
+#define NST_COLOR_RGB 0
+#define NST_COLOR_LUMINANCE 1
+int nst_job_set_color(nst_ctx* ctx, int mode);
+int nst_job_color(const nst_ctx* ctx);
+
 /* LossBuilder.__init__ (neural_style_transfer.py:68-82): target content representation
  * ReLU(conv4_2) of the content image and the 5 target Gram matrices of the style image of one
- * level (of the maps nst_job_set_taps chose, when it was called).  content: device (3,h,w) of that level's size; style: device (3,hs,ws), any size. */
+ * level (of the maps nst_job_set_taps chose, when it was called).  content: device (3,h,w) of that level's size; style: device (3,hs,ws), any size.
+ * (1,h,w) / (1,hs,ws) prepared luminance images under NST_COLOR_LUMINANCE (nst_job_set_color). */
 int nst_level_set_targets(nst_ctx* ctx, int level, const float* content, const float* style,
                           int hs, int ws, void* stream);
 
 /* optimizer_step_callback without its LR decay and prints (neural_style_transfer.py:152-199) =
  * sum over levels of LossBuilder.build (:84-112) on the bicubic 1/2 chain of x (:170-176),
- * then backward (:193).  x, grad: device (3,H0,W0).  losses: device, NST_LOSS_ROW*levels+1
+ * then backward (:193).  x, grad: device (3,H0,W0) ((1,H0,W0) under NST_COLOR_LUMINANCE).  losses: device, NST_LOSS_ROW*levels+1
  * floats = per level (total, content, style, tv) unweighted components as the reference
  * prints them, then the grand total.  Asynchronous on `stream`. */
 int nst_closure(nst_ctx* ctx, const float* x, float content_weight, float style_weight,
@@ -271,6 +290,25 @@ int nst_noise_blend(nst_ctx* ctx, const float* content, const float* noise, int 
 /* dst = alpha * src (init_method 'random': 0.5 * noise, :351) */
 int nst_scale(nst_ctx* ctx, const float* src, float alpha, size_t n, float* dst, void* stream);
 
+/* ---- colour preservation set-up (Gatys et al. 2016; nst_job_set_color) ------------------------------------------
+ * Images are HWC float32 RGB in [0,1].  YIQ (NTSC): Y = 0.299 R + 0.587 G + 0.114 B, I = 0.595716 R - 0.274453 G
+ * - 0.321263 B, Q = 0.211456 R - 0.522591 G + 0.311135 B; its inverse is the fp64 inverse of that matrix.
+ * nst_color_stats: per-channel mean (3) and population covariance (3x3, row-major) over all pixels, fp64, to HOST memory
+ *   (a device reduction with fp64 partials in a fixed order).  Synchronous.
+ * nst_color_transfer_matrix (host only): A = Sigma_c^{1/2} Sigma_s^{-1/2} (symmetric square roots by a Jacobi eigen-
+ *   decomposition in fp64; style eigenvalues clamped below at 1e-10), b = mu_c - A mu_s.  Host pointers; A row-major.
+ * nst_color_affine: dst = A p + b per pixel (fp64 arithmetic, stored fp32, not clipped); A, b HOST doubles; in place allowed.
+ * nst_luminance: out (1,h,w) = 255 (alpha Y(p) + beta) - the luminance image u of an RGB image (alpha = 1, beta = 0) or of
+ *   a style image matched to the content's luminance mean and deviation.
+ * nst_luminance_recombine: out HWC = YIQ^-1 (u / 255, I(content), Q(content)), not clipped: the RGB image of a luminance
+ *   job (in place of nst_unprepare_img). */
+int nst_color_stats(nst_ctx* ctx, const float* hwc, int h, int w, double* mean, double* cov, void* stream);
+int nst_color_transfer_matrix(const double* mean_c, const double* cov_c, const double* mean_s, const double* cov_s, double* A,
+                              double* b);
+int nst_color_affine(nst_ctx* ctx, const float* src, int h, int w, const double* A, const double* b, float* dst, void* stream);
+int nst_luminance(nst_ctx* ctx, const float* hwc, int h, int w, double alpha, double beta, float* out, void* stream);
+int nst_luminance_recombine(nst_ctx* ctx, const float* u, const float* content, int h, int w, float* out, void* stream);
+
 /* ---- spatial sharding of one pyramid level: a context evaluates a horizontal STRIPE of a larger image ------------
  * (SURVEY 8(e) partition B with halo recompute.  There is no counterpart in the reference; the quantities are those of
  * neural_style_transfer.py:84-112 restricted to the rows a rank owns.)
@@ -288,7 +326,7 @@ int nst_scale(nst_ctx* ctx, const float* src, float alpha, size_t n, float* dst,
  *     the caller adds the stripes' gradients into the full image (overlap-add, one all-reduce).  losses[0..3] = (total,
  *     content, style, tv) of the level, losses[4] = total - identical on every rank.
  * Nothing else may run on the context between begin and end.  The stripe closure implements the default feature maps
- * only: after nst_job_set_taps with any other taps both calls return NST_E_STATE. */
+ * only: after nst_job_set_taps with any other taps both calls return NST_E_STATE, as they do under NST_COLOR_LUMINANCE. */
 int nst_window_sums_count(size_t* count);
 int nst_window_begin(nst_ctx* ctx, const float* xs, int row0, int rows, int H0, float* sums, void* stream);
 int nst_window_end(nst_ctx* ctx, const float* xs, int row0, int rows, int H0, float content_weight, float style_weight,
