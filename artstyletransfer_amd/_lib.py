@@ -68,6 +68,8 @@ SYMBOLS = {
     "nst_opt_shard_levels": (C.c_int, [c_void, C.c_uint, c_void, c_void, c_void, c_void]),
     "nst_opt_shard_levels_comm": (C.c_int, [c_void, C.c_uint, c_void]),
     "nst_opt_history": (C.c_int, [c_void, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "nst_opt_set_closure_reuse": (C.c_int, [c_void, C.c_int]),
+    "nst_opt_closure_stats": (C.c_int, [c_void, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     "nst_comm_unique_id": (C.c_int, [c_void]),
     "nst_comm_create": (C.c_int, [C.c_int, C.c_int, C.c_int, c_void, C.POINTER(c_void)]),
     "nst_comm_destroy": (None, [c_void]),

@@ -153,6 +153,9 @@ struct nst_ctx {
     int levels = 0;
     Taps taps;                  // nst_job_set_taps
     int channels = 3;           // nst_job_set_color: 3 = RGB, 1 = luminance (the optimised image is u = 255 Y)
+    // bumped on entry to every call that changes what a closure computes (configure, taps, colour, targets), failure paths
+    // included: an optimiser's remembered closure result is valid only under the epoch it was made in (nst_opt.cpp)
+    unsigned long long closure_epoch = 0;
     double* color_scratch = nullptr;   // nst_color_stats: COLOR_BLOCKS * 9 partials | mean (3) | cov (9), made on first use
     LevelWs lv[NST_MAX_LEVELS];
     hipEvent_t fork = nullptr;
@@ -1286,6 +1289,7 @@ int nst_ctx_bytes(const nst_ctx* ctx, size_t* bytes) {
 }
 
 int nst_job_configure(nst_ctx* ctx, int levels_num, int H0, int W0) {
+    if (ctx) ++ctx->closure_epoch;
     NSTCHK(bind(ctx));
     if (levels_num < 1 || levels_num > NST_MAX_LEVELS) return fail(ctx, NST_E_ARG, "levels_num out of range");
     if ((H0 >> (levels_num - 1)) < 16 || (W0 >> (levels_num - 1)) < 16)
@@ -1317,6 +1321,7 @@ int nst_job_configure(nst_ctx* ctx, int levels_num, int H0, int W0) {
 // LossBuilder(content_feature_maps_index, style_feature_maps_indices, ...) and Vgg19(use_relu=...) of the reference
 // (neural_style_transfer.py:41-82, neural_nets.py:17-28) as a context setting
 int nst_job_set_taps(nst_ctx* ctx, int content_index, unsigned style_mask, int use_relu) {
+    if (ctx) ++ctx->closure_epoch;
     NSTCHK(bind(ctx));
     if (content_index < 0 || content_index > 5) return fail(ctx, NST_E_ARG, "content_index must be 0 .. 5");
     if (style_mask == 0u || (style_mask & ~0x3Fu) != 0u)
@@ -1347,6 +1352,7 @@ int nst_job_set_taps(nst_ctx* ctx, int content_index, unsigned style_mask, int u
 // Gatys et al. 2016, luminance-only transfer: the optimised image becomes one plane u = 255 Y (channels = 1) that the
 // network sees as x_c = u - mean_c.  Same life cycle as the taps: every level's targets and the captured closure go.
 int nst_job_set_color(nst_ctx* ctx, int mode) {
+    if (ctx) ++ctx->closure_epoch;
     NSTCHK(bind(ctx));
     if (mode != NST_COLOR_RGB && mode != NST_COLOR_LUMINANCE) return fail(ctx, NST_E_ARG, "mode must be NST_COLOR_RGB or NST_COLOR_LUMINANCE");
     const int channels = mode == NST_COLOR_LUMINANCE ? 1 : 3;
@@ -1388,6 +1394,7 @@ int nst_job_color(const nst_ctx* ctx) { return ctx ? (ctx->channels == 1 ? NST_C
 static bool batch_eligible(const nst_ctx* ctx);
 int nst_level_set_targets(nst_ctx* ctx, int level, const float* content, const float* style, int hs, int ws,
                           void* stream) {
+    if (ctx) ++ctx->closure_epoch;
     NSTCHK(bind(ctx));
     if (level < 0 || level >= ctx->levels) return fail(ctx, NST_E_STATE, "level not configured");
     if (!content || !style) return fail(ctx, NST_E_ARG, "null image");
@@ -2116,6 +2123,7 @@ size_t nst_internal_pixels(const nst_ctx* ctx) { return (ctx && ctx->levels > 0)
 int nst_internal_fail(nst_ctx* ctx, int code, const char* msg) { return fail(ctx, code, msg ? msg : ""); }
 void nst_internal_poison(void* p, size_t bytes) { poison_if_asked(p, bytes); }
 int nst_internal_lbfgs_gram(const nst_ctx* ctx) { return ctx ? ctx->lbfgs_gram : 1; }
+unsigned long long nst_internal_closure_epoch(const nst_ctx* ctx) { return ctx ? ctx->closure_epoch : 0; }
 void nst_internal_mark(nst_ctx* ctx, void* stream) { mark(ctx, static_cast<hipStream_t>(stream)); }
 
 }  // extern "C"

@@ -261,6 +261,9 @@ constexpr int RED_BLOCKS = 256;
 hipError_t launch_dot(const float* a, const float* b, size_t n, double* scratch, float* out, hipStream_t stream);
 // out[0] = max|a|, out[1] = sum|a|
 hipError_t launch_absmax_abssum(const float* a, size_t n, double* scratch, float* out, hipStream_t stream);
+// out[0] (32-bit word, read back as an unsigned) = how many of the n elements of a and b differ in their bit patterns.
+// scratch: RED_BLOCKS doubles (stream order lets it share the scratch of launch_absmax_abssum in one launch sequence)
+hipError_t launch_count_diff(const float* a, const float* b, size_t n, double* scratch, float* out, hipStream_t stream);
 // y = alpha * x + beta * y'  variants
 hipError_t launch_dot_partial(const float* a, const float* b, size_t n, double* scratch, hipStream_t stream);   // RED_BLOCKS partials
 // one history pair of the L-BFGS two-loop recursion on the device (see vector_ops.hip)

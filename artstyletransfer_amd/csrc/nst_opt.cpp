@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -28,6 +29,22 @@ extern "C" void nst_internal_poison(void* p, size_t bytes);
 extern "C" int nst_internal_zero_now(void* p, size_t bytes);      // a zero fill that has RUN when it returns (nst_api.cpp)
 extern "C" int nst_internal_lbfgs_gram(const nst_ctx* ctx);
 extern "C" void nst_internal_mark(nst_ctx* ctx, void* stream);
+extern "C" unsigned long long nst_internal_closure_epoch(const nst_ctx* ctx);
+
+// What L-BFGS knows about the point P its last step left in x (and, bitwise, in xinit).  The closure is bitwise
+// reproducible, so while x still equals P and nothing the closure depends on has changed, the next step's first
+// closure is the one already made at P: it is served from here instead of evaluated.
+struct ClosureMemo {
+    bool valid = false;
+    bool have_abs = false;       // gmax, gsum known (else taken from g in the compare's launch sequence)
+    bool have_dir = false;       // d, gtd, d_norm, d_sum were formed from g(P) under the current history; g(P) is then in
+                                 // prev_g (the trial's gradient is in g), else in g
+    float gmax = 0.f, gsum = 0.f;
+    float gtd = 0.f, d_norm = 0.f, d_sum = 0.f;
+    float w[3] = {0.f, 0.f, 0.f};          // cw, sw, tvw (compared bitwise)
+    unsigned long long epoch = 0;          // nst_internal_closure_epoch when P was evaluated
+    std::vector<float> row;                // P's loss row
+};
 
 struct nst_opt {
     nst_ctx* ctx = nullptr;
@@ -85,6 +102,10 @@ struct nst_opt {
     size_t pack_floats = 0;
     // per-step outputs
     std::vector<float> loss_rows;   // host copy of every closure's loss rows in this step
+    // L-BFGS closure reuse (env NST_CLOSURE_REUSE, default on; nst_opt_set_closure_reuse)
+    bool reuse = true;
+    ClosureMemo memo;
+    long served = 0;             // closures served from the memo (counted in total_closures like evaluated ones)
 };
 
 namespace {
@@ -202,15 +223,17 @@ double cubic_interpolate(double x1, double f1, double g1, double x2, double f2, 
     return (xmin + xmax) / 2.0;
 }
 
-struct LsResult { double t; float f; int evals; };
+struct LsResult { double t; float f; int evals; double last_t; };   // last_t: the step length evaluated last
 
 // torch:optim/lbfgs.py:40-209.  Gradients of bracket points are never needed by the caller with
 // max_iter == 1 (only f, g.d and t are consumed), so no gradient clones are kept.
 int strong_wolfe(nst_opt* o, float* x, double t, float f, float gtd, float d_norm, int max_ls, float cw, float sw,
                  float tvw, hipStream_t s, LsResult* res) {
     const double c1 = 1e-4, c2 = 0.9, tol_change = 1e-9;
+    double last_t = t;
     auto eval_at = [&](double tt, float* f_new, float* gtd_new) -> int {
         // x = x_init + t*d ; closure ; (x restored by the caller at the end)
+        last_t = tt;
         OHIP(o, launch_add_scaled(o->xinit, (float)tt, o->d, x, o->n, s));
         GradStats gs;
         gs.dot_with = o->d;
@@ -284,7 +307,7 @@ int strong_wolfe(nst_opt* o, float* x, double t, float f, float gtd, float d_nor
             br[low] = t; br_f[low] = f_new; br_gtd[low] = gtd_new;
         }
     }
-    res->t = br[low]; res->f = br_f[low]; res->evals = evals;
+    res->t = br[low]; res->f = br_f[low]; res->evals = evals; res->last_t = last_t;
     return NST_OK;
 }
 
@@ -349,16 +372,42 @@ int gram_direction(nst_opt* o, bool new_pair, hipStream_t s) {
     return NST_OK;
 }
 
-int lbfgs_step(nst_opt* o, float* x, float cw, float sw, float tvw, hipStream_t s, nst_step_info* info) {
-    const double lr = o->lr;                                     // read before the closure decays it (lbfgs.py:349)
-    float loss;
-    GradStats g0;
-    g0.want_abs = true;
-    OCHK(eval_closure(o, x, cw, sw, tvw, s, &loss, &g0));
-    info->loss = loss;
-    const float gmax = g0.gmax, gsum = g0.gsum;
-    if (gmax <= 1e-7f) { info->accepted = 0; info->t = 0.f; return NST_OK; }
-    o->n_iter += 1;
+// the memo applies while this optimiser evaluates whole closures itself: reuse on, no level sharding, no reduce hook (a
+// rank-local decision to skip a closure would leave the other ranks in a collective alone)
+bool memo_applies(const nst_opt* o) {
+    const unsigned all = o->levels >= 32 ? 0xFFFFFFFFu : (1u << o->levels) - 1u;
+    return o->reuse && !o->comm && !o->hook && (o->level_mask & all) == all;
+}
+
+// The first closure of an L-BFGS step, served from a valid memo if x is bitwise its P under the same weights and context
+// epoch: one compare of x with xinit (plus max|g|, sum|g| when the memo lacks them) and one synchronisation.  A served
+// closure decays lr, counts and appends its row exactly as eval_closure would.
+int serve_closure(nst_opt* o, const float* x, float cw, float sw, float tvw, unsigned long long epoch, hipStream_t s,
+                  bool* served) {
+    *served = false;
+    ClosureMemo& M = o->memo;
+    const float w[3] = {cw, sw, tvw};
+    if (std::memcmp(M.w, w, sizeof(w)) != 0 || M.epoch != epoch) return NST_OK;
+    float* r = o->pinned;
+    OHIP(o, launch_count_diff(x, o->xinit, o->n, o->scratch, o->scal + 3, s));
+    if (!M.have_abs) OHIP(o, launch_absmax_abssum(o->g, o->n, o->scratch, o->scal, s));     // g(P) is in g
+    OHIP(o, hipMemcpyAsync(r, o->scal, 4 * sizeof(float), hipMemcpyDeviceToHost, s));
+    OHIP(o, hipStreamSynchronize(s));
+    unsigned diff;
+    std::memcpy(&diff, r + 3, sizeof(diff));
+    if (diff != 0) return NST_OK;
+    if (!M.have_abs) { M.gmax = r[0]; M.gsum = r[1]; M.have_abs = true; }
+    o->lr *= 0.999;                                                          // neural_style_transfer.py:155-158
+    o->loss_rows.insert(o->loss_rows.end(), M.row.begin(), M.row.end());
+    o->total_closures += 1;                                                  // :198
+    o->served += 1;
+    *served = true;
+    return NST_OK;
+}
+
+// the start of an L-BFGS step after its first closure (g in o->g, lbfgs.py:396-488): the curvature pair, the direction d,
+// prev_g = g, the first step length t, and g.d, max|d|, sum|d|
+int form_direction(nst_opt* o, double lr, float gsum, hipStream_t s, double* t, float* gtd, float* d_norm, float* d_sum) {
     if (o->n_iter == 1) {
         OHIP(o, launch_scale_copy(-1.f, o->g, o->d, o->n, s));   // d = -g
         for (float* p : o->old_dirs) o->spare.push_back(p);
@@ -429,18 +478,69 @@ int lbfgs_step(nst_opt* o, float* x, float cw, float sw, float tvw, hipStream_t 
     }
     OHIP(o, launch_copy(o->g, o->prev_g, o->n, s));
     o->have_prev = true;
-    double t;
     if (o->n_iter == 1) {
         const float inv = 1.0f / gsum;
-        t = (inv < 1.0f) ? (double)(inv * (float)lr) : lr;       // min(1., 1./|g|_1) * lr
+        *t = (inv < 1.0f) ? (double)(inv * (float)lr) : lr;      // min(1., 1./|g|_1) * lr
     } else {
-        t = lr;
+        *t = lr;
     }
+    OCHK(dot_and_absstats(o, o->g, o->d, s, gtd, d_norm, d_sum));
+    return NST_OK;
+}
+
+int lbfgs_step(nst_opt* o, float* x, float cw, float sw, float tvw, hipStream_t s, nst_step_info* info) {
+    const double lr = o->lr;                                     // read before the closure decays it (lbfgs.py:349)
+    const bool memo_on = memo_applies(o);
+    const unsigned long long epoch = nst_internal_closure_epoch(o->ctx);
+    ClosureMemo& M = o->memo;
+    const bool memo_valid = M.valid;
+    M.valid = false;                                             // until this step has completed
+    bool served = false;
+    if (memo_on && memo_valid) OCHK(serve_closure(o, x, cw, sw, tvw, epoch, s, &served));
+    // a step that left x where it began (no accepted trial) and had formed its direction: then g(P) = prev_g, the pair
+    // y = g(P) - prev_g = 0 is dropped, and history, H_diag, d, g.d, max|d|, sum|d| are bitwise that step's
+    const bool reuse_dir = served && M.have_dir;
+    float loss, gmax, gsum;
+    if (served) {
+        loss = M.row.back(); gmax = M.gmax; gsum = M.gsum;
+    } else {
+        GradStats g0;
+        g0.want_abs = true;
+        OCHK(eval_closure(o, x, cw, sw, tvw, s, &loss, &g0));
+        gmax = g0.gmax; gsum = g0.gsum;
+    }
+    info->loss = loss;
+    const size_t row = (size_t)NST_LOSS_ROW * o->levels + 1;
+    // memo of the point x holds when this step returns; xinit must hold it too (copied unless the compare showed it)
+    auto remember = [&](bool have_dir, bool have_abs, const float* prow, bool copy_x) -> int {
+        if (copy_x) OHIP(o, launch_copy(x, o->xinit, o->n, s));
+        M.have_dir = have_dir; M.have_abs = have_abs;
+        M.gmax = gmax; M.gsum = gsum;
+        M.w[0] = cw; M.w[1] = sw; M.w[2] = tvw;
+        M.epoch = epoch;
+        M.row.assign(prow, prow + row);
+        M.valid = true;
+        return NST_OK;
+    };
+    if (gmax <= 1e-7f) {
+        info->accepted = 0; info->t = 0.f;
+        if (memo_on) OCHK(remember(false, true, o->loss_rows.data(), !served));      // g(P) is in g
+        return NST_OK;
+    }
+    o->n_iter += 1;
+    double t;
     float gtd, d_norm, d_sum;
-    OCHK(dot_and_absstats(o, o->g, o->d, s, &gtd, &d_norm, &d_sum));
+    if (reuse_dir) {
+        gtd = M.gtd; d_norm = M.d_norm; d_sum = M.d_sum;
+        t = lr;                                                  // n_iter >= 2
+    } else {
+        OCHK(form_direction(o, lr, gsum, s, &t, &gtd, &d_norm, &d_sum));
+    }
     info->accepted = 0; info->t = 0.f;
-    if (!(gtd > -1e-9f)) {
-        OHIP(o, launch_copy(x, o->xinit, o->n, s));
+    const bool ran_ls = !(gtd > -1e-9f);
+    bool moved = false, g_at_x = false;
+    if (ran_ls) {
+        if (!served) OHIP(o, launch_copy(x, o->xinit, o->n, s));     // (served: the compare found x == xinit)
         LsResult r;
         OCHK(strong_wolfe(o, x, t, loss, gtd, d_norm, o->max_eval - 1, cw, sw, tvw, s, &r));
         t = r.t;
@@ -448,8 +548,20 @@ int lbfgs_step(nst_opt* o, float* x, float cw, float sw, float tvw, hipStream_t 
         else OHIP(o, launch_copy(o->xinit, x, o->n, s));
         info->accepted = (t != 0.0) ? 1 : 0;
         info->t = (float)t;
+        moved = t != 0.0;
+        g_at_x = moved && r.last_t == t;                         // the last closure was at the point taken: its g is in g
     }
     o->t = t;
+    if (memo_on) {
+        if (!moved) {
+            // x is still P, and the direction formed here stays valid while the next step drops its pair.  A rejected trial
+            // restored x from xinit; a step that skipped the line search left xinit as it was
+            M.gtd = gtd; M.d_norm = d_norm; M.d_sum = d_sum;
+            OCHK(remember(true, true, o->loss_rows.data(), !served && !ran_ls));
+        } else if (g_at_x) {
+            OCHK(remember(false, false, o->loss_rows.data() + o->loss_rows.size() - row, true));
+        }
+    }
     return NST_OK;
 }
 
@@ -469,6 +581,8 @@ int nst_opt_create(nst_ctx* ctx, int kind, float lr_start, int lbfgs_max_eval, n
     o->channels = nst_internal_channels(ctx);
     o->n = (size_t)o->channels * nst_internal_pixels(ctx);
     o->max_eval = lbfgs_max_eval < 1 ? 1 : lbfgs_max_eval;
+    const char* reuse_env = std::getenv("NST_CLOSURE_REUSE");
+    o->reuse = !(reuse_env && reuse_env[0] && std::atoi(reuse_env) == 0);
     const size_t row = (size_t)NST_LOSS_ROW * o->levels + 1;
     // gradient and loss row live in ONE allocation (gradient padded to 64 floats): the sharded closure all-reduces both
     // with a single collective (nst_opt_shard_levels_comm)
@@ -545,6 +659,7 @@ int nst_opt_shard_levels(nst_opt* o, unsigned level_mask, float* grad, float* lo
     o->level_mask = level_mask;
     o->hook = hook; o->hook_user = user;
     o->comm = nullptr;
+    o->memo.valid = false;
     o->g = grad ? grad : o->own_g;
     o->losses = losses ? losses : o->own_losses;
     return NST_OK;
@@ -556,6 +671,7 @@ int nst_opt_shard_levels_comm(nst_opt* o, unsigned level_mask, nst_comm* comm) {
     o->hook = nullptr; o->hook_user = nullptr;
     o->comm = comm;
     o->g = o->own_g; o->losses = o->own_losses;
+    o->memo.valid = false;
     return NST_OK;
 }
 
@@ -563,6 +679,20 @@ int nst_opt_history(const nst_opt* o, int* pairs, int* n_iter) {
     if (!o) return nst_internal_fail(nullptr, NST_E_ARG, "null optimiser");
     if (pairs) *pairs = (int)o->old_dirs.size();
     if (n_iter) *n_iter = o->kind == NST_OPT_ADAM ? o->k : o->n_iter;
+    return NST_OK;
+}
+
+int nst_opt_set_closure_reuse(nst_opt* o, int enabled) {
+    if (!o) return nst_internal_fail(nullptr, NST_E_ARG, "null optimiser");
+    o->reuse = enabled != 0;
+    o->memo.valid = false;
+    return NST_OK;
+}
+
+int nst_opt_closure_stats(const nst_opt* o, long* evaluated, long* served) {
+    if (!o) return nst_internal_fail(nullptr, NST_E_ARG, "null optimiser");
+    if (evaluated) *evaluated = (long)o->total_closures - o->served;
+    if (served) *served = o->served;
     return NST_OK;
 }
 

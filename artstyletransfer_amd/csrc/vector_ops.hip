@@ -308,6 +308,49 @@ hipError_t launch_absmax_abssum(const float* a, size_t n, double* scratch, float
     return hipGetLastError();
 }
 
+// ---- bitwise compare: how many of the n 32-bit patterns of a and b differ (so NaN == NaN of the same payload and
+// -0 != +0).  Fixed grid, integer counts: the result does not depend on the order of the reduction. --------------------
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+__global__ __launch_bounds__(256) void count_diff_partial_kernel(const unsigned* __restrict__ a, const unsigned* __restrict__ b,
+                                                                 size_t n, double* __restrict__ scratch) {
+    __shared__ double sh[4];
+    const size_t n4 = n / 4;
+    const u32x4* av = reinterpret_cast<const u32x4*>(a);
+    const u32x4* bv = reinterpret_cast<const u32x4*>(b);
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned c = 0;
+    // four 16-byte pairs in flight per lane: 256 workgroups x 4 waves cannot cover HBM latency one load at a time
+    constexpr int U = 4;
+    for (; i + (U - 1) * stride < n4; i += U * stride) {
+        u32x4 x[U], y[U];
+#pragma unroll
+        for (int k = 0; k < U; ++k) { x[k] = av[i + k * stride]; y[k] = bv[i + k * stride]; }
+#pragma unroll
+        for (int k = 0; k < U; ++k)
+            c += (x[k][0] != y[k][0]) + (x[k][1] != y[k][1]) + (x[k][2] != y[k][2]) + (x[k][3] != y[k][3]);
+    }
+    for (; i < n4; i += stride) {
+        const u32x4 x = av[i], y = bv[i];
+        c += (x[0] != y[0]) + (x[1] != y[1]) + (x[2] != y[2]) + (x[3] != y[3]);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        for (size_t k = n4 * 4; k < n; ++k) c += a[k] != b[k];
+    const double r = vblock_sum((double)c, sh);
+    if (threadIdx.x == 0) scratch[blockIdx.x] = r;
+}
+__global__ __launch_bounds__(256) void count_diff_finish_kernel(const double* __restrict__ scratch, unsigned* __restrict__ out) {
+    __shared__ double sh[4];
+    const double r = vblock_sum(threadIdx.x < RED_BLOCKS ? scratch[threadIdx.x] : 0.0, sh);
+    if (threadIdx.x == 0) out[0] = r < 4294967295.0 ? (unsigned)r : 0xFFFFFFFFu;
+}
+hipError_t launch_count_diff(const float* a, const float* b, size_t n, double* scratch, float* out, hipStream_t stream) {
+    hipLaunchKernelGGL(count_diff_partial_kernel, dim3(RED_BLOCKS), dim3(256), 0, stream, reinterpret_cast<const unsigned*>(a),
+                       reinterpret_cast<const unsigned*>(b), n, scratch);
+    hipLaunchKernelGGL(count_diff_finish_kernel, dim3(1), dim3(256), 0, stream, scratch, reinterpret_cast<unsigned*>(out));
+    return hipGetLastError();
+}
+
 // ---- axpy family ----------------------------------------------------------------------------------
 __global__ void axpy_kernel(float alpha, const float* __restrict__ x, float* __restrict__ y, size_t n) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)

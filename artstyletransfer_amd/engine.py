@@ -535,6 +535,19 @@ class PixelOptimizer:
         _lib.check(self.engine.ctx, self.engine.lib.nst_opt_history(self.h, C.byref(p), C.byref(n)), "nst_opt_history")
         return p.value, n.value
 
+    def set_closure_reuse(self, enabled: bool) -> None:
+        """L-BFGS: serve a step's first closure from the previous step when x is bitwise the image that step left
+        (nst_opt_set_closure_reuse; default on, env NST_CLOSURE_REUSE=0 off).  Results are the same either way."""
+        _lib.check(self.engine.ctx, self.engine.lib.nst_opt_set_closure_reuse(self.h, int(bool(enabled))),
+                   "nst_opt_set_closure_reuse")
+
+    def closure_stats(self):
+        """(closures evaluated, closures served) so far."""
+        ev, sv = C.c_long(), C.c_long()
+        _lib.check(self.engine.ctx, self.engine.lib.nst_opt_closure_stats(self.h, C.byref(ev), C.byref(sv)),
+                   "nst_opt_closure_stats")
+        return ev.value, sv.value
+
     def shard_levels(self, rank: int, world: int, dist_mod=None, group=None) -> None:
         """Level sharding (BASELINE config 4): this rank evaluates only its levels; after every closure
         the partial gradient and loss rows are all-reduced (RCCL) before the driver reads them."""

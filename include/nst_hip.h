@@ -175,7 +175,8 @@ int nst_opt_create(nst_ctx* ctx, int kind, float lr_start, int lbfgs_max_eval, n
 void nst_opt_destroy(nst_opt* opt);
 
 typedef struct nst_step_info {
-    int closures;        /* closure evaluations made by this step (Adam 1, L-BFGS >= 1) */
+    int closures;        /* closures of this step as the reference's `step` counts them (Adam 1, L-BFGS >= 1), served
+                            ones included (nst_opt_set_closure_reuse) */
     int total_closures;  /* the reference's `step` counter after this call */
     int accepted;        /* L-BFGS: 1 if x moved, 0 if the trial was rejected; Adam: 1 */
     float loss;          /* loss of the FIRST closure of this step (what optimizer.step returns) */
@@ -208,6 +209,17 @@ int nst_opt_shard_levels_comm(nst_opt* opt, unsigned level_mask, nst_comm* comm)
 
 /* curvature pairs currently held by L-BFGS and the optimiser's iteration count (Adam: its step count k) */
 int nst_opt_history(const nst_opt* opt, int* pairs, int* n_iter);
+
+/* L-BFGS closure reuse (default on; env NST_CLOSURE_REUSE=0 at nst_opt_create turns it off).  The closure is bitwise
+ * reproducible, so when a step starts at bitwise the image the previous step left (a rejected or skipped trial, or an
+ * accepted trial whose closure was the last one made), with the same weights and no change to the job in between
+ * (nst_job_configure, nst_job_set_taps, nst_job_set_color, nst_level_set_targets), its first closure is served from what
+ * the optimiser remembers instead of evaluated: same loss row, step counter, lr decay, step info and image.  One
+ * device compare of x decides, so the caller may write x between steps.  Never in the sharded modes; Adam never.
+ * Changing the setting drops what is remembered. */
+int nst_opt_set_closure_reuse(nst_opt* opt, int enabled);
+/* closures this optimiser evaluated and served so far (their sum is nst_step_info.total_closures) */
+int nst_opt_closure_stats(const nst_opt* opt, long* evaluated, long* served);
 
 /* ---- RCCL communicator (one rank per GPU; the reference has no collective: neural_style_transfer.py:236-245).
  * librccl is resolved at run time; without it these return NST_E_STATE.  Bootstrap: rank 0 calls nst_comm_unique_id and
