@@ -21,6 +21,8 @@ NST_OPT_ADAM = 0
 NST_OPT_LBFGS = 1
 NST_COLOR_RGB = 0
 NST_COLOR_LUMINANCE = 1
+NST_POOL_MAX = 0
+NST_POOL_AVG = 1
 
 c_float_p = C.POINTER(C.c_float)
 REDUCE_HOOK = C.CFUNCTYPE(None, C.c_void_p)
@@ -57,6 +59,8 @@ SYMBOLS = {
     "nst_job_set_taps": (C.c_int, [c_void, C.c_int, C.c_uint, C.c_int]),
     "nst_job_set_color": (C.c_int, [c_void, C.c_int]),
     "nst_job_color": (C.c_int, [c_void]),
+    "nst_job_set_pooling": (C.c_int, [c_void, C.c_int]),
+    "nst_job_pooling": (C.c_int, [c_void]),
     "nst_color_stats": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), c_void]),
     "nst_color_transfer_matrix": (C.c_int, [C.POINTER(C.c_double)] * 6),
     "nst_color_affine": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), c_void, c_void]),

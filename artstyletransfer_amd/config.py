@@ -1,5 +1,6 @@
 """Configuration surface of the reference (config.py:1-31): same names, same defaults."""
 from .color_modes import check_preserve_color
+from .pooling_modes import check_pooling
 
 # jobs that may run at once PER GPU (the reference runs everything on device 0; here the
 # scheduler multiplies this by the number of GPUs of the node). Use 1 when levels_num > 2.
@@ -21,13 +22,15 @@ _DEFAULTS = dict(
     noise_levels_dispersion=(0.20, 0.30, 0.40, 0.60, 0.30),
 )
 # extension, keyword-only: the feature maps the losses read (neural_style_transfer(..., content_layer=, style_layers=,
-# use_relu=)); None = the reference's content 4 / style [0, 1, 2, 3, 5]; and colour preservation (preserve_color=).
+# use_relu=)); None = the reference's content 4 / style [0, 1, 2, 3, 5]; colour preservation (preserve_color=); and the
+# pooling of the feature network (pooling=).
 # Not part of the positional order or the repr.
 _KW_ONLY = dict(
     content_layer=None,            # index 0..5 or a name of Vgg19.layer_names
     style_layers=None,             # indices / names
     use_relu=True,                 # False: the reference's Vgg19(use_relu=False) taps
     preserve_color=None,           # None | 'luminance' | 'histogram': keep the content's colours (Gatys et al. 2016)
+    pooling="max",                 # 'max' | 'avg': average instead of max pooling in VGG19 (Gatys et al. 2016, section 2)
 )
 
 
@@ -49,6 +52,7 @@ class Config:
         for name, default in {**_DEFAULTS, **_KW_ONLY}.items():
             setattr(self, name, kwargs.get(name, default))
         check_preserve_color(self.preserve_color)
+        check_pooling(self.pooling)
 
     def __repr__(self):
         return "Config(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in _DEFAULTS) + ")"

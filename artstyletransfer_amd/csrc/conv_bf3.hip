@@ -328,8 +328,10 @@ __device__ __forceinline__ void conv_bf3_body(const ConvParams& p, const int sp,
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int r = 2 * j;
-                    const float mx = fmaxf(fmaxf(acc[mt][nt][r], acc[mt][nt][r + 1]),
-                                           fmaxf(acc[mt][nt][r + 8], acc[mt][nt][r + 9]));
+                    // (nst_job_set_pooling(NST_POOL_AVG): the window's average in the one order every pooling kernel uses)
+                    const float mx = p.pool_avg ? (((acc[mt][nt][r] + acc[mt][nt][r + 1]) + acc[mt][nt][r + 8]) + acc[mt][nt][r + 9]) * 0.25f
+                                                : fmaxf(fmaxf(acc[mt][nt][r], acc[mt][nt][r + 1]),
+                                                        fmaxf(acc[mt][nt][r + 8], acc[mt][nt][r + 9]));
                     const int mcol = (r & 3) + 8 * (r >> 2) + 4 * half;      // column of register r (row 0 of the pair)
                     const int px = (x0 + mcol) >> 1;
                     if (py < PH2 && px < PW2) p.pool_out[((size_t)py * PW2 + px) * p.Cout + co] = mx;
@@ -361,7 +363,7 @@ __global__ __launch_bounds__(512, 2) void conv_bf3_batch_kernel(ConvBatch b) {
     p.H = im.H; p.W = im.W; p.Cin = b.Cin; p.Cout = b.Cout; p.relu = b.relu;
     p.tiles_x = im.tiles_x; p.tiles_y = 0; p.partial = nullptr; p.partial_floats = 0; p.ksplit = 1;
     p.in2 = im.in2; p.Cin2 = b.Cin2; p.wt2_bf = im.wt2_bf; p.bits_out = im.bits_out; p.bits_in = im.bits_in;
-    p.pool_out = im.pool_out;
+    p.pool_out = im.pool_out; p.pool_avg = b.pool_avg;
     conv_bf3_body<TH, BN, NBUF>(p, sp_all - (i ? b.img[i - 1].tile_end : 0), blockIdx.x % n_ct, 0);
 }
 

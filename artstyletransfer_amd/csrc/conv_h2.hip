@@ -761,6 +761,7 @@ __device__ __forceinline__ void conv_h2_body(const Tiles& tiles, const int slot_
         else p = p_loop;
     }
     const int words = p.Cout >> 5;          // ReLU bit-mask words per pixel
+    const bool avg = p.pool_avg != 0;       // nst_job_set_pooling(NST_POOL_AVG): launch-uniform, a scalar select in the pooling code
     float amax = 0.f;
     auto record_amax = [&]() {
         if (p.amax_out) {
@@ -878,17 +879,25 @@ __device__ __forceinline__ void conv_h2_body(const Tiles& tiles, const int slot_
 #pragma unroll
                             for (int nt = 0; nt < NT16; ++nt) {
                                 const float e0 = am16[mt][nt][i], e1 = am16[mt][nt][i + 1], e2 = am16[mt + 1][nt][i], e3 = am16[mt + 1][nt][i + 1];
-                                const float mx = fmaxf(fmaxf(e0, e1), fmaxf(e2, e3));
+                                // (avg: the one summation order of every pooling kernel; code = the four ReLU-on ballots)
+                                const float mx = avg ? (((e0 + e1) + e2) + e3) * 0.25f : fmaxf(fmaxf(e0, e1), fmaxf(e2, e3));
                                 __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, mx), rs_pool, pbase, poff * colB + nt * 64, 0);
                                 if (p.pcode_out) {
-                                    int pos = 0;
-                                    float best = e0;
-                                    if (e1 > best) { best = e1; pos = 1; }
-                                    if (e2 > best) { best = e2; pos = 2; }
-                                    if (e3 > best) { best = e3; pos = 3; }
-                                    const bool live = best > 0.f;
+                                    if (avg) {
+                                        code[nt >> 1][0][nt & 1] = __ballot(e0 > 0.f);
+                                        code[nt >> 1][1][nt & 1] = __ballot(e1 > 0.f);
+                                        code[nt >> 1][2][nt & 1] = __ballot(e2 > 0.f);
+                                        code[nt >> 1][3][nt & 1] = __ballot(e3 > 0.f);
+                                    } else {
+                                        int pos = 0;
+                                        float best = e0;
+                                        if (e1 > best) { best = e1; pos = 1; }
+                                        if (e2 > best) { best = e2; pos = 2; }
+                                        if (e3 > best) { best = e3; pos = 3; }
+                                        const bool live = best > 0.f;
 #pragma unroll
-                                    for (int q = 0; q < 4; ++q) code[nt >> 1][q][nt & 1] = __ballot(live && pos == q);
+                                        for (int q = 0; q < 4; ++q) code[nt >> 1][q][nt & 1] = __ballot(live && pos == q);
+                                    }
                                 }
                             }
                             if (p.pcode_out) {
@@ -954,16 +963,23 @@ __device__ __forceinline__ void conv_h2_body(const Tiles& tiles, const int slot_
 #pragma unroll
                     for (int nt = 0; nt < NT16; ++nt) {
                         const float e0 = am16[mt][nt][i], e1 = am16[mt][nt][i + 1], e2 = am16[mt + 1][nt][i], e3 = am16[mt + 1][nt][i + 1];
-                        const float mx = fmaxf(fmaxf(e0, e1), fmaxf(e2, e3));
+                        const float mx = avg ? (((e0 + e1) + e2) + e3) * 0.25f : fmaxf(fmaxf(e0, e1), fmaxf(e2, e3));
                         if (inw) p.pool_out[((size_t)py * PW2 + px) * p.Cout + cg0 + nt * 16 + l15] = mx;
-                        int pos = 0;
-                        float best = e0;
-                        if (e1 > best) { best = e1; pos = 1; }
-                        if (e2 > best) { best = e2; pos = 2; }
-                        if (e3 > best) { best = e3; pos = 3; }
-                        const bool live = best > 0.f;
+                        if (avg) {
+                            code[nt >> 1][0][nt & 1] = __ballot(e0 > 0.f);
+                            code[nt >> 1][1][nt & 1] = __ballot(e1 > 0.f);
+                            code[nt >> 1][2][nt & 1] = __ballot(e2 > 0.f);
+                            code[nt >> 1][3][nt & 1] = __ballot(e3 > 0.f);
+                        } else {
+                            int pos = 0;
+                            float best = e0;
+                            if (e1 > best) { best = e1; pos = 1; }
+                            if (e2 > best) { best = e2; pos = 2; }
+                            if (e3 > best) { best = e3; pos = 3; }
+                            const bool live = best > 0.f;
 #pragma unroll
-                        for (int q = 0; q < 4; ++q) code[nt >> 1][q][nt & 1] = __ballot(live && pos == q);
+                            for (int q = 0; q < 4; ++q) code[nt >> 1][q][nt & 1] = __ballot(live && pos == q);
+                        }
                     }
                     if (p.pcode_out) {
 #pragma unroll
@@ -1109,8 +1125,9 @@ __device__ __forceinline__ void conv_h2_body(const Tiles& tiles, const int slot_
                         for (int j = 0; j < 4; ++j) {
                             const int r = 2 * j;
                             const int pcol = (j & 1) + 4 * (j >> 1);
-                            const float mx = fmaxf(fmaxf(accm[mt][nt][r], accm[mt][nt][r + 1]),
-                                                   fmaxf(accm[mt][nt][r + 8], accm[mt][nt][r + 9]));
+                            const float mx = avg ? (((accm[mt][nt][r] + accm[mt][nt][r + 1]) + accm[mt][nt][r + 8]) + accm[mt][nt][r + 9]) * 0.25f
+                                                 : fmaxf(fmaxf(accm[mt][nt][r], accm[mt][nt][r + 1]),
+                                                         fmaxf(accm[mt][nt][r + 8], accm[mt][nt][r + 9]));
                             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, mx), rs_pool, pbase,
                                                                   (mt * PW2 + pcol) * colB + nt * 128, 0);
                             if (p.pcode_out) {
@@ -1121,9 +1138,10 @@ __device__ __forceinline__ void conv_h2_body(const Tiles& tiles, const int slot_
                                 if (accm[mt][nt][r + 8] > best) { best = accm[mt][nt][r + 8]; pos = 2; }
                                 if (accm[mt][nt][r + 9] > best) { best = accm[mt][nt][r + 9]; pos = 3; }
                                 const bool live = best > 0.f;
+                                constexpr int roff[4] = {0, 1, 8, 9};
 #pragma unroll
                                 for (int q = 0; q < 4; ++q) {
-                                    const unsigned long long bal = __ballot(live && pos == q);
+                                    const unsigned long long bal = __ballot(avg ? accm[mt][nt][r + roff[q]] > 0.f : (live && pos == q));
                                     __builtin_amdgcn_raw_buffer_store_b32(half ? (unsigned)(bal >> 32) : (unsigned)bal, rs_code, cbase,
                                                                           ((mt * PW2 + pcol) * words + nt) * 16 + q * 4, 0);
                                 }
@@ -1182,8 +1200,9 @@ __device__ __forceinline__ void conv_h2_body(const Tiles& tiles, const int slot_
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int r = 2 * j;
-                    const float mx = fmaxf(fmaxf(accm[mt][nt][r], accm[mt][nt][r + 1]),
-                                           fmaxf(accm[mt][nt][r + 8], accm[mt][nt][r + 9]));
+                    const float mx = avg ? (((accm[mt][nt][r] + accm[mt][nt][r + 1]) + accm[mt][nt][r + 8]) + accm[mt][nt][r + 9]) * 0.25f
+                                         : fmaxf(fmaxf(accm[mt][nt][r], accm[mt][nt][r + 1]),
+                                                 fmaxf(accm[mt][nt][r + 8], accm[mt][nt][r + 9]));
                     const int mcol = (r & 3) + 8 * (r >> 2) + 4 * half;      // column of register r (row 0 of the pair)
                     const int px = (x0 + mcol) >> 1;
                     const bool inw = (py < PH2 && px < PW2);
@@ -1191,16 +1210,19 @@ __device__ __forceinline__ void conv_h2_body(const Tiles& tiles, const int slot_
                     if (p.pcode_out) {
                         // arg-max code for the un-pooling input-gradient loader: one word per window position, bit =
                         // channel & 31, set where that position holds the window's FIRST maximum and it is positive
-                        // (max_pool2d backward + the ReLU mask of the pooled activation)
+                        // (max_pool2d backward + the ReLU mask of the pooled activation).  Average pooling: every position
+                        // whose unit is on - a multi-hot code; the loaders test each position's bit on its own, and the 1/4
+                        // of avg_pool2d's backward rides on the un-pooling launch's accumulator scale
                         int pos = 0;
                         float best = accm[mt][nt][r];
                         if (accm[mt][nt][r + 1] > best) { best = accm[mt][nt][r + 1]; pos = 1; }
                         if (accm[mt][nt][r + 8] > best) { best = accm[mt][nt][r + 8]; pos = 2; }
                         if (accm[mt][nt][r + 9] > best) { best = accm[mt][nt][r + 9]; pos = 3; }
                         const bool live = best > 0.f;
+                        constexpr int roff[4] = {0, 1, 8, 9};
 #pragma unroll
                         for (int q = 0; q < 4; ++q) {
-                            const unsigned long long bal = __ballot(live && pos == q);
+                            const unsigned long long bal = __ballot(avg ? accm[mt][nt][r + roff[q]] > 0.f : (live && pos == q));
                             if (l31 == 0 && inw)
                                 p.pcode_out[(((size_t)py * PW2 + px) * words + cw) * 4 + q] = half ? (unsigned)(bal >> 32) : (unsigned)bal;
                         }
@@ -1276,7 +1298,7 @@ struct H2BatchTiles {
         p.pool_out = im.pool_out;
         p.wt_h2 = b.wt_h2; p.wt_h2_inv = b.wt_h2_inv; p.wt2_f32 = im.wt2_f32;
         p.amax_in = im.amax_in; p.amax_in2 = im.amax_in2; p.amax_w2 = im.amax_w2; p.amax_out = im.amax_out;
-        p.pcode_in = im.pcode_in; p.pcode_out = im.pcode_out;
+        p.pcode_in = im.pcode_in; p.pcode_out = im.pcode_out; p.pool_avg = b.pool_avg;
         p.in2_row0 = im.in2_row0; p.in2_rows = im.in2_rows; p.ty0 = 0;
         sp = sp_all - (i ? b.img[i - 1].tile_end : 0);
         return true;

@@ -480,6 +480,16 @@ __global__ __launch_bounds__(512, 2) void conv_wino_batch_kernel(ConvBatch b) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float e0 = win[0][0][e], e1 = win[0][1][e], e2 = win[1][0][e], e3 = win[1][1][e];
+                if (b.pool_avg) {
+                    // nst_job_set_pooling(NST_POOL_AVG): the window's average in the one order every pooling kernel uses, and
+                    // a multi-hot code - every position whose unit is on (the loaders test each position's bit on its own)
+                    mx[e] = (((e0 + e1) + e2) + e3) * 0.25f;
+                    cn[0] |= (e0 > 0.f ? 1u : 0u) << e;
+                    cn[1] |= (e1 > 0.f ? 1u : 0u) << e;
+                    cn[2] |= (e2 > 0.f ? 1u : 0u) << e;
+                    cn[3] |= (e3 > 0.f ? 1u : 0u) << e;
+                    continue;
+                }
                 mx[e] = fmaxf(fmaxf(e0, e1), fmaxf(e2, e3));
                 int pos = 0;
                 float best = e0;

@@ -49,8 +49,8 @@ struct ActSet {                 // activations of one forward pass, NHWC
     // ids: act[l] -> l; the Gram factor S of style slot q -> NL + q (6 slots); the gradient w.r.t. the pre-ReLU output
     // of layer l (or a bound of it: the pooled gradient it was un-pooled from) -> NL + 6 + l
     unsigned* amax = nullptr;
-    // arg-max codes of the four max-pools, written by the fused pooling of the f16x2 forward launches and read by
-    // the un-pooling loader of the input-gradient launch below each pool: [H/2*W/2][C/32][4] words
+    // arg-max codes of the four max-pools (average pooling: the multi-hot ReLU-on codes), written by the fused pooling of the
+    // f16x2 forward launches and read by the un-pooling loader of the input-gradient launch below each pool: [H/2*W/2][C/32][4] words
     unsigned* pcode[4] = {};
     size_t bytes = 0;
 };
@@ -153,7 +153,8 @@ struct nst_ctx {
     int levels = 0;
     Taps taps;                  // nst_job_set_taps
     int channels = 3;           // nst_job_set_color: 3 = RGB, 1 = luminance (the optimised image is u = 255 Y)
-    // bumped on entry to every call that changes what a closure computes (configure, taps, colour, targets), failure paths
+    int pool_avg = 0;           // nst_job_set_pooling: 1 = the four pools average their windows (include/nst_hip.h has the definition)
+    // bumped on entry to every call that changes what a closure computes (configure, taps, colour, pooling, targets), failure paths
     // included: an optimiser's remembered closure result is valid only under the epoch it was made in (nst_opt.cpp)
     unsigned long long closure_epoch = 0;
     double* color_scratch = nullptr;   // nst_color_stats: COLOR_BLOCKS * 9 partials | mean (3) | cov (9), made on first use
@@ -513,6 +514,7 @@ int forward(nst_ctx* ctx, ActSet& a, const float* x, int h, int w, hipStream_t s
         p.in = in; p.wt = ctx->wf[l]; p.bias = ctx->bias[l]; p.addend = nullptr; p.mask = nullptr; p.out = a.act[l];
         p.H = a.h[l]; p.W = a.w[l]; p.Cin = kCin[l]; p.Cout = kCout[l];
         p.relu = (l == NL - 1 && !ctx->taps.use_relu) ? 0 : 1;      // conv5_1 before its ReLU (use_relu = 0)
+        p.pool_avg = ctx->pool_avg;
         p.partial = a.splitk; p.partial_floats = a.splitk_floats; p.wt_bf = ctx->wf_bf[l];
         if (h2) {
             p.wt_h2 = ctx->wf_h2[l]; p.wt_h2_inv = ctx->wf_h2_inv[l];
@@ -536,7 +538,7 @@ int forward(nst_ctx* ctx, ActSet& a, const float* x, int h, int w, hipStream_t s
                 a.pooled[pa] = true;
             } else {
                 Timer t(ctx, s, K_OTHER, 0);
-                HIPCHK(ctx, launch_maxpool_fwd(a.act[l], a.h[l], a.w[l], kCout[l], a.pool[pa], s));
+                HIPCHK(ctx, (ctx->pool_avg ? launch_avgpool_fwd : launch_maxpool_fwd)(a.act[l], a.h[l], a.w[l], kCout[l], a.pool[pa], s));
             }
         }
     }
@@ -606,13 +608,19 @@ int backward(nst_ctx* ctx, ActSet& a, const Inject* inj, const ContentJob* cj, f
             p.band_rows = ctx->band_rows; p.mfma16 = ctx->mfma16; p.wg256 = ctx->wg256; p.tile_rows = ctx->tile_rows;
         }
         if (pk >= 0) {
+            // (average pooling: the un-pooled gradient is a quarter of the pooled one, so the pooled gradient's absmax would
+            // describe a tensor four times what the next launch reads - that launch's record is taken after the un-pooling)
+            const bool avg = ctx->pool_avg != 0;
+            if (avg) p.amax_out = nullptr;
             {
                 Timer t(ctx, s, K_CONV3, conv_flops(p.H, p.W, p.Cin, p.Cout, 9), p.H, p.W, p.Cin, p.Cout, 9, -l);
                 HIPCHK(ctx, launch_conv3(ctx, p, s));
             }
             // oth = g(pool[pk]); un-pool through act[l-1] with its ReLU mask -> cur
             Timer t(ctx, s, K_OTHER, 0);
-            HIPCHK(ctx, launch_maxpool_bwd_relu(a.act[l - 1], oth, a.h[l - 1], a.w[l - 1], kCout[l - 1], cur, s));
+            HIPCHK(ctx, (avg ? launch_avgpool_bwd_relu : launch_maxpool_bwd_relu)(a.act[l - 1], oth, a.h[l - 1], a.w[l - 1], kCout[l - 1], cur, s));
+            if (avg && h2)
+                HIPCHK(ctx, launch_absmax_slots(cur, (size_t)a.h[l - 1] * a.w[l - 1] * kCout[l - 1], amax_grad(a, l - 1), s));
             // cur now holds g(pre-ReLU of layer l-1); no tap layer sits directly before a pool
         } else {
             const int m = l - 1;   // the layer whose activation this gradient flows into
@@ -737,6 +745,7 @@ int batched_forward(nst_ctx* ctx, const float* const* xi, const int* lv, int n, 
         b.relu = (l == NL - 1 && !ctx->taps.use_relu) ? 0 : 1;
         b.wt_h2 = ctx->wf_h2[l]; b.wt_h2_inv = ctx->wf_h2_inv[l]; b.mfma16 = ctx->mfma16; b.wg256 = ctx->wg256; b.tile_rows = ctx->tile_rows; b.persist = ctx->persist;
         b.wt_wino = ctx->wf_wino[l]; b.wt_wino_inv = ctx->wf_wino_inv[l];
+        b.pool_avg = ctx->pool_avg;
         double flops = 0;
         for (int k = 0; k < n; ++k) {
             ActSet& a = ctx->lv[lv[k]].acts;
@@ -898,6 +907,11 @@ int batched_backward(nst_ctx* ctx, const float* const* xi, float* const* gi, con
         // loader un-pools it through the arg-max code (no un-pool kernel, no full-size gradient round trip)
         const int pl = pool_index_after(l);
         b.unpool = (h2 && pl >= 0) ? 1 : 0;
+        // average pooling: every position whose code bit is on gets a QUARTER of the pooled gradient.  The loader hands the
+        // pooled gradient through as it is (same loads, same selects, a multi-hot code) and the 1/4 rides on the scale the
+        // launch multiplies its accumulators by: exact (a power of two), and the second K source - re-expressed in the main
+        // source's scale through the same factor - comes out unchanged.  The launch records the absmax of what it stores.
+        if (b.unpool && ctx->pool_avg) { b.wt_h2_inv *= 0.25f; b.wt_wino_inv *= 0.25f; }
         b.Cin2 = (pk < 0 && style_q >= 0) ? kCout[m] : 0;
         double flops = 0;
         for (int k = 0; k < n; ++k) {
@@ -932,7 +946,7 @@ int batched_backward(nst_ctx* ctx, const float* const* xi, float* const* gi, con
             ActSet& a = ctx->lv[lv[k]].acts;
             if (pk >= 0 && !h2) {
                 Timer t(ctx, s, K_OTHER, 0);
-                HIPCHK(ctx, launch_maxpool_bwd_relu(a.act[l - 1], oth[k], a.h[l - 1], a.w[l - 1], kCout[l - 1], cur[k], s));
+                HIPCHK(ctx, (ctx->pool_avg ? launch_avgpool_bwd_relu : launch_maxpool_bwd_relu)(a.act[l - 1], oth[k], a.h[l - 1], a.w[l - 1], kCout[l - 1], cur[k], s));
             } else {
                 float* tmp = cur[k]; cur[k] = oth[k]; oth[k] = tmp;
             }
@@ -1391,6 +1405,22 @@ int nst_job_set_color(nst_ctx* ctx, int mode) {
 
 int nst_job_color(const nst_ctx* ctx) { return ctx ? (ctx->channels == 1 ? NST_COLOR_LUMINANCE : NST_COLOR_RGB) : -1; }
 
+// Gatys et al. 2016, section 2: average instead of max pooling in the feature network.  Same life cycle as the taps and the
+// colour mode: every level's targets (made with the other network) and the captured closure go; no buffer changes size.
+int nst_job_set_pooling(nst_ctx* ctx, int mode) {
+    if (ctx) ++ctx->closure_epoch;
+    NSTCHK(bind(ctx));
+    if (mode != NST_POOL_MAX && mode != NST_POOL_AVG) return fail(ctx, NST_E_ARG, "mode must be NST_POOL_MAX or NST_POOL_AVG");
+    quiesce(ctx);
+    if (ctx->gexec) { (void)hipGraphExecDestroy(ctx->gexec); ctx->gexec = nullptr; }
+    ctx->gkey = {}; ctx->glast = {};
+    ctx->pool_avg = mode == NST_POOL_AVG ? 1 : 0;
+    for (int i = 0; i < ctx->levels; ++i) ctx->lv[i].targets = false;
+    return NST_OK;
+}
+
+int nst_job_pooling(const nst_ctx* ctx) { return ctx ? (ctx->pool_avg ? NST_POOL_AVG : NST_POOL_MAX) : -1; }
+
 static bool batch_eligible(const nst_ctx* ctx);
 int nst_level_set_targets(nst_ctx* ctx, int level, const float* content, const float* style, int hs, int ws,
                           void* stream) {
@@ -1628,6 +1658,8 @@ static int window_check(nst_ctx* ctx, const float* xs, int row0, int rows, int H
         return fail(ctx, NST_E_STATE, "the stripe closure implements the default feature maps only (nst_job_set_taps(ctx, 4, 0x2F, 1))");
     if (ctx->channels != 3)
         return fail(ctx, NST_E_STATE, "the stripe closure implements RGB only (nst_job_set_color(ctx, NST_COLOR_RGB))");
+    if (ctx->pool_avg)
+        return fail(ctx, NST_E_STATE, "the stripe closure implements max pooling only (nst_job_set_pooling(ctx, NST_POOL_MAX))");
     LevelWs& L = ctx->lv[0];
     if (!L.targets) return fail(ctx, NST_E_STATE, "targets of the stripe not set");
     if (!xs) return fail(ctx, NST_E_ARG, "null buffer");

@@ -49,6 +49,10 @@ struct ConvParams {
     int mfma16;                // conv_h2: the 32-channel-chunk shapes run on v_mfma_f32_16x16x32_f16 (nst_options.h2_mfma16)
     int wg256;                 // conv_h2: the 16x16 x 128 tile as 4 waves of 64 x 128 (nst_options.h2_wg256)
     int tile_rows;             // conv_h2: 4 / 8 / 16 forces that tile height on the 128-channel shapes (nst_options.h2_tile_rows)
+    // nst_job_set_pooling(NST_POOL_AVG): pool_out is the 2x2/2 AVERAGE, ((e00 + e01) + e10) + e11 times 1/4, and pcode_out the
+    // multi-hot code bit q = (e_q > 0) (launch-uniform: a scalar branch in the epilogues).  The un-pooling loaders test every
+    // position's bit on its own and are the same for both; the 1/4 of the average's backward rides on wt_h2_inv.
+    int pool_avg;
 };
 
 constexpr int NST_AMAX_SLOTS = 64;
@@ -96,6 +100,7 @@ struct ConvBatch {
     int total_tiles;         // conv_h2: filled by the launcher (tiles x output-channel tiles)
     const void* wt_wino;     // conv_wino: the layer's transformed weights in fragment order (nullptr: none)
     float wt_wino_inv;
+    int pool_avg;            // see ConvParams
 };
 
 // conv_wino.hip: forward 3x3 convolution as 1-D Winograd F(2,3) in the f16x2 arithmetic (nst_options.h2_winograd)
@@ -144,6 +149,12 @@ hipError_t launch_maxpool_fwd(const float* in, int H, int W, int C, float* out, 
 // gin[y][x][c] = (a[y][x][c] is the first maximum of its window and a > 0) ? gpool[y/2][x/2][c] : 0
 // (max_pool2d backward fused with the ReLU mask of the activation `a` that was pooled)
 hipError_t launch_maxpool_bwd_relu(const float* a, const float* gpool, int H, int W, int C, float* gin,
+                                   hipStream_t stream);
+// 2x2/2 average pool (floor) over NHWC, C % 4 == 0: ((e00 + e01) + e10) + e11, times 1/4 (the order of every pooling kernel)
+hipError_t launch_avgpool_fwd(const float* in, int H, int W, int C, float* out, hipStream_t stream);
+// gin[y][x][c] = a[y][x][c] > 0 ? gpool[y/2][x/2][c] / 4 : 0 (avg_pool2d backward fused with the ReLU mask of the
+// activation `a` that was pooled; the odd last row / column gets zeros)
+hipError_t launch_avgpool_bwd_relu(const float* a, const float* gpool, int H, int W, int C, float* gin,
                                    hipStream_t stream);
 // planar (C,h,w) <-> NHWC
 hipError_t launch_chw_to_hwc(const float* src, int C, int H, int W, float* dst, hipStream_t stream);

@@ -1,4 +1,4 @@
-// pixel_ops.hip - the HBM-bound kernels of the closure: max-pool forward / backward(+ReLU mask),
+// pixel_ops.hip - the HBM-bound kernels of the closure: max- / average-pool forward / backward(+ReLU mask),
 // bicubic pyramid down-sample and its transpose, total variation, content MSE, image
 // prepare/unprepare, layout changes and the loss assembly.  All are streaming kernels: 16-byte
 // accesses where the layout allows, grid capped and grid-strided, reductions two-stage and
@@ -114,6 +114,87 @@ hipError_t launch_maxpool_bwd_relu(const float* a, const float* gpool, int H, in
     const size_t total = (size_t)((H + 1) / 2) * ((W + 1) / 2) * (C / 4);
     if (total == 0) return hipSuccess;
     hipLaunchKernelGGL(maxpool_bwd_relu_kernel, dim3(cap_blocks(total, 256)), dim3(256), 0, stream, a, gpool, H, W,
+                       C / 4, gin);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ average pool (nst_job_set_pooling(NST_POOL_AVG))
+// One summation order for every kernel that pools (include/nst_hip.h): the window in scan order, added left to right.
+__global__ void avgpool_fwd_kernel(const float* __restrict__ in, int H, int W, int C4, float* __restrict__ out) {
+    const int oh = H >> 1, ow = W >> 1;
+    const size_t total = (size_t)oh * ow * C4;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int c = (int)(i % C4);
+        const size_t pix = i / C4;
+        const int ox = (int)(pix % ow);
+        const int oy = (int)(pix / ow);
+        const f32x4* src = reinterpret_cast<const f32x4*>(in);
+        const size_t r0 = ((size_t)(2 * oy) * W + 2 * ox) * C4 + c;
+        const size_t r1 = r0 + (size_t)W * C4;
+        const f32x4 a = src[r0], b = src[r0 + C4], d = src[r1], e = src[r1 + C4];
+        f32x4 m;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) m[k] = (((a[k] + b[k]) + d[k]) + e[k]) * 0.25f;
+        reinterpret_cast<f32x4*>(out)[i] = m;
+    }
+}
+
+hipError_t launch_avgpool_fwd(const float* in, int H, int W, int C, float* out, hipStream_t stream) {
+    const size_t total = (size_t)(H / 2) * (W / 2) * (C / 4);
+    if (total == 0) return hipSuccess;
+    hipLaunchKernelGGL(avgpool_fwd_kernel, dim3(cap_blocks(total, 256)), dim3(256), 0, stream, in, H, W, C / 4, out);
+    return hipGetLastError();
+}
+
+// backward of avg_pool2d (a quarter of the pooled gradient to each window position) fused with the ReLU mask of the
+// pooled activation.
+__global__ void avgpool_bwd_relu_kernel(const float* __restrict__ a, const float* __restrict__ gpool, int H, int W,
+                                        int C4, float* __restrict__ gin) {
+    const int oh = H >> 1, ow = W >> 1;
+    const int wh = (H + 1) >> 1, ww = (W + 1) >> 1;
+    const size_t total = (size_t)wh * ww * C4;
+    const f32x4* av = reinterpret_cast<const f32x4*>(a);
+    const f32x4* gv = reinterpret_cast<const f32x4*>(gpool);
+    f32x4* ov = reinterpret_cast<f32x4*>(gin);
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int c = (int)(i % C4);
+        const size_t pix = i / C4;
+        const int wx = (int)(pix % ww);
+        const int wy = (int)(pix / ww);
+        const int y = 2 * wy, x = 2 * wx;
+        const size_t r0 = ((size_t)y * W + x) * C4 + c;
+        const size_t r1 = r0 + (size_t)W * C4;
+        const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+        if (wy < oh && wx < ow) {
+            const f32x4 v0 = av[r0], v1 = av[r0 + C4], v2 = av[r1], v3 = av[r1 + C4];
+            const f32x4 g = gv[((size_t)wy * ow + wx) * C4 + c];
+            f32x4 o0, o1, o2, o3;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float gg = g[k] * 0.25f;
+                o0[k] = (v0[k] > 0.f) ? gg : 0.f;
+                o1[k] = (v1[k] > 0.f) ? gg : 0.f;
+                o2[k] = (v2[k] > 0.f) ? gg : 0.f;
+                o3[k] = (v3[k] > 0.f) ? gg : 0.f;
+            }
+            ov[r0] = o0; ov[r0 + C4] = o1; ov[r1] = o2; ov[r1 + C4] = o3;
+        } else {
+            // odd border: pixels not covered by any window get no gradient
+            ov[r0] = zero;
+            if (x + 1 < W) ov[r0 + C4] = zero;
+            if (y + 1 < H) {
+                ov[r1] = zero;
+                if (x + 1 < W) ov[r1 + C4] = zero;
+            }
+        }
+    }
+}
+
+hipError_t launch_avgpool_bwd_relu(const float* a, const float* gpool, int H, int W, int C, float* gin,
+                                   hipStream_t stream) {
+    const size_t total = (size_t)((H + 1) / 2) * ((W + 1) / 2) * (C / 4);
+    if (total == 0) return hipSuccess;
+    hipLaunchKernelGGL(avgpool_bwd_relu_kernel, dim3(cap_blocks(total, 256)), dim3(256), 0, stream, a, gpool, H, W,
                        C / 4, gin);
     return hipGetLastError();
 }

@@ -10,6 +10,7 @@ import torch
 
 from . import _lib
 from . import taps as _taps
+from .pooling_modes import check_pooling
 from ._lib import NST_LOSS_ROW, NstError, StepInfo
 
 TAP_CHANNELS = (64, 128, 256, 512, 512, 512)
@@ -80,6 +81,7 @@ class StyleEngine:
         self.shape = None
         self.taps = DEFAULT_TAPS                 # (content index, style indices, use_relu): set_taps
         self.channels = 3                        # 1 under set_color("luminance")
+        self.pooling = "max"                     # "avg" under set_pooling("avg")
 
     def close(self):
         if getattr(self, "ctx", None):
@@ -129,6 +131,22 @@ class StyleEngine:
         """Back to RGB, if the colour mode was changed."""
         if self.channels != 3:
             self.set_color("rgb")
+
+    def set_pooling(self, mode) -> None:
+        """Pooling of the feature network (nst_job_set_pooling): "max" = torchvision's vgg19, "avg" = every 2x2 max-pool
+        replaced by a 2x2 average pool (Gatys et al. 2016).  Drops the targets of every configured level: call
+        set_targets again.  ValueError for any other value."""
+        check_pooling(mode)
+        try:
+            _lib.check(self.ctx, self.lib.nst_job_set_pooling(self.ctx, _lib.NST_POOL_AVG if mode == "avg" else _lib.NST_POOL_MAX),
+                       "nst_job_set_pooling")
+        finally:                                 # the context's mode, whether the call succeeded or not
+            self.pooling = "avg" if self.lib.nst_job_pooling(self.ctx) == _lib.NST_POOL_AVG else "max"
+
+    def reset_pooling(self) -> None:
+        """Back to max pooling, if the mode was changed."""
+        if self.pooling != "max":
+            self.set_pooling("max")
 
     def release_job(self) -> None:
         """Give the job's pyramid workspace back (4.7 GB at L=2) and keep the context with its uploaded weights: what an

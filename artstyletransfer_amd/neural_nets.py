@@ -22,6 +22,7 @@ import torch
 
 from . import synthetic
 from .engine import StyleEngine
+from .pooling_modes import check_pooling
 from .taps import DEFAULT_CONTENT_INDEX, DEFAULT_STYLE_INDICES, LAYER_NAMES
 
 _FEATURE_CONV_INDICES = (0, 2, 5, 7, 10, 12, 14, 16, 19, 21, 23, 25, 28)   # torchvision vgg19.features
@@ -114,7 +115,7 @@ def lease_engine(device) -> StyleEngine:
 
 
 def return_engine(eng: StyleEngine) -> None:
-    """Back to the per-GPU pool, with the default taps and RGB: the next job must not inherit this one's."""
+    """Back to the per-GPU pool, with the default taps, RGB and max pooling: the next job must not inherit this one's."""
     if getattr(eng, "ctx", None) is None:
         return
     idx = eng.device.index
@@ -126,6 +127,7 @@ def return_engine(eng: StyleEngine) -> None:
             eng.release_job()                  # the workspace goes back now, only the weights stay resident
             eng.reset_taps()
             eng.reset_color()
+            eng.reset_pooling()
         except Exception:
             keep = False
     if keep:
@@ -145,15 +147,29 @@ def shared_engine(device) -> StyleEngine:
         return _engines[idx]
 
 
-class Vgg19:
+class _Vgg19Call(type):
+    """Vgg19(..., pooling="max" | "avg"): the keyword-only extension is taken by the class call, so that Vgg19.__init__
+    keeps exactly the reference's parameter list (requires_grad, show_progress, use_relu).  Validated before the
+    constructor runs (ValueError)."""
+
+    def __call__(cls, *args, pooling="max", **kwargs):
+        check_pooling(pooling)
+        net = super().__call__(*args, **kwargs)
+        net.pooling = pooling
+        return net
+
+
+class Vgg19(metaclass=_Vgg19Call):
     """Only the layers the original NST paper uses are exposed (relu1_1, relu2_1, relu3_1, relu4_1,
     conv4_2, relu5_1); 'conv4_2' carries ReLU(conv4_2) exactly as the reference's in-place ReLU
     leaves it.  use_relu=False names them conv1_1 ... conv5_1 as the reference does; torchvision's
-    in-place ReLUs still leave maps 0..4 post-ReLU there, and only map 5 is conv5_1 BEFORE its ReLU."""
+    in-place ReLUs still leave maps 0..4 post-ReLU there, and only map 5 is conv5_1 BEFORE its ReLU.
+    pooling="avg" (extension, keyword-only): every MaxPool2d of the network is an AvgPool2d(2, 2) (Gatys et al. 2016)."""
 
     def __init__(self, requires_grad=False, show_progress=False, use_relu=True):
         if requires_grad:
             raise NotImplementedError("the feature network is frozen; only the image is optimised")
+        self.pooling = "max"                    # Vgg19(..., pooling=): set by the class call
         self.use_relu = bool(use_relu)
         self.layer_names = list(LAYER_NAMES[self.use_relu])
         self.offset = 1 if self.use_relu else 0
@@ -175,13 +191,15 @@ class Vgg19:
             yield b
 
     def forward(self, x: torch.Tensor):
-        if self.use_relu:
+        if self.use_relu and self.pooling == "max":
             outs = shared_engine(x.device).vgg_features(x.contiguous())
         else:
-            # the pre-ReLU conv5_1 is a setting of the context: a pooled one, handed back with the default taps
+            # the pre-ReLU conv5_1 and the pooling are settings of the context: a pooled one, handed back with the defaults
             eng = lease_engine(x.device)
             try:
-                eng.set_taps(DEFAULT_CONTENT_INDEX, DEFAULT_STYLE_INDICES, use_relu=False)
+                if not self.use_relu:
+                    eng.set_taps(DEFAULT_CONTENT_INDEX, DEFAULT_STYLE_INDICES, use_relu=False)
+                eng.set_pooling(self.pooling)
                 outs = eng.vgg_features(x.contiguous())
             finally:
                 return_engine(eng)

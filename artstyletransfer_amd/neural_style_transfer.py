@@ -20,6 +20,7 @@ from . import device_image, host_image, math_utils
 from . import taps as _taps
 from .engine import PixelOptimizer, StyleEngine
 from .neural_nets import lease_engine, return_engine, shared_engine
+from .pooling_modes import check_pooling
 
 # ImageNet statistics (reference :22-23)
 IMAGENET_MEAN_255 = [123.675, 116.28, 103.53]
@@ -80,8 +81,9 @@ class LossBuilder:
     def __init__(self, content_feature_maps_index, style_feature_maps_indices, target_content_image,
                  target_style_image, neural_net, content_weight, style_weight, tv_weight):
         # any taps of the reference's six maps (ValueError where the reference would fail or silently ignore an index:
-        # taps.normalize_taps); the flavour (use_relu) is the network's
+        # taps.normalize_taps); the flavour (use_relu) and the pooling are the network's
         use_relu = bool(getattr(neural_net, "use_relu", True))
+        pooling = check_pooling(getattr(neural_net, "pooling", "max"))
         taps = _taps.normalize_taps(content_feature_maps_index, style_feature_maps_indices, use_relu)
         self.__weights = (float(content_weight), float(style_weight), float(tv_weight))
         c = target_content_image
@@ -90,6 +92,8 @@ class LossBuilder:
         self.__engine = lease_engine(c.device)
         self.__engine.configure(1, c.shape[-2], c.shape[-1])
         self.__engine.set_taps(*taps, use_relu=use_relu)
+        if pooling != "max":
+            self.__engine.set_pooling(pooling)
         self.__engine.set_targets(0, c.contiguous(), target_style_image.contiguous())
 
     def __del__(self):
@@ -111,7 +115,8 @@ class _DeviceJob:
     otherwise plain asyncio, so the hand-over and tear-down ordering can be tested with a fake in its place
     (`_make_job`, tests/test_host_api.py)."""
 
-    def __init__(self, device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, taps=None, color=None):
+    def __init__(self, device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, taps=None, color=None,
+                 pooling=None):
         self.dev = dev = device
         self.optimizer = None
         self.luminance = color == "luminance"   # the optimised image is u = 255 Y; the yield puts the content's I, Q back
@@ -142,6 +147,8 @@ class _DeviceJob:
                 engine.configure(len(content_imgs), h0, w0)
                 if taps is not None:                # (content index, style indices, use_relu), normalised
                     engine.set_taps(*taps)
+                if pooling is not None:             # "avg": average pooling in the feature network
+                    engine.set_pooling(pooling)
                 if self.luminance:
                     # luminance-only transfer: content targets 255 Y(content), style targets 255 (alpha Y(style) + beta)
                     # with the style luminance matched to the content's (statistics of the top level), u0 = 255 Y(init)
@@ -204,8 +211,8 @@ class _DeviceJob:
         return_engine(self.engine)             # back to the per-GPU pool: the next job re-uses its uploaded weights
 
 
-def _make_job(device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, taps=None, color=None):
-    return _DeviceJob(device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, taps, color)
+def _make_job(device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, taps=None, color=None, pooling=None):
+    return _DeviceJob(device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, taps, color, pooling)
 
 
 async def _drain(step_future):
@@ -238,6 +245,7 @@ class NeuralStyleTransfer:
         self.__optimizer_name = optimizer_name
         self.__taps = None                       # None: the reference's feature maps
         self.__color = None                      # set_preserve_color
+        self.__pooling = "max"                   # set_pooling
 
     def set_feature_maps(self, content_layer=None, style_layers=None, use_relu=True):
         """Extension: the feature maps the losses of the next `process` read - a content map and a set of style maps of
@@ -256,6 +264,12 @@ class NeuralStyleTransfer:
         (neural_style_transfer() recolours before it builds the initial image and hands the recoloured levels over).
         ValueError for any other value."""
         self.__color = host_image.check_preserve_color(mode)
+
+    def set_pooling(self, mode="max"):
+        """Extension: the pooling of the feature network in the next `process` - "max" (the reference's torchvision vgg19)
+        or "avg": every 2x2 max-pool replaced by a 2x2 average pool (Gatys, Ecker & Bethge 2016, section 2).  ValueError
+        for any other value."""
+        self.__pooling = check_pooling(mode)
 
     async def process(self, content_imgs, init_img, lr_start, iters_num, content_weight, style_weight, tv_weight,
                       init_img_name):
@@ -276,6 +290,8 @@ class NeuralStyleTransfer:
             extra["taps"] = self.__taps
         if self.__color == "luminance":
             extra["color"] = "luminance"
+        if self.__pooling != "max":
+            extra["pooling"] = self.__pooling
         job = _make_job(self.__device, self.__optimizer_name, style_imgs, content_imgs, init_img, lr_start, **extra)
         cw, sw, tvw = float(content_weight), float(style_weight), float(tv_weight)
         loop = asyncio.get_running_loop()
@@ -331,15 +347,18 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
                                 optimizer, model, init_method,
                                 iters_num, levels_num, noise_factor, noise_levels, noise_levels_central_amplitude,
                                 noise_levels_peripheral_amplitude, noise_levels_dispersion, device=None, *,
-                                content_layer=None, style_layers=None, use_relu=True, preserve_color=None):
+                                content_layer=None, style_layers=None, use_relu=True, preserve_color=None,
+                                pooling="max"):
     """Async generator yielding (percent, HWC float32 image) after every optimiser step
     (reference :229-372). `device` (extension): the GPU to run on; default = current.  `content_layer`,
     `style_layers`, `use_relu` (extension): the feature maps the losses read, see NeuralStyleTransfer.set_feature_maps
     (None: the reference's).  `preserve_color` (extension): None, "luminance" or "histogram", see
     NeuralStyleTransfer.set_preserve_color; under "histogram" the style levels are recoloured once, here, and the noise
-    map and the "style" initial image are built from the recoloured ones.  They are validated before any GPU work."""
+    map and the "style" initial image are built from the recoloured ones.  `pooling` (extension): "max" or "avg", see
+    NeuralStyleTransfer.set_pooling.  They are validated before any GPU work."""
     taps = _taps.normalize_taps(content_layer, style_layers, use_relu)
     host_image.check_preserve_color(preserve_color)
+    check_pooling(pooling)
     if device is None:
         if not torch.cuda.is_available():
             raise RuntimeError("no GPU visible: the HIP style-transfer engine has no CPU path")
@@ -367,6 +386,7 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
     nst = NeuralStyleTransfer(device, model, style_levels, optimizer)
     nst.set_feature_maps(*taps, use_relu=use_relu)
     nst.set_preserve_color("luminance" if preserve_color == "luminance" else None)   # (histogram: recoloured above)
+    nst.set_pooling(pooling)
     lr_start = 10.0
     async for img, cur_iter in nst.process(content_levels, init_img, lr_start, iters_num, content_weight,
                                            style_weight, tv_weight, init_name):

@@ -141,6 +141,30 @@ int nst_job_set_taps(nst_ctx* ctx, int content_index, unsigned style_mask, int u
 int nst_job_set_color(nst_ctx* ctx, int mode);
 int nst_job_color(const nst_ctx* ctx);
 
+/* Pooling of the VGG19 feature network (Gatys, Ecker & Bethge, "Image Style Transfer Using Convolutional Neural
+ * Networks", 2016, section 2: average pooling gives smoother gradients than max pooling), a setting of the context like
+ * the taps and the colour mode.
+ *   NST_POOL_MAX (a new context's): the four 2x2/2 max-pools of torchvision's vgg19.
+ *   NST_POOL_AVG: each of them is a 2x2/2 average pool.  Definition, the same in every arithmetic mode and schedule:
+ *     - sizes floor (h // 2, w // 2): a last odd row / column belongs to no window and receives no gradient, as with max;
+ *     - pooled value = ((e00 + e01) + e10) + e11, then * 0.25f, in fp32, where e_yx is the post-ReLU activation at
+ *       window row y, column x (the scan order of the window, added left to right).  EVERY kernel that pools uses
+ *       this order, so the modes and schedules differ by the rounding of their convolutions only;
+ *     - backward: each of the four positions gets 1/4 of the pooled map's gradient, then the ReLU mask of the pooled
+ *       activation (a position whose unit is off gets none).  In the fused f16x2 path the code words of a window are
+ *       multi-hot (bit of position q = e_q > 0) and the 1/4, a power of two, rides exactly on the scale the un-pooling
+ *       input-gradient launch multiplies its accumulators by.
+ * NST_E_ARG for any other value.  Setting the mode (even the same one) waits for the context's work and drops every
+ * level's targets (a closure returns NST_E_STATE until nst_level_set_targets has run again: they were made with the
+ * other network) and any captured closure graph.  It composes with any taps, NST_COLOR_LUMINANCE, every conv mode and
+ * schedule, and level sharding.  nst_vgg_features / nst_vgg_activations / nst_vgg_features_backward follow it.  The
+ * stripe closure (nst_window_*) implements max pooling only and returns NST_E_STATE under NST_POOL_AVG.
+ * nst_job_pooling returns the current mode. */
+#define NST_POOL_MAX 0
+#define NST_POOL_AVG 1
+int nst_job_set_pooling(nst_ctx* ctx, int mode);
+int nst_job_pooling(const nst_ctx* ctx);
+
 /* LossBuilder.__init__ (neural_style_transfer.py:68-82): target content representation
  * ReLU(conv4_2) of the content image and the 5 target Gram matrices of the style image of one
  * level (of the maps nst_job_set_taps chose, when it was called).  content: device (3,h,w) of that level's size; style: device (3,hs,ws), any size.
@@ -213,7 +237,7 @@ int nst_opt_history(const nst_opt* opt, int* pairs, int* n_iter);
 /* L-BFGS closure reuse (default on; env NST_CLOSURE_REUSE=0 at nst_opt_create turns it off).  The closure is bitwise
  * reproducible, so when a step starts at bitwise the image the previous step left (a rejected or skipped trial, or an
  * accepted trial whose closure was the last one made), with the same weights and no change to the job in between
- * (nst_job_configure, nst_job_set_taps, nst_job_set_color, nst_level_set_targets), its first closure is served from what
+ * (nst_job_configure, nst_job_set_taps, nst_job_set_color, nst_job_set_pooling, nst_level_set_targets), its first closure is served from what
  * the optimiser remembers instead of evaluated: same loss row, step counter, lr decay, step info and image.  One
  * device compare of x decides, so the caller may write x between steps.  Never in the sharded modes; Adam never.
  * Changing the setting drops what is remembered. */
@@ -338,7 +362,8 @@ int nst_luminance_recombine(nst_ctx* ctx, const float* u, const float* content, 
  *     the caller adds the stripes' gradients into the full image (overlap-add, one all-reduce).  losses[0..3] = (total,
  *     content, style, tv) of the level, losses[4] = total - identical on every rank.
  * Nothing else may run on the context between begin and end.  The stripe closure implements the default feature maps
- * only: after nst_job_set_taps with any other taps both calls return NST_E_STATE, as they do under NST_COLOR_LUMINANCE. */
+ * only: after nst_job_set_taps with any other taps both calls return NST_E_STATE, as they do under NST_COLOR_LUMINANCE
+ * and under NST_POOL_AVG (nst_job_set_pooling). */
 int nst_window_sums_count(size_t* count);
 int nst_window_begin(nst_ctx* ctx, const float* xs, int row0, int rows, int H0, float* sums, void* stream);
 int nst_window_end(nst_ctx* ctx, const float* xs, int row0, int rows, int H0, float content_weight, float style_weight,
