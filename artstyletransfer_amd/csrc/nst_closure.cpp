@@ -1,0 +1,862 @@
+// nst_closure.cpp - network and closure of libnst_hip.so (include/nst_hip.h): the two walkers of the VGG19 feature network
+// (per level: forward / backward; one launch per layer for all pyramid levels: batched_*), the Gram / style terms, the
+// closure (forward + losses + backward of every pyramid level) with its optional hipGraph, the targets of a level, and the
+// stripe closure of spatial sharding.  One vocabulary serves all of them: conv_setup, launch_conv_batch, launch_pool_*,
+// style_term, content_coef, fill_loss_assembly.
+//
+// Host-side control only; every FLOP and byte of the path is in the .hip kernels.
+#include <algorithm>
+#include <cstring>
+
+#include "nst_ctx.h"
+
+using namespace nst;
+
+namespace {
+
+double conv_flops(int h, int w, int cin, int cout, int taps) { return 2.0 * h * w * (double)cin * cout * taps; }
+
+// the bf16-piece kernels address with 32-bit buffer offsets: tensors from 4 GiB up go to the fp32 kernel
+bool uses_pieces(const nst_ctx* ctx, const ConvParams& p) {
+    if (ctx->conv_mode == 2) return true;           // launch_conv_h2 runs larger tensors in row bands
+    return ctx->conv_mode != 0 && (size_t)p.H * p.W * p.Cin * 4 < 0xFFFFFF00ull;
+}
+// 3x3 conv dispatch by mode; whatever kernel runs, the absmax record of the output is produced when asked for
+hipError_t launch_conv3(nst_ctx* ctx, const ConvParams& p, hipStream_t s) {
+    if (uses_pieces(ctx, p)) return ctx->conv_mode == 2 ? launch_conv_h2(p, s) : launch_conv_bf3(p, s);
+    hipError_t e = launch_conv_mfma(p, 9, s);
+    if (e == hipSuccess && ctx->conv_mode == 2 && p.amax_out)
+        e = launch_absmax_slots(p.out, (size_t)p.H * p.W * p.Cout, p.amax_out, s);
+    return e;
+}
+// true when the launch runs as ONE piece kernel, whose epilogue can write ReLU bit-masks / the pooled map and
+// take a second K source (the fp16 kernel never splits K; the bf16 one may)
+bool bf3_unsplit(const nst_ctx* ctx, const ConvParams& p) {
+    if (!uses_pieces(ctx, p)) return false;
+    if (ctx->conv_mode == 2) return true;
+    const int S = conv_bf3_ksplit(p.H, p.W, p.Cin, p.Cout);
+    return !(p.partial && S > 1 && (size_t)S * p.H * p.W * p.Cout <= p.partial_floats);
+}
+
+// Layer l's weights (dgrad: those of its input-gradient launch), the split-K workspace and the context's f16x2 launch knobs
+void conv_setup(const nst_ctx* ctx, ConvParams& p, const ActSet& a, int l, bool dgrad) {
+    p.wt = dgrad ? ctx->wd[l] : ctx->wf[l]; p.wt_bf = dgrad ? ctx->wd_bf[l] : ctx->wf_bf[l];
+    p.partial = a.splitk; p.partial_floats = a.splitk_floats;
+    if (ctx->conv_mode != 2) return;
+    p.wt_h2 = dgrad ? ctx->wd_h2[l] : ctx->wf_h2[l]; p.wt_h2_inv = dgrad ? ctx->wd_h2_inv[l] : ctx->wf_h2_inv[l];
+    p.band_rows = ctx->band_rows; p.mfma16 = ctx->mfma16; p.wg256 = ctx->wg256; p.tile_rows = ctx->tile_rows;
+}
+// The same for one launch per layer; l = 0: a launch without 3x3 weights (the Gram term alone)
+void conv_setup(const nst_ctx* ctx, ConvBatch& b, int l, bool dgrad) {
+    b.mfma16 = ctx->mfma16; b.wg256 = ctx->wg256; b.tile_rows = ctx->tile_rows; b.persist = ctx->persist;
+    if (l < 1) { b.wt_h2_inv = 1.f; return; }
+    b.wt_bf = dgrad ? ctx->wd_bf[l] : ctx->wf_bf[l];
+    b.wt_h2 = dgrad ? ctx->wd_h2[l] : ctx->wf_h2[l]; b.wt_h2_inv = dgrad ? ctx->wd_h2_inv[l] : ctx->wf_h2_inv[l];
+    b.wt_wino = dgrad ? ctx->wd_wino[l] : ctx->wf_wino[l]; b.wt_wino_inv = dgrad ? ctx->wd_wino_inv[l] : ctx->wf_wino_inv[l];
+}
+// One conv launch for every level, under the caller's timer: the Winograd form where the layer has its weights and the
+// launch qualifies (2/3 of the direct form's matrix-pipe work), else the direct kernel of the arithmetic mode
+int launch_conv_batch(nst_ctx* ctx, const ConvBatch& b, Timer& t, bool allow_wino) {
+    const bool h2 = ctx->conv_mode == 2;
+    if (h2 && allow_wino && b.wt_wino && conv_wino_eligible(b)) { t.mfma_factor(2.0); HIPCHK(ctx, launch_conv_wino_batch(b, t.s)); }
+    else HIPCHK(ctx, h2 ? launch_conv_h2_batch(b, t.s) : launch_conv_bf3_batch(b, t.s));
+    return NST_OK;
+}
+
+// the 2x2/2 pool of the job (nst_job_set_pooling) as kernels of their own, and its backward fused with the ReLU mask of `a`
+hipError_t launch_pool_fwd(const nst_ctx* ctx, const float* in, int H, int W, int C, float* out, hipStream_t s) {
+    return (ctx->pool_avg ? launch_avgpool_fwd : launch_maxpool_fwd)(in, H, W, C, out, s);
+}
+hipError_t launch_pool_bwd_relu(const nst_ctx* ctx, const float* a, const float* gpool, int H, int W, int C, float* gin, hipStream_t s) {
+    return (ctx->pool_avg ? launch_avgpool_bwd_relu : launch_maxpool_bwd_relu)(a, gpool, H, W, C, gin, s);
+}
+
+// The style term of slot q on a map of N = rows x w pixels and C channels: style = mean_q mse(G_q, Gt_q), G = F^T F / divisor,
+// so dL/dG = sw/nstyle * 2 (G - Gt)/C^2 and dF = 2 * dL/dG * F / (C h w) = F * S with S = coef * (G - Gt).
+// norm_rows > 0 (stripe closure): the normalisers of the full image, norm_rows level-0 rows, instead of the ActSet's own.
+struct StyleTerm { int C; size_t N; double divisor; float coef; };
+StyleTerm style_term(const Taps& tp, int q, const ActSet& a, float sw, int norm_rows = 0) {
+    const int l = tp.style[q], C = kCout[l];
+    const size_t N = (size_t)(norm_rows > 0 ? norm_rows >> kScale[l] : a.h[l]) * a.w[l];
+    const double chw = (double)C * (double)N;
+    return {C, N, chw, (float)((double)sw * 4.0 / ((double)tp.nstyle * (double)C * C * chw))};
+}
+// content = cw * mse(F, Ft) over n elements: dF = coef * (F - Ft)
+float content_coef(float cw, double n) { return (float)((double)cw * 2.0 / n); }
+
+// partial-Gram workspace of one image: the style layers one after the other (the batched launch works on
+// all of them at once); offset of style slot k = gram_part_offset(tp, h, w, k), total = gram_part_offset(tp, h, w, tp.nstyle)
+size_t gram_part_offset(const Taps& tp, int h, int w, int k) {
+    size_t off = 0;
+    for (int q = 0; q < k; ++q) {
+        const int l = tp.style[q];
+        const size_t N = (size_t)(h >> kScale[l]) * (w >> kScale[l]);
+        off += (size_t)gram_nsplit(kCout[l], N) * kCout[l] * kCout[l];
+    }
+    return off;
+}
+
+}  // namespace
+
+namespace nst {
+
+// ---- network forward ----------------------------------------------------------------------------
+int forward(nst_ctx* ctx, ActSet& a, const float* x, int h, int w, hipStream_t s, int last_layer, int channels) {
+    a.begin_pass();
+    const bool h2 = ctx->conv_mode == 2;
+    if (h2) HIPCHK(ctx, launch_zero(a.amax, (size_t)(NL + kMaxStyle) * NST_AMAX_SLOTS, s));     // act + S records
+    {
+        Timer t(ctx, s, K_CONV1, conv_flops(h, w, 3, 64, 9));
+        unsigned* bits = ctx->conv_mode ? a.bits[0] : nullptr;
+        HIPCHK(ctx, launch_conv1_1_fwd(x, h, w, ctx->w11k, ctx->bias[0], a.act[0], bits, h2 ? amax_act(a, 0) : nullptr, s, channels));
+        a.bits_valid[0] = bits != nullptr;
+    }
+    for (int l = 1; l <= last_layer; ++l) {
+        const int pk = pool_index_after(l - 1);
+        const float* in = (pk >= 0) ? a.pool[pk] : a.act[l - 1];
+        ConvParams p{};
+        p.in = in; p.bias = ctx->bias[l]; p.addend = nullptr; p.mask = nullptr; p.out = a.act[l];
+        p.H = a.h[l]; p.W = a.w[l]; p.Cin = kCin[l]; p.Cout = kCout[l];
+        p.relu = ctx->taps.relu_of(l);
+        p.pool_avg = ctx->pool_avg;
+        conv_setup(ctx, p, a, l, false);
+        if (h2) {
+            p.amax_in = amax_act(a, l - 1);       // the pooled map's maximum is its source's
+            p.amax_out = amax_act(a, l);
+        }
+        const int pa = pool_index_after(l);
+        const bool fuse = bf3_unsplit(ctx, p);        // the epilogue extras exist in the unsplit bf3 kernel only
+        if (fuse) {
+            p.bits_out = a.bits[l];                   // nullptr for layers whose mask nobody reads
+            if (pa >= 0 && l < last_layer) p.pool_out = a.pool[pa];
+        }
+        {
+            Timer t(ctx, s, K_CONV3, conv_flops(p.H, p.W, p.Cin, p.Cout, 9), p.H, p.W, p.Cin, p.Cout, 9, l);
+            HIPCHK(ctx, launch_conv3(ctx, p, s));
+        }
+        a.bits_valid[l] = fuse && a.bits[l] != nullptr;
+        if (pa >= 0 && l < last_layer) {
+            if (p.pool_out) {
+                a.pooled[pa] = true;
+            } else {
+                Timer t(ctx, s, K_OTHER, 0);
+                HIPCHK(ctx, launch_pool_fwd(ctx, a.act[l], a.h[l], a.w[l], kCout[l], a.pool[pa], s));
+            }
+        }
+    }
+    return NST_OK;
+}
+
+// ---- network backward (nst_ctx.h has the contract) --------------------------------------------------
+int backward(nst_ctx* ctx, ActSet& a, const Inject* inj, const ContentJob* cj, float* gbuf0, float* gbuf1, float* gx,
+             int h, int w, hipStream_t s, int top, bool top_mask, int channels) {
+    float* cur = gbuf0;     // holds the gradient w.r.t. the pre-ReLU output of the layer being processed
+    float* oth = gbuf1;
+    const bool h2 = ctx->conv_mode == 2;
+    if (h2) HIPCHK(ctx, launch_zero(amax_grad(a, 0), (size_t)NL * NST_AMAX_SLOTS, s));
+    // top of the chain
+    {
+        const int l = top;
+        const size_t n = (size_t)a.h[l] * a.w[l] * kCout[l];
+        const bool content = inj[l].content && cj;
+        if (content) {
+            Timer t(ctx, s, K_OTHER, 0);
+            HIPCHK(ctx, launch_mse_grad(a.act[l], cj->target, cj->n, cj->coef, oth, cj->partial, s));
+        }
+        if (inj[l].S) {
+            // (the content gradient, if any, as the addend of the 1x1 Gram launch)
+            ConvParams p{};
+            p.in = a.act[l]; p.wt = inj[l].S; p.out = cur; p.mask = top_mask ? a.act[l] : nullptr;
+            p.addend = content ? oth : nullptr;
+            p.H = a.h[l]; p.W = a.w[l]; p.Cin = kCout[l]; p.Cout = kCout[l];
+            Timer t(ctx, s, K_GRAM, conv_flops(p.H, p.W, p.Cin, p.Cout, 1));
+            HIPCHK(ctx, launch_conv_mfma(p, 1, s));
+        } else if (content || inj[l].direct) {
+            const float* g = content ? oth : inj[l].direct;
+            Timer t(ctx, s, K_OTHER, 0);
+            if (top_mask) HIPCHK(ctx, launch_relu_mask(a.act[l], g, n, cur, s));
+            else HIPCHK(ctx, launch_copy(g, cur, n, s));
+        } else {
+            HIPCHK(ctx, launch_zero(cur, n, s));
+        }
+        if (h2) HIPCHK(ctx, launch_absmax_slots(cur, n, amax_grad(a, l), s));
+    }
+    for (int l = top; l >= 1; --l) {
+        // cur = g(pre-ReLU of layer l), dims of layer l, kCout[l] channels.  dgrad -> gradient w.r.t.
+        // layer l's input: either pool[k] (then un-pool into act[l-1]'s shape) or act[l-1] directly.
+        const int pk = pool_index_after(l - 1);
+        ConvParams p{};
+        p.in = cur; p.out = oth;
+        p.H = a.h[l]; p.W = a.w[l]; p.Cin = kCout[l]; p.Cout = kCin[l];
+        conv_setup(ctx, p, a, l, true);
+        if (h2) {
+            p.amax_in = amax_grad(a, l);
+            p.amax_out = amax_grad(a, l - 1);     // when un-pooled next, this bounds the un-pooled gradient too
+        }
+        if (pk >= 0) {
+            // (average pooling: the un-pooled gradient is a quarter of the pooled one, so the pooled gradient's absmax would
+            // describe a tensor four times what the next launch reads - that launch's record is taken after the un-pooling)
+            const bool avg = ctx->pool_avg != 0;
+            if (avg) p.amax_out = nullptr;
+            {
+                Timer t(ctx, s, K_CONV3, conv_flops(p.H, p.W, p.Cin, p.Cout, 9), p.H, p.W, p.Cin, p.Cout, 9, -l);
+                HIPCHK(ctx, launch_conv3(ctx, p, s));
+            }
+            // oth = g(pool[pk]); un-pool through act[l-1] with its ReLU mask -> cur
+            Timer t(ctx, s, K_OTHER, 0);
+            HIPCHK(ctx, launch_pool_bwd_relu(ctx, a.act[l - 1], oth, a.h[l - 1], a.w[l - 1], kCout[l - 1], cur, s));
+            if (avg && h2)
+                HIPCHK(ctx, launch_absmax_slots(cur, (size_t)a.h[l - 1] * a.w[l - 1] * kCout[l - 1], amax_grad(a, l - 1), s));
+            // cur now holds g(pre-ReLU of layer l-1); no tap layer sits directly before a pool
+        } else {
+            const int m = l - 1;   // the layer whose activation this gradient flows into
+            const Inject& in = inj[m];
+            const bool fuse = bf3_unsplit(ctx, p);
+            double extra_flops = 0;
+            // the content gradient first: a Gram term of the same map then rides on the launch as well (second K source)
+            // or accumulates into the addend (standalone 1x1 launch)
+            if (in.content && cj) {
+                Timer t(ctx, s, K_OTHER, 0);
+                HIPCHK(ctx, launch_mse_grad(a.act[m], cj->target, cj->n, cj->coef, oth, cj->partial, s));
+                p.addend = oth;
+            } else if (in.direct) {
+                p.addend = in.direct;
+            }
+            if (in.S && fuse && (h2 ? in.S_amax != nullptr : in.S_bf != nullptr)) {
+                // Gram backward rides on this launch as a second K source: acc += act[m] * S
+                p.in2 = a.act[m]; p.Cin2 = kCout[m]; p.wt2_bf = in.S_bf;
+                p.wt2_f32 = in.S; p.amax_in2 = amax_act(a, m); p.amax_w2 = in.S_amax;
+                extra_flops = conv_flops(a.h[m], a.w[m], kCout[m], kCout[m], 1);
+            } else if (in.S) {
+                ConvParams q{};
+                q.in = a.act[m]; q.wt = in.S; q.out = oth; q.addend = p.addend;
+                q.H = a.h[m]; q.W = a.w[m]; q.Cin = kCout[m]; q.Cout = kCout[m];
+                Timer t(ctx, s, K_GRAM, conv_flops(q.H, q.W, q.Cin, q.Cout, 1));
+                HIPCHK(ctx, launch_conv_mfma(q, 1, s));
+                p.addend = oth;
+            }
+            if (fuse && a.bits_valid[m]) p.bits_in = a.bits[m];
+            else p.mask = a.act[m];
+            {
+                Timer t(ctx, s, K_CONV3, conv_flops(p.H, p.W, p.Cin, p.Cout, 9) + extra_flops, p.H, p.W, p.Cin, p.Cout, 9, -l);
+                HIPCHK(ctx, launch_conv3(ctx, p, s));
+            }
+            float* tmp = cur; cur = oth; oth = tmp;
+        }
+    }
+    {
+        Timer t(ctx, s, K_CONV1, conv_flops(h, w, 64, 3, 9));
+        HIPCHK(ctx, launch_conv1_1_dgrad(cur, h, w, ctx->w11d, h2 ? amax_grad(a, 0) : nullptr, gx, s, channels));
+    }
+    return NST_OK;
+}
+
+int gram_of(nst_ctx* ctx, const float* f_nhwc, size_t N, int C, const unsigned* f_amax, float divisor, float* part, const float* target,
+            float coef, float* gram_out, float* S, unsigned short* S_bf, unsigned* S_amax, double* mse_partial,
+            hipStream_t s) {
+    const int ns = gram_nsplit(C, N);
+    {
+        Timer t(ctx, s, K_GRAM, 2.0 * (double)N * C * C);
+        HIPCHK(ctx, launch_gram_partial(f_nhwc, N, C, ns, f_amax, part, s));
+    }
+    Timer t(ctx, s, K_OTHER, 0);
+    HIPCHK(ctx, launch_gram_finish(part, gram_nslabs(C, ns), C, divisor, target, coef, gram_out, S, S_bf, S_amax,
+                                   mse_partial, s));
+    return NST_OK;
+}
+
+size_t gram_part_floats_for(const Taps& tp, int h, int w) { return gram_part_offset(tp, h, w, tp.nstyle); }
+
+}  // namespace nst
+
+namespace {
+
+// ---- closure with every conv layer launched once for all pyramid levels ("batched") ----------------------
+// Layer l has the same weights and channel counts at every level, and layer l of any level depends only on
+// layer l-1 of that level, so the 12 forward and 12 input-gradient convolutions each become ONE launch whose
+// grid lists the tiles of level 0, then level 1, ...: the small levels fill the tail of the big level's grid
+// instead of running as under-filled launches.  Everything is ordered on the caller's stream.
+// A job evaluated on a horizontal stripe of a larger image (spatial sharding): the level-0 image of this
+// context is rows [.., ..) of an H0-row image; the loss terms of its rows [row0, row0 + rows) are this context's,
+// with the normalisers of the full image.  Per-layer quantities scale by the layer's stride (row0, rows: multiples
+// of 16).  Style / content / TV sums of the owned rows go to `sums` (begin); after the caller has added the other
+// stripes' sums the backward uses them (end).
+struct Window {
+    int row0, rows, H0;
+    float* sums;          // begin: out;  end: in (summed over the stripes)
+};
+// owned rows at a layer of stride 2^sc: [row0 >> sc, (row0 + rows) >> sc) (the bottom stripe may end on a ragged row)
+inline int win_r0(const Window& w, int sc) { return w.row0 >> sc; }
+inline int win_nr(const Window& w, int sc) { return ((w.row0 + w.rows) >> sc) - (w.row0 >> sc); }
+constexpr size_t kWinGramOff[5] = {0, 64 * 64, 64 * 64 + 128 * 128, 64 * 64 + 128 * 128 + 256 * 256,
+                                   64 * 64 + 128 * 128 + 256 * 256 + 512 * 512};
+constexpr size_t kWinScalarOff = 64 * 64 + 128 * 128 + 256 * 256 + 2 * 512 * 512;    // content SSE, TV x, TV y
+constexpr size_t kWinSums = kWinScalarOff + 4;
+
+// `fork_sw` >= 0 (f16x2 closure, nst_options.gram_overlap): once relu3_1 is written, the Gram matrices of relu1_1, relu2_1 and
+// relu3_1 - HBM-bound streams over 85 % of the style bytes - are launched on the context's side stream, where they run
+// under the MFMA-bound convolutions of conv3_2 ... conv5_1 instead of after them; the caller joins before the backward.
+int batched_gram(nst_ctx* ctx, const int* lv, int n, float sw, hipStream_t s, unsigned qmask);
+int batched_forward(nst_ctx* ctx, const float* const* xi, const int* lv, int n, hipStream_t s, const Window* win, float fork_sw = -1.f) {
+    const bool h2 = ctx->conv_mode == 2;
+    const int top = ctx->taps.top;
+    for (int k = 0; k < n; ++k) {
+        LevelWs& L = ctx->lv[lv[k]];
+        ActSet& a = L.acts;
+        a.begin_pass();
+        if (h2) HIPCHK(ctx, launch_zero(a.amax, (size_t)AMAX_IDS * NST_AMAX_SLOTS, s));
+        {
+            Timer t(ctx, s, K_OTHER, 0);
+            HIPCHK(ctx, launch_tv_partial(xi[lv[k]], ctx->channels, L.h, L.w, L.tv_partial, s, win ? win->row0 : 0, win ? win->rows : 0));
+        }
+        Timer t(ctx, s, K_CONV1, conv_flops(L.h, L.w, 3, 64, 9));
+        HIPCHK(ctx, launch_conv1_1_fwd(xi[lv[k]], L.h, L.w, ctx->w11k, ctx->bias[0], a.act[0], a.bits[0],
+                                       h2 ? amax_act(a, 0) : nullptr, s, ctx->channels));
+        a.bits_valid[0] = true;
+    }
+    for (int l = 1; l <= top; ++l) {
+        const int pk = pool_index_after(l - 1), pa = pool_index_after(l);
+        ConvBatch b{};
+        b.n = n; b.bias = ctx->bias[l]; b.Cin = kCin[l]; b.Cout = kCout[l];
+        // conv5_1 before its ReLU (use_relu = 0): the Winograd launch takes its general epilogue (MODE 0), which honours relu = 0
+        b.relu = ctx->taps.relu_of(l);
+        conv_setup(ctx, b, l, false);
+        b.pool_avg = ctx->pool_avg;
+        double flops = 0;
+        for (int k = 0; k < n; ++k) {
+            ActSet& a = ctx->lv[lv[k]].acts;
+            ConvImage& im = b.img[k];
+            im.in = (pk >= 0) ? a.pool[pk] : a.act[l - 1];
+            im.out = a.act[l]; im.H = a.h[l]; im.W = a.w[l];
+            im.bits_out = a.bits[l];
+            im.pool_out = (pa >= 0) ? a.pool[pa] : nullptr;
+            im.pcode_out = (pa >= 0 && h2) ? a.pcode[pa] : nullptr;
+            a.bits_valid[l] = a.bits[l] != nullptr;
+            if (pa >= 0) a.pooled[pa] = true;
+            im.amax_in = amax_act(a, l - 1); im.amax_out = amax_act(a, l);
+            flops += conv_flops(im.H, im.W, b.Cin, b.Cout, 9);
+        }
+        {
+            Timer t(ctx, s, K_CONV3, flops, b.img[0].H, b.img[0].W, b.Cin, b.Cout, 9, l);
+            NSTCHK(launch_conv_batch(ctx, b, t, true));
+        }
+        if (l == 4 && fork_sw >= 0.f && ctx->side) {
+            HIPCHK(ctx, hipEventRecord(ctx->side_fork, s));
+            HIPCHK(ctx, hipStreamWaitEvent(ctx->side, ctx->side_fork, 0));
+            NSTCHK(batched_gram(ctx, lv, n, fork_sw, ctx->side, 0x07u));
+            HIPCHK(ctx, hipEventRecord(ctx->side_join, ctx->side));
+        }
+    }
+    return NST_OK;
+}
+
+// ---- style losses: Gram matrices, S = d loss / d G folded for the backward
+int batched_gram(nst_ctx* ctx, const int* lv, int n, float sw, hipStream_t s, unsigned qmask) {
+    const bool h2 = ctx->conv_mode == 2;
+    if (h2) {
+        // every (level, style layer) pair in two partial launches (one per tile shape) and one finish launch
+        const int per = std::max(1, NST_GRAM_BATCH_MAX / ctx->taps.nstyle);      // levels per launch (3 with five style maps)
+        for (int k0 = 0; k0 < n; k0 += per) {
+            GramBatch gb{};
+            double flops = 0;
+            for (int k = k0; k < n && k < k0 + per; ++k) {
+                LevelWs& L = ctx->lv[lv[k]];
+                for (int q = 0; q < ctx->taps.nstyle; ++q) {
+                    if (!((qmask >> q) & 1u)) continue;
+                    const int l = ctx->taps.style[q];
+                    const StyleTerm st = style_term(ctx->taps, q, L.acts, sw);
+                    GramItem& it = gb.it[gb.n++];
+                    it.f = L.acts.act[l]; it.N = st.N; it.C = st.C; it.amax = amax_act(L.acts, l);
+                    it.part = L.gram_part + gram_part_offset(ctx->taps, L.h, L.w, q);
+                    it.divisor = (float)st.divisor; it.target = L.gram_t[q];
+                    it.coef = st.coef;
+                    it.gram_out = nullptr; it.S = L.S[q]; it.S_bf = L.S_bf[q]; it.S_amax = amax_S(L.acts, q);
+                    it.mse_partial = L.style_partial[q];
+                    flops += 2.0 * (double)st.N * st.C * st.C;
+                }
+            }
+            if (gb.n == 0) continue;
+            Timer t(ctx, s, K_GRAM, flops);
+            HIPCHK(ctx, launch_gram_batch(gb, s));
+        }
+    }
+    for (int k = 0; k < n && !h2; ++k) {
+        LevelWs& L = ctx->lv[lv[k]];
+        for (int q = 0; q < ctx->taps.nstyle; ++q) {
+            const StyleTerm st = style_term(ctx->taps, q, L.acts, sw);
+            NSTCHK(gram_of(ctx, L.acts.act[ctx->taps.style[q]], st.N, st.C, nullptr, (float)st.divisor, L.gram_part, L.gram_t[q], st.coef, nullptr, L.S[q],
+                           L.S_bf[q], nullptr, L.style_partial[q], s));
+        }
+    }
+    return NST_OK;
+}
+
+int batched_backward(nst_ctx* ctx, const float* const* xi, float* const* gi, const int* lv, int n, float cw, float tvw,
+                     hipStream_t s, const Window* win, const float* win_means, double win_nx, double win_ny) {
+    const bool h2 = ctx->conv_mode == 2;
+    float* cur[NST_MAX_LEVELS]; float* oth[NST_MAX_LEVELS];
+    for (int k = 0; k < n; ++k) { cur[k] = ctx->lv[lv[k]].gbuf[0]; oth[k] = ctx->lv[lv[k]].gbuf[1]; }
+    const Taps& tp = ctx->taps;
+    const int top = tp.top;
+    const int top_q = tp.style_slot(top);
+    const bool top_content = tp.content == top;
+    // content gradient of level image k into dst (the content map's own shape), windowed or not
+    auto content_grad = [&](int k, float* dst) -> int {
+        LevelWs& L = ctx->lv[lv[k]];
+        ActSet& a = L.acts;
+        const int m = tp.content;
+        Timer t(ctx, s, K_OTHER, 0);
+        if (win) {
+            // content gradient on the owned rows only (zero elsewhere), normalised by the full image's size
+            const size_t off = (size_t)win_r0(*win, kScale[m]) * a.w[m] * kCout[m];
+            const size_t cnt = (size_t)win_nr(*win, kScale[m]) * a.w[m] * kCout[m];
+            const double n_all = (double)(win->H0 >> kScale[m]) * a.w[m] * kCout[m];
+            HIPCHK(ctx, launch_zero(dst, L.content_n, s));
+            HIPCHK(ctx, launch_mse_grad(a.act[m] + off, L.content_t + off, cnt, content_coef(cw, n_all), dst + off, L.content_partial, s));
+        } else {
+            HIPCHK(ctx, launch_mse_grad(a.act[m], L.content_t, L.content_n, content_coef(cw, (double)L.content_n), dst, L.content_partial, s));
+        }
+        return NST_OK;
+    };
+    if (top_content)
+        for (int k = 0; k < n; ++k) NSTCHK(content_grad(k, oth[k]));
+    if (h2 && top_q >= 0) {
+        // top of the chain: g(pre-ReLU of the top map) = mask(act * S (+ content gradient)) - the second K source of the
+        // fp16 kernel on its own (no 3x3 part), one launch for all levels; its epilogue adds the content gradient (when the
+        // top map is the content map too), applies the ReLU mask (not for the pre-ReLU conv5_1) and records the absmax
+        const int l = top;
+        ConvBatch b{};
+        b.n = n; b.Cin = 0; b.Cout = kCout[l]; b.Cin2 = kCout[l]; b.relu = 0;
+        conv_setup(ctx, b, 0, true);
+        double flops = 0;
+        for (int k = 0; k < n; ++k) {
+            LevelWs& L = ctx->lv[lv[k]];
+            ActSet& a = L.acts;
+            ConvImage& im = b.img[k];
+            im.out = cur[k]; im.H = a.h[l]; im.W = a.w[l];
+            im.in2 = a.act[l]; im.wt2_f32 = L.S[top_q]; im.amax_in2 = amax_act(a, l); im.amax_w2 = amax_S(a, top_q);
+            im.bits_in = tp.top_mask() ? a.bits[l] : nullptr; im.amax_out = amax_grad(a, l);
+            im.addend = top_content ? oth[k] : nullptr;
+            if (win) { im.in2_row0 = win_r0(*win, kScale[l]); im.in2_rows = win_nr(*win, kScale[l]); }
+            flops += conv_flops(im.H, im.W, b.Cin2, b.Cout, 1);
+        }
+        Timer t(ctx, s, K_GRAM, flops);
+        NSTCHK(launch_conv_batch(ctx, b, t, false));
+    }
+    for (int k = 0; k < n && !(h2 && top_q >= 0); ++k) {
+        LevelWs& L = ctx->lv[lv[k]];
+        ActSet& a = L.acts;
+        const int l = top;
+        const size_t cnt = (size_t)a.h[l] * a.w[l] * kCout[l];
+        if (top_q >= 0) {
+            ConvParams p{};
+            p.in = a.act[l]; p.wt = L.S[top_q]; p.out = cur[k]; p.mask = tp.top_mask() ? a.act[l] : nullptr;
+            p.addend = top_content ? oth[k] : nullptr;
+            p.H = a.h[l]; p.W = a.w[l]; p.Cin = kCout[l]; p.Cout = kCout[l];
+            Timer t(ctx, s, K_GRAM, conv_flops(p.H, p.W, p.Cin, p.Cout, 1));
+            HIPCHK(ctx, launch_conv_mfma(p, 1, s));
+        } else {
+            // the content map alone at the top: its gradient through the ReLU mask
+            Timer t(ctx, s, K_OTHER, 0);
+            if (tp.top_mask()) HIPCHK(ctx, launch_relu_mask(a.act[l], oth[k], cnt, cur[k], s));
+            else HIPCHK(ctx, launch_copy(oth[k], cur[k], cnt, s));
+        }
+        if (h2) HIPCHK(ctx, launch_absmax_slots(cur[k], cnt, amax_grad(a, l), s));
+    }
+    for (int l = top; l >= 1; --l) {
+        const int pk = pool_index_after(l - 1);
+        const int m = l - 1;
+        const int style_q = tp.style_slot(m);
+        ConvBatch b{};
+        b.n = n; b.bias = nullptr; b.Cin = kCout[l]; b.Cout = kCin[l]; b.relu = 0;
+        conv_setup(ctx, b, l, true);
+        // f16x2: when a max-pool follows layer l, cur[] holds the gradient w.r.t. the POOLED map and this launch's
+        // loader un-pools it through the arg-max code (no un-pool kernel, no full-size gradient round trip)
+        const int pl = pool_index_after(l);
+        b.unpool = (h2 && pl >= 0) ? 1 : 0;
+        // average pooling: every position whose code bit is on gets a QUARTER of the pooled gradient.  The loader hands the
+        // pooled gradient through as it is (same loads, same selects, a multi-hot code) and the 1/4 rides on the scale the
+        // launch multiplies its accumulators by: exact (a power of two), and the second K source - re-expressed in the main
+        // source's scale through the same factor - comes out unchanged.  The launch records the absmax of what it stores.
+        if (b.unpool && ctx->pool_avg) { b.wt_h2_inv *= 0.25f; b.wt_wino_inv *= 0.25f; }
+        b.Cin2 = (pk < 0 && style_q >= 0) ? kCout[m] : 0;
+        double flops = 0;
+        for (int k = 0; k < n; ++k) {
+            LevelWs& L = ctx->lv[lv[k]];
+            ActSet& a = L.acts;
+            ConvImage& im = b.img[k];
+            im.in = cur[k]; im.out = oth[k]; im.H = a.h[l]; im.W = a.w[l];
+            im.pcode_in = b.unpool ? a.pcode[pl] : nullptr;
+            im.amax_in = amax_grad(a, l); im.amax_out = amax_grad(a, l - 1);
+            flops += conv_flops(im.H, im.W, b.Cin, b.Cout, 9);
+            if (pk >= 0) continue;
+            // a map that is both a style and the content map: the Gram term as the second K source AND the content
+            // gradient as the addend of the same launch
+            if (style_q >= 0) {
+                im.in2 = a.act[m]; im.wt2_bf = L.S_bf[style_q];
+                im.wt2_f32 = L.S[style_q]; im.amax_in2 = amax_act(a, m); im.amax_w2 = amax_S(a, style_q);
+                if (win) { im.in2_row0 = win_r0(*win, kScale[m]); im.in2_rows = win_nr(*win, kScale[m]); }
+                flops += conv_flops(a.h[m], a.w[m], kCout[m], kCout[m], 1);
+            }
+            if (m == tp.content) {
+                NSTCHK(content_grad(k, oth[k]));
+                im.addend = oth[k];
+            }
+            im.bits_in = a.bits[m];
+        }
+        {
+            Timer t(ctx, s, K_CONV3, flops, b.img[0].H, b.img[0].W, b.Cin, b.Cout, 9, -l);
+            NSTCHK(launch_conv_batch(ctx, b, t, !win));
+        }
+        for (int k = 0; k < n; ++k) {
+            ActSet& a = ctx->lv[lv[k]].acts;
+            if (pk >= 0 && !h2) {
+                Timer t(ctx, s, K_OTHER, 0);
+                HIPCHK(ctx, launch_pool_bwd_relu(ctx, a.act[l - 1], oth[k], a.h[l - 1], a.w[l - 1], kCout[l - 1], cur[k], s));
+            } else {
+                float* tmp = cur[k]; cur[k] = oth[k]; oth[k] = tmp;
+            }
+        }
+    }
+    for (int k = 0; k < n; ++k) {
+        LevelWs& L = ctx->lv[lv[k]];
+        {
+            Timer t(ctx, s, K_CONV1, conv_flops(L.h, L.w, 64, 3, 9));
+            HIPCHK(ctx, launch_conv1_1_dgrad(cur[k], L.h, L.w, ctx->w11d, h2 ? amax_grad(L.acts, 0) : nullptr, gi[lv[k]], s,
+                                             ctx->channels));
+        }
+        Timer t(ctx, s, K_OTHER, 0);
+        if (win)
+            HIPCHK(ctx, launch_tv_finish(xi[lv[k]], ctx->channels, L.h, L.w, L.tv_partial, tvw, gi[lv[k]], 1, nullptr, s, win->row0, win->rows,
+                                         win_means, win_nx, win_ny));
+        else
+            HIPCHK(ctx, launch_tv_finish(xi[lv[k]], ctx->channels, L.h, L.w, L.tv_partial, tvw, gi[lv[k]], 1, L.tv_means, s));
+    }
+    return NST_OK;
+}
+
+// `zero_mask`: the levels whose gradient this call clears when they are not in `level_mask` (levels another rank owns)
+int closure_batched(nst_ctx* ctx, const float* const* xi, float* const* gi, unsigned level_mask, float cw, float sw,
+                    float tvw, hipStream_t s, unsigned zero_mask = ~0u) {
+    int lv[NST_MAX_LEVELS], n = 0;
+    for (int i = 0; i < ctx->levels; ++i) {
+        if ((level_mask >> i) & 1u) lv[n++] = i;
+        else if ((zero_mask >> i) & 1u) HIPCHK(ctx, launch_zero(gi[i], (size_t)ctx->channels * ctx->lv[i].h * ctx->lv[i].w, s));
+    }
+    if (n == 0) return NST_OK;
+    // (not while a hipGraph is being captured or replayed: the closure then stays on one stream)
+    // (the overlap's split of the style maps - relu1_1 .. relu3_1 on the side stream - is the default taps')
+    const bool overlap = ctx->gram_overlap && ctx->conv_mode == 2 && !ctx->use_graph && ctx->side != nullptr && ctx->taps.is_default;
+    NSTCHK(batched_forward(ctx, xi, lv, n, s, nullptr, overlap ? sw : -1.f));
+    NSTCHK(batched_gram(ctx, lv, n, sw, s, overlap ? 0x18u : (1u << ctx->taps.nstyle) - 1u));
+    if (overlap) HIPCHK(ctx, hipStreamWaitEvent(s, ctx->side_join, 0));
+    return batched_backward(ctx, xi, gi, lv, n, cw, tvw, s, nullptr, nullptr, 0, 0);
+}
+
+bool batch_eligible(const nst_ctx* ctx) {
+    // needs the bf16 conv kernels (32-bit buffer offsets) and enough tiles to be worth it
+    return ctx->batched && ctx->conv_mode && (size_t)ctx->lv[0].h * ctx->lv[0].w * 64 * 4 < 0xFFFFFF00ull &&
+           (ctx->levels > 1 || (size_t)ctx->lv[0].h * ctx->lv[0].w >= (size_t)256 * 256);
+}
+
+// ---- closure of ONE pyramid level by the per-level walker, on stream s (the counterpart of closure_batched) ------------
+int closure_per_level(nst_ctx* ctx, const float* const* xi, float* const* gi, int level, float cw, float sw, float tvw,
+                      hipStream_t s) {
+    LevelWs& L = ctx->lv[level];
+    const Taps& tp = ctx->taps;
+    const bool h2 = ctx->conv_mode == 2;
+    {
+        Timer t(ctx, s, K_OTHER, 0);
+        HIPCHK(ctx, launch_tv_partial(xi[level], ctx->channels, L.h, L.w, L.tv_partial, s));
+    }
+    NSTCHK(forward(ctx, L.acts, xi[level], L.h, L.w, s, tp.top, ctx->channels));
+    Inject inj[NL];
+    for (int k = 0; k < tp.nstyle; ++k) {
+        const int l = tp.style[k];
+        const StyleTerm st = style_term(tp, k, L.acts, sw);
+        NSTCHK(gram_of(ctx, L.acts.act[l], st.N, st.C, h2 ? amax_act(L.acts, l) : nullptr, (float)st.divisor, L.gram_part, L.gram_t[k], st.coef, nullptr, L.S[k],
+                       L.S_bf[k], h2 ? amax_S(L.acts, k) : nullptr, L.style_partial[k], s));
+        inj[l].S = L.S[k];
+        inj[l].S_bf = L.S_bf[k];
+        inj[l].S_amax = h2 ? amax_S(L.acts, k) : nullptr;
+    }
+    inj[tp.content].content = true;
+    ContentJob cj{L.content_t, L.content_n, content_coef(cw, (double)L.content_n), L.content_partial};
+    NSTCHK(backward(ctx, L.acts, inj, &cj, L.gbuf[0], L.gbuf[1], gi[level], L.h, L.w, s, tp.top, tp.top_mask(), ctx->channels));
+    Timer t(ctx, s, K_OTHER, 0);
+    HIPCHK(ctx, launch_tv_finish(xi[level], ctx->channels, L.h, L.w, L.tv_partial, tvw, gi[level], 1, L.tv_means, s));
+    return NST_OK;
+}
+
+// what the loss-assembly kernel reads: every level's partial sums and normalisers; the rows of levels not in level_mask are zeros
+LossAssembly fill_loss_assembly(const nst_ctx* ctx, unsigned level_mask, float cw, float sw, float tvw, float* losses) {
+    LossAssembly la{};
+    la.levels = ctx->levels; la.nstyle = ctx->taps.nstyle; la.cw = cw; la.sw = sw; la.tvw = tvw; la.out = losses;
+    for (int i = 0; i < ctx->levels; ++i) {
+        const LevelWs& L = ctx->lv[i];
+        la.lv[i].content_partial = L.content_partial;
+        la.lv[i].content_n = L.content_n;
+        for (int k = 0; k < ctx->taps.nstyle; ++k) { la.lv[i].style_partial[k] = L.style_partial[k]; la.lv[i].style_c[k] = kCout[ctx->taps.style[k]]; }
+        la.lv[i].tv_means = L.tv_means;
+        la.lv[i].owned = (int)((level_mask >> i) & 1u);
+    }
+    return la;
+}
+
+// enqueues the whole closure on `main` (no host synchronisation; capturable unless it forks level streams)
+int closure_record(nst_ctx* ctx, const float* x, float cw, float sw, float tvw, unsigned level_mask, float* grad,
+                   float* losses, hipStream_t main) {
+    // pyramid of the optimised image (neural_style_transfer.py:170-176)
+    const float* xi[NST_MAX_LEVELS];
+    float* gi[NST_MAX_LEVELS];
+    xi[0] = x; gi[0] = grad;
+    for (int i = 1; i < ctx->levels; ++i) {
+        LevelWs& L = ctx->lv[i];
+        Timer t(ctx, main, K_OTHER, 0);
+        HIPCHK(ctx, launch_bicubic_down(xi[i - 1], ctx->channels, ctx->lv[i - 1].h, ctx->lv[i - 1].w, L.h, L.w, L.xl, main));
+        xi[i] = L.xl; gi[i] = L.gxl;
+    }
+    const bool batch = batch_eligible(ctx);
+    if (batch) {
+        const unsigned top = level_mask & 1u, rest = level_mask & ~1u;
+        if (ctx->level_split && ctx->side && !ctx->use_graph && top && rest) {
+            // nst_options.level_split: the top level's chain on the caller's stream, the lower levels' (batched among
+            // themselves) on the side stream - two chains of unequal size whose launch ramps, tails and epilogue bursts can
+            // fill one another, as two jobs on one GPU do.  Same kernels on the same tiles: bitwise the same.
+            HIPCHK(ctx, hipEventRecord(ctx->side_fork, main));
+            HIPCHK(ctx, hipStreamWaitEvent(ctx->side, ctx->side_fork, 0));
+            NSTCHK(closure_batched(ctx, xi, gi, top, cw, sw, tvw, main, 1u));
+            NSTCHK(closure_batched(ctx, xi, gi, rest, cw, sw, tvw, ctx->side, ~1u));
+            HIPCHK(ctx, hipEventRecord(ctx->side_join, ctx->side));
+            HIPCHK(ctx, hipStreamWaitEvent(main, ctx->side_join, 0));
+        } else {
+            NSTCHK(closure_batched(ctx, xi, gi, level_mask, cw, sw, tvw, main));
+        }
+    }
+    const bool multi = !batch && !ctx->single_stream && ctx->levels > 1;
+    if (multi) {
+        // the per-level streams exist only for this schedule (a stream costs device memory that HIP does not hand back)
+        for (int i = 0; i < ctx->levels; ++i) {
+            LevelWs& L = ctx->lv[i];
+            if (!L.stream) HIPCHK(ctx, hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
+            if (!L.done) HIPCHK(ctx, hipEventCreateWithFlags(&L.done, hipEventDisableTiming));
+        }
+        HIPCHK(ctx, hipEventRecord(ctx->fork, main));
+    }
+    for (int i = 0; i < ctx->levels && !batch; ++i) {
+        LevelWs& L = ctx->lv[i];
+        hipStream_t s = multi ? L.stream : main;
+        if (multi) HIPCHK(ctx, hipStreamWaitEvent(s, ctx->fork, 0));
+        // (a level another rank owns contributes nothing here: its gradient arrives by all-reduce)
+        if ((level_mask >> i) & 1u) NSTCHK(closure_per_level(ctx, xi, gi, i, cw, sw, tvw, s));
+        else HIPCHK(ctx, launch_zero(gi[i], (size_t)ctx->channels * L.h * L.w, s));
+        if (multi) HIPCHK(ctx, hipEventRecord(L.done, s));
+    }
+    if (multi)
+        for (int i = 0; i < ctx->levels; ++i) HIPCHK(ctx, hipStreamWaitEvent(main, ctx->lv[i].done, 0));
+
+    // pull the coarse-level gradients back up the bicubic chain (autograd of :173-176)
+    for (int i = ctx->levels - 1; i >= 1; --i) {
+        Timer t(ctx, main, K_OTHER, 0);
+        HIPCHK(ctx, launch_bicubic_down_bwd(gi[i], ctx->channels, ctx->lv[i - 1].h, ctx->lv[i - 1].w, ctx->lv[i].h, ctx->lv[i].w,
+                                            gi[i - 1], 1, main));
+    }
+    HIPCHK(ctx, launch_loss_assemble(fill_loss_assembly(ctx, level_mask, cw, sw, tvw, losses), main));
+    return NST_OK;
+}
+
+int window_check(nst_ctx* ctx, const float* xs, int row0, int rows, int H0) {
+    if (ctx->levels != 1) return fail(ctx, NST_E_STATE, "a stripe context is configured with levels_num = 1");
+    if (ctx->conv_mode != 2) return fail(ctx, NST_E_STATE, "the stripe closure runs on the f16x2 convolutions (NST_CONV unset)");
+    if (!ctx->taps.is_default)
+        return fail(ctx, NST_E_STATE, "the stripe closure implements the default feature maps only (nst_job_set_taps(ctx, 4, 0x2F, 1))");
+    if (ctx->channels != 3)
+        return fail(ctx, NST_E_STATE, "the stripe closure implements RGB only (nst_job_set_color(ctx, NST_COLOR_RGB))");
+    if (ctx->pool_avg)
+        return fail(ctx, NST_E_STATE, "the stripe closure implements max pooling only (nst_job_set_pooling(ctx, NST_POOL_MAX))");
+    LevelWs& L = ctx->lv[0];
+    if (!L.targets) return fail(ctx, NST_E_STATE, "targets of the stripe not set");
+    if (!xs) return fail(ctx, NST_E_ARG, "null buffer");
+    // boundaries between stripes on multiples of 16 rows (pooling alignment); only a stripe that ends with the stripe
+    // image - the bottom of the full image - may own a ragged last row group
+    const bool to_bottom = (row0 + rows == L.h);
+    if (row0 < 0 || rows < 16 || row0 % 16 || (!to_bottom && rows % 16) || row0 + rows > L.h || H0 < L.h)
+        return fail(ctx, NST_E_ARG, "stripe rows: start and interior boundaries on multiples of 16 rows, inside the stripe image");
+    if ((size_t)L.h * L.w * 64 * 4 >= 0xFFFFFF00ull) return fail(ctx, NST_E_ARG, "stripe image too large for the f16x2 kernels");
+    return NST_OK;
+}
+
+}  // namespace
+
+// ================================================================================================
+extern "C" {
+
+int nst_level_set_targets(nst_ctx* ctx, int level, const float* content, const float* style, int hs, int ws,
+                          void* stream) {
+    if (ctx) ++ctx->closure_epoch;
+    NSTCHK(bind(ctx));
+    if (level < 0 || level >= ctx->levels) return fail(ctx, NST_E_STATE, "level not configured");
+    if (!content || !style) return fail(ctx, NST_E_ARG, "null image");
+    if (hs < 16 || ws < 16) return fail(ctx, NST_E_ARG, "style image must be at least 16x16");
+    hipStream_t s = enter(ctx, stream);
+    LevelWs& L = ctx->lv[level];
+    const Taps& tp = ctx->taps;
+    // content: the content map (default ReLU(conv4_2)) of the content image, through the level's own activation buffers - by the launches the closure
+    // of this job will use (one launch per layer, Winograd F(2,3) where it applies), so that target and current features
+    // carry the same rounding: an image that IS the content image then has a content loss of (all but) exactly zero, as in
+    // the reference, whose target and current features come from one and the same forward code
+    if (batch_eligible(ctx)) {
+        const float* xi[NST_MAX_LEVELS] = {};
+        xi[level] = content;
+        const int lv1 = level;
+        NSTCHK(batched_forward(ctx, xi, &lv1, 1, s, nullptr));
+    } else {
+        NSTCHK(forward(ctx, L.acts, content, L.h, L.w, s, tp.content, ctx->channels));
+    }
+    HIPCHK(ctx, hipMemcpyAsync(L.content_t, L.acts.act[tp.content], L.content_n * 4, hipMemcpyDeviceToDevice, s));
+    // style: the Gram matrices of the style image (its own size)
+    Scratch sc(ctx, s);
+    float* part = nullptr;
+    NSTCHK(alloc_acts(ctx, sc.acts, hs, ws));
+    NSTCHK(sc.alloc(&part, gram_part_floats_for(tp, hs, ws)));
+    NSTCHK(forward(ctx, sc.acts, style, hs, ws, s, tp.style[tp.nstyle - 1], ctx->channels));
+    for (int k = 0; k < tp.nstyle; ++k) {
+        const int l = tp.style[k];
+        const StyleTerm st = style_term(tp, k, sc.acts, 0.f);
+        NSTCHK(gram_of(ctx, sc.acts.act[l], st.N, st.C, ctx->conv_mode == 2 ? amax_act(sc.acts, l) : nullptr, (float)st.divisor, part, nullptr, 0.f, L.gram_t[k],
+                       nullptr, nullptr, nullptr, nullptr, s));
+    }
+    NSTCHK(sc.finish());
+    L.targets = true;
+    return NST_OK;
+}
+
+int nst_closure(nst_ctx* ctx, const float* x, float cw, float sw, float tvw, float* grad, float* losses, void* stream) {
+    return nst_closure_levels(ctx, x, cw, sw, tvw, 0xFFFFFFFFu, grad, losses, stream);
+}
+
+int nst_closure_levels(nst_ctx* ctx, const float* x, float cw, float sw, float tvw, unsigned level_mask, float* grad,
+                       float* losses, void* stream) {
+    NSTCHK(bind(ctx));
+    if (ctx->levels < 1) return fail(ctx, NST_E_STATE, "nst_job_configure has not been called");
+    if (!x || !grad || !losses) return fail(ctx, NST_E_ARG, "null buffer");
+    for (int i = 0; i < ctx->levels; ++i)
+        if (((level_mask >> i) & 1u) && !ctx->lv[i].targets)
+            return fail(ctx, NST_E_STATE, "targets of level " + std::to_string(i) + " not set");
+    hipStream_t main = enter(ctx, stream);
+    if (ctx->timing >= 2) NSTCHK(fold_timed(ctx));
+    ctx->timed.clear();
+    ctx->ev_used = 0;
+    ctx->timed_valid = false;
+    // mode 4: event pairs around the conv launches of every fourth closure only - a pair around each of the 24 conv
+    // launches of EVERY closure (mode 3) costs 5 % of the closure rate at 9.5 ms per closure
+    ctx->sample_now = (ctx->timing != 4) || ((ctx->closure_seq++ & 3) == 0);
+    if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->t0, main));
+
+    // Optional (NST_GRAPH=1): replay the ~110 dependent launches as a hipGraph.  Captured the second consecutive time the
+    // same buffers / weights / mask are passed (optimiser drivers always pass the same ones), never while per-launch
+    // timing is on.  The closure holds kernel nodes only: hipMemsetAsync nodes were NOT ordered against the kernels
+    // around them on replay (absmax records zeroed late -> garbage scales, run-to-run different losses), which is why
+    // every zero fill in the closure is launch_zero.  Measured gain: none (the host runs ~16 ms ahead of the GPU).
+    const nst_ctx::GraphKey key{x, grad, losses, cw, sw, tvw, level_mask};
+    const bool same_as_last = std::memcmp(&key, &ctx->glast, sizeof(key)) == 0;
+    ctx->glast = key;
+    bool done = false;
+    if (ctx->use_graph && ctx->timing < 2 && batch_eligible(ctx) && same_as_last) {
+        if (!ctx->gexec || std::memcmp(&key, &ctx->gkey, sizeof(key)) != 0) {
+            if (ctx->gexec) { (void)hipGraphExecDestroy(ctx->gexec); ctx->gexec = nullptr; }
+            hipGraph_t graph = nullptr;
+            HIPCHK(ctx, hipStreamBeginCapture(ctx->gstream, hipStreamCaptureModeThreadLocal));
+            const int rc = closure_record(ctx, x, cw, sw, tvw, level_mask, grad, losses, ctx->gstream);
+            const hipError_t ce = hipStreamEndCapture(ctx->gstream, &graph);
+            if (rc != NST_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
+            HIPCHK(ctx, ce);
+            const hipError_t ie = hipGraphInstantiate(&ctx->gexec, graph, nullptr, nullptr, 0);
+            (void)hipGraphDestroy(graph);
+            HIPCHK(ctx, ie);
+            ctx->gkey = key;
+        }
+        HIPCHK(ctx, hipGraphLaunch(ctx->gexec, main));
+        done = true;
+    }
+    if (!done) NSTCHK(closure_record(ctx, x, cw, sw, tvw, level_mask, grad, losses, main));
+    if (ctx->timing) { HIPCHK(ctx, hipEventRecord(ctx->t1, main)); ctx->timed_valid = true; }
+    mark(ctx, main);
+    return NST_OK;
+}
+
+// ---- stripe (window) closure: spatial sharding of one pyramid level -------------------------------------
+int nst_window_sums_count(size_t* count) {
+    if (!count) return fail(nullptr, NST_E_ARG, "null argument");
+    *count = kWinSums;
+    return NST_OK;
+}
+
+int nst_window_begin(nst_ctx* ctx, const float* xs, int row0, int rows, int H0, float* sums, void* stream) {
+    NSTCHK(bind(ctx));
+    NSTCHK(window_check(ctx, xs, row0, rows, H0));
+    if (!sums) return fail(ctx, NST_E_ARG, "null buffer");
+    hipStream_t s = enter(ctx, stream);
+    LevelWs& L = ctx->lv[0];
+    ActSet& a = L.acts;
+    Window win{row0, rows, H0, sums};
+    const int lv[1] = {0};
+    const float* xi[1] = {xs};
+    NSTCHK(batched_forward(ctx, xi, lv, 1, s, &win));
+    // un-normalised Gram sums of the owned rows
+    for (int q = 0; q < ctx->taps.nstyle; ++q) {
+        const int l = ctx->taps.style[q], C = kCout[l];
+        const size_t off = (size_t)win_r0(win, kScale[l]) * a.w[l] * C;
+        const size_t N = (size_t)win_nr(win, kScale[l]) * a.w[l];
+        const int ns = gram_nsplit(C, N);
+        HIPCHK(ctx, launch_gram_partial(a.act[l] + off, N, C, ns, amax_act(a, l), L.gram_part, s));
+        HIPCHK(ctx, launch_gram_finish(L.gram_part, gram_nslabs(C, ns), C, 1.f, nullptr, 0.f, sums + kWinGramOff[q], nullptr, nullptr,
+                                       nullptr, nullptr, s));
+    }
+    // content: sum of squared differences over the owned rows
+    {
+        const int m = ctx->taps.content;
+        const size_t off = (size_t)win_r0(win, kScale[m]) * a.w[m] * kCout[m];
+        const size_t cnt = (size_t)win_nr(win, kScale[m]) * a.w[m] * kCout[m];
+        HIPCHK(ctx, launch_mse_grad(a.act[m] + off, L.content_t + off, cnt, 0.f, nullptr, L.content_partial, s));
+        HIPCHK(ctx, launch_sum_doubles(L.content_partial, MSE_BLOCKS, 1, 0, sums + kWinScalarOff, s));
+    }
+    // total variation: sums of |dx|, |dy| over the owned rows (batched_forward ran the windowed partial pass)
+    HIPCHK(ctx, launch_sum_doubles(L.tv_partial, TV_BLOCKS, 2, 0, sums + kWinScalarOff + 1, s));
+    HIPCHK(ctx, launch_sum_doubles(L.tv_partial, TV_BLOCKS, 2, 1, sums + kWinScalarOff + 2, s));
+    mark(ctx, s);
+    return NST_OK;
+}
+
+int nst_window_end(nst_ctx* ctx, const float* xs, int row0, int rows, int H0, float cw, float sw, float tvw, float* sums,
+                   float* gxs, float* losses, void* stream) {
+    NSTCHK(bind(ctx));
+    NSTCHK(window_check(ctx, xs, row0, rows, H0));
+    if (!sums || !gxs || !losses) return fail(ctx, NST_E_ARG, "null buffer");
+    hipStream_t s = enter(ctx, stream);
+    LevelWs& L = ctx->lv[0];
+    ActSet& a = L.acts;
+    Window win{row0, rows, H0, sums};
+    // S = d loss / d G from the Gram sums of ALL stripes, normalised by the full image
+    for (int q = 0; q < ctx->taps.nstyle; ++q) {
+        const StyleTerm st = style_term(ctx->taps, q, a, sw, H0);
+        HIPCHK(ctx, launch_gram_finish(sums + kWinGramOff[q], 1, st.C, (float)st.divisor, L.gram_t[q], st.coef, nullptr, L.S[q], L.S_bf[q],
+                                       amax_S(a, q), L.style_partial[q], s));
+    }
+    const double nx = 3.0 * H0 * (L.w - 1), ny = 3.0 * (H0 - 1) * L.w;
+    HIPCHK(ctx, launch_window_scalars(sums + kWinScalarOff, nx, ny, L.tv_means, L.content_partial, 0, s));   // means only
+    const int lv[1] = {0};
+    const float* xi[1] = {xs};
+    float* gi[1] = {gxs};
+    NSTCHK(batched_backward(ctx, xi, gi, lv, 1, cw, tvw, s, &win, L.tv_means, nx, ny));
+    // the level's loss row from the global sums (the backward's content pass left this stripe's partials behind)
+    HIPCHK(ctx, launch_window_scalars(sums + kWinScalarOff, nx, ny, L.tv_means, L.content_partial, MSE_BLOCKS, s));
+    LossAssembly la = fill_loss_assembly(ctx, 1u, cw, sw, tvw, losses);
+    const int m = ctx->taps.content;
+    la.lv[0].content_n = (size_t)(H0 >> kScale[m]) * a.w[m] * kCout[m];      // the full image's, not the stripe's
+    HIPCHK(ctx, launch_loss_assemble(la, s));
+    mark(ctx, s);
+    return NST_OK;
+}
+
+}  // extern "C"

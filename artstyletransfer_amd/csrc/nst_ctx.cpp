@@ -1,0 +1,792 @@
+// nst_ctx.cpp - context and job state of libnst_hip.so (include/nst_hip.h): the VGG19 weights re-laid-out for the gfx950
+// kernels (three arithmetic modes), context creation and destruction, the job settings (pyramid, taps, colour, pooling) with
+// the per-level workspace they size, the ordering of caller streams against context-owned memory, and launch timing.
+//
+// Host-side control only; every FLOP and byte of the path is in the .hip kernels.
+#include <algorithm>
+#include <atomic>
+#include <climits>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+
+#include "nst_ctx.h"
+
+using namespace nst;
+
+namespace {
+thread_local std::string g_err;
+}
+
+int nst::fail(nst_ctx* ctx, int code, const std::string& msg) {
+    if (ctx) ctx->err = msg; else g_err = msg;
+    return code;
+}
+
+namespace {
+// Debugging aid (tools/check_uninit_reads.py): NST_POISON_ALLOC=all | <first>-<last> fills the allocations with those
+// sequence numbers with 0xFF bytes (NaN as floats, all-ones as masks), so that a kernel which reads memory nobody wrote -
+// harmless on a fresh process, whose pages arrive zeroed, and wrong once the allocator recycles another context's blocks -
+// shows in the results of a single job.
+void poison_if_asked(void* p, size_t bytes) {
+    static const char* spec = getenv("NST_POISON_ALLOC");
+    static std::atomic<long> seq{0};
+    if (!spec || !*spec) return;
+    const long k = seq++;
+    long lo = 0, hi = -1;
+    if (strcmp(spec, "all") == 0) hi = LONG_MAX;
+    else if (sscanf(spec, "%ld-%ld", &lo, &hi) != 2) return;
+    if (k >= lo && k <= hi) { (void)hipMemset(p, 0xFF, bytes); (void)hipStreamSynchronize(nullptr); }
+    if (getenv("NST_POISON_TRACE")) fprintf(stderr, "nst alloc #%ld: %zu bytes%s\n", k, bytes, (k >= lo && k <= hi) ? " (poisoned)" : "");
+}
+}  // namespace
+// hipMemset on device memory is enqueued on the NULL stream and returns before it has run: with another context's work
+// queued there (two jobs per GPU is the scheduler's default) it lands AFTER the first kernels of this context, which run on
+// the caller's non-blocking stream - and wipes what they wrote (absmax records -> a zero scale -> NaN targets; Adam
+// moments; the packed loss rows).  Set-up-time zero fills therefore run on a stream of their own and are waited for:
+// nothing of a context rides on the null stream.
+extern "C" int nst_internal_zero_now(void* p, size_t bytes) {
+    hipStream_t zs = nullptr;
+    hipError_t e = hipStreamCreateWithFlags(&zs, hipStreamNonBlocking);
+    if (e != hipSuccess) return 1;
+    e = hipMemsetAsync(p, 0, bytes, zs);
+    if (e == hipSuccess) e = hipStreamSynchronize(zs);
+    (void)hipStreamDestroy(zs);
+    return e == hipSuccess ? 0 : 1;
+}
+
+namespace nst {
+
+int dev_alloc(nst_ctx* ctx, void** p, size_t bytes) {
+    if (bytes == 0) bytes = 16;
+    hipError_t e = hipMalloc(p, bytes);
+    if (e != hipSuccess) return fail(ctx, NST_E_NOMEM, std::string("hipMalloc(") + std::to_string(bytes) + "): " + hipGetErrorString(e));
+    poison_if_asked(*p, bytes);
+    ctx->bytes += bytes;
+    return NST_OK;
+}
+
+int alloc_acts(nst_ctx* ctx, ActSet& a, int h, int w) {
+    a.bytes = 0;
+    for (int l = 0; l < NL; ++l) {
+        a.h[l] = h >> kScale[l];
+        a.w[l] = w >> kScale[l];
+        if (a.h[l] < 1 || a.w[l] < 1) return fail(ctx, NST_E_ARG, "image too small for VGG19 (needs >= 16 px per side)");
+        const size_t n = (size_t)a.h[l] * a.w[l] * kCout[l];
+        NSTCHK(dev_alloc_t(ctx, &a.act[l], n));
+        a.bytes += n * 4;
+    }
+    for (int k = 0; k < 4; ++k) {
+        const int l = kPoolAfter[k];
+        const size_t n = (size_t)(a.h[l] / 2) * (a.w[l] / 2) * kCout[l];
+        NSTCHK(dev_alloc_t(ctx, &a.pool[k], n));
+        a.bytes += n * 4;
+        NSTCHK(dev_alloc_t(ctx, &a.pcode[k], n / 8));          // n / 32 channel groups x 4 words
+        a.bytes += n / 8 * 4;
+    }
+    size_t need = 0;
+    for (int l = 1; l < NL; ++l) {
+        const size_t px = (size_t)a.h[l] * a.w[l];
+        const int sf = std::max(conv_ksplit(a.h[l], a.w[l], kCin[l], kCout[l]), conv_bf3_ksplit(a.h[l], a.w[l], kCin[l], kCout[l]));
+        const int sb = std::max(conv_ksplit(a.h[l], a.w[l], kCout[l], kCin[l]), conv_bf3_ksplit(a.h[l], a.w[l], kCout[l], kCin[l]));
+        const size_t fwd = (size_t)sf * px * kCout[l];
+        const size_t bwd = (size_t)sb * px * kCin[l];
+        if (fwd > px * kCout[l] && fwd > need) need = fwd;
+        if (bwd > px * kCin[l] && bwd > need) need = bwd;
+    }
+    // layers m whose ReLU mask a non-pooling input-gradient launch consumes
+    const int mask_layers[9] = {0, 2, 4, 5, 6, 8, 9, 10, 12};     // (12: the Gram backward at relu5_1)
+    for (int k = 0; k < 9; ++k) {
+        const int m = mask_layers[k];
+        const size_t nw = (size_t)a.h[m] * a.w[m] * (kCout[m] / 32);
+        NSTCHK(dev_alloc_t(ctx, &a.bits[m], nw));
+        a.bytes += nw * 4;
+    }
+    NSTCHK(dev_alloc_t(ctx, &a.amax, (size_t)AMAX_IDS * NST_AMAX_SLOTS));
+    a.bytes += (size_t)AMAX_IDS * NST_AMAX_SLOTS * 4;
+    if (nst_internal_zero_now(a.amax, (size_t)AMAX_IDS * NST_AMAX_SLOTS * 4)) return fail(ctx, NST_E_HIP, "hipMemset failed");
+    a.splitk_floats = need;
+    if (need) {
+        NSTCHK(dev_alloc_t(ctx, &a.splitk, need));
+        a.bytes += need * 4;
+    }
+    return NST_OK;
+}
+void free_acts(nst_ctx* ctx, ActSet& a) {
+    for (int l = 0; l < NL; ++l) { dev_free(a.act[l]); a.act[l] = nullptr; }
+    for (int k = 0; k < 4; ++k) { dev_free(a.pool[k]); a.pool[k] = nullptr; dev_free(a.pcode[k]); a.pcode[k] = nullptr; }
+    dev_free(a.splitk); a.splitk = nullptr; a.splitk_floats = 0;
+    dev_free(a.amax); a.amax = nullptr;
+    for (int l = 0; l < NL; ++l) { dev_free(a.bits[l]); a.bits[l] = nullptr; a.bits_valid[l] = false; }
+    if (ctx->bytes >= a.bytes) ctx->bytes -= a.bytes;
+    a.bytes = 0;
+}
+
+}  // namespace nst
+
+namespace {
+
+// fp32 -> three bf16 pieces that sum to it exactly (same cut as conv_bf3.hip::cut3)
+void cut3_host(float a, uint16_t& h, uint16_t& m, uint16_t& l) {
+    uint32_t u; std::memcpy(&u, &a, 4);
+    const uint32_t uh = u & 0xFFFF0000u;
+    float fh; std::memcpy(&fh, &uh, 4);
+    const float r1 = a - fh;
+    uint32_t u1; std::memcpy(&u1, &r1, 4);
+    const uint32_t um = u1 & 0xFFFF0000u;
+    float fm; std::memcpy(&fm, &um, 4);
+    const float r2 = r1 - fm;
+    uint32_t u2; std::memcpy(&u2, &r2, 4);
+    h = (uint16_t)(uh >> 16); m = (uint16_t)(um >> 16); l = (uint16_t)(u2 >> 16);
+}
+// w: [taps][rows][K] fp32  ->  out: [taps][rows][K/32][3][32] bf16
+void make_bf3(const float* w, int taps, int rows, int K, std::vector<uint16_t>& out) {
+    const int nch = K / 32;
+    out.assign((size_t)taps * rows * nch * 96, 0);
+    for (int t = 0; t < taps; ++t)
+        for (int r = 0; r < rows; ++r)
+            for (int k = 0; k < K; ++k) {
+                uint16_t h, m, l;
+                cut3_host(w[((size_t)t * rows + r) * K + k], h, m, l);
+                const size_t base = (((size_t)t * rows + r) * nch + k / 32) * 96 + (k % 32);
+                out[base] = h; out[base + 32] = m; out[base + 64] = l;
+            }
+}
+
+// fp32 <-> fp16 on the host with integer arithmetic (round to nearest even, subnormals, overflow to infinity: bit-identical to
+// the compiler's _Float16 conversions over 4e7 random values) - without F16C code generation those go through a soft-float
+// call each, and a context converts ~1e8 weights: 0.5 s of its 0.8 s creation.
+static inline uint16_t f32_to_f16(float f) {
+    uint32_t x; std::memcpy(&x, &f, 4);
+    const uint32_t sign = (x >> 16) & 0x8000u;
+    x &= 0x7FFFFFFFu;
+    uint32_t o;
+    if (x >= 0x47800000u) {                      // >= 65536 (rounds to infinity), infinity, NaN
+        o = (x > 0x7F800000u) ? 0x7E00u : 0x7C00u;
+    } else if (x < 0x38800000u) {                // < 2^-14: a half subnormal or zero: round(f * 2^24) through a float add
+        float a; std::memcpy(&a, &x, 4);
+        const uint32_t magic_bits = (uint32_t)((127 - 15) + (23 - 10) + 1) << 23;
+        float magic; std::memcpy(&magic, &magic_bits, 4);
+        a += magic;
+        uint32_t ab; std::memcpy(&ab, &a, 4);
+        o = ab - magic_bits;
+    } else {                                     // normal: re-bias the exponent, round to nearest even on bit 13
+        const uint32_t odd = (x >> 13) & 1u;
+        x += 0xC8000FFFu + odd;
+        o = x >> 13;
+    }
+    return (uint16_t)(sign | o);
+}
+static inline float f16_to_f32(uint16_t h) {
+    const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, e = (h >> 10) & 31u, m = h & 0x3FFu;
+    uint32_t b;
+    if (e == 0) { const float f = (float)m * 5.9604644775390625e-8f; std::memcpy(&b, &f, 4); b |= sign; }
+    else if (e == 31) b = sign | 0x7F800000u | (m << 13);
+    else b = sign | ((e + 112u) << 23) | (m << 13);
+    float r; std::memcpy(&r, &b, 4);
+    return r;
+}
+
+// w: [taps][rows][K] fp32  ->  out: [taps][rows][K/kc][2][kc] fp16 pieces of w * s, s = the power of two that
+// brings the largest |w| into [2^14, 2^15); *inv = 1 / s (same cut as conv_h2.hip::cut2x4).  kc = channels per K
+// chunk of the kernel shape that consumes these weights: 32 when `rows` (its output channels) is a multiple of
+// 128 and K (its input channels) > NST_H2_SHORTK_CIN, else 16 (conv_h2.hip, shapes in use).
+void make_h2(const float* w, int taps, int rows, int K, std::vector<uint16_t>& out, float* inv) {
+    const int kc = (rows % 128 == 0 && K > NST_H2_SHORTK_CIN) ? 32 : 16;
+    const size_t n = (size_t)taps * rows * K;
+    float mx = 0.f;
+    for (size_t i = 0; i < n; ++i) mx = std::max(mx, std::fabs(w[i]));
+    int ex = 0;
+    if (mx > 0.f) (void)std::frexp(mx, &ex);          // mx = f * 2^ex, f in [0.5, 1)
+    const float s = std::ldexp(1.f, 15 - ex);          // mx * s in [2^14, 2^15)
+    *inv = std::ldexp(1.f, ex - 15);
+    const int nch = K / kc;
+    out.assign((size_t)taps * rows * nch * 2 * kc, 0);
+    for (int t = 0; t < taps; ++t)
+        for (int r = 0; r < rows; ++r)
+            for (int k = 0; k < K; ++k) {
+                const float x = w[((size_t)t * rows + r) * K + k] * s;
+                const uint16_t uh = f32_to_f16(x);
+                const uint16_t ul = f32_to_f16((x - f16_to_f32(uh)) * 2048.f);
+                const size_t base = (((size_t)t * rows + r) * nch + k / kc) * 2 * kc + (k % kc);
+                out[base] = uh; out[base + kc] = ul;
+            }
+}
+
+// w: [9 taps = ky*3 + kx][rows = Cout][K = Cin] fp32  ->  the 1-D Winograd F(2,3) weights of conv_wino.hip: for every ky the
+// four transformed taps u0 = g0, u1 = (g0 + g1 + g2)/2, u2 = (g0 - g1 + g2)/2, u3 = g2 (fp64), scaled by the power of two that
+// brings the largest |u| into [2^14, 2^15), cut into two fp16 pieces, in MFMA FRAGMENT order - 16-byte units
+// [Cout/128][K/32][ky][wave = xi + 4 wn][k-step][n tile][piece][lane]: lane (r = lane & 31, h = lane >> 5) holds the 8 input
+// channels chunk*32 + kstep*16 + 8 h .. + 7 of output channel ct*128 + wn*64 + ntile*32 + r.
+void make_wino(const float* w, int rows, int K, std::vector<uint16_t>& out, float* inv) {
+    const int nct = rows / 128, nch = K / 32;
+    // the transformed taps once, [ky][xi][Cout][Cin], and their largest magnitude
+    std::vector<float> U((size_t)12 * rows * K);
+    float mx = 0.f;
+    for (int ky = 0; ky < 3; ++ky)
+        for (int o = 0; o < rows; ++o) {
+            const float* g0 = w + ((size_t)(ky * 3 + 0) * rows + o) * K;
+            const float* g1 = w + ((size_t)(ky * 3 + 1) * rows + o) * K;
+            const float* g2 = w + ((size_t)(ky * 3 + 2) * rows + o) * K;
+            float* u0 = U.data() + ((size_t)(ky * 4 + 0) * rows + o) * K;
+            float* u1 = U.data() + ((size_t)(ky * 4 + 1) * rows + o) * K;
+            float* u2 = U.data() + ((size_t)(ky * 4 + 2) * rows + o) * K;
+            float* u3 = U.data() + ((size_t)(ky * 4 + 3) * rows + o) * K;
+            for (int c = 0; c < K; ++c) {
+                const double a = g0[c], b = g1[c], d = g2[c];
+                u0[c] = (float)a;
+                u1[c] = (float)(0.5 * (a + b + d));
+                u2[c] = (float)(0.5 * (a - b + d));
+                u3[c] = (float)d;
+                mx = std::max(std::max(mx, std::fabs(u0[c])), std::max(std::fabs(u1[c]), std::max(std::fabs(u2[c]), std::fabs(u3[c]))));
+            }
+        }
+    int ex = 0;
+    if (mx > 0.f) (void)std::frexp(mx, &ex);
+    const float s = std::ldexp(1.f, 15 - ex);
+    *inv = std::ldexp(1.f, ex - 15);
+    out.assign((size_t)nct * nch * 3 * 8 * 2 * 2 * 2 * 64 * 8, 0);
+    for (int ct = 0; ct < nct; ++ct)
+        for (int ch = 0; ch < nch; ++ch)
+            for (int ky = 0; ky < 3; ++ky)
+                for (int wave = 0; wave < 8; ++wave)
+                    for (int ks = 0; ks < 2; ++ks)
+                        for (int nt = 0; nt < 2; ++nt) {
+                            const int x = wave & 3, wn = wave >> 2;
+                            const size_t unit0 = ((((((size_t)(ct * nch + ch) * 3 + ky) * 8 + wave) * 2 + ks) * 2 + nt) * 2) * 64;
+                            for (int lane = 0; lane < 64; ++lane) {
+                                const int r = lane & 31, h = lane >> 5;
+                                const int o = ct * 128 + wn * 64 + nt * 32 + r;
+                                const float* src = U.data() + ((size_t)(ky * 4 + x) * rows + o) * K + ch * 32 + ks * 16 + 8 * h;
+                                uint16_t* hi_dst = out.data() + (unit0 + lane) * 8;             // piece 0
+                                uint16_t* lo_dst = out.data() + (unit0 + 64 + lane) * 8;        // piece 1
+                                for (int j = 0; j < 8; ++j) {
+                                    const float v = src[j] * s;
+                                    hi_dst[j] = f32_to_f16(v);
+                                    lo_dst[j] = f32_to_f16((v - f16_to_f32(hi_dst[j])) * 2048.f);
+                                }
+                            }
+                        }
+}
+
+// the buffers whose size depends on the taps: content target, Gram targets / factors / partial sums, partial-Gram workspace
+void free_tap_buffers(nst_ctx* ctx, LevelWs& L) {
+    auto drop = [&](void* p, size_t bytes) { if (p) { dev_free(p); if (ctx->bytes >= bytes) ctx->bytes -= bytes; } };
+    drop(L.content_t, L.content_n * 4); L.content_t = nullptr; L.content_n = 0;
+    for (int k = 0; k < kMaxStyle; ++k) {
+        const size_t C = (size_t)L.tap_c[k];
+        drop(L.gram_t[k], C * C * 4); drop(L.S[k], C * C * 4); drop(L.S_bf[k], C * C * 6);
+        drop(L.style_partial[k], (size_t)gram_finish_blocks((int)std::max<size_t>(C, 1)) * 8);
+        L.gram_t[k] = nullptr; L.S[k] = nullptr; L.S_bf[k] = nullptr; L.style_partial[k] = nullptr; L.tap_c[k] = 0;
+    }
+    drop(L.gram_part, L.gram_part_floats * 4); L.gram_part = nullptr; L.gram_part_floats = 0;
+}
+int alloc_tap_buffers(nst_ctx* ctx, LevelWs& L) {
+    const Taps& tp = ctx->taps;
+    const int m = tp.content;
+    L.content_n = (size_t)L.acts.h[m] * L.acts.w[m] * kCout[m];
+    NSTCHK(dev_alloc_t(ctx, &L.content_t, L.content_n));
+    for (int k = 0; k < tp.nstyle; ++k) {
+        const int C = kCout[tp.style[k]];
+        L.tap_c[k] = C;
+        NSTCHK(dev_alloc_t(ctx, &L.gram_t[k], (size_t)C * C));
+        NSTCHK(dev_alloc_t(ctx, &L.S[k], (size_t)C * C));
+        NSTCHK(dev_alloc_t(ctx, &L.S_bf[k], (size_t)C * C * 3));
+        NSTCHK(dev_alloc_t(ctx, &L.style_partial[k], gram_finish_blocks(C)));
+    }
+    L.gram_part_floats = gram_part_floats_for(tp, L.h, L.w);
+    NSTCHK(dev_alloc_t(ctx, &L.gram_part, L.gram_part_floats));
+    return NST_OK;
+}
+
+// the level image and its gradient (levels >= 1): their size follows the channel count (nst_job_set_color)
+void free_level_image(nst_ctx* ctx, LevelWs& L) {
+    for (float** p : {&L.xl, &L.gxl}) {
+        if (*p) { dev_free(*p); if (ctx->bytes >= L.xl_floats * 4) ctx->bytes -= L.xl_floats * 4; }
+        *p = nullptr;
+    }
+    L.xl_floats = 0;
+}
+int alloc_level_image(nst_ctx* ctx, LevelWs& L) {
+    L.xl_floats = (size_t)ctx->channels * L.h * L.w;
+    NSTCHK(dev_alloc_t(ctx, &L.xl, L.xl_floats));
+    NSTCHK(dev_alloc_t(ctx, &L.gxl, L.xl_floats));
+    return NST_OK;
+}
+
+void free_level(nst_ctx* ctx, LevelWs& L) {
+    free_acts(ctx, L.acts);
+    dev_free(L.gbuf[0]); dev_free(L.gbuf[1]); dev_free(L.xl); dev_free(L.gxl);
+    free_tap_buffers(ctx, L);
+    dev_free(L.content_partial); dev_free(L.tv_partial); dev_free(L.tv_means);
+    if (L.stream) (void)hipStreamDestroy(L.stream);
+    if (L.done) (void)hipEventDestroy(L.done);
+    L = LevelWs();
+}
+
+}  // namespace
+
+namespace nst {
+
+// folds the event pairs of the previous closure into the accumulators (waits for them to complete)
+int fold_timed(nst_ctx* ctx) {
+    if (!ctx->timed_valid) return NST_OK;
+    HIPCHK(ctx, hipEventSynchronize(ctx->t1));
+    float ms = 0.f;
+    HIPCHK(ctx, hipEventElapsedTime(&ms, ctx->t0, ctx->t1));
+    ctx->acc_closure_ms += ms;
+    ctx->acc_closures += 1;
+    if (!ctx->timed.empty()) ctx->acc_sampled += 1;
+    for (const TimedLaunch& t : ctx->timed) {
+        float d = 0.f;
+        HIPCHK(ctx, hipEventSynchronize(t.b));
+        HIPCHK(ctx, hipEventElapsedTime(&d, t.a, t.b));
+        ctx->acc_ms[t.cls] += d;
+        ctx->acc_flops[t.cls] += t.flops;
+        {
+            // f16x2: 3 MFMAs per product block, bf16x3: 6, fp32 MFMA: 1 (conv1_1 and the streaming kernels run no 16-bit MFMA)
+            const double mode = (t.cls == K_CONV3 || t.cls == K_GRAM) ? (ctx->conv_mode == 2 ? 3.0 : ctx->conv_mode == 1 ? 6.0 : 1.0) : 1.0;
+            ctx->acc_mfma[t.cls] += t.flops * (t.mfma_factor >= 0.0 ? t.mfma_factor : mode);
+        }
+        ctx->acc_launches[t.cls] += 1;
+    }
+    ctx->timed.clear();
+    ctx->ev_used = 0;
+    ctx->timed_valid = false;
+    return NST_OK;
+}
+
+int bind(nst_ctx* ctx) {
+    if (!ctx) return fail(nullptr, NST_E_ARG, "null context");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return NST_OK;
+}
+
+// Remember where the context's work ends: an event on the caller's stream after the last launch of an entry point that
+// reads or writes context-owned memory.
+void mark(nst_ctx* ctx, hipStream_t s) {
+    if (ctx && ctx->tail && hipEventRecord(ctx->tail, s) == hipSuccess) { ctx->tail_stream = s; ctx->tail_set = true; }
+}
+// The entry points that read or write context-owned memory (targets, workspace, level images) are ordered as they are
+// issued, whatever stream each is issued on: a call on ANOTHER stream than the previous one first makes its stream wait for
+// the context's tail event.  One tail event then covers everything the context has in flight - what nst_job_configure and
+// nst_ctx_destroy wait for before they free the workspace - without relying on hipFree's implicit synchronisation, and a
+// read-back issued on a second stream (nst_level_image after nst_closure) sees the closure's results.
+hipStream_t enter(nst_ctx* ctx, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (ctx->tail_set && s != ctx->tail_stream) (void)hipStreamWaitEvent(s, ctx->tail, 0);
+    return s;
+}
+// Wait until nothing on the device uses the context's memory any more: its tail event and its own streams - NOT
+// hipDeviceSynchronize, which would stall the other job sharing the GPU (two jobs per GPU is the scheduler's default).
+void quiesce(nst_ctx* ctx) {
+    if (ctx->tail) (void)hipEventSynchronize(ctx->tail);
+    for (int i = 0; i < NST_MAX_LEVELS; ++i)
+        if (ctx->lv[i].stream) (void)hipStreamSynchronize(ctx->lv[i].stream);
+    if (ctx->gstream) (void)hipStreamSynchronize(ctx->gstream);
+    if (ctx->side) (void)hipStreamSynchronize(ctx->side);
+}
+
+}  // namespace nst
+
+namespace {
+
+int env_flag(const char* name, int dflt) {
+    const char* e = getenv(name);
+    if (!e || !e[0]) return dflt;
+    return std::atoi(e);
+}
+
+// What a closure remembered is void once the job changes: the captured graph and the keys it was captured under, and
+// (drop_targets) every level's targets
+void drop_closure_state(nst_ctx* ctx, bool drop_targets) {
+    if (ctx->gexec) { (void)hipGraphExecDestroy(ctx->gexec); ctx->gexec = nullptr; }
+    ctx->gkey = {}; ctx->glast = {};
+    for (int i = 0; drop_targets && i < ctx->levels; ++i) ctx->lv[i].targets = false;
+}
+
+}  // namespace
+
+// ================================================================================================
+extern "C" {
+
+int nst_version(void) { return 200; }
+
+const char* nst_last_error(const nst_ctx* ctx) { return ctx ? ctx->err.c_str() : g_err.c_str(); }
+
+int nst_device_count(int* count) {
+    if (!count) return fail(nullptr, NST_E_ARG, "count is null");
+    int n = 0;
+    hipError_t e = hipGetDeviceCount(&n);
+    if (e != hipSuccess) { *count = 0; return fail(nullptr, NST_E_HIP, hipGetErrorString(e)); }
+    *count = n;
+    return NST_OK;
+}
+
+void nst_options_default(nst_options* o) {
+    if (!o) return;
+    o->struct_size = (int)sizeof(nst_options);
+    o->conv_mode = -1; o->batched = -1; o->single_stream = -1; o->use_graph = -1; o->h2_band_rows = -1; o->lbfgs_gram = -1;
+    o->h2_mfma16 = -1; o->h2_wg256 = -1; o->h2_tile_rows = -1; o->gram_overlap = -1; o->h2_persist = -1; o->level_split = -1; o->h2_winograd = -1;
+}
+
+int nst_ctx_create(int device, const float* const* weights, const float* const* biases, nst_ctx** out) {
+    return nst_ctx_create_ex(device, weights, biases, nullptr, out);
+}
+
+int nst_ctx_create_ex(int device, const float* const* weights, const float* const* biases, const nst_options* opts_in,
+                      nst_ctx** out) {
+    if (!weights || !biases || !out) return fail(nullptr, NST_E_ARG, "null argument");
+    nst_options opts;
+    nst_options_default(&opts);
+    if (opts_in) {
+        if (opts_in->struct_size != (int)sizeof(nst_options)) return fail(nullptr, NST_E_ARG, "nst_options.struct_size mismatch (use nst_options_default)");
+        opts = *opts_in;
+    }
+    for (int l = 0; l < NL; ++l)
+        if (!weights[l] || !biases[l]) return fail(nullptr, NST_E_ARG, "null weight/bias pointer");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(nullptr, NST_E_HIP, "no HIP device visible");
+    if (device < 0 || device >= ndev) return fail(nullptr, NST_E_ARG, "device index out of range");
+    nst_ctx* ctx = new (std::nothrow) nst_ctx();
+    if (!ctx) return fail(nullptr, NST_E_NOMEM, "out of host memory");
+    ctx->device = device;
+    auto bail = [&](int code) { g_err = ctx->err; nst_ctx_destroy(ctx); return code; };
+    if (hipSetDevice(device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return bail(NST_E_HIP); }
+    hipError_t e = conv_mfma_init_device();
+    if (e == hipSuccess) e = conv_bf3_init_device();
+    if (e == hipSuccess) e = conv_h2_init_device();
+    if (e == hipSuccess) e = conv_wino_init_device();
+    if (e == hipSuccess) e = gram_init_device();
+    // options: an explicit argument wins; -1 falls back to the environment (read here, once), then to the default
+    if (opts.conv_mode >= 0) {
+        if (opts.conv_mode > NST_CONV_F16X2) { ctx->err = "nst_options.conv_mode must be NST_CONV_F32, NST_CONV_BF16X3 or NST_CONV_F16X2"; return bail(NST_E_ARG); }
+        ctx->conv_mode = opts.conv_mode;
+    } else {
+        const char* cm = getenv("NST_CONV");
+        if (cm && std::strcmp(cm, "f32") == 0) ctx->conv_mode = 0;
+        else if (cm && std::strcmp(cm, "bf16x3") == 0) ctx->conv_mode = 1;
+        else if (cm && std::strcmp(cm, "f16x2") == 0) ctx->conv_mode = 2;
+        else if (cm && cm[0]) { ctx->err = "NST_CONV must be f32, bf16x3 or f16x2"; return bail(NST_E_ARG); }
+    }
+    ctx->batched = (opts.batched >= 0 ? opts.batched : env_flag("NST_BATCH", 1)) ? 1 : 0;
+    ctx->use_graph = (opts.use_graph >= 0 ? opts.use_graph : env_flag("NST_GRAPH", 0)) ? 1 : 0;
+    ctx->single_stream = (opts.single_stream >= 0 ? opts.single_stream : env_flag("NST_SINGLE_STREAM", 0)) != 0;
+    ctx->band_rows = opts.h2_band_rows >= 0 ? opts.h2_band_rows : env_flag("NST_H2_BAND_ROWS", 0);
+    ctx->lbfgs_gram = (opts.lbfgs_gram >= 0 ? opts.lbfgs_gram : env_flag("NST_LBFGS_GRAM", 1)) ? 1 : 0;
+    ctx->mfma16 = opts.h2_mfma16 >= 0 ? opts.h2_mfma16 : env_flag("NST_H2_MFMA16", 1);
+    ctx->wg256 = (opts.h2_wg256 >= 0 ? opts.h2_wg256 : env_flag("NST_H2_WG256", 0)) ? 1 : 0;
+    ctx->tile_rows = opts.h2_tile_rows >= 0 ? opts.h2_tile_rows : env_flag("NST_H2_TILE_ROWS", 0);
+    ctx->persist = (opts.h2_persist >= 0 ? opts.h2_persist : env_flag("NST_H2_PERSIST", 0)) ? 1 : 0;
+    ctx->winograd = (opts.h2_winograd >= 0 ? opts.h2_winograd : env_flag("NST_H2_WINOGRAD", 1)) ? 1 : 0;
+    ctx->level_split = (opts.level_split >= 0 ? opts.level_split : env_flag("NST_LEVEL_SPLIT", 0)) ? 1 : 0;
+    ctx->gram_overlap = (opts.gram_overlap >= 0 ? opts.gram_overlap : env_flag("NST_GRAM_OVERLAP", 0)) ? 1 : 0;
+    if (ctx->use_graph && hipStreamCreateWithFlags(&ctx->gstream, hipStreamNonBlocking) != hipSuccess) { ctx->err = "stream creation failed"; return bail(NST_E_HIP); }
+    if (e != hipSuccess) { ctx->err = std::string("kernel attribute setup: ") + hipGetErrorString(e); return bail(NST_E_HIP); }
+
+    std::vector<float> tmp;
+    std::vector<uint16_t> tmp16;
+    auto upload = [&](auto& dst, const void* src, size_t bytes, const char* what) -> int {      // a device copy of host data
+        if (dev_alloc(ctx, reinterpret_cast<void**>(&dst), bytes) != NST_OK) return NST_E_NOMEM;
+        if (hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) != hipSuccess) { ctx->err = std::string(what) + " upload failed"; return NST_E_HIP; }
+        return NST_OK;
+    };
+    // tmp = [9][rows][K] cut into the 16-bit pieces of the active arithmetic only (a context is created per job: 0.24 s -
+    // tools/time_ctx_create.py - and ~200 MB of weight images)
+    auto pieces = [&](int rows, int K, void*& bf, void*& h2, float& h2_inv, void*& wino, float& wino_inv) -> int {
+        if (ctx->conv_mode == 1) {
+            make_bf3(tmp.data(), 9, rows, K, tmp16);
+            return upload(bf, tmp16.data(), tmp16.size() * 2, "weight");
+        }
+        if (ctx->conv_mode != 2) return NST_OK;
+        make_h2(tmp.data(), 9, rows, K, tmp16, &h2_inv);
+        NSTCHK(upload(h2, tmp16.data(), tmp16.size() * 2, "weight"));
+        if (ctx->winograd && K >= 256 && K % 64 == 0 && rows % 128 == 0) {      // (K = 128: no gain measured)
+            make_wino(tmp.data(), rows, K, tmp16, &wino_inv);
+            NSTCHK(upload(wino, tmp16.data(), tmp16.size() * 2, "weight"));
+        }
+        return NST_OK;
+    };
+    for (int l = 0; l < NL; ++l) {
+        const int ci = kCin[l], co = kCout[l];
+        const float* W = weights[l];   // [co][ci][3][3]
+        if (int r = upload(ctx->bias[l], biases[l], co * 4, "bias")) return bail(r);
+        if (l == 0) {
+            tmp.assign(28 * 64, 0.f);
+            for (int o = 0; o < 64; ++o)
+                for (int c = 0; c < 3; ++c)
+                    for (int t = 0; t < 9; ++t) tmp[(c * 9 + t) * 64 + o] = W[(o * 3 + c) * 9 + t];
+            if (int r = upload(ctx->w11k, tmp.data(), tmp.size() * 4, "weight")) return bail(r);
+            tmp.assign(9 * 64 * 4, 0.f);
+            for (int t = 0; t < 9; ++t) {
+                const int ky = 2 - t / 3, kx = 2 - t % 3;
+                for (int o = 0; o < 64; ++o)
+                    for (int c = 0; c < 3; ++c) tmp[(t * 64 + o) * 4 + c] = W[(o * 3 + c) * 9 + ky * 3 + kx];
+            }
+            if (int r = upload(ctx->w11d, tmp.data(), tmp.size() * 4, "weight")) return bail(r);
+            continue;
+        }
+        const size_t n = (size_t)9 * ci * co;
+        tmp.resize(n);
+        // forward: wf[tap][co][ci]
+        for (int t = 0; t < 9; ++t)
+            for (int o = 0; o < co; ++o)
+                for (int c = 0; c < ci; ++c) tmp[((size_t)t * co + o) * ci + c] = W[((size_t)o * ci + c) * 9 + t];
+        if (int r = upload(ctx->wf[l], tmp.data(), n * 4, "weight")) return bail(r);
+        if (int r = pieces(co, ci, ctx->wf_bf[l], ctx->wf_h2[l], ctx->wf_h2_inv[l], ctx->wf_wino[l], ctx->wf_wino_inv[l])) return bail(r);
+        // input gradient: a conv with "Cout" = ci and "Cin" = co: wd[tap'][ci][co] = W[co][ci][2-ky'][2-kx']
+        for (int t = 0; t < 9; ++t) {
+            const int ky = 2 - t / 3, kx = 2 - t % 3;
+            for (int c = 0; c < ci; ++c)
+                for (int o = 0; o < co; ++o) tmp[((size_t)t * ci + c) * co + o] = W[((size_t)o * ci + c) * 9 + ky * 3 + kx];
+        }
+        if (int r = upload(ctx->wd[l], tmp.data(), n * 4, "weight")) return bail(r);
+        if (int r = pieces(ci, co, ctx->wd_bf[l], ctx->wd_h2[l], ctx->wd_h2_inv[l], ctx->wd_wino[l], ctx->wd_wino_inv[l])) return bail(r);
+    }
+    if (ctx->level_split) ctx->gram_overlap = 0;      // (one side stream: the two experiments exclude each other)
+    if ((ctx->gram_overlap || ctx->level_split) && ctx->conv_mode == 2 &&
+        (hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking) != hipSuccess ||
+         hipEventCreateWithFlags(&ctx->side_fork, hipEventDisableTiming) != hipSuccess ||
+         hipEventCreateWithFlags(&ctx->side_join, hipEventDisableTiming) != hipSuccess)) {
+        ctx->err = "side stream creation failed";
+        return bail(NST_E_HIP);
+    }
+    if (hipEventCreateWithFlags(&ctx->fork, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&ctx->tail, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreate(&ctx->t0) != hipSuccess || hipEventCreate(&ctx->t1) != hipSuccess) {
+        ctx->err = "event creation failed";
+        return bail(NST_E_HIP);
+    }
+    *out = ctx;
+    return NST_OK;
+}
+
+void nst_ctx_destroy(nst_ctx* ctx) {
+    if (!ctx) return;
+    (void)hipSetDevice(ctx->device);
+    quiesce(ctx);
+    for (int i = 0; i < NST_MAX_LEVELS; ++i) free_level(ctx, ctx->lv[i]);
+    if (ctx->tail) (void)hipEventDestroy(ctx->tail);
+    for (int l = 0; l < NL; ++l) { dev_free(ctx->wf[l]); dev_free(ctx->wd[l]); dev_free(ctx->bias[l]); dev_free(ctx->wf_bf[l]); dev_free(ctx->wd_bf[l]); dev_free(ctx->wf_h2[l]); dev_free(ctx->wd_h2[l]); dev_free(ctx->wf_wino[l]); dev_free(ctx->wd_wino[l]); }
+    dev_free(ctx->w11k); dev_free(ctx->w11d); dev_free(ctx->color_scratch);
+    drop_closure_state(ctx, false);
+    if (ctx->gstream) (void)hipStreamDestroy(ctx->gstream);
+    if (ctx->side) (void)hipStreamDestroy(ctx->side);
+    if (ctx->side_fork) (void)hipEventDestroy(ctx->side_fork);
+    if (ctx->side_join) (void)hipEventDestroy(ctx->side_join);
+    if (ctx->fork) (void)hipEventDestroy(ctx->fork);
+    if (ctx->t0) (void)hipEventDestroy(ctx->t0);
+    if (ctx->t1) (void)hipEventDestroy(ctx->t1);
+    for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
+    delete ctx;
+}
+
+int nst_conv_mode(const nst_ctx* ctx) { return ctx ? ctx->conv_mode : -1; }
+
+int nst_ctx_bytes(const nst_ctx* ctx, size_t* bytes) {
+    if (!ctx || !bytes) return fail(nullptr, NST_E_ARG, "null argument");
+    *bytes = ctx->bytes;
+    return NST_OK;
+}
+
+int nst_job_configure(nst_ctx* ctx, int levels_num, int H0, int W0) {
+    if (ctx) ++ctx->closure_epoch;
+    NSTCHK(bind(ctx));
+    if (levels_num < 1 || levels_num > NST_MAX_LEVELS) return fail(ctx, NST_E_ARG, "levels_num out of range");
+    if ((H0 >> (levels_num - 1)) < 16 || (W0 >> (levels_num - 1)) < 16)
+        return fail(ctx, NST_E_ARG, "coarsest pyramid level must be at least 16x16");
+    quiesce(ctx);
+    for (int i = 0; i < NST_MAX_LEVELS; ++i) free_level(ctx, ctx->lv[i]);      // (the targets go with the levels)
+    drop_closure_state(ctx, false);
+    ctx->levels = 0;
+    int h = H0, w = W0;
+    for (int i = 0; i < levels_num; ++i) {
+        LevelWs& L = ctx->lv[i];
+        L.h = h; L.w = w;
+        NSTCHK(alloc_acts(ctx, L.acts, h, w));
+        L.gbuf_floats = (size_t)h * w * 64;
+        NSTCHK(dev_alloc_t(ctx, &L.gbuf[0], L.gbuf_floats));
+        NSTCHK(dev_alloc_t(ctx, &L.gbuf[1], L.gbuf_floats));
+        if (i > 0) NSTCHK(alloc_level_image(ctx, L));      // sized for the context's current channel count
+        NSTCHK(alloc_tap_buffers(ctx, L));       // sized for the context's current taps
+        NSTCHK(dev_alloc_t(ctx, &L.content_partial, MSE_BLOCKS));
+        NSTCHK(dev_alloc_t(ctx, &L.tv_partial, 2 * TV_BLOCKS));
+        NSTCHK(dev_alloc_t(ctx, &L.tv_means, 2));
+        h /= 2; w /= 2;
+    }
+    ctx->levels = levels_num;
+    return NST_OK;
+}
+
+// LossBuilder(content_feature_maps_index, style_feature_maps_indices, ...) and Vgg19(use_relu=...) of the reference
+// (neural_style_transfer.py:41-82, neural_nets.py:17-28) as a context setting
+int nst_job_set_taps(nst_ctx* ctx, int content_index, unsigned style_mask, int use_relu) {
+    if (ctx) ++ctx->closure_epoch;
+    NSTCHK(bind(ctx));
+    if (content_index < 0 || content_index > 5) return fail(ctx, NST_E_ARG, "content_index must be 0 .. 5");
+    if (style_mask == 0u || (style_mask & ~0x3Fu) != 0u)
+        return fail(ctx, NST_E_ARG, "style_mask must be a non-empty set of bits 0 .. 5");
+    if (use_relu != 0 && use_relu != 1) return fail(ctx, NST_E_ARG, "use_relu must be 0 or 1");
+    Taps tp;
+    tp.content = kTapLayer[content_index];
+    tp.nstyle = 0;
+    for (int i = 0; i < 6; ++i)
+        if ((style_mask >> i) & 1u) tp.style[tp.nstyle++] = kTapLayer[i];      // (ascending: kTapLayer increases)
+    tp.top = std::max(tp.content, tp.style[tp.nstyle - 1]);
+    tp.use_relu = use_relu;
+    tp.is_default = content_index == 4 && style_mask == 0x2Fu && use_relu == 1;
+    // every level's targets and the captured closure belong to the old taps; the tap-sized buffers are re-allocated
+    quiesce(ctx);
+    drop_closure_state(ctx, true);
+    ctx->taps = tp;
+    for (int i = 0; i < ctx->levels; ++i) {
+        LevelWs& L = ctx->lv[i];
+        free_tap_buffers(ctx, L);
+        NSTCHK(alloc_tap_buffers(ctx, L));
+    }
+    return NST_OK;
+}
+
+// Gatys et al. 2016, luminance-only transfer: the optimised image becomes one plane u = 255 Y (channels = 1) that the
+// network sees as x_c = u - mean_c.  Same life cycle as the taps: every level's targets and the captured closure go.
+int nst_job_set_color(nst_ctx* ctx, int mode) {
+    if (ctx) ++ctx->closure_epoch;
+    NSTCHK(bind(ctx));
+    if (mode != NST_COLOR_RGB && mode != NST_COLOR_LUMINANCE) return fail(ctx, NST_E_ARG, "mode must be NST_COLOR_RGB or NST_COLOR_LUMINANCE");
+    const int channels = mode == NST_COLOR_LUMINANCE ? 1 : 3;
+    quiesce(ctx);
+    // the level images of the new channel count first: if one cannot be had, the context stays as it was (old mode, old
+    // buffers, targets kept)
+    float* img[NST_MAX_LEVELS][2] = {};
+    int r = NST_OK;
+    for (int i = 1; i < ctx->levels && r == NST_OK; ++i) {
+        const size_t n = (size_t)channels * ctx->lv[i].h * ctx->lv[i].w;
+        r = dev_alloc_t(ctx, &img[i][0], n);
+        if (r == NST_OK) r = dev_alloc_t(ctx, &img[i][1], n);
+    }
+    if (r != NST_OK) {
+        for (int i = 1; i < ctx->levels; ++i) {
+            const size_t bytes = (size_t)channels * ctx->lv[i].h * ctx->lv[i].w * 4;
+            for (float* p : img[i])
+                if (p) { dev_free(p); if (ctx->bytes >= bytes) ctx->bytes -= bytes; }
+        }
+        return r;
+    }
+    drop_closure_state(ctx, true);
+    ctx->channels = channels;
+    for (int i = 1; i < ctx->levels; ++i) {
+        LevelWs& L = ctx->lv[i];
+        free_level_image(ctx, L);
+        L.xl = img[i][0]; L.gxl = img[i][1];
+        L.xl_floats = (size_t)channels * L.h * L.w;
+    }
+    return NST_OK;
+}
+
+int nst_job_color(const nst_ctx* ctx) { return ctx ? (ctx->channels == 1 ? NST_COLOR_LUMINANCE : NST_COLOR_RGB) : -1; }
+
+// Gatys et al. 2016, section 2: average instead of max pooling in the feature network.  Same life cycle as the taps and the
+// colour mode: every level's targets (made with the other network) and the captured closure go; no buffer changes size.
+int nst_job_set_pooling(nst_ctx* ctx, int mode) {
+    if (ctx) ++ctx->closure_epoch;
+    NSTCHK(bind(ctx));
+    if (mode != NST_POOL_MAX && mode != NST_POOL_AVG) return fail(ctx, NST_E_ARG, "mode must be NST_POOL_MAX or NST_POOL_AVG");
+    quiesce(ctx);
+    drop_closure_state(ctx, true);
+    ctx->pool_avg = mode == NST_POOL_AVG ? 1 : 0;
+    return NST_OK;
+}
+
+int nst_job_pooling(const nst_ctx* ctx) { return ctx ? (ctx->pool_avg ? NST_POOL_AVG : NST_POOL_MAX) : -1; }
+
+int nst_set_timing(nst_ctx* ctx, int enabled) {
+    NSTCHK(bind(ctx));
+    ctx->timing = enabled;
+    if (enabled >= 2 && ctx->ev_pool.empty()) {
+        ctx->ev_pool.resize(2048);
+        for (auto& e : ctx->ev_pool) HIPCHK(ctx, hipEventCreate(&e));
+    }
+    return NST_OK;
+}
+
+int nst_last_closure_ms(nst_ctx* ctx, float* ms) {
+    NSTCHK(bind(ctx));
+    if (!ms) return fail(ctx, NST_E_ARG, "null argument");
+    *ms = 0.f;
+    if (!ctx->timed_valid) return NST_OK;
+    HIPCHK(ctx, hipEventSynchronize(ctx->t1));
+    HIPCHK(ctx, hipEventElapsedTime(ms, ctx->t0, ctx->t1));
+    return NST_OK;
+}
+
+// per kernel class of the last closure: summed launch durations (ms), launch count, algorithmic flops
+int nst_last_closure_class(nst_ctx* ctx, int cls, float* ms, int* launches, double* flops) {
+    NSTCHK(bind(ctx));
+    if (!ms || !launches || !flops || cls < 0 || cls >= K_NCLASS) return fail(ctx, NST_E_ARG, "bad argument");
+    *ms = 0.f; *launches = 0; *flops = 0.0;
+    if (!ctx->timed_valid) return NST_OK;
+    HIPCHK(ctx, hipEventSynchronize(ctx->t1));
+    for (const TimedLaunch& t : ctx->timed) {
+        if (t.cls != cls) continue;
+        float d = 0.f;
+        HIPCHK(ctx, hipEventSynchronize(t.b));
+        HIPCHK(ctx, hipEventElapsedTime(&d, t.a, t.b));
+        *ms += d; *launches += 1; *flops += t.flops;
+    }
+    return NST_OK;
+}
+
+// debugging aid: one line per timed launch of the last closure to stderr
+int nst_dump_last_closure(nst_ctx* ctx) {
+    NSTCHK(bind(ctx));
+    if (!ctx->timed_valid) return NST_OK;
+    HIPCHK(ctx, hipEventSynchronize(ctx->t1));
+    for (const TimedLaunch& t : ctx->timed) {
+        float d = 0.f;
+        HIPCHK(ctx, hipEventSynchronize(t.b));
+        HIPCHK(ctx, hipEventElapsedTime(&d, t.a, t.b));
+        fprintf(stderr, "cls %d  %4dx%-4d cin %3d cout %3d taps %d layer %3d  %8.3f ms  %7.2f TFLOP/s\n", t.cls, t.tag[0],
+                t.tag[1], t.tag[2], t.tag[3], t.tag[4], t.tag[5], d, d > 0 ? t.flops / (d * 1e-3) / 1e12 : 0.0);
+    }
+    return NST_OK;
+}
+
+// totals since the last reset (timing mode 2): per kernel class cls in 0..3 (0 = 3x3 MFMA conv fwd+dgrad,
+// 1 = Gram forward + its 1x1 backward, 2 = conv1_1 fwd+dgrad, 3 = streaming kernels); cls = -1: whole closures
+// (ms = summed closure wall on the caller's stream, launches = closures).  reset != 0 clears afterwards.
+int nst_timing_totals(nst_ctx* ctx, int cls, double* ms, long* launches, double* flops, int reset) {
+    NSTCHK(bind(ctx));
+    if (!ms || !launches || !flops || cls < -2 || cls >= K_NCLASS) return fail(ctx, NST_E_ARG, "bad argument");
+    NSTCHK(fold_timed(ctx));
+    if (cls == -2) { *ms = 0; *launches = ctx->acc_sampled; *flops = 0; }       // closures with per-launch events
+    else if (cls < 0) { *ms = ctx->acc_closure_ms; *launches = ctx->acc_closures; *flops = 0; }
+    else { *ms = ctx->acc_ms[cls]; *launches = ctx->acc_launches[cls]; *flops = ctx->acc_flops[cls]; }
+    if (reset) {
+        for (int i = 0; i < 4; ++i) { ctx->acc_ms[i] = 0; ctx->acc_flops[i] = 0; ctx->acc_mfma[i] = 0; ctx->acc_launches[i] = 0; }
+        ctx->acc_closure_ms = 0; ctx->acc_closures = 0; ctx->acc_sampled = 0;
+    }
+    return NST_OK;
+}
+
+int nst_timing_mfma_flops(nst_ctx* ctx, int cls, double* mfma_flops) {
+    NSTCHK(bind(ctx));
+    if (!mfma_flops || cls < 0 || cls >= K_NCLASS) return fail(ctx, NST_E_ARG, "bad argument");
+    NSTCHK(fold_timed(ctx));
+    *mfma_flops = ctx->acc_mfma[cls];
+    return NST_OK;
+}
+
+// ---- internal accessors for nst_opt.cpp (not part of the public ABI) --------------------------------
+int nst_internal_device(const nst_ctx* ctx) { return ctx ? ctx->device : 0; }
+int nst_internal_levels(const nst_ctx* ctx) { return ctx ? ctx->levels : 0; }
+int nst_internal_channels(const nst_ctx* ctx) { return ctx ? ctx->channels : 3; }
+size_t nst_internal_pixels(const nst_ctx* ctx) { return (ctx && ctx->levels > 0) ? (size_t)ctx->lv[0].h * ctx->lv[0].w : 0; }
+int nst_internal_fail(nst_ctx* ctx, int code, const char* msg) { return fail(ctx, code, msg ? msg : ""); }
+void nst_internal_poison(void* p, size_t bytes) { poison_if_asked(p, bytes); }
+int nst_internal_lbfgs_gram(const nst_ctx* ctx) { return ctx ? ctx->lbfgs_gram : 1; }
+unsigned long long nst_internal_closure_epoch(const nst_ctx* ctx) { return ctx ? ctx->closure_epoch : 0; }
+void nst_internal_mark(nst_ctx* ctx, void* stream) { mark(ctx, static_cast<hipStream_t>(stream)); }
+
+}  // extern "C"

@@ -1,0 +1,287 @@
+// nst_ctx.h - what the three host sources of the C ABI share (not installed, not part of include/nst_hip.h): the VGG19 layer
+// tables, the context and its per-level workspace, error reporting, the launch timer, and the helpers one source defines
+// and another calls.  nst_ctx.cpp: context and job state; nst_closure.cpp: network and closure; nst_api.cpp: standalone
+// entry points.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <vector>
+
+#include "../../include/nst_hip.h"
+#include "nst_kernels.h"
+
+#pragma GCC visibility push(hidden)      // host-internal: none of this is a symbol of libnst_hip.so
+namespace nst {
+
+constexpr int NL = NST_VGG19_CONVS;
+constexpr int kCin[NL] = {3, 64, 64, 128, 128, 256, 256, 256, 256, 512, 512, 512, 512};
+constexpr int kCout[NL] = {64, 64, 128, 128, 256, 256, 256, 256, 512, 512, 512, 512, 512};
+constexpr int kScale[NL] = {0, 0, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4};      // log2 of the spatial divisor
+constexpr int kPoolAfter[4] = {1, 3, 7, 11};
+// reference output index (neural_nets.py:22) -> conv layer
+constexpr int kTapLayer[6] = {0, 2, 4, 8, 9, 12};
+// the reference's default taps (neural_nets.py:25-28): content 4 = ReLU(conv4_2), style 0, 1, 2, 3, 5 =
+// relu1_1, relu2_1, relu3_1, relu4_1, relu5_1; a context's own taps (nst_job_set_taps) live in nst_ctx::taps
+constexpr int kMaxStyle = 6;
+inline int pool_index_after(int l) {
+    for (int k = 0; k < 4; ++k) if (kPoolAfter[k] == l) return k;
+    return -1;
+}
+
+struct ActSet {                 // activations of one forward pass, NHWC
+    int h[NL], w[NL];
+    float* act[NL] = {};
+    float* pool[4] = {};
+    float* splitk = nullptr;     // split-K partial sums of the small-spatial conv layers
+    size_t splitk_floats = 0;
+    unsigned* bits[NL] = {};     // ReLU bit-masks ([h*w][C/32] words) of the layers whose mask the backward reads
+    bool bits_valid[NL] = {};    // written by the last forward pass (false when that layer ran split-K / fp32)
+    bool pooled[4] = {};         // pool[k] already produced by the conv epilogue of the last forward pass
+    // absmax records for the fp16-piece convolutions (conv_h2.hip): AMAX_IDS x NST_AMAX_SLOTS words.
+    // ids: act[l] -> l; the Gram factor S of style slot q -> NL + q (6 slots); the gradient w.r.t. the pre-ReLU output
+    // of layer l (or a bound of it: the pooled gradient it was un-pooled from) -> NL + 6 + l
+    unsigned* amax = nullptr;
+    // arg-max codes of the four max-pools (average pooling: the multi-hot ReLU-on codes), written by the fused pooling of the
+    // f16x2 forward launches and read by the un-pooling loader of the input-gradient launch below each pool: [H/2*W/2][C/32][4] words
+    unsigned* pcode[4] = {};
+    size_t bytes = 0;
+    // a forward pass starts: nothing of the previous one's masks and fused pools is valid any more
+    void begin_pass() {
+        for (int l = 0; l < NL; ++l) bits_valid[l] = false;
+        for (int k = 0; k < 4; ++k) pooled[k] = false;
+    }
+};
+constexpr int AMAX_IDS = 2 * NST_VGG19_CONVS + kMaxStyle;
+inline unsigned* amax_act(const ActSet& a, int l) { return a.amax + (size_t)l * NST_AMAX_SLOTS; }
+inline unsigned* amax_S(const ActSet& a, int q) { return a.amax + (size_t)(NST_VGG19_CONVS + q) * NST_AMAX_SLOTS; }
+inline unsigned* amax_grad(const ActSet& a, int l) { return a.amax + (size_t)(NST_VGG19_CONVS + kMaxStyle + l) * NST_AMAX_SLOTS; }
+
+// The feature maps a job's losses read (nst_job_set_taps), as conv layers.  The reference's LossBuilder keeps the indices
+// of enumerate(features) that are `in` its lists (neural_style_transfer.py:48-64): order and repeats do not matter, the
+// style term is the mean over the distinct maps kept (:104-106).
+struct Taps {
+    int content = 9;                           // conv layer of the content map
+    int style[kMaxStyle] = {0, 2, 4, 8, 12};   // conv layers of the style maps, ascending (style slot q -> style[q])
+    int nstyle = 5;
+    int top = 12;                              // the deepest layer any loss reads: the forward stops, the backward starts there
+    int use_relu = 1;                          // 0: tap 5 is conv5_1 BEFORE its ReLU (neural_nets.py:24-26 with use_relu=False)
+    bool is_default = true;
+    int style_slot(int l) const {
+        for (int q = 0; q < nstyle; ++q) if (style[q] == l) return q;
+        return -1;
+    }
+    // every layer's output goes through its ReLU, but conv5_1's under use_relu = 0
+    int relu_of(int l) const { return (l == NL - 1 && !use_relu) ? 0 : 1; }
+    // the top layer's gradient goes through its ReLU mask unless it is the pre-ReLU conv5_1
+    bool top_mask() const { return use_relu || top != NST_VGG19_CONVS - 1; }
+};
+
+enum KClass { K_CONV3 = 0, K_GRAM = 1, K_CONV1 = 2, K_OTHER = 3, K_NCLASS = 4 };
+
+struct TimedLaunch { hipEvent_t a, b; int cls; double flops; int tag[6]; double mfma_factor; };      // mfma_factor: executed matrix-pipe FLOPs per algorithmic FLOP (< 0: the arithmetic mode's)
+
+struct LevelWs {
+    int h = 0, w = 0;
+    ActSet acts;
+    float* gbuf[2] = {};
+    size_t gbuf_floats = 0;
+    float* xl = nullptr;        // level image (levels >= 1), planar
+    float* gxl = nullptr;       // its gradient (levels >= 1), planar
+    size_t xl_floats = 0;       // channels (nst_job_set_color) x h x w
+    float* content_t = nullptr; // NHWC target ReLU(conv4_2)
+    size_t content_n = 0;
+    float* gram_t[kMaxStyle] = {};
+    float* S[kMaxStyle] = {};
+    unsigned short* S_bf[kMaxStyle] = {};
+    float* gram_part = nullptr;
+    size_t gram_part_floats = 0;
+    double* style_partial[kMaxStyle] = {};
+    int tap_c[kMaxStyle] = {};  // channels of the style map each Gram buffer was sized for
+    double* content_partial = nullptr;
+    double* tv_partial = nullptr;
+    float* tv_means = nullptr;
+    bool targets = false;
+    hipStream_t stream = nullptr;
+    hipEvent_t done = nullptr;
+};
+
+}  // namespace nst
+
+struct nst_ctx {
+    int device = 0;
+    std::string err;
+    float* wf[nst::NL] = {};
+    float* wd[nst::NL] = {};
+    void* wf_bf[nst::NL] = {};       // the same weights cut into 3 bf16 pieces (conv_bf3.hip layout)
+    void* wd_bf[nst::NL] = {};
+    void* wd_wino[nst::NL] = {};     // the same for the input-gradient launches
+    float wd_wino_inv[nst::NL] = {};
+    void* wf_wino[nst::NL] = {};     // conv_wino.hip's transformed forward weights (nst_options.h2_winograd), true = pieces * wf_wino_inv
+    float wf_wino_inv[nst::NL] = {};
+    int winograd = 0;           // nst_options.h2_winograd
+    void* wf_h2[nst::NL] = {};       // ... cut into 2 scaled fp16 pieces (conv_h2.hip layout), true = pieces * w*_h2_inv
+    void* wd_h2[nst::NL] = {};
+    float wf_h2_inv[nst::NL] = {};
+    float wd_h2_inv[nst::NL] = {};
+    // 3x3 convs: 2 = fp16 pipe, 2 scaled pieces per operand (3 MFMAs per product block; default),
+    //            1 = bf16 pipe, 3 exact pieces (6 MFMAs), 0 = fp32 MFMA
+    int conv_mode = 2;
+    int band_rows = 0;          // nst_options.h2_band_rows (0 = bands only for tensors beyond 4 GiB)
+    int lbfgs_gram = 1;         // nst_options.lbfgs_gram
+    int mfma16 = 1;             // nst_options.h2_mfma16
+    int wg256 = 0;              // nst_options.h2_wg256
+    int tile_rows = 0;          // nst_options.h2_tile_rows
+    int gram_overlap = 0;       // nst_options.gram_overlap
+    int persist = 1;            // nst_options.h2_persist
+    int level_split = 0;        // nst_options.level_split
+    hipStream_t side = nullptr; // the Gram launches of the shallow style layers run here, under the deeper forward convolutions
+    hipEvent_t side_fork = nullptr, side_join = nullptr;
+    hipStream_t tail_stream = nullptr;   // the stream the tail event was last recorded on (see enter())
+    bool tail_set = false;
+    hipEvent_t tail = nullptr;  // recorded after the last launch that touches context-owned memory: what
+                                // nst_job_configure / nst_ctx_destroy wait for instead of the whole device
+    int batched = 1;            // 1: one conv launch per layer covering every pyramid level (one stream)
+    // hipGraph of the closure: captured the second time the same (buffers, weights, mask) are seen
+    int use_graph = 0;          // measured: no gain (the host already runs ~16 ms ahead of the GPU); NST_GRAPH=1 enables
+    hipStream_t gstream = nullptr;          // capture stream (capture on the legacy stream is not allowed)
+    hipGraphExec_t gexec = nullptr;
+    struct GraphKey { const float* x; float* grad; float* losses; float cw, sw, tvw; unsigned mask; } gkey{}, glast{};
+    float* bias[nst::NL] = {};
+    float* w11k = nullptr;      // [28][64]
+    float* w11d = nullptr;      // [9][64][4]
+    int levels = 0;
+    nst::Taps taps;             // nst_job_set_taps
+    int channels = 3;           // nst_job_set_color: 3 = RGB, 1 = luminance (the optimised image is u = 255 Y)
+    int pool_avg = 0;           // nst_job_set_pooling: 1 = the four pools average their windows (include/nst_hip.h has the definition)
+    // bumped on entry to every call that changes what a closure computes (configure, taps, colour, pooling, targets), failure paths
+    // included: an optimiser's remembered closure result is valid only under the epoch it was made in (nst_opt.cpp)
+    unsigned long long closure_epoch = 0;
+    double* color_scratch = nullptr;   // nst_color_stats: COLOR_BLOCKS * 9 partials | mean (3) | cov (9), made on first use
+    nst::LevelWs lv[NST_MAX_LEVELS];
+    hipEvent_t fork = nullptr;
+    size_t bytes = 0;
+    bool single_stream = false;
+    // timing
+    int timing = 0;
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    std::vector<hipEvent_t> ev_pool;
+    size_t ev_used = 0;
+    std::vector<nst::TimedLaunch> timed;
+    bool timed_valid = false;
+    // accumulated over closures since the last reset (timing mode 2)
+    double acc_ms[4] = {0, 0, 0, 0};
+    double acc_flops[4] = {0, 0, 0, 0};
+    double acc_mfma[4] = {0, 0, 0, 0};          // executed matrix-pipe FLOPs of the timed launches
+    long acc_launches[4] = {0, 0, 0, 0};
+    double acc_closure_ms = 0;
+    long acc_closures = 0;
+    long acc_sampled = 0;       // closures whose launches carried event pairs (timing mode 4 samples one in four)
+    long closure_seq = 0;
+    bool sample_now = true;
+};
+
+namespace nst {
+
+// records msg as the context's (ctx = nullptr: the thread's) last error and returns code
+int fail(nst_ctx* ctx, int code, const std::string& msg);
+
+#define HIPCHK(ctx, expr)                                                                         \
+    do {                                                                                          \
+        hipError_t _e = (expr);                                                                   \
+        if (_e != hipSuccess)                                                                     \
+            return fail(ctx, NST_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));       \
+    } while (0)
+
+#define NSTCHK(expr)                 \
+    do {                             \
+        int _r = (expr);             \
+        if (_r != NST_OK) return _r; \
+    } while (0)
+
+// ---- timed launches ---------------------------------------------------------------------------
+struct Timer {
+    nst_ctx* ctx; hipStream_t s; bool on; size_t slot;
+    Timer(nst_ctx* c, hipStream_t st, int cls, double flops, int t0 = 0, int t1 = 0, int t2 = 0, int t3 = 0, int t4 = 0,
+          int t5 = 0)
+        : ctx(c), s(st), on(false), slot(0) {
+        if (c->timing >= 2 && (c->timing < 3 || cls == K_CONV3) && c->sample_now && c->ev_used + 2 <= c->ev_pool.size()) {
+            on = true;
+            TimedLaunch t{c->ev_pool[c->ev_used], c->ev_pool[c->ev_used + 1], cls, flops, {t0, t1, t2, t3, t4, t5}, -1.0};
+            c->ev_used += 2;
+            slot = c->timed.size();
+            c->timed.push_back(t);
+            (void)hipEventRecord(t.a, st);
+        }
+    }
+    ~Timer() { if (on) (void)hipEventRecord(ctx->timed[slot].b, s); }
+    // a launch whose matrix-pipe work per algorithmic FLOP differs from its arithmetic mode's (the Winograd form: 2/3 of it)
+    void mfma_factor(double f) { if (on) ctx->timed[slot].mfma_factor = f; }
+};
+// folds the event pairs of the previous closure into the accumulators (waits for them to complete)
+int fold_timed(nst_ctx* ctx);
+
+// ---- nst_ctx.cpp: device memory (counted in ctx->bytes), workspace, stream ordering ------------------------------------
+int dev_alloc(nst_ctx* ctx, void** p, size_t bytes);
+template <typename T>
+int dev_alloc_t(nst_ctx* ctx, T** p, size_t count) { return dev_alloc(ctx, reinterpret_cast<void**>(p), count * sizeof(T)); }
+inline void dev_free(void* p) { if (p) (void)hipFree(p); }
+int alloc_acts(nst_ctx* ctx, ActSet& a, int h, int w);
+void free_acts(nst_ctx* ctx, ActSet& a);
+int bind(nst_ctx* ctx);                            // null check + hipSetDevice: first line of every entry point
+hipStream_t enter(nst_ctx* ctx, void* stream);     // orders the caller's stream after the context's tail event
+void mark(nst_ctx* ctx, hipStream_t s);            // records the tail event
+void quiesce(nst_ctx* ctx);                        // waits until nothing on the device uses the context's memory
+
+// Scratch of a standalone call - an ActSet and device buffers that its launches on `s` use: freed on every path out of the
+// scope, after the stream has been synchronised.  `return sc.finish();` ends the good path: synchronise, free, then report.
+// (The buffers stay counted in ctx->bytes as alloc_acts / free_acts and dev_alloc count them.)
+struct Scratch {
+    nst_ctx* ctx; hipStream_t s; ActSet acts; std::vector<void*> bufs; bool open = true;
+    Scratch(nst_ctx* c, hipStream_t st) : ctx(c), s(st) {}
+    Scratch(const Scratch&) = delete;
+    ~Scratch() { (void)release(); }
+    template <typename T>
+    int alloc(T** p, size_t count) {
+        NSTCHK(dev_alloc_t(ctx, p, count));
+        bufs.push_back(*p);
+        return NST_OK;
+    }
+    hipError_t release() {
+        if (!open) return hipSuccess;
+        open = false;
+        const hipError_t e = hipStreamSynchronize(s);
+        free_acts(ctx, acts);
+        for (void* p : bufs) dev_free(p);
+        return e;
+    }
+    int finish() { const hipError_t e = release(); HIPCHK(ctx, e); return NST_OK; }
+};
+
+// ---- nst_closure.cpp: the per-level network walker and Gram, as the standalone entry points use them --------------------
+// gradient injected at a tap layer, w.r.t. its post-ReLU activation
+struct Inject {
+    const float* S = nullptr;        // Gram backward: dF = F * S (1x1 conv of the activation itself)
+    const void* S_bf = nullptr;      // the same S cut into bf16 pieces (conv_bf3 weight layout), if available
+    const unsigned* S_amax = nullptr; // absmax record of S (conv_h2), if available
+    const float* direct = nullptr;   // or a ready NHWC gradient
+    bool content = false;            // or the content MSE gradient (closure only)
+};
+struct ContentJob { const float* target; size_t n; float coef; double* partial; };
+// channels = 1: x is a luminance plane u, conv1_1 sees x_c = u - mean_c (nst_job_set_color)
+int forward(nst_ctx* ctx, ActSet& a, const float* x, int h, int w, hipStream_t s, int last_layer = NL - 1, int channels = 3);
+// Backward through the network down to the planar image gradient gx (overwritten).
+// inj[l] describes what enters at conv layer l; gbuf: two NHWC scratch buffers of the largest size.  The chain starts at
+// layer `top` (nothing above it is read); `top_mask` = false: the top map is pre-ReLU (its gradient passes unmasked).
+// channels = 1: gx is the gradient of a luminance plane (the sum over the three channels)
+int backward(nst_ctx* ctx, ActSet& a, const Inject* inj, const ContentJob* cj, float* gbuf0, float* gbuf1, float* gx,
+             int h, int w, hipStream_t s, int top = NL - 1, bool top_mask = true, int channels = 3);
+// f_amax (nullable): absmax record of f_nhwc; with it the partial products run on the fp16 pipe
+int gram_of(nst_ctx* ctx, const float* f_nhwc, size_t N, int C, const unsigned* f_amax, float divisor, float* part, const float* target,
+            float coef, float* gram_out, float* S, unsigned short* S_bf, unsigned* S_amax, double* mse_partial,
+            hipStream_t s);
+// floats of the partial-Gram workspace of one h x w image under these taps (the style layers one after the other)
+size_t gram_part_floats_for(const Taps& tp, int h, int w);
+
+}  // namespace nst
+#pragma GCC visibility pop

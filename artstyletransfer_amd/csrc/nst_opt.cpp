@@ -26,7 +26,7 @@ extern "C" size_t nst_internal_pixels(const nst_ctx* ctx);
 extern "C" int nst_internal_channels(const nst_ctx* ctx);     // 3, or 1 under NST_COLOR_LUMINANCE
 extern "C" int nst_internal_fail(nst_ctx* ctx, int code, const char* msg);
 extern "C" void nst_internal_poison(void* p, size_t bytes);
-extern "C" int nst_internal_zero_now(void* p, size_t bytes);      // a zero fill that has RUN when it returns (nst_api.cpp)
+extern "C" int nst_internal_zero_now(void* p, size_t bytes);      // a zero fill that has RUN when it returns (nst_ctx.cpp)
 extern "C" int nst_internal_lbfgs_gram(const nst_ctx* ctx);
 extern "C" void nst_internal_mark(nst_ctx* ctx, void* stream);
 extern "C" unsigned long long nst_internal_closure_epoch(const nst_ctx* ctx);

@@ -1,5 +1,5 @@
 """Does any kernel of a job read device memory that nobody wrote?  Runs one small two-level L-BFGS job in a child process
-with NST_POISON_ALLOC (csrc/nst_api.cpp: chosen allocations are filled with 0xFF bytes = NaN as floats) and compares its
+with NST_POISON_ALLOC (csrc/nst_ctx.cpp: chosen allocations are filled with 0xFF bytes = NaN as floats) and compares its
 loss rows and final image with an unpoisoned run.  With `--bisect` the range of poisoned allocation numbers is halved
 until one allocation is left.  GPU only:  python tools/check_uninit_reads.py [--bisect] [--optimizer lbfgs|adam]"""
 import argparse
