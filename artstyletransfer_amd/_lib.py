@@ -14,6 +14,8 @@ LIB_PATH = os.environ.get("NST_LIB") or os.path.join(_HERE, "libnst_hip.so")   #
 CSRC = os.path.join(_HERE, "csrc")
 
 NST_OK = 0
+NST_E_STATE = -2
+NST_E_UNAVAILABLE = -5
 NST_VGG19_CONVS = 13
 NST_MAX_LEVELS = 8
 NST_LOSS_ROW = 4
@@ -69,11 +71,15 @@ SYMBOLS = {
     "nst_level_set_targets": (C.c_int, [c_void, C.c_int, c_void, c_void, C.c_int, C.c_int, c_void]),
     "nst_closure": (C.c_int, [c_void, c_void, C.c_float, C.c_float, C.c_float, c_void, c_void, c_void]),
     "nst_closure_levels": (C.c_int, [c_void, c_void, C.c_float, C.c_float, C.c_float, C.c_uint, c_void, c_void, c_void]),
+    "nst_closure_forward": (C.c_int, [c_void, c_void, C.c_float, C.c_float, C.c_float, C.c_uint, c_void, c_void]),
+    "nst_closure_backward": (C.c_int, [c_void, c_void, C.c_float, C.c_float, C.c_float, C.c_uint, c_void, c_void]),
     "nst_opt_shard_levels": (C.c_int, [c_void, C.c_uint, c_void, c_void, c_void, c_void]),
     "nst_opt_shard_levels_comm": (C.c_int, [c_void, C.c_uint, c_void]),
     "nst_opt_history": (C.c_int, [c_void, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "nst_opt_set_closure_reuse": (C.c_int, [c_void, C.c_int]),
     "nst_opt_closure_stats": (C.c_int, [c_void, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
+    "nst_opt_set_lazy_backward": (C.c_int, [c_void, C.c_int]),
+    "nst_opt_backward_stats": (C.c_int, [c_void, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     "nst_comm_unique_id": (C.c_int, [c_void]),
     "nst_comm_create": (C.c_int, [C.c_int, C.c_int, C.c_int, c_void, C.POINTER(c_void)]),
     "nst_comm_destroy": (None, [c_void]),

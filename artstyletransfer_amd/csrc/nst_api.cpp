@@ -84,6 +84,7 @@ int nst_gram(nst_ctx* ctx, const float* f, int C, int h, int w, int normalize, f
 
 int nst_level_activation(nst_ctx* ctx, int level, int layer, float* out, void* stream) {
     NSTCHK(bind(ctx));
+    ++ctx->ws_seq;
     if (level < 0 || level >= ctx->levels) return fail(ctx, NST_E_STATE, "level not configured");
     if (layer < 0 || layer >= NL || !out) return fail(ctx, NST_E_ARG, "bad argument");
     const ActSet& a = ctx->lv[level].acts;

@@ -535,14 +535,23 @@ int batched_backward(nst_ctx* ctx, const float* const* xi, float* const* gi, con
     return NST_OK;
 }
 
-// `zero_mask`: the levels whose gradient this call clears when they are not in `level_mask` (levels another rank owns)
-int closure_batched(nst_ctx* ctx, const float* const* xi, float* const* gi, unsigned level_mask, float cw, float sw,
-                    float tvw, hipStream_t s, unsigned zero_mask = ~0u) {
-    int lv[NST_MAX_LEVELS], n = 0;
-    for (int i = 0; i < ctx->levels; ++i) {
+// The batched closure of the levels in `level_mask` in two halves that meet where the stripe closure splits too: the
+// forward half leaves every activation, ReLU bit-mask, pool code, absmax record and S matrix in the level workspaces, the
+// backward half reads them.  closure_batched runs one after the other; nst_closure_forward / nst_closure_backward run them
+// apart.
+int level_list(const nst_ctx* ctx, unsigned level_mask, int* lv) {
+    int n = 0;
+    for (int i = 0; i < ctx->levels; ++i)
         if ((level_mask >> i) & 1u) lv[n++] = i;
-        else if ((zero_mask >> i) & 1u) HIPCHK(ctx, launch_zero(gi[i], (size_t)ctx->channels * ctx->lv[i].h * ctx->lv[i].w, s));
-    }
+    return n;
+}
+// forward convolutions and every Gram launch, the side-stream overlap joined.  `loss_terms` (a forward half on its own):
+// also the content SSE partials and the TV means of the loss row, by the launches the backward half produces them with
+// (same kernels, same per-block reduction order, no gradient write), which that half then writes again.
+int closure_batched_forward(nst_ctx* ctx, const float* const* xi, unsigned level_mask, float sw, float tvw, hipStream_t s,
+                            bool loss_terms) {
+    int lv[NST_MAX_LEVELS];
+    const int n = level_list(ctx, level_mask, lv);
     if (n == 0) return NST_OK;
     // (not while a hipGraph is being captured or replayed: the closure then stays on one stream)
     // (the overlap's split of the style maps - relu1_1 .. relu3_1 on the side stream - is the default taps')
@@ -550,7 +559,29 @@ int closure_batched(nst_ctx* ctx, const float* const* xi, float* const* gi, unsi
     NSTCHK(batched_forward(ctx, xi, lv, n, s, nullptr, overlap ? sw : -1.f));
     NSTCHK(batched_gram(ctx, lv, n, sw, s, overlap ? 0x18u : (1u << ctx->taps.nstyle) - 1u));
     if (overlap) HIPCHK(ctx, hipStreamWaitEvent(s, ctx->side_join, 0));
+    for (int k = 0; k < n && loss_terms; ++k) {
+        LevelWs& L = ctx->lv[lv[k]];
+        Timer t(ctx, s, K_OTHER, 0);
+        HIPCHK(ctx, launch_mse_grad(L.acts.act[ctx->taps.content], L.content_t, L.content_n, 0.f, nullptr, L.content_partial, s));
+        HIPCHK(ctx, launch_tv_finish(xi[lv[k]], ctx->channels, L.h, L.w, L.tv_partial, tvw, nullptr, 1, L.tv_means, s));
+    }
+    return NST_OK;
+}
+// `zero_mask`: the levels whose gradient this call clears when they are not in `level_mask` (levels another rank owns)
+int closure_batched_backward(nst_ctx* ctx, const float* const* xi, float* const* gi, unsigned level_mask, float cw, float tvw,
+                             hipStream_t s, unsigned zero_mask) {
+    for (int i = 0; i < ctx->levels; ++i)
+        if (!((level_mask >> i) & 1u) && ((zero_mask >> i) & 1u))
+            HIPCHK(ctx, launch_zero(gi[i], (size_t)ctx->channels * ctx->lv[i].h * ctx->lv[i].w, s));
+    int lv[NST_MAX_LEVELS];
+    const int n = level_list(ctx, level_mask, lv);
+    if (n == 0) return NST_OK;
     return batched_backward(ctx, xi, gi, lv, n, cw, tvw, s, nullptr, nullptr, 0, 0);
+}
+int closure_batched(nst_ctx* ctx, const float* const* xi, float* const* gi, unsigned level_mask, float cw, float sw,
+                    float tvw, hipStream_t s, unsigned zero_mask = ~0u) {
+    NSTCHK(closure_batched_forward(ctx, xi, level_mask, sw, tvw, s, false));
+    return closure_batched_backward(ctx, xi, gi, level_mask, cw, tvw, s, zero_mask);
 }
 
 bool batch_eligible(const nst_ctx* ctx) {
@@ -603,20 +634,31 @@ LossAssembly fill_loss_assembly(const nst_ctx* ctx, unsigned level_mask, float c
     return la;
 }
 
-// enqueues the whole closure on `main` (no host synchronisation; capturable unless it forks level streams)
+// enqueues the closure on `main` (no host synchronisation; capturable unless it forks level streams): all of it, or - the
+// batched schedule only - one of its halves.  FORWARD: pyramid, forward, Gram, loss row (`grad` unused); BACKWARD: the
+// backward of the forward half the level workspaces still hold, and the bicubic-transpose chain (`losses` unused)
+enum Half { WHOLE = 0, FORWARD = 1, BACKWARD = 2 };
 int closure_record(nst_ctx* ctx, const float* x, float cw, float sw, float tvw, unsigned level_mask, float* grad,
-                   float* losses, hipStream_t main) {
+                   float* losses, hipStream_t main, Half half = WHOLE) {
+    const bool batch = batch_eligible(ctx);
+    if (!batch && half != WHOLE) return fail(ctx, NST_E_STATE, "the closure halves run on the batched schedule only");
     // pyramid of the optimised image (neural_style_transfer.py:170-176)
     const float* xi[NST_MAX_LEVELS];
     float* gi[NST_MAX_LEVELS];
     xi[0] = x; gi[0] = grad;
     for (int i = 1; i < ctx->levels; ++i) {
         LevelWs& L = ctx->lv[i];
+        xi[i] = L.xl; gi[i] = L.gxl;
+        if (half == BACKWARD) continue;      // (the forward half left the level images in place)
         Timer t(ctx, main, K_OTHER, 0);
         HIPCHK(ctx, launch_bicubic_down(xi[i - 1], ctx->channels, ctx->lv[i - 1].h, ctx->lv[i - 1].w, L.h, L.w, L.xl, main));
-        xi[i] = L.xl; gi[i] = L.gxl;
     }
-    const bool batch = batch_eligible(ctx);
+    // the levels in `mask` on stream s
+    auto batched = [&](unsigned mask, hipStream_t s, unsigned zero_mask) -> int {
+        if (half == WHOLE) return closure_batched(ctx, xi, gi, mask, cw, sw, tvw, s, zero_mask);
+        if (half == FORWARD) return closure_batched_forward(ctx, xi, mask, sw, tvw, s, true);
+        return closure_batched_backward(ctx, xi, gi, mask, cw, tvw, s, zero_mask);
+    };
     if (batch) {
         const unsigned top = level_mask & 1u, rest = level_mask & ~1u;
         if (ctx->level_split && ctx->side && !ctx->use_graph && top && rest) {
@@ -625,12 +667,12 @@ int closure_record(nst_ctx* ctx, const float* x, float cw, float sw, float tvw, 
             // fill one another, as two jobs on one GPU do.  Same kernels on the same tiles: bitwise the same.
             HIPCHK(ctx, hipEventRecord(ctx->side_fork, main));
             HIPCHK(ctx, hipStreamWaitEvent(ctx->side, ctx->side_fork, 0));
-            NSTCHK(closure_batched(ctx, xi, gi, top, cw, sw, tvw, main, 1u));
-            NSTCHK(closure_batched(ctx, xi, gi, rest, cw, sw, tvw, ctx->side, ~1u));
+            NSTCHK(batched(top, main, 1u));
+            NSTCHK(batched(rest, ctx->side, ~1u));
             HIPCHK(ctx, hipEventRecord(ctx->side_join, ctx->side));
             HIPCHK(ctx, hipStreamWaitEvent(main, ctx->side_join, 0));
         } else {
-            NSTCHK(closure_batched(ctx, xi, gi, level_mask, cw, sw, tvw, main));
+            NSTCHK(batched(level_mask, main, ~0u));
         }
     }
     const bool multi = !batch && !ctx->single_stream && ctx->levels > 1;
@@ -656,12 +698,12 @@ int closure_record(nst_ctx* ctx, const float* x, float cw, float sw, float tvw, 
         for (int i = 0; i < ctx->levels; ++i) HIPCHK(ctx, hipStreamWaitEvent(main, ctx->lv[i].done, 0));
 
     // pull the coarse-level gradients back up the bicubic chain (autograd of :173-176)
-    for (int i = ctx->levels - 1; i >= 1; --i) {
+    for (int i = ctx->levels - 1; i >= 1 && half != FORWARD; --i) {
         Timer t(ctx, main, K_OTHER, 0);
         HIPCHK(ctx, launch_bicubic_down_bwd(gi[i], ctx->channels, ctx->lv[i - 1].h, ctx->lv[i - 1].w, ctx->lv[i].h, ctx->lv[i].w,
                                             gi[i - 1], 1, main));
     }
-    HIPCHK(ctx, launch_loss_assemble(fill_loss_assembly(ctx, level_mask, cw, sw, tvw, losses), main));
+    if (half != BACKWARD) HIPCHK(ctx, launch_loss_assemble(fill_loss_assembly(ctx, level_mask, cw, sw, tvw, losses), main));
     return NST_OK;
 }
 
@@ -693,7 +735,7 @@ extern "C" {
 
 int nst_level_set_targets(nst_ctx* ctx, int level, const float* content, const float* style, int hs, int ws,
                           void* stream) {
-    if (ctx) ++ctx->closure_epoch;
+    if (ctx) { ++ctx->closure_epoch; ++ctx->ws_seq; }
     NSTCHK(bind(ctx));
     if (level < 0 || level >= ctx->levels) return fail(ctx, NST_E_STATE, "level not configured");
     if (!content || !style) return fail(ctx, NST_E_ARG, "null image");
@@ -738,6 +780,7 @@ int nst_closure(nst_ctx* ctx, const float* x, float cw, float sw, float tvw, flo
 int nst_closure_levels(nst_ctx* ctx, const float* x, float cw, float sw, float tvw, unsigned level_mask, float* grad,
                        float* losses, void* stream) {
     NSTCHK(bind(ctx));
+    ++ctx->ws_seq;
     if (ctx->levels < 1) return fail(ctx, NST_E_STATE, "nst_job_configure has not been called");
     if (!x || !grad || !losses) return fail(ctx, NST_E_ARG, "null buffer");
     for (int i = 0; i < ctx->levels; ++i)
@@ -748,6 +791,7 @@ int nst_closure_levels(nst_ctx* ctx, const float* x, float cw, float sw, float t
     ctx->timed.clear();
     ctx->ev_used = 0;
     ctx->timed_valid = false;
+    ctx->timed_backward = false;
     // mode 4: event pairs around the conv launches of every fourth closure only - a pair around each of the 24 conv
     // launches of EVERY closure (mode 3) costs 5 % of the closure rate at 9.5 ms per closure
     ctx->sample_now = (ctx->timing != 4) || ((ctx->closure_seq++ & 3) == 0);
@@ -785,6 +829,63 @@ int nst_closure_levels(nst_ctx* ctx, const float* x, float cw, float sw, float t
     return NST_OK;
 }
 
+// ---- the closure in two halves (include/nst_hip.h) -----------------------------------------------------------------
+// A caller that needs the loss before it knows whether it needs the gradient - a line search whose trial point is taken
+// or dropped on its loss alone - evaluates the forward half, reads the loss, and runs the backward half only for a point
+// it takes.  Both halves are the launches of nst_closure_levels on the batched schedule, in its order.
+int nst_closure_forward(nst_ctx* ctx, const float* x, float cw, float sw, float tvw, unsigned level_mask, float* losses,
+                        void* stream) {
+    NSTCHK(bind(ctx));
+    ++ctx->ws_seq;
+    ctx->fwd_token.valid = false;
+    if (ctx->levels < 1) return fail(ctx, NST_E_STATE, "nst_job_configure has not been called");
+    if (!x || !losses) return fail(ctx, NST_E_ARG, "null buffer");
+    for (int i = 0; i < ctx->levels; ++i)
+        if (((level_mask >> i) & 1u) && !ctx->lv[i].targets)
+            return fail(ctx, NST_E_STATE, "targets of level " + std::to_string(i) + " not set");
+    if (!batch_eligible(ctx) || ctx->use_graph)
+        return fail(ctx, NST_E_UNAVAILABLE, "the closure halves run on the batched schedule without a hipGraph only: use nst_closure");
+    hipStream_t main = enter(ctx, stream);
+    if (ctx->timing >= 2) NSTCHK(fold_timed(ctx));
+    ctx->timed.clear();
+    ctx->ev_used = 0;
+    ctx->timed_valid = false;
+    ctx->timed_backward = false;
+    ctx->sample_now = (ctx->timing != 4) || ((ctx->closure_seq++ & 3) == 0);
+    if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->t0, main));
+    const int rc = closure_record(ctx, x, cw, sw, tvw, level_mask, nullptr, losses, main, FORWARD);
+    if (rc == NST_OK && ctx->timing && hipEventRecord(ctx->t1, main) == hipSuccess) ctx->timed_valid = true;
+    mark(ctx, main);             // on every path out that may have launched work
+    NSTCHK(rc);
+    ctx->fwd_token = {true, x, cw, sw, tvw, level_mask, ctx->closure_epoch, ctx->ws_seq};
+    return NST_OK;
+}
+
+int nst_closure_backward(nst_ctx* ctx, const float* x, float cw, float sw, float tvw, unsigned level_mask, float* grad,
+                         void* stream) {
+    NSTCHK(bind(ctx));
+    if (!x || !grad) return fail(ctx, NST_E_ARG, "null buffer");
+    const nst_ctx::ForwardToken tk = ctx->fwd_token;
+    const float w[3] = {cw, sw, tvw}, tw[3] = {tk.cw, tk.sw, tk.tvw};
+    if (!tk.valid || tk.seq != ctx->ws_seq || tk.epoch != ctx->closure_epoch || tk.x != x || tk.mask != level_mask ||
+        std::memcmp(w, tw, sizeof(w)) != 0)
+        return fail(ctx, NST_E_STATE, "nst_closure_backward: no forward half of these arguments is the last use of the context's workspaces");
+    ++ctx->ws_seq;               // (one backward per forward: the gradient buffers of the levels are consumed)
+    ctx->fwd_token.valid = false;
+    hipStream_t main = enter(ctx, stream);
+    // timing: the forward half's record is folded as a closure, this half's launches and time then join the totals
+    if (ctx->timing >= 2) NSTCHK(fold_timed(ctx));
+    ctx->timed.clear();
+    ctx->ev_used = 0;
+    ctx->timed_valid = false;
+    ctx->timed_backward = true;
+    if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->t0, main));
+    const int rc = closure_record(ctx, x, cw, sw, tvw, level_mask, grad, nullptr, main, BACKWARD);
+    if (rc == NST_OK && ctx->timing && hipEventRecord(ctx->t1, main) == hipSuccess) ctx->timed_valid = true;
+    mark(ctx, main);
+    return rc;
+}
+
 // ---- stripe (window) closure: spatial sharding of one pyramid level -------------------------------------
 int nst_window_sums_count(size_t* count) {
     if (!count) return fail(nullptr, NST_E_ARG, "null argument");
@@ -794,6 +895,7 @@ int nst_window_sums_count(size_t* count) {
 
 int nst_window_begin(nst_ctx* ctx, const float* xs, int row0, int rows, int H0, float* sums, void* stream) {
     NSTCHK(bind(ctx));
+    ++ctx->ws_seq;
     NSTCHK(window_check(ctx, xs, row0, rows, H0));
     if (!sums) return fail(ctx, NST_E_ARG, "null buffer");
     hipStream_t s = enter(ctx, stream);
@@ -831,6 +933,7 @@ int nst_window_begin(nst_ctx* ctx, const float* xs, int row0, int rows, int H0, 
 int nst_window_end(nst_ctx* ctx, const float* xs, int row0, int rows, int H0, float cw, float sw, float tvw, float* sums,
                    float* gxs, float* losses, void* stream) {
     NSTCHK(bind(ctx));
+    ++ctx->ws_seq;
     NSTCHK(window_check(ctx, xs, row0, rows, H0));
     if (!sums || !gxs || !losses) return fail(ctx, NST_E_ARG, "null buffer");
     hipStream_t s = enter(ctx, stream);

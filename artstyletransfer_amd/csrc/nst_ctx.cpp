@@ -337,8 +337,11 @@ int fold_timed(nst_ctx* ctx) {
     float ms = 0.f;
     HIPCHK(ctx, hipEventElapsedTime(&ms, ctx->t0, ctx->t1));
     ctx->acc_closure_ms += ms;
-    ctx->acc_closures += 1;
-    if (!ctx->timed.empty()) ctx->acc_sampled += 1;
+    if (!ctx->timed_backward) {          // (a backward half belongs to the closure its forward half counted)
+        ctx->acc_closures += 1;
+        if (!ctx->timed.empty()) ctx->acc_sampled += 1;
+    }
+    ctx->timed_backward = false;
     for (const TimedLaunch& t : ctx->timed) {
         float d = 0.f;
         HIPCHK(ctx, hipEventSynchronize(t.b));
@@ -592,7 +595,7 @@ int nst_ctx_bytes(const nst_ctx* ctx, size_t* bytes) {
 }
 
 int nst_job_configure(nst_ctx* ctx, int levels_num, int H0, int W0) {
-    if (ctx) ++ctx->closure_epoch;
+    if (ctx) { ++ctx->closure_epoch; ++ctx->ws_seq; }
     NSTCHK(bind(ctx));
     if (levels_num < 1 || levels_num > NST_MAX_LEVELS) return fail(ctx, NST_E_ARG, "levels_num out of range");
     if ((H0 >> (levels_num - 1)) < 16 || (W0 >> (levels_num - 1)) < 16)
@@ -623,7 +626,7 @@ int nst_job_configure(nst_ctx* ctx, int levels_num, int H0, int W0) {
 // LossBuilder(content_feature_maps_index, style_feature_maps_indices, ...) and Vgg19(use_relu=...) of the reference
 // (neural_style_transfer.py:41-82, neural_nets.py:17-28) as a context setting
 int nst_job_set_taps(nst_ctx* ctx, int content_index, unsigned style_mask, int use_relu) {
-    if (ctx) ++ctx->closure_epoch;
+    if (ctx) { ++ctx->closure_epoch; ++ctx->ws_seq; }
     NSTCHK(bind(ctx));
     if (content_index < 0 || content_index > 5) return fail(ctx, NST_E_ARG, "content_index must be 0 .. 5");
     if (style_mask == 0u || (style_mask & ~0x3Fu) != 0u)
@@ -652,7 +655,7 @@ int nst_job_set_taps(nst_ctx* ctx, int content_index, unsigned style_mask, int u
 // Gatys et al. 2016, luminance-only transfer: the optimised image becomes one plane u = 255 Y (channels = 1) that the
 // network sees as x_c = u - mean_c.  Same life cycle as the taps: every level's targets and the captured closure go.
 int nst_job_set_color(nst_ctx* ctx, int mode) {
-    if (ctx) ++ctx->closure_epoch;
+    if (ctx) { ++ctx->closure_epoch; ++ctx->ws_seq; }
     NSTCHK(bind(ctx));
     if (mode != NST_COLOR_RGB && mode != NST_COLOR_LUMINANCE) return fail(ctx, NST_E_ARG, "mode must be NST_COLOR_RGB or NST_COLOR_LUMINANCE");
     const int channels = mode == NST_COLOR_LUMINANCE ? 1 : 3;
@@ -690,7 +693,7 @@ int nst_job_color(const nst_ctx* ctx) { return ctx ? (ctx->channels == 1 ? NST_C
 // Gatys et al. 2016, section 2: average instead of max pooling in the feature network.  Same life cycle as the taps and the
 // colour mode: every level's targets (made with the other network) and the captured closure go; no buffer changes size.
 int nst_job_set_pooling(nst_ctx* ctx, int mode) {
-    if (ctx) ++ctx->closure_epoch;
+    if (ctx) { ++ctx->closure_epoch; ++ctx->ws_seq; }
     NSTCHK(bind(ctx));
     if (mode != NST_POOL_MAX && mode != NST_POOL_AVG) return fail(ctx, NST_E_ARG, "mode must be NST_POOL_MAX or NST_POOL_AVG");
     quiesce(ctx);

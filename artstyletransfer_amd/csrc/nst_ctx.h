@@ -157,6 +157,17 @@ struct nst_ctx {
     // bumped on entry to every call that changes what a closure computes (configure, taps, colour, pooling, targets), failure paths
     // included: an optimiser's remembered closure result is valid only under the epoch it was made in (nst_opt.cpp)
     unsigned long long closure_epoch = 0;
+    // advanced on entry to every call that reads or writes the level workspaces (nst_closure*, nst_window_*,
+    // nst_level_activation, nst_level_set_targets, nst_job_*): what tells nst_closure_backward that the forward it
+    // belongs to is still the last thing that used them
+    unsigned long long ws_seq = 0;
+    struct ForwardToken {                // the arguments and state of the last nst_closure_forward
+        bool valid = false;
+        const float* x = nullptr;
+        float cw = 0.f, sw = 0.f, tvw = 0.f;
+        unsigned mask = 0;
+        unsigned long long epoch = 0, seq = 0;
+    } fwd_token;
     double* color_scratch = nullptr;   // nst_color_stats: COLOR_BLOCKS * 9 partials | mean (3) | cov (9), made on first use
     nst::LevelWs lv[NST_MAX_LEVELS];
     hipEvent_t fork = nullptr;
@@ -169,6 +180,8 @@ struct nst_ctx {
     size_t ev_used = 0;
     std::vector<nst::TimedLaunch> timed;
     bool timed_valid = false;
+    bool timed_backward = false; // the pending record is a backward half (nst_closure_backward): its launches and time
+                                 // join the totals, the closure was counted with its forward half
     // accumulated over closures since the last reset (timing mode 2)
     double acc_ms[4] = {0, 0, 0, 0};
     double acc_flops[4] = {0, 0, 0, 0};

@@ -106,6 +106,13 @@ struct nst_opt {
     bool reuse = true;
     ClosureMemo memo;
     long served = 0;             // closures served from the memo (counted in total_closures like evaluated ones)
+    // L-BFGS lazy backward (env NST_LAZY_BACKWARD, default on; nst_opt_set_lazy_backward)
+    bool lazy = true;
+    bool fwd_pending = false;    // the last closure ran as a forward half whose backward half can still be run
+    bool no_halves = false;      // nst_closure_forward reported NST_E_UNAVAILABLE under closure epoch no_halves_epoch:
+    unsigned long long no_halves_epoch = 0;   // not asked again until the job changes
+    long forward_only = 0;       // evaluated closures that ran as a forward half
+    long skipped = 0;            // ... whose backward half never ran
 };
 
 namespace {
@@ -137,11 +144,21 @@ struct GradStats {
     float gmax = 0.f, gsum = 0.f, gdot = 0.f;
 };
 
-// one closure evaluation at x: decays lr, fills o->g, returns the total loss (host) - synchronises once
+// one closure evaluation at x: decays lr, fills o->g, returns the total loss (host) - synchronises once.
+// `forward_only` (lazy_applies; no GradStats): the loss row alone by nst_closure_forward - o->g keeps what it held, and
+// o->fwd_pending says that nst_closure_backward can still fill it; where the context has no forward half, the whole closure
 int eval_closure(nst_opt* o, const float* x, float cw, float sw, float tvw, hipStream_t s, float* loss_out,
-                 GradStats* gs = nullptr) {
+                 GradStats* gs = nullptr, bool forward_only = false) {
     o->lr *= 0.999;                                                          // neural_style_transfer.py:155-158
-    OCHK(nst_closure_levels(o->ctx, x, cw, sw, tvw, o->level_mask, o->g, o->losses, s));
+    o->fwd_pending = false;
+    if (forward_only && !(o->no_halves && o->no_halves_epoch == nst_internal_closure_epoch(o->ctx))) {
+        const int rc = nst_closure_forward(o->ctx, x, cw, sw, tvw, o->level_mask, o->losses, s);
+        if (rc == NST_OK) { o->fwd_pending = true; o->forward_only += 1; }
+        else if (rc != NST_E_UNAVAILABLE) return rc;
+        o->no_halves = rc == NST_E_UNAVAILABLE;
+        o->no_halves_epoch = nst_internal_closure_epoch(o->ctx);
+    }
+    if (!o->fwd_pending) OCHK(nst_closure_levels(o->ctx, x, cw, sw, tvw, o->level_mask, o->g, o->losses, s));
     if (o->comm) OCHK(nst_comm_allreduce_sum(o->comm, o->pack, o->pack_floats, s));   // gradient + loss row, one call
     else if (o->hook) o->hook(o->hook_user);                                 // all-reduce(sum) over the ranks
     const size_t row = (size_t)NST_LOSS_ROW * o->levels + 1;
@@ -225,16 +242,28 @@ double cubic_interpolate(double x1, double f1, double g1, double x2, double f2, 
 
 struct LsResult { double t; float f; int evals; double last_t; };   // last_t: the step length evaluated last
 
+bool lazy_applies(const nst_opt* o);
+
 // torch:optim/lbfgs.py:40-209.  Gradients of bracket points are never needed by the caller with
 // max_iter == 1 (only f, g.d and t are consumed), so no gradient clones are kept.
 int strong_wolfe(nst_opt* o, float* x, double t, float f, float gtd, float d_norm, int max_ls, float cw, float sw,
                  float tvw, hipStream_t s, LsResult* res) {
     const double c1 = 1e-4, c2 = 0.9, tol_change = 1e-9;
     double last_t = t;
-    auto eval_at = [&](double tt, float* f_new, float* gtd_new) -> int {
+    const bool lazy = lazy_applies(o);
+    // `ls_after`: ls_iter once this evaluation is counted.  At ls_after == max_ls neither loop below runs again, so of this
+    // evaluation only f_new can reach the result: gtd_new goes into br_gtd (read by cubic_interpolate alone, which is not
+    // reached), into `done` (which only ends a loop that has ended) and into br[high] (not returned), and the gradient is
+    // read by the caller only if this point is the one taken.  Such an evaluation runs as a forward half, without g.d
+    // (gtd_new = 0); the caller runs the backward half if it takes the point.
+    auto eval_at = [&](double tt, int ls_after, float* f_new, float* gtd_new) -> int {
         // x = x_init + t*d ; closure ; (x restored by the caller at the end)
         last_t = tt;
         OHIP(o, launch_add_scaled(o->xinit, (float)tt, o->d, x, o->n, s));
+        if (lazy && ls_after == max_ls) {
+            *gtd_new = 0.f;
+            return eval_closure(o, x, cw, sw, tvw, s, f_new, nullptr, true);
+        }
         GradStats gs;
         gs.dot_with = o->d;
         OCHK(eval_closure(o, x, cw, sw, tvw, s, f_new, &gs));
@@ -242,7 +271,7 @@ int strong_wolfe(nst_opt* o, float* x, double t, float f, float gtd, float d_nor
         return NST_OK;
     };
     float f_new, gtd_new;
-    OCHK(eval_at(t, &f_new, &gtd_new));
+    OCHK(eval_at(t, 0, &f_new, &gtd_new));
     int evals = 1;
     double t_prev = 0; float f_prev = f; float gtd_prev = gtd;
     bool done = false;
@@ -267,7 +296,7 @@ int strong_wolfe(nst_opt* o, float* x, double t, float f, float gtd, float d_nor
         const double tmp = t;
         t = cubic_interpolate(t_prev, f_prev, gtd_prev, t, f_new, gtd_new, true, min_step, max_step);
         t_prev = tmp; f_prev = f_new; gtd_prev = gtd_new;
-        OCHK(eval_at(t, &f_new, &gtd_new));
+        OCHK(eval_at(t, ls_iter + 1, &f_new, &gtd_new));
         evals += 1;
         ls_iter += 1;
     }
@@ -292,7 +321,7 @@ int strong_wolfe(nst_opt* o, float* x, double t, float f, float gtd, float d_nor
         } else {
             insuf = false;
         }
-        OCHK(eval_at(t, &f_new, &gtd_new));
+        OCHK(eval_at(t, ls_iter + 1, &f_new, &gtd_new));
         evals += 1;
         ls_iter += 1;
         if (f_new > (float)(f + (float)(c1 * t) * gtd) || f_new >= br_f[low]) {
@@ -377,6 +406,13 @@ int gram_direction(nst_opt* o, bool new_pair, hipStream_t s) {
 bool memo_applies(const nst_opt* o) {
     const unsigned all = o->levels >= 32 ? 0xFFFFFFFFu : (1u << o->levels) - 1u;
     return o->reuse && !o->comm && !o->hook && (o->level_mask & all) == all;
+}
+
+// a forward half in place of a whole closure: under the conditions of the memo without its switch (a rank-local decision
+// to skip a backward pass would leave the other ranks' all-reduce of the gradient alone), L-BFGS only
+bool lazy_applies(const nst_opt* o) {
+    const unsigned all = o->levels >= 32 ? 0xFFFFFFFFu : (1u << o->levels) - 1u;
+    return o->lazy && o->kind == NST_OPT_LBFGS && !o->comm && !o->hook && (o->level_mask & all) == all;
 }
 
 // The first closure of an L-BFGS step, served from a valid memo if x is bitwise its P under the same weights and context
@@ -550,6 +586,13 @@ int lbfgs_step(nst_opt* o, float* x, float cw, float sw, float tvw, hipStream_t 
         info->t = (float)t;
         moved = t != 0.0;
         g_at_x = moved && r.last_t == t;                         // the last closure was at the point taken: its g is in g
+        if (o->fwd_pending) {
+            // the last closure was a forward half.  Taken: x holds xinit + t d, bitwise the image it evaluated (written again
+            // above with the same operands), so its backward half puts g(x) into g now.  Not taken: nothing reads its gradient
+            if (g_at_x) OCHK(nst_closure_backward(o->ctx, x, cw, sw, tvw, o->level_mask, o->g, s));
+            else o->skipped += 1;
+            o->fwd_pending = false;
+        }
     }
     o->t = t;
     if (memo_on) {
@@ -583,6 +626,8 @@ int nst_opt_create(nst_ctx* ctx, int kind, float lr_start, int lbfgs_max_eval, n
     o->max_eval = lbfgs_max_eval < 1 ? 1 : lbfgs_max_eval;
     const char* reuse_env = std::getenv("NST_CLOSURE_REUSE");
     o->reuse = !(reuse_env && reuse_env[0] && std::atoi(reuse_env) == 0);
+    const char* lazy_env = std::getenv("NST_LAZY_BACKWARD");
+    o->lazy = !(lazy_env && lazy_env[0] && std::atoi(lazy_env) == 0);
     const size_t row = (size_t)NST_LOSS_ROW * o->levels + 1;
     // gradient and loss row live in ONE allocation (gradient padded to 64 floats): the sharded closure all-reduces both
     // with a single collective (nst_opt_shard_levels_comm)
@@ -693,6 +738,19 @@ int nst_opt_closure_stats(const nst_opt* o, long* evaluated, long* served) {
     if (!o) return nst_internal_fail(nullptr, NST_E_ARG, "null optimiser");
     if (evaluated) *evaluated = (long)o->total_closures - o->served;
     if (served) *served = o->served;
+    return NST_OK;
+}
+
+int nst_opt_set_lazy_backward(nst_opt* o, int enabled) {
+    if (!o) return nst_internal_fail(nullptr, NST_E_ARG, "null optimiser");
+    o->lazy = enabled != 0;
+    return NST_OK;
+}
+
+int nst_opt_backward_stats(const nst_opt* o, long* forward_only, long* skipped) {
+    if (!o) return nst_internal_fail(nullptr, NST_E_ARG, "null optimiser");
+    if (forward_only) *forward_only = o->forward_only;
+    if (skipped) *skipped = o->skipped;
     return NST_OK;
 }
 

@@ -205,6 +205,33 @@ class StyleEngine:
                                                          _ptr(losses), _stream(self.device)), "nst_closure_levels")
         return grad, losses
 
+    def closure_forward(self, x: torch.Tensor, cw: float, sw: float, tvw: float, mask: int = 0xFFFFFFFF,
+                        losses: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The forward half of the closure (nst_closure_forward): the loss row alone, bitwise closure()'s.  NstError
+        with code NST_E_UNAVAILABLE outside the batched schedule."""
+        _chk_dev(x, self.device)
+        if x.numel() != self.channels * self.shape[0] * self.shape[1]:
+            raise NstError("x has the wrong number of elements")
+        if losses is None:
+            losses = torch.empty(NST_LOSS_ROW * self.levels + 1, dtype=torch.float32, device=self.device)
+        _lib.check(self.ctx, self.lib.nst_closure_forward(self.ctx, _ptr(x), cw, sw, tvw, mask, _ptr(losses),
+                                                          _stream(self.device)), "nst_closure_forward")
+        return losses
+
+    def closure_backward(self, x: torch.Tensor, cw: float, sw: float, tvw: float, mask: int = 0xFFFFFFFF,
+                         grad: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The backward half of the last closure_forward (nst_closure_backward): the gradient, bitwise closure()'s.  Valid
+        only with that call's arguments and while nothing else has used the context since; else NstError (NST_E_STATE)."""
+        H, W = self.shape
+        _chk_dev(x, self.device)
+        if grad is None:
+            grad = torch.empty((1, self.channels, H, W), dtype=torch.float32, device=self.device)
+        elif grad.numel() != self.channels * H * W:
+            raise NstError("grad has the wrong number of elements")
+        _lib.check(self.ctx, self.lib.nst_closure_backward(self.ctx, _ptr(x), cw, sw, tvw, mask, _ptr(grad),
+                                                           _stream(self.device)), "nst_closure_backward")
+        return grad
+
     # ---- stripe (window) closure: this engine evaluates a horizontal stripe of a larger image (sharding.StripePlan)
     def window_sums_count(self) -> int:
         n = C.c_size_t()
@@ -565,6 +592,20 @@ class PixelOptimizer:
         _lib.check(self.engine.ctx, self.engine.lib.nst_opt_closure_stats(self.h, C.byref(ev), C.byref(sv)),
                    "nst_opt_closure_stats")
         return ev.value, sv.value
+
+    def set_lazy_backward(self, enabled: bool) -> None:
+        """L-BFGS: evaluate the last trial point a line-search budget allows by its forward half and run the backward
+        half only when the point is taken (nst_opt_set_lazy_backward; default on, env NST_LAZY_BACKWARD=0 off).  Results
+        are the same either way."""
+        _lib.check(self.engine.ctx, self.engine.lib.nst_opt_set_lazy_backward(self.h, int(bool(enabled))),
+                   "nst_opt_set_lazy_backward")
+
+    def backward_stats(self):
+        """(closures evaluated by their forward half only, those of them whose backward half never ran) so far."""
+        fo, sk = C.c_long(), C.c_long()
+        _lib.check(self.engine.ctx, self.engine.lib.nst_opt_backward_stats(self.h, C.byref(fo), C.byref(sk)),
+                   "nst_opt_backward_stats")
+        return fo.value, sk.value
 
     def shard_levels(self, rank: int, world: int, dist_mod=None, group=None) -> None:
         """Level sharding (BASELINE config 4): this rank evaluates only its levels; after every closure

@@ -34,6 +34,8 @@ extern "C" {
 #define NST_E_STATE (-2)    /* call order violated (e.g. closure before targets) */
 #define NST_E_HIP (-3)      /* a HIP runtime call failed; see nst_last_error */
 #define NST_E_NOMEM (-4)
+#define NST_E_UNAVAILABLE (-5) /* this entry point does not run under the context's schedule; nothing was launched, use the
+                                  entry point named in nst_last_error instead */
 
 #define NST_VGG19_CONVS 13  /* conv1_1 ... conv5_1 (torchvision features[0:30]) */
 #define NST_MAX_LEVELS 8
@@ -187,6 +189,26 @@ int nst_closure(nst_ctx* ctx, const float* x, float content_weight, float style_
 int nst_closure_levels(nst_ctx* ctx, const float* x, float content_weight, float style_weight,
                        float tv_weight, unsigned level_mask, float* grad, float* losses, void* stream);
 
+/* nst_closure_levels in two halves, for a caller that needs the loss before it knows whether it needs the gradient (a
+ * line search that takes or drops a trial point on its loss alone; the reference always runs both: loss.backward() at
+ * neural_style_transfer.py:193).  Same arguments, same launches in the same order:
+ *   nst_closure_forward: the bicubic pyramid, the forward convolutions, every Gram launch, the loss terms; writes
+ *     `losses`, BITWISE the row nst_closure_levels writes for these arguments.  Nothing of the backward is launched.
+ *   nst_closure_backward: the backward pass of that forward; writes `grad`, BITWISE the gradient nst_closure_levels
+ *     writes.  x must still hold the image the forward half evaluated (the total-variation gradient reads it).
+ * Validity: the backward half belongs to the LAST nst_closure_forward on the context and is valid only while that
+ * forward is the last thing that used the context's workspaces - no nst_closure / nst_closure_levels, nst_window_*,
+ * nst_level_activation, nst_level_set_targets or nst_job_* call in between, not even a failed one - and only with the
+ * same x pointer, weights and level_mask, once.  Otherwise it returns NST_E_STATE, launches nothing and leaves `grad`
+ * untouched; the context stays usable.  Both halves run on the batched schedule only (nst_options.batched, its default,
+ * without use_graph): elsewhere nst_closure_forward returns NST_E_UNAVAILABLE before it launches anything, and the
+ * caller evaluates nst_closure_levels.  Asynchronous on `stream`.  Timing (nst_set_timing): a forward half is one
+ * closure record; its backward half adds its launches and time to the totals without counting a second closure. */
+int nst_closure_forward(nst_ctx* ctx, const float* x, float content_weight, float style_weight, float tv_weight,
+                        unsigned level_mask, float* losses, void* stream);
+int nst_closure_backward(nst_ctx* ctx, const float* x, float content_weight, float style_weight, float tv_weight,
+                         unsigned level_mask, float* grad, void* stream);
+
 /* torch.optim.Adam / torch.optim.LBFGS as constructed at neural_style_transfer.py:134-136,
  * driving nst_closure, including the closure's `lr *= 0.999` (:155-158).  kind: 0 = adam
  * (torch:optim/adam.py:457-546, betas (0.9,0.999), eps 1e-8), 1 = lbfgs
@@ -244,6 +266,16 @@ int nst_opt_history(const nst_opt* opt, int* pairs, int* n_iter);
 int nst_opt_set_closure_reuse(nst_opt* opt, int enabled);
 /* closures this optimiser evaluated and served so far (their sum is nst_step_info.total_closures) */
 int nst_opt_closure_stats(const nst_opt* opt, long* evaluated, long* served);
+
+/* L-BFGS lazy backward (default on; env NST_LAZY_BACKWARD=0 at nst_opt_create turns it off).  The last evaluation a
+ * line-search budget allows (with lbfgs_max_eval 1: every trial point) is used for its loss alone unless its point is
+ * the one taken: strong_wolfe (torch:optim/lbfgs.py:40-209) never reads its gradient or its g.d again.  The driver
+ * evaluates it with nst_closure_forward, decides as before, and runs nst_closure_backward only when that point is taken.
+ * Loss rows, step info, lr decay, closure counts and the image are bitwise what they are with the setting off.  Never in
+ * the sharded modes or under a partial level mask, and not where nst_closure_forward is unavailable; Adam never. */
+int nst_opt_set_lazy_backward(nst_opt* opt, int enabled);
+/* evaluated closures that ran as a forward half only so far, and those of them whose backward half never ran */
+int nst_opt_backward_stats(const nst_opt* opt, long* forward_only, long* skipped);
 
 /* ---- RCCL communicator (one rank per GPU; the reference has no collective: neural_style_transfer.py:236-245).
  * librccl is resolved at run time; without it these return NST_E_STATE.  Bootstrap: rank 0 calls nst_comm_unique_id and
