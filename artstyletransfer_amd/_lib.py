@@ -48,6 +48,12 @@ class Options(C.Structure):
                 ("h2_wg256", C.c_int), ("h2_tile_rows", C.c_int), ("gram_overlap", C.c_int), ("h2_persist", C.c_int), ("level_split", C.c_int), ("h2_winograd", C.c_int)]
 
 
+class LaunchInfo(C.Structure):
+    """nst_launch_info: one timed launch of the last closure and the kernel shape the conv_h2 launcher decided for it."""
+    _fields_ = [(n, C.c_int) for n in ("cls", "h", "w", "cin", "cout", "layer", "h2_rows", "h2_bn", "h2_ntw", "h2_chunk",
+                                       "h2_mfma16", "h2_persist", "h2_second", "h2_unpool", "h2_bands")]
+
+
 # name -> (restype, argtypes); every symbol include/nst_hip.h declares
 SYMBOLS = {
     "nst_version": (C.c_int, []),
@@ -119,6 +125,7 @@ SYMBOLS = {
     "nst_last_closure_ms": (C.c_int, [c_void, C.POINTER(C.c_float)]),
     "nst_last_closure_class": (C.c_int, [c_void, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int),
                                          C.POINTER(C.c_double)]),
+    "nst_last_closure_launches": (C.c_int, [c_void, C.POINTER(LaunchInfo), C.c_int, C.POINTER(C.c_int)]),
     "nst_dump_last_closure": (C.c_int, [c_void]),
     "nst_timing_totals": (C.c_int, [c_void, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_long),
                                     C.POINTER(C.c_double), C.c_int]),

@@ -1318,6 +1318,9 @@ __global__ __launch_bounds__((H2Cfg<TH, BN, NTW, KC>::NT), (H2Cfg<TH, BN, NTW, K
 // the shapes the persistent form is built for: the ones whose launches have more tiles than the chip holds workgroups
 template <int TH, int BN, int NTW, int KC>
 constexpr bool h2_persist_shape = (KC == 16) || (TH == 16 && NTW == 2 && KC == 32);
+// the shapes the 16x16x32 MFMA form is built for: 32-channel chunks, wave tiles of at most 64 x 64
+template <int NTW, int KC>
+constexpr bool h2_m16_built = (KC == 32 && NTW <= 2);
 
 template <int TH, int BN, int NTW, int KC, bool UNPOOL, bool M16>
 static hipError_t init_form() {
@@ -1337,7 +1340,7 @@ static hipError_t init_form() {
 template <int TH, int BN, int NTW, int KC, bool UNPOOL>
 static hipError_t init_one() {
     hipError_t e = init_form<TH, BN, NTW, KC, UNPOOL, false>();
-    if constexpr (KC == 32 && NTW <= 2) {
+    if constexpr (h2_m16_built<NTW, KC>) {
         if (e == hipSuccess) e = init_form<TH, BN, NTW, KC, UNPOOL, true>();
     }
     return e;
@@ -1380,19 +1383,53 @@ static bool h2_use_m16(int mfma16, int th, int ntw, bool unpool) {
     if (mfma16 == 2) return th == 8 || (th == 16 && ntw == 2 && !unpool);
     return mfma16 == 1 && th == 8;
 }
+// workgroups of a shape the chip holds at once: 256 CUs x 2 for the 256-thread shapes that fit twice on a CU
+static int h2_resident(const H2Shape& sh) { return 256 * ((sh.chunk == 16 || sh.rows == 4) ? 2 : 1); }
+
+// THE shape decision of a conv_h2 launch, for both launchers: one layer over the n images (H[i] x W[i]) of a batched launch,
+// or one image of the per-level launcher (persist_opt = 0: it has no persistent form).  unpool / second: the launch un-pools
+// its input in the loader / carries a second K source (Cin == 0: that source alone).  tile_rows, mfma16, wg256, persist_opt:
+// the nst_options of those names.  `blocks` receives the workgroups of a one-tile-per-workgroup grid over all images.
+static H2Shape h2_launch_shape(const int* H, const int* W, int n, int Cin, int Cout, bool unpool, bool second, int tile_rows,
+                               int mfma16, int wg256, int persist_opt, int* blocks) {
+    H2Shape sh{};
+    const bool wide = (Cout % 128 == 0);
+    long blocks16 = 0;
+    for (int i = 0; i < n; ++i) blocks16 += (long)((H[i] + 15) / 16) * ((W[i] + 15) / 16) * (Cout / 128);
+    const bool shortk = wide && Cin > 0 && Cin <= NST_H2_SHORTK_CIN;      // 8-row tiles, two workgroups per CU
+    sh.rows = shortk ? 8 : h2_tile_rows(Cout, blocks16, tile_rows);
+    sh.bn = wide ? 128 : 64;
+    sh.chunk = (!wide || shortk) ? 16 : 32;
+    sh.ntw = (sh.chunk == 16) ? 2 : (sh.rows < 16 ? 1 : (wg256 ? 4 : 2));
+    sh.m16 = (sh.chunk == 32 && sh.ntw <= 2 && h2_use_m16(mfma16, sh.rows, sh.ntw, unpool)) ? 1 : 0;
+    sh.second = second ? 1 : 0;
+    sh.unpool = unpool ? 1 : 0;
+    sh.bands = 1;
+    int tiles = 0;
+    for (int i = 0; i < n; ++i) tiles += ((W[i] + 15) / 16) * ((H[i] + sh.rows - 1) / sh.rows);
+    *blocks = tiles * (Cout / sh.bn);
+    // Persistent form (nst_options.h2_persist): as many workgroups as the chip holds at once (256 CUs x 1 or 2 by the
+    // shape's LDS / thread budget), each walking its share of the tiles with the K pipeline chained across them.  Not for
+    // launches with a second K source (its stages use the LDS buffers the chained prologue would be staged in), and the
+    // 16x16x32 form has no persistent build.
+    const bool pshape = sh.chunk == 16 || (sh.rows == 16 && sh.ntw == 2);
+    sh.persist = (persist_opt && !second && Cin > 0 && *blocks > h2_resident(sh) && pshape && !sh.m16) ? 1 : 0;
+    return sh;
+}
+
 template <int TH, int BN, int NTW, int KC>
-static void launch_batch_cfg(const ConvBatch& b, int blocks, hipStream_t stream) {
+static void launch_batch_cfg(const ConvBatch& b, const H2Shape& sh, int blocks, hipStream_t stream) {
     constexpr int lds = H2Cfg<TH, BN, NTW, KC>::LDS_BYTES;
     constexpr int nt = H2Cfg<TH, BN, NTW, KC>::NT;
-    if constexpr (KC == 32 && NTW <= 2) {
-        if (h2_use_m16(b.mfma16, TH, NTW, b.unpool != 0)) {
+    if constexpr (h2_m16_built<NTW, KC>) {
+        if (sh.m16) {
             if (b.unpool) hipLaunchKernelGGL((conv_h2_batch_kernel<TH, BN, NTW, KC, true, true, false>), dim3(blocks), dim3(nt), lds, stream, b);
             else hipLaunchKernelGGL((conv_h2_batch_kernel<TH, BN, NTW, KC, false, true, false>), dim3(blocks), dim3(nt), lds, stream, b);
             return;
         }
     }
     if constexpr (h2_persist_shape<TH, BN, NTW, KC>) {
-        if (b.persist) {
+        if (sh.persist) {
             if (b.unpool) hipLaunchKernelGGL((conv_h2_batch_kernel<TH, BN, NTW, KC, true, false, true>), dim3(blocks), dim3(nt), lds, stream, b);
             else hipLaunchKernelGGL((conv_h2_batch_kernel<TH, BN, NTW, KC, false, false, true>), dim3(blocks), dim3(nt), lds, stream, b);
             return;
@@ -1402,11 +1439,11 @@ static void launch_batch_cfg(const ConvBatch& b, int blocks, hipStream_t stream)
     else hipLaunchKernelGGL((conv_h2_batch_kernel<TH, BN, NTW, KC, false, false, false>), dim3(blocks), dim3(nt), lds, stream, b);
 }
 template <int TH, int BN, int NTW, int KC>
-static void launch_single_cfg(const ConvParams& p, int blocks, hipStream_t stream) {
+static void launch_single_cfg(const ConvParams& p, const H2Shape& sh, int blocks, hipStream_t stream) {
     constexpr int lds = H2Cfg<TH, BN, NTW, KC>::LDS_BYTES;
     constexpr int nt = H2Cfg<TH, BN, NTW, KC>::NT;
-    if constexpr (KC == 32 && NTW <= 2) {
-        if (h2_use_m16(p.mfma16, TH, NTW, p.pcode_in != nullptr)) {
+    if constexpr (h2_m16_built<NTW, KC>) {
+        if (sh.m16) {
             if (p.pcode_in) hipLaunchKernelGGL((conv_h2_kernel<TH, BN, NTW, KC, true, true>), dim3(blocks), dim3(nt), lds, stream, p);
             else hipLaunchKernelGGL((conv_h2_kernel<TH, BN, NTW, KC, false, true>), dim3(blocks), dim3(nt), lds, stream, p);
             return;
@@ -1424,58 +1461,58 @@ static bool h2_operands_ok(const void* wt, const unsigned* amax_in, int Cin, int
     return true;
 }
 
+// the kernel of a decided shape
+template <int TH, int BN, int NTW, int KC>
+struct H2Tag { static constexpr int th = TH, bn = BN, ntw = NTW, kc = KC; };
+template <typename Launch>
+static void h2_dispatch(const H2Shape& sh, Launch&& go) {
+    if (sh.bn == 64) go(H2Tag<16, 64, 2, 16>{});
+    else if (sh.chunk == 16) go(H2Tag<8, 128, 2, 16>{});
+    else if (sh.rows == 4) go(H2Tag<4, 128, 1, 32>{});
+    else if (sh.rows == 8) go(H2Tag<8, 128, 1, 32>{});
+    else if (sh.ntw == 4) go(H2Tag<16, 128, 4, 32>{});
+    else go(H2Tag<16, 128, 2, 32>{});
+}
+
 // fills tiles_x / tile_end of every image and launches one grid over all of them
-hipError_t launch_conv_h2_batch(const ConvBatch& b0, hipStream_t stream) {
+hipError_t launch_conv_h2_batch(const ConvBatch& b0, hipStream_t stream, H2Shape* shape) {
     if (b0.n < 1 || b0.n > 8) return hipErrorInvalidValue;
     ConvBatch b = b0;
-    const bool wide = (b.Cout % 128 == 0);
-    long blocks16 = 0;
+    int H[8], W[8];
+    bool second = false;
     for (int i = 0; i < b.n; ++i) {
         const ConvImage& im = b.img[i];
         if (!h2_operands_ok(b.wt_h2, im.amax_in, b.Cin, b.Cout, im.in2, im.wt2_f32, im.amax_in2, im.amax_w2, b.Cin2))
             return hipErrorInvalidValue;
         if ((size_t)im.H * im.W * (b.Cin > b.Cin2 ? b.Cin : b.Cin2) * 4 >= 0xFFFFFF00ull) return hipErrorInvalidValue;
         if ((b.unpool != 0) != (im.pcode_in != nullptr)) return hipErrorInvalidValue;
-        blocks16 += (long)((im.H + 15) / 16) * ((im.W + 15) / 16) * (b.Cout / 128);
+        H[i] = im.H; W[i] = im.W;
+        second = second || (im.in2 != nullptr);
     }
-    const bool shortk = wide && b.Cin > 0 && b.Cin <= NST_H2_SHORTK_CIN;      // 8-row tiles, two workgroups per CU
-    const int th = shortk ? 8 : h2_tile_rows(b.Cout, blocks16, b.tile_rows), bn = wide ? 128 : 64;
+    int blocks = 0;
+    const H2Shape sh = h2_launch_shape(H, W, b.n, b.Cin, b.Cout, b.unpool != 0, second, b.tile_rows, b.mfma16, b.wg256, b.persist, &blocks);
     int tiles = 0;
     for (int i = 0; i < b.n; ++i) {
         b.img[i].tiles_x = (b.img[i].W + 15) / 16;
-        tiles += b.img[i].tiles_x * ((b.img[i].H + th - 1) / th);
+        tiles += b.img[i].tiles_x * ((b.img[i].H + sh.rows - 1) / sh.rows);
         b.img[i].tile_end = tiles;
     }
-    int blocks = tiles * (b.Cout / bn);
-    // Persistent form (nst_options.h2_persist): as many workgroups as the chip holds at once (256 CUs x 1 or 2 by the
-    // shape's LDS / thread budget), each walking its share of the tiles with the K pipeline chained across them.  Not for
-    // launches with a second K source (its stages use the LDS buffers the chained prologue would be staged in).
-    bool second = false;
-    for (int i = 0; i < b.n; ++i) second = second || (b.img[i].in2 != nullptr);
-    const int resident = 256 * ((!wide || shortk || th == 4) ? 2 : 1);
     b.total_tiles = blocks;
-    const bool m16 = h2_use_m16(b.mfma16, th, 2, b.unpool != 0) && !shortk && wide;      // (the 16x16x32 form has no persistent build)
-    const bool pshape = !wide || shortk || (th == 16 && !b.wg256);
-    b.persist = (b.persist && !second && b.Cin > 0 && blocks > resident && pshape && !m16) ? 1 : 0;
-    if (b.persist) blocks = resident;
-    if (!wide) launch_batch_cfg<16, 64, 2, 16>(b, blocks, stream);
-    else if (shortk) launch_batch_cfg<8, 128, 2, 16>(b, blocks, stream);
-    else if (th == 4) launch_batch_cfg<4, 128, 1, 32>(b, blocks, stream);
-    else if (th == 8) launch_batch_cfg<8, 128, 1, 32>(b, blocks, stream);
-    else if (b.wg256) launch_batch_cfg<16, 128, 4, 32>(b, blocks, stream);
-    else launch_batch_cfg<16, 128, 2, 32>(b, blocks, stream);
+    b.persist = sh.persist;
+    if (sh.persist) blocks = h2_resident(sh);
+    if (shape) *shape = sh;
+    h2_dispatch(sh, [&](auto cfg) { launch_batch_cfg<decltype(cfg)::th, decltype(cfg)::bn, decltype(cfg)::ntw, decltype(cfg)::kc>(b, sh, blocks, stream); });
     return hipGetLastError();
 }
 
-hipError_t launch_conv_h2(const ConvParams& p0, hipStream_t stream) {
+hipError_t launch_conv_h2(const ConvParams& p0, hipStream_t stream, H2Shape* shape) {
     if (!h2_operands_ok(p0.wt_h2, p0.amax_in, p0.Cin, p0.Cout, p0.in2, p0.wt2_f32, p0.amax_in2, p0.amax_w2, p0.Cin2))
         return hipErrorInvalidValue;
     ConvParams p = p0;
     p.ksplit = 1;
-    const bool wide = (p.Cout % 128 == 0);
-    const long blocks16 = (long)((p.H + 15) / 16) * ((p.W + 15) / 16) * (p.Cout / 128);
-    const bool shortk = wide && p.Cin > 0 && p.Cin <= NST_H2_SHORTK_CIN;
-    const int th = shortk ? 8 : h2_tile_rows(p.Cout, blocks16, p.tile_rows), bn = wide ? 128 : 64;
+    int all_blocks = 0;
+    H2Shape sh = h2_launch_shape(&p.H, &p.W, 1, p.Cin, p.Cout, p.pcode_in != nullptr, p.in2 != nullptr, p.tile_rows, p.mfma16, p.wg256, 0, &all_blocks);
+    const int th = sh.rows;
     p.tiles_x = (p.W + 15) / 16;
     // The kernels address with 32-bit buffer offsets.  A launch whose tensors reach 4 GiB runs in bands of output rows
     // (multiples of 16, so tiles and pooling windows stay aligned): every tensor pointer is moved to the band's first
@@ -1493,6 +1530,7 @@ hipError_t launch_conv_h2(const ConvParams& p0, hipStream_t stream) {
     const int forced_band = p.band_rows;
     if (forced_band >= 16 && forced_band / 16 * 16 < band_rows) band_rows = forced_band / 16 * 16;
     const int PW2 = p.W >> 1, wi = p.Cin >> 5, wo = p.Cout >> 5;
+    int bands = 0;
     for (int r0 = 0; r0 < p.H; r0 += band_rows) {
         const int r1 = (r0 + band_rows < p.H) ? r0 + band_rows : p.H;
         const int b0 = (r0 >= 16) ? r0 - 16 : 0, b1 = (r1 + 16 < p.H) ? r1 + 16 : p.H;
@@ -1511,16 +1549,14 @@ hipError_t launch_conv_h2(const ConvParams& p0, hipStream_t stream) {
         q.H = b1 - b0;
         q.ty0 = (r0 - b0) / th;
         q.tiles_y = (r1 - r0 + th - 1) / th;
-        const int blocks = q.tiles_x * q.tiles_y * (p.Cout / bn);
-        if (!wide) launch_single_cfg<16, 64, 2, 16>(q, blocks, stream);
-        else if (shortk) launch_single_cfg<8, 128, 2, 16>(q, blocks, stream);
-        else if (th == 4) launch_single_cfg<4, 128, 1, 32>(q, blocks, stream);
-        else if (th == 8) launch_single_cfg<8, 128, 1, 32>(q, blocks, stream);
-        else if (q.wg256) launch_single_cfg<16, 128, 4, 32>(q, blocks, stream);
-        else launch_single_cfg<16, 128, 2, 32>(q, blocks, stream);
+        const int blocks = q.tiles_x * q.tiles_y * (p.Cout / sh.bn);
+        h2_dispatch(sh, [&](auto cfg) { launch_single_cfg<decltype(cfg)::th, decltype(cfg)::bn, decltype(cfg)::ntw, decltype(cfg)::kc>(q, sh, blocks, stream); });
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
+        ++bands;
     }
+    sh.bands = bands;
+    if (shape) *shape = sh;
     return hipSuccess;
 }
 

@@ -1,7 +1,7 @@
 // conv_wino.hip - the 3x3 convolution (forward: bias + ReLU + ReLU bit mask + 2x2 max-pool with its arg-max code; input
 // gradient: loss-gradient addend + ReLU mask of the map below, un-pooling loader) as a 1-D Winograd F(2,3) along x on the
 // fp16 matrix pipe, in the f16x2 arithmetic of conv_h2.hip: 1.5x fewer MFMAs per output.  Default (nst_options.h2_winograd)
-// for the launches with Cin >= 256, Cout a multiple of 128 and no second (Gram) source: 14 of the 24 conv launches of a closure.
+// for the launches with Cin >= 256, Cout a multiple of 128 and no second (Gram) source: 15 of the 24 conv launches of a closure.
 //
 // For an output pair (x = 2p, 2p + 1) of a row and the input columns d0..d3 = x - 1 .. x + 2 (one tap row ky):
 //     t0 = d0 - d2, t1 = d1 + d2, t2 = d2 - d1, t3 = d1 - d3                    (input transform, fp32, before the cut)

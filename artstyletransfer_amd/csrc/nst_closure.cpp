@@ -21,9 +21,17 @@ bool uses_pieces(const nst_ctx* ctx, const ConvParams& p) {
     if (ctx->conv_mode == 2) return true;           // launch_conv_h2 runs larger tensors in row bands
     return ctx->conv_mode != 0 && (size_t)p.H * p.W * p.Cin * 4 < 0xFFFFFF00ull;
 }
-// 3x3 conv dispatch by mode; whatever kernel runs, the absmax record of the output is produced when asked for
-hipError_t launch_conv3(nst_ctx* ctx, const ConvParams& p, hipStream_t s) {
-    if (uses_pieces(ctx, p)) return ctx->conv_mode == 2 ? launch_conv_h2(p, s) : launch_conv_bf3(p, s);
+// 3x3 conv dispatch by mode, under the caller's timer (which keeps the shape a conv_h2 launch took); whatever kernel runs,
+// the absmax record of the output is produced when asked for
+hipError_t launch_conv3(nst_ctx* ctx, const ConvParams& p, Timer& t) {
+    hipStream_t s = t.s;
+    if (uses_pieces(ctx, p)) {
+        if (ctx->conv_mode != 2) return launch_conv_bf3(p, s);
+        H2Shape sh{};
+        const hipError_t e = launch_conv_h2(p, s, &sh);
+        t.shape(sh);
+        return e;
+    }
     hipError_t e = launch_conv_mfma(p, 9, s);
     if (e == hipSuccess && ctx->conv_mode == 2 && p.amax_out)
         e = launch_absmax_slots(p.out, (size_t)p.H * p.W * p.Cout, p.amax_out, s);
@@ -59,7 +67,12 @@ void conv_setup(const nst_ctx* ctx, ConvBatch& b, int l, bool dgrad) {
 int launch_conv_batch(nst_ctx* ctx, const ConvBatch& b, Timer& t, bool allow_wino) {
     const bool h2 = ctx->conv_mode == 2;
     if (h2 && allow_wino && b.wt_wino && conv_wino_eligible(b)) { t.mfma_factor(2.0); HIPCHK(ctx, launch_conv_wino_batch(b, t.s)); }
-    else HIPCHK(ctx, h2 ? launch_conv_h2_batch(b, t.s) : launch_conv_bf3_batch(b, t.s));
+    else if (h2) {
+        H2Shape sh{};
+        const hipError_t e = launch_conv_h2_batch(b, t.s, &sh);
+        t.shape(sh);
+        HIPCHK(ctx, e);
+    } else HIPCHK(ctx, launch_conv_bf3_batch(b, t.s));
     return NST_OK;
 }
 
@@ -132,7 +145,7 @@ int forward(nst_ctx* ctx, ActSet& a, const float* x, int h, int w, hipStream_t s
         }
         {
             Timer t(ctx, s, K_CONV3, conv_flops(p.H, p.W, p.Cin, p.Cout, 9), p.H, p.W, p.Cin, p.Cout, 9, l);
-            HIPCHK(ctx, launch_conv3(ctx, p, s));
+            HIPCHK(ctx, launch_conv3(ctx, p, t));
         }
         a.bits_valid[l] = fuse && a.bits[l] != nullptr;
         if (pa >= 0 && l < last_layer) {
@@ -200,7 +213,7 @@ int backward(nst_ctx* ctx, ActSet& a, const Inject* inj, const ContentJob* cj, f
             if (avg) p.amax_out = nullptr;
             {
                 Timer t(ctx, s, K_CONV3, conv_flops(p.H, p.W, p.Cin, p.Cout, 9), p.H, p.W, p.Cin, p.Cout, 9, -l);
-                HIPCHK(ctx, launch_conv3(ctx, p, s));
+                HIPCHK(ctx, launch_conv3(ctx, p, t));
             }
             // oth = g(pool[pk]); un-pool through act[l-1] with its ReLU mask -> cur
             Timer t(ctx, s, K_OTHER, 0);
@@ -239,7 +252,7 @@ int backward(nst_ctx* ctx, ActSet& a, const Inject* inj, const ContentJob* cj, f
             else p.mask = a.act[m];
             {
                 Timer t(ctx, s, K_CONV3, conv_flops(p.H, p.W, p.Cin, p.Cout, 9) + extra_flops, p.H, p.W, p.Cin, p.Cout, 9, -l);
-                HIPCHK(ctx, launch_conv3(ctx, p, s));
+                HIPCHK(ctx, launch_conv3(ctx, p, t));
             }
             float* tmp = cur; cur = oth; oth = tmp;
         }

@@ -741,6 +741,20 @@ int nst_last_closure_class(nst_ctx* ctx, int cls, float* ms, int* launches, doub
     return NST_OK;
 }
 
+// the timed launches of the last closure in launch order, with the kernel shape the conv_h2 launcher decided for each
+int nst_last_closure_launches(nst_ctx* ctx, nst_launch_info* out, int capacity, int* count) {
+    NSTCHK(bind(ctx));
+    if (!count || capacity < 0 || (capacity > 0 && !out)) return fail(ctx, NST_E_ARG, "bad argument");
+    *count = ctx->timed_valid ? (int)ctx->timed.size() : 0;
+    for (int i = 0; i < *count && i < capacity; ++i) {
+        const TimedLaunch& t = ctx->timed[i];
+        const H2Shape& sh = t.shape;
+        out[i] = nst_launch_info{t.cls, t.tag[0], t.tag[1], t.tag[2], t.tag[3], t.tag[5], sh.rows, sh.bn, sh.ntw, sh.chunk,
+                                 sh.m16, sh.persist, sh.second, sh.unpool, sh.bands};
+    }
+    return NST_OK;
+}
+
 // debugging aid: one line per timed launch of the last closure to stderr
 int nst_dump_last_closure(nst_ctx* ctx) {
     NSTCHK(bind(ctx));
@@ -750,8 +764,12 @@ int nst_dump_last_closure(nst_ctx* ctx) {
         float d = 0.f;
         HIPCHK(ctx, hipEventSynchronize(t.b));
         HIPCHK(ctx, hipEventElapsedTime(&d, t.a, t.b));
-        fprintf(stderr, "cls %d  %4dx%-4d cin %3d cout %3d taps %d layer %3d  %8.3f ms  %7.2f TFLOP/s\n", t.cls, t.tag[0],
-                t.tag[1], t.tag[2], t.tag[3], t.tag[4], t.tag[5], d, d > 0 ? t.flops / (d * 1e-3) / 1e12 : 0.0);
+        char shape[64] = "";
+        if (t.shape.rows > 0)
+            snprintf(shape, sizeof(shape), "  h2<%d,%d,%d,%d>%s%s x%d", t.shape.rows, t.shape.bn, t.shape.ntw, t.shape.chunk,
+                     t.shape.m16 ? " m16" : "", t.shape.persist ? " persist" : "", t.shape.bands);
+        fprintf(stderr, "cls %d  %4dx%-4d cin %3d cout %3d taps %d layer %3d  %8.3f ms  %7.2f TFLOP/s%s\n", t.cls, t.tag[0],
+                t.tag[1], t.tag[2], t.tag[3], t.tag[4], t.tag[5], d, d > 0 ? t.flops / (d * 1e-3) / 1e12 : 0.0, shape);
     }
     return NST_OK;
 }

@@ -79,7 +79,9 @@ struct Taps {
 
 enum KClass { K_CONV3 = 0, K_GRAM = 1, K_CONV1 = 2, K_OTHER = 3, K_NCLASS = 4 };
 
-struct TimedLaunch { hipEvent_t a, b; int cls; double flops; int tag[6]; double mfma_factor; };      // mfma_factor: executed matrix-pipe FLOPs per algorithmic FLOP (< 0: the arithmetic mode's)
+// mfma_factor: executed matrix-pipe FLOPs per algorithmic FLOP (< 0: the arithmetic mode's); shape: what the conv_h2 launcher
+// decided for this launch (rows = 0: another kernel ran)
+struct TimedLaunch { hipEvent_t a, b; int cls; double flops; int tag[6]; double mfma_factor; H2Shape shape; };
 
 struct LevelWs {
     int h = 0, w = 0;
@@ -220,7 +222,7 @@ struct Timer {
         : ctx(c), s(st), on(false), slot(0) {
         if (c->timing >= 2 && (c->timing < 3 || cls == K_CONV3) && c->sample_now && c->ev_used + 2 <= c->ev_pool.size()) {
             on = true;
-            TimedLaunch t{c->ev_pool[c->ev_used], c->ev_pool[c->ev_used + 1], cls, flops, {t0, t1, t2, t3, t4, t5}, -1.0};
+            TimedLaunch t{c->ev_pool[c->ev_used], c->ev_pool[c->ev_used + 1], cls, flops, {t0, t1, t2, t3, t4, t5}, -1.0, H2Shape{}};
             c->ev_used += 2;
             slot = c->timed.size();
             c->timed.push_back(t);
@@ -230,6 +232,7 @@ struct Timer {
     ~Timer() { if (on) (void)hipEventRecord(ctx->timed[slot].b, s); }
     // a launch whose matrix-pipe work per algorithmic FLOP differs from its arithmetic mode's (the Winograd form: 2/3 of it)
     void mfma_factor(double f) { if (on) ctx->timed[slot].mfma_factor = f; }
+    void shape(const H2Shape& sh) { if (on) ctx->timed[slot].shape = sh; }
 };
 // folds the event pairs of the previous closure into the accumulators (waits for them to complete)
 int fold_timed(nst_ctx* ctx);

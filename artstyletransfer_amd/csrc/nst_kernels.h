@@ -124,8 +124,19 @@ int conv_bf3_ksplit(int H, int W, int Cin, int Cout);
 
 // conv_h2.hip: the same on the fp16 matrix pipe with 2-piece scaled operands (3 MFMAs per product block)
 hipError_t conv_h2_init_device();
-hipError_t launch_conv_h2(const ConvParams& p, hipStream_t stream);
-hipError_t launch_conv_h2_batch(const ConvBatch& b, hipStream_t stream);
+// The kernel shape a conv_h2 launch ran as - conv_h2_kernel<rows, bn, ntw, chunk> (conv_h2.hip lists the shapes) - and the
+// properties of the launch that entered the choice.  Decided in ONE place (h2_launch_shape) for both launchers, which hand it
+// back through `shape` (nullable): what the timing record of a launch keeps (nst_last_closure_launches).  rows = 0: not a
+// conv_h2 launch.
+struct H2Shape {
+    int rows, bn, ntw, chunk;   // pixel rows of the workgroup tile (x 16 columns), output channels per tile, 32-channel tiles per wave, channels per K chunk
+    int m16;                    // the 16x16x32 MFMA form
+    int persist;                // persistent workgroups (batched launches only)
+    int second, unpool;         // the launch has a second K source / un-pools its input in the loader
+    int bands;                  // kernel launches it took (per-level launcher: row bands; else 1)
+};
+hipError_t launch_conv_h2(const ConvParams& p, hipStream_t stream, H2Shape* shape = nullptr);
+hipError_t launch_conv_h2_batch(const ConvBatch& b, hipStream_t stream, H2Shape* shape = nullptr);
 // absmax of n floats into NST_AMAX_SLOTS slots (atomic max; zero them beforehand)
 hipError_t launch_absmax_slots(const float* x, size_t n, unsigned* slots, hipStream_t stream);
 

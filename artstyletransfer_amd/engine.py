@@ -313,6 +313,15 @@ class StyleEngine:
                    "nst_last_closure_class")
         return ms.value, n.value, fl.value
 
+    def last_closure_launches(self) -> List[dict]:
+        """The timed launches of the last closure (set_timing(2)) in launch order, one dict per launch with the fields of
+        nst_launch_info: h2_rows ... h2_bands are the kernel shape the conv_h2 launcher reported (h2_rows = 0: another kernel)."""
+        n = C.c_int()
+        _lib.check(self.ctx, self.lib.nst_last_closure_launches(self.ctx, None, 0, C.byref(n)), "nst_last_closure_launches")
+        buf = (_lib.LaunchInfo * max(n.value, 1))()
+        _lib.check(self.ctx, self.lib.nst_last_closure_launches(self.ctx, buf, n.value, C.byref(n)), "nst_last_closure_launches")
+        return [{name: getattr(buf[i], name) for name, _ in _lib.LaunchInfo._fields_} for i in range(n.value)]
+
     def timing_totals(self, cls: int, reset: bool = False):
         """(ms, launches, flops) accumulated since the last reset; cls -1 = whole closures."""
         ms, n, fl = C.c_double(), C.c_long(), C.c_double()

@@ -85,8 +85,12 @@ typedef struct nst_options {
     int h2_wg256;         /* f16x2 convolutions, the 16x16-pixel x 128-channel tile: 1 = 256-thread workgroups, one wave per SIMD
                              with a 64 x 128 wave tile (accumulators in AGPRs), 0 = 512 threads with 64 x 64 wave tiles;
                              -1: env NST_H2_WG256, default 0 */
-    int h2_tile_rows;     /* f16x2 convolutions with 128-channel tiles and 32-channel chunks: 4 / 8 / 16 = pixel rows per workgroup tile,
-                             0 = chosen per launch from the number of workgroups; -1: env NST_H2_TILE_ROWS, default 0 */
+    int h2_tile_rows;     /* f16x2 direct convolutions (conv_h2.hip) with 128-channel tiles and 32-channel chunks - Cout a multiple
+                             of 128 and Cin > 128, or the Gram source alone; batched and per-level launches alike: 4 / 8 / 16 =
+                             pixel rows per workgroup tile, 0 = chosen per launch from the number of workgroups.  The short-K
+                             launches (Cin <= 128), the 64-channel layers and the Winograd launches keep their own shape: with
+                             h2_winograd = 1 the option reaches the launches that carry a Gram source only.
+                             -1: env NST_H2_TILE_ROWS, default 0 */
     int gram_overlap;     /* f16x2 closure: 1 = the Gram matrices of relu1_1 ... relu3_1 (HBM-bound) run on a side stream of the
                              context under the MFMA-bound convolutions of conv3_2 ... conv5_1, joined before the backward pass;
                              0 = everything in order on the caller's stream; -1: env NST_GRAM_OVERLAP, default 0 (measured: no gain) */
@@ -98,7 +102,7 @@ typedef struct nst_options {
                              chain on a side stream of the context, joined before the gradients are merged; 0 = one launch per
                              layer over all levels; -1: env NST_LEVEL_SPLIT, default 0 */
     int h2_winograd;      /* f16x2 batched closure: 1 = the forward and input-gradient launches with Cin >= 256 and Cout a
-                             multiple of 128 that have no second (Gram) source - 14 of the 24 of a closure - run as a 1-D Winograd
+                             multiple of 128 that have no second (Gram) source - 15 of the 24 of a closure - run as a 1-D Winograd
                              F(2,3) along x (conv_wino.hip: 1.5x fewer MFMAs there; the feature maps are no further from an fp64
                              evaluation than the direct path's); 0 = direct convolution everywhere;
                              -1: env NST_H2_WINOGRAD, default 1 */
@@ -424,6 +428,23 @@ int nst_timing_totals(nst_ctx* ctx, int cls, double* ms, long* launches, double*
 /* executed matrix-pipe FLOPs of the launches accumulated in nst_timing_totals(cls): algorithmic FLOPs x the MFMAs the
  * arithmetic spends per product (f16x2: 3, bf16x3: 6, f32: 1), x 2/3 for the launches that ran as Winograd F(2,3). */
 int nst_timing_mfma_flops(nst_ctx* ctx, int cls, double* mfma_flops);
+/* The timed launches of the last closure (timing mode 2), in launch order: up to `capacity` records into `out`, their
+ * number into `count` (which may exceed capacity; 0 without a timed closure).  Read-only; waits for nothing.  h2_*: the kernel
+ * shape the f16x2 direct-convolution launcher (conv_h2.hip) decided for the launch - conv_h2_kernel<h2_rows, h2_bn, h2_ntw,
+ * h2_chunk> - as the launcher itself reported it; h2_rows = 0: another kernel ran (Winograd, conv1_1, Gram, streaming, or
+ * another arithmetic mode). */
+typedef struct nst_launch_info {
+    int cls;                      /* kernel class, as in nst_last_closure_class */
+    int h, w, cin, cout;          /* 3x3 convolutions (cls 0): the launch's (first level's) map and channel counts; else 0 */
+    int layer;                    /* 3x3 convolutions: conv layer 1..12 of a forward launch, minus that of an input-gradient launch */
+    int h2_rows, h2_bn, h2_ntw, h2_chunk;   /* pixel rows (x 16 columns) and output channels of the workgroup tile, 32-channel
+                                     tiles per wave, channels per K chunk */
+    int h2_mfma16;                /* 1: the launch ran the 16x16x32 MFMA form */
+    int h2_persist;               /* 1: persistent workgroups */
+    int h2_second, h2_unpool;     /* 1: the launch carried a second (Gram) K source / un-pooled its input in the loader */
+    int h2_bands;                 /* kernel launches it took (row bands of the per-level launcher; else 1) */
+} nst_launch_info;
+int nst_last_closure_launches(nst_ctx* ctx, nst_launch_info* out, int capacity, int* count);
 /* debugging aid: prints one line per timed launch of the last closure (timing mode 2) to stderr */
 int nst_dump_last_closure(nst_ctx* ctx);
 

@@ -335,7 +335,8 @@ def test_persistent_launches_are_bitwise_the_one_tile_launches(vgg_weights, h, w
 
 
 @pytest.mark.parametrize("opts", [dict(h2_mfma16=0), dict(h2_mfma16=2), dict(h2_mfma16=3), dict(h2_wg256=True), dict(h2_tile_rows=8),
-                                  dict(gram_overlap=True), dict(level_split=True), dict(h2_persist=True, h2_mfma16=0), dict(h2_winograd=True)])
+                                  dict(gram_overlap=True), dict(level_split=True), dict(h2_persist=True, h2_mfma16=0), dict(h2_winograd=True),
+                                  dict(h2_tile_rows=4), dict(h2_tile_rows=16, h2_winograd=False)])
 def test_experiment_switches_agree_with_the_default(vgg_weights, opts):
     """The measured experiments of DESIGN 4.1 that stay behind nst_options (MFMA shape per tile shape, the one-wave-per-SIMD
     workgroup, forced tile heights, the Gram side stream, persistent launches): same products and the same loss terms in
