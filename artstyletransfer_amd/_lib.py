@@ -14,11 +14,13 @@ LIB_PATH = os.environ.get("NST_LIB") or os.path.join(_HERE, "libnst_hip.so")   #
 CSRC = os.path.join(_HERE, "csrc")
 
 NST_OK = 0
+NST_E_ARG = -1
 NST_E_STATE = -2
 NST_E_UNAVAILABLE = -5
 NST_VGG19_CONVS = 13
 NST_MAX_LEVELS = 8
 NST_LOSS_ROW = 4
+NST_MAX_STYLES = 8
 NST_OPT_ADAM = 0
 NST_OPT_LBFGS = 1
 NST_COLOR_RGB = 0
@@ -69,12 +71,16 @@ SYMBOLS = {
     "nst_job_color": (C.c_int, [c_void]),
     "nst_job_set_pooling": (C.c_int, [c_void, C.c_int]),
     "nst_job_pooling": (C.c_int, [c_void]),
+    "nst_job_set_style_weights": (C.c_int, [c_void, c_float_p]),
+    "nst_job_style_weights": (C.c_int, [c_void, c_float_p]),
     "nst_color_stats": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), c_void]),
     "nst_color_transfer_matrix": (C.c_int, [C.POINTER(C.c_double)] * 6),
     "nst_color_affine": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), c_void, c_void]),
     "nst_luminance": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_double, C.c_double, c_void, c_void]),
     "nst_luminance_recombine": (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, c_void, c_void]),
     "nst_level_set_targets": (C.c_int, [c_void, C.c_int, c_void, c_void, C.c_int, C.c_int, c_void]),
+    "nst_level_set_targets_blend": (C.c_int, [c_void, C.c_int, c_void, C.c_int, C.POINTER(c_void), C.POINTER(C.c_int),
+                                              C.POINTER(C.c_int), c_float_p, c_void]),
     "nst_closure": (C.c_int, [c_void, c_void, C.c_float, C.c_float, C.c_float, c_void, c_void, c_void]),
     "nst_closure_levels": (C.c_int, [c_void, c_void, C.c_float, C.c_float, C.c_float, C.c_uint, c_void, c_void, c_void]),
     "nst_closure_forward": (C.c_int, [c_void, c_void, C.c_float, C.c_float, C.c_float, C.c_uint, c_void, c_void]),

@@ -1,6 +1,7 @@
 """Configuration surface of the reference (config.py:1-31): same names, same defaults."""
 from .color_modes import check_preserve_color
 from .pooling_modes import check_pooling
+from .style_modes import check_style_blend, check_style_layer_weights
 
 # jobs that may run at once PER GPU (the reference runs everything on device 0; here the
 # scheduler multiplies this by the number of GPUs of the node). Use 1 when levels_num > 2.
@@ -23,7 +24,8 @@ _DEFAULTS = dict(
 )
 # extension, keyword-only: the feature maps the losses read (neural_style_transfer(..., content_layer=, style_layers=,
 # use_relu=)); None = the reference's content 4 / style [0, 1, 2, 3, 5]; colour preservation (preserve_color=); and the
-# pooling of the feature network (pooling=).
+# pooling of the feature network (pooling=); further style images with their blend (extra_styles=, style_blend=) and the
+# per-layer style weights (style_layer_weights=).
 # Not part of the positional order or the repr.
 _KW_ONLY = dict(
     content_layer=None,            # index 0..5 or a name of Vgg19.layer_names
@@ -31,6 +33,9 @@ _KW_ONLY = dict(
     use_relu=True,                 # False: the reference's Vgg19(use_relu=False) taps
     preserve_color=None,           # None | 'luminance' | 'histogram': keep the content's colours (Gatys et al. 2016)
     pooling="max",                 # 'max' | 'avg': average instead of max pooling in VGG19 (Gatys et al. 2016, section 2)
+    extra_styles=None,             # further style images (HWC float [0,1]) blended with the pair's style image
+    style_blend=None,              # K numbers or a K x 6 array: weight of style k (on map i); K = 1 + len(extra_styles)
+    style_layer_weights=None,      # 6 numbers or {map index or name: weight}: the w_l of Gatys et al. 2016
 )
 
 
@@ -53,6 +58,10 @@ class Config:
             setattr(self, name, kwargs.get(name, default))
         check_preserve_color(self.preserve_color)
         check_pooling(self.pooling)
+        # (against every map: the style set of the job is checked again where the taps are known)
+        check_style_layer_weights(self.style_layer_weights, style_indices=range(6))
+        if self.extra_styles is not None or self.style_blend is not None:
+            check_style_blend(self.style_blend, 1 + len(self.extra_styles or ()), style_indices=())
 
     def __repr__(self):
         return "Config(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in _DEFAULTS) + ")"

@@ -455,12 +455,15 @@ hipError_t launch_gram_partial(const float* f, size_t N, int C, int nsplit, cons
 // add every 8th slab, then the 8 group sums are added in group order - a fixed order, so the result is reproducible.
 // (Blocks of 32 elements - 57 000 of them for an L=2 closure, each a handful of 128-byte reads, a barrier and a serial tail -
 // made this pass launch- and latency-bound: 0.129 ms for 273 MB.)
+// BLEND (the targets of a level): gram_out = alpha * G, or gram_out + alpha * G when `accumulate` - same slab order, product
+// and sum each rounded (no contraction), so a blended target is the fp32 sum of its rounded terms in call order.
 constexpr int GF_EPB = NST_GRAM_FINISH_EPB;      // elements per block
+template <bool BLEND = false>
 __device__ __forceinline__ void gram_finish_body(const float* __restrict__ part, int nslabs, int C, int ts, float divisor,
                                                  const float* __restrict__ target, float coef, float* __restrict__ gram_out,
                                                  float* __restrict__ S, unsigned short* __restrict__ S_bf,
                                                  unsigned* __restrict__ S_amax, double* __restrict__ mse_partial,
-                                                 const unsigned bid) {
+                                                 const unsigned bid, float alpha = 1.f, int accumulate = 0) {
     __shared__ f32x4 sh[8][32];
     __shared__ double shd[32];
     const size_t CC = (size_t)C * C;
@@ -521,7 +524,12 @@ __device__ __forceinline__ void gram_finish_body(const float* __restrict__ part,
             const bool both = tri && j > i;
             const size_t em = (size_t)j * C + i;      // the mirrored element
             const float g = t[q] / divisor;      // torch: gram /= ch*h*w
-            if (gram_out) { gram_out[e] = g; if (both) gram_out[em] = g; }
+            if constexpr (BLEND) {
+                // (element (i,j), j >= i, is read and written by this lane alone; its mirror is only ever written)
+                float v = __fmul_rn(alpha, g);
+                if (accumulate) v = __fadd_rn(gram_out[e], v);
+                gram_out[e] = v; if (both) gram_out[em] = v;
+            } else if (gram_out) { gram_out[e] = g; if (both) gram_out[em] = g; }
             if (target) {
                 const float d = g - target[e];
                 sq += (double)d * (double)d * (both ? 2.0 : 1.0);
@@ -570,6 +578,12 @@ __global__ __launch_bounds__(256) void gram_finish_kernel(const float* __restric
                                                           unsigned* __restrict__ S_amax,
                                                           double* __restrict__ mse_partial) {
     gram_finish_body(part, nslabs, C, ts, divisor, target, coef, gram_out, S, S_bf, S_amax, mse_partial, blockIdx.x);
+}
+__global__ __launch_bounds__(256) void gram_finish_blend_kernel(const float* __restrict__ part, int nslabs, int C, int ts,
+                                                                float divisor, float alpha, int accumulate,
+                                                                float* gram_out) {
+    gram_finish_body<true>(part, nslabs, C, ts, divisor, nullptr, 0.f, gram_out, nullptr, nullptr, nullptr, nullptr, blockIdx.x,
+                           alpha, accumulate);
 }
 __global__ __launch_bounds__(256) void gram_finish_batch_kernel(GramBatch b) {
     int i = 0;
@@ -648,6 +662,14 @@ hipError_t launch_gram_finish(const float* part, int nslabs, int C, float diviso
                               hipStream_t stream) {
     hipLaunchKernelGGL(gram_finish_kernel, dim3(gram_finish_blocks(C)), dim3(256), 0, stream, part, nslabs, C,
                        gram_ts(C), divisor, target, coef, gram_out, S, (C % 32 == 0) ? S_bf : nullptr, S_amax, mse_partial);
+    return hipGetLastError();
+}
+
+hipError_t launch_gram_finish_blend(const float* part, int nslabs, int C, float divisor, float alpha, int accumulate,
+                                    float* gram_out, hipStream_t stream) {
+    if (!gram_out) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gram_finish_blend_kernel, dim3(gram_finish_blocks(C)), dim3(256), 0, stream, part, nslabs, C,
+                       gram_ts(C), divisor, alpha, accumulate, gram_out);
     return hipGetLastError();
 }
 

@@ -6,6 +6,7 @@
 //
 // Host-side control only; every FLOP and byte of the path is in the .hip kernels.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 #include "nst_ctx.h"
@@ -84,15 +85,16 @@ hipError_t launch_pool_bwd_relu(const nst_ctx* ctx, const float* a, const float*
     return (ctx->pool_avg ? launch_avgpool_bwd_relu : launch_maxpool_bwd_relu)(a, gpool, H, W, C, gin, s);
 }
 
-// The style term of slot q on a map of N = rows x w pixels and C channels: style = mean_q mse(G_q, Gt_q), G = F^T F / divisor,
-// so dL/dG = sw/nstyle * 2 (G - Gt)/C^2 and dF = 2 * dL/dG * F / (C h w) = F * S with S = coef * (G - Gt).
+// The style term of slot q on a map of N = rows x w pixels and C channels: style = (sum_q w_q mse(G_q, Gt_q)) / nstyle,
+// G = F^T F / divisor, so dL/dG = sw w_q/nstyle * 2 (G - Gt)/C^2 and dF = 2 * dL/dG * F / (C h w) = F * S with
+// S = coef * (G - Gt).  w: the layer weight of the slot's map (nst_job_set_style_weights; 1 multiplies exactly).
 // norm_rows > 0 (stripe closure): the normalisers of the full image, norm_rows level-0 rows, instead of the ActSet's own.
 struct StyleTerm { int C; size_t N; double divisor; float coef; };
-StyleTerm style_term(const Taps& tp, int q, const ActSet& a, float sw, int norm_rows = 0) {
+StyleTerm style_term(const Taps& tp, int q, const ActSet& a, float sw, float w, int norm_rows = 0) {
     const int l = tp.style[q], C = kCout[l];
     const size_t N = (size_t)(norm_rows > 0 ? norm_rows >> kScale[l] : a.h[l]) * a.w[l];
     const double chw = (double)C * (double)N;
-    return {C, N, chw, (float)((double)sw * 4.0 / ((double)tp.nstyle * (double)C * C * chw))};
+    return {C, N, chw, (float)((double)sw * (double)w * 4.0 / ((double)tp.nstyle * (double)C * C * chw))};
 }
 // content = cw * mse(F, Ft) over n elements: dF = coef * (F - Ft)
 float content_coef(float cw, double n) { return (float)((double)cw * 2.0 / n); }
@@ -377,7 +379,7 @@ int batched_gram(nst_ctx* ctx, const int* lv, int n, float sw, hipStream_t s, un
                 for (int q = 0; q < ctx->taps.nstyle; ++q) {
                     if (!((qmask >> q) & 1u)) continue;
                     const int l = ctx->taps.style[q];
-                    const StyleTerm st = style_term(ctx->taps, q, L.acts, sw);
+                    const StyleTerm st = style_term(ctx->taps, q, L.acts, sw, ctx->style_weight(q));
                     GramItem& it = gb.it[gb.n++];
                     it.f = L.acts.act[l]; it.N = st.N; it.C = st.C; it.amax = amax_act(L.acts, l);
                     it.part = L.gram_part + gram_part_offset(ctx->taps, L.h, L.w, q);
@@ -396,7 +398,7 @@ int batched_gram(nst_ctx* ctx, const int* lv, int n, float sw, hipStream_t s, un
     for (int k = 0; k < n && !h2; ++k) {
         LevelWs& L = ctx->lv[lv[k]];
         for (int q = 0; q < ctx->taps.nstyle; ++q) {
-            const StyleTerm st = style_term(ctx->taps, q, L.acts, sw);
+            const StyleTerm st = style_term(ctx->taps, q, L.acts, sw, ctx->style_weight(q));
             NSTCHK(gram_of(ctx, L.acts.act[ctx->taps.style[q]], st.N, st.C, nullptr, (float)st.divisor, L.gram_part, L.gram_t[q], st.coef, nullptr, L.S[q],
                            L.S_bf[q], nullptr, L.style_partial[q], s));
         }
@@ -617,7 +619,7 @@ int closure_per_level(nst_ctx* ctx, const float* const* xi, float* const* gi, in
     Inject inj[NL];
     for (int k = 0; k < tp.nstyle; ++k) {
         const int l = tp.style[k];
-        const StyleTerm st = style_term(tp, k, L.acts, sw);
+        const StyleTerm st = style_term(tp, k, L.acts, sw, ctx->style_weight(k));
         NSTCHK(gram_of(ctx, L.acts.act[l], st.N, st.C, h2 ? amax_act(L.acts, l) : nullptr, (float)st.divisor, L.gram_part, L.gram_t[k], st.coef, nullptr, L.S[k],
                        L.S_bf[k], h2 ? amax_S(L.acts, k) : nullptr, L.style_partial[k], s));
         inj[l].S = L.S[k];
@@ -640,7 +642,7 @@ LossAssembly fill_loss_assembly(const nst_ctx* ctx, unsigned level_mask, float c
         const LevelWs& L = ctx->lv[i];
         la.lv[i].content_partial = L.content_partial;
         la.lv[i].content_n = L.content_n;
-        for (int k = 0; k < ctx->taps.nstyle; ++k) { la.lv[i].style_partial[k] = L.style_partial[k]; la.lv[i].style_c[k] = kCout[ctx->taps.style[k]]; }
+        for (int k = 0; k < ctx->taps.nstyle; ++k) { la.lv[i].style_partial[k] = L.style_partial[k]; la.lv[i].style_c[k] = kCout[ctx->taps.style[k]]; la.lv[i].style_w[k] = ctx->style_weight(k); }
         la.lv[i].tv_means = L.tv_means;
         la.lv[i].owned = (int)((level_mask >> i) & 1u);
     }
@@ -729,6 +731,8 @@ int window_check(nst_ctx* ctx, const float* xs, int row0, int rows, int H0) {
         return fail(ctx, NST_E_STATE, "the stripe closure implements RGB only (nst_job_set_color(ctx, NST_COLOR_RGB))");
     if (ctx->pool_avg)
         return fail(ctx, NST_E_STATE, "the stripe closure implements max pooling only (nst_job_set_pooling(ctx, NST_POOL_MAX))");
+    if (!ctx->unit_style_weights())
+        return fail(ctx, NST_E_STATE, "the stripe closure implements unit style layer weights only (nst_job_set_style_weights)");
     LevelWs& L = ctx->lv[0];
     if (!L.targets) return fail(ctx, NST_E_STATE, "targets of the stripe not set");
     if (!xs) return fail(ctx, NST_E_ARG, "null buffer");
@@ -746,16 +750,33 @@ int window_check(nst_ctx* ctx, const float* xs, int row0, int rows, int H0) {
 // ================================================================================================
 extern "C" {
 
-int nst_level_set_targets(nst_ctx* ctx, int level, const float* content, const float* style, int hs, int ws,
-                          void* stream) {
+// The targets of one level from K style images blended per map (include/nst_hip.h has the definition).  nst_level_set_targets
+// is its K = 1 case: one image, b^ = 1 on every map, whose alpha = 1 finish writes the bits the plain finish pass writes.
+int nst_level_set_targets_blend(nst_ctx* ctx, int level, const float* content, int K, const float* const* styles, const int* hs,
+                                const int* ws, const float* blend, void* stream) {
     if (ctx) { ++ctx->closure_epoch; ++ctx->ws_seq; }
     NSTCHK(bind(ctx));
     if (level < 0 || level >= ctx->levels) return fail(ctx, NST_E_STATE, "level not configured");
-    if (!content || !style) return fail(ctx, NST_E_ARG, "null image");
-    if (hs < 16 || ws < 16) return fail(ctx, NST_E_ARG, "style image must be at least 16x16");
+    if (K < 1 || K > NST_MAX_STYLES) return fail(ctx, NST_E_ARG, "the number of style images must be 1 .. NST_MAX_STYLES");
+    if (!content || !styles || !hs || !ws || !blend) return fail(ctx, NST_E_ARG, "null argument");
+    for (int k = 0; k < K; ++k) {
+        if (!styles[k]) return fail(ctx, NST_E_ARG, "null image");
+        if (hs[k] < 16 || ws[k] < 16) return fail(ctx, NST_E_ARG, "style image must be at least 16x16");
+    }
+    for (int i = 0; i < K * 6; ++i)
+        if (!(blend[i] >= 0.f) || std::isinf(blend[i])) return fail(ctx, NST_E_ARG, "blend weights must be finite and >= 0");
+    const Taps& tp = ctx->taps;
+    // b^[k][q] = B[k][i] / sum_k B[k][i] (fp64, then fp32) for the map i of style slot q
+    float bhat[NST_MAX_STYLES][kMaxStyle] = {};
+    for (int q = 0; q < tp.nstyle; ++q) {
+        const int i = tap_index_of(tp.style[q]);
+        double sum = 0.0;
+        for (int k = 0; k < K; ++k) sum += (double)blend[k * 6 + i];
+        if (!(sum > 0.0)) return fail(ctx, NST_E_ARG, "every map of the style set needs a positive blend weight of some style image");
+        for (int k = 0; k < K; ++k) bhat[k][q] = (float)((double)blend[k * 6 + i] / sum);
+    }
     hipStream_t s = enter(ctx, stream);
     LevelWs& L = ctx->lv[level];
-    const Taps& tp = ctx->taps;
     // content: the content map (default ReLU(conv4_2)) of the content image, through the level's own activation buffers - by the launches the closure
     // of this job will use (one launch per layer, Winograd F(2,3) where it applies), so that target and current features
     // carry the same rounding: an image that IS the content image then has a content loss of (all but) exactly zero, as in
@@ -769,21 +790,43 @@ int nst_level_set_targets(nst_ctx* ctx, int level, const float* content, const f
         NSTCHK(forward(ctx, L.acts, content, L.h, L.w, s, tp.content, ctx->channels));
     }
     HIPCHK(ctx, hipMemcpyAsync(L.content_t, L.acts.act[tp.content], L.content_n * 4, hipMemcpyDeviceToDevice, s));
-    // style: the Gram matrices of the style image (its own size)
-    Scratch sc(ctx, s);
-    float* part = nullptr;
-    NSTCHK(alloc_acts(ctx, sc.acts, hs, ws));
-    NSTCHK(sc.alloc(&part, gram_part_floats_for(tp, hs, ws)));
-    NSTCHK(forward(ctx, sc.acts, style, hs, ws, s, tp.style[tp.nstyle - 1], ctx->channels));
-    for (int k = 0; k < tp.nstyle; ++k) {
-        const int l = tp.style[k];
-        const StyleTerm st = style_term(tp, k, sc.acts, 0.f);
-        NSTCHK(gram_of(ctx, sc.acts.act[l], st.N, st.C, ctx->conv_mode == 2 ? amax_act(sc.acts, l) : nullptr, (float)st.divisor, part, nullptr, 0.f, L.gram_t[k],
-                       nullptr, nullptr, nullptr, nullptr, s));
+    // style: Gt_q = sum_k b^[k][q] G_q(style_k), each image at its own size, in ascending k; the first contributing image
+    // writes b^ G, the later ones add to it; an image with b^ = 0 on a map is skipped there, one with b^ = 0 on every map
+    // of the set gets no forward pass, and no forward pass goes deeper than the deepest map its image contributes to
+    bool written[kMaxStyle] = {};
+    for (int k = 0; k < K; ++k) {
+        int deepest = -1;
+        for (int q = 0; q < tp.nstyle; ++q) if (bhat[k][q] > 0.f) deepest = q;
+        if (deepest < 0) continue;
+        Scratch sc(ctx, s);
+        float* part = nullptr;
+        NSTCHK(alloc_acts(ctx, sc.acts, hs[k], ws[k]));
+        NSTCHK(sc.alloc(&part, gram_part_floats_for(tp, hs[k], ws[k])));
+        NSTCHK(forward(ctx, sc.acts, styles[k], hs[k], ws[k], s, tp.style[deepest], ctx->channels));
+        for (int q = 0; q <= deepest; ++q) {
+            if (!(bhat[k][q] > 0.f)) continue;
+            const int l = tp.style[q];
+            const StyleTerm st = style_term(tp, q, sc.acts, 0.f, 1.f);
+            const int ns = gram_nsplit(st.C, st.N);
+            {
+                Timer t(ctx, s, K_GRAM, 2.0 * (double)st.N * st.C * st.C);
+                HIPCHK(ctx, launch_gram_partial(sc.acts.act[l], st.N, st.C, ns, ctx->conv_mode == 2 ? amax_act(sc.acts, l) : nullptr, part, s));
+            }
+            Timer t(ctx, s, K_OTHER, 0);
+            HIPCHK(ctx, launch_gram_finish_blend(part, gram_nslabs(st.C, ns), st.C, (float)st.divisor, bhat[k][q], written[q] ? 1 : 0,
+                                                 L.gram_t[q], s));
+            written[q] = true;
+        }
+        NSTCHK(sc.finish());
     }
-    NSTCHK(sc.finish());
     L.targets = true;
     return NST_OK;
+}
+
+int nst_level_set_targets(nst_ctx* ctx, int level, const float* content, const float* style, int hs, int ws,
+                          void* stream) {
+    const float ones[6] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
+    return nst_level_set_targets_blend(ctx, level, content, 1, &style, &hs, &ws, ones, stream);
 }
 
 int nst_closure(nst_ctx* ctx, const float* x, float cw, float sw, float tvw, float* grad, float* losses, void* stream) {
@@ -955,7 +998,7 @@ int nst_window_end(nst_ctx* ctx, const float* xs, int row0, int rows, int H0, fl
     Window win{row0, rows, H0, sums};
     // S = d loss / d G from the Gram sums of ALL stripes, normalised by the full image
     for (int q = 0; q < ctx->taps.nstyle; ++q) {
-        const StyleTerm st = style_term(ctx->taps, q, a, sw, H0);
+        const StyleTerm st = style_term(ctx->taps, q, a, sw, ctx->style_weight(q), H0);
         HIPCHK(ctx, launch_gram_finish(sums + kWinGramOff[q], 1, st.C, (float)st.divisor, L.gram_t[q], st.coef, nullptr, L.S[q], L.S_bf[q],
                                        amax_S(a, q), L.style_partial[q], s));
     }

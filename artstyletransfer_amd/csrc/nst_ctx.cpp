@@ -410,6 +410,18 @@ void drop_closure_state(nst_ctx* ctx, bool drop_targets) {
     for (int i = 0; drop_targets && i < ctx->levels; ++i) ctx->lv[i].targets = false;
 }
 
+// bit i = map i has a positive style layer weight
+unsigned positive_weight_mask(const float* w) {
+    unsigned m = 0;
+    for (int i = 0; i < 6; ++i) if (w[i] > 0.f) m |= 1u << i;
+    return m;
+}
+unsigned style_mask_of(const Taps& tp) {
+    unsigned m = 0;
+    for (int q = 0; q < tp.nstyle; ++q) m |= 1u << tap_index_of(tp.style[q]);
+    return m;
+}
+
 }  // namespace
 
 // ================================================================================================
@@ -640,6 +652,9 @@ int nst_job_set_taps(nst_ctx* ctx, int content_index, unsigned style_mask, int u
     tp.top = std::max(tp.content, tp.style[tp.nstyle - 1]);
     tp.use_relu = use_relu;
     tp.is_default = content_index == 4 && style_mask == 0x2Fu && use_relu == 1;
+    // the style layer weights stay as they are (they belong to map indices): the new set needs a map that counts
+    if ((style_mask & positive_weight_mask(ctx->style_w)) == 0u)
+        return fail(ctx, NST_E_ARG, "no map of style_mask has a positive style layer weight (nst_job_set_style_weights)");
     // every level's targets and the captured closure belong to the old taps; the tap-sized buffers are re-allocated
     quiesce(ctx);
     drop_closure_state(ctx, true);
@@ -703,6 +718,29 @@ int nst_job_set_pooling(nst_ctx* ctx, int mode) {
 }
 
 int nst_job_pooling(const nst_ctx* ctx) { return ctx ? (ctx->pool_avg ? NST_POOL_AVG : NST_POOL_MAX) : -1; }
+
+// Per-layer style weights (the w_l of Gatys, Ecker & Bethge 2016): a factor of each map's term in the loss row and in the
+// coefficient of its Gram backward.  The targets do not depend on them and stay; what an optimiser remembers of a closure,
+// a pending backward half and a captured graph (the coefficients are baked into it) do not.
+int nst_job_set_style_weights(nst_ctx* ctx, const float* w) {
+    if (ctx) { ++ctx->closure_epoch; ++ctx->ws_seq; }
+    NSTCHK(bind(ctx));
+    if (!w) return fail(ctx, NST_E_ARG, "null argument");
+    for (int i = 0; i < 6; ++i)
+        if (!(w[i] >= 0.f) || std::isinf(w[i])) return fail(ctx, NST_E_ARG, "style layer weights must be finite and >= 0");
+    if ((style_mask_of(ctx->taps) & positive_weight_mask(w)) == 0u)
+        return fail(ctx, NST_E_ARG, "at least one map of the current style set needs a positive style layer weight");
+    quiesce(ctx);
+    drop_closure_state(ctx, false);
+    for (int i = 0; i < 6; ++i) ctx->style_w[i] = w[i];
+    return NST_OK;
+}
+
+int nst_job_style_weights(const nst_ctx* ctx, float* w) {
+    if (!ctx || !w) return fail(nullptr, NST_E_ARG, "null argument");
+    for (int i = 0; i < 6; ++i) w[i] = ctx->style_w[i];
+    return NST_OK;
+}
 
 int nst_set_timing(nst_ctx* ctx, int enabled) {
     NSTCHK(bind(ctx));

@@ -24,6 +24,11 @@ constexpr int kTapLayer[6] = {0, 2, 4, 8, 9, 12};
 // the reference's default taps (neural_nets.py:25-28): content 4 = ReLU(conv4_2), style 0, 1, 2, 3, 5 =
 // relu1_1, relu2_1, relu3_1, relu4_1, relu5_1; a context's own taps (nst_job_set_taps) live in nst_ctx::taps
 constexpr int kMaxStyle = 6;
+// conv layer of a tap -> its index in Vgg19.layer_names (what the style layer weights are indexed by)
+inline int tap_index_of(int layer) {
+    for (int i = 0; i < 6; ++i) if (kTapLayer[i] == layer) return i;
+    return -1;
+}
 inline int pool_index_after(int l) {
     for (int k = 0; k < 4; ++k) if (kPoolAfter[k] == l) return k;
     return -1;
@@ -156,7 +161,15 @@ struct nst_ctx {
     nst::Taps taps;             // nst_job_set_taps
     int channels = 3;           // nst_job_set_color: 3 = RGB, 1 = luminance (the optimised image is u = 255 Y)
     int pool_avg = 0;           // nst_job_set_pooling: 1 = the four pools average their windows (include/nst_hip.h has the definition)
-    // bumped on entry to every call that changes what a closure computes (configure, taps, colour, pooling, targets), failure paths
+    // nst_job_set_style_weights: the weight of each of the six maps in the style term, by map index (not by style slot: they
+    // survive nst_job_set_taps).  One code path: a new context's ones multiply exactly
+    float style_w[6] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
+    float style_weight(int q) const { return style_w[nst::tap_index_of(taps.style[q])]; }      // of style slot q
+    bool unit_style_weights() const {
+        for (float w : style_w) if (w != 1.f) return false;
+        return true;
+    }
+    // bumped on entry to every call that changes what a closure computes (configure, taps, colour, pooling, style weights, targets), failure paths
     // included: an optimiser's remembered closure result is valid only under the epoch it was made in (nst_opt.cpp)
     unsigned long long closure_epoch = 0;
     // advanced on entry to every call that reads or writes the level workspaces (nst_closure*, nst_window_*,

@@ -212,13 +212,14 @@ struct LevelLossInputs {
     size_t content_n;
     const double* style_partial[6];  // gram_finish_blocks(C) doubles each: partial sums of (G-Gt)^2
     int style_c[6];                  // C of each style layer (mse mean over C*C)
+    float style_w[6];                // layer weight of each style layer (nst_job_set_style_weights; 1 = the plain mean)
     const float* tv_means;           // 2 floats (mean_x, mean_y)
     int owned;                       // 0: level computed by another rank, its row is written as zeros
 };
 struct LossAssembly {
     LevelLossInputs lv[8];
     int levels;
-    int nstyle;                      // style layers in use (1..6): the style term is the mean over them
+    int nstyle;                      // style layers in use (1..6): the style term is (sum_k w_k mse_k) / nstyle
     float cw, sw, tvw;
     float* out;                      // 4*levels + 1
 };
@@ -252,6 +253,11 @@ int gram_finish_blocks(int C);
 hipError_t launch_gram_finish(const float* part, int nslabs, int C, float divisor, const float* target, float coef,
                               float* gram_out, float* S, unsigned short* S_bf, unsigned* S_amax, double* mse_partial,
                               hipStream_t stream);
+// The blend form of the finish pass (the targets of a level, nst_level_set_targets_blend): the same sum of the slabs in the
+// same order, G = sum / divisor, then gram_out = alpha * G (accumulate = 0) or gram_out = gram_out + alpha * G (accumulate
+// != 0), product and sum each rounded to fp32.  alpha = 1 without accumulation writes the bits launch_gram_finish writes.
+hipError_t launch_gram_finish_blend(const float* part, int nslabs, int C, float divisor, float alpha, int accumulate,
+                                    float* gram_out, hipStream_t stream);
 
 // image_ops.hip: job set-up on the device (pyramid resize, structured-noise initial image) ---------------------
 hipError_t launch_resize_hwc(const float* src, int h, int w, int C, float* dst, int oh, int ow, hipStream_t stream);

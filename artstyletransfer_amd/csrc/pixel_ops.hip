@@ -628,7 +628,8 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(LossAssembly la) {
         for (int q = 0; q < 7; ++q) { r[q] = 0.0; for (int i = 0; i < 4; ++i) r[q] += sh[q][i]; }
         const float content = (float)(r[0] / (double)in.content_n);
         float style = 0.f;
-        for (int k = 0; k < la.nstyle; ++k) style = style + (float)(r[k + 1] / ((double)in.style_c[k] * in.style_c[k]));
+        // sum_k w_k mse_k (product and sum each rounded; w = 1, a new context's, is exact: the plain sum)
+        for (int k = 0; k < la.nstyle; ++k) style = style + in.style_w[k] * (float)(r[k + 1] / ((double)in.style_c[k] * in.style_c[k]));
         style = style / (float)la.nstyle;
         const float mx = in.tv_means[0], my = in.tv_means[1];
         const float tv = mx * mx + my * my;

@@ -11,6 +11,7 @@ import torch
 from . import _lib
 from . import taps as _taps
 from .pooling_modes import check_pooling
+from . import style_modes as _style
 from ._lib import NST_LOSS_ROW, NstError, StepInfo
 
 TAP_CHANNELS = (64, 128, 256, 512, 512, 512)
@@ -82,6 +83,7 @@ class StyleEngine:
         self.taps = DEFAULT_TAPS                 # (content index, style indices, use_relu): set_taps
         self.channels = 3                        # 1 under set_color("luminance")
         self.pooling = "max"                     # "avg" under set_pooling("avg")
+        self.layer_weights = _style.UNIT_WEIGHTS # set_style_weights
 
     def close(self):
         if getattr(self, "ctx", None):
@@ -148,6 +150,28 @@ class StyleEngine:
         if self.pooling != "max":
             self.set_pooling("max")
 
+    def set_style_weights(self, w) -> None:
+        """Per-layer style weights (nst_job_set_style_weights): six numbers >= 0, one per map of Vgg19.layer_names; the
+        style term becomes (sum_i w_i MSE_i) / nstyle.  Keeps the targets.  ValueError for a wrong length, a negative or
+        non-finite entry, or when no map of the current style set has a positive weight."""
+        w = _style.check_style_layer_weights(w, style_indices=self.taps[1])
+        arr = (C.c_float * _style.NUM_MAPS)(*w)
+        try:
+            _lib.check(self.ctx, self.lib.nst_job_set_style_weights(self.ctx, arr), "nst_job_set_style_weights")
+        finally:                                 # the context's weights, whether the call succeeded or not
+            self.layer_weights = self.style_weights()
+
+    def style_weights(self) -> Tuple[float, ...]:
+        """The context's six style layer weights (nst_job_style_weights)."""
+        arr = (C.c_float * _style.NUM_MAPS)()
+        _lib.check(self.ctx, self.lib.nst_job_style_weights(self.ctx, arr), "nst_job_style_weights")
+        return tuple(float(v) for v in arr)
+
+    def reset_style_weights(self) -> None:
+        """Back to w = 1 on every map, if the weights were changed."""
+        if self.layer_weights != _style.UNIT_WEIGHTS:
+            self.set_style_weights(_style.UNIT_WEIGHTS)
+
     def release_job(self) -> None:
         """Give the job's pyramid workspace back (4.7 GB at L=2) and keep the context with its uploaded weights: what an
         engine waiting in neural_nets' pool holds is the smallest job nst_job_configure accepts."""
@@ -169,6 +193,30 @@ class StyleEngine:
         _lib.check(self.ctx, self.lib.nst_level_set_targets(self.ctx, level, _ptr(content), _ptr(style),
                                                             style.shape[1], style.shape[2], _stream(self.device)),
                    "nst_level_set_targets")
+
+    def set_targets_blend(self, level: int, content: torch.Tensor, styles: Sequence[torch.Tensor], blend) -> None:
+        """Targets of one level with the style Gram targets blended from K style images, each of its own size
+        (nst_level_set_targets_blend).  blend: K numbers (the same weight on every map) or a K x 6 array B[k][i] >= 0, the
+        weight of image k on map i; the target of map i is sum_k B[k][i] G_i(style_k) / sum_k B[k][i].  ValueError for a
+        malformed blend, K outside 1..8 or a map of the style set with an all-zero column."""
+        h, w = self.level_shape(level)
+        ch = self.channels
+        styles = list(styles)
+        rows = _style.check_style_blend(blend, len(styles), style_indices=self.taps[1])
+        k = len(styles)
+        if content.numel() != ch * h * w or any(s.numel() != ch * s.shape[-2] * s.shape[-1] for s in styles):
+            raise NstError(f"targets must have {ch} channel(s) in this colour mode")
+        content = content.contiguous().reshape(ch, h, w)
+        _chk_dev(content, self.device)
+        styles = [s.contiguous().reshape(ch, s.shape[-2], s.shape[-1]) for s in styles]
+        for s in styles:
+            _chk_dev(s, self.device)
+        ptrs = (C.c_void_p * k)(*[s.data_ptr() for s in styles])
+        hs = (C.c_int * k)(*[s.shape[1] for s in styles])
+        ws = (C.c_int * k)(*[s.shape[2] for s in styles])
+        flat = (C.c_float * (k * _style.NUM_MAPS))(*[v for row in rows for v in row])
+        _lib.check(self.ctx, self.lib.nst_level_set_targets_blend(self.ctx, level, _ptr(content), k, ptrs, hs, ws, flat,
+                                                                  _stream(self.device)), "nst_level_set_targets_blend")
 
     def closure(self, x: torch.Tensor, cw: float, sw: float, tvw: float,
                 grad: Optional[torch.Tensor] = None, losses: Optional[torch.Tensor] = None):
@@ -634,7 +682,7 @@ class PixelOptimizer:
                    "nst_opt_shard_levels")
 
     def shard_stripes(self, rank: int, world: int, weights, content_t, style_t,
-                      dist_mod=None, group=None, comm: "Communicator" = None) -> None:
+                      dist_mod=None, group=None, comm: "Communicator" = None, blend=None) -> None:
         """Spatial sharding of the large levels (SURVEY 8(e) partition B, halo recompute) on top of level sharding of the
         rest: every rank evaluates a horizontal stripe (its rows + a 96-row halo, a single-level engine of its own) of
         every STRIPED level and its share of the other levels.  content_t / style_t: the prepared (1,3,h,w) content and
@@ -647,15 +695,22 @@ class PixelOptimizer:
         ranks' parts.
         `comm` (a Communicator): both collectives go through the C ABI's RCCL communicator (nst_comm_allreduce_sum on
         the job's stream; gradient and loss row are ONE packed buffer, as in nst_opt_shard_levels_comm) and rank / world
-        are the communicator's; otherwise through `dist_mod` (torch.distributed: gloo rehearsals, or nccl)."""
+        are the communicator's; otherwise through `dist_mod` (torch.distributed: gloo rehearsals, or nccl).
+        `blend`: the job's style blend (set_targets_blend) - every entry of style_t is then the LIST of that level's K style
+        images; the stripe closure takes its Gram targets from the level's targets, so a blend is honoured.  Style layer
+        weights other than 1 are not (nst_window_* returns NST_E_STATE under them): ValueError."""
         from . import sharding
         if comm is not None:
             rank, world = comm.rank, comm.world
         elif dist_mod is None:
             import torch.distributed as dist_mod
+        e = self.engine
+        if e.layer_weights != _style.UNIT_WEIGHTS:
+            raise ValueError("the stripe closure implements unit style layer weights only (reset_style_weights())")
         contents = list(content_t) if isinstance(content_t, (list, tuple)) else [content_t]
         styles = list(style_t) if isinstance(style_t, (list, tuple)) else [style_t]
-        e = self.engine
+        if blend is not None and styles and isinstance(styles[0], torch.Tensor):
+            styles = [styles]                    # one striped level: its K style images
         if e.channels != 3:
             raise NstError("the stripe closure implements RGB only (set_color('rgb'))")
         H, W = e.shape
@@ -665,7 +720,10 @@ class PixelOptimizer:
             plan = sharding.StripePlan(H >> l, world, rank)
             st = StyleEngine(weights, e.device)
             st.configure(1, plan.ext_rows, W >> l)
-            st.set_targets(0, plan.cut(contents[l]), styles[l].contiguous())
+            if blend is None:
+                st.set_targets(0, plan.cut(contents[l]), styles[l].contiguous())
+            else:
+                st.set_targets_blend(0, plan.cut(contents[l]), styles[l], blend)
             plans.append(plan)
             stripes.append(st)
         self._stripes, self._plans = stripes, plans

@@ -115,7 +115,8 @@ def lease_engine(device) -> StyleEngine:
 
 
 def return_engine(eng: StyleEngine) -> None:
-    """Back to the per-GPU pool, with the default taps, RGB and max pooling: the next job must not inherit this one's."""
+    """Back to the per-GPU pool, with unit style layer weights, the default taps, RGB and max pooling: the next job must not
+    inherit this one's."""
     if getattr(eng, "ctx", None) is None:
         return
     idx = eng.device.index
@@ -125,6 +126,7 @@ def return_engine(eng: StyleEngine) -> None:
     if keep:
         try:
             eng.release_job()                  # the workspace goes back now, only the weights stay resident
+            eng.reset_style_weights()          # (before the taps: a style set needs a map with a positive weight)
             eng.reset_taps()
             eng.reset_color()
             eng.reset_pooling()

@@ -21,6 +21,7 @@ from . import taps as _taps
 from .engine import PixelOptimizer, StyleEngine
 from .neural_nets import lease_engine, return_engine, shared_engine
 from .pooling_modes import check_pooling
+from . import style_modes as _style
 
 # ImageNet statistics (reference :22-23)
 IMAGENET_MEAN_255 = [123.675, 116.28, 103.53]
@@ -116,7 +117,7 @@ class _DeviceJob:
     (`_make_job`, tests/test_host_api.py)."""
 
     def __init__(self, device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, taps=None, color=None,
-                 pooling=None):
+                 pooling=None, style_weights=None, blend=None):
         self.dev = dev = device
         self.optimizer = None
         self.luminance = color == "luminance"   # the optimised image is u = 255 Y; the yield puts the content's I, Q back
@@ -149,20 +150,30 @@ class _DeviceJob:
                     engine.set_taps(*taps)
                 if pooling is not None:             # "avg": average pooling in the feature network
                     engine.set_pooling(pooling)
+                if style_weights is not None:       # six per-layer style weights, checked against the taps
+                    engine.set_style_weights(style_weights)
+                # blend = (per-level image lists of the extra styles, K x 6 matrix): style 0 is style_imgs
+                all_styles = [style_imgs] + (list(blend[0]) if blend is not None else [])
                 if self.luminance:
                     # luminance-only transfer: content targets 255 Y(content), style targets 255 (alpha Y(style) + beta)
                     # with the style luminance matched to the content's (statistics of the top level), u0 = 255 Y(init)
                     engine.set_color("luminance")
                     self.content_top = on_device(content_imgs[0])
-                    alpha, beta = device_image.luminance_params(engine, self.content_top, on_device(style_imgs[0]))
+                    # (every style image is matched to the content's luminance on its own, by its top level's statistics)
+                    ab = [device_image.luminance_params(engine, self.content_top, on_device(lv[0])) for lv in all_styles]
                     content_t = lambda img: engine.luminance(on_device(img))                      # noqa: E731
-                    style_t = lambda img: engine.luminance(on_device(img), alpha, beta)           # noqa: E731
+                    style_t = lambda img, k=0: engine.luminance(on_device(img), *ab[k])           # noqa: E731
                 else:
-                    content_t = style_t = prepared
+                    content_t = prepared
+                    style_t = lambda img, k=0: prepared(img)                                      # noqa: E731
                 for lvl, (c_img, s_img) in enumerate(zip(content_imgs, style_imgs)):
                     if tuple(c_img.shape[:2]) != engine.level_shape(lvl):
                         raise ValueError(f"content level {lvl} is {tuple(c_img.shape[:2])}, expected {engine.level_shape(lvl)}")
-                    engine.set_targets(lvl, content_t(c_img), style_t(s_img))
+                    if blend is None:
+                        engine.set_targets(lvl, content_t(c_img), style_t(s_img))
+                    else:
+                        engine.set_targets_blend(lvl, content_t(c_img), [style_t(lv[lvl], k) for k, lv in enumerate(all_styles)],
+                                                 blend[1])
                 self.x = content_t(init_img) if self.luminance else prepared(init_img)
                 self.optimizer = PixelOptimizer(engine, optimizer_name, lr_start, LBFGS_MAX_EVAL)
             # Per-step yield (reference :207-208): the image is un-prepared into its own device buffer, copied to
@@ -211,8 +222,10 @@ class _DeviceJob:
         return_engine(self.engine)             # back to the per-GPU pool: the next job re-uses its uploaded weights
 
 
-def _make_job(device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, taps=None, color=None, pooling=None):
-    return _DeviceJob(device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, taps, color, pooling)
+def _make_job(device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, taps=None, color=None, pooling=None,
+              style_weights=None, blend=None):
+    return _DeviceJob(device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, taps, color, pooling,
+                      style_weights, blend)
 
 
 async def _drain(step_future):
@@ -246,6 +259,8 @@ class NeuralStyleTransfer:
         self.__taps = None                       # None: the reference's feature maps
         self.__color = None                      # set_preserve_color
         self.__pooling = "max"                   # set_pooling
+        self.__layer_weights = None              # set_style_layer_weights (None: w = 1 on every map)
+        self.__blend = None                      # set_style_blend: (extra style levels, blend as given)
 
     def set_feature_maps(self, content_layer=None, style_layers=None, use_relu=True):
         """Extension: the feature maps the losses of the next `process` read - a content map and a set of style maps of
@@ -271,6 +286,32 @@ class NeuralStyleTransfer:
         for any other value."""
         self.__pooling = check_pooling(mode)
 
+    def set_style_layer_weights(self, weights=None):
+        """Extension: per-layer style weights (the w_l of Gatys, Ecker & Bethge 2016) of the next `process`: the style term
+        of a level becomes (sum_i w_i MSE_i) / nstyle.  `weights`: a sequence of 6 numbers >= 0, one per map of
+        Vgg19.layer_names, or a dict {map index or name: weight} (maps not named get 1); None: w = 1 everywhere, the
+        reference's plain mean.  ValueError for a wrong length, a negative or non-finite entry, an unknown key, or - in
+        `process`, where the style set is known - when no map of the style set has a positive weight."""
+        w = _style.check_style_layer_weights(weights, style_indices=range(_style.NUM_MAPS))
+        self.__layer_weights = None if _style.is_unit(w) else w
+
+    def set_style_blend(self, extra_style_levels=None, blend=None):
+        """Extension: more than one style image in the next `process` (jcjohnson's -style_blend_weights; per map, the scale
+        control of Gatys et al. 2017).  `extra_style_levels`: a list of per-level image lists, one per extra style, each
+        like the constructor's `style_imgs` (style 0 is the constructor's; sizes are each style's own).  `blend`: K numbers
+        (the same weight on every map) or a K x 6 array B[k][i] >= 0, K = 1 + the number of extra styles; the Gram target
+        of map i is sum_k B[k][i] G_i(style_k) / sum_k B[k][i]; None: an even blend.  None / an empty list: the single
+        style.  ValueError for a K that does not match, K > 8, a negative or non-finite entry or - in `process` - a map of
+        the style set with an all-zero column."""
+        extra = list(extra_style_levels or [])
+        if not extra:
+            if blend is not None:
+                _style.check_style_blend(blend, 1, style_indices=())
+            self.__blend = None
+            return
+        _style.check_style_blend(blend, 1 + len(extra), style_indices=())
+        self.__blend = ([list(lv) for lv in extra], blend)
+
     async def process(self, content_imgs, init_img, lr_start, iters_num, content_weight, style_weight, tv_weight,
                       init_img_name):
         # validates the model name exactly as the reference does (ValueError for anything but vgg19)
@@ -279,12 +320,29 @@ class NeuralStyleTransfer:
             raise RuntimeError("Unknown optimizer")
         if self.__device.type != "cuda":
             raise RuntimeError("the HIP style-transfer engine needs a GPU; no CPU path exists")
+        # the style settings against the style set of THIS job, before any GPU work
+        style_set = (self.__taps or (None, _taps.DEFAULT_STYLE_INDICES))[1]
+        layer_weights = blend = None
+        if self.__layer_weights is not None:
+            layer_weights = _style.check_style_layer_weights(self.__layer_weights, style_indices=style_set)
+        if self.__blend is not None:
+            for lv in self.__blend[0]:
+                if len(lv) != len(self.__style_imgs):
+                    raise ValueError(f"an extra style has {len(lv)} levels, the job has {len(self.__style_imgs)}")
+            blend = (self.__blend[0], _style.check_style_blend(self.__blend[1], 1 + len(self.__blend[0]), style_indices=style_set))
         style_imgs = self.__style_imgs
         if self.__color == "histogram":
+            # every style's levels recoloured with its own statistics (those of its top level)
             setup = shared_engine(self.__device)
-            up = [s if isinstance(s, torch.Tensor) else device_image.upload(setup, s) for s in (content_imgs[0], *style_imgs)]
-            style_imgs = device_image.recolor_histogram(setup, up[0].to(self.__device).contiguous(),
-                                                        [s.to(self.__device).contiguous() for s in up[1:]])
+
+            def up(img):
+                t = img if isinstance(img, torch.Tensor) else device_image.upload(setup, img)
+                return t.to(self.__device).contiguous()
+
+            content_top = up(content_imgs[0])
+            style_imgs = device_image.recolor_histogram(setup, content_top, [up(s) for s in style_imgs])
+            if blend is not None:
+                blend = ([device_image.recolor_histogram(setup, content_top, [up(s) for s in lv]) for lv in blend[0]], blend[1])
         extra = {}
         if self.__taps is not None:
             extra["taps"] = self.__taps
@@ -292,6 +350,10 @@ class NeuralStyleTransfer:
             extra["color"] = "luminance"
         if self.__pooling != "max":
             extra["pooling"] = self.__pooling
+        if layer_weights is not None:
+            extra["style_weights"] = layer_weights
+        if blend is not None:
+            extra["blend"] = blend
         job = _make_job(self.__device, self.__optimizer_name, style_imgs, content_imgs, init_img, lr_start, **extra)
         cw, sw, tvw = float(content_weight), float(style_weight), float(tv_weight)
         loop = asyncio.get_running_loop()
@@ -348,17 +410,29 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
                                 iters_num, levels_num, noise_factor, noise_levels, noise_levels_central_amplitude,
                                 noise_levels_peripheral_amplitude, noise_levels_dispersion, device=None, *,
                                 content_layer=None, style_layers=None, use_relu=True, preserve_color=None,
-                                pooling="max"):
+                                pooling="max", extra_styles=None, style_blend=None, style_layer_weights=None):
     """Async generator yielding (percent, HWC float32 image) after every optimiser step
     (reference :229-372). `device` (extension): the GPU to run on; default = current.  `content_layer`,
     `style_layers`, `use_relu` (extension): the feature maps the losses read, see NeuralStyleTransfer.set_feature_maps
     (None: the reference's).  `preserve_color` (extension): None, "luminance" or "histogram", see
     NeuralStyleTransfer.set_preserve_color; under "histogram" the style levels are recoloured once, here, and the noise
     map and the "style" initial image are built from the recoloured ones.  `pooling` (extension): "max" or "avg", see
-    NeuralStyleTransfer.set_pooling.  They are validated before any GPU work."""
+    NeuralStyleTransfer.set_pooling.  `extra_styles` (extension): further style images (HWC float [0,1], any sizes; their
+    pyramids are built here), blended with `content_n_style.style` - style 0, which alone feeds the noise map and the
+    "style" initial image - by `style_blend`: K numbers or a K x 6 array, see NeuralStyleTransfer.set_style_blend (None: an
+    even blend).  `style_layer_weights` (extension): see NeuralStyleTransfer.set_style_layer_weights.  Under
+    preserve_color="histogram" every style's levels are recoloured with its own statistics, under "luminance" every
+    style's luminance is matched to the content's on its own.  They are validated before any GPU work."""
     taps = _taps.normalize_taps(content_layer, style_layers, use_relu)
     host_image.check_preserve_color(preserve_color)
     check_pooling(pooling)
+    extra_styles = list(extra_styles) if extra_styles is not None else []
+    layer_weights = _style.check_style_layer_weights(style_layer_weights, style_indices=taps[1], use_relu=use_relu)
+    if extra_styles or style_blend is not None:
+        style_blend = _style.check_style_blend(style_blend, 1 + len(extra_styles), style_indices=taps[1])
+    for img in extra_styles:
+        if np.ndim(img) != 3 or np.shape(img)[2] != 3:
+            raise ValueError(f"extra_styles: expected HWC images with 3 channels, got shape {np.shape(img)}")
     if device is None:
         if not torch.cuda.is_available():
             raise RuntimeError("no GPU visible: the HIP style-transfer engine has no CPU path")
@@ -372,9 +446,11 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
     style_dev = device_image.upload(setup, content_n_style.style[1])
     content_levels = device_image.pyramid(setup, content_dev, levels_num)
     style_levels = device_image.pyramid(setup, style_dev, levels_num)
+    extra_levels = [device_image.pyramid(setup, device_image.upload(setup, img), levels_num) for img in extra_styles]
     style_init = None
     if preserve_color == "histogram":
         style_levels = device_image.recolor_histogram(setup, content_levels[0], style_levels)
+        extra_levels = [device_image.recolor_histogram(setup, content_levels[0], lv) for lv in extra_levels]
         style_init = style_levels[0]
     level = max(levels_num - 1, 0)
     init_img, tag = device_image.initial_image(
@@ -387,6 +463,8 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
     nst.set_feature_maps(*taps, use_relu=use_relu)
     nst.set_preserve_color("luminance" if preserve_color == "luminance" else None)   # (histogram: recoloured above)
     nst.set_pooling(pooling)
+    nst.set_style_layer_weights(layer_weights)
+    nst.set_style_blend(extra_levels, style_blend if extra_levels else None)
     lr_start = 10.0
     async for img, cur_iter in nst.process(content_levels, init_img, lr_start, iters_num, content_weight,
                                            style_weight, tv_weight, init_name):

@@ -62,10 +62,13 @@ class Task:
 
     async def __do_job(self):
         cfg = self.__config
-        # the keyword-only feature-map, colour and pooling fields of Config, passed on when set (a config without them is the reference's)
+        # the keyword-only feature-map, colour, pooling and style fields of Config, passed on when set (a config without them is the reference's)
         extensions = {k: getattr(cfg, k) for k, dflt in (("content_layer", None), ("style_layers", None), ("use_relu", True),
                                                    ("preserve_color", None), ("pooling", "max"))
                 if getattr(cfg, k, dflt) != dflt}
+        # (images and arrays: `is not None`, not `!=`)
+        extensions.update({k: getattr(cfg, k) for k in ("extra_styles", "style_blend", "style_layer_weights")
+                           if getattr(cfg, k, None) is not None})
         gpu = await self.__slots.acquire()
         self.gpu = gpu
         try:

@@ -40,6 +40,7 @@ extern "C" {
 #define NST_VGG19_CONVS 13  /* conv1_1 ... conv5_1 (torchvision features[0:30]) */
 #define NST_MAX_LEVELS 8
 #define NST_LOSS_ROW 4      /* per level: total, content, style, tv */
+#define NST_MAX_STYLES 8    /* style images one level's targets may blend (nst_level_set_targets_blend) */
 
 typedef struct nst_ctx nst_ctx;
 typedef struct nst_opt nst_opt;
@@ -171,12 +172,49 @@ int nst_job_color(const nst_ctx* ctx);
 int nst_job_set_pooling(nst_ctx* ctx, int mode);
 int nst_job_pooling(const nst_ctx* ctx);
 
+/* Per-layer style weights (the w_l of Gatys, Ecker & Bethge 2016, eq. 5), a setting of the context.  w[i]: the weight of
+ * map i of Vgg19.layer_names (0..5), finite and >= 0; at least one map of the current style set (nst_job_set_taps) has
+ * w > 0; NST_E_ARG for anything else (the weights then stay as they were).  With them
+ *   style term of a level = (sum_i w_i MSE(G_i, Gt_i)) / nstyle, over the maps of the style set in ascending order,
+ *   backward of map i: S_i = coef_i (G_i - Gt_i), coef_i = (float)((double)style_weight (double)w_i 4 / (nstyle C^2 C h w)).
+ * A new context has w = 1 everywhere, which multiplies exactly: there is one code path, and under w = 1 every loss row and
+ * gradient is bitwise what it is without the setting.  A map of the set with w_i = 0 is still evaluated and contributes
+ * zero.  The weights belong to map indices, not to positions in the style set: they survive nst_job_set_taps, which
+ * returns NST_E_ARG (and changes nothing) when no map of its style_mask has a positive weight.
+ * Setting the weights (even the same ones, and when the call fails) waits for the context's work, drops any captured
+ * closure graph and ends the validity of an optimiser's remembered closure (nst_opt_set_closure_reuse) and of a pending
+ * nst_closure_backward.  It does NOT drop the targets: they do not depend on the weights.  It composes with any taps,
+ * colour mode, pooling, conv mode and schedule, and with level sharding (targets are per level, weights per context).
+ * The stripe closure (nst_window_*) implements w = 1 only and returns NST_E_STATE under any other weights.
+ * nst_job_style_weights writes the current weights to w. */
+int nst_job_set_style_weights(nst_ctx* ctx, const float w[6]);
+int nst_job_style_weights(const nst_ctx* ctx, float w[6]);
+
 /* LossBuilder.__init__ (neural_style_transfer.py:68-82): target content representation
  * ReLU(conv4_2) of the content image and the 5 target Gram matrices of the style image of one
  * level (of the maps nst_job_set_taps chose, when it was called).  content: device (3,h,w) of that level's size; style: device (3,hs,ws), any size.
  * (1,h,w) / (1,hs,ws) prepared luminance images under NST_COLOR_LUMINANCE (nst_job_set_color). */
 int nst_level_set_targets(nst_ctx* ctx, int level, const float* content, const float* style,
                           int hs, int ws, void* stream);
+
+/* The same with the style targets blended from K style images (jcjohnson/neural-style's -style_blend_weights; per map, the
+ * scale control of Gatys et al. 2017, "Controlling Perceptual Factors in Neural Style Transfer": fine structure from one
+ * painting, coarse structure from another).  1 <= K <= NST_MAX_STYLES.  styles[k]: device (3,hs[k],ws[k]) ((1,hs[k],ws[k])
+ * under NST_COLOR_LUMINANCE), every size its own and >= 16x16.  blend: HOST, K x 6 row-major, B[k][i] = weight of image k
+ * on map i of Vgg19.layer_names; every entry finite and >= 0, every column of a map in the style set with a positive sum;
+ * NST_E_ARG for anything else (the level then has the targets it had).  Columns of maps outside the style set are ignored.
+ *   b^[k][i] = B[k][i] / sum_k B[k][i], computed in fp64 and cast to float;
+ *   target of map i: Gt_i = sum_k b^[k][i] G_i(style_k), accumulated in fp32 in ascending k - the first contributing k is
+ *   written as b^ G (not added to a zero fill), every later one as Gt + b^ G, product and sum each rounded; a k with
+ *   B[k][i] = 0 is skipped, and a style image whose row is zero over the whole style set gets no forward pass.
+ * The gradient of the style term is that of sum_k b^[k][i] MSE(G_i, G_i(style_k)); the LOSS differs from that sum by a
+ * constant that does not depend on the image (sum_k b^_k |G_k|^2 - |sum_k b^_k G_k|^2, over C^2): the loss row reports
+ * MSE(G_i, Gt_i).  The content target is that of nst_level_set_targets.  K = 1 gives the targets of nst_level_set_targets
+ * bitwise, whatever the (positive) entries of its row: nst_level_set_targets is the K = 1 case of the same code.  Same
+ * life cycle as nst_level_set_targets.  The stripe closure (nst_window_*) reads its Gram targets from the level's targets,
+ * so blended targets are honoured there. */
+int nst_level_set_targets_blend(nst_ctx* ctx, int level, const float* content, int K, const float* const* styles,
+                                const int* hs, const int* ws, const float* blend /* K x 6, row-major */, void* stream);
 
 /* optimizer_step_callback without its LR decay and prints (neural_style_transfer.py:152-199) =
  * sum over levels of LossBuilder.build (:84-112) on the bicubic 1/2 chain of x (:170-176),
@@ -263,7 +301,8 @@ int nst_opt_history(const nst_opt* opt, int* pairs, int* n_iter);
 /* L-BFGS closure reuse (default on; env NST_CLOSURE_REUSE=0 at nst_opt_create turns it off).  The closure is bitwise
  * reproducible, so when a step starts at bitwise the image the previous step left (a rejected or skipped trial, or an
  * accepted trial whose closure was the last one made), with the same weights and no change to the job in between
- * (nst_job_configure, nst_job_set_taps, nst_job_set_color, nst_job_set_pooling, nst_level_set_targets), its first closure is served from what
+ * (nst_job_configure, nst_job_set_taps, nst_job_set_color, nst_job_set_pooling, nst_job_set_style_weights,
+ * nst_level_set_targets, nst_level_set_targets_blend), its first closure is served from what
  * the optimiser remembers instead of evaluated: same loss row, step counter, lr decay, step info and image.  One
  * device compare of x decides, so the caller may write x between steps.  Never in the sharded modes; Adam never.
  * Changing the setting drops what is remembered. */
@@ -398,8 +437,9 @@ int nst_luminance_recombine(nst_ctx* ctx, const float* u, const float* content, 
  *     the caller adds the stripes' gradients into the full image (overlap-add, one all-reduce).  losses[0..3] = (total,
  *     content, style, tv) of the level, losses[4] = total - identical on every rank.
  * Nothing else may run on the context between begin and end.  The stripe closure implements the default feature maps
- * only: after nst_job_set_taps with any other taps both calls return NST_E_STATE, as they do under NST_COLOR_LUMINANCE
- * and under NST_POOL_AVG (nst_job_set_pooling). */
+ * only: after nst_job_set_taps with any other taps both calls return NST_E_STATE, as they do under NST_COLOR_LUMINANCE,
+ * under NST_POOL_AVG (nst_job_set_pooling) and under style layer weights other than 1 (nst_job_set_style_weights).  The
+ * Gram targets are the level's, so those of nst_level_set_targets_blend are honoured. */
 int nst_window_sums_count(size_t* count);
 int nst_window_begin(nst_ctx* ctx, const float* xs, int row0, int rows, int H0, float* sums, void* stream);
 int nst_window_end(nst_ctx* ctx, const float* xs, int row0, int rows, int H0, float content_weight, float style_weight,
