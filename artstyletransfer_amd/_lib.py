@@ -81,6 +81,10 @@ SYMBOLS = {
     "nst_level_set_targets": (C.c_int, [c_void, C.c_int, c_void, c_void, C.c_int, C.c_int, c_void]),
     "nst_level_set_targets_blend": (C.c_int, [c_void, C.c_int, c_void, C.c_int, C.POINTER(c_void), C.POINTER(C.c_int),
                                               C.POINTER(C.c_int), c_float_p, c_void]),
+    "nst_level_set_guidance": (C.c_int, [c_void, C.c_int, C.c_int, c_void, c_float_p, c_void]),
+    "nst_level_set_targets_guided": (C.c_int, [c_void, C.c_int, c_void, c_void, C.c_int, C.c_int, c_void, c_void]),
+    "nst_level_guidance": (C.c_int, [c_void, C.c_int, C.POINTER(C.c_int), c_float_p, C.POINTER(C.c_double)]),
+    "nst_level_guidance_planes": (C.c_int, [c_void, C.c_int, C.c_int, c_void, c_void]),
     "nst_closure": (C.c_int, [c_void, c_void, C.c_float, C.c_float, C.c_float, c_void, c_void, c_void]),
     "nst_closure_levels": (C.c_int, [c_void, c_void, C.c_float, C.c_float, C.c_float, C.c_uint, c_void, c_void, c_void]),
     "nst_closure_forward": (C.c_int, [c_void, c_void, C.c_float, C.c_float, C.c_float, C.c_uint, c_void, c_void]),
@@ -110,6 +114,8 @@ SYMBOLS = {
     "nst_level_activation": (C.c_int, [c_void, C.c_int, C.c_int, c_void, c_void]),
     "nst_level_image": (C.c_int, [c_void, C.c_int, c_void, c_void]),
     "nst_gram": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, c_void, c_void]),
+    "nst_guided_gram_backward": (C.c_int, [c_void, c_void, C.c_size_t, C.c_int, C.c_int, c_void, c_void, c_void, c_void, c_void,
+                                            c_void, c_void]),
     "nst_total_variation": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, c_void, c_void]),
     "nst_bicubic_half": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, c_void]),
     "nst_bicubic_half_backward": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, c_void]),

@@ -2,6 +2,7 @@
 from .color_modes import check_preserve_color
 from .pooling_modes import check_pooling
 from .style_modes import check_style_blend, check_style_layer_weights
+from .regions import check_exclusive, check_regions
 
 # jobs that may run at once PER GPU (the reference runs everything on device 0; here the
 # scheduler multiplies this by the number of GPUs of the node). Use 1 when levels_num > 2.
@@ -25,7 +26,7 @@ _DEFAULTS = dict(
 # extension, keyword-only: the feature maps the losses read (neural_style_transfer(..., content_layer=, style_layers=,
 # use_relu=)); None = the reference's content 4 / style [0, 1, 2, 3, 5]; colour preservation (preserve_color=); and the
 # pooling of the feature network (pooling=); further style images with their blend (extra_styles=, style_blend=) and the
-# per-layer style weights (style_layer_weights=).
+# per-layer style weights (style_layer_weights=); and spatial control (content_regions=, style_regions=, region_weights=).
 # Not part of the positional order or the repr.
 _KW_ONLY = dict(
     content_layer=None,            # index 0..5 or a name of Vgg19.layer_names
@@ -36,6 +37,9 @@ _KW_ONLY = dict(
     extra_styles=None,             # further style images (HWC float [0,1]) blended with the pair's style image
     style_blend=None,              # K numbers or a K x 6 array: weight of style k (on map i); K = 1 + len(extra_styles)
     style_layer_weights=None,      # 6 numbers or {map index or name: weight}: the w_l of Gatys et al. 2016
+    content_regions=None,          # integer label map (H,W) or float stack (R,H,W) in [0,1] over the content image (Gatys et al. 2017)
+    style_regions=None,            # the same over the style image: region r of the content takes its style from region r here
+    region_weights=None,           # R numbers >= 0: the lambda_r of the regions' terms (None: ones)
 )
 
 
@@ -62,6 +66,7 @@ class Config:
         check_style_layer_weights(self.style_layer_weights, style_indices=range(6))
         if self.extra_styles is not None or self.style_blend is not None:
             check_style_blend(self.style_blend, 1 + len(self.extra_styles or ()), style_indices=())
+        check_exclusive(check_regions(self.content_regions, self.style_regions, self.region_weights), self.extra_styles)
 
     def __repr__(self):
         return "Config(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in _DEFAULTS) + ")"

@@ -174,9 +174,13 @@ struct GramH2Cfg {
     static constexpr int LDS_BYTES = 2 * BUF_BYTES;            // 72 KiB: two workgroups per CU
 };
 
-template <int TS>
+// GUIDED: the guided Gram sum_p t(p)^2 F(p) F(p)^T - every pixel row is multiplied by t(p) = guide[p] as it is staged.
+// t is in [0,1], so the map's recorded absmax still bounds the operand.  t is read through a buffer descriptor of this
+// split's pixels, as the map is: the pixels of a ragged last group beyond p1 read t = 0 (and F = 0).
+template <int TS, bool GUIDED = false>
 __device__ __forceinline__ void gram_h2_body(const float* __restrict__ f, size_t N, int C, int nsplit, size_t pix_per_split,
-                                             const unsigned* __restrict__ amax, float* __restrict__ part, const int bid) {
+                                             const unsigned* __restrict__ amax, float* __restrict__ part, const int bid,
+                                             const float* __restrict__ guide = nullptr) {
     using G = GramH2Cfg<TS>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_h2[];
     const int tid = threadIdx.x;
@@ -216,8 +220,21 @@ __device__ __forceinline__ void gram_h2_body(const float* __restrict__ f, size_t
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float*>(f) + p0 * (size_t)C, 0, (p0 < p1) ? (unsigned)((p1 - p0) * (size_t)C * 4) : 0u, 0x00020000);
     float st[G::SIDES][G::PER_T][8];
+    __amdgpu_buffer_rsrc_t grsrc = rsrc;
+    if constexpr (GUIDED)
+        grsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(guide) + p0, 0, (p0 < p1) ? (unsigned)((p1 - p0) * 4) : 0u, 0x00020000);
     auto load = [&](int chunk) {
         const unsigned base = (unsigned)((size_t)chunk * G::KP * (size_t)C * 4);
+        float tg[G::PER_T][8];
+        if constexpr (GUIDED) {
+#pragma unroll
+            for (int i = 0; i < G::PER_T; ++i) {
+                const int gg = (tid + i * 256) / TS;
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+                    tg[i][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(grsrc, (unsigned)((gg * 8 + j) * 4), (unsigned)(chunk * G::KP * 4), 0));
+            }
+        }
 #pragma unroll
         for (int sd = 0; sd < G::SIDES; ++sd) {
             if (sd == 1 && diag) break;
@@ -228,8 +245,10 @@ __device__ __forceinline__ void gram_h2_body(const float* __restrict__ f, size_t
                 const int ch = u % TS, gg = u / TS;
                 const unsigned voff = (unsigned)(((gg * 8) * C + cb + ch) * 4);
 #pragma unroll
-                for (int j = 0; j < 8; ++j)
+                for (int j = 0; j < 8; ++j) {
                     st[sd][i][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, voff, base + (unsigned)(j * C * 4), 0));
+                    if constexpr (GUIDED) st[sd][i][j] *= tg[i][j];
+                }
             }
         }
     };
@@ -362,6 +381,21 @@ __global__ __launch_bounds__(256, 2) void gram_h2_batch_kernel(GramBatch b) {
     gram_h2_body<TS>(it.f, it.N, it.C, it.nsplit, it.pix_per_split, it.amax, it.part,
                      (int)blockIdx.x - (i ? b.it[i - 1].part_end : 0));
 }
+// the guided forms (gram_guided.hip has the rest of spatial control): the same bodies with the staged rows scaled by t(p)
+template <int TS>
+__global__ __launch_bounds__(256, 2) void gram_h2_guided_kernel(const float* __restrict__ f, size_t N, int C, int nsplit,
+                                                                size_t pix_per_split, const unsigned* __restrict__ amax,
+                                                                float* __restrict__ part, const float* __restrict__ guide) {
+    gram_h2_body<TS, true>(f, N, C, nsplit, pix_per_split, amax, part, blockIdx.x, guide);
+}
+template <int TS>
+__global__ __launch_bounds__(256, 2) void gram_h2_guided_batch_kernel(GramBatch b) {
+    int i = 0;
+    while (i + 1 < b.n && (int)blockIdx.x >= b.it[i].part_end) ++i;
+    const GramItem& it = b.it[i];
+    gram_h2_body<TS, true>(it.f, it.N, it.C, it.nsplit, it.pix_per_split, it.amax, it.part,
+                           (int)blockIdx.x - (i ? b.it[i - 1].part_end : 0), it.guide);
+}
 
 // generic fallback for channel counts that are not a multiple of 64 (unit-parity API only)
 __global__ void gram_generic_kernel(const float* __restrict__ f, size_t N, int C, float* __restrict__ part) {
@@ -415,13 +449,26 @@ hipError_t gram_init_device() {
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gram_h2_batch_kernel<64>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, GramH2Cfg<64>::LDS_BYTES);
     if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gram_h2_guided_kernel<128>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, GramH2Cfg<128>::LDS_BYTES);
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gram_h2_guided_kernel<64>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, GramH2Cfg<64>::LDS_BYTES);
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gram_h2_guided_batch_kernel<128>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, GramH2Cfg<128>::LDS_BYTES);
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gram_h2_guided_batch_kernel<64>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, GramH2Cfg<64>::LDS_BYTES);
+    if (e != hipSuccess) return e;
     return hipFuncSetAttribute(reinterpret_cast<const void*>(&gram_h2_kernel<64>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, GramH2Cfg<64>::LDS_BYTES);
 }
 
 hipError_t launch_gram_partial(const float* f, size_t N, int C, int nsplit, const unsigned* amax, float* part,
-                               hipStream_t stream) {
+                               hipStream_t stream, const float* guide) {
     const int ts = gram_ts(C);
+    if (guide && (ts == 0 || !amax)) return hipErrorInvalidValue;
     if (ts == 0) {
         hipLaunchKernelGGL(gram_generic_kernel, dim3(C * C), dim3(256), 0, stream, f, N, C, part);
         return hipGetLastError();
@@ -434,7 +481,15 @@ hipError_t launch_gram_partial(const float* f, size_t N, int C, int nsplit, cons
     const size_t pix_per_split = cps * kp;
     // fp16-piece kernel when the absmax record of f is available (32-bit buffer offsets inside one split)
     const bool h2 = amax != nullptr && pix_per_split * (size_t)C * 4 < 0xFFFFFF00ull;
-    if (h2 && ts == 128) {
+    if (guide) {
+        if (!h2) return hipErrorInvalidValue;
+        if (ts == 128)
+            hipLaunchKernelGGL(gram_h2_guided_kernel<128>, dim3(pairs * nsplit), dim3(256), GramH2Cfg<128>::LDS_BYTES, stream, f, N, C,
+                               nsplit, pix_per_split, amax, part, guide);
+        else
+            hipLaunchKernelGGL(gram_h2_guided_kernel<64>, dim3(pairs * nsplit), dim3(256), GramH2Cfg<64>::LDS_BYTES, stream, f, N, C,
+                               nsplit, pix_per_split, amax, part, guide);
+    } else if (h2 && ts == 128) {
         hipLaunchKernelGGL(gram_h2_kernel<128>, dim3(pairs * nsplit), dim3(256), GramH2Cfg<128>::LDS_BYTES, stream, f, N, C,
                            nsplit, pix_per_split, amax, part);
     } else if (h2) {
@@ -619,6 +674,10 @@ static int gram_nsplit_in_batch(const GramBatch& b, int i) {
 // own partial buffer of nsplit x C x C floats).  Fills nsplit / pix_per_split / the block prefixes.
 hipError_t launch_gram_batch(const GramBatch& b0, hipStream_t stream) {
     if (b0.n < 1 || b0.n > NST_GRAM_BATCH_MAX) return hipErrorInvalidValue;
+    // a batch is guided as a whole (every item carries its guidance plane) or not at all
+    const bool guided = b0.it[0].guide != nullptr;
+    for (int i = 0; i < b0.n; ++i)
+        if ((b0.it[i].guide != nullptr) != guided) return hipErrorInvalidValue;
     // partial products: one launch per tile shape
     for (int ts = 128; ts >= 64; ts -= 64) {
         GramBatch b{};
@@ -640,7 +699,9 @@ hipError_t launch_gram_batch(const GramBatch& b0, hipStream_t stream) {
         }
         if (b.n == 0) continue;
         const int blocks = b.it[b.n - 1].part_end;
-        if (ts == 128) hipLaunchKernelGGL(gram_h2_batch_kernel<128>, dim3(blocks), dim3(256), GramH2Cfg<128>::LDS_BYTES, stream, b);
+        if (guided && ts == 128) hipLaunchKernelGGL(gram_h2_guided_batch_kernel<128>, dim3(blocks), dim3(256), GramH2Cfg<128>::LDS_BYTES, stream, b);
+        else if (guided) hipLaunchKernelGGL(gram_h2_guided_batch_kernel<64>, dim3(blocks), dim3(256), GramH2Cfg<64>::LDS_BYTES, stream, b);
+        else if (ts == 128) hipLaunchKernelGGL(gram_h2_batch_kernel<128>, dim3(blocks), dim3(256), GramH2Cfg<128>::LDS_BYTES, stream, b);
         else hipLaunchKernelGGL(gram_h2_batch_kernel<64>, dim3(blocks), dim3(256), GramH2Cfg<64>::LDS_BYTES, stream, b);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;

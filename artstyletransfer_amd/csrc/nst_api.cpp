@@ -82,6 +82,21 @@ int nst_gram(nst_ctx* ctx, const float* f, int C, int h, int w, int normalize, f
     return sc.finish();
 }
 
+int nst_guided_gram_backward(nst_ctx* ctx, const float* f, size_t N, int C, int R, const float* planes, const float* S,
+                             const float* addend, const unsigned* relu_bits, float* out, unsigned* amax_slots, void* stream) {
+    NSTCHK(bind(ctx));
+    if (!f || !planes || !S || !out || N < 1 || C < 64 || C % 64 != 0 || R < 1 || R > NST_MAX_REGIONS)
+        return fail(ctx, NST_E_ARG, "bad argument");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    GuidedBwd gb{};
+    gb.F = f; gb.N = N; gb.C = C; gb.R = R;
+    for (int r = 0; r < R; ++r) { gb.t[r] = planes + (size_t)r * N; gb.S[r] = S + (size_t)r * C * C; }
+    gb.addend = addend; gb.out = out; gb.bits = relu_bits; gb.amax_out = amax_slots;
+    if (amax_slots) HIPCHK(ctx, launch_zero(amax_slots, NST_AMAX_SLOTS, s));
+    HIPCHK(ctx, launch_guided_bwd(gb, s));
+    return NST_OK;
+}
+
 int nst_level_activation(nst_ctx* ctx, int level, int layer, float* out, void* stream) {
     NSTCHK(bind(ctx));
     ++ctx->ws_seq;

@@ -111,6 +111,40 @@ size_t gram_part_offset(const Taps& tp, int h, int w, int k) {
     return off;
 }
 
+// ---- spatial control (include/nst_hip.h has the definitions) -----------------------------------------------------------
+// the guided style term of region r of slot q: divisor C n_r and coef_r, from the mass of the map's scale
+StyleTerm guided_term(const Taps& tp, int q, const ActSet& a, float sw, float w, const Guidance& g, int r) {
+    const int l = tp.style[q], C = kCout[l];
+    const size_t N = (size_t)a.h[l] * a.w[l];
+    const double cn = (double)C * g.mass[kScale[l]][r];
+    return {C, N, cn, (float)((double)sw * (double)w * (double)g.lambda[r] * 4.0 / ((double)tp.nstyle * (double)C * C * cn))};
+}
+// the levels of a closure call are all guided or all unguided (the caller has checked): what the first one is
+bool guided_levels(const nst_ctx* ctx, const int* lv, int n) { return n > 0 && ctx->lv[lv[0]].guide.R > 0; }
+// R, planes and S matrices of style slot q of a guided level: what the backward launch of that map starts from
+GuidedBwd guided_bwd_of(const nst_ctx* ctx, const LevelWs& L, int q) {
+    const int l = ctx->taps.style[q], C = kCout[l];
+    GuidedBwd gb{};
+    gb.R = L.guide.R; gb.C = C; gb.N = (size_t)L.acts.h[l] * L.acts.w[l]; gb.F = L.acts.act[l];
+    for (int r = 0; r < gb.R; ++r) {
+        gb.t[r] = L.guide.plane(kScale[l], r, L.h, L.w);
+        gb.S[r] = L.guide.S[q] + (size_t)r * C * C;
+    }
+    return gb;
+}
+int launch_guided_backward(nst_ctx* ctx, const GuidedBwd& gb, hipStream_t s) {
+    Timer t(ctx, s, K_GRAM, 2.0 * (double)gb.N * gb.C * gb.C * gb.R);
+    HIPCHK(ctx, launch_guided_bwd(gb, s));
+    return NST_OK;
+}
+// one region's sum of (G - Gt)^2 partials per finish block -> the map's, weighted by lambda_r: what the loss row reads
+int guided_fold(nst_ctx* ctx, LevelWs& L, int q, hipStream_t s) {
+    Timer t(ctx, s, K_OTHER, 0);
+    HIPCHK(ctx, launch_guided_fold(L.guide.partial[q], L.guide.R, gram_finish_blocks(kCout[ctx->taps.style[q]]), L.guide.lambda,
+                                   L.style_partial[q], s));
+    return NST_OK;
+}
+
 }  // namespace
 
 namespace nst {
@@ -178,7 +212,11 @@ int backward(nst_ctx* ctx, ActSet& a, const Inject* inj, const ContentJob* cj, f
             Timer t(ctx, s, K_OTHER, 0);
             HIPCHK(ctx, launch_mse_grad(a.act[l], cj->target, cj->n, cj->coef, oth, cj->partial, s));
         }
-        if (inj[l].S) {
+        if (inj[l].guided) {
+            GuidedBwd gb = *inj[l].guided;
+            gb.addend = content ? oth : nullptr; gb.out = cur; gb.mask = top_mask ? a.act[l] : nullptr;
+            NSTCHK(launch_guided_backward(ctx, gb, s));
+        } else if (inj[l].S) {
             // (the content gradient, if any, as the addend of the 1x1 Gram launch)
             ConvParams p{};
             p.in = a.act[l]; p.wt = inj[l].S; p.out = cur; p.mask = top_mask ? a.act[l] : nullptr;
@@ -237,7 +275,13 @@ int backward(nst_ctx* ctx, ActSet& a, const Inject* inj, const ContentJob* cj, f
             } else if (in.direct) {
                 p.addend = in.direct;
             }
-            if (in.S && fuse && (h2 ? in.S_amax != nullptr : in.S_bf != nullptr)) {
+            if (in.guided) {
+                // the guided Gram backward by its own launch, onto the content gradient when there is one: the addend
+                GuidedBwd gb = *in.guided;
+                gb.addend = p.addend; gb.out = oth;
+                NSTCHK(launch_guided_backward(ctx, gb, s));
+                p.addend = oth;
+            } else if (in.S && fuse && (h2 ? in.S_amax != nullptr : in.S_bf != nullptr)) {
                 // Gram backward rides on this launch as a second K source: acc += act[m] * S
                 p.in2 = a.act[m]; p.Cin2 = kCout[m]; p.wt2_bf = in.S_bf;
                 p.wt2_f32 = in.S; p.amax_in2 = amax_act(a, m); p.amax_w2 = in.S_amax;
@@ -366,8 +410,47 @@ int batched_forward(nst_ctx* ctx, const float* const* xi, const int* lv, int n, 
 }
 
 // ---- style losses: Gram matrices, S = d loss / d G folded for the backward
+// guided levels: R items per (level, style map), as many batches as that takes, then the loss partials of every map
+int batched_gram_guided(nst_ctx* ctx, const int* lv, int n, float sw, hipStream_t s) {
+    GramBatch gb{};
+    double flops = 0;
+    auto flush = [&]() -> int {
+        if (gb.n == 0) return NST_OK;
+        Timer t(ctx, s, K_GRAM, flops);
+        HIPCHK(ctx, launch_gram_batch(gb, s));
+        gb = GramBatch{};
+        flops = 0;
+        return NST_OK;
+    };
+    for (int k = 0; k < n; ++k) {
+        LevelWs& L = ctx->lv[lv[k]];
+        const Guidance& g = L.guide;
+        for (int q = 0; q < ctx->taps.nstyle; ++q) {
+            const int l = ctx->taps.style[q];
+            for (int r = 0; r < g.R; ++r) {
+                if (gb.n == NST_GRAM_BATCH_MAX) NSTCHK(flush());
+                const StyleTerm st = guided_term(ctx->taps, q, L.acts, sw, ctx->style_weight(q), g, r);
+                GramItem& it = gb.it[gb.n++];
+                it.f = L.acts.act[l]; it.N = st.N; it.C = st.C; it.amax = amax_act(L.acts, l);
+                it.guide = g.plane(kScale[l], r, L.h, L.w);
+                it.part = g.part + (size_t)r * g.part_floats_r + gram_part_offset(ctx->taps, L.h, L.w, q);
+                it.divisor = (float)st.divisor; it.target = g.gram_t[q] + (size_t)r * st.C * st.C;
+                it.coef = st.coef;
+                it.gram_out = nullptr; it.S = g.S[q] + (size_t)r * st.C * st.C; it.S_bf = nullptr; it.S_amax = nullptr;
+                it.mse_partial = g.partial[q] + (size_t)r * gram_finish_blocks(st.C);
+                flops += 2.0 * (double)st.N * st.C * st.C;
+            }
+        }
+    }
+    NSTCHK(flush());
+    for (int k = 0; k < n; ++k)
+        for (int q = 0; q < ctx->taps.nstyle; ++q) NSTCHK(guided_fold(ctx, ctx->lv[lv[k]], q, s));
+    return NST_OK;
+}
+
 int batched_gram(nst_ctx* ctx, const int* lv, int n, float sw, hipStream_t s, unsigned qmask) {
     const bool h2 = ctx->conv_mode == 2;
+    if (guided_levels(ctx, lv, n)) return qmask ? batched_gram_guided(ctx, lv, n, sw, s) : NST_OK;
     if (h2) {
         // every (level, style layer) pair in two partial launches (one per tile shape) and one finish launch
         const int per = std::max(1, NST_GRAM_BATCH_MAX / ctx->taps.nstyle);      // levels per launch (3 with five style maps)
@@ -435,7 +518,18 @@ int batched_backward(nst_ctx* ctx, const float* const* xi, float* const* gi, con
     };
     if (top_content)
         for (int k = 0; k < n; ++k) NSTCHK(content_grad(k, oth[k]));
-    if (h2 && top_q >= 0) {
+    const bool guided = guided_levels(ctx, lv, n);
+    if (guided && top_q >= 0) {
+        // top of the chain of a guided job: the guided Gram backward of each level, which adds the content gradient (when
+        // the top map is the content map too), applies the ReLU bit-mask (not for the pre-ReLU conv5_1) and records the absmax
+        for (int k = 0; k < n; ++k) {
+            LevelWs& L = ctx->lv[lv[k]];
+            GuidedBwd gb = guided_bwd_of(ctx, L, top_q);
+            gb.addend = top_content ? oth[k] : nullptr; gb.out = cur[k];
+            gb.bits = tp.top_mask() ? L.acts.bits[top] : nullptr; gb.amax_out = amax_grad(L.acts, top);
+            NSTCHK(launch_guided_backward(ctx, gb, s));
+        }
+    } else if (h2 && top_q >= 0) {
         // top of the chain: g(pre-ReLU of the top map) = mask(act * S (+ content gradient)) - the second K source of the
         // fp16 kernel on its own (no 3x3 part), one launch for all levels; its epilogue adds the content gradient (when the
         // top map is the content map too), applies the ReLU mask (not for the pre-ReLU conv5_1) and records the absmax
@@ -458,7 +552,7 @@ int batched_backward(nst_ctx* ctx, const float* const* xi, float* const* gi, con
         Timer t(ctx, s, K_GRAM, flops);
         NSTCHK(launch_conv_batch(ctx, b, t, false));
     }
-    for (int k = 0; k < n && !(h2 && top_q >= 0); ++k) {
+    for (int k = 0; k < n && !((h2 || guided) && top_q >= 0); ++k) {
         LevelWs& L = ctx->lv[lv[k]];
         ActSet& a = L.acts;
         const int l = top;
@@ -494,7 +588,7 @@ int batched_backward(nst_ctx* ctx, const float* const* xi, float* const* gi, con
         // launch multiplies its accumulators by: exact (a power of two), and the second K source - re-expressed in the main
         // source's scale through the same factor - comes out unchanged.  The launch records the absmax of what it stores.
         if (b.unpool && ctx->pool_avg) { b.wt_h2_inv *= 0.25f; b.wt_wino_inv *= 0.25f; }
-        b.Cin2 = (pk < 0 && style_q >= 0) ? kCout[m] : 0;
+        b.Cin2 = (pk < 0 && style_q >= 0 && !guided) ? kCout[m] : 0;      // (a guided job: the addend carries the style gradient)
         double flops = 0;
         for (int k = 0; k < n; ++k) {
             LevelWs& L = ctx->lv[lv[k]];
@@ -507,6 +601,17 @@ int batched_backward(nst_ctx* ctx, const float* const* xi, float* const* gi, con
             if (pk >= 0) continue;
             // a map that is both a style and the content map: the Gram term as the second K source AND the content
             // gradient as the addend of the same launch
+            if (style_q >= 0 && guided) {
+                // the guided Gram backward of the map into oth[k], onto the content gradient when the map is the content
+                // map too; the launch below takes it as its addend and carries no second K source
+                GuidedBwd gb = guided_bwd_of(ctx, L, style_q);
+                if (m == tp.content) { NSTCHK(content_grad(k, oth[k])); gb.addend = oth[k]; }
+                gb.out = oth[k];
+                NSTCHK(launch_guided_backward(ctx, gb, s));
+                im.addend = oth[k];
+                im.bits_in = a.bits[m];
+                continue;
+            }
             if (style_q >= 0) {
                 im.in2 = a.act[m]; im.wt2_bf = L.S_bf[style_q];
                 im.wt2_f32 = L.S[style_q]; im.amax_in2 = amax_act(a, m); im.amax_w2 = amax_S(a, style_q);
@@ -570,7 +675,8 @@ int closure_batched_forward(nst_ctx* ctx, const float* const* xi, unsigned level
     if (n == 0) return NST_OK;
     // (not while a hipGraph is being captured or replayed: the closure then stays on one stream)
     // (the overlap's split of the style maps - relu1_1 .. relu3_1 on the side stream - is the default taps')
-    const bool overlap = ctx->gram_overlap && ctx->conv_mode == 2 && !ctx->use_graph && ctx->side != nullptr && ctx->taps.is_default;
+    const bool overlap = ctx->gram_overlap && ctx->conv_mode == 2 && !ctx->use_graph && ctx->side != nullptr && ctx->taps.is_default &&
+                         !guided_levels(ctx, lv, n);
     NSTCHK(batched_forward(ctx, xi, lv, n, s, nullptr, overlap ? sw : -1.f));
     NSTCHK(batched_gram(ctx, lv, n, sw, s, overlap ? 0x18u : (1u << ctx->taps.nstyle) - 1u));
     if (overlap) HIPCHK(ctx, hipStreamWaitEvent(s, ctx->side_join, 0));
@@ -617,7 +723,28 @@ int closure_per_level(nst_ctx* ctx, const float* const* xi, float* const* gi, in
     }
     NSTCHK(forward(ctx, L.acts, xi[level], L.h, L.w, s, tp.top, ctx->channels));
     Inject inj[NL];
-    for (int k = 0; k < tp.nstyle; ++k) {
+    GuidedBwd gbw[kMaxStyle];
+    for (int k = 0; k < tp.nstyle && L.guide.R > 0; ++k) {
+        // guided: R Gram matrices per map through the one slab workspace, then the map's loss partials
+        const int l = tp.style[k];
+        const Guidance& g = L.guide;
+        for (int r = 0; r < g.R; ++r) {
+            const StyleTerm st = guided_term(tp, k, L.acts, sw, ctx->style_weight(k), g, r);
+            const int ns = gram_nsplit(st.C, st.N);
+            {
+                Timer t(ctx, s, K_GRAM, 2.0 * (double)st.N * st.C * st.C);
+                HIPCHK(ctx, launch_gram_partial(L.acts.act[l], st.N, st.C, ns, amax_act(L.acts, l), g.part, s, g.plane(kScale[l], r, L.h, L.w)));
+            }
+            Timer t(ctx, s, K_OTHER, 0);
+            HIPCHK(ctx, launch_gram_finish(g.part, gram_nslabs(st.C, ns), st.C, (float)st.divisor, g.gram_t[k] + (size_t)r * st.C * st.C, st.coef,
+                                           nullptr, g.S[k] + (size_t)r * st.C * st.C, nullptr, nullptr,
+                                           g.partial[k] + (size_t)r * gram_finish_blocks(st.C), s));
+        }
+        NSTCHK(guided_fold(ctx, L, k, s));
+        gbw[k] = guided_bwd_of(ctx, L, k);
+        inj[l].guided = &gbw[k];
+    }
+    for (int k = 0; k < tp.nstyle && L.guide.R == 0; ++k) {
         const int l = tp.style[k];
         const StyleTerm st = style_term(tp, k, L.acts, sw, ctx->style_weight(k));
         NSTCHK(gram_of(ctx, L.acts.act[l], st.N, st.C, h2 ? amax_act(L.acts, l) : nullptr, (float)st.divisor, L.gram_part, L.gram_t[k], st.coef, nullptr, L.S[k],
@@ -722,6 +849,79 @@ int closure_record(nst_ctx* ctx, const float* x, float cw, float sw, float tvw, 
     return NST_OK;
 }
 
+// the levels of a closure call have their targets: the guided ones those of their R regions (nst_level_set_targets_guided),
+// and they are all guided or all unguided
+int closure_targets_check(nst_ctx* ctx, unsigned level_mask) {
+    int guided = 0, plain = 0;
+    for (int i = 0; i < ctx->levels; ++i) {
+        if (!((level_mask >> i) & 1u)) continue;
+        const LevelWs& L = ctx->lv[i];
+        if (L.guide.R > 0) {
+            ++guided;
+            if (!L.guide.targets || L.guide.targets_R != L.guide.R)
+                return fail(ctx, NST_E_STATE, "guided targets of level " + std::to_string(i) + " not set (nst_level_set_targets_guided)");
+        } else {
+            ++plain;
+            if (!L.targets) return fail(ctx, NST_E_STATE, "targets of level " + std::to_string(i) + " not set");
+        }
+    }
+    if (guided && plain) return fail(ctx, NST_E_STATE, "the levels of one closure are all guided or all unguided (nst_level_set_guidance)");
+    return NST_OK;
+}
+
+// The content target of a level: the content map (default ReLU(conv4_2)) of the content image, through the level's own
+// activation buffers - by the launches the closure of this job will use (one launch per layer, Winograd F(2,3) where it
+// applies), so that target and current features carry the same rounding: an image that IS the content image then has a
+// content loss of (all but) exactly zero, as in the reference, whose target and current features come from one and the
+// same forward code
+int set_content_target(nst_ctx* ctx, int level, const float* content, hipStream_t s) {
+    LevelWs& L = ctx->lv[level];
+    const Taps& tp = ctx->taps;
+    if (batch_eligible(ctx)) {
+        const float* xi[NST_MAX_LEVELS] = {};
+        xi[level] = content;
+        const int lv1 = level;
+        NSTCHK(batched_forward(ctx, xi, &lv1, 1, s, nullptr));
+    } else {
+        NSTCHK(forward(ctx, L.acts, content, L.h, L.w, s, tp.content, ctx->channels));
+    }
+    HIPCHK(ctx, hipMemcpyAsync(L.content_t, L.acts.act[tp.content], L.content_n * 4, hipMemcpyDeviceToDevice, s));
+    return NST_OK;
+}
+
+// The guidance pyramid of (R,h,w) planes (already at dst + off[0]) and its masses: the four pooling steps, the mass of every
+// scale, then a wait for `s` and the read-back.  dscratch: (R GUIDE_MASS_BLOCKS + 5 R) * 2 device doubles.  bad: how many
+// values of the level planes are outside [0,1] or not finite.
+void guidance_offsets(int R, int h, int w, size_t off[6]) {
+    off[0] = 0;
+    for (int sc = 0; sc < 5; ++sc) off[sc + 1] = off[sc] + (size_t)R * (h >> sc) * (w >> sc);
+}
+int build_guidance(nst_ctx* ctx, float* dst, const size_t* off, int R, int h, int w, double* dscratch, double mass[5][NST_MAX_REGIONS],
+                   double* bad, hipStream_t s) {
+    double* out = dscratch + (size_t)R * GUIDE_MASS_BLOCKS * 2;
+    for (int sc = 0; sc < 5; ++sc) {
+        if (sc > 0) HIPCHK(ctx, launch_guide_pool(dst + off[sc - 1], R, h >> (sc - 1), w >> (sc - 1), dst + off[sc], s));
+        HIPCHK(ctx, launch_guide_mass(dst + off[sc], R, (size_t)(h >> sc) * (w >> sc), dscratch, out + (size_t)sc * R * 2, s));
+    }
+    double host[5 * NST_MAX_REGIONS * 2];
+    HIPCHK(ctx, hipMemcpyAsync(host, out, (size_t)5 * R * 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    *bad = 0.0;
+    for (int sc = 0; sc < 5; ++sc)
+        for (int r = 0; r < R; ++r) {
+            mass[sc][r] = host[((size_t)sc * R + r) * 2];
+            if (sc == 0) *bad += host[((size_t)sc * R + r) * 2 + 1];
+        }
+    return NST_OK;
+}
+// every (map in use, region) carries at least one pixel's worth of guidance
+bool guidance_mass_ok(const Taps& tp, const double mass[5][NST_MAX_REGIONS], int R) {
+    for (int q = 0; q < tp.nstyle; ++q)
+        for (int r = 0; r < R; ++r)
+            if (!(mass[kScale[tp.style[q]]][r] >= 1.0)) return false;
+    return true;
+}
+
 int window_check(nst_ctx* ctx, const float* xs, int row0, int rows, int H0) {
     if (ctx->levels != 1) return fail(ctx, NST_E_STATE, "a stripe context is configured with levels_num = 1");
     if (ctx->conv_mode != 2) return fail(ctx, NST_E_STATE, "the stripe closure runs on the f16x2 convolutions (NST_CONV unset)");
@@ -734,6 +934,8 @@ int window_check(nst_ctx* ctx, const float* xs, int row0, int rows, int H0) {
     if (!ctx->unit_style_weights())
         return fail(ctx, NST_E_STATE, "the stripe closure implements unit style layer weights only (nst_job_set_style_weights)");
     LevelWs& L = ctx->lv[0];
+    if (L.guide.R > 0)
+        return fail(ctx, NST_E_STATE, "the stripe closure implements no spatial control (nst_level_set_guidance(ctx, 0, 0, ...) clears it)");
     if (!L.targets) return fail(ctx, NST_E_STATE, "targets of the stripe not set");
     if (!xs) return fail(ctx, NST_E_ARG, "null buffer");
     // boundaries between stripes on multiples of 16 rows (pooling alignment); only a stripe that ends with the stripe
@@ -775,21 +977,11 @@ int nst_level_set_targets_blend(nst_ctx* ctx, int level, const float* content, i
         if (!(sum > 0.0)) return fail(ctx, NST_E_ARG, "every map of the style set needs a positive blend weight of some style image");
         for (int k = 0; k < K; ++k) bhat[k][q] = (float)((double)blend[k * 6 + i] / sum);
     }
+    if (K > 1 && ctx->lv[level].guide.R > 0)
+        return fail(ctx, NST_E_STATE, "a guided level takes one style image (nst_level_set_targets_guided): no blend of several");
     hipStream_t s = enter(ctx, stream);
     LevelWs& L = ctx->lv[level];
-    // content: the content map (default ReLU(conv4_2)) of the content image, through the level's own activation buffers - by the launches the closure
-    // of this job will use (one launch per layer, Winograd F(2,3) where it applies), so that target and current features
-    // carry the same rounding: an image that IS the content image then has a content loss of (all but) exactly zero, as in
-    // the reference, whose target and current features come from one and the same forward code
-    if (batch_eligible(ctx)) {
-        const float* xi[NST_MAX_LEVELS] = {};
-        xi[level] = content;
-        const int lv1 = level;
-        NSTCHK(batched_forward(ctx, xi, &lv1, 1, s, nullptr));
-    } else {
-        NSTCHK(forward(ctx, L.acts, content, L.h, L.w, s, tp.content, ctx->channels));
-    }
-    HIPCHK(ctx, hipMemcpyAsync(L.content_t, L.acts.act[tp.content], L.content_n * 4, hipMemcpyDeviceToDevice, s));
+    NSTCHK(set_content_target(ctx, level, content, s));
     // style: Gt_q = sum_k b^[k][q] G_q(style_k), each image at its own size, in ascending k; the first contributing image
     // writes b^ G, the later ones add to it; an image with b^ = 0 on a map is skipped there, one with b^ = 0 on every map
     // of the set gets no forward pass, and no forward pass goes deeper than the deepest map its image contributes to
@@ -829,6 +1021,169 @@ int nst_level_set_targets(nst_ctx* ctx, int level, const float* content, const f
     return nst_level_set_targets_blend(ctx, level, content, 1, &style, &hs, &ws, ones, stream);
 }
 
+// ---- spatial control (include/nst_hip.h has the definitions) -----------------------------------------------------------
+int nst_level_set_guidance(nst_ctx* ctx, int level, int R, const float* planes, const float* lambda, void* stream) {
+    if (ctx) { ++ctx->closure_epoch; ++ctx->ws_seq; }
+    NSTCHK(bind(ctx));
+    drop_closure_state(ctx, false);
+    if (level < 0 || level >= ctx->levels) return fail(ctx, NST_E_STATE, "level not configured");
+    if (R < 0 || R > NST_MAX_REGIONS) return fail(ctx, NST_E_ARG, "the number of regions must be 0 .. NST_MAX_REGIONS");
+    LevelWs& L = ctx->lv[level];
+    if (R == 0) {                       // (in every arithmetic mode: there is nothing to clear in the others)
+        quiesce(ctx);
+        free_guidance(ctx, L);
+        return NST_OK;
+    }
+    if (ctx->conv_mode != 2) return fail(ctx, NST_E_STATE, "spatial control runs in the f16x2 arithmetic only (NST_CONV unset)");
+    if (!planes) return fail(ctx, NST_E_ARG, "null argument");
+    float lam[NST_MAX_REGIONS] = {1.f, 1.f, 1.f, 1.f};
+    bool positive = lambda == nullptr;
+    for (int r = 0; r < R && lambda; ++r) {
+        if (!(lambda[r] >= 0.f) || std::isinf(lambda[r])) return fail(ctx, NST_E_ARG, "region weights must be finite and >= 0");
+        lam[r] = lambda[r];
+        positive = positive || lambda[r] > 0.f;
+    }
+    if (!positive) return fail(ctx, NST_E_ARG, "at least one region weight must be positive");
+    hipStream_t s = enter(ctx, stream);
+    const Taps& tp = ctx->taps;
+    // the new pyramid and its masses beside what the level has: a refusal leaves the level as it was
+    LevelWs tmp;
+    Guidance& g = tmp.guide;
+    auto refuse = [&](int code, const char* msg) { const int rc = msg ? fail(ctx, code, msg) : code; free_guidance(ctx, tmp); return rc; };
+    auto take = [&](auto** p, size_t count) -> int {
+        const int rc = dev_alloc_t(ctx, p, count);
+        if (rc == NST_OK) g.bytes += std::max<size_t>(count * sizeof(**p), 16);
+        return rc;
+    };
+    size_t off[6];
+    guidance_offsets(R, L.h, L.w, off);
+    g.R = R; g.plane_floats = off[5];
+    for (int sc = 0; sc < 5; ++sc) g.plane_off[sc] = off[sc];
+    for (int r = 0; r < NST_MAX_REGIONS; ++r) g.lambda[r] = lam[r];
+    int rc = take(&g.planes, g.plane_floats);
+    if (rc != NST_OK) return refuse(rc, nullptr);
+    double bad = 0.0;
+    {
+        Scratch sc(ctx, s);
+        double* dscratch = nullptr;
+        rc = sc.alloc(&dscratch, ((size_t)R * GUIDE_MASS_BLOCKS + 5 * R) * 2);
+        if (rc == NST_OK && hipMemcpyAsync(g.planes, planes, (size_t)R * L.h * L.w * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
+            rc = fail(ctx, NST_E_HIP, "hipMemcpyAsync of the guidance planes failed");
+        if (rc == NST_OK) rc = build_guidance(ctx, g.planes, off, R, L.h, L.w, dscratch, g.mass, &bad, s);
+        if (rc == NST_OK) rc = sc.finish();
+        if (rc != NST_OK) return refuse(rc, nullptr);
+    }
+    if (bad > 0.0) return refuse(NST_E_ARG, "guidance values must be finite and in [0,1]");
+    if (!guidance_mass_ok(tp, g.mass, R))
+        return refuse(NST_E_ARG, "a region has a mass sum t^2 below 1 on a map in use: less than one pixel's worth of guidance");
+    Guidance& old = L.guide;
+    if (old.R == R) {
+        // same R: the workspace and the guided targets (which depend on the style side only) stay, the planes change
+        quiesce(ctx);
+        std::swap(old.planes, g.planes);      // (planes of the same size: both byte counts stay)
+        for (int sc = 0; sc < 5; ++sc)
+            for (int r = 0; r < NST_MAX_REGIONS; ++r) old.mass[sc][r] = g.mass[sc][r];
+        for (int r = 0; r < NST_MAX_REGIONS; ++r) old.lambda[r] = g.lambda[r];
+        free_guidance(ctx, tmp);
+        mark(ctx, s);
+        return NST_OK;
+    }
+    g.part_floats_r = gram_part_floats_for(tp, L.h, L.w);
+    rc = take(&g.part, (size_t)R * g.part_floats_r);
+    for (int q = 0; q < tp.nstyle && rc == NST_OK; ++q) {
+        const size_t C = (size_t)kCout[tp.style[q]];
+        rc = take(&g.gram_t[q], (size_t)R * C * C);
+        if (rc == NST_OK) rc = take(&g.S[q], (size_t)R * C * C);
+        if (rc == NST_OK) rc = take(&g.partial[q], (size_t)R * gram_finish_blocks((int)C));
+    }
+    if (rc != NST_OK) return refuse(rc, nullptr);
+    quiesce(ctx);
+    free_guidance(ctx, L);
+    L.guide = g;
+    tmp.guide = Guidance();
+    mark(ctx, s);
+    return NST_OK;
+}
+
+int nst_level_set_targets_guided(nst_ctx* ctx, int level, const float* content, const float* style, int hs, int ws,
+                                 const float* style_planes, void* stream) {
+    if (ctx) { ++ctx->closure_epoch; ++ctx->ws_seq; }
+    NSTCHK(bind(ctx));
+    drop_closure_state(ctx, false);
+    if (level < 0 || level >= ctx->levels) return fail(ctx, NST_E_STATE, "level not configured");
+    LevelWs& L = ctx->lv[level];
+    Guidance& g = L.guide;
+    if (g.R < 1) return fail(ctx, NST_E_STATE, "the level has no guidance (nst_level_set_guidance first)");
+    if (!content || !style || !style_planes) return fail(ctx, NST_E_ARG, "null argument");
+    if (hs < 16 || ws < 16) return fail(ctx, NST_E_ARG, "style image must be at least 16x16");
+    const Taps& tp = ctx->taps;
+    const int R = g.R;
+    hipStream_t s = enter(ctx, stream);
+    Scratch sc(ctx, s);
+    // the style side's pyramid and masses first: a refusal leaves the level's targets as they were
+    size_t off[6];
+    guidance_offsets(R, hs, ws, off);
+    float* sp = nullptr;
+    double* dscratch = nullptr;
+    double smass[5][NST_MAX_REGIONS] = {};
+    double bad = 0.0;
+    NSTCHK(sc.alloc(&sp, off[5]));
+    NSTCHK(sc.alloc(&dscratch, ((size_t)R * GUIDE_MASS_BLOCKS + 5 * R) * 2));
+    HIPCHK(ctx, hipMemcpyAsync(sp, style_planes, (size_t)R * hs * ws * 4, hipMemcpyDeviceToDevice, s));
+    NSTCHK(build_guidance(ctx, sp, off, R, hs, ws, dscratch, smass, &bad, s));
+    if (bad > 0.0) return fail(ctx, NST_E_ARG, "guidance values must be finite and in [0,1]");
+    if (!guidance_mass_ok(tp, smass, R))
+        return fail(ctx, NST_E_ARG, "a style region has a mass sum t^2 below 1 on a map in use: less than one pixel's worth of guidance");
+    g.targets = false;
+    NSTCHK(set_content_target(ctx, level, content, s));
+    float* part = nullptr;
+    NSTCHK(alloc_acts(ctx, sc.acts, hs, ws));
+    NSTCHK(sc.alloc(&part, gram_part_floats_for(tp, hs, ws)));
+    NSTCHK(forward(ctx, sc.acts, style, hs, ws, s, tp.style[tp.nstyle - 1], ctx->channels));
+    for (int q = 0; q < tp.nstyle; ++q) {
+        const int l = tp.style[q], C = kCout[l], scl = kScale[l];
+        const size_t N = (size_t)sc.acts.h[l] * sc.acts.w[l];
+        const int ns = gram_nsplit(C, N);
+        for (int r = 0; r < R; ++r) {
+            {
+                Timer t(ctx, s, K_GRAM, 2.0 * (double)N * C * C);
+                HIPCHK(ctx, launch_gram_partial(sc.acts.act[l], N, C, ns, amax_act(sc.acts, l), part, s, sp + off[scl] + (size_t)r * N));
+            }
+            Timer t(ctx, s, K_OTHER, 0);
+            HIPCHK(ctx, launch_gram_finish_blend(part, gram_nslabs(C, ns), C, (float)((double)C * smass[scl][r]), 1.f, 0,
+                                                 g.gram_t[q] + (size_t)r * C * C, s));
+        }
+    }
+    NSTCHK(sc.finish());
+    g.targets = true; g.targets_R = R;
+    mark(ctx, s);
+    return NST_OK;
+}
+
+int nst_level_guidance(const nst_ctx* ctx, int level, int* R, float* lambda, double* mass) {
+    if (!ctx) return fail(nullptr, NST_E_ARG, "null context");
+    if (level < 0 || level >= ctx->levels) return NST_E_STATE;
+    const Guidance& g = ctx->lv[level].guide;
+    if (R) *R = g.R;
+    for (int r = 0; r < NST_MAX_REGIONS && lambda; ++r) lambda[r] = g.lambda[r];
+    for (int sc = 0; sc < 5 && mass; ++sc)
+        for (int r = 0; r < NST_MAX_REGIONS; ++r) mass[sc * NST_MAX_REGIONS + r] = r < g.R ? g.mass[sc][r] : 0.0;
+    return NST_OK;
+}
+
+int nst_level_guidance_planes(nst_ctx* ctx, int level, int scale, float* out, void* stream) {
+    NSTCHK(bind(ctx));
+    if (level < 0 || level >= ctx->levels) return fail(ctx, NST_E_STATE, "level not configured");
+    const LevelWs& L = ctx->lv[level];
+    if (L.guide.R < 1) return fail(ctx, NST_E_STATE, "the level has no guidance");
+    if (scale < 0 || scale > 4 || !out) return fail(ctx, NST_E_ARG, "scale must be 0 .. 4 and out not null");
+    hipStream_t s = enter(ctx, stream);
+    HIPCHK(ctx, hipMemcpyAsync(out, L.guide.planes + L.guide.plane_off[scale],
+                               (size_t)L.guide.R * (L.h >> scale) * (L.w >> scale) * 4, hipMemcpyDeviceToDevice, s));
+    mark(ctx, s);
+    return NST_OK;
+}
+
 int nst_closure(nst_ctx* ctx, const float* x, float cw, float sw, float tvw, float* grad, float* losses, void* stream) {
     return nst_closure_levels(ctx, x, cw, sw, tvw, 0xFFFFFFFFu, grad, losses, stream);
 }
@@ -839,9 +1194,7 @@ int nst_closure_levels(nst_ctx* ctx, const float* x, float cw, float sw, float t
     ++ctx->ws_seq;
     if (ctx->levels < 1) return fail(ctx, NST_E_STATE, "nst_job_configure has not been called");
     if (!x || !grad || !losses) return fail(ctx, NST_E_ARG, "null buffer");
-    for (int i = 0; i < ctx->levels; ++i)
-        if (((level_mask >> i) & 1u) && !ctx->lv[i].targets)
-            return fail(ctx, NST_E_STATE, "targets of level " + std::to_string(i) + " not set");
+    NSTCHK(closure_targets_check(ctx, level_mask));
     hipStream_t main = enter(ctx, stream);
     if (ctx->timing >= 2) NSTCHK(fold_timed(ctx));
     ctx->timed.clear();
@@ -896,9 +1249,7 @@ int nst_closure_forward(nst_ctx* ctx, const float* x, float cw, float sw, float 
     ctx->fwd_token.valid = false;
     if (ctx->levels < 1) return fail(ctx, NST_E_STATE, "nst_job_configure has not been called");
     if (!x || !losses) return fail(ctx, NST_E_ARG, "null buffer");
-    for (int i = 0; i < ctx->levels; ++i)
-        if (((level_mask >> i) & 1u) && !ctx->lv[i].targets)
-            return fail(ctx, NST_E_STATE, "targets of level " + std::to_string(i) + " not set");
+    NSTCHK(closure_targets_check(ctx, level_mask));
     if (!batch_eligible(ctx) || ctx->use_graph)
         return fail(ctx, NST_E_UNAVAILABLE, "the closure halves run on the batched schedule without a hipGraph only: use nst_closure");
     hipStream_t main = enter(ctx, stream);

@@ -317,6 +317,7 @@ int alloc_level_image(nst_ctx* ctx, LevelWs& L) {
 }
 
 void free_level(nst_ctx* ctx, LevelWs& L) {
+    free_guidance(ctx, L);
     free_acts(ctx, L.acts);
     dev_free(L.gbuf[0]); dev_free(L.gbuf[1]); dev_free(L.xl); dev_free(L.gxl);
     free_tap_buffers(ctx, L);
@@ -329,6 +330,22 @@ void free_level(nst_ctx* ctx, LevelWs& L) {
 }  // namespace
 
 namespace nst {
+
+void free_guidance(nst_ctx* ctx, LevelWs& L) {
+    Guidance& g = L.guide;
+    dev_free(g.planes); dev_free(g.part);
+    for (int k = 0; k < kMaxStyle; ++k) { dev_free(g.gram_t[k]); dev_free(g.S[k]); dev_free(g.partial[k]); }
+    if (ctx->bytes >= g.bytes) ctx->bytes -= g.bytes;
+    g = Guidance();
+}
+
+// What a closure remembered is void once the job changes: the captured graph and the keys it was captured under, and
+// (drop_targets) every level's targets
+void drop_closure_state(nst_ctx* ctx, bool drop_targets) {
+    if (ctx->gexec) { (void)hipGraphExecDestroy(ctx->gexec); ctx->gexec = nullptr; }
+    ctx->gkey = {}; ctx->glast = {};
+    for (int i = 0; drop_targets && i < ctx->levels; ++i) { ctx->lv[i].targets = false; ctx->lv[i].guide.targets = false; }
+}
 
 // folds the event pairs of the previous closure into the accumulators (waits for them to complete)
 int fold_timed(nst_ctx* ctx) {
@@ -400,14 +417,6 @@ int env_flag(const char* name, int dflt) {
     const char* e = getenv(name);
     if (!e || !e[0]) return dflt;
     return std::atoi(e);
-}
-
-// What a closure remembered is void once the job changes: the captured graph and the keys it was captured under, and
-// (drop_targets) every level's targets
-void drop_closure_state(nst_ctx* ctx, bool drop_targets) {
-    if (ctx->gexec) { (void)hipGraphExecDestroy(ctx->gexec); ctx->gexec = nullptr; }
-    ctx->gkey = {}; ctx->glast = {};
-    for (int i = 0; drop_targets && i < ctx->levels; ++i) ctx->lv[i].targets = false;
 }
 
 // bit i = map i has a positive style layer weight
@@ -661,6 +670,7 @@ int nst_job_set_taps(nst_ctx* ctx, int content_index, unsigned style_mask, int u
     ctx->taps = tp;
     for (int i = 0; i < ctx->levels; ++i) {
         LevelWs& L = ctx->lv[i];
+        free_guidance(ctx, L);          // (sized for the old style set: nst_level_set_guidance again)
         free_tap_buffers(ctx, L);
         NSTCHK(alloc_tap_buffers(ctx, L));
     }

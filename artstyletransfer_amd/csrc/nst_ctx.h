@@ -88,8 +88,30 @@ enum KClass { K_CONV3 = 0, K_GRAM = 1, K_CONV1 = 2, K_OTHER = 3, K_NCLASS = 4 };
 // decided for this launch (rows = 0: another kernel ran)
 struct TimedLaunch { hipEvent_t a, b; int cls; double flops; int tag[6]; double mfma_factor; H2Shape shape; };
 
+// Spatial control of one level (nst_level_set_guidance; include/nst_hip.h has the definitions).  Everything here is made
+// when guidance is set and freed when it is cleared, the taps change or the job is configured again: a closure allocates
+// nothing.  Region r of style slot q: gram_t[q] + r C^2, S[q] + r C^2, partial[q] + r gram_finish_blocks(C).
+struct Guidance {
+    int R = 0;                          // 0: the level is not guided
+    float lambda[NST_MAX_REGIONS] = {1.f, 1.f, 1.f, 1.f};
+    float* planes = nullptr;            // the guidance pyramid: scale s at plane_off[s], (R, h >> s, w >> s)
+    size_t plane_off[5] = {};
+    size_t plane_floats = 0;
+    double mass[5][NST_MAX_REGIONS] = {};   // n_r of every scale (host copy: the divisors and coefficients are made from it)
+    float* gram_t[kMaxStyle] = {};      // guided targets (nst_level_set_targets_guided)
+    float* S[kMaxStyle] = {};
+    double* partial[kMaxStyle] = {};
+    float* part = nullptr;              // partial-Gram slabs: region r at r * part_floats_r
+    size_t part_floats_r = 0;
+    bool targets = false;               // gram_t holds the targets of targets_R regions
+    int targets_R = 0;
+    size_t bytes = 0;
+    const float* plane(int scale, int r, int h, int w) const { return planes + plane_off[scale] + (size_t)r * (h >> scale) * (w >> scale); }
+};
+
 struct LevelWs {
     int h = 0, w = 0;
+    Guidance guide;
     ActSet acts;
     float* gbuf[2] = {};
     size_t gbuf_floats = 0;
@@ -258,6 +280,9 @@ inline void dev_free(void* p) { if (p) (void)hipFree(p); }
 int alloc_acts(nst_ctx* ctx, ActSet& a, int h, int w);
 void free_acts(nst_ctx* ctx, ActSet& a);
 int bind(nst_ctx* ctx);                            // null check + hipSetDevice: first line of every entry point
+// what a closure remembered is void once the job changes (captured graph; drop_targets: every level's targets)
+void drop_closure_state(nst_ctx* ctx, bool drop_targets);
+void free_guidance(nst_ctx* ctx, LevelWs& L);      // the level is unguided afterwards
 hipStream_t enter(nst_ctx* ctx, void* stream);     // orders the caller's stream after the context's tail event
 void mark(nst_ctx* ctx, hipStream_t s);            // records the tail event
 void quiesce(nst_ctx* ctx);                        // waits until nothing on the device uses the context's memory
@@ -295,6 +320,7 @@ struct Inject {
     const unsigned* S_amax = nullptr; // absmax record of S (conv_h2), if available
     const float* direct = nullptr;   // or a ready NHWC gradient
     bool content = false;            // or the content MSE gradient (closure only)
+    const GuidedBwd* guided = nullptr; // guided Gram backward (R, t, S filled in): dF = sum_r t_r^2 F S_r, by a launch of its own
 };
 struct ContentJob { const float* target; size_t n; float coef; double* partial; };
 // channels = 1: x is a luminance plane u, conv1_1 sees x_c = u - mean_c (nst_job_set_color)

@@ -230,8 +230,10 @@ hipError_t launch_loss_assemble(const LossAssembly& la, hipStream_t stream);
 hipError_t gram_init_device();
 int gram_nsplit(int C, size_t N);
 // amax (nullable): NST_AMAX_SLOTS-word absmax record of f -> the fp16-piece kernel (3 MFMAs per product block)
+// guide (nullable): the guided Gram sum_p t(p)^2 F(p) F(p)^T - every staged pixel row is scaled by t(p) in [0,1] (so the
+// map's absmax still bounds the operand); the fp16-piece kernels only (amax required, C = 64 or a multiple of 128)
 hipError_t launch_gram_partial(const float* f, size_t N, int C, int nsplit, const unsigned* amax, float* part,
-                               hipStream_t stream);
+                               hipStream_t stream, const float* guide = nullptr);
 // G = (sum_s part[s]) / divisor (fixed order).  If target: mse_out[0] = sum((G-Gt)^2) (double) and
 // S = coef * (G - Gt) (C x C, for the backward 1x1 conv).  gram_out / target / S / mse_partial nullable;
 // mse_partial: gram_finish_blocks(C) doubles.  `nslabs` = gram_nslabs(C, nsplit).
@@ -244,6 +246,7 @@ struct GramItem {
     float divisor; const float* target; float coef; float* gram_out; float* S; unsigned short* S_bf; unsigned* S_amax;
     double* mse_partial;
     int nsplit; size_t pix_per_split; int part_end, finish_end;     // filled by the launcher
+    const float* guide;   // guided Gram (gram_guided.hip): t(p) of the N pixels, the staged pixel row is scaled by it; nullptr: plain
 };
 struct GramBatch { GramItem it[NST_GRAM_BATCH_MAX]; int n; };
 hipError_t launch_gram_batch(const GramBatch& b, hipStream_t stream);
@@ -258,6 +261,30 @@ hipError_t launch_gram_finish(const float* part, int nslabs, int C, float diviso
 // != 0), product and sum each rounded to fp32.  alpha = 1 without accumulation writes the bits launch_gram_finish writes.
 hipError_t launch_gram_finish_blend(const float* part, int nslabs, int C, float divisor, float alpha, int accumulate,
                                     float* gram_out, hipStream_t stream);
+
+// gram_guided.hip: spatial control (guided Gram matrices; include/nst_hip.h has the definitions) ---------------------
+constexpr int NST_MAX_REGIONS_K = 4;
+constexpr int GUIDE_MASS_BLOCKS = 64;
+// one step of the guidance pyramid: out (R,H/2,W/2) = the 2x2/2 mean of in (R,H,W), ((e00 + e01) + e10) + e11 times 1/4
+hipError_t launch_guide_pool(const float* in, int R, int H, int W, float* out, hipStream_t stream);
+// out[r * 2] = sum_p t_r(p)^2 over the n values of plane r (double, two ordered stages), out[r * 2 + 1] = how many of them
+// are not in [0,1] (NaN included); scratch: R * GUIDE_MASS_BLOCKS * 2 doubles
+hipError_t launch_guide_mass(const float* t, int R, size_t n, double* scratch, double* out, hipStream_t stream);
+// out[b] = sum_r lambda[r] * part[r * blocks + b] (double): the (G - Gt)^2 partials of a guided map's R regions as one set
+hipError_t launch_guided_fold(const double* part, int R, int blocks, const float* lambda, double* out, hipStream_t stream);
+// Guided Gram backward: out[p][c] = addend[p][c] + sum_r t_r(p)^2 sum_k F[p][k] S_r[k][c] on the fp32 MFMA, then the
+// optional ReLU mask (bits: [N][C/32] words, bit = channel & 31; else mask: out = mask > 0 ? v : 0) and absmax record
+struct GuidedBwd {
+    const float* F; size_t N; int C; int R;
+    const float* t[NST_MAX_REGIONS_K];      // N floats each
+    const float* S[NST_MAX_REGIONS_K];      // C x C each
+    const float* addend;                    // nullable, may alias out
+    float* out;
+    const unsigned* bits;
+    const float* mask;
+    unsigned* amax_out;                     // nullable: NST_AMAX_SLOTS words (atomic max; zeroed beforehand)
+};
+hipError_t launch_guided_bwd(const GuidedBwd& g, hipStream_t stream);
 
 // image_ops.hip: job set-up on the device (pyramid resize, structured-noise initial image) ---------------------
 hipError_t launch_resize_hwc(const float* src, int h, int w, int C, float* dst, int oh, int ow, hipStream_t stream);

@@ -12,6 +12,7 @@ from . import _lib
 from . import taps as _taps
 from .pooling_modes import check_pooling
 from . import style_modes as _style
+from . import regions as _regions
 from ._lib import NST_LOSS_ROW, NstError, StepInfo
 
 TAP_CHANNELS = (64, 128, 256, 512, 512, 512)
@@ -217,6 +218,74 @@ class StyleEngine:
         flat = (C.c_float * (k * _style.NUM_MAPS))(*[v for row in rows for v in row])
         _lib.check(self.ctx, self.lib.nst_level_set_targets_blend(self.ctx, level, _ptr(content), k, ptrs, hs, ws, flat,
                                                                   _stream(self.device)), "nst_level_set_targets_blend")
+
+    # ---- spatial control (nst_level_set_guidance; regions.py is the host side) ---------------------------
+    def set_guidance(self, level: int, planes: Optional[torch.Tensor], weights=None) -> None:
+        """Guidance planes of one level (nst_level_set_guidance): a device (R,h,w) float32 tensor in [0,1] of the level's
+        size, 1 <= R <= 4, and R region weights >= 0 (None: ones).  planes = None clears the level's guidance.  The
+        guided targets of another R become invalid: set_targets_guided again.  ValueError for weights that do not fit;
+        NstError (NST_E_ARG) for values outside [0,1] or a region with a mass below 1 on a map in use, (NST_E_STATE) in
+        the bf16x3 / f32 arithmetic."""
+        if planes is None:
+            _lib.check(self.ctx, self.lib.nst_level_set_guidance(self.ctx, level, 0, None, None, _stream(self.device)),
+                       "nst_level_set_guidance")
+            return
+        h, w = self.level_shape(level)
+        if planes.dim() != 3 or tuple(planes.shape[1:]) != (h, w):
+            raise NstError(f"guidance planes of level {level} must have shape (R,{h},{w}), got {tuple(planes.shape)}")
+        r = planes.shape[0]
+        lam = None
+        if weights is not None:
+            lam = (C.c_float * max(r, 1))(*_regions.check_region_weights(weights, r))
+        planes = planes.contiguous()
+        _chk_dev(planes, self.device)
+        _lib.check(self.ctx, self.lib.nst_level_set_guidance(self.ctx, level, r, _ptr(planes), lam, _stream(self.device)),
+                   "nst_level_set_guidance")
+
+    def clear_guidance(self) -> None:
+        """No guidance on any configured level."""
+        for level in range(self.levels):
+            self.set_guidance(level, None)
+
+    def set_targets_guided(self, level: int, content: torch.Tensor, style: torch.Tensor, style_planes: torch.Tensor) -> None:
+        """The level's content target and the guided Gram targets of the R regions of its guidance
+        (nst_level_set_targets_guided): style_planes is a device (R,hs,ws) float32 tensor in [0,1] of the style image's
+        size.  set_guidance first."""
+        h, w = self.level_shape(level)
+        ch = self.channels
+        if content.numel() != ch * h * w or style.numel() != ch * style.shape[-2] * style.shape[-1]:
+            raise NstError(f"targets must have {ch} channel(s) in this colour mode")
+        content = content.contiguous().reshape(ch, h, w)
+        _chk_dev(content, self.device)
+        style = style.contiguous().reshape(ch, style.shape[-2], style.shape[-1])
+        _chk_dev(style, self.device)
+        r = self.guidance(level)[0]
+        if style_planes.dim() != 3 or tuple(style_planes.shape) != (r, style.shape[1], style.shape[2]):
+            raise NstError(f"style planes must have shape ({r},{style.shape[1]},{style.shape[2]}), got {tuple(style_planes.shape)}")
+        style_planes = style_planes.contiguous()
+        _chk_dev(style_planes, self.device)
+        _lib.check(self.ctx, self.lib.nst_level_set_targets_guided(self.ctx, level, _ptr(content), _ptr(style), style.shape[1],
+                                                                   style.shape[2], _ptr(style_planes), _stream(self.device)),
+                   "nst_level_set_targets_guided")
+
+    def guidance(self, level: int):
+        """(R, region weights (R,), masses (5,R) float64: n_r of the five network scales) of a level (nst_level_guidance);
+        R = 0: the level is not guided."""
+        r = C.c_int()
+        lam = (C.c_float * _regions.MAX_REGIONS)()
+        mass = (C.c_double * (_regions.NUM_SCALES * _regions.MAX_REGIONS))()
+        _lib.check(self.ctx, self.lib.nst_level_guidance(self.ctx, level, C.byref(r), lam, mass), "nst_level_guidance")
+        m = np.array(list(mass), dtype=np.float64).reshape(_regions.NUM_SCALES, _regions.MAX_REGIONS)
+        return r.value, tuple(float(v) for v in lam[:r.value]), m[:, :r.value].copy()
+
+    def guidance_planes(self, level: int, scale: int) -> torch.Tensor:
+        """The (R, h >> scale, w >> scale) guidance of one network scale of a guided level (nst_level_guidance_planes)."""
+        h, w = self.level_shape(level)
+        r = self.guidance(level)[0]
+        out = torch.empty((r, h >> scale, w >> scale), dtype=torch.float32, device=self.device)
+        _lib.check(self.ctx, self.lib.nst_level_guidance_planes(self.ctx, level, scale, _ptr(out), _stream(self.device)),
+                   "nst_level_guidance_planes")
+        return out
 
     def closure(self, x: torch.Tensor, cw: float, sw: float, tvw: float,
                 grad: Optional[torch.Tensor] = None, losses: Optional[torch.Tensor] = None):
@@ -458,6 +527,31 @@ class StyleEngine:
         _lib.check(self.ctx, self.lib.nst_gram(self.ctx, _ptr(f), c, h, w, int(normalize), _ptr(g),
                                                _stream(self.device)), "nst_gram")
         return g
+
+    def guided_gram_backward(self, f: torch.Tensor, planes: torch.Tensor, s_mats: torch.Tensor, addend: Optional[torch.Tensor] = None,
+                             relu_bits: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, want_absmax: bool = False):
+        """The guided Gram backward launch on its own (nst_guided_gram_backward): out (N,C) = addend + sum_r t_r^2 . f . S_r for
+        f (N,C), planes (R,N), s_mats (R,C,C), all float32 on the device; relu_bits (N, C/32) int32 words zero the outputs
+        whose bit is clear; `out` may be `addend` itself.  Returns out, or (out, max |out| as a device scalar)."""
+        n, c = f.shape
+        r = planes.shape[0]
+        if tuple(planes.shape) != (r, n) or tuple(s_mats.shape) != (r, c, c):
+            raise NstError("planes must be (R,N) and s_mats (R,C,C)")
+        if out is None:
+            out = torch.empty((n, c), dtype=torch.float32, device=self.device)
+        slots = torch.empty(64, dtype=torch.int32, device=self.device) if want_absmax else None
+        for t in (f, planes, s_mats, addend, out):
+            if t is not None:
+                _chk_dev(t, self.device)
+        if relu_bits is not None and not (relu_bits.is_cuda and relu_bits.dtype == torch.int32 and relu_bits.is_contiguous()
+                                          and tuple(relu_bits.shape) == (n, c // 32)):
+            raise NstError(f"relu_bits must be a contiguous int32 CUDA tensor of shape ({n},{c // 32})")
+        if (addend is not None and addend.shape != f.shape) or out.shape != f.shape:
+            raise NstError("addend and out must have the shape of f")
+        _lib.check(self.ctx, self.lib.nst_guided_gram_backward(self.ctx, _ptr(f), n, c, r, _ptr(planes), _ptr(s_mats), _ptr(addend),
+                                                               _ptr(relu_bits), _ptr(out), _ptr(slots), _stream(self.device)),
+                   "nst_guided_gram_backward")
+        return (out, slots.view(torch.float32).max()) if want_absmax else out
 
     def total_variation(self, y: torch.Tensor, want_grad: bool = False):
         _chk_dev(y, self.device)
@@ -705,6 +799,8 @@ class PixelOptimizer:
         elif dist_mod is None:
             import torch.distributed as dist_mod
         e = self.engine
+        if any(e.guidance(l)[0] for l in range(e.levels)):
+            raise ValueError("content_regions / style_regions cannot be combined with stripe sharding")
         if e.layer_weights != _style.UNIT_WEIGHTS:
             raise ValueError("the stripe closure implements unit style layer weights only (reset_style_weights())")
         contents = list(content_t) if isinstance(content_t, (list, tuple)) else [content_t]

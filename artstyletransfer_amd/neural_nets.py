@@ -125,6 +125,7 @@ def return_engine(eng: StyleEngine) -> None:
         keep = len(pool) < _IDLE_MAX and _weights_cache is not None and getattr(eng, "weights_id", None) == id(_weights_cache)
     if keep:
         try:
+            eng.clear_guidance()               # (no region guidance: the re-configuration below drops it with the levels too)
             eng.release_job()                  # the workspace goes back now, only the weights stay resident
             eng.reset_style_weights()          # (before the taps: a style set needs a map with a positive weight)
             eng.reset_taps()

@@ -22,6 +22,7 @@ from .engine import PixelOptimizer, StyleEngine
 from .neural_nets import lease_engine, return_engine, shared_engine
 from .pooling_modes import check_pooling
 from . import style_modes as _style
+from . import regions as _regions
 
 # ImageNet statistics (reference :22-23)
 IMAGENET_MEAN_255 = [123.675, 116.28, 103.53]
@@ -117,7 +118,7 @@ class _DeviceJob:
     (`_make_job`, tests/test_host_api.py)."""
 
     def __init__(self, device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, taps=None, color=None,
-                 pooling=None, style_weights=None, blend=None):
+                 pooling=None, style_weights=None, blend=None, regions=None):
         self.dev = dev = device
         self.optimizer = None
         self.luminance = color == "luminance"   # the optimised image is u = 255 Y; the yield puts the content's I, Q back
@@ -169,7 +170,11 @@ class _DeviceJob:
                 for lvl, (c_img, s_img) in enumerate(zip(content_imgs, style_imgs)):
                     if tuple(c_img.shape[:2]) != engine.level_shape(lvl):
                         raise ValueError(f"content level {lvl} is {tuple(c_img.shape[:2])}, expected {engine.level_shape(lvl)}")
-                    if blend is None:
+                    if regions is not None:
+                        # regions = (per-level content planes, per-level style planes, region weights), host float32 stacks
+                        engine.set_guidance(lvl, torch.from_numpy(regions[0][lvl]).to(dev), regions[2])
+                        engine.set_targets_guided(lvl, content_t(c_img), style_t(s_img), torch.from_numpy(regions[1][lvl]).to(dev))
+                    elif blend is None:
                         engine.set_targets(lvl, content_t(c_img), style_t(s_img))
                     else:
                         engine.set_targets_blend(lvl, content_t(c_img), [style_t(lv[lvl], k) for k, lv in enumerate(all_styles)],
@@ -223,9 +228,9 @@ class _DeviceJob:
 
 
 def _make_job(device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, taps=None, color=None, pooling=None,
-              style_weights=None, blend=None):
+              style_weights=None, blend=None, regions=None):
     return _DeviceJob(device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, taps, color, pooling,
-                      style_weights, blend)
+                      style_weights, blend, regions)
 
 
 async def _drain(step_future):
@@ -261,6 +266,7 @@ class NeuralStyleTransfer:
         self.__pooling = "max"                   # set_pooling
         self.__layer_weights = None              # set_style_layer_weights (None: w = 1 on every map)
         self.__blend = None                      # set_style_blend: (extra style levels, blend as given)
+        self.__regions = None                    # set_regions: (content stack, style stack, region weights)
 
     def set_feature_maps(self, content_layer=None, style_layers=None, use_relu=True):
         """Extension: the feature maps the losses of the next `process` read - a content map and a set of style maps of
@@ -312,6 +318,16 @@ class NeuralStyleTransfer:
         _style.check_style_blend(blend, 1 + len(extra), style_indices=())
         self.__blend = ([list(lv) for lv in extra], blend)
 
+    def set_regions(self, content_regions=None, style_regions=None, region_weights=None):
+        """Extension: spatial control (Gatys et al. 2017, guided Gram matrices) in the next `process`: region r of the
+        content image takes its style from region r of the style image.  Each argument is an integer label map (H,W) with
+        labels 0..R-1 or a float stack (R,H,W) in [0,1], at any resolution (it is resized to every pyramid level of its
+        image, nearest neighbour); R <= 4; regions may overlap and need not cover the image.  `region_weights`: R numbers
+        >= 0, the weight of each region's term (None: ones).  None, None: no guidance.  ValueError for one of the two
+        without the other, mismatched R, values outside [0,1], and - in `process`, where the level sizes are known - a
+        region with a mass sum t^2 below 1 on a map of the style set, or guidance together with a style blend."""
+        self.__regions = _regions.check_regions(content_regions, style_regions, region_weights)
+
     async def process(self, content_imgs, init_img, lr_start, iters_num, content_weight, style_weight, tv_weight,
                       init_img_name):
         # validates the model name exactly as the reference does (ValueError for anything but vgg19)
@@ -331,6 +347,13 @@ class NeuralStyleTransfer:
                     raise ValueError(f"an extra style has {len(lv)} levels, the job has {len(self.__style_imgs)}")
             blend = (self.__blend[0], _style.check_style_blend(self.__blend[1], 1 + len(self.__blend[0]), style_indices=style_set))
         style_imgs = self.__style_imgs
+        regions = None
+        if self.__regions is not None:
+            # resized to every level of the content and of the style pyramid and checked for their masses, on the host
+            _regions.check_exclusive(self.__regions, blend[0] if blend is not None else None)
+            c_stack, s_stack, lam = self.__regions
+            regions = (_regions.level_planes(c_stack, [tuple(c.shape[:2]) for c in content_imgs], style_set, "content_regions"),
+                       _regions.level_planes(s_stack, [tuple(s.shape[:2]) for s in style_imgs], style_set, "style_regions"), lam)
         if self.__color == "histogram":
             # every style's levels recoloured with its own statistics (those of its top level)
             setup = shared_engine(self.__device)
@@ -354,6 +377,8 @@ class NeuralStyleTransfer:
             extra["style_weights"] = layer_weights
         if blend is not None:
             extra["blend"] = blend
+        if regions is not None:
+            extra["regions"] = regions
         job = _make_job(self.__device, self.__optimizer_name, style_imgs, content_imgs, init_img, lr_start, **extra)
         cw, sw, tvw = float(content_weight), float(style_weight), float(tv_weight)
         loop = asyncio.get_running_loop()
@@ -410,7 +435,8 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
                                 iters_num, levels_num, noise_factor, noise_levels, noise_levels_central_amplitude,
                                 noise_levels_peripheral_amplitude, noise_levels_dispersion, device=None, *,
                                 content_layer=None, style_layers=None, use_relu=True, preserve_color=None,
-                                pooling="max", extra_styles=None, style_blend=None, style_layer_weights=None):
+                                pooling="max", extra_styles=None, style_blend=None, style_layer_weights=None,
+                                content_regions=None, style_regions=None, region_weights=None):
     """Async generator yielding (percent, HWC float32 image) after every optimiser step
     (reference :229-372). `device` (extension): the GPU to run on; default = current.  `content_layer`,
     `style_layers`, `use_relu` (extension): the feature maps the losses read, see NeuralStyleTransfer.set_feature_maps
@@ -422,7 +448,9 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
     "style" initial image - by `style_blend`: K numbers or a K x 6 array, see NeuralStyleTransfer.set_style_blend (None: an
     even blend).  `style_layer_weights` (extension): see NeuralStyleTransfer.set_style_layer_weights.  Under
     preserve_color="histogram" every style's levels are recoloured with its own statistics, under "luminance" every
-    style's luminance is matched to the content's on its own.  They are validated before any GPU work."""
+    style's luminance is matched to the content's on its own.  `content_regions`, `style_regions`, `region_weights`
+    (extension): spatial control, see NeuralStyleTransfer.set_regions; not with `extra_styles`.  They are validated before
+    any GPU work (the masses of the regions on every level included: the level sizes follow from the image sizes)."""
     taps = _taps.normalize_taps(content_layer, style_layers, use_relu)
     host_image.check_preserve_color(preserve_color)
     check_pooling(pooling)
@@ -430,6 +458,14 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
     layer_weights = _style.check_style_layer_weights(style_layer_weights, style_indices=taps[1], use_relu=use_relu)
     if extra_styles or style_blend is not None:
         style_blend = _style.check_style_blend(style_blend, 1 + len(extra_styles), style_indices=taps[1])
+    regions = _regions.check_regions(content_regions, style_regions, region_weights)
+    _regions.check_exclusive(regions, extra_styles)
+    if regions is not None:
+        for stack, img, what in ((regions[0], content_n_style.content[1], "content_regions"),
+                                 (regions[1], content_n_style.style[1], "style_regions")):
+            ih, iw = np.shape(img)[:2]
+            shapes = [host_image.level_size(ih, iw, lvl) for lvl in range(max(levels_num - 1, 0), -1, -1)]
+            _regions.level_planes(stack, shapes, taps[1], what)
     for img in extra_styles:
         if np.ndim(img) != 3 or np.shape(img)[2] != 3:
             raise ValueError(f"extra_styles: expected HWC images with 3 channels, got shape {np.shape(img)}")
@@ -465,6 +501,8 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
     nst.set_pooling(pooling)
     nst.set_style_layer_weights(layer_weights)
     nst.set_style_blend(extra_levels, style_blend if extra_levels else None)
+    if regions is not None:
+        nst.set_regions(regions[0], regions[1], regions[2])
     lr_start = 10.0
     async for img, cur_iter in nst.process(content_levels, init_img, lr_start, iters_num, content_weight,
                                            style_weight, tv_weight, init_name):

@@ -67,7 +67,8 @@ class Task:
                                                    ("preserve_color", None), ("pooling", "max"))
                 if getattr(cfg, k, dflt) != dflt}
         # (images and arrays: `is not None`, not `!=`)
-        extensions.update({k: getattr(cfg, k) for k in ("extra_styles", "style_blend", "style_layer_weights")
+        extensions.update({k: getattr(cfg, k) for k in ("extra_styles", "style_blend", "style_layer_weights", "content_regions",
+                                                        "style_regions", "region_weights")
                            if getattr(cfg, k, None) is not None})
         gpu = await self.__slots.acquire()
         self.gpu = gpu

@@ -41,6 +41,7 @@ extern "C" {
 #define NST_MAX_LEVELS 8
 #define NST_LOSS_ROW 4      /* per level: total, content, style, tv */
 #define NST_MAX_STYLES 8    /* style images one level's targets may blend (nst_level_set_targets_blend) */
+#define NST_MAX_REGIONS 4   /* regions of spatial control (nst_level_set_guidance) */
 
 typedef struct nst_ctx nst_ctx;
 typedef struct nst_opt nst_opt;
@@ -216,6 +217,72 @@ int nst_level_set_targets(nst_ctx* ctx, int level, const float* content, const f
 int nst_level_set_targets_blend(nst_ctx* ctx, int level, const float* content, int K, const float* const* styles,
                                 const int* hs, const int* ws, const float* blend /* K x 6, row-major */, void* stream);
 
+/* Spatial control (Gatys et al. 2017, "Controlling Perceptual Factors in Neural Style Transfer", guided Gram matrices):
+ * every region of the image takes its style from its own region of the style image.
+ *
+ * Regions and guidance maps
+ * - Regions are r = 0..R-1, with 1 <= R <= 4.
+ * - Each level has one guidance plane per region at the level's resolution: t_r(y,x) in [0,1], fp32, shape (R,h,w).
+ * - Regions may overlap and need not cover the image.
+ * - The guidance of a map at network scale s (0..4) is the level plane passed s times through a 2x2/2 mean pool.
+ *   - Floor sizes.
+ *   - Order ((e00+e01)+e10)+e11 times 1/4, the order of every pooling kernel here.
+ *   - This holds regardless of nst_job_set_pooling.
+ * Mass
+ * - n_r = sum_p t_r(p)^2, formed in double in a fixed two-stage order and kept per (level, map, region).
+ * Guided Gram of a map F (N pixels x C)
+ * - G_r = sum_p t_r(p)^2 F(p)F(p)^T / (C n_r).
+ * - With t = 1 this is today's F^T F/(C h w).
+ * Style term of a level
+ * - (sum_i w_i sum_r lambda_r MSE(G_ri, Gt_ri)) / nstyle.
+ * - lambda_r >= 0 are the region weights.  The default is 1, and at least one must be positive.
+ * - The loss rows keep their layout: the style entry holds this sum.
+ * Backward
+ * - dF(p) = sum_r t_r(p)^2 F(p) S_r.
+ * - S_r = coef_r (G_r - Gt_r).
+ * - coef_r = (float)((double)sw w_i lambda_r 4 / (nstyle C^2 C n_r)).
+ * Targets
+ * - Gt_ri is the guided Gram of the style image's map i under the style image's own guidance planes.
+ * - Those planes use the same R, are sized to the style image of that level, and use the same pooling chain.
+ * Refusals
+ * - Refuse with NST_E_ARG, leaving the context unchanged and usable, when any of these holds:
+ *   - a value lies outside [0,1] or is non-finite;
+ *   - R is out of range;
+ *   - any (map in use, region) has mass n_r < 1 on the image side or the style side.  Less than one pixel's worth gives a
+ *     Gram of noise.
+ *
+ * nst_level_set_guidance: planes = device (R,h,w) of the level's size, copied (the caller's buffer is free on return: the
+ * call synchronises `stream` to read the masses back); lambda = HOST, R floats, or NULL for ones.  R = 0 clears the level's
+ * guidance (planes and lambda are ignored): the level is then evaluated by exactly the launches of a context that never had
+ * any, with the targets nst_level_set_targets* gave it.  Guidance of another R than the level's guided targets were made
+ * for invalidates those targets; new planes of the same R keep them (they depend on the style side only).  The workspace of
+ * the R guided Grams (slabs, targets, S matrices, loss partials, the plane pyramid) is allocated here, never in a closure.
+ * nst_level_set_targets_guided: the level's content target as nst_level_set_targets makes it, and the guided targets of the
+ * R regions of the level's guidance (NST_E_STATE when the level has none) from `style` (device (3,hs,ws), (1,hs,ws) in
+ * luminance mode) under style_planes = device (R,hs,ws).  The unguided Gram targets of the level are left as they are; the content target is
+ * ONE buffer shared by the guided and the unguided path, so after a later nst_level_set_guidance(R = 0) the level is
+ * evaluated with the content target given here and the style targets the last nst_level_set_targets* gave it.
+ * A guided level is evaluated by nst_closure, nst_closure_levels and the closure halves under both schedules, with any
+ * taps, pooling, colour mode and style layer weights; the levels of one closure call are all guided or all unguided
+ * (NST_E_STATE otherwise), and under level sharding a level's guidance lives with the rank that owns it.  The guided Gram
+ * partials run in the f16x2 arithmetic with the pixel row scaled by t_r(p) as it is staged; the guided backward is a launch
+ * of its own on the exact fp32 matrix cores whose output reaches the input-gradient launch below the map as its addend, so
+ * no convolution launch of a guided job carries a second K source.
+ * NST_E_STATE (see nst_last_error): contexts in the bf16x3 / f32 arithmetic; the stripe closure (nst_window_*) while any
+ * level is guided; nst_level_set_targets_blend with K > 1 on a guided level.
+ * Both setters (also when they fail) drop any captured closure graph and end the validity of an optimiser's remembered
+ * closure and of a pending nst_closure_backward.  nst_job_configure and nst_job_set_taps clear every level's guidance;
+ * nst_job_set_color and nst_job_set_pooling keep the planes and drop the guided targets with the others.
+ * nst_level_guidance: R (0: none), the R region weights, and the masses n_r of the five network scales (mass[s * 4 + r];
+ * any pointer may be NULL).  nst_level_guidance_planes: the (R, h >> scale, w >> scale) planes of one scale, to device
+ * memory. */
+int nst_level_set_guidance(nst_ctx* ctx, int level, int R, const float* planes /* device (R,h,w) */,
+                           const float* lambda /* host, R floats, or NULL */, void* stream);
+int nst_level_set_targets_guided(nst_ctx* ctx, int level, const float* content, const float* style, int hs, int ws,
+                                 const float* style_planes /* device (R,hs,ws) */, void* stream);
+int nst_level_guidance(const nst_ctx* ctx, int level, int* R, float lambda[NST_MAX_REGIONS], double mass[5 * NST_MAX_REGIONS]);
+int nst_level_guidance_planes(nst_ctx* ctx, int level, int scale, float* out, void* stream);
+
 /* optimizer_step_callback without its LR decay and prints (neural_style_transfer.py:152-199) =
  * sum over levels of LossBuilder.build (:84-112) on the bicubic 1/2 chain of x (:170-176),
  * then backward (:193).  x, grad: device (3,H0,W0) ((1,H0,W0) under NST_COLOR_LUMINANCE).  losses: device, NST_LOSS_ROW*levels+1
@@ -368,6 +435,13 @@ int nst_level_activation(nst_ctx* ctx, int level, int layer, float* out, void* s
 int nst_level_image(nst_ctx* ctx, int level, float* out, void* stream);
 /* math_utils.gram_matrix (math_utils.py:26-34): f device (C,h,w) -> gram device (C,C). */
 int nst_gram(nst_ctx* ctx, const float* f, int C, int h, int w, int normalize, float* gram, void* stream);
+/* The guided Gram backward launch on its own, in the closure's own layout: out = addend + sum_r t_r^2 . F . S_r.
+ * f, addend (nullable; may be `out` itself), out: device pixel-major (N,C); planes: device (R,N); S: device (R,C,C);
+ * relu_bits (nullable): device (N, C/32) words, out is zero where the bit of (pixel, channel) is clear; amax_slots
+ * (nullable): device, 64 words, zeroed by the call, whose maximum is the bit pattern of max |out|.  C a multiple of 64,
+ * 1 <= R <= NST_MAX_REGIONS.  Reads no job state and needs no particular arithmetic mode. */
+int nst_guided_gram_backward(nst_ctx* ctx, const float* f, size_t N, int C, int R, const float* planes, const float* S,
+                             const float* addend, const unsigned* relu_bits, float* out, unsigned* amax_slots, void* stream);
 /* math_utils.total_variation (math_utils.py:37-41): value (device scalar) and, if grad != NULL,
  * grad (C,h,w) = d tv / d y. */
 int nst_total_variation(nst_ctx* ctx, const float* y, int C, int h, int w, float* value, float* grad,
