@@ -112,6 +112,9 @@ SYMBOLS = {
     "nst_vgg_features_backward": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.POINTER(c_void), c_void, c_void]),
     "nst_vgg_activations": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.POINTER(c_void), c_void]),
     "nst_level_activation": (C.c_int, [c_void, C.c_int, C.c_int, c_void, c_void]),
+    "nst_job_map_stats": (C.c_int, [c_void, C.c_int, C.POINTER(C.c_uint)]),
+    "nst_ctx_set_keep_all_maps": (C.c_int, [c_void, C.c_int]),
+    "nst_ctx_keep_all_maps": (C.c_int, [c_void]),
     "nst_level_image": (C.c_int, [c_void, C.c_int, c_void, c_void]),
     "nst_gram": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, c_void, c_void]),
     "nst_guided_gram_backward": (C.c_int, [c_void, c_void, C.c_size_t, C.c_int, C.c_int, c_void, c_void, c_void, c_void, c_void,

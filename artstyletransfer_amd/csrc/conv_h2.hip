@@ -843,6 +843,7 @@ __device__ __forceinline__ void conv_h2_body(const Tiles& tiles, const int slot_
                 const int ppix0 = ((y0 + wm * 4) >> 1) * PW2 + ((x0 + 4 * kg) >> 1);
                 const unsigned pbase = (unsigned)ppix0 * (unsigned)colB + (unsigned)(cg0 + l15) * 4u;
                 const unsigned cbase = (l15 == 0) ? ((unsigned)ppix0 * (unsigned)words + (unsigned)(cg0 >> 5)) * 16u : 0xFFFFFF00u;
+                const bool full = UNPOOL || p.out != nullptr;      // (null: a map nothing reads - only its pooled form is written; never an un-pooling launch's)
 #pragma unroll
                 for (int nt = 0; nt < NT16; ++nt) {
                     const float bv = p.bias ? p.bias[cg0 + nt * 16 + l15] : 0.f;
@@ -853,7 +854,7 @@ __device__ __forceinline__ void conv_h2_body(const Tiles& tiles, const int slot_
                             float v = fmaf(ax16[mt][nt][i], LO_DOWN, am16[mt][nt][i]) * inv + bv;
                             v = fmaxf(v, lo_clamp);
                             am16[mt][nt][i] = v;
-                            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rs_out, vbase, mt * rowB + i * colB + nt * 64, 0);
+                            if (full) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rs_out, vbase, mt * rowB + i * colB + nt * 64, 0);
                             amax = fmaxf(amax, fabsf(v));
                         }
                 }
@@ -938,7 +939,7 @@ __device__ __forceinline__ void conv_h2_body(const Tiles& tiles, const int slot_
                     }
                     am16[mt][nt][i] = v;
                     if (inb) {
-                        p.out[idx] = v;
+                        if (UNPOOL || p.out) p.out[idx] = v;
                         amax = fmaxf(amax, fabsf(v));
                     }
                 }
@@ -1099,6 +1100,7 @@ __device__ __forceinline__ void conv_h2_body(const Tiles& tiles, const int slot_
             const unsigned pbase = (unsigned)ppix0 * (unsigned)colB + (unsigned)(cg0 + l31) * 4u;
             const unsigned cbase = (l31 == 0) ? ((unsigned)ppix0 * (unsigned)words + (unsigned)(cg0 >> 5)) * 16u : 0xFFFFFF00u;
             const float lo_clamp = p.relu ? 0.f : -__builtin_inff();
+            const bool full = UNPOOL || p.out != nullptr;      // (null: a map nothing reads - only its pooled form is written; never an un-pooling launch's)
 #pragma unroll
             for (int nt = 0; nt < NTW; ++nt) {
                 const float bv = p.bias ? p.bias[cg0 + nt * 32 + l31] : 0.f;
@@ -1109,7 +1111,7 @@ __device__ __forceinline__ void conv_h2_body(const Tiles& tiles, const int slot_
                         float v = fmaf(accx[mt][nt][r], LO_DOWN, accm[mt][nt][r]) * inv + bv;
                         v = fmaxf(v, lo_clamp);
                         accm[mt][nt][r] = v;
-                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rs_out, vbase, soff(mt, r, rowB, colB) + nt * 128, 0);
+                        if (full) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rs_out, vbase, soff(mt, r, rowB, colB) + nt * 128, 0);
                         amax = fmaxf(amax, fabsf(v));
                         if (p.bits_out) {
                             // ReLU mask of this output for the backward pass: bit = lane, one word per half-wave
@@ -1188,7 +1190,7 @@ __device__ __forceinline__ void conv_h2_body(const Tiles& tiles, const int slot_
                 }
                 accm[mt][nt][r] = v;
                 if (inb) {
-                    p.out[idx] = v;
+                    if (UNPOOL || p.out) p.out[idx] = v;
                     amax = fmaxf(amax, fabsf(v));
                 }
             }
@@ -1486,6 +1488,7 @@ hipError_t launch_conv_h2_batch(const ConvBatch& b0, hipStream_t stream, H2Shape
             return hipErrorInvalidValue;
         if ((size_t)im.H * im.W * (b.Cin > b.Cin2 ? b.Cin : b.Cin2) * 4 >= 0xFFFFFF00ull) return hipErrorInvalidValue;
         if ((b.unpool != 0) != (im.pcode_in != nullptr)) return hipErrorInvalidValue;
+        if (!im.out && !im.pool_out) return hipErrorInvalidValue;       // a launch may leave out the full map only beside the pooled one
         H[i] = im.H; W[i] = im.W;
         second = second || (im.in2 != nullptr);
     }
@@ -1508,6 +1511,7 @@ hipError_t launch_conv_h2_batch(const ConvBatch& b0, hipStream_t stream, H2Shape
 hipError_t launch_conv_h2(const ConvParams& p0, hipStream_t stream, H2Shape* shape) {
     if (!h2_operands_ok(p0.wt_h2, p0.amax_in, p0.Cin, p0.Cout, p0.in2, p0.wt2_f32, p0.amax_in2, p0.amax_w2, p0.Cin2))
         return hipErrorInvalidValue;
+    if (!p0.out && !p0.pool_out) return hipErrorInvalidValue;
     ConvParams p = p0;
     p.ksplit = 1;
     int all_blocks = 0;
@@ -1539,7 +1543,7 @@ hipError_t launch_conv_h2(const ConvParams& p0, hipStream_t stream, H2Shape* sha
         if (q.pcode_in) { q.in += pp0 * p.Cin; q.pcode_in += pp0 * wi * 4; }
         else if (q.in) q.in += px0 * p.Cin;
         if (q.in2) { q.in2 += px0 * p.Cin2; if (q.in2_rows > 0) q.in2_row0 -= b0; }
-        q.out += px0 * p.Cout;
+        if (q.out) q.out += px0 * p.Cout;
         if (q.addend) q.addend += px0 * p.Cout;
         if (q.mask) q.mask += px0 * p.Cout;
         if (q.bits_in) q.bits_in += px0 * wo;

@@ -389,6 +389,8 @@ __global__ __launch_bounds__(512, 2) void conv_wino_batch_kernel(ConvBatch b) {
     unsigned* const e_pcode_out = M_FWD ? im.pcode_out : nullptr;
     const float* const e_addend = M_BWD ? im.addend : nullptr;
     const unsigned* const e_bits_in = M_BWD ? im.bits_in : nullptr;
+    // a forward launch leaves out the full-resolution map nothing reads (out = null, beside a pooled map): wave-uniform
+    const bool e_full = M_FWD ? im.out != nullptr : true;
     float* E = reinterpret_cast<float*>(smem);                               // [xi][pair row 64][128]
     unsigned* WB = reinterpret_cast<unsigned*>(smem + W_BITS_OFF);           // [pixel 128][4 words]
     unsigned* PC = reinterpret_cast<unsigned*>(smem + W_CODE_OFF);           // [pooled pixel 32][4 words][4 positions]
@@ -460,8 +462,10 @@ __global__ __launch_bounds__(512, 2) void conv_wino_batch_kernel(ConvBatch b) {
                 if (ina) amax = fmaxf(amax, fabsf(ya[e]));
                 if (inb) amax = fmaxf(amax, fabsf(yb[e]));
             }
-            if (ina) *reinterpret_cast<f32x4*>(im.out + pa * Cout + co) = ya;
-            if (inb) *reinterpret_cast<f32x4*>(im.out + (pa + 1) * Cout + co) = yb;
+            if (e_full) {
+                if (ina) *reinterpret_cast<f32x4*>(im.out + pa * Cout + co) = ya;
+                if (inb) *reinterpret_cast<f32x4*>(im.out + (pa + 1) * Cout + co) = yb;
+            }
             if (e_bits_out) {
                 const int pix = yy * 16 + 2 * p;
                 // (the 8 threads cq & 7 = 0..7 hold the 8 nibbles of one 32-channel word)
@@ -558,6 +562,7 @@ bool conv_wino_eligible(const ConvBatch& b) {
         const ConvImage& im = b.img[i];
         if (im.in2 || im.mask || !im.amax_in || (b.unpool != 0) != (im.pcode_in != nullptr)) return false;
         if (im.pcode_out && !im.pool_out) return false;
+        if (!im.out && !im.pool_out) return false;       // the full map may be left out only beside the pooled one
         if ((size_t)im.H * im.W * (b.Cin > b.Cout ? b.Cin : b.Cout) * 4 >= 0xFFFFFF00ull) return false;
     }
     return true;

@@ -104,9 +104,14 @@ int nst_level_activation(nst_ctx* ctx, int level, int layer, float* out, void* s
     if (layer < 0 || layer >= NL || !out) return fail(ctx, NST_E_ARG, "bad argument");
     const ActSet& a = ctx->lv[level].acts;
     hipStream_t s = enter(ctx, stream);
-    HIPCHK(ctx, launch_hwc_to_chw(a.act[layer], kCout[layer], a.h[layer], a.w[layer], out, s));
+    // a map the last forward pass left out (nothing of a closure reads it): that layer's launch once more, with the map
+    const int rc = restore_map(ctx, level, layer, s);
+    if (rc == NST_OK && launch_hwc_to_chw(a.act[layer], kCout[layer], a.h[layer], a.w[layer], out, s) != hipSuccess) {
+        mark(ctx, s);
+        return fail(ctx, NST_E_HIP, "hwc_to_chw launch failed");
+    }
     mark(ctx, s);
-    return NST_OK;
+    return rc;
 }
 
 int nst_level_image(nst_ctx* ctx, int level, float* out, void* stream) {

@@ -65,17 +65,18 @@ void conv_setup(const nst_ctx* ctx, ConvBatch& b, int l, bool dgrad) {
 }
 // One conv launch for every level, under the caller's timer: the Winograd form where the layer has its weights and the
 // launch qualifies (2/3 of the direct form's matrix-pipe work), else the direct kernel of the arithmetic mode
-int launch_conv_batch(nst_ctx* ctx, const ConvBatch& b, Timer& t, bool allow_wino) {
+int launch_conv_batch(nst_ctx* ctx, const ConvBatch& b, hipStream_t s, Timer* t, bool allow_wino) {
     const bool h2 = ctx->conv_mode == 2;
-    if (h2 && allow_wino && b.wt_wino && conv_wino_eligible(b)) { t.mfma_factor(2.0); HIPCHK(ctx, launch_conv_wino_batch(b, t.s)); }
+    if (h2 && allow_wino && b.wt_wino && conv_wino_eligible(b)) { if (t) t->mfma_factor(2.0); HIPCHK(ctx, launch_conv_wino_batch(b, s)); }
     else if (h2) {
         H2Shape sh{};
-        const hipError_t e = launch_conv_h2_batch(b, t.s, &sh);
-        t.shape(sh);
+        const hipError_t e = launch_conv_h2_batch(b, s, &sh);
+        if (t) t->shape(sh);
         HIPCHK(ctx, e);
-    } else HIPCHK(ctx, launch_conv_bf3_batch(b, t.s));
+    } else HIPCHK(ctx, launch_conv_bf3_batch(b, s));
     return NST_OK;
 }
+int launch_conv_batch(nst_ctx* ctx, const ConvBatch& b, Timer& t, bool allow_wino) { return launch_conv_batch(ctx, b, t.s, &t, allow_wino); }
 
 // the 2x2/2 pool of the job (nst_job_set_pooling) as kernels of their own, and its backward fused with the ReLU mask of `a`
 hipError_t launch_pool_fwd(const nst_ctx* ctx, const float* in, int H, int W, int C, float* out, hipStream_t s) {
@@ -98,6 +99,24 @@ StyleTerm style_term(const Taps& tp, int q, const ActSet& a, float sw, float w, 
 }
 // content = cw * mse(F, Ft) over n elements: dF = coef * (F - Ft)
 float content_coef(float cw, double n) { return (float)((double)cw * 2.0 / n); }
+
+// Which full-resolution maps a batched f16x2 forward pass stores.  A launch that feeds a pooling layer writes the pooled map
+// beside the full one, and in that schedule the backward pass takes the ReLU and pool decisions from the bit-masks and the
+// pool codes: the full map of such a layer has no reader there.  Every map a loss reads (Gram launches - guided ones too -,
+// content MSE, second K source, the stripe closure's sums, the top of the chain) is one of the six of kTapLayer, and none of
+// those lies in front of a pooling layer (asserted below: a tap that could land there would have to make the rule keep it).
+// Under a captured graph every map is stored: a replay runs no host code, so what ActSet::stored[] says could go stale.
+// Every other walker and arithmetic mode reads act[] as masks and pool inputs and stores all of it.
+constexpr bool taps_avoid_pools() {
+    for (int t : kTapLayer)
+        for (int p : kPoolAfter) if (t == p) return false;
+    return true;
+}
+static_assert(taps_avoid_pools(), "a map in front of a pooling layer became a tap: map_stored must keep it where a job reads it");
+bool map_stored(const nst_ctx* ctx, int l) {
+    if (ctx->conv_mode != 2 || ctx->keep_all_maps || ctx->use_graph) return true;
+    return pool_index_after(l) < 0;
+}
 
 // partial-Gram workspace of one image: the style layers one after the other (the batched launch works on
 // all of them at once); offset of style slot k = gram_part_offset(tp, h, w, k), total = gram_part_offset(tp, h, w, tp.nstyle)
@@ -160,6 +179,8 @@ int forward(nst_ctx* ctx, ActSet& a, const float* x, int h, int w, hipStream_t s
         HIPCHK(ctx, launch_conv1_1_fwd(x, h, w, ctx->w11k, ctx->bias[0], a.act[0], bits, h2 ? amax_act(a, 0) : nullptr, s, channels));
         a.bits_valid[0] = bits != nullptr;
     }
+    a.pass = 0;
+    for (int l = 0; l <= last_layer; ++l) a.stored[l] = true;
     for (int l = 1; l <= last_layer; ++l) {
         const int pk = pool_index_after(l - 1);
         const float* in = (pk >= 0) ? a.pool[pk] : a.act[l - 1];
@@ -352,6 +373,34 @@ constexpr size_t kWinGramOff[5] = {0, 64 * 64, 64 * 64 + 128 * 128, 64 * 64 + 12
 constexpr size_t kWinScalarOff = 64 * 64 + 128 * 128 + 256 * 256 + 2 * 512 * 512;    // content SSE, TV x, TV y
 constexpr size_t kWinSums = kWinScalarOff + 4;
 
+// Layer l's forward launch over the levels lv[0 .. n): what batched_forward enqueues and restore_map repeats.  full = false:
+// the launch leaves out the full-resolution map (map_stored) and writes the pooled one, the mask and the code words only.
+ConvBatch forward_batch(nst_ctx* ctx, const int* lv, int n, int l, bool full, double* flops) {
+    const bool h2 = ctx->conv_mode == 2;
+    const int pk = pool_index_after(l - 1), pa = pool_index_after(l);
+    ConvBatch b{};
+    b.n = n; b.bias = ctx->bias[l]; b.Cin = kCin[l]; b.Cout = kCout[l];
+    // conv5_1 before its ReLU (use_relu = 0): the Winograd launch takes its general epilogue (MODE 0), which honours relu = 0
+    b.relu = ctx->taps.relu_of(l);
+    conv_setup(ctx, b, l, false);
+    b.pool_avg = ctx->pool_avg;
+    for (int k = 0; k < n; ++k) {
+        ActSet& a = ctx->lv[lv[k]].acts;
+        ConvImage& im = b.img[k];
+        im.in = (pk >= 0) ? a.pool[pk] : a.act[l - 1];
+        im.out = full ? a.act[l] : nullptr; im.H = a.h[l]; im.W = a.w[l];
+        im.bits_out = a.bits[l];
+        im.pool_out = (pa >= 0) ? a.pool[pa] : nullptr;
+        im.pcode_out = (pa >= 0 && h2) ? a.pcode[pa] : nullptr;
+        a.bits_valid[l] = a.bits[l] != nullptr;
+        a.stored[l] = full;
+        if (pa >= 0) a.pooled[pa] = true;
+        im.amax_in = amax_act(a, l - 1); im.amax_out = amax_act(a, l);
+        *flops += conv_flops(im.H, im.W, b.Cin, b.Cout, 9);
+    }
+    return b;
+}
+
 // `fork_sw` >= 0 (f16x2 closure, nst_options.gram_overlap): once relu3_1 is written, the Gram matrices of relu1_1, relu2_1 and
 // relu3_1 - HBM-bound streams over 85 % of the style bytes - are launched on the context's side stream, where they run
 // under the MFMA-bound convolutions of conv3_2 ... conv5_1 instead of after them; the caller joins before the backward.
@@ -372,29 +421,17 @@ int batched_forward(nst_ctx* ctx, const float* const* xi, const int* lv, int n, 
         HIPCHK(ctx, launch_conv1_1_fwd(xi[lv[k]], L.h, L.w, ctx->w11k, ctx->bias[0], a.act[0], a.bits[0],
                                        h2 ? amax_act(a, 0) : nullptr, s, ctx->channels));
         a.bits_valid[0] = true;
+        a.stored[0] = true;
+    }
+    ++ctx->fwd_pass;
+    for (int k = 0; k < n; ++k) {
+        ActSet& a = ctx->lv[lv[k]].acts;
+        a.pass = ctx->fwd_pass; a.pass_n = n;
+        for (int j = 0; j < n; ++j) a.pass_lv[j] = lv[j];
     }
     for (int l = 1; l <= top; ++l) {
-        const int pk = pool_index_after(l - 1), pa = pool_index_after(l);
-        ConvBatch b{};
-        b.n = n; b.bias = ctx->bias[l]; b.Cin = kCin[l]; b.Cout = kCout[l];
-        // conv5_1 before its ReLU (use_relu = 0): the Winograd launch takes its general epilogue (MODE 0), which honours relu = 0
-        b.relu = ctx->taps.relu_of(l);
-        conv_setup(ctx, b, l, false);
-        b.pool_avg = ctx->pool_avg;
         double flops = 0;
-        for (int k = 0; k < n; ++k) {
-            ActSet& a = ctx->lv[lv[k]].acts;
-            ConvImage& im = b.img[k];
-            im.in = (pk >= 0) ? a.pool[pk] : a.act[l - 1];
-            im.out = a.act[l]; im.H = a.h[l]; im.W = a.w[l];
-            im.bits_out = a.bits[l];
-            im.pool_out = (pa >= 0) ? a.pool[pa] : nullptr;
-            im.pcode_out = (pa >= 0 && h2) ? a.pcode[pa] : nullptr;
-            a.bits_valid[l] = a.bits[l] != nullptr;
-            if (pa >= 0) a.pooled[pa] = true;
-            im.amax_in = amax_act(a, l - 1); im.amax_out = amax_act(a, l);
-            flops += conv_flops(im.H, im.W, b.Cin, b.Cout, 9);
-        }
+        const ConvBatch b = forward_batch(ctx, lv, n, l, map_stored(ctx, l), &flops);
         {
             Timer t(ctx, s, K_CONV3, flops, b.img[0].H, b.img[0].W, b.Cin, b.Cout, 9, l);
             NSTCHK(launch_conv_batch(ctx, b, t, true));
@@ -949,6 +986,27 @@ int window_check(nst_ctx* ctx, const float* xs, int row0, int rows, int H0) {
 
 }  // namespace
 
+namespace nst {
+
+int restore_map(nst_ctx* ctx, int level, int layer, hipStream_t s) {
+    ActSet& a = ctx->lv[level].acts;
+    // the map is there; or nothing to repeat: no pass since the job was set up, or one that stopped below this layer
+    if (a.stored[layer] || a.pass == 0 || layer > ctx->taps.top) return NST_OK;
+    // the launch covers every level of that pass: all of them must still hold it (its inputs, and what it rewrites)
+    bool whole = a.pass_n >= 1;
+    for (int k = 0; k < a.pass_n; ++k) whole = whole && ctx->lv[a.pass_lv[k]].acts.pass == a.pass;
+    if (!whole)
+        return fail(ctx, NST_E_STATE, "the level's last forward pass left this map out and a later pass has run over some of its levels: "
+                                      "evaluate the level again, or set keep_all_maps");
+    int lv[NST_MAX_LEVELS];
+    for (int k = 0; k < a.pass_n; ++k) lv[k] = a.pass_lv[k];
+    double flops = 0;
+    const ConvBatch b = forward_batch(ctx, lv, a.pass_n, layer, true, &flops);
+    return launch_conv_batch(ctx, b, s, nullptr, true);
+}
+
+}  // namespace nst
+
 // ================================================================================================
 extern "C" {
 
@@ -1012,6 +1070,7 @@ int nst_level_set_targets_blend(nst_ctx* ctx, int level, const float* content, i
         NSTCHK(sc.finish());
     }
     L.targets = true;
+    forget_forward_pass(ctx);           // (the content target's pass is no closure's)
     return NST_OK;
 }
 
@@ -1156,6 +1215,7 @@ int nst_level_set_targets_guided(nst_ctx* ctx, int level, const float* content, 
     }
     NSTCHK(sc.finish());
     g.targets = true; g.targets_R = R;
+    forget_forward_pass(ctx);
     mark(ctx, s);
     return NST_OK;
 }

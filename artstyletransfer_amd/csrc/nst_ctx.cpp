@@ -345,6 +345,13 @@ void drop_closure_state(nst_ctx* ctx, bool drop_targets) {
     if (ctx->gexec) { (void)hipGraphExecDestroy(ctx->gexec); ctx->gexec = nullptr; }
     ctx->gkey = {}; ctx->glast = {};
     for (int i = 0; drop_targets && i < ctx->levels; ++i) { ctx->lv[i].targets = false; ctx->lv[i].guide.targets = false; }
+    if (drop_targets) forget_forward_pass(ctx);
+}
+void forget_forward_pass(nst_ctx* ctx) {
+    for (int i = 0; i < NST_MAX_LEVELS; ++i) {
+        ctx->lv[i].acts.pass = 0; ctx->lv[i].acts.pass_n = 0;
+        for (bool& st : ctx->lv[i].acts.stored) st = false;
+    }
 }
 
 // folds the event pairs of the previous closure into the accumulators (waits for them to complete)
@@ -507,6 +514,7 @@ int nst_ctx_create_ex(int device, const float* const* weights, const float* cons
     ctx->winograd = (opts.h2_winograd >= 0 ? opts.h2_winograd : env_flag("NST_H2_WINOGRAD", 1)) ? 1 : 0;
     ctx->level_split = (opts.level_split >= 0 ? opts.level_split : env_flag("NST_LEVEL_SPLIT", 0)) ? 1 : 0;
     ctx->gram_overlap = (opts.gram_overlap >= 0 ? opts.gram_overlap : env_flag("NST_GRAM_OVERLAP", 0)) ? 1 : 0;
+    ctx->keep_all_maps = env_flag("NST_KEEP_ALL_MAPS", 0) ? 1 : 0;      // (nst_ctx_set_keep_all_maps overrides)
     if (ctx->use_graph && hipStreamCreateWithFlags(&ctx->gstream, hipStreamNonBlocking) != hipSuccess) { ctx->err = "stream creation failed"; return bail(NST_E_HIP); }
     if (e != hipSuccess) { ctx->err = std::string("kernel attribute setup: ") + hipGetErrorString(e); return bail(NST_E_HIP); }
 
@@ -624,6 +632,7 @@ int nst_job_configure(nst_ctx* ctx, int levels_num, int H0, int W0) {
     quiesce(ctx);
     for (int i = 0; i < NST_MAX_LEVELS; ++i) free_level(ctx, ctx->lv[i]);      // (the targets go with the levels)
     drop_closure_state(ctx, false);
+    forget_forward_pass(ctx);
     ctx->levels = 0;
     int h = H0, w = W0;
     for (int i = 0; i < levels_num; ++i) {
@@ -724,6 +733,27 @@ int nst_job_set_pooling(nst_ctx* ctx, int mode) {
     quiesce(ctx);
     drop_closure_state(ctx, true);
     ctx->pool_avg = mode == NST_POOL_AVG ? 1 : 0;
+    return NST_OK;
+}
+
+// The A/B twin of the unread-map elision in one build: 1 = every batched forward launch stores its full-resolution map.
+// Results do not depend on it; a captured graph holds the launches of the setting it was captured under and goes.
+int nst_ctx_set_keep_all_maps(nst_ctx* ctx, int enabled) {
+    NSTCHK(bind(ctx));
+    ++ctx->ws_seq;
+    drop_closure_state(ctx, false);
+    ctx->keep_all_maps = enabled ? 1 : 0;
+    return NST_OK;
+}
+int nst_ctx_keep_all_maps(const nst_ctx* ctx) { return ctx ? ctx->keep_all_maps : -1; }
+
+int nst_job_map_stats(nst_ctx* ctx, int level, unsigned* stored_mask) {
+    NSTCHK(bind(ctx));
+    if (level < 0 || level >= ctx->levels) return fail(ctx, NST_E_STATE, "level not configured");
+    if (!stored_mask) return fail(ctx, NST_E_ARG, "null argument");
+    unsigned m = 0;
+    for (int l = 0; l < NL; ++l) m |= (ctx->lv[level].acts.stored[l] ? 1u : 0u) << l;
+    *stored_mask = m;
     return NST_OK;
 }
 
@@ -854,6 +884,34 @@ int nst_internal_channels(const nst_ctx* ctx) { return ctx ? ctx->channels : 3; 
 size_t nst_internal_pixels(const nst_ctx* ctx) { return (ctx && ctx->levels > 0) ? (size_t)ctx->lv[0].h * ctx->lv[0].w : 0; }
 int nst_internal_fail(nst_ctx* ctx, int code, const char* msg) { return fail(ctx, code, msg ? msg : ""); }
 void nst_internal_poison(void* p, size_t bytes) { poison_if_asked(p, bytes); }
+// test hooks (tests/test_hip_unread_maps.py): the raw NHWC buffer of one feature map filled with a byte / copied to `dst`
+// (device memory), on a stream of their own and waited for - see nst_internal_zero_now
+int nst_internal_map_fill(nst_ctx* ctx, int level, int layer, int byte) {
+    if (!ctx || level < 0 || level >= ctx->levels || layer < 0 || layer >= NL) return 1;
+    const ActSet& a = ctx->lv[level].acts;
+    const size_t bytes = (size_t)a.h[layer] * a.w[layer] * kCout[layer] * 4;
+    if (hipSetDevice(ctx->device) != hipSuccess) return 1;
+    quiesce(ctx);
+    hipStream_t zs = nullptr;
+    if (hipStreamCreateWithFlags(&zs, hipStreamNonBlocking) != hipSuccess) return 1;
+    hipError_t e = hipMemsetAsync(a.act[layer], byte, bytes, zs);
+    if (e == hipSuccess) e = hipStreamSynchronize(zs);
+    (void)hipStreamDestroy(zs);
+    return e == hipSuccess ? 0 : 1;
+}
+int nst_internal_map_read(nst_ctx* ctx, int level, int layer, void* dst) {
+    if (!ctx || !dst || level < 0 || level >= ctx->levels || layer < 0 || layer >= NL) return 1;
+    const ActSet& a = ctx->lv[level].acts;
+    const size_t bytes = (size_t)a.h[layer] * a.w[layer] * kCout[layer] * 4;
+    if (hipSetDevice(ctx->device) != hipSuccess) return 1;
+    quiesce(ctx);
+    hipStream_t zs = nullptr;
+    if (hipStreamCreateWithFlags(&zs, hipStreamNonBlocking) != hipSuccess) return 1;
+    hipError_t e = hipMemcpyAsync(dst, a.act[layer], bytes, hipMemcpyDeviceToDevice, zs);
+    if (e == hipSuccess) e = hipStreamSynchronize(zs);
+    (void)hipStreamDestroy(zs);
+    return e == hipSuccess ? 0 : 1;
+}
 int nst_internal_lbfgs_gram(const nst_ctx* ctx) { return ctx ? ctx->lbfgs_gram : 1; }
 unsigned long long nst_internal_closure_epoch(const nst_ctx* ctx) { return ctx ? ctx->closure_epoch : 0; }
 void nst_internal_mark(nst_ctx* ctx, void* stream) { mark(ctx, static_cast<hipStream_t>(stream)); }

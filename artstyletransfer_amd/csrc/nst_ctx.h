@@ -43,6 +43,14 @@ struct ActSet {                 // activations of one forward pass, NHWC
     unsigned* bits[NL] = {};     // ReLU bit-masks ([h*w][C/32] words) of the layers whose mask the backward reads
     bool bits_valid[NL] = {};    // written by the last forward pass (false when that layer ran split-K / fp32)
     bool pooled[4] = {};         // pool[k] already produced by the conv epilogue of the last forward pass
+    // act[l] written by the last forward pass: the batched f16x2 walker leaves out a full-resolution map that nothing reads
+    // (map_stored in nst_closure.cpp has the rule); nst_level_activation writes such a map on request (restore_map)
+    bool stored[NL] = {};
+    // the batched pass that last wrote this set: its number (nst_ctx::fwd_pass; 0: none since the job was set up) and the
+    // levels its launches covered, in launch order - what restore_map repeats a layer's launch over
+    unsigned long long pass = 0;
+    int pass_lv[NST_MAX_LEVELS] = {};
+    int pass_n = 0;
     // absmax records for the fp16-piece convolutions (conv_h2.hip): AMAX_IDS x NST_AMAX_SLOTS words.
     // ids: act[l] -> l; the Gram factor S of style slot q -> NL + q (6 slots); the gradient w.r.t. the pre-ReLU output
     // of layer l (or a bound of it: the pooled gradient it was un-pooled from) -> NL + 6 + l
@@ -55,6 +63,7 @@ struct ActSet {                 // activations of one forward pass, NHWC
     void begin_pass() {
         for (int l = 0; l < NL; ++l) bits_valid[l] = false;
         for (int k = 0; k < 4; ++k) pooled[k] = false;
+        for (int l = 0; l < NL; ++l) stored[l] = false;
     }
 };
 constexpr int AMAX_IDS = 2 * NST_VGG19_CONVS + kMaxStyle;
@@ -164,6 +173,8 @@ struct nst_ctx {
     int gram_overlap = 0;       // nst_options.gram_overlap
     int persist = 1;            // nst_options.h2_persist
     int level_split = 0;        // nst_options.level_split
+    int keep_all_maps = 0;      // nst_ctx_set_keep_all_maps: 1 = every batched forward launch stores its full-resolution map
+    unsigned long long fwd_pass = 0;     // batched forward passes so far (ActSet::pass)
     hipStream_t side = nullptr; // the Gram launches of the shallow style layers run here, under the deeper forward convolutions
     hipEvent_t side_fork = nullptr, side_join = nullptr;
     hipStream_t tail_stream = nullptr;   // the stream the tail event was last recorded on (see enter())
@@ -335,6 +346,12 @@ int backward(nst_ctx* ctx, ActSet& a, const Inject* inj, const ContentJob* cj, f
 int gram_of(nst_ctx* ctx, const float* f_nhwc, size_t N, int C, const unsigned* f_amax, float divisor, float* part, const float* target,
             float coef, float* gram_out, float* S, unsigned short* S_bf, unsigned* S_amax, double* mse_partial,
             hipStream_t s);
+// A full-resolution map of `level` that its last batched forward pass left out: that layer's launch again, over the levels
+// of that pass (same ConvBatch, so the same tile shape and summation order), with `out` set.  The pooled map, mask and code
+// words it rewrites are the values they hold; the absmax records stay (atomicMax of the same values).
+int restore_map(nst_ctx* ctx, int level, int layer, hipStream_t s);
+// the job changed: no forward pass is remembered (nst_level_activation copies what the buffers hold, as before any pass)
+void forget_forward_pass(nst_ctx* ctx);
 // floats of the partial-Gram workspace of one h x w image under these taps (the style layers one after the other)
 size_t gram_part_floats_for(const Taps& tp, int h, int w);
 

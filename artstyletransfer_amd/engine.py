@@ -46,9 +46,11 @@ class StyleEngine:
                  h2_mfma16: Optional[bool] = None, h2_wg256: Optional[bool] = None,
                  h2_tile_rows: Optional[int] = None, gram_overlap: Optional[bool] = None,
                  h2_persist: Optional[bool] = None, level_split: Optional[bool] = None,
-                 h2_winograd: Optional[bool] = None):
+                 h2_winograd: Optional[bool] = None, keep_all_maps: Optional[bool] = None):
         """Options (nst_options): None = environment variable (NST_CONV, NST_BATCH, NST_SINGLE_STREAM, NST_GRAPH,
-        NST_H2_BAND_ROWS, NST_LBFGS_GRAM, NST_H2_MFMA16; read once, here) and otherwise the default (f16x2, batched, ...)."""
+        NST_H2_BAND_ROWS, NST_LBFGS_GRAM, NST_H2_MFMA16; read once, here) and otherwise the default (f16x2, batched, ...).
+        keep_all_maps (nst_ctx_set_keep_all_maps; None = env NST_KEEP_ALL_MAPS, default off): every batched forward launch
+        stores its full-resolution map, also the four that nothing reads - same results, the A/B twin of the elision."""
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise NstError("no GPU visible: the style-transfer hot path runs only on the HIP device")
@@ -78,6 +80,8 @@ class StyleEngine:
         ctx = C.c_void_p()
         _lib.check(None, self.lib.nst_ctx_create_ex(idx, wp, bp, C.byref(opts), C.byref(ctx)), "nst_ctx_create_ex")
         self.ctx = ctx
+        if keep_all_maps is not None:
+            _lib.check(self.ctx, self.lib.nst_ctx_set_keep_all_maps(self.ctx, int(bool(keep_all_maps))), "nst_ctx_set_keep_all_maps")
         self.weights_id = id(weights)          # which weight set this context carries (neural_nets' engine pool)
         self.levels = 0
         self.shape = None
@@ -499,6 +503,13 @@ class StyleEngine:
         _lib.check(self.ctx, self.lib.nst_level_activation(self.ctx, level, layer, _ptr(t), _stream(self.device)),
                    "nst_level_activation")
         return t
+
+    def map_stats(self, level: int) -> int:
+        """Bit l = the last forward pass of `level` stored conv layer l's full-resolution map, or a level_activation request
+        since has written it (nst_job_map_stats)."""
+        m = C.c_uint(0)
+        _lib.check(self.ctx, self.lib.nst_job_map_stats(self.ctx, level, C.byref(m)), "nst_job_map_stats")
+        return int(m.value)
 
     def level_image(self, level: int) -> torch.Tensor:
         """The (1,C,h,w) image of pyramid level `level` >= 1 that the last closure evaluated (nst_level_image)."""

@@ -428,6 +428,24 @@ int nst_vgg_features_backward(nst_ctx* ctx, const float* x, int h, int w, const 
  * ReLU and max-pool DECISIONS of the device pass from it (a unit is on where the value is > 0; a pooling window passes its
  * gradient to its first maximum) and hand them to the oracle, so that gradients are compared under equal decisions. */
 int nst_level_activation(nst_ctx* ctx, int level, int layer, float* out, void* stream);
+/* Which maps exist after a pass.  In the batched f16x2 schedule a forward launch that feeds a pooling layer (conv1_2,
+ * conv2_2, conv3_4, conv4_4) writes the pooled map, the ReLU mask and the pool code, and its full-resolution map only where
+ * something reads it: where it is a style or the content map of the job's taps, or the top of the chain.  With the default
+ * taps none of the four is stored.  nst_level_activation stays exact: a request for a map that was left out repeats that
+ * layer's launch over the levels of the level's last pass (same tiles, same summation order), now storing the map.  One
+ * sequence cannot be served and returns NST_E_STATE with nothing written: the level's last pass covered other levels too
+ * (nst_closure over levels {0, 1}) and a later call has evaluated some of those without this one (nst_closure_levels,
+ * nst_closure_forward or nst_opt_shard_levels with a mask that leaves this level out) - evaluate the level again, or keep
+ * all maps.  Every other schedule and arithmetic, and a context with use_graph = 1 (a replay runs no host code that could
+ * keep the record of stored maps), stores all maps.
+ *   nst_job_map_stats: bit l of *stored_mask = conv layer l's map was stored by the last forward pass of `level` (or by a
+ *     request since); 0 before any pass and after a call that sets the job up anew.
+ *   nst_ctx_set_keep_all_maps(ctx, 1): every launch stores its map, as before the elision - the A/B twin in one build;
+ *     losses, gradients, pooled maps, masks and codes are bitwise the same under either setting.  A new context takes
+ *     env NST_KEEP_ALL_MAPS (read once at creation), default 0.  nst_ctx_keep_all_maps: the setting, -1 for a null context. */
+int nst_job_map_stats(nst_ctx* ctx, int level, unsigned* stored_mask);
+int nst_ctx_set_keep_all_maps(nst_ctx* ctx, int enabled);
+int nst_ctx_keep_all_maps(const nst_ctx* ctx);
 /* The image of pyramid level `level` >= 1 that the last closure evaluated - the bicubic 1/2 chain of x
  * (neural_style_transfer.py:170-176) - as (3,h_l,w_l) planar fp32 to out (device).  The total-variation term takes
  * sign(y_i - y_j) of neighbouring pixels: on flat image regions those differences are rounding noise of the down-sampling,
