@@ -27,6 +27,7 @@ NST_COLOR_RGB = 0
 NST_COLOR_LUMINANCE = 1
 NST_POOL_MAX = 0
 NST_POOL_AVG = 1
+NST_MAX_LAPLACIAN = 4
 
 c_float_p = C.POINTER(C.c_float)
 REDUCE_HOOK = C.CFUNCTYPE(None, C.c_void_p)
@@ -71,6 +72,10 @@ SYMBOLS = {
     "nst_job_color": (C.c_int, [c_void]),
     "nst_job_set_pooling": (C.c_int, [c_void, C.c_int]),
     "nst_job_pooling": (C.c_int, [c_void]),
+    "nst_job_set_laplacian": (C.c_int, [c_void, C.c_int, C.POINTER(C.c_int), c_float_p]),
+    "nst_job_laplacian": (C.c_int, [c_void, C.POINTER(C.c_int), C.POINTER(C.c_int), c_float_p]),
+    "nst_job_laplacian_losses": (C.c_int, [c_void, c_void, c_void]),
+    "nst_laplacian_loss": (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, c_void, c_void, c_void]),
     "nst_job_set_style_weights": (C.c_int, [c_void, c_float_p]),
     "nst_job_style_weights": (C.c_int, [c_void, c_float_p]),
     "nst_color_stats": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), c_void]),

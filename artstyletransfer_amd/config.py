@@ -3,6 +3,7 @@ from .color_modes import check_preserve_color
 from .pooling_modes import check_pooling
 from .style_modes import check_style_blend, check_style_layer_weights
 from .regions import check_exclusive, check_regions
+from .laplacian_modes import DEFAULT_POOL, normalize_laplacian
 
 # jobs that may run at once PER GPU (the reference runs everything on device 0; here the
 # scheduler multiplies this by the number of GPUs of the node). Use 1 when levels_num > 2.
@@ -26,7 +27,8 @@ _DEFAULTS = dict(
 # extension, keyword-only: the feature maps the losses read (neural_style_transfer(..., content_layer=, style_layers=,
 # use_relu=)); None = the reference's content 4 / style [0, 1, 2, 3, 5]; colour preservation (preserve_color=); and the
 # pooling of the feature network (pooling=); further style images with their blend (extra_styles=, style_blend=) and the
-# per-layer style weights (style_layer_weights=); and spatial control (content_regions=, style_regions=, region_weights=).
+# per-layer style weights (style_layer_weights=); spatial control (content_regions=, style_regions=, region_weights=); and
+# the Laplacian loss (laplacian_weight=, laplacian_pool=).
 # Not part of the positional order or the repr.
 _KW_ONLY = dict(
     content_layer=None,            # index 0..5 or a name of Vgg19.layer_names
@@ -40,6 +42,8 @@ _KW_ONLY = dict(
     content_regions=None,          # integer label map (H,W) or float stack (R,H,W) in [0,1] over the content image (Gatys et al. 2017)
     style_regions=None,            # the same over the style image: region r of the content takes its style from region r here
     region_weights=None,           # R numbers >= 0: the lambda_r of the regions' terms (None: ones)
+    laplacian_weight=None,         # number or up to 4 numbers >= 0: the gamma_k of the Laplacian loss (Li et al. 2017); None / 0: off
+    laplacian_pool=DEFAULT_POOL,   # integer 1..32 or up to 4 distinct ones: the pool sizes p_k of its entries
 )
 
 
@@ -67,6 +71,7 @@ class Config:
         if self.extra_styles is not None or self.style_blend is not None:
             check_style_blend(self.style_blend, 1 + len(self.extra_styles or ()), style_indices=())
         check_exclusive(check_regions(self.content_regions, self.style_regions, self.region_weights), self.extra_styles)
+        normalize_laplacian(self.laplacian_weight, self.laplacian_pool)
 
     def __repr__(self):
         return "Config(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in _DEFAULTS) + ")"

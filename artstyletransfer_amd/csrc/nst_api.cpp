@@ -148,6 +148,38 @@ int nst_total_variation(nst_ctx* ctx, const float* y, int C, int h, int w, float
     return NST_OK;
 }
 
+// The Laplacian term of one entry on its own (include/nst_hip.h): value = lap_k of y against content, grad (nullable,
+// overwritten) = d lap_k / dy with gamma = 1.  The launches of the closure, on scratch buffers.  Synchronous.
+int nst_laplacian_loss(nst_ctx* ctx, const float* y, const float* content, int C, int h, int w, int p, float* value, float* grad,
+                       void* stream) {
+    NSTCHK(bind(ctx));
+    if (!y || !content || !value) return fail(ctx, NST_E_ARG, "null argument");
+    if (C != 1 && C != 3) return fail(ctx, NST_E_ARG, "C must be 3, or 1 for a luminance plane");
+    if (p < 1 || p > 32) return fail(ctx, NST_E_ARG, "a Laplacian pool size must be 1 .. 32");
+    if (h < 1 || w < 1 || h / p < 3 || w / p < 3) return fail(ctx, NST_E_ARG, "the pooled image must be at least 3x3");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int hk = h / p, wk = w / p;
+    const size_t n = (size_t)(hk - 2) * (wk - 2);
+    Scratch sc(ctx, s);
+    double* pooled = nullptr; double* target = nullptr; float* r = nullptr; double* partial = nullptr;
+    NSTCHK(sc.alloc(&pooled, (size_t)hk * wk));
+    NSTCHK(sc.alloc(&target, n));
+    NSTCHK(sc.alloc(&r, n));
+    NSTCHK(sc.alloc(&partial, LAP_BLOCKS));
+    HIPCHK(ctx, launch_lap_pool(content, C, h, w, p, pooled, s));
+    HIPCHK(ctx, launch_lap_stencil(pooled, hk, wk, nullptr, target, nullptr, nullptr, s));
+    HIPCHK(ctx, launch_lap_pool(y, C, h, w, p, pooled, s));
+    HIPCHK(ctx, launch_lap_stencil(pooled, hk, wk, target, nullptr, r, partial, s));
+    HIPCHK(ctx, launch_lap_value(partial, (double)n, value, s));
+    if (grad) {
+        LapBackward lb{};
+        lb.K = 1; lb.p[0] = p; lb.r[0] = r;
+        lb.coef[0] = (float)(2.0 * (C == 1 ? 3.0 : 1.0) / ((double)n * (double)p * (double)p));
+        HIPCHK(ctx, launch_lap_backward(lb, C, h, w, grad, 0, s));
+    }
+    return sc.finish();
+}
+
 int nst_bicubic_half(nst_ctx* ctx, const float* x, int C, int h, int w, float* y, void* stream) {
     NSTCHK(bind(ctx));
     if (!x || !y || h < 2 || w < 2) return fail(ctx, NST_E_ARG, "bad argument");

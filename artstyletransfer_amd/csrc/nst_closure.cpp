@@ -164,6 +164,42 @@ int guided_fold(nst_ctx* ctx, LevelWs& L, int q, hipStream_t s) {
     return NST_OK;
 }
 
+// ---- the Laplacian loss (include/nst_hip.h has the definition; kernels: laplacian.hip) ---------------------------------
+// forward part of level L on image y: per entry the pooled sum, then D s - target with the SSE partials the loss row reads.
+// as_target: y is the level's content image and D s itself goes to the entry's target.
+int lap_forward(nst_ctx* ctx, LevelWs& L, const float* y, bool as_target, hipStream_t s) {
+    for (int k = 0; k < ctx->lap_k; ++k) {
+        const int p = ctx->lap_pool[k];
+        {
+            Timer t(ctx, s, K_OTHER, 0);
+            HIPCHK(ctx, launch_lap_pool(y, ctx->channels, L.h, L.w, p, L.lap.s[k], s));
+        }
+        Timer t(ctx, s, K_OTHER, 0);
+        if (as_target) HIPCHK(ctx, launch_lap_stencil(L.lap.s[k], L.h / p, L.w / p, nullptr, L.lap.target[k], nullptr, nullptr, s));
+        else HIPCHK(ctx, launch_lap_stencil(L.lap.s[k], L.h / p, L.w / p, L.lap.target[k], nullptr, L.lap.r[k], L.lap.partial[k], s));
+    }
+    return NST_OK;
+}
+// n_k = (hk-2)(wk-2) and coef_k = (float)(gamma_k 2 / (n_k p^2)); a luminance plane takes the sum over the three channels
+double lap_n(const LevelWs& L, int p) { return (double)(L.h / p - 2) * (double)(L.w / p - 2); }
+float lap_coef(float gamma, double n, int p, int channels) {
+    return (float)((double)gamma * 2.0 * (channels == 1 ? 3.0 : 1.0) / (n * (double)p * (double)p));
+}
+// gradient part: one pass that adds every entry's coef_k D^T r_k into the level gradient (after the TV gradient)
+int lap_backward(nst_ctx* ctx, LevelWs& L, float* grad, hipStream_t s) {
+    if (ctx->lap_k < 1) return NST_OK;
+    LapBackward lb{};
+    lb.K = ctx->lap_k;
+    for (int k = 0; k < lb.K; ++k) {
+        lb.p[k] = ctx->lap_pool[k];
+        lb.coef[k] = lap_coef(ctx->lap_gamma[k], lap_n(L, lb.p[k]), lb.p[k], ctx->channels);
+        lb.r[k] = L.lap.r[k];
+    }
+    Timer t(ctx, s, K_OTHER, 0);
+    HIPCHK(ctx, launch_lap_backward(lb, ctx->channels, L.h, L.w, grad, 1, s));
+    return NST_OK;
+}
+
 }  // namespace
 
 namespace nst {
@@ -688,6 +724,7 @@ int batched_backward(nst_ctx* ctx, const float* const* xi, float* const* gi, con
                                          win_means, win_nx, win_ny));
         else
             HIPCHK(ctx, launch_tv_finish(xi[lv[k]], ctx->channels, L.h, L.w, L.tv_partial, tvw, gi[lv[k]], 1, L.tv_means, s));
+        if (!win) NSTCHK(lap_backward(ctx, L, gi[lv[k]], s));
     }
     return NST_OK;
 }
@@ -714,6 +751,8 @@ int closure_batched_forward(nst_ctx* ctx, const float* const* xi, unsigned level
     // (the overlap's split of the style maps - relu1_1 .. relu3_1 on the side stream - is the default taps')
     const bool overlap = ctx->gram_overlap && ctx->conv_mode == 2 && !ctx->use_graph && ctx->side != nullptr && ctx->taps.is_default &&
                          !guided_levels(ctx, lv, n);
+    // the Laplacian term's residuals and partials (nst_job_set_laplacian): pixel space, beside the TV partials
+    for (int k = 0; k < n; ++k) NSTCHK(lap_forward(ctx, ctx->lv[lv[k]], xi[lv[k]], false, s));
     NSTCHK(batched_forward(ctx, xi, lv, n, s, nullptr, overlap ? sw : -1.f));
     NSTCHK(batched_gram(ctx, lv, n, sw, s, overlap ? 0x18u : (1u << ctx->taps.nstyle) - 1u));
     if (overlap) HIPCHK(ctx, hipStreamWaitEvent(s, ctx->side_join, 0));
@@ -758,6 +797,7 @@ int closure_per_level(nst_ctx* ctx, const float* const* xi, float* const* gi, in
         Timer t(ctx, s, K_OTHER, 0);
         HIPCHK(ctx, launch_tv_partial(xi[level], ctx->channels, L.h, L.w, L.tv_partial, s));
     }
+    NSTCHK(lap_forward(ctx, L, xi[level], false, s));
     NSTCHK(forward(ctx, L.acts, xi[level], L.h, L.w, s, tp.top, ctx->channels));
     Inject inj[NL];
     GuidedBwd gbw[kMaxStyle];
@@ -793,9 +833,11 @@ int closure_per_level(nst_ctx* ctx, const float* const* xi, float* const* gi, in
     inj[tp.content].content = true;
     ContentJob cj{L.content_t, L.content_n, content_coef(cw, (double)L.content_n), L.content_partial};
     NSTCHK(backward(ctx, L.acts, inj, &cj, L.gbuf[0], L.gbuf[1], gi[level], L.h, L.w, s, tp.top, tp.top_mask(), ctx->channels));
-    Timer t(ctx, s, K_OTHER, 0);
-    HIPCHK(ctx, launch_tv_finish(xi[level], ctx->channels, L.h, L.w, L.tv_partial, tvw, gi[level], 1, L.tv_means, s));
-    return NST_OK;
+    {
+        Timer t(ctx, s, K_OTHER, 0);
+        HIPCHK(ctx, launch_tv_finish(xi[level], ctx->channels, L.h, L.w, L.tv_partial, tvw, gi[level], 1, L.tv_means, s));
+    }
+    return lap_backward(ctx, L, gi[level], s);
 }
 
 // what the loss-assembly kernel reads: every level's partial sums and normalisers; the rows of levels not in level_mask are zeros
@@ -809,7 +851,10 @@ LossAssembly fill_loss_assembly(const nst_ctx* ctx, unsigned level_mask, float c
         for (int k = 0; k < ctx->taps.nstyle; ++k) { la.lv[i].style_partial[k] = L.style_partial[k]; la.lv[i].style_c[k] = kCout[ctx->taps.style[k]]; la.lv[i].style_w[k] = ctx->style_weight(k); }
         la.lv[i].tv_means = L.tv_means;
         la.lv[i].owned = (int)((level_mask >> i) & 1u);
+        for (int k = 0; k < ctx->lap_k; ++k) { la.lv[i].lap_partial[k] = L.lap.partial[k]; la.lv[i].lap_n[k] = lap_n(L, ctx->lap_pool[k]); }
     }
+    la.nlap = ctx->lap_k; la.lap_out = ctx->lap_vals;
+    for (int k = 0; k < ctx->lap_k; ++k) la.lap_gamma[k] = ctx->lap_gamma[k];
     return la;
 }
 
@@ -970,6 +1015,8 @@ int window_check(nst_ctx* ctx, const float* xs, int row0, int rows, int H0) {
         return fail(ctx, NST_E_STATE, "the stripe closure implements max pooling only (nst_job_set_pooling(ctx, NST_POOL_MAX))");
     if (!ctx->unit_style_weights())
         return fail(ctx, NST_E_STATE, "the stripe closure implements unit style layer weights only (nst_job_set_style_weights)");
+    if (ctx->lap_k > 0)
+        return fail(ctx, NST_E_STATE, "the stripe closure implements no Laplacian loss (nst_job_set_laplacian(ctx, 0, NULL, NULL) switches it off)");
     LevelWs& L = ctx->lv[0];
     if (L.guide.R > 0)
         return fail(ctx, NST_E_STATE, "the stripe closure implements no spatial control (nst_level_set_guidance(ctx, 0, 0, ...) clears it)");
@@ -1040,6 +1087,7 @@ int nst_level_set_targets_blend(nst_ctx* ctx, int level, const float* content, i
     hipStream_t s = enter(ctx, stream);
     LevelWs& L = ctx->lv[level];
     NSTCHK(set_content_target(ctx, level, content, s));
+    NSTCHK(lap_forward(ctx, L, content, true, s));      // D s_k(content): the Laplacian targets are made with the others
     // style: Gt_q = sum_k b^[k][q] G_q(style_k), each image at its own size, in ascending k; the first contributing image
     // writes b^ G, the later ones add to it; an image with b^ = 0 on a map is skipped there, one with b^ = 0 on every map
     // of the set gets no forward pass, and no forward pass goes deeper than the deepest map its image contributes to
@@ -1195,6 +1243,7 @@ int nst_level_set_targets_guided(nst_ctx* ctx, int level, const float* content, 
         return fail(ctx, NST_E_ARG, "a style region has a mass sum t^2 below 1 on a map in use: less than one pixel's worth of guidance");
     g.targets = false;
     NSTCHK(set_content_target(ctx, level, content, s));
+    NSTCHK(lap_forward(ctx, L, content, true, s));
     float* part = nullptr;
     NSTCHK(alloc_acts(ctx, sc.acts, hs, ws));
     NSTCHK(sc.alloc(&part, gram_part_floats_for(tp, hs, ws)));

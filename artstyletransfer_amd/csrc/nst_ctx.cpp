@@ -318,6 +318,7 @@ int alloc_level_image(nst_ctx* ctx, LevelWs& L) {
 
 void free_level(nst_ctx* ctx, LevelWs& L) {
     free_guidance(ctx, L);
+    free_laplacian(ctx, L);
     free_acts(ctx, L.acts);
     dev_free(L.gbuf[0]); dev_free(L.gbuf[1]); dev_free(L.xl); dev_free(L.gxl);
     free_tap_buffers(ctx, L);
@@ -337,6 +338,13 @@ void free_guidance(nst_ctx* ctx, LevelWs& L) {
     for (int k = 0; k < kMaxStyle; ++k) { dev_free(g.gram_t[k]); dev_free(g.S[k]); dev_free(g.partial[k]); }
     if (ctx->bytes >= g.bytes) ctx->bytes -= g.bytes;
     g = Guidance();
+}
+
+void free_laplacian(nst_ctx* ctx, LevelWs& L) {
+    LapLevel& q = L.lap;
+    for (int k = 0; k < NST_LAP_MAX; ++k) { dev_free(q.s[k]); dev_free(q.r[k]); dev_free(q.target[k]); dev_free(q.partial[k]); }
+    if (ctx->bytes >= q.bytes) ctx->bytes -= q.bytes;
+    q = LapLevel();
 }
 
 // What a closure remembered is void once the job changes: the captured graph and the keys it was captured under, and
@@ -602,7 +610,7 @@ void nst_ctx_destroy(nst_ctx* ctx) {
     for (int i = 0; i < NST_MAX_LEVELS; ++i) free_level(ctx, ctx->lv[i]);
     if (ctx->tail) (void)hipEventDestroy(ctx->tail);
     for (int l = 0; l < NL; ++l) { dev_free(ctx->wf[l]); dev_free(ctx->wd[l]); dev_free(ctx->bias[l]); dev_free(ctx->wf_bf[l]); dev_free(ctx->wd_bf[l]); dev_free(ctx->wf_h2[l]); dev_free(ctx->wd_h2[l]); dev_free(ctx->wf_wino[l]); dev_free(ctx->wd_wino[l]); }
-    dev_free(ctx->w11k); dev_free(ctx->w11d); dev_free(ctx->color_scratch);
+    dev_free(ctx->w11k); dev_free(ctx->w11d); dev_free(ctx->color_scratch); dev_free(ctx->lap_vals);
     drop_closure_state(ctx, false);
     if (ctx->gstream) (void)hipStreamDestroy(ctx->gstream);
     if (ctx->side) (void)hipStreamDestroy(ctx->side);
@@ -634,6 +642,7 @@ int nst_job_configure(nst_ctx* ctx, int levels_num, int H0, int W0) {
     drop_closure_state(ctx, false);
     forget_forward_pass(ctx);
     ctx->levels = 0;
+    ctx->lap_k = 0;                      // (the Laplacian setting belongs to the job's geometry: its buffers went with the levels)
     int h = H0, w = W0;
     for (int i = 0; i < levels_num; ++i) {
         LevelWs& L = ctx->lv[i];
@@ -758,6 +767,91 @@ int nst_job_map_stats(nst_ctx* ctx, int level, unsigned* stored_mask) {
 }
 
 int nst_job_pooling(const nst_ctx* ctx) { return ctx ? (ctx->pool_avg ? NST_POOL_AVG : NST_POOL_MAX) : -1; }
+
+// The Laplacian loss (Li et al. 2017; include/nst_hip.h has the definition): up to NST_MAX_LAPLACIAN entries (pool size,
+// weight).  Same life cycle as the pooling: every level's targets go (the Laplacian targets D s_k(content) are made with
+// them), and the captured closure.  Every buffer of the term is allocated here; a refusal changes nothing.
+int nst_job_set_laplacian(nst_ctx* ctx, int K, const int* pool, const float* gamma) {
+    if (ctx) { ++ctx->closure_epoch; ++ctx->ws_seq; }
+    NSTCHK(bind(ctx));
+    if (ctx->levels < 1) return fail(ctx, NST_E_STATE, "nst_job_configure has not been called");
+    if (K < 0 || K > NST_MAX_LAPLACIAN) return fail(ctx, NST_E_ARG, "the number of Laplacian entries must be 0 .. NST_MAX_LAPLACIAN");
+    if (K > 0 && (!pool || !gamma)) return fail(ctx, NST_E_ARG, "null argument");
+    bool positive = false;
+    for (int k = 0; k < K; ++k) {
+        if (pool[k] < 1 || pool[k] > 32) return fail(ctx, NST_E_ARG, "a Laplacian pool size must be 1 .. 32");
+        for (int j = 0; j < k; ++j)
+            if (pool[j] == pool[k]) return fail(ctx, NST_E_ARG, "the Laplacian entries must have distinct pool sizes");
+        if (!(gamma[k] >= 0.f) || std::isinf(gamma[k])) return fail(ctx, NST_E_ARG, "Laplacian weights must be finite and >= 0");
+        positive = positive || gamma[k] > 0.f;
+        for (int i = 0; i < ctx->levels; ++i)
+            if (ctx->lv[i].h / pool[k] < 3 || ctx->lv[i].w / pool[k] < 3)
+                return fail(ctx, NST_E_ARG, "level " + std::to_string(i) + " is too small for Laplacian pool size " + std::to_string(pool[k]) +
+                                            ": the pooled image must be at least 3x3");
+    }
+    if (K > 0 && !positive) return fail(ctx, NST_E_ARG, "at least one Laplacian weight must be positive");
+    // the new buffers beside the old ones: a failed allocation leaves the context as it was
+    LapLevel fresh[NST_MAX_LEVELS];
+    int rc = NST_OK;
+    if (K > 0 && !ctx->lap_vals) rc = dev_alloc_t(ctx, &ctx->lap_vals, (size_t)NST_MAX_LEVELS * NST_LAP_MAX);
+    for (int i = 0; i < ctx->levels && rc == NST_OK; ++i) {
+        LapLevel& q = fresh[i];
+        auto take = [&](auto** p, size_t count) -> int {
+            const int r = dev_alloc_t(ctx, p, count);
+            if (r == NST_OK) q.bytes += std::max<size_t>(count * sizeof(**p), 16);
+            return r;
+        };
+        for (int k = 0; k < K && rc == NST_OK; ++k) {
+            const size_t hk = (size_t)(ctx->lv[i].h / pool[k]), wk = (size_t)(ctx->lv[i].w / pool[k]);
+            rc = take(&q.s[k], hk * wk);
+            if (rc == NST_OK) rc = take(&q.r[k], (hk - 2) * (wk - 2));
+            if (rc == NST_OK) rc = take(&q.target[k], (hk - 2) * (wk - 2));
+            if (rc == NST_OK) rc = take(&q.partial[k], LAP_BLOCKS);
+        }
+    }
+    if (rc != NST_OK) {
+        LevelWs tmp;
+        for (int i = 0; i < ctx->levels; ++i) { tmp.lap = fresh[i]; free_laplacian(ctx, tmp); }
+        return rc;
+    }
+    quiesce(ctx);
+    drop_closure_state(ctx, true);
+    for (int i = 0; i < ctx->levels; ++i) {
+        free_laplacian(ctx, ctx->lv[i]);
+        ctx->lv[i].lap = fresh[i];
+    }
+    ctx->lap_k = K;
+    for (int k = 0; k < NST_LAP_MAX; ++k) {
+        ctx->lap_pool[k] = k < K ? pool[k] : 0;
+        ctx->lap_gamma[k] = k < K ? gamma[k] : 0.f;
+    }
+    if (ctx->lap_vals) HIPCHK(ctx, hipMemset(ctx->lap_vals, 0, (size_t)NST_MAX_LEVELS * NST_LAP_MAX * sizeof(float)));
+    return NST_OK;
+}
+
+int nst_job_laplacian(const nst_ctx* ctx, int* K, int* pool, float* gamma) {
+    if (!ctx) return fail(nullptr, NST_E_ARG, "null context");
+    if (K) *K = ctx->lap_k;
+    for (int k = 0; k < NST_LAP_MAX; ++k) {
+        if (pool) pool[k] = ctx->lap_pool[k];
+        if (gamma) gamma[k] = ctx->lap_gamma[k];
+    }
+    return NST_OK;
+}
+
+// the unweighted lap_k of the last closure, levels x NST_MAX_LAPLACIAN, as the loss rows left them (zeros: levels outside
+// the last level mask, unused entries, no closure yet, term off)
+int nst_job_laplacian_losses(nst_ctx* ctx, float* out, void* stream) {
+    NSTCHK(bind(ctx));
+    if (ctx->levels < 1) return fail(ctx, NST_E_STATE, "nst_job_configure has not been called");
+    if (!out) return fail(ctx, NST_E_ARG, "null argument");
+    hipStream_t s = enter(ctx, stream);
+    const size_t bytes = (size_t)ctx->levels * NST_LAP_MAX * sizeof(float);
+    if (ctx->lap_k > 0 && ctx->lap_vals) HIPCHK(ctx, hipMemcpyAsync(out, ctx->lap_vals, bytes, hipMemcpyDeviceToDevice, s));
+    else HIPCHK(ctx, hipMemsetAsync(out, 0, bytes, s));
+    mark(ctx, s);
+    return NST_OK;
+}
 
 // Per-layer style weights (the w_l of Gatys, Ecker & Bethge 2016): a factor of each map's term in the loss row and in the
 // coefficient of its Gram backward.  The targets do not depend on them and stay; what an optimiser remembers of a closure,

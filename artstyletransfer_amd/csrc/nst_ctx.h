@@ -118,9 +118,21 @@ struct Guidance {
     const float* plane(int scale, int r, int h, int w) const { return planes + plane_off[scale] + (size_t)r * (h >> scale) * (w >> scale); }
 };
 
+// The Laplacian loss of one level (nst_job_set_laplacian; include/nst_hip.h has the definition): per entry k the pooled sum
+// s (h / p, w / p, double), the residual r (float) and the target D s(content) (double; both (h / p - 2, w / p - 2)) and the SSE partials.  Made by
+// the setter, freed when the setting is cleared or the job configured again: a closure allocates nothing.
+struct LapLevel {
+    double* s[NST_LAP_MAX] = {};
+    float* r[NST_LAP_MAX] = {};
+    double* target[NST_LAP_MAX] = {};
+    double* partial[NST_LAP_MAX] = {};
+    size_t bytes = 0;
+};
+
 struct LevelWs {
     int h = 0, w = 0;
     Guidance guide;
+    LapLevel lap;
     ActSet acts;
     float* gbuf[2] = {};
     size_t gbuf_floats = 0;
@@ -202,6 +214,12 @@ struct nst_ctx {
         for (float w : style_w) if (w != 1.f) return false;
         return true;
     }
+    // nst_job_set_laplacian: lap_k entries (pool size, weight), 0 = the term is off; lap_vals: device, NST_MAX_LEVELS x
+    // NST_LAP_MAX floats, the unweighted lap_k of the last closure (written by the loss rows; made by the first setter call)
+    int lap_k = 0;
+    int lap_pool[nst::NST_LAP_MAX] = {};
+    float lap_gamma[nst::NST_LAP_MAX] = {};
+    float* lap_vals = nullptr;
     // bumped on entry to every call that changes what a closure computes (configure, taps, colour, pooling, style weights, targets), failure paths
     // included: an optimiser's remembered closure result is valid only under the epoch it was made in (nst_opt.cpp)
     unsigned long long closure_epoch = 0;
@@ -294,6 +312,7 @@ int bind(nst_ctx* ctx);                            // null check + hipSetDevice:
 // what a closure remembered is void once the job changes (captured graph; drop_targets: every level's targets)
 void drop_closure_state(nst_ctx* ctx, bool drop_targets);
 void free_guidance(nst_ctx* ctx, LevelWs& L);      // the level is unguided afterwards
+void free_laplacian(nst_ctx* ctx, LevelWs& L);     // the level's Laplacian buffers (the setting itself is the context's)
 hipStream_t enter(nst_ctx* ctx, void* stream);     // orders the caller's stream after the context's tail event
 void mark(nst_ctx* ctx, hipStream_t s);            // records the tail event
 void quiesce(nst_ctx* ctx);                        // waits until nothing on the device uses the context's memory

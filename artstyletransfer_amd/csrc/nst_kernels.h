@@ -206,6 +206,29 @@ hipError_t launch_window_scalars(const float* sums, double nx, double ny, float*
 hipError_t launch_prepare_img(const float* hwc, int h, int w, float* chw, hipStream_t stream);
 hipError_t launch_unprepare_img(const float* chw, int h, int w, float* hwc, hipStream_t stream);
 
+// laplacian.hip: the Laplacian loss (include/nst_hip.h has the definition) ----------------------------------------
+constexpr int NST_LAP_MAX = 4;       // = NST_MAX_LAPLACIAN
+constexpr int LAP_BLOCKS = 256;      // SSE partials of one entry
+// s (h / p, w / p) = sum over the channels of the p x p / p mean pool of planar y (C,h,w), C = 3, or 1 = a luminance plane
+// whose three channels pool alike (s = 3 P_p(u)); cell sums in double, s kept in double
+hipError_t launch_lap_pool(const float* y, int C, int h, int w, int p, double* s, hipStream_t stream);
+// target nullptr: target_out (hk-2, wk-2) = D s.  Else r = (float)(D s - target) and partial: LAP_BLOCKS doubles, sums of r^2
+hipError_t launch_lap_stencil(const double* s, int hk, int wk, const double* target, double* target_out, float* r, double* partial,
+                              hipStream_t stream);
+// out[0] = (float)(sum of the LAP_BLOCKS partials / n)
+hipError_t launch_lap_value(const double* partial, double n, float* out, hipStream_t stream);
+// grad (C,h,w) (+)= sum_k coef[k] (D^T r[k])(i / p[k], j / p[k]) over the cells' pixels, ascending k; the caller sets K, p,
+// coef and r, the launcher fills the rest
+struct LapBackward {
+    int K;
+    int p[NST_LAP_MAX];
+    float coef[NST_LAP_MAX];
+    const float* r[NST_LAP_MAX];         // residuals, (h / p - 2, w / p - 2)
+    int hk[NST_LAP_MAX], wk[NST_LAP_MAX];
+    unsigned magic[NST_LAP_MAX];         // ceil(2^32 / p): j / p as a multiply-high
+};
+hipError_t launch_lap_backward(const LapBackward& lb, int C, int h, int w, float* grad, int accumulate, hipStream_t stream);
+
 // loss assembly -----------------------------------------------------------------------------------
 struct LevelLossInputs {
     const double* content_partial;   // MSE_BLOCKS doubles
@@ -215,6 +238,8 @@ struct LevelLossInputs {
     float style_w[6];                // layer weight of each style layer (nst_job_set_style_weights; 1 = the plain mean)
     const float* tv_means;           // 2 floats (mean_x, mean_y)
     int owned;                       // 0: level computed by another rank, its row is written as zeros
+    const double* lap_partial[NST_LAP_MAX];   // Laplacian entries: LAP_BLOCKS doubles each, partial sums of r_k^2
+    double lap_n[NST_LAP_MAX];       // (hk-2)(wk-2) of each entry
 };
 struct LossAssembly {
     LevelLossInputs lv[8];
@@ -222,6 +247,9 @@ struct LossAssembly {
     int nstyle;                      // style layers in use (1..6): the style term is (sum_k w_k mse_k) / nstyle
     float cw, sw, tvw;
     float* out;                      // 4*levels + 1
+    int nlap;                        // Laplacian entries (nst_job_set_laplacian); 0: the row is what it is without the term
+    float lap_gamma[NST_LAP_MAX];
+    float* lap_out;                  // levels x NST_LAP_MAX: the unweighted lap_k (zeros for levels not owned, unused entries)
 };
 hipError_t launch_loss_assemble(const LossAssembly& la, hipStream_t stream);
 

@@ -590,10 +590,12 @@ hipError_t launch_unprepare_img(const float* chw, int h, int w, float* hwc, hipS
 __global__ __launch_bounds__(256) void loss_rows_kernel(LossAssembly la) {
 #pragma clang fp contract(off)
     __shared__ double sh[7][4];
+    __shared__ double shl[NST_LAP_MAX][4];
     const int l = blockIdx.x;
     const LevelLossInputs& in = la.lv[l];
     if (!in.owned) {
         if (threadIdx.x < 4) la.out[4 * l + threadIdx.x] = 0.f;
+        if (la.nlap > 0 && threadIdx.x < NST_LAP_MAX) la.lap_out[NST_LAP_MAX * l + threadIdx.x] = 0.f;
         return;
     }
     double v[7];
@@ -622,6 +624,15 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(LossAssembly la) {
         for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
         if (lane == 0) sh[q][w] = x;
     }
+    // the Laplacian entries' LAP_BLOCKS partials by the same tree (nst_job_set_laplacian; nlap = 0: nothing here runs)
+    if (la.nlap > 0) {
+#pragma unroll
+        for (int k = 0; k < NST_LAP_MAX; ++k) {
+            double x = (k < la.nlap && threadIdx.x < LAP_BLOCKS) ? in.lap_partial[k][threadIdx.x] : 0.0;
+            for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
+            if (lane == 0) shl[k][w] = x;
+        }
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
         double r[7];
@@ -635,7 +646,24 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(LossAssembly la) {
         const float tv = mx * mx + my * my;
         // cw*content + sw*style + tvw*tv, each product and sum rounded (contraction is off here)
         const float t0 = la.cw * content, t1 = la.sw * style, t2 = la.tvw * tv;
-        la.out[4 * l + 0] = (t0 + t1) + t2;
+        float total = (t0 + t1) + t2;
+        if (la.nlap > 0) {
+            // lap = sum_k gamma_k lap_k in ascending k, lap_k = (float)(sum r_k^2 / n_k); then ((.) + tvw*tv) + lap
+            float lap = 0.f;
+            for (int k = 0; k < NST_LAP_MAX; ++k) {
+                float lk = 0.f;
+                if (k < la.nlap) {
+                    double rk = 0.0;
+                    for (int i = 0; i < 4; ++i) rk += shl[k][i];
+                    lk = (float)(rk / in.lap_n[k]);
+                    const float term = la.lap_gamma[k] * lk;
+                    lap = (k == 0) ? term : lap + term;
+                }
+                la.lap_out[NST_LAP_MAX * l + k] = lk;
+            }
+            total = total + lap;
+        }
+        la.out[4 * l + 0] = total;
         la.out[4 * l + 1] = content;
         la.out[4 * l + 2] = style;
         la.out[4 * l + 3] = tv;

@@ -13,6 +13,7 @@ from . import taps as _taps
 from .pooling_modes import check_pooling
 from . import style_modes as _style
 from . import regions as _regions
+from . import laplacian_modes as _lap
 from ._lib import NST_LOSS_ROW, NstError, StepInfo
 
 TAP_CHANNELS = (64, 128, 256, 512, 512, 512)
@@ -89,6 +90,7 @@ class StyleEngine:
         self.channels = 3                        # 1 under set_color("luminance")
         self.pooling = "max"                     # "avg" under set_pooling("avg")
         self.layer_weights = _style.UNIT_WEIGHTS # set_style_weights
+        self.laplacian = None                    # (pools, weights) under set_laplacian
 
     def close(self):
         if getattr(self, "ctx", None):
@@ -106,6 +108,7 @@ class StyleEngine:
         _lib.check(self.ctx, self.lib.nst_job_configure(self.ctx, levels_num, H0, W0), "nst_job_configure")
         self.levels = levels_num
         self.shape = (H0, W0)
+        self.laplacian = None                    # (nst_job_configure clears the Laplacian setting)
 
     def set_taps(self, content_index, style_indices, use_relu: bool = True) -> None:
         """The feature maps the losses read (nst_job_set_taps): a content index and style indices of Vgg19.layer_names
@@ -176,6 +179,52 @@ class StyleEngine:
         """Back to w = 1 on every map, if the weights were changed."""
         if self.layer_weights != _style.UNIT_WEIGHTS:
             self.set_style_weights(_style.UNIT_WEIGHTS)
+
+    def set_laplacian(self, pools, weights) -> None:
+        """The Laplacian loss of the job (nst_job_set_laplacian; Li et al. 2017): pool sizes (integers 1..32, distinct) and
+        their weights gamma >= 0, each a number or a sequence of up to four; the level total gains sum_k gamma_k lap_k.
+        All-zero weights switch the term off.  Needs a configured job; drops the targets of every level: call set_targets
+        again.  ValueError (before the context is touched) for a malformed setting or a level too small for a pool size."""
+        entries = _lap.normalize_laplacian(weights, pools)
+        if entries is None:
+            self.reset_laplacian()
+            return
+        if not self.levels:
+            raise NstError("set_laplacian needs a configured job (configure first)")
+        _lap.check_levels(entries[0], self.levels, *self.shape)
+        k = len(entries[0])
+        pool = (C.c_int * k)(*entries[0])
+        gamma = (C.c_float * k)(*entries[1])
+        try:
+            _lib.check(self.ctx, self.lib.nst_job_set_laplacian(self.ctx, k, pool, gamma), "nst_job_set_laplacian")
+        finally:                                 # the context's setting, whether the call succeeded or not
+            self.laplacian = self.laplacian_setting()
+
+    def laplacian_setting(self):
+        """The context's Laplacian entries as (pools, weights), or None when the term is off (nst_job_laplacian)."""
+        k = C.c_int()
+        pool = (C.c_int * _lib.NST_MAX_LAPLACIAN)()
+        gamma = (C.c_float * _lib.NST_MAX_LAPLACIAN)()
+        _lib.check(self.ctx, self.lib.nst_job_laplacian(self.ctx, C.byref(k), pool, gamma), "nst_job_laplacian")
+        if k.value == 0:
+            return None
+        return tuple(int(v) for v in pool[:k.value]), tuple(float(v) for v in gamma[:k.value])
+
+    def reset_laplacian(self) -> None:
+        """The Laplacian term off, if it was set (drops the targets then, as set_laplacian does)."""
+        if self.laplacian is not None:
+            try:
+                _lib.check(self.ctx, self.lib.nst_job_set_laplacian(self.ctx, 0, None, None), "nst_job_set_laplacian")
+            finally:
+                self.laplacian = self.laplacian_setting()
+
+    def laplacian_losses(self) -> torch.Tensor:
+        """(levels, 4) device tensor: the unweighted lap_k of the last closure per level and entry
+        (nst_job_laplacian_losses); zeros for levels outside the last level mask and for unused entries."""
+        out = torch.empty((self.levels, _lib.NST_MAX_LAPLACIAN), dtype=torch.float32, device=self.device)
+        _lib.check(self.ctx, self.lib.nst_job_laplacian_losses(self.ctx, _ptr(out), _stream(self.device)),
+                   "nst_job_laplacian_losses")
+        return out
 
     def release_job(self) -> None:
         """Give the job's pyramid workspace back (4.7 GB at L=2) and keep the context with its uploaded weights: what an
@@ -573,6 +622,18 @@ class StyleEngine:
                                                           _stream(self.device)), "nst_total_variation")
         return (val, grad) if want_grad else val
 
+    def laplacian_loss(self, y: torch.Tensor, content: torch.Tensor, p: int, want_grad: bool = False):
+        """One entry of the Laplacian loss on its own (nst_laplacian_loss): lap of the (1,C,h,w) image y against content
+        under pool size p, C = 3 or 1 (a luminance plane); with want_grad also d lap / dy."""
+        _chk_dev(y, self.device)
+        _chk_dev(content, self.device, y.shape)
+        b, c, h, w = y.shape
+        val = torch.empty(1, dtype=torch.float32, device=self.device)
+        grad = torch.empty_like(y) if want_grad else None
+        _lib.check(self.ctx, self.lib.nst_laplacian_loss(self.ctx, _ptr(y), _ptr(content), b * c, h, w, int(p), _ptr(val),
+                                                         _ptr(grad), _stream(self.device)), "nst_laplacian_loss")
+        return (val, grad) if want_grad else val
+
     def bicubic_half(self, x: torch.Tensor) -> torch.Tensor:
         _chk_dev(x, self.device)
         b, c, h, w = x.shape
@@ -814,6 +875,8 @@ class PixelOptimizer:
             raise ValueError("content_regions / style_regions cannot be combined with stripe sharding")
         if e.layer_weights != _style.UNIT_WEIGHTS:
             raise ValueError("the stripe closure implements unit style layer weights only (reset_style_weights())")
+        if e.laplacian is not None:
+            raise ValueError("laplacian_weight cannot be combined with stripe sharding (reset_laplacian())")
         contents = list(content_t) if isinstance(content_t, (list, tuple)) else [content_t]
         styles = list(style_t) if isinstance(style_t, (list, tuple)) else [style_t]
         if blend is not None and styles and isinstance(styles[0], torch.Tensor):

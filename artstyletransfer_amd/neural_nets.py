@@ -115,8 +115,8 @@ def lease_engine(device) -> StyleEngine:
 
 
 def return_engine(eng: StyleEngine) -> None:
-    """Back to the per-GPU pool, with unit style layer weights, the default taps, RGB and max pooling: the next job must not
-    inherit this one's."""
+    """Back to the per-GPU pool, with unit style layer weights, the default taps, RGB, max pooling and no Laplacian term: the
+    next job must not inherit this one's."""
     if getattr(eng, "ctx", None) is None:
         return
     idx = eng.device.index
@@ -126,11 +126,12 @@ def return_engine(eng: StyleEngine) -> None:
     if keep:
         try:
             eng.clear_guidance()               # (no region guidance: the re-configuration below drops it with the levels too)
-            eng.release_job()                  # the workspace goes back now, only the weights stay resident
+            eng.release_job()                  # the workspace goes back now, only the weights stay resident (and the Laplacian setting goes)
             eng.reset_style_weights()          # (before the taps: a style set needs a map with a positive weight)
             eng.reset_taps()
             eng.reset_color()
             eng.reset_pooling()
+            eng.reset_laplacian()              # (already off: release_job configured the context anew)
         except Exception:
             keep = False
     if keep:

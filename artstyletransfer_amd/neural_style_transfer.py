@@ -23,6 +23,7 @@ from .neural_nets import lease_engine, return_engine, shared_engine
 from .pooling_modes import check_pooling
 from . import style_modes as _style
 from . import regions as _regions
+from . import laplacian_modes as _lap
 
 # ImageNet statistics (reference :22-23)
 IMAGENET_MEAN_255 = [123.675, 116.28, 103.53]
@@ -96,7 +97,24 @@ class LossBuilder:
         self.__engine.set_taps(*taps, use_relu=use_relu)
         if pooling != "max":
             self.__engine.set_pooling(pooling)
-        self.__engine.set_targets(0, c.contiguous(), target_style_image.contiguous())
+        self.__targets = (c.contiguous(), target_style_image.contiguous())
+        self.__engine.set_targets(0, *self.__targets)
+
+    def set_laplacian(self, laplacian_weight=None, laplacian_pool=_lap.DEFAULT_POOL):
+        """Extension: the Laplacian loss (Li et al. 2017) as one more term of `build` - weight(s) gamma_k and pool size(s)
+        p_k, each a number or a sequence of up to four; the level total gains sum_k gamma_k lap_k (see
+        nst_job_set_laplacian in include/nst_hip.h).  None, 0 or all-zero weights switch it off.  ValueError for a malformed
+        setting or an image too small for a pool size."""
+        entries = _lap.normalize_laplacian(laplacian_weight, laplacian_pool)
+        if entries is not None:
+            _lap.check_levels(entries[0], 1, *self.__engine.shape)
+        if entries is None and self.__engine.laplacian is None:
+            return
+        if entries is None:
+            self.__engine.reset_laplacian()
+        else:
+            self.__engine.set_laplacian(*entries)
+        self.__engine.set_targets(0, *self.__targets)       # (the setting drops them: the Laplacian targets are made with them)
 
     def __del__(self):
         try:
@@ -118,7 +136,7 @@ class _DeviceJob:
     (`_make_job`, tests/test_host_api.py)."""
 
     def __init__(self, device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, taps=None, color=None,
-                 pooling=None, style_weights=None, blend=None, regions=None):
+                 pooling=None, style_weights=None, blend=None, regions=None, laplacian=None):
         self.dev = dev = device
         self.optimizer = None
         self.luminance = color == "luminance"   # the optimised image is u = 255 Y; the yield puts the content's I, Q back
@@ -153,6 +171,8 @@ class _DeviceJob:
                     engine.set_pooling(pooling)
                 if style_weights is not None:       # six per-layer style weights, checked against the taps
                     engine.set_style_weights(style_weights)
+                if laplacian is not None:           # (pools, weights) of the Laplacian loss, normalised
+                    engine.set_laplacian(*laplacian)
                 # blend = (per-level image lists of the extra styles, K x 6 matrix): style 0 is style_imgs
                 all_styles = [style_imgs] + (list(blend[0]) if blend is not None else [])
                 if self.luminance:
@@ -228,9 +248,9 @@ class _DeviceJob:
 
 
 def _make_job(device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, taps=None, color=None, pooling=None,
-              style_weights=None, blend=None, regions=None):
+              style_weights=None, blend=None, regions=None, laplacian=None):
     return _DeviceJob(device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, taps, color, pooling,
-                      style_weights, blend, regions)
+                      style_weights, blend, regions, laplacian)
 
 
 async def _drain(step_future):
@@ -267,6 +287,7 @@ class NeuralStyleTransfer:
         self.__layer_weights = None              # set_style_layer_weights (None: w = 1 on every map)
         self.__blend = None                      # set_style_blend: (extra style levels, blend as given)
         self.__regions = None                    # set_regions: (content stack, style stack, region weights)
+        self.__laplacian = None                  # set_laplacian: (pools, weights)
 
     def set_feature_maps(self, content_layer=None, style_layers=None, use_relu=True):
         """Extension: the feature maps the losses of the next `process` read - a content map and a set of style maps of
@@ -328,6 +349,16 @@ class NeuralStyleTransfer:
         region with a mass sum t^2 below 1 on a map of the style set, or guidance together with a style blend."""
         self.__regions = _regions.check_regions(content_regions, style_regions, region_weights)
 
+    def set_laplacian(self, laplacian_weight=None, laplacian_pool=_lap.DEFAULT_POOL):
+        """Extension: the Laplacian loss (Li, Xu, Nikolova & He 2017) in the next `process`: a pixel-space term that keeps
+        the content's edges.  Per pyramid level and entry k it is gamma_k times the mean squared difference between the
+        Laplacian of the p_k x p_k mean-pooled image and that of the pooled content level (nst_job_set_laplacian in
+        include/nst_hip.h has the definition).  `laplacian_weight`, `laplacian_pool`: each a number or a sequence of up to
+        four (a single weight goes with every pool size); pool sizes are distinct integers in 1..32.  None, 0 or all-zero
+        weights: off; zero-weight entries are dropped.  ValueError for a malformed setting and - in `process`, where the
+        level sizes are known - for a level too small for a pool size."""
+        self.__laplacian = _lap.normalize_laplacian(laplacian_weight, laplacian_pool)
+
     async def process(self, content_imgs, init_img, lr_start, iters_num, content_weight, style_weight, tv_weight,
                       init_img_name):
         # validates the model name exactly as the reference does (ValueError for anything but vgg19)
@@ -346,6 +377,8 @@ class NeuralStyleTransfer:
                 if len(lv) != len(self.__style_imgs):
                     raise ValueError(f"an extra style has {len(lv)} levels, the job has {len(self.__style_imgs)}")
             blend = (self.__blend[0], _style.check_style_blend(self.__blend[1], 1 + len(self.__blend[0]), style_indices=style_set))
+        if self.__laplacian is not None and len(content_imgs):
+            _lap.check_levels(self.__laplacian[0], len(content_imgs), *tuple(content_imgs[0].shape[:2]))
         style_imgs = self.__style_imgs
         regions = None
         if self.__regions is not None:
@@ -379,6 +412,8 @@ class NeuralStyleTransfer:
             extra["blend"] = blend
         if regions is not None:
             extra["regions"] = regions
+        if self.__laplacian is not None:
+            extra["laplacian"] = self.__laplacian
         job = _make_job(self.__device, self.__optimizer_name, style_imgs, content_imgs, init_img, lr_start, **extra)
         cw, sw, tvw = float(content_weight), float(style_weight), float(tv_weight)
         loop = asyncio.get_running_loop()
@@ -436,7 +471,8 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
                                 noise_levels_peripheral_amplitude, noise_levels_dispersion, device=None, *,
                                 content_layer=None, style_layers=None, use_relu=True, preserve_color=None,
                                 pooling="max", extra_styles=None, style_blend=None, style_layer_weights=None,
-                                content_regions=None, style_regions=None, region_weights=None):
+                                content_regions=None, style_regions=None, region_weights=None,
+                                laplacian_weight=None, laplacian_pool=_lap.DEFAULT_POOL):
     """Async generator yielding (percent, HWC float32 image) after every optimiser step
     (reference :229-372). `device` (extension): the GPU to run on; default = current.  `content_layer`,
     `style_layers`, `use_relu` (extension): the feature maps the losses read, see NeuralStyleTransfer.set_feature_maps
@@ -450,7 +486,9 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
     preserve_color="histogram" every style's levels are recoloured with its own statistics, under "luminance" every
     style's luminance is matched to the content's on its own.  `content_regions`, `style_regions`, `region_weights`
     (extension): spatial control, see NeuralStyleTransfer.set_regions; not with `extra_styles`.  They are validated before
-    any GPU work (the masses of the regions on every level included: the level sizes follow from the image sizes)."""
+    any GPU work (the masses of the regions on every level included: the level sizes follow from the image sizes).
+    `laplacian_weight`, `laplacian_pool` (extension): the Laplacian loss, see NeuralStyleTransfer.set_laplacian (None, 0 or
+    all-zero weights: off); validated before any GPU work too, a level too small for a pool size included."""
     taps = _taps.normalize_taps(content_layer, style_layers, use_relu)
     host_image.check_preserve_color(preserve_color)
     check_pooling(pooling)
@@ -460,6 +498,10 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
         style_blend = _style.check_style_blend(style_blend, 1 + len(extra_styles), style_indices=taps[1])
     regions = _regions.check_regions(content_regions, style_regions, region_weights)
     _regions.check_exclusive(regions, extra_styles)
+    laplacian = _lap.normalize_laplacian(laplacian_weight, laplacian_pool)
+    if laplacian is not None:
+        ih, iw = np.shape(content_n_style.content[1])[:2]
+        _lap.check_levels(laplacian[0], max(levels_num, 1), *host_image.level_size(ih, iw, max(levels_num - 1, 0)))
     if regions is not None:
         for stack, img, what in ((regions[0], content_n_style.content[1], "content_regions"),
                                  (regions[1], content_n_style.style[1], "style_regions")):
@@ -503,6 +545,8 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
     nst.set_style_blend(extra_levels, style_blend if extra_levels else None)
     if regions is not None:
         nst.set_regions(regions[0], regions[1], regions[2])
+    if laplacian is not None:
+        nst.set_laplacian(laplacian[1], laplacian[0])
     lr_start = 10.0
     async for img, cur_iter in nst.process(content_levels, init_img, lr_start, iters_num, content_weight,
                                            style_weight, tv_weight, init_name):

@@ -70,6 +70,10 @@ class Task:
         extensions.update({k: getattr(cfg, k) for k in ("extra_styles", "style_blend", "style_layer_weights", "content_regions",
                                                         "style_regions", "region_weights")
                            if getattr(cfg, k, None) is not None})
+        # the Laplacian loss: weight and pool sizes together, when a weight is set
+        if getattr(cfg, "laplacian_weight", None) is not None:
+            extensions["laplacian_weight"] = cfg.laplacian_weight
+            extensions["laplacian_pool"] = getattr(cfg, "laplacian_pool", 4)
         gpu = await self.__slots.acquire()
         self.gpu = gpu
         try:

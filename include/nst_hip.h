@@ -42,6 +42,7 @@ extern "C" {
 #define NST_LOSS_ROW 4      /* per level: total, content, style, tv */
 #define NST_MAX_STYLES 8    /* style images one level's targets may blend (nst_level_set_targets_blend) */
 #define NST_MAX_REGIONS 4   /* regions of spatial control (nst_level_set_guidance) */
+#define NST_MAX_LAPLACIAN 4 /* entries (pool size, weight) of the Laplacian loss (nst_job_set_laplacian) */
 
 typedef struct nst_ctx nst_ctx;
 typedef struct nst_opt nst_opt;
@@ -190,6 +191,54 @@ int nst_job_pooling(const nst_ctx* ctx);
  * nst_job_style_weights writes the current weights to w. */
 int nst_job_set_style_weights(nst_ctx* ctx, const float w[6]);
 int nst_job_style_weights(const nst_ctx* ctx, float w[6]);
+
+/* Laplacian loss (Li, Xu, Nikolova & He, "Laplacian-Steered Neural Style Transfer", ACM MM 2017): a pixel-space term that
+ * keeps the content's edges, a setting of the context.  The reference has no counterpart.
+ *
+ * Entries
+ * - A job has up to NST_MAX_LAPLACIAN entries (p_k, gamma_k).
+ * - The pool size p_k is an integer in 1..32; the entries have distinct pool sizes.
+ * - The weight gamma_k is finite and >= 0, and at least one is > 0.
+ * Term of a level image y, prepared, (3,h,w), and entry k
+ * - s_k(y) = sum_c P_p(y_c), P_p a p x p mean pool with stride p.
+ *   - Sizes floor: hk = h / p, wk = w / p.  Ragged last rows and columns belong to no cell and get no gradient.
+ *   - The cell sum is accumulated in double (exactly: at most 3 x 32 x 32 fp32 values) and s_k stays in double: with prepared
+ *     values near +-120 an fp32 s_k loses the digits that the stencil then needs.
+ * - D is the valid (unpadded) 3x3 stencil [[0,-1,0],[-1,4,-1],[0,-1,0]]; its output is (hk-2, wk-2).  Unpadded, so the
+ *   constant ImageNet means cancel.
+ * - Residual r_k = (float)(D s_k(y) - D s_k(content_l)), both stencils in double, rounded once.
+ * - lap_k = (float)(sum r_k^2 / n_k), n_k = (hk-2)(wk-2), the sum in double in a fixed two-stage order.
+ * - lap = sum_k gamma_k lap_k, in float in ascending k, each product and each sum rounded.
+ * Loss row
+ * - With K > 0 the level total is ((cw content + sw style) + tvw tv) + lap.  With K = 0 it is the expression without the term.
+ * - NST_LOSS_ROW stays 4 and entries 1..3 keep their meaning: the gamma_k carry the term's weight, and nst_closure* /
+ *   nst_opt_step keep their signatures.  nst_job_laplacian_losses returns the lap_k.
+ * Gradient
+ * - d/dy_c(i,j) = coef_k (D^T r_k)(i / p, j / p) for i < hk p, j < wk p.
+ * - coef_k = (float)((double)gamma_k 2 / (n_k p^2)).
+ * - D^T is the full correlation of r_k with the symmetric stencil, zero outside r_k.
+ * - It is accumulated into the level gradient after the total-variation gradient, in ascending k.
+ * Luminance
+ * - Under NST_COLOR_LUMINANCE the term is that of the RGB closure at E(u): s_k = 3 P_p(u), and the gradient with respect
+ *   to u is the sum over the three channels.
+ * No float atomics: a closure with the term is bitwise reproducible, as closure reuse and the lazy backward need.
+ *
+ * nst_job_set_laplacian: K = 0 switches the term off (pool and gamma are ignored).  Needs a configured job (NST_E_STATE
+ * otherwise).  NST_E_ARG, with nothing changed, for a bad K, pool size or gamma, duplicate pool sizes, no positive gamma, or
+ * when any level has h_l / p < 3 or w_l / p < 3.  Life cycle of nst_job_set_pooling: the call waits for the context's work,
+ * drops every level's targets (the Laplacian targets D s_k(content) are made with them: nst_level_set_targets,
+ * nst_level_set_targets_blend and nst_level_set_targets_guided make them from the `content` they are given) and any captured
+ * closure graph, and ends the validity of an optimiser's remembered closure and of a pending nst_closure_backward.  Every
+ * buffer of the term is allocated here, never in a closure.  nst_job_configure clears the setting.  It composes with any
+ * taps, colour mode, pooling, style layer weights, blends, guidance, every conv mode and schedule (use_graph included), the
+ * closure halves and level sharding (rows and gradients add up).  The stripe closure (nst_window_*) returns NST_E_STATE
+ * while K > 0.
+ * nst_job_laplacian: the current setting (any pointer may be NULL; unused entries are zeros).
+ * nst_job_laplacian_losses: the unweighted lap_k of the last closure per level and entry, to out (DEVICE, levels x
+ * NST_MAX_LAPLACIAN floats); levels outside the last level mask and unused entries are zeros.  Asynchronous on `stream`. */
+int nst_job_set_laplacian(nst_ctx* ctx, int K, const int* pool, const float* gamma);
+int nst_job_laplacian(const nst_ctx* ctx, int* K, int pool[NST_MAX_LAPLACIAN], float gamma[NST_MAX_LAPLACIAN]);
+int nst_job_laplacian_losses(nst_ctx* ctx, float* out /* device, levels x NST_MAX_LAPLACIAN */, void* stream);
 
 /* LossBuilder.__init__ (neural_style_transfer.py:68-82): target content representation
  * ReLU(conv4_2) of the content image and the 5 target Gram matrices of the style image of one
@@ -369,7 +418,7 @@ int nst_opt_history(const nst_opt* opt, int* pairs, int* n_iter);
  * reproducible, so when a step starts at bitwise the image the previous step left (a rejected or skipped trial, or an
  * accepted trial whose closure was the last one made), with the same weights and no change to the job in between
  * (nst_job_configure, nst_job_set_taps, nst_job_set_color, nst_job_set_pooling, nst_job_set_style_weights,
- * nst_level_set_targets, nst_level_set_targets_blend), its first closure is served from what
+ * nst_job_set_laplacian, nst_level_set_targets, nst_level_set_targets_blend), its first closure is served from what
  * the optimiser remembers instead of evaluated: same loss row, step counter, lr decay, step info and image.  One
  * device compare of x decides, so the caller may write x between steps.  Never in the sharded modes; Adam never.
  * Changing the setting drops what is remembered. */
@@ -464,6 +513,11 @@ int nst_guided_gram_backward(nst_ctx* ctx, const float* f, size_t N, int C, int 
  * grad (C,h,w) = d tv / d y. */
 int nst_total_variation(nst_ctx* ctx, const float* y, int C, int h, int w, float* value, float* grad,
                         void* stream);
+/* One entry of the Laplacian loss on its own (nst_job_set_laplacian has the definition): y, content device (C,h,w), C = 3, or
+ * 1 with the luminance rule; p the pool size.  value (device scalar) = lap_k; grad (nullable, overwritten) (C,h,w) =
+ * d lap_k / dy, with gamma = 1.  Reads no job state.  Synchronous. */
+int nst_laplacian_loss(nst_ctx* ctx, const float* y, const float* content, int C, int h, int w, int p, float* value,
+                       float* grad /* nullable, overwritten */, void* stream);
 /* F.interpolate(x, size=(h//2,w//2), mode='bicubic') (neural_style_transfer.py:173-176) and its
  * transpose (autograd backward); x (C,h,w) -> y (C,h/2,w/2); gy -> gx (overwritten). */
 int nst_bicubic_half(nst_ctx* ctx, const float* x, int C, int h, int w, float* y, void* stream);
@@ -531,7 +585,8 @@ int nst_luminance_recombine(nst_ctx* ctx, const float* u, const float* content, 
  * Nothing else may run on the context between begin and end.  The stripe closure implements the default feature maps
  * only: after nst_job_set_taps with any other taps both calls return NST_E_STATE, as they do under NST_COLOR_LUMINANCE,
  * under NST_POOL_AVG (nst_job_set_pooling) and under style layer weights other than 1 (nst_job_set_style_weights).  The
- * Gram targets are the level's, so those of nst_level_set_targets_blend are honoured. */
+ * Gram targets are the level's, so those of nst_level_set_targets_blend are honoured.  nst_window_* returns NST_E_STATE
+ * while the Laplacian loss is set (nst_job_set_laplacian with K > 0). */
 int nst_window_sums_count(size_t* count);
 int nst_window_begin(nst_ctx* ctx, const float* xs, int row0, int rows, int H0, float* sums, void* stream);
 int nst_window_end(nst_ctx* ctx, const float* xs, int row0, int rows, int H0, float content_weight, float style_weight,

@@ -1,0 +1,270 @@
+"""CPU: the Laplacian loss option (laplacian_weight=, laplacian_pool=) on the host layers - the one normaliser
+(artstyletransfer_amd/laplacian_modes.py) with every refusal, validation before any GPU work, the too-small-level
+arithmetic, the Config fields and their way through Task, NeuralStyleTransfer.set_laplacian down to the device job (a fake in
+its place), the refusal together with stripe sharding, and the bindings against the header and the built library.  No GPU."""
+import asyncio
+import ctypes as C
+import inspect
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from artstyletransfer_amd import _lib
+from artstyletransfer_amd import laplacian_modes as lap
+
+
+# ---- the normaliser -------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("weight,pool,expected", [
+    (None, 4, None),
+    (0, 4, None),
+    (0.0, (4, 8), None),
+    ((0, 0.0), (4, 8), None),
+    (5.0, 4, ((4,), (5.0,))),
+    (5, 4, ((4,), (5.0,))),
+    (2.5, (4, 8), ((4, 8), (2.5, 2.5))),                       # a single weight goes with every pool size
+    ([1.0, 2.0], [4, 16], ((4, 16), (1.0, 2.0))),
+    ((1.0, 0.0, 3.0), (1, 2, 8), ((1, 8), (1.0, 3.0))),        # zero-weight entries are dropped
+    ((1, 2, 3, 4), (32, 1, 2, 8), ((32, 1, 2, 8), (1.0, 2.0, 3.0, 4.0))),   # the order given is kept
+    (np.float32(1.5), np.int64(2), ((2,), (1.5,))),
+    (np.array([1.0, 2.0]), np.array([2, 4]), ((2, 4), (1.0, 2.0))),
+    ([7.0], 4, ((4,), (7.0,))),
+])
+def test_normaliser_accepts(weight, pool, expected):
+    assert lap.normalize_laplacian(weight, pool) == expected
+
+
+def test_normaliser_defaults():
+    assert lap.normalize_laplacian() is None
+    assert lap.normalize_laplacian(3.0) == ((lap.DEFAULT_POOL,), (3.0,)) and lap.DEFAULT_POOL == 4
+    assert (lap.MAX_ENTRIES, lap.MAX_POOL, lap.MIN_POOLED) == (4, 32, 3)
+
+
+BAD = [
+    (1.0, 0), (1.0, 33), (1.0, -4), (1.0, 4.0), (1.0, 2.5), (1.0, True), (1.0, "4"), (1.0, None), (1.0, ()), (1.0, [4, "8"]),
+    (1.0, (4, 4)), (1.0, (1, 2, 4, 8, 16)), ((1.0, 2.0), (4, 8, 16)), ((1.0, 2.0, 3.0), (4, 8)), ((1.0, 2.0), 4),
+    (-1.0, 4), (float("nan"), 4), (float("inf"), 4), ((1.0, -0.5), (4, 8)), ((1.0, float("nan")), (4, 8)),
+    ("1.0", 4), (True, 4), ((), 4), ((1, 2, 3, 4, 5), (1, 2, 4, 8, 16)), ({4: 1.0}, 4), (1j, 4),
+    (None, 0), (None, (4, 4)), (0, 33),                        # the pool sizes are checked even when the term is off
+]
+
+
+@pytest.mark.parametrize("weight,pool", BAD)
+def test_normaliser_refuses(weight, pool):
+    with pytest.raises(ValueError):
+        lap.normalize_laplacian(weight, pool)
+
+
+# ---- level sizes ----------------------------------------------------------------------------------------------------------
+def test_too_small_level_arithmetic():
+    # 64x96 + 32x48: pool 8 gives 8x12 and 4x6; pool 16 gives 4x6 and 2x3 - level 1 is too small
+    assert lap.pooled_shape(64, 96, 0, 16) == (4, 6) and lap.pooled_shape(64, 96, 1, 16) == (2, 3)
+    lap.check_levels((1, 8), 2, 64, 96)
+    lap.check_levels((16,), 1, 64, 96)
+    with pytest.raises(ValueError, match=r"level 1 is too small for pool 16"):
+        lap.check_levels((16,), 2, 64, 96)
+    with pytest.raises(ValueError, match=r"level 1 is too small for pool 16"):
+        lap.check_levels((1, 16), 2, 64, 96)
+    # 50x76: floors - pool 16 gives 3x4 (the smallest legal shape), pool 17 gives 2x4
+    assert lap.pooled_shape(50, 76, 0, 16) == (3, 4) and lap.pooled_shape(50, 76, 0, 4) == (12, 19)
+    lap.check_levels((16,), 1, 50, 76)
+    with pytest.raises(ValueError, match=r"level 0 is too small for pool 17"):
+        lap.check_levels((17,), 1, 50, 76)
+    # level sizes halve with floor before they pool: 50x76 -> 25x38 -> 12x19; pool 4 on level 2 gives 3x4, pool 5 gives 2x3
+    assert lap.pooled_shape(50, 76, 2, 4) == (3, 4)
+    lap.check_levels((4,), 3, 50, 76)
+    with pytest.raises(ValueError, match=r"level 2 is too small for pool 5"):
+        lap.check_levels((5,), 3, 50, 76)
+    # the width alone can be the short side
+    with pytest.raises(ValueError, match=r"level 0 is too small for pool 32"):
+        lap.check_levels((32,), 1, 512, 95)
+
+
+# ---- before any GPU work ----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("weight,pool", [(-1.0, 4), (1.0, 0), (1.0, (4, 4)), ((1.0, 2.0), (4, 8, 16)), (float("nan"), 4)])
+def test_laplacian_is_validated_before_any_gpu_work(weight, pool, monkeypatch):
+    import neural_style_transfer as nst
+    from artstyletransfer_amd import config, engine, neural_nets
+
+    def no_engine(*a, **k):
+        raise AssertionError("an engine was created before the Laplacian setting was validated")
+
+    monkeypatch.setattr(engine.StyleEngine, "__init__", no_engine)
+    monkeypatch.setattr(neural_nets, "_weights_cache", [])
+
+    async def run():
+        async for _ in nst.neural_style_transfer(None, 1e3, 4e5, 1e2, "adam", "vgg19", "random", 1, 1, 0.0, (), (), (), (),
+                                                  laplacian_weight=weight, laplacian_pool=pool):
+            pass
+
+    with pytest.raises(ValueError):
+        asyncio.run(run())
+    with pytest.raises(ValueError):
+        config.Config(laplacian_weight=weight, laplacian_pool=pool)
+    with pytest.raises(ValueError):
+        nst.NeuralStyleTransfer("cpu", "vgg19", [], "adam").set_laplacian(weight, pool)
+    # the engine's own setter validates before it touches the context
+    eng = object.__new__(engine.StyleEngine)
+    with pytest.raises(ValueError):
+        eng.set_laplacian(pool, weight)
+
+
+def test_too_small_level_is_refused_before_any_gpu_work(monkeypatch):
+    """From the job geometry alone: the engine setter against its configured shape, `process` against its content levels."""
+    import neural_style_transfer as nst
+    from artstyletransfer_amd import engine, math_utils
+    from artstyletransfer_amd import neural_style_transfer as impl
+    eng = object.__new__(engine.StyleEngine)
+    eng.levels, eng.shape, eng.laplacian = 2, (64, 96), None      # (no context: a call that reached it would fail otherwise)
+    with pytest.raises(ValueError, match=r"level 1 is too small for pool 16"):
+        eng.set_laplacian((4, 16), (1.0, 1.0))
+
+    def no_job(*a, **k):
+        raise AssertionError("a device job was made before the level sizes were checked")
+
+    monkeypatch.setattr(impl, "_make_job", no_job)
+    monkeypatch.setattr(math_utils, "prepare_model", lambda name, device: None)
+    job = nst.NeuralStyleTransfer(torch.device("cuda", 0), "vgg19", [], "adam")
+    job.set_laplacian(1.0, 16)
+    levels = [np.zeros((64, 96, 3), np.float32), np.zeros((32, 48, 3), np.float32)]
+
+    async def run():
+        async for _ in job.process(levels, None, 10.0, 0, 1e3, 4e5, 1e2, "x"):
+            pass
+
+    with pytest.raises(ValueError, match=r"level 1 is too small for pool 16"):
+        asyncio.run(run())
+
+
+def test_laplacian_is_keyword_only_in_the_job_driver():
+    import neural_style_transfer as nst
+    pars = inspect.signature(nst.neural_style_transfer).parameters
+    assert pars["laplacian_weight"].kind is inspect.Parameter.KEYWORD_ONLY and pars["laplacian_weight"].default is None
+    assert pars["laplacian_pool"].kind is inspect.Parameter.KEYWORD_ONLY and pars["laplacian_pool"].default == 4
+    assert hasattr(nst.LossBuilder, "set_laplacian") and hasattr(nst.NeuralStyleTransfer, "set_laplacian")
+
+
+# ---- Config / Task ------------------------------------------------------------------------------------------------------------
+def test_config_laplacian_fields():
+    from artstyletransfer_amd import config
+    before = repr(config.Config())
+    c = config.Config(laplacian_weight=(1.0, 2.0), laplacian_pool=(4, 16))
+    assert c.laplacian_weight == (1.0, 2.0) and c.laplacian_pool == (4, 16)
+    d = config.Config()
+    assert d.laplacian_weight is None and d.laplacian_pool == 4
+    assert repr(c) == before and "laplacian" not in before
+    assert config.Config(*range(13)).laplacian_weight is None
+    with pytest.raises(TypeError):
+        config.Config(*range(14))
+    import config as dropin                       # the drop-in module name re-exports the same class
+    assert dropin.Config(laplacian_weight=3.0).laplacian_weight == 3.0
+
+
+@pytest.mark.parametrize("fields,expected", [
+    ({}, {"device"}),
+    ({"laplacian_pool": 8}, {"device"}),                                  # no weight: the term is off, nothing is passed
+    ({"laplacian_weight": 5.0}, {"device", "laplacian_weight", "laplacian_pool"}),
+    ({"laplacian_weight": (1.0, 2.0), "laplacian_pool": (4, 8)}, {"device", "laplacian_weight", "laplacian_pool"}),
+    ({"laplacian_weight": 5.0, "pooling": "avg"}, {"device", "laplacian_weight", "laplacian_pool", "pooling"}),
+])
+def test_task_passes_laplacian_through(monkeypatch, fields, expected):
+    from artstyletransfer_amd import config, task_executor as te
+    seen = []
+
+    async def fake_nst(pair, *args, **kw):
+        seen.append(kw)
+        yield 100.0, np.zeros((2, 2, 3), "float32")
+
+    monkeypatch.setattr(te, "neural_style_transfer", fake_nst)
+
+    async def main():
+        ex = te.Executor(config.Config(iters_num=1, **fields), gpu_slots=te.GpuSlots(per_gpu=1, n_gpus=1))
+        await ex.add_task("t", None)
+        await ex.wait_all()
+
+    asyncio.run(main())
+    assert len(seen) == 1 and set(seen[0]) == expected
+    for k in expected - {"device"}:
+        assert seen[0][k] == fields.get(k, 4)
+
+
+@pytest.mark.parametrize("args,expected", [
+    ((None, 4), {}),
+    ((0.0, (4, 8)), {}),
+    ((5.0, 4), {"laplacian": ((4,), (5.0,))}),
+    (((1.0, 0.0, 2.0), (4, 8, 16)), {"laplacian": ((4, 16), (1.0, 2.0))}),
+])
+def test_process_hands_laplacian_to_the_job(monkeypatch, args, expected):
+    """NeuralStyleTransfer.set_laplacian reaches the device job (a fake in its place), normalised; off passes nothing."""
+    import neural_style_transfer as nst
+    from artstyletransfer_amd import math_utils
+    from artstyletransfer_amd import neural_style_transfer as impl
+    seen = []
+    assert "laplacian" in inspect.signature(impl._make_job).parameters        # (the real one takes what process passes)
+
+    class FakeJob:
+        def close(self):
+            pass
+
+    def fake_make_job(device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, **extra):
+        seen.append(extra)
+        return FakeJob()
+
+    monkeypatch.setattr(impl, "_make_job", fake_make_job)
+    monkeypatch.setattr(math_utils, "prepare_model", lambda name, device: None)
+    job = nst.NeuralStyleTransfer(torch.device("cuda", 0), "vgg19", [], "adam")
+    job.set_laplacian(*args)
+
+    async def run():
+        async for _ in job.process([np.zeros((256, 384, 3), np.float32)], None, 10.0, 0, 1e3, 4e5, 1e2, "x"):
+            pass
+
+    asyncio.run(run())
+    assert seen == [expected]
+
+
+# ---- stripe sharding ----------------------------------------------------------------------------------------------------------
+def test_stripe_sharding_refuses_the_laplacian_term():
+    """PixelOptimizer.shard_stripes on an engine that carries the setting: ValueError before any stripe engine is made."""
+    from artstyletransfer_amd import engine, style_modes
+
+    class FakeEngine:
+        levels = 1
+        layer_weights = style_modes.UNIT_WEIGHTS
+        laplacian = ((4,), (1.0,))
+        channels = 3
+
+        def guidance(self, level):
+            return 0, (), None
+
+    opt = object.__new__(engine.PixelOptimizer)
+    opt.engine = FakeEngine()
+    with pytest.raises(ValueError, match="stripe sharding"):
+        opt.shard_stripes(0, 2, None, None, None, dist_mod=object())
+    src = inspect.getsource(engine.PixelOptimizer.shard_stripes)
+    assert src.index("e.laplacian is not None") < src.index("StyleEngine(weights")
+
+
+# ---- bindings -------------------------------------------------------------------------------------------------------------------
+def test_laplacian_bindings_match_header_and_library():
+    hdr = open(os.path.join(os.path.dirname(_lib._HERE), "include", "nst_hip.h")).read()
+    assert "#define NST_MAX_LAPLACIAN 4" in hdr and _lib.NST_MAX_LAPLACIAN == 4 == lap.MAX_ENTRIES
+    assert "#define NST_LOSS_ROW 4 " in hdr                           # the loss row keeps its layout
+    assert re.search(r"int nst_job_set_laplacian\(nst_ctx\* ctx, int K, const int\* pool, const float\* gamma\);", hdr)
+    assert re.search(r"int nst_job_laplacian\(const nst_ctx\* ctx, int\* K, int pool\[NST_MAX_LAPLACIAN\], float gamma\[NST_MAX_LAPLACIAN\]\);", hdr)
+    assert re.search(r"int nst_job_laplacian_losses\(nst_ctx\* ctx, float\* out[^;]*void\* stream\);", hdr)
+    assert re.search(r"int nst_laplacian_loss\(nst_ctx\* ctx, const float\* y, const float\* content, int C, int h, int w, int p, float\* value,", hdr)
+    assert re.search(r"nst_window_\* returns NST_E_STATE\s+\* while the Laplacian loss is set", hdr)
+    assert _lib.SYMBOLS["nst_job_set_laplacian"] == (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float)])
+    assert _lib.SYMBOLS["nst_job_laplacian_losses"] == (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p])
+    lib = C.CDLL(_lib.LIB_PATH)                      # the built library exports all four
+    for name in ("nst_job_set_laplacian", "nst_job_laplacian", "nst_job_laplacian_losses", "nst_laplacian_loss"):
+        assert hasattr(lib, name), name
+    # without a context: an error code, no crash (bind() refuses a null context)
+    lib.nst_job_set_laplacian.restype = C.c_int
+    lib.nst_job_set_laplacian.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lib.nst_job_laplacian.restype = C.c_int
+    lib.nst_job_laplacian.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    assert lib.nst_job_set_laplacian(None, 0, None, None) < 0 and lib.nst_job_laplacian(None, None, None, None) < 0
