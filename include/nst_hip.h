@@ -38,7 +38,7 @@ extern "C" {
                                   entry point named in nst_last_error instead */
 
 #define NST_VGG19_CONVS 13  /* conv1_1 ... conv5_1 (torchvision features[0:30]) */
-#define NST_MAX_LEVELS 8
+#define NST_MAX_LEVELS 8    /* jobs of 4 .. 7 levels are held to the CPU oracle whole, the 8-level job in pieces: tests/test_hip_deep_pyramids.py */
 #define NST_LOSS_ROW 4      /* per level: total, content, style, tv */
 #define NST_MAX_STYLES 8    /* style images one level's targets may blend (nst_level_set_targets_blend) */
 #define NST_MAX_REGIONS 4   /* regions of spatial control (nst_level_set_guidance) */
@@ -129,7 +129,9 @@ int nst_job_configure(nst_ctx* ctx, int levels_num, int H0, int W0);
  * re-sizes the target buffers of every configured level and drops their targets (a closure returns NST_E_STATE until
  * nst_level_set_targets has run again) and any captured closure graph.  nst_vgg_features / nst_vgg_activations return
  * conv5_1 before its ReLU under use_relu = 0.  The stripe closure (nst_window_*) implements the default taps only and
- * returns NST_E_STATE under any other. */
+ * returns NST_E_STATE under any other.  The full range is held to the CPU oracle: single maps and pairs in
+ * tests/test_hip_taps.py, all six style maps (style_mask 0x3F, also with a content map below the top of the chain and with
+ * unequal nst_job_set_style_weights) in tests/test_hip_deep_pyramids.py. */
 int nst_job_set_taps(nst_ctx* ctx, int content_index, unsigned style_mask, int use_relu);
 
 /* Colour preservation, luminance-only transfer (Gatys, Bethge, Hertzmann & Shechtman, "Preserving Color in Neural

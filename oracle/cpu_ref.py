@@ -216,16 +216,24 @@ def level_loss(x: torch.Tensor, tg: LevelTargets, weights, cw: float, sw: float,
 
 def closure_eval(x: torch.Tensor, targets: Sequence[LevelTargets], weights,
                  cw: float, sw: float, tvw: float, decisions: Optional[Sequence[Decisions]] = None,
-                 record: Optional[list] = None):
+                 record: Optional[list] = None, only_levels: Optional[Sequence[int]] = None):
     """One closure evaluation (neural_style_transfer.py:152-199, without the LR decay and
     prints): returns (total_loss float32 tensor, grad (1,3,H,W), per-level rows
     [(total, content, style, tv), ...]).  `decisions` (one Decisions per level): evaluate under another pass's
-    ReLU / pooling decisions; `record` receives one list of 13 pre-activations per level."""
+    ReLU / pooling decisions; `record` receives one list of 13 pre-activations per level.
+    `only_levels` (no counterpart in the reference; the library's nst_closure_levels): the closure of these pyramid levels
+    alone - the bicubic chain from x is formed as ever, the levels left out add no loss (their rows are zeros, their
+    `record` entry is None) and their entries of `targets` / `decisions` are not read (None will do)."""
     x = x.detach().clone().requires_grad_(True)
     levels, total, rows = [x], None, []
     for i, tg in enumerate(targets):
         if i > 0:      # same op order as the reference: autograd's accumulation order follows it
             levels.append(bicubic_half(levels[i - 1]))
+        if only_levels is not None and i not in only_levels:
+            rows.append((0.0, 0.0, 0.0, 0.0))
+            if record is not None:
+                record.append(None)
+            continue
         rec = None
         if record is not None:
             rec = []

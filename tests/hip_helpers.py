@@ -115,12 +115,16 @@ def check_summary(t, fx, key, atol, rtol=0.0):
 
 
 # ---- comparison under equal ReLU / pooling decisions -------------------------------------------------------------
-def device_decisions(eng, x=None):
+def device_decisions(eng, x=None, only_levels=None):
     """cpu_ref.Decisions of the closure the engine evaluated last, one per pyramid level: ReLU / pooling decisions from
     the level's activations and, when the level-0 image x is given, the signs its total-variation term took (levels >= 1:
-    from the device's own down-sampled image, nst_level_image)."""
+    from the device's own down-sampled image, nst_level_image).  `only_levels`: None for the levels outside it (a closure
+    of a level mask; the top levels of a deep job are gigabytes of activations nobody then copies)."""
     out = []
     for l in range(eng.levels):
+        if only_levels is not None and l not in only_levels:
+            out.append(None)
+            continue
         img = None
         if x is not None:
             img = (x if l == 0 else eng.level_image(l)).cpu().reshape(1, 3, *eng.level_shape(l))
@@ -242,6 +246,30 @@ def closure_vs_oracle_under_equal_decisions(eng, xt, tg, weights, what, terms=TE
         add = float(np.linalg.norm(parts["all"] - s) / np.linalg.norm(s))
         report(f"closure {what}: |g(all) - sum of the terms| / |.| = {add:.1e}")
         assert add < 2e-6, (what, add)
+
+
+def masked_closure_vs_oracle_under_device_decisions(eng, xt, tg, weights, mask, what, loss_tol=1e-5, grad_tol=BULK_RTOL):
+    """nst_closure_levels of the levels in `mask` against the oracle evaluated on exactly those levels (cpu_ref.closure_eval
+    with only_levels: the bicubic chain from x, the level losses of the mask, autograd to x) under the DEVICE pass's ReLU /
+    pooling / TV-sign decisions, at the tolerances of closure_vs_oracle_under_equal_decisions: total 1e-5, rows 2e-5, the
+    whole gradient 2e-5 rel-L2.  `tg`: one cpu_ref.LevelTargets per level, None outside the mask.  Returns the device's
+    (gradient, losses)."""
+    nlev = eng.levels
+    own = [l for l in range(nlev) if (mask >> l) & 1]
+    xd = dev(xt)
+    grad, losses = eng.closure_levels(xd, CW, SW, TVW, mask)
+    dec = device_decisions(eng, xd, only_levels=own)
+    loss, g_ref, rows = cpu_ref.closure_eval(xt, tg, weights, CW, SW, TVW, decisions=dec, only_levels=own)
+    got = losses.cpu().numpy()
+    e_l = abs(float(got[-1]) - float(loss)) / abs(float(loss))
+    e_g = rel_l2(grad.cpu().numpy(), g_ref.numpy())
+    report(f"masked closure {what} (mask {mask:#b}): total rel {e_l:.2e}, gradient rel-L2 under equal decisions {e_g:.2e}")
+    assert e_l < loss_tol, (what, e_l)
+    check_rows(got[:-1].reshape(nlev, 4)[own], np.array(rows)[own], 2 * loss_tol)
+    outside = [l for l in range(nlev) if l not in own]
+    assert not got[:-1].reshape(nlev, 4)[outside].any()                    # rows of the levels left out are zeros
+    assert e_g < grad_tol, (what, e_g)
+    return grad, losses
 
 
 def pytest_approx(value, rel):
