@@ -76,6 +76,10 @@ SYMBOLS = {
     "nst_job_laplacian": (C.c_int, [c_void, C.POINTER(C.c_int), C.POINTER(C.c_int), c_float_p]),
     "nst_job_laplacian_losses": (C.c_int, [c_void, c_void, c_void]),
     "nst_laplacian_loss": (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, c_void, c_void, c_void]),
+    "nst_job_set_gram_shift": (C.c_int, [c_void, c_float_p, C.c_uint]),
+    "nst_job_gram_shift": (C.c_int, [c_void, c_float_p, C.POINTER(C.c_uint)]),
+    "nst_level_gram_offsets": (C.c_int, [c_void, C.c_int, C.c_int, c_void, c_void]),
+    "nst_gram_shifted": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, c_void, c_void, c_void]),
     "nst_job_set_style_weights": (C.c_int, [c_void, c_float_p]),
     "nst_job_style_weights": (C.c_int, [c_void, c_float_p]),
     "nst_color_stats": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), c_void]),

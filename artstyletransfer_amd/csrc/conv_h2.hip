@@ -1293,7 +1293,7 @@ struct H2BatchTiles {
         int i = 0;
         while (i + 1 < b.n && sp_all >= b.img[i].tile_end) ++i;
         const ConvImage& im = b.img[i];
-        p.in = im.in; p.wt = nullptr; p.wt_bf = nullptr; p.bias = b.bias; p.addend = im.addend; p.mask = im.mask; p.out = im.out;
+        p.in = im.in; p.wt = nullptr; p.wt_bf = nullptr; p.bias = im.bias ? im.bias : b.bias; p.addend = im.addend; p.mask = im.mask; p.out = im.out;
         p.H = im.H; p.W = im.W; p.Cin = b.Cin; p.Cout = b.Cout; p.relu = b.relu;
         p.tiles_x = im.tiles_x; p.tiles_y = 0; p.partial = nullptr; p.partial_floats = 0; p.ksplit = 1;
         p.in2 = im.in2; p.Cin2 = b.Cin2; p.wt2_bf = nullptr; p.bits_out = im.bits_out; p.bits_in = im.bits_in;

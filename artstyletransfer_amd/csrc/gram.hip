@@ -177,10 +177,14 @@ struct GramH2Cfg {
 // GUIDED: the guided Gram sum_p t(p)^2 F(p) F(p)^T - every pixel row is multiplied by t(p) = guide[p] as it is staged.
 // t is in [0,1], so the map's recorded absmax still bounds the operand.  t is read through a buffer descriptor of this
 // split's pixels, as the map is: the pixels of a ragged last group beyond p1 read t = 0 (and F = 0).
-template <int TS, bool GUIDED = false>
+// SHIFT: the shifted Gram sum_p (F(p) + o)(F(p) + o)^T (gram_shift.hip has the rest) - o[channel] is added to every staged
+// value.  A unit's channel is fixed, so that is one scalar per unit, read once.  `amax` is then the record of the SHIFTED
+// operand (launch_gram_offsets writes it): the map's own does not bound F + o.  A pixel beyond p1 reads F = 0 through the
+// range check and must contribute 0, not o: the staged value of such a pixel is forced to zero.
+template <int TS, bool GUIDED = false, bool SHIFT = false>
 __device__ __forceinline__ void gram_h2_body(const float* __restrict__ f, size_t N, int C, int nsplit, size_t pix_per_split,
                                              const unsigned* __restrict__ amax, float* __restrict__ part, const int bid,
-                                             const float* __restrict__ guide = nullptr) {
+                                             const float* __restrict__ guide = nullptr, const float* __restrict__ offs = nullptr) {
     using G = GramH2Cfg<TS>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_h2[];
     const int tid = threadIdx.x;
@@ -223,6 +227,14 @@ __device__ __forceinline__ void gram_h2_body(const float* __restrict__ f, size_t
     __amdgpu_buffer_rsrc_t grsrc = rsrc;
     if constexpr (GUIDED)
         grsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(guide) + p0, 0, (p0 < p1) ? (unsigned)((p1 - p0) * 4) : 0u, 0x00020000);
+    [[maybe_unused]] float ov[G::SIDES][G::PER_T];
+    if constexpr (SHIFT) {
+#pragma unroll
+        for (int sd = 0; sd < G::SIDES; ++sd)
+#pragma unroll
+            for (int i = 0; i < G::PER_T; ++i) ov[sd][i] = offs[(sd == 0 ? ti : tj) * TS + (tid + i * 256) % TS];
+    }
+    [[maybe_unused]] const int npix = (p0 < p1) ? (int)(p1 - p0) : 0;      // pixels of this split (one split's bytes fit 32 bits)
     auto load = [&](int chunk) {
         const unsigned base = (unsigned)((size_t)chunk * G::KP * (size_t)C * 4);
         float tg[G::PER_T][8];
@@ -248,6 +260,7 @@ __device__ __forceinline__ void gram_h2_body(const float* __restrict__ f, size_t
                 for (int j = 0; j < 8; ++j) {
                     st[sd][i][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, voff, base + (unsigned)(j * C * 4), 0));
                     if constexpr (GUIDED) st[sd][i][j] *= tg[i][j];
+                    if constexpr (SHIFT) st[sd][i][j] = (chunk * G::KP + gg * 8 + j < npix) ? st[sd][i][j] + ov[sd][i] : 0.f;
                 }
             }
         }
@@ -397,6 +410,22 @@ __global__ __launch_bounds__(256, 2) void gram_h2_guided_batch_kernel(GramBatch 
                            (int)blockIdx.x - (i ? b.it[i - 1].part_end : 0), it.guide);
 }
 
+// the shifted forms (gram_shift.hip has the rest of the shifted / centred statistic)
+template <int TS>
+__global__ __launch_bounds__(256, 2) void gram_h2_shift_kernel(const float* __restrict__ f, size_t N, int C, int nsplit,
+                                                               size_t pix_per_split, const unsigned* __restrict__ amax,
+                                                               float* __restrict__ part, const float* __restrict__ offs) {
+    gram_h2_body<TS, false, true>(f, N, C, nsplit, pix_per_split, amax, part, blockIdx.x, nullptr, offs);
+}
+template <int TS>
+__global__ __launch_bounds__(256, 2) void gram_h2_shift_batch_kernel(GramBatch b) {
+    int i = 0;
+    while (i + 1 < b.n && (int)blockIdx.x >= b.it[i].part_end) ++i;
+    const GramItem& it = b.it[i];
+    gram_h2_body<TS, false, true>(it.f, it.N, it.C, it.nsplit, it.pix_per_split, it.amax, it.part,
+                                  (int)blockIdx.x - (i ? b.it[i - 1].part_end : 0), nullptr, it.offset);
+}
+
 // generic fallback for channel counts that are not a multiple of 64 (unit-parity API only)
 __global__ void gram_generic_kernel(const float* __restrict__ f, size_t N, int C, float* __restrict__ part) {
     const int i = blockIdx.x / C, j = blockIdx.x % C;
@@ -449,6 +478,18 @@ hipError_t gram_init_device() {
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gram_h2_batch_kernel<64>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, GramH2Cfg<64>::LDS_BYTES);
     if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gram_h2_shift_kernel<128>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, GramH2Cfg<128>::LDS_BYTES);
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gram_h2_shift_kernel<64>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, GramH2Cfg<64>::LDS_BYTES);
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gram_h2_shift_batch_kernel<128>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, GramH2Cfg<128>::LDS_BYTES);
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gram_h2_shift_batch_kernel<64>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, GramH2Cfg<64>::LDS_BYTES);
+    if (e != hipSuccess) return e;
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gram_h2_guided_kernel<128>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, GramH2Cfg<128>::LDS_BYTES);
     if (e != hipSuccess) return e;
@@ -466,9 +507,10 @@ hipError_t gram_init_device() {
 }
 
 hipError_t launch_gram_partial(const float* f, size_t N, int C, int nsplit, const unsigned* amax, float* part,
-                               hipStream_t stream, const float* guide) {
+                               hipStream_t stream, const float* guide, const float* offset) {
     const int ts = gram_ts(C);
-    if (guide && (ts == 0 || !amax)) return hipErrorInvalidValue;
+    if ((guide || offset) && (ts == 0 || !amax)) return hipErrorInvalidValue;
+    if (guide && offset) return hipErrorInvalidValue;
     if (ts == 0) {
         hipLaunchKernelGGL(gram_generic_kernel, dim3(C * C), dim3(256), 0, stream, f, N, C, part);
         return hipGetLastError();
@@ -489,6 +531,14 @@ hipError_t launch_gram_partial(const float* f, size_t N, int C, int nsplit, cons
         else
             hipLaunchKernelGGL(gram_h2_guided_kernel<64>, dim3(pairs * nsplit), dim3(256), GramH2Cfg<64>::LDS_BYTES, stream, f, N, C,
                                nsplit, pix_per_split, amax, part, guide);
+    } else if (offset) {
+        if (!h2) return hipErrorInvalidValue;
+        if (ts == 128)
+            hipLaunchKernelGGL(gram_h2_shift_kernel<128>, dim3(pairs * nsplit), dim3(256), GramH2Cfg<128>::LDS_BYTES, stream, f, N, C,
+                               nsplit, pix_per_split, amax, part, offset);
+        else
+            hipLaunchKernelGGL(gram_h2_shift_kernel<64>, dim3(pairs * nsplit), dim3(256), GramH2Cfg<64>::LDS_BYTES, stream, f, N, C,
+                               nsplit, pix_per_split, amax, part, offset);
     } else if (h2 && ts == 128) {
         hipLaunchKernelGGL(gram_h2_kernel<128>, dim3(pairs * nsplit), dim3(256), GramH2Cfg<128>::LDS_BYTES, stream, f, N, C,
                            nsplit, pix_per_split, amax, part);
@@ -678,6 +728,11 @@ hipError_t launch_gram_batch(const GramBatch& b0, hipStream_t stream) {
     const bool guided = b0.it[0].guide != nullptr;
     for (int i = 0; i < b0.n; ++i)
         if ((b0.it[i].guide != nullptr) != guided) return hipErrorInvalidValue;
+    // ... and shifted as a whole (every item carries its offsets and the record of its shifted operand), never both
+    const bool shifted = b0.it[0].offset != nullptr;
+    for (int i = 0; i < b0.n; ++i)
+        if ((b0.it[i].offset != nullptr) != shifted) return hipErrorInvalidValue;
+    if (guided && shifted) return hipErrorInvalidValue;
     // partial products: one launch per tile shape
     for (int ts = 128; ts >= 64; ts -= 64) {
         GramBatch b{};
@@ -701,6 +756,8 @@ hipError_t launch_gram_batch(const GramBatch& b0, hipStream_t stream) {
         const int blocks = b.it[b.n - 1].part_end;
         if (guided && ts == 128) hipLaunchKernelGGL(gram_h2_guided_batch_kernel<128>, dim3(blocks), dim3(256), GramH2Cfg<128>::LDS_BYTES, stream, b);
         else if (guided) hipLaunchKernelGGL(gram_h2_guided_batch_kernel<64>, dim3(blocks), dim3(256), GramH2Cfg<64>::LDS_BYTES, stream, b);
+        else if (shifted && ts == 128) hipLaunchKernelGGL(gram_h2_shift_batch_kernel<128>, dim3(blocks), dim3(256), GramH2Cfg<128>::LDS_BYTES, stream, b);
+        else if (shifted) hipLaunchKernelGGL(gram_h2_shift_batch_kernel<64>, dim3(blocks), dim3(256), GramH2Cfg<64>::LDS_BYTES, stream, b);
         else if (ts == 128) hipLaunchKernelGGL(gram_h2_batch_kernel<128>, dim3(blocks), dim3(256), GramH2Cfg<128>::LDS_BYTES, stream, b);
         else hipLaunchKernelGGL(gram_h2_batch_kernel<64>, dim3(blocks), dim3(256), GramH2Cfg<64>::LDS_BYTES, stream, b);
         hipError_t e = hipGetLastError();

@@ -82,6 +82,38 @@ int nst_gram(nst_ctx* ctx, const float* f, int C, int h, int w, int normalize, f
     return sc.finish();
 }
 
+// the shifted / centred statistic alone (nst_job_set_gram_shift has the definition), beside nst_gram
+int nst_gram_shifted(nst_ctx* ctx, const float* f, int C, int h, int w, int normalize, int center, float shift, float* gram,
+                     float* offset_out, void* stream) {
+    NSTCHK(bind(ctx));
+    if (!f || !gram || C < 1 || h < 1 || w < 1) return fail(ctx, NST_E_ARG, "bad argument");
+    if (!std::isfinite(shift) || (center && shift != 0.f)) return fail(ctx, NST_E_ARG, "shift must be finite, and 0 for a centred Gram");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!center && shift == 0.f) {
+        // the plain statistic, by the plain kernels: bitwise nst_gram
+        if (offset_out) HIPCHK(ctx, hipMemsetAsync(offset_out, 0, (size_t)C * sizeof(float), s));
+        return nst_gram(ctx, f, C, h, w, normalize, gram, stream);
+    }
+    if (ctx->conv_mode != 2) return fail(ctx, NST_E_STATE, "the shifted Gram runs in the f16x2 arithmetic only (NST_CONV unset)");
+    if (!(C == 64 || C % 128 == 0) || C > 1024) return fail(ctx, NST_E_ARG, "the shifted Gram takes C = 64 or a multiple of 128, at most 1024");
+    const size_t N = (size_t)h * w;
+    Scratch sc(ctx, s);
+    float* nhwc = nullptr; float* part = nullptr; unsigned* amax = nullptr; float* words = nullptr; double* sums = nullptr;
+    NSTCHK(sc.alloc(&nhwc, N * C));
+    NSTCHK(sc.alloc(&part, (size_t)gram_nsplit(C, N) * C * C));
+    NSTCHK(sc.alloc(&amax, (size_t)NST_AMAX_SLOTS));
+    NSTCHK(sc.alloc(&words, (size_t)C + NST_AMAX_SLOTS));
+    if (center) NSTCHK(sc.alloc(&sums, (size_t)GS_PART_DOUBLES));
+    if (launch_chw_to_hwc(f, C, h, w, nhwc, s) != hipSuccess) return fail(ctx, NST_E_HIP, "chw_to_hwc launch failed");
+    if (launch_zero(amax, NST_AMAX_SLOTS, s) != hipSuccess || launch_absmax_slots(nhwc, N * C, amax, s) != hipSuccess)
+        return fail(ctx, NST_E_HIP, "absmax launch failed");
+    const ShiftedGram sg{shift, center ? 1 : 0, words, reinterpret_cast<unsigned*>(words + C), sums, nullptr};
+    NSTCHK(gram_shifted_of(ctx, nhwc, N, C, amax, sg, normalize ? (float)((double)C * h * w) : 1.f, part, nullptr, 0.f, gram, nullptr, nullptr,
+                           nullptr, nullptr, s));
+    if (offset_out) HIPCHK(ctx, hipMemcpyAsync(offset_out, words, (size_t)C * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return sc.finish();
+}
+
 int nst_guided_gram_backward(nst_ctx* ctx, const float* f, size_t N, int C, int R, const float* planes, const float* S,
                              const float* addend, const unsigned* relu_bits, float* out, unsigned* amax_slots, void* stream) {
     NSTCHK(bind(ctx));

@@ -278,6 +278,7 @@ int backward(nst_ctx* ctx, ActSet& a, const Inject* inj, const ContentJob* cj, f
             ConvParams p{};
             p.in = a.act[l]; p.wt = inj[l].S; p.out = cur; p.mask = top_mask ? a.act[l] : nullptr;
             p.addend = content ? oth : nullptr;
+            p.bias = inj[l].bias;                  // (a shifted Gram: F S + r, then the addend and the mask)
             p.H = a.h[l]; p.W = a.w[l]; p.Cin = kCout[l]; p.Cout = kCout[l];
             Timer t(ctx, s, K_GRAM, conv_flops(p.H, p.W, p.Cin, p.Cout, 1));
             HIPCHK(ctx, launch_conv_mfma(p, 1, s));
@@ -342,10 +343,11 @@ int backward(nst_ctx* ctx, ActSet& a, const Inject* inj, const ContentJob* cj, f
                 // Gram backward rides on this launch as a second K source: acc += act[m] * S
                 p.in2 = a.act[m]; p.Cin2 = kCout[m]; p.wt2_bf = in.S_bf;
                 p.wt2_f32 = in.S; p.amax_in2 = amax_act(a, m); p.amax_w2 = in.S_amax;
+                p.bias = in.bias;                  // (a shifted Gram's row bias: after the scale, before the addend and the mask)
                 extra_flops = conv_flops(a.h[m], a.w[m], kCout[m], kCout[m], 1);
             } else if (in.S) {
                 ConvParams q{};
-                q.in = a.act[m]; q.wt = in.S; q.out = oth; q.addend = p.addend;
+                q.in = a.act[m]; q.wt = in.S; q.out = oth; q.addend = p.addend; q.bias = in.bias;
                 q.H = a.h[m]; q.W = a.w[m]; q.Cin = kCout[m]; q.Cout = kCout[m];
                 Timer t(ctx, s, K_GRAM, conv_flops(q.H, q.W, q.Cin, q.Cout, 1));
                 HIPCHK(ctx, launch_conv_mfma(q, 1, s));
@@ -378,6 +380,37 @@ int gram_of(nst_ctx* ctx, const float* f_nhwc, size_t N, int C, const unsigned* 
     Timer t(ctx, s, K_OTHER, 0);
     HIPCHK(ctx, launch_gram_finish(part, gram_nslabs(C, ns), C, divisor, target, coef, gram_out, S, S_bf, S_amax,
                                    mse_partial, s));
+    return NST_OK;
+}
+
+int gram_shifted_of(nst_ctx* ctx, const float* f_nhwc, size_t N, int C, const unsigned* f_amax, const ShiftedGram& sg, float divisor,
+                    float* part, const float* target, float coef, float* gram_out, float* S, unsigned short* S_bf, unsigned* S_amax,
+                    double* mse_partial, hipStream_t s) {
+    if (!f_amax) return fail(ctx, NST_E_STATE, "the shifted Gram runs in the f16x2 arithmetic only");
+    const int ns = gram_nsplit(C, N);
+    {
+        OffsetBatch ob{};
+        ob.n = 1;
+        ob.it[0] = OffsetItem{f_nhwc, N, C, f_amax, sg.shift, sg.center, sg.offset, sg.rec, sg.sums, 0, 0, 0};
+        Timer t(ctx, s, K_OTHER, 0);
+        HIPCHK(ctx, launch_gram_offsets(ob, s));
+    }
+    {
+        Timer t(ctx, s, K_GRAM, 2.0 * (double)N * C * C);
+        HIPCHK(ctx, launch_gram_partial(f_nhwc, N, C, ns, sg.rec, part, s, nullptr, sg.offset));
+    }
+    {
+        Timer t(ctx, s, K_OTHER, 0);
+        if (sg.alpha >= 0.f) HIPCHK(ctx, launch_gram_finish_blend(part, gram_nslabs(C, ns), C, divisor, sg.alpha, sg.accumulate, gram_out, s));
+        else HIPCHK(ctx, launch_gram_finish(part, gram_nslabs(C, ns), C, divisor, target, coef, gram_out, S, S_bf, S_amax, mse_partial, s));
+    }
+    if (sg.r && S) {
+        RowBiasBatch rb{};
+        rb.n = 1;
+        rb.it[0] = RowBiasItem{sg.offset, S, sg.r, C, 0};
+        Timer t(ctx, s, K_OTHER, 0);
+        HIPCHK(ctx, launch_gram_row_bias(rb, s));
+    }
     return NST_OK;
 }
 
@@ -527,8 +560,11 @@ int batched_gram(nst_ctx* ctx, const int* lv, int n, float sw, hipStream_t s, un
     if (h2) {
         // every (level, style layer) pair in two partial launches (one per tile shape) and one finish launch
         const int per = std::max(1, NST_GRAM_BATCH_MAX / ctx->taps.nstyle);      // levels per launch (3 with five style maps)
+        const bool shifted = ctx->gs_on();
         for (int k0 = 0; k0 < n; k0 += per) {
             GramBatch gb{};
+            OffsetBatch ob{};
+            RowBiasBatch rb{};
             double flops = 0;
             for (int k = k0; k < n && k < k0 + per; ++k) {
                 LevelWs& L = ctx->lv[lv[k]];
@@ -544,11 +580,28 @@ int batched_gram(nst_ctx* ctx, const int* lv, int n, float sw, hipStream_t s, un
                     it.gram_out = nullptr; it.S = L.S[q]; it.S_bf = L.S_bf[q]; it.S_amax = amax_S(L.acts, q);
                     it.mse_partial = L.style_partial[q];
                     flops += 2.0 * (double)st.N * st.C * st.C;
+                    if (shifted) {
+                        // means -> SHIFT partial products -> finish -> row bias: the item reads o and the shifted operand's record
+                        ob.it[ob.n++] = OffsetItem{it.f, it.N, it.C, it.amax, ctx->gs_shift_of(q), ctx->gs_center_of(q), L.gs.offset(q),
+                                                   L.gs.amax(q), L.gs.part(q), 0, 0, 0};
+                        rb.it[rb.n++] = RowBiasItem{L.gs.offset(q), L.S[q], L.gs.row_bias(q), it.C, 0};
+                        it.offset = L.gs.offset(q); it.amax = L.gs.amax(q);
+                    }
                 }
             }
             if (gb.n == 0) continue;
-            Timer t(ctx, s, K_GRAM, flops);
-            HIPCHK(ctx, launch_gram_batch(gb, s));
+            if (shifted) {
+                Timer t(ctx, s, K_OTHER, 0);
+                HIPCHK(ctx, launch_gram_offsets(ob, s));
+            }
+            {
+                Timer t(ctx, s, K_GRAM, flops);
+                HIPCHK(ctx, launch_gram_batch(gb, s));
+            }
+            if (shifted) {
+                Timer t(ctx, s, K_OTHER, 0);
+                HIPCHK(ctx, launch_gram_row_bias(rb, s));
+            }
         }
     }
     for (int k = 0; k < n && !h2; ++k) {
@@ -619,6 +672,7 @@ int batched_backward(nst_ctx* ctx, const float* const* xi, float* const* gi, con
             im.in2 = a.act[l]; im.wt2_f32 = L.S[top_q]; im.amax_in2 = amax_act(a, l); im.amax_w2 = amax_S(a, top_q);
             im.bits_in = tp.top_mask() ? a.bits[l] : nullptr; im.amax_out = amax_grad(a, l);
             im.addend = top_content ? oth[k] : nullptr;
+            if (ctx->gs_on()) im.bias = L.gs.row_bias(top_q);      // (a shifted Gram: F S + r, then the addend and the mask)
             if (win) { im.in2_row0 = win_r0(*win, kScale[l]); im.in2_rows = win_nr(*win, kScale[l]); }
             flops += conv_flops(im.H, im.W, b.Cin2, b.Cout, 1);
         }
@@ -688,6 +742,7 @@ int batched_backward(nst_ctx* ctx, const float* const* xi, float* const* gi, con
             if (style_q >= 0) {
                 im.in2 = a.act[m]; im.wt2_bf = L.S_bf[style_q];
                 im.wt2_f32 = L.S[style_q]; im.amax_in2 = amax_act(a, m); im.amax_w2 = amax_S(a, style_q);
+                if (ctx->gs_on()) im.bias = L.gs.row_bias(style_q);
                 if (win) { im.in2_row0 = win_r0(*win, kScale[m]); im.in2_rows = win_nr(*win, kScale[m]); }
                 flops += conv_flops(a.h[m], a.w[m], kCout[m], kCout[m], 1);
             }
@@ -824,8 +879,15 @@ int closure_per_level(nst_ctx* ctx, const float* const* xi, float* const* gi, in
     for (int k = 0; k < tp.nstyle && L.guide.R == 0; ++k) {
         const int l = tp.style[k];
         const StyleTerm st = style_term(tp, k, L.acts, sw, ctx->style_weight(k));
-        NSTCHK(gram_of(ctx, L.acts.act[l], st.N, st.C, h2 ? amax_act(L.acts, l) : nullptr, (float)st.divisor, L.gram_part, L.gram_t[k], st.coef, nullptr, L.S[k],
-                       L.S_bf[k], h2 ? amax_S(L.acts, k) : nullptr, L.style_partial[k], s));
+        if (ctx->gs_on()) {
+            const ShiftedGram sg{ctx->gs_shift_of(k), ctx->gs_center_of(k), L.gs.offset(k), L.gs.amax(k), L.gs.part(k), L.gs.row_bias(k)};
+            NSTCHK(gram_shifted_of(ctx, L.acts.act[l], st.N, st.C, h2 ? amax_act(L.acts, l) : nullptr, sg, (float)st.divisor, L.gram_part, L.gram_t[k],
+                                   st.coef, nullptr, L.S[k], L.S_bf[k], h2 ? amax_S(L.acts, k) : nullptr, L.style_partial[k], s));
+            inj[l].bias = L.gs.row_bias(k);
+        } else {
+            NSTCHK(gram_of(ctx, L.acts.act[l], st.N, st.C, h2 ? amax_act(L.acts, l) : nullptr, (float)st.divisor, L.gram_part, L.gram_t[k], st.coef, nullptr, L.S[k],
+                           L.S_bf[k], h2 ? amax_S(L.acts, k) : nullptr, L.style_partial[k], s));
+        }
         inj[l].S = L.S[k];
         inj[l].S_bf = L.S_bf[k];
         inj[l].S_amax = h2 ? amax_S(L.acts, k) : nullptr;
@@ -1017,6 +1079,8 @@ int window_check(nst_ctx* ctx, const float* xs, int row0, int rows, int H0) {
         return fail(ctx, NST_E_STATE, "the stripe closure implements unit style layer weights only (nst_job_set_style_weights)");
     if (ctx->lap_k > 0)
         return fail(ctx, NST_E_STATE, "the stripe closure implements no Laplacian loss (nst_job_set_laplacian(ctx, 0, NULL, NULL) switches it off)");
+    if (ctx->gs_on())
+        return fail(ctx, NST_E_STATE, "the stripe closure implements the plain Gram statistic only (nst_job_set_gram_shift with zeros switches the shift off)");
     LevelWs& L = ctx->lv[0];
     if (L.guide.R > 0)
         return fail(ctx, NST_E_STATE, "the stripe closure implements no spatial control (nst_level_set_guidance(ctx, 0, 0, ...) clears it)");
@@ -1100,11 +1164,25 @@ int nst_level_set_targets_blend(nst_ctx* ctx, int level, const float* content, i
         float* part = nullptr;
         NSTCHK(alloc_acts(ctx, sc.acts, hs[k], ws[k]));
         NSTCHK(sc.alloc(&part, gram_part_floats_for(tp, hs[k], ws[k])));
+        // a shifted / centred statistic (nst_job_set_gram_shift): this image's own offsets, through the closure's kernels
+        GramShiftLevel gsl;
+        if (ctx->gs_on()) {
+            NSTCHK(sc.alloc(&gsl.words, (size_t)GS_STRIDE));
+            if (ctx->gs_center) NSTCHK(sc.alloc(&gsl.sums, (size_t)GS_PART_DOUBLES));
+        }
         NSTCHK(forward(ctx, sc.acts, styles[k], hs[k], ws[k], s, tp.style[deepest], ctx->channels));
         for (int q = 0; q <= deepest; ++q) {
             if (!(bhat[k][q] > 0.f)) continue;
             const int l = tp.style[q];
             const StyleTerm st = style_term(tp, q, sc.acts, 0.f, 1.f);
+            if (ctx->gs_on()) {
+                ShiftedGram sg{ctx->gs_shift_of(q), ctx->gs_center_of(q), gsl.offset(0), gsl.amax(0), gsl.part(0), nullptr};
+                sg.alpha = bhat[k][q]; sg.accumulate = written[q] ? 1 : 0;
+                NSTCHK(gram_shifted_of(ctx, sc.acts.act[l], st.N, st.C, ctx->conv_mode == 2 ? amax_act(sc.acts, l) : nullptr, sg, (float)st.divisor,
+                                       part, nullptr, 0.f, L.gram_t[q], nullptr, nullptr, nullptr, nullptr, s));
+                written[q] = true;
+                continue;
+            }
             const int ns = gram_nsplit(st.C, st.N);
             {
                 Timer t(ctx, s, K_GRAM, 2.0 * (double)st.N * st.C * st.C);
@@ -1142,6 +1220,7 @@ int nst_level_set_guidance(nst_ctx* ctx, int level, int R, const float* planes, 
         return NST_OK;
     }
     if (ctx->conv_mode != 2) return fail(ctx, NST_E_STATE, "spatial control runs in the f16x2 arithmetic only (NST_CONV unset)");
+    if (ctx->gs_on()) return fail(ctx, NST_E_STATE, "guided Gram matrices take the plain statistic only (nst_job_set_gram_shift with zeros switches the shift off)");
     if (!planes) return fail(ctx, NST_E_ARG, "null argument");
     float lam[NST_MAX_REGIONS] = {1.f, 1.f, 1.f, 1.f};
     bool positive = lambda == nullptr;
@@ -1220,6 +1299,7 @@ int nst_level_set_targets_guided(nst_ctx* ctx, int level, const float* content, 
     if (level < 0 || level >= ctx->levels) return fail(ctx, NST_E_STATE, "level not configured");
     LevelWs& L = ctx->lv[level];
     Guidance& g = L.guide;
+    if (ctx->gs_on()) return fail(ctx, NST_E_STATE, "guided Gram matrices take the plain statistic only (nst_job_set_gram_shift with zeros switches the shift off)");
     if (g.R < 1) return fail(ctx, NST_E_STATE, "the level has no guidance (nst_level_set_guidance first)");
     if (!content || !style || !style_planes) return fail(ctx, NST_E_ARG, "null argument");
     if (hs < 16 || ws < 16) return fail(ctx, NST_E_ARG, "style image must be at least 16x16");

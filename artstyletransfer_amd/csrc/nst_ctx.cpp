@@ -319,6 +319,7 @@ int alloc_level_image(nst_ctx* ctx, LevelWs& L) {
 void free_level(nst_ctx* ctx, LevelWs& L) {
     free_guidance(ctx, L);
     free_laplacian(ctx, L);
+    free_gram_shift(ctx, L);
     free_acts(ctx, L.acts);
     dev_free(L.gbuf[0]); dev_free(L.gbuf[1]); dev_free(L.xl); dev_free(L.gxl);
     free_tap_buffers(ctx, L);
@@ -345,6 +346,12 @@ void free_laplacian(nst_ctx* ctx, LevelWs& L) {
     for (int k = 0; k < NST_LAP_MAX; ++k) { dev_free(q.s[k]); dev_free(q.r[k]); dev_free(q.target[k]); dev_free(q.partial[k]); }
     if (ctx->bytes >= q.bytes) ctx->bytes -= q.bytes;
     q = LapLevel();
+}
+
+void free_gram_shift(nst_ctx* ctx, LevelWs& L) {
+    dev_free(L.gs.words); dev_free(L.gs.sums);
+    if (ctx->bytes >= L.gs.bytes) ctx->bytes -= L.gs.bytes;
+    L.gs = GramShiftLevel();
 }
 
 // What a closure remembered is void once the job changes: the captured graph and the keys it was captured under, and
@@ -643,6 +650,8 @@ int nst_job_configure(nst_ctx* ctx, int levels_num, int H0, int W0) {
     forget_forward_pass(ctx);
     ctx->levels = 0;
     ctx->lap_k = 0;                      // (the Laplacian setting belongs to the job's geometry: its buffers went with the levels)
+    for (float& v : ctx->gs_shift) v = 0.f;      // (the Gram shift likewise)
+    ctx->gs_center = 0u;
     int h = H0, w = W0;
     for (int i = 0; i < levels_num; ++i) {
         LevelWs& L = ctx->lv[i];
@@ -849,6 +858,76 @@ int nst_job_laplacian_losses(nst_ctx* ctx, float* out, void* stream) {
     const size_t bytes = (size_t)ctx->levels * NST_LAP_MAX * sizeof(float);
     if (ctx->lap_k > 0 && ctx->lap_vals) HIPCHK(ctx, hipMemcpyAsync(out, ctx->lap_vals, bytes, hipMemcpyDeviceToDevice, s));
     else HIPCHK(ctx, hipMemsetAsync(out, 0, bytes, s));
+    mark(ctx, s);
+    return NST_OK;
+}
+
+// Activation-shifted and mean-centred Gram matrices (Novak & Nikulin 2016; Li et al. 2017; include/nst_hip.h has the
+// definition).  Same life cycle as the pooling: every level's targets go (they are made with the statistic), and the captured
+// closure.  Every buffer of the option is allocated here; a refusal changes nothing.
+int nst_job_set_gram_shift(nst_ctx* ctx, const float* shift, unsigned center_mask) {
+    if (ctx) { ++ctx->closure_epoch; ++ctx->ws_seq; }
+    NSTCHK(bind(ctx));
+    if (!shift) return fail(ctx, NST_E_ARG, "null argument");
+    if ((center_mask & ~0x3Fu) != 0u) return fail(ctx, NST_E_ARG, "center_mask must be a set of bits 0 .. 5");
+    bool on = center_mask != 0u;
+    for (int i = 0; i < 6; ++i) {
+        if (!std::isfinite(shift[i])) return fail(ctx, NST_E_ARG, "Gram shifts must be finite");
+        if (((center_mask >> i) & 1u) && shift[i] != 0.f) return fail(ctx, NST_E_ARG, "a centred map takes no constant shift: its entry must be 0");
+        on = on || shift[i] != 0.f;
+    }
+    GramShiftLevel fresh[NST_MAX_LEVELS];
+    if (on) {
+        if (ctx->levels < 1) return fail(ctx, NST_E_STATE, "nst_job_configure has not been called");
+        if (ctx->conv_mode != 2) return fail(ctx, NST_E_STATE, "the shifted Gram runs in the f16x2 arithmetic only (NST_CONV unset)");
+        for (int i = 0; i < ctx->levels; ++i)
+            if (ctx->lv[i].guide.R > 0)
+                return fail(ctx, NST_E_STATE, "guided Gram matrices take the plain statistic only (nst_level_set_guidance(ctx, level, 0, ...) clears the guidance)");
+        int rc = NST_OK;
+        for (int i = 0; i < ctx->levels && rc == NST_OK; ++i) {
+            GramShiftLevel& q = fresh[i];
+            rc = dev_alloc_t(ctx, &q.words, (size_t)kMaxStyle * GS_STRIDE);
+            if (rc == NST_OK) q.bytes += (size_t)kMaxStyle * GS_STRIDE * sizeof(float);
+            if (rc == NST_OK && center_mask) {
+                rc = dev_alloc_t(ctx, &q.sums, (size_t)kMaxStyle * GS_PART_DOUBLES);
+                if (rc == NST_OK) q.bytes += (size_t)kMaxStyle * GS_PART_DOUBLES * sizeof(double);
+            }
+            // (o reads as zeros until a closure has run: nst_level_gram_offsets)
+            if (rc == NST_OK && hipMemset(q.words, 0, (size_t)kMaxStyle * GS_STRIDE * sizeof(float)) != hipSuccess)
+                rc = fail(ctx, NST_E_HIP, "hipMemset of the Gram offsets failed");
+        }
+        if (rc != NST_OK) {
+            LevelWs tmp;
+            for (int i = 0; i < ctx->levels; ++i) { tmp.gs = fresh[i]; free_gram_shift(ctx, tmp); }
+            return rc;
+        }
+    }
+    quiesce(ctx);
+    drop_closure_state(ctx, true);
+    for (int i = 0; i < ctx->levels; ++i) {
+        free_gram_shift(ctx, ctx->lv[i]);
+        ctx->lv[i].gs = fresh[i];
+    }
+    for (int i = 0; i < 6; ++i) ctx->gs_shift[i] = shift[i];
+    ctx->gs_center = center_mask;
+    return NST_OK;
+}
+
+int nst_job_gram_shift(const nst_ctx* ctx, float* shift, unsigned* center_mask) {
+    if (!ctx) return fail(nullptr, NST_E_ARG, "null context");
+    for (int i = 0; i < 6 && shift; ++i) shift[i] = ctx->gs_shift[i];
+    if (center_mask) *center_mask = ctx->gs_center;
+    return NST_OK;
+}
+
+// the o of style slot `slot` as the level's last closure (or targets-free forward half) left it: C floats
+int nst_level_gram_offsets(nst_ctx* ctx, int level, int slot, float* out, void* stream) {
+    NSTCHK(bind(ctx));
+    if (level < 0 || level >= ctx->levels) return fail(ctx, NST_E_STATE, "level not configured");
+    if (!ctx->gs_on()) return fail(ctx, NST_E_STATE, "no Gram shift is set (nst_job_set_gram_shift)");
+    if (slot < 0 || slot >= ctx->taps.nstyle || !out) return fail(ctx, NST_E_ARG, "slot must be a style slot of the current taps and out not null");
+    hipStream_t s = enter(ctx, stream);
+    HIPCHK(ctx, hipMemcpyAsync(out, ctx->lv[level].gs.offset(slot), (size_t)kCout[ctx->taps.style[slot]] * sizeof(float), hipMemcpyDeviceToDevice, s));
     mark(ctx, s);
     return NST_OK;
 }

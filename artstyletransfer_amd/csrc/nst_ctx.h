@@ -129,10 +129,32 @@ struct LapLevel {
     size_t bytes = 0;
 };
 
+// The shifted / centred Gram statistic of one level (nst_job_set_gram_shift; include/nst_hip.h has the definition): per style
+// slot the offsets o the last closure used, the row bias r = o S of its backward, the absmax record of the shifted operand
+// F + o, and (a centred map) the scratch of the channel sums.  Sized for the widest map, so the taps may change under it.
+// Made by the setter, freed when the setting is cleared or the job configured again: a closure allocates nothing.
+constexpr int GS_MAX_C = 512;
+constexpr int GS_STRIDE = 2 * GS_MAX_C + NST_AMAX_SLOTS;      // words of one slot: o | r | record
+constexpr bool maps_fit_gram_shift() {
+    for (int c : kCout) if (c > GS_MAX_C) return false;
+    return true;
+}
+static_assert(maps_fit_gram_shift(), "a map wider than GS_MAX_C: the per-slot buffers of GramShiftLevel are sized by it");
+struct GramShiftLevel {
+    float* words = nullptr;     // kMaxStyle x GS_STRIDE
+    double* sums = nullptr;     // kMaxStyle x GS_PART_DOUBLES (only with a centred map)
+    size_t bytes = 0;
+    float* offset(int q) const { return words + (size_t)q * GS_STRIDE; }
+    float* row_bias(int q) const { return words + (size_t)q * GS_STRIDE + GS_MAX_C; }
+    unsigned* amax(int q) const { return reinterpret_cast<unsigned*>(words + (size_t)q * GS_STRIDE + 2 * GS_MAX_C); }
+    double* part(int q) const { return sums ? sums + (size_t)q * GS_PART_DOUBLES : nullptr; }
+};
+
 struct LevelWs {
     int h = 0, w = 0;
     Guidance guide;
     LapLevel lap;
+    GramShiftLevel gs;
     ActSet acts;
     float* gbuf[2] = {};
     size_t gbuf_floats = 0;
@@ -220,7 +242,16 @@ struct nst_ctx {
     int lap_pool[nst::NST_LAP_MAX] = {};
     float lap_gamma[nst::NST_LAP_MAX] = {};
     float* lap_vals = nullptr;
-    // bumped on entry to every call that changes what a closure computes (configure, taps, colour, pooling, style weights, targets), failure paths
+    // nst_job_set_gram_shift: per map index (as the style layer weights) a constant shift, or (bit of gs_center) centring
+    float gs_shift[6] = {};
+    unsigned gs_center = 0;
+    bool gs_on() const {
+        for (float v : gs_shift) if (v != 0.f) return true;
+        return gs_center != 0u;
+    }
+    float gs_shift_of(int q) const { return gs_shift[nst::tap_index_of(taps.style[q])]; }                  // of style slot q
+    int gs_center_of(int q) const { return (int)((gs_center >> nst::tap_index_of(taps.style[q])) & 1u); }
+    // bumped on entry to every call that changes what a closure computes (configure, taps, colour, pooling, style weights, Laplacian, Gram shift, targets), failure paths
     // included: an optimiser's remembered closure result is valid only under the epoch it was made in (nst_opt.cpp)
     unsigned long long closure_epoch = 0;
     // advanced on entry to every call that reads or writes the level workspaces (nst_closure*, nst_window_*,
@@ -313,6 +344,7 @@ int bind(nst_ctx* ctx);                            // null check + hipSetDevice:
 void drop_closure_state(nst_ctx* ctx, bool drop_targets);
 void free_guidance(nst_ctx* ctx, LevelWs& L);      // the level is unguided afterwards
 void free_laplacian(nst_ctx* ctx, LevelWs& L);     // the level's Laplacian buffers (the setting itself is the context's)
+void free_gram_shift(nst_ctx* ctx, LevelWs& L);    // the level's shifted-Gram buffers (likewise)
 hipStream_t enter(nst_ctx* ctx, void* stream);     // orders the caller's stream after the context's tail event
 void mark(nst_ctx* ctx, hipStream_t s);            // records the tail event
 void quiesce(nst_ctx* ctx);                        // waits until nothing on the device uses the context's memory
@@ -350,6 +382,7 @@ struct Inject {
     const unsigned* S_amax = nullptr; // absmax record of S (conv_h2), if available
     const float* direct = nullptr;   // or a ready NHWC gradient
     bool content = false;            // or the content MSE gradient (closure only)
+    const float* bias = nullptr;     // with S, a shifted Gram (nst_job_set_gram_shift): the row bias r = o S, dF = F * S + r
     const GuidedBwd* guided = nullptr; // guided Gram backward (R, t, S filled in): dF = sum_r t_r^2 F S_r, by a launch of its own
 };
 struct ContentJob { const float* target; size_t n; float coef; double* partial; };
@@ -365,6 +398,17 @@ int backward(nst_ctx* ctx, ActSet& a, const Inject* inj, const ContentJob* cj, f
 int gram_of(nst_ctx* ctx, const float* f_nhwc, size_t N, int C, const unsigned* f_amax, float divisor, float* part, const float* target,
             float coef, float* gram_out, float* S, unsigned short* S_bf, unsigned* S_amax, double* mse_partial,
             hipStream_t s);
+// The shifted Gram of one map (nst_job_set_gram_shift): offsets and operand record (launch_gram_offsets) -> SHIFT partial
+// products -> the finish pass of gram_of (alpha < 0) or its blend form (gram_out = alpha G, or += when accumulate) -> the row
+// bias r = o S (when r and S are given).  offset: C floats, rec: NST_AMAX_SLOTS words, sums: GS_PART_DOUBLES doubles (a
+// centred map).  The fp16-piece kernels only: f_amax is required.
+struct ShiftedGram {
+    float shift; int center; float* offset; unsigned* rec; double* sums; float* r;
+    float alpha = -1.f; int accumulate = 0;
+};
+int gram_shifted_of(nst_ctx* ctx, const float* f_nhwc, size_t N, int C, const unsigned* f_amax, const ShiftedGram& sg, float divisor,
+                    float* part, const float* target, float coef, float* gram_out, float* S, unsigned short* S_bf, unsigned* S_amax,
+                    double* mse_partial, hipStream_t s);
 // A full-resolution map of `level` that its last batched forward pass left out: that layer's launch again, over the levels
 // of that pass (same ConvBatch, so the same tile shape and summation order), with `out` set.  The pooled map, mask and code
 // words it rewrites are the values they hold; the absmax records stay (atomicMax of the same values).

@@ -85,6 +85,7 @@ struct ConvImage {
     const unsigned* pcode_in;
     unsigned* pcode_out;
     int in2_row0, in2_rows;
+    const float* bias;       // conv_h2 only: this image's bias [Cout] (the row bias of a shifted Gram backward); nullptr: ConvBatch::bias
 };
 struct ConvBatch {
     ConvImage img[8];
@@ -260,8 +261,10 @@ int gram_nsplit(int C, size_t N);
 // amax (nullable): NST_AMAX_SLOTS-word absmax record of f -> the fp16-piece kernel (3 MFMAs per product block)
 // guide (nullable): the guided Gram sum_p t(p)^2 F(p) F(p)^T - every staged pixel row is scaled by t(p) in [0,1] (so the
 // map's absmax still bounds the operand); the fp16-piece kernels only (amax required, C = 64 or a multiple of 128)
+// offset (nullable; not with guide): the shifted Gram sum_p (F(p) + o)(F(p) + o)^T, o = offset[C]; `amax` is then the record
+// of the shifted operand that launch_gram_offsets writes; the fp16-piece kernels only
 hipError_t launch_gram_partial(const float* f, size_t N, int C, int nsplit, const unsigned* amax, float* part,
-                               hipStream_t stream, const float* guide = nullptr);
+                               hipStream_t stream, const float* guide = nullptr, const float* offset = nullptr);
 // G = (sum_s part[s]) / divisor (fixed order).  If target: mse_out[0] = sum((G-Gt)^2) (double) and
 // S = coef * (G - Gt) (C x C, for the backward 1x1 conv).  gram_out / target / S / mse_partial nullable;
 // mse_partial: gram_finish_blocks(C) doubles.  `nslabs` = gram_nslabs(C, nsplit).
@@ -275,6 +278,7 @@ struct GramItem {
     double* mse_partial;
     int nsplit; size_t pix_per_split; int part_end, finish_end;     // filled by the launcher
     const float* guide;   // guided Gram (gram_guided.hip): t(p) of the N pixels, the staged pixel row is scaled by it; nullptr: plain
+    const float* offset;  // shifted Gram (gram_shift.hip): o[C] added to every staged value, `amax` the shifted operand's record; nullptr: plain
 };
 struct GramBatch { GramItem it[NST_GRAM_BATCH_MAX]; int n; };
 hipError_t launch_gram_batch(const GramBatch& b, hipStream_t stream);
@@ -289,6 +293,31 @@ hipError_t launch_gram_finish(const float* part, int nslabs, int C, float diviso
 // != 0), product and sum each rounded to fp32.  alpha = 1 without accumulation writes the bits launch_gram_finish writes.
 hipError_t launch_gram_finish_blend(const float* part, int nslabs, int C, float divisor, float alpha, int accumulate,
                                     float* gram_out, hipStream_t stream);
+
+// gram_shift.hip: activation-shifted and mean-centred Gram matrices (include/nst_hip.h has the definition) -----------
+// Per item the offsets o[C] - center: o_c = -(1/N) sum_p F[p][c], the sums in double through two ordered stages (no atomics:
+// bitwise reproducible); else o_c = shift for every c, without a pass over the map - and the NST_AMAX_SLOTS-word record of
+// the shifted operand, absmax(F) + max_c |o_c| rounded up: a bound of |F + o| whatever the signs of F.  One launch pair
+// covers all items.  C: 64 or a multiple of 128, at most 1024 - the launcher's own limit: `offset` is the caller's, C floats
+// (a context's per-slot buffers hold GS_MAX_C; nst_ctx.h asserts that the network's maps fit).
+constexpr int GS_PART_DOUBLES = 128 * 1024;     // stage-one partial sums of one item: gram_offset_blocks(C, N) x C doubles at most
+struct OffsetItem {
+    const float* f; size_t N; int C;
+    const unsigned* amax;     // record of f
+    float shift; int center;
+    float* offset;            // out: C floats
+    unsigned* amax_out;       // out: NST_AMAX_SLOTS words
+    double* part;             // centred items: GS_PART_DOUBLES doubles of scratch
+    int nblk; size_t pix_per_blk; int blk_end;     // filled by the launcher
+};
+struct OffsetBatch { OffsetItem it[NST_GRAM_BATCH_MAX]; int n; };
+int gram_offset_blocks(int C, size_t N);
+hipError_t launch_gram_offsets(const OffsetBatch& b, hipStream_t stream);
+// r[c] = sum_k o[k] S[k][c] per item (double accumulation in a fixed order): the row bias of the shifted Gram backward,
+// dF_p = (F_p + o) S = F_p S + r
+struct RowBiasItem { const float* offset; const float* S; float* r; int C; int blk_end; };
+struct RowBiasBatch { RowBiasItem it[NST_GRAM_BATCH_MAX]; int n; };
+hipError_t launch_gram_row_bias(const RowBiasBatch& b, hipStream_t stream);
 
 // gram_guided.hip: spatial control (guided Gram matrices; include/nst_hip.h has the definitions) ---------------------
 constexpr int NST_MAX_REGIONS_K = 4;

@@ -13,6 +13,7 @@ from . import taps as _taps
 from .pooling_modes import check_pooling
 from . import style_modes as _style
 from . import regions as _regions
+from . import gram_modes as _gram
 from . import laplacian_modes as _lap
 from ._lib import NST_LOSS_ROW, NstError, StepInfo
 
@@ -91,6 +92,7 @@ class StyleEngine:
         self.pooling = "max"                     # "avg" under set_pooling("avg")
         self.layer_weights = _style.UNIT_WEIGHTS # set_style_weights
         self.laplacian = None                    # (pools, weights) under set_laplacian
+        self.gram_shift = None                   # (shift[6], center_mask) under set_gram_shift
 
     def close(self):
         if getattr(self, "ctx", None):
@@ -109,6 +111,7 @@ class StyleEngine:
         self.levels = levels_num
         self.shape = (H0, W0)
         self.laplacian = None                    # (nst_job_configure clears the Laplacian setting)
+        self.gram_shift = None                   # (and the Gram shift)
 
     def set_taps(self, content_index, style_indices, use_relu: bool = True) -> None:
         """The feature maps the losses read (nst_job_set_taps): a content index and style indices of Vgg19.layer_names
@@ -224,6 +227,64 @@ class StyleEngine:
         out = torch.empty((self.levels, _lib.NST_MAX_LAPLACIAN), dtype=torch.float32, device=self.device)
         _lib.check(self.ctx, self.lib.nst_job_laplacian_losses(self.ctx, _ptr(out), _stream(self.device)),
                    "nst_job_laplacian_losses")
+        return out
+
+    def set_gram_shift(self, shift, center_mask: int = 0) -> None:
+        """The Gram statistic of the job (nst_job_set_gram_shift): `shift` - None, a number, "mean", six entries or a dict, as
+        gram_modes.normalize_gram_shift takes them, the explicit form being six floats with `center_mask`, the bit set of the
+        centred maps (whose shift is 0).  G = (F + o)^T (F + o) / (C N) with o the map's constant shift or minus its own
+        channel means.  All zeros with an empty mask: the plain Gram.  Needs a configured job, the f16x2 arithmetic and no
+        guided level; drops the targets of every level: call set_targets again.  ValueError (before the context is touched)
+        for a malformed setting."""
+        setting = _gram.normalize_gram_shift(shift)
+        mask = int(center_mask)
+        if mask < 0 or mask >> _gram.NUM_MAPS:
+            raise ValueError(f"center_mask must be a set of bits 0..{_gram.NUM_MAPS - 1}, got {center_mask!r}")
+        if mask:
+            s6, m0 = setting if setting is not None else ((0.0,) * _gram.NUM_MAPS, 0)
+            if any(s6[i] != 0.0 for i in range(_gram.NUM_MAPS) if (mask >> i) & 1):
+                raise ValueError("a centred map takes no constant shift: its entry must be 0")
+            setting = (s6, m0 | mask)
+        if setting is None:
+            self.reset_gram_shift()
+            return
+        if not self.levels:
+            raise NstError("set_gram_shift needs a configured job (configure first)")
+        arr = (C.c_float * _gram.NUM_MAPS)(*setting[0])
+        try:
+            _lib.check(self.ctx, self.lib.nst_job_set_gram_shift(self.ctx, arr, setting[1]), "nst_job_set_gram_shift")
+        finally:                                 # the context's setting, whether the call succeeded or not
+            self.gram_shift = self.gram_shift_setting()
+
+    def gram_shift_setting(self):
+        """The context's Gram shift as (shift[6], center_mask), or None when it is off (nst_job_gram_shift)."""
+        arr = (C.c_float * _gram.NUM_MAPS)()
+        mask = C.c_uint(0)
+        _lib.check(self.ctx, self.lib.nst_job_gram_shift(self.ctx, arr, C.byref(mask)), "nst_job_gram_shift")
+        shift = tuple(float(v) for v in arr)
+        if mask.value == 0 and all(v == 0.0 for v in shift):
+            return None
+        return shift, int(mask.value)
+
+    def reset_gram_shift(self) -> None:
+        """The plain Gram statistic again, if a shift was set (drops the targets then, as set_gram_shift does)."""
+        if self.gram_shift is not None:
+            zeros = (C.c_float * _gram.NUM_MAPS)()
+            try:
+                _lib.check(self.ctx, self.lib.nst_job_set_gram_shift(self.ctx, zeros, 0), "nst_job_set_gram_shift")
+            finally:
+                self.gram_shift = self.gram_shift_setting()
+
+    def level_gram_offsets(self, level: int, slot: int) -> torch.Tensor:
+        """(C,) device tensor: the offsets o that the last closure of `level` used for style slot `slot` (the slots are the
+        style maps of the current taps in ascending order; nst_level_gram_offsets)."""
+        style = self.taps[1]
+        if not 0 <= slot < len(style):
+            raise ValueError(f"slot {slot} is outside the {len(style)} style maps of the current taps")
+        c = (64, 128, 256, 512, 512, 512)[style[slot]]      # channels of the six maps of Vgg19.layer_names
+        out = torch.empty((c,), dtype=torch.float32, device=self.device)
+        _lib.check(self.ctx, self.lib.nst_level_gram_offsets(self.ctx, level, slot, _ptr(out), _stream(self.device)),
+                   "nst_level_gram_offsets")
         return out
 
     def release_job(self) -> None:
@@ -588,6 +649,18 @@ class StyleEngine:
                                                _stream(self.device)), "nst_gram")
         return g
 
+    def gram_shifted(self, f: torch.Tensor, shift: float = 0.0, center: bool = False, normalize: bool = True):
+        """The shifted / centred statistic alone (nst_gram_shifted): (G (1,C,C), o (C,)) of the (1,C,h,w) map f, o = shift
+        on every channel or (center) minus the map's channel means."""
+        _chk_dev(f, self.device)
+        b, c, h, w = f.shape
+        assert b == 1
+        g = torch.empty((1, c, c), dtype=torch.float32, device=self.device)
+        o = torch.empty((c,), dtype=torch.float32, device=self.device)
+        _lib.check(self.ctx, self.lib.nst_gram_shifted(self.ctx, _ptr(f), c, h, w, int(normalize), int(bool(center)), float(shift),
+                                                       _ptr(g), _ptr(o), _stream(self.device)), "nst_gram_shifted")
+        return g, o
+
     def guided_gram_backward(self, f: torch.Tensor, planes: torch.Tensor, s_mats: torch.Tensor, addend: Optional[torch.Tensor] = None,
                              relu_bits: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, want_absmax: bool = False):
         """The guided Gram backward launch on its own (nst_guided_gram_backward): out (N,C) = addend + sum_r t_r^2 . f . S_r for
@@ -877,6 +950,7 @@ class PixelOptimizer:
             raise ValueError("the stripe closure implements unit style layer weights only (reset_style_weights())")
         if e.laplacian is not None:
             raise ValueError("laplacian_weight cannot be combined with stripe sharding (reset_laplacian())")
+        _gram.check_exclusive(getattr(e, "gram_shift", None), stripes=True)
         contents = list(content_t) if isinstance(content_t, (list, tuple)) else [content_t]
         styles = list(style_t) if isinstance(style_t, (list, tuple)) else [style_t]
         if blend is not None and styles and isinstance(styles[0], torch.Tensor):

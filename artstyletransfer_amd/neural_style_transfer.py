@@ -23,6 +23,7 @@ from .neural_nets import lease_engine, return_engine, shared_engine
 from .pooling_modes import check_pooling
 from . import style_modes as _style
 from . import regions as _regions
+from . import gram_modes as _gram
 from . import laplacian_modes as _lap
 
 # ImageNet statistics (reference :22-23)
@@ -116,6 +117,20 @@ class LossBuilder:
             self.__engine.set_laplacian(*entries)
         self.__engine.set_targets(0, *self.__targets)       # (the setting drops them: the Laplacian targets are made with them)
 
+    def set_gram_shift(self, gram_shift=None):
+        """Extension: the Gram statistic of the style term of `build` - activation-shifted (Novak & Nikulin 2016) or
+        mean-centred (the covariance; Li et al. 2017) per feature map: None or 0 (the plain Gram), a number (that shift on
+        every map), "mean" (every map centred), six entries, or a dict {map index or name: number or "mean"} (see
+        nst_job_set_gram_shift in include/nst_hip.h).  ValueError for a malformed setting."""
+        setting = _gram.normalize_gram_shift(gram_shift)
+        if setting is None and self.__engine.gram_shift is None:
+            return
+        if setting is None:
+            self.__engine.reset_gram_shift()
+        else:
+            self.__engine.set_gram_shift(*setting)
+        self.__engine.set_targets(0, *self.__targets)       # (the setting drops them: the Gram targets are made with the statistic)
+
     def __del__(self):
         try:
             return_engine(self.__engine)
@@ -136,7 +151,7 @@ class _DeviceJob:
     (`_make_job`, tests/test_host_api.py)."""
 
     def __init__(self, device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, taps=None, color=None,
-                 pooling=None, style_weights=None, blend=None, regions=None, laplacian=None):
+                 pooling=None, style_weights=None, blend=None, regions=None, laplacian=None, gram_shift=None):
         self.dev = dev = device
         self.optimizer = None
         self.luminance = color == "luminance"   # the optimised image is u = 255 Y; the yield puts the content's I, Q back
@@ -173,6 +188,8 @@ class _DeviceJob:
                     engine.set_style_weights(style_weights)
                 if laplacian is not None:           # (pools, weights) of the Laplacian loss, normalised
                     engine.set_laplacian(*laplacian)
+                if gram_shift is not None:          # (shift[6], center_mask) of the Gram statistic, normalised
+                    engine.set_gram_shift(*gram_shift)
                 # blend = (per-level image lists of the extra styles, K x 6 matrix): style 0 is style_imgs
                 all_styles = [style_imgs] + (list(blend[0]) if blend is not None else [])
                 if self.luminance:
@@ -248,9 +265,9 @@ class _DeviceJob:
 
 
 def _make_job(device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, taps=None, color=None, pooling=None,
-              style_weights=None, blend=None, regions=None, laplacian=None):
+              style_weights=None, blend=None, regions=None, laplacian=None, gram_shift=None):
     return _DeviceJob(device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, taps, color, pooling,
-                      style_weights, blend, regions, laplacian)
+                      style_weights, blend, regions, laplacian, gram_shift)
 
 
 async def _drain(step_future):
@@ -288,6 +305,7 @@ class NeuralStyleTransfer:
         self.__blend = None                      # set_style_blend: (extra style levels, blend as given)
         self.__regions = None                    # set_regions: (content stack, style stack, region weights)
         self.__laplacian = None                  # set_laplacian: (pools, weights)
+        self.__gram_shift = None                 # set_gram_shift: (shift[6], center_mask)
 
     def set_feature_maps(self, content_layer=None, style_layers=None, use_relu=True):
         """Extension: the feature maps the losses of the next `process` read - a content map and a set of style maps of
@@ -359,6 +377,15 @@ class NeuralStyleTransfer:
         level sizes are known - for a level too small for a pool size."""
         self.__laplacian = _lap.normalize_laplacian(laplacian_weight, laplacian_pool)
 
+    def set_gram_shift(self, gram_shift=None):
+        """Extension: the Gram statistic of the style term in the next `process` - activation-shifted (Novak & Nikulin 2016:
+        G = (F + s)^T (F + s), s = -1 in the paper) or mean-centred (the covariance; Li et al. 2017), per feature map of
+        Vgg19.layer_names: None or 0 (the plain Gram), a number (that shift on every map), "mean" (every map centred), six
+        entries, or a dict {map index or name: number or "mean"} (the rest 0); nst_job_set_gram_shift in include/nst_hip.h
+        has the definition.  ValueError for a non-finite number, another string, a wrong length or an unknown map, and - in
+        `process` - together with regions."""
+        self.__gram_shift = _gram.normalize_gram_shift(gram_shift)
+
     async def process(self, content_imgs, init_img, lr_start, iters_num, content_weight, style_weight, tv_weight,
                       init_img_name):
         # validates the model name exactly as the reference does (ValueError for anything but vgg19)
@@ -379,6 +406,7 @@ class NeuralStyleTransfer:
             blend = (self.__blend[0], _style.check_style_blend(self.__blend[1], 1 + len(self.__blend[0]), style_indices=style_set))
         if self.__laplacian is not None and len(content_imgs):
             _lap.check_levels(self.__laplacian[0], len(content_imgs), *tuple(content_imgs[0].shape[:2]))
+        _gram.check_exclusive(self.__gram_shift, self.__regions)
         style_imgs = self.__style_imgs
         regions = None
         if self.__regions is not None:
@@ -414,6 +442,8 @@ class NeuralStyleTransfer:
             extra["regions"] = regions
         if self.__laplacian is not None:
             extra["laplacian"] = self.__laplacian
+        if self.__gram_shift is not None:
+            extra["gram_shift"] = self.__gram_shift
         job = _make_job(self.__device, self.__optimizer_name, style_imgs, content_imgs, init_img, lr_start, **extra)
         cw, sw, tvw = float(content_weight), float(style_weight), float(tv_weight)
         loop = asyncio.get_running_loop()
@@ -472,7 +502,7 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
                                 content_layer=None, style_layers=None, use_relu=True, preserve_color=None,
                                 pooling="max", extra_styles=None, style_blend=None, style_layer_weights=None,
                                 content_regions=None, style_regions=None, region_weights=None,
-                                laplacian_weight=None, laplacian_pool=_lap.DEFAULT_POOL):
+                                laplacian_weight=None, laplacian_pool=_lap.DEFAULT_POOL, gram_shift=None):
     """Async generator yielding (percent, HWC float32 image) after every optimiser step
     (reference :229-372). `device` (extension): the GPU to run on; default = current.  `content_layer`,
     `style_layers`, `use_relu` (extension): the feature maps the losses read, see NeuralStyleTransfer.set_feature_maps
@@ -488,7 +518,9 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
     (extension): spatial control, see NeuralStyleTransfer.set_regions; not with `extra_styles`.  They are validated before
     any GPU work (the masses of the regions on every level included: the level sizes follow from the image sizes).
     `laplacian_weight`, `laplacian_pool` (extension): the Laplacian loss, see NeuralStyleTransfer.set_laplacian (None, 0 or
-    all-zero weights: off); validated before any GPU work too, a level too small for a pool size included."""
+    all-zero weights: off); validated before any GPU work too, a level too small for a pool size included.  `gram_shift`
+    (extension): activation-shifted or mean-centred Gram matrices, see NeuralStyleTransfer.set_gram_shift (None or 0: the
+    plain Gram); validated before any GPU work too; not with `content_regions` / `style_regions`."""
     taps = _taps.normalize_taps(content_layer, style_layers, use_relu)
     host_image.check_preserve_color(preserve_color)
     check_pooling(pooling)
@@ -498,6 +530,8 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
         style_blend = _style.check_style_blend(style_blend, 1 + len(extra_styles), style_indices=taps[1])
     regions = _regions.check_regions(content_regions, style_regions, region_weights)
     _regions.check_exclusive(regions, extra_styles)
+    gram_setting = _gram.normalize_gram_shift(gram_shift, use_relu)
+    _gram.check_exclusive(gram_setting, regions)
     laplacian = _lap.normalize_laplacian(laplacian_weight, laplacian_pool)
     if laplacian is not None:
         ih, iw = np.shape(content_n_style.content[1])[:2]
@@ -547,6 +581,8 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
         nst.set_regions(regions[0], regions[1], regions[2])
     if laplacian is not None:
         nst.set_laplacian(laplacian[1], laplacian[0])
+    if gram_setting is not None:
+        nst.set_gram_shift(gram_shift)
     lr_start = 10.0
     async for img, cur_iter in nst.process(content_levels, init_img, lr_start, iters_num, content_weight,
                                            style_weight, tv_weight, init_name):

@@ -74,6 +74,9 @@ class Task:
         if getattr(cfg, "laplacian_weight", None) is not None:
             extensions["laplacian_weight"] = cfg.laplacian_weight
             extensions["laplacian_pool"] = getattr(cfg, "laplacian_pool", 4)
+        # the Gram statistic (a number, 'mean', a sequence or a dict: `is not None`)
+        if getattr(cfg, "gram_shift", None) is not None:
+            extensions["gram_shift"] = cfg.gram_shift
         gpu = await self.__slots.acquire()
         self.gpu = gpu
         try:

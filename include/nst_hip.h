@@ -242,6 +242,56 @@ int nst_job_set_laplacian(nst_ctx* ctx, int K, const int* pool, const float* gam
 int nst_job_laplacian(const nst_ctx* ctx, int* K, int pool[NST_MAX_LAPLACIAN], float gamma[NST_MAX_LAPLACIAN]);
 int nst_job_laplacian_losses(nst_ctx* ctx, float* out /* device, levels x NST_MAX_LAPLACIAN */, void* stream);
 
+/* Gram shift: activation-shifted and mean-centred style statistics, a setting of the context.  The reference has no
+ * counterpart: its statistic is the raw second moment G = F^T F / (C N) of the tapped maps.
+ * - Activation shift (Novak & Nikulin, "Improving the Neural Algorithm of Artistic Style", 2016): G = (F + s)^T (F + s), s = -1
+ *   in the paper.  Post-ReLU maps are sparse, and a raw Gram entry cannot tell "both channels off" from "one off".
+ * - Mean-centred Gram, the covariance (Li, Wang, Liu & Hou, "Demystifying Neural Style Transfer", 2017; WCT-style methods).
+ *
+ * Setting
+ * - Each of the six maps of Vgg19.layer_names has a setting, by map index as the style layer weights: a finite float s_i
+ *   (0 = the plain Gram), or *centred* (bit i of center_mask; shift[i] must then be 0).
+ * Statistic of a style map of C channels and N pixels
+ * - o_c = s_i for a shifted map.
+ * - o_c = -(1/N) sum_p F_pc for a centred map, the sum in double in a fixed two-stage order, rounded to fp32 once.  The style
+ *   TARGET uses the style image's own means; the closure uses those of the image being optimised.
+ * - G = sum_p (F_p + o)(F_p + o)^T / (C N), summed directly: on post-ReLU maps the covariance is a small difference of large
+ *   second moments, so the correction form G - N mu mu^T would lose digits.  The pixels that pad a ragged last group of a
+ *   split contribute 0, not o.
+ * - The style term, layer weights, nstyle division and coefficients stay what they are for the plain Gram.
+ * - Blended targets (nst_level_set_targets_blend) are the weighted mean of each style's G, each with its own means.
+ * Gradient
+ * - dF_p = (F_p + o) S = F_p S + r with S = coef (G - Gt) and r = o S, one C-vector per map: the launches that carry F S as
+ *   their second K source add r in their epilogue, after the scale and before the addend and the ReLU mask.
+ * - Under centring the dependence of the means on F drops out exactly, because sum_p (F_p + o) = 0.
+ * - Pre-ReLU taps (use_relu = 0): the style gradient, r included, joins unmasked where the Gram term joins.
+ * Operand bound
+ * - The fp16-piece Gram kernels scale by a power of two from a bound of their operand.  F's own absmax does not bound F + o,
+ *   so the offsets kernel records absmax(F) + max_c |o_c|, rounded up.
+ * No float atomics: a closure with the option is bitwise reproducible.
+ *
+ * nst_job_set_gram_shift: all zeros with an empty mask switches the option off: the job then launches what it launches
+ * without the call and computes the same bits.  NST_E_ARG, with nothing changed, for a non-finite shift, mask bits above
+ * 5, or a non-zero shift of a centred map.  A non-trivial setting needs a configured job and the f16x2 arithmetic, and no
+ * guided level (NST_E_STATE otherwise).  Life cycle of nst_job_set_pooling: the call waits for the context's work, drops
+ * every level's targets (they are made with the statistic) and any captured closure graph, and ends the validity of an
+ * optimiser's remembered closure and of a pending nst_closure_backward.  Every buffer of the option is allocated here,
+ * never in a closure.  nst_job_configure clears the setting.  The work belongs to the forward half of the closure.  It
+ * composes with any taps, colour mode, pooling, style layer weights, blends, the Laplacian loss, both schedules, the
+ * closure halves and level sharding.  While it is non-trivial, nst_level_set_guidance (R > 0),
+ * nst_level_set_targets_guided and nst_window_* return NST_E_STATE.
+ * nst_job_gram_shift: the current setting (either pointer may be NULL).
+ * nst_level_gram_offsets: the o that the level's last closure used for style slot `slot` (ascending map order of the
+ * current taps), C floats to out (DEVICE); zeros before the first closure.  NST_E_STATE without a non-trivial setting.
+ * nst_gram_shifted: the statistic alone, beside nst_gram: f device (C,h,w), C = 64 or a multiple of 128 up to 1024;
+ * center != 0: centred (shift must be 0); gram device (C,C); offset_out (nullable): device, C floats, the o used.  shift = 0
+ * without centring is nst_gram, bitwise.  f16x2 arithmetic only.  Synchronous on `stream`, as nst_gram. */
+int nst_job_set_gram_shift(nst_ctx* ctx, const float shift[6], unsigned center_mask);
+int nst_job_gram_shift(const nst_ctx* ctx, float shift[6], unsigned* center_mask);
+int nst_level_gram_offsets(nst_ctx* ctx, int level, int slot, float* out, void* stream);
+int nst_gram_shifted(nst_ctx* ctx, const float* f, int C, int h, int w, int normalize, int center, float shift, float* gram,
+                     float* offset_out /* nullable, C floats */, void* stream);
+
 /* LossBuilder.__init__ (neural_style_transfer.py:68-82): target content representation
  * ReLU(conv4_2) of the content image and the 5 target Gram matrices of the style image of one
  * level (of the maps nst_job_set_taps chose, when it was called).  content: device (3,h,w) of that level's size; style: device (3,hs,ws), any size.
@@ -420,7 +470,7 @@ int nst_opt_history(const nst_opt* opt, int* pairs, int* n_iter);
  * reproducible, so when a step starts at bitwise the image the previous step left (a rejected or skipped trial, or an
  * accepted trial whose closure was the last one made), with the same weights and no change to the job in between
  * (nst_job_configure, nst_job_set_taps, nst_job_set_color, nst_job_set_pooling, nst_job_set_style_weights,
- * nst_job_set_laplacian, nst_level_set_targets, nst_level_set_targets_blend), its first closure is served from what
+ * nst_job_set_laplacian, nst_job_set_gram_shift, nst_level_set_targets, nst_level_set_targets_blend), its first closure is served from what
  * the optimiser remembers instead of evaluated: same loss row, step counter, lr decay, step info and image.  One
  * device compare of x decides, so the caller may write x between steps.  Never in the sharded modes; Adam never.
  * Changing the setting drops what is remembered. */
@@ -588,7 +638,7 @@ int nst_luminance_recombine(nst_ctx* ctx, const float* u, const float* content, 
  * only: after nst_job_set_taps with any other taps both calls return NST_E_STATE, as they do under NST_COLOR_LUMINANCE,
  * under NST_POOL_AVG (nst_job_set_pooling) and under style layer weights other than 1 (nst_job_set_style_weights).  The
  * Gram targets are the level's, so those of nst_level_set_targets_blend are honoured.  nst_window_* returns NST_E_STATE
- * while the Laplacian loss is set (nst_job_set_laplacian with K > 0). */
+ * while the Laplacian loss is set (nst_job_set_laplacian with K > 0) or a Gram shift (nst_job_set_gram_shift). */
 int nst_window_sums_count(size_t* count);
 int nst_window_begin(nst_ctx* ctx, const float* xs, int row0, int rows, int H0, float* sums, void* stream);
 int nst_window_end(nst_ctx* ctx, const float* xs, int row0, int rows, int H0, float content_weight, float style_weight,
