@@ -47,17 +47,35 @@ __device__ __forceinline__ float mean255(int c) { return c == 0 ? 123.675f : (c 
 // LUM (nst_job_set_color luminance): x is ONE plane u (1,H,W) and the patch planes are x_c = u - mean_c inside the image,
 // 0 in the padding - the same LDS contents the RGB form stages from a planar image x_c = fl(u - mean_c), from a third of
 // the bytes.  Weights, MFMAs and epilogue are the RGB form's.
-template <bool LUM>
-__global__ __launch_bounds__(256, 2) void conv1_1_fwd_kernel(const float* __restrict__ x, int H, int W,
-                                                          const float* __restrict__ wk,
-                                                          const float* __restrict__ bias, float* __restrict__ out,
-                                                          unsigned* __restrict__ bits_out,
-                                                          unsigned* __restrict__ amax_out, int ntiles) {
+// BATCH (launch_conv1_1_fwd_batch): the loop walks the tiles of several images - global tile g belongs to the image i with
+// tile_end[i - 1] <= g < tile_end[i] - and x, H, W, the outputs and the absmax slots are that image's.  A workgroup's tiles
+// ascend, so its images do: the running absmax goes to an image's slots when the workgroup leaves the image.  Per tile the
+// instructions are the single-image form's.
+struct FwdTile {
+    const float* x; float* out; unsigned* bits_out;
+    int H, W, tiles_x, tile, img;
+};
+template <bool LUM, bool BATCH>
+__device__ __forceinline__ void conv1_1_fwd_body(const float* __restrict__ x1, int H1, int W1, const float* __restrict__ wk,
+                                                 const float* __restrict__ bias, float* __restrict__ out1,
+                                                 unsigned* __restrict__ bits1, unsigned* __restrict__ amax1, const int ntiles,
+                                                 const Conv1Batch* __restrict__ bp) {
     __shared__ float patch[3 * F_PLANE];
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const int half = lane >> 5, l31 = lane & 31;
-    const int tiles_x = (W + F_TW - 1) / F_TW;
+
+    // the image of global tile g and the tile's number inside it (g >= ntiles: any image - nothing of it is touched)
+    auto locate = [&](const int g) -> FwdTile {
+        if constexpr (BATCH) {
+            int i = 0;
+            while (i + 1 < bp->n && g >= bp->img[i].tile_end) ++i;
+            const Conv1Image& im = bp->img[i];
+            return FwdTile{im.x, im.out, im.bits_out, im.H, im.W, im.tiles_x, g - (i ? bp->img[i - 1].tile_end : 0), i};
+        } else {
+            return FwdTile{x1, out1, bits1, H1, W1, (W1 + F_TW - 1) / F_TW, g, 0};
+        }
+    };
 
     // patch element u of this thread: plane c, patch row r, patch column col (fixed for every tile)
     int pu_off[F_PATCH_PER_T];          // (c, r, col) packed
@@ -67,14 +85,17 @@ __global__ __launch_bounds__(256, 2) void conv1_1_fwd_kernel(const float* __rest
         const int c = u / F_PLANE, r = (u % F_PLANE) / F_PW, col = u % F_PW;
         pu_off[i] = (u < 3 * F_PLANE) ? (c << 16) | (r << 8) | col : -1;
     }
-    auto fetch = [&](int tile, float* v) {
-        const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    auto fetch = [&](const int g, float* v) {
+        const FwdTile t = locate(g);
+        const float* __restrict__ x = t.x;
+        const int H = t.H, W = t.W;
+        const int ty = t.tile / t.tiles_x, tx = t.tile - ty * t.tiles_x;
         const int y0 = ty * F_TH, x0 = tx * F_TW;
 #pragma unroll
         for (int i = 0; i < F_PATCH_PER_T; ++i) {
             const int pk = pu_off[i];
             const int c = pk >> 16, gy = y0 - 1 + ((pk >> 8) & 255), gx = x0 - 1 + (pk & 255);
-            const bool inb = pk >= 0 && tile < ntiles && gy >= 0 && gy < H && gx >= 0 && gx < W;
+            const bool inb = pk >= 0 && g < ntiles && gy >= 0 && gy < H && gx >= 0 && gx < W;
             if (LUM) v[i] = inb ? x[(size_t)gy * W + gx] - mean255(c) : 0.f;
             else v[i] = inb ? x[((size_t)c * H + gy) * W + gx] : 0.f;
         }
@@ -104,14 +125,32 @@ __global__ __launch_bounds__(256, 2) void conv1_1_fwd_kernel(const float* __rest
     const int pcol = l31 & 15;
     const int base0 = prow * F_PW + pcol;           // M-tile mt: rows wave * WROWS + 2 mt + {0,1}
     float amax = 0.f;
-    const bool small = (size_t)H * W * 256 < 0xFFFFFF00ull;
-    const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(out, 0, small ? (unsigned)((size_t)H * W * 256) : 0u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_bits = __builtin_amdgcn_make_buffer_rsrc(bits_out, 0, (bits_out && small) ? (unsigned)((size_t)H * W * 8) : 0u, 0x00020000);
+    // absmax of the output for the fp16-piece convolution that consumes it (conv_h2.hip)
+    auto record = [&](unsigned* __restrict__ slots) {
+        if (!slots) return;
+        float m = amax;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+        if (lane == 0) atomicMax(slots + ((blockIdx.x * 4 + wave) & (NST_AMAX_SLOTS - 1)), __float_as_uint(m));
+    };
+    int cur_img = BATCH ? locate(blockIdx.x).img : 0;
 
-    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    for (int g = blockIdx.x; g < ntiles; g += gridDim.x) {
+        const FwdTile t = locate(g);
+        if (BATCH && t.img != cur_img) {            // (workgroup-uniform) the outputs so far were the image before's
+            record(bp->img[cur_img].amax_out);
+            amax = 0.f;
+            cur_img = t.img;
+        }
+        float* __restrict__ out = t.out;
+        unsigned* __restrict__ bits_out = t.bits_out;
+        const int H = t.H, W = t.W;
+        const bool small = (size_t)H * W * 256 < 0xFFFFFF00ull;
+        const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(out, 0, small ? (unsigned)((size_t)H * W * 256) : 0u, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_bits = __builtin_amdgcn_make_buffer_rsrc(bits_out, 0, (bits_out && small) ? (unsigned)((size_t)H * W * 8) : 0u, 0x00020000);
+        const int ty = t.tile / t.tiles_x, tx = t.tile - ty * t.tiles_x;
         const int y0 = ty * F_TH, x0 = tx * F_TW;
-        fetch(tile + gridDim.x, pv);                // the next tile's patch: in flight under this tile's MFMAs
+        fetch(g + gridDim.x, pv);                   // the next tile's patch: in flight under this tile's MFMAs
 
         f32x16 acc[F_MT][2];
 #pragma unroll
@@ -186,12 +225,20 @@ __global__ __launch_bounds__(256, 2) void conv1_1_fwd_kernel(const float* __rest
         stash(pv);
         __syncthreads();
     }
-    if (amax_out) {
-        // absmax of the output for the fp16-piece convolution that consumes it (conv_h2.hip)
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off));
-        if (lane == 0) atomicMax(amax_out + ((blockIdx.x * 4 + wave) & (NST_AMAX_SLOTS - 1)), __float_as_uint(amax));
-    }
+    record(BATCH ? bp->img[cur_img].amax_out : amax1);
+}
+
+template <bool LUM>
+__global__ __launch_bounds__(256, 2) void conv1_1_fwd_kernel(const float* __restrict__ x, int H, int W,
+                                                          const float* __restrict__ wk,
+                                                          const float* __restrict__ bias, float* __restrict__ out,
+                                                          unsigned* __restrict__ bits_out,
+                                                          unsigned* __restrict__ amax_out, int ntiles) {
+    conv1_1_fwd_body<LUM, false>(x, H, W, wk, bias, out, bits_out, amax_out, ntiles, nullptr);
+}
+template <bool LUM>
+__global__ __launch_bounds__(256, 2) void conv1_1_fwd_batch_kernel(const Conv1Batch b) {
+    conv1_1_fwd_body<LUM, true>(nullptr, 0, 0, b.wk, b.bias, nullptr, nullptr, nullptr, b.img[b.n - 1].tile_end, &b);
 }
 
 hipError_t launch_conv1_1_fwd(const float* x, int H, int W, const float* wk, const float* bias, float* out,
@@ -202,6 +249,23 @@ hipError_t launch_conv1_1_fwd(const float* x, int H, int W, const float* wk, con
         hipLaunchKernelGGL(conv1_1_fwd_kernel<true>, dim3(blocks), dim3(256), 0, stream, x, H, W, wk, bias, out, bits_out, amax_out, ntiles);
     else
         hipLaunchKernelGGL(conv1_1_fwd_kernel<false>, dim3(blocks), dim3(256), 0, stream, x, H, W, wk, bias, out, bits_out, amax_out, ntiles);
+    return hipGetLastError();
+}
+
+hipError_t launch_conv1_1_fwd_batch(const Conv1Batch& b0, hipStream_t stream) {
+    if (b0.n < 1 || b0.n > 8) return hipErrorInvalidValue;
+    Conv1Batch b = b0;
+    int total = 0;
+    for (int i = 0; i < b.n; ++i) {
+        Conv1Image& im = b.img[i];
+        if (!im.x || !im.out || im.H < 1 || im.W < 1) return hipErrorInvalidValue;
+        im.tiles_x = (im.W + F_TW - 1) / F_TW;
+        total += ((im.H + F_TH - 1) / F_TH) * im.tiles_x;
+        im.tile_end = total;
+    }
+    const int blocks = total < 512 ? total : 512;            // as the single-image launch: every workgroup has a first tile
+    if (b.channels == 1) hipLaunchKernelGGL(conv1_1_fwd_batch_kernel<true>, dim3(blocks), dim3(256), 0, stream, b);
+    else hipLaunchKernelGGL(conv1_1_fwd_batch_kernel<false>, dim3(blocks), dim3(256), 0, stream, b);
     return hipGetLastError();
 }
 

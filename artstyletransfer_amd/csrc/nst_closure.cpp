@@ -477,7 +477,38 @@ int batched_gram(nst_ctx* ctx, const int* lv, int n, float sw, hipStream_t s, un
 int batched_forward(nst_ctx* ctx, const float* const* xi, const int* lv, int n, hipStream_t s, const Window* win, float fork_sw = -1.f) {
     const bool h2 = ctx->conv_mode == 2;
     const int top = ctx->taps.top;
-    for (int k = 0; k < n; ++k) {
+    // nst_ctx_set_forward_pack: the front of the network - absmax clears, TV partials, conv1_1 - in one launch each for all
+    // levels (levels 1 and 2 cannot fill the chip with conv1_1's two persistent workgroups per CU); stripes and a captured
+    // graph keep the per-level launches below
+    const bool pack = ctx->forward_pack && h2 && !win && !ctx->use_graph && n > 1;      // (one level: nothing to pack - target forwards)
+    if (pack) {
+        ZeroBatch zb{};
+        TvBatch tb{};
+        Conv1Batch cb{};
+        double flops = 0;
+        zb.n = tb.n = cb.n = n;
+        tb.C = ctx->channels;
+        cb.wk = ctx->w11k; cb.bias = ctx->bias[0]; cb.channels = ctx->channels;
+        for (int k = 0; k < n; ++k) {
+            LevelWs& L = ctx->lv[lv[k]];
+            ActSet& a = L.acts;
+            a.begin_pass();
+            zb.out[k] = a.amax; zb.n_words[k] = (size_t)AMAX_IDS * NST_AMAX_SLOTS;
+            tb.y[k] = xi[lv[k]]; tb.h[k] = L.h; tb.w[k] = L.w; tb.partial[k] = L.tv_partial;
+            cb.img[k] = Conv1Image{xi[lv[k]], a.act[0], a.bits[0], amax_act(a, 0), L.h, L.w, 0, 0};
+            flops += conv_flops(L.h, L.w, 3, 64, 9);
+            a.bits_valid[0] = true;
+            a.stored[0] = true;
+        }
+        HIPCHK(ctx, launch_zero_batch(zb, s));
+        {
+            Timer t(ctx, s, K_OTHER, 0);
+            HIPCHK(ctx, launch_tv_partial_batch(tb, s));
+        }
+        Timer t(ctx, s, K_CONV1, flops);
+        HIPCHK(ctx, launch_conv1_1_fwd_batch(cb, s));
+    }
+    for (int k = 0; k < n && !pack; ++k) {
         LevelWs& L = ctx->lv[lv[k]];
         ActSet& a = L.acts;
         a.begin_pass();
@@ -577,7 +608,10 @@ int batched_gram(nst_ctx* ctx, const int* lv, int n, float sw, hipStream_t s, un
                     it.part = L.gram_part + gram_part_offset(ctx->taps, L.h, L.w, q);
                     it.divisor = (float)st.divisor; it.target = L.gram_t[q];
                     it.coef = st.coef;
-                    it.gram_out = nullptr; it.S = L.S[q]; it.S_bf = L.S_bf[q]; it.S_amax = amax_S(L.acts, q);
+                    // (S in bf16 pieces is conv_bf3's operand: the f16x2 launches that multiply by S cut the fp32 S themselves -
+                    // conv_h2.hip takes wt2_f32 and never wt2_bf - so those 6 C^2 bytes per map are not written here;
+                    // nst_ctx_set_forward_pack(0) writes them as before)
+                    it.gram_out = nullptr; it.S = L.S[q]; it.S_bf = ctx->forward_pack ? nullptr : L.S_bf[q]; it.S_amax = amax_S(L.acts, q);
                     it.mse_partial = L.style_partial[q];
                     flops += 2.0 * (double)st.N * st.C * st.C;
                     if (shifted) {
@@ -811,6 +845,22 @@ int closure_batched_forward(nst_ctx* ctx, const float* const* xi, unsigned level
     NSTCHK(batched_forward(ctx, xi, lv, n, s, nullptr, overlap ? sw : -1.f));
     NSTCHK(batched_gram(ctx, lv, n, sw, s, overlap ? 0x18u : (1u << ctx->taps.nstyle) - 1u));
     if (overlap) HIPCHK(ctx, hipStreamWaitEvent(s, ctx->side_join, 0));
+    if (loss_terms && ctx->forward_pack && ctx->conv_mode == 2 && !ctx->use_graph && n > 1) {
+        // one launch each for all levels; every level keeps its partial buffers and block decomposition
+        MseBatch mb{};
+        TvBatch tb{};
+        mb.n = tb.n = n;
+        tb.C = ctx->channels;
+        for (int k = 0; k < n; ++k) {
+            LevelWs& L = ctx->lv[lv[k]];
+            mb.a[k] = L.acts.act[ctx->taps.content]; mb.t[k] = L.content_t; mb.cnt[k] = L.content_n; mb.partial[k] = L.content_partial;
+            tb.y[k] = xi[lv[k]]; tb.h[k] = L.h; tb.w[k] = L.w; tb.partial[k] = L.tv_partial; tb.means[k] = L.tv_means;
+        }
+        Timer t(ctx, s, K_OTHER, 0);
+        HIPCHK(ctx, launch_mse_partial_batch(mb, s));
+        HIPCHK(ctx, launch_tv_means_batch(tb, s));
+        return NST_OK;
+    }
     for (int k = 0; k < n && loss_terms; ++k) {
         LevelWs& L = ctx->lv[lv[k]];
         Timer t(ctx, s, K_OTHER, 0);

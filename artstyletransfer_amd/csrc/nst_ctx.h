@@ -208,6 +208,9 @@ struct nst_ctx {
     int persist = 1;            // nst_options.h2_persist
     int level_split = 0;        // nst_options.level_split
     int keep_all_maps = 0;      // nst_ctx_set_keep_all_maps: 1 = every batched forward launch stores its full-resolution map
+    // nst_ctx_set_forward_pack: 1 = the batched f16x2 forward half launches its front (absmax clears, TV partials, conv1_1)
+    // and its loss terms once for all levels and leaves S in bf16 pieces unwritten; 0 = per level, with the pieces
+    int forward_pack = 1;
     unsigned long long fwd_pass = 0;     // batched forward passes so far (ActSet::pass)
     hipStream_t side = nullptr; // the Gram launches of the shallow style layers run here, under the deeper forward convolutions
     hipEvent_t side_fork = nullptr, side_join = nullptr;

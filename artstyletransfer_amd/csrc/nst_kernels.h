@@ -148,6 +148,17 @@ hipError_t launch_absmax_slots(const float* x, size_t n, unsigned* slots, hipStr
 // convolution sees x_c = u - mean_c (bitwise the channels = 3 result at that planar image)
 hipError_t launch_conv1_1_fwd(const float* x, int H, int W, const float* wk, const float* bias, float* out,
                               unsigned* bits_out, unsigned* amax_out, hipStream_t stream, int channels = 3);
+// The same for every pyramid level of a pass in ONE launch: the persistent tile loop walks the tiles of image 0, then image
+// 1, ... (tile_end: the prefix, as ConvBatch's), so the small levels - which cannot fill the chip with two workgroups per CU
+// of their own - ride in the tail of the big one.  Every image keeps its outputs, mask words and absmax slots; each output
+// element is computed as launch_conv1_1_fwd computes it (a record's maximum may land in another slot).
+struct Conv1Image {
+    const float* x; float* out; unsigned* bits_out; unsigned* amax_out;
+    int H, W;
+    int tiles_x, tile_end;   // filled by the launcher
+};
+struct Conv1Batch { Conv1Image img[8]; int n; const float* wk; const float* bias; int channels; };
+hipError_t launch_conv1_1_fwd_batch(const Conv1Batch& b, hipStream_t stream);
 // g: [H][W][64] gradient w.r.t. the pre-ReLU conv1_1 output; wd: [9][64][4] flipped taps
 // (wd[t][co][c] = W[co][c][2-ky][2-kx], c = 3 unused 0); gx planar (3,H,W), overwritten.
 // amax_g: the absmax slots of g (the matrix-pipe form), or null (fp32 on the VALU).  channels = 1 (luminance mode):
@@ -188,6 +199,12 @@ constexpr int TV_BLOCKS = 1024;
 // row window [row0, row0 + rows) of every channel (rows <= 0: all rows): the sums / the gradient of those rows only
 hipError_t launch_tv_partial(const float* y, int C, int h, int w, double* partial, hipStream_t stream, int row0 = 0,
                              int rows = 0);
+// Several images (the pyramid levels of a pass) in one launch each: launch_tv_partial of every image (all rows), and the
+// means-only form of launch_tv_finish (grad = nullptr) - image i's TV_BLOCKS workgroups / one workgroup do what the launch of
+// its own does, on its own partial buffer
+struct TvBatch { const float* y[8]; int h[8], w[8]; double* partial[8]; float* means[8]; int n; int C; };
+hipError_t launch_tv_partial_batch(const TvBatch& b, hipStream_t stream);
+hipError_t launch_tv_means_batch(const TvBatch& b, hipStream_t stream);
 // reduces the partials (fixed order), writes means to scal[0..1]; if grad: grad (+)= weight * d tv/dy
 hipError_t launch_tv_finish(const float* y, int C, int h, int w, const double* partial, float weight, float* grad,
                             int accumulate, float* means, hipStream_t stream, int row0 = 0, int rows = 0,
@@ -197,6 +214,10 @@ hipError_t launch_tv_finish(const float* y, int C, int h, int w, const double* p
 constexpr int MSE_BLOCKS = 256;
 hipError_t launch_mse_grad(const float* a, const float* t, size_t n, float coef, float* g, double* partial,
                            hipStream_t stream);
+
+// the partial sums alone (g = nullptr) of several pairs in one launch: pair i's MSE_BLOCKS workgroups as launch_mse_grad's
+struct MseBatch { const float* a[8]; const float* t[8]; size_t cnt[8]; double* partial[8]; int n; };
+hipError_t launch_mse_partial_batch(const MseBatch& b, hipStream_t stream);
 
 // scalar plumbing of the stripe closure (pixel_ops.hip)
 hipError_t launch_sum_doubles(const double* p, int n, int stride, int offset, float* out, hipStream_t stream);
@@ -391,6 +412,8 @@ hipError_t launch_axpy(float alpha, const float* x, float* y, size_t n, hipStrea
 hipError_t launch_axpy_dev(const float* alpha_dev, float sign, const float* x, float* y, size_t n, hipStream_t stream);
 hipError_t launch_scale_copy(float alpha, const float* x, float* y, size_t n, hipStream_t stream);         // y = alpha*x
 hipError_t launch_add_scaled(const float* a, float alpha, const float* b, float* out, size_t n, hipStream_t stream);  // out = a + alpha*b
+struct ZeroBatch { void* out[8]; size_t n_words[8]; int n; };
+hipError_t launch_zero_batch(const ZeroBatch& b, hipStream_t stream);                                       // launch_zero of each buffer, one launch
 hipError_t launch_zero(void* out, size_t n_words, hipStream_t stream);                                      // out[0..n) = 0 (32-bit words, 16-byte aligned)
 hipError_t launch_copy(const float* a, float* out, size_t n, hipStream_t stream);                          // out = a (16-byte aligned)
 hipError_t launch_sub(const float* a, const float* b, float* out, size_t n, hipStream_t stream);           // out = a-b

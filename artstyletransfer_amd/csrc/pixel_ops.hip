@@ -401,13 +401,14 @@ hipError_t launch_bicubic_down_bwd(const float* gy, int C, int h, int w, int oh,
 }
 
 // ------------------------------------------------------------------ total variation (math_utils.py:37-41)
-__global__ __launch_bounds__(256) void tv_partial_kernel(const float* __restrict__ y, int C, int h, int w,
-                                                         double* __restrict__ partial, int row0, int rows) {
+// (bid of nblk: the block of ONE image's decomposition - the batched launch runs several images' blocks in one grid)
+__device__ __forceinline__ void tv_partial_body(const float* __restrict__ y, int C, int h, int w, double* __restrict__ partial,
+                                                int row0, int rows, const int bid, const int nblk) {
     __shared__ double sh[4];
     // block b takes the image rows (c, r) with (c h + r) % TV_BLOCKS == b, a thread every 256th column: a fixed
     // assignment (reproducible sums) without any per-element division
     float sx = 0.f, sy = 0.f;
-    for (int row = blockIdx.x; row < C * h; row += gridDim.x) {
+    for (int row = bid; row < C * h; row += nblk) {
         const int r = row % h;
         if (rows > 0 && (unsigned)(r - row0) >= (unsigned)rows) continue;
         const float* line = y + (size_t)row * w;
@@ -420,13 +421,27 @@ __global__ __launch_bounds__(256) void tv_partial_kernel(const float* __restrict
     const double bx = block_reduce_sum((double)sx, sh);
     const double by = block_reduce_sum((double)sy, sh);
     if (threadIdx.x == 0) {
-        partial[2 * blockIdx.x] = bx;
-        partial[2 * blockIdx.x + 1] = by;
+        partial[2 * bid] = bx;
+        partial[2 * bid + 1] = by;
     }
+}
+__global__ __launch_bounds__(256) void tv_partial_kernel(const float* __restrict__ y, int C, int h, int w,
+                                                         double* __restrict__ partial, int row0, int rows) {
+    tv_partial_body(y, C, h, w, partial, row0, rows, (int)blockIdx.x, (int)gridDim.x);
+}
+__global__ __launch_bounds__(256) void tv_partial_batch_kernel(TvBatch b) {
+    const int i = (int)blockIdx.x / TV_BLOCKS;
+    tv_partial_body(b.y[i], b.C, b.h[i], b.w[i], b.partial[i], 0, 0, (int)blockIdx.x - i * TV_BLOCKS, TV_BLOCKS);
 }
 
 hipError_t launch_tv_partial(const float* y, int C, int h, int w, double* partial, hipStream_t stream, int row0, int rows) {
     hipLaunchKernelGGL(tv_partial_kernel, dim3(TV_BLOCKS), dim3(256), 0, stream, y, C, h, w, partial, row0, rows);
+    return hipGetLastError();
+}
+
+hipError_t launch_tv_partial_batch(const TvBatch& b, hipStream_t stream) {
+    if (b.n < 1 || b.n > 8) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(tv_partial_batch_kernel, dim3(TV_BLOCKS * b.n), dim3(256), 0, stream, b);
     return hipGetLastError();
 }
 
@@ -474,6 +489,27 @@ __global__ __launch_bounds__(256) void tv_finish_kernel(const float* __restrict_
     }
 }
 
+// the means-only form (grad = nullptr: one workgroup) of several images: the same reduction of each image's partials
+__global__ __launch_bounds__(256) void tv_means_batch_kernel(TvBatch b) {
+    __shared__ double sh[4];
+    const int i = blockIdx.x;
+    const double* partial = b.partial[i];
+    double px = 0.0, py = 0.0;
+    for (int k = threadIdx.x; k < TV_BLOCKS; k += blockDim.x) { px += partial[2 * k]; py += partial[2 * k + 1]; }
+    const double tx = block_reduce_sum(px, sh);
+    const double ty = block_reduce_sum(py, sh);
+    const double nx = (double)b.C * b.h[i] * (b.w[i] - 1), ny = (double)b.C * (b.h[i] - 1) * b.w[i];
+    if (threadIdx.x == 0) {
+        b.means[i][0] = (float)tx / (float)nx;
+        b.means[i][1] = (float)ty / (float)ny;
+    }
+}
+hipError_t launch_tv_means_batch(const TvBatch& b, hipStream_t stream) {
+    if (b.n < 1 || b.n > 8) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(tv_means_batch_kernel, dim3(b.n), dim3(256), 0, stream, b);
+    return hipGetLastError();
+}
+
 hipError_t launch_tv_finish(const float* y, int C, int h, int w, const double* partial, float weight, float* grad,
                             int accumulate, float* means, hipStream_t stream, int row0, int rows, const float* given_means,
                             double nx, double ny) {
@@ -516,16 +552,15 @@ hipError_t launch_window_scalars(const float* sums, double nx, double ny, float*
 }
 
 // ------------------------------------------------------------------ content MSE (neural_style_transfer.py:95)
-__global__ __launch_bounds__(256) void mse_grad_kernel(const float* __restrict__ a, const float* __restrict__ t,
-                                                       size_t n, float coef, float* __restrict__ g,
-                                                       double* __restrict__ partial) {
+__device__ __forceinline__ void mse_grad_body(const float* __restrict__ a, const float* __restrict__ t, size_t n, float coef,
+                                              float* __restrict__ g, double* __restrict__ partial, const int bid, const int nblk) {
     __shared__ double sh[4];
     float s = 0.f;
     const size_t n4 = n / 4;
     const f32x4* av = reinterpret_cast<const f32x4*>(a);
     const f32x4* tv = reinterpret_cast<const f32x4*>(t);
     f32x4* gv = reinterpret_cast<f32x4*>(g);
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+    for (size_t i = (size_t)bid * blockDim.x + threadIdx.x; i < n4; i += (size_t)nblk * blockDim.x) {
         const f32x4 x = av[i], y = tv[i];
         f32x4 d;
 #pragma unroll
@@ -537,13 +572,30 @@ __global__ __launch_bounds__(256) void mse_grad_kernel(const float* __restrict__
         }
     }
     const double b = block_reduce_sum((double)s, sh);
-    if (threadIdx.x == 0) partial[blockIdx.x] = b;
+    if (threadIdx.x == 0) partial[bid] = b;
+}
+__global__ __launch_bounds__(256) void mse_grad_kernel(const float* __restrict__ a, const float* __restrict__ t,
+                                                       size_t n, float coef, float* __restrict__ g,
+                                                       double* __restrict__ partial) {
+    mse_grad_body(a, t, n, coef, g, partial, (int)blockIdx.x, (int)gridDim.x);
+}
+__global__ __launch_bounds__(256) void mse_partial_batch_kernel(MseBatch b) {
+    const int i = (int)blockIdx.x / MSE_BLOCKS;
+    mse_grad_body(b.a[i], b.t[i], b.cnt[i], 0.f, nullptr, b.partial[i], (int)blockIdx.x - i * MSE_BLOCKS, MSE_BLOCKS);
 }
 
 hipError_t launch_mse_grad(const float* a, const float* t, size_t n, float coef, float* g, double* partial,
                            hipStream_t stream) {
     if (n % 4 != 0) return hipErrorInvalidValue;
     hipLaunchKernelGGL(mse_grad_kernel, dim3(MSE_BLOCKS), dim3(256), 0, stream, a, t, n, coef, g, partial);
+    return hipGetLastError();
+}
+
+hipError_t launch_mse_partial_batch(const MseBatch& b, hipStream_t stream) {
+    if (b.n < 1 || b.n > 8) return hipErrorInvalidValue;
+    for (int i = 0; i < b.n; ++i)
+        if (b.cnt[i] % 4 != 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(mse_partial_batch_kernel, dim3(MSE_BLOCKS * b.n), dim3(256), 0, stream, b);
     return hipGetLastError();
 }
 

@@ -408,6 +408,22 @@ hipError_t launch_zero(void* out, size_t n_words, hipStream_t stream) {
     hipLaunchKernelGGL(zero_kernel, dim3(vblocks(n_words / 4 + 1)), dim3(256), 0, stream, static_cast<float*>(out), n_words);
     return hipGetLastError();
 }
+// the same clear of several small buffers in one launch (the absmax records of every pyramid level): blockIdx.y = buffer
+__global__ void zero_batch_kernel(ZeroBatch b) {
+    float* out = static_cast<float*>(b.out[blockIdx.y]);
+    const size_t n = b.n_words[blockIdx.y], n4 = n / 4;
+    const f32x4v z = {0.f, 0.f, 0.f, 0.f};
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x)
+        reinterpret_cast<f32x4v*>(out)[i] = z;
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) out[n4 * 4 + threadIdx.x] = 0.f;
+}
+hipError_t launch_zero_batch(const ZeroBatch& b, hipStream_t stream) {
+    if (b.n < 1 || b.n > 8) return hipErrorInvalidValue;
+    size_t nmax = 0;
+    for (int i = 0; i < b.n; ++i) nmax = b.n_words[i] > nmax ? b.n_words[i] : nmax;
+    hipLaunchKernelGGL(zero_batch_kernel, dim3(vblocks(nmax / 4 + 1), b.n), dim3(256), 0, stream, b);
+    return hipGetLastError();
+}
 hipError_t launch_add_scaled(const float* a, float alpha, const float* b, float* out, size_t n, hipStream_t stream) {
     hipLaunchKernelGGL(add_scaled_kernel, dim3(vblocks(n / 4 + 1)), dim3(256), 0, stream, a, alpha, b, out, n);
     return hipGetLastError();

@@ -547,6 +547,18 @@ int nst_level_activation(nst_ctx* ctx, int level, int layer, float* out, void* s
 int nst_job_map_stats(nst_ctx* ctx, int level, unsigned* stored_mask);
 int nst_ctx_set_keep_all_maps(nst_ctx* ctx, int enabled);
 int nst_ctx_keep_all_maps(const nst_ctx* ctx);
+/* The packed forward half (on by default).  In the batched f16x2 schedule a forward pass over more than one pyramid level
+ * clears the absmax records, takes the TV partial sums and runs conv1_1 in ONE launch each for all levels of the pass
+ * (conv1_1's persistent tile loop walks the tiles of every level), a forward half on its own (nst_closure_forward) takes its
+ * content and TV loss terms in one launch each, and the Gram finish pass no longer writes S in bf16 pieces, which only the
+ * bf16x3 arithmetic reads.  Every output element is computed by the same instructions in the same order under either
+ * setting: losses, gradients, maps, masks and codes are bitwise the same (an absmax record may hold its maximum in another
+ * slot).  Per-level walkers, target forwards, stripes and a context with use_graph = 1 keep the per-level launches.
+ *   nst_ctx_set_forward_pack(ctx, 0): the per-level launches and the bf16 pieces of S - the A/B twin in one build.  A new
+ *     context takes env NST_FORWARD_PACK (read once at creation), default 1.  nst_ctx_forward_pack: the setting, -1 for a
+ *     null context. */
+int nst_ctx_set_forward_pack(nst_ctx* ctx, int enabled);
+int nst_ctx_forward_pack(const nst_ctx* ctx);
 /* The image of pyramid level `level` >= 1 that the last closure evaluated - the bicubic 1/2 chain of x
  * (neural_style_transfer.py:170-176) - as (3,h_l,w_l) planar fp32 to out (device).  The total-variation term takes
  * sign(y_i - y_j) of neighbouring pixels: on flat image regions those differences are rounding noise of the down-sampling,
