@@ -76,6 +76,10 @@ SYMBOLS = {
     "nst_job_laplacian": (C.c_int, [c_void, C.POINTER(C.c_int), C.POINTER(C.c_int), c_float_p]),
     "nst_job_laplacian_losses": (C.c_int, [c_void, c_void, c_void]),
     "nst_laplacian_loss": (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, c_void, c_void, c_void]),
+    "nst_job_set_matting": (C.c_int, [c_void, C.c_float, C.c_double]),
+    "nst_job_matting": (C.c_int, [c_void, c_float_p, C.POINTER(C.c_double)]),
+    "nst_job_matting_losses": (C.c_int, [c_void, c_void, c_void]),
+    "nst_matting_loss": (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_double, c_void, c_void, c_void]),
     "nst_job_set_gram_shift": (C.c_int, [c_void, c_float_p, C.c_uint]),
     "nst_job_gram_shift": (C.c_int, [c_void, c_float_p, C.POINTER(C.c_uint)]),
     "nst_level_gram_offsets": (C.c_int, [c_void, C.c_int, C.c_int, c_void, c_void]),

@@ -5,6 +5,7 @@ from .style_modes import check_style_blend, check_style_layer_weights
 from .regions import check_exclusive, check_regions
 from .laplacian_modes import DEFAULT_POOL, normalize_laplacian
 from .gram_modes import check_exclusive as check_gram_exclusive, normalize_gram_shift
+from .matting_modes import DEFAULT_EPSILON, normalize_matting
 
 # jobs that may run at once PER GPU (the reference runs everything on device 0; here the
 # scheduler multiplies this by the number of GPUs of the node). Use 1 when levels_num > 2.
@@ -29,7 +30,8 @@ _DEFAULTS = dict(
 # use_relu=)); None = the reference's content 4 / style [0, 1, 2, 3, 5]; colour preservation (preserve_color=); and the
 # pooling of the feature network (pooling=); further style images with their blend (extra_styles=, style_blend=) and the
 # per-layer style weights (style_layer_weights=); spatial control (content_regions=, style_regions=, region_weights=); and
-# the Laplacian loss (laplacian_weight=, laplacian_pool=); and the Gram statistic (gram_shift=).
+# the Laplacian loss (laplacian_weight=, laplacian_pool=); the Gram statistic (gram_shift=); and the matting term
+# (matting_weight=, matting_epsilon=).
 # Not part of the positional order or the repr.
 _KW_ONLY = dict(
     content_layer=None,            # index 0..5 or a name of Vgg19.layer_names
@@ -46,6 +48,8 @@ _KW_ONLY = dict(
     laplacian_weight=None,         # number or up to 4 numbers >= 0: the gamma_k of the Laplacian loss (Li et al. 2017); None / 0: off
     laplacian_pool=DEFAULT_POOL,   # integer 1..32 or up to 4 distinct ones: the pool sizes p_k of its entries
     gram_shift=None,               # None / 0 | number | 'mean' | 6 entries | {map index or name: number or 'mean'}: shifted / centred Gram matrices
+    matting_weight=None,           # number >= 0: the gamma of the matting term (Luan et al. 2017: the photorealism regulariser); None / 0: off
+    matting_epsilon=DEFAULT_EPSILON,   # number > 0: the epsilon of the matting Laplacian
 )
 
 
@@ -74,6 +78,7 @@ class Config:
             check_style_blend(self.style_blend, 1 + len(self.extra_styles or ()), style_indices=())
         check_exclusive(check_regions(self.content_regions, self.style_regions, self.region_weights), self.extra_styles)
         normalize_laplacian(self.laplacian_weight, self.laplacian_pool)
+        normalize_matting(self.matting_weight, self.matting_epsilon)
         check_gram_exclusive(normalize_gram_shift(self.gram_shift, self.use_relu if isinstance(self.use_relu, bool) else None),
                              regions=check_regions(self.content_regions, self.style_regions, self.region_weights))
 

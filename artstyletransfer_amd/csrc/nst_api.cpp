@@ -212,6 +212,27 @@ int nst_laplacian_loss(nst_ctx* ctx, const float* y, const float* content, int C
     return sc.finish();
 }
 
+// The matting term on its own (include/nst_hip.h): value = mat of y under the guide I, grad (nullable, overwritten) =
+// d mat / dy with gamma = 1.  The launches of the closure, on scratch buffers.  Synchronous.
+int nst_matting_loss(nst_ctx* ctx, const float* y, const float* guide, int C, int h, int w, double epsilon, float* value, float* grad,
+                     void* stream) {
+    NSTCHK(bind(ctx));
+    if (!y || !guide || !value) return fail(ctx, NST_E_ARG, "null argument");
+    if (C != 1 && C != 3) return fail(ctx, NST_E_ARG, "C must be 3, or 1 for a luminance plane");
+    if (h < 3 || w < 3) return fail(ctx, NST_E_ARG, "the image must be at least 3x3");
+    if (!(epsilon > 0.0) || std::isinf(epsilon)) return fail(ctx, NST_E_ARG, "the matting epsilon must be finite and > 0");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int tiles = mat_tiles(h, w);
+    const double n = (C == 1 ? 1.0 : 3.0) * (double)(h - 2) * (double)(w - 2);
+    Scratch sc(ctx, s);
+    double* partial = nullptr;
+    NSTCHK(sc.alloc(&partial, (size_t)tiles));
+    HIPCHK(ctx, launch_mat_forward(y, guide, C, h, w, 1.0, epsilon, partial, s));
+    HIPCHK(ctx, launch_mat_value(partial, tiles, n, value, s));
+    if (grad) HIPCHK(ctx, launch_mat_backward(y, guide, C, h, w, 1.0, epsilon, (float)(2.0 / (255.0 * n)), grad, 0, s));
+    return sc.finish();
+}
+
 int nst_bicubic_half(nst_ctx* ctx, const float* x, int C, int h, int w, float* y, void* stream) {
     NSTCHK(bind(ctx));
     if (!x || !y || h < 2 || w < 2) return fail(ctx, NST_E_ARG, "bad argument");

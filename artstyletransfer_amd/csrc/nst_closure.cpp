@@ -200,6 +200,34 @@ int lap_backward(nst_ctx* ctx, LevelWs& L, float* grad, hipStream_t s) {
     return NST_OK;
 }
 
+// ---- the matting-Laplacian regulariser (include/nst_hip.h has the definition; kernels: matting.hip) --------------------
+// n: 3 (h-2)(w-2); a luminance plane (h-2)(w-2), with which the one-plane value is the three-channel one
+double mat_n(const nst_ctx* ctx, const LevelWs& L) { return (ctx->channels == 1 ? 1.0 : 3.0) * (double)(L.h - 2) * (double)(L.w - 2); }
+// coef = (float)(gamma 2 / (255 n)); on a luminance plane that is the sum over the three channels of E(u)
+float mat_coef(float gamma, double n) { return (float)((double)gamma * 2.0 / (255.0 * n)); }
+// forward part of level L on image y: the value partials of the tiles, which the loss row reads
+int mat_forward(nst_ctx* ctx, LevelWs& L, const float* y, hipStream_t s) {
+    if (!(ctx->mat_gamma > 0.f)) return NST_OK;
+    Timer t(ctx, s, K_OTHER, 0);
+    HIPCHK(ctx, launch_mat_forward(y, L.mat.guide, ctx->channels, L.h, L.w, 1.0 / 255.0, ctx->mat_eps, L.mat.partial, s));
+    return NST_OK;
+}
+// gradient part: one pass that adds coef * (the residuals of a pixel's windows) into the level gradient (after the TV and
+// Laplacian gradients)
+int mat_backward(nst_ctx* ctx, LevelWs& L, const float* y, float* grad, hipStream_t s) {
+    if (!(ctx->mat_gamma > 0.f)) return NST_OK;
+    Timer t(ctx, s, K_OTHER, 0);
+    HIPCHK(ctx, launch_mat_backward(y, L.mat.guide, ctx->channels, L.h, L.w, 1.0 / 255.0, ctx->mat_eps,
+                                    mat_coef(ctx->mat_gamma, mat_n(ctx, L)), grad, 1, s));
+    return NST_OK;
+}
+// the guide of level L: a copy of its content, made where the Laplacian targets are made
+int mat_set_guide(nst_ctx* ctx, LevelWs& L, const float* content, hipStream_t s) {
+    if (!(ctx->mat_gamma > 0.f)) return NST_OK;
+    HIPCHK(ctx, hipMemcpyAsync(L.mat.guide, content, (size_t)ctx->channels * L.h * L.w * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return NST_OK;
+}
+
 }  // namespace
 
 namespace nst {
@@ -814,6 +842,7 @@ int batched_backward(nst_ctx* ctx, const float* const* xi, float* const* gi, con
         else
             HIPCHK(ctx, launch_tv_finish(xi[lv[k]], ctx->channels, L.h, L.w, L.tv_partial, tvw, gi[lv[k]], 1, L.tv_means, s));
         if (!win) NSTCHK(lap_backward(ctx, L, gi[lv[k]], s));
+        if (!win) NSTCHK(mat_backward(ctx, L, xi[lv[k]], gi[lv[k]], s));
     }
     return NST_OK;
 }
@@ -842,6 +871,7 @@ int closure_batched_forward(nst_ctx* ctx, const float* const* xi, unsigned level
                          !guided_levels(ctx, lv, n);
     // the Laplacian term's residuals and partials (nst_job_set_laplacian): pixel space, beside the TV partials
     for (int k = 0; k < n; ++k) NSTCHK(lap_forward(ctx, ctx->lv[lv[k]], xi[lv[k]], false, s));
+    for (int k = 0; k < n; ++k) NSTCHK(mat_forward(ctx, ctx->lv[lv[k]], xi[lv[k]], s));       // (nst_job_set_matting: likewise)
     NSTCHK(batched_forward(ctx, xi, lv, n, s, nullptr, overlap ? sw : -1.f));
     NSTCHK(batched_gram(ctx, lv, n, sw, s, overlap ? 0x18u : (1u << ctx->taps.nstyle) - 1u));
     if (overlap) HIPCHK(ctx, hipStreamWaitEvent(s, ctx->side_join, 0));
@@ -903,6 +933,7 @@ int closure_per_level(nst_ctx* ctx, const float* const* xi, float* const* gi, in
         HIPCHK(ctx, launch_tv_partial(xi[level], ctx->channels, L.h, L.w, L.tv_partial, s));
     }
     NSTCHK(lap_forward(ctx, L, xi[level], false, s));
+    NSTCHK(mat_forward(ctx, L, xi[level], s));
     NSTCHK(forward(ctx, L.acts, xi[level], L.h, L.w, s, tp.top, ctx->channels));
     Inject inj[NL];
     GuidedBwd gbw[kMaxStyle];
@@ -949,7 +980,8 @@ int closure_per_level(nst_ctx* ctx, const float* const* xi, float* const* gi, in
         Timer t(ctx, s, K_OTHER, 0);
         HIPCHK(ctx, launch_tv_finish(xi[level], ctx->channels, L.h, L.w, L.tv_partial, tvw, gi[level], 1, L.tv_means, s));
     }
-    return lap_backward(ctx, L, gi[level], s);
+    NSTCHK(lap_backward(ctx, L, gi[level], s));
+    return mat_backward(ctx, L, xi[level], gi[level], s);
 }
 
 // what the loss-assembly kernel reads: every level's partial sums and normalisers; the rows of levels not in level_mask are zeros
@@ -966,6 +998,11 @@ LossAssembly fill_loss_assembly(const nst_ctx* ctx, unsigned level_mask, float c
         for (int k = 0; k < ctx->lap_k; ++k) { la.lv[i].lap_partial[k] = L.lap.partial[k]; la.lv[i].lap_n[k] = lap_n(L, ctx->lap_pool[k]); }
     }
     la.nlap = ctx->lap_k; la.lap_out = ctx->lap_vals;
+    la.mat_gamma = ctx->mat_gamma; la.mat_out = ctx->mat_vals;
+    for (int i = 0; i < ctx->levels && ctx->mat_gamma > 0.f; ++i) {
+        const LevelWs& L = ctx->lv[i];
+        la.lv[i].mat_partial = L.mat.partial; la.lv[i].mat_tiles = L.mat.tiles; la.lv[i].mat_n = mat_n(ctx, L);
+    }
     for (int k = 0; k < ctx->lap_k; ++k) la.lap_gamma[k] = ctx->lap_gamma[k];
     return la;
 }
@@ -1129,6 +1166,8 @@ int window_check(nst_ctx* ctx, const float* xs, int row0, int rows, int H0) {
         return fail(ctx, NST_E_STATE, "the stripe closure implements unit style layer weights only (nst_job_set_style_weights)");
     if (ctx->lap_k > 0)
         return fail(ctx, NST_E_STATE, "the stripe closure implements no Laplacian loss (nst_job_set_laplacian(ctx, 0, NULL, NULL) switches it off)");
+    if (ctx->mat_gamma > 0.f)
+        return fail(ctx, NST_E_STATE, "the stripe closure implements no matting term (nst_job_set_matting(ctx, 0, epsilon) switches it off)");
     if (ctx->gs_on())
         return fail(ctx, NST_E_STATE, "the stripe closure implements the plain Gram statistic only (nst_job_set_gram_shift with zeros switches the shift off)");
     LevelWs& L = ctx->lv[0];
@@ -1202,6 +1241,7 @@ int nst_level_set_targets_blend(nst_ctx* ctx, int level, const float* content, i
     LevelWs& L = ctx->lv[level];
     NSTCHK(set_content_target(ctx, level, content, s));
     NSTCHK(lap_forward(ctx, L, content, true, s));      // D s_k(content): the Laplacian targets are made with the others
+    NSTCHK(mat_set_guide(ctx, L, content, s));          // and the matting term's guide
     // style: Gt_q = sum_k b^[k][q] G_q(style_k), each image at its own size, in ascending k; the first contributing image
     // writes b^ G, the later ones add to it; an image with b^ = 0 on a map is skipped there, one with b^ = 0 on every map
     // of the set gets no forward pass, and no forward pass goes deeper than the deepest map its image contributes to
@@ -1374,6 +1414,7 @@ int nst_level_set_targets_guided(nst_ctx* ctx, int level, const float* content, 
     g.targets = false;
     NSTCHK(set_content_target(ctx, level, content, s));
     NSTCHK(lap_forward(ctx, L, content, true, s));
+    NSTCHK(mat_set_guide(ctx, L, content, s));
     float* part = nullptr;
     NSTCHK(alloc_acts(ctx, sc.acts, hs, ws));
     NSTCHK(sc.alloc(&part, gram_part_floats_for(tp, hs, ws)));

@@ -319,6 +319,7 @@ int alloc_level_image(nst_ctx* ctx, LevelWs& L) {
 void free_level(nst_ctx* ctx, LevelWs& L) {
     free_guidance(ctx, L);
     free_laplacian(ctx, L);
+    free_matting(ctx, L);
     free_gram_shift(ctx, L);
     free_acts(ctx, L.acts);
     dev_free(L.gbuf[0]); dev_free(L.gbuf[1]); dev_free(L.xl); dev_free(L.gxl);
@@ -346,6 +347,12 @@ void free_laplacian(nst_ctx* ctx, LevelWs& L) {
     for (int k = 0; k < NST_LAP_MAX; ++k) { dev_free(q.s[k]); dev_free(q.r[k]); dev_free(q.target[k]); dev_free(q.partial[k]); }
     if (ctx->bytes >= q.bytes) ctx->bytes -= q.bytes;
     q = LapLevel();
+}
+
+void free_matting(nst_ctx* ctx, LevelWs& L) {
+    dev_free(L.mat.guide); dev_free(L.mat.partial);
+    if (ctx->bytes >= L.mat.bytes) ctx->bytes -= L.mat.bytes;
+    L.mat = MatLevel();
 }
 
 void free_gram_shift(nst_ctx* ctx, LevelWs& L) {
@@ -618,7 +625,7 @@ void nst_ctx_destroy(nst_ctx* ctx) {
     for (int i = 0; i < NST_MAX_LEVELS; ++i) free_level(ctx, ctx->lv[i]);
     if (ctx->tail) (void)hipEventDestroy(ctx->tail);
     for (int l = 0; l < NL; ++l) { dev_free(ctx->wf[l]); dev_free(ctx->wd[l]); dev_free(ctx->bias[l]); dev_free(ctx->wf_bf[l]); dev_free(ctx->wd_bf[l]); dev_free(ctx->wf_h2[l]); dev_free(ctx->wd_h2[l]); dev_free(ctx->wf_wino[l]); dev_free(ctx->wd_wino[l]); }
-    dev_free(ctx->w11k); dev_free(ctx->w11d); dev_free(ctx->color_scratch); dev_free(ctx->lap_vals);
+    dev_free(ctx->w11k); dev_free(ctx->w11d); dev_free(ctx->color_scratch); dev_free(ctx->lap_vals); dev_free(ctx->mat_vals);
     drop_closure_state(ctx, false);
     if (ctx->gstream) (void)hipStreamDestroy(ctx->gstream);
     if (ctx->side) (void)hipStreamDestroy(ctx->side);
@@ -651,6 +658,7 @@ int nst_job_configure(nst_ctx* ctx, int levels_num, int H0, int W0) {
     forget_forward_pass(ctx);
     ctx->levels = 0;
     ctx->lap_k = 0;                      // (the Laplacian setting belongs to the job's geometry: its buffers went with the levels)
+    ctx->mat_gamma = 0.f; ctx->mat_eps = 1e-7;   // (the matting term likewise)
     for (float& v : ctx->gs_shift) v = 0.f;      // (the Gram shift likewise)
     ctx->gs_center = 0u;
     int h = H0, w = W0;
@@ -869,6 +877,67 @@ int nst_job_laplacian_losses(nst_ctx* ctx, float* out, void* stream) {
     hipStream_t s = enter(ctx, stream);
     const size_t bytes = (size_t)ctx->levels * NST_LAP_MAX * sizeof(float);
     if (ctx->lap_k > 0 && ctx->lap_vals) HIPCHK(ctx, hipMemcpyAsync(out, ctx->lap_vals, bytes, hipMemcpyDeviceToDevice, s));
+    else HIPCHK(ctx, hipMemsetAsync(out, 0, bytes, s));
+    mark(ctx, s);
+    return NST_OK;
+}
+
+// The matting-Laplacian regulariser (Luan et al. 2017; include/nst_hip.h has the definition): a weight and epsilon.  The
+// life cycle of nst_job_set_laplacian: every level's targets go (the guide, a copy of the level's content, is made with
+// them), and the captured closure.  Every buffer of the term is allocated here; a refusal changes nothing.
+int nst_job_set_matting(nst_ctx* ctx, float gamma, double epsilon) {
+    if (ctx) { ++ctx->closure_epoch; ++ctx->ws_seq; }
+    NSTCHK(bind(ctx));
+    if (ctx->levels < 1) return fail(ctx, NST_E_STATE, "nst_job_configure has not been called");
+    if (!(gamma >= 0.f) || std::isinf(gamma)) return fail(ctx, NST_E_ARG, "the matting weight must be finite and >= 0");
+    if (!(epsilon > 0.0) || std::isinf(epsilon)) return fail(ctx, NST_E_ARG, "the matting epsilon must be finite and > 0");
+    const bool on = gamma > 0.f;
+    // the new buffers beside the old ones: a failed allocation leaves the context as it was
+    MatLevel fresh[NST_MAX_LEVELS];
+    int rc = NST_OK;
+    if (on && !ctx->mat_vals) rc = dev_alloc_t(ctx, &ctx->mat_vals, (size_t)NST_MAX_LEVELS);
+    for (int i = 0; on && i < ctx->levels && rc == NST_OK; ++i) {
+        MatLevel& q = fresh[i];
+        const size_t px = (size_t)ctx->lv[i].h * ctx->lv[i].w;
+        q.tiles = mat_tiles(ctx->lv[i].h, ctx->lv[i].w);
+        rc = dev_alloc_t(ctx, &q.guide, 3 * px);             // (three planes: a colour mode set later fits)
+        if (rc == NST_OK) q.bytes += std::max<size_t>(3 * px * sizeof(float), 16);
+        if (rc == NST_OK) rc = dev_alloc_t(ctx, &q.partial, (size_t)q.tiles);
+        if (rc == NST_OK) q.bytes += std::max<size_t>((size_t)q.tiles * sizeof(double), 16);
+    }
+    if (rc != NST_OK) {
+        LevelWs tmp;
+        for (int i = 0; i < ctx->levels; ++i) { tmp.mat = fresh[i]; free_matting(ctx, tmp); }
+        return rc;
+    }
+    quiesce(ctx);
+    drop_closure_state(ctx, true);
+    for (int i = 0; i < ctx->levels; ++i) {
+        free_matting(ctx, ctx->lv[i]);
+        ctx->lv[i].mat = fresh[i];
+    }
+    ctx->mat_gamma = gamma;
+    ctx->mat_eps = epsilon;
+    if (ctx->mat_vals) HIPCHK(ctx, hipMemset(ctx->mat_vals, 0, (size_t)NST_MAX_LEVELS * sizeof(float)));
+    return NST_OK;
+}
+
+int nst_job_matting(const nst_ctx* ctx, float* gamma, double* epsilon) {
+    if (!ctx) return fail(nullptr, NST_E_ARG, "null context");
+    if (gamma) *gamma = ctx->mat_gamma;
+    if (epsilon) *epsilon = ctx->mat_eps;
+    return NST_OK;
+}
+
+// the unweighted mat of the last closure per level, as the loss rows left it (zeros: levels outside the last level mask, no
+// closure yet, term off)
+int nst_job_matting_losses(nst_ctx* ctx, float* out, void* stream) {
+    NSTCHK(bind(ctx));
+    if (ctx->levels < 1) return fail(ctx, NST_E_STATE, "nst_job_configure has not been called");
+    if (!out) return fail(ctx, NST_E_ARG, "null argument");
+    hipStream_t s = enter(ctx, stream);
+    const size_t bytes = (size_t)ctx->levels * sizeof(float);
+    if (ctx->mat_gamma > 0.f && ctx->mat_vals) HIPCHK(ctx, hipMemcpyAsync(out, ctx->mat_vals, bytes, hipMemcpyDeviceToDevice, s));
     else HIPCHK(ctx, hipMemsetAsync(out, 0, bytes, s));
     mark(ctx, s);
     return NST_OK;

@@ -129,6 +129,16 @@ struct LapLevel {
     size_t bytes = 0;
 };
 
+// The matting term of one level (nst_job_set_matting; include/nst_hip.h has the definition): the guide, a copy of the level's
+// content as nst_level_set_targets* got it (channels x h x w, made with the targets), and the value partials of the tiles.
+// Made by the setter, freed when the setting is cleared or the job configured again: a closure allocates nothing.
+struct MatLevel {
+    float* guide = nullptr;
+    double* partial = nullptr;
+    int tiles = 0;
+    size_t bytes = 0;
+};
+
 // The shifted / centred Gram statistic of one level (nst_job_set_gram_shift; include/nst_hip.h has the definition): per style
 // slot the offsets o the last closure used, the row bias r = o S of its backward, the absmax record of the shifted operand
 // F + o, and (a centred map) the scratch of the channel sums.  Sized for the widest map, so the taps may change under it.
@@ -154,6 +164,7 @@ struct LevelWs {
     int h = 0, w = 0;
     Guidance guide;
     LapLevel lap;
+    MatLevel mat;
     GramShiftLevel gs;
     ActSet acts;
     float* gbuf[2] = {};
@@ -245,6 +256,11 @@ struct nst_ctx {
     int lap_pool[nst::NST_LAP_MAX] = {};
     float lap_gamma[nst::NST_LAP_MAX] = {};
     float* lap_vals = nullptr;
+    // nst_job_set_matting: the weight (0 = the term is off) and epsilon; mat_vals: device, NST_MAX_LEVELS floats, the
+    // unweighted mat of the last closure (written by the loss rows; made by the first setter call that switches the term on)
+    float mat_gamma = 0.f;
+    double mat_eps = 1e-7;
+    float* mat_vals = nullptr;
     // nst_job_set_gram_shift: per map index (as the style layer weights) a constant shift, or (bit of gs_center) centring
     float gs_shift[6] = {};
     unsigned gs_center = 0;
@@ -254,7 +270,7 @@ struct nst_ctx {
     }
     float gs_shift_of(int q) const { return gs_shift[nst::tap_index_of(taps.style[q])]; }                  // of style slot q
     int gs_center_of(int q) const { return (int)((gs_center >> nst::tap_index_of(taps.style[q])) & 1u); }
-    // bumped on entry to every call that changes what a closure computes (configure, taps, colour, pooling, style weights, Laplacian, Gram shift, targets), failure paths
+    // bumped on entry to every call that changes what a closure computes (configure, taps, colour, pooling, style weights, Laplacian, matting, Gram shift, targets), failure paths
     // included: an optimiser's remembered closure result is valid only under the epoch it was made in (nst_opt.cpp)
     unsigned long long closure_epoch = 0;
     // advanced on entry to every call that reads or writes the level workspaces (nst_closure*, nst_window_*,
@@ -347,6 +363,7 @@ int bind(nst_ctx* ctx);                            // null check + hipSetDevice:
 void drop_closure_state(nst_ctx* ctx, bool drop_targets);
 void free_guidance(nst_ctx* ctx, LevelWs& L);      // the level is unguided afterwards
 void free_laplacian(nst_ctx* ctx, LevelWs& L);     // the level's Laplacian buffers (the setting itself is the context's)
+void free_matting(nst_ctx* ctx, LevelWs& L);       // the level's matting buffers (likewise)
 void free_gram_shift(nst_ctx* ctx, LevelWs& L);    // the level's shifted-Gram buffers (likewise)
 hipStream_t enter(nst_ctx* ctx, void* stream);     // orders the caller's stream after the context's tail event
 void mark(nst_ctx* ctx, hipStream_t s);            // records the tail event

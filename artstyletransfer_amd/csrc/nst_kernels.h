@@ -251,6 +251,19 @@ struct LapBackward {
 };
 hipError_t launch_lap_backward(const LapBackward& lb, int C, int h, int w, float* grad, int accumulate, hipStream_t stream);
 
+// matting.hip: the matting-Laplacian regulariser (include/nst_hip.h has the definition) -------------------------------
+// guide (C,h,w): gscale * guide is the guide I up to a constant per channel (1 / 255: the level's prepared content; 1: I
+// itself).  C = 3, or 1 = a luminance plane under a one-plane guide (the scalar reduction, epsilon / 3).
+int mat_tiles(int h, int w);         // tile partials of one image (0: smaller than 3x3)
+// partial: mat_tiles(h, w) doubles, partial[t] = sum of E_kc over the windows of tile t (fixed order)
+hipError_t launch_mat_forward(const float* y, const float* guide, int C, int h, int w, double gscale, double eps, double* partial,
+                              hipStream_t stream);
+// grad (C,h,w) (+)= coef * sum over the windows k of a pixel of (Vc_i - a_kc^T Ic_i); the windows are computed again
+hipError_t launch_mat_backward(const float* y, const float* guide, int C, int h, int w, double gscale, double eps, float coef,
+                               float* grad, int accumulate, hipStream_t stream);
+// out[0] = (float)(sum of the tile partials / n), in the order of the loss rows
+hipError_t launch_mat_value(const double* partial, int tiles, double n, float* out, hipStream_t stream);
+
 // loss assembly -----------------------------------------------------------------------------------
 struct LevelLossInputs {
     const double* content_partial;   // MSE_BLOCKS doubles
@@ -262,6 +275,9 @@ struct LevelLossInputs {
     int owned;                       // 0: level computed by another rank, its row is written as zeros
     const double* lap_partial[NST_LAP_MAX];   // Laplacian entries: LAP_BLOCKS doubles each, partial sums of r_k^2
     double lap_n[NST_LAP_MAX];       // (hk-2)(wk-2) of each entry
+    const double* mat_partial;       // matting term: mat_tiles doubles, partial sums of E_kc
+    int mat_tiles;
+    double mat_n;                    // channels (h-2)(w-2)
 };
 struct LossAssembly {
     LevelLossInputs lv[8];
@@ -272,6 +288,8 @@ struct LossAssembly {
     int nlap;                        // Laplacian entries (nst_job_set_laplacian); 0: the row is what it is without the term
     float lap_gamma[NST_LAP_MAX];
     float* lap_out;                  // levels x NST_LAP_MAX: the unweighted lap_k (zeros for levels not owned, unused entries)
+    float mat_gamma;                 // matting term (nst_job_set_matting); 0: the row is what it is without the term
+    float* mat_out;                  // levels: the unweighted mat (zeros for levels not owned)
 };
 hipError_t launch_loss_assemble(const LossAssembly& la, hipStream_t stream);
 

@@ -643,11 +643,13 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(LossAssembly la) {
 #pragma clang fp contract(off)
     __shared__ double sh[7][4];
     __shared__ double shl[NST_LAP_MAX][4];
+    __shared__ double shm[4];
     const int l = blockIdx.x;
     const LevelLossInputs& in = la.lv[l];
     if (!in.owned) {
         if (threadIdx.x < 4) la.out[4 * l + threadIdx.x] = 0.f;
         if (la.nlap > 0 && threadIdx.x < NST_LAP_MAX) la.lap_out[NST_LAP_MAX * l + threadIdx.x] = 0.f;
+        if (la.mat_gamma > 0.f && threadIdx.x == 0) la.mat_out[l] = 0.f;
         return;
     }
     double v[7];
@@ -685,6 +687,13 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(LossAssembly la) {
             if (lane == 0) shl[k][w] = x;
         }
     }
+    // the matting term's tile partials: strided share in index order, then the same tree (mat_gamma = 0: nothing here runs)
+    if (la.mat_gamma > 0.f) {
+        double x = 0.0;
+        for (int b = threadIdx.x; b < in.mat_tiles; b += 256) x += in.mat_partial[b];
+        for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
+        if (lane == 0) shm[w] = x;
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
         double r[7];
@@ -714,6 +723,14 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(LossAssembly la) {
                 la.lap_out[NST_LAP_MAX * l + k] = lk;
             }
             total = total + lap;
+        }
+        if (la.mat_gamma > 0.f) {
+            // (... + lap) + gamma * mat, mat = (float)(sum E / n): added last, product and sum each rounded
+            double rm = 0.0;
+            for (int i = 0; i < 4; ++i) rm += shm[i];
+            const float mat = (float)(rm / in.mat_n);
+            la.mat_out[l] = mat;
+            total = total + la.mat_gamma * mat;
         }
         la.out[4 * l + 0] = total;
         la.out[4 * l + 1] = content;

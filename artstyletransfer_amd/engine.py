@@ -15,6 +15,7 @@ from . import style_modes as _style
 from . import regions as _regions
 from . import gram_modes as _gram
 from . import laplacian_modes as _lap
+from . import matting_modes as _mat
 from ._lib import NST_LOSS_ROW, NstError, StepInfo
 
 TAP_CHANNELS = (64, 128, 256, 512, 512, 512)
@@ -97,6 +98,7 @@ class StyleEngine:
         self.pooling = "max"                     # "avg" under set_pooling("avg")
         self.layer_weights = _style.UNIT_WEIGHTS # set_style_weights
         self.laplacian = None                    # (pools, weights) under set_laplacian
+        self.matting = None                      # (gamma, epsilon) under set_matting
         self.gram_shift = None                   # (shift[6], center_mask) under set_gram_shift
 
     def close(self):
@@ -116,6 +118,7 @@ class StyleEngine:
         self.levels = levels_num
         self.shape = (H0, W0)
         self.laplacian = None                    # (nst_job_configure clears the Laplacian setting)
+        self.matting = None                      # (the matting term)
         self.gram_shift = None                   # (and the Gram shift)
 
     def set_taps(self, content_index, style_indices, use_relu: bool = True) -> None:
@@ -232,6 +235,45 @@ class StyleEngine:
         out = torch.empty((self.levels, _lib.NST_MAX_LAPLACIAN), dtype=torch.float32, device=self.device)
         _lib.check(self.ctx, self.lib.nst_job_laplacian_losses(self.ctx, _ptr(out), _stream(self.device)),
                    "nst_job_laplacian_losses")
+        return out
+
+    def set_matting(self, gamma, epsilon=_mat.DEFAULT_EPSILON) -> None:
+        """The matting term of the job (nst_job_set_matting; Luan et al. 2017): the level total gains gamma * mat, the
+        quadratic form of the matting Laplacian of the level's content on the level image.  gamma None or 0 switches the
+        term off.  Needs a configured job; drops the targets of every level: call set_targets again.  ValueError (before
+        the context is touched) for a malformed setting or a level smaller than 3x3."""
+        setting = _mat.normalize_matting(gamma, epsilon)
+        if setting is None:
+            self.reset_matting()
+            return
+        if not self.levels:
+            raise NstError("set_matting needs a configured job (configure first)")
+        _mat.check_levels(self.levels, *self.shape)
+        try:
+            _lib.check(self.ctx, self.lib.nst_job_set_matting(self.ctx, setting[0], setting[1]), "nst_job_set_matting")
+        finally:                                 # the context's setting, whether the call succeeded or not
+            self.matting = self.matting_setting()
+
+    def matting_setting(self):
+        """The context's matting term as (gamma, epsilon), or None when it is off (nst_job_matting)."""
+        gamma, eps = C.c_float(), C.c_double()
+        _lib.check(self.ctx, self.lib.nst_job_matting(self.ctx, C.byref(gamma), C.byref(eps)), "nst_job_matting")
+        return (float(gamma.value), float(eps.value)) if gamma.value > 0 else None
+
+    def reset_matting(self) -> None:
+        """The matting term off, if it was set (drops the targets then, as set_matting does)."""
+        if self.matting is not None:
+            try:
+                _lib.check(self.ctx, self.lib.nst_job_set_matting(self.ctx, 0.0, self.matting[1]), "nst_job_set_matting")
+            finally:
+                self.matting = self.matting_setting()
+
+    def matting_losses(self) -> torch.Tensor:
+        """(levels,) device tensor: the unweighted mat of the last closure per level (nst_job_matting_losses); zeros for
+        levels outside the last level mask and while the term is off."""
+        out = torch.empty((self.levels,), dtype=torch.float32, device=self.device)
+        _lib.check(self.ctx, self.lib.nst_job_matting_losses(self.ctx, _ptr(out), _stream(self.device)),
+                   "nst_job_matting_losses")
         return out
 
     def set_gram_shift(self, shift, center_mask: int = 0) -> None:
@@ -712,6 +754,20 @@ class StyleEngine:
                                                          _ptr(grad), _stream(self.device)), "nst_laplacian_loss")
         return (val, grad) if want_grad else val
 
+    def matting_loss(self, y: torch.Tensor, guide: torch.Tensor, epsilon: float = _mat.DEFAULT_EPSILON, want_grad: bool = False):
+        """The matting term on its own (nst_matting_loss): mat of the prepared (1,C,h,w) image y under the guide I (same
+        shape, in [0,1] for ordinary input), C = 3 or 1 (a luminance plane under a one-plane guide); with want_grad also
+        d mat / dy."""
+        eps = _mat.normalize_matting(1.0, epsilon)[1]
+        _chk_dev(y, self.device)
+        _chk_dev(guide, self.device, y.shape)
+        b, c, h, w = y.shape
+        val = torch.empty(1, dtype=torch.float32, device=self.device)
+        grad = torch.empty_like(y) if want_grad else None
+        _lib.check(self.ctx, self.lib.nst_matting_loss(self.ctx, _ptr(y), _ptr(guide), b * c, h, w, eps, _ptr(val),
+                                                       _ptr(grad), _stream(self.device)), "nst_matting_loss")
+        return (val, grad) if want_grad else val
+
     def bicubic_half(self, x: torch.Tensor) -> torch.Tensor:
         _chk_dev(x, self.device)
         b, c, h, w = x.shape
@@ -955,6 +1011,8 @@ class PixelOptimizer:
             raise ValueError("the stripe closure implements unit style layer weights only (reset_style_weights())")
         if e.laplacian is not None:
             raise ValueError("laplacian_weight cannot be combined with stripe sharding (reset_laplacian())")
+        if getattr(e, "matting", None) is not None:
+            raise ValueError("matting_weight cannot be combined with stripe sharding (reset_matting())")
         _gram.check_exclusive(getattr(e, "gram_shift", None), stripes=True)
         contents = list(content_t) if isinstance(content_t, (list, tuple)) else [content_t]
         styles = list(style_t) if isinstance(style_t, (list, tuple)) else [style_t]

@@ -133,6 +133,7 @@ def return_engine(eng: StyleEngine) -> None:
             eng.reset_pooling()
             eng.reset_laplacian()              # (already off: release_job configured the context anew)
             eng.reset_gram_shift()             # (likewise)
+            eng.reset_matting()                # (likewise)
         except Exception:
             keep = False
     if keep:

@@ -25,6 +25,7 @@ from . import style_modes as _style
 from . import regions as _regions
 from . import gram_modes as _gram
 from . import laplacian_modes as _lap
+from . import matting_modes as _mat
 
 # ImageNet statistics (reference :22-23)
 IMAGENET_MEAN_255 = [123.675, 116.28, 103.53]
@@ -117,6 +118,19 @@ class LossBuilder:
             self.__engine.set_laplacian(*entries)
         self.__engine.set_targets(0, *self.__targets)       # (the setting drops them: the Laplacian targets are made with them)
 
+    def set_matting(self, matting_weight=None, matting_epsilon=_mat.DEFAULT_EPSILON):
+        """Extension: the matting term (Luan et al. 2017) as one more term of `build` - the level total gains
+        matting_weight * mat, the quadratic form of the content's matting Laplacian on the image (see nst_job_set_matting in
+        include/nst_hip.h).  None or 0 switches it off.  ValueError for a malformed setting."""
+        setting = _mat.normalize_matting(matting_weight, matting_epsilon)
+        if setting is None and self.__engine.matting is None:
+            return
+        if setting is None:
+            self.__engine.reset_matting()
+        else:
+            self.__engine.set_matting(*setting)
+        self.__engine.set_targets(0, *self.__targets)       # (the setting drops them: the guide is made with them)
+
     def set_gram_shift(self, gram_shift=None):
         """Extension: the Gram statistic of the style term of `build` - activation-shifted (Novak & Nikulin 2016) or
         mean-centred (the covariance; Li et al. 2017) per feature map: None or 0 (the plain Gram), a number (that shift on
@@ -151,7 +165,7 @@ class _DeviceJob:
     (`_make_job`, tests/test_host_api.py)."""
 
     def __init__(self, device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, taps=None, color=None,
-                 pooling=None, style_weights=None, blend=None, regions=None, laplacian=None, gram_shift=None):
+                 pooling=None, style_weights=None, blend=None, regions=None, laplacian=None, gram_shift=None, matting=None):
         self.dev = dev = device
         self.optimizer = None
         self.luminance = color == "luminance"   # the optimised image is u = 255 Y; the yield puts the content's I, Q back
@@ -188,7 +202,9 @@ class _DeviceJob:
                     engine.set_style_weights(style_weights)
                 if laplacian is not None:           # (pools, weights) of the Laplacian loss, normalised
                     engine.set_laplacian(*laplacian)
-                if gram_shift is not None:          # (shift[6], center_mask) of the Gram statistic, normalised
+                if matting is not None:             # (gamma, epsilon) of the matting term, normalised
+                    engine.set_matting(*matting)
+                if gram_shift is not None:         # (shift[6], center_mask) of the Gram statistic, normalised
                     engine.set_gram_shift(*gram_shift)
                 # blend = (per-level image lists of the extra styles, K x 6 matrix): style 0 is style_imgs
                 all_styles = [style_imgs] + (list(blend[0]) if blend is not None else [])
@@ -265,9 +281,9 @@ class _DeviceJob:
 
 
 def _make_job(device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, taps=None, color=None, pooling=None,
-              style_weights=None, blend=None, regions=None, laplacian=None, gram_shift=None):
+              style_weights=None, blend=None, regions=None, laplacian=None, gram_shift=None, matting=None):
     return _DeviceJob(device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, taps, color, pooling,
-                      style_weights, blend, regions, laplacian, gram_shift)
+                      style_weights, blend, regions, laplacian, gram_shift, matting)
 
 
 async def _drain(step_future):
@@ -305,7 +321,8 @@ class NeuralStyleTransfer:
         self.__blend = None                      # set_style_blend: (extra style levels, blend as given)
         self.__regions = None                    # set_regions: (content stack, style stack, region weights)
         self.__laplacian = None                  # set_laplacian: (pools, weights)
-        self.__gram_shift = None                 # set_gram_shift: (shift[6], center_mask)
+        self.__matting = None                    # set_matting: (gamma, epsilon)
+        self.__gram_shift = None               # set_gram_shift: (shift[6], center_mask)
 
     def set_feature_maps(self, content_layer=None, style_layers=None, use_relu=True):
         """Extension: the feature maps the losses of the next `process` read - a content map and a set of style maps of
@@ -377,6 +394,14 @@ class NeuralStyleTransfer:
         level sizes are known - for a level too small for a pool size."""
         self.__laplacian = _lap.normalize_laplacian(laplacian_weight, laplacian_pool)
 
+    def set_matting(self, matting_weight=None, matting_epsilon=_mat.DEFAULT_EPSILON):
+        """Extension: the photorealism regulariser of Luan, Paris, Shechtman & Bala 2017 in the next `process`: per pyramid
+        level matting_weight times the quadratic form of the matting Laplacian of the content level on the level image,
+        which is zero where the image is, in every 3x3 window, an affine function of the content's colours
+        (nst_job_set_matting in include/nst_hip.h has the definition).  `matting_epsilon` > 0 regularises the windows whose
+        colours lie on a line or are constant.  None or 0: off.  ValueError for a malformed setting."""
+        self.__matting = _mat.normalize_matting(matting_weight, matting_epsilon)
+
     def set_gram_shift(self, gram_shift=None):
         """Extension: the Gram statistic of the style term in the next `process` - activation-shifted (Novak & Nikulin 2016:
         G = (F + s)^T (F + s), s = -1 in the paper) or mean-centred (the covariance; Li et al. 2017), per feature map of
@@ -406,6 +431,8 @@ class NeuralStyleTransfer:
             blend = (self.__blend[0], _style.check_style_blend(self.__blend[1], 1 + len(self.__blend[0]), style_indices=style_set))
         if self.__laplacian is not None and len(content_imgs):
             _lap.check_levels(self.__laplacian[0], len(content_imgs), *tuple(content_imgs[0].shape[:2]))
+        if self.__matting is not None and len(content_imgs):
+            _mat.check_levels(len(content_imgs), *tuple(content_imgs[0].shape[:2]))
         _gram.check_exclusive(self.__gram_shift, self.__regions)
         style_imgs = self.__style_imgs
         regions = None
@@ -442,6 +469,8 @@ class NeuralStyleTransfer:
             extra["regions"] = regions
         if self.__laplacian is not None:
             extra["laplacian"] = self.__laplacian
+        if self.__matting is not None:
+            extra["matting"] = self.__matting
         if self.__gram_shift is not None:
             extra["gram_shift"] = self.__gram_shift
         job = _make_job(self.__device, self.__optimizer_name, style_imgs, content_imgs, init_img, lr_start, **extra)
@@ -502,7 +531,8 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
                                 content_layer=None, style_layers=None, use_relu=True, preserve_color=None,
                                 pooling="max", extra_styles=None, style_blend=None, style_layer_weights=None,
                                 content_regions=None, style_regions=None, region_weights=None,
-                                laplacian_weight=None, laplacian_pool=_lap.DEFAULT_POOL, gram_shift=None):
+                                laplacian_weight=None, laplacian_pool=_lap.DEFAULT_POOL, gram_shift=None,
+                                matting_weight=None, matting_epsilon=_mat.DEFAULT_EPSILON):
     """Async generator yielding (percent, HWC float32 image) after every optimiser step
     (reference :229-372). `device` (extension): the GPU to run on; default = current.  `content_layer`,
     `style_layers`, `use_relu` (extension): the feature maps the losses read, see NeuralStyleTransfer.set_feature_maps
@@ -520,7 +550,9 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
     `laplacian_weight`, `laplacian_pool` (extension): the Laplacian loss, see NeuralStyleTransfer.set_laplacian (None, 0 or
     all-zero weights: off); validated before any GPU work too, a level too small for a pool size included.  `gram_shift`
     (extension): activation-shifted or mean-centred Gram matrices, see NeuralStyleTransfer.set_gram_shift (None or 0: the
-    plain Gram); validated before any GPU work too; not with `content_regions` / `style_regions`."""
+    plain Gram); validated before any GPU work too; not with `content_regions` / `style_regions`.  `matting_weight`,
+    `matting_epsilon` (extension): the photorealism regulariser of Luan et al. 2017, see NeuralStyleTransfer.set_matting
+    (None or 0: off); validated before any GPU work too."""
     taps = _taps.normalize_taps(content_layer, style_layers, use_relu)
     host_image.check_preserve_color(preserve_color)
     check_pooling(pooling)
@@ -536,6 +568,10 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
     if laplacian is not None:
         ih, iw = np.shape(content_n_style.content[1])[:2]
         _lap.check_levels(laplacian[0], max(levels_num, 1), *host_image.level_size(ih, iw, max(levels_num - 1, 0)))
+    matting = _mat.normalize_matting(matting_weight, matting_epsilon)
+    if matting is not None:
+        ih, iw = np.shape(content_n_style.content[1])[:2]
+        _mat.check_levels(max(levels_num, 1), *host_image.level_size(ih, iw, max(levels_num - 1, 0)))
     if regions is not None:
         for stack, img, what in ((regions[0], content_n_style.content[1], "content_regions"),
                                  (regions[1], content_n_style.style[1], "style_regions")):
@@ -583,6 +619,8 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
         nst.set_laplacian(laplacian[1], laplacian[0])
     if gram_setting is not None:
         nst.set_gram_shift(gram_shift)
+    if matting is not None:
+        nst.set_matting(*matting)
     lr_start = 10.0
     async for img, cur_iter in nst.process(content_levels, init_img, lr_start, iters_num, content_weight,
                                            style_weight, tv_weight, init_name):

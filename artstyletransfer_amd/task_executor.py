@@ -77,6 +77,10 @@ class Task:
         # the Gram statistic (a number, 'mean', a sequence or a dict: `is not None`)
         if getattr(cfg, "gram_shift", None) is not None:
             extensions["gram_shift"] = cfg.gram_shift
+        # the matting term: weight and epsilon together, when a weight is set
+        if getattr(cfg, "matting_weight", None) is not None:
+            extensions["matting_weight"] = cfg.matting_weight
+            extensions["matting_epsilon"] = getattr(cfg, "matting_epsilon", 1e-7)
         gpu = await self.__slots.acquire()
         self.gpu = gpu
         try:

@@ -242,6 +242,54 @@ int nst_job_set_laplacian(nst_ctx* ctx, int K, const int* pool, const float* gam
 int nst_job_laplacian(const nst_ctx* ctx, int* K, int pool[NST_MAX_LAPLACIAN], float gamma[NST_MAX_LAPLACIAN]);
 int nst_job_laplacian_losses(nst_ctx* ctx, float* out /* device, levels x NST_MAX_LAPLACIAN */, void* stream);
 
+/* Matting term: the photorealism regulariser of Luan, Paris, Shechtman & Bala ("Deep Photo Style Transfer", CVPR 2017), the
+ * quadratic form of Levin's matting Laplacian.  It penalises an output that is not, in every 3x3 window, an affine function
+ * of the content's colours.  A pixel-space term, a setting of the context.  The reference has no counterpart.
+ *
+ * Setting
+ * - A weight gamma, finite and >= 0 (0 = off), and epsilon, finite and > 0 (Luan's value is 1e-7).
+ * Term of a level image y, prepared, (3,h,w), with the guide I = (content_l + IMAGENET_MEAN_255) / 255
+ * - content_l is the level's content as given to nst_level_set_targets*; the context keeps a device copy per level, made
+ *   where the Laplacian targets are made.  Only differences inside a window enter, so the means cancel.
+ * - Windows: every 3x3 window k that lies fully inside the image, (h-2)(w-2) of them; n = 3 (h-2)(w-2).  Its nine pixels i:
+ *   mu_k = mean_i I_i, Ic_i = I_i - mu_k, M_k = (1/9) sum_i Ic_i Ic_i^T + (epsilon/9) Id_3.
+ * - Per output channel c, V = y_c / 255: Vc_i = V_i - mean_i V_i (the centred form: the ImageNet means cancel exactly),
+ *   v = sum_i Vc_i Ic_i, a = M_k^{-1} v / 9, E_kc = sum_i Vc_i^2 - v^T a
+ *   (= sum_i (Vc_i - a^T Ic_i)^2 + epsilon |a|^2 in exact arithmetic).
+ * - mat = (float)((1/n) sum_k sum_c E_kc) = (1/n) sum_c V_c^T L V_c with Levin's matrix L.
+ * - Per window the moments, v, the solve (an LDL^T factorisation of M_k; no inverse is stored) and E are formed in double
+ *   from the fp32 images; the sum is in double in a fixed two-stage order (tiles of 32 x 8 windows, then the tile partials).
+ *   M_k is singular up to epsilon/9 wherever the content's colours lie on a line or are constant.
+ * Loss row
+ * - With gamma > 0 the level total is (((cw content + sw style) + tvw tv) + lap) + gamma mat: added last, product and sum
+ *   each rounded (the lap term only when it is set).  NST_LOSS_ROW stays 4.  nst_job_matting_losses returns the mat.
+ * Gradient
+ * - d/dy_c(i) = coef sum_{k containing i} (Vc_i^(k) - a_kc^T Ic_i^(k)), coef = (float)((double)gamma 2 / (255 n)); the sum
+ *   over the (up to nine) windows in double in a fixed order, rounded once.  Border pixels lie in fewer windows.
+ * - It is accumulated into the level gradient after the total-variation and the Laplacian gradients.
+ * Luminance
+ * - Under NST_COLOR_LUMINANCE the term is that of the RGB closure at E(u) with a guide whose three channels all equal
+ *   content_u / 255, and the gradient with respect to u is the sum over the three channels.  That is the scalar form
+ *   b = sum_i Vc_i gc_i / (sum_i gc_i^2 + epsilon/3), E_k = sum_i Vc_i^2 - b sum_i Vc_i gc_i, mat = sum_k E_k / ((h-2)(w-2)),
+ *   which is what runs.
+ * No float atomics: a closure with the term is bitwise reproducible, as closure reuse and the lazy backward need.
+ *
+ * nst_job_set_matting: needs a configured job (NST_E_STATE otherwise).  NST_E_ARG, with nothing changed, for a non-finite
+ * or negative gamma or a non-finite or non-positive epsilon.  Life cycle of nst_job_set_laplacian: the call waits for the
+ * context's work, drops every level's targets (the guide is made with them) and any captured closure graph, and ends the
+ * validity of an optimiser's remembered closure and of a pending nst_closure_backward.  Every buffer of the term is
+ * allocated here, never in a closure.  nst_job_configure clears the setting.  With gamma = 0 a closure launches what it
+ * launches without the call and computes the same bits.  It composes with any taps, colour mode, pooling, style layer
+ * weights, blends, guidance, the Laplacian loss, the Gram shift, every conv mode and schedule (use_graph included), the
+ * closure halves and level sharding (rows and gradients add up).  The stripe closure (nst_window_*) returns NST_E_STATE
+ * while gamma > 0.
+ * nst_job_matting: the current setting (either pointer may be NULL).
+ * nst_job_matting_losses: the unweighted mat of the last closure per level, to out (DEVICE, levels floats); levels outside
+ * the last level mask are zeros.  Asynchronous on `stream`. */
+int nst_job_set_matting(nst_ctx* ctx, float gamma, double epsilon);
+int nst_job_matting(const nst_ctx* ctx, float* gamma, double* epsilon);
+int nst_job_matting_losses(nst_ctx* ctx, float* out /* device, levels */, void* stream);
+
 /* Gram shift: activation-shifted and mean-centred style statistics, a setting of the context.  The reference has no
  * counterpart: its statistic is the raw second moment G = F^T F / (C N) of the tapped maps.
  * - Activation shift (Novak & Nikulin, "Improving the Neural Algorithm of Artistic Style", 2016): G = (F + s)^T (F + s), s = -1
@@ -470,7 +518,7 @@ int nst_opt_history(const nst_opt* opt, int* pairs, int* n_iter);
  * reproducible, so when a step starts at bitwise the image the previous step left (a rejected or skipped trial, or an
  * accepted trial whose closure was the last one made), with the same weights and no change to the job in between
  * (nst_job_configure, nst_job_set_taps, nst_job_set_color, nst_job_set_pooling, nst_job_set_style_weights,
- * nst_job_set_laplacian, nst_job_set_gram_shift, nst_level_set_targets, nst_level_set_targets_blend), its first closure is served from what
+ * nst_job_set_laplacian, nst_job_set_matting, nst_job_set_gram_shift, nst_level_set_targets, nst_level_set_targets_blend), its first closure is served from what
  * the optimiser remembers instead of evaluated: same loss row, step counter, lr decay, step info and image.  One
  * device compare of x decides, so the caller may write x between steps.  Never in the sharded modes; Adam never.
  * Changing the setting drops what is remembered. */
@@ -582,6 +630,12 @@ int nst_total_variation(nst_ctx* ctx, const float* y, int C, int h, int w, float
  * d lap_k / dy, with gamma = 1.  Reads no job state.  Synchronous. */
 int nst_laplacian_loss(nst_ctx* ctx, const float* y, const float* content, int C, int h, int w, int p, float* value,
                        float* grad /* nullable, overwritten */, void* stream);
+/* The matting term on its own (nst_job_set_matting has the definition): y device (C,h,w), prepared; guide device (C,h,w), the
+ * guide I itself (in [0,1] for ordinary input); C = 3, or 1 with the luminance rule (y and guide one plane each); h, w >= 3.
+ * value (device scalar) = mat; grad (nullable, overwritten) (C,h,w) = d mat / dy, with gamma = 1.  The value is bitwise
+ * the same with and without grad.  Reads no job state.  Synchronous. */
+int nst_matting_loss(nst_ctx* ctx, const float* y, const float* guide, int C, int h, int w, double epsilon, float* value,
+                     float* grad /* nullable, overwritten */, void* stream);
 /* F.interpolate(x, size=(h//2,w//2), mode='bicubic') (neural_style_transfer.py:173-176) and its
  * transpose (autograd backward); x (C,h,w) -> y (C,h/2,w/2); gy -> gx (overwritten). */
 int nst_bicubic_half(nst_ctx* ctx, const float* x, int C, int h, int w, float* y, void* stream);
@@ -650,7 +704,8 @@ int nst_luminance_recombine(nst_ctx* ctx, const float* u, const float* content, 
  * only: after nst_job_set_taps with any other taps both calls return NST_E_STATE, as they do under NST_COLOR_LUMINANCE,
  * under NST_POOL_AVG (nst_job_set_pooling) and under style layer weights other than 1 (nst_job_set_style_weights).  The
  * Gram targets are the level's, so those of nst_level_set_targets_blend are honoured.  nst_window_* returns NST_E_STATE
- * while the Laplacian loss is set (nst_job_set_laplacian with K > 0) or a Gram shift (nst_job_set_gram_shift). */
+ * while the Laplacian loss is set (nst_job_set_laplacian with K > 0), the matting term (nst_job_set_matting with gamma > 0)
+ * or a Gram shift (nst_job_set_gram_shift). */
 int nst_window_sums_count(size_t* count);
 int nst_window_begin(nst_ctx* ctx, const float* xs, int row0, int rows, int H0, float* sums, void* stream);
 int nst_window_end(nst_ctx* ctx, const float* xs, int row0, int rows, int H0, float content_weight, float style_weight,
