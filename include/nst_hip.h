@@ -456,9 +456,15 @@ int nst_closure_levels(nst_ctx* ctx, const float* x, float content_weight, float
  *     writes.  x must still hold the image the forward half evaluated (the total-variation gradient reads it).
  * Validity: the backward half belongs to the LAST nst_closure_forward on the context and is valid only while that
  * forward is the last thing that used the context's workspaces - no nst_closure / nst_closure_levels, nst_window_*,
- * nst_level_activation, nst_level_set_targets or nst_job_* call in between, not even a failed one - and only with the
+ * nst_level_activation, nst_level_set_* or nst_job_configure / nst_job_set_* call in between, not even a failed one - and only with the
  * same x pointer, weights and level_mask, once.  Otherwise it returns NST_E_STATE, launches nothing and leaves `grad`
- * untouched; the context stays usable.  Both halves run on the batched schedule only (nst_options.batched, its default,
+ * untouched; the context stays usable (a refused backward half itself ends nothing: the forward half before it is still good).
+ * What does NOT end the validity: calls that write no level's buffers - the standalone pieces below, which work on caller
+ * buffers and scratch of their own (nst_vgg_*, nst_gram*, nst_guided_gram_backward, nst_total_variation, nst_laplacian_loss,
+ * nst_matting_loss, nst_bicubic_*, nst_resize_bicubic, nst_color_*, nst_luminance*, nst_adam_step, nst_lbfgs_direction), the
+ * getters (nst_job_color ... nst_job_gram_shift, nst_level_guidance, nst_job_map_stats), the copies nst_level_image,
+ * nst_job_laplacian_losses, nst_job_matting_losses, nst_level_gram_offsets and nst_level_guidance_planes, refused or not,
+ * and nst_set_timing.  Both halves run on the batched schedule only (nst_options.batched, its default,
  * without use_graph): elsewhere nst_closure_forward returns NST_E_UNAVAILABLE before it launches anything, and the
  * caller evaluates nst_closure_levels.  Asynchronous on `stream`.  Timing (nst_set_timing): a forward half is one
  * closure record; its backward half adds its launches and time to the totals without counting a second closure. */
