@@ -84,6 +84,10 @@ SYMBOLS = {
     "nst_job_gram_shift": (C.c_int, [c_void, c_float_p, C.POINTER(C.c_uint)]),
     "nst_level_gram_offsets": (C.c_int, [c_void, C.c_int, C.c_int, c_void, c_void]),
     "nst_gram_shifted": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, c_void, c_void, c_void]),
+    "nst_job_set_moments": (C.c_int, [c_void, c_float_p, c_float_p, C.c_float]),
+    "nst_job_moments": (C.c_int, [c_void, c_float_p, c_float_p, c_float_p]),
+    "nst_job_moment_losses": (C.c_int, [c_void, c_void, c_void]),
+    "nst_moments": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_float, c_void, c_void, c_void]),
     "nst_job_set_style_weights": (C.c_int, [c_void, c_float_p]),
     "nst_job_style_weights": (C.c_int, [c_void, c_float_p]),
     "nst_color_stats": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), c_void]),

@@ -6,6 +6,7 @@ from .regions import check_exclusive, check_regions
 from .laplacian_modes import DEFAULT_POOL, normalize_laplacian
 from .gram_modes import check_exclusive as check_gram_exclusive, normalize_gram_shift
 from .matting_modes import DEFAULT_EPSILON, normalize_matting
+from .moment_modes import DEFAULT_EPSILON as MOMENT_EPSILON, check_exclusive as check_moment_exclusive, normalize_moments
 
 # jobs that may run at once PER GPU (the reference runs everything on device 0; here the
 # scheduler multiplies this by the number of GPUs of the node). Use 1 when levels_num > 2.
@@ -31,7 +32,7 @@ _DEFAULTS = dict(
 # pooling of the feature network (pooling=); further style images with their blend (extra_styles=, style_blend=) and the
 # per-layer style weights (style_layer_weights=); spatial control (content_regions=, style_regions=, region_weights=); and
 # the Laplacian loss (laplacian_weight=, laplacian_pool=); the Gram statistic (gram_shift=); and the matting term
-# (matting_weight=, matting_epsilon=).
+# (matting_weight=, matting_epsilon=); and the moment loss (moment_weight=, moment_terms=, moment_epsilon=).
 # Not part of the positional order or the repr.
 _KW_ONLY = dict(
     content_layer=None,            # index 0..5 or a name of Vgg19.layer_names
@@ -50,6 +51,9 @@ _KW_ONLY = dict(
     gram_shift=None,               # None / 0 | number | 'mean' | 6 entries | {map index or name: number or 'mean'}: shifted / centred Gram matrices
     matting_weight=None,           # number >= 0: the gamma of the matting term (Luan et al. 2017: the photorealism regulariser); None / 0: off
     matting_epsilon=DEFAULT_EPSILON,   # number > 0: the epsilon of the matting Laplacian
+    moment_weight=None,            # None / 0 | number | 6 numbers | {map index or name: number}: the moment loss (Li et al. 2017; Huang & Belongie 2017)
+    moment_terms="both",           # 'both' | 'mean' | 'std': which of the channel means and deviations are matched
+    moment_epsilon=MOMENT_EPSILON, # number > 0: sigma = sqrt(var + epsilon)
 )
 
 
@@ -81,6 +85,10 @@ class Config:
         normalize_matting(self.matting_weight, self.matting_epsilon)
         check_gram_exclusive(normalize_gram_shift(self.gram_shift, self.use_relu if isinstance(self.use_relu, bool) else None),
                              regions=check_regions(self.content_regions, self.style_regions, self.region_weights))
+        # (against every map: the style set of the job is checked again where the taps are known)
+        check_moment_exclusive(normalize_moments(self.moment_weight, self.moment_terms, self.moment_epsilon, style_indices=range(6),
+                                                 use_relu=self.use_relu if isinstance(self.use_relu, bool) else None),
+                               regions=check_regions(self.content_regions, self.style_regions, self.region_weights))
 
     def __repr__(self):
         return "Config(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in _DEFAULTS) + ")"

@@ -114,6 +114,27 @@ int nst_gram_shifted(nst_ctx* ctx, const float* f, int C, int h, int w, int norm
     return sc.finish();
 }
 
+// the moment statistic alone (nst_job_set_moments has the definition), beside nst_gram_shifted: the closure's kernels
+int nst_moments(nst_ctx* ctx, const float* f, int C, int h, int w, float epsilon, float* mean_out, float* std_out, void* stream) {
+    NSTCHK(bind(ctx));
+    if (!f || !mean_out || !std_out || C < 1 || h < 1 || w < 1) return fail(ctx, NST_E_ARG, "bad argument");
+    if (!(epsilon > 0.f) || std::isinf(epsilon)) return fail(ctx, NST_E_ARG, "the moment epsilon must be finite and > 0");
+    if (!(C == 64 || C % 128 == 0) || C > 1024) return fail(ctx, NST_E_ARG, "the moment statistic takes C = 64 or a multiple of 128, at most 1024");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t N = (size_t)h * w;
+    Scratch sc(ctx, s);
+    float* nhwc = nullptr; double* part = nullptr; double* stat = nullptr;
+    NSTCHK(sc.alloc(&nhwc, N * C));
+    NSTCHK(sc.alloc(&part, (size_t)MOM_PART_DOUBLES));
+    NSTCHK(sc.alloc(&stat, (size_t)2 * C));
+    if (launch_chw_to_hwc(f, C, h, w, nhwc, s) != hipSuccess) return fail(ctx, NST_E_HIP, "chw_to_hwc launch failed");
+    MomentBatch mb{};
+    mb.n = 1;
+    mb.it[0] = MomentItem{nhwc, N, C, (double)epsilon, part, stat, mean_out, std_out, 1.f, 0, 0, 0, 0};
+    HIPCHK(ctx, launch_moment_stats(mb, s));
+    return sc.finish();
+}
+
 int nst_guided_gram_backward(nst_ctx* ctx, const float* f, size_t N, int C, int R, const float* planes, const float* S,
                              const float* addend, const unsigned* relu_bits, float* out, unsigned* amax_slots, void* stream) {
     NSTCHK(bind(ctx));

@@ -228,6 +228,18 @@ int mat_set_guide(nst_ctx* ctx, LevelWs& L, const float* content, hipStream_t s)
     return NST_OK;
 }
 
+// ---- the moment loss (include/nst_hip.h has the definition; kernels: moments.hip) ----------------------------------------
+// style slot q of level L on its map f (N pixels, C channels): the statistics item, and the fold item that follows the Gram
+// finish pass and the row bias of a shifted Gram (r0: that bias, or nullptr)
+MomentItem moment_item(const nst_ctx* ctx, const LevelWs& L, int q, const float* f, size_t N, int C) {
+    return MomentItem{f, N, C, (double)ctx->mom_eps, L.mom.part(q), L.mom.stat(q), nullptr, nullptr, 1.f, 0, 0, 0, 0};
+}
+MomentFoldItem moment_fold_item(const nst_ctx* ctx, const LevelWs& L, int q, size_t N, int C, unsigned short* S_bf, unsigned* S_amax) {
+    return MomentFoldItem{L.mom.stat(q), L.mom.mean_t(q), L.mom.std_t(q), L.S[q], S_bf, S_amax,
+                          ctx->gs_on() ? L.gs.row_bias(q) : nullptr, L.mom.row_bias(q), L.mom.loss(q), N, C,
+                          ctx->mom_wm_of(q), ctx->mom_ws_of(q)};
+}
+
 }  // namespace
 
 namespace nst {
@@ -620,10 +632,13 @@ int batched_gram(nst_ctx* ctx, const int* lv, int n, float sw, hipStream_t s, un
         // every (level, style layer) pair in two partial launches (one per tile shape) and one finish launch
         const int per = std::max(1, NST_GRAM_BATCH_MAX / ctx->taps.nstyle);      // levels per launch (3 with five style maps)
         const bool shifted = ctx->gs_on();
+        const bool moments = ctx->mom_on();
         for (int k0 = 0; k0 < n; k0 += per) {
             GramBatch gb{};
             OffsetBatch ob{};
             RowBiasBatch rb{};
+            MomentBatch mb{};
+            MomentFoldBatch mf{};
             double flops = 0;
             for (int k = k0; k < n && k < k0 + per; ++k) {
                 LevelWs& L = ctx->lv[lv[k]];
@@ -649,9 +664,18 @@ int batched_gram(nst_ctx* ctx, const int* lv, int n, float sw, hipStream_t s, un
                         rb.it[rb.n++] = RowBiasItem{L.gs.offset(q), L.S[q], L.gs.row_bias(q), it.C, 0};
                         it.offset = L.gs.offset(q); it.amax = L.gs.amax(q);
                     }
+                    if (moments && ctx->mom_slot(q)) {
+                        // channel sums of the map -> (after the Gram finish pass and r = o S) the fold into S and the row bias
+                        mb.it[mb.n++] = moment_item(ctx, L, q, it.f, it.N, it.C);
+                        mf.it[mf.n++] = moment_fold_item(ctx, L, q, it.N, it.C, it.S_bf, it.S_amax);
+                    }
                 }
             }
             if (gb.n == 0) continue;
+            if (mb.n > 0) {
+                Timer t(ctx, s, K_OTHER, 0);
+                HIPCHK(ctx, launch_moment_stats(mb, s));
+            }
             if (shifted) {
                 Timer t(ctx, s, K_OTHER, 0);
                 HIPCHK(ctx, launch_gram_offsets(ob, s));
@@ -663,6 +687,10 @@ int batched_gram(nst_ctx* ctx, const int* lv, int n, float sw, hipStream_t s, un
             if (shifted) {
                 Timer t(ctx, s, K_OTHER, 0);
                 HIPCHK(ctx, launch_gram_row_bias(rb, s));
+            }
+            if (mf.n > 0) {
+                Timer t(ctx, s, K_OTHER, 0);
+                HIPCHK(ctx, launch_moment_fold(mf, s));
             }
         }
     }
@@ -734,7 +762,7 @@ int batched_backward(nst_ctx* ctx, const float* const* xi, float* const* gi, con
             im.in2 = a.act[l]; im.wt2_f32 = L.S[top_q]; im.amax_in2 = amax_act(a, l); im.amax_w2 = amax_S(a, top_q);
             im.bits_in = tp.top_mask() ? a.bits[l] : nullptr; im.amax_out = amax_grad(a, l);
             im.addend = top_content ? oth[k] : nullptr;
-            if (ctx->gs_on()) im.bias = L.gs.row_bias(top_q);      // (a shifted Gram: F S + r, then the addend and the mask)
+            im.bias = ctx->row_bias_of(L, top_q);      // (a shifted Gram, the moment term: F S + r, then the addend and the mask)
             if (win) { im.in2_row0 = win_r0(*win, kScale[l]); im.in2_rows = win_nr(*win, kScale[l]); }
             flops += conv_flops(im.H, im.W, b.Cin2, b.Cout, 1);
         }
@@ -804,7 +832,7 @@ int batched_backward(nst_ctx* ctx, const float* const* xi, float* const* gi, con
             if (style_q >= 0) {
                 im.in2 = a.act[m]; im.wt2_bf = L.S_bf[style_q];
                 im.wt2_f32 = L.S[style_q]; im.amax_in2 = amax_act(a, m); im.amax_w2 = amax_S(a, style_q);
-                if (ctx->gs_on()) im.bias = L.gs.row_bias(style_q);
+                im.bias = ctx->row_bias_of(L, style_q);
                 if (win) { im.in2_row0 = win_r0(*win, kScale[m]); im.in2_rows = win_nr(*win, kScale[m]); }
                 flops += conv_flops(a.h[m], a.w[m], kCout[m], kCout[m], 1);
             }
@@ -964,11 +992,21 @@ int closure_per_level(nst_ctx* ctx, const float* const* xi, float* const* gi, in
             const ShiftedGram sg{ctx->gs_shift_of(k), ctx->gs_center_of(k), L.gs.offset(k), L.gs.amax(k), L.gs.part(k), L.gs.row_bias(k)};
             NSTCHK(gram_shifted_of(ctx, L.acts.act[l], st.N, st.C, h2 ? amax_act(L.acts, l) : nullptr, sg, (float)st.divisor, L.gram_part, L.gram_t[k],
                                    st.coef, nullptr, L.S[k], L.S_bf[k], h2 ? amax_S(L.acts, k) : nullptr, L.style_partial[k], s));
-            inj[l].bias = L.gs.row_bias(k);
         } else {
             NSTCHK(gram_of(ctx, L.acts.act[l], st.N, st.C, h2 ? amax_act(L.acts, l) : nullptr, (float)st.divisor, L.gram_part, L.gram_t[k], st.coef, nullptr, L.S[k],
                            L.S_bf[k], h2 ? amax_S(L.acts, k) : nullptr, L.style_partial[k], s));
         }
+        if (ctx->mom_on() && ctx->mom_slot(k)) {
+            MomentBatch mb{};
+            MomentFoldBatch mf{};
+            mb.n = mf.n = 1;
+            mb.it[0] = moment_item(ctx, L, k, L.acts.act[l], st.N, st.C);
+            mf.it[0] = moment_fold_item(ctx, L, k, st.N, st.C, L.S_bf[k], h2 ? amax_S(L.acts, k) : nullptr);
+            Timer t(ctx, s, K_OTHER, 0);
+            HIPCHK(ctx, launch_moment_stats(mb, s));
+            HIPCHK(ctx, launch_moment_fold(mf, s));
+        }
+        inj[l].bias = ctx->row_bias_of(L, k);
         inj[l].S = L.S[k];
         inj[l].S_bf = L.S_bf[k];
         inj[l].S_amax = h2 ? amax_S(L.acts, k) : nullptr;
@@ -1004,6 +1042,11 @@ LossAssembly fill_loss_assembly(const nst_ctx* ctx, unsigned level_mask, float c
         la.lv[i].mat_partial = L.mat.partial; la.lv[i].mat_tiles = L.mat.tiles; la.lv[i].mat_n = mat_n(ctx, L);
     }
     for (int k = 0; k < ctx->lap_k; ++k) la.lap_gamma[k] = ctx->lap_gamma[k];
+    la.mom_on = ctx->mom_on() ? 1 : 0; la.mom_out = ctx->mom_vals; la.mom_stride = MOM_STAT_STRIDE;
+    for (int k = 0; k < ctx->taps.nstyle && la.mom_on; ++k) {
+        la.mom_wm[k] = ctx->mom_wm_of(k); la.mom_ws[k] = ctx->mom_ws_of(k); la.mom_index[k] = tap_index_of(ctx->taps.style[k]);
+    }
+    for (int i = 0; i < ctx->levels && la.mom_on; ++i) la.lv[i].mom_loss = ctx->lv[i].mom.stats ? ctx->lv[i].mom.loss(0) : nullptr;
     return la;
 }
 
@@ -1170,6 +1213,8 @@ int window_check(nst_ctx* ctx, const float* xs, int row0, int rows, int H0) {
         return fail(ctx, NST_E_STATE, "the stripe closure implements no matting term (nst_job_set_matting(ctx, 0, epsilon) switches it off)");
     if (ctx->gs_on())
         return fail(ctx, NST_E_STATE, "the stripe closure implements the plain Gram statistic only (nst_job_set_gram_shift with zeros switches the shift off)");
+    if (ctx->mom_on())
+        return fail(ctx, NST_E_STATE, "the stripe closure implements no moment loss (nst_job_set_moments with zeros switches it off)");
     LevelWs& L = ctx->lv[0];
     if (L.guide.R > 0)
         return fail(ctx, NST_E_STATE, "the stripe closure implements no spatial control (nst_level_set_guidance(ctx, 0, 0, ...) clears it)");
@@ -1265,6 +1310,17 @@ int nst_level_set_targets_blend(nst_ctx* ctx, int level, const float* content, i
             if (!(bhat[k][q] > 0.f)) continue;
             const int l = tp.style[q];
             const StyleTerm st = style_term(tp, q, sc.acts, 0.f, 1.f);
+            if (ctx->mom_on() && ctx->mom_slot(q)) {
+                // the moment targets: this image's mu and sigma, b^-weighted into the slot's mu^t and sigma^t as G is into Gt
+                // (the level's own scratch: no closure runs while its targets are made)
+                MomentBatch mb{};
+                mb.n = 1;
+                mb.it[0] = moment_item(ctx, L, q, sc.acts.act[l], st.N, st.C);
+                mb.it[0].mean_out = L.mom.mean_t(q); mb.it[0].std_out = L.mom.std_t(q);
+                mb.it[0].alpha = bhat[k][q]; mb.it[0].accumulate = written[q] ? 1 : 0;
+                Timer t(ctx, s, K_OTHER, 0);
+                HIPCHK(ctx, launch_moment_stats(mb, s));
+            }
             if (ctx->gs_on()) {
                 ShiftedGram sg{ctx->gs_shift_of(q), ctx->gs_center_of(q), gsl.offset(0), gsl.amax(0), gsl.part(0), nullptr};
                 sg.alpha = bhat[k][q]; sg.accumulate = written[q] ? 1 : 0;
@@ -1311,6 +1367,7 @@ int nst_level_set_guidance(nst_ctx* ctx, int level, int R, const float* planes, 
     }
     if (ctx->conv_mode != 2) return fail(ctx, NST_E_STATE, "spatial control runs in the f16x2 arithmetic only (NST_CONV unset)");
     if (ctx->gs_on()) return fail(ctx, NST_E_STATE, "guided Gram matrices take the plain statistic only (nst_job_set_gram_shift with zeros switches the shift off)");
+    if (ctx->mom_on()) return fail(ctx, NST_E_STATE, "guided levels take no moment loss (nst_job_set_moments with zeros switches it off)");
     if (!planes) return fail(ctx, NST_E_ARG, "null argument");
     float lam[NST_MAX_REGIONS] = {1.f, 1.f, 1.f, 1.f};
     bool positive = lambda == nullptr;
@@ -1390,6 +1447,7 @@ int nst_level_set_targets_guided(nst_ctx* ctx, int level, const float* content, 
     LevelWs& L = ctx->lv[level];
     Guidance& g = L.guide;
     if (ctx->gs_on()) return fail(ctx, NST_E_STATE, "guided Gram matrices take the plain statistic only (nst_job_set_gram_shift with zeros switches the shift off)");
+    if (ctx->mom_on()) return fail(ctx, NST_E_STATE, "guided levels take no moment loss (nst_job_set_moments with zeros switches it off)");
     if (g.R < 1) return fail(ctx, NST_E_STATE, "the level has no guidance (nst_level_set_guidance first)");
     if (!content || !style || !style_planes) return fail(ctx, NST_E_ARG, "null argument");
     if (hs < 16 || ws < 16) return fail(ctx, NST_E_ARG, "style image must be at least 16x16");

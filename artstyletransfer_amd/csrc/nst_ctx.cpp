@@ -321,6 +321,7 @@ void free_level(nst_ctx* ctx, LevelWs& L) {
     free_laplacian(ctx, L);
     free_matting(ctx, L);
     free_gram_shift(ctx, L);
+    free_moments(ctx, L);
     free_acts(ctx, L.acts);
     dev_free(L.gbuf[0]); dev_free(L.gbuf[1]); dev_free(L.xl); dev_free(L.gxl);
     free_tap_buffers(ctx, L);
@@ -359,6 +360,12 @@ void free_gram_shift(nst_ctx* ctx, LevelWs& L) {
     dev_free(L.gs.words); dev_free(L.gs.sums);
     if (ctx->bytes >= L.gs.bytes) ctx->bytes -= L.gs.bytes;
     L.gs = GramShiftLevel();
+}
+
+void free_moments(nst_ctx* ctx, LevelWs& L) {
+    dev_free(L.mom.words); dev_free(L.mom.stats); dev_free(L.mom.sums);
+    if (ctx->bytes >= L.mom.bytes) ctx->bytes -= L.mom.bytes;
+    L.mom = MomentLevel();
 }
 
 // What a closure remembered is void once the job changes: the captured graph and the keys it was captured under, and
@@ -625,7 +632,7 @@ void nst_ctx_destroy(nst_ctx* ctx) {
     for (int i = 0; i < NST_MAX_LEVELS; ++i) free_level(ctx, ctx->lv[i]);
     if (ctx->tail) (void)hipEventDestroy(ctx->tail);
     for (int l = 0; l < NL; ++l) { dev_free(ctx->wf[l]); dev_free(ctx->wd[l]); dev_free(ctx->bias[l]); dev_free(ctx->wf_bf[l]); dev_free(ctx->wd_bf[l]); dev_free(ctx->wf_h2[l]); dev_free(ctx->wd_h2[l]); dev_free(ctx->wf_wino[l]); dev_free(ctx->wd_wino[l]); }
-    dev_free(ctx->w11k); dev_free(ctx->w11d); dev_free(ctx->color_scratch); dev_free(ctx->lap_vals); dev_free(ctx->mat_vals);
+    dev_free(ctx->w11k); dev_free(ctx->w11d); dev_free(ctx->color_scratch); dev_free(ctx->lap_vals); dev_free(ctx->mat_vals); dev_free(ctx->mom_vals);
     drop_closure_state(ctx, false);
     if (ctx->gstream) (void)hipStreamDestroy(ctx->gstream);
     if (ctx->side) (void)hipStreamDestroy(ctx->side);
@@ -661,6 +668,8 @@ int nst_job_configure(nst_ctx* ctx, int levels_num, int H0, int W0) {
     ctx->mat_gamma = 0.f; ctx->mat_eps = 1e-7;   // (the matting term likewise)
     for (float& v : ctx->gs_shift) v = 0.f;      // (the Gram shift likewise)
     ctx->gs_center = 0u;
+    for (int i = 0; i < 6; ++i) { ctx->mom_wm[i] = 0.f; ctx->mom_ws[i] = 0.f; }      // (the moment term likewise)
+    ctx->mom_eps = 1e-5f;
     int h = H0, w = W0;
     for (int i = 0; i < levels_num; ++i) {
         LevelWs& L = ctx->lv[i];
@@ -1009,6 +1018,88 @@ int nst_level_gram_offsets(nst_ctx* ctx, int level, int slot, float* out, void* 
     if (slot < 0 || slot >= ctx->taps.nstyle || !out) return fail(ctx, NST_E_ARG, "slot must be a style slot of the current taps and out not null");
     hipStream_t s = enter(ctx, stream);
     HIPCHK(ctx, hipMemcpyAsync(out, ctx->lv[level].gs.offset(slot), (size_t)kCout[ctx->taps.style[slot]] * sizeof(float), hipMemcpyDeviceToDevice, s));
+    mark(ctx, s);
+    return NST_OK;
+}
+
+// The moment loss (Li et al. 2017; Huang & Belongie 2017; include/nst_hip.h has the definition): per map the weights of its
+// mean and deviation terms, and epsilon.  The life cycle of nst_job_set_gram_shift: every level's targets go (mu^t and
+// sigma^t are made with them), and the captured closure.  Every buffer of the term is allocated here; a refusal changes
+// nothing.
+int nst_job_set_moments(nst_ctx* ctx, const float* mean_w, const float* std_w, float epsilon) {
+    if (ctx) { ++ctx->closure_epoch; ++ctx->ws_seq; }
+    NSTCHK(bind(ctx));
+    if (!mean_w || !std_w) return fail(ctx, NST_E_ARG, "null argument");
+    if (!(epsilon > 0.f) || std::isinf(epsilon)) return fail(ctx, NST_E_ARG, "the moment epsilon must be finite and > 0");
+    bool on = false;
+    for (int i = 0; i < 6; ++i) {
+        if (!(mean_w[i] >= 0.f) || std::isinf(mean_w[i]) || !(std_w[i] >= 0.f) || std::isinf(std_w[i]))
+            return fail(ctx, NST_E_ARG, "moment weights must be finite and >= 0");
+        on = on || mean_w[i] > 0.f || std_w[i] > 0.f;
+    }
+    MomentLevel fresh[NST_MAX_LEVELS];
+    if (on) {
+        if (ctx->levels < 1) return fail(ctx, NST_E_STATE, "nst_job_configure has not been called");
+        if (ctx->conv_mode != 2) return fail(ctx, NST_E_STATE, "the moment loss runs in the f16x2 arithmetic only (NST_CONV unset)");
+        for (int i = 0; i < ctx->levels; ++i)
+            if (ctx->lv[i].guide.R > 0)
+                return fail(ctx, NST_E_STATE, "guided levels take no moment loss (nst_level_set_guidance(ctx, level, 0, ...) clears the guidance)");
+        const unsigned taps_mask = style_mask_of(ctx->taps);
+        for (int i = 0; i < 6; ++i)
+            if ((mean_w[i] > 0.f || std_w[i] > 0.f) && !((taps_mask >> i) & 1u))
+                return fail(ctx, NST_E_ARG, "a moment weight is positive on map " + std::to_string(i) + ", which is not a style map of the job (nst_job_set_taps)");
+        int rc = NST_OK;
+        if (!ctx->mom_vals) rc = dev_alloc_t(ctx, &ctx->mom_vals, (size_t)NST_MAX_LEVELS * 12);
+        for (int i = 0; i < ctx->levels && rc == NST_OK; ++i) {
+            MomentLevel& q = fresh[i];
+            rc = dev_alloc_t(ctx, &q.words, (size_t)kMaxStyle * MOM_STRIDE);
+            if (rc == NST_OK) q.bytes += (size_t)kMaxStyle * MOM_STRIDE * sizeof(float);
+            if (rc == NST_OK) rc = dev_alloc_t(ctx, &q.stats, (size_t)kMaxStyle * MOM_STAT_STRIDE);
+            if (rc == NST_OK) q.bytes += (size_t)kMaxStyle * MOM_STAT_STRIDE * sizeof(double);
+            if (rc == NST_OK) rc = dev_alloc_t(ctx, &q.sums, (size_t)kMaxStyle * MOM_PART_DOUBLES);
+            if (rc == NST_OK) q.bytes += (size_t)kMaxStyle * MOM_PART_DOUBLES * sizeof(double);
+            if (rc == NST_OK && (hipMemset(q.words, 0, (size_t)kMaxStyle * MOM_STRIDE * sizeof(float)) != hipSuccess ||
+                                 hipMemset(q.stats, 0, (size_t)kMaxStyle * MOM_STAT_STRIDE * sizeof(double)) != hipSuccess))
+                rc = fail(ctx, NST_E_HIP, "hipMemset of the moment buffers failed");
+        }
+        if (rc != NST_OK) {
+            LevelWs tmp;
+            for (int i = 0; i < ctx->levels; ++i) { tmp.mom = fresh[i]; free_moments(ctx, tmp); }
+            return rc;
+        }
+    }
+    quiesce(ctx);
+    drop_closure_state(ctx, true);
+    for (int i = 0; i < ctx->levels; ++i) {
+        free_moments(ctx, ctx->lv[i]);
+        ctx->lv[i].mom = fresh[i];
+    }
+    for (int i = 0; i < 6; ++i) { ctx->mom_wm[i] = mean_w[i]; ctx->mom_ws[i] = std_w[i]; }
+    ctx->mom_eps = epsilon;
+    if (ctx->mom_vals) HIPCHK(ctx, hipMemset(ctx->mom_vals, 0, (size_t)NST_MAX_LEVELS * 12 * sizeof(float)));
+    return NST_OK;
+}
+
+int nst_job_moments(const nst_ctx* ctx, float* mean_w, float* std_w, float* epsilon) {
+    if (!ctx) return fail(nullptr, NST_E_ARG, "null context");
+    for (int i = 0; i < 6; ++i) {
+        if (mean_w) mean_w[i] = ctx->mom_wm[i];
+        if (std_w) std_w[i] = ctx->mom_ws[i];
+    }
+    if (epsilon) *epsilon = ctx->mom_eps;
+    return NST_OK;
+}
+
+// the unweighted (mean_i, std_i) of the last closure, levels x 6 x 2 by map index, as the loss rows left them (zeros: levels
+// outside the last level mask, maps without the term, no closure yet, term off)
+int nst_job_moment_losses(nst_ctx* ctx, float* out, void* stream) {
+    NSTCHK(bind(ctx));
+    if (ctx->levels < 1) return fail(ctx, NST_E_STATE, "nst_job_configure has not been called");
+    if (!out) return fail(ctx, NST_E_ARG, "null argument");
+    hipStream_t s = enter(ctx, stream);
+    const size_t bytes = (size_t)ctx->levels * 12 * sizeof(float);
+    if (ctx->mom_on() && ctx->mom_vals) HIPCHK(ctx, hipMemcpyAsync(out, ctx->mom_vals, bytes, hipMemcpyDeviceToDevice, s));
+    else HIPCHK(ctx, hipMemsetAsync(out, 0, bytes, s));
     mark(ctx, s);
     return NST_OK;
 }

@@ -160,12 +160,33 @@ struct GramShiftLevel {
     double* part(int q) const { return sums ? sums + (size_t)q * GS_PART_DOUBLES : nullptr; }
 };
 
+// The moment loss of one level (nst_job_set_moments; include/nst_hip.h has the definition): per style slot the targets mu^t
+// and sigma^t (made with the level's targets), the row bias of the slot's backward launch (a - b o mu, on top of a shifted
+// Gram's r = o S), mu and sigma of the last closure with its two values (doubles), and the scratch of the channel sums.
+// Sized for the widest map, so the taps may change under it.  Made by the setter, freed when the setting is cleared or the
+// job configured again: a closure allocates nothing.
+constexpr int MOM_STRIDE = 3 * GS_MAX_C;                      // words of one slot: mu^t | sigma^t | row bias
+constexpr int MOM_STAT_STRIDE = 2 * GS_MAX_C + 2;             // doubles of one slot: mu | sigma | mean_i, std_i
+struct MomentLevel {
+    float* words = nullptr;     // kMaxStyle x MOM_STRIDE
+    double* stats = nullptr;    // kMaxStyle x MOM_STAT_STRIDE
+    double* sums = nullptr;     // kMaxStyle x MOM_PART_DOUBLES
+    size_t bytes = 0;
+    float* mean_t(int q) const { return words + (size_t)q * MOM_STRIDE; }
+    float* std_t(int q) const { return words + (size_t)q * MOM_STRIDE + GS_MAX_C; }
+    float* row_bias(int q) const { return words + (size_t)q * MOM_STRIDE + 2 * GS_MAX_C; }
+    double* stat(int q) const { return stats + (size_t)q * MOM_STAT_STRIDE; }
+    double* loss(int q) const { return stats + (size_t)q * MOM_STAT_STRIDE + 2 * GS_MAX_C; }
+    double* part(int q) const { return sums + (size_t)q * MOM_PART_DOUBLES; }
+};
+
 struct LevelWs {
     int h = 0, w = 0;
     Guidance guide;
     LapLevel lap;
     MatLevel mat;
     GramShiftLevel gs;
+    MomentLevel mom;
     ActSet acts;
     float* gbuf[2] = {};
     size_t gbuf_floats = 0;
@@ -270,7 +291,27 @@ struct nst_ctx {
     }
     float gs_shift_of(int q) const { return gs_shift[nst::tap_index_of(taps.style[q])]; }                  // of style slot q
     int gs_center_of(int q) const { return (int)((gs_center >> nst::tap_index_of(taps.style[q])) & 1u); }
-    // bumped on entry to every call that changes what a closure computes (configure, taps, colour, pooling, style weights, Laplacian, matting, Gram shift, targets), failure paths
+    // nst_job_set_moments: per map index (as the style layer weights) the weights of mean_i and std_i, and epsilon; all zero =
+    // the term is off.  mom_vals: device, NST_MAX_LEVELS x 6 x 2 floats, the unweighted (mean_i, std_i) of the last closure by
+    // map index (written by the loss rows; made by the first setter call that switches the term on)
+    float mom_wm[6] = {};
+    float mom_ws[6] = {};
+    float mom_eps = 1e-5f;
+    float* mom_vals = nullptr;
+    bool mom_on() const {
+        for (int i = 0; i < 6; ++i) if (mom_wm[i] > 0.f || mom_ws[i] > 0.f) return true;
+        return false;
+    }
+    float mom_wm_of(int q) const { return mom_wm[nst::tap_index_of(taps.style[q])]; }                      // of style slot q
+    float mom_ws_of(int q) const { return mom_ws[nst::tap_index_of(taps.style[q])]; }
+    bool mom_slot(int q) const { return mom_wm_of(q) > 0.f || mom_ws_of(q) > 0.f; }                        // slot q carries the term
+    // the row bias of style slot q's backward launch at level L: the moment term's (which holds a shifted Gram's r too), else
+    // a shifted Gram's, else none
+    const float* row_bias_of(const nst::LevelWs& L, int q) const {
+        if (mom_on() && mom_slot(q)) return L.mom.row_bias(q);
+        return gs_on() ? L.gs.row_bias(q) : nullptr;
+    }
+    // bumped on entry to every call that changes what a closure computes (configure, taps, colour, pooling, style weights, Laplacian, matting, Gram shift, moments, targets), failure paths
     // included: an optimiser's remembered closure result is valid only under the epoch it was made in (nst_opt.cpp)
     unsigned long long closure_epoch = 0;
     // advanced on entry to every call that reads or writes the level workspaces (nst_closure*, nst_window_*,
@@ -365,6 +406,7 @@ void free_guidance(nst_ctx* ctx, LevelWs& L);      // the level is unguided afte
 void free_laplacian(nst_ctx* ctx, LevelWs& L);     // the level's Laplacian buffers (the setting itself is the context's)
 void free_matting(nst_ctx* ctx, LevelWs& L);       // the level's matting buffers (likewise)
 void free_gram_shift(nst_ctx* ctx, LevelWs& L);    // the level's shifted-Gram buffers (likewise)
+void free_moments(nst_ctx* ctx, LevelWs& L);       // the level's moment-loss buffers (likewise)
 hipStream_t enter(nst_ctx* ctx, void* stream);     // orders the caller's stream after the context's tail event
 void mark(nst_ctx* ctx, hipStream_t s);            // records the tail event
 void quiesce(nst_ctx* ctx);                        // waits until nothing on the device uses the context's memory
@@ -402,7 +444,7 @@ struct Inject {
     const unsigned* S_amax = nullptr; // absmax record of S (conv_h2), if available
     const float* direct = nullptr;   // or a ready NHWC gradient
     bool content = false;            // or the content MSE gradient (closure only)
-    const float* bias = nullptr;     // with S, a shifted Gram (nst_job_set_gram_shift): the row bias r = o S, dF = F * S + r
+    const float* bias = nullptr;     // with S, a shifted Gram (nst_job_set_gram_shift) and / or the moment term: the row bias, dF = F * S + r
     const GuidedBwd* guided = nullptr; // guided Gram backward (R, t, S filled in): dF = sum_r t_r^2 F S_r, by a launch of its own
 };
 struct ContentJob { const float* target; size_t n; float coef; double* partial; };

@@ -278,6 +278,7 @@ struct LevelLossInputs {
     const double* mat_partial;       // matting term: mat_tiles doubles, partial sums of E_kc
     int mat_tiles;
     double mat_n;                    // channels (h-2)(w-2)
+    const double* mom_loss;          // moment term: style slot k's (mean_i, std_i) as the fold left them, at k * mom_stride
 };
 struct LossAssembly {
     LevelLossInputs lv[8];
@@ -290,6 +291,11 @@ struct LossAssembly {
     float* lap_out;                  // levels x NST_LAP_MAX: the unweighted lap_k (zeros for levels not owned, unused entries)
     float mat_gamma;                 // matting term (nst_job_set_matting); 0: the row is what it is without the term
     float* mat_out;                  // levels: the unweighted mat (zeros for levels not owned)
+    int mom_on;                      // moment term (nst_job_set_moments); 0: the row is what it is without the term
+    float mom_wm[6], mom_ws[6];      // per style slot: the weights of mean_i and std_i (both 0: the slot has no term)
+    int mom_stride;                  // doubles between two slots' values in LevelLossInputs::mom_loss
+    int mom_index[6];                // per style slot: its map's index in Vgg19.layer_names
+    float* mom_out;                  // levels x 6 x 2: the unweighted (mean_i, std_i) by map index (zeros: not owned, unused maps)
 };
 hipError_t launch_loss_assemble(const LossAssembly& la, hipStream_t stream);
 
@@ -357,6 +363,40 @@ hipError_t launch_gram_offsets(const OffsetBatch& b, hipStream_t stream);
 struct RowBiasItem { const float* offset; const float* S; float* r; int C; int blk_end; };
 struct RowBiasBatch { RowBiasItem it[NST_GRAM_BATCH_MAX]; int n; };
 hipError_t launch_gram_row_bias(const RowBiasBatch& b, hipStream_t stream);
+
+// moments.hip: the moment loss - channel means and deviations of the style maps (include/nst_hip.h has the definition) ---
+// Per item mu_c = (1/N) sum_p F[p][c], var_c = (1/N) sum_p F[p][c]^2 - mu_c^2 clamped at 0, sigma_c = sqrt(var_c + epsilon):
+// the sums in double through two ordered stages (no atomics: bitwise reproducible), one launch pair for all items.
+// stat: 2 C doubles, mu then sigma.  mean_out / std_out (nullable, C floats): alpha * (float)mu and alpha * (float)sigma,
+// written (accumulate = 0) or added to what is there (product and sum each rounded) - the targets of a blend of styles.
+// C: 64 or a multiple of 128, at most 1024.
+constexpr int MOM_PART_DOUBLES = 128 * 1024;    // stage-one partial sums of one item: moment_blocks(C, N) x 2 C doubles at most
+struct MomentItem {
+    const float* f; size_t N; int C;
+    double epsilon;
+    double* part;             // MOM_PART_DOUBLES doubles of scratch
+    double* stat;             // out: 2 C doubles
+    float* mean_out; float* std_out;
+    float alpha; int accumulate;
+    int nblk; size_t pix_per_blk; int blk_end;     // filled by the launcher
+};
+struct MomentBatch { MomentItem it[NST_GRAM_BATCH_MAX]; int n; };
+int moment_blocks(int C, size_t N);
+hipError_t launch_moment_stats(const MomentBatch& b, hipStream_t stream);
+// The fold of the term into the Gram backward of its map, after the Gram finish pass and the row bias of a shifted Gram (which
+// must see S without the diagonal).  Per item, from stat and the targets: loss[0] = mean_i = (1/C) sum_c (mu_c - mu^t_c)^2,
+// loss[1] = std_i = (1/C) sum_c (sigma_c - sigma^t_c)^2; a_c = wm 2 (mu_c - mu^t_c) / (C N), b_c = ws 2 (sigma_c - sigma^t_c)
+// / (C N sigma_c); S[c][c] += b_c (S_bf, nullable, likewise re-cut); S_amax (nullable): word 0 raised to the new diagonal's
+// absmax; bias[c] = (bias0 ? bias0[c] : 0) + (a_c - b_c mu_c), with b_c as the rounded diagonal holds it.  bias0 may be bias.
+struct MomentFoldItem {
+    const double* stat; const float* mean_t; const float* std_t;
+    float* S; unsigned short* S_bf; unsigned* S_amax;
+    const float* bias0; float* bias;
+    double* loss;             // out: 2 doubles
+    size_t N; int C; float wm, ws;
+};
+struct MomentFoldBatch { MomentFoldItem it[NST_GRAM_BATCH_MAX]; int n; };
+hipError_t launch_moment_fold(const MomentFoldBatch& b, hipStream_t stream);
 
 // gram_guided.hip: spatial control (guided Gram matrices; include/nst_hip.h has the definitions) ---------------------
 constexpr int NST_MAX_REGIONS_K = 4;

@@ -650,6 +650,7 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(LossAssembly la) {
         if (threadIdx.x < 4) la.out[4 * l + threadIdx.x] = 0.f;
         if (la.nlap > 0 && threadIdx.x < NST_LAP_MAX) la.lap_out[NST_LAP_MAX * l + threadIdx.x] = 0.f;
         if (la.mat_gamma > 0.f && threadIdx.x == 0) la.mat_out[l] = 0.f;
+        if (la.mom_on && threadIdx.x < 12) la.mom_out[12 * l + threadIdx.x] = 0.f;
         return;
     }
     double v[7];
@@ -731,6 +732,23 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(LossAssembly la) {
             const float mat = (float)(rm / in.mat_n);
             la.mat_out[l] = mat;
             total = total + la.mat_gamma * mat;
+        }
+        if (la.mom_on) {
+            // (... + mat) + mom, mom = sum over the style slots with a weight, in slot order, of (wm * mean_i + ws * std_i):
+            // every product and sum rounded; the values themselves are the fold's doubles rounded to fp32
+            for (int i = 0; i < 12; ++i) la.mom_out[12 * l + i] = 0.f;
+            float mom = 0.f;
+            bool first = true;
+            for (int k = 0; k < la.nstyle; ++k) {
+                if (!(la.mom_wm[k] > 0.f) && !(la.mom_ws[k] > 0.f)) continue;
+                const float mean = (float)in.mom_loss[(size_t)k * la.mom_stride], sd = (float)in.mom_loss[(size_t)k * la.mom_stride + 1];
+                la.mom_out[12 * l + 2 * la.mom_index[k]] = mean;
+                la.mom_out[12 * l + 2 * la.mom_index[k] + 1] = sd;
+                const float term = la.mom_wm[k] * mean + la.mom_ws[k] * sd;
+                mom = first ? term : mom + term;
+                first = false;
+            }
+            total = total + mom;
         }
         la.out[4 * l + 0] = total;
         la.out[4 * l + 1] = content;

@@ -14,6 +14,7 @@ from .pooling_modes import check_pooling
 from . import style_modes as _style
 from . import regions as _regions
 from . import gram_modes as _gram
+from . import moment_modes as _mom
 from . import laplacian_modes as _lap
 from . import matting_modes as _mat
 from ._lib import NST_LOSS_ROW, NstError, StepInfo
@@ -100,6 +101,7 @@ class StyleEngine:
         self.laplacian = None                    # (pools, weights) under set_laplacian
         self.matting = None                      # (gamma, epsilon) under set_matting
         self.gram_shift = None                   # (shift[6], center_mask) under set_gram_shift
+        self.moment_loss = None                  # (mean_w[6], std_w[6], epsilon) under set_moments
 
     def close(self):
         if getattr(self, "ctx", None):
@@ -119,7 +121,8 @@ class StyleEngine:
         self.shape = (H0, W0)
         self.laplacian = None                    # (nst_job_configure clears the Laplacian setting)
         self.matting = None                      # (the matting term)
-        self.gram_shift = None                   # (and the Gram shift)
+        self.gram_shift = None                   # (the Gram shift)
+        self.moment_loss = None                  # (and the moment loss)
 
     def set_taps(self, content_index, style_indices, use_relu: bool = True) -> None:
         """The feature maps the losses read (nst_job_set_taps): a content index and style indices of Vgg19.layer_names
@@ -332,6 +335,54 @@ class StyleEngine:
         out = torch.empty((c,), dtype=torch.float32, device=self.device)
         _lib.check(self.ctx, self.lib.nst_level_gram_offsets(self.ctx, level, slot, _ptr(out), _stream(self.device)),
                    "nst_level_gram_offsets")
+        return out
+
+    def set_moments(self, mean_w, std_w=None, epsilon=_mom.DEFAULT_EPSILON) -> None:
+        """The moment loss of the job (nst_job_set_moments; Li et al. 2017, Huang & Belongie 2017): the level total gains
+        sum_i (mean_w[i] mean_i + std_w[i] std_i), the mean squared differences of the channel means and of the channel
+        deviations sigma = sqrt(var + epsilon) of style map i from the style's.  `mean_w`, `std_w`: each None or 0, a number
+        (that weight on every style map of the current taps), six numbers by map index of Vgg19.layer_names, or a dict
+        {map index or name: number}.  All zeros: off.  Needs a configured job, the f16x2 arithmetic and no guided level;
+        drops the targets of every level: call set_targets again.  ValueError (before the context is touched) for a
+        malformed setting or a positive weight on a map that is not a style map of the current taps."""
+        setting = _mom.check_setting(mean_w, std_w, epsilon, style_indices=getattr(self, "taps", DEFAULT_TAPS)[1])
+        if setting is None:
+            self.reset_moments()
+            return
+        if not self.levels:
+            raise NstError("set_moments needs a configured job (configure first)")
+        wm = (C.c_float * _mom.NUM_MAPS)(*setting[0])
+        ws = (C.c_float * _mom.NUM_MAPS)(*setting[1])
+        try:
+            _lib.check(self.ctx, self.lib.nst_job_set_moments(self.ctx, wm, ws, setting[2]), "nst_job_set_moments")
+        finally:                                 # the context's setting, whether the call succeeded or not
+            self.moment_loss = self.moments_setting()
+
+    def moments_setting(self):
+        """The context's moment loss as (mean_w[6], std_w[6], epsilon), or None when it is off (nst_job_moments)."""
+        wm = (C.c_float * _mom.NUM_MAPS)()
+        ws = (C.c_float * _mom.NUM_MAPS)()
+        eps = C.c_float()
+        _lib.check(self.ctx, self.lib.nst_job_moments(self.ctx, wm, ws, C.byref(eps)), "nst_job_moments")
+        mean_w, std_w = tuple(float(v) for v in wm), tuple(float(v) for v in ws)
+        if all(v == 0.0 for v in mean_w + std_w):
+            return None
+        return mean_w, std_w, float(eps.value)
+
+    def reset_moments(self) -> None:
+        """The moment loss off, if it was set (drops the targets then, as set_moments does)."""
+        if self.moment_loss is not None:
+            zeros = (C.c_float * _mom.NUM_MAPS)()
+            try:
+                _lib.check(self.ctx, self.lib.nst_job_set_moments(self.ctx, zeros, zeros, self.moment_loss[2]), "nst_job_set_moments")
+            finally:
+                self.moment_loss = self.moments_setting()
+
+    def moment_losses(self) -> torch.Tensor:
+        """(levels, 6, 2) device tensor: the unweighted (mean_i, std_i) of the last closure per level and map index
+        (nst_job_moment_losses); zeros for maps without the term, levels outside the last level mask and while it is off."""
+        out = torch.empty((self.levels, _mom.NUM_MAPS, 2), dtype=torch.float32, device=self.device)
+        _lib.check(self.ctx, self.lib.nst_job_moment_losses(self.ctx, _ptr(out), _stream(self.device)), "nst_job_moment_losses")
         return out
 
     def release_job(self) -> None:
@@ -696,6 +747,18 @@ class StyleEngine:
                                                _stream(self.device)), "nst_gram")
         return g
 
+    def moments(self, f: torch.Tensor, epsilon: float = _mom.DEFAULT_EPSILON):
+        """The moment statistic alone (nst_moments): (mu (C,), sigma (C,)) of the (1,C,h,w) map f, sigma = sqrt(var + epsilon),
+        the sums in double by the closure's kernels.  C = 64 or a multiple of 128, at most 1024."""
+        eps = _mom.check_epsilon(epsilon)
+        f = f.contiguous()
+        _chk_dev(f, self.device)
+        c, h, w = f.shape[-3], f.shape[-2], f.shape[-1]
+        mu = torch.empty((c,), dtype=torch.float32, device=self.device)
+        sd = torch.empty((c,), dtype=torch.float32, device=self.device)
+        _lib.check(self.ctx, self.lib.nst_moments(self.ctx, _ptr(f), c, h, w, eps, _ptr(mu), _ptr(sd), _stream(self.device)), "nst_moments")
+        return mu, sd
+
     def gram_shifted(self, f: torch.Tensor, shift: float = 0.0, center: bool = False, normalize: bool = True):
         """The shifted / centred statistic alone (nst_gram_shifted): (G (1,C,C), o (C,)) of the (1,C,h,w) map f, o = shift
         on every channel or (center) minus the map's channel means."""
@@ -1014,6 +1077,7 @@ class PixelOptimizer:
         if getattr(e, "matting", None) is not None:
             raise ValueError("matting_weight cannot be combined with stripe sharding (reset_matting())")
         _gram.check_exclusive(getattr(e, "gram_shift", None), stripes=True)
+        _mom.check_exclusive(getattr(e, "moment_loss", None), stripes=True)
         contents = list(content_t) if isinstance(content_t, (list, tuple)) else [content_t]
         styles = list(style_t) if isinstance(style_t, (list, tuple)) else [style_t]
         if blend is not None and styles and isinstance(styles[0], torch.Tensor):

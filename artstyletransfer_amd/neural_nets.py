@@ -115,7 +115,7 @@ def lease_engine(device) -> StyleEngine:
 
 
 def return_engine(eng: StyleEngine) -> None:
-    """Back to the per-GPU pool, with unit style layer weights, the default taps, RGB, max pooling, no Laplacian term and the plain Gram statistic: the
+    """Back to the per-GPU pool, with unit style layer weights, the default taps, RGB, max pooling, no Laplacian, matting or moment term and the plain Gram statistic: the
     next job must not inherit this one's."""
     if getattr(eng, "ctx", None) is None:
         return
@@ -134,6 +134,7 @@ def return_engine(eng: StyleEngine) -> None:
             eng.reset_laplacian()              # (already off: release_job configured the context anew)
             eng.reset_gram_shift()             # (likewise)
             eng.reset_matting()                # (likewise)
+            eng.reset_moments()                # (likewise)
         except Exception:
             keep = False
     if keep:

@@ -26,6 +26,7 @@ from . import regions as _regions
 from . import gram_modes as _gram
 from . import laplacian_modes as _lap
 from . import matting_modes as _mat
+from . import moment_modes as _mom
 
 # ImageNet statistics (reference :22-23)
 IMAGENET_MEAN_255 = [123.675, 116.28, 103.53]
@@ -145,6 +146,22 @@ class LossBuilder:
             self.__engine.set_gram_shift(*setting)
         self.__engine.set_targets(0, *self.__targets)       # (the setting drops them: the Gram targets are made with the statistic)
 
+    def set_moments(self, moment_weight=None, moment_terms="both", moment_epsilon=_mom.DEFAULT_EPSILON):
+        """Extension: the moment loss (Li et al. 2017; Huang & Belongie 2017) as one more term of `build` - the level total
+        gains sum_i w_i (mean_i + std_i), the mean squared differences of the channel means and deviations of style map i
+        from the style's (see nst_job_set_moments in include/nst_hip.h).  `moment_weight`: None or 0 (off), a number (on
+        every style map of this builder), six numbers, or a dict {map index or name: number}; `moment_terms`: "both", "mean"
+        or "std".  ValueError for a malformed setting or a positive weight on a map that is not a style map."""
+        setting = _mom.normalize_moments(moment_weight, moment_terms, moment_epsilon, style_indices=self.__engine.taps[1],
+                                         use_relu=self.__engine.taps[2])
+        if setting is None and self.__engine.moment_loss is None:
+            return
+        if setting is None:
+            self.__engine.reset_moments()
+        else:
+            self.__engine.set_moments(*setting)
+        self.__engine.set_targets(0, *self.__targets)       # (the setting drops them: the moment targets are made with them)
+
     def __del__(self):
         try:
             return_engine(self.__engine)
@@ -165,7 +182,7 @@ class _DeviceJob:
     (`_make_job`, tests/test_host_api.py)."""
 
     def __init__(self, device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, taps=None, color=None,
-                 pooling=None, style_weights=None, blend=None, regions=None, laplacian=None, gram_shift=None, matting=None):
+                 pooling=None, style_weights=None, blend=None, regions=None, laplacian=None, gram_shift=None, matting=None, moments=None):
         self.dev = dev = device
         self.optimizer = None
         self.luminance = color == "luminance"   # the optimised image is u = 255 Y; the yield puts the content's I, Q back
@@ -206,6 +223,8 @@ class _DeviceJob:
                     engine.set_matting(*matting)
                 if gram_shift is not None:         # (shift[6], center_mask) of the Gram statistic, normalised
                     engine.set_gram_shift(*gram_shift)
+                if moments is not None:            # (mean_w[6], std_w[6], epsilon) of the moment loss, normalised
+                    engine.set_moments(*moments)
                 # blend = (per-level image lists of the extra styles, K x 6 matrix): style 0 is style_imgs
                 all_styles = [style_imgs] + (list(blend[0]) if blend is not None else [])
                 if self.luminance:
@@ -281,9 +300,9 @@ class _DeviceJob:
 
 
 def _make_job(device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, taps=None, color=None, pooling=None,
-              style_weights=None, blend=None, regions=None, laplacian=None, gram_shift=None, matting=None):
+              style_weights=None, blend=None, regions=None, laplacian=None, gram_shift=None, matting=None, moments=None):
     return _DeviceJob(device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, taps, color, pooling,
-                      style_weights, blend, regions, laplacian, gram_shift, matting)
+                      style_weights, blend, regions, laplacian, gram_shift, matting, moments)
 
 
 async def _drain(step_future):
@@ -323,6 +342,7 @@ class NeuralStyleTransfer:
         self.__laplacian = None                  # set_laplacian: (pools, weights)
         self.__matting = None                    # set_matting: (gamma, epsilon)
         self.__gram_shift = None               # set_gram_shift: (shift[6], center_mask)
+        self.__moments = None                    # set_moments: (moment_weight, moment_terms, moment_epsilon) as given
 
     def set_feature_maps(self, content_layer=None, style_layers=None, use_relu=True):
         """Extension: the feature maps the losses of the next `process` read - a content map and a set of style maps of
@@ -411,6 +431,18 @@ class NeuralStyleTransfer:
         `process` - together with regions."""
         self.__gram_shift = _gram.normalize_gram_shift(gram_shift)
 
+    def set_moments(self, moment_weight=None, moment_terms="both", moment_epsilon=_mom.DEFAULT_EPSILON):
+        """Extension: the moment loss in the next `process` - the "BN statistics matching" of Li et al. 2017 and the style
+        loss of Huang & Belongie 2017: per pyramid level sum_i w_i (mean_i + std_i), the mean squared differences of the
+        channel means and of the channel deviations sqrt(var + epsilon) of style map i from the style's
+        (nst_job_set_moments in include/nst_hip.h has the definition).  `moment_weight`: None or 0 (off), a number (that
+        weight on every style map of the job), six numbers by map index of Vgg19.layer_names, or a dict {map index or name:
+        number} (the rest 0); `moment_terms`: "both", "mean" or "std"; `moment_epsilon` > 0.  ValueError for a malformed
+        setting and - in `process`, where the style set is known - for a positive weight on a map that is not a style map,
+        or together with regions."""
+        off = _mom.normalize_moments(moment_weight, moment_terms, moment_epsilon, style_indices=range(_mom.NUM_MAPS)) is None
+        self.__moments = None if off else (moment_weight, moment_terms, moment_epsilon)
+
     async def process(self, content_imgs, init_img, lr_start, iters_num, content_weight, style_weight, tv_weight,
                       init_img_name):
         # validates the model name exactly as the reference does (ValueError for anything but vgg19)
@@ -434,6 +466,11 @@ class NeuralStyleTransfer:
         if self.__matting is not None and len(content_imgs):
             _mat.check_levels(len(content_imgs), *tuple(content_imgs[0].shape[:2]))
         _gram.check_exclusive(self.__gram_shift, self.__regions)
+        moments = None
+        if self.__moments is not None:
+            moments = _mom.normalize_moments(*self.__moments, style_indices=style_set,
+                                             use_relu=self.__taps[2] if self.__taps is not None else True)
+            _mom.check_exclusive(moments, self.__regions)
         style_imgs = self.__style_imgs
         regions = None
         if self.__regions is not None:
@@ -473,6 +510,8 @@ class NeuralStyleTransfer:
             extra["matting"] = self.__matting
         if self.__gram_shift is not None:
             extra["gram_shift"] = self.__gram_shift
+        if moments is not None:
+            extra["moments"] = moments
         job = _make_job(self.__device, self.__optimizer_name, style_imgs, content_imgs, init_img, lr_start, **extra)
         cw, sw, tvw = float(content_weight), float(style_weight), float(tv_weight)
         loop = asyncio.get_running_loop()
@@ -532,7 +571,8 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
                                 pooling="max", extra_styles=None, style_blend=None, style_layer_weights=None,
                                 content_regions=None, style_regions=None, region_weights=None,
                                 laplacian_weight=None, laplacian_pool=_lap.DEFAULT_POOL, gram_shift=None,
-                                matting_weight=None, matting_epsilon=_mat.DEFAULT_EPSILON):
+                                matting_weight=None, matting_epsilon=_mat.DEFAULT_EPSILON,
+                                moment_weight=None, moment_terms="both", moment_epsilon=_mom.DEFAULT_EPSILON):
     """Async generator yielding (percent, HWC float32 image) after every optimiser step
     (reference :229-372). `device` (extension): the GPU to run on; default = current.  `content_layer`,
     `style_layers`, `use_relu` (extension): the feature maps the losses read, see NeuralStyleTransfer.set_feature_maps
@@ -552,7 +592,10 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
     (extension): activation-shifted or mean-centred Gram matrices, see NeuralStyleTransfer.set_gram_shift (None or 0: the
     plain Gram); validated before any GPU work too; not with `content_regions` / `style_regions`.  `matting_weight`,
     `matting_epsilon` (extension): the photorealism regulariser of Luan et al. 2017, see NeuralStyleTransfer.set_matting
-    (None or 0: off); validated before any GPU work too."""
+    (None or 0: off); validated before any GPU work too.  `moment_weight`, `moment_terms`, `moment_epsilon` (extension): the
+    moment loss - channel means and deviations of the style maps matched to the style's - see
+    NeuralStyleTransfer.set_moments (None or 0: off); validated before any GPU work too; not with `content_regions` /
+    `style_regions`."""
     taps = _taps.normalize_taps(content_layer, style_layers, use_relu)
     host_image.check_preserve_color(preserve_color)
     check_pooling(pooling)
@@ -564,6 +607,8 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
     _regions.check_exclusive(regions, extra_styles)
     gram_setting = _gram.normalize_gram_shift(gram_shift, use_relu)
     _gram.check_exclusive(gram_setting, regions)
+    moment_setting = _mom.normalize_moments(moment_weight, moment_terms, moment_epsilon, style_indices=taps[1], use_relu=use_relu)
+    _mom.check_exclusive(moment_setting, regions)
     laplacian = _lap.normalize_laplacian(laplacian_weight, laplacian_pool)
     if laplacian is not None:
         ih, iw = np.shape(content_n_style.content[1])[:2]
@@ -621,6 +666,8 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
         nst.set_gram_shift(gram_shift)
     if matting is not None:
         nst.set_matting(*matting)
+    if moment_setting is not None:
+        nst.set_moments(moment_weight, moment_terms, moment_epsilon)
     lr_start = 10.0
     async for img, cur_iter in nst.process(content_levels, init_img, lr_start, iters_num, content_weight,
                                            style_weight, tv_weight, init_name):

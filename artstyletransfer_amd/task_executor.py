@@ -81,6 +81,11 @@ class Task:
         if getattr(cfg, "matting_weight", None) is not None:
             extensions["matting_weight"] = cfg.matting_weight
             extensions["matting_epsilon"] = getattr(cfg, "matting_epsilon", 1e-7)
+        # the moment loss: weight, terms and epsilon together, when a weight is set
+        if getattr(cfg, "moment_weight", None) is not None:
+            extensions["moment_weight"] = cfg.moment_weight
+            extensions["moment_terms"] = getattr(cfg, "moment_terms", "both")
+            extensions["moment_epsilon"] = getattr(cfg, "moment_epsilon", 1e-5)
         gpu = await self.__slots.acquire()
         self.gpu = gpu
         try:

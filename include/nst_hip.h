@@ -340,6 +340,60 @@ int nst_level_gram_offsets(nst_ctx* ctx, int level, int slot, float* out, void* 
 int nst_gram_shifted(nst_ctx* ctx, const float* f, int C, int h, int w, int normalize, int center, float shift, float* gram,
                      float* offset_out /* nullable, C floats */, void* stream);
 
+/* Moment loss: the channel means and standard deviations of the style maps matched to the style's, a setting of the
+ * context.  The reference has no counterpart.  It is the "BN statistics matching" of Li, Wang, Liu & Hou, "Demystifying
+ * Neural Style Transfer" (2017), and the style loss of Huang & Belongie, "Arbitrary Style Transfer in Real-time with
+ * Adaptive Instance Normalization" (2017): sum_i |mu(F_i) - mu(F_i^style)|^2 + |sigma(F_i) - sigma(F_i^style)|^2.  Beside a
+ * centred Gram (nst_job_set_gram_shift) it restores the first moment that centring removes from the statistic.
+ *
+ * Setting
+ * - Each of the six maps of Vgg19.layer_names has two weights, by map index as the style layer weights: wm_i of its mean
+ *   term and ws_i of its deviation term, finite and >= 0; and one epsilon > 0 (default 1e-5) for all maps.
+ * Statistic of map i, C channels and N pixels, the sums in double in a fixed two-stage order
+ * - mu_c = (1/N) sum_p F[p][c]
+ * - var_c = (1/N) sum_p F[p][c]^2 - mu_c^2, clamped at 0 (one pass: in double the cancellation error is about 1e-13 E[F^2],
+ *   against epsilon = 1e-5)
+ * - sigma_c = sqrt(var_c + epsilon)
+ * - mean_i = (1/C) sum_c (mu_c - mu^t_c)^2,  std_i = (1/C) sum_c (sigma_c - sigma^t_c)^2, in double, rounded to fp32 once
+ * - The targets mu^t, sigma^t are the same statistics of the style level's map, rounded to fp32, taken when the targets are
+ *   set.  Under nst_level_set_targets_blend they are the weighted mean of each style's moments with the b^ of the map's
+ *   Gram target, accumulated in fp32 in ascending k as the Gram targets are.
+ * Loss row
+ * - The level total gains mom = sum_i (wm_i mean_i + ws_i std_i) over the style maps with a positive weight, in ascending
+ *   map order, every product and sum rounded: ((((cw content + sw style) + tvw tv) + lap) + gamma mat) + mom, the lap and
+ *   mat terms only when they are set.  The weights are the term's own: sw does not scale it.  NST_LOSS_ROW stays 4 and
+ *   entries 1..3 keep their meaning.  nst_job_moment_losses returns the unweighted values.
+ * Gradient
+ * - dF[p][c] = b_c F[p][c] + (a_c - b_c mu_c) with a_c = wm_i 2 (mu_c - mu^t_c) / (C N) and
+ *   b_c = ws_i 2 (sigma_c - sigma^t_c) / (C N sigma_c).  A channel with var_c = 0 has sigma_c = sqrt(epsilon) and a finite b_c.
+ * - The launches that carry the Gram backward F S + r take it as S += diag(b), r += a - b o mu, after the Gram finish pass
+ *   and after r = o S of a shifted Gram (which sees S without the diagonal).  b_c enters the bias as the rounded diagonal
+ *   holds it (new entry minus old entry), so F S + r is a_c + b_c (F - mu_c) with one b_c.  The absmax record of S is raised
+ *   to the diagonal.  A map whose style layer weight is 0 has S = diag(b).
+ * No float atomics: a closure with the term is bitwise reproducible, as closure reuse and the lazy backward need.
+ *
+ * nst_job_set_moments: all-zero weights switch the term off: the job then launches what it launches without the call and
+ * computes the same bits.  NST_E_ARG, with nothing changed, for a negative or non-finite weight, a non-finite or
+ * non-positive epsilon, or a positive weight on a map that is not a style map of the job's taps.  A setting with a positive
+ * weight needs a configured job, the f16x2 arithmetic and no guided level (NST_E_STATE otherwise).  Life cycle of
+ * nst_job_set_gram_shift: the call waits for the context's work, drops every level's targets (mu^t and sigma^t are made with
+ * them) and any captured closure graph, and ends the validity of an optimiser's remembered closure and of a pending
+ * nst_closure_backward.  Every buffer of the term is allocated here, never in a closure.  nst_job_configure clears the
+ * setting.  The work belongs to the forward half of the closure.  It composes with any taps (pre-ReLU included; a weight
+ * on a map that later taps leave out is ignored), colour mode, pooling, style layer weights, blends, the Laplacian loss,
+ * the matting term, the Gram shift, both schedules, the closure halves, closure reuse, the lazy backward and level
+ * sharding.  While a weight is positive, nst_level_set_guidance (R > 0), nst_level_set_targets_guided and nst_window_*
+ * return NST_E_STATE.
+ * nst_job_moments: the current setting (any pointer may be NULL).
+ * nst_job_moment_losses: the unweighted (mean_i, std_i) of the last closure, to out (DEVICE, levels x 6 x 2 floats, by map
+ * index); zeros for maps without the term and for levels outside the last level mask.  Asynchronous on `stream`.
+ * nst_moments: the statistic alone, beside nst_gram_shifted, by the closure's kernels: f device (C,h,w), C = 64 or a
+ * multiple of 128 up to 1024; mean_out, std_out: device, C floats each.  Any arithmetic mode.  Synchronous on `stream`. */
+int nst_job_set_moments(nst_ctx* ctx, const float mean_w[6], const float std_w[6], float epsilon);
+int nst_job_moments(const nst_ctx* ctx, float mean_w[6], float std_w[6], float* epsilon);
+int nst_job_moment_losses(nst_ctx* ctx, float* out /* device, levels x 6 x 2 */, void* stream);
+int nst_moments(nst_ctx* ctx, const float* f, int C, int h, int w, float epsilon, float* mean_out, float* std_out, void* stream);
+
 /* LossBuilder.__init__ (neural_style_transfer.py:68-82): target content representation
  * ReLU(conv4_2) of the content image and the 5 target Gram matrices of the style image of one
  * level (of the maps nst_job_set_taps chose, when it was called).  content: device (3,h,w) of that level's size; style: device (3,hs,ws), any size.
@@ -460,10 +514,11 @@ int nst_closure_levels(nst_ctx* ctx, const float* x, float content_weight, float
  * same x pointer, weights and level_mask, once.  Otherwise it returns NST_E_STATE, launches nothing and leaves `grad`
  * untouched; the context stays usable (a refused backward half itself ends nothing: the forward half before it is still good).
  * What does NOT end the validity: calls that write no level's buffers - the standalone pieces below, which work on caller
- * buffers and scratch of their own (nst_vgg_*, nst_gram*, nst_guided_gram_backward, nst_total_variation, nst_laplacian_loss,
+ * buffers and scratch of their own (nst_vgg_*, nst_gram*, nst_moments, nst_guided_gram_backward, nst_total_variation, nst_laplacian_loss,
  * nst_matting_loss, nst_bicubic_*, nst_resize_bicubic, nst_color_*, nst_luminance*, nst_adam_step, nst_lbfgs_direction), the
- * getters (nst_job_color ... nst_job_gram_shift, nst_level_guidance, nst_job_map_stats), the copies nst_level_image,
- * nst_job_laplacian_losses, nst_job_matting_losses, nst_level_gram_offsets and nst_level_guidance_planes, refused or not,
+ * getters (nst_job_color ... nst_job_moments, nst_level_guidance, nst_job_map_stats), the copies nst_level_image,
+ * nst_job_laplacian_losses, nst_job_matting_losses, nst_job_moment_losses, nst_level_gram_offsets and
+ * nst_level_guidance_planes, refused or not,
  * and nst_set_timing.  Both halves run on the batched schedule only (nst_options.batched, its default,
  * without use_graph): elsewhere nst_closure_forward returns NST_E_UNAVAILABLE before it launches anything, and the
  * caller evaluates nst_closure_levels.  Asynchronous on `stream`.  Timing (nst_set_timing): a forward half is one
@@ -524,7 +579,7 @@ int nst_opt_history(const nst_opt* opt, int* pairs, int* n_iter);
  * reproducible, so when a step starts at bitwise the image the previous step left (a rejected or skipped trial, or an
  * accepted trial whose closure was the last one made), with the same weights and no change to the job in between
  * (nst_job_configure, nst_job_set_taps, nst_job_set_color, nst_job_set_pooling, nst_job_set_style_weights,
- * nst_job_set_laplacian, nst_job_set_matting, nst_job_set_gram_shift, nst_level_set_targets, nst_level_set_targets_blend), its first closure is served from what
+ * nst_job_set_laplacian, nst_job_set_matting, nst_job_set_gram_shift, nst_job_set_moments, nst_level_set_targets, nst_level_set_targets_blend), its first closure is served from what
  * the optimiser remembers instead of evaluated: same loss row, step counter, lr decay, step info and image.  One
  * device compare of x decides, so the caller may write x between steps.  Never in the sharded modes; Adam never.
  * Changing the setting drops what is remembered. */
@@ -710,8 +765,8 @@ int nst_luminance_recombine(nst_ctx* ctx, const float* u, const float* content, 
  * only: after nst_job_set_taps with any other taps both calls return NST_E_STATE, as they do under NST_COLOR_LUMINANCE,
  * under NST_POOL_AVG (nst_job_set_pooling) and under style layer weights other than 1 (nst_job_set_style_weights).  The
  * Gram targets are the level's, so those of nst_level_set_targets_blend are honoured.  nst_window_* returns NST_E_STATE
- * while the Laplacian loss is set (nst_job_set_laplacian with K > 0), the matting term (nst_job_set_matting with gamma > 0)
- * or a Gram shift (nst_job_set_gram_shift). */
+ * while the Laplacian loss is set (nst_job_set_laplacian with K > 0), the matting term (nst_job_set_matting with gamma > 0),
+ * a Gram shift (nst_job_set_gram_shift) or the moment loss (nst_job_set_moments with a positive weight). */
 int nst_window_sums_count(size_t* count);
 int nst_window_begin(nst_ctx* ctx, const float* xs, int row0, int rows, int H0, float* sums, void* stream);
 int nst_window_end(nst_ctx* ctx, const float* xs, int row0, int rows, int H0, float content_weight, float style_weight,
