@@ -572,7 +572,9 @@ int nst_opt_shard_levels(nst_opt* opt, unsigned level_mask, float* grad, float* 
  * in level order, so L-BFGS' accept test takes the same branch as the unsharded run.  comm == NULL switches sharding off. */
 int nst_opt_shard_levels_comm(nst_opt* opt, unsigned level_mask, nst_comm* comm);
 
-/* curvature pairs currently held by L-BFGS and the optimiser's iteration count (Adam: its step count k) */
+/* curvature pairs currently held by L-BFGS and the optimiser's iteration count (Adam: its step count k).  The pair count
+ * rises to 100 and stays there: the oldest pair leaves when a new one is kept (tests/test_hip_lbfgs_history.py holds a run
+ * through a full history, 23 evictions and a dropped pair). */
 int nst_opt_history(const nst_opt* opt, int* pairs, int* n_iter);
 
 /* L-BFGS closure reuse (default on; env NST_CLOSURE_REUSE=0 at nst_opt_create turns it off).  The closure is bitwise
