@@ -134,6 +134,8 @@ SYMBOLS = {
     "nst_ctx_keep_all_maps": (C.c_int, [c_void]),
     "nst_ctx_set_forward_pack": (C.c_int, [c_void, C.c_int]),
     "nst_ctx_forward_pack": (C.c_int, [c_void]),
+    "nst_ctx_set_gram_pack": (C.c_int, [c_void, C.c_int]),
+    "nst_ctx_gram_pack": (C.c_int, [c_void]),
     "nst_level_image": (C.c_int, [c_void, C.c_int, c_void, c_void]),
     "nst_gram": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, c_void, c_void]),
     "nst_guided_gram_backward": (C.c_int, [c_void, c_void, C.c_size_t, C.c_int, C.c_int, c_void, c_void, c_void, c_void, c_void,

@@ -8,6 +8,8 @@
 // the diagonal are computed; the finish kernel mirrors them.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "nst_kernels.h"
 
 namespace nst {
@@ -174,6 +176,61 @@ struct GramH2Cfg {
     static constexpr int LDS_BYTES = 2 * BUF_BYTES;            // 72 KiB: two workgroups per CU
 };
 
+// PACK (nst_ctx_set_gram_pack, the default): a DIAGONAL tile computes only the 32x32 blocks with block column >= block row.
+// The finish pass reads elements with j >= i only and writes each result to (i,j) and (j,i), so the blocks strictly below the
+// diagonal of a diagonal tile were computed for nothing; with PACK they are neither computed NOR WRITTEN - that part of a
+// slab holds whatever the buffer held before.  Every reader of a slab goes through gram_finish_body's `tri` path, which
+// never loads a 16-byte group that lies in such a block (its four elements share a row and a 32-wide block).
+//   TS = 128: the 10 kept blocks (rb, cb) are dealt 3 / 2 / 2 / 3 to the waves (wm, wn) = (0,0) (1,0) (0,1) (1,1): the two
+//     waves on the diagonal keep (r,r) (r,r+1) (r+1,r+1) of their 64x64 quarter, wave (0,1) keeps rows 0-31 x columns 64-127
+//     of its quarter and hands rows 32-63 x columns 64-127 to wave (1,0), whose own quarter lies below the diagonal.
+//   TS = 64: every wave drops block (1,0) of its pixel slice.
+// A kept block sees the MFMAs it saw before, in the same order (whichever wave issues them), so its bits are the parent's.
+// Slot s of a wave -> (row block, column block); gram_diag_partition_ok is the host-side proof that this is a partition.
+constexpr int gram_diag_nblk(int ts, int wave) { return (ts == 64 || (wave & 1) == (wave >> 1)) ? 3 : 2; }
+constexpr int gram_diag_rb(int ts, int wave, int s) {
+    if (ts == 64) return s == 2 ? 1 : 0;
+    const int wm = wave & 1, wn = wave >> 1;
+    return (wm == wn) ? 2 * wm + (s == 2 ? 1 : 0) : wm;
+}
+constexpr int gram_diag_cb(int ts, int wave, int s) {
+    if (ts == 64) return s == 0 ? 0 : 1;
+    const int wm = wave & 1, wn = wave >> 1;
+    return (wm == wn) ? 2 * wm + (s == 0 ? 0 : 1) : 2 + s;
+}
+// TS = 128: the four waves together cover every block with cb >= rb exactly once and no other; TS = 64: each wave does
+// (its waves hold disjoint pixel slices of the same 64x64 tile)
+constexpr bool gram_diag_partition_ok(int ts) {
+    const int nb = ts / 32;
+    for (int w0 = 0; w0 < 4; w0 += (ts == 64 ? 1 : 4)) {
+        int seen[4][4] = {};
+        for (int wave = w0; wave < (ts == 64 ? w0 + 1 : 4); ++wave)
+            for (int s = 0; s < gram_diag_nblk(ts, wave); ++s) {
+                const int rb = gram_diag_rb(ts, wave, s), cb = gram_diag_cb(ts, wave, s);
+                if (rb < 0 || rb >= nb || cb < rb || cb >= nb) return false;
+                ++seen[rb][cb];
+            }
+        for (int rb = 0; rb < nb; ++rb)
+            for (int cb = 0; cb < nb; ++cb)
+                if (seen[rb][cb] != (cb >= rb ? 1 : 0)) return false;
+    }
+    return true;
+}
+static_assert(gram_diag_partition_ok(128) && gram_diag_partition_ok(64), "diagonal tile: the waves' blocks are not the upper triangle, each once");
+static_assert(gram_diag_nblk(128, 0) == 3 && gram_diag_nblk(128, 1) == 2 && gram_diag_nblk(128, 2) == 2 && gram_diag_nblk(128, 3) == 3,
+              "diagonal tile: 3 / 2 / 2 / 3 blocks per wave");
+
+// What a wave multiplies per k-step: NF fragment row blocks (hi and lo piece each) and NS accumulator pairs, slot s = fragment
+// fa(s) x fragment fb(s).  FULL: the parent's 2x2 blocks of a 64x64 quarter; TRI3 / TRI2: the waves of a diagonal tile above.
+enum { GRAM_FULL = 0, GRAM_TRI3 = 1, GRAM_TRI2 = 2 };
+template <int MODE>
+struct GramSlots {
+    static constexpr int NF = (MODE == GRAM_FULL) ? 4 : (MODE == GRAM_TRI3 ? 2 : 3);
+    static constexpr int NS = (MODE == GRAM_FULL) ? 4 : (MODE == GRAM_TRI3 ? 3 : 2);
+    static constexpr int fa(int s) { return (MODE == GRAM_FULL) ? (s >> 1) : (MODE == GRAM_TRI3 ? (s == 2 ? 1 : 0) : 0); }
+    static constexpr int fb(int s) { return (MODE == GRAM_FULL) ? 2 + (s & 1) : (MODE == GRAM_TRI3 ? (s == 0 ? 0 : 1) : 1 + s); }
+};
+
 // GUIDED: the guided Gram sum_p t(p)^2 F(p) F(p)^T - every pixel row is multiplied by t(p) = guide[p] as it is staged.
 // t is in [0,1], so the map's recorded absmax still bounds the operand.  t is read through a buffer descriptor of this
 // split's pixels, as the map is: the pixels of a ragged last group beyond p1 read t = 0 (and F = 0).
@@ -181,14 +238,15 @@ struct GramH2Cfg {
 // value.  A unit's channel is fixed, so that is one scalar per unit, read once.  `amax` is then the record of the SHIFTED
 // operand (launch_gram_offsets writes it): the map's own does not bound F + o.  A pixel beyond p1 reads F = 0 through the
 // range check and must contribute 0, not o: the staged value of such a pixel is forced to zero.
-template <int TS, bool GUIDED = false, bool SHIFT = false>
+template <int TS, bool GUIDED = false, bool SHIFT = false, bool PACK = false>
 __device__ __forceinline__ void gram_h2_body(const float* __restrict__ f, size_t N, int C, int nsplit, size_t pix_per_split,
                                              const unsigned* __restrict__ amax, float* __restrict__ part, const int bid,
                                              const float* __restrict__ guide = nullptr, const float* __restrict__ offs = nullptr) {
     using G = GramH2Cfg<TS>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_h2[];
     const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
+    const int lane = tid & 63;
+    const int wave = PACK ? __builtin_amdgcn_readfirstlane(tid >> 6) : (tid >> 6);      // (PACK: a scalar, the block choice branches on it)
     const int half = lane >> 5, l31 = lane & 31;
 
     const int split = bid % nsplit;
@@ -294,18 +352,10 @@ __device__ __forceinline__ void gram_h2_body(const float* __restrict__ f, size_t
 
     const int wm = (TS == 128) ? (wave & 1) : 0;
     const int wn = (TS == 128) ? (wave >> 1) : 0;
-    const int arow = (TS == 128) ? wm * 64 : wave * 64;
-    const int brow = (TS == 128) ? (diag ? 0 : 128) + wn * 64 : wave * 64;
-    const int a_off = (arow + l31) * G::ROWB + half * 16;
-    const int b_off = (brow + l31) * G::ROWB + half * 16;
-
-    f32x16 accm[2][2], accx[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { accm[a][b][r] = 0.f; accx[a][b][r] = 0.f; }
+    const float inv2 = inv * inv;
+    float* slab = part + (size_t)split * C * C;
+    // a diagonal tile under PACK computes its upper triangle of blocks (a 64-wide tile is always diagonal: C == 64)
+    const bool tri = PACK && (TS == 64 || diag);
 
     if (nchunks > 0) {
         load(0);
@@ -313,117 +363,170 @@ __device__ __forceinline__ void gram_h2_body(const float* __restrict__ f, size_t
         if (nchunks > 1) load(1);
     }
     __syncthreads();
-    for (int c = 0; c < nchunks; ++c) {
-        const int cb = c & 1;
-        if (c + 1 < nchunks) {
-            store(cb ^ 1);              // the other buffer was last read in chunk c-1, which every wave has left
-            if (c + 2 < nchunks) load(c + 2);
-        }
-        const unsigned char* base = smem_h2 + cb * G::BUF_BYTES;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            f16x8 fa[2][2], fb[2][2];
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int pc = 0; pc < 2; ++pc) {
-                    fa[t][pc] = *reinterpret_cast<const f16x8*>(base + a_off + t * 32 * G::ROWB + pc * 64 + ks * 32);
-                    fb[t][pc] = *reinterpret_cast<const f16x8*>(base + b_off + t * 32 * G::ROWB + pc * 64 + ks * 32);
-                }
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                for (int nt = 0; nt < 2; ++nt) {
-                    accx[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[mt][1], fb[nt][0], accx[mt][nt], 0, 0, 0);
-                    accm[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[mt][0], fb[nt][0], accm[mt][nt], 0, 0, 0);
-                    accx[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[mt][0], fb[nt][1], accx[mt][nt], 0, 0, 0);
-                }
-        }
-        __syncthreads();
-    }
 
-    const float inv2 = inv * inv;
-    float* slab = part + (size_t)split * C * C;
-    if (TS == 128) {
+    // The chunk loop and the slab write of one block choice.  Per accumulator pair the order is the parent's: chunk by chunk,
+    // k-step 0 then 1, and inside a k-step cross (lo x hi), main (hi x hi), cross (hi x lo).
+    auto run = [&](auto mode_tag) {
+        constexpr int MODE = decltype(mode_tag)::value;
+        using SL = GramSlots<MODE>;
+        // slot -> its 32x32 block of the tile
+        int rb[SL::NS], cb[SL::NS];
 #pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int m = (r & 3) + 8 * (r >> 2) + 4 * half;
-                    const int row = ti * TS + wm * 64 + mt * 32 + m;
-                    const int col = tj * TS + wn * 64 + nt * 32 + l31;
-                    slab[(size_t)row * C + col] = fmaf(accx[mt][nt][r], 1.f / 2048.f, accm[mt][nt][r]) * inv2;
-                }
-    } else {
-        // the four waves hold partial sums over disjoint pixel slices: combine through LDS in wave order
-        float* red = reinterpret_cast<float*>(smem_h2);
-        float* mine = red + wave * 4096;
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int m = (r & 3) + 8 * (r >> 2) + 4 * half;
-                    mine[(mt * 32 + m) * 64 + nt * 32 + l31] = fmaf(accx[mt][nt][r], 1.f / 2048.f, accm[mt][nt][r]);
-                }
-        __syncthreads();
-        for (int e = tid; e < 4096; e += 256) {
-            const float sum = ((red[e] + red[4096 + e]) + red[8192 + e]) + red[12288 + e];
-            const int row = ti * TS + (e >> 6), col = tj * TS + (e & 63);
-            slab[(size_t)row * C + col] = sum * inv2;
+        for (int sl = 0; sl < SL::NS; ++sl) {
+            rb[sl] = (MODE == GRAM_FULL) ? 2 * wm + (sl >> 1) : gram_diag_rb(TS, wave, sl);
+            cb[sl] = (MODE == GRAM_FULL) ? 2 * wn + (sl & 1) : gram_diag_cb(TS, wave, sl);
         }
-    }
+        // fragment -> LDS row of its block (TS = 128: side A rows 0..127, side B rows 128..255 - or side A again in a diagonal
+        // tile; TS = 64: the wave's pixel slice)
+        int foff[SL::NF];
+#pragma unroll
+        for (int sl = 0; sl < SL::NS; ++sl) {
+            const int ra = (TS == 128) ? rb[sl] * 32 : wave * 64 + rb[sl] * 32;
+            const int rbb = (TS == 128) ? (diag ? 0 : 128) + cb[sl] * 32 : wave * 64 + cb[sl] * 32;
+            foff[SL::fa(sl)] = (ra + l31) * G::ROWB + half * 16;
+            foff[SL::fb(sl)] = (rbb + l31) * G::ROWB + half * 16;
+        }
+
+        f32x16 accm[SL::NS], accx[SL::NS];
+#pragma unroll
+        for (int sl = 0; sl < SL::NS; ++sl)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { accm[sl][r] = 0.f; accx[sl][r] = 0.f; }
+
+        for (int c = 0; c < nchunks; ++c) {
+            const int cbuf = c & 1;
+            if (c + 1 < nchunks) {
+                store(cbuf ^ 1);              // the other buffer was last read in chunk c-1, which every wave has left
+                if (c + 2 < nchunks) load(c + 2);
+            }
+            const unsigned char* base = smem_h2 + cbuf * G::BUF_BYTES;
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                f16x8 fr[SL::NF][2];          // [fragment][piece: hi, lo] - a wave reads only what it multiplies
+#pragma unroll
+                for (int i = 0; i < SL::NF; ++i)
+#pragma unroll
+                    for (int pc = 0; pc < 2; ++pc)
+                        fr[i][pc] = *reinterpret_cast<const f16x8*>(base + foff[i] + pc * 64 + ks * 32);
+#pragma unroll
+                for (int sl = 0; sl < SL::NS; ++sl) {
+                    accx[sl] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fr[SL::fa(sl)][1], fr[SL::fb(sl)][0], accx[sl], 0, 0, 0);
+                    accm[sl] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fr[SL::fa(sl)][0], fr[SL::fb(sl)][0], accm[sl], 0, 0, 0);
+                    accx[sl] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fr[SL::fa(sl)][0], fr[SL::fb(sl)][1], accx[sl], 0, 0, 0);
+                }
+            }
+            __syncthreads();
+        }
+
+        if (TS == 128) {
+#pragma unroll
+            for (int sl = 0; sl < SL::NS; ++sl)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int m = (r & 3) + 8 * (r >> 2) + 4 * half;
+                    const int row = ti * TS + rb[sl] * 32 + m;
+                    const int col = tj * TS + cb[sl] * 32 + l31;
+                    slab[(size_t)row * C + col] = fmaf(accx[sl][r], 1.f / 2048.f, accm[sl][r]) * inv2;
+                }
+        } else {
+            // the four waves hold partial sums over disjoint pixel slices: combine through LDS in wave order
+            float* red = reinterpret_cast<float*>(smem_h2);
+            float* mine = red + wave * 4096;
+#pragma unroll
+            for (int sl = 0; sl < SL::NS; ++sl)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int m = (r & 3) + 8 * (r >> 2) + 4 * half;
+                    mine[(rb[sl] * 32 + m) * 64 + cb[sl] * 32 + l31] = fmaf(accx[sl][r], 1.f / 2048.f, accm[sl][r]);
+                }
+            __syncthreads();
+            for (int e = tid; e < 4096; e += 256) {
+                // (block (1,0) of a triangle was neither computed nor staged: it is not summed and not written)
+                if (MODE != GRAM_FULL && (e >> 6) >= 32 && (e & 63) < 32) continue;
+                const float sum = ((red[e] + red[4096 + e]) + red[8192 + e]) + red[12288 + e];
+                const int row = ti * TS + (e >> 6), col = tj * TS + (e & 63);
+                slab[(size_t)row * C + col] = sum * inv2;
+            }
+        }
+    };
+    // (workgroup-uniform in `tri`, wave-uniform in the block count: every wave passes the same barriers, one per chunk)
+    if (!tri) run(std::integral_constant<int, GRAM_FULL>{});
+    else if (gram_diag_nblk(TS, wave) == 3) run(std::integral_constant<int, GRAM_TRI3>{});
+    else if (TS == 128) run(std::integral_constant<int, GRAM_TRI2>{});
 }
 
-template <int TS>
+// PACK = false is the parent's kernel (nst_ctx_set_gram_pack(ctx, 0)), in every form below
+template <int TS, bool PACK = false>
 __global__ __launch_bounds__(256, 2) void gram_h2_kernel(const float* __restrict__ f, size_t N, int C, int nsplit,
                                                          size_t pix_per_split, const unsigned* __restrict__ amax,
                                                          float* __restrict__ part) {
-    gram_h2_body<TS>(f, N, C, nsplit, pix_per_split, amax, part, blockIdx.x);
+    gram_h2_body<TS, false, false, PACK>(f, N, C, nsplit, pix_per_split, amax, part, blockIdx.x);
 }
 // several maps (the style taps of every pyramid level of a closure) in one launch: their workgroups are numbered
 // item by item, so the short ones fill the tail of the long ones
-template <int TS>
+template <int TS, bool PACK = false>
 __global__ __launch_bounds__(256, 2) void gram_h2_batch_kernel(GramBatch b) {
     int i = 0;
     while (i + 1 < b.n && (int)blockIdx.x >= b.it[i].part_end) ++i;
     const GramItem& it = b.it[i];
-    gram_h2_body<TS>(it.f, it.N, it.C, it.nsplit, it.pix_per_split, it.amax, it.part,
-                     (int)blockIdx.x - (i ? b.it[i - 1].part_end : 0));
+    gram_h2_body<TS, false, false, PACK>(it.f, it.N, it.C, it.nsplit, it.pix_per_split, it.amax, it.part,
+                                         (int)blockIdx.x - (i ? b.it[i - 1].part_end : 0));
 }
 // the guided forms (gram_guided.hip has the rest of spatial control): the same bodies with the staged rows scaled by t(p)
-template <int TS>
+template <int TS, bool PACK = false>
 __global__ __launch_bounds__(256, 2) void gram_h2_guided_kernel(const float* __restrict__ f, size_t N, int C, int nsplit,
                                                                 size_t pix_per_split, const unsigned* __restrict__ amax,
                                                                 float* __restrict__ part, const float* __restrict__ guide) {
-    gram_h2_body<TS, true>(f, N, C, nsplit, pix_per_split, amax, part, blockIdx.x, guide);
+    gram_h2_body<TS, true, false, PACK>(f, N, C, nsplit, pix_per_split, amax, part, blockIdx.x, guide);
 }
-template <int TS>
+template <int TS, bool PACK = false>
 __global__ __launch_bounds__(256, 2) void gram_h2_guided_batch_kernel(GramBatch b) {
     int i = 0;
     while (i + 1 < b.n && (int)blockIdx.x >= b.it[i].part_end) ++i;
     const GramItem& it = b.it[i];
-    gram_h2_body<TS, true>(it.f, it.N, it.C, it.nsplit, it.pix_per_split, it.amax, it.part,
-                           (int)blockIdx.x - (i ? b.it[i - 1].part_end : 0), it.guide);
+    gram_h2_body<TS, true, false, PACK>(it.f, it.N, it.C, it.nsplit, it.pix_per_split, it.amax, it.part,
+                                        (int)blockIdx.x - (i ? b.it[i - 1].part_end : 0), it.guide);
 }
 
 // the shifted forms (gram_shift.hip has the rest of the shifted / centred statistic)
-template <int TS>
+template <int TS, bool PACK = false>
 __global__ __launch_bounds__(256, 2) void gram_h2_shift_kernel(const float* __restrict__ f, size_t N, int C, int nsplit,
                                                                size_t pix_per_split, const unsigned* __restrict__ amax,
                                                                float* __restrict__ part, const float* __restrict__ offs) {
-    gram_h2_body<TS, false, true>(f, N, C, nsplit, pix_per_split, amax, part, blockIdx.x, nullptr, offs);
+    gram_h2_body<TS, false, true, PACK>(f, N, C, nsplit, pix_per_split, amax, part, blockIdx.x, nullptr, offs);
 }
-template <int TS>
+template <int TS, bool PACK = false>
 __global__ __launch_bounds__(256, 2) void gram_h2_shift_batch_kernel(GramBatch b) {
     int i = 0;
     while (i + 1 < b.n && (int)blockIdx.x >= b.it[i].part_end) ++i;
     const GramItem& it = b.it[i];
-    gram_h2_body<TS, false, true>(it.f, it.N, it.C, it.nsplit, it.pix_per_split, it.amax, it.part,
-                                  (int)blockIdx.x - (i ? b.it[i - 1].part_end : 0), nullptr, it.offset);
+    gram_h2_body<TS, false, true, PACK>(it.f, it.N, it.C, it.nsplit, it.pix_per_split, it.amax, it.part,
+                                        (int)blockIdx.x - (i ? b.it[i - 1].part_end : 0), nullptr, it.offset);
+}
+
+// Plain batches under PACK: the items of BOTH tile shapes in one grid.  The 64-wide items (relu1_1: HBM-bound) and the
+// 128-wide ones (matrix-pipe- and LDS-bound) use 256 threads and 72 KiB of LDS alike, so two workgroups of either kind share
+// a CU.  The batch lists the n128 items of the 128-wide shape first, then the others; part_end counts inside a shape.
+// Every workgroup keeps its (item, tile pair, split) - only the block index that carries it changes: the nb64 workgroups of
+// the 64-wide shape are dealt evenly through the nb128 others, the order inside a shape kept (block b is the k-th 64-wide
+// one when floor(b nb64 / nb) steps from k to k + 1 there).
+__global__ __launch_bounds__(256, 2) void gram_h2_pack_kernel(GramBatch b, int n128, int nb128, int nb64) {
+    const unsigned long long nb = (unsigned long long)nb128 + nb64;
+    const int k0 = (int)((unsigned long long)blockIdx.x * nb64 / nb), k1 = (int)(((unsigned long long)blockIdx.x + 1) * nb64 / nb);
+    if (k1 > k0) {
+        int i = n128;
+        while (i + 1 < b.n && k0 >= b.it[i].part_end) ++i;
+        const GramItem& it = b.it[i];
+        gram_h2_body<64, false, false, true>(it.f, it.N, it.C, it.nsplit, it.pix_per_split, it.amax, it.part,
+                                             k0 - (i > n128 ? b.it[i - 1].part_end : 0));
+    } else {
+        const int k = (int)blockIdx.x - k0;
+        int i = 0;
+        while (i + 1 < n128 && k >= b.it[i].part_end) ++i;
+        const GramItem& it = b.it[i];
+        gram_h2_body<128, false, false, true>(it.f, it.N, it.C, it.nsplit, it.pix_per_split, it.amax, it.part,
+                                              k - (i ? b.it[i - 1].part_end : 0));
+    }
 }
 
 // generic fallback for channel counts that are not a multiple of 64 (unit-parity API only)
@@ -469,45 +572,51 @@ hipError_t gram_init_device() {
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gram_partial_kernel<64>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, GramCfg<64>::LDS_BYTES);
     if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gram_h2_kernel<128>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, GramH2Cfg<128>::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gram_h2_batch_kernel<128>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, GramH2Cfg<128>::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gram_h2_batch_kernel<64>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, GramH2Cfg<64>::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gram_h2_shift_kernel<128>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, GramH2Cfg<128>::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gram_h2_shift_kernel<64>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, GramH2Cfg<64>::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gram_h2_shift_batch_kernel<128>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, GramH2Cfg<128>::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gram_h2_shift_batch_kernel<64>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, GramH2Cfg<64>::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gram_h2_guided_kernel<128>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, GramH2Cfg<128>::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gram_h2_guided_kernel<64>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, GramH2Cfg<64>::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gram_h2_guided_batch_kernel<128>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, GramH2Cfg<128>::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gram_h2_guided_batch_kernel<64>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, GramH2Cfg<64>::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&gram_h2_kernel<64>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, GramH2Cfg<64>::LDS_BYTES);
+    // every fp16-piece form, both tile shapes, the parent's kernels and the PACK ones
+    static_assert(GramH2Cfg<128>::LDS_BYTES == GramH2Cfg<64>::LDS_BYTES, "gram_h2_pack_kernel runs both bodies in one LDS size");
+    const void* h2_128[] = {
+        reinterpret_cast<const void*>(&gram_h2_kernel<128, false>),              reinterpret_cast<const void*>(&gram_h2_kernel<128, true>),
+        reinterpret_cast<const void*>(&gram_h2_batch_kernel<128, false>),        reinterpret_cast<const void*>(&gram_h2_batch_kernel<128, true>),
+        reinterpret_cast<const void*>(&gram_h2_guided_kernel<128, false>),       reinterpret_cast<const void*>(&gram_h2_guided_kernel<128, true>),
+        reinterpret_cast<const void*>(&gram_h2_guided_batch_kernel<128, false>), reinterpret_cast<const void*>(&gram_h2_guided_batch_kernel<128, true>),
+        reinterpret_cast<const void*>(&gram_h2_shift_kernel<128, false>),        reinterpret_cast<const void*>(&gram_h2_shift_kernel<128, true>),
+        reinterpret_cast<const void*>(&gram_h2_shift_batch_kernel<128, false>),  reinterpret_cast<const void*>(&gram_h2_shift_batch_kernel<128, true>),
+        reinterpret_cast<const void*>(&gram_h2_pack_kernel)};
+    const void* h2_64[] = {
+        reinterpret_cast<const void*>(&gram_h2_kernel<64, false>),              reinterpret_cast<const void*>(&gram_h2_kernel<64, true>),
+        reinterpret_cast<const void*>(&gram_h2_batch_kernel<64, false>),        reinterpret_cast<const void*>(&gram_h2_batch_kernel<64, true>),
+        reinterpret_cast<const void*>(&gram_h2_guided_kernel<64, false>),       reinterpret_cast<const void*>(&gram_h2_guided_kernel<64, true>),
+        reinterpret_cast<const void*>(&gram_h2_guided_batch_kernel<64, false>), reinterpret_cast<const void*>(&gram_h2_guided_batch_kernel<64, true>),
+        reinterpret_cast<const void*>(&gram_h2_shift_kernel<64, false>),        reinterpret_cast<const void*>(&gram_h2_shift_kernel<64, true>),
+        reinterpret_cast<const void*>(&gram_h2_shift_batch_kernel<64, false>),  reinterpret_cast<const void*>(&gram_h2_shift_batch_kernel<64, true>)};
+    for (const void* k : h2_128) {
+        e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, GramH2Cfg<128>::LDS_BYTES);
+        if (e != hipSuccess) return e;
+    }
+    for (const void* k : h2_64) {
+        e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, GramH2Cfg<64>::LDS_BYTES);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// one map on the fp16 matrix pipe: plain, guided or shifted (never both)
+template <int TS, bool PACK>
+static void launch_h2_single(int blocks, hipStream_t stream, const float* f, size_t N, int C, int nsplit, size_t pix_per_split,
+                             const unsigned* amax, float* part, const float* guide, const float* offset) {
+    if (guide)
+        hipLaunchKernelGGL((gram_h2_guided_kernel<TS, PACK>), dim3(blocks), dim3(256), GramH2Cfg<TS>::LDS_BYTES, stream, f, N, C, nsplit,
+                           pix_per_split, amax, part, guide);
+    else if (offset)
+        hipLaunchKernelGGL((gram_h2_shift_kernel<TS, PACK>), dim3(blocks), dim3(256), GramH2Cfg<TS>::LDS_BYTES, stream, f, N, C, nsplit,
+                           pix_per_split, amax, part, offset);
+    else
+        hipLaunchKernelGGL((gram_h2_kernel<TS, PACK>), dim3(blocks), dim3(256), GramH2Cfg<TS>::LDS_BYTES, stream, f, N, C, nsplit,
+                           pix_per_split, amax, part);
 }
 
 hipError_t launch_gram_partial(const float* f, size_t N, int C, int nsplit, const unsigned* amax, float* part,
-                               hipStream_t stream, const float* guide, const float* offset) {
+                               hipStream_t stream, const float* guide, const float* offset, int pack) {
     const int ts = gram_ts(C);
     if ((guide || offset) && (ts == 0 || !amax)) return hipErrorInvalidValue;
     if (guide && offset) return hipErrorInvalidValue;
@@ -523,28 +632,12 @@ hipError_t launch_gram_partial(const float* f, size_t N, int C, int nsplit, cons
     const size_t pix_per_split = cps * kp;
     // fp16-piece kernel when the absmax record of f is available (32-bit buffer offsets inside one split)
     const bool h2 = amax != nullptr && pix_per_split * (size_t)C * 4 < 0xFFFFFF00ull;
-    if (guide) {
+    if (guide || offset || h2) {
         if (!h2) return hipErrorInvalidValue;
-        if (ts == 128)
-            hipLaunchKernelGGL(gram_h2_guided_kernel<128>, dim3(pairs * nsplit), dim3(256), GramH2Cfg<128>::LDS_BYTES, stream, f, N, C,
-                               nsplit, pix_per_split, amax, part, guide);
-        else
-            hipLaunchKernelGGL(gram_h2_guided_kernel<64>, dim3(pairs * nsplit), dim3(256), GramH2Cfg<64>::LDS_BYTES, stream, f, N, C,
-                               nsplit, pix_per_split, amax, part, guide);
-    } else if (offset) {
-        if (!h2) return hipErrorInvalidValue;
-        if (ts == 128)
-            hipLaunchKernelGGL(gram_h2_shift_kernel<128>, dim3(pairs * nsplit), dim3(256), GramH2Cfg<128>::LDS_BYTES, stream, f, N, C,
-                               nsplit, pix_per_split, amax, part, offset);
-        else
-            hipLaunchKernelGGL(gram_h2_shift_kernel<64>, dim3(pairs * nsplit), dim3(256), GramH2Cfg<64>::LDS_BYTES, stream, f, N, C,
-                               nsplit, pix_per_split, amax, part, offset);
-    } else if (h2 && ts == 128) {
-        hipLaunchKernelGGL(gram_h2_kernel<128>, dim3(pairs * nsplit), dim3(256), GramH2Cfg<128>::LDS_BYTES, stream, f, N, C,
-                           nsplit, pix_per_split, amax, part);
-    } else if (h2) {
-        hipLaunchKernelGGL(gram_h2_kernel<64>, dim3(pairs * nsplit), dim3(256), GramH2Cfg<64>::LDS_BYTES, stream, f, N, C,
-                           nsplit, pix_per_split, amax, part);
+        if (ts == 128 && pack) launch_h2_single<128, true>(pairs * nsplit, stream, f, N, C, nsplit, pix_per_split, amax, part, guide, offset);
+        else if (ts == 128) launch_h2_single<128, false>(pairs * nsplit, stream, f, N, C, nsplit, pix_per_split, amax, part, guide, offset);
+        else if (pack) launch_h2_single<64, true>(pairs * nsplit, stream, f, N, C, nsplit, pix_per_split, amax, part, guide, offset);
+        else launch_h2_single<64, false>(pairs * nsplit, stream, f, N, C, nsplit, pix_per_split, amax, part, guide, offset);
     } else if (ts == 128) {
         hipLaunchKernelGGL(gram_partial_kernel<128>, dim3(pairs * nsplit), dim3(256), GramCfg<128>::LDS_BYTES, stream, f,
                            N, C, nsplit, pix_per_split, part);
@@ -579,6 +672,12 @@ __device__ __forceinline__ void gram_finish_body(const float* __restrict__ part,
     // kernel adds the two cross products of (i,j) and (j,i) in opposite orders: only elements with j >= i are read
     // and each result is written to (i,j) AND (j,i), which makes G exactly symmetric.  With C a multiple of 128 a
     // block's segment lies in one row; segments entirely below the diagonal do nothing.
+    // THE RULE THE PACK KERNELS RELY ON: with `tri`, a 16-byte group (four elements of one row, inside one 32-wide block
+    // column) is loaded only when one of its elements has j >= i - so no load ever touches a 32x32 block that lies strictly
+    // below the diagonal, and under nst_ctx_set_gram_pack such blocks of a slab are never written (gram_h2_body, PACK).  Every
+    // reader of a partial buffer (L.gram_part, the guided g.part, the scratch of the target forwards and the window sums of
+    // the stripe path; L.gs.part holds channel sums, not slabs) comes through here with ts > 0.  A new reader of slabs must
+    // keep to j >= i or run with the pack switched off.
     const bool tri = ts > 0;
     if (tri && C % GF_EPB == 0 && (int)((size_t)bid * GF_EPB % C) + GF_EPB - 1 < (int)((size_t)bid * GF_EPB / C)) {
         if (threadIdx.x == 0 && mse_partial) mse_partial[bid] = 0.0;
@@ -722,7 +821,16 @@ static int gram_nsplit_in_batch(const GramBatch& b, int i) {
 
 // Batched forms (fp16-piece kernels only: every item needs its absmax record, C = 64 or a multiple of 128, and its
 // own partial buffer of nsplit x C x C floats).  Fills nsplit / pix_per_split / the block prefixes.
-hipError_t launch_gram_batch(const GramBatch& b0, hipStream_t stream) {
+template <int TS, bool PACK>
+static void launch_h2_batch(int blocks, hipStream_t stream, const GramBatch& b, bool guided, bool shifted) {
+    if (guided) hipLaunchKernelGGL((gram_h2_guided_batch_kernel<TS, PACK>), dim3(blocks), dim3(256), GramH2Cfg<TS>::LDS_BYTES, stream, b);
+    else if (shifted) hipLaunchKernelGGL((gram_h2_shift_batch_kernel<TS, PACK>), dim3(blocks), dim3(256), GramH2Cfg<TS>::LDS_BYTES, stream, b);
+    else hipLaunchKernelGGL((gram_h2_batch_kernel<TS, PACK>), dim3(blocks), dim3(256), GramH2Cfg<TS>::LDS_BYTES, stream, b);
+}
+
+// pack (nst_ctx_set_gram_pack): the PACK kernels, and a plain batch's two tile shapes in one grid; 0: the parent's kernels
+// and launch sequence
+hipError_t launch_gram_batch(const GramBatch& b0, hipStream_t stream, int pack) {
     if (b0.n < 1 || b0.n > NST_GRAM_BATCH_MAX) return hipErrorInvalidValue;
     // a batch is guided as a whole (every item carries its guidance plane) or not at all
     const bool guided = b0.it[0].guide != nullptr;
@@ -733,7 +841,11 @@ hipError_t launch_gram_batch(const GramBatch& b0, hipStream_t stream) {
     for (int i = 0; i < b0.n; ++i)
         if ((b0.it[i].offset != nullptr) != shifted) return hipErrorInvalidValue;
     if (guided && shifted) return hipErrorInvalidValue;
-    // partial products: one launch per tile shape
+    // partial products: one launch per tile shape - or, for a plain batch under `pack`, one launch for both (the 128-wide
+    // items are collected first, the 64-wide ones behind them: the item order gram_h2_pack_kernel reads)
+    const bool one_grid = pack && !guided && !shifted;
+    GramBatch both{};
+    int n128 = 0, nb128 = 0, nb64 = 0;
     for (int ts = 128; ts >= 64; ts -= 64) {
         GramBatch b{};
         for (int i = 0; i < b0.n; ++i) {
@@ -754,12 +866,25 @@ hipError_t launch_gram_batch(const GramBatch& b0, hipStream_t stream) {
         }
         if (b.n == 0) continue;
         const int blocks = b.it[b.n - 1].part_end;
-        if (guided && ts == 128) hipLaunchKernelGGL(gram_h2_guided_batch_kernel<128>, dim3(blocks), dim3(256), GramH2Cfg<128>::LDS_BYTES, stream, b);
-        else if (guided) hipLaunchKernelGGL(gram_h2_guided_batch_kernel<64>, dim3(blocks), dim3(256), GramH2Cfg<64>::LDS_BYTES, stream, b);
-        else if (shifted && ts == 128) hipLaunchKernelGGL(gram_h2_shift_batch_kernel<128>, dim3(blocks), dim3(256), GramH2Cfg<128>::LDS_BYTES, stream, b);
-        else if (shifted) hipLaunchKernelGGL(gram_h2_shift_batch_kernel<64>, dim3(blocks), dim3(256), GramH2Cfg<64>::LDS_BYTES, stream, b);
-        else if (ts == 128) hipLaunchKernelGGL(gram_h2_batch_kernel<128>, dim3(blocks), dim3(256), GramH2Cfg<128>::LDS_BYTES, stream, b);
-        else hipLaunchKernelGGL(gram_h2_batch_kernel<64>, dim3(blocks), dim3(256), GramH2Cfg<64>::LDS_BYTES, stream, b);
+        if (one_grid) {
+            for (int i = 0; i < b.n; ++i) both.it[both.n++] = b.it[i];
+            if (ts == 128) { n128 = b.n; nb128 = blocks; }
+            else nb64 = blocks;
+            continue;
+        }
+        if (ts == 128 && pack) launch_h2_batch<128, true>(blocks, stream, b, guided, shifted);
+        else if (ts == 128) launch_h2_batch<128, false>(blocks, stream, b, guided, shifted);
+        else if (pack) launch_h2_batch<64, true>(blocks, stream, b, guided, shifted);
+        else launch_h2_batch<64, false>(blocks, stream, b, guided, shifted);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    if (one_grid) {
+        // (a batch of one shape only has nothing to interleave: its own kernel)
+        if (nb128 > 0 && nb64 > 0)
+            hipLaunchKernelGGL(gram_h2_pack_kernel, dim3(nb128 + nb64), dim3(256), GramH2Cfg<128>::LDS_BYTES, stream, both, n128, nb128, nb64);
+        else if (nb128 > 0) launch_h2_batch<128, true>(nb128, stream, both, false, false);
+        else if (nb64 > 0) launch_h2_batch<64, true>(nb64, stream, both, false, false);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

@@ -415,7 +415,7 @@ int gram_of(nst_ctx* ctx, const float* f_nhwc, size_t N, int C, const unsigned* 
     const int ns = gram_nsplit(C, N);
     {
         Timer t(ctx, s, K_GRAM, 2.0 * (double)N * C * C);
-        HIPCHK(ctx, launch_gram_partial(f_nhwc, N, C, ns, f_amax, part, s));
+        HIPCHK(ctx, launch_gram_partial(f_nhwc, N, C, ns, f_amax, part, s, nullptr, nullptr, ctx->gram_pack));
     }
     Timer t(ctx, s, K_OTHER, 0);
     HIPCHK(ctx, launch_gram_finish(part, gram_nslabs(C, ns), C, divisor, target, coef, gram_out, S, S_bf, S_amax,
@@ -437,7 +437,7 @@ int gram_shifted_of(nst_ctx* ctx, const float* f_nhwc, size_t N, int C, const un
     }
     {
         Timer t(ctx, s, K_GRAM, 2.0 * (double)N * C * C);
-        HIPCHK(ctx, launch_gram_partial(f_nhwc, N, C, ns, sg.rec, part, s, nullptr, sg.offset));
+        HIPCHK(ctx, launch_gram_partial(f_nhwc, N, C, ns, sg.rec, part, s, nullptr, sg.offset, ctx->gram_pack));
     }
     {
         Timer t(ctx, s, K_OTHER, 0);
@@ -594,7 +594,7 @@ int batched_gram_guided(nst_ctx* ctx, const int* lv, int n, float sw, hipStream_
     auto flush = [&]() -> int {
         if (gb.n == 0) return NST_OK;
         Timer t(ctx, s, K_GRAM, flops);
-        HIPCHK(ctx, launch_gram_batch(gb, s));
+        HIPCHK(ctx, launch_gram_batch(gb, s, ctx->gram_pack));
         gb = GramBatch{};
         flops = 0;
         return NST_OK;
@@ -629,7 +629,8 @@ int batched_gram(nst_ctx* ctx, const int* lv, int n, float sw, hipStream_t s, un
     const bool h2 = ctx->conv_mode == 2;
     if (guided_levels(ctx, lv, n)) return qmask ? batched_gram_guided(ctx, lv, n, sw, s) : NST_OK;
     if (h2) {
-        // every (level, style layer) pair in two partial launches (one per tile shape) and one finish launch
+        // every (level, style layer) pair in one partial launch (two, one per tile shape, when shifted or with the Gram pack
+        // switched off) and one finish launch
         const int per = std::max(1, NST_GRAM_BATCH_MAX / ctx->taps.nstyle);      // levels per launch (3 with five style maps)
         const bool shifted = ctx->gs_on();
         const bool moments = ctx->mom_on();
@@ -682,7 +683,7 @@ int batched_gram(nst_ctx* ctx, const int* lv, int n, float sw, hipStream_t s, un
             }
             {
                 Timer t(ctx, s, K_GRAM, flops);
-                HIPCHK(ctx, launch_gram_batch(gb, s));
+                HIPCHK(ctx, launch_gram_batch(gb, s, ctx->gram_pack));
             }
             if (shifted) {
                 Timer t(ctx, s, K_OTHER, 0);
@@ -974,7 +975,7 @@ int closure_per_level(nst_ctx* ctx, const float* const* xi, float* const* gi, in
             const int ns = gram_nsplit(st.C, st.N);
             {
                 Timer t(ctx, s, K_GRAM, 2.0 * (double)st.N * st.C * st.C);
-                HIPCHK(ctx, launch_gram_partial(L.acts.act[l], st.N, st.C, ns, amax_act(L.acts, l), g.part, s, g.plane(kScale[l], r, L.h, L.w)));
+                HIPCHK(ctx, launch_gram_partial(L.acts.act[l], st.N, st.C, ns, amax_act(L.acts, l), g.part, s, g.plane(kScale[l], r, L.h, L.w), nullptr, ctx->gram_pack));
             }
             Timer t(ctx, s, K_OTHER, 0);
             HIPCHK(ctx, launch_gram_finish(g.part, gram_nslabs(st.C, ns), st.C, (float)st.divisor, g.gram_t[k] + (size_t)r * st.C * st.C, st.coef,
@@ -1332,7 +1333,7 @@ int nst_level_set_targets_blend(nst_ctx* ctx, int level, const float* content, i
             const int ns = gram_nsplit(st.C, st.N);
             {
                 Timer t(ctx, s, K_GRAM, 2.0 * (double)st.N * st.C * st.C);
-                HIPCHK(ctx, launch_gram_partial(sc.acts.act[l], st.N, st.C, ns, ctx->conv_mode == 2 ? amax_act(sc.acts, l) : nullptr, part, s));
+                HIPCHK(ctx, launch_gram_partial(sc.acts.act[l], st.N, st.C, ns, ctx->conv_mode == 2 ? amax_act(sc.acts, l) : nullptr, part, s, nullptr, nullptr, ctx->gram_pack));
             }
             Timer t(ctx, s, K_OTHER, 0);
             HIPCHK(ctx, launch_gram_finish_blend(part, gram_nslabs(st.C, ns), st.C, (float)st.divisor, bhat[k][q], written[q] ? 1 : 0,
@@ -1484,7 +1485,7 @@ int nst_level_set_targets_guided(nst_ctx* ctx, int level, const float* content, 
         for (int r = 0; r < R; ++r) {
             {
                 Timer t(ctx, s, K_GRAM, 2.0 * (double)N * C * C);
-                HIPCHK(ctx, launch_gram_partial(sc.acts.act[l], N, C, ns, amax_act(sc.acts, l), part, s, sp + off[scl] + (size_t)r * N));
+                HIPCHK(ctx, launch_gram_partial(sc.acts.act[l], N, C, ns, amax_act(sc.acts, l), part, s, sp + off[scl] + (size_t)r * N, nullptr, ctx->gram_pack));
             }
             Timer t(ctx, s, K_OTHER, 0);
             HIPCHK(ctx, launch_gram_finish_blend(part, gram_nslabs(C, ns), C, (float)((double)C * smass[scl][r]), 1.f, 0,
@@ -1656,7 +1657,7 @@ int nst_window_begin(nst_ctx* ctx, const float* xs, int row0, int rows, int H0, 
         const size_t off = (size_t)win_r0(win, kScale[l]) * a.w[l] * C;
         const size_t N = (size_t)win_nr(win, kScale[l]) * a.w[l];
         const int ns = gram_nsplit(C, N);
-        HIPCHK(ctx, launch_gram_partial(a.act[l] + off, N, C, ns, amax_act(a, l), L.gram_part, s));
+        HIPCHK(ctx, launch_gram_partial(a.act[l] + off, N, C, ns, amax_act(a, l), L.gram_part, s, nullptr, nullptr, ctx->gram_pack));
         HIPCHK(ctx, launch_gram_finish(L.gram_part, gram_nslabs(C, ns), C, 1.f, nullptr, 0.f, sums + kWinGramOff[q], nullptr, nullptr,
                                        nullptr, nullptr, s));
     }

@@ -545,6 +545,7 @@ int nst_ctx_create_ex(int device, const float* const* weights, const float* cons
     ctx->gram_overlap = (opts.gram_overlap >= 0 ? opts.gram_overlap : env_flag("NST_GRAM_OVERLAP", 0)) ? 1 : 0;
     ctx->keep_all_maps = env_flag("NST_KEEP_ALL_MAPS", 0) ? 1 : 0;      // (nst_ctx_set_keep_all_maps overrides)
     ctx->forward_pack = env_flag("NST_FORWARD_PACK", 1) ? 1 : 0;        // (nst_ctx_set_forward_pack overrides)
+    ctx->gram_pack = env_flag("NST_GRAM_PACK", 1) ? 1 : 0;              // (nst_ctx_set_gram_pack overrides)
     if (ctx->use_graph && hipStreamCreateWithFlags(&ctx->gstream, hipStreamNonBlocking) != hipSuccess) { ctx->err = "stream creation failed"; return bail(NST_E_HIP); }
     if (e != hipSuccess) { ctx->err = std::string("kernel attribute setup: ") + hipGetErrorString(e); return bail(NST_E_HIP); }
 
@@ -793,6 +794,18 @@ int nst_ctx_set_forward_pack(nst_ctx* ctx, int enabled) {
     return NST_OK;
 }
 int nst_ctx_forward_pack(const nst_ctx* ctx) { return ctx ? ctx->forward_pack : -1; }
+
+// The A/B twin of the packed Gram pass in one build: 0 = every block of a diagonal tile is computed and written, and a plain
+// batch launches once per tile shape.  Results do not depend on it (gram.hip: a kept block sees the same MFMAs in the same
+// order, and nothing reads the dropped ones).
+int nst_ctx_set_gram_pack(nst_ctx* ctx, int enabled) {
+    NSTCHK(bind(ctx));
+    ++ctx->ws_seq;
+    drop_closure_state(ctx, false);
+    ctx->gram_pack = enabled ? 1 : 0;
+    return NST_OK;
+}
+int nst_ctx_gram_pack(const nst_ctx* ctx) { return ctx ? ctx->gram_pack : -1; }
 
 int nst_job_map_stats(nst_ctx* ctx, int level, unsigned* stored_mask) {
     NSTCHK(bind(ctx));

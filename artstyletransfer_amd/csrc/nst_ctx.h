@@ -243,6 +243,9 @@ struct nst_ctx {
     // nst_ctx_set_forward_pack: 1 = the batched f16x2 forward half launches its front (absmax clears, TV partials, conv1_1)
     // and its loss terms once for all levels and leaves S in bf16 pieces unwritten; 0 = per level, with the pieces
     int forward_pack = 1;
+    // nst_ctx_set_gram_pack: 1 = the fp16-piece Gram kernels skip the blocks below the diagonal of a diagonal tile and a
+    // plain batch takes both tile shapes in one launch; 0 = the kernels and the two launches from before
+    int gram_pack = 1;
     unsigned long long fwd_pass = 0;     // batched forward passes so far (ActSet::pass)
     hipStream_t side = nullptr; // the Gram launches of the shallow style layers run here, under the deeper forward convolutions
     hipEvent_t side_fork = nullptr, side_join = nullptr;

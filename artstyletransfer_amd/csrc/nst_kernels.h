@@ -309,12 +309,13 @@ int gram_nsplit(int C, size_t N);
 // offset (nullable; not with guide): the shifted Gram sum_p (F(p) + o)(F(p) + o)^T, o = offset[C]; `amax` is then the record
 // of the shifted operand that launch_gram_offsets writes; the fp16-piece kernels only
 hipError_t launch_gram_partial(const float* f, size_t N, int C, int nsplit, const unsigned* amax, float* part,
-                               hipStream_t stream, const float* guide = nullptr, const float* offset = nullptr);
+                               hipStream_t stream, const float* guide = nullptr, const float* offset = nullptr, int pack = 1);
 // G = (sum_s part[s]) / divisor (fixed order).  If target: mse_out[0] = sum((G-Gt)^2) (double) and
 // S = coef * (G - Gt) (C x C, for the backward 1x1 conv).  gram_out / target / S / mse_partial nullable;
 // mse_partial: gram_finish_blocks(C) doubles.  `nslabs` = gram_nslabs(C, nsplit).
 int gram_nslabs(int C, int nsplit);
-// Several Gram matrices in two partial launches (one per tile shape) + one finish launch.  Per item the caller sets
+// Several Gram matrices in two partial launches (one per tile shape; a plain batch under `pack`: one for both) + one finish
+// launch.  pack (nst_ctx_set_gram_pack): the kernels that skip the below-diagonal blocks of a diagonal tile.  Per item the caller sets
 // f, N, C, amax, part (its own gram_nsplit(C, N) x C x C floats) and the finish arguments; the rest is filled in.
 constexpr int NST_GRAM_BATCH_MAX = 16;
 struct GramItem {
@@ -326,7 +327,7 @@ struct GramItem {
     const float* offset;  // shifted Gram (gram_shift.hip): o[C] added to every staged value, `amax` the shifted operand's record; nullptr: plain
 };
 struct GramBatch { GramItem it[NST_GRAM_BATCH_MAX]; int n; };
-hipError_t launch_gram_batch(const GramBatch& b, hipStream_t stream);
+hipError_t launch_gram_batch(const GramBatch& b, hipStream_t stream, int pack = 1);
 #define NST_GRAM_FINISH_EPB 128      // elements of G a block of the finish pass owns (one partial sum of (G-Gt)^2 each)
 int gram_finish_blocks(int C);
 // S_amax (nullable): NST_AMAX_SLOTS words receiving the absmax of S (atomic max; zero them beforehand).

@@ -670,6 +670,17 @@ int nst_ctx_keep_all_maps(const nst_ctx* ctx);
  *     null context. */
 int nst_ctx_set_forward_pack(nst_ctx* ctx, int enabled);
 int nst_ctx_forward_pack(const nst_ctx* ctx);
+/* The packed Gram pass (on by default).  The finish pass of a Gram matrix reads only the elements with j >= i of every
+ * partial slab and writes each result to (i,j) and (j,i).  Packed, the fp16-piece partial kernels - plain, guided and shifted,
+ * single maps and batches - do not compute the 32x32 blocks strictly below the diagonal of a diagonal tile and leave that
+ * part of a slab unwritten, and a plain batch (the style maps of all pyramid levels of a closure) takes its 64-channel and its
+ * 128-channel-tile maps in ONE partial launch instead of two.  Every element that is read is the sum of the same products in
+ * the same order under either setting: Gram matrices, losses and gradients are bitwise the same.
+ *   nst_ctx_set_gram_pack(ctx, 0): every block computed and written, one partial launch per tile shape - the A/B twin in one
+ *     build.  A new context takes env NST_GRAM_PACK (read once at creation), default 1.  nst_ctx_gram_pack: the setting, -1
+ *     for a null context. */
+int nst_ctx_set_gram_pack(nst_ctx* ctx, int enabled);
+int nst_ctx_gram_pack(const nst_ctx* ctx);
 /* The image of pyramid level `level` >= 1 that the last closure evaluated - the bicubic 1/2 chain of x
  * (neural_style_transfer.py:170-176) - as (3,h_l,w_l) planar fp32 to out (device).  The total-variation term takes
  * sign(y_i - y_j) of neighbouring pixels: on flat image regions those differences are rounding noise of the down-sampling,

@@ -89,10 +89,12 @@ def mfma(directory, out_txt):
              "# rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_ANY",
              "#   --output-format csv -- python tools/pmc_run.py 3 2",
              "# mfma_util = SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE/8 * 256 CU * 4 SIMD); clk ~ GRBM_GUI_ACTIVE/8/duration"]
+    lines.append("# and of the Gram partial launches (gram_h2_*), which are not part of the 3x3 conv sum")
     busy_sum = cyc_sum = 0.0
     for d in last_closure(rows):
         m = meta[d]
-        if "conv_bf3" not in m["Kernel_Name"] and "conv_h2" not in m["Kernel_Name"] and "conv_wino" not in m["Kernel_Name"]:
+        gram = "gram_h2" in m["Kernel_Name"]
+        if "conv_bf3" not in m["Kernel_Name"] and "conv_h2" not in m["Kernel_Name"] and "conv_wino" not in m["Kernel_Name"] and not gram:
             continue
         v = vals[d]
         dur = (int(m["End_Timestamp"]) - int(m["Start_Timestamp"])) / 1e3
@@ -100,8 +102,9 @@ def mfma(directory, out_txt):
         busy = v.get("SQ_VALU_MFMA_BUSY_CYCLES", 0.0)
         util = busy / (gui * 256 * 4) if gui else 0.0
         wait = v.get("SQ_WAIT_ANY", 0.0) / v["SQ_WAVE_CYCLES"] if v.get("SQ_WAVE_CYCLES") else 0.0
-        busy_sum += busy
-        cyc_sum += gui * 1024
+        if not gram:
+            busy_sum += busy
+            cyc_sum += gui * 1024
         lines.append(f"{short(m['Kernel_Name']):<34} grid {int(m['Grid_Size']):>8} dur {dur:>6.0f} us "
                      f"clk~{gui / dur / 1e3:.2f} GHz mfma_util {util:.3f} wait_any/wave_cyc {wait:.2f}")
     if cyc_sum:
