@@ -173,7 +173,7 @@ int nst_level_image(nst_ctx* ctx, int level, float* out, void* stream) {
     if (!out) return fail(ctx, NST_E_ARG, "null argument");
     const LevelWs& L = ctx->lv[level];
     hipStream_t s = enter(ctx, stream);
-    HIPCHK(ctx, hipMemcpyAsync(out, L.xl, (size_t)ctx->channels * L.h * L.w * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(out, L.img.xl, (size_t)ctx->channels * L.h * L.w * sizeof(float), hipMemcpyDeviceToDevice, s));
     mark(ctx, s);
     return NST_OK;
 }
@@ -182,23 +182,19 @@ int nst_total_variation(nst_ctx* ctx, const float* y, int C, int h, int w, float
     NSTCHK(bind(ctx));
     if (!y || !value) return fail(ctx, NST_E_ARG, "null argument");
     hipStream_t s = static_cast<hipStream_t>(stream);
+    Scratch sc(ctx, s);
     double* partial = nullptr; float* means = nullptr;
-    int r = dev_alloc_t(ctx, &partial, 2 * TV_BLOCKS);
-    if (r == NST_OK) r = dev_alloc_t(ctx, &means, 2);
-    hipError_t e = hipSuccess;
-    if (r == NST_OK) {
-        e = launch_tv_partial(y, C, h, w, partial, s);
-        if (e == hipSuccess) e = launch_tv_finish(y, C, h, w, partial, 1.f, grad, 0, means, s);
-        float m[2] = {0, 0};
-        if (e == hipSuccess) e = hipMemcpyAsync(m, means, 8, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        const float tv = m[0] * m[0] + m[1] * m[1];
-        if (e == hipSuccess) e = hipMemcpy(value, &tv, 4, hipMemcpyHostToDevice);
-    }
-    dev_free(partial); dev_free(means);
-    if (r != NST_OK) return r;
+    NSTCHK(sc.alloc(&partial, 2 * TV_BLOCKS));
+    NSTCHK(sc.alloc(&means, 2));
+    hipError_t e = launch_tv_partial(y, C, h, w, partial, s);
+    if (e == hipSuccess) e = launch_tv_finish(y, C, h, w, partial, 1.f, grad, 0, means, s);
+    float m[2] = {0, 0};
+    if (e == hipSuccess) e = hipMemcpyAsync(m, means, 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    const float tv = m[0] * m[0] + m[1] * m[1];
+    if (e == hipSuccess) e = hipMemcpy(value, &tv, 4, hipMemcpyHostToDevice);
     HIPCHK(ctx, e);
-    return NST_OK;
+    return sc.finish();
 }
 
 // The Laplacian term of one entry on its own (include/nst_hip.h): value = lap_k of y against content, grad (nullable,
@@ -305,21 +301,15 @@ int nst_noise_blend(nst_ctx* ctx, const float* content, const float* noise, int 
     if (!content || !noise || !out || h < 1 || w < 1 || channels < 1) return fail(ctx, NST_E_ARG, "bad argument");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t n = (size_t)h * w * channels;
+    Scratch sc(ctx, s);
     double* t0 = nullptr; double* t1 = nullptr; double* wt = nullptr;
-    int r = dev_alloc_t(ctx, &t0, n);
-    if (r == NST_OK) r = dev_alloc_t(ctx, &t1, n);
-    if (r == NST_OK) r = dev_alloc_t(ctx, &wt, n);
-    hipError_t e = hipSuccess;
-    if (r == NST_OK) {
-        e = launch_blend_weight(content, h, w, channels, noise_factor, t0, t1, wt, s);
-        if (e == hipSuccess) e = launch_blend_init(content, noise, wt, n, out, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-    }
-    dev_free(t0); dev_free(t1); dev_free(wt);
-    if (ctx->bytes >= 3 * n * 8) ctx->bytes -= 3 * n * 8;
-    if (r != NST_OK) return r;
+    NSTCHK(sc.alloc(&t0, n));
+    NSTCHK(sc.alloc(&t1, n));
+    NSTCHK(sc.alloc(&wt, n));
+    hipError_t e = launch_blend_weight(content, h, w, channels, noise_factor, t0, t1, wt, s);
+    if (e == hipSuccess) e = launch_blend_init(content, noise, wt, n, out, s);
     HIPCHK(ctx, e);
-    return NST_OK;
+    return sc.finish();
 }
 int nst_scale(nst_ctx* ctx, const float* src, float alpha, size_t n, float* dst, void* stream) {
     NSTCHK(bind(ctx));
@@ -334,7 +324,7 @@ int nst_color_stats(nst_ctx* ctx, const float* hwc, int h, int w, double* mean, 
     if (!hwc || !mean || !cov || h < 1 || w < 1) return fail(ctx, NST_E_ARG, "bad argument");
     hipStream_t s = static_cast<hipStream_t>(stream);
     // the context's own scratch (kept: no allocation or free, and so no device-wide synchronisation, per call)
-    if (!ctx->color_scratch) NSTCHK(dev_alloc_t(ctx, &ctx->color_scratch, (size_t)COLOR_BLOCKS * 9 + 12));
+    if (!ctx->color_scratch) NSTCHK(ctx->mem.alloc(ctx, &ctx->color_scratch, (size_t)COLOR_BLOCKS * 9 + 12));
     double* dev = ctx->color_scratch;
     double host[12];
     HIPCHK(ctx, launch_color_stats(hwc, (size_t)h * w, dev, dev + (size_t)COLOR_BLOCKS * 9, dev + (size_t)COLOR_BLOCKS * 9 + 3, s));

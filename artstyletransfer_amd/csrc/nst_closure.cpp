@@ -1036,14 +1036,14 @@ LossAssembly fill_loss_assembly(const nst_ctx* ctx, unsigned level_mask, float c
         la.lv[i].owned = (int)((level_mask >> i) & 1u);
         for (int k = 0; k < ctx->lap_k; ++k) { la.lv[i].lap_partial[k] = L.lap.partial[k]; la.lv[i].lap_n[k] = lap_n(L, ctx->lap_pool[k]); }
     }
-    la.nlap = ctx->lap_k; la.lap_out = ctx->lap_vals;
-    la.mat_gamma = ctx->mat_gamma; la.mat_out = ctx->mat_vals;
+    la.nlap = ctx->lap_k; la.lap_out = ctx->lv[0].lap.vals;
+    la.mat_gamma = ctx->mat_gamma; la.mat_out = ctx->lv[0].mat.vals;
     for (int i = 0; i < ctx->levels && ctx->mat_gamma > 0.f; ++i) {
         const LevelWs& L = ctx->lv[i];
         la.lv[i].mat_partial = L.mat.partial; la.lv[i].mat_tiles = L.mat.tiles; la.lv[i].mat_n = mat_n(ctx, L);
     }
     for (int k = 0; k < ctx->lap_k; ++k) la.lap_gamma[k] = ctx->lap_gamma[k];
-    la.mom_on = ctx->mom_on() ? 1 : 0; la.mom_out = ctx->mom_vals; la.mom_stride = MOM_STAT_STRIDE;
+    la.mom_on = ctx->mom_on() ? 1 : 0; la.mom_out = ctx->lv[0].mom.vals; la.mom_stride = MOM_STAT_STRIDE;
     for (int k = 0; k < ctx->taps.nstyle && la.mom_on; ++k) {
         la.mom_wm[k] = ctx->mom_wm_of(k); la.mom_ws[k] = ctx->mom_ws_of(k); la.mom_index[k] = tap_index_of(ctx->taps.style[k]);
     }
@@ -1065,10 +1065,10 @@ int closure_record(nst_ctx* ctx, const float* x, float cw, float sw, float tvw, 
     xi[0] = x; gi[0] = grad;
     for (int i = 1; i < ctx->levels; ++i) {
         LevelWs& L = ctx->lv[i];
-        xi[i] = L.xl; gi[i] = L.gxl;
+        xi[i] = L.img.xl; gi[i] = L.img.gxl;
         if (half == BACKWARD) continue;      // (the forward half left the level images in place)
         Timer t(ctx, main, K_OTHER, 0);
-        HIPCHK(ctx, launch_bicubic_down(xi[i - 1], ctx->channels, ctx->lv[i - 1].h, ctx->lv[i - 1].w, L.h, L.w, L.xl, main));
+        HIPCHK(ctx, launch_bicubic_down(xi[i - 1], ctx->channels, ctx->lv[i - 1].h, ctx->lv[i - 1].w, L.h, L.w, L.img.xl, main));
     }
     // the levels in `mask` on stream s
     auto batched = [&](unsigned mask, hipStream_t s, unsigned zero_mask) -> int {
@@ -1363,7 +1363,7 @@ int nst_level_set_guidance(nst_ctx* ctx, int level, int R, const float* planes, 
     LevelWs& L = ctx->lv[level];
     if (R == 0) {                       // (in every arithmetic mode: there is nothing to clear in the others)
         quiesce(ctx);
-        free_guidance(ctx, L);
+        L.guide = Guidance();
         return NST_OK;
     }
     if (ctx->conv_mode != 2) return fail(ctx, NST_E_STATE, "spatial control runs in the f16x2 arithmetic only (NST_CONV unset)");
@@ -1380,61 +1380,51 @@ int nst_level_set_guidance(nst_ctx* ctx, int level, int R, const float* planes, 
     if (!positive) return fail(ctx, NST_E_ARG, "at least one region weight must be positive");
     hipStream_t s = enter(ctx, stream);
     const Taps& tp = ctx->taps;
-    // the new pyramid and its masses beside what the level has: a refusal leaves the level as it was
-    LevelWs tmp;
-    Guidance& g = tmp.guide;
-    auto refuse = [&](int code, const char* msg) { const int rc = msg ? fail(ctx, code, msg) : code; free_guidance(ctx, tmp); return rc; };
-    auto take = [&](auto** p, size_t count) -> int {
-        const int rc = dev_alloc_t(ctx, p, count);
-        if (rc == NST_OK) g.bytes += std::max<size_t>(count * sizeof(**p), 16);
-        return rc;
-    };
+    // the new pyramid and its masses beside what the level has: a refusal leaves the level as it was (g gives back what it
+    // took on every path out)
+    Guidance g;
     size_t off[6];
     guidance_offsets(R, L.h, L.w, off);
     g.R = R; g.plane_floats = off[5];
     for (int sc = 0; sc < 5; ++sc) g.plane_off[sc] = off[sc];
     for (int r = 0; r < NST_MAX_REGIONS; ++r) g.lambda[r] = lam[r];
-    int rc = take(&g.planes, g.plane_floats);
-    if (rc != NST_OK) return refuse(rc, nullptr);
+    NSTCHK(g.mem.alloc(ctx, &g.planes, g.plane_floats));
     double bad = 0.0;
     {
         Scratch sc(ctx, s);
         double* dscratch = nullptr;
-        rc = sc.alloc(&dscratch, ((size_t)R * GUIDE_MASS_BLOCKS + 5 * R) * 2);
-        if (rc == NST_OK && hipMemcpyAsync(g.planes, planes, (size_t)R * L.h * L.w * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
-            rc = fail(ctx, NST_E_HIP, "hipMemcpyAsync of the guidance planes failed");
-        if (rc == NST_OK) rc = build_guidance(ctx, g.planes, off, R, L.h, L.w, dscratch, g.mass, &bad, s);
-        if (rc == NST_OK) rc = sc.finish();
-        if (rc != NST_OK) return refuse(rc, nullptr);
+        NSTCHK(sc.alloc(&dscratch, ((size_t)R * GUIDE_MASS_BLOCKS + 5 * R) * 2));
+        if (hipMemcpyAsync(g.planes, planes, (size_t)R * L.h * L.w * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
+            return fail(ctx, NST_E_HIP, "hipMemcpyAsync of the guidance planes failed");
+        NSTCHK(build_guidance(ctx, g.planes, off, R, L.h, L.w, dscratch, g.mass, &bad, s));
+        NSTCHK(sc.finish());
     }
-    if (bad > 0.0) return refuse(NST_E_ARG, "guidance values must be finite and in [0,1]");
+    if (bad > 0.0) return fail(ctx, NST_E_ARG, "guidance values must be finite and in [0,1]");
     if (!guidance_mass_ok(tp, g.mass, R))
-        return refuse(NST_E_ARG, "a region has a mass sum t^2 below 1 on a map in use: less than one pixel's worth of guidance");
+        return fail(ctx, NST_E_ARG, "a region has a mass sum t^2 below 1 on a map in use: less than one pixel's worth of guidance");
     Guidance& old = L.guide;
     if (old.R == R) {
         // same R: the workspace and the guided targets (which depend on the style side only) stay, the planes change
         quiesce(ctx);
-        std::swap(old.planes, g.planes);      // (planes of the same size: both byte counts stay)
+        old.mem.exchange(old.planes, g.mem, g.planes);
+        std::swap(old.planes, g.planes);
         for (int sc = 0; sc < 5; ++sc)
             for (int r = 0; r < NST_MAX_REGIONS; ++r) old.mass[sc][r] = g.mass[sc][r];
         for (int r = 0; r < NST_MAX_REGIONS; ++r) old.lambda[r] = g.lambda[r];
-        free_guidance(ctx, tmp);
+        g = Guidance();
         mark(ctx, s);
         return NST_OK;
     }
     g.part_floats_r = gram_part_floats_for(tp, L.h, L.w);
-    rc = take(&g.part, (size_t)R * g.part_floats_r);
-    for (int q = 0; q < tp.nstyle && rc == NST_OK; ++q) {
+    NSTCHK(g.mem.alloc(ctx, &g.part, (size_t)R * g.part_floats_r));
+    for (int q = 0; q < tp.nstyle; ++q) {
         const size_t C = (size_t)kCout[tp.style[q]];
-        rc = take(&g.gram_t[q], (size_t)R * C * C);
-        if (rc == NST_OK) rc = take(&g.S[q], (size_t)R * C * C);
-        if (rc == NST_OK) rc = take(&g.partial[q], (size_t)R * gram_finish_blocks((int)C));
+        NSTCHK(g.mem.alloc(ctx, &g.gram_t[q], (size_t)R * C * C));
+        NSTCHK(g.mem.alloc(ctx, &g.S[q], (size_t)R * C * C));
+        NSTCHK(g.mem.alloc(ctx, &g.partial[q], (size_t)R * gram_finish_blocks((int)C)));
     }
-    if (rc != NST_OK) return refuse(rc, nullptr);
     quiesce(ctx);
-    free_guidance(ctx, L);
-    L.guide = g;
-    tmp.guide = Guidance();
+    L.guide = std::move(g);
     mark(ctx, s);
     return NST_OK;
 }

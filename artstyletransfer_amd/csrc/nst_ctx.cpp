@@ -59,32 +59,33 @@ extern "C" int nst_internal_zero_now(void* p, size_t bytes) {
 
 namespace nst {
 
-int dev_alloc(nst_ctx* ctx, void** p, size_t bytes) {
+int dev_alloc(nst_ctx* ctx, void** p, size_t bytes, size_t* charged) {
     if (bytes == 0) bytes = 16;
     hipError_t e = hipMalloc(p, bytes);
     if (e != hipSuccess) return fail(ctx, NST_E_NOMEM, std::string("hipMalloc(") + std::to_string(bytes) + "): " + hipGetErrorString(e));
     poison_if_asked(*p, bytes);
     ctx->bytes += bytes;
+    if (charged) *charged = bytes;
     return NST_OK;
+}
+void dev_release(nst_ctx* ctx, void* p, size_t bytes) {
+    (void)hipFree(p);
+    ctx->bytes -= bytes;
 }
 
 int alloc_acts(nst_ctx* ctx, ActSet& a, int h, int w) {
-    a.bytes = 0;
     for (int l = 0; l < NL; ++l) {
         a.h[l] = h >> kScale[l];
         a.w[l] = w >> kScale[l];
         if (a.h[l] < 1 || a.w[l] < 1) return fail(ctx, NST_E_ARG, "image too small for VGG19 (needs >= 16 px per side)");
         const size_t n = (size_t)a.h[l] * a.w[l] * kCout[l];
-        NSTCHK(dev_alloc_t(ctx, &a.act[l], n));
-        a.bytes += n * 4;
+        NSTCHK(a.mem.alloc(ctx, &a.act[l], n));
     }
     for (int k = 0; k < 4; ++k) {
         const int l = kPoolAfter[k];
         const size_t n = (size_t)(a.h[l] / 2) * (a.w[l] / 2) * kCout[l];
-        NSTCHK(dev_alloc_t(ctx, &a.pool[k], n));
-        a.bytes += n * 4;
-        NSTCHK(dev_alloc_t(ctx, &a.pcode[k], n / 8));          // n / 32 channel groups x 4 words
-        a.bytes += n / 8 * 4;
+        NSTCHK(a.mem.alloc(ctx, &a.pool[k], n));
+        NSTCHK(a.mem.alloc(ctx, &a.pcode[k], n / 8));          // n / 32 channel groups x 4 words
     }
     size_t need = 0;
     for (int l = 1; l < NL; ++l) {
@@ -101,27 +102,13 @@ int alloc_acts(nst_ctx* ctx, ActSet& a, int h, int w) {
     for (int k = 0; k < 9; ++k) {
         const int m = mask_layers[k];
         const size_t nw = (size_t)a.h[m] * a.w[m] * (kCout[m] / 32);
-        NSTCHK(dev_alloc_t(ctx, &a.bits[m], nw));
-        a.bytes += nw * 4;
+        NSTCHK(a.mem.alloc(ctx, &a.bits[m], nw));
     }
-    NSTCHK(dev_alloc_t(ctx, &a.amax, (size_t)AMAX_IDS * NST_AMAX_SLOTS));
-    a.bytes += (size_t)AMAX_IDS * NST_AMAX_SLOTS * 4;
+    NSTCHK(a.mem.alloc(ctx, &a.amax, (size_t)AMAX_IDS * NST_AMAX_SLOTS));
     if (nst_internal_zero_now(a.amax, (size_t)AMAX_IDS * NST_AMAX_SLOTS * 4)) return fail(ctx, NST_E_HIP, "hipMemset failed");
     a.splitk_floats = need;
-    if (need) {
-        NSTCHK(dev_alloc_t(ctx, &a.splitk, need));
-        a.bytes += need * 4;
-    }
+    if (need) NSTCHK(a.mem.alloc(ctx, &a.splitk, need));
     return NST_OK;
-}
-void free_acts(nst_ctx* ctx, ActSet& a) {
-    for (int l = 0; l < NL; ++l) { dev_free(a.act[l]); a.act[l] = nullptr; }
-    for (int k = 0; k < 4; ++k) { dev_free(a.pool[k]); a.pool[k] = nullptr; dev_free(a.pcode[k]); a.pcode[k] = nullptr; }
-    dev_free(a.splitk); a.splitk = nullptr; a.splitk_floats = 0;
-    dev_free(a.amax); a.amax = nullptr;
-    for (int l = 0; l < NL; ++l) { dev_free(a.bits[l]); a.bits[l] = nullptr; a.bits_valid[l] = false; }
-    if (ctx->bytes >= a.bytes) ctx->bytes -= a.bytes;
-    a.bytes = 0;
 }
 
 }  // namespace nst
@@ -271,102 +258,47 @@ void make_wino(const float* w, int rows, int K, std::vector<uint16_t>& out, floa
                         }
 }
 
-// the buffers whose size depends on the taps: content target, Gram targets / factors / partial sums, partial-Gram workspace
-void free_tap_buffers(nst_ctx* ctx, LevelWs& L) {
-    auto drop = [&](void* p, size_t bytes) { if (p) { dev_free(p); if (ctx->bytes >= bytes) ctx->bytes -= bytes; } };
-    drop(L.content_t, L.content_n * 4); L.content_t = nullptr; L.content_n = 0;
-    for (int k = 0; k < kMaxStyle; ++k) {
-        const size_t C = (size_t)L.tap_c[k];
-        drop(L.gram_t[k], C * C * 4); drop(L.S[k], C * C * 4); drop(L.S_bf[k], C * C * 6);
-        drop(L.style_partial[k], (size_t)gram_finish_blocks((int)std::max<size_t>(C, 1)) * 8);
-        L.gram_t[k] = nullptr; L.S[k] = nullptr; L.S_bf[k] = nullptr; L.style_partial[k] = nullptr; L.tap_c[k] = 0;
-    }
-    drop(L.gram_part, L.gram_part_floats * 4); L.gram_part = nullptr; L.gram_part_floats = 0;
+// the tap-sized buffers of a level (LevelWs has the list), for the context's current taps
+void free_tap_buffers(LevelWs& L) {
+    L.tap_mem.release();
+    L.content_t = nullptr; L.content_n = 0;
+    for (int k = 0; k < kMaxStyle; ++k) { L.gram_t[k] = nullptr; L.S[k] = nullptr; L.S_bf[k] = nullptr; L.style_partial[k] = nullptr; }
+    L.gram_part = nullptr; L.gram_part_floats = 0;
 }
 int alloc_tap_buffers(nst_ctx* ctx, LevelWs& L) {
     const Taps& tp = ctx->taps;
     const int m = tp.content;
     L.content_n = (size_t)L.acts.h[m] * L.acts.w[m] * kCout[m];
-    NSTCHK(dev_alloc_t(ctx, &L.content_t, L.content_n));
+    NSTCHK(L.tap_mem.alloc(ctx, &L.content_t, L.content_n));
     for (int k = 0; k < tp.nstyle; ++k) {
         const int C = kCout[tp.style[k]];
-        L.tap_c[k] = C;
-        NSTCHK(dev_alloc_t(ctx, &L.gram_t[k], (size_t)C * C));
-        NSTCHK(dev_alloc_t(ctx, &L.S[k], (size_t)C * C));
-        NSTCHK(dev_alloc_t(ctx, &L.S_bf[k], (size_t)C * C * 3));
-        NSTCHK(dev_alloc_t(ctx, &L.style_partial[k], gram_finish_blocks(C)));
+        NSTCHK(L.tap_mem.alloc(ctx, &L.gram_t[k], (size_t)C * C));
+        NSTCHK(L.tap_mem.alloc(ctx, &L.S[k], (size_t)C * C));
+        NSTCHK(L.tap_mem.alloc(ctx, &L.S_bf[k], (size_t)C * C * 3));
+        NSTCHK(L.tap_mem.alloc(ctx, &L.style_partial[k], gram_finish_blocks(C)));
     }
     L.gram_part_floats = gram_part_floats_for(tp, L.h, L.w);
-    NSTCHK(dev_alloc_t(ctx, &L.gram_part, L.gram_part_floats));
+    NSTCHK(L.tap_mem.alloc(ctx, &L.gram_part, L.gram_part_floats));
     return NST_OK;
 }
 
-// the level image and its gradient (levels >= 1): their size follows the channel count (nst_job_set_color)
-void free_level_image(nst_ctx* ctx, LevelWs& L) {
-    for (float** p : {&L.xl, &L.gxl}) {
-        if (*p) { dev_free(*p); if (ctx->bytes >= L.xl_floats * 4) ctx->bytes -= L.xl_floats * 4; }
-        *p = nullptr;
-    }
-    L.xl_floats = 0;
-}
-int alloc_level_image(nst_ctx* ctx, LevelWs& L) {
-    L.xl_floats = (size_t)ctx->channels * L.h * L.w;
-    NSTCHK(dev_alloc_t(ctx, &L.xl, L.xl_floats));
-    NSTCHK(dev_alloc_t(ctx, &L.gxl, L.xl_floats));
+// the level image and its gradient of an h x w level under `channels` (nst_job_set_color)
+int alloc_level_image(nst_ctx* ctx, LevelImage& im, int channels, int h, int w) {
+    const size_t n = (size_t)channels * h * w;
+    NSTCHK(im.mem.alloc(ctx, &im.xl, n));
+    NSTCHK(im.mem.alloc(ctx, &im.gxl, n));
     return NST_OK;
 }
 
-void free_level(nst_ctx* ctx, LevelWs& L) {
-    free_guidance(ctx, L);
-    free_laplacian(ctx, L);
-    free_matting(ctx, L);
-    free_gram_shift(ctx, L);
-    free_moments(ctx, L);
-    free_acts(ctx, L.acts);
-    dev_free(L.gbuf[0]); dev_free(L.gbuf[1]); dev_free(L.xl); dev_free(L.gxl);
-    free_tap_buffers(ctx, L);
-    dev_free(L.content_partial); dev_free(L.tv_partial); dev_free(L.tv_means);
+void free_level(LevelWs& L) {
     if (L.stream) (void)hipStreamDestroy(L.stream);
     if (L.done) (void)hipEventDestroy(L.done);
-    L = LevelWs();
+    L = LevelWs();      // (every member's DevMem gives back what it holds)
 }
 
 }  // namespace
 
 namespace nst {
-
-void free_guidance(nst_ctx* ctx, LevelWs& L) {
-    Guidance& g = L.guide;
-    dev_free(g.planes); dev_free(g.part);
-    for (int k = 0; k < kMaxStyle; ++k) { dev_free(g.gram_t[k]); dev_free(g.S[k]); dev_free(g.partial[k]); }
-    if (ctx->bytes >= g.bytes) ctx->bytes -= g.bytes;
-    g = Guidance();
-}
-
-void free_laplacian(nst_ctx* ctx, LevelWs& L) {
-    LapLevel& q = L.lap;
-    for (int k = 0; k < NST_LAP_MAX; ++k) { dev_free(q.s[k]); dev_free(q.r[k]); dev_free(q.target[k]); dev_free(q.partial[k]); }
-    if (ctx->bytes >= q.bytes) ctx->bytes -= q.bytes;
-    q = LapLevel();
-}
-
-void free_matting(nst_ctx* ctx, LevelWs& L) {
-    dev_free(L.mat.guide); dev_free(L.mat.partial);
-    if (ctx->bytes >= L.mat.bytes) ctx->bytes -= L.mat.bytes;
-    L.mat = MatLevel();
-}
-
-void free_gram_shift(nst_ctx* ctx, LevelWs& L) {
-    dev_free(L.gs.words); dev_free(L.gs.sums);
-    if (ctx->bytes >= L.gs.bytes) ctx->bytes -= L.gs.bytes;
-    L.gs = GramShiftLevel();
-}
-
-void free_moments(nst_ctx* ctx, LevelWs& L) {
-    dev_free(L.mom.words); dev_free(L.mom.stats); dev_free(L.mom.sums);
-    if (ctx->bytes >= L.mom.bytes) ctx->bytes -= L.mom.bytes;
-    L.mom = MomentLevel();
-}
 
 // What a closure remembered is void once the job changes: the captured graph and the keys it was captured under, and
 // (drop_targets) every level's targets
@@ -467,6 +399,13 @@ unsigned style_mask_of(const Taps& tp) {
     return m;
 }
 
+// An optional term's per-level block replaced by what fill builds (an untouched block: the term is off), every buffer
+// allocated beside the old ones: a refusal changes nothing; else every level's targets and the captured closure go
+template <typename Block, typename Fill>
+int replace_term(nst_ctx* ctx, Block LevelWs::*member, Fill fill) {
+    return replace_blocks(ctx->lv, ctx->levels, member, fill, [&] { quiesce(ctx); drop_closure_state(ctx, true); });
+}
+
 }  // namespace
 
 // ================================================================================================
@@ -552,7 +491,7 @@ int nst_ctx_create_ex(int device, const float* const* weights, const float* cons
     std::vector<float> tmp;
     std::vector<uint16_t> tmp16;
     auto upload = [&](auto& dst, const void* src, size_t bytes, const char* what) -> int {      // a device copy of host data
-        if (dev_alloc(ctx, reinterpret_cast<void**>(&dst), bytes) != NST_OK) return NST_E_NOMEM;
+        if (ctx->mem.alloc_bytes(ctx, reinterpret_cast<void**>(&dst), bytes) != NST_OK) return NST_E_NOMEM;
         if (hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) != hipSuccess) { ctx->err = std::string(what) + " upload failed"; return NST_E_HIP; }
         return NST_OK;
     };
@@ -630,10 +569,9 @@ void nst_ctx_destroy(nst_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     quiesce(ctx);
-    for (int i = 0; i < NST_MAX_LEVELS; ++i) free_level(ctx, ctx->lv[i]);
+    for (int i = 0; i < NST_MAX_LEVELS; ++i) free_level(ctx->lv[i]);
     if (ctx->tail) (void)hipEventDestroy(ctx->tail);
-    for (int l = 0; l < NL; ++l) { dev_free(ctx->wf[l]); dev_free(ctx->wd[l]); dev_free(ctx->bias[l]); dev_free(ctx->wf_bf[l]); dev_free(ctx->wd_bf[l]); dev_free(ctx->wf_h2[l]); dev_free(ctx->wd_h2[l]); dev_free(ctx->wf_wino[l]); dev_free(ctx->wd_wino[l]); }
-    dev_free(ctx->w11k); dev_free(ctx->w11d); dev_free(ctx->color_scratch); dev_free(ctx->lap_vals); dev_free(ctx->mat_vals); dev_free(ctx->mom_vals);
+    ctx->mem.release();
     drop_closure_state(ctx, false);
     if (ctx->gstream) (void)hipStreamDestroy(ctx->gstream);
     if (ctx->side) (void)hipStreamDestroy(ctx->side);
@@ -661,7 +599,7 @@ int nst_job_configure(nst_ctx* ctx, int levels_num, int H0, int W0) {
     if ((H0 >> (levels_num - 1)) < 16 || (W0 >> (levels_num - 1)) < 16)
         return fail(ctx, NST_E_ARG, "coarsest pyramid level must be at least 16x16");
     quiesce(ctx);
-    for (int i = 0; i < NST_MAX_LEVELS; ++i) free_level(ctx, ctx->lv[i]);      // (the targets go with the levels)
+    for (int i = 0; i < NST_MAX_LEVELS; ++i) free_level(ctx->lv[i]);      // (the targets go with the levels)
     drop_closure_state(ctx, false);
     forget_forward_pass(ctx);
     ctx->levels = 0;
@@ -677,13 +615,13 @@ int nst_job_configure(nst_ctx* ctx, int levels_num, int H0, int W0) {
         L.h = h; L.w = w;
         NSTCHK(alloc_acts(ctx, L.acts, h, w));
         L.gbuf_floats = (size_t)h * w * 64;
-        NSTCHK(dev_alloc_t(ctx, &L.gbuf[0], L.gbuf_floats));
-        NSTCHK(dev_alloc_t(ctx, &L.gbuf[1], L.gbuf_floats));
-        if (i > 0) NSTCHK(alloc_level_image(ctx, L));      // sized for the context's current channel count
+        NSTCHK(L.mem.alloc(ctx, &L.gbuf[0], L.gbuf_floats));
+        NSTCHK(L.mem.alloc(ctx, &L.gbuf[1], L.gbuf_floats));
+        if (i > 0) NSTCHK(alloc_level_image(ctx, L.img, ctx->channels, h, w));
         NSTCHK(alloc_tap_buffers(ctx, L));       // sized for the context's current taps
-        NSTCHK(dev_alloc_t(ctx, &L.content_partial, MSE_BLOCKS));
-        NSTCHK(dev_alloc_t(ctx, &L.tv_partial, 2 * TV_BLOCKS));
-        NSTCHK(dev_alloc_t(ctx, &L.tv_means, 2));
+        NSTCHK(L.mem.alloc(ctx, &L.content_partial, MSE_BLOCKS));
+        NSTCHK(L.mem.alloc(ctx, &L.tv_partial, 2 * TV_BLOCKS));
+        NSTCHK(L.mem.alloc(ctx, &L.tv_means, 2));
         h /= 2; w /= 2;
     }
     ctx->levels = levels_num;
@@ -716,8 +654,8 @@ int nst_job_set_taps(nst_ctx* ctx, int content_index, unsigned style_mask, int u
     ctx->taps = tp;
     for (int i = 0; i < ctx->levels; ++i) {
         LevelWs& L = ctx->lv[i];
-        free_guidance(ctx, L);          // (sized for the old style set: nst_level_set_guidance again)
-        free_tap_buffers(ctx, L);
+        L.guide = Guidance();           // (sized for the old style set: nst_level_set_guidance again)
+        free_tap_buffers(L);
         NSTCHK(alloc_tap_buffers(ctx, L));
     }
     return NST_OK;
@@ -733,29 +671,11 @@ int nst_job_set_color(nst_ctx* ctx, int mode) {
     quiesce(ctx);
     // the level images of the new channel count first: if one cannot be had, the context stays as it was (old mode, old
     // buffers, targets kept)
-    float* img[NST_MAX_LEVELS][2] = {};
-    int r = NST_OK;
-    for (int i = 1; i < ctx->levels && r == NST_OK; ++i) {
-        const size_t n = (size_t)channels * ctx->lv[i].h * ctx->lv[i].w;
-        r = dev_alloc_t(ctx, &img[i][0], n);
-        if (r == NST_OK) r = dev_alloc_t(ctx, &img[i][1], n);
-    }
-    if (r != NST_OK) {
-        for (int i = 1; i < ctx->levels; ++i) {
-            const size_t bytes = (size_t)channels * ctx->lv[i].h * ctx->lv[i].w * 4;
-            for (float* p : img[i])
-                if (p) { dev_free(p); if (ctx->bytes >= bytes) ctx->bytes -= bytes; }
-        }
-        return r;
-    }
-    drop_closure_state(ctx, true);
+    LevelWs* lv = ctx->lv + 1;
+    NSTCHK(replace_blocks(lv, ctx->levels - 1, &LevelWs::img,
+                          [&](int i, LevelImage& im) { return alloc_level_image(ctx, im, channels, lv[i].h, lv[i].w); },
+                          [&] { drop_closure_state(ctx, true); }));
     ctx->channels = channels;
-    for (int i = 1; i < ctx->levels; ++i) {
-        LevelWs& L = ctx->lv[i];
-        free_level_image(ctx, L);
-        L.xl = img[i][0]; L.gxl = img[i][1];
-        L.xl_floats = (size_t)channels * L.h * L.w;
-    }
     return NST_OK;
 }
 
@@ -841,42 +761,23 @@ int nst_job_set_laplacian(nst_ctx* ctx, int K, const int* pool, const float* gam
                                             ": the pooled image must be at least 3x3");
     }
     if (K > 0 && !positive) return fail(ctx, NST_E_ARG, "at least one Laplacian weight must be positive");
-    // the new buffers beside the old ones: a failed allocation leaves the context as it was
-    LapLevel fresh[NST_MAX_LEVELS];
-    int rc = NST_OK;
-    if (K > 0 && !ctx->lap_vals) rc = dev_alloc_t(ctx, &ctx->lap_vals, (size_t)NST_MAX_LEVELS * NST_LAP_MAX);
-    for (int i = 0; i < ctx->levels && rc == NST_OK; ++i) {
-        LapLevel& q = fresh[i];
-        auto take = [&](auto** p, size_t count) -> int {
-            const int r = dev_alloc_t(ctx, p, count);
-            if (r == NST_OK) q.bytes += std::max<size_t>(count * sizeof(**p), 16);
-            return r;
-        };
-        for (int k = 0; k < K && rc == NST_OK; ++k) {
+    NSTCHK(replace_term(ctx, &LevelWs::lap, [&](int i, LapLevel& q) {
+        if (K > 0 && i == 0) NSTCHK(q.mem.alloc(ctx, &q.vals, (size_t)NST_MAX_LEVELS * NST_LAP_MAX));
+        for (int k = 0; k < K; ++k) {
             const size_t hk = (size_t)(ctx->lv[i].h / pool[k]), wk = (size_t)(ctx->lv[i].w / pool[k]);
-            rc = take(&q.s[k], hk * wk);
-            if (rc == NST_OK) rc = take(&q.r[k], (hk - 2) * (wk - 2));
-            if (rc == NST_OK) rc = take(&q.target[k], (hk - 2) * (wk - 2));
-            if (rc == NST_OK) rc = take(&q.partial[k], LAP_BLOCKS);
+            NSTCHK(q.mem.alloc(ctx, &q.s[k], hk * wk));
+            NSTCHK(q.mem.alloc(ctx, &q.r[k], (hk - 2) * (wk - 2)));
+            NSTCHK(q.mem.alloc(ctx, &q.target[k], (hk - 2) * (wk - 2)));
+            NSTCHK(q.mem.alloc(ctx, &q.partial[k], LAP_BLOCKS));
         }
-    }
-    if (rc != NST_OK) {
-        LevelWs tmp;
-        for (int i = 0; i < ctx->levels; ++i) { tmp.lap = fresh[i]; free_laplacian(ctx, tmp); }
-        return rc;
-    }
-    quiesce(ctx);
-    drop_closure_state(ctx, true);
-    for (int i = 0; i < ctx->levels; ++i) {
-        free_laplacian(ctx, ctx->lv[i]);
-        ctx->lv[i].lap = fresh[i];
-    }
+        return NST_OK;
+    }));
     ctx->lap_k = K;
     for (int k = 0; k < NST_LAP_MAX; ++k) {
         ctx->lap_pool[k] = k < K ? pool[k] : 0;
         ctx->lap_gamma[k] = k < K ? gamma[k] : 0.f;
     }
-    if (ctx->lap_vals) HIPCHK(ctx, hipMemset(ctx->lap_vals, 0, (size_t)NST_MAX_LEVELS * NST_LAP_MAX * sizeof(float)));
+    if (K > 0) HIPCHK(ctx, hipMemset(ctx->lv[0].lap.vals, 0, (size_t)NST_MAX_LEVELS * NST_LAP_MAX * sizeof(float)));
     return NST_OK;
 }
 
@@ -898,7 +799,7 @@ int nst_job_laplacian_losses(nst_ctx* ctx, float* out, void* stream) {
     if (!out) return fail(ctx, NST_E_ARG, "null argument");
     hipStream_t s = enter(ctx, stream);
     const size_t bytes = (size_t)ctx->levels * NST_LAP_MAX * sizeof(float);
-    if (ctx->lap_k > 0 && ctx->lap_vals) HIPCHK(ctx, hipMemcpyAsync(out, ctx->lap_vals, bytes, hipMemcpyDeviceToDevice, s));
+    if (ctx->lap_k > 0) HIPCHK(ctx, hipMemcpyAsync(out, ctx->lv[0].lap.vals, bytes, hipMemcpyDeviceToDevice, s));
     else HIPCHK(ctx, hipMemsetAsync(out, 0, bytes, s));
     mark(ctx, s);
     return NST_OK;
@@ -914,33 +815,18 @@ int nst_job_set_matting(nst_ctx* ctx, float gamma, double epsilon) {
     if (!(gamma >= 0.f) || std::isinf(gamma)) return fail(ctx, NST_E_ARG, "the matting weight must be finite and >= 0");
     if (!(epsilon > 0.0) || std::isinf(epsilon)) return fail(ctx, NST_E_ARG, "the matting epsilon must be finite and > 0");
     const bool on = gamma > 0.f;
-    // the new buffers beside the old ones: a failed allocation leaves the context as it was
-    MatLevel fresh[NST_MAX_LEVELS];
-    int rc = NST_OK;
-    if (on && !ctx->mat_vals) rc = dev_alloc_t(ctx, &ctx->mat_vals, (size_t)NST_MAX_LEVELS);
-    for (int i = 0; on && i < ctx->levels && rc == NST_OK; ++i) {
-        MatLevel& q = fresh[i];
+    NSTCHK(replace_term(ctx, &LevelWs::mat, [&](int i, MatLevel& q) {
+        if (!on) return NST_OK;
+        if (i == 0) NSTCHK(q.mem.alloc(ctx, &q.vals, (size_t)NST_MAX_LEVELS));
         const size_t px = (size_t)ctx->lv[i].h * ctx->lv[i].w;
         q.tiles = mat_tiles(ctx->lv[i].h, ctx->lv[i].w);
-        rc = dev_alloc_t(ctx, &q.guide, 3 * px);             // (three planes: a colour mode set later fits)
-        if (rc == NST_OK) q.bytes += std::max<size_t>(3 * px * sizeof(float), 16);
-        if (rc == NST_OK) rc = dev_alloc_t(ctx, &q.partial, (size_t)q.tiles);
-        if (rc == NST_OK) q.bytes += std::max<size_t>((size_t)q.tiles * sizeof(double), 16);
-    }
-    if (rc != NST_OK) {
-        LevelWs tmp;
-        for (int i = 0; i < ctx->levels; ++i) { tmp.mat = fresh[i]; free_matting(ctx, tmp); }
-        return rc;
-    }
-    quiesce(ctx);
-    drop_closure_state(ctx, true);
-    for (int i = 0; i < ctx->levels; ++i) {
-        free_matting(ctx, ctx->lv[i]);
-        ctx->lv[i].mat = fresh[i];
-    }
+        NSTCHK(q.mem.alloc(ctx, &q.guide, 3 * px));             // (three planes: a colour mode set later fits)
+        NSTCHK(q.mem.alloc(ctx, &q.partial, (size_t)q.tiles));
+        return NST_OK;
+    }));
     ctx->mat_gamma = gamma;
     ctx->mat_eps = epsilon;
-    if (ctx->mat_vals) HIPCHK(ctx, hipMemset(ctx->mat_vals, 0, (size_t)NST_MAX_LEVELS * sizeof(float)));
+    if (on) HIPCHK(ctx, hipMemset(ctx->lv[0].mat.vals, 0, (size_t)NST_MAX_LEVELS * sizeof(float)));
     return NST_OK;
 }
 
@@ -959,7 +845,7 @@ int nst_job_matting_losses(nst_ctx* ctx, float* out, void* stream) {
     if (!out) return fail(ctx, NST_E_ARG, "null argument");
     hipStream_t s = enter(ctx, stream);
     const size_t bytes = (size_t)ctx->levels * sizeof(float);
-    if (ctx->mat_gamma > 0.f && ctx->mat_vals) HIPCHK(ctx, hipMemcpyAsync(out, ctx->mat_vals, bytes, hipMemcpyDeviceToDevice, s));
+    if (ctx->mat_gamma > 0.f) HIPCHK(ctx, hipMemcpyAsync(out, ctx->lv[0].mat.vals, bytes, hipMemcpyDeviceToDevice, s));
     else HIPCHK(ctx, hipMemsetAsync(out, 0, bytes, s));
     mark(ctx, s);
     return NST_OK;
@@ -979,38 +865,22 @@ int nst_job_set_gram_shift(nst_ctx* ctx, const float* shift, unsigned center_mas
         if (((center_mask >> i) & 1u) && shift[i] != 0.f) return fail(ctx, NST_E_ARG, "a centred map takes no constant shift: its entry must be 0");
         on = on || shift[i] != 0.f;
     }
-    GramShiftLevel fresh[NST_MAX_LEVELS];
     if (on) {
         if (ctx->levels < 1) return fail(ctx, NST_E_STATE, "nst_job_configure has not been called");
         if (ctx->conv_mode != 2) return fail(ctx, NST_E_STATE, "the shifted Gram runs in the f16x2 arithmetic only (NST_CONV unset)");
         for (int i = 0; i < ctx->levels; ++i)
             if (ctx->lv[i].guide.R > 0)
                 return fail(ctx, NST_E_STATE, "guided Gram matrices take the plain statistic only (nst_level_set_guidance(ctx, level, 0, ...) clears the guidance)");
-        int rc = NST_OK;
-        for (int i = 0; i < ctx->levels && rc == NST_OK; ++i) {
-            GramShiftLevel& q = fresh[i];
-            rc = dev_alloc_t(ctx, &q.words, (size_t)kMaxStyle * GS_STRIDE);
-            if (rc == NST_OK) q.bytes += (size_t)kMaxStyle * GS_STRIDE * sizeof(float);
-            if (rc == NST_OK && center_mask) {
-                rc = dev_alloc_t(ctx, &q.sums, (size_t)kMaxStyle * GS_PART_DOUBLES);
-                if (rc == NST_OK) q.bytes += (size_t)kMaxStyle * GS_PART_DOUBLES * sizeof(double);
-            }
-            // (o reads as zeros until a closure has run: nst_level_gram_offsets)
-            if (rc == NST_OK && hipMemset(q.words, 0, (size_t)kMaxStyle * GS_STRIDE * sizeof(float)) != hipSuccess)
-                rc = fail(ctx, NST_E_HIP, "hipMemset of the Gram offsets failed");
-        }
-        if (rc != NST_OK) {
-            LevelWs tmp;
-            for (int i = 0; i < ctx->levels; ++i) { tmp.gs = fresh[i]; free_gram_shift(ctx, tmp); }
-            return rc;
-        }
     }
-    quiesce(ctx);
-    drop_closure_state(ctx, true);
-    for (int i = 0; i < ctx->levels; ++i) {
-        free_gram_shift(ctx, ctx->lv[i]);
-        ctx->lv[i].gs = fresh[i];
-    }
+    NSTCHK(replace_term(ctx, &LevelWs::gs, [&](int, GramShiftLevel& q) {
+        if (!on) return NST_OK;
+        NSTCHK(q.mem.alloc(ctx, &q.words, (size_t)kMaxStyle * GS_STRIDE));
+        if (center_mask) NSTCHK(q.mem.alloc(ctx, &q.sums, (size_t)kMaxStyle * GS_PART_DOUBLES));
+        // (o reads as zeros until a closure has run: nst_level_gram_offsets)
+        if (hipMemset(q.words, 0, (size_t)kMaxStyle * GS_STRIDE * sizeof(float)) != hipSuccess)
+            return fail(ctx, NST_E_HIP, "hipMemset of the Gram offsets failed");
+        return NST_OK;
+    }));
     for (int i = 0; i < 6; ++i) ctx->gs_shift[i] = shift[i];
     ctx->gs_center = center_mask;
     return NST_OK;
@@ -1050,7 +920,6 @@ int nst_job_set_moments(nst_ctx* ctx, const float* mean_w, const float* std_w, f
             return fail(ctx, NST_E_ARG, "moment weights must be finite and >= 0");
         on = on || mean_w[i] > 0.f || std_w[i] > 0.f;
     }
-    MomentLevel fresh[NST_MAX_LEVELS];
     if (on) {
         if (ctx->levels < 1) return fail(ctx, NST_E_STATE, "nst_job_configure has not been called");
         if (ctx->conv_mode != 2) return fail(ctx, NST_E_STATE, "the moment loss runs in the f16x2 arithmetic only (NST_CONV unset)");
@@ -1061,35 +930,21 @@ int nst_job_set_moments(nst_ctx* ctx, const float* mean_w, const float* std_w, f
         for (int i = 0; i < 6; ++i)
             if ((mean_w[i] > 0.f || std_w[i] > 0.f) && !((taps_mask >> i) & 1u))
                 return fail(ctx, NST_E_ARG, "a moment weight is positive on map " + std::to_string(i) + ", which is not a style map of the job (nst_job_set_taps)");
-        int rc = NST_OK;
-        if (!ctx->mom_vals) rc = dev_alloc_t(ctx, &ctx->mom_vals, (size_t)NST_MAX_LEVELS * 12);
-        for (int i = 0; i < ctx->levels && rc == NST_OK; ++i) {
-            MomentLevel& q = fresh[i];
-            rc = dev_alloc_t(ctx, &q.words, (size_t)kMaxStyle * MOM_STRIDE);
-            if (rc == NST_OK) q.bytes += (size_t)kMaxStyle * MOM_STRIDE * sizeof(float);
-            if (rc == NST_OK) rc = dev_alloc_t(ctx, &q.stats, (size_t)kMaxStyle * MOM_STAT_STRIDE);
-            if (rc == NST_OK) q.bytes += (size_t)kMaxStyle * MOM_STAT_STRIDE * sizeof(double);
-            if (rc == NST_OK) rc = dev_alloc_t(ctx, &q.sums, (size_t)kMaxStyle * MOM_PART_DOUBLES);
-            if (rc == NST_OK) q.bytes += (size_t)kMaxStyle * MOM_PART_DOUBLES * sizeof(double);
-            if (rc == NST_OK && (hipMemset(q.words, 0, (size_t)kMaxStyle * MOM_STRIDE * sizeof(float)) != hipSuccess ||
-                                 hipMemset(q.stats, 0, (size_t)kMaxStyle * MOM_STAT_STRIDE * sizeof(double)) != hipSuccess))
-                rc = fail(ctx, NST_E_HIP, "hipMemset of the moment buffers failed");
-        }
-        if (rc != NST_OK) {
-            LevelWs tmp;
-            for (int i = 0; i < ctx->levels; ++i) { tmp.mom = fresh[i]; free_moments(ctx, tmp); }
-            return rc;
-        }
     }
-    quiesce(ctx);
-    drop_closure_state(ctx, true);
-    for (int i = 0; i < ctx->levels; ++i) {
-        free_moments(ctx, ctx->lv[i]);
-        ctx->lv[i].mom = fresh[i];
-    }
+    NSTCHK(replace_term(ctx, &LevelWs::mom, [&](int i, MomentLevel& q) {
+        if (!on) return NST_OK;
+        if (i == 0) NSTCHK(q.mem.alloc(ctx, &q.vals, (size_t)NST_MAX_LEVELS * 12));
+        NSTCHK(q.mem.alloc(ctx, &q.words, (size_t)kMaxStyle * MOM_STRIDE));
+        NSTCHK(q.mem.alloc(ctx, &q.stats, (size_t)kMaxStyle * MOM_STAT_STRIDE));
+        NSTCHK(q.mem.alloc(ctx, &q.sums, (size_t)kMaxStyle * MOM_PART_DOUBLES));
+        if (hipMemset(q.words, 0, (size_t)kMaxStyle * MOM_STRIDE * sizeof(float)) != hipSuccess ||
+            hipMemset(q.stats, 0, (size_t)kMaxStyle * MOM_STAT_STRIDE * sizeof(double)) != hipSuccess)
+            return fail(ctx, NST_E_HIP, "hipMemset of the moment buffers failed");
+        return NST_OK;
+    }));
     for (int i = 0; i < 6; ++i) { ctx->mom_wm[i] = mean_w[i]; ctx->mom_ws[i] = std_w[i]; }
     ctx->mom_eps = epsilon;
-    if (ctx->mom_vals) HIPCHK(ctx, hipMemset(ctx->mom_vals, 0, (size_t)NST_MAX_LEVELS * 12 * sizeof(float)));
+    if (on) HIPCHK(ctx, hipMemset(ctx->lv[0].mom.vals, 0, (size_t)NST_MAX_LEVELS * 12 * sizeof(float)));
     return NST_OK;
 }
 
@@ -1111,7 +966,7 @@ int nst_job_moment_losses(nst_ctx* ctx, float* out, void* stream) {
     if (!out) return fail(ctx, NST_E_ARG, "null argument");
     hipStream_t s = enter(ctx, stream);
     const size_t bytes = (size_t)ctx->levels * 12 * sizeof(float);
-    if (ctx->mom_on() && ctx->mom_vals) HIPCHK(ctx, hipMemcpyAsync(out, ctx->mom_vals, bytes, hipMemcpyDeviceToDevice, s));
+    if (ctx->mom_on()) HIPCHK(ctx, hipMemcpyAsync(out, ctx->lv[0].mom.vals, bytes, hipMemcpyDeviceToDevice, s));
     else HIPCHK(ctx, hipMemsetAsync(out, 0, bytes, s));
     mark(ctx, s);
     return NST_OK;

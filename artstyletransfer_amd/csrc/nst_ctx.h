@@ -5,13 +5,16 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/nst_hip.h"
 #include "nst_kernels.h"
 
 #pragma GCC visibility push(hidden)      // host-internal: none of this is a symbol of libnst_hip.so
+#include "nst_devmem.h"                  // (in here: its two functions are host-internal too)
 namespace nst {
 
 constexpr int NL = NST_VGG19_CONVS;
@@ -58,7 +61,7 @@ struct ActSet {                 // activations of one forward pass, NHWC
     // arg-max codes of the four max-pools (average pooling: the multi-hot ReLU-on codes), written by the fused pooling of the
     // f16x2 forward launches and read by the un-pooling loader of the input-gradient launch below each pool: [H/2*W/2][C/32][4] words
     unsigned* pcode[4] = {};
-    size_t bytes = 0;
+    DevMem mem;                  // owns every buffer above: `a = ActSet()` frees the set
     // a forward pass starts: nothing of the previous one's masks and fused pools is valid any more
     void begin_pass() {
         for (int l = 0; l < NL; ++l) bits_valid[l] = false;
@@ -114,7 +117,7 @@ struct Guidance {
     size_t part_floats_r = 0;
     bool targets = false;               // gram_t holds the targets of targets_R regions
     int targets_R = 0;
-    size_t bytes = 0;
+    DevMem mem;
     const float* plane(int scale, int r, int h, int w) const { return planes + plane_off[scale] + (size_t)r * (h >> scale) * (w >> scale); }
 };
 
@@ -126,7 +129,8 @@ struct LapLevel {
     float* r[NST_LAP_MAX] = {};
     double* target[NST_LAP_MAX] = {};
     double* partial[NST_LAP_MAX] = {};
-    size_t bytes = 0;
+    float* vals = nullptr;      // level 0 only: NST_MAX_LEVELS x NST_LAP_MAX, the unweighted lap_k of the last closure (the loss rows write it)
+    DevMem mem;
 };
 
 // The matting term of one level (nst_job_set_matting; include/nst_hip.h has the definition): the guide, a copy of the level's
@@ -136,7 +140,8 @@ struct MatLevel {
     float* guide = nullptr;
     double* partial = nullptr;
     int tiles = 0;
-    size_t bytes = 0;
+    float* vals = nullptr;      // level 0 only: NST_MAX_LEVELS, the unweighted mat of the last closure (the loss rows write it)
+    DevMem mem;
 };
 
 // The shifted / centred Gram statistic of one level (nst_job_set_gram_shift; include/nst_hip.h has the definition): per style
@@ -153,7 +158,7 @@ static_assert(maps_fit_gram_shift(), "a map wider than GS_MAX_C: the per-slot bu
 struct GramShiftLevel {
     float* words = nullptr;     // kMaxStyle x GS_STRIDE
     double* sums = nullptr;     // kMaxStyle x GS_PART_DOUBLES (only with a centred map)
-    size_t bytes = 0;
+    DevMem mem;
     float* offset(int q) const { return words + (size_t)q * GS_STRIDE; }
     float* row_bias(int q) const { return words + (size_t)q * GS_STRIDE + GS_MAX_C; }
     unsigned* amax(int q) const { return reinterpret_cast<unsigned*>(words + (size_t)q * GS_STRIDE + 2 * GS_MAX_C); }
@@ -171,13 +176,21 @@ struct MomentLevel {
     float* words = nullptr;     // kMaxStyle x MOM_STRIDE
     double* stats = nullptr;    // kMaxStyle x MOM_STAT_STRIDE
     double* sums = nullptr;     // kMaxStyle x MOM_PART_DOUBLES
-    size_t bytes = 0;
+    float* vals = nullptr;      // level 0 only: NST_MAX_LEVELS x 6 x 2, the unweighted (mean_i, std_i) of the last closure by map index
+    DevMem mem;
     float* mean_t(int q) const { return words + (size_t)q * MOM_STRIDE; }
     float* std_t(int q) const { return words + (size_t)q * MOM_STRIDE + GS_MAX_C; }
     float* row_bias(int q) const { return words + (size_t)q * MOM_STRIDE + 2 * GS_MAX_C; }
     double* stat(int q) const { return stats + (size_t)q * MOM_STAT_STRIDE; }
     double* loss(int q) const { return stats + (size_t)q * MOM_STAT_STRIDE + 2 * GS_MAX_C; }
     double* part(int q) const { return sums + (size_t)q * MOM_PART_DOUBLES; }
+};
+
+// the level image and its gradient (levels >= 1), planar: channels (nst_job_set_color) x h x w floats each
+struct LevelImage {
+    float* xl = nullptr;
+    float* gxl = nullptr;
+    DevMem mem;
 };
 
 struct LevelWs {
@@ -190,9 +203,9 @@ struct LevelWs {
     ActSet acts;
     float* gbuf[2] = {};
     size_t gbuf_floats = 0;
-    float* xl = nullptr;        // level image (levels >= 1), planar
-    float* gxl = nullptr;       // its gradient (levels >= 1), planar
-    size_t xl_floats = 0;       // channels (nst_job_set_color) x h x w
+    LevelImage img;
+    // the buffers whose size depends on the taps (tap_mem owns them): content target, Gram targets / factors / partial sums,
+    // partial-Gram workspace
     float* content_t = nullptr; // NHWC target ReLU(conv4_2)
     size_t content_n = 0;
     float* gram_t[kMaxStyle] = {};
@@ -201,13 +214,14 @@ struct LevelWs {
     float* gram_part = nullptr;
     size_t gram_part_floats = 0;
     double* style_partial[kMaxStyle] = {};
-    int tap_c[kMaxStyle] = {};  // channels of the style map each Gram buffer was sized for
+    DevMem tap_mem;
     double* content_partial = nullptr;
     double* tv_partial = nullptr;
     float* tv_means = nullptr;
     bool targets = false;
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;
+    DevMem mem;                 // owns gbuf and the partials
 };
 
 }  // namespace nst
@@ -274,17 +288,13 @@ struct nst_ctx {
         for (float w : style_w) if (w != 1.f) return false;
         return true;
     }
-    // nst_job_set_laplacian: lap_k entries (pool size, weight), 0 = the term is off; lap_vals: device, NST_MAX_LEVELS x
-    // NST_LAP_MAX floats, the unweighted lap_k of the last closure (written by the loss rows; made by the first setter call)
+    // nst_job_set_laplacian: lap_k entries (pool size, weight), 0 = the term is off
     int lap_k = 0;
     int lap_pool[nst::NST_LAP_MAX] = {};
     float lap_gamma[nst::NST_LAP_MAX] = {};
-    float* lap_vals = nullptr;
-    // nst_job_set_matting: the weight (0 = the term is off) and epsilon; mat_vals: device, NST_MAX_LEVELS floats, the
-    // unweighted mat of the last closure (written by the loss rows; made by the first setter call that switches the term on)
+    // nst_job_set_matting: the weight (0 = the term is off) and epsilon
     float mat_gamma = 0.f;
     double mat_eps = 1e-7;
-    float* mat_vals = nullptr;
     // nst_job_set_gram_shift: per map index (as the style layer weights) a constant shift, or (bit of gs_center) centring
     float gs_shift[6] = {};
     unsigned gs_center = 0;
@@ -295,12 +305,10 @@ struct nst_ctx {
     float gs_shift_of(int q) const { return gs_shift[nst::tap_index_of(taps.style[q])]; }                  // of style slot q
     int gs_center_of(int q) const { return (int)((gs_center >> nst::tap_index_of(taps.style[q])) & 1u); }
     // nst_job_set_moments: per map index (as the style layer weights) the weights of mean_i and std_i, and epsilon; all zero =
-    // the term is off.  mom_vals: device, NST_MAX_LEVELS x 6 x 2 floats, the unweighted (mean_i, std_i) of the last closure by
-    // map index (written by the loss rows; made by the first setter call that switches the term on)
+    // the term is off
     float mom_wm[6] = {};
     float mom_ws[6] = {};
     float mom_eps = 1e-5f;
-    float* mom_vals = nullptr;
     bool mom_on() const {
         for (int i = 0; i < 6; ++i) if (mom_wm[i] > 0.f || mom_ws[i] > 0.f) return true;
         return false;
@@ -331,7 +339,8 @@ struct nst_ctx {
     double* color_scratch = nullptr;   // nst_color_stats: COLOR_BLOCKS * 9 partials | mean (3) | cov (9), made on first use
     nst::LevelWs lv[NST_MAX_LEVELS];
     hipEvent_t fork = nullptr;
-    size_t bytes = 0;
+    size_t bytes = 0;           // nst_ctx_bytes: what dev_alloc charged and dev_release has not yet credited
+    nst::DevMem mem;            // owns the context's own buffers: weight images, biases, w11k / w11d, color_scratch
     bool single_stream = false;
     // timing
     int timing = 0;
@@ -395,45 +404,30 @@ struct Timer {
 // folds the event pairs of the previous closure into the accumulators (waits for them to complete)
 int fold_timed(nst_ctx* ctx);
 
-// ---- nst_ctx.cpp: device memory (counted in ctx->bytes), workspace, stream ordering ------------------------------------
-int dev_alloc(nst_ctx* ctx, void** p, size_t bytes);
-template <typename T>
-int dev_alloc_t(nst_ctx* ctx, T** p, size_t count) { return dev_alloc(ctx, reinterpret_cast<void**>(p), count * sizeof(T)); }
-inline void dev_free(void* p) { if (p) (void)hipFree(p); }
+// ---- nst_ctx.cpp: device memory (nst_devmem.h), workspace, stream ordering ---------------------------------------------
 int alloc_acts(nst_ctx* ctx, ActSet& a, int h, int w);
-void free_acts(nst_ctx* ctx, ActSet& a);
 int bind(nst_ctx* ctx);                            // null check + hipSetDevice: first line of every entry point
 // what a closure remembered is void once the job changes (captured graph; drop_targets: every level's targets)
 void drop_closure_state(nst_ctx* ctx, bool drop_targets);
-void free_guidance(nst_ctx* ctx, LevelWs& L);      // the level is unguided afterwards
-void free_laplacian(nst_ctx* ctx, LevelWs& L);     // the level's Laplacian buffers (the setting itself is the context's)
-void free_matting(nst_ctx* ctx, LevelWs& L);       // the level's matting buffers (likewise)
-void free_gram_shift(nst_ctx* ctx, LevelWs& L);    // the level's shifted-Gram buffers (likewise)
-void free_moments(nst_ctx* ctx, LevelWs& L);       // the level's moment-loss buffers (likewise)
 hipStream_t enter(nst_ctx* ctx, void* stream);     // orders the caller's stream after the context's tail event
 void mark(nst_ctx* ctx, hipStream_t s);            // records the tail event
 void quiesce(nst_ctx* ctx);                        // waits until nothing on the device uses the context's memory
 
 // Scratch of a standalone call - an ActSet and device buffers that its launches on `s` use: freed on every path out of the
 // scope, after the stream has been synchronised.  `return sc.finish();` ends the good path: synchronise, free, then report.
-// (The buffers stay counted in ctx->bytes as alloc_acts / free_acts and dev_alloc count them.)
+// (Counted in ctx->bytes while the call runs.)
 struct Scratch {
-    nst_ctx* ctx; hipStream_t s; ActSet acts; std::vector<void*> bufs; bool open = true;
+    nst_ctx* ctx; hipStream_t s; ActSet acts; DevMem bufs; bool open = true;
     Scratch(nst_ctx* c, hipStream_t st) : ctx(c), s(st) {}
-    Scratch(const Scratch&) = delete;
     ~Scratch() { (void)release(); }
     template <typename T>
-    int alloc(T** p, size_t count) {
-        NSTCHK(dev_alloc_t(ctx, p, count));
-        bufs.push_back(*p);
-        return NST_OK;
-    }
+    int alloc(T** p, size_t count) { return bufs.alloc(ctx, p, count); }
     hipError_t release() {
         if (!open) return hipSuccess;
         open = false;
         const hipError_t e = hipStreamSynchronize(s);
-        free_acts(ctx, acts);
-        for (void* p : bufs) dev_free(p);
+        acts = ActSet();
+        bufs.release();
         return e;
     }
     int finish() { const hipError_t e = release(); HIPCHK(ctx, e); return NST_OK; }

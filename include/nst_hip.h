@@ -790,7 +790,13 @@ int nst_window_end(nst_ctx* ctx, const float* xs, int row0, int rows, int H0, fl
  * an fp32 MFMA's), NST_CONV_BF16X3 or NST_CONV_F32. */
 int nst_conv_mode(const nst_ctx* ctx);
 
-/* workspace bytes currently held by the context (activations, gradients, history, targets) */
+/* Device bytes the context holds right now: a function of its current state, whatever calls led there.  Counted, each at
+ * the size actually allocated (a zero-size request takes 16 bytes): the weight images in the layouts of the context's
+ * arithmetic, with the biases and the scratch of nst_color_stats (made by its first call and kept); the level workspaces
+ * of the configured job (activations, gradient buffers, level images, targets and the buffers sized by the taps); the
+ * blocks of the optional terms while they are on (guidance, Laplacian, matting, Gram shift, moments); and, while a
+ * standalone call or a target-setting call runs, its scratch - gone again when the call returns.  Not counted: the
+ * vectors of an optimiser (nst_opt_create: moments, L-BFGS history), which are allocated apart from the context. */
 int nst_ctx_bytes(const nst_ctx* ctx, size_t* bytes);
 
 /* wall time in ms of the kernels of the last nst_closure on `ctx`, measured with HIP events on

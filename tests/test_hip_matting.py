@@ -308,8 +308,6 @@ def test_off_is_off(vgg_weights, mode):
                 before = e.bytes()
                 assert e.lib.nst_job_set_matting(e.ctx, 0.0, 1e-7) == 0
                 assert e.matting_setting() is None and e.bytes() == before
-            # (both engines make their targets a second time: the scratch of a target call stays counted in nst_ctx_bytes, so
-            # only equal call sequences have equal counts)
             _targets(e, *_job("L1")[:2])
             g, l = e.closure(x, CW, SW, TVW)
             out.append((_bits(g), _bits(l), len(e.last_closure_launches()), e.bytes()))
