@@ -1256,22 +1256,9 @@ __device__ __forceinline__ int xcd_contiguous(const int b, const int grid) {
 #endif
 }
 
-// one image, one tile per workgroup
-struct H2OneTile {
-    static constexpr bool REFETCH = false;
-    const ConvParams& p;
-    int n_ct;
-    __device__ __forceinline__ bool get(const int k, ConvParams& q, int& sp, int& ct) const {
-        if (k > 0) return false;
-        const int t = xcd_contiguous((int)blockIdx.x, (int)gridDim.x);
-        q = p;
-        sp = t / n_ct;
-        ct = t % n_ct;
-        return true;
-    }
-};
-// several images; one tile per workgroup, or (b.persist: the grid is a multiple of 8 that fills the chip once) the
-// workgroup's share of its XCD's contiguous range: the order in which a one-tile-per-workgroup grid would have met them
+// the images of a launch (a lone image, and each row band of one, is a batch of one); one tile per workgroup, or
+// (b.persist: the grid is a multiple of 8 that fills the chip once) the workgroup's share of its XCD's contiguous range:
+// the order in which a one-tile-per-workgroup grid would have met them
 template <bool PERSIST>
 struct H2BatchTiles {
     static constexpr bool REFETCH = PERSIST;
@@ -1301,16 +1288,11 @@ struct H2BatchTiles {
         p.wt_h2 = b.wt_h2; p.wt_h2_inv = b.wt_h2_inv; p.wt2_f32 = im.wt2_f32;
         p.amax_in = im.amax_in; p.amax_in2 = im.amax_in2; p.amax_w2 = im.amax_w2; p.amax_out = im.amax_out;
         p.pcode_in = im.pcode_in; p.pcode_out = im.pcode_out; p.pool_avg = b.pool_avg;
-        p.in2_row0 = im.in2_row0; p.in2_rows = im.in2_rows; p.ty0 = 0;
+        p.in2_row0 = im.in2_row0; p.in2_rows = im.in2_rows; p.ty0 = im.ty0;
         sp = sp_all - (i ? b.img[i - 1].tile_end : 0);
         return true;
     }
 };
-
-template <int TH, int BN, int NTW, int KC, bool UNPOOL, bool M16>
-__global__ __launch_bounds__((H2Cfg<TH, BN, NTW, KC>::NT), (H2Cfg<TH, BN, NTW, KC>::WAVES_PER_EU)) void conv_h2_kernel(ConvParams p) {
-    conv_h2_body<TH, BN, NTW, KC, UNPOOL, M16>(H2OneTile{p, p.Cout / BN}, blockIdx.x);
-}
 
 // One launch = one layer over several images (the pyramid levels of a closure), see conv_bf3.hip.
 template <int TH, int BN, int NTW, int KC, bool UNPOOL, bool M16, bool PERSIST>
@@ -1327,11 +1309,8 @@ constexpr bool h2_m16_built = (KC == 32 && NTW <= 2);
 template <int TH, int BN, int NTW, int KC, bool UNPOOL, bool M16>
 static hipError_t init_form() {
     constexpr int lds = H2Cfg<TH, BN, NTW, KC>::LDS_BYTES;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_h2_kernel<TH, BN, NTW, KC, UNPOOL, M16>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_h2_batch_kernel<TH, BN, NTW, KC, UNPOOL, M16, false>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_h2_batch_kernel<TH, BN, NTW, KC, UNPOOL, M16, false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if constexpr (h2_persist_shape<TH, BN, NTW, KC> && !M16) {
         if (e == hipSuccess)
             e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_h2_batch_kernel<TH, BN, NTW, KC, UNPOOL, false, true>),
@@ -1440,21 +1419,6 @@ static void launch_batch_cfg(const ConvBatch& b, const H2Shape& sh, int blocks, 
     if (b.unpool) hipLaunchKernelGGL((conv_h2_batch_kernel<TH, BN, NTW, KC, true, false, false>), dim3(blocks), dim3(nt), lds, stream, b);
     else hipLaunchKernelGGL((conv_h2_batch_kernel<TH, BN, NTW, KC, false, false, false>), dim3(blocks), dim3(nt), lds, stream, b);
 }
-template <int TH, int BN, int NTW, int KC>
-static void launch_single_cfg(const ConvParams& p, const H2Shape& sh, int blocks, hipStream_t stream) {
-    constexpr int lds = H2Cfg<TH, BN, NTW, KC>::LDS_BYTES;
-    constexpr int nt = H2Cfg<TH, BN, NTW, KC>::NT;
-    if constexpr (h2_m16_built<NTW, KC>) {
-        if (sh.m16) {
-            if (p.pcode_in) hipLaunchKernelGGL((conv_h2_kernel<TH, BN, NTW, KC, true, true>), dim3(blocks), dim3(nt), lds, stream, p);
-            else hipLaunchKernelGGL((conv_h2_kernel<TH, BN, NTW, KC, false, true>), dim3(blocks), dim3(nt), lds, stream, p);
-            return;
-        }
-    }
-    if (p.pcode_in) hipLaunchKernelGGL((conv_h2_kernel<TH, BN, NTW, KC, true, false>), dim3(blocks), dim3(nt), lds, stream, p);
-    else hipLaunchKernelGGL((conv_h2_kernel<TH, BN, NTW, KC, false, false>), dim3(blocks), dim3(nt), lds, stream, p);
-}
-
 static bool h2_operands_ok(const void* wt, const unsigned* amax_in, int Cin, int Cout, const float* in2, const float* wt2,
                            const unsigned* a2, const unsigned* w2, int Cin2) {
     if (Cin % 32 != 0 || Cout % 64 != 0) return false;
@@ -1497,6 +1461,7 @@ hipError_t launch_conv_h2_batch(const ConvBatch& b0, hipStream_t stream, H2Shape
     int tiles = 0;
     for (int i = 0; i < b.n; ++i) {
         b.img[i].tiles_x = (b.img[i].W + 15) / 16;
+        b.img[i].ty0 = 0;
         tiles += b.img[i].tiles_x * ((b.img[i].H + sh.rows - 1) / sh.rows);
         b.img[i].tile_end = tiles;
     }
@@ -1508,16 +1473,13 @@ hipError_t launch_conv_h2_batch(const ConvBatch& b0, hipStream_t stream, H2Shape
     return hipGetLastError();
 }
 
-hipError_t launch_conv_h2(const ConvParams& p0, hipStream_t stream, H2Shape* shape) {
-    if (!h2_operands_ok(p0.wt_h2, p0.amax_in, p0.Cin, p0.Cout, p0.in2, p0.wt2_f32, p0.amax_in2, p0.amax_w2, p0.Cin2))
+hipError_t launch_conv_h2(const ConvParams& p, hipStream_t stream, H2Shape* shape) {
+    if (!h2_operands_ok(p.wt_h2, p.amax_in, p.Cin, p.Cout, p.in2, p.wt2_f32, p.amax_in2, p.amax_w2, p.Cin2))
         return hipErrorInvalidValue;
-    if (!p0.out && !p0.pool_out) return hipErrorInvalidValue;
-    ConvParams p = p0;
-    p.ksplit = 1;
+    if (!p.out && !p.pool_out) return hipErrorInvalidValue;
     int all_blocks = 0;
     H2Shape sh = h2_launch_shape(&p.H, &p.W, 1, p.Cin, p.Cout, p.pcode_in != nullptr, p.in2 != nullptr, p.tile_rows, p.mfma16, p.wg256, 0, &all_blocks);
     const int th = sh.rows;
-    p.tiles_x = (p.W + 15) / 16;
     // The kernels address with 32-bit buffer offsets.  A launch whose tensors reach 4 GiB runs in bands of output rows
     // (multiples of 16, so tiles and pooling windows stay aligned): every tensor pointer is moved to the band's first
     // row minus a 16-row halo, the band "image" ends 16 rows below the band, and only the band's tile rows are
@@ -1534,27 +1496,44 @@ hipError_t launch_conv_h2(const ConvParams& p0, hipStream_t stream, H2Shape* sha
     const int forced_band = p.band_rows;
     if (forced_band >= 16 && forced_band / 16 * 16 < band_rows) band_rows = forced_band / 16 * 16;
     const int PW2 = p.W >> 1, wi = p.Cin >> 5, wo = p.Cout >> 5;
+    // a band is a batch of one image in the one-tile-per-workgroup form (not through launch_conv_h2_batch: the shape is
+    // the whole image's, and that launcher refuses the tensors bands exist for)
+    ConvBatch b{};
+    b.n = 1;
+    b.bias = p.bias;
+    b.Cin = p.Cin; b.Cout = p.Cout; b.Cin2 = p.Cin2; b.relu = p.relu;
+    b.wt_h2 = p.wt_h2; b.wt_h2_inv = p.wt_h2_inv;
+    b.unpool = (p.pcode_in != nullptr);
+    b.persist = 0;
+    b.pool_avg = p.pool_avg;
     int bands = 0;
     for (int r0 = 0; r0 < p.H; r0 += band_rows) {
         const int r1 = (r0 + band_rows < p.H) ? r0 + band_rows : p.H;
         const int b0 = (r0 >= 16) ? r0 - 16 : 0, b1 = (r1 + 16 < p.H) ? r1 + 16 : p.H;
-        ConvParams q = p;
         const size_t px0 = (size_t)b0 * p.W, pp0 = (size_t)(b0 >> 1) * PW2;       // first pixel / pooled pixel of the band image
-        if (q.pcode_in) { q.in += pp0 * p.Cin; q.pcode_in += pp0 * wi * 4; }
-        else if (q.in) q.in += px0 * p.Cin;
-        if (q.in2) { q.in2 += px0 * p.Cin2; if (q.in2_rows > 0) q.in2_row0 -= b0; }
-        if (q.out) q.out += px0 * p.Cout;
-        if (q.addend) q.addend += px0 * p.Cout;
-        if (q.mask) q.mask += px0 * p.Cout;
-        if (q.bits_in) q.bits_in += px0 * wo;
-        if (q.bits_out) q.bits_out += px0 * wo;
-        if (q.pool_out) q.pool_out += pp0 * p.Cout;
-        if (q.pcode_out) q.pcode_out += pp0 * wo * 4;
-        q.H = b1 - b0;
+        ConvImage& q = b.img[0];
+        q = ConvImage{};
+        if (p.pcode_in) { q.in = p.in + pp0 * p.Cin; q.pcode_in = p.pcode_in + pp0 * wi * 4; }
+        else if (p.in) q.in = p.in + px0 * p.Cin;
+        q.in2_row0 = p.in2_row0; q.in2_rows = p.in2_rows;
+        if (p.in2) { q.in2 = p.in2 + px0 * p.Cin2; if (q.in2_rows > 0) q.in2_row0 -= b0; }
+        if (p.out) q.out = p.out + px0 * p.Cout;
+        if (p.addend) q.addend = p.addend + px0 * p.Cout;
+        if (p.mask) q.mask = p.mask + px0 * p.Cout;
+        if (p.bits_in) q.bits_in = p.bits_in + px0 * wo;
+        if (p.bits_out) q.bits_out = p.bits_out + px0 * wo;
+        if (p.pool_out) q.pool_out = p.pool_out + pp0 * p.Cout;
+        if (p.pcode_out) q.pcode_out = p.pcode_out + pp0 * wo * 4;
+        q.wt2_f32 = p.wt2_f32;
+        q.amax_in = p.amax_in; q.amax_in2 = p.amax_in2; q.amax_w2 = p.amax_w2; q.amax_out = p.amax_out;
+        q.H = b1 - b0; q.W = p.W;
         q.ty0 = (r0 - b0) / th;
-        q.tiles_y = (r1 - r0 + th - 1) / th;
-        const int blocks = q.tiles_x * q.tiles_y * (p.Cout / sh.bn);
-        h2_dispatch(sh, [&](auto cfg) { launch_single_cfg<decltype(cfg)::th, decltype(cfg)::bn, decltype(cfg)::ntw, decltype(cfg)::kc>(q, sh, blocks, stream); });
+        const int tiles_y = (r1 - r0 + th - 1) / th;
+        q.tiles_x = (p.W + 15) / 16;
+        q.tile_end = q.tiles_x * tiles_y;
+        const int blocks = q.tile_end * (p.Cout / sh.bn);
+        b.total_tiles = blocks;
+        h2_dispatch(sh, [&](auto cfg) { launch_batch_cfg<decltype(cfg)::th, decltype(cfg)::bn, decltype(cfg)::ntw, decltype(cfg)::kc>(b, sh, blocks, stream); });
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
         ++bands;

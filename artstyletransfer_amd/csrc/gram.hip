@@ -455,15 +455,9 @@ __device__ __forceinline__ void gram_h2_body(const float* __restrict__ f, size_t
     else if (TS == 128) run(std::integral_constant<int, GRAM_TRI2>{});
 }
 
-// PACK = false is the parent's kernel (nst_ctx_set_gram_pack(ctx, 0)), in every form below
-template <int TS, bool PACK = false>
-__global__ __launch_bounds__(256, 2) void gram_h2_kernel(const float* __restrict__ f, size_t N, int C, int nsplit,
-                                                         size_t pix_per_split, const unsigned* __restrict__ amax,
-                                                         float* __restrict__ part) {
-    gram_h2_body<TS, false, false, PACK>(f, N, C, nsplit, pix_per_split, amax, part, blockIdx.x);
-}
-// several maps (the style taps of every pyramid level of a closure) in one launch: their workgroups are numbered
-// item by item, so the short ones fill the tail of the long ones
+// PACK = false is the parent's kernel (nst_ctx_set_gram_pack(ctx, 0)), in every form below.
+// Several maps (the style taps of every pyramid level of a closure) in one launch: their workgroups are numbered
+// item by item, so the short ones fill the tail of the long ones.  A lone map is a batch of one.
 template <int TS, bool PACK = false>
 __global__ __launch_bounds__(256, 2) void gram_h2_batch_kernel(GramBatch b) {
     int i = 0;
@@ -474,12 +468,6 @@ __global__ __launch_bounds__(256, 2) void gram_h2_batch_kernel(GramBatch b) {
 }
 // the guided forms (gram_guided.hip has the rest of spatial control): the same bodies with the staged rows scaled by t(p)
 template <int TS, bool PACK = false>
-__global__ __launch_bounds__(256, 2) void gram_h2_guided_kernel(const float* __restrict__ f, size_t N, int C, int nsplit,
-                                                                size_t pix_per_split, const unsigned* __restrict__ amax,
-                                                                float* __restrict__ part, const float* __restrict__ guide) {
-    gram_h2_body<TS, true, false, PACK>(f, N, C, nsplit, pix_per_split, amax, part, blockIdx.x, guide);
-}
-template <int TS, bool PACK = false>
 __global__ __launch_bounds__(256, 2) void gram_h2_guided_batch_kernel(GramBatch b) {
     int i = 0;
     while (i + 1 < b.n && (int)blockIdx.x >= b.it[i].part_end) ++i;
@@ -489,12 +477,6 @@ __global__ __launch_bounds__(256, 2) void gram_h2_guided_batch_kernel(GramBatch 
 }
 
 // the shifted forms (gram_shift.hip has the rest of the shifted / centred statistic)
-template <int TS, bool PACK = false>
-__global__ __launch_bounds__(256, 2) void gram_h2_shift_kernel(const float* __restrict__ f, size_t N, int C, int nsplit,
-                                                               size_t pix_per_split, const unsigned* __restrict__ amax,
-                                                               float* __restrict__ part, const float* __restrict__ offs) {
-    gram_h2_body<TS, false, true, PACK>(f, N, C, nsplit, pix_per_split, amax, part, blockIdx.x, nullptr, offs);
-}
 template <int TS, bool PACK = false>
 __global__ __launch_bounds__(256, 2) void gram_h2_shift_batch_kernel(GramBatch b) {
     int i = 0;
@@ -575,19 +557,13 @@ hipError_t gram_init_device() {
     // every fp16-piece form, both tile shapes, the parent's kernels and the PACK ones
     static_assert(GramH2Cfg<128>::LDS_BYTES == GramH2Cfg<64>::LDS_BYTES, "gram_h2_pack_kernel runs both bodies in one LDS size");
     const void* h2_128[] = {
-        reinterpret_cast<const void*>(&gram_h2_kernel<128, false>),              reinterpret_cast<const void*>(&gram_h2_kernel<128, true>),
         reinterpret_cast<const void*>(&gram_h2_batch_kernel<128, false>),        reinterpret_cast<const void*>(&gram_h2_batch_kernel<128, true>),
-        reinterpret_cast<const void*>(&gram_h2_guided_kernel<128, false>),       reinterpret_cast<const void*>(&gram_h2_guided_kernel<128, true>),
         reinterpret_cast<const void*>(&gram_h2_guided_batch_kernel<128, false>), reinterpret_cast<const void*>(&gram_h2_guided_batch_kernel<128, true>),
-        reinterpret_cast<const void*>(&gram_h2_shift_kernel<128, false>),        reinterpret_cast<const void*>(&gram_h2_shift_kernel<128, true>),
         reinterpret_cast<const void*>(&gram_h2_shift_batch_kernel<128, false>),  reinterpret_cast<const void*>(&gram_h2_shift_batch_kernel<128, true>),
         reinterpret_cast<const void*>(&gram_h2_pack_kernel)};
     const void* h2_64[] = {
-        reinterpret_cast<const void*>(&gram_h2_kernel<64, false>),              reinterpret_cast<const void*>(&gram_h2_kernel<64, true>),
         reinterpret_cast<const void*>(&gram_h2_batch_kernel<64, false>),        reinterpret_cast<const void*>(&gram_h2_batch_kernel<64, true>),
-        reinterpret_cast<const void*>(&gram_h2_guided_kernel<64, false>),       reinterpret_cast<const void*>(&gram_h2_guided_kernel<64, true>),
         reinterpret_cast<const void*>(&gram_h2_guided_batch_kernel<64, false>), reinterpret_cast<const void*>(&gram_h2_guided_batch_kernel<64, true>),
-        reinterpret_cast<const void*>(&gram_h2_shift_kernel<64, false>),        reinterpret_cast<const void*>(&gram_h2_shift_kernel<64, true>),
         reinterpret_cast<const void*>(&gram_h2_shift_batch_kernel<64, false>),  reinterpret_cast<const void*>(&gram_h2_shift_batch_kernel<64, true>)};
     for (const void* k : h2_128) {
         e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, GramH2Cfg<128>::LDS_BYTES);
@@ -600,19 +576,12 @@ hipError_t gram_init_device() {
     return hipSuccess;
 }
 
-// one map on the fp16 matrix pipe: plain, guided or shifted (never both)
+// the fp16-piece kernel of a batch: plain, guided or shifted (never both)
 template <int TS, bool PACK>
-static void launch_h2_single(int blocks, hipStream_t stream, const float* f, size_t N, int C, int nsplit, size_t pix_per_split,
-                             const unsigned* amax, float* part, const float* guide, const float* offset) {
-    if (guide)
-        hipLaunchKernelGGL((gram_h2_guided_kernel<TS, PACK>), dim3(blocks), dim3(256), GramH2Cfg<TS>::LDS_BYTES, stream, f, N, C, nsplit,
-                           pix_per_split, amax, part, guide);
-    else if (offset)
-        hipLaunchKernelGGL((gram_h2_shift_kernel<TS, PACK>), dim3(blocks), dim3(256), GramH2Cfg<TS>::LDS_BYTES, stream, f, N, C, nsplit,
-                           pix_per_split, amax, part, offset);
-    else
-        hipLaunchKernelGGL((gram_h2_kernel<TS, PACK>), dim3(blocks), dim3(256), GramH2Cfg<TS>::LDS_BYTES, stream, f, N, C, nsplit,
-                           pix_per_split, amax, part);
+static void launch_h2_batch(int blocks, hipStream_t stream, const GramBatch& b, bool guided, bool shifted) {
+    if (guided) hipLaunchKernelGGL((gram_h2_guided_batch_kernel<TS, PACK>), dim3(blocks), dim3(256), GramH2Cfg<TS>::LDS_BYTES, stream, b);
+    else if (shifted) hipLaunchKernelGGL((gram_h2_shift_batch_kernel<TS, PACK>), dim3(blocks), dim3(256), GramH2Cfg<TS>::LDS_BYTES, stream, b);
+    else hipLaunchKernelGGL((gram_h2_batch_kernel<TS, PACK>), dim3(blocks), dim3(256), GramH2Cfg<TS>::LDS_BYTES, stream, b);
 }
 
 hipError_t launch_gram_partial(const float* f, size_t N, int C, int nsplit, const unsigned* amax, float* part,
@@ -634,10 +603,16 @@ hipError_t launch_gram_partial(const float* f, size_t N, int C, int nsplit, cons
     const bool h2 = amax != nullptr && pix_per_split * (size_t)C * 4 < 0xFFFFFF00ull;
     if (guide || offset || h2) {
         if (!h2) return hipErrorInvalidValue;
-        if (ts == 128 && pack) launch_h2_single<128, true>(pairs * nsplit, stream, f, N, C, nsplit, pix_per_split, amax, part, guide, offset);
-        else if (ts == 128) launch_h2_single<128, false>(pairs * nsplit, stream, f, N, C, nsplit, pix_per_split, amax, part, guide, offset);
-        else if (pack) launch_h2_single<64, true>(pairs * nsplit, stream, f, N, C, nsplit, pix_per_split, amax, part, guide, offset);
-        else launch_h2_single<64, false>(pairs * nsplit, stream, f, N, C, nsplit, pix_per_split, amax, part, guide, offset);
+        // a lone map is a batch of one, with the caller's split count
+        GramBatch b{};
+        b.n = 1;
+        GramItem& it = b.it[0];
+        it.f = f; it.N = N; it.C = C; it.amax = amax; it.part = part; it.guide = guide; it.offset = offset;
+        it.nsplit = nsplit; it.pix_per_split = pix_per_split; it.part_end = pairs * nsplit;
+        if (ts == 128 && pack) launch_h2_batch<128, true>(it.part_end, stream, b, guide != nullptr, offset != nullptr);
+        else if (ts == 128) launch_h2_batch<128, false>(it.part_end, stream, b, guide != nullptr, offset != nullptr);
+        else if (pack) launch_h2_batch<64, true>(it.part_end, stream, b, guide != nullptr, offset != nullptr);
+        else launch_h2_batch<64, false>(it.part_end, stream, b, guide != nullptr, offset != nullptr);
     } else if (ts == 128) {
         hipLaunchKernelGGL(gram_partial_kernel<128>, dim3(pairs * nsplit), dim3(256), GramCfg<128>::LDS_BYTES, stream, f,
                            N, C, nsplit, pix_per_split, part);
@@ -821,13 +796,6 @@ static int gram_nsplit_in_batch(const GramBatch& b, int i) {
 
 // Batched forms (fp16-piece kernels only: every item needs its absmax record, C = 64 or a multiple of 128, and its
 // own partial buffer of nsplit x C x C floats).  Fills nsplit / pix_per_split / the block prefixes.
-template <int TS, bool PACK>
-static void launch_h2_batch(int blocks, hipStream_t stream, const GramBatch& b, bool guided, bool shifted) {
-    if (guided) hipLaunchKernelGGL((gram_h2_guided_batch_kernel<TS, PACK>), dim3(blocks), dim3(256), GramH2Cfg<TS>::LDS_BYTES, stream, b);
-    else if (shifted) hipLaunchKernelGGL((gram_h2_shift_batch_kernel<TS, PACK>), dim3(blocks), dim3(256), GramH2Cfg<TS>::LDS_BYTES, stream, b);
-    else hipLaunchKernelGGL((gram_h2_batch_kernel<TS, PACK>), dim3(blocks), dim3(256), GramH2Cfg<TS>::LDS_BYTES, stream, b);
-}
-
 // pack (nst_ctx_set_gram_pack): the PACK kernels, and a plain batch's two tile shapes in one grid; 0: the parent's kernels
 // and launch sequence
 hipError_t launch_gram_batch(const GramBatch& b0, hipStream_t stream, int pack) {

@@ -78,7 +78,9 @@ int nst_gram(nst_ctx* ctx, const float* f, int C, int h, int w, int normalize, f
     // the fp16-piece kernel needs the absmax of its operand (in the closure the producing conv records it)
     if (amax && (launch_zero(amax, NST_AMAX_SLOTS, s) != hipSuccess || launch_absmax_slots(nhwc, N * C, amax, s) != hipSuccess))
         return fail(ctx, NST_E_HIP, "absmax launch failed");
-    NSTCHK(gram_of(ctx, nhwc, N, C, amax, normalize ? (float)((double)C * h * w) : 1.f, part, nullptr, 0.f, gram, nullptr, nullptr, nullptr, nullptr, s));
+    GramFinish fin;
+    fin.gram_out = gram;
+    NSTCHK(gram_of(ctx, GramOperand{nhwc, N, C, amax, nullptr, part, normalize ? (float)((double)C * h * w) : 1.f}, fin, s));
     return sc.finish();
 }
 
@@ -108,8 +110,9 @@ int nst_gram_shifted(nst_ctx* ctx, const float* f, int C, int h, int w, int norm
     if (launch_zero(amax, NST_AMAX_SLOTS, s) != hipSuccess || launch_absmax_slots(nhwc, N * C, amax, s) != hipSuccess)
         return fail(ctx, NST_E_HIP, "absmax launch failed");
     const ShiftedGram sg{shift, center ? 1 : 0, words, reinterpret_cast<unsigned*>(words + C), sums, nullptr};
-    NSTCHK(gram_shifted_of(ctx, nhwc, N, C, amax, sg, normalize ? (float)((double)C * h * w) : 1.f, part, nullptr, 0.f, gram, nullptr, nullptr,
-                           nullptr, nullptr, s));
+    GramFinish fin;
+    fin.gram_out = gram;
+    NSTCHK(gram_shifted_of(ctx, GramOperand{nhwc, N, C, amax, nullptr, part, normalize ? (float)((double)C * h * w) : 1.f}, sg, fin, s));
     if (offset_out) HIPCHK(ctx, hipMemcpyAsync(offset_out, words, (size_t)C * sizeof(float), hipMemcpyDeviceToDevice, s));
     return sc.finish();
 }

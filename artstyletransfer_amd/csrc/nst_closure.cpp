@@ -409,45 +409,39 @@ int backward(nst_ctx* ctx, ActSet& a, const Inject* inj, const ContentJob* cj, f
     return NST_OK;
 }
 
-int gram_of(nst_ctx* ctx, const float* f_nhwc, size_t N, int C, const unsigned* f_amax, float divisor, float* part, const float* target,
-            float coef, float* gram_out, float* S, unsigned short* S_bf, unsigned* S_amax, double* mse_partial,
-            hipStream_t s) {
-    const int ns = gram_nsplit(C, N);
+int gram_of(nst_ctx* ctx, const GramOperand& op, const GramFinish& fin, hipStream_t s, bool timed) {
+    const int ns = gram_nsplit(op.C, op.N);
     {
-        Timer t(ctx, s, K_GRAM, 2.0 * (double)N * C * C);
-        HIPCHK(ctx, launch_gram_partial(f_nhwc, N, C, ns, f_amax, part, s, nullptr, nullptr, ctx->gram_pack));
+        std::optional<Timer> t;
+        if (timed) t.emplace(ctx, s, K_GRAM, 2.0 * (double)op.N * op.C * op.C);
+        HIPCHK(ctx, launch_gram_partial(op.f, op.N, op.C, ns, op.amax, op.part, s, op.guide, op.offset, ctx->gram_pack));
     }
-    Timer t(ctx, s, K_OTHER, 0);
-    HIPCHK(ctx, launch_gram_finish(part, gram_nslabs(C, ns), C, divisor, target, coef, gram_out, S, S_bf, S_amax,
-                                   mse_partial, s));
+    std::optional<Timer> t;
+    if (timed) t.emplace(ctx, s, K_OTHER, 0);
+    if (fin.alpha >= 0.f)
+        HIPCHK(ctx, launch_gram_finish_blend(op.part, gram_nslabs(op.C, ns), op.C, op.divisor, fin.alpha, fin.accumulate, fin.gram_out, s));
+    else
+        HIPCHK(ctx, launch_gram_finish(op.part, gram_nslabs(op.C, ns), op.C, op.divisor, fin.target, fin.coef, fin.gram_out, fin.S, fin.S_bf,
+                                       fin.S_amax, fin.mse_partial, s));
     return NST_OK;
 }
 
-int gram_shifted_of(nst_ctx* ctx, const float* f_nhwc, size_t N, int C, const unsigned* f_amax, const ShiftedGram& sg, float divisor,
-                    float* part, const float* target, float coef, float* gram_out, float* S, unsigned short* S_bf, unsigned* S_amax,
-                    double* mse_partial, hipStream_t s) {
-    if (!f_amax) return fail(ctx, NST_E_STATE, "the shifted Gram runs in the f16x2 arithmetic only");
-    const int ns = gram_nsplit(C, N);
+int gram_shifted_of(nst_ctx* ctx, const GramOperand& op, const ShiftedGram& sg, const GramFinish& fin, hipStream_t s) {
+    if (!op.amax) return fail(ctx, NST_E_STATE, "the shifted Gram runs in the f16x2 arithmetic only");
     {
         OffsetBatch ob{};
         ob.n = 1;
-        ob.it[0] = OffsetItem{f_nhwc, N, C, f_amax, sg.shift, sg.center, sg.offset, sg.rec, sg.sums, 0, 0, 0};
+        ob.it[0] = OffsetItem{op.f, op.N, op.C, op.amax, sg.shift, sg.center, sg.offset, sg.rec, sg.sums, 0, 0, 0};
         Timer t(ctx, s, K_OTHER, 0);
         HIPCHK(ctx, launch_gram_offsets(ob, s));
     }
-    {
-        Timer t(ctx, s, K_GRAM, 2.0 * (double)N * C * C);
-        HIPCHK(ctx, launch_gram_partial(f_nhwc, N, C, ns, sg.rec, part, s, nullptr, sg.offset, ctx->gram_pack));
-    }
-    {
-        Timer t(ctx, s, K_OTHER, 0);
-        if (sg.alpha >= 0.f) HIPCHK(ctx, launch_gram_finish_blend(part, gram_nslabs(C, ns), C, divisor, sg.alpha, sg.accumulate, gram_out, s));
-        else HIPCHK(ctx, launch_gram_finish(part, gram_nslabs(C, ns), C, divisor, target, coef, gram_out, S, S_bf, S_amax, mse_partial, s));
-    }
-    if (sg.r && S) {
+    GramOperand shifted = op;
+    shifted.amax = sg.rec; shifted.guide = nullptr; shifted.offset = sg.offset;
+    NSTCHK(gram_of(ctx, shifted, fin, s));
+    if (sg.r && fin.S) {
         RowBiasBatch rb{};
         rb.n = 1;
-        rb.it[0] = RowBiasItem{sg.offset, S, sg.r, C, 0};
+        rb.it[0] = RowBiasItem{sg.offset, fin.S, sg.r, op.C, 0};
         Timer t(ctx, s, K_OTHER, 0);
         HIPCHK(ctx, launch_gram_row_bias(rb, s));
     }
@@ -699,8 +693,8 @@ int batched_gram(nst_ctx* ctx, const int* lv, int n, float sw, hipStream_t s, un
         LevelWs& L = ctx->lv[lv[k]];
         for (int q = 0; q < ctx->taps.nstyle; ++q) {
             const StyleTerm st = style_term(ctx->taps, q, L.acts, sw, ctx->style_weight(q));
-            NSTCHK(gram_of(ctx, L.acts.act[ctx->taps.style[q]], st.N, st.C, nullptr, (float)st.divisor, L.gram_part, L.gram_t[q], st.coef, nullptr, L.S[q],
-                           L.S_bf[q], nullptr, L.style_partial[q], s));
+            NSTCHK(gram_of(ctx, GramOperand{L.acts.act[ctx->taps.style[q]], st.N, st.C, nullptr, nullptr, L.gram_part, (float)st.divisor},
+                           GramFinish{L.gram_t[q], st.coef, L.S[q], L.S_bf[q], nullptr, L.style_partial[q]}, s));
         }
     }
     return NST_OK;
@@ -972,15 +966,9 @@ int closure_per_level(nst_ctx* ctx, const float* const* xi, float* const* gi, in
         const Guidance& g = L.guide;
         for (int r = 0; r < g.R; ++r) {
             const StyleTerm st = guided_term(tp, k, L.acts, sw, ctx->style_weight(k), g, r);
-            const int ns = gram_nsplit(st.C, st.N);
-            {
-                Timer t(ctx, s, K_GRAM, 2.0 * (double)st.N * st.C * st.C);
-                HIPCHK(ctx, launch_gram_partial(L.acts.act[l], st.N, st.C, ns, amax_act(L.acts, l), g.part, s, g.plane(kScale[l], r, L.h, L.w), nullptr, ctx->gram_pack));
-            }
-            Timer t(ctx, s, K_OTHER, 0);
-            HIPCHK(ctx, launch_gram_finish(g.part, gram_nslabs(st.C, ns), st.C, (float)st.divisor, g.gram_t[k] + (size_t)r * st.C * st.C, st.coef,
-                                           nullptr, g.S[k] + (size_t)r * st.C * st.C, nullptr, nullptr,
-                                           g.partial[k] + (size_t)r * gram_finish_blocks(st.C), s));
+            NSTCHK(gram_of(ctx, GramOperand{L.acts.act[l], st.N, st.C, amax_act(L.acts, l), g.plane(kScale[l], r, L.h, L.w), g.part, (float)st.divisor},
+                           GramFinish{g.gram_t[k] + (size_t)r * st.C * st.C, st.coef, g.S[k] + (size_t)r * st.C * st.C, nullptr, nullptr,
+                                      g.partial[k] + (size_t)r * gram_finish_blocks(st.C)}, s));
         }
         NSTCHK(guided_fold(ctx, L, k, s));
         gbw[k] = guided_bwd_of(ctx, L, k);
@@ -989,13 +977,13 @@ int closure_per_level(nst_ctx* ctx, const float* const* xi, float* const* gi, in
     for (int k = 0; k < tp.nstyle && L.guide.R == 0; ++k) {
         const int l = tp.style[k];
         const StyleTerm st = style_term(tp, k, L.acts, sw, ctx->style_weight(k));
+        const GramOperand op{L.acts.act[l], st.N, st.C, h2 ? amax_act(L.acts, l) : nullptr, nullptr, L.gram_part, (float)st.divisor};
+        const GramFinish fin{L.gram_t[k], st.coef, L.S[k], L.S_bf[k], h2 ? amax_S(L.acts, k) : nullptr, L.style_partial[k]};
         if (ctx->gs_on()) {
             const ShiftedGram sg{ctx->gs_shift_of(k), ctx->gs_center_of(k), L.gs.offset(k), L.gs.amax(k), L.gs.part(k), L.gs.row_bias(k)};
-            NSTCHK(gram_shifted_of(ctx, L.acts.act[l], st.N, st.C, h2 ? amax_act(L.acts, l) : nullptr, sg, (float)st.divisor, L.gram_part, L.gram_t[k],
-                                   st.coef, nullptr, L.S[k], L.S_bf[k], h2 ? amax_S(L.acts, k) : nullptr, L.style_partial[k], s));
+            NSTCHK(gram_shifted_of(ctx, op, sg, fin, s));
         } else {
-            NSTCHK(gram_of(ctx, L.acts.act[l], st.N, st.C, h2 ? amax_act(L.acts, l) : nullptr, (float)st.divisor, L.gram_part, L.gram_t[k], st.coef, nullptr, L.S[k],
-                           L.S_bf[k], h2 ? amax_S(L.acts, k) : nullptr, L.style_partial[k], s));
+            NSTCHK(gram_of(ctx, op, fin, s));
         }
         if (ctx->mom_on() && ctx->mom_slot(k)) {
             MomentBatch mb{};
@@ -1322,22 +1310,16 @@ int nst_level_set_targets_blend(nst_ctx* ctx, int level, const float* content, i
                 Timer t(ctx, s, K_OTHER, 0);
                 HIPCHK(ctx, launch_moment_stats(mb, s));
             }
+            // G, b^-weighted into the slot's Gt
+            const GramOperand op{sc.acts.act[l], st.N, st.C, ctx->conv_mode == 2 ? amax_act(sc.acts, l) : nullptr, nullptr, part, (float)st.divisor};
+            GramFinish fin;
+            fin.gram_out = L.gram_t[q]; fin.alpha = bhat[k][q]; fin.accumulate = written[q] ? 1 : 0;
             if (ctx->gs_on()) {
-                ShiftedGram sg{ctx->gs_shift_of(q), ctx->gs_center_of(q), gsl.offset(0), gsl.amax(0), gsl.part(0), nullptr};
-                sg.alpha = bhat[k][q]; sg.accumulate = written[q] ? 1 : 0;
-                NSTCHK(gram_shifted_of(ctx, sc.acts.act[l], st.N, st.C, ctx->conv_mode == 2 ? amax_act(sc.acts, l) : nullptr, sg, (float)st.divisor,
-                                       part, nullptr, 0.f, L.gram_t[q], nullptr, nullptr, nullptr, nullptr, s));
-                written[q] = true;
-                continue;
+                const ShiftedGram sg{ctx->gs_shift_of(q), ctx->gs_center_of(q), gsl.offset(0), gsl.amax(0), gsl.part(0), nullptr};
+                NSTCHK(gram_shifted_of(ctx, op, sg, fin, s));
+            } else {
+                NSTCHK(gram_of(ctx, op, fin, s));
             }
-            const int ns = gram_nsplit(st.C, st.N);
-            {
-                Timer t(ctx, s, K_GRAM, 2.0 * (double)st.N * st.C * st.C);
-                HIPCHK(ctx, launch_gram_partial(sc.acts.act[l], st.N, st.C, ns, ctx->conv_mode == 2 ? amax_act(sc.acts, l) : nullptr, part, s, nullptr, nullptr, ctx->gram_pack));
-            }
-            Timer t(ctx, s, K_OTHER, 0);
-            HIPCHK(ctx, launch_gram_finish_blend(part, gram_nslabs(st.C, ns), st.C, (float)st.divisor, bhat[k][q], written[q] ? 1 : 0,
-                                                 L.gram_t[q], s));
             written[q] = true;
         }
         NSTCHK(sc.finish());
@@ -1471,15 +1453,11 @@ int nst_level_set_targets_guided(nst_ctx* ctx, int level, const float* content, 
     for (int q = 0; q < tp.nstyle; ++q) {
         const int l = tp.style[q], C = kCout[l], scl = kScale[l];
         const size_t N = (size_t)sc.acts.h[l] * sc.acts.w[l];
-        const int ns = gram_nsplit(C, N);
         for (int r = 0; r < R; ++r) {
-            {
-                Timer t(ctx, s, K_GRAM, 2.0 * (double)N * C * C);
-                HIPCHK(ctx, launch_gram_partial(sc.acts.act[l], N, C, ns, amax_act(sc.acts, l), part, s, sp + off[scl] + (size_t)r * N, nullptr, ctx->gram_pack));
-            }
-            Timer t(ctx, s, K_OTHER, 0);
-            HIPCHK(ctx, launch_gram_finish_blend(part, gram_nslabs(C, ns), C, (float)((double)C * smass[scl][r]), 1.f, 0,
-                                                 g.gram_t[q] + (size_t)r * C * C, s));
+            GramFinish fin;
+            fin.gram_out = g.gram_t[q] + (size_t)r * C * C; fin.alpha = 1.f;
+            NSTCHK(gram_of(ctx, GramOperand{sc.acts.act[l], N, C, amax_act(sc.acts, l), sp + off[scl] + (size_t)r * N, part,
+                                            (float)((double)C * smass[scl][r])}, fin, s));
         }
     }
     NSTCHK(sc.finish());
@@ -1646,10 +1624,9 @@ int nst_window_begin(nst_ctx* ctx, const float* xs, int row0, int rows, int H0, 
         const int l = ctx->taps.style[q], C = kCout[l];
         const size_t off = (size_t)win_r0(win, kScale[l]) * a.w[l] * C;
         const size_t N = (size_t)win_nr(win, kScale[l]) * a.w[l];
-        const int ns = gram_nsplit(C, N);
-        HIPCHK(ctx, launch_gram_partial(a.act[l] + off, N, C, ns, amax_act(a, l), L.gram_part, s, nullptr, nullptr, ctx->gram_pack));
-        HIPCHK(ctx, launch_gram_finish(L.gram_part, gram_nslabs(C, ns), C, 1.f, nullptr, 0.f, sums + kWinGramOff[q], nullptr, nullptr,
-                                       nullptr, nullptr, s));
+        GramFinish fin;
+        fin.gram_out = sums + kWinGramOff[q];
+        NSTCHK(gram_of(ctx, GramOperand{a.act[l] + off, N, C, amax_act(a, l), nullptr, L.gram_part, 1.f}, fin, s, false));
     }
     // content: sum of squared differences over the owned rows
     {

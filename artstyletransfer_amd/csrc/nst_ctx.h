@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
+#include <optional>
 #include <string>
 #include <utility>
 #include <vector>
@@ -453,21 +454,32 @@ int forward(nst_ctx* ctx, ActSet& a, const float* x, int h, int w, hipStream_t s
 // channels = 1: gx is the gradient of a luminance plane (the sum over the three channels)
 int backward(nst_ctx* ctx, ActSet& a, const Inject* inj, const ContentJob* cj, float* gbuf0, float* gbuf1, float* gx,
              int h, int w, hipStream_t s, int top = NL - 1, bool top_mask = true, int channels = 3);
-// f_amax (nullable): absmax record of f_nhwc; with it the partial products run on the fp16 pipe
-int gram_of(nst_ctx* ctx, const float* f_nhwc, size_t N, int C, const unsigned* f_amax, float divisor, float* part, const float* target,
-            float coef, float* gram_out, float* S, unsigned short* S_bf, unsigned* S_amax, double* mse_partial,
-            hipStream_t s);
-// The shifted Gram of one map (nst_job_set_gram_shift): offsets and operand record (launch_gram_offsets) -> SHIFT partial
-// products -> the finish pass of gram_of (alpha < 0) or its blend form (gram_out = alpha G, or += when accumulate) -> the row
-// bias r = o S (when r and S are given).  offset: C floats, rec: NST_AMAX_SLOTS words, sums: GS_PART_DOUBLES doubles (a
-// centred map).  The fp16-piece kernels only: f_amax is required.
-struct ShiftedGram {
-    float shift; int center; float* offset; unsigned* rec; double* sums; float* r;
+// The Gram of one map, the one recipe of every caller outside the batched closure: the partial products (launch_gram_partial,
+// gram_nsplit(C, N) splits, timed as K_GRAM) and the finish pass over their slabs (timed as K_OTHER).
+struct GramOperand {
+    const float* f; size_t N; int C;     // NHWC map, N pixels x C
+    const unsigned* amax;                // nullable: absmax record of f; with it the partial products run on the fp16 pipe
+    const float* guide;                  // nullable: guidance plane t(p) of the N pixels (the guided Gram; amax required)
+    float* part;                         // slab workspace, gram_nsplit(C, N) x C x C floats
+    float divisor;
+    const float* offset = nullptr;       // gram_shifted_of only: o[C], `amax` then the record of the shifted operand
+};
+// What the finish pass makes of G = (sum of the slabs) / divisor.  alpha < 0, launch_gram_finish: gram_out = G, and with a
+// target S = coef (G - target) (S_bf / S_amax: its bf16 cut / absmax record) and the partial sums of (G - target)^2 - all
+// nullable.  alpha >= 0, launch_gram_finish_blend: gram_out = alpha G, or gram_out + alpha G when `accumulate`.
+struct GramFinish {
+    const float* target = nullptr; float coef = 0.f;
+    float* S = nullptr; unsigned short* S_bf = nullptr; unsigned* S_amax = nullptr; double* mse_partial = nullptr;
+    float* gram_out = nullptr;
     float alpha = -1.f; int accumulate = 0;
 };
-int gram_shifted_of(nst_ctx* ctx, const float* f_nhwc, size_t N, int C, const unsigned* f_amax, const ShiftedGram& sg, float divisor,
-                    float* part, const float* target, float coef, float* gram_out, float* S, unsigned short* S_bf, unsigned* S_amax,
-                    double* mse_partial, hipStream_t s);
+// timed = false: the two launches without their timers (nst_window_begin)
+int gram_of(nst_ctx* ctx, const GramOperand& op, const GramFinish& fin, hipStream_t s, bool timed = true);
+// The shifted Gram of one map (nst_job_set_gram_shift): offsets and operand record (launch_gram_offsets) -> gram_of on the
+// shifted operand -> the row bias r = o S (when r and fin.S are given).  offset: C floats, rec: NST_AMAX_SLOTS words, sums:
+// GS_PART_DOUBLES doubles (a centred map).  The fp16-piece kernels only: op.amax is required (op.guide / op.offset unused).
+struct ShiftedGram { float shift; int center; float* offset; unsigned* rec; double* sums; float* r; };
+int gram_shifted_of(nst_ctx* ctx, const GramOperand& op, const ShiftedGram& sg, const GramFinish& fin, hipStream_t s);
 // A full-resolution map of `level` that its last batched forward pass left out: that layer's launch again, over the levels
 // of that pass (same ConvBatch, so the same tile shape and summation order), with `out` set.  The pooled map, mask and code
 // words it rewrites are the values they hold; the absmax records stay (atomicMax of the same values).

@@ -63,7 +63,8 @@ constexpr int NST_AMAX_SLOTS = 64;
 #endif
 constexpr int NST_H2_SHORTK_CIN = NST_H2_SHORTK_CIN_VALUE;      // (-DNST_H2_SHORTK_CIN_VALUE=512: experiment builds)
 
-// One image (pyramid level) of a batched conv_bf3 launch; the layer's weights / channel counts are shared.
+// One image (pyramid level) of a batched conv_bf3 / conv_h2 launch; the layer's weights / channel counts are shared.  conv_h2
+// has no other form: a lone image, and each row band of one, is a batch of one.
 struct ConvImage {
     const float* in;
     const float* addend;
@@ -77,6 +78,7 @@ struct ConvImage {
     int H, W;
     int tiles_x, tile_end;   // filled by the launcher
     // conv_h2 only
+    int ty0;                 // first tile row of the image in this launch (filled by the launcher: 0, or a row band's first)
     const float* wt2_f32;
     const unsigned* amax_in;
     const unsigned* amax_in2;
@@ -125,16 +127,16 @@ int conv_bf3_ksplit(int H, int W, int Cin, int Cout);
 
 // conv_h2.hip: the same on the fp16 matrix pipe with 2-piece scaled operands (3 MFMAs per product block)
 hipError_t conv_h2_init_device();
-// The kernel shape a conv_h2 launch ran as - conv_h2_kernel<rows, bn, ntw, chunk> (conv_h2.hip lists the shapes) - and the
+// The kernel shape a conv_h2 launch ran as - conv_h2_batch_kernel<rows, bn, ntw, chunk> (conv_h2.hip lists the shapes) - and the
 // properties of the launch that entered the choice.  Decided in ONE place (h2_launch_shape) for both launchers, which hand it
 // back through `shape` (nullable): what the timing record of a launch keeps (nst_last_closure_launches).  rows = 0: not a
 // conv_h2 launch.
 struct H2Shape {
     int rows, bn, ntw, chunk;   // pixel rows of the workgroup tile (x 16 columns), output channels per tile, 32-channel tiles per wave, channels per K chunk
     int m16;                    // the 16x16x32 MFMA form
-    int persist;                // persistent workgroups (batched launches only)
+    int persist;                // persistent workgroups (launch_conv_h2_batch only)
     int second, unpool;         // the launch has a second K source / un-pools its input in the loader
-    int bands;                  // kernel launches it took (per-level launcher: row bands; else 1)
+    int bands;                  // kernel launches it took (per-level launcher: one one-image batch per row band; else 1)
 };
 hipError_t launch_conv_h2(const ConvParams& p, hipStream_t stream, H2Shape* shape = nullptr);
 hipError_t launch_conv_h2_batch(const ConvBatch& b, hipStream_t stream, H2Shape* shape = nullptr);

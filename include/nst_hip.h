@@ -816,8 +816,8 @@ int nst_timing_totals(nst_ctx* ctx, int cls, double* ms, long* launches, double*
 int nst_timing_mfma_flops(nst_ctx* ctx, int cls, double* mfma_flops);
 /* The timed launches of the last closure (timing mode 2), in launch order: up to `capacity` records into `out`, their
  * number into `count` (which may exceed capacity; 0 without a timed closure).  Read-only; waits for nothing.  h2_*: the kernel
- * shape the f16x2 direct-convolution launcher (conv_h2.hip) decided for the launch - conv_h2_kernel<h2_rows, h2_bn, h2_ntw,
- * h2_chunk> - as the launcher itself reported it; h2_rows = 0: another kernel ran (Winograd, conv1_1, Gram, streaming, or
+ * shape the f16x2 direct-convolution launcher (conv_h2.hip) decided for the launch - conv_h2_batch_kernel<h2_rows, h2_bn,
+ * h2_ntw, h2_chunk> - as the launcher itself reported it; h2_rows = 0: another kernel ran (Winograd, conv1_1, Gram, streaming, or
  * another arithmetic mode). */
 typedef struct nst_launch_info {
     int cls;                      /* kernel class, as in nst_last_closure_class */
