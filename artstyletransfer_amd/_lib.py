@@ -162,6 +162,7 @@ SYMBOLS = {
     "nst_last_closure_class": (C.c_int, [c_void, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int),
                                          C.POINTER(C.c_double)]),
     "nst_last_closure_launches": (C.c_int, [c_void, C.POINTER(LaunchInfo), C.c_int, C.POINTER(C.c_int)]),
+    "nst_last_closure_schedule": (C.c_int, [c_void, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "nst_dump_last_closure": (C.c_int, [c_void]),
     "nst_timing_totals": (C.c_int, [c_void, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_long),
                                     C.POINTER(C.c_double), C.c_int]),

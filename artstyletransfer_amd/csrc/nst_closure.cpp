@@ -573,6 +573,7 @@ int batched_forward(nst_ctx* ctx, const float* const* xi, const int* lv, int n, 
         if (l == 4 && fork_sw >= 0.f && ctx->side) {
             HIPCHK(ctx, hipEventRecord(ctx->side_fork, s));
             HIPCHK(ctx, hipStreamWaitEvent(ctx->side, ctx->side_fork, 0));
+            ++ctx->sched.side_forks;
             NSTCHK(batched_gram(ctx, lv, n, fork_sw, ctx->side, 0x07u));
             HIPCHK(ctx, hipEventRecord(ctx->side_join, ctx->side));
         }
@@ -1072,6 +1073,7 @@ int closure_record(nst_ctx* ctx, const float* x, float cw, float sw, float tvw, 
             // fill one another, as two jobs on one GPU do.  Same kernels on the same tiles: bitwise the same.
             HIPCHK(ctx, hipEventRecord(ctx->side_fork, main));
             HIPCHK(ctx, hipStreamWaitEvent(ctx->side, ctx->side_fork, 0));
+            ++ctx->sched.side_forks;
             NSTCHK(batched(top, main, 1u));
             NSTCHK(batched(rest, ctx->side, ~1u));
             HIPCHK(ctx, hipEventRecord(ctx->side_join, ctx->side));
@@ -1089,6 +1091,7 @@ int closure_record(nst_ctx* ctx, const float* x, float cw, float sw, float tvw, 
             if (!L.done) HIPCHK(ctx, hipEventCreateWithFlags(&L.done, hipEventDisableTiming));
         }
         HIPCHK(ctx, hipEventRecord(ctx->fork, main));
+        ctx->sched.level_streams = ctx->levels;
     }
     for (int i = 0; i < ctx->levels && !batch; ++i) {
         LevelWs& L = ctx->lv[i];
@@ -1503,6 +1506,7 @@ int nst_closure_levels(nst_ctx* ctx, const float* x, float cw, float sw, float t
     if (!x || !grad || !losses) return fail(ctx, NST_E_ARG, "null buffer");
     NSTCHK(closure_targets_check(ctx, level_mask));
     hipStream_t main = enter(ctx, stream);
+    ctx->sched = {};
     if (ctx->timing >= 2) NSTCHK(fold_timed(ctx));
     ctx->timed.clear();
     ctx->ev_used = 0;
@@ -1537,6 +1541,8 @@ int nst_closure_levels(nst_ctx* ctx, const float* x, float cw, float sw, float t
             ctx->gkey = key;
         }
         HIPCHK(ctx, hipGraphLaunch(ctx->gexec, main));
+        ctx->sched = {};                 // (what closure_record counted while capturing describes the capture, not this launch)
+        ctx->sched.graph_replay = 1;
         done = true;
     }
     if (!done) NSTCHK(closure_record(ctx, x, cw, sw, tvw, level_mask, grad, losses, main));
@@ -1560,6 +1566,7 @@ int nst_closure_forward(nst_ctx* ctx, const float* x, float cw, float sw, float 
     if (!batch_eligible(ctx) || ctx->use_graph)
         return fail(ctx, NST_E_UNAVAILABLE, "the closure halves run on the batched schedule without a hipGraph only: use nst_closure");
     hipStream_t main = enter(ctx, stream);
+    ctx->sched = {};
     if (ctx->timing >= 2) NSTCHK(fold_timed(ctx));
     ctx->timed.clear();
     ctx->ev_used = 0;
@@ -1587,6 +1594,7 @@ int nst_closure_backward(nst_ctx* ctx, const float* x, float cw, float sw, float
     ++ctx->ws_seq;               // (one backward per forward: the gradient buffers of the levels are consumed)
     ctx->fwd_token.valid = false;
     hipStream_t main = enter(ctx, stream);
+    ctx->sched = {};
     // timing: the forward half's record is folded as a closure, this half's launches and time then join the totals
     if (ctx->timing >= 2) NSTCHK(fold_timed(ctx));
     ctx->timed.clear();

@@ -1046,6 +1046,15 @@ int nst_last_closure_launches(nst_ctx* ctx, nst_launch_info* out, int capacity, 
     return NST_OK;
 }
 
+// what the last nst_closure* call did with streams and graphs: host counters of the context, nothing is launched or waited for
+int nst_last_closure_schedule(const nst_ctx* ctx, int* side_forks, int* level_streams, int* graph_replay) {
+    if (!ctx) return fail(nullptr, NST_E_ARG, "null context");
+    if (side_forks) *side_forks = ctx->sched.side_forks;
+    if (level_streams) *level_streams = ctx->sched.level_streams;
+    if (graph_replay) *graph_replay = ctx->sched.graph_replay;
+    return NST_OK;
+}
+
 // debugging aid: one line per timed launch of the last closure to stderr
 int nst_dump_last_closure(nst_ctx* ctx) {
     NSTCHK(bind(ctx));

@@ -343,6 +343,9 @@ struct nst_ctx {
     size_t bytes = 0;           // nst_ctx_bytes: what dev_alloc charged and dev_release has not yet credited
     nst::DevMem mem;            // owns the context's own buffers: weight images, biases, w11k / w11d, color_scratch
     bool single_stream = false;
+    // nst_last_closure_schedule: what the last nst_closure* call did - host integers, counted where the forks are recorded
+    // (closure_record, batched_forward) and where a captured graph is launched; no launch or stream depends on them
+    struct ClosureSchedule { int side_forks = 0, level_streams = 0, graph_replay = 0; } sched;
     // timing
     int timing = 0;
     hipEvent_t t0 = nullptr, t1 = nullptr;

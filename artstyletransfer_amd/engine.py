@@ -655,6 +655,14 @@ class StyleEngine:
         _lib.check(self.ctx, self.lib.nst_last_closure_launches(self.ctx, buf, n.value, C.byref(n)), "nst_last_closure_launches")
         return [{name: getattr(buf[i], name) for name, _ in _lib.LaunchInfo._fields_} for i in range(n.value)]
 
+    def last_closure_schedule(self) -> dict:
+        """What the last closure call did with streams and graphs (nst_last_closure_schedule): side_forks, level_streams,
+        graph_replay.  Reads host integers of the context: no launch, no wait, no timing mode needed."""
+        forks, streams, replay = C.c_int(), C.c_int(), C.c_int()
+        _lib.check(self.ctx, self.lib.nst_last_closure_schedule(self.ctx, C.byref(forks), C.byref(streams), C.byref(replay)),
+                   "nst_last_closure_schedule")
+        return {"side_forks": forks.value, "level_streams": streams.value, "graph_replay": replay.value}
+
     def timing_totals(self, cls: int, reset: bool = False):
         """(ms, launches, flops) accumulated since the last reset; cls -1 = whole closures."""
         ms, n, fl = C.c_double(), C.c_long(), C.c_double()

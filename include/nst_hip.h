@@ -103,7 +103,8 @@ typedef struct nst_options {
                              costs more than the hidden prologues gain) */
     int level_split;      /* f16x2 batched closure: 1 = the top pyramid level's chain on the caller's stream and the lower levels'
                              chain on a side stream of the context, joined before the gradients are merged; 0 = one launch per
-                             layer over all levels; -1: env NST_LEVEL_SPLIT, default 0 */
+                             layer over all levels; -1: env NST_LEVEL_SPLIT, default 0.  The context has ONE side
+                             stream: level_split = 1 switches gram_overlap off, whatever that field or NST_GRAM_OVERLAP says */
     int h2_winograd;      /* f16x2 batched closure: 1 = the forward and input-gradient launches with Cin >= 256 and Cout a
                              multiple of 128 that have no second (Gram) source - 15 of the 24 of a closure - run as a 1-D Winograd
                              F(2,3) along x (conv_wino.hip: 1.5x fewer MFMAs there; the feature maps are no further from an fp64
@@ -325,8 +326,11 @@ int nst_job_matting_losses(nst_ctx* ctx, float* out /* device, levels */, void* 
  * every level's targets (they are made with the statistic) and any captured closure graph, and ends the validity of an
  * optimiser's remembered closure and of a pending nst_closure_backward.  Every buffer of the option is allocated here,
  * never in a closure.  nst_job_configure clears the setting.  The work belongs to the forward half of the closure.  It
- * composes with any taps, colour mode, pooling, style layer weights, blends, the Laplacian loss, both schedules, the
- * closure halves and level sharding.  While it is non-trivial, nst_level_set_guidance (R > 0),
+ * composes with any taps, colour mode, pooling, style layer weights, blends, the Laplacian loss, the closure halves, level
+ * sharding and every f16x2 schedule - batched and per level (single_stream and h2_band_rows included), use_graph,
+ * gram_overlap (its offset and row-bias launches ride with the Gram batch of their maps, on either stream), level_split,
+ * h2_persist, keep_all_maps, forward_pack = 0, gram_pack = 0 - with the bits of the default schedule (level_split: of the two
+ * masked closures its chains are); tests/test_hip_schedule_matrix.py holds each.  While it is non-trivial, nst_level_set_guidance (R > 0),
  * nst_level_set_targets_guided and nst_window_* return NST_E_STATE.
  * nst_job_gram_shift: the current setting (either pointer may be NULL).
  * nst_level_gram_offsets: the o that the level's last closure used for style slot `slot` (ascending map order of the
@@ -381,8 +385,11 @@ int nst_gram_shifted(nst_ctx* ctx, const float* f, int C, int h, int w, int norm
  * nst_closure_backward.  Every buffer of the term is allocated here, never in a closure.  nst_job_configure clears the
  * setting.  The work belongs to the forward half of the closure.  It composes with any taps (pre-ReLU included; a weight
  * on a map that later taps leave out is ignored), colour mode, pooling, style layer weights, blends, the Laplacian loss,
- * the matting term, the Gram shift, both schedules, the closure halves, closure reuse, the lazy backward and level
- * sharding.  While a weight is positive, nst_level_set_guidance (R > 0), nst_level_set_targets_guided and nst_window_*
+ * the matting term, the Gram shift, the closure halves, closure reuse, the lazy backward, level sharding and every f16x2
+ * schedule - batched and per level (single_stream and h2_band_rows included), use_graph, gram_overlap (the statistics and
+ * fold launches ride with the Gram batch of their maps, on either stream), level_split, h2_persist, keep_all_maps,
+ * forward_pack = 0, gram_pack = 0 - with the bits of the default schedule (level_split: of the two masked closures its chains
+ * are); tests/test_hip_schedule_matrix.py holds each.  While a weight is positive, nst_level_set_guidance (R > 0), nst_level_set_targets_guided and nst_window_*
  * return NST_E_STATE.
  * nst_job_moments: the current setting (any pointer may be NULL).
  * nst_job_moment_losses: the unweighted (mean_i, std_i) of the last closure, to out (DEVICE, levels x 6 x 2 floats, by map
@@ -831,6 +838,21 @@ typedef struct nst_launch_info {
     int h2_bands;                 /* kernel launches it took (row bands of the per-level launcher; else 1) */
 } nst_launch_info;
 int nst_last_closure_launches(nst_ctx* ctx, nst_launch_info* out, int capacity, int* count);
+/* What the last nst_closure, nst_closure_levels, nst_closure_forward or nst_closure_backward call on `ctx` did with streams
+ * and graphs (any pointer may be NULL; zeros before the first such call; a call refused before it launched anything leaves
+ * the record of the call before it).  Host integers of the context: the call reads state only - it launches nothing, waits
+ * for nothing, needs no timing mode, and between nst_closure_forward and nst_closure_backward it leaves the backward half
+ * valid.
+ *   side_forks:    forks onto the context's side stream.  gram_overlap: 1 where the overlap ran, 0 where it fell back
+ *                  (non-default taps, guided levels, use_graph, another arithmetic than f16x2).  level_split: 1 when the
+ *                  level mask holds level 0 and a lower level, else 0.  level_split switches gram_overlap off (one side
+ *                  stream), so both together report what level_split alone reports.
+ *   level_streams: per-level streams the call forked to - the number of levels on the per-level schedule with more than
+ *                  one level and single_stream = 0, else 0.
+ *   graph_replay:  1 when the call was served by launching the captured hipGraph (use_graph: from the second consecutive
+ *                  call with the same arguments on), 0 when its launches were enqueued one by one.  The fork counts of
+ *                  such a call are 0: a captured closure stays on one stream. */
+int nst_last_closure_schedule(const nst_ctx* ctx, int* side_forks, int* level_streams, int* graph_replay);
 /* debugging aid: prints one line per timed launch of the last closure (timing mode 2) to stderr */
 int nst_dump_last_closure(nst_ctx* ctx);
 

@@ -29,10 +29,14 @@ SENTINEL = -12345.0
 TAP_LAYER = (0, 2, 4, 8, 9, 12)              # conv layer of the six maps of Vgg19.layer_names
 W_ONE = (1.0, 0.5, 2.0, 0.25, 1.0, 0.0)      # style layer weights: every tap set of the stations keeps a positive map under either
 W_TWO = (0.0, 1.5, 0.75, 3.0, 1.0, 0.5)
+# moment loss (set_moments): (weights of the mean terms, of the deviation terms) by map index; a map with both, with one, with neither
+M_ONE = ((1e3, 0.0, 5e2, 1e3, 0.0, 2e3), (1e3, 7e2, 0.0, 1e3, 0.0, 2e3))
+M_TWO = ((0.0, 8e2, 1e3, 0.0, 0.0, 5e2), (2e3, 0.0, 1e3, 6e2, 0.0, 0.0))
+M_TAPS = ((0.0, 5e2, 0.0, 1e3, 0.0, 2e3), (0.0, 7e2, 0.0, 0.0, 0.0, 2e3))      # on the style maps of taps (1, 3, 5) only
 
 Station = collections.namedtuple(
-    "Station", "name h w nlev hs ws seed amp taps color pooling style_weights laplacian matting gram_shift guidance blend eval",
-    defaults=(0, None, "rgb", "max", None, None, None, None, None, None, ("closure",)))
+    "Station", "name h w nlev hs ws seed amp taps color pooling style_weights laplacian matting gram_shift guidance blend eval moments",
+    defaults=(0, None, "rgb", "max", None, None, None, None, None, None, ("closure",), None))
 
 # guidance: (split direction, region weights); blend: the `blend` argument of set_targets_blend for K = 2
 STATIONS = (
@@ -55,10 +59,18 @@ STATIONS = (
     Station("rgb_lap_mat", 64, 96, 2, 56, 88, 1, laplacian=((1, 2), (5.0, 60.0)), matting=(2.8e8, 1e-7)),
     Station("weights_level0", 64, 96, 2, 56, 88, 1, style_weights=W_ONE, eval=("levels", 0b01)),
     Station("adam_lum", 50, 76, 1, 40, 60, 11, color="luminance", eval=("adam",)),
+    # the moment loss: alone; under a centred Gram shift, a blend, unequal style weights and average pooling; under luminance with
+    # the two pixel-space terms; on non-default taps whose deepest map is taken before its ReLU
+    Station("moments3", 68, 260, 3, 80, 120, 1, moments=M_ONE),
+    Station("mom_shift_blend_avg", 124, 252, 2, 100, 180, 3, pooling="avg", style_weights=W_TWO,
+            gram_shift=(0.5, "mean", 0.0, "mean", 0.0, -0.25), blend=(0.25, 0.75), moments=M_TWO),
+    Station("mom_lum_lap_mat", 64, 96, 2, 56, 88, 5, color="luminance", laplacian=((1, 2), (3.0, 40.0)), matting=(2.8e8, 1e-7),
+            moments=M_ONE),
+    Station("mom_taps_norelu", 64, 96, 2, 56, 88, 7, taps=(4, (1, 3, 5), False), moments=M_TAPS),
 )
 BY_NAME = {s.name: s for s in STATIONS}
 AMPLITUDE = ("plain3", "plain3_hi", "plain3_lo")
-SETTERS = ("taps", "color", "pooling", "style_weights", "laplacian", "matting", "gram_shift", "guidance", "blend")
+SETTERS = ("taps", "color", "pooling", "style_weights", "laplacian", "matting", "gram_shift", "guidance", "blend", "moments")
 EVAL_KINDS = ("closure", "levels", "halves", "window", "adam", "lbfgs")
 
 VARIANTS = collections.OrderedDict((
@@ -78,19 +90,22 @@ def is_set(st, setter):
 def kept(variant):
     """The stations of an engine variant.  Left out: the halves where nst_closure_forward is unavailable (the per-level schedule -
     test_forward_half_is_unavailable_off_the_batched_schedule - and use_graph, include/nst_hip.h), and outside the f16x2 arithmetic
-    the shifted Gram, spatial control and the stripe closure, which all return NST_E_STATE there."""
+    the shifted Gram, the moment loss, spatial control and the stripe closure, which all return NST_E_STATE there."""
     opts = VARIANTS[variant]
     no_halves = opts.get("batched") is False or opts.get("use_graph")
     f16x2 = opts.get("conv_mode") is None
     return tuple(s.name for s in STATIONS
                  if not (no_halves and s.eval[0] == "halves")
-                 and (f16x2 or not (s.gram_shift or s.guidance or s.eval[0] == "window")))
+                 and (f16x2 or not (s.gram_shift or s.moments or s.guidance or s.eval[0] == "window")))
 
 
-_ORDER_A = ("rgb_lap_mat", "plain3_hi", "plain3_lo", "plain3", "adam_lum", "avg_guided", "small_lap_blend", "shift_blend", "lum_lap_mat",
-            "shift_taps", "stripes", "lum_avg_mat", "six_norelu", "lbfgs", "guided_rgb", "weights_level0")
-_ORDER_B = ("lbfgs", "plain3_lo", "plain3_hi", "adam_lum", "six_norelu", "small_lap_blend", "plain3", "weights_level0", "shift_blend",
-            "guided_rgb", "avg_guided", "lum_lap_mat", "stripes", "shift_taps", "lum_avg_mat", "rgb_lap_mat")
+# (the moment stations: after and before the plain job of their geometry, a guided job, a shifted one, and each other)
+_ORDER_A = ("rgb_lap_mat", "plain3_hi", "plain3_lo", "plain3", "moments3", "adam_lum", "avg_guided", "mom_taps_norelu", "small_lap_blend",
+            "shift_blend", "mom_shift_blend_avg", "lum_lap_mat", "shift_taps", "stripes", "lum_avg_mat", "mom_lum_lap_mat", "six_norelu",
+            "lbfgs", "guided_rgb", "weights_level0")
+_ORDER_B = ("lbfgs", "mom_lum_lap_mat", "plain3_lo", "plain3_hi", "adam_lum", "six_norelu", "moments3", "small_lap_blend", "plain3",
+            "weights_level0", "shift_blend", "guided_rgb", "mom_shift_blend_avg", "mom_taps_norelu", "avg_guided", "lum_lap_mat",
+            "stripes", "shift_taps", "lum_avg_mat", "rgb_lap_mat")
 ORDERS = collections.OrderedDict((
     ("a", _ORDER_A),
     ("b", _ORDER_B),
@@ -121,13 +136,14 @@ DISTURBANCES = collections.OrderedDict((
     ("gram_shifted64", "a"), ("gram_shifted256", "a"), ("guided_gram_backward", "a"), ("total_variation", "a"),
     ("laplacian_loss", "a"), ("matting_loss", "a"), ("bicubic_half", "a"), ("bicubic_half_backward", "a"), ("resize", "a"),
     ("color_stats", "a"), ("color_affine", "a"), ("luminance", "a"), ("adam_step", "a"), ("lbfgs_direction", "a"),
-    ("refused_backward", "a"),
+    ("refused_backward", "a"), ("moments", "a"),
     ("abandoned_forward", "b"), ("refused_configure", "b"), ("refused_gram_shift", "b"), ("timed_closure", "b"),
-    ("level_activations0", "b"),
+    ("level_activations0", "b"), ("refused_moments", "b"),
 ))
 # between the halves only: read-backs of the job
 READ_BACKS = collections.OrderedDict((
     ("level_image", "a"), ("laplacian_losses", "a"), ("matting_losses", "a"), ("level_gram_offsets", "a"), ("guidance_planes", "a"),
+    ("moment_losses", "a"), ("closure_schedule", "a"),
     ("level_activation", "b"),
 ))
 PICKS = 3
@@ -181,6 +197,17 @@ def test_plan_stations_hold_every_setter_combination_and_evaluation():
     assert any(s.pooling == "avg" and s.guidance for s in STATIONS)
     assert any(s.gram_shift and s.blend for s in STATIONS)
     assert any(s.gram_shift and not s.blend and not s.guidance for s in STATIONS)
+    for s in STATIONS:
+        if s.moments:                                                      # only on style maps of the station's taps, never guided
+            live = s.taps[1] if s.taps else (0, 1, 2, 3, 5)
+            assert all(i in live for wts in s.moments[:2] for i, v in enumerate(wts) if v > 0) and not s.guidance, s.name
+            assert any(v > 0 for v in s.moments[0]) and any(v > 0 for v in s.moments[1]), s.name
+    mom = [s for s in STATIONS if s.moments]
+    assert any(not any(is_set(s, k) for k in SETTERS if k != "moments") and (s.h, s.w, s.nlev) == (68, 260, 3) for s in mom)
+    assert any(s.gram_shift and "mean" in s.gram_shift and s.blend and s.style_weights and s.pooling == "avg"
+               and (s.h, s.w, s.nlev) == (124, 252, 2) for s in mom)
+    assert any(s.color == "luminance" and s.laplacian and s.matting and (s.h, s.w, s.nlev) == (64, 96, 2) for s in mom)
+    assert any(s.taps and s.taps[2] is False and 5 in s.taps[1] and s.moments[0][5] > 0 for s in mom)
     base = BY_NAME["plain3"]
     assert [BY_NAME[n].amp for n in AMPLITUDE] == [0, 4, -10]
     assert all(BY_NAME[n]._replace(name="", amp=0) == base._replace(name="") for n in AMPLITUDE)
@@ -226,7 +253,7 @@ def test_plan_orders_give_every_station_two_predecessors_and_every_setter_both_p
         assert all(len(pred[n]) >= 2 for n in names), (variant, {n: pred[n] for n in names if len(pred[n]) < 2})
         for setter in SETTERS:
             if not any(is_set(BY_NAME[n], setter) for n in names):
-                assert variant == "f32_per_level" and setter in ("gram_shift", "guidance")
+                assert variant == "f32_per_level" and setter in ("gram_shift", "guidance", "moments")
                 continue
             pasts = {(is_set(BY_NAME[a], setter), is_set(BY_NAME[b], setter)) for a, b in pairs}
             assert {(True, True), (False, True), (True, False)} <= pasts, (variant, setter)
@@ -304,8 +331,9 @@ def _apply_settings(eng, st):
     eng.set_laplacian(*st.laplacian) if st.laplacian else eng.reset_laplacian()
     eng.set_matting(*st.matting) if st.matting else eng.reset_matting()
     eng.set_gram_shift(list(st.gram_shift)) if st.gram_shift else eng.reset_gram_shift()
+    eng.set_moments(*st.moments) if st.moments else eng.reset_moments()
     return repr((eng.levels, eng.shape, eng.lib.nst_job_color(eng.ctx), eng.lib.nst_job_pooling(eng.ctx), eng.style_weights(),
-                 eng.laplacian_setting(), eng.matting_setting(), eng.gram_shift_setting(),
+                 eng.laplacian_setting(), eng.matting_setting(), eng.gram_shift_setting(), eng.moments_setting(),
                  [eng.guidance(l)[0] for l in range(st.nlev)], [eng.map_stats(l) for l in range(st.nlev)]))
 
 
@@ -396,6 +424,8 @@ def _evaluate(eng, st, graph):
         out["laplacian_losses()"] = _bits(eng.laplacian_losses())
     if st.matting:
         out["matting_losses()"] = _bits(eng.matting_losses())
+    if st.moments:
+        out["moment_losses()"] = _bits(eng.moment_losses())
     lv = [l for l in range(st.nlev) if (mask >> l) & 1]
     if st.gram_shift:
         for l in lv:
@@ -448,6 +478,10 @@ def _guard(st, res):
         assert (_floats(res["laplacian_losses()"]).reshape(st.nlev, 4)[lv][:, :2] > 0).all(), st.name
     if st.matting:
         assert (_floats(res["matting_losses()"])[lv] > 0).all(), st.name
+    if st.moments:                                                          # every weighted (level, map, term) entry
+        ml = _floats(res["moment_losses()"]).reshape(st.nlev, 6, 2)[lv]
+        on = np.stack([np.array(st.moments[0]) > 0, np.array(st.moments[1]) > 0], axis=1)
+        assert np.isfinite(ml).all() and (ml[:, on] > 0).all(), (st.name, ml)
     if st.gram_shift:
         assert any(res[k].any() for k in res if "gram offsets" in k), st.name
     assert all(res[k].any() for k in res if "activation" in k), st.name
@@ -574,6 +608,21 @@ def disturb(eng, name, x, variant):
         assert eng.lib.nst_job_configure(eng.ctx, 9, 4096, 4096) == _lib.NST_E_ARG
     elif name == "refused_gram_shift":
         assert eng.lib.nst_job_set_gram_shift(eng.ctx, (C.c_float * 6)(0.0, float("nan"), 0.0, 0.0, 0.0, 0.0), 0) == _lib.NST_E_ARG
+    elif name == "moments":
+        res = list(eng.moments(f["f64"])) + list(eng.moments(f["f256"], 1e-3))
+    elif name == "refused_moments":
+        # a positive weight while a level is guided: NST_E_STATE; elsewhere a NaN weight: NST_E_ARG - "with nothing changed"
+        one = (C.c_float * 6)(1.0, 0.0, 0.0, 0.0, 0.0, 0.0)
+        before = eng.moments_setting()
+        if eng.levels and eng.guidance(0)[0]:
+            assert eng.lib.nst_job_set_moments(eng.ctx, one, one, 1e-5) == _lib.NST_E_STATE
+        else:
+            assert eng.lib.nst_job_set_moments(eng.ctx, (C.c_float * 6)(0.0, float("nan"), 0.0, 0.0, 0.0, 0.0), one, 1e-5) == _lib.NST_E_ARG
+        assert eng.moments_setting() == before
+    elif name == "moment_losses":
+        eng.moment_losses()
+    elif name == "closure_schedule":
+        assert set(eng.last_closure_schedule()) == {"side_forks", "level_streams", "graph_replay"}
     elif name == "timed_closure":
         eng.set_timing(2)
         try:
@@ -700,12 +749,12 @@ def _set_up(eng, name):
 
 
 @gpu
-@pytest.mark.parametrize("job", ("rgb_lap_mat", "shift_taps", "guided_rgb"))
+@pytest.mark.parametrize("job", ("rgb_lap_mat", "shift_taps", "guided_rgb", "mom_lum_lap_mat"))
 def test_one_call_between_the_halves(eng, vgg_weights, job):
     """closure_forward(x), ONE other call, closure_backward(x) into a sentinel-filled buffer.  Contract (a): the gradient is bitwise
     nst_closure's (the fresh engine's).  Contract (b): NST_E_STATE, the buffer untouched, and the next closure gives the fresh
-    bits.  rgb_lap_mat (64x96 L2, Laplacian and matting on) takes every call; the shifted and the guided job take the read-backs
-    that need them."""
+    bits.  rgb_lap_mat (64x96 L2, Laplacian and matting on) takes every call; the shifted, the guided and the moment job take
+    the read-backs and refusals that need them (the moment job: its row biases and folded S wait between the halves)."""
     from artstyletransfer_amd import _lib
     ref = fresh("default", vgg_weights)[job]
     st, x = _set_up(eng, job)
@@ -713,7 +762,9 @@ def test_one_call_between_the_halves(eng, vgg_weights, job):
     if job == "shift_taps":
         calls = [("level_gram_offsets", "a"), ("level_activation", "b")]
     elif job == "guided_rgb":
-        calls = [("guidance_planes", "a"), ("level_image", "a")]
+        calls = [("guidance_planes", "a"), ("level_image", "a"), ("refused_moments", "b")]     # (refused BECAUSE the level is guided)
+    elif job == "mom_lum_lap_mat":
+        calls = [("moment_losses", "a"), ("closure_schedule", "a"), ("moments", "a"), ("laplacian_losses", "a"), ("refused_moments", "b")]
     bad = []
     for name, contract in calls:
         eng.closure_forward(x, CW, SW, TVW)
