@@ -15,9 +15,9 @@
 #include <new>
 #include <string>
 
-#include "../../include/nst_hip.h"
+#include "nst_ctx.h"
 
-extern "C" int nst_internal_fail(nst_ctx* ctx, int code, const char* msg);
+using nst::fail;
 
 namespace {
 
@@ -58,7 +58,7 @@ Api& api() {
 
 int rccl_fail(const char* what, int rc) {
     Api& a = api();
-    return nst_internal_fail(nullptr, NST_E_HIP, (std::string(what) + ": " + (a.GetErrorString ? a.GetErrorString(rc) : "?")).c_str());
+    return fail(nullptr, NST_E_HIP, std::string(what) + ": " + (a.GetErrorString ? a.GetErrorString(rc) : "?"));
 }
 
 }  // namespace
@@ -73,9 +73,9 @@ struct nst_comm {
 extern "C" {
 
 int nst_comm_unique_id(void* id) {
-    if (!id) return nst_internal_fail(nullptr, NST_E_ARG, "null argument");
+    if (!id) return fail(nullptr, NST_E_ARG, "null argument");
     Api& a = api();
-    if (!a.ok) return nst_internal_fail(nullptr, NST_E_STATE, a.why.c_str());
+    if (!a.ok) return fail(nullptr, NST_E_STATE, a.why);
     UniqueId u;
     const int rc = a.GetUniqueId(&u);
     if (rc != 0) return rccl_fail("ncclGetUniqueId", rc);
@@ -84,12 +84,12 @@ int nst_comm_unique_id(void* id) {
 }
 
 int nst_comm_create(int device, int rank, int world, const void* id, nst_comm** out) {
-    if (!id || !out || world < 1 || rank < 0 || rank >= world) return nst_internal_fail(nullptr, NST_E_ARG, "bad communicator arguments");
+    if (!id || !out || world < 1 || rank < 0 || rank >= world) return fail(nullptr, NST_E_ARG, "bad communicator arguments");
     Api& a = api();
-    if (!a.ok) return nst_internal_fail(nullptr, NST_E_STATE, a.why.c_str());
-    if (hipSetDevice(device) != hipSuccess) return nst_internal_fail(nullptr, NST_E_HIP, "hipSetDevice failed");
+    if (!a.ok) return fail(nullptr, NST_E_STATE, a.why);
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, NST_E_HIP, "hipSetDevice failed");
     nst_comm* c = new (std::nothrow) nst_comm();
-    if (!c) return nst_internal_fail(nullptr, NST_E_NOMEM, "out of host memory");
+    if (!c) return fail(nullptr, NST_E_NOMEM, "out of host memory");
     c->device = device; c->rank = rank; c->world = world;
     UniqueId u;
     std::memcpy(u.internal, id, NST_COMM_ID_BYTES);
@@ -107,7 +107,7 @@ void nst_comm_destroy(nst_comm* c) {
 }
 
 int nst_comm_info(const nst_comm* c, int* rank, int* world, long* calls, double* bytes) {
-    if (!c) return nst_internal_fail(nullptr, NST_E_ARG, "null communicator");
+    if (!c) return fail(nullptr, NST_E_ARG, "null communicator");
     if (rank) *rank = c->rank;
     if (world) *world = c->world;
     if (calls) *calls = c->calls;
@@ -116,8 +116,8 @@ int nst_comm_info(const nst_comm* c, int* rank, int* world, long* calls, double*
 }
 
 int nst_comm_allreduce_sum(nst_comm* c, float* buf, size_t n, void* stream) {
-    if (!c || !buf) return nst_internal_fail(nullptr, NST_E_ARG, "null argument");
-    if (hipSetDevice(c->device) != hipSuccess) return nst_internal_fail(nullptr, NST_E_HIP, "hipSetDevice failed");
+    if (!c || !buf) return fail(nullptr, NST_E_ARG, "null argument");
+    if (hipSetDevice(c->device) != hipSuccess) return fail(nullptr, NST_E_HIP, "hipSetDevice failed");
     const int rc = api().AllReduce(buf, buf, n, /*ncclFloat32*/ 7, /*ncclSum*/ 0, c->comm, static_cast<hipStream_t>(stream));
     if (rc != 0) return rccl_fail("ncclAllReduce", rc);
     c->calls += 1;

@@ -25,7 +25,8 @@ int nst::fail(nst_ctx* ctx, int code, const std::string& msg) {
     return code;
 }
 
-namespace {
+namespace nst {
+
 // Debugging aid (tools/check_uninit_reads.py): NST_POISON_ALLOC=all | <first>-<last> fills the allocations with those
 // sequence numbers with 0xFF bytes (NaN as floats, all-ones as masks), so that a kernel which reads memory nobody wrote -
 // harmless on a fresh process, whose pages arrive zeroed, and wrong once the allocator recycles another context's blocks -
@@ -41,13 +42,12 @@ void poison_if_asked(void* p, size_t bytes) {
     if (k >= lo && k <= hi) { (void)hipMemset(p, 0xFF, bytes); (void)hipStreamSynchronize(nullptr); }
     if (getenv("NST_POISON_TRACE")) fprintf(stderr, "nst alloc #%ld: %zu bytes%s\n", k, bytes, (k >= lo && k <= hi) ? " (poisoned)" : "");
 }
-}  // namespace
 // hipMemset on device memory is enqueued on the NULL stream and returns before it has run: with another context's work
 // queued there (two jobs per GPU is the scheduler's default) it lands AFTER the first kernels of this context, which run on
 // the caller's non-blocking stream - and wipes what they wrote (absmax records -> a zero scale -> NaN targets; Adam
 // moments; the packed loss rows).  Set-up-time zero fills therefore run on a stream of their own and are waited for:
 // nothing of a context rides on the null stream.
-extern "C" int nst_internal_zero_now(void* p, size_t bytes) {
+int zero_now(void* p, size_t bytes) {
     hipStream_t zs = nullptr;
     hipError_t e = hipStreamCreateWithFlags(&zs, hipStreamNonBlocking);
     if (e != hipSuccess) return 1;
@@ -56,8 +56,6 @@ extern "C" int nst_internal_zero_now(void* p, size_t bytes) {
     (void)hipStreamDestroy(zs);
     return e == hipSuccess ? 0 : 1;
 }
-
-namespace nst {
 
 int dev_alloc(nst_ctx* ctx, void** p, size_t bytes, size_t* charged) {
     if (bytes == 0) bytes = 16;
@@ -105,7 +103,7 @@ int alloc_acts(nst_ctx* ctx, ActSet& a, int h, int w) {
         NSTCHK(a.mem.alloc(ctx, &a.bits[m], nw));
     }
     NSTCHK(a.mem.alloc(ctx, &a.amax, (size_t)AMAX_IDS * NST_AMAX_SLOTS));
-    if (nst_internal_zero_now(a.amax, (size_t)AMAX_IDS * NST_AMAX_SLOTS * 4)) return fail(ctx, NST_E_HIP, "hipMemset failed");
+    if (zero_now(a.amax, (size_t)AMAX_IDS * NST_AMAX_SLOTS * 4)) return fail(ctx, NST_E_HIP, "hipMemset failed");
     a.splitk_floats = need;
     if (need) NSTCHK(a.mem.alloc(ctx, &a.splitk, need));
     return NST_OK;
@@ -1099,15 +1097,9 @@ int nst_timing_mfma_flops(nst_ctx* ctx, int cls, double* mfma_flops) {
     return NST_OK;
 }
 
-// ---- internal accessors for nst_opt.cpp (not part of the public ABI) --------------------------------
-int nst_internal_device(const nst_ctx* ctx) { return ctx ? ctx->device : 0; }
-int nst_internal_levels(const nst_ctx* ctx) { return ctx ? ctx->levels : 0; }
-int nst_internal_channels(const nst_ctx* ctx) { return ctx ? ctx->channels : 3; }
-size_t nst_internal_pixels(const nst_ctx* ctx) { return (ctx && ctx->levels > 0) ? (size_t)ctx->lv[0].h * ctx->lv[0].w : 0; }
-int nst_internal_fail(nst_ctx* ctx, int code, const char* msg) { return fail(ctx, code, msg ? msg : ""); }
-void nst_internal_poison(void* p, size_t bytes) { poison_if_asked(p, bytes); }
+// ---- not part of the public ABI ------------------------------------------------------------------
 // test hooks (tests/test_hip_unread_maps.py): the raw NHWC buffer of one feature map filled with a byte / copied to `dst`
-// (device memory), on a stream of their own and waited for - see nst_internal_zero_now
+// (device memory), on a stream of their own and waited for - see zero_now
 int nst_internal_map_fill(nst_ctx* ctx, int level, int layer, int byte) {
     if (!ctx || level < 0 || level >= ctx->levels || layer < 0 || layer >= NL) return 1;
     const ActSet& a = ctx->lv[level].acts;
@@ -1134,8 +1126,5 @@ int nst_internal_map_read(nst_ctx* ctx, int level, int layer, void* dst) {
     (void)hipStreamDestroy(zs);
     return e == hipSuccess ? 0 : 1;
 }
-int nst_internal_lbfgs_gram(const nst_ctx* ctx) { return ctx ? ctx->lbfgs_gram : 1; }
-unsigned long long nst_internal_closure_epoch(const nst_ctx* ctx) { return ctx ? ctx->closure_epoch : 0; }
-void nst_internal_mark(nst_ctx* ctx, void* stream) { mark(ctx, static_cast<hipStream_t>(stream)); }
 
 }  // extern "C"

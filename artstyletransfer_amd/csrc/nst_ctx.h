@@ -1,7 +1,7 @@
-// nst_ctx.h - what the three host sources of the C ABI share (not installed, not part of include/nst_hip.h): the VGG19 layer
+// nst_ctx.h - what the host sources of the C ABI share (not installed, not part of include/nst_hip.h): the VGG19 layer
 // tables, the context and its per-level workspace, error reporting, the launch timer, and the helpers one source defines
 // and another calls.  nst_ctx.cpp: context and job state; nst_closure.cpp: network and closure; nst_api.cpp: standalone
-// entry points.
+// entry points; nst_opt.cpp: the optimisers; nst_comm.cpp: the collective (error reporting only).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -409,6 +409,8 @@ struct Timer {
 int fold_timed(nst_ctx* ctx);
 
 // ---- nst_ctx.cpp: device memory (nst_devmem.h), workspace, stream ordering ---------------------------------------------
+void poison_if_asked(void* p, size_t bytes);       // a fresh device allocation under NST_POISON_ALLOC: 0xFF bytes if it is one asked for
+int zero_now(void* p, size_t bytes);               // a set-up-time zero fill that has RUN when it returns (0: done)
 int alloc_acts(nst_ctx* ctx, ActSet& a, int h, int w);
 int bind(nst_ctx* ctx);                            // null check + hipSetDevice: first line of every entry point
 // what a closure remembered is void once the job changes (captured graph; drop_targets: every level's targets)

@@ -1,7 +1,9 @@
 // nst_devmem.h - who owns device memory (nothing of HIP is needed here: tests/devmem_host.cpp drives this header alone over
-// malloc).  Every allocation of nst_ctx.cpp, nst_closure.cpp and nst_api.cpp belongs to a DevMem, which remembers per
-// allocation the pointer and the bytes the context was charged, and gives back exactly that.  The typed pointers of ActSet,
-// Guidance, LapLevel ... are views into their struct's DevMem.
+// malloc).  Every allocation of nst_ctx.cpp, nst_closure.cpp and nst_api.cpp, and the scratch of nst_opt.cpp's standalone
+// nst_lbfgs_direction, belongs to a DevMem, which remembers per allocation the pointer and the bytes the context was
+// charged, and gives back exactly that.  The typed pointers of ActSet, Guidance, LapLevel ... are views into their struct's
+// DevMem.  The one other owner is nst_opt.cpp's OptMem: an optimiser's vectors are deliberately NOT charged to the context
+// (nst_ctx_bytes, include/nst_hip.h), so they do not go through dev_alloc.
 #pragma once
 #include <cstddef>
 #include <utility>
@@ -12,7 +14,7 @@ struct nst_ctx;
 namespace nst {
 
 // nst_ctx.cpp: the only hipMalloc (a zero-size request gets 16 bytes; *charged = what ctx->bytes grew by) and the only
-// hipFree (ctx->bytes shrinks by `bytes`) of the three sources
+// hipFree (ctx->bytes shrinks by `bytes`) of context-charged memory
 int dev_alloc(nst_ctx* ctx, void** p, size_t bytes, size_t* charged = nullptr);
 void dev_release(nst_ctx* ctx, void* p, size_t bytes);
 
