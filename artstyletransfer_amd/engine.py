@@ -24,6 +24,21 @@ TAP_SCALE = (0, 1, 2, 3, 3, 4)
 DEFAULT_TAPS = (_taps.DEFAULT_CONTENT_INDEX, _taps.DEFAULT_STYLE_INDICES, True)
 
 
+# The job settings a StyleEngine caches: (attribute, method that reads the context's setting, method that undoes the setting,
+# whether nst_job_configure clears it), in the order reset_job_settings undoes them.
+_JOB_SETTINGS = (
+    ("layer_weights", "style_weights", "reset_style_weights", False),
+    ("taps", None, "reset_taps", False),                      # (set_taps caches what it set: no reader)
+    ("channels", "_channels", "reset_color", False),
+    ("pooling", "_pooling", "reset_pooling", False),
+    ("laplacian", "laplacian_setting", "reset_laplacian", True),
+    ("gram_shift", "gram_shift_setting", "reset_gram_shift", True),
+    ("matting", "matting_setting", "reset_matting", True),
+    ("moment_loss", "moments_setting", "reset_moments", True),
+)
+_READER = {attr: reader for attr, reader, _, _ in _JOB_SETTINGS}
+
+
 def _ptr(t: Optional[torch.Tensor]):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
@@ -123,10 +138,24 @@ class StyleEngine:
         _lib.check(self.ctx, self.lib.nst_job_configure(self.ctx, levels_num, H0, W0), "nst_job_configure")
         self.levels = levels_num
         self.shape = (H0, W0)
-        self.laplacian = None                    # (nst_job_configure clears the Laplacian setting)
-        self.matting = None                      # (the matting term)
-        self.gram_shift = None                   # (the Gram shift)
-        self.moment_loss = None                  # (and the moment loss)
+        for attr, _, _, cleared in _JOB_SETTINGS:   # (nst_job_configure clears the settings of the loss terms)
+            if cleared:
+                setattr(self, attr, None)
+
+    def _set_native(self, attr: str, fn: str, *args) -> None:
+        """Call the native setter `fn`, then - whether it succeeded or not - re-read the context's setting into the cached
+        attribute `attr`."""
+        try:
+            _lib.check(self.ctx, getattr(self.lib, fn)(self.ctx, *args), fn)
+        finally:
+            setattr(self, attr, getattr(self, _READER[attr])())
+
+    def reset_job_settings(self) -> None:
+        """Every job setting back to the reference's, if it was changed: unit style weights (before the taps: a style set
+        needs a map with a positive weight), the default taps, RGB, max pooling, no Laplacian, Gram shift, matting or
+        moment term."""
+        for _, _, reset, _ in _JOB_SETTINGS:
+            getattr(self, reset)()
 
     def set_taps(self, content_index, style_indices, use_relu: bool = True) -> None:
         """The feature maps the losses read (nst_job_set_taps): a content index and style indices of Vgg19.layer_names
@@ -148,12 +177,10 @@ class StyleEngine:
         level: call set_targets again."""
         if mode not in (None, "rgb", "luminance"):
             raise ValueError(f"colour mode must be 'rgb' or 'luminance', not {mode!r}")
-        lum = mode == "luminance"
-        try:
-            _lib.check(self.ctx, self.lib.nst_job_set_color(self.ctx, _lib.NST_COLOR_LUMINANCE if lum else _lib.NST_COLOR_RGB),
-                       "nst_job_set_color")
-        finally:                                 # the context's mode, whether the call succeeded or not
-            self.channels = 1 if self.lib.nst_job_color(self.ctx) == _lib.NST_COLOR_LUMINANCE else 3
+        self._set_native("channels", "nst_job_set_color", _lib.NST_COLOR_LUMINANCE if mode == "luminance" else _lib.NST_COLOR_RGB)
+
+    def _channels(self) -> int:
+        return 1 if self.lib.nst_job_color(self.ctx) == _lib.NST_COLOR_LUMINANCE else 3
 
     def reset_color(self) -> None:
         """Back to RGB, if the colour mode was changed."""
@@ -165,11 +192,10 @@ class StyleEngine:
         replaced by a 2x2 average pool (Gatys et al. 2016).  Drops the targets of every configured level: call
         set_targets again.  ValueError for any other value."""
         check_pooling(mode)
-        try:
-            _lib.check(self.ctx, self.lib.nst_job_set_pooling(self.ctx, _lib.NST_POOL_AVG if mode == "avg" else _lib.NST_POOL_MAX),
-                       "nst_job_set_pooling")
-        finally:                                 # the context's mode, whether the call succeeded or not
-            self.pooling = "avg" if self.lib.nst_job_pooling(self.ctx) == _lib.NST_POOL_AVG else "max"
+        self._set_native("pooling", "nst_job_set_pooling", _lib.NST_POOL_AVG if mode == "avg" else _lib.NST_POOL_MAX)
+
+    def _pooling(self) -> str:
+        return "avg" if self.lib.nst_job_pooling(self.ctx) == _lib.NST_POOL_AVG else "max"
 
     def reset_pooling(self) -> None:
         """Back to max pooling, if the mode was changed."""
@@ -181,11 +207,7 @@ class StyleEngine:
         style term becomes (sum_i w_i MSE_i) / nstyle.  Keeps the targets.  ValueError for a wrong length, a negative or
         non-finite entry, or when no map of the current style set has a positive weight."""
         w = _style.check_style_layer_weights(w, style_indices=self.taps[1])
-        arr = (C.c_float * _style.NUM_MAPS)(*w)
-        try:
-            _lib.check(self.ctx, self.lib.nst_job_set_style_weights(self.ctx, arr), "nst_job_set_style_weights")
-        finally:                                 # the context's weights, whether the call succeeded or not
-            self.layer_weights = self.style_weights()
+        self._set_native("layer_weights", "nst_job_set_style_weights", (C.c_float * _style.NUM_MAPS)(*w))
 
     def style_weights(self) -> Tuple[float, ...]:
         """The context's six style layer weights (nst_job_style_weights)."""
@@ -213,10 +235,7 @@ class StyleEngine:
         k = len(entries[0])
         pool = (C.c_int * k)(*entries[0])
         gamma = (C.c_float * k)(*entries[1])
-        try:
-            _lib.check(self.ctx, self.lib.nst_job_set_laplacian(self.ctx, k, pool, gamma), "nst_job_set_laplacian")
-        finally:                                 # the context's setting, whether the call succeeded or not
-            self.laplacian = self.laplacian_setting()
+        self._set_native("laplacian", "nst_job_set_laplacian", k, pool, gamma)
 
     def laplacian_setting(self):
         """The context's Laplacian entries as (pools, weights), or None when the term is off (nst_job_laplacian)."""
@@ -231,10 +250,7 @@ class StyleEngine:
     def reset_laplacian(self) -> None:
         """The Laplacian term off, if it was set (drops the targets then, as set_laplacian does)."""
         if self.laplacian is not None:
-            try:
-                _lib.check(self.ctx, self.lib.nst_job_set_laplacian(self.ctx, 0, None, None), "nst_job_set_laplacian")
-            finally:
-                self.laplacian = self.laplacian_setting()
+            self._set_native("laplacian", "nst_job_set_laplacian", 0, None, None)
 
     def laplacian_losses(self) -> torch.Tensor:
         """(levels, 4) device tensor: the unweighted lap_k of the last closure per level and entry
@@ -256,10 +272,7 @@ class StyleEngine:
         if not self.levels:
             raise NstError("set_matting needs a configured job (configure first)")
         _mat.check_levels(self.levels, *self.shape)
-        try:
-            _lib.check(self.ctx, self.lib.nst_job_set_matting(self.ctx, setting[0], setting[1]), "nst_job_set_matting")
-        finally:                                 # the context's setting, whether the call succeeded or not
-            self.matting = self.matting_setting()
+        self._set_native("matting", "nst_job_set_matting", setting[0], setting[1])
 
     def matting_setting(self):
         """The context's matting term as (gamma, epsilon), or None when it is off (nst_job_matting)."""
@@ -270,10 +283,7 @@ class StyleEngine:
     def reset_matting(self) -> None:
         """The matting term off, if it was set (drops the targets then, as set_matting does)."""
         if self.matting is not None:
-            try:
-                _lib.check(self.ctx, self.lib.nst_job_set_matting(self.ctx, 0.0, self.matting[1]), "nst_job_set_matting")
-            finally:
-                self.matting = self.matting_setting()
+            self._set_native("matting", "nst_job_set_matting", 0.0, self.matting[1])
 
     def matting_losses(self) -> torch.Tensor:
         """(levels,) device tensor: the unweighted mat of the last closure per level (nst_job_matting_losses); zeros for
@@ -304,11 +314,7 @@ class StyleEngine:
             return
         if not self.levels:
             raise NstError("set_gram_shift needs a configured job (configure first)")
-        arr = (C.c_float * _gram.NUM_MAPS)(*setting[0])
-        try:
-            _lib.check(self.ctx, self.lib.nst_job_set_gram_shift(self.ctx, arr, setting[1]), "nst_job_set_gram_shift")
-        finally:                                 # the context's setting, whether the call succeeded or not
-            self.gram_shift = self.gram_shift_setting()
+        self._set_native("gram_shift", "nst_job_set_gram_shift", (C.c_float * _gram.NUM_MAPS)(*setting[0]), setting[1])
 
     def gram_shift_setting(self):
         """The context's Gram shift as (shift[6], center_mask), or None when it is off (nst_job_gram_shift)."""
@@ -323,11 +329,7 @@ class StyleEngine:
     def reset_gram_shift(self) -> None:
         """The plain Gram statistic again, if a shift was set (drops the targets then, as set_gram_shift does)."""
         if self.gram_shift is not None:
-            zeros = (C.c_float * _gram.NUM_MAPS)()
-            try:
-                _lib.check(self.ctx, self.lib.nst_job_set_gram_shift(self.ctx, zeros, 0), "nst_job_set_gram_shift")
-            finally:
-                self.gram_shift = self.gram_shift_setting()
+            self._set_native("gram_shift", "nst_job_set_gram_shift", (C.c_float * _gram.NUM_MAPS)(), 0)
 
     def level_gram_offsets(self, level: int, slot: int) -> torch.Tensor:
         """(C,) device tensor: the offsets o that the last closure of `level` used for style slot `slot` (the slots are the
@@ -357,10 +359,7 @@ class StyleEngine:
             raise NstError("set_moments needs a configured job (configure first)")
         wm = (C.c_float * _mom.NUM_MAPS)(*setting[0])
         ws = (C.c_float * _mom.NUM_MAPS)(*setting[1])
-        try:
-            _lib.check(self.ctx, self.lib.nst_job_set_moments(self.ctx, wm, ws, setting[2]), "nst_job_set_moments")
-        finally:                                 # the context's setting, whether the call succeeded or not
-            self.moment_loss = self.moments_setting()
+        self._set_native("moment_loss", "nst_job_set_moments", wm, ws, setting[2])
 
     def moments_setting(self):
         """The context's moment loss as (mean_w[6], std_w[6], epsilon), or None when it is off (nst_job_moments)."""
@@ -377,10 +376,7 @@ class StyleEngine:
         """The moment loss off, if it was set (drops the targets then, as set_moments does)."""
         if self.moment_loss is not None:
             zeros = (C.c_float * _mom.NUM_MAPS)()
-            try:
-                _lib.check(self.ctx, self.lib.nst_job_set_moments(self.ctx, zeros, zeros, self.moment_loss[2]), "nst_job_set_moments")
-            finally:
-                self.moment_loss = self.moments_setting()
+            self._set_native("moment_loss", "nst_job_set_moments", zeros, zeros, self.moment_loss[2])
 
     def moment_losses(self) -> torch.Tensor:
         """(levels, 6, 2) device tensor: the unweighted (mean_i, std_i) of the last closure per level and map index

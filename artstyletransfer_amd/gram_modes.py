@@ -6,9 +6,9 @@ raises ValueError before any GPU work."""
 import math
 import numbers
 
-from .taps import LAYER_NAMES
+from .taps import NUM_MAPS, map_index, map_index_texts
 
-NUM_MAPS = 6
+_MAP_TEXTS = map_index_texts("gram_shift")
 MEAN = "mean"            # the spelling of a centred map
 
 
@@ -26,20 +26,6 @@ def _entry(v, what):
     return s, False
 
 
-def _map_index(key, use_relu):
-    if isinstance(key, str):
-        flavours = (LAYER_NAMES[True], LAYER_NAMES[False]) if use_relu is None else (LAYER_NAMES[bool(use_relu)],)
-        for names in flavours:
-            if key in names:
-                return names.index(key)
-        raise ValueError(f"gram_shift: {key!r} is not one of the feature maps {[n for names in flavours for n in names]}")
-    if isinstance(key, bool) or not isinstance(key, numbers.Integral):
-        raise ValueError(f"gram_shift: expected a map index 0..{NUM_MAPS - 1} or a map name, got {key!r}")
-    if not 0 <= int(key) < NUM_MAPS:
-        raise ValueError(f"gram_shift: map index {key} is outside 0..{NUM_MAPS - 1}")
-    return int(key)
-
-
 def normalize_gram_shift(value=None, use_relu=None):
     """(shift, center_mask) - six floats by map index of Vgg19.layer_names and the bit set of the centred maps, whose shift
     is 0 - or None when the option is off (None, 0, all zeros).  `value`: None; a number (that shift on every map); "mean"
@@ -53,7 +39,7 @@ def normalize_gram_shift(value=None, use_relu=None):
     elif isinstance(value, dict):
         entries = [(0.0, False)] * NUM_MAPS
         for key, v in value.items():
-            entries[_map_index(key, use_relu)] = _entry(v, f"gram_shift of {key!r}")
+            entries[map_index(key, use_relu, _MAP_TEXTS)] = _entry(v, f"gram_shift of {key!r}")
     else:
         if isinstance(value, (bytes, set, frozenset)):
             raise ValueError(f"gram_shift: expected a number, {MEAN!r}, {NUM_MAPS} entries or a dict, got {value!r}")

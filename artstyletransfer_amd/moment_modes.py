@@ -7,9 +7,9 @@ work."""
 import math
 import numbers
 
-from .taps import DEFAULT_STYLE_INDICES, LAYER_NAMES
+from .taps import DEFAULT_STYLE_INDICES, NUM_MAPS, map_index, map_index_texts
 
-NUM_MAPS = 6
+_MAP_TEXTS = map_index_texts("moment_weight")
 DEFAULT_EPSILON = 1e-5
 TERMS = ("both", "mean", "std")
 
@@ -21,20 +21,6 @@ def _weight(v, what):
     if not math.isfinite(w) or w < 0.0:
         raise ValueError(f"{what} must be a finite number >= 0, not {v!r}")
     return w
-
-
-def _map_index(key, use_relu):
-    if isinstance(key, str):
-        flavours = (LAYER_NAMES[True], LAYER_NAMES[False]) if use_relu is None else (LAYER_NAMES[bool(use_relu)],)
-        for names in flavours:
-            if key in names:
-                return names.index(key)
-        raise ValueError(f"moment_weight: {key!r} is not one of the feature maps {[n for names in flavours for n in names]}")
-    if isinstance(key, bool) or not isinstance(key, numbers.Integral):
-        raise ValueError(f"moment_weight: expected a map index 0..{NUM_MAPS - 1} or a map name, got {key!r}")
-    if not 0 <= int(key) < NUM_MAPS:
-        raise ValueError(f"moment_weight: map index {key} is outside 0..{NUM_MAPS - 1}")
-    return int(key)
 
 
 def check_epsilon(epsilon=DEFAULT_EPSILON):
@@ -70,7 +56,7 @@ def normalize_weights(value=None, style_indices=None, use_relu=None):
     if isinstance(value, dict):
         ws = [0.0] * NUM_MAPS
         for key, v in value.items():
-            ws[_map_index(key, use_relu)] = _weight(v, f"moment_weight of {key!r}")
+            ws[map_index(key, use_relu, _MAP_TEXTS)] = _weight(v, f"moment_weight of {key!r}")
     else:
         try:
             items = list(value)

@@ -127,14 +127,7 @@ def return_engine(eng: StyleEngine) -> None:
         try:
             eng.clear_guidance()               # (no region guidance: the re-configuration below drops it with the levels too)
             eng.release_job()                  # the workspace goes back now, only the weights stay resident (and the Laplacian setting goes)
-            eng.reset_style_weights()          # (before the taps: a style set needs a map with a positive weight)
-            eng.reset_taps()
-            eng.reset_color()
-            eng.reset_pooling()
-            eng.reset_laplacian()              # (already off: release_job configured the context anew)
-            eng.reset_gram_shift()             # (likewise)
-            eng.reset_matting()                # (likewise)
-            eng.reset_moments()                # (likewise)
+            eng.reset_job_settings()           # (the loss terms are already off: release_job configured the context anew)
         except Exception:
             keep = False
     if keep:

@@ -21,8 +21,7 @@ from . import taps as _taps
 from .engine import PixelOptimizer, StyleEngine
 from .neural_nets import lease_engine, return_engine, shared_engine
 from .pooling_modes import check_pooling
-from . import style_modes as _style
-from . import regions as _regions
+from . import job_settings as _job
 from . import gram_modes as _gram
 from . import laplacian_modes as _lap
 from . import matting_modes as _mat
@@ -111,40 +110,20 @@ class LossBuilder:
         entries = _lap.normalize_laplacian(laplacian_weight, laplacian_pool)
         if entries is not None:
             _lap.check_levels(entries[0], 1, *self.__engine.shape)
-        if entries is None and self.__engine.laplacian is None:
-            return
-        if entries is None:
-            self.__engine.reset_laplacian()
-        else:
-            self.__engine.set_laplacian(*entries)
-        self.__engine.set_targets(0, *self.__targets)       # (the setting drops them: the Laplacian targets are made with them)
+        self.__set_term("laplacian", "laplacian", entries)
 
     def set_matting(self, matting_weight=None, matting_epsilon=_mat.DEFAULT_EPSILON):
         """Extension: the matting term (Luan et al. 2017) as one more term of `build` - the level total gains
         matting_weight * mat, the quadratic form of the content's matting Laplacian on the image (see nst_job_set_matting in
         include/nst_hip.h).  None or 0 switches it off.  ValueError for a malformed setting."""
-        setting = _mat.normalize_matting(matting_weight, matting_epsilon)
-        if setting is None and self.__engine.matting is None:
-            return
-        if setting is None:
-            self.__engine.reset_matting()
-        else:
-            self.__engine.set_matting(*setting)
-        self.__engine.set_targets(0, *self.__targets)       # (the setting drops them: the guide is made with them)
+        self.__set_term("matting", "matting", _mat.normalize_matting(matting_weight, matting_epsilon))
 
     def set_gram_shift(self, gram_shift=None):
         """Extension: the Gram statistic of the style term of `build` - activation-shifted (Novak & Nikulin 2016) or
         mean-centred (the covariance; Li et al. 2017) per feature map: None or 0 (the plain Gram), a number (that shift on
         every map), "mean" (every map centred), six entries, or a dict {map index or name: number or "mean"} (see
         nst_job_set_gram_shift in include/nst_hip.h).  ValueError for a malformed setting."""
-        setting = _gram.normalize_gram_shift(gram_shift)
-        if setting is None and self.__engine.gram_shift is None:
-            return
-        if setting is None:
-            self.__engine.reset_gram_shift()
-        else:
-            self.__engine.set_gram_shift(*setting)
-        self.__engine.set_targets(0, *self.__targets)       # (the setting drops them: the Gram targets are made with the statistic)
+        self.__set_term("gram_shift", "gram_shift", _gram.normalize_gram_shift(gram_shift))
 
     def set_moments(self, moment_weight=None, moment_terms="both", moment_epsilon=_mom.DEFAULT_EPSILON):
         """Extension: the moment loss (Li et al. 2017; Huang & Belongie 2017) as one more term of `build` - the level total
@@ -154,13 +133,19 @@ class LossBuilder:
         or "std".  ValueError for a malformed setting or a positive weight on a map that is not a style map."""
         setting = _mom.normalize_moments(moment_weight, moment_terms, moment_epsilon, style_indices=self.__engine.taps[1],
                                          use_relu=self.__engine.taps[2])
-        if setting is None and self.__engine.moment_loss is None:
+        self.__set_term("moments", "moment_loss", setting)
+
+    def __set_term(self, name, cached, setting):
+        """A loss term of the engine set (`setting`: the arguments of its set_<name>) or switched off (None); `cached` is
+        the engine's attribute that says whether it is on."""
+        eng = self.__engine
+        if setting is None and getattr(eng, cached) is None:
             return
         if setting is None:
-            self.__engine.reset_moments()
+            getattr(eng, "reset_" + name)()
         else:
-            self.__engine.set_moments(*setting)
-        self.__engine.set_targets(0, *self.__targets)       # (the setting drops them: the moment targets are made with them)
+            getattr(eng, "set_" + name)(*setting)
+        eng.set_targets(0, *self.__targets)             # (the setting drops them: the term's targets are made with them)
 
     def __del__(self):
         try:
@@ -181,8 +166,15 @@ class _DeviceJob:
     otherwise plain asyncio, so the hand-over and tear-down ordering can be tested with a fake in its place
     (`_make_job`, tests/test_host_api.py)."""
 
-    def __init__(self, device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, taps=None, color=None,
-                 pooling=None, style_weights=None, blend=None, regions=None, laplacian=None, gram_shift=None, matting=None, moments=None):
+    CONSUMES = ("color", "blend", "regions")   # the resolved settings read here; job_settings.apply makes the engine calls of the others
+
+    def __init__(self, device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, settings):
+        """`settings`: the dict JobSettings.resolve gave - "taps": (content index, style indices, use_relu); "pooling":
+        "avg"; "style_weights": six per-layer weights; "laplacian": (pools, weights); "matting": (gamma, epsilon);
+        "gram_shift": (shift[6], center_mask); "moments": (mean_w[6], std_w[6], epsilon); "color": "luminance"; "blend":
+        (per-level image lists of the extra styles, K x 6 matrix); "regions": (per-level content planes, per-level style
+        planes, region weights)."""
+        color, blend, regions = (settings.get(k) for k in self.CONSUMES)
         self.dev = dev = device
         self.optimizer = None
         self.luminance = color == "luminance"   # the optimised image is u = 255 Y; the yield puts the content's I, Q back
@@ -211,26 +203,12 @@ class _DeviceJob:
 
             with torch.cuda.stream(self.job_stream):
                 engine.configure(len(content_imgs), h0, w0)
-                if taps is not None:                # (content index, style indices, use_relu), normalised
-                    engine.set_taps(*taps)
-                if pooling is not None:             # "avg": average pooling in the feature network
-                    engine.set_pooling(pooling)
-                if style_weights is not None:       # six per-layer style weights, checked against the taps
-                    engine.set_style_weights(style_weights)
-                if laplacian is not None:           # (pools, weights) of the Laplacian loss, normalised
-                    engine.set_laplacian(*laplacian)
-                if matting is not None:             # (gamma, epsilon) of the matting term, normalised
-                    engine.set_matting(*matting)
-                if gram_shift is not None:         # (shift[6], center_mask) of the Gram statistic, normalised
-                    engine.set_gram_shift(*gram_shift)
-                if moments is not None:            # (mean_w[6], std_w[6], epsilon) of the moment loss, normalised
-                    engine.set_moments(*moments)
+                _job.apply(engine, settings)          # (the colour mode last: the planes below are made under it)
                 # blend = (per-level image lists of the extra styles, K x 6 matrix): style 0 is style_imgs
                 all_styles = [style_imgs] + (list(blend[0]) if blend is not None else [])
                 if self.luminance:
                     # luminance-only transfer: content targets 255 Y(content), style targets 255 (alpha Y(style) + beta)
                     # with the style luminance matched to the content's (statistics of the top level), u0 = 255 Y(init)
-                    engine.set_color("luminance")
                     self.content_top = on_device(content_imgs[0])
                     # (every style image is matched to the content's luminance on its own, by its top level's statistics)
                     ab = [device_image.luminance_params(engine, self.content_top, on_device(lv[0])) for lv in all_styles]
@@ -299,10 +277,11 @@ class _DeviceJob:
         return_engine(self.engine)             # back to the per-GPU pool: the next job re-uses its uploaded weights
 
 
-def _make_job(device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, taps=None, color=None, pooling=None,
-              style_weights=None, blend=None, regions=None, laplacian=None, gram_shift=None, matting=None, moments=None):
-    return _DeviceJob(device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, taps, color, pooling,
-                      style_weights, blend, regions, laplacian, gram_shift, matting, moments)
+def _make_job(device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, **settings):
+    unknown = set(settings) - set(_job.KEYS)
+    if unknown:
+        raise TypeError(f"_make_job() got unexpected setting(s): {sorted(unknown)}")
+    return _DeviceJob(device, optimizer_name, style_imgs, content_imgs, init_img, lr_start, settings)
 
 
 async def _drain(step_future):
@@ -333,24 +312,14 @@ class NeuralStyleTransfer:
         self.__model_name = model_name
         self.__style_imgs = style_imgs
         self.__optimizer_name = optimizer_name
-        self.__taps = None                       # None: the reference's feature maps
-        self.__color = None                      # set_preserve_color
-        self.__pooling = "max"                   # set_pooling
-        self.__layer_weights = None              # set_style_layer_weights (None: w = 1 on every map)
-        self.__blend = None                      # set_style_blend: (extra style levels, blend as given)
-        self.__regions = None                    # set_regions: (content stack, style stack, region weights)
-        self.__laplacian = None                  # set_laplacian: (pools, weights)
-        self.__matting = None                    # set_matting: (gamma, epsilon)
-        self.__gram_shift = None               # set_gram_shift: (shift[6], center_mask)
-        self.__moments = None                    # set_moments: (moment_weight, moment_terms, moment_epsilon) as given
+        self.settings = _job.JobSettings()       # the optional settings of the next `process`: the set_* below update it
 
     def set_feature_maps(self, content_layer=None, style_layers=None, use_relu=True):
         """Extension: the feature maps the losses of the next `process` read - a content map and a set of style maps of
         Vgg19.layer_names, as indices 0..5 or names of the `use_relu` flavour (None: the reference's content 4, style
         [0, 1, 2, 3, 5]).  ValueError for an empty style set, an index out of range or a content map that is not one
         index or name."""
-        content, style = _taps.normalize_taps(content_layer, style_layers, use_relu)
-        self.__taps = None if _taps.is_default(content, style, use_relu) else (content, style, use_relu)
+        self.settings.update(content_layer=content_layer, style_layers=style_layers, use_relu=use_relu)
 
     def set_preserve_color(self, mode=None):
         """Extension: keep the content image's colours (Gatys, Bethge, Hertzmann & Shechtman 2016) in the next `process`.
@@ -360,13 +329,13 @@ class NeuralStyleTransfer:
         that gives the top style level the top content level's pixel mean and covariance, then runs the RGB job
         (neural_style_transfer() recolours before it builds the initial image and hands the recoloured levels over).
         ValueError for any other value."""
-        self.__color = host_image.check_preserve_color(mode)
+        self.settings.update(preserve_color=mode)
 
     def set_pooling(self, mode="max"):
         """Extension: the pooling of the feature network in the next `process` - "max" (the reference's torchvision vgg19)
         or "avg": every 2x2 max-pool replaced by a 2x2 average pool (Gatys, Ecker & Bethge 2016, section 2).  ValueError
         for any other value."""
-        self.__pooling = check_pooling(mode)
+        self.settings.update(pooling=mode)
 
     def set_style_layer_weights(self, weights=None):
         """Extension: per-layer style weights (the w_l of Gatys, Ecker & Bethge 2016) of the next `process`: the style term
@@ -374,8 +343,7 @@ class NeuralStyleTransfer:
         Vgg19.layer_names, or a dict {map index or name: weight} (maps not named get 1); None: w = 1 everywhere, the
         reference's plain mean.  ValueError for a wrong length, a negative or non-finite entry, an unknown key, or - in
         `process`, where the style set is known - when no map of the style set has a positive weight."""
-        w = _style.check_style_layer_weights(weights, style_indices=range(_style.NUM_MAPS))
-        self.__layer_weights = None if _style.is_unit(w) else w
+        self.settings.update(style_layer_weights=weights)
 
     def set_style_blend(self, extra_style_levels=None, blend=None):
         """Extension: more than one style image in the next `process` (jcjohnson's -style_blend_weights; per map, the scale
@@ -385,14 +353,7 @@ class NeuralStyleTransfer:
         of map i is sum_k B[k][i] G_i(style_k) / sum_k B[k][i]; None: an even blend.  None / an empty list: the single
         style.  ValueError for a K that does not match, K > 8, a negative or non-finite entry or - in `process` - a map of
         the style set with an all-zero column."""
-        extra = list(extra_style_levels or [])
-        if not extra:
-            if blend is not None:
-                _style.check_style_blend(blend, 1, style_indices=())
-            self.__blend = None
-            return
-        _style.check_style_blend(blend, 1 + len(extra), style_indices=())
-        self.__blend = ([list(lv) for lv in extra], blend)
+        self.settings.update(extra_styles=[list(lv) for lv in extra_style_levels or []], style_blend=blend)
 
     def set_regions(self, content_regions=None, style_regions=None, region_weights=None):
         """Extension: spatial control (Gatys et al. 2017, guided Gram matrices) in the next `process`: region r of the
@@ -402,7 +363,7 @@ class NeuralStyleTransfer:
         >= 0, the weight of each region's term (None: ones).  None, None: no guidance.  ValueError for one of the two
         without the other, mismatched R, values outside [0,1], and - in `process`, where the level sizes are known - a
         region with a mass sum t^2 below 1 on a map of the style set, or guidance together with a style blend."""
-        self.__regions = _regions.check_regions(content_regions, style_regions, region_weights)
+        self.settings.update(content_regions=content_regions, style_regions=style_regions, region_weights=region_weights)
 
     def set_laplacian(self, laplacian_weight=None, laplacian_pool=_lap.DEFAULT_POOL):
         """Extension: the Laplacian loss (Li, Xu, Nikolova & He 2017) in the next `process`: a pixel-space term that keeps
@@ -412,7 +373,7 @@ class NeuralStyleTransfer:
         four (a single weight goes with every pool size); pool sizes are distinct integers in 1..32.  None, 0 or all-zero
         weights: off; zero-weight entries are dropped.  ValueError for a malformed setting and - in `process`, where the
         level sizes are known - for a level too small for a pool size."""
-        self.__laplacian = _lap.normalize_laplacian(laplacian_weight, laplacian_pool)
+        self.settings.update(laplacian_weight=laplacian_weight, laplacian_pool=laplacian_pool)
 
     def set_matting(self, matting_weight=None, matting_epsilon=_mat.DEFAULT_EPSILON):
         """Extension: the photorealism regulariser of Luan, Paris, Shechtman & Bala 2017 in the next `process`: per pyramid
@@ -420,7 +381,7 @@ class NeuralStyleTransfer:
         which is zero where the image is, in every 3x3 window, an affine function of the content's colours
         (nst_job_set_matting in include/nst_hip.h has the definition).  `matting_epsilon` > 0 regularises the windows whose
         colours lie on a line or are constant.  None or 0: off.  ValueError for a malformed setting."""
-        self.__matting = _mat.normalize_matting(matting_weight, matting_epsilon)
+        self.settings.update(matting_weight=matting_weight, matting_epsilon=matting_epsilon)
 
     def set_gram_shift(self, gram_shift=None):
         """Extension: the Gram statistic of the style term in the next `process` - activation-shifted (Novak & Nikulin 2016:
@@ -429,7 +390,7 @@ class NeuralStyleTransfer:
         entries, or a dict {map index or name: number or "mean"} (the rest 0); nst_job_set_gram_shift in include/nst_hip.h
         has the definition.  ValueError for a non-finite number, another string, a wrong length or an unknown map, and - in
         `process` - together with regions."""
-        self.__gram_shift = _gram.normalize_gram_shift(gram_shift)
+        self.settings.update(gram_shift=gram_shift)
 
     def set_moments(self, moment_weight=None, moment_terms="both", moment_epsilon=_mom.DEFAULT_EPSILON):
         """Extension: the moment loss in the next `process` - the "BN statistics matching" of Li et al. 2017 and the style
@@ -440,8 +401,7 @@ class NeuralStyleTransfer:
         number} (the rest 0); `moment_terms`: "both", "mean" or "std"; `moment_epsilon` > 0.  ValueError for a malformed
         setting and - in `process`, where the style set is known - for a positive weight on a map that is not a style map,
         or together with regions."""
-        off = _mom.normalize_moments(moment_weight, moment_terms, moment_epsilon, style_indices=range(_mom.NUM_MAPS)) is None
-        self.__moments = None if off else (moment_weight, moment_terms, moment_epsilon)
+        self.settings.update(moment_weight=moment_weight, moment_terms=moment_terms, moment_epsilon=moment_epsilon)
 
     async def process(self, content_imgs, init_img, lr_start, iters_num, content_weight, style_weight, tv_weight,
                       init_img_name):
@@ -451,35 +411,11 @@ class NeuralStyleTransfer:
             raise RuntimeError("Unknown optimizer")
         if self.__device.type != "cuda":
             raise RuntimeError("the HIP style-transfer engine needs a GPU; no CPU path exists")
-        # the style settings against the style set of THIS job, before any GPU work
-        style_set = (self.__taps or (None, _taps.DEFAULT_STYLE_INDICES))[1]
-        layer_weights = blend = None
-        if self.__layer_weights is not None:
-            layer_weights = _style.check_style_layer_weights(self.__layer_weights, style_indices=style_set)
-        if self.__blend is not None:
-            for lv in self.__blend[0]:
-                if len(lv) != len(self.__style_imgs):
-                    raise ValueError(f"an extra style has {len(lv)} levels, the job has {len(self.__style_imgs)}")
-            blend = (self.__blend[0], _style.check_style_blend(self.__blend[1], 1 + len(self.__blend[0]), style_indices=style_set))
-        if self.__laplacian is not None and len(content_imgs):
-            _lap.check_levels(self.__laplacian[0], len(content_imgs), *tuple(content_imgs[0].shape[:2]))
-        if self.__matting is not None and len(content_imgs):
-            _mat.check_levels(len(content_imgs), *tuple(content_imgs[0].shape[:2]))
-        _gram.check_exclusive(self.__gram_shift, self.__regions)
-        moments = None
-        if self.__moments is not None:
-            moments = _mom.normalize_moments(*self.__moments, style_indices=style_set,
-                                             use_relu=self.__taps[2] if self.__taps is not None else True)
-            _mom.check_exclusive(moments, self.__regions)
+        # the settings against the style set and the level sizes of THIS job, before any GPU work
         style_imgs = self.__style_imgs
-        regions = None
-        if self.__regions is not None:
-            # resized to every level of the content and of the style pyramid and checked for their masses, on the host
-            _regions.check_exclusive(self.__regions, blend[0] if blend is not None else None)
-            c_stack, s_stack, lam = self.__regions
-            regions = (_regions.level_planes(c_stack, [tuple(c.shape[:2]) for c in content_imgs], style_set, "content_regions"),
-                       _regions.level_planes(s_stack, [tuple(s.shape[:2]) for s in style_imgs], style_set, "style_regions"), lam)
-        if self.__color == "histogram":
+        resolved = self.settings.resolve(lambda: [tuple(c.shape[:2]) for c in content_imgs],
+                                         lambda: [tuple(s.shape[:2]) for s in style_imgs], style_levels=len(style_imgs))
+        if self.settings["color"] == "histogram":
             # every style's levels recoloured with its own statistics (those of its top level)
             setup = shared_engine(self.__device)
 
@@ -489,30 +425,10 @@ class NeuralStyleTransfer:
 
             content_top = up(content_imgs[0])
             style_imgs = device_image.recolor_histogram(setup, content_top, [up(s) for s in style_imgs])
-            if blend is not None:
-                blend = ([device_image.recolor_histogram(setup, content_top, [up(s) for s in lv]) for lv in blend[0]], blend[1])
-        extra = {}
-        if self.__taps is not None:
-            extra["taps"] = self.__taps
-        if self.__color == "luminance":
-            extra["color"] = "luminance"
-        if self.__pooling != "max":
-            extra["pooling"] = self.__pooling
-        if layer_weights is not None:
-            extra["style_weights"] = layer_weights
-        if blend is not None:
-            extra["blend"] = blend
-        if regions is not None:
-            extra["regions"] = regions
-        if self.__laplacian is not None:
-            extra["laplacian"] = self.__laplacian
-        if self.__matting is not None:
-            extra["matting"] = self.__matting
-        if self.__gram_shift is not None:
-            extra["gram_shift"] = self.__gram_shift
-        if moments is not None:
-            extra["moments"] = moments
-        job = _make_job(self.__device, self.__optimizer_name, style_imgs, content_imgs, init_img, lr_start, **extra)
+            if "blend" in resolved:
+                extra, blend = resolved["blend"]
+                resolved["blend"] = ([device_image.recolor_histogram(setup, content_top, [up(s) for s in lv]) for lv in extra], blend)
+        job = _make_job(self.__device, self.__optimizer_name, style_imgs, content_imgs, init_img, lr_start, **resolved)
         cw, sw, tvw = float(content_weight), float(style_weight), float(tv_weight)
         loop = asyncio.get_running_loop()
 
@@ -596,33 +512,19 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
     moment loss - channel means and deviations of the style maps matched to the style's - see
     NeuralStyleTransfer.set_moments (None or 0: off); validated before any GPU work too; not with `content_regions` /
     `style_regions`."""
-    taps = _taps.normalize_taps(content_layer, style_layers, use_relu)
-    host_image.check_preserve_color(preserve_color)
-    check_pooling(pooling)
+    settings = _job.JobSettings(
+        for_job=True, content_layer=content_layer, style_layers=style_layers, use_relu=use_relu, preserve_color=preserve_color,
+        pooling=pooling, extra_styles=extra_styles, style_blend=style_blend, style_layer_weights=style_layer_weights,
+        content_regions=content_regions, style_regions=style_regions, region_weights=region_weights,
+        laplacian_weight=laplacian_weight, laplacian_pool=laplacian_pool, gram_shift=gram_shift, matting_weight=matting_weight,
+        matting_epsilon=matting_epsilon, moment_weight=moment_weight, moment_terms=moment_terms, moment_epsilon=moment_epsilon)
+
+    def level_shapes(img):      # (the level sizes follow from the image size: top level first)
+        ih, iw = np.shape(img)[:2]
+        return [host_image.level_size(ih, iw, lvl) for lvl in range(max(levels_num - 1, 0), -1, -1)]
+
+    settings.resolve(lambda: level_shapes(content_n_style.content[1]), lambda: level_shapes(content_n_style.style[1]))
     extra_styles = list(extra_styles) if extra_styles is not None else []
-    layer_weights = _style.check_style_layer_weights(style_layer_weights, style_indices=taps[1], use_relu=use_relu)
-    if extra_styles or style_blend is not None:
-        style_blend = _style.check_style_blend(style_blend, 1 + len(extra_styles), style_indices=taps[1])
-    regions = _regions.check_regions(content_regions, style_regions, region_weights)
-    _regions.check_exclusive(regions, extra_styles)
-    gram_setting = _gram.normalize_gram_shift(gram_shift, use_relu)
-    _gram.check_exclusive(gram_setting, regions)
-    moment_setting = _mom.normalize_moments(moment_weight, moment_terms, moment_epsilon, style_indices=taps[1], use_relu=use_relu)
-    _mom.check_exclusive(moment_setting, regions)
-    laplacian = _lap.normalize_laplacian(laplacian_weight, laplacian_pool)
-    if laplacian is not None:
-        ih, iw = np.shape(content_n_style.content[1])[:2]
-        _lap.check_levels(laplacian[0], max(levels_num, 1), *host_image.level_size(ih, iw, max(levels_num - 1, 0)))
-    matting = _mat.normalize_matting(matting_weight, matting_epsilon)
-    if matting is not None:
-        ih, iw = np.shape(content_n_style.content[1])[:2]
-        _mat.check_levels(max(levels_num, 1), *host_image.level_size(ih, iw, max(levels_num - 1, 0)))
-    if regions is not None:
-        for stack, img, what in ((regions[0], content_n_style.content[1], "content_regions"),
-                                 (regions[1], content_n_style.style[1], "style_regions")):
-            ih, iw = np.shape(img)[:2]
-            shapes = [host_image.level_size(ih, iw, lvl) for lvl in range(max(levels_num - 1, 0), -1, -1)]
-            _regions.level_planes(stack, shapes, taps[1], what)
     for img in extra_styles:
         if np.ndim(img) != 3 or np.shape(img)[2] != 3:
             raise ValueError(f"extra_styles: expected HWC images with 3 channels, got shape {np.shape(img)}")
@@ -653,21 +555,11 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
     init_name = {"random": "random", "content": content_n_style.content[0], "style": content_n_style.style[0]}[tag]
 
     nst = NeuralStyleTransfer(device, model, style_levels, optimizer)
-    nst.set_feature_maps(*taps, use_relu=use_relu)
-    nst.set_preserve_color("luminance" if preserve_color == "luminance" else None)   # (histogram: recoloured above)
-    nst.set_pooling(pooling)
-    nst.set_style_layer_weights(layer_weights)
-    nst.set_style_blend(extra_levels, style_blend if extra_levels else None)
-    if regions is not None:
-        nst.set_regions(regions[0], regions[1], regions[2])
-    if laplacian is not None:
-        nst.set_laplacian(laplacian[1], laplacian[0])
-    if gram_setting is not None:
-        nst.set_gram_shift(gram_shift)
-    if matting is not None:
-        nst.set_matting(*matting)
-    if moment_setting is not None:
-        nst.set_moments(moment_weight, moment_terms, moment_epsilon)
+    # (the extra styles as their pyramids; "histogram" has recoloured the style levels above)
+    settings.update(extra_styles=extra_levels, style_blend=style_blend if extra_levels else None)
+    if preserve_color == "histogram":
+        settings.update(preserve_color=None)
+    nst.settings = settings
     lr_start = 10.0
     async for img, cur_iter in nst.process(content_levels, init_img, lr_start, iters_num, content_weight,
                                            style_weight, tv_weight, init_name):

@@ -8,11 +8,12 @@ import math
 
 import numpy as np
 
-from .taps import DEFAULT_STYLE_INDICES, LAYER_NAMES
+from .taps import DEFAULT_STYLE_INDICES, NUM_MAPS, map_index
 
-NUM_MAPS = 6
 MAX_STYLES = 8            # NST_MAX_STYLES
 UNIT_WEIGHTS = (1.0,) * NUM_MAPS
+_NO_INDEX = f"style layer weights: expected a map index 0..{NUM_MAPS - 1} or a name, got {{key!r}}"
+_MAP_TEXTS = ("style layer weights: {key!r} is not a feature map name", _NO_INDEX, _NO_INDEX)
 
 
 def _weight(v, what):
@@ -26,17 +27,6 @@ def _weight(v, what):
     return v
 
 
-def _map_index(key, use_relu) -> int:
-    if isinstance(key, str):
-        for names in ((LAYER_NAMES[bool(use_relu)],) if use_relu is not None else LAYER_NAMES.values()):
-            if key in names:
-                return names.index(key)
-        raise ValueError(f"style layer weights: {key!r} is not a feature map name")
-    if isinstance(key, bool) or not isinstance(key, (int, np.integer)) or not 0 <= int(key) < NUM_MAPS:
-        raise ValueError(f"style layer weights: expected a map index 0..{NUM_MAPS - 1} or a name, got {key!r}")
-    return int(key)
-
-
 def check_style_layer_weights(weights, style_indices=None, use_relu=None):
     """The six layer weights as a tuple of floats from a sequence of 6 numbers or a dict {map index or name: weight}
     (maps not named get 1); None = all ones.  ValueError for a wrong length, a negative or non-finite entry, an unknown
@@ -46,7 +36,7 @@ def check_style_layer_weights(weights, style_indices=None, use_relu=None):
     if isinstance(weights, dict):
         w = list(UNIT_WEIGHTS)
         for key, v in weights.items():
-            w[_map_index(key, use_relu)] = _weight(v, f"style layer weight of {key!r}")
+            w[map_index(key, use_relu, _MAP_TEXTS)] = _weight(v, f"style layer weight of {key!r}")
     else:
         if isinstance(weights, (str, bytes)) or not hasattr(weights, "__len__"):
             raise ValueError(f"style layer weights: expected {NUM_MAPS} numbers or a dict, got {weights!r}")

@@ -14,6 +14,7 @@ from typing import Callable, Optional
 import torch
 
 from . import config as _config
+from .job_settings import handed_on
 from .neural_style_transfer import ContentStylePair, neural_style_transfer
 
 
@@ -62,30 +63,8 @@ class Task:
 
     async def __do_job(self):
         cfg = self.__config
-        # the keyword-only feature-map, colour, pooling and style fields of Config, passed on when set (a config without them is the reference's)
-        extensions = {k: getattr(cfg, k) for k, dflt in (("content_layer", None), ("style_layers", None), ("use_relu", True),
-                                                   ("preserve_color", None), ("pooling", "max"))
-                if getattr(cfg, k, dflt) != dflt}
-        # (images and arrays: `is not None`, not `!=`)
-        extensions.update({k: getattr(cfg, k) for k in ("extra_styles", "style_blend", "style_layer_weights", "content_regions",
-                                                        "style_regions", "region_weights")
-                           if getattr(cfg, k, None) is not None})
-        # the Laplacian loss: weight and pool sizes together, when a weight is set
-        if getattr(cfg, "laplacian_weight", None) is not None:
-            extensions["laplacian_weight"] = cfg.laplacian_weight
-            extensions["laplacian_pool"] = getattr(cfg, "laplacian_pool", 4)
-        # the Gram statistic (a number, 'mean', a sequence or a dict: `is not None`)
-        if getattr(cfg, "gram_shift", None) is not None:
-            extensions["gram_shift"] = cfg.gram_shift
-        # the matting term: weight and epsilon together, when a weight is set
-        if getattr(cfg, "matting_weight", None) is not None:
-            extensions["matting_weight"] = cfg.matting_weight
-            extensions["matting_epsilon"] = getattr(cfg, "matting_epsilon", 1e-7)
-        # the moment loss: weight, terms and epsilon together, when a weight is set
-        if getattr(cfg, "moment_weight", None) is not None:
-            extensions["moment_weight"] = cfg.moment_weight
-            extensions["moment_terms"] = getattr(cfg, "moment_terms", "both")
-            extensions["moment_epsilon"] = getattr(cfg, "moment_epsilon", 1e-5)
+        # the keyword-only fields of Config, passed on when set (a config without them is the reference's): job_settings has the rules
+        extensions = handed_on(cfg)
         gpu = await self.__slots.acquire()
         self.gpu = gpu
         try:

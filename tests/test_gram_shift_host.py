@@ -196,8 +196,10 @@ def test_process_hands_gram_shift_to_the_job(monkeypatch, value, expected):
     from artstyletransfer_amd import math_utils
     from artstyletransfer_amd import neural_style_transfer as impl
     seen = []
-    assert "gram_shift" in inspect.signature(impl._make_job).parameters          # (the real one takes what process passes)
-    assert "gram_shift" in inspect.signature(impl._DeviceJob.__init__).parameters
+    # (the real one takes what process passes: every key the table can emit, consumed by job_settings.apply or by _DeviceJob)
+    from artstyletransfer_amd import job_settings
+    assert "gram_shift" in job_settings.KEYS and set(job_settings.KEYS) <= set(job_settings.APPLY_ORDER) | set(impl._DeviceJob.CONSUMES)
+    assert inspect.signature(impl._make_job).parameters["settings"].kind is inspect.Parameter.VAR_KEYWORD
 
     class FakeJob:
         def close(self):
@@ -244,9 +246,13 @@ def test_stripe_sharding_refuses_the_setting():
 
 
 def test_pooled_engine_is_reset():
-    from artstyletransfer_amd import neural_nets
-    src = inspect.getsource(neural_nets.return_engine)
-    assert "eng.reset_gram_shift()" in src
+    """return_engine undoes the job settings through StyleEngine.reset_job_settings, which switches the Gram shift off."""
+    from artstyletransfer_amd import engine, neural_nets
+    assert "eng.reset_job_settings()" in inspect.getsource(neural_nets.return_engine)
+    calls = []
+    fake = type("RecordingEngine", (), {"__getattr__": lambda self, method: lambda: calls.append(method)})()
+    engine.StyleEngine.reset_job_settings(fake)
+    assert "reset_gram_shift" in calls
 
 
 # ---- the package does not import the oracle -------------------------------------------------------------------------------------

@@ -202,7 +202,10 @@ def test_process_hands_laplacian_to_the_job(monkeypatch, args, expected):
     from artstyletransfer_amd import math_utils
     from artstyletransfer_amd import neural_style_transfer as impl
     seen = []
-    assert "laplacian" in inspect.signature(impl._make_job).parameters        # (the real one takes what process passes)
+    # (the real one takes what process passes: every key the table can emit, consumed by job_settings.apply or by _DeviceJob)
+    from artstyletransfer_amd import job_settings
+    assert "laplacian" in job_settings.KEYS and set(job_settings.KEYS) <= set(job_settings.APPLY_ORDER) | set(impl._DeviceJob.CONSUMES)
+    assert inspect.signature(impl._make_job).parameters["settings"].kind is inspect.Parameter.VAR_KEYWORD
 
     class FakeJob:
         def close(self):
