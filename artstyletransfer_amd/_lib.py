@@ -80,6 +80,13 @@ SYMBOLS = {
     "nst_job_matting": (C.c_int, [c_void, c_float_p, C.POINTER(C.c_double)]),
     "nst_job_matting_losses": (C.c_int, [c_void, c_void, c_void]),
     "nst_matting_loss": (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_double, c_void, c_void, c_void]),
+    "nst_level_set_anchor": (C.c_int, [c_void, C.c_int, c_void, c_void, C.c_float, c_void]),
+    "nst_level_anchor": (C.c_int, [c_void, C.c_int, c_float_p, C.POINTER(C.c_int)]),
+    "nst_job_temporal_losses": (C.c_int, [c_void, c_void, c_void]),
+    "nst_anchor_loss": (C.c_int, [c_void, c_void, c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, c_void, c_void]),
+    "nst_anchor_geometry": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "nst_warp_bilinear": (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, c_void, c_void]),
+    "nst_flow_weights": (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, c_void, c_void]),
     "nst_job_set_gram_shift": (C.c_int, [c_void, c_float_p, C.c_uint]),
     "nst_job_gram_shift": (C.c_int, [c_void, c_float_p, C.POINTER(C.c_uint)]),
     "nst_level_gram_offsets": (C.c_int, [c_void, C.c_int, C.c_int, c_void, c_void]),

@@ -253,6 +253,55 @@ int nst_matting_loss(nst_ctx* ctx, const float* y, const float* guide, int C, in
     return sc.finish();
 }
 
+// The temporal term on its own (include/nst_hip.h): value = tmp of y against the anchor under the weight plane (nullable:
+// ones), grad (nullable, overwritten) = d tmp / dy with gamma = 1.  The launches of the closure, on scratch buffers.  Synchronous.
+int nst_anchor_loss(nst_ctx* ctx, const float* y, const float* anchor, const float* weights, int C, int h, int w, float* value,
+                    float* grad, void* stream) {
+    NSTCHK(bind(ctx));
+    if (!y || !anchor || !value) return fail(ctx, NST_E_ARG, "null argument");
+    if (C != 1 && C != 3) return fail(ctx, NST_E_ARG, "C must be 3, or 1 for a luminance plane");
+    if (h < 1 || w < 1) return fail(ctx, NST_E_ARG, "the image must be at least 1x1");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const double n = (double)C * (double)h * (double)w;
+    Scratch sc(ctx, s);
+    double* partial = nullptr;
+    NSTCHK(sc.alloc(&partial, (size_t)ANCHOR_BLOCKS));
+    HIPCHK(ctx, launch_anchor_forward(y, anchor, weights, C, h, w, partial, s));
+    HIPCHK(ctx, launch_anchor_value(partial, ANCHOR_BLOCKS, n, value, s));
+    if (grad) HIPCHK(ctx, launch_anchor_backward(y, anchor, weights, C, h, w, (float)(2.0 / n), grad, 0, s));
+    return sc.finish();
+}
+
+int nst_anchor_geometry(int* blocks, int* block_elems) {
+    if (blocks) *blocks = ANCHOR_BLOCKS;
+    if (block_elems) *block_elems = anchor_block_elems();
+    return NST_OK;
+}
+
+// The warp of a sequence (include/nst_hip.h): out = src sampled bilinearly at p + flow(p), valid (nullable) = the four taps
+// lie inside the image.  Synchronous.
+int nst_warp_bilinear(nst_ctx* ctx, const float* src, const float* flow, int C, int h, int w, float* out, float* valid, void* stream) {
+    NSTCHK(bind(ctx));
+    if (!src || !flow || !out) return fail(ctx, NST_E_ARG, "null argument");
+    if (C < 1 || h < 1 || w < 1) return fail(ctx, NST_E_ARG, "the image must be at least 1x1 with one plane");
+    if (out == src) return fail(ctx, NST_E_ARG, "the warp does not run in place");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIPCHK(ctx, launch_warp_bilinear(src, flow, C, h, w, out, valid, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return NST_OK;
+}
+
+// The reliability plane of a forward / backward flow pair (include/nst_hip.h).  Synchronous.
+int nst_flow_weights(nst_ctx* ctx, const float* fwd, const float* bwd, int h, int w, float* out, void* stream) {
+    NSTCHK(bind(ctx));
+    if (!fwd || !bwd || !out) return fail(ctx, NST_E_ARG, "null argument");
+    if (h < 1 || w < 1) return fail(ctx, NST_E_ARG, "the flow fields must be at least 1x1");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIPCHK(ctx, launch_flow_weights(fwd, bwd, h, w, out, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return NST_OK;
+}
+
 int nst_bicubic_half(nst_ctx* ctx, const float* x, int C, int h, int w, float* y, void* stream) {
     NSTCHK(bind(ctx));
     if (!x || !y || h < 2 || w < 2) return fail(ctx, NST_E_ARG, "bad argument");

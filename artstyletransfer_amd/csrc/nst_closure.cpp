@@ -228,6 +228,26 @@ int mat_set_guide(nst_ctx* ctx, LevelWs& L, const float* content, hipStream_t s)
     return NST_OK;
 }
 
+// ---- the temporal consistency term (include/nst_hip.h has the definition; kernels: temporal.hip) -----------------------
+// n = channels h w; coef = (float)(gamma 2 / n), formed in double as content_coef is
+double anchor_n(const nst_ctx* ctx, const LevelWs& L) { return (double)ctx->channels * (double)L.h * (double)L.w; }
+float anchor_coef(float gamma, double n) { return (float)((double)gamma * 2.0 / n); }
+// forward part of level L on image y: the value partials, which the loss row reads (a level without an anchor: no launch)
+int anchor_forward(nst_ctx* ctx, LevelWs& L, const float* y, hipStream_t s) {
+    if (!(L.anc.gamma > 0.f)) return NST_OK;
+    Timer t(ctx, s, K_OTHER, 0);
+    HIPCHK(ctx, launch_anchor_forward(y, L.anc.anchor, L.anc.weights, ctx->channels, L.h, L.w, L.anc.partial, s));
+    return NST_OK;
+}
+// gradient part: one pass that adds coef c (y - a) into the level gradient (after the TV, Laplacian and matting gradients)
+int anchor_backward(nst_ctx* ctx, LevelWs& L, const float* y, float* grad, hipStream_t s) {
+    if (!(L.anc.gamma > 0.f)) return NST_OK;
+    Timer t(ctx, s, K_OTHER, 0);
+    HIPCHK(ctx, launch_anchor_backward(y, L.anc.anchor, L.anc.weights, ctx->channels, L.h, L.w,
+                                       anchor_coef(L.anc.gamma, anchor_n(ctx, L)), grad, 1, s));
+    return NST_OK;
+}
+
 // ---- the moment loss (include/nst_hip.h has the definition; kernels: moments.hip) ----------------------------------------
 // style slot q of level L on its map f (N pixels, C channels): the statistics item, and the fold item that follows the Gram
 // finish pass and the row bias of a shifted Gram (r0: that bias, or nullptr)
@@ -867,6 +887,7 @@ int batched_backward(nst_ctx* ctx, const float* const* xi, float* const* gi, con
             HIPCHK(ctx, launch_tv_finish(xi[lv[k]], ctx->channels, L.h, L.w, L.tv_partial, tvw, gi[lv[k]], 1, L.tv_means, s));
         if (!win) NSTCHK(lap_backward(ctx, L, gi[lv[k]], s));
         if (!win) NSTCHK(mat_backward(ctx, L, xi[lv[k]], gi[lv[k]], s));
+        if (!win) NSTCHK(anchor_backward(ctx, L, xi[lv[k]], gi[lv[k]], s));
     }
     return NST_OK;
 }
@@ -896,6 +917,7 @@ int closure_batched_forward(nst_ctx* ctx, const float* const* xi, unsigned level
     // the Laplacian term's residuals and partials (nst_job_set_laplacian): pixel space, beside the TV partials
     for (int k = 0; k < n; ++k) NSTCHK(lap_forward(ctx, ctx->lv[lv[k]], xi[lv[k]], false, s));
     for (int k = 0; k < n; ++k) NSTCHK(mat_forward(ctx, ctx->lv[lv[k]], xi[lv[k]], s));       // (nst_job_set_matting: likewise)
+    for (int k = 0; k < n; ++k) NSTCHK(anchor_forward(ctx, ctx->lv[lv[k]], xi[lv[k]], s));    // (nst_level_set_anchor: likewise)
     NSTCHK(batched_forward(ctx, xi, lv, n, s, nullptr, overlap ? sw : -1.f));
     NSTCHK(batched_gram(ctx, lv, n, sw, s, overlap ? 0x18u : (1u << ctx->taps.nstyle) - 1u));
     if (overlap) HIPCHK(ctx, hipStreamWaitEvent(s, ctx->side_join, 0));
@@ -958,6 +980,7 @@ int closure_per_level(nst_ctx* ctx, const float* const* xi, float* const* gi, in
     }
     NSTCHK(lap_forward(ctx, L, xi[level], false, s));
     NSTCHK(mat_forward(ctx, L, xi[level], s));
+    NSTCHK(anchor_forward(ctx, L, xi[level], s));
     NSTCHK(forward(ctx, L.acts, xi[level], L.h, L.w, s, tp.top, ctx->channels));
     Inject inj[NL];
     GuidedBwd gbw[kMaxStyle];
@@ -1009,7 +1032,8 @@ int closure_per_level(nst_ctx* ctx, const float* const* xi, float* const* gi, in
         HIPCHK(ctx, launch_tv_finish(xi[level], ctx->channels, L.h, L.w, L.tv_partial, tvw, gi[level], 1, L.tv_means, s));
     }
     NSTCHK(lap_backward(ctx, L, gi[level], s));
-    return mat_backward(ctx, L, xi[level], gi[level], s);
+    NSTCHK(mat_backward(ctx, L, xi[level], gi[level], s));
+    return anchor_backward(ctx, L, xi[level], gi[level], s);
 }
 
 // what the loss-assembly kernel reads: every level's partial sums and normalisers; the rows of levels not in level_mask are zeros
@@ -1037,6 +1061,11 @@ LossAssembly fill_loss_assembly(const nst_ctx* ctx, unsigned level_mask, float c
         la.mom_wm[k] = ctx->mom_wm_of(k); la.mom_ws[k] = ctx->mom_ws_of(k); la.mom_index[k] = tap_index_of(ctx->taps.style[k]);
     }
     for (int i = 0; i < ctx->levels && la.mom_on; ++i) la.lv[i].mom_loss = ctx->lv[i].mom.stats ? ctx->lv[i].mom.loss(0) : nullptr;
+    for (int i = 0; i < ctx->levels; ++i) {      // (a level's own: la{} left the levels without an anchor at gamma = 0)
+        const LevelWs& L = ctx->lv[i];
+        if (!(L.anc.gamma > 0.f)) continue;
+        la.lv[i].tmp_partial = L.anc.partial; la.lv[i].tmp_gamma = L.anc.gamma; la.lv[i].tmp_n = anchor_n(ctx, L); la.lv[i].tmp_out = L.anc.val;
+    }
     return la;
 }
 
@@ -1208,6 +1237,8 @@ int window_check(nst_ctx* ctx, const float* xs, int row0, int rows, int H0) {
     if (ctx->mom_on())
         return fail(ctx, NST_E_STATE, "the stripe closure implements no moment loss (nst_job_set_moments with zeros switches it off)");
     LevelWs& L = ctx->lv[0];
+    if (L.anc.gamma > 0.f)
+        return fail(ctx, NST_E_STATE, "the stripe closure implements no temporal term (nst_level_set_anchor(ctx, 0, NULL, NULL, 0, stream) clears it)");
     if (L.guide.R > 0)
         return fail(ctx, NST_E_STATE, "the stripe closure implements no spatial control (nst_level_set_guidance(ctx, 0, 0, ...) clears it)");
     if (!L.targets) return fail(ctx, NST_E_STATE, "targets of the stripe not set");

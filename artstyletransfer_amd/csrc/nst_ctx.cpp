@@ -673,6 +673,8 @@ int nst_job_set_color(nst_ctx* ctx, int mode) {
     NSTCHK(replace_blocks(lv, ctx->levels - 1, &LevelWs::img,
                           [&](int i, LevelImage& im) { return alloc_level_image(ctx, im, channels, lv[i].h, lv[i].w); },
                           [&] { drop_closure_state(ctx, true); }));
+    // an anchor has the planes of the mode it was set under (nst_level_set_anchor): another mode drops it
+    for (int i = 0; i < ctx->levels && channels != ctx->channels; ++i) ctx->lv[i].anc = AnchorLevel();
     ctx->channels = channels;
     return NST_OK;
 }
@@ -967,6 +969,63 @@ int nst_job_moment_losses(nst_ctx* ctx, float* out, void* stream) {
     if (ctx->mom_on()) HIPCHK(ctx, hipMemcpyAsync(out, ctx->lv[0].mom.vals, bytes, hipMemcpyDeviceToDevice, s));
     else HIPCHK(ctx, hipMemsetAsync(out, 0, bytes, s));
     mark(ctx, s);
+    return NST_OK;
+}
+
+// The temporal consistency term of one level (Ruder et al. 2016; include/nst_hip.h has the definition): the anchor, its weight
+// plane and the weight.  Data of one job with the life cycle of nst_level_set_guidance: the copies are made here, beside what
+// the level has (a refusal changes nothing), the context's work is waited for before the level's block is replaced, and the
+// captured closure, an optimiser's remembered closure and a pending backward half go.  The targets stay: they do not depend
+// on it.  nst_job_configure drops it with the levels.
+int nst_level_set_anchor(nst_ctx* ctx, int level, const float* anchor, const float* weights, float gamma, void* stream) {
+    if (ctx) { ++ctx->closure_epoch; ++ctx->ws_seq; }
+    NSTCHK(bind(ctx));
+    if (ctx->levels < 1) return fail(ctx, NST_E_STATE, "nst_job_configure has not been called");
+    if (level < 0 || level >= ctx->levels) return fail(ctx, NST_E_ARG, "level out of range");
+    if (!(gamma >= 0.f) || std::isinf(gamma)) return fail(ctx, NST_E_ARG, "the temporal weight must be finite and >= 0");
+    LevelWs& L = ctx->lv[level];
+    AnchorLevel g;
+    hipStream_t s = enter(ctx, stream);
+    if (anchor && gamma > 0.f) {
+        const size_t px = (size_t)L.h * L.w;
+        g.gamma = gamma;
+        NSTCHK(g.mem.alloc(ctx, &g.anchor, (size_t)ctx->channels * px));
+        if (weights) NSTCHK(g.mem.alloc(ctx, &g.weights, px));
+        NSTCHK(g.mem.alloc(ctx, &g.partial, (size_t)ANCHOR_BLOCKS));
+        NSTCHK(g.mem.alloc(ctx, &g.val, 1));
+        hipError_t e = hipMemcpyAsync(g.anchor, anchor, (size_t)ctx->channels * px * sizeof(float), hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess && weights) e = hipMemcpyAsync(g.weights, weights, px * sizeof(float), hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipMemsetAsync(g.val, 0, sizeof(float), s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);       // (the caller's buffers are free again when this returns)
+        HIPCHK(ctx, e);
+    }
+    quiesce(ctx);
+    drop_closure_state(ctx, false);
+    L.anc = std::move(g);
+    return NST_OK;
+}
+
+// the unweighted tmp of the last closure per level, as the loss rows left it (zeros: levels without an anchor or outside the
+// last level mask, no closure yet)
+int nst_job_temporal_losses(nst_ctx* ctx, float* out, void* stream) {
+    NSTCHK(bind(ctx));
+    if (ctx->levels < 1) return fail(ctx, NST_E_STATE, "nst_job_configure has not been called");
+    if (!out) return fail(ctx, NST_E_ARG, "null argument");
+    hipStream_t s = enter(ctx, stream);
+    for (int i = 0; i < ctx->levels; ++i) {
+        const AnchorLevel& a = ctx->lv[i].anc;
+        if (a.gamma > 0.f) HIPCHK(ctx, hipMemcpyAsync(out + i, a.val, sizeof(float), hipMemcpyDeviceToDevice, s));
+        else HIPCHK(ctx, hipMemsetAsync(out + i, 0, sizeof(float), s));
+    }
+    mark(ctx, s);
+    return NST_OK;
+}
+
+int nst_level_anchor(const nst_ctx* ctx, int level, float* gamma, int* weighted) {
+    if (!ctx) return fail(nullptr, NST_E_ARG, "null context");
+    if (level < 0 || level >= ctx->levels) return NST_E_ARG;
+    if (gamma) *gamma = ctx->lv[level].anc.gamma;
+    if (weighted) *weighted = ctx->lv[level].anc.weights ? 1 : 0;
     return NST_OK;
 }
 

@@ -187,6 +187,19 @@ struct MomentLevel {
     double* part(int q) const { return sums + (size_t)q * MOM_PART_DOUBLES; }
 };
 
+// The temporal term of one level (nst_level_set_anchor; include/nst_hip.h has the definition): copies of the anchor
+// (channels x h x w) and of the weight plane (h x w; nullptr: ones), the value partials, and the unweighted tmp of the last
+// closure (one float, which the loss rows write).  Data of one job, not a setting: made by the setter, freed when the level's
+// anchor is cleared, the colour mode changes or the job is configured again: a closure allocates nothing.
+struct AnchorLevel {
+    float gamma = 0.f;          // 0: the level has no anchor
+    float* anchor = nullptr;
+    float* weights = nullptr;
+    double* partial = nullptr;  // ANCHOR_BLOCKS
+    float* val = nullptr;
+    DevMem mem;
+};
+
 // the level image and its gradient (levels >= 1), planar: channels (nst_job_set_color) x h x w floats each
 struct LevelImage {
     float* xl = nullptr;
@@ -201,6 +214,7 @@ struct LevelWs {
     MatLevel mat;
     GramShiftLevel gs;
     MomentLevel mom;
+    AnchorLevel anc;
     ActSet acts;
     float* gbuf[2] = {};
     size_t gbuf_floats = 0;
@@ -323,7 +337,7 @@ struct nst_ctx {
         if (mom_on() && mom_slot(q)) return L.mom.row_bias(q);
         return gs_on() ? L.gs.row_bias(q) : nullptr;
     }
-    // bumped on entry to every call that changes what a closure computes (configure, taps, colour, pooling, style weights, Laplacian, matting, Gram shift, moments, targets), failure paths
+    // bumped on entry to every call that changes what a closure computes (configure, taps, colour, pooling, style weights, Laplacian, matting, Gram shift, moments, targets, a level's anchor), failure paths
     // included: an optimiser's remembered closure result is valid only under the epoch it was made in (nst_opt.cpp)
     unsigned long long closure_epoch = 0;
     // advanced on entry to every call that reads or writes the level workspaces (nst_closure*, nst_window_*,

@@ -266,6 +266,23 @@ hipError_t launch_mat_backward(const float* y, const float* guide, int C, int h,
 // out[0] = (float)(sum of the tile partials / n), in the order of the loss rows
 hipError_t launch_mat_value(const double* partial, int tiles, double n, float* out, hipStream_t stream);
 
+// temporal.hip: the temporal consistency term, the warp and the flow weights (include/nst_hip.h has the definitions) ----
+constexpr int ANCHOR_BLOCKS = 256;   // value partials of one image: the fixed grid of the forward half
+int anchor_block_elems();            // elements one block covers per pass of its grid-stride loop (threads x lane width)
+// partial: ANCHOR_BLOCKS doubles, partial[b] = block b's share of sum c d^2, d = y - a (fixed order); c nullptr: ones
+hipError_t launch_anchor_forward(const float* y, const float* a, const float* c, int C, int h, int w, double* partial,
+                                 hipStream_t stream);
+// out[0] = (float)(sum of the block partials / n), in the order of the loss rows
+hipError_t launch_anchor_value(const double* partial, int blocks, double n, float* out, hipStream_t stream);
+// grad (C,h,w) (+)= coef * (c * (y - a)), the difference formed again; accumulating, a term of exactly 0 leaves grad's bits
+hipError_t launch_anchor_backward(const float* y, const float* a, const float* c, int C, int h, int w, float coef, float* grad,
+                                  int accumulate, hipStream_t stream);
+// out (C,h,w) = src sampled bilinearly at p + flow(p) (flow (2,h,w): dx, dy in pixels); valid (h,w) nullable
+hipError_t launch_warp_bilinear(const float* src, const float* flow, int C, int h, int w, float* out, float* valid,
+                                hipStream_t stream);
+// out (h,w) = the reliability plane c of a forward / backward flow pair
+hipError_t launch_flow_weights(const float* fwd, const float* bwd, int h, int w, float* out, hipStream_t stream);
+
 // loss assembly -----------------------------------------------------------------------------------
 struct LevelLossInputs {
     const double* content_partial;   // MSE_BLOCKS doubles
@@ -281,6 +298,12 @@ struct LevelLossInputs {
     int mat_tiles;
     double mat_n;                    // channels (h-2)(w-2)
     const double* mom_loss;          // moment term: style slot k's (mean_i, std_i) as the fold left them, at k * mom_stride
+    // temporal term (nst_level_set_anchor), a level's own: ANCHOR_BLOCKS doubles, partial sums of c d^2; the weight (0: the
+    // level has no anchor and its row is what it is without the term); channels h w; where the unweighted tmp goes
+    const double* tmp_partial;
+    float tmp_gamma;
+    double tmp_n;
+    float* tmp_out;
 };
 struct LossAssembly {
     LevelLossInputs lv[8];

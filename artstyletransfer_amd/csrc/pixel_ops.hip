@@ -644,6 +644,7 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(LossAssembly la) {
     __shared__ double sh[7][4];
     __shared__ double shl[NST_LAP_MAX][4];
     __shared__ double shm[4];
+    __shared__ double sht[4];
     const int l = blockIdx.x;
     const LevelLossInputs& in = la.lv[l];
     if (!in.owned) {
@@ -651,6 +652,7 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(LossAssembly la) {
         if (la.nlap > 0 && threadIdx.x < NST_LAP_MAX) la.lap_out[NST_LAP_MAX * l + threadIdx.x] = 0.f;
         if (la.mat_gamma > 0.f && threadIdx.x == 0) la.mat_out[l] = 0.f;
         if (la.mom_on && threadIdx.x < 12) la.mom_out[12 * l + threadIdx.x] = 0.f;
+        if (in.tmp_gamma > 0.f && threadIdx.x == 0) in.tmp_out[0] = 0.f;
         return;
     }
     double v[7];
@@ -694,6 +696,13 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(LossAssembly la) {
         for (int b = threadIdx.x; b < in.mat_tiles; b += 256) x += in.mat_partial[b];
         for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
         if (lane == 0) shm[w] = x;
+    }
+    // the temporal term's ANCHOR_BLOCKS partials by the same tree (a level without an anchor: nothing here runs)
+    if (in.tmp_gamma > 0.f) {
+        double x = 0.0;
+        for (int b = threadIdx.x; b < ANCHOR_BLOCKS; b += 256) x += in.tmp_partial[b];
+        for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
+        if (lane == 0) sht[w] = x;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -749,6 +758,14 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(LossAssembly la) {
                 first = false;
             }
             total = total + mom;
+        }
+        if (in.tmp_gamma > 0.f) {
+            // (... + mom) + gamma * tmp, tmp = (float)(sum c d^2 / n): added last, product and sum each rounded
+            double rt = 0.0;
+            for (int i = 0; i < 4; ++i) rt += sht[i];
+            const float tmp = (float)(rt / in.tmp_n);
+            in.tmp_out[0] = tmp;
+            total = total + in.tmp_gamma * tmp;
         }
         la.out[4 * l + 0] = total;
         la.out[4 * l + 1] = content;

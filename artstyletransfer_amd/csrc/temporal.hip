@@ -1,0 +1,265 @@
+// temporal.hip - what a sequence needs on top of the still-image job (Ruder, Dosovitskiy & Brox, "Artistic Style Transfer for
+// Videos", GCPR 2016; include/nst_hip.h has the normative definitions): a pixel-space term that holds the level image to an
+// anchor under a per-pixel weight plane, the bilinear warp that makes the anchor from the previous frame's result, and the
+// weight plane from a forward / backward flow pair (section 4 of the paper, after Sundaram, Brox & Keutzer 2010).
+//   anchor_kernel<false>   the forward half: ANCHOR_BLOCKS double partials of c d^2, d = y - a
+//   anchor_kernel<true>    the backward half: grad (+)= coef * (c * d); d is formed again, no residual goes through HBM
+//   anchor_value_kernel    the block partials -> tmp (the standalone entry point; the loss rows read the partials)
+//   warp_kernel            out = bilinear(src, p + flow(p)), valid = the four taps lie inside the image
+//   flow_weights_kernel    c = 0 at disocclusions, motion boundaries and samples off the image, 1 elsewhere
+// Streaming kernels: 16 bytes per lane where a plane's offset keeps every operand on a 16-byte boundary, scalar loads on
+// such a plane's last h w % 4 pixels and on the planes that are not.  The grid of the anchor kernels is fixed, every thread
+// adds its share in index order, and the block tree is the one of pixel_ops.hip: no float atomics, the same bits every run.
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+
+#include "nst_kernels.h"
+
+namespace nst {
+
+namespace {
+
+constexpr int ANCHOR_THREADS = 256;
+constexpr int ANCHOR_VEC = 4;               // pixels of one lane's 16-byte load
+
+__device__ __forceinline__ double anchor_block_sum(double v, double* sh) {
+    // 256 threads; fixed tree order (pixel_ops.hip's block_reduce_sum)
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) sh[w] = v;
+    __syncthreads();
+    double r = 0.0;
+    if (threadIdx.x == 0)
+        for (int i = 0; i < 4; ++i) r += sh[i];
+    __syncthreads();
+    return r;   // valid in thread 0
+}
+
+// one pixel of the backward half: coef * (c * d), product by product (the caller switches contraction off); a term of
+// exactly zero (d = 0, c = 0) leaves the gradient's bits alone, the sign of a zero included
+__device__ __forceinline__ float anchor_grad(float g, float y, float a, float c, bool has_c, float coef, int accumulate) {
+#pragma clang fp contract(off)
+    const float d = y - a;
+    const float t = has_c ? c * d : d;
+    const float term = coef * t;
+    if (!accumulate) return term;
+    return term != 0.f ? g + term : g;
+}
+
+}  // namespace
+
+// y, a (C,hw), c (hw) or nullptr = ones.  vec_mask bit ch: plane ch of y, a (and grad) and c start on 16-byte boundaries.
+// GRAD = false: partial[block] = sum of c d^2 over the block's share (channel by channel: quads, then the scalar pixels)
+// GRAD = true: grad (+)= coef * (c * d)
+template <bool GRAD>
+__global__ __launch_bounds__(ANCHOR_THREADS) void anchor_kernel(const float* __restrict__ y, const float* __restrict__ a,
+                                                                const float* __restrict__ c, int C, size_t hw, unsigned vec_mask,
+                                                                double* __restrict__ partial, float coef, float* __restrict__ grad,
+                                                                int accumulate) {
+    __shared__ double sh[4];
+    const size_t tid = (size_t)blockIdx.x * ANCHOR_THREADS + threadIdx.x;
+    const size_t nthreads = (size_t)gridDim.x * ANCHOR_THREADS;
+    const bool has_c = c != nullptr;
+    double acc = 0.0;
+    for (int ch = 0; ch < C; ++ch) {
+        const float* yc = y + (size_t)ch * hw;
+        const float* ac = a + (size_t)ch * hw;
+        float* gc = GRAD ? grad + (size_t)ch * hw : nullptr;
+        const size_t nq = ((vec_mask >> ch) & 1u) ? hw / ANCHOR_VEC : 0;
+        for (size_t q = tid; q < nq; q += nthreads) {
+            const float4 yv = reinterpret_cast<const float4*>(yc)[q];
+            const float4 av = reinterpret_cast<const float4*>(ac)[q];
+            const float4 cv = has_c ? reinterpret_cast<const float4*>(c)[q] : make_float4(1.f, 1.f, 1.f, 1.f);
+            if (GRAD) {
+                float4 gv = accumulate ? reinterpret_cast<const float4*>(gc)[q] : make_float4(0.f, 0.f, 0.f, 0.f);
+                gv.x = anchor_grad(gv.x, yv.x, av.x, cv.x, has_c, coef, accumulate);
+                gv.y = anchor_grad(gv.y, yv.y, av.y, cv.y, has_c, coef, accumulate);
+                gv.z = anchor_grad(gv.z, yv.z, av.z, cv.z, has_c, coef, accumulate);
+                gv.w = anchor_grad(gv.w, yv.w, av.w, cv.w, has_c, coef, accumulate);
+                reinterpret_cast<float4*>(gc)[q] = gv;
+            } else {
+                const double d0 = (double)yv.x - (double)av.x, d1 = (double)yv.y - (double)av.y;
+                const double d2 = (double)yv.z - (double)av.z, d3 = (double)yv.w - (double)av.w;
+                acc += (double)cv.x * (d0 * d0);
+                acc += (double)cv.y * (d1 * d1);
+                acc += (double)cv.z * (d2 * d2);
+                acc += (double)cv.w * (d3 * d3);
+            }
+        }
+        for (size_t p = nq * ANCHOR_VEC + tid; p < hw; p += nthreads) {
+            const float cp = has_c ? c[p] : 1.f;
+            if (GRAD) {
+                gc[p] = anchor_grad(accumulate ? gc[p] : 0.f, yc[p], ac[p], cp, has_c, coef, accumulate);
+            } else {
+                const double d = (double)yc[p] - (double)ac[p];
+                acc += (double)cp * (d * d);
+            }
+        }
+    }
+    if (!GRAD) {
+        const double b = anchor_block_sum(acc, sh);
+        if (threadIdx.x == 0) partial[blockIdx.x] = b;
+    }
+}
+
+namespace {
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// bit ch: plane ch of every (C,hw) operand, and the weight plane, start on a 16-byte boundary
+unsigned anchor_vec_mask(const float* y, const float* a, const float* c, const float* grad, int C, size_t hw) {
+    unsigned m = 0;
+    if (c && !aligned16(c)) return 0;
+    for (int ch = 0; ch < C; ++ch) {
+        const size_t o = (size_t)ch * hw;
+        if (aligned16(y + o) && aligned16(a + o) && (!grad || aligned16(grad + o))) m |= 1u << ch;
+    }
+    return m;
+}
+
+}  // namespace
+
+int anchor_block_elems() { return ANCHOR_THREADS * ANCHOR_VEC; }
+
+hipError_t launch_anchor_forward(const float* y, const float* a, const float* c, int C, int h, int w, double* partial,
+                                 hipStream_t stream) {
+    if ((C != 1 && C != 3) || h < 1 || w < 1 || !y || !a || !partial) return hipErrorInvalidValue;
+    const size_t hw = (size_t)h * w;
+    hipLaunchKernelGGL(anchor_kernel<false>, dim3(ANCHOR_BLOCKS), dim3(ANCHOR_THREADS), 0, stream, y, a, c, C, hw,
+                       anchor_vec_mask(y, a, c, nullptr, C, hw), partial, 0.f, nullptr, 0);
+    return hipGetLastError();
+}
+
+hipError_t launch_anchor_backward(const float* y, const float* a, const float* c, int C, int h, int w, float coef, float* grad,
+                                  int accumulate, hipStream_t stream) {
+    if ((C != 1 && C != 3) || h < 1 || w < 1 || !y || !a || !grad) return hipErrorInvalidValue;
+    const size_t hw = (size_t)h * w;
+    // (no reduction here: enough blocks to cover the image once, capped where the forward half's grid is)
+    const size_t want = (hw / ANCHOR_VEC + ANCHOR_THREADS) / ANCHOR_THREADS;
+    const int blocks = (int)(want < (size_t)ANCHOR_BLOCKS ? want : (size_t)ANCHOR_BLOCKS);
+    hipLaunchKernelGGL(anchor_kernel<true>, dim3(blocks), dim3(ANCHOR_THREADS), 0, stream, y, a, c, C, hw,
+                       anchor_vec_mask(y, a, c, grad, C, hw), nullptr, coef, grad, accumulate);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ tmp = (float)(sum of the block partials / n)
+// thread t adds the partials t, t + 256, ... in index order, then the fixed tree: the order of loss_rows_kernel
+__global__ __launch_bounds__(256) void anchor_value_kernel(const double* __restrict__ partial, int blocks, double n, float* __restrict__ out) {
+    __shared__ double sh[4];
+    double v = 0.0;
+    for (int b = threadIdx.x; b < blocks; b += 256) v += partial[b];
+    const double r = anchor_block_sum(v, sh);
+    if (threadIdx.x == 0) out[0] = (float)(r / n);
+}
+hipError_t launch_anchor_value(const double* partial, int blocks, double n, float* out, hipStream_t stream) {
+    hipLaunchKernelGGL(anchor_value_kernel, dim3(1), dim3(256), 0, stream, partial, blocks, n, out);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ the bilinear sample both kernels below share
+namespace {
+
+// The sample position of one axis: pixel index x plus displacement d, as integer part and fraction of d ALONE - x + d is
+// never formed in fp32, so the fraction is as accurate at every image size.  i0, i1: the two taps clamped to [0, n - 1]; t: the
+// weight of the second; inside: both taps lie in the image before clamping.  d must be finite.
+struct AxisTap { int i0, i1; float t; bool inside; };
+__device__ __forceinline__ AxisTap axis_tap(int x, float d, int n) {
+    const float f = floorf(d);
+    AxisTap r;
+    r.t = d - f;                                  // in [0, 1]; exact for d >= 0, one rounding of at most 2^-25 for d < 0 - whatever x is
+    // a displacement beyond the image on either side: every tap clamps to the border whatever the integer part is
+    const float lim = (float)n + 1.f;
+    const int k = (int)fminf(fmaxf(f, -lim), lim);
+    const int a = x + k, b = a + 1;
+    r.inside = a >= 0 && b <= n - 1;
+    r.i0 = min(max(a, 0), n - 1);
+    r.i1 = min(max(b, 0), n - 1);
+    return r;
+}
+// (v00 (1 - tx) + v01 tx)(1 - ty) + (v10 (1 - tx) + v11 tx) ty, every operation rounded once
+__device__ __forceinline__ float bilinear(const float* __restrict__ plane, int w, const AxisTap& ax, const AxisTap& ay) {
+#pragma clang fp contract(off)
+    const float* r0 = plane + (size_t)ay.i0 * w;
+    const float* r1 = plane + (size_t)ay.i1 * w;
+    const float ux = 1.f - ax.t, uy = 1.f - ay.t;
+    const float top = r0[ax.i0] * ux + r0[ax.i1] * ax.t;
+    const float bot = r1[ax.i0] * ux + r1[ax.i1] * ax.t;
+    return top * uy + bot * ay.t;
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------ warp
+__global__ __launch_bounds__(256) void warp_kernel(const float* __restrict__ src, const float* __restrict__ flow, int C, int h, int w,
+                                                   float* __restrict__ out, float* __restrict__ valid) {
+    const size_t hw = (size_t)h * w;
+    for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < hw; p += (size_t)gridDim.x * blockDim.x) {
+        const int y = (int)(p / (size_t)w), x = (int)(p - (size_t)y * w);
+        const float dx = flow[p], dy = flow[hw + p];
+        if (!(isfinite(dx) && isfinite(dy))) {
+            for (int ch = 0; ch < C; ++ch) out[(size_t)ch * hw + p] = src[(size_t)ch * hw + p];
+            if (valid) valid[p] = 0.f;
+            continue;
+        }
+        const AxisTap ax = axis_tap(x, dx, w), ay = axis_tap(y, dy, h);
+        for (int ch = 0; ch < C; ++ch) out[(size_t)ch * hw + p] = bilinear(src + (size_t)ch * hw, w, ax, ay);
+        if (valid) valid[p] = (ax.inside && ay.inside) ? 1.f : 0.f;
+    }
+}
+hipError_t launch_warp_bilinear(const float* src, const float* flow, int C, int h, int w, float* out, float* valid,
+                                hipStream_t stream) {
+    if (C < 1 || h < 1 || w < 1 || !src || !flow || !out) return hipErrorInvalidValue;
+    const size_t hw = (size_t)h * w;
+    const size_t want = (hw + 255) / 256;
+    hipLaunchKernelGGL(warp_kernel, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, stream, src, flow, C, h, w, out, valid);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ flow weights
+// fwd, bwd (2,h,w): plane 0 = u (x), plane 1 = v (y).  Every comparison in fp32, one rounding per operation.
+__global__ __launch_bounds__(256) void flow_weights_kernel(const float* __restrict__ fwd, const float* __restrict__ bwd, int h, int w,
+                                                           float* __restrict__ out) {
+#pragma clang fp contract(off)
+    const size_t hw = (size_t)h * w;
+    const float* bu_p = bwd;
+    const float* bv_p = bwd + hw;
+    for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < hw; p += (size_t)gridDim.x * blockDim.x) {
+        const int y = (int)(p / (size_t)w), x = (int)(p - (size_t)y * w);
+        const float bu = bu_p[p], bv = bv_p[p];
+        if (!(isfinite(bu) && isfinite(bv))) { out[p] = 0.f; continue; }
+        const AxisTap ax = axis_tap(x, bu, w), ay = axis_tap(y, bv, h);
+        bool ok = ax.inside && ay.inside;
+        // w~ = fwd at p + bwd(p)
+        const float wu = bilinear(fwd, w, ax, ay), wv = bilinear(fwd + hw, w, ax, ay);
+        const float bb = bu * bu + bv * bv;
+        // disocclusion: |w~ + bwd|^2 > 0.01 (|w~|^2 + |bwd|^2) + 0.5
+        {
+            const float su = wu + bu, sv = wv + bv;
+            const float lhs = su * su + sv * sv;
+            const float rhs = 0.01f * ((wu * wu + wv * wv) + bb) + 0.5f;
+            ok = ok && lhs <= rhs;        // (a NaN on either side: not reliable)
+        }
+        // motion boundary: |grad u|^2 + |grad v|^2 > 0.01 |bwd|^2 + 0.002, central differences with replicated borders
+        {
+            const int xm = max(x - 1, 0), xp = min(x + 1, w - 1), ym = max(y - 1, 0), yp = min(y + 1, h - 1);
+            const size_t row = (size_t)y * w;
+            const float ux = 0.5f * (bu_p[row + xp] - bu_p[row + xm]);
+            const float uy = 0.5f * (bu_p[(size_t)yp * w + x] - bu_p[(size_t)ym * w + x]);
+            const float vx = 0.5f * (bv_p[row + xp] - bv_p[row + xm]);
+            const float vy = 0.5f * (bv_p[(size_t)yp * w + x] - bv_p[(size_t)ym * w + x]);
+            const float lhs = (ux * ux + uy * uy) + (vx * vx + vy * vy);
+            const float rhs = 0.01f * bb + 0.002f;
+            ok = ok && lhs <= rhs;
+        }
+        out[p] = ok ? 1.f : 0.f;
+    }
+}
+hipError_t launch_flow_weights(const float* fwd, const float* bwd, int h, int w, float* out, hipStream_t stream) {
+    if (h < 1 || w < 1 || !fwd || !bwd || !out) return hipErrorInvalidValue;
+    const size_t hw = (size_t)h * w;
+    const size_t want = (hw + 255) / 256;
+    hipLaunchKernelGGL(flow_weights_kernel, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, stream, fwd, bwd, h, w, out);
+    return hipGetLastError();
+}
+
+}  // namespace nst

@@ -499,6 +499,52 @@ class StyleEngine:
                    "nst_level_guidance_planes")
         return out
 
+    # ---- temporal consistency (nst_level_set_anchor; video.py is the driver) -----------------------------
+    def set_anchor(self, level: int, anchor: Optional[torch.Tensor], weights: Optional[torch.Tensor] = None, *, gamma) -> None:
+        """The temporal term of one level (nst_level_set_anchor; Ruder et al. 2016): the level total gains gamma * tmp, the
+        mean over channels and pixels of weights(p) (y - anchor)^2.  anchor: a device float32 tensor of the level image's
+        size ((C,h,w), any leading ones; C = 3, or 1 in luminance mode), weights: (h,w) in [0,1] or None for ones; both are
+        copied.  Data of the job, not a setting: configure() drops it.  anchor None or gamma 0 clears the level's term."""
+        gamma = float(gamma)
+        if anchor is None:
+            _lib.check(self.ctx, self.lib.nst_level_set_anchor(self.ctx, int(level), None, None, 0.0, _stream(self.device)),
+                       "nst_level_set_anchor")
+            return
+        if not 0 <= level < self.levels:
+            raise NstError(f"level {level} is not configured")
+        h, w = self.level_shape(level)
+        ch = self.channels
+        if anchor.numel() != ch * h * w or tuple(anchor.shape[-2:]) != (h, w):
+            raise NstError(f"the anchor of level {level} must have shape ({ch},{h},{w}), got {tuple(anchor.shape)}")
+        anchor = anchor.contiguous()
+        _chk_dev(anchor, self.device)
+        if weights is not None:
+            if weights.numel() != h * w or tuple(weights.shape[-2:]) != (h, w):
+                raise NstError(f"the weights of level {level} must have shape ({h},{w}), got {tuple(weights.shape)}")
+            weights = weights.contiguous()
+            _chk_dev(weights, self.device)
+        _lib.check(self.ctx, self.lib.nst_level_set_anchor(self.ctx, int(level), _ptr(anchor), _ptr(weights), gamma,
+                                                           _stream(self.device)), "nst_level_set_anchor")
+
+    def clear_anchor(self, level: Optional[int] = None) -> None:
+        """No temporal term on one level, or (None) on any configured level."""
+        for l in (range(self.levels) if level is None else (level,)):
+            self.set_anchor(l, None, gamma=0.0)
+
+    def anchor(self, level: int):
+        """(gamma, whether a weight plane is set) of a level (nst_level_anchor); gamma = 0: the level has no anchor."""
+        g, wt = C.c_float(), C.c_int()
+        _lib.check(self.ctx, self.lib.nst_level_anchor(self.ctx, int(level), C.byref(g), C.byref(wt)), "nst_level_anchor")
+        return g.value, bool(wt.value)
+
+    def temporal_losses(self) -> torch.Tensor:
+        """(levels,) device tensor: the unweighted tmp of the last closure per level (nst_job_temporal_losses); zeros for
+        levels without an anchor and levels outside the last level mask."""
+        out = torch.empty(self.levels, dtype=torch.float32, device=self.device)
+        _lib.check(self.ctx, self.lib.nst_job_temporal_losses(self.ctx, _ptr(out), _stream(self.device)),
+                   "nst_job_temporal_losses")
+        return out
+
     def closure(self, x: torch.Tensor, cw: float, sw: float, tvw: float,
                 grad: Optional[torch.Tensor] = None, losses: Optional[torch.Tensor] = None):
         """Asynchronous on the current stream. Returns (grad (C,H,W), losses (4*levels+1,)) device tensors (C = 3, or 1
@@ -839,6 +885,50 @@ class StyleEngine:
                                                        _ptr(grad), _stream(self.device)), "nst_matting_loss")
         return (val, grad) if want_grad else val
 
+    def anchor_loss(self, y: torch.Tensor, anchor: torch.Tensor, weights: Optional[torch.Tensor] = None, want_grad: bool = False):
+        """The temporal term on its own (nst_anchor_loss): tmp of the (1,C,h,w) image y against the anchor (same shape) under
+        the (h,w) weight plane (None: ones), C = 3 or 1; with want_grad also d tmp / dy."""
+        _chk_dev(y, self.device)
+        _chk_dev(anchor, self.device, y.shape)
+        b, c, h, w = y.shape
+        if weights is not None:
+            _chk_dev(weights, self.device, (h, w))
+        val = torch.empty(1, dtype=torch.float32, device=self.device)
+        grad = torch.empty_like(y) if want_grad else None
+        _lib.check(self.ctx, self.lib.nst_anchor_loss(self.ctx, _ptr(y), _ptr(anchor), _ptr(weights), b * c, h, w, _ptr(val),
+                                                      _ptr(grad), _stream(self.device)), "nst_anchor_loss")
+        return (val, grad) if want_grad else val
+
+    def anchor_geometry(self) -> Tuple[int, int]:
+        """(blocks of the temporal term's value pass, elements a block covers per pass of its loop) (nst_anchor_geometry)."""
+        nb, ne = C.c_int(), C.c_int()
+        _lib.check(self.ctx, self.lib.nst_anchor_geometry(C.byref(nb), C.byref(ne)), "nst_anchor_geometry")
+        return nb.value, ne.value
+
+    def warp_bilinear(self, src: torch.Tensor, flow: torch.Tensor):
+        """(out, valid): the (C,h,w) planes src sampled bilinearly at p + flow(p), flow (2,h,w) = (dx, dy) in pixels, and the
+        (h,w) plane that is 1 where the four taps lie inside the image (nst_warp_bilinear)."""
+        _chk_dev(src, self.device)
+        h, w = src.shape[-2:]
+        _chk_dev(flow, self.device, (2, h, w))
+        out = torch.empty_like(src)
+        valid = torch.empty((h, w), dtype=torch.float32, device=self.device)
+        _lib.check(self.ctx, self.lib.nst_warp_bilinear(self.ctx, _ptr(src), _ptr(flow), src.numel() // (h * w), h, w, _ptr(out),
+                                                        _ptr(valid), _stream(self.device)), "nst_warp_bilinear")
+        return out, valid
+
+    def flow_weights(self, fwd: torch.Tensor, bwd: torch.Tensor) -> torch.Tensor:
+        """The (h,w) reliability plane of a forward / backward flow pair, (2,h,w) each (nst_flow_weights): 0 at
+        disocclusions, motion boundaries and where the backward flow leaves the image, 1 elsewhere."""
+        _chk_dev(bwd, self.device)
+        _, h, w = bwd.shape
+        _chk_dev(bwd, self.device, (2, h, w))
+        _chk_dev(fwd, self.device, (2, h, w))
+        out = torch.empty((h, w), dtype=torch.float32, device=self.device)
+        _lib.check(self.ctx, self.lib.nst_flow_weights(self.ctx, _ptr(fwd), _ptr(bwd), h, w, _ptr(out), _stream(self.device)),
+                   "nst_flow_weights")
+        return out
+
     def bicubic_half(self, x: torch.Tensor) -> torch.Tensor:
         _chk_dev(x, self.device)
         b, c, h, w = x.shape
@@ -1086,6 +1176,8 @@ class PixelOptimizer:
             raise ValueError("matting_weight cannot be combined with stripe sharding (reset_matting())")
         _gram.check_exclusive(getattr(e, "gram_shift", None), stripes=True)
         _mom.check_exclusive(getattr(e, "moment_loss", None), stripes=True)
+        if any(e.anchor(l)[0] > 0 for l in range(e.levels)):
+            raise ValueError("a temporal anchor cannot be combined with stripe sharding (clear_anchor())")
         contents = list(content_t) if isinstance(content_t, (list, tuple)) else [content_t]
         styles = list(style_t) if isinstance(style_t, (list, tuple)) else [style_t]
         if blend is not None and styles and isinstance(styles[0], torch.Tensor):

@@ -239,6 +239,13 @@ class _DeviceJob:
             self.close()
             raise
 
+    def set_anchor(self, anchor_levels, weight_levels, gamma):
+        """The temporal term's anchors and weights of the levels (StyleEngine.set_anchor; None: a level without)."""
+        with torch.cuda.device(self.dev), torch.cuda.stream(self.job_stream):
+            for lvl, (a, c) in enumerate(zip(anchor_levels, weight_levels)):
+                if a is not None:
+                    self.engine.set_anchor(lvl, a, c, gamma=gamma)
+
     def step(self, cw, sw, tvw):
         """One optimizer.step(closure) (nst_opt_step).  Runs on a pool thread, whose current stream is its own."""
         with torch.cuda.stream(self.job_stream):
@@ -313,6 +320,7 @@ class NeuralStyleTransfer:
         self.__style_imgs = style_imgs
         self.__optimizer_name = optimizer_name
         self.settings = _job.JobSettings()       # the optional settings of the next `process`: the set_* below update it
+        self.__anchor = None                     # set_anchor: data of the next `process`, not a setting
 
     def set_feature_maps(self, content_layer=None, style_layers=None, use_relu=True):
         """Extension: the feature maps the losses of the next `process` read - a content map and a set of style maps of
@@ -403,6 +411,26 @@ class NeuralStyleTransfer:
         or together with regions."""
         self.settings.update(moment_weight=moment_weight, moment_terms=moment_terms, moment_epsilon=moment_epsilon)
 
+    def set_anchor(self, anchor_levels=None, weight_levels=None, gamma=0.0):
+        """Extension: the temporal consistency term of Ruder, Dosovitskiy & Brox 2016 in the next `process`: per pyramid level
+        gamma times the weighted mean squared distance of the level image from an anchor (nst_level_set_anchor in
+        include/nst_hip.h has the definition).  `anchor_levels`: per level, top level first, a device tensor of the level
+        image's size ((1,3,h,w) prepared; (1,1,h,w) = StyleEngine.luminance(...) under preserve_color "luminance") or None
+        for a level without the term; `weight_levels`: per level an (h,w) device tensor in [0,1] or None for ones, or None
+        for ones everywhere.  Data of one job, like the content levels - not one of `settings`.  None or gamma 0: off.
+        ValueError for a negative or non-finite gamma or lists of differing lengths."""
+        g = float(gamma)
+        if not np.isfinite(g) or g < 0.0:
+            raise ValueError(f"the temporal weight must be finite and >= 0, got {gamma!r}")
+        if anchor_levels is None or g == 0.0:
+            self.__anchor = None
+            return
+        anchors = list(anchor_levels)
+        weights = list(weight_levels) if weight_levels is not None else [None] * len(anchors)
+        if len(weights) != len(anchors):
+            raise ValueError(f"{len(anchors)} anchor levels but {len(weights)} weight levels")
+        self.__anchor = (anchors, weights, g)
+
     async def process(self, content_imgs, init_img, lr_start, iters_num, content_weight, style_weight, tv_weight,
                       init_img_name):
         # validates the model name exactly as the reference does (ValueError for anything but vgg19)
@@ -428,7 +456,15 @@ class NeuralStyleTransfer:
             if "blend" in resolved:
                 extra, blend = resolved["blend"]
                 resolved["blend"] = ([device_image.recolor_histogram(setup, content_top, [up(s) for s in lv]) for lv in extra], blend)
+        if self.__anchor is not None and len(self.__anchor[0]) != len(content_imgs):
+            raise ValueError(f"{len(self.__anchor[0])} anchor levels for a job of {len(content_imgs)} levels")
         job = _make_job(self.__device, self.__optimizer_name, style_imgs, content_imgs, init_img, lr_start, **resolved)
+        if self.__anchor is not None:        # (data of the job, handed over once the job exists: not one of its settings)
+            try:
+                job.set_anchor(*self.__anchor)
+            except BaseException:
+                job.close()
+                raise
         cw, sw, tvw = float(content_weight), float(style_weight), float(tv_weight)
         loop = asyncio.get_running_loop()
 
@@ -512,22 +548,51 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
     moment loss - channel means and deviations of the style maps matched to the style's - see
     NeuralStyleTransfer.set_moments (None or 0: off); validated before any GPU work too; not with `content_regions` /
     `style_regions`."""
-    settings = _job.JobSettings(
-        for_job=True, content_layer=content_layer, style_layers=style_layers, use_relu=use_relu, preserve_color=preserve_color,
-        pooling=pooling, extra_styles=extra_styles, style_blend=style_blend, style_layer_weights=style_layer_weights,
-        content_regions=content_regions, style_regions=style_regions, region_weights=region_weights,
-        laplacian_weight=laplacian_weight, laplacian_pool=laplacian_pool, gram_shift=gram_shift, matting_weight=matting_weight,
-        matting_epsilon=matting_epsilon, moment_weight=moment_weight, moment_terms=moment_terms, moment_epsilon=moment_epsilon)
+    kw = dict(content_layer=content_layer, style_layers=style_layers, use_relu=use_relu, preserve_color=preserve_color,
+              pooling=pooling, extra_styles=extra_styles, style_blend=style_blend, style_layer_weights=style_layer_weights,
+              content_regions=content_regions, style_regions=style_regions, region_weights=region_weights,
+              laplacian_weight=laplacian_weight, laplacian_pool=laplacian_pool, gram_shift=gram_shift, matting_weight=matting_weight,
+              matting_epsilon=matting_epsilon, moment_weight=moment_weight, moment_terms=moment_terms, moment_epsilon=moment_epsilon)
+    job = _transfer_from(content_n_style, content_weight, style_weight, tv_weight, optimizer, model, init_method, iters_num,
+                         levels_num, noise_factor, noise_levels, noise_levels_central_amplitude, noise_levels_peripheral_amplitude,
+                         noise_levels_dispersion, device=device, start=None, **kw)
+    try:
+        async for out in job:
+            yield out
+    finally:
+        await job.aclose()       # (a consumer that stops early: the job's device objects go here, not at collection)
+
+
+def _transfer_from(content_n_style, content_weight, style_weight, tv_weight, optimizer, model, init_method, iters_num, levels_num,
+                   noise_factor, noise_levels, noise_levels_central_amplitude, noise_levels_peripheral_amplitude,
+                   noise_levels_dispersion, *, device=None, start=None, **keywords):
+    """The settings validation of neural_style_transfer() (`keywords`: its keyword-only parameters), here and now - before any
+    GPU work, ValueError - and then the job as an async generator, from the `init_method` image or from `start` (_transfer)."""
+    settings = _job.JobSettings(for_job=True, **keywords)
 
     def level_shapes(img):      # (the level sizes follow from the image size: top level first)
         ih, iw = np.shape(img)[:2]
         return [host_image.level_size(ih, iw, lvl) for lvl in range(max(levels_num - 1, 0), -1, -1)]
 
     settings.resolve(lambda: level_shapes(content_n_style.content[1]), lambda: level_shapes(content_n_style.style[1]))
+    extra_styles = keywords.get("extra_styles")
     extra_styles = list(extra_styles) if extra_styles is not None else []
     for img in extra_styles:
         if np.ndim(img) != 3 or np.shape(img)[2] != 3:
             raise ValueError(f"extra_styles: expected HWC images with 3 channels, got shape {np.shape(img)}")
+    return _transfer(content_n_style, content_weight, style_weight, tv_weight, optimizer, model, init_method, iters_num, levels_num,
+                     noise_factor, noise_levels, noise_levels_central_amplitude, noise_levels_peripheral_amplitude,
+                     noise_levels_dispersion, device, settings, keywords.get("preserve_color"), extra_styles,
+                     keywords.get("style_blend"), start)
+
+
+async def _transfer(content_n_style, content_weight, style_weight, tv_weight, optimizer, model, init_method, iters_num, levels_num,
+                    noise_factor, noise_levels, noise_levels_central_amplitude, noise_levels_peripheral_amplitude,
+                    noise_levels_dispersion, device, settings, preserve_color, extra_styles, style_blend, start=None):
+    """neural_style_transfer() below its settings validation: `settings` is its validated JobSettings, `extra_styles` its
+    checked list.  `start` (video.py): None, or a callable (setup engine, level-0 (h, w)) -> (start image: a device HWC
+    tensor the job starts from in place of the `init_method` image, anchor levels, weight levels, gamma) - the arguments of
+    NeuralStyleTransfer.set_anchor - called once the level sizes are known."""
     if device is None:
         if not torch.cuda.is_available():
             raise RuntimeError("no GPU visible: the HIP style-transfer engine has no CPU path")
@@ -548,13 +613,20 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
         extra_levels = [device_image.recolor_histogram(setup, content_levels[0], lv) for lv in extra_levels]
         style_init = style_levels[0]
     level = max(levels_num - 1, 0)
-    init_img, tag = device_image.initial_image(
-        setup, init_method, content_dev, style_dev, content_levels[0], style_levels[0], level,
-        noise_factor, noise_levels, noise_levels_central_amplitude, noise_levels_peripheral_amplitude,
-        noise_levels_dispersion, style_init=style_init)
-    init_name = {"random": "random", "content": content_n_style.content[0], "style": content_n_style.style[0]}[tag]
+    anchor = None
+    if start is None:
+        init_img, tag = device_image.initial_image(
+            setup, init_method, content_dev, style_dev, content_levels[0], style_levels[0], level,
+            noise_factor, noise_levels, noise_levels_central_amplitude, noise_levels_peripheral_amplitude,
+            noise_levels_dispersion, style_init=style_init)
+        init_name = {"random": "random", "content": content_n_style.content[0], "style": content_n_style.style[0]}[tag]
+    else:
+        init_img, *anchor = start(setup, tuple(content_levels[0].shape[:2]))
+        init_name = "previous frame"
 
     nst = NeuralStyleTransfer(device, model, style_levels, optimizer)
+    if anchor is not None:
+        nst.set_anchor(*anchor)
     # (the extra styles as their pyramids; "histogram" has recoloured the style levels above)
     settings.update(extra_styles=extra_levels, style_blend=style_blend if extra_levels else None)
     if preserve_color == "histogram":

@@ -493,6 +493,63 @@ int nst_level_set_targets_guided(nst_ctx* ctx, int level, const float* content, 
 int nst_level_guidance(const nst_ctx* ctx, int level, int* R, float lambda[NST_MAX_REGIONS], double mass[5 * NST_MAX_REGIONS]);
 int nst_level_guidance_planes(nst_ctx* ctx, int level, int scale, float* out, void* stream);
 
+/* Temporal consistency: a pixel-space term that holds a level image to an anchor under a per-pixel weight plane, the warp
+ * that makes the anchor and the weights that say where to trust it.  After Ruder, Dosovitskiy & Brox, "Artistic Style
+ * Transfer for Videos" (GCPR 2016): frame i starts from the previous result warped along the optical flow (section 3,
+ * "initialization"), a weighted squared distance to that warped result joins the loss (their eq. 7, the short-term temporal
+ * loss), and the weight is 0 where the flow is unreliable (section 4, after Sundaram, Brox & Keutzer, ECCV 2010).  The
+ * reference has no counterpart.  The anchor is DATA of one job, like the content levels - not a setting of the context.
+ * Term of a level image y (C,h,w), C = 3, or 1 under NST_COLOR_LUMINANCE, an anchor a (C,h,w) and weights c (h,w) in [0,1]
+ * - tmp = (float)((1/n) sum_{ch,p} c(p) (y(ch,p) - a(ch,p))^2), n = C h w.  c absent: ones.
+ * - The differences and products are formed in double from the fp32 planes; the sum is in double in a fixed two-stage order
+ *   (a fixed grid of blocks whose threads add their strided shares in index order, then the block partials).
+ * Loss row
+ * - A level with an anchor of weight gamma > 0 has the total (... + mom) + gamma tmp: added after the moment term, product
+ *   and sum each rounded.  NST_LOSS_ROW stays 4.  nst_job_temporal_losses returns the tmp.
+ * Gradient
+ * - d/dy(ch,p) = coef (c(p) (y(ch,p) - a(ch,p))), coef = (float)((double)gamma 2 / n): the difference, the product with c
+ *   (left out when c is absent) and the product with coef are fp32, each rounded.  It is accumulated into the level gradient
+ *   after the total-variation, Laplacian and matting gradients; a term of exactly 0 leaves the gradient's bits as they are.
+ * - Nothing is kept between the halves: the backward half forms the difference again.
+ * Luminance
+ * - The anchor is one plane in the units of the optimised plane u (nst_luminance of the warped frame), and C = 1 above.
+ * Warp (nst_warp_bilinear): out(ch, x, y) = bilinear(src(ch), x + dx, y + dy), flow plane 0 = dx, plane 1 = dy, in pixels
+ * - Per axis the sample position is the integer part and the fraction of the FLOW alone: x0 = x + (int)floor(dx),
+ *   t = dx - floor(dx); x + dx is never formed in fp32, so the fraction does not depend on the image size.
+ * - Taps x0, x0 + 1 (y0, y0 + 1) clamped to the image; out = (v00 (1-tx) + v01 tx)(1-ty) + (v10 (1-tx) + v11 tx) ty in fp32,
+ *   every operation rounded once.
+ * - valid = 1 where the four taps lie inside the image before clamping (x0 >= 0, x0 + 1 <= w - 1, likewise y), else 0: a
+ *   sample exactly on the last column or row has its second tap outside and is not valid.
+ * - Non-finite flow: valid = 0 and out = the source pixel itself.
+ * Flow weights (nst_flow_weights): c (h,w) from the forward flow fwd (frame i-1 -> i) and the backward flow bwd (i -> i-1)
+ * - w~(p) = fwd sampled bilinearly at p + bwd(p), by the position rule of the warp; (u^, v^) = bwd(p).
+ * - c(p) = 0 where |w~ + bwd|^2 > 0.01 (|w~|^2 + |bwd|^2) + 0.5 (disocclusion: the flows do not undo one another),
+ * - c(p) = 0 where |grad u^|^2 + |grad v^|^2 > 0.01 |bwd|^2 + 0.002 (motion boundary), grad = central differences with
+ *   replicated borders, 0.5 (f(x+1) - f(x-1)) and likewise in y,
+ * - c(p) = 0 where the sample of w~ is not valid or bwd(p) is not finite, c(p) = 1 everywhere else.
+ * - The comparisons run in fp32, one rounding per operation, in this order: (su su + sv sv), s = w~ + bwd, against
+ *   0.01 ((wu wu + wv wv) + (bu bu + bv bv)) + 0.5; ((ux ux + uy uy) + (vx vx + vy vy)) against 0.01 (bu bu + bv bv) + 0.002.
+ * No float atomics: a closure with the term is bitwise reproducible, as closure reuse and the lazy backward need.
+ *
+ * nst_level_set_anchor: anchor = device (C,h,w) of the level's size, weights = device (h,w) or NULL for ones; both are
+ * copied into buffers of the level that nst_ctx_bytes counts, and the caller's are free on return (the call synchronises
+ * `stream`).  A NULL anchor or gamma = 0 clears the level's term and credits exactly what it was charged.  NST_E_STATE: no
+ * configured job.  NST_E_ARG: level out of range, gamma negative or non-finite.  A refusal changes nothing about the level.
+ * Life cycle of nst_level_set_guidance: the call waits for the context's work, never allocates in a closure, drops any
+ * captured closure graph and ends the validity of an optimiser's remembered closure and of a pending nst_closure_backward.
+ * The targets stay.  nst_job_configure drops every level's anchor with the levels; nst_job_set_color drops them when the
+ * mode changes (the planes are the other mode's).  A level without an anchor is evaluated by exactly the launches of a
+ * context that never had one and computes the same bits.  The term composes with every setting, conv mode and schedule
+ * (use_graph included), the closure halves and level sharding (a level not owned contributes zeros).  The stripe closure
+ * (nst_window_*) returns NST_E_STATE while its level carries an anchor.
+ * nst_level_anchor: the level's gamma (0: none) and whether it has a weight plane (either pointer may be NULL).
+ * nst_job_temporal_losses: the unweighted tmp of the last closure per level, to out (DEVICE, levels floats); zeros for
+ * levels without an anchor or outside the last level mask.  Asynchronous on `stream`. */
+int nst_level_set_anchor(nst_ctx* ctx, int level, const float* anchor /* device (C,h,w), or NULL: clear */,
+                         const float* weights /* device (h,w), or NULL: ones */, float gamma, void* stream);
+int nst_level_anchor(const nst_ctx* ctx, int level, float* gamma, int* weighted);
+int nst_job_temporal_losses(nst_ctx* ctx, float* out /* device, levels */, void* stream);
+
 /* optimizer_step_callback without its LR decay and prints (neural_style_transfer.py:152-199) =
  * sum over levels of LossBuilder.build (:84-112) on the bicubic 1/2 chain of x (:170-176),
  * then backward (:193).  x, grad: device (3,H0,W0) ((1,H0,W0) under NST_COLOR_LUMINANCE).  losses: device, NST_LOSS_ROW*levels+1
@@ -717,6 +774,19 @@ int nst_laplacian_loss(nst_ctx* ctx, const float* y, const float* content, int C
  * the same with and without grad.  Reads no job state.  Synchronous. */
 int nst_matting_loss(nst_ctx* ctx, const float* y, const float* guide, int C, int h, int w, double epsilon, float* value,
                      float* grad /* nullable, overwritten */, void* stream);
+/* The temporal term on its own (nst_level_set_anchor has the definitions of these four): y, anchor device (C,h,w), C = 3 or 1;
+ * weights device (h,w) or NULL for ones.  value (device scalar) = tmp; grad (nullable, overwritten) (C,h,w) = d tmp / dy, with
+ * gamma = 1.  The value is bitwise the same with and without grad.  Reads no job state.  Synchronous.
+ * nst_anchor_geometry: the blocks of the value pass and the elements one block covers per pass of its loop (what a test
+ * sizes its block-boundary case by).
+ * nst_warp_bilinear: src device (C,h,w), C >= 1; flow device (2,h,w); out device (C,h,w), not src; valid device (h,w) or NULL.
+ * nst_flow_weights: fwd, bwd device (2,h,w); out device (h,w).  Both read no job state and are synchronous. */
+int nst_anchor_loss(nst_ctx* ctx, const float* y, const float* anchor, const float* weights /* nullable */, int C, int h, int w,
+                    float* value, float* grad /* nullable, overwritten */, void* stream);
+int nst_anchor_geometry(int* blocks, int* block_elems);
+int nst_warp_bilinear(nst_ctx* ctx, const float* src, const float* flow, int C, int h, int w, float* out,
+                      float* valid /* nullable */, void* stream);
+int nst_flow_weights(nst_ctx* ctx, const float* fwd, const float* bwd, int h, int w, float* out, void* stream);
 /* F.interpolate(x, size=(h//2,w//2), mode='bicubic') (neural_style_transfer.py:173-176) and its
  * transpose (autograd backward); x (C,h,w) -> y (C,h/2,w/2); gy -> gx (overwritten). */
 int nst_bicubic_half(nst_ctx* ctx, const float* x, int C, int h, int w, float* y, void* stream);
@@ -786,7 +856,8 @@ int nst_luminance_recombine(nst_ctx* ctx, const float* u, const float* content, 
  * under NST_POOL_AVG (nst_job_set_pooling) and under style layer weights other than 1 (nst_job_set_style_weights).  The
  * Gram targets are the level's, so those of nst_level_set_targets_blend are honoured.  nst_window_* returns NST_E_STATE
  * while the Laplacian loss is set (nst_job_set_laplacian with K > 0), the matting term (nst_job_set_matting with gamma > 0),
- * a Gram shift (nst_job_set_gram_shift) or the moment loss (nst_job_set_moments with a positive weight). */
+ * a Gram shift (nst_job_set_gram_shift) or the moment loss (nst_job_set_moments with a positive weight), and while the
+ * level carries an anchor (nst_level_set_anchor). */
 int nst_window_sums_count(size_t* count);
 int nst_window_begin(nst_ctx* ctx, const float* xs, int row0, int rows, int H0, float* sums, void* stream);
 int nst_window_end(nst_ctx* ctx, const float* xs, int row0, int rows, int H0, float content_weight, float style_weight,
