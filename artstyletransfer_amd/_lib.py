@@ -28,6 +28,7 @@ NST_COLOR_LUMINANCE = 1
 NST_POOL_MAX = 0
 NST_POOL_AVG = 1
 NST_MAX_LAPLACIAN = 4
+NST_MAX_FLOW_SCALES = 12
 
 c_float_p = C.POINTER(C.c_float)
 REDUCE_HOOK = C.CFUNCTYPE(None, C.c_void_p)
@@ -87,6 +88,14 @@ SYMBOLS = {
     "nst_anchor_geometry": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "nst_warp_bilinear": (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, c_void, c_void]),
     "nst_flow_weights": (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, c_void, c_void]),
+    "nst_flow_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
+    "nst_flow_estimate": (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, c_void, c_void,
+                                    C.c_size_t, c_void]),
+    "nst_flow_reduce": (C.c_int, [c_void, c_void, C.c_int, C.c_int, c_void, c_void]),
+    "nst_flow_prolong": (C.c_int, [c_void, c_void, C.c_int, C.c_int, c_void, c_void]),
+    "nst_flow_linearize": (C.c_int, [c_void, c_void, c_void, c_void, C.c_int, C.c_int, c_void, c_void, c_void, c_void]),
+    "nst_flow_sweeps": (C.c_int, [c_void, c_void, c_void, c_void, c_void, C.c_int, C.c_int, C.c_float, C.c_int, c_void, c_void,
+                                  c_void]),
     "nst_job_set_gram_shift": (C.c_int, [c_void, c_float_p, C.c_uint]),
     "nst_job_gram_shift": (C.c_int, [c_void, c_float_p, C.POINTER(C.c_uint)]),
     "nst_level_gram_offsets": (C.c_int, [c_void, C.c_int, C.c_int, c_void, c_void]),

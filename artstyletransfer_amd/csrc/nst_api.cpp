@@ -6,6 +6,7 @@
 // Host-side control only; every FLOP and byte of the path is in the .hip kernels.
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <cstring>
 
 #include "nst_ctx.h"
@@ -298,6 +299,109 @@ int nst_flow_weights(nst_ctx* ctx, const float* fwd, const float* bwd, int h, in
     if (h < 1 || w < 1) return fail(ctx, NST_E_ARG, "the flow fields must be at least 1x1");
     hipStream_t s = static_cast<hipStream_t>(stream);
     HIPCHK(ctx, launch_flow_weights(fwd, bwd, h, w, out, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return NST_OK;
+}
+
+// ---- the flow estimator (include/nst_hip.h, nst_flow_estimate; flow.hip).  The caller owns every buffer: the context
+// allocates nothing here, so nst_ctx_bytes does not move.  All synchronous.
+static_assert(NST_FLOW_MAX_SCALES == NST_MAX_FLOW_SCALES, "nst_kernels.h and include/nst_hip.h disagree about the scale cap");
+
+// an output of `nb` floats that shares memory with `na` floats another argument names (the kernels read neighbours: none runs in place)
+static bool flow_overlap(const float* a, size_t na, const float* b, size_t nb) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a && b && a0 < b0 + nb * sizeof(float) && b0 < a0 + na * sizeof(float);
+}
+// alpha is finite and > 0 and its fp32 square, the smoothness weight the sweep divides by, a normal number (a square that
+// underflows leaves a pixel without a data term with 0 / 0)
+static bool flow_alpha_ok(float alpha) {
+    const float a2 = alpha * alpha;
+    return std::isfinite(alpha) && alpha > 0.f && std::isnormal(a2);
+}
+static const char* const kFlowAlpha = "alpha must be finite and > 0 and its fp32 square a normal number";
+static const char* const kFlowOverlap = "an output overlaps another argument: no stage of the flow estimator runs in place";
+
+int nst_flow_workspace(int h, int w, int scales, size_t* floats, int* scales_used) {
+    FlowLayout l;
+    if (flow_layout(h, w, scales, &l) != 0) return NST_E_ARG;
+    if (floats) *floats = l.floats;
+    if (scales_used) *scales_used = l.scales;
+    return NST_OK;
+}
+
+int nst_flow_estimate(nst_ctx* ctx, const float* from, const float* to, int h, int w, float alpha, int scales, int warps,
+                      int iterations, float* flow, float* workspace, size_t workspace_floats, void* stream) {
+    NSTCHK(bind(ctx));
+    if (!from || !to || !flow || !workspace) return fail(ctx, NST_E_ARG, "null argument");
+    if (h < 1 || w < 1) return fail(ctx, NST_E_ARG, "the images must be at least 1x1");
+    if (!flow_alpha_ok(alpha)) return fail(ctx, NST_E_ARG, kFlowAlpha);
+    if (warps < 1 || iterations < 1) return fail(ctx, NST_E_ARG, "warps and iterations must be at least 1");
+    FlowLayout l;
+    if (flow_layout(h, w, scales, &l) != 0) return fail(ctx, NST_E_ARG, "scales must lie in 0 .. NST_MAX_FLOW_SCALES");
+    if (workspace_floats < l.floats) return fail(ctx, NST_E_ARG, "the workspace is smaller than nst_flow_workspace says");
+    const size_t hw = (size_t)h * w;
+    if (flow_overlap(from, hw, flow, 2 * hw) || flow_overlap(to, hw, flow, 2 * hw) || flow_overlap(workspace, l.floats, flow, 2 * hw) ||
+        flow_overlap(from, hw, workspace, l.floats) || flow_overlap(to, hw, workspace, l.floats))
+        return fail(ctx, NST_E_ARG, kFlowOverlap);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIPCHK(ctx, launch_flow_estimate(from, to, l, alpha * alpha, warps, iterations, flow, workspace, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return NST_OK;
+}
+
+int nst_flow_reduce(nst_ctx* ctx, const float* in, int h, int w, float* out, void* stream) {
+    NSTCHK(bind(ctx));
+    if (!in || !out) return fail(ctx, NST_E_ARG, "null argument");
+    if (h < 1 || w < 1) return fail(ctx, NST_E_ARG, "the image must be at least 1x1");
+    if (flow_overlap(in, (size_t)h * w, out, (size_t)((h + 1) / 2) * ((w + 1) / 2))) return fail(ctx, NST_E_ARG, kFlowOverlap);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIPCHK(ctx, launch_flow_reduce(in, h, w, out, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return NST_OK;
+}
+
+int nst_flow_prolong(nst_ctx* ctx, const float* coarse, int h, int w, float* fine, void* stream) {
+    NSTCHK(bind(ctx));
+    if (!coarse || !fine) return fail(ctx, NST_E_ARG, "null argument");
+    if (h < 1 || w < 1) return fail(ctx, NST_E_ARG, "the fine grid must be at least 1x1");
+    if (flow_overlap(coarse, 2 * (size_t)((h + 1) / 2) * ((w + 1) / 2), fine, 2 * (size_t)h * w)) return fail(ctx, NST_E_ARG, kFlowOverlap);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIPCHK(ctx, launch_flow_prolong(coarse, h, w, fine, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return NST_OK;
+}
+
+int nst_flow_linearize(nst_ctx* ctx, const float* from, const float* to, const float* flow, int h, int w, float* ix, float* iy,
+                       float* rho, void* stream) {
+    NSTCHK(bind(ctx));
+    if (!from || !to || !flow || !ix || !iy || !rho) return fail(ctx, NST_E_ARG, "null argument");
+    if (h < 1 || w < 1) return fail(ctx, NST_E_ARG, "the images must be at least 1x1");
+    const size_t hw = (size_t)h * w;
+    float* const outs[3] = {ix, iy, rho};
+    for (int i = 0; i < 3; ++i)
+        if (flow_overlap(from, hw, outs[i], hw) || flow_overlap(to, hw, outs[i], hw) || flow_overlap(flow, 2 * hw, outs[i], hw) ||
+            flow_overlap(outs[(i + 1) % 3], hw, outs[i], hw))
+            return fail(ctx, NST_E_ARG, kFlowOverlap);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIPCHK(ctx, launch_flow_linearize(from, to, flow, flow + hw, h, w, ix, iy, rho, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return NST_OK;
+}
+
+int nst_flow_sweeps(nst_ctx* ctx, const float* ix, const float* iy, const float* rho, const float* flow_in, int h, int w, float alpha,
+                    int n, float* flow_out, float* scratch, void* stream) {
+    NSTCHK(bind(ctx));
+    if (!ix || !iy || !rho || !flow_in || !flow_out || (n > 1 && !scratch)) return fail(ctx, NST_E_ARG, "null argument");
+    if (h < 1 || w < 1 || n < 1) return fail(ctx, NST_E_ARG, "the planes must be at least 1x1 and n at least 1");
+    if (!flow_alpha_ok(alpha)) return fail(ctx, NST_E_ARG, kFlowAlpha);
+    const size_t hw = (size_t)h * w;
+    float* const outs[2] = {flow_out, n > 1 ? scratch : nullptr};       // (scratch is not touched for n = 1)
+    for (int i = 0; i < 2; ++i)
+        if (flow_overlap(ix, hw, outs[i], 2 * hw) || flow_overlap(iy, hw, outs[i], 2 * hw) || flow_overlap(rho, hw, outs[i], 2 * hw) ||
+            flow_overlap(flow_in, 2 * hw, outs[i], 2 * hw) || (i == 1 && flow_overlap(flow_out, 2 * hw, outs[i], 2 * hw)))
+            return fail(ctx, NST_E_ARG, kFlowOverlap);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIPCHK(ctx, launch_flow_sweeps(ix, iy, rho, flow_in, h, w, alpha * alpha, n, flow_out, scratch, s));
     HIPCHK(ctx, hipStreamSynchronize(s));
     return NST_OK;
 }

@@ -283,6 +283,34 @@ hipError_t launch_warp_bilinear(const float* src, const float* flow, int C, int 
 // out (h,w) = the reliability plane c of a forward / backward flow pair
 hipError_t launch_flow_weights(const float* fwd, const float* bwd, int h, int w, float* out, hipStream_t stream);
 
+// flow.hip: multi-scale Horn-Schunck optical flow with warping (include/nst_hip.h, nst_flow_estimate, has the definitions) ----
+constexpr int NST_FLOW_MAX_SCALES = 12;   // = NST_MAX_FLOW_SCALES
+// The scales of one estimate and where its planes lie in the caller's workspace (offsets in floats, multiples of 4).
+struct FlowLayout {
+    int scales;                                                 // scales in use, scale 0 = the images themselves
+    int h[NST_FLOW_MAX_SCALES], w[NST_FLOW_MAX_SCALES];
+    size_t from[NST_FLOW_MAX_SCALES], to[NST_FLOW_MAX_SCALES];  // the reduced planes of scale s >= 1
+    size_t ix, iy, rho;                                         // the linearisation, h w floats each, shared by the scales
+    size_t other;                                               // the second flow buffer, 2 h w floats
+    size_t floats;                                              // the whole workspace
+};
+// 0, or -1 for h or w < 1, scales < 0 or above the cap.  scales = 0: as many as fit.  Pure.
+int flow_layout(int h, int w, int scales, FlowLayout* out);
+// out ((h+1)/2, (w+1)/2) = the 5-tap binomial of in (h,w) along x, then along y, every second pixel
+hipError_t launch_flow_reduce(const float* in, int h, int w, float* out, hipStream_t stream);
+// fine (2,h,w) = 2 x the two-tap mean per axis of coarse (2,(h+1)/2,(w+1)/2)
+hipError_t launch_flow_prolong(const float* coarse, int h, int w, float* fine, hipStream_t stream);
+// Ix, Iy, rho (h,w) of the pair at the flow (u, v); zeros where the four taps do not lie inside the image
+hipError_t launch_flow_linearize(const float* from, const float* to, const float* u, const float* v, int h, int w, float* Ix,
+                                 float* Iy, float* rho, hipStream_t stream);
+// n Jacobi sweeps of the flow `in` (2,h,w), one launch each, alternating between `out` and `tmp` so that the last writes `out`;
+// tmp may be null for n = 1; the first sweep's target must not be `in`
+hipError_t launch_flow_sweeps(const float* Ix, const float* Iy, const float* rho, const float* in, int h, int w, float alpha2, int n,
+                              float* out, float* tmp, hipStream_t stream);
+// the driver: pyramids, then per scale `warps` x (linearise, `iterations` sweeps), prolong; the result ends in `flow`
+hipError_t launch_flow_estimate(const float* from, const float* to, const FlowLayout& l, float alpha2, int warps, int iterations,
+                                float* flow, float* ws, hipStream_t stream);
+
 // loss assembly -----------------------------------------------------------------------------------
 struct LevelLossInputs {
     const double* content_partial;   // MSE_BLOCKS doubles

@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "nst_kernels.h"
+#include "nst_sample.h"   // axis_tap, bilinear: the position rule the warp, the flow weights and flow.hip share
 
 namespace nst {
 
@@ -155,39 +156,6 @@ hipError_t launch_anchor_value(const double* partial, int blocks, double n, floa
     hipLaunchKernelGGL(anchor_value_kernel, dim3(1), dim3(256), 0, stream, partial, blocks, n, out);
     return hipGetLastError();
 }
-
-// ------------------------------------------------------------------ the bilinear sample both kernels below share
-namespace {
-
-// The sample position of one axis: pixel index x plus displacement d, as integer part and fraction of d ALONE - x + d is
-// never formed in fp32, so the fraction is as accurate at every image size.  i0, i1: the two taps clamped to [0, n - 1]; t: the
-// weight of the second; inside: both taps lie in the image before clamping.  d must be finite.
-struct AxisTap { int i0, i1; float t; bool inside; };
-__device__ __forceinline__ AxisTap axis_tap(int x, float d, int n) {
-    const float f = floorf(d);
-    AxisTap r;
-    r.t = d - f;                                  // in [0, 1]; exact for d >= 0, one rounding of at most 2^-25 for d < 0 - whatever x is
-    // a displacement beyond the image on either side: every tap clamps to the border whatever the integer part is
-    const float lim = (float)n + 1.f;
-    const int k = (int)fminf(fmaxf(f, -lim), lim);
-    const int a = x + k, b = a + 1;
-    r.inside = a >= 0 && b <= n - 1;
-    r.i0 = min(max(a, 0), n - 1);
-    r.i1 = min(max(b, 0), n - 1);
-    return r;
-}
-// (v00 (1 - tx) + v01 tx)(1 - ty) + (v10 (1 - tx) + v11 tx) ty, every operation rounded once
-__device__ __forceinline__ float bilinear(const float* __restrict__ plane, int w, const AxisTap& ax, const AxisTap& ay) {
-#pragma clang fp contract(off)
-    const float* r0 = plane + (size_t)ay.i0 * w;
-    const float* r1 = plane + (size_t)ay.i1 * w;
-    const float ux = 1.f - ax.t, uy = 1.f - ay.t;
-    const float top = r0[ax.i0] * ux + r0[ax.i1] * ax.t;
-    const float bot = r1[ax.i0] * ux + r1[ax.i1] * ax.t;
-    return top * uy + bot * ay.t;
-}
-
-}  // namespace
 
 // ------------------------------------------------------------------ warp
 __global__ __launch_bounds__(256) void warp_kernel(const float* __restrict__ src, const float* __restrict__ flow, int C, int h, int w,

@@ -17,6 +17,7 @@ from . import gram_modes as _gram
 from . import moment_modes as _mom
 from . import laplacian_modes as _lap
 from . import matting_modes as _mat
+from . import flow_modes as _flow
 from ._lib import NST_LOSS_ROW, NstError, StepInfo
 
 TAP_CHANNELS = (64, 128, 256, 512, 512, 512)
@@ -54,6 +55,15 @@ def _chk_dev(t: torch.Tensor, device, shape=None):
         raise NstError(f"tensor is on {t.device}, context on {device}")
     if shape is not None and tuple(t.shape) != tuple(shape):
         raise NstError(f"expected shape {tuple(shape)}, got {tuple(t.shape)}")
+
+
+def flow_workspace(h: int, w: int, scales: int = 0) -> Tuple[int, int]:
+    """(floats of the workspace nst_flow_estimate needs for two (h,w) planes, pyramid scales it uses) (nst_flow_workspace): a
+    pure function of the library, no GPU.  ValueError for h or w < 1 and scales outside 0 .. NST_MAX_FLOW_SCALES."""
+    floats, used = C.c_size_t(), C.c_int()
+    if _lib.load().nst_flow_workspace(int(h), int(w), int(scales), C.byref(floats), C.byref(used)) != _lib.NST_OK:
+        raise ValueError(f"no flow workspace for {h}x{w} planes and scales={scales}")
+    return floats.value, used.value
 
 
 class StyleEngine:
@@ -927,6 +937,62 @@ class StyleEngine:
         out = torch.empty((h, w), dtype=torch.float32, device=self.device)
         _lib.check(self.ctx, self.lib.nst_flow_weights(self.ctx, _ptr(fwd), _ptr(bwd), h, w, _ptr(out), _stream(self.device)),
                    "nst_flow_weights")
+        return out
+
+    # ---- the flow estimator (nst_flow_estimate in include/nst_hip.h has the definitions); every buffer is torch's
+    def flow_estimate(self, from_plane: torch.Tensor, to_plane: torch.Tensor, params=None) -> torch.Tensor:
+        """The (2,h,w) flow w = (u, v) with from(p) ~ to(p + w(p)) of two (h,w) planes on the 0 ... 255 scale of luminance()
+        (nst_flow_estimate): multi-scale Horn-Schunck with warping.  `params`: a flow_modes.FlowParams (None: the defaults)."""
+        p = _flow.normalize_flow(params)
+        _chk_dev(from_plane, self.device)
+        h, w = from_plane.shape
+        _chk_dev(to_plane, self.device, (h, w))
+        floats, _ = flow_workspace(h, w, p.scales)
+        work = torch.empty(floats, dtype=torch.float32, device=self.device)
+        out = torch.empty((2, h, w), dtype=torch.float32, device=self.device)
+        _lib.check(self.ctx, self.lib.nst_flow_estimate(self.ctx, _ptr(from_plane), _ptr(to_plane), h, w, p.alpha, p.scales, p.warps,
+                                                        p.iterations, _ptr(out), _ptr(work), floats, _stream(self.device)),
+                   "nst_flow_estimate")
+        return out
+
+    def flow_reduce(self, plane: torch.Tensor) -> torch.Tensor:
+        """One pyramid step of an (h,w) plane: ((h+1)//2, (w+1)//2) (nst_flow_reduce)."""
+        _chk_dev(plane, self.device)
+        h, w = plane.shape
+        out = torch.empty(((h + 1) // 2, (w + 1) // 2), dtype=torch.float32, device=self.device)
+        _lib.check(self.ctx, self.lib.nst_flow_reduce(self.ctx, _ptr(plane), h, w, _ptr(out), _stream(self.device)), "nst_flow_reduce")
+        return out
+
+    def flow_prolong(self, coarse: torch.Tensor, h: int, w: int) -> torch.Tensor:
+        """A (2,(h+1)//2,(w+1)//2) flow on the next finer grid, (2,h,w), its displacements doubled (nst_flow_prolong)."""
+        h, w = int(h), int(w)
+        _chk_dev(coarse, self.device, (2, (h + 1) // 2, (w + 1) // 2))
+        out = torch.empty((2, h, w), dtype=torch.float32, device=self.device)
+        _lib.check(self.ctx, self.lib.nst_flow_prolong(self.ctx, _ptr(coarse), h, w, _ptr(out), _stream(self.device)), "nst_flow_prolong")
+        return out
+
+    def flow_linearize(self, from_plane: torch.Tensor, to_plane: torch.Tensor, flow: torch.Tensor):
+        """(Ix, Iy, rho), (h,w) each: the linearisation of the pair at the (2,h,w) flow (nst_flow_linearize)."""
+        _chk_dev(from_plane, self.device)
+        h, w = from_plane.shape
+        _chk_dev(to_plane, self.device, (h, w))
+        _chk_dev(flow, self.device, (2, h, w))
+        ix, iy, rho = (torch.empty((h, w), dtype=torch.float32, device=self.device) for _ in range(3))
+        _lib.check(self.ctx, self.lib.nst_flow_linearize(self.ctx, _ptr(from_plane), _ptr(to_plane), _ptr(flow), h, w, _ptr(ix), _ptr(iy),
+                                                         _ptr(rho), _stream(self.device)), "nst_flow_linearize")
+        return ix, iy, rho
+
+    def flow_sweeps(self, ix: torch.Tensor, iy: torch.Tensor, rho: torch.Tensor, flow: torch.Tensor, alpha: float, n: int) -> torch.Tensor:
+        """The (2,h,w) flow after n Jacobi sweeps from `flow` under the linearisation (ix, iy, rho) (nst_flow_sweeps)."""
+        _chk_dev(flow, self.device)
+        _, h, w = flow.shape
+        _chk_dev(flow, self.device, (2, h, w))
+        for t in (ix, iy, rho):
+            _chk_dev(t, self.device, (h, w))
+        out = torch.empty_like(flow)
+        scratch = torch.empty_like(flow) if int(n) > 1 else None
+        _lib.check(self.ctx, self.lib.nst_flow_sweeps(self.ctx, _ptr(ix), _ptr(iy), _ptr(rho), _ptr(flow), h, w, float(alpha), int(n),
+                                                      _ptr(out), _ptr(scratch), _stream(self.device)), "nst_flow_sweeps")
         return out
 
     def bicubic_half(self, x: torch.Tensor) -> torch.Tensor:

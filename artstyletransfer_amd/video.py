@@ -1,8 +1,10 @@
 """A sequence of frames stylised with temporal consistency, after Ruder, Dosovitskiy & Brox, "Artistic Style Transfer for
 Videos" (GCPR 2016): frame 0 is the plain job; frame i > 0 starts from the previous result warped along the backward optical
 flow and is held to it by a per-pixel weighted pixel-space term whose weight is 0 where the flow is unreliable
-(nst_level_set_anchor, nst_warp_bilinear and nst_flow_weights in include/nst_hip.h have the definitions).  Optical-flow
-estimation is not part of this project: the caller supplies the flows.
+(nst_level_set_anchor, nst_warp_bilinear and nst_flow_weights in include/nst_hip.h have the definitions).  The flows are
+the caller's, from whatever estimator they trust - or, when none are given, estimated on the device between the luminance
+planes of consecutive frames by multi-scale Horn-Schunck with warping (nst_flow_estimate; flow_modes.FlowParams): a
+baseline that makes the path usable with this project alone, not a replacement for a better estimator.
 
 The anchor is data of one job, like its content levels - not one of job_settings.SETTINGS: it reaches the job through
 NeuralStyleTransfer.set_anchor once the job exists.  Everything here raises ValueError before any GPU work."""
@@ -11,6 +13,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from . import flow_modes as _flow
 from . import host_image
 from . import job_settings as _job
 from . import neural_style_transfer as _nst
@@ -68,19 +71,29 @@ def _planar(flow_hw2, device):
     return torch.from_numpy(flow_hw2).to(device).permute(2, 0, 1).contiguous()
 
 
-async def neural_style_transfer_video(frames, style, backward_flows, forward_flows=None, weights=None, *, temporal_weight, cfg,
+def _luminance_plane(setup, frame, h, w):
+    """The (h,w) device plane 255 Y of a host frame at the size of the yielded images: what the flows are estimated between."""
+    img = torch.from_numpy(np.ascontiguousarray(frame, dtype=np.float32)).to(setup.device)
+    return setup.luminance(setup.resize(img, h, w)).reshape(h, w)
+
+
+async def neural_style_transfer_video(frames, style, backward_flows=None, forward_flows=None, weights=None, *, temporal_weight, cfg,
                                       device=None):
     """Async generator of (frame index, percent, HWC float32 image) over the frames of a sequence, one job per frame in
     order.  `frames`: HWC float [0,1] images of one size; `style`: the style image; `cfg`: a Config - its reference fields
     and the job settings job_settings.handed_on(cfg) gives are used exactly as Task uses them.
     Frame 0 is neural_style_transfer() of (frames[0], style).  Frame i > 0 starts from omega, the last image of frame i - 1
     warped by backward_flows[i-1] - an (h,w,2) array (dx, dy) in pixels from frame i to frame i - 1, at the size of the
-    yielded images (result_size) - and its every level carries the anchor made from omega with weight `temporal_weight`
+    yielded images (result_size); backward_flows None or a flow_modes.FlowParams: estimated on the device
+    (StyleEngine.flow_estimate, with the defaults or these parameters) from the luminance plane of frame i to that of frame
+    i - 1, both resized to the yielded size - and its every level carries the anchor made from omega with weight `temporal_weight`
     (no default: its useful magnitude is a matter of the content, style and TV weights; DESIGN.md 4.12 has measurements) under
     the weight plane c = weights[i-1] if given ((h,w) in [0,1]), else StyleEngine.flow_weights(forward_flows[i-1],
-    backward_flows[i-1]) if forward flows are given, else the warp's valid plane.  temporal_weight = 0: the warped start
+    backward_flows[i-1]) if forward flows are given, else the warp's valid plane.  With estimated backward flows and no
+    weights the forward flow is estimated too and c = flow_weights of the pair.  temporal_weight = 0: the warped start
     only.  ValueError before any GPU work for frames of differing sizes, a flow or weight list of the wrong length or shape,
-    weights outside [0,1], and a negative or non-finite temporal_weight.  (A job of this driver is never stripe-sharded;
+    weights outside [0,1], a negative or non-finite temporal_weight, bad flow parameters, and forward_flows beside
+    estimated backward flows (the pair would come from two estimators).  (A job of this driver is never stripe-sharded;
     PixelOptimizer.shard_stripes refuses an engine that carries an anchor.)"""
     frames = list(frames)
     if not frames:
@@ -96,13 +109,25 @@ async def neural_style_transfer_video(frames, style, backward_flows, forward_flo
         raise ValueError(f"temporal_weight must be finite and >= 0, got {temporal_weight!r}")
     n = len(frames) - 1
     h, w = result_size(shape, cfg.levels_num)
-    bwd = _check_planes("backward_flows", backward_flows, n, (h, w, 2))
+    estimate = backward_flows is None or isinstance(backward_flows, _flow.FlowParams)
+    if estimate:
+        params = _flow.normalize_flow(backward_flows)
+        if forward_flows is not None:
+            raise ValueError("forward_flows cannot be combined with estimated backward flows: give both, or neither")
+    bwd = None if estimate else _check_planes("backward_flows", backward_flows, n, (h, w, 2))
     fwd = _check_planes("forward_flows", forward_flows, n, (h, w, 2)) if forward_flows is not None else None
     wts = _check_planes("weights", weights, n, (h, w), 0.0, 1.0) if weights is not None else None
     extensions = _job.handed_on(cfg)
     luminance = extensions.get("preserve_color") == "luminance"
     levels = int(cfg.levels_num)
     previous = None
+
+    planes = {}       # frame index -> its luminance plane: frame i's is formed once and read again for frame i + 1
+
+    def plane(setup, j):
+        if j not in planes or planes[j].device != setup.device:
+            planes[j] = _luminance_plane(setup, frames[j], h, w)
+        return planes[j]
 
     for i, frame in enumerate(frames):
         start = None
@@ -114,13 +139,23 @@ async def neural_style_transfer_video(frames, style, backward_flows, forward_flo
                     raise ValueError(f"the job's top level is {tuple(top_shape)}, the flows are {(h, w)}")
                 dev = setup.device
                 src = torch.from_numpy(np.ascontiguousarray(prev, dtype=np.float32)).to(dev).permute(2, 0, 1).contiguous()
-                flow = _planar(bwd[k], dev)
+                forward = None      # (only the weight plane reads it)
+                if estimate:        # backward: frame i -> frame i - 1; forward: the other way
+                    here, there = plane(setup, k + 1), plane(setup, k)
+                    planes.pop(k, None)
+                    flow = setup.flow_estimate(here, there, params)
+                    if wts is None:
+                        forward = setup.flow_estimate(there, here, params)
+                else:
+                    flow = _planar(bwd[k], dev)
+                    if fwd is not None and wts is None:
+                        forward = _planar(fwd[k], dev)
                 warped, valid = setup.warp_bilinear(src, flow)
                 omega = warped.permute(1, 2, 0).contiguous()
                 if wts is not None:
                     c = torch.from_numpy(wts[k]).to(dev)
-                elif fwd is not None:
-                    c = setup.flow_weights(_planar(fwd[k], dev), flow)
+                elif forward is not None:
+                    c = setup.flow_weights(forward, flow)
                 else:
                     c = valid
                 return omega, level_anchors(setup, omega, levels, luminance), level_weights(c, levels), gamma

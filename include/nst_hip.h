@@ -43,6 +43,7 @@ extern "C" {
 #define NST_MAX_STYLES 8    /* style images one level's targets may blend (nst_level_set_targets_blend) */
 #define NST_MAX_REGIONS 4   /* regions of spatial control (nst_level_set_guidance) */
 #define NST_MAX_LAPLACIAN 4 /* entries (pool size, weight) of the Laplacian loss (nst_job_set_laplacian) */
+#define NST_MAX_FLOW_SCALES 12 /* pyramid scales of the flow estimator (nst_flow_estimate) */
 
 typedef struct nst_ctx nst_ctx;
 typedef struct nst_opt nst_opt;
@@ -787,6 +788,66 @@ int nst_anchor_geometry(int* blocks, int* block_elems);
 int nst_warp_bilinear(nst_ctx* ctx, const float* src, const float* flow, int C, int h, int w, float* out,
                       float* valid /* nullable */, void* stream);
 int nst_flow_weights(nst_ctx* ctx, const float* fwd, const float* bwd, int h, int w, float* out, void* stream);
+/* Optical flow for a sequence whose caller has none: multi-scale Horn-Schunck with warping - Horn & Schunck, "Determining
+ * Optical Flow" (1981) in the coarse-to-fine form of Meinhardt-Llopis, Sanchez & Kondermann, "Horn-Schunck Optical Flow with a
+ * Multi-Scale Strategy" (IPOL 2013).  A baseline estimator: flows from a better one are handed to the warp as before.
+ * Convention: estimate(from, to) gives w = (u, v) on the grid of `from` with from(p) ~ to(p + w(p)) - the convention of
+ *   nst_warp_bilinear, out(p) = src(p + flow(p)).  The backward flow of frame i is estimate(frame i, frame i-1), the forward
+ *   flow estimate(frame i-1, frame i).  Images are single planes (h,w), fp32, on the scale of nst_luminance (255 Y).  A flow
+ *   is (2,h,w): plane 0 = u (x), plane 1 = v (y), in pixels.
+ * Everything is fp32, every operation rounded once (no contraction), divisions correctly rounded; nothing is reduced and
+ * nothing is added atomically: the same bits on every run.  The stages, with their order of operations:
+ * reduce (nst_flow_reduce): (h,w) -> (hc,wc) = ((h+1)/2, (w+1)/2).  With k = (1, 4, 6, 4, 1)/16 (exact) and indices clamped to
+ *   the image: r(y', x) = sum_i k_i in(y', clamp(2x+i-2)) (the pass along a row first), out(y, x) = sum_j k_j r(clamp(2y+j-2), x);
+ *   each pass forms its five products and adds them in index order, ((((p0 + p1) + p2) + p3) + p4).
+ * prolong (nst_flow_prolong): coarse (2,hc,wc) -> fine (2,h,w), hc = (h+1)/2, wc = (w+1)/2.  Per axis a = i >> 1,
+ *   b = min(a + (i & 1), nc - 1); r(Y, x) = 0.5 (c(Y, a_x) + c(Y, b_x)) (along a row first), m = 0.5 (r(a_y, x) + r(b_y, x)),
+ *   out = 2 m: a displacement doubles with the grid.
+ * gradient: Bx = 0.5 (B(x+1) - B(x-1)), By likewise in y, B = `to` at the scale, replicated borders - the expression of the
+ *   motion-boundary test of nst_flow_weights.
+ * linearise (nst_flow_linearize) at the flow (u, v): the sample position of pixel p is p + (u, v)(p) by the position rule of
+ *   the warp (integer part and fraction of the flow alone; four taps; "inside" = the warp's valid).  Bw, Ix, Iy = the bilinear
+ *   samples of B, Bx, By in the warp's order of operations.  Inside: rho = ((Bw - Ix u) - Iy v) - A, A = `from`.  Elsewhere, and
+ *   where the flow is not finite: Ix = Iy = rho = 0 - such a pixel has no data term and only diffuses.
+ * sweep (nst_flow_sweeps): one Jacobi step, both new planes from the old ones.  With replicated borders
+ *   u~ = (((N + S) + W) + E) / 6 + (((NW + NE) + SW) + SE) / 12, v~ likewise;
+ *   t = ((rho + Ix u~) + Iy v~) / ((alpha^2 + Ix Ix) + Iy Iy), alpha^2 = the fp32 product alpha alpha;
+ *   u' = u~ - Ix t, v' = v~ - Iy t.
+ * driver (nst_flow_estimate): pyramids of both planes by reduce; scale s+1 exists while min(hc, wc) >= 8 for its size and
+ *   s+1 < scales (scales = 0: as many as fit, at most NST_MAX_FLOW_SCALES); the flow is zero at the coarsest scale; per
+ *   scale, `warps` times: linearise at the current flow, then `iterations` sweeps that start from it; then prolong to the
+ *   next finer scale.  alpha is the same at every scale.  IPOL's defaults: alpha = 15 (images in 0 ... 255), warps = 5,
+ *   iterations = 50 here, scales = 0.
+ *
+ * The CALLER supplies every buffer; the context allocates nothing and nst_ctx_bytes does not move.  All of these read no
+ * job state and are synchronous.
+ * nst_flow_workspace: pure (no context, no device).  floats = what nst_flow_estimate needs for (h, w, scales) (reduced
+ *   planes of both images, Ix, Iy, rho, a second flow buffer); scales_used by the rule above.  Either pointer may be NULL.
+ *   NST_E_ARG: h or w < 1, scales < 0 or > NST_MAX_FLOW_SCALES.
+ * nst_flow_estimate: from, to device (h,w); flow device (2,h,w), out; workspace device, workspace_floats floats.  NST_E_ARG,
+ *   with nothing launched and `flow` untouched: a workspace smaller than nst_flow_workspace says, a null pointer, h or w < 1,
+ *   alpha non-finite or <= 0, or whose fp32 square overflows or is subnormal (the sweep divides by it alone where a pixel has
+ *   no data term), warps < 1,
+ *   iterations < 1, scales < 0 or > NST_MAX_FLOW_SCALES; an output that overlaps another argument.
+ * nst_flow_reduce: in (h,w) -> out ((h+1)/2,(w+1)/2).  nst_flow_prolong: coarse (2,(h+1)/2,(w+1)/2) -> fine (2,h,w).
+ * nst_flow_linearize: from, to (h,w), flow (2,h,w) -> ix, iy, rho (h,w).
+ * nst_flow_sweeps: n >= 1 sweeps, one launch each, from flow_in (2,h,w, left as it is); the sweeps alternate between
+ *   flow_out and scratch (2,h,w each; scratch may be NULL for n = 1) so that the result is always in flow_out.  alpha as
+ *   for nst_flow_estimate.
+ * No stage runs in place (every kernel reads neighbouring pixels): an output that overlaps an input or another output is
+ *   NST_E_ARG for each of these entry points.
+ * 16-byte accesses of the sweep: a group of four pixels takes them where u', v', u, v, Ix, Iy and rho all lie on a 16-byte
+ *   boundary there.  The planes of a (2,h,w) flow are h w floats apart, so a flow whose h w is not a multiple of 4 (odd
+ *   pyramid scales among them) is swept with single floats throughout; the result is the same either way. */
+int nst_flow_workspace(int h, int w, int scales, size_t* floats, int* scales_used);
+int nst_flow_estimate(nst_ctx* ctx, const float* from, const float* to, int h, int w, float alpha, int scales, int warps,
+                      int iterations, float* flow /* out (2,h,w) */, float* workspace, size_t workspace_floats, void* stream);
+int nst_flow_reduce(nst_ctx* ctx, const float* in, int h, int w, float* out, void* stream);
+int nst_flow_prolong(nst_ctx* ctx, const float* coarse, int h, int w, float* fine, void* stream);
+int nst_flow_linearize(nst_ctx* ctx, const float* from, const float* to, const float* flow, int h, int w, float* ix, float* iy,
+                       float* rho, void* stream);
+int nst_flow_sweeps(nst_ctx* ctx, const float* ix, const float* iy, const float* rho, const float* flow_in, int h, int w,
+                    float alpha, int n, float* flow_out, float* scratch /* nullable for n = 1 */, void* stream);
 /* F.interpolate(x, size=(h//2,w//2), mode='bicubic') (neural_style_transfer.py:173-176) and its
  * transpose (autograd backward); x (C,h,w) -> y (C,h/2,w/2); gy -> gx (overwritten). */
 int nst_bicubic_half(nst_ctx* ctx, const float* x, int C, int h, int w, float* y, void* stream);
