@@ -96,6 +96,11 @@ SYMBOLS = {
     "nst_flow_linearize": (C.c_int, [c_void, c_void, c_void, c_void, C.c_int, C.c_int, c_void, c_void, c_void, c_void]),
     "nst_flow_sweeps": (C.c_int, [c_void, c_void, c_void, c_void, c_void, C.c_int, C.c_int, C.c_float, C.c_int, c_void, c_void,
                                   c_void]),
+    "nst_flow_tvl1_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
+    "nst_flow_tvl1_estimate": (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int,
+                                         C.c_int, c_void, c_void, C.c_size_t, c_void]),
+    "nst_flow_tvl1_iterations": (C.c_int, [c_void, c_void, c_void, c_void, c_void, c_void, C.c_int, C.c_int, C.c_float, C.c_float,
+                                           C.c_float, C.c_int, c_void, c_void, c_void, c_void]),
     "nst_job_set_gram_shift": (C.c_int, [c_void, c_float_p, C.c_uint]),
     "nst_job_gram_shift": (C.c_int, [c_void, c_float_p, C.POINTER(C.c_uint)]),
     "nst_level_gram_offsets": (C.c_int, [c_void, C.c_int, C.c_int, c_void, c_void]),

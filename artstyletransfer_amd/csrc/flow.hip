@@ -15,25 +15,11 @@
 
 #include <stdint.h>
 
+#include "nst_flow.h"
 #include "nst_kernels.h"
 #include "nst_sample.h"
 
 namespace nst {
-
-namespace {
-
-constexpr int FLOW_THREADS = 256;
-constexpr size_t FLOW_MAX_BLOCKS = 4096;      // grids are capped and strided (launch_warp_bilinear's rule)
-
-inline unsigned flow_blocks(size_t items) {
-    const size_t want = (items + FLOW_THREADS - 1) / FLOW_THREADS;
-    return (unsigned)(want < FLOW_MAX_BLOCKS ? (want < 1 ? 1 : want) : FLOW_MAX_BLOCKS);
-}
-inline size_t round4(size_t n) { return (n + 3) & ~(size_t)3; }      // workspace planes start on 16-byte boundaries
-
-__device__ __forceinline__ bool aligned16(const float* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-}  // namespace
 
 // ------------------------------------------------------------------ reduce: (h,w) -> ((h+1)/2, (w+1)/2)
 __global__ __launch_bounds__(FLOW_THREADS) void flow_reduce_kernel(const float* __restrict__ in, int h, int w, int hc, int wc,

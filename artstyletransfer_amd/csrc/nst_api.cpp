@@ -406,6 +406,69 @@ int nst_flow_sweeps(nst_ctx* ctx, const float* ix, const float* iy, const float*
     return NST_OK;
 }
 
+// ---- TV-L1 (include/nst_hip.h, nst_flow_tvl1_estimate; flow_tvl1.hip) on the same terms: the caller's buffers, synchronous.
+// lambda, theta, tau are finite and > 0 and the two constants of the iteration, lt = lambda theta and taut = tau / theta (the
+// fp32 product and quotient), normal numbers
+static bool flow_tvl1_ok(float lambda, float theta, float tau) {
+    const float lt = lambda * theta, taut = tau / theta;
+    return std::isfinite(lambda) && lambda > 0.f && std::isfinite(theta) && theta > 0.f && std::isfinite(tau) && tau > 0.f &&
+           std::isnormal(lt) && std::isnormal(taut);
+}
+static const char* const kFlowTvl1 = "lambda, theta and tau must be finite and > 0, and lambda theta and tau / theta normal fp32 numbers";
+
+int nst_flow_tvl1_workspace(int h, int w, int scales, size_t* floats, int* scales_used) {
+    FlowTvl1Layout t;
+    if (flow_tvl1_layout(h, w, scales, &t) != 0) return NST_E_ARG;
+    if (floats) *floats = t.floats;
+    if (scales_used) *scales_used = t.hs.scales;
+    return NST_OK;
+}
+
+int nst_flow_tvl1_estimate(nst_ctx* ctx, const float* from, const float* to, int h, int w, float lambda, float theta, float tau,
+                           int scales, int warps, int iterations, float* flow, float* workspace, size_t workspace_floats, void* stream) {
+    NSTCHK(bind(ctx));
+    if (!from || !to || !flow || !workspace) return fail(ctx, NST_E_ARG, "null argument");
+    if (h < 1 || w < 1) return fail(ctx, NST_E_ARG, "the images must be at least 1x1");
+    if (!flow_tvl1_ok(lambda, theta, tau)) return fail(ctx, NST_E_ARG, kFlowTvl1);
+    if (warps < 1 || iterations < 1) return fail(ctx, NST_E_ARG, "warps and iterations must be at least 1");
+    FlowTvl1Layout t;
+    if (flow_tvl1_layout(h, w, scales, &t) != 0) return fail(ctx, NST_E_ARG, "scales must lie in 0 .. NST_MAX_FLOW_SCALES");
+    if (workspace_floats < t.floats) return fail(ctx, NST_E_ARG, "the workspace is smaller than nst_flow_tvl1_workspace says");
+    const size_t hw = (size_t)h * w;
+    if (flow_overlap(from, hw, flow, 2 * hw) || flow_overlap(to, hw, flow, 2 * hw) || flow_overlap(workspace, t.floats, flow, 2 * hw) ||
+        flow_overlap(from, hw, workspace, t.floats) || flow_overlap(to, hw, workspace, t.floats))
+        return fail(ctx, NST_E_ARG, kFlowOverlap);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIPCHK(ctx, launch_flow_tvl1_estimate(from, to, t, lambda * theta, theta, tau / theta, warps, iterations, flow, workspace, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return NST_OK;
+}
+
+int nst_flow_tvl1_iterations(nst_ctx* ctx, const float* ix, const float* iy, const float* rho, const float* flow_in,
+                             const float* dual_in, int h, int w, float lambda, float theta, float tau, int n, float* flow_out,
+                             float* dual_out, float* scratch, void* stream) {
+    NSTCHK(bind(ctx));
+    if (!ix || !iy || !rho || !flow_in || !dual_in || !flow_out || !dual_out || (n > 1 && !scratch))
+        return fail(ctx, NST_E_ARG, "null argument");
+    if (h < 1 || w < 1 || n < 1) return fail(ctx, NST_E_ARG, "the planes must be at least 1x1 and n at least 1");
+    if (!flow_tvl1_ok(lambda, theta, tau)) return fail(ctx, NST_E_ARG, kFlowTvl1);
+    const size_t hw = (size_t)h * w;
+    const float* const outs[3] = {flow_out, dual_out, n > 1 ? scratch : nullptr};       // (scratch is not touched for n = 1)
+    const size_t sizes[3] = {2 * hw, 4 * hw, 6 * hw};
+    for (int i = 0; i < 3; ++i) {
+        if (flow_overlap(ix, hw, outs[i], sizes[i]) || flow_overlap(iy, hw, outs[i], sizes[i]) || flow_overlap(rho, hw, outs[i], sizes[i]) ||
+            flow_overlap(flow_in, 2 * hw, outs[i], sizes[i]) || flow_overlap(dual_in, 4 * hw, outs[i], sizes[i]))
+            return fail(ctx, NST_E_ARG, kFlowOverlap);
+        for (int j = 0; j < i; ++j)
+            if (flow_overlap(outs[j], sizes[j], outs[i], sizes[i])) return fail(ctx, NST_E_ARG, kFlowOverlap);
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIPCHK(ctx, launch_flow_tvl1_iterations(ix, iy, rho, flow_in, dual_in, h, w, lambda * theta, theta, tau / theta, n, flow_out, dual_out,
+                                            n > 1 ? scratch : nullptr, n > 1 ? scratch + 2 * hw : nullptr, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return NST_OK;
+}
+
 int nst_bicubic_half(nst_ctx* ctx, const float* x, int C, int h, int w, float* y, void* stream) {
     NSTCHK(bind(ctx));
     if (!x || !y || h < 2 || w < 2) return fail(ctx, NST_E_ARG, "bad argument");

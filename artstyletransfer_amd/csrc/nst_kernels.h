@@ -311,6 +311,25 @@ hipError_t launch_flow_sweeps(const float* Ix, const float* Iy, const float* rho
 hipError_t launch_flow_estimate(const float* from, const float* to, const FlowLayout& l, float alpha2, int warps, int iterations,
                                 float* flow, float* ws, hipStream_t stream);
 
+// flow_tvl1.hip: TV-L1 optical flow on the pyramid, warps and linearisation above (include/nst_hip.h, nst_flow_tvl1_estimate) ----
+// The workspace of one estimate: flow.hip's, then the two copies of the duals (4 h w floats each) the iterations alternate between.
+struct FlowTvl1Layout {
+    FlowLayout hs;
+    size_t dual[2];
+    size_t floats;                                              // the whole workspace
+};
+// 0, or -1 where flow_layout gives -1.  Pure.
+int flow_tvl1_layout(int h, int w, int scales, FlowTvl1Layout* out);
+// n iterations of the flow `fin` (2,h,w) and the duals `pin` (4,h,w), one launch each, alternating between (fout, pout) and
+// (ftmp, ptmp) so that the last writes (fout, pout); the tmp pair may be null for n = 1; the first iteration's target must not
+// be the input.  lt = lambda theta, taut = tau / theta.
+hipError_t launch_flow_tvl1_iterations(const float* Ix, const float* Iy, const float* rho, const float* fin, const float* pin, int h,
+                                       int w, float lt, float theta, float taut, int n, float* fout, float* pout, float* ftmp,
+                                       float* ptmp, hipStream_t stream);
+// the driver: pyramids, then per scale zero duals and `warps` x (linearise, `iterations` iterations), prolong; ends in `flow`
+hipError_t launch_flow_tvl1_estimate(const float* from, const float* to, const FlowTvl1Layout& t, float lt, float theta, float taut,
+                                     int warps, int iterations, float* flow, float* ws, hipStream_t stream);
+
 // loss assembly -----------------------------------------------------------------------------------
 struct LevelLossInputs {
     const double* content_partial;   // MSE_BLOCKS doubles

@@ -66,6 +66,14 @@ def flow_workspace(h: int, w: int, scales: int = 0) -> Tuple[int, int]:
     return floats.value, used.value
 
 
+def flow_tvl1_workspace(h: int, w: int, scales: int = 0) -> Tuple[int, int]:
+    """flow_workspace for nst_flow_tvl1_estimate (nst_flow_tvl1_workspace): that workspace plus two copies of the duals."""
+    floats, used = C.c_size_t(), C.c_int()
+    if _lib.load().nst_flow_tvl1_workspace(int(h), int(w), int(scales), C.byref(floats), C.byref(used)) != _lib.NST_OK:
+        raise ValueError(f"no TV-L1 flow workspace for {h}x{w} planes and scales={scales}")
+    return floats.value, used.value
+
+
 class StyleEngine:
     """One nst_ctx: VGG19 weights on one GPU + the pyramid workspace of one job."""
 
@@ -942,14 +950,21 @@ class StyleEngine:
     # ---- the flow estimator (nst_flow_estimate in include/nst_hip.h has the definitions); every buffer is torch's
     def flow_estimate(self, from_plane: torch.Tensor, to_plane: torch.Tensor, params=None) -> torch.Tensor:
         """The (2,h,w) flow w = (u, v) with from(p) ~ to(p + w(p)) of two (h,w) planes on the 0 ... 255 scale of luminance()
-        (nst_flow_estimate): multi-scale Horn-Schunck with warping.  `params`: a flow_modes.FlowParams (None: the defaults)."""
-        p = _flow.normalize_flow(params)
+        (nst_flow_estimate): multi-scale Horn-Schunck with warping.  `params`: a flow_modes.FlowParams (None: the defaults) -
+        or a flow_modes.TVL1Params: TV-L1 on the same pyramid (nst_flow_tvl1_estimate), sharp at motion boundaries."""
+        tvl1 = isinstance(params, _flow.TVL1Params)
+        p = _flow.normalize_tvl1(params) if tvl1 else _flow.normalize_flow(params)
         _chk_dev(from_plane, self.device)
         h, w = from_plane.shape
         _chk_dev(to_plane, self.device, (h, w))
-        floats, _ = flow_workspace(h, w, p.scales)
+        floats, _ = (flow_tvl1_workspace if tvl1 else flow_workspace)(h, w, p.scales)
         work = torch.empty(floats, dtype=torch.float32, device=self.device)
         out = torch.empty((2, h, w), dtype=torch.float32, device=self.device)
+        if tvl1:
+            _lib.check(self.ctx, self.lib.nst_flow_tvl1_estimate(self.ctx, _ptr(from_plane), _ptr(to_plane), h, w, p.lambda_, p.theta,
+                                                                 p.tau, p.scales, p.warps, p.iterations, _ptr(out), _ptr(work), floats,
+                                                                 _stream(self.device)), "nst_flow_tvl1_estimate")
+            return out
         _lib.check(self.ctx, self.lib.nst_flow_estimate(self.ctx, _ptr(from_plane), _ptr(to_plane), h, w, p.alpha, p.scales, p.warps,
                                                         p.iterations, _ptr(out), _ptr(work), floats, _stream(self.device)),
                    "nst_flow_estimate")
@@ -994,6 +1009,24 @@ class StyleEngine:
         _lib.check(self.ctx, self.lib.nst_flow_sweeps(self.ctx, _ptr(ix), _ptr(iy), _ptr(rho), _ptr(flow), h, w, float(alpha), int(n),
                                                       _ptr(out), _ptr(scratch), _stream(self.device)), "nst_flow_sweeps")
         return out
+
+    def flow_tvl1_iterations(self, ix: torch.Tensor, iy: torch.Tensor, rho: torch.Tensor, flow: torch.Tensor, dual: torch.Tensor,
+                             lambda_: float, theta: float, tau: float, n: int):
+        """(flow (2,h,w), duals (4,h,w)) after n TV-L1 iterations from `flow` and `dual` (p11, p12, p21, p22) under the
+        linearisation (ix, iy, rho) (nst_flow_tvl1_iterations)."""
+        _chk_dev(flow, self.device)
+        _, h, w = flow.shape
+        _chk_dev(flow, self.device, (2, h, w))
+        _chk_dev(dual, self.device, (4, h, w))
+        for t in (ix, iy, rho):
+            _chk_dev(t, self.device, (h, w))
+        out, dual_out = torch.empty_like(flow), torch.empty_like(dual)
+        scratch = torch.empty((6, h, w), dtype=torch.float32, device=self.device) if int(n) > 1 else None
+        _lib.check(self.ctx, self.lib.nst_flow_tvl1_iterations(self.ctx, _ptr(ix), _ptr(iy), _ptr(rho), _ptr(flow), _ptr(dual), h, w,
+                                                               float(lambda_), float(theta), float(tau), int(n), _ptr(out),
+                                                               _ptr(dual_out), _ptr(scratch), _stream(self.device)),
+                   "nst_flow_tvl1_iterations")
+        return out, dual_out
 
     def bicubic_half(self, x: torch.Tensor) -> torch.Tensor:
         _chk_dev(x, self.device)

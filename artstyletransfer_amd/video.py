@@ -4,7 +4,8 @@ flow and is held to it by a per-pixel weighted pixel-space term whose weight is 
 (nst_level_set_anchor, nst_warp_bilinear and nst_flow_weights in include/nst_hip.h have the definitions).  The flows are
 the caller's, from whatever estimator they trust - or, when none are given, estimated on the device between the luminance
 planes of consecutive frames by multi-scale Horn-Schunck with warping (nst_flow_estimate; flow_modes.FlowParams): a
-baseline that makes the path usable with this project alone, not a replacement for a better estimator.
+baseline that makes the path usable with this project alone, not a replacement for a better estimator - or, handed a
+flow_modes.TVL1Params, by TV-L1 on the same pyramid (nst_flow_tvl1_estimate), whose flows stay sharp at motion boundaries.
 
 The anchor is data of one job, like its content levels - not one of job_settings.SETTINGS: it reaches the job through
 NeuralStyleTransfer.set_anchor once the job exists.  Everything here raises ValueError before any GPU work."""
@@ -84,8 +85,9 @@ async def neural_style_transfer_video(frames, style, backward_flows=None, forwar
     and the job settings job_settings.handed_on(cfg) gives are used exactly as Task uses them.
     Frame 0 is neural_style_transfer() of (frames[0], style).  Frame i > 0 starts from omega, the last image of frame i - 1
     warped by backward_flows[i-1] - an (h,w,2) array (dx, dy) in pixels from frame i to frame i - 1, at the size of the
-    yielded images (result_size); backward_flows None or a flow_modes.FlowParams: estimated on the device
-    (StyleEngine.flow_estimate, with the defaults or these parameters) from the luminance plane of frame i to that of frame
+    yielded images (result_size); backward_flows None, a flow_modes.FlowParams or a flow_modes.TVL1Params: estimated on the
+    device (StyleEngine.flow_estimate: Horn-Schunck with the defaults or these parameters, or - a TVL1Params - TV-L1, which
+    keeps the flow sharp around moving objects) from the luminance plane of frame i to that of frame
     i - 1, both resized to the yielded size - and its every level carries the anchor made from omega with weight `temporal_weight`
     (no default: its useful magnitude is a matter of the content, style and TV weights; DESIGN.md 4.12 has measurements) under
     the weight plane c = weights[i-1] if given ((h,w) in [0,1]), else StyleEngine.flow_weights(forward_flows[i-1],
@@ -109,9 +111,10 @@ async def neural_style_transfer_video(frames, style, backward_flows=None, forwar
         raise ValueError(f"temporal_weight must be finite and >= 0, got {temporal_weight!r}")
     n = len(frames) - 1
     h, w = result_size(shape, cfg.levels_num)
-    estimate = backward_flows is None or isinstance(backward_flows, _flow.FlowParams)
+    tvl1 = isinstance(backward_flows, _flow.TVL1Params)
+    estimate = backward_flows is None or tvl1 or isinstance(backward_flows, _flow.FlowParams)
     if estimate:
-        params = _flow.normalize_flow(backward_flows)
+        params = _flow.normalize_tvl1(backward_flows) if tvl1 else _flow.normalize_flow(backward_flows)
         if forward_flows is not None:
             raise ValueError("forward_flows cannot be combined with estimated backward flows: give both, or neither")
     bwd = None if estimate else _check_planes("backward_flows", backward_flows, n, (h, w, 2))

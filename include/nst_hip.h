@@ -848,6 +848,49 @@ int nst_flow_linearize(nst_ctx* ctx, const float* from, const float* to, const f
                        float* rho, void* stream);
 int nst_flow_sweeps(nst_ctx* ctx, const float* ix, const float* iy, const float* rho, const float* flow_in, int h, int w,
                     float alpha, int n, float* flow_out, float* scratch /* nullable for n = 1 */, void* stream);
+/* TV-L1 optical flow in its dual form - Zach, Pock & Bischof, "A Duality Based Approach for Realtime TV-L1 Optical Flow"
+ * (DAGM 2007) as Sanchez, Meinhardt-Llopis & Facciolo state it, "TV-L1 Optical Flow Estimation" (IPOL 2013) - for flows that
+ * stay sharp at motion boundaries, where the quadratic smoothness term of nst_flow_estimate blurs them.  The convention, the
+ * planes, the pyramid (reduce, prolong, the scale rule min(hc, wc) >= 8 and NST_MAX_FLOW_SCALES, the zero flow at the coarsest
+ * scale) and the linearisation are nst_flow_estimate's, unchanged: Ix, Iy, rho of nst_flow_linearize - rho is TV-L1's constant
+ * part rho_c - with the inside flag and the non-finite rule (no data term: Ix = Iy = rho_c = 0).  There is no stopping test
+ * and no median filter: either makes the result discontinuous in its inputs or dependent on the run.
+ * Parameters: lambda (data weight, default 0.15), theta (coupling, 0.3), tau (dual step, 0.25), scales (0), warps (5),
+ *   iterations (50).  Constants, fp32: lt = lambda theta, taut = tau / theta.
+ * Per scale: the duals p11, p12 (of u) and p21, p22 (of v) start at zero and are kept across the warps of the scale; then
+ *   `warps` times: linearise at the current flow, then `iterations` iterations; then prolong the flow to the next finer scale.
+ * One iteration (nst_flow_tvl1_iterations), fp32, every written operation rounded once (no contraction), division and square
+ *   root correctly rounded; g2 = Ix Ix + Iy Iy:
+ *     r = (rho_c + Ix u) + Iy v;  b = lt g2
+ *     k = lt if r < -b;  k = -lt if r > b;  otherwise k = (-r) / g2 if g2 >= 1e-10f, else k = 0
+ *     v1 = u + k Ix,  v2 = v + k Iy
+ *     u' = v1 + theta (dx(p11) + dy(p12)),  v' = v2 + theta (dx(p21) + dy(p22)), with the backward differences
+ *       dx(p)(x) = p(x) - p(x-1), dy likewise along y, where p(-1) = 0 and the last column of p11, p21 and the last row of
+ *       p12, p22 are READ AS 0 (they stay exactly 0 from a zero start; the stage reads them as 0 whatever the caller passed)
+ *     ux = u'(x+1) - u'(x) (0 in the last column), uy = u'(y+1) - u'(y) (0 in the last row); vx, vy likewise
+ *     n1 = 1 + taut sqrt(ux ux + uy uy);  p11' = (p11 + taut ux) / n1,  p12' = (p12 + taut uy) / n1 (p11, p12 as read above)
+ *     n2 = 1 + taut sqrt(vx vx + vy vy);  p21' = (p21 + taut vx) / n2,  p22' = (p22 + taut vy) / n2
+ *   The flow of the next iteration is (u', v').  Nothing is reduced and nothing is added atomically: the same bits on every run.
+ * The CALLER supplies every buffer; the context allocates nothing and nst_ctx_bytes does not move.  Synchronous, no job state.
+ * nst_flow_tvl1_workspace: pure.  floats = what nst_flow_tvl1_estimate needs: what nst_flow_workspace counts plus two copies
+ *   of the duals, 4 h w floats each (an iteration is one launch that writes a second copy of the flow and of the duals).
+ *   Either pointer may be NULL.  NST_E_ARG: h or w < 1, scales < 0 or > NST_MAX_FLOW_SCALES.
+ * nst_flow_tvl1_estimate: from, to device (h,w); flow device (2,h,w), out; workspace device, workspace_floats floats.
+ * nst_flow_tvl1_iterations: n >= 1 iterations from flow_in (2,h,w) and dual_in (4,h,w: p11, p12, p21, p22), both left as they
+ *   are, under the linearisation ix, iy, rho (h,w); the result in flow_out (2,h,w) and dual_out (4,h,w); scratch: 6 h w floats
+ *   the iterations alternate with, not touched (and may be NULL) for n = 1.
+ * NST_E_ARG for both, with nothing launched and the outputs untouched: a workspace smaller than nst_flow_tvl1_workspace says;
+ *   a null pointer; h or w < 1; lambda, theta or tau non-finite or <= 0; lt or taut not a normal fp32 number; warps,
+ *   iterations or n < 1; scales < 0 or > NST_MAX_FLOW_SCALES; an output that overlaps another argument.
+ * 16-byte accesses: as the sweep's, over the fifteen planes of an iteration; the planes of the duals too are h w floats
+ *   apart, so with h w % 4 != 0 an iteration takes single floats throughout; the result is the same either way. */
+int nst_flow_tvl1_workspace(int h, int w, int scales, size_t* floats, int* scales_used);
+int nst_flow_tvl1_estimate(nst_ctx* ctx, const float* from, const float* to, int h, int w, float lambda, float theta, float tau,
+                           int scales, int warps, int iterations, float* flow /* out (2,h,w) */, float* workspace,
+                           size_t workspace_floats, void* stream);
+int nst_flow_tvl1_iterations(nst_ctx* ctx, const float* ix, const float* iy, const float* rho, const float* flow_in,
+                             const float* dual_in, int h, int w, float lambda, float theta, float tau, int n, float* flow_out,
+                             float* dual_out, float* scratch /* nullable for n = 1 */, void* stream);
 /* F.interpolate(x, size=(h//2,w//2), mode='bicubic') (neural_style_transfer.py:173-176) and its
  * transpose (autograd backward); x (C,h,w) -> y (C,h/2,w/2); gy -> gx (overwritten). */
 int nst_bicubic_half(nst_ctx* ctx, const float* x, int C, int h, int w, float* y, void* stream);

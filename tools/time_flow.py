@@ -4,7 +4,10 @@ stage's share, from the stage entry points run scale by scale as the driver runs
 device synchronise, so a host clock around it measures the kernels plus one synchronise; the sweeps are timed `iterations`
 at a call, as the driver launches them).  The frame pair is a synthetic image and itself moved by (3, 1) pixels.
     python tools/time_flow.py [reps=5] [out=profiles/r17_flow.txt]
-The figures replace the section between the two marker lines of `out` (the rest of the file is kept)."""
+The figures replace the section between the two marker lines of `out` (the rest of the file is kept).
+    python tools/time_flow.py [reps=5] [out=profiles/r18_flow_tvl1.txt] tvl1
+times TV-L1 instead (flow_modes.TVL1Params at the defaults; an iteration moves fifteen planes in one launch), beside
+Horn-Schunck in the same run, and the iterations of the top scale from their stage entry point."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -14,7 +17,9 @@ from artstyletransfer_amd.engine import StyleEngine, flow_workspace
 from artstyletransfer_amd.flow_modes import FlowParams
 
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 5
-out_path = sys.argv[2] if len(sys.argv) > 2 else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "r17_flow.txt")
+TVL1 = len(sys.argv) > 3 and sys.argv[3] == "tvl1"
+out_path = sys.argv[2] if len(sys.argv) > 2 else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                                            "r18_flow_tvl1.txt" if TVL1 else "r17_flow.txt")
 BEGIN, END = "== timing (tools/time_flow.py) ==", "== end of timing =="
 HBM = 6.3e12          # achievable bytes per second of the MI355X's HBM: the yardstick of the estimate from bytes
 P = FlowParams()
@@ -36,10 +41,48 @@ def clock(f, n=1):
     return (time.perf_counter() - t) / n, r
 
 
+def time_tvl1(h, w, planes):
+    """One TV-L1 flow beside one Horn-Schunck flow, and the iterations of the top scale."""
+    from artstyletransfer_amd.engine import flow_tvl1_workspace
+    from artstyletransfer_amd.flow_modes import TVL1Params
+    T = TVL1Params()
+    floats, scales = flow_tvl1_workspace(h, w, T.scales)
+    sizes = [(h, w)]
+    for _ in range(1, scales):
+        sizes.append(((sizes[-1][0] + 1) // 2, (sizes[-1][1] + 1) // 2))
+    px = sum(a * b for a, b in sizes)
+    it_bytes = 4 * 15 * px * T.warps * T.iterations
+    launches = 2 * (scales - 1) + 1 + scales + scales * T.warps * (1 + T.iterations) + (scales - 1)
+    say(f"{h}x{w} TV-L1: {scales} scales, workspace {4 * floats / 1e6:.1f} MB; {T.warps * T.iterations} iterations per scale, {launches} launches; "
+        f"bytes of the iterations {it_bytes / 1e9:.2f} GB = {1e3 * it_bytes / HBM:.2f} ms at {HBM / 1e12:.1f} TB/s (the fifteen planes of the top "
+        f"scale are {4 * 15 * h * w / 1e6:.0f} MB: they fit the 256 MiB Infinity Cache)")
+    for name, par in (("Horn-Schunck", None), ("TV-L1", T)):
+        clock(lambda: eng.flow_estimate(planes[0], planes[1], par), 2)                     # warm-up
+        runs = [clock(lambda: eng.flow_estimate(planes[0], planes[1], par))[0] for _ in range(reps)]
+        flow = eng.flow_estimate(planes[0], planes[1], par)
+        inner = flow[:, h // 8: -h // 8, w // 8: -w // 8]
+        say(f"{h}x{w} {name}: one flow {1e3 * np.mean(runs):.2f} ms (mean of {reps}; min {1e3 * min(runs):.2f}, max {1e3 * max(runs):.2f}); "
+            f"inner mean flow ({float(inner[0].mean()):.3f}, {float(inner[1].mean()):.3f}) px for a true (3, 1)")
+    f = eng.flow_estimate(planes[0], planes[1], T)
+    ix, iy, rho = eng.flow_linearize(planes[0], planes[1], f)
+    dual = torch.zeros((4, h, w), dtype=torch.float32, device="cuda")
+    eng.flow_tvl1_iterations(ix, iy, rho, f, dual, T.lambda_, T.theta, T.tau, T.iterations)
+    dt, _ = clock(lambda: eng.flow_tvl1_iterations(ix, iy, rho, f, dual, T.lambda_, T.theta, T.tau, T.iterations), reps)
+    say(f"{h}x{w} TV-L1: a top-scale iteration {1e6 * dt / T.iterations:.1f} us ({T.iterations} at a call, one synchronise) = "
+        f"{4 * 15 * h * w / (dt / T.iterations) / 1e12:.2f} TB/s over its fifteen planes")
+    small = [torch.zeros(k + sizes[-1], dtype=torch.float32, device="cuda") for k in ((), (), (), (2,), (4,))]
+    eng.flow_tvl1_iterations(*small, T.lambda_, T.theta, T.tau, T.iterations)
+    dt, _ = clock(lambda: eng.flow_tvl1_iterations(*small, T.lambda_, T.theta, T.tau, T.iterations), reps)
+    say(f"{h}x{w} TV-L1: an iteration of the coarsest scale {sizes[-1]} {1e6 * dt / T.iterations:.1f} us: what a launch costs")
+
+
 for h, w in ((1024, 1536), (512, 768)):
     img = synthetic.image(h, w, seed=1)
     planes = [eng.luminance(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()).reshape(h, w)
               for a in (img, np.roll(img, (1, 3), axis=(0, 1)))]
+    if TVL1:
+        time_tvl1(h, w, planes)
+        continue
     floats, scales = flow_workspace(h, w, P.scales)
     sizes = [(h, w)]
     for _ in range(1, scales):
