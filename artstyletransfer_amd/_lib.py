@@ -29,6 +29,7 @@ NST_POOL_MAX = 0
 NST_POOL_AVG = 1
 NST_MAX_LAPLACIAN = 4
 NST_MAX_FLOW_SCALES = 12
+NST_MAX_ANCHOR_SOURCES = 8
 
 c_float_p = C.POINTER(C.c_float)
 REDUCE_HOOK = C.CFUNCTYPE(None, C.c_void_p)
@@ -88,6 +89,8 @@ SYMBOLS = {
     "nst_anchor_geometry": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "nst_warp_bilinear": (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, c_void, c_void]),
     "nst_flow_weights": (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, c_void, c_void]),
+    "nst_anchor_fold": (C.c_int, [c_void, C.c_int, C.POINTER(c_void), C.POINTER(c_void), C.c_int, C.c_int, C.c_int, c_void, c_void,
+                                  c_void, c_void]),
     "nst_flow_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     "nst_flow_estimate": (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, c_void, c_void,
                                     C.c_size_t, c_void]),

@@ -303,15 +303,44 @@ int nst_flow_weights(nst_ctx* ctx, const float* fwd, const float* bwd, int h, in
     return NST_OK;
 }
 
-// ---- the flow estimator (include/nst_hip.h, nst_flow_estimate; flow.hip).  The caller owns every buffer: the context
-// allocates nothing here, so nst_ctx_bytes does not move.  All synchronous.
-static_assert(NST_FLOW_MAX_SCALES == NST_MAX_FLOW_SCALES, "nst_kernels.h and include/nst_hip.h disagree about the scale cap");
-
-// an output of `nb` floats that shares memory with `na` floats another argument names (the kernels read neighbours: none runs in place)
+// `na` floats at a and `nb` floats at b share memory (either null: no)
 static bool flow_overlap(const float* a, size_t na, const float* b, size_t nb) {
     const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
     return a && b && a0 < b0 + nb * sizeof(float) && b0 < a0 + na * sizeof(float);
 }
+
+// The long-term anchor (include/nst_hip.h): J warped results under J reliability planes -> the one anchor and weight plane a
+// level holds.  One launch; the pointers travel as a kernel argument; nothing is allocated.  Asynchronous on `stream`.
+static_assert(NST_FOLD_MAX_SOURCES == NST_MAX_ANCHOR_SOURCES, "nst_kernels.h and include/nst_hip.h disagree about the source cap");
+int nst_anchor_fold(nst_ctx* ctx, int J, const float* const* sources, const float* const* weights, int C, int h, int w, float* anchor,
+                    float* weight, float* parts, void* stream) {
+    NSTCHK(bind(ctx));
+    if (J < 1 || J > NST_MAX_ANCHOR_SOURCES) return fail(ctx, NST_E_ARG, "J must lie in 1 .. NST_MAX_ANCHOR_SOURCES");
+    if (C != 1 && C != 3) return fail(ctx, NST_E_ARG, "C must be 3, or 1 for a luminance plane");
+    if (h < 1 || w < 1) return fail(ctx, NST_E_ARG, "the image must be at least 1x1");
+    if (!sources || !weights || !anchor || !weight) return fail(ctx, NST_E_ARG, "null argument");
+    const size_t hw = (size_t)h * w, chw = (size_t)C * hw;
+    AnchorFoldArgs a{};
+    for (int j = 0; j < J; ++j) {
+        if (!sources[j] || !weights[j]) return fail(ctx, NST_E_ARG, "null source or weight plane");
+        a.sources[j] = sources[j];
+        a.weights[j] = weights[j];
+    }
+    const float* const outs[3] = {anchor, weight, parts};
+    const size_t out_n[3] = {chw, hw, (size_t)J * hw};
+    bool clash = flow_overlap(anchor, chw, weight, hw) || flow_overlap(anchor, chw, parts, out_n[2]) || flow_overlap(weight, hw, parts, out_n[2]);
+    for (int o = 0; o < 3 && !clash; ++o)
+        for (int j = 0; j < J && !clash; ++j)
+            clash = flow_overlap(sources[j], chw, outs[o], out_n[o]) || flow_overlap(weights[j], hw, outs[o], out_n[o]);
+    if (clash) return fail(ctx, NST_E_ARG, "an output overlaps an input or another output: the fold does not run in place");
+    HIPCHK(ctx, launch_anchor_fold(a, J, C, h, w, anchor, weight, parts, static_cast<hipStream_t>(stream)));
+    return NST_OK;
+}
+
+// ---- the flow estimator (include/nst_hip.h, nst_flow_estimate; flow.hip).  The caller owns every buffer: the context
+// allocates nothing here, so nst_ctx_bytes does not move.  All synchronous.
+static_assert(NST_FLOW_MAX_SCALES == NST_MAX_FLOW_SCALES, "nst_kernels.h and include/nst_hip.h disagree about the scale cap");
+
 // alpha is finite and > 0 and its fp32 square, the smoothness weight the sweep divides by, a normal number (a square that
 // underflows leaves a pixel without a data term with 0 / 0)
 static bool flow_alpha_ok(float alpha) {

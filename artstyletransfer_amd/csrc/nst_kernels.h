@@ -282,6 +282,19 @@ hipError_t launch_warp_bilinear(const float* src, const float* flow, int C, int 
                                 hipStream_t stream);
 // out (h,w) = the reliability plane c of a forward / backward flow pair
 hipError_t launch_flow_weights(const float* fwd, const float* bwd, int h, int w, float* out, hipStream_t stream);
+// the long-term anchor: J sources (C,h,w) under J weight planes (h,w), in ascending order of frame offset -> anchor (C,h,w),
+// weight (h,w) and, if asked for, the parts l_j (J,h,w).  The 2 J pointers travel by value as one kernel argument.
+constexpr int NST_FOLD_MAX_SOURCES = 8;   // = NST_MAX_ANCHOR_SOURCES
+struct AnchorFoldArgs {
+    const float* sources[NST_FOLD_MAX_SOURCES];
+    const float* weights[NST_FOLD_MAX_SOURCES];
+};
+hipError_t launch_anchor_fold(const AnchorFoldArgs& a, int J, int C, int h, int w, float* anchor, float* weight,
+                              float* parts /* nullable */, hipStream_t stream);
+// which planes take 16-byte accesses: bits 0..2 plane ch of every source and of the anchor, bit 3 the weight planes in and
+// out, bit 8 + j plane j of parts
+unsigned anchor_fold_vec_mask(const AnchorFoldArgs& a, int J, int C, size_t hw, const float* anchor, const float* weight,
+                              const float* parts);
 
 // flow.hip: multi-scale Horn-Schunck optical flow with warping (include/nst_hip.h, nst_flow_estimate, has the definitions) ----
 constexpr int NST_FLOW_MAX_SCALES = 12;   // = NST_MAX_FLOW_SCALES

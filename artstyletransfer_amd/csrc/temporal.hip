@@ -7,6 +7,7 @@
 //   anchor_value_kernel    the block partials -> tmp (the standalone entry point; the loss rows read the partials)
 //   warp_kernel            out = bilinear(src, p + flow(p)), valid = the four taps lie inside the image
 //   flow_weights_kernel    c = 0 at disocclusions, motion boundaries and samples off the image, 1 elsewhere
+//   anchor_fold_kernel     several warped results under their weight planes -> the one anchor and weight plane of a level
 // Streaming kernels: 16 bytes per lane where a plane's offset keeps every operand on a 16-byte boundary, scalar loads on
 // such a plane's last h w % 4 pixels and on the planes that are not.  The grid of the anchor kernels is fixed, every thread
 // adds its share in index order, and the block tree is the one of pixel_ops.hip: no float atomics, the same bits every run.
@@ -227,6 +228,142 @@ hipError_t launch_flow_weights(const float* fwd, const float* bwd, int h, int w,
     const size_t hw = (size_t)h * w;
     const size_t want = (hw + 255) / 256;
     hipLaunchKernelGGL(flow_weights_kernel, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, stream, fwd, bwd, h, w, out);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ anchor fold (the long-term anchor)
+// J warped results under J reliability planes -> the ONE anchor and weight plane a level holds (include/nst_hip.h,
+// nst_anchor_fold).  A lane owns four consecutive pixels: the weights give l_j, Wsum and the live set once, then channel by
+// channel the sources are mixed.  Every plane is read or written 16 bytes at a time where its bit of the mask is set and the
+// lane's four pixels exist, pixel by pixel otherwise.  A source none of the lane's pixels takes is not loaded; one that a
+// neighbour takes is loaded and dropped by a select, never by a product - its non-finite values do not leak.
+namespace {
+
+constexpr int FOLD_THREADS = 256;
+constexpr unsigned FOLD_VEC_WEIGHTS = 1u << 3;     // bits 0..2: plane ch of every source and of the anchor
+constexpr unsigned FOLD_VEC_PARTS = 1u << 8;       // bit 8 + j: plane j of parts
+
+__device__ __forceinline__ void fold_load4(const float* __restrict__ p, size_t at, bool vec, int n, float v[4]) {
+    if (vec) {
+        const float4 t = *reinterpret_cast<const float4*>(p + at);
+        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = k < n ? p[at + k] : 0.f;
+    }
+}
+__device__ __forceinline__ void fold_store4(float* __restrict__ p, size_t at, bool vec, int n, const float v[4]) {
+    if (vec) {
+        *reinterpret_cast<float4*>(p + at) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (k < n) p[at + k] = v[k];
+    }
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(FOLD_THREADS) void anchor_fold_kernel(const AnchorFoldArgs a, int J, int C, size_t hw, unsigned vec_mask,
+                                                                   float* __restrict__ anchor, float* __restrict__ weight,
+                                                                   float* __restrict__ parts) {
+#pragma clang fp contract(off)
+    const size_t nq = (hw + 3) / 4;
+    for (size_t q = (size_t)blockIdx.x * FOLD_THREADS + threadIdx.x; q < nq; q += (size_t)gridDim.x * FOLD_THREADS) {
+        const size_t at = q * 4;
+        const int n = hw - at >= 4 ? 4 : (int)(hw - at);
+        const bool full = n == 4;
+        // r[j][k]: l_j of pixel k, then l_j / Wsum; live bit 4 j + k: l_j > 0
+        float r[NST_FOLD_MAX_SOURCES][4], s[4] = {0.f, 0.f, 0.f, 0.f}, wsum[4] = {0.f, 0.f, 0.f, 0.f};
+        unsigned live = 0;
+#pragma unroll
+        for (int j = 0; j < NST_FOLD_MAX_SOURCES; ++j) {
+            if (j < J) {
+                float wv[4];
+                fold_load4(a.weights[j], at, full && (vec_mask & FOLD_VEC_WEIGHTS), n, wv);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float c = wv[k] > 0.f ? fminf(wv[k], 1.f) : 0.f;      // NaN, negative: 0
+                    const float l = fmaxf(c - s[k], 0.f);
+                    s[k] = s[k] + c;
+                    wsum[k] = j == 0 ? l : wsum[k] + l;
+                    r[j][k] = l;
+                    if (l > 0.f) live |= 1u << (4 * j + k);
+                }
+                if (parts) fold_store4(parts + (size_t)j * hw, at, full && ((vec_mask >> j) & FOLD_VEC_PARTS), n, r[j]);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) r[j][k] = 0.f;
+            }
+        }
+        unsigned none = 0;                  // bit k: no source is live at pixel k
+        {
+            float wo[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (!(wsum[k] > 0.f)) none |= 1u << k;
+                wo[k] = fminf(wsum[k], 1.f);
+            }
+            fold_store4(weight, at, full && (vec_mask & FOLD_VEC_WEIGHTS), n, wo);
+        }
+#pragma unroll
+        for (int j = 1; j < NST_FOLD_MAX_SOURCES; ++j)      // (source 0, where live, is the base: its ratio is never read)
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if ((live >> (4 * j + k)) & 1u) r[j][k] = r[j][k] / wsum[k];
+        for (int ch = 0; ch < C; ++ch) {
+            const bool vec = full && ((vec_mask >> ch) & 1u);
+            const size_t o = (size_t)ch * hw + at;
+            float base[4] = {0.f, 0.f, 0.f, 0.f}, acc[4] = {0.f, 0.f, 0.f, 0.f};
+            unsigned have = 0;          // bit k: pixel k has its base, the first live source (source 0 where none is)
+#pragma unroll
+            for (int j = 0; j < NST_FOLD_MAX_SOURCES; ++j) {
+                const unsigned lj = ((live >> (4 * j)) & 15u) | (j == 0 ? none : 0u);
+                if (j < J && lj) {
+                    float v[4];
+                    fold_load4(a.sources[j], o, vec, n, v);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const bool on = (lj >> k) & 1u, first = !((have >> k) & 1u);
+                        const float next = acc[k] + r[j][k] * (v[k] - base[k]);
+                        if (on && first) base[k] = v[k];
+                        acc[k] = on ? (first ? v[k] : next) : acc[k];
+                    }
+                    have |= lj;
+                }
+            }
+            fold_store4(anchor, o, vec, n, acc);
+        }
+    }
+}
+
+unsigned anchor_fold_vec_mask(const AnchorFoldArgs& a, int J, int C, size_t hw, const float* anchor, const float* weight,
+                              const float* parts) {
+    unsigned m = 0;
+    bool wv = aligned16(weight);
+    for (int j = 0; j < J; ++j) wv = wv && aligned16(a.weights[j]);
+    if (wv) m |= FOLD_VEC_WEIGHTS;
+    for (int ch = 0; ch < C; ++ch) {
+        const size_t o = (size_t)ch * hw;
+        bool v = aligned16(anchor + o);
+        for (int j = 0; j < J; ++j) v = v && aligned16(a.sources[j] + o);
+        if (v) m |= 1u << ch;
+    }
+    if (parts)
+        for (int j = 0; j < J; ++j)
+            if (aligned16(parts + (size_t)j * hw)) m |= FOLD_VEC_PARTS << j;
+    return m;
+}
+
+hipError_t launch_anchor_fold(const AnchorFoldArgs& a, int J, int C, int h, int w, float* anchor, float* weight, float* parts,
+                              hipStream_t stream) {
+    if (J < 1 || J > NST_FOLD_MAX_SOURCES || (C != 1 && C != 3) || h < 1 || w < 1 || !anchor || !weight) return hipErrorInvalidValue;
+    for (int j = 0; j < J; ++j)
+        if (!a.sources[j] || !a.weights[j]) return hipErrorInvalidValue;
+    const size_t hw = (size_t)h * w;
+    const size_t want = ((hw + 3) / 4 + FOLD_THREADS - 1) / FOLD_THREADS;
+    hipLaunchKernelGGL(anchor_fold_kernel, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(FOLD_THREADS), 0, stream, a, J, C, hw,
+                       anchor_fold_vec_mask(a, J, C, hw, anchor, weight, parts), anchor, weight, parts);
     return hipGetLastError();
 }
 

@@ -947,6 +947,31 @@ class StyleEngine:
                    "nst_flow_weights")
         return out
 
+    def anchor_fold(self, sources, weights, want_parts: bool = False):
+        """(anchor, weight): the one (C,h,w) anchor and (h,w) weight plane that stand for the J = 1 .. 8 `sources` ((C,h,w)
+        each, C = 3 or 1: earlier results warped to this frame, ascending in frame offset) under their (h,w) reliability
+        planes `weights` (nst_anchor_fold): per pixel a source counts only where no nearer one is reliable.  With want_parts
+        also the (J,h,w) planes l_j each source counts with."""
+        sources, weights = list(sources), list(weights)
+        n = len(sources)
+        if not 1 <= n <= _lib.NST_MAX_ANCHOR_SOURCES or len(weights) != n:
+            raise ValueError(f"anchor_fold: 1 .. {_lib.NST_MAX_ANCHOR_SOURCES} sources and as many weight planes, got {n} and {len(weights)}")
+        _chk_dev(sources[0], self.device)
+        if sources[0].dim() != 3:
+            raise NstError(f"expected (C,h,w) sources, got {tuple(sources[0].shape)}")
+        c, h, w = sources[0].shape
+        for s, p in zip(sources, weights):
+            _chk_dev(s, self.device, (c, h, w))
+            _chk_dev(p, self.device, (h, w))
+        anchor = torch.empty_like(sources[0])
+        weight = torch.empty((h, w), dtype=torch.float32, device=self.device)
+        parts = torch.empty((n, h, w), dtype=torch.float32, device=self.device) if want_parts else None
+        src = (C.c_void_p * n)(*[s.data_ptr() for s in sources])
+        wts = (C.c_void_p * n)(*[p.data_ptr() for p in weights])
+        _lib.check(self.ctx, self.lib.nst_anchor_fold(self.ctx, n, src, wts, c, h, w, _ptr(anchor), _ptr(weight), _ptr(parts),
+                                                      _stream(self.device)), "nst_anchor_fold")
+        return (anchor, weight, parts) if want_parts else (anchor, weight)
+
     # ---- the flow estimator (nst_flow_estimate in include/nst_hip.h has the definitions); every buffer is torch's
     def flow_estimate(self, from_plane: torch.Tensor, to_plane: torch.Tensor, params=None) -> torch.Tensor:
         """The (2,h,w) flow w = (u, v) with from(p) ~ to(p + w(p)) of two (h,w) planes on the 0 ... 255 scale of luminance()

@@ -6,6 +6,10 @@ the caller's, from whatever estimator they trust - or, when none are given, esti
 planes of consecutive frames by multi-scale Horn-Schunck with warping (nst_flow_estimate; flow_modes.FlowParams): a
 baseline that makes the path usable with this project alone, not a replacement for a better estimator - or, handed a
 flow_modes.TVL1Params, by TV-L1 on the same pyramid (nst_flow_tvl1_estimate), whose flows stay sharp at motion boundaries.
+neural_style_transfer_video_long_term adds the paper's long-term term (section 4.3, eq. 9-10): where the flow to frame i - 1 is
+unreliable the frame is held to frame i - 2, then i - 4, ... - whichever offsets are asked for - so what a moving object
+uncovers comes back with the texture it had.  The warped earlier results are folded into the ONE anchor and weight plane a
+level holds (nst_anchor_fold has the identity that makes this exact); the closure does not change.
 
 The anchor is data of one job, like its content levels - not one of job_settings.SETTINGS: it reaches the job through
 NeuralStyleTransfer.set_anchor once the job exists.  Everything here raises ValueError before any GPU work."""
@@ -19,7 +23,9 @@ from . import host_image
 from . import job_settings as _job
 from . import neural_style_transfer as _nst
 
-__all__ = ["neural_style_transfer_video", "result_size"]
+__all__ = ["neural_style_transfer_video", "neural_style_transfer_video_long_term", "long_term_anchor", "result_size"]
+
+MAX_LONG_TERM = 7          # offsets besides 1: NST_MAX_ANCHOR_SOURCES sources in one fold
 
 
 def result_size(frame_shape, levels_num):
@@ -28,12 +34,12 @@ def result_size(frame_shape, levels_num):
     return host_image.level_size(int(frame_shape[0]), int(frame_shape[1]), max(int(levels_num) - 1, 0))
 
 
-def _check_planes(what, seq, count, shape, lo=None, hi=None):
+def _check_planes(what, seq, count, shape, lo=None, hi=None, per="one per frame after the first"):
     """`seq`: `count` arrays of `shape`, finite (flows may hold non-finite entries: the warp marks them invalid) and - with
     bounds - inside them.  Returns them as contiguous float32 arrays."""
     seq = list(seq)
     if len(seq) != count:
-        raise ValueError(f"{what}: expected {count} entries (one per frame after the first), got {len(seq)}")
+        raise ValueError(f"{what}: expected {count} entries ({per}), got {len(seq)}")
     out = []
     for k, a in enumerate(seq):
         a = np.asarray(a)
@@ -78,6 +84,47 @@ def _luminance_plane(setup, frame, h, w):
     return setup.luminance(setup.resize(img, h, w)).reshape(h, w)
 
 
+def normalize_long_term(long_term):
+    """None, or the offsets besides 1 as an ascending tuple of ints: distinct integers >= 2, at most MAX_LONG_TERM."""
+    if long_term is None:
+        return None
+    out = []
+    for o in long_term:
+        if isinstance(o, (bool, np.bool_)) or not isinstance(o, (int, np.integer)):
+            raise ValueError(f"long_term: offsets are integers, got {o!r}")
+        if o < 2:
+            raise ValueError(f"long_term: offsets are >= 2 (offset 1 is always present), got {int(o)}")
+        out.append(int(o))
+    if len(set(out)) != len(out):
+        raise ValueError(f"long_term: offsets must be distinct, got {tuple(out)}")
+    if len(out) > MAX_LONG_TERM:
+        raise ValueError(f"long_term: at most {MAX_LONG_TERM} offsets, got {len(out)}")
+    return tuple(sorted(out))
+
+
+def long_term_anchor(engine, results_chw, backward, forward=None, weights=None):
+    """(omega, c, parts) of J earlier results, nearest first: results_chw[j] (device (C,h,w)) is warped along backward[j]
+    (device (2,h,w), from this frame to that one) and counts under weights[j] if given (device (h,w)), else
+    StyleEngine.flow_weights(forward[j], backward[j]) if that forward flow is given, else the warp's valid plane; the warped
+    results are folded (StyleEngine.anchor_fold) into the anchor omega (C,h,w) and the weight plane c (h,w), parts (J,h,w)
+    being what each source counts with.  `forward`, `weights`: None or J entries, each of which may be None."""
+    n = len(results_chw)
+    if len(backward) != n or any(x is not None and len(x) != n for x in (forward, weights)):
+        raise ValueError(f"long_term_anchor: {n} results need {n} backward flows (and forward flows and weights, where given)")
+    sources, planes = [], []
+    for j in range(n):
+        warped, valid = engine.warp_bilinear(results_chw[j], backward[j])
+        if weights is not None and weights[j] is not None:
+            c = weights[j]
+        elif forward is not None and forward[j] is not None:
+            c = engine.flow_weights(forward[j], backward[j])
+        else:
+            c = valid
+        sources.append(warped)
+        planes.append(c)
+    return engine.anchor_fold(sources, planes, want_parts=True)
+
+
 async def neural_style_transfer_video(frames, style, backward_flows=None, forward_flows=None, weights=None, *, temporal_weight, cfg,
                                       device=None):
     """Async generator of (frame index, percent, HWC float32 image) over the frames of a sequence, one job per frame in
@@ -97,6 +144,32 @@ async def neural_style_transfer_video(frames, style, backward_flows=None, forwar
     weights outside [0,1], a negative or non-finite temporal_weight, bad flow parameters, and forward_flows beside
     estimated backward flows (the pair would come from two estimators).  (A job of this driver is never stripe-sharded;
     PixelOptimizer.shard_stripes refuses an engine that carries an anchor.)"""
+    job = neural_style_transfer_video_long_term(frames, style, backward_flows, forward_flows, weights, temporal_weight=temporal_weight,
+                                                cfg=cfg, device=device)
+    try:
+        async for item in job:
+            yield item
+    finally:
+        await job.aclose()
+
+
+async def neural_style_transfer_video_long_term(frames, style, backward_flows=None, forward_flows=None, weights=None, *, temporal_weight,
+                                                cfg, device=None, long_term=None, long_term_flows=None):
+    """neural_style_transfer_video with the long-term term of Ruder et al. (section 4.3): its arguments, and
+    `long_term`: None - exactly neural_style_transfer_video - or the frame offsets besides 1 a frame is also held to: distinct
+    integers >= 2, at most 7, in any order.  Frame i uses the offsets j <= i.  Its anchor takes every pixel from frame i - 1
+    where c_1 says that flow is reliable, elsewhere from the nearest offset whose c_j does (StyleEngine.anchor_fold; include/
+    nst_hip.h, nst_anchor_fold); the start image is that anchor, which keeps the offset-1 warp where no offset is reliable.
+    Estimated backward flows (None, a FlowParams, a TVL1Params): for every offset in use the backward flow
+    flow_estimate(plane(i), plane(i-j)), the forward flow flow_estimate(plane(i-j), plane(i)), c_j = flow_weights of the
+    pair, source j = the last image of frame i - j warped along the backward flow - all on the device; the luminance planes
+    and last images of the max(long_term) latest frames are kept, no more.
+    Caller flows: `long_term_flows`, a dict offset -> (backward, forward, weights) under the rules of the offset-1 arguments:
+    each list has len(frames) - j entries, entry k relating frame k + j to frame k; forward and weights may be None, and c_j
+    then falls back as for offset 1.  Its keys are the offsets of `long_term`.
+    ValueError before any GPU work, besides neural_style_transfer_video's: an offset < 2, duplicate or non-integer offsets,
+    more than 7; long_term_flows without long_term or with other keys; lists of the wrong length or shape; weights outside
+    [0,1]; long_term_flows beside estimated backward flows; long_term beside caller backward flows without long_term_flows."""
     frames = list(frames)
     if not frames:
         raise ValueError("frames: at least one frame")
@@ -120,6 +193,32 @@ async def neural_style_transfer_video(frames, style, backward_flows=None, forwar
     bwd = None if estimate else _check_planes("backward_flows", backward_flows, n, (h, w, 2))
     fwd = _check_planes("forward_flows", forward_flows, n, (h, w, 2)) if forward_flows is not None else None
     wts = _check_planes("weights", weights, n, (h, w), 0.0, 1.0) if weights is not None else None
+    offsets = normalize_long_term(long_term)
+    far = None              # offset -> (backward, forward or None, weights or None): the caller's flows of the offsets >= 2
+    if long_term_flows is not None:
+        if offsets is None:
+            raise ValueError("long_term_flows without long_term: name the offsets")
+        if estimate:
+            raise ValueError("long_term_flows cannot be combined with estimated backward flows: give the flows of every offset, or none")
+        try:
+            keys = normalize_long_term(list(long_term_flows))
+        except ValueError as e:
+            raise ValueError(f"long_term_flows: its keys must be the offsets of long_term {offsets} ({e})") from None
+        if keys != offsets:
+            raise ValueError(f"long_term_flows: its keys must be the offsets of long_term {offsets}, got {keys}")
+        far = {}
+        for j in offsets:
+            entry = tuple(long_term_flows[j])
+            if len(entry) != 3:
+                raise ValueError(f"long_term_flows[{j}]: expected (backward, forward, weights), got {len(entry)} entries")
+            m, per = max(len(frames) - j, 0), f"one per frame from frame {j} on"
+            if entry[0] is None:
+                raise ValueError(f"long_term_flows[{j}]: the backward flows are missing")
+            far[j] = (_check_planes(f"long_term_flows[{j}] backward", entry[0], m, (h, w, 2), per=per),
+                      _check_planes(f"long_term_flows[{j}] forward", entry[1], m, (h, w, 2), per=per) if entry[1] is not None else None,
+                      _check_planes(f"long_term_flows[{j}] weights", entry[2], m, (h, w), 0.0, 1.0, per=per) if entry[2] is not None else None)
+    elif offsets is not None and not estimate:
+        raise ValueError("long_term beside caller backward flows needs long_term_flows: the flows of the other offsets")
     extensions = _job.handed_on(cfg)
     luminance = extensions.get("preserve_color") == "luminance"
     levels = int(cfg.levels_num)
@@ -131,6 +230,45 @@ async def neural_style_transfer_video(frames, style, backward_flows=None, forwar
         if j not in planes or planes[j].device != setup.device:
             planes[j] = _luminance_plane(setup, frames[j], h, w)
         return planes[j]
+
+    reach = max(offsets, default=1) if offsets is not None else 1
+    results = {}      # long_term only: frame index -> its last image, of the `reach` latest frames
+
+    def long_start(i):
+        """The start callable of frame i under long_term: the offsets whose frame has a result, nearest first."""
+        use = [1] + [j for j in offsets if i - j in results]
+        held = [results[i - j] for j in use]
+
+        def start(setup, top_shape):
+            if tuple(top_shape) != (h, w) or any(tuple(r.shape[:2]) != (h, w) for r in held):
+                raise ValueError(f"the job's top level is {tuple(top_shape)}, the flows are {(h, w)}")
+            dev = setup.device
+            srcs, back, forw, cs = [], [], [], []
+            for j, img in zip(use, held):
+                k = i - j           # entry k of an offset's lists relates frame k + j to frame k
+                srcs.append(torch.from_numpy(np.ascontiguousarray(img, dtype=np.float32)).to(dev).permute(2, 0, 1).contiguous())
+                given = wts if j == 1 else far[j][2] if far is not None else None
+                forward = None
+                if estimate:
+                    here, there = plane(setup, i), plane(setup, k)
+                    flow = setup.flow_estimate(here, there, params)
+                    if given is None:
+                        forward = setup.flow_estimate(there, here, params)
+                else:
+                    flows, forwards = (bwd, fwd) if j == 1 else far[j][:2]
+                    flow = _planar(flows[k], dev)
+                    if forwards is not None and given is None:
+                        forward = _planar(forwards[k], dev)
+                back.append(flow)
+                forw.append(forward)
+                cs.append(torch.from_numpy(given[k]).to(dev) if given is not None else None)
+            for old in [f for f in planes if f <= i - reach]:       # frame i + 1 reads the planes i + 1 - reach .. i + 1
+                del planes[old]
+            omega, c, _ = long_term_anchor(setup, srcs, back, forw, cs)
+            omega = omega.permute(1, 2, 0).contiguous()
+            return omega, level_anchors(setup, omega, levels, luminance), level_weights(c, levels), gamma
+
+        return start
 
     for i, frame in enumerate(frames):
         start = None
@@ -163,6 +301,9 @@ async def neural_style_transfer_video(frames, style, backward_flows=None, forwar
                     c = valid
                 return omega, level_anchors(setup, omega, levels, luminance), level_weights(c, levels), gamma
 
+            if offsets is not None:
+                start = long_start(i)
+
         job = _frame_job(frame, style, cfg, device, extensions, start)
         last = None
         try:
@@ -172,6 +313,10 @@ async def neural_style_transfer_video(frames, style, backward_flows=None, forwar
         finally:
             await job.aclose()
         previous = last
+        if offsets is not None:
+            if last is not None:
+                results[i] = last
+            results.pop(i - reach, None)
 
 
 def _frame_job(frame, style, cfg, device, extensions, start):

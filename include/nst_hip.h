@@ -551,6 +551,37 @@ int nst_level_set_anchor(nst_ctx* ctx, int level, const float* anchor /* device 
 int nst_level_anchor(const nst_ctx* ctx, int level, float* gamma, int* weighted);
 int nst_job_temporal_losses(nst_ctx* ctx, float* out /* device, levels */, void* stream);
 
+/* Long-term consistency: several earlier frames in the one anchor a level holds.  Ruder, Dosovitskiy & Brox (GCPR 2016),
+ * section 4.3, eq. 9-10: frame i is held to frame i-1 where that flow is reliable, elsewhere to i-2, then i-4, ... - so what
+ * an object uncovers as it moves on comes back with the texture it had before it was covered.
+ * Identity.  For anchors a_j under weights l_j, W = sum_j l_j and a~ = sum_j l_j a_j / W:
+ *   sum_j l_j (y - a_j)^2 = W (y - a~)^2 + sum_j l_j (a_j - a~)^2, and the second sum does not depend on y.
+ *   The single anchor a~ under the weight plane W has exactly the gradient of the J-term loss; tmp differs from the J-term
+ *   value by the constant (1/n) sum_{ch,p} sum_j l_j (a_j - a~)^2 of the job, which is exactly 0 where at most one l_j is not 0
+ *   (weights of 0 and 1, as nst_flow_weights makes them).  nst_level_set_anchor, the term and the closure are unchanged.
+ * nst_anchor_fold: J sources (device (C,h,w) each: the warped results, ascending in frame offset) and J weight planes
+ * (device (h,w) each: their reliability) -> anchor (C,h,w), weight (h,w) and, if parts is not NULL, parts (J,h,w).
+ * Per pixel p, in fp32, no contraction, every operation rounded once, in this order:
+ * - c_j = w_j(p) > 0 ? min(w_j(p), 1) : 0: a NaN or a negative weight counts as 0; values in [0,1] keep their bits.
+ * - s_0 = 0, l_j = max(c_j - s_j, 0), s_{j+1} = s_j + c_j (eq. 10: a source counts only where no nearer one is reliable).
+ * - Wsum = ((l_0 + l_1) + ...) in index order; weight(p) = min(Wsum, 1); parts(j, p) = l_j.
+ * - j* = the first j with l_j > 0.  None: anchor(ch, p) = sources[0](ch, p) and weight(p) = 0.
+ * - Otherwise anchor(ch, p) = ((a_j* + t_j') + t_j'') + ... over the j > j* with l_j > 0 in index order,
+ *   t_j = (l_j / Wsum) (a_j - a_j*), the division correctly rounded.
+ * - With one live source the sum is empty and the anchor has that source's bits.  A source with l_j = 0 never enters the
+ *   result: its non-finite values do not leak.
+ * One launch of a streaming kernel; the 2 J pointers travel by value as a kernel argument; the context allocates nothing and
+ * nst_ctx_bytes does not move; reads no job state.  Asynchronous on `stream`.  16-byte accesses on every plane that starts
+ * on a 16-byte boundary (per channel: plane ch of every source and of the anchor; the weight planes in and out together;
+ * each plane of parts), pixel by pixel on the others and on the last h w % 4 pixels.
+ * NST_E_ARG, with nothing launched: J outside 1 .. NST_MAX_ANCHOR_SOURCES, C not 1 or 3, h or w < 1, a null pointer other
+ * than parts, an output that overlaps an input or another output. */
+#define NST_MAX_ANCHOR_SOURCES 8
+int nst_anchor_fold(nst_ctx* ctx, int J, const float* const* sources /* host array of J device (C,h,w) */,
+                    const float* const* weights /* host array of J device (h,w) */, int C, int h, int w,
+                    float* anchor /* device (C,h,w) */, float* weight /* device (h,w) */,
+                    float* parts /* device (J,h,w), nullable */, void* stream);
+
 /* optimizer_step_callback without its LR decay and prints (neural_style_transfer.py:152-199) =
  * sum over levels of LossBuilder.build (:84-112) on the bicubic 1/2 chain of x (:170-176),
  * then backward (:193).  x, grad: device (3,H0,W0) ((1,H0,W0) under NST_COLOR_LUMINANCE).  losses: device, NST_LOSS_ROW*levels+1
