@@ -87,6 +87,14 @@ SYMBOLS = {
     "nst_job_temporal_losses": (C.c_int, [c_void, c_void, c_void]),
     "nst_anchor_loss": (C.c_int, [c_void, c_void, c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, c_void, c_void]),
     "nst_anchor_geometry": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "nst_level_set_patches": (C.c_int, [c_void, C.c_int, c_void, C.c_int, C.c_int, c_float_p, C.c_int, C.c_double, c_void]),
+    "nst_level_patches": (C.c_int, [c_void, C.c_int, c_float_p, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    "nst_job_patch_losses": (C.c_int, [c_void, c_void, c_void]),
+    "nst_level_patch_matches": (C.c_int, [c_void, C.c_int, C.c_int, c_void, c_void]),
+    "nst_patch_match": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, C.c_int, C.c_int, C.c_int, C.c_double, c_void,
+                                  c_void, c_void]),
+    "nst_patch_term": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, C.c_int, C.c_int, C.c_int, c_void, C.c_float,
+                                 c_void, c_void, c_void]),
     "nst_warp_bilinear": (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, c_void, c_void]),
     "nst_flow_weights": (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, c_void, c_void]),
     "nst_anchor_fold": (C.c_int, [c_void, C.c_int, C.POINTER(c_void), C.POINTER(c_void), C.c_int, C.c_int, C.c_int, c_void, c_void,

@@ -279,6 +279,66 @@ int nst_anchor_geometry(int* blocks, int* block_elems) {
     return NST_OK;
 }
 
+// The MRF term's pieces on their own (include/nst_hip.h has the definition): the kernels of patch_match.hip on scratch
+// buffers.  Synchronous.
+static int patch_args(nst_ctx* ctx, const float* f, int h, int w, int C, const float* fs, int hs, int ws, int stride, PatchDict* d) {
+    if (!f || !fs) return fail(ctx, NST_E_ARG, "null argument");
+    if (C != 64 && C != 128 && C != 256 && C != 512) return fail(ctx, NST_E_ARG, "the patch match takes maps of 64, 128, 256 or 512 channels");
+    if (h < 3 || w < 3 || hs < 3 || ws < 3) return fail(ctx, NST_E_ARG, "the map and the style map must be at least 3x3");
+    if (stride < 1 || stride > 8) return fail(ctx, NST_E_ARG, "the style stride must be 1..8");
+    if ((double)h * w * C >= 2147483648.0 || (double)hs * ws * C >= 2147483648.0) return fail(ctx, NST_E_ARG, "the map is too large");
+    *d = PatchDict{};
+    d->fs = fs;
+    if (!pm_dict_geometry(hs, ws, C, stride, d)) return fail(ctx, NST_E_ARG, "bad dictionary geometry");
+    return NST_OK;
+}
+
+int nst_patch_match(nst_ctx* ctx, const float* f, int h, int w, int C, const float* fs, int hs, int ws, int stride, double epsilon,
+                    int* idx_out, float* score_out, void* stream) {
+    NSTCHK(bind(ctx));
+    PatchDict d;
+    NSTCHK(patch_args(ctx, f, h, w, C, fs, hs, ws, stride, &d));
+    if (!idx_out && !score_out) return fail(ctx, NST_E_ARG, "null argument");
+    if (!(epsilon > 0.0) || std::isinf(epsilon)) return fail(ctx, NST_E_ARG, "the patch epsilon must be finite and > 0");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t n = (size_t)(h - 2) * (w - 2);
+    Scratch sc(ctx, s);
+    unsigned* amax = nullptr; float* rq = nullptr; unsigned char* packed = nullptr; unsigned long long* keys = nullptr;
+    NSTCHK(sc.alloc(&amax, (size_t)2 * NST_AMAX_SLOTS));
+    NSTCHK(sc.alloc(&rq, (size_t)pm_dict_tiles(d.m) * 32));
+    NSTCHK(sc.alloc(&packed, pm_packed_bytes(d.m, C)));
+    NSTCHK(sc.alloc(&keys, n));
+    HIPCHK(ctx, launch_pm_prepare(d, epsilon, amax, rq, packed, s));
+    d.amax = amax; d.rq = rq; d.packed = packed;
+    unsigned* amax_f = amax + NST_AMAX_SLOTS;
+    HIPCHK(ctx, launch_zero(amax_f, NST_AMAX_SLOTS, s));
+    HIPCHK(ctx, launch_absmax_slots(f, (size_t)h * w * C, amax_f, s));
+    PatchSearch p{};
+    p.f = f; p.h = h; p.w = w; p.C = C; p.amax_f = amax_f; p.d = d; p.keys = keys;
+    HIPCHK(ctx, launch_pm_search(p, idx_out, score_out, s));
+    return sc.finish();
+}
+
+int nst_patch_term(nst_ctx* ctx, const float* f, int h, int w, int C, const float* fs, int hs, int ws, int stride, const int* idx,
+                   float coef, float* value_out, float* grad_out, void* stream) {
+    NSTCHK(bind(ctx));
+    PatchDict d;
+    NSTCHK(patch_args(ctx, f, h, w, C, fs, hs, ws, stride, &d));
+    if (!idx || (!value_out && !grad_out)) return fail(ctx, NST_E_ARG, "null argument");
+    if (!std::isfinite(coef)) return fail(ctx, NST_E_ARG, "the coefficient must be finite");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const PatchTerm t{f, h, w, idx, d};
+    Scratch sc(ctx, s);
+    if (value_out) {
+        double* partial = nullptr;
+        NSTCHK(sc.alloc(&partial, (size_t)PM_VALUE_BLOCKS));
+        HIPCHK(ctx, launch_pm_value_partials(t, partial, s));
+        HIPCHK(ctx, launch_pm_value(partial, 9.0 * (double)C * (double)(h - 2) * (double)(w - 2), value_out, s));
+    }
+    if (grad_out) HIPCHK(ctx, launch_pm_grad(t, coef, grad_out, 0, s));
+    return sc.finish();
+}
+
 // The warp of a sequence (include/nst_hip.h): out = src sampled bilinearly at p + flow(p), valid (nullable) = the four taps
 // lie inside the image.  Synchronous.
 int nst_warp_bilinear(nst_ctx* ctx, const float* src, const float* flow, int C, int h, int w, float* out, float* valid, void* stream) {

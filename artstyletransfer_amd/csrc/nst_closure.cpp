@@ -248,6 +248,48 @@ int anchor_backward(nst_ctx* ctx, LevelWs& L, const float* y, float* grad, hipSt
     return NST_OK;
 }
 
+// ---- the MRF term (include/nst_hip.h has the definition; kernels: patch_match.hip) ---------------------------------------
+// map index i of level L: the term's operands on the level's own map, 9 C n, and coef = (float)(w 2 / (9 C n)) formed in double
+PatchTerm patch_term_of(const LevelWs& L, int i) {
+    const int l = kTapLayer[i];
+    return PatchTerm{L.acts.act[l], L.acts.h[l], L.acts.w[l], L.pm.nn[i], L.pm.d[i]};
+}
+double patch_denom(const LevelWs& L, int i) {
+    const int l = kTapLayer[i];
+    return 9.0 * (double)kCout[l] * (double)(L.acts.h[l] - 2) * (double)(L.acts.w[l] - 2);
+}
+float patch_coef(float w, double denom) { return (float)((double)w * 2.0 / denom); }
+// forward part of level L, once its maps exist: per map with a weight the search (nn), the value partials and mrf_i (a level
+// without the term: no launch)
+int patch_forward(nst_ctx* ctx, LevelWs& L, hipStream_t s) {
+    for (int i = 0; i < 6 && L.pm.on(); ++i) {
+        if (!(L.pm.w[i] > 0.f)) continue;
+        const int l = kTapLayer[i];
+        const PatchTerm t = patch_term_of(L, i);
+        PatchSearch p{};
+        p.f = t.f; p.h = t.h; p.w = t.w; p.C = kCout[l]; p.amax_f = amax_act(L.acts, l); p.d = t.d; p.keys = L.pm.keys[i];
+        {
+            Timer tm(ctx, s, K_OTHER, 2.0 * (double)(t.h - 2) * (t.w - 2) * (double)t.d.m * 9.0 * kCout[l], t.h, t.w, kCout[l], t.d.m, 9, 100 + i);
+            HIPCHK(ctx, launch_pm_search(p, L.pm.nn[i], nullptr, s));
+        }
+        Timer tm(ctx, s, K_OTHER, 0);
+        HIPCHK(ctx, launch_pm_value_partials(t, L.pm.partial[i], s));
+        HIPCHK(ctx, launch_pm_value(L.pm.partial[i], patch_denom(L, i), L.pm.vals + i, s));
+    }
+    return NST_OK;
+}
+// gradient part of map index i: into dst (the map's shape), written or added to what is there
+int patch_backward(nst_ctx* ctx, LevelWs& L, int i, float* dst, int accumulate, hipStream_t s) {
+    Timer tm(ctx, s, K_OTHER, 0);
+    HIPCHK(ctx, launch_pm_grad(patch_term_of(L, i), patch_coef(L.pm.w[i], patch_denom(L, i)), dst, accumulate, s));
+    return NST_OK;
+}
+// conv layer m of level L carries the term
+bool patch_layer(const LevelWs& L, int m) {
+    const int i = tap_index_of(m);
+    return i >= 0 && L.pm.w[i] > 0.f;
+}
+
 // ---- the moment loss (include/nst_hip.h has the definition; kernels: moments.hip) ----------------------------------------
 // style slot q of level L on its map f (N pixels, C channels): the statistics item, and the fold item that follows the Gram
 // finish pass and the row bias of a shifted Gram (r0: that bias, or nullptr)
@@ -329,6 +371,12 @@ int backward(nst_ctx* ctx, ActSet& a, const Inject* inj, const ContentJob* cj, f
             Timer t(ctx, s, K_OTHER, 0);
             HIPCHK(ctx, launch_mse_grad(a.act[l], cj->target, cj->n, cj->coef, oth, cj->partial, s));
         }
+        // the MRF term of the top map: onto the content gradient when there is one, the addend of the 1x1 Gram launch
+        const bool mrf = inj[l].mrf && inj[l].S;
+        if (mrf) {
+            Timer t(ctx, s, K_OTHER, 0);
+            HIPCHK(ctx, launch_pm_grad(*inj[l].mrf, inj[l].mrf_coef, oth, content ? 1 : 0, s));
+        }
         if (inj[l].guided) {
             GuidedBwd gb = *inj[l].guided;
             gb.addend = content ? oth : nullptr; gb.out = cur; gb.mask = top_mask ? a.act[l] : nullptr;
@@ -337,7 +385,7 @@ int backward(nst_ctx* ctx, ActSet& a, const Inject* inj, const ContentJob* cj, f
             // (the content gradient, if any, as the addend of the 1x1 Gram launch)
             ConvParams p{};
             p.in = a.act[l]; p.wt = inj[l].S; p.out = cur; p.mask = top_mask ? a.act[l] : nullptr;
-            p.addend = content ? oth : nullptr;
+            p.addend = (content || mrf) ? oth : nullptr;
             p.bias = inj[l].bias;                  // (a shifted Gram: F S + r, then the addend and the mask)
             p.H = a.h[l]; p.W = a.w[l]; p.Cin = kCout[l]; p.Cout = kCout[l];
             Timer t(ctx, s, K_GRAM, conv_flops(p.H, p.W, p.Cin, p.Cout, 1));
@@ -392,6 +440,12 @@ int backward(nst_ctx* ctx, ActSet& a, const Inject* inj, const ContentJob* cj, f
                 p.addend = oth;
             } else if (in.direct) {
                 p.addend = in.direct;
+            }
+            if (in.mrf) {
+                // the MRF term of the map: written, or added to the content gradient
+                Timer t(ctx, s, K_OTHER, 0);
+                HIPCHK(ctx, launch_pm_grad(*in.mrf, in.mrf_coef, oth, p.addend == oth ? 1 : 0, s));
+                p.addend = oth;
             }
             if (in.guided) {
                 // the guided Gram backward by its own launch, onto the content gradient when there is one: the addend
@@ -750,6 +804,13 @@ int batched_backward(nst_ctx* ctx, const float* const* xi, float* const* gi, con
     };
     if (top_content)
         for (int k = 0; k < n; ++k) NSTCHK(content_grad(k, oth[k]));
+    // the MRF term of the top map (nst_level_set_patches; a level's own), written after the content gradient: the launch's addend
+    bool top_mrf[NST_MAX_LEVELS] = {};
+    for (int k = 0; k < n && top_q >= 0; ++k) {
+        LevelWs& L = ctx->lv[lv[k]];
+        top_mrf[k] = patch_layer(L, top);
+        if (top_mrf[k]) NSTCHK(patch_backward(ctx, L, tap_index_of(top), oth[k], top_content ? 1 : 0, s));
+    }
     const bool guided = guided_levels(ctx, lv, n);
     if (guided && top_q >= 0) {
         // top of the chain of a guided job: the guided Gram backward of each level, which adds the content gradient (when
@@ -777,7 +838,7 @@ int batched_backward(nst_ctx* ctx, const float* const* xi, float* const* gi, con
             im.out = cur[k]; im.H = a.h[l]; im.W = a.w[l];
             im.in2 = a.act[l]; im.wt2_f32 = L.S[top_q]; im.amax_in2 = amax_act(a, l); im.amax_w2 = amax_S(a, top_q);
             im.bits_in = tp.top_mask() ? a.bits[l] : nullptr; im.amax_out = amax_grad(a, l);
-            im.addend = top_content ? oth[k] : nullptr;
+            im.addend = (top_content || top_mrf[k]) ? oth[k] : nullptr;
             im.bias = ctx->row_bias_of(L, top_q);      // (a shifted Gram, the moment term: F S + r, then the addend and the mask)
             if (win) { im.in2_row0 = win_r0(*win, kScale[l]); im.in2_rows = win_nr(*win, kScale[l]); }
             flops += conv_flops(im.H, im.W, b.Cin2, b.Cout, 1);
@@ -856,6 +917,11 @@ int batched_backward(nst_ctx* ctx, const float* const* xi, float* const* gi, con
                 NSTCHK(content_grad(k, oth[k]));
                 im.addend = oth[k];
             }
+            if (patch_layer(L, m)) {
+                // the MRF term of the map, after the content gradient when the map is the content map too
+                NSTCHK(patch_backward(ctx, L, tap_index_of(m), oth[k], m == tp.content ? 1 : 0, s));
+                im.addend = oth[k];
+            }
             im.bits_in = a.bits[m];
         }
         {
@@ -921,6 +987,7 @@ int closure_batched_forward(nst_ctx* ctx, const float* const* xi, unsigned level
     NSTCHK(batched_forward(ctx, xi, lv, n, s, nullptr, overlap ? sw : -1.f));
     NSTCHK(batched_gram(ctx, lv, n, sw, s, overlap ? 0x18u : (1u << ctx->taps.nstyle) - 1u));
     if (overlap) HIPCHK(ctx, hipStreamWaitEvent(s, ctx->side_join, 0));
+    for (int k = 0; k < n; ++k) NSTCHK(patch_forward(ctx, ctx->lv[lv[k]], s));       // (nst_level_set_patches: the maps exist)
     if (loss_terms && ctx->forward_pack && ctx->conv_mode == 2 && !ctx->use_graph && n > 1) {
         // one launch each for all levels; every level keeps its partial buffers and block decomposition
         MseBatch mb{};
@@ -1025,6 +1092,15 @@ int closure_per_level(nst_ctx* ctx, const float* const* xi, float* const* gi, in
         inj[l].S_amax = h2 ? amax_S(L.acts, k) : nullptr;
     }
     inj[tp.content].content = true;
+    // the MRF term (nst_level_set_patches): nn and the values now, the gradients as addends of the walk
+    NSTCHK(patch_forward(ctx, L, s));
+    PatchTerm pterm[6];
+    for (int i = 0; i < 6 && L.pm.on(); ++i) {
+        if (!(L.pm.w[i] > 0.f)) continue;
+        pterm[i] = patch_term_of(L, i);
+        inj[kTapLayer[i]].mrf = &pterm[i];
+        inj[kTapLayer[i]].mrf_coef = patch_coef(L.pm.w[i], patch_denom(L, i));
+    }
     ContentJob cj{L.content_t, L.content_n, content_coef(cw, (double)L.content_n), L.content_partial};
     NSTCHK(backward(ctx, L.acts, inj, &cj, L.gbuf[0], L.gbuf[1], gi[level], L.h, L.w, s, tp.top, tp.top_mask(), ctx->channels));
     {
@@ -1065,6 +1141,12 @@ LossAssembly fill_loss_assembly(const nst_ctx* ctx, unsigned level_mask, float c
         const LevelWs& L = ctx->lv[i];
         if (!(L.anc.gamma > 0.f)) continue;
         la.lv[i].tmp_partial = L.anc.partial; la.lv[i].tmp_gamma = L.anc.gamma; la.lv[i].tmp_n = anchor_n(ctx, L); la.lv[i].tmp_out = L.anc.val;
+    }
+    for (int i = 0; i < ctx->levels; ++i) {      // (a level's own: la{} left the levels without the MRF term at nullptr)
+        const LevelWs& L = ctx->lv[i];
+        if (!L.pm.on()) continue;
+        la.lv[i].mrf_vals = L.pm.vals;
+        for (int k = 0; k < 6; ++k) la.lv[i].mrf_w[k] = L.pm.w[k];
     }
     return la;
 }
@@ -1239,6 +1321,8 @@ int window_check(nst_ctx* ctx, const float* xs, int row0, int rows, int H0) {
     LevelWs& L = ctx->lv[0];
     if (L.anc.gamma > 0.f)
         return fail(ctx, NST_E_STATE, "the stripe closure implements no temporal term (nst_level_set_anchor(ctx, 0, NULL, NULL, 0, stream) clears it)");
+    if (L.pm.on())
+        return fail(ctx, NST_E_STATE, "the stripe closure implements no MRF term (nst_level_set_patches(ctx, 0, NULL, ...) clears it)");
     if (L.guide.R > 0)
         return fail(ctx, NST_E_STATE, "the stripe closure implements no spatial control (nst_level_set_guidance(ctx, 0, 0, ...) clears it)");
     if (!L.targets) return fail(ctx, NST_E_STATE, "targets of the stripe not set");
@@ -1385,6 +1469,7 @@ int nst_level_set_guidance(nst_ctx* ctx, int level, int R, const float* planes, 
     if (ctx->conv_mode != 2) return fail(ctx, NST_E_STATE, "spatial control runs in the f16x2 arithmetic only (NST_CONV unset)");
     if (ctx->gs_on()) return fail(ctx, NST_E_STATE, "guided Gram matrices take the plain statistic only (nst_job_set_gram_shift with zeros switches the shift off)");
     if (ctx->mom_on()) return fail(ctx, NST_E_STATE, "guided levels take no moment loss (nst_job_set_moments with zeros switches it off)");
+    if (L.pm.on()) return fail(ctx, NST_E_STATE, "a level with the MRF term takes no guidance (nst_level_set_patches(ctx, level, NULL, ...) clears the term)");
     if (!planes) return fail(ctx, NST_E_ARG, "null argument");
     float lam[NST_MAX_REGIONS] = {1.f, 1.f, 1.f, 1.f};
     bool positive = lambda == nullptr;

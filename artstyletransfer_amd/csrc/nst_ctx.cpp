@@ -457,6 +457,7 @@ int nst_ctx_create_ex(int device, const float* const* weights, const float* cons
     if (e == hipSuccess) e = conv_h2_init_device();
     if (e == hipSuccess) e = conv_wino_init_device();
     if (e == hipSuccess) e = gram_init_device();
+    if (e == hipSuccess) e = pm_init_device();
     // options: an explicit argument wins; -1 falls back to the environment (read here, once), then to the default
     if (opts.conv_mode >= 0) {
         if (opts.conv_mode > NST_CONV_F16X2) { ctx->err = "nst_options.conv_mode must be NST_CONV_F32, NST_CONV_BF16X3 or NST_CONV_F16X2"; return bail(NST_E_ARG); }
@@ -653,6 +654,7 @@ int nst_job_set_taps(nst_ctx* ctx, int content_index, unsigned style_mask, int u
     for (int i = 0; i < ctx->levels; ++i) {
         LevelWs& L = ctx->lv[i];
         L.guide = Guidance();           // (sized for the old style set: nst_level_set_guidance again)
+        L.pm = PatchLevel();            // (the style's maps of the old taps: nst_level_set_patches again)
         free_tap_buffers(L);
         NSTCHK(alloc_tap_buffers(ctx, L));
     }
@@ -675,6 +677,8 @@ int nst_job_set_color(nst_ctx* ctx, int mode) {
                           [&] { drop_closure_state(ctx, true); }));
     // an anchor has the planes of the mode it was set under (nst_level_set_anchor): another mode drops it
     for (int i = 0; i < ctx->levels && channels != ctx->channels; ++i) ctx->lv[i].anc = AnchorLevel();
+    // the MRF term holds maps of the style image as the other mode's network saw it (nst_level_set_patches): dropped
+    for (int i = 0; i < ctx->levels; ++i) ctx->lv[i].pm = PatchLevel();
     ctx->channels = channels;
     return NST_OK;
 }
@@ -689,6 +693,7 @@ int nst_job_set_pooling(nst_ctx* ctx, int mode) {
     if (mode != NST_POOL_MAX && mode != NST_POOL_AVG) return fail(ctx, NST_E_ARG, "mode must be NST_POOL_MAX or NST_POOL_AVG");
     quiesce(ctx);
     drop_closure_state(ctx, true);
+    for (int i = 0; i < ctx->levels; ++i) ctx->lv[i].pm = PatchLevel();      // (the MRF term's maps are the other network's)
     ctx->pool_avg = mode == NST_POOL_AVG ? 1 : 0;
     return NST_OK;
 }
@@ -1026,6 +1031,122 @@ int nst_level_anchor(const nst_ctx* ctx, int level, float* gamma, int* weighted)
     if (level < 0 || level >= ctx->levels) return NST_E_ARG;
     if (gamma) *gamma = ctx->lv[level].anc.gamma;
     if (weighted) *weighted = ctx->lv[level].anc.weights ? 1 : 0;
+    return NST_OK;
+}
+
+// The MRF term of one level (Li & Wand 2016; include/nst_hip.h has the definition): the style's weighted maps, their
+// dictionaries, nn and the value partials.  Data of one job with the life cycle of nst_level_set_anchor: everything is made
+// here, beside what the level has (a refusal changes nothing), the context's work is waited for before the level's block is
+// replaced, and the captured closure, an optimiser's remembered closure and a pending backward half go.  The targets stay.
+int nst_level_set_patches(nst_ctx* ctx, int level, const float* style, int hs, int ws, const float* weights, int stride, double epsilon,
+                          void* stream) {
+    if (ctx) { ++ctx->closure_epoch; ++ctx->ws_seq; }
+    NSTCHK(bind(ctx));
+    if (ctx->levels < 1) return fail(ctx, NST_E_STATE, "nst_job_configure has not been called");
+    if (level < 0 || level >= ctx->levels) return fail(ctx, NST_E_ARG, "level out of range");
+    LevelWs& L = ctx->lv[level];
+    PatchLevel g;
+    bool on = false;
+    if (style) {
+        if (!weights) return fail(ctx, NST_E_ARG, "null argument");
+        for (int i = 0; i < 6; ++i) {
+            if (!(weights[i] >= 0.f) || std::isinf(weights[i])) return fail(ctx, NST_E_ARG, "the MRF weights must be finite and >= 0");
+            g.w[i] = weights[i];
+            on = on || weights[i] > 0.f;
+        }
+        if (!(epsilon > 0.0) || std::isinf(epsilon)) return fail(ctx, NST_E_ARG, "the MRF epsilon must be finite and > 0");
+        if (stride < 1 || stride > 8) return fail(ctx, NST_E_ARG, "the style stride must be 1..8");
+    }
+    hipStream_t s = enter(ctx, stream);
+    if (on) {
+        if (ctx->conv_mode != 2) return fail(ctx, NST_E_STATE, "the MRF term runs in the f16x2 arithmetic only (NST_CONV unset)");
+        if (ctx->use_graph) return fail(ctx, NST_E_STATE, "the MRF term's launches are not captured: a context with use_graph takes no term");
+        if (L.guide.R > 0) return fail(ctx, NST_E_STATE, "a guided level takes no MRF term (nst_level_set_guidance(ctx, level, 0, ...) clears the guidance)");
+        if (hs < 16 || ws < 16) return fail(ctx, NST_E_ARG, "style image must be at least 16x16");
+        const unsigned style_mask = style_mask_of(ctx->taps);
+        int deepest = -1;
+        for (int i = 0; i < 6; ++i) {
+            if (!(g.w[i] > 0.f)) continue;
+            if (!((style_mask >> i) & 1u)) return fail(ctx, NST_E_ARG, "a positive MRF weight on a map that is not a style map of the job");
+            const int l = kTapLayer[i];
+            if (L.acts.h[l] < 3 || L.acts.w[l] < 3 || (hs >> kScale[l]) < 3 || (ws >> kScale[l]) < 3)
+                return fail(ctx, NST_E_ARG, "a weighted map or its style map is below 3x3");
+            deepest = l;
+        }
+        g.stride = stride; g.eps = epsilon;
+        Scratch sc(ctx, s);
+        NSTCHK(alloc_acts(ctx, sc.acts, hs, ws));
+        NSTCHK(forward(ctx, sc.acts, style, hs, ws, s, deepest, ctx->channels));
+        NSTCHK(g.mem.alloc(ctx, &g.vals, 6));
+        HIPCHK(ctx, hipMemsetAsync(g.vals, 0, 6 * sizeof(float), s));
+        for (int i = 0; i < 6; ++i) {
+            if (!(g.w[i] > 0.f)) continue;
+            const int l = kTapLayer[i], C = kCout[l], mh = sc.acts.h[l], mw = sc.acts.w[l];
+            PatchDict& d = g.d[i];
+            if (!pm_dict_geometry(mh, mw, C, stride, &d)) return fail(ctx, NST_E_ARG, "a weighted map or its style map is below 3x3");
+            float* fs = nullptr; unsigned* amax = nullptr; float* rq = nullptr; unsigned char* packed = nullptr;
+            const size_t fs_n = (size_t)mh * mw * C, n = (size_t)(L.acts.h[l] - 2) * (L.acts.w[l] - 2);
+            NSTCHK(g.mem.alloc(ctx, &fs, fs_n));
+            NSTCHK(g.mem.alloc(ctx, &amax, (size_t)NST_AMAX_SLOTS));
+            NSTCHK(g.mem.alloc(ctx, &rq, (size_t)pm_dict_tiles(d.m) * 32));
+            NSTCHK(g.mem.alloc(ctx, &packed, pm_packed_bytes(d.m, C)));
+            NSTCHK(g.mem.alloc(ctx, &g.keys[i], n));
+            NSTCHK(g.mem.alloc(ctx, &g.nn[i], n));
+            NSTCHK(g.mem.alloc(ctx, &g.partial[i], (size_t)PM_VALUE_BLOCKS));
+            HIPCHK(ctx, hipMemcpyAsync(fs, sc.acts.act[l], fs_n * sizeof(float), hipMemcpyDeviceToDevice, s));
+            HIPCHK(ctx, hipMemsetAsync(g.nn[i], 0, n * sizeof(int), s));
+            d.fs = fs;
+            HIPCHK(ctx, launch_pm_prepare(d, epsilon, amax, rq, packed, s));
+            d.amax = amax; d.rq = rq; d.packed = packed;
+        }
+        NSTCHK(sc.finish());       // (synchronises: the caller's image is free again when this returns)
+    } else {
+        g = PatchLevel();
+    }
+    quiesce(ctx);
+    drop_closure_state(ctx, false);
+    L.pm = std::move(g);
+    return NST_OK;
+}
+
+int nst_level_patches(const nst_ctx* ctx, int level, float* weights, int* stride, double* epsilon) {
+    if (!ctx) return fail(nullptr, NST_E_ARG, "null context");
+    if (level < 0 || level >= ctx->levels) return fail(nullptr, NST_E_ARG, "level out of range");
+    const PatchLevel& g = ctx->lv[level].pm;
+    for (int i = 0; i < 6 && weights; ++i) weights[i] = g.w[i];
+    if (stride) *stride = g.stride;
+    if (epsilon) *epsilon = g.eps;
+    return NST_OK;
+}
+
+// the unweighted mrf_i of the last closure, levels x 6 by map index (zeros: levels without the term or outside the last level
+// mask, maps without a weight, no closure yet)
+int nst_job_patch_losses(nst_ctx* ctx, float* out, void* stream) {
+    NSTCHK(bind(ctx));
+    if (ctx->levels < 1) return fail(ctx, NST_E_STATE, "nst_job_configure has not been called");
+    if (!out) return fail(ctx, NST_E_ARG, "null argument");
+    hipStream_t s = enter(ctx, stream);
+    for (int i = 0; i < ctx->levels; ++i) {
+        const PatchLevel& g = ctx->lv[i].pm;
+        if (g.on()) HIPCHK(ctx, hipMemcpyAsync(out + 6 * i, g.vals, 6 * sizeof(float), hipMemcpyDeviceToDevice, s));
+        else HIPCHK(ctx, hipMemsetAsync(out + 6 * i, 0, 6 * sizeof(float), s));
+    }
+    mark(ctx, s);
+    return NST_OK;
+}
+
+// the nn of the last closure of one weighted map of a level ((h - 2)(w - 2) int32 of the map; zeros before any closure)
+int nst_level_patch_matches(nst_ctx* ctx, int level, int map, int* idx_out, void* stream) {
+    NSTCHK(bind(ctx));
+    if (level < 0 || level >= ctx->levels) return fail(ctx, NST_E_ARG, "level out of range");
+    if (map < 0 || map > 5 || !idx_out) return fail(ctx, NST_E_ARG, "bad argument");
+    const LevelWs& L = ctx->lv[level];
+    if (!(L.pm.w[map] > 0.f)) return fail(ctx, NST_E_STATE, "the map carries no MRF term on this level (nst_level_set_patches)");
+    const int l = kTapLayer[map];
+    const size_t n = (size_t)(L.acts.h[l] - 2) * (L.acts.w[l] - 2);
+    hipStream_t s = enter(ctx, stream);
+    HIPCHK(ctx, hipMemcpyAsync(idx_out, L.pm.nn[map], n * sizeof(int), hipMemcpyDeviceToDevice, s));
+    mark(ctx, s);
     return NST_OK;
 }
 

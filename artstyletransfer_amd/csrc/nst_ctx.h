@@ -200,6 +200,27 @@ struct AnchorLevel {
     DevMem mem;
 };
 
+// The MRF term of one level (nst_level_set_patches; include/nst_hip.h has the definition), by map index: the weight (0: the
+// map has no term), the style's map with its dictionary (d[i]: fs, the absmax record, rq and the packed operand), the search
+// keys, nn and the value partials of the last closure, and the unweighted mrf_i (six floats, which the forward half writes
+// and the loss rows read).  Data of one job, not a setting: made by the setter, freed when the level's term is cleared, the
+// taps, the pooling or the colour mode are set or the job is configured again: a closure allocates nothing.
+struct PatchLevel {
+    float w[6] = {};
+    int stride = 1;
+    double eps = 1e-5;
+    PatchDict d[6] = {};
+    unsigned long long* keys[6] = {};
+    int* nn[6] = {};
+    double* partial[6] = {};    // PM_VALUE_BLOCKS each
+    float* vals = nullptr;
+    DevMem mem;
+    bool on() const {
+        for (float v : w) if (v > 0.f) return true;
+        return false;
+    }
+};
+
 // the level image and its gradient (levels >= 1), planar: channels (nst_job_set_color) x h x w floats each
 struct LevelImage {
     float* xl = nullptr;
@@ -215,6 +236,7 @@ struct LevelWs {
     GramShiftLevel gs;
     MomentLevel mom;
     AnchorLevel anc;
+    PatchLevel pm;
     ActSet acts;
     float* gbuf[2] = {};
     size_t gbuf_floats = 0;
@@ -337,7 +359,7 @@ struct nst_ctx {
         if (mom_on() && mom_slot(q)) return L.mom.row_bias(q);
         return gs_on() ? L.gs.row_bias(q) : nullptr;
     }
-    // bumped on entry to every call that changes what a closure computes (configure, taps, colour, pooling, style weights, Laplacian, matting, Gram shift, moments, targets, a level's anchor), failure paths
+    // bumped on entry to every call that changes what a closure computes (configure, taps, colour, pooling, style weights, Laplacian, matting, Gram shift, moments, targets, a level's anchor, a level's MRF term), failure paths
     // included: an optimiser's remembered closure result is valid only under the epoch it was made in (nst_opt.cpp)
     unsigned long long closure_epoch = 0;
     // advanced on entry to every call that reads or writes the level workspaces (nst_closure*, nst_window_*,
@@ -463,6 +485,8 @@ struct Inject {
     bool content = false;            // or the content MSE gradient (closure only)
     const float* bias = nullptr;     // with S, a shifted Gram (nst_job_set_gram_shift) and / or the moment term: the row bias, dF = F * S + r
     const GuidedBwd* guided = nullptr; // guided Gram backward (R, t, S filled in): dF = sum_r t_r^2 F S_r, by a launch of its own
+    const PatchTerm* mrf = nullptr;  // the MRF term of the map (nst_level_set_patches): its gradient joins the addend of the launch
+    float mrf_coef = 0.f;
 };
 struct ContentJob { const float* target; size_t n; float coef; double* partial; };
 // channels = 1: x is a luminance plane u, conv1_1 sees x_c = u - mean_c (nst_job_set_color)

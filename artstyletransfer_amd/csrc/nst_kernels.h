@@ -364,6 +364,10 @@ struct LevelLossInputs {
     float tmp_gamma;
     double tmp_n;
     float* tmp_out;
+    // MRF term (nst_level_set_patches), a level's own: the six unweighted mrf_i by map index as the forward half left them
+    // (nullptr: the level has no term and its row is what it is without it), and the weights (0: the map has no term)
+    float* mrf_vals;
+    float mrf_w[6];
 };
 struct LossAssembly {
     LevelLossInputs lv[8];
@@ -483,6 +487,41 @@ struct MomentFoldItem {
 };
 struct MomentFoldBatch { MomentFoldItem it[NST_GRAM_BATCH_MAX]; int n; };
 hipError_t launch_moment_fold(const MomentFoldBatch& b, hipStream_t stream);
+
+// patch_match.hip: the MRF style term (include/nst_hip.h has the definition) --------------------------------------------
+// The dictionary of one style map: the 3x3xC patches of fs (NHWC, hs x ws x C) centred at (1 + a stride, 1 + b stride), entry
+// j = a nb + b, m = na nb of them.  pm_dict_geometry fills the integers (false: a map below 3x3, a stride outside 1..8, a C
+// other than 64 / 128 / 256 / 512, or more than 2^30 entries); launch_pm_prepare writes the three buffers: the absmax record of
+// fs (NST_AMAX_SLOTS words), rq (32 pm_dict_tiles(m) floats: rq_j, zeros behind entry m) and the packed operand
+// (pm_packed_bytes(m, C) bytes: both fp16 pieces of every entry in the lane order of the search kernel's row operand - nine
+// times the entries' share of the map).
+struct PatchDict {
+    const float* fs; int hs, ws, C, stride, na, nb, m;
+    const unsigned* amax; const float* rq; const void* packed;
+};
+hipError_t pm_init_device();     // raises the dynamic-LDS limit of the search kernels: once per device, before the first launch there
+__host__ __device__ inline int pm_dict_tiles(int m) { return (m + 31) / 32; }
+size_t pm_packed_bytes(int m, int C);
+bool pm_dict_geometry(int hs, int ws, int C, int stride, PatchDict* d);
+hipError_t launch_pm_prepare(const PatchDict& d, double epsilon, unsigned* amax, float* rq, void* packed, hipStream_t stream);
+// The search: nn and score of every 3x3 patch of f (NHWC, h x w x C; amax_f: its absmax record) against the dictionary.  keys:
+// (h - 2)(w - 2) 64-bit words of scratch, which the launch clears and the kernel raises by atomicMax; idx / score (nullable):
+// what the keys decode to.  (tiles_x, tiles_y, cshift: the launcher's.)
+struct PatchSearch {
+    const float* f; int h, w, C; const unsigned* amax_f;
+    PatchDict d;
+    unsigned long long* keys;
+    int tiles_x, tiles_y, cshift;
+};
+hipError_t launch_pm_search(const PatchSearch& p, int* idx, float* score, hipStream_t stream);
+// Value and gradient at fixed idx (d.fs and the integers of d are read; entries outside [0, m) are clamped).  The value in two
+// ordered stages: PM_VALUE_BLOCKS double partials of sum_i |P_i - Q_idx(i)|^2, then out = (float)(their sum / denom).  The
+// gradient in gather form: out (NHWC, the map's shape) = coef sum_taps (F - Fs), written or (accumulate) added.
+constexpr int PM_VALUE_BLOCKS = 256;
+struct PatchTerm { const float* f; int h, w; const int* idx; PatchDict d; };
+hipError_t launch_pm_value_partials(const PatchTerm& t, double* partial, hipStream_t stream);
+hipError_t launch_pm_value(const double* partial, double denom, float* out, hipStream_t stream);
+hipError_t launch_pm_grad(const PatchTerm& t, float coef, float* out, int accumulate, hipStream_t stream);
 
 // gram_guided.hip: spatial control (guided Gram matrices; include/nst_hip.h has the definitions) ---------------------
 constexpr int NST_MAX_REGIONS_K = 4;

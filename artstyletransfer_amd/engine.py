@@ -18,6 +18,7 @@ from . import moment_modes as _mom
 from . import laplacian_modes as _lap
 from . import matting_modes as _mat
 from . import flow_modes as _flow
+from . import mrf_modes as _mrf
 from ._lib import NST_LOSS_ROW, NstError, StepInfo
 
 TAP_CHANNELS = (64, 128, 256, 512, 512, 512)
@@ -562,6 +563,94 @@ class StyleEngine:
         _lib.check(self.ctx, self.lib.nst_job_temporal_losses(self.ctx, _ptr(out), _stream(self.device)),
                    "nst_job_temporal_losses")
         return out
+
+    # ---- the MRF style term (nst_level_set_patches; patch_match.py is the driver) ---------------------------
+    def set_patches(self, level: int, style: Optional[torch.Tensor], weights=None, stride: int = 1,
+                    epsilon: float = _mrf.DEFAULT_EPSILON) -> None:
+        """The MRF term of one level (nst_level_set_patches; Li & Wand 2016): the level total gains sum_i w_i mrf_i, mrf_i
+        the mean squared distance of the 3x3 patches of map i to their nearest style patch.  style: the level's style image,
+        a device float32 (C,hs,ws) tensor (any leading ones; C = 3, or 1 in luminance mode), which is run through the
+        network and whose weighted maps are kept; weights: as mrf_modes.normalize_weights takes them.  Data of the job, not
+        a setting: configure(), set_taps, set_pooling and set_color drop it.  style None or zero weights clear the level's
+        term."""
+        setting = None if style is None else _mrf.normalize_mrf(weights, stride, epsilon, None, self.taps[1])
+        if setting is None:
+            _lib.check(self.ctx, self.lib.nst_level_set_patches(self.ctx, int(level), None, 0, 0, None, 1, _mrf.DEFAULT_EPSILON,
+                                                                _stream(self.device)), "nst_level_set_patches")
+            return
+        w, stride, eps, _ = setting
+        ch = self.channels
+        if style.dim() < 3 or style.numel() != ch * style.shape[-2] * style.shape[-1]:
+            raise NstError(f"the style image of level {level} must have shape ({ch},hs,ws), got {tuple(style.shape)}")
+        style = style.contiguous()
+        _chk_dev(style, self.device)
+        _lib.check(self.ctx, self.lib.nst_level_set_patches(self.ctx, int(level), _ptr(style), int(style.shape[-2]), int(style.shape[-1]),
+                                                            (C.c_float * 6)(*w), stride, eps, _stream(self.device)),
+                   "nst_level_set_patches")
+
+    def clear_patches(self, level: Optional[int] = None) -> None:
+        """No MRF term on one level, or (None) on any configured level."""
+        for l in (range(self.levels) if level is None else (level,)):
+            self.set_patches(l, None)
+
+    def patches_setting(self, level: int):
+        """(weights (6,), stride, epsilon) of a level (nst_level_patches), or None when the level has no term."""
+        w, st, eps = (C.c_float * 6)(), C.c_int(), C.c_double()
+        _lib.check(self.ctx, self.lib.nst_level_patches(self.ctx, int(level), w, C.byref(st), C.byref(eps)), "nst_level_patches")
+        ws = tuple(float(v) for v in w)
+        return None if all(v == 0.0 for v in ws) else (ws, st.value, eps.value)
+
+    def patch_losses(self) -> torch.Tensor:
+        """(levels, 6) device tensor: the unweighted mrf_i of the last closure by map index (nst_job_patch_losses); zeros for
+        maps without the term and levels outside the last level mask."""
+        out = torch.empty((self.levels, 6), dtype=torch.float32, device=self.device)
+        _lib.check(self.ctx, self.lib.nst_job_patch_losses(self.ctx, _ptr(out), _stream(self.device)), "nst_job_patch_losses")
+        return out
+
+    def patch_matches(self, level: int, map: int) -> torch.Tensor:
+        """(h-2, w-2) int32 device tensor: the nearest style patch of every patch of map index `map` of a level, as the last
+        closure found it (nst_level_patch_matches)."""
+        h, w = self.level_shape(level)
+        mh, mw = h >> TAP_SCALE[map], w >> TAP_SCALE[map]
+        out = torch.empty((mh - 2, mw - 2), dtype=torch.int32, device=self.device)
+        _lib.check(self.ctx, self.lib.nst_level_patch_matches(self.ctx, int(level), int(map), _ptr(out), _stream(self.device)),
+                   "nst_level_patch_matches")
+        return out
+
+    def patch_match(self, f: torch.Tensor, fs: torch.Tensor, stride: int = 1, epsilon: float = _mrf.DEFAULT_EPSILON):
+        """The match alone (nst_patch_match): f (h,w,C) and fs (hs,ws,C) device float32 maps in NHWC, C = 64, 128, 256 or
+        512 -> (nn (h-2,w-2) int32, score (h-2,w-2) float32)."""
+        stride, eps = _mrf.check_stride(stride), _mrf.check_epsilon(epsilon)
+        _chk_dev(f, self.device)
+        _chk_dev(fs, self.device)
+        if f.dim() != 3 or fs.dim() != 3 or f.shape[2] != fs.shape[2]:
+            raise NstError("f and fs must be (h,w,C) and (hs,ws,C) with the same C")
+        h, w, c = f.shape
+        idx = torch.empty((h - 2, w - 2), dtype=torch.int32, device=self.device)
+        score = torch.empty((h - 2, w - 2), dtype=torch.float32, device=self.device)
+        _lib.check(self.ctx, self.lib.nst_patch_match(self.ctx, _ptr(f), h, w, c, _ptr(fs), fs.shape[0], fs.shape[1], stride, eps,
+                                                      _ptr(idx), _ptr(score), _stream(self.device)), "nst_patch_match")
+        return idx, score
+
+    def patch_term(self, f: torch.Tensor, fs: torch.Tensor, idx: torch.Tensor, stride: int = 1, coef: Optional[float] = None,
+                   want_grad: bool = True):
+        """Value and gradient alone at the given matches (nst_patch_term): mrf (device scalar) and, with want_grad, the
+        (h,w,C) gradient under `coef` (None: 2 / (9 C n), the gradient of mrf itself)."""
+        stride = _mrf.check_stride(stride)
+        _chk_dev(f, self.device)
+        _chk_dev(fs, self.device)
+        if f.dim() != 3 or fs.dim() != 3 or f.shape[2] != fs.shape[2]:
+            raise NstError("f and fs must be (h,w,C) and (hs,ws,C) with the same C")
+        h, w, c = f.shape
+        if not (idx.is_cuda and idx.dtype == torch.int32 and idx.is_contiguous() and idx.numel() == (h - 2) * (w - 2)):
+            raise NstError(f"idx must be a contiguous int32 CUDA tensor of {(h - 2) * (w - 2)} entries")
+        if coef is None:
+            coef = 2.0 / (9.0 * c * (h - 2) * (w - 2))
+        val = torch.empty(1, dtype=torch.float32, device=self.device)
+        grad = torch.empty_like(f) if want_grad else None
+        _lib.check(self.ctx, self.lib.nst_patch_term(self.ctx, _ptr(f), h, w, c, _ptr(fs), fs.shape[0], fs.shape[1], stride, _ptr(idx),
+                                                     float(coef), _ptr(val), _ptr(grad), _stream(self.device)), "nst_patch_term")
+        return (val, grad) if want_grad else val
 
     def closure(self, x: torch.Tensor, cw: float, sw: float, tvw: float,
                 grad: Optional[torch.Tensor] = None, losses: Optional[torch.Tensor] = None):
@@ -1302,6 +1391,7 @@ class PixelOptimizer:
         _mom.check_exclusive(getattr(e, "moment_loss", None), stripes=True)
         if any(e.anchor(l)[0] > 0 for l in range(e.levels)):
             raise ValueError("a temporal anchor cannot be combined with stripe sharding (clear_anchor())")
+        _mrf.check_exclusive(next((st for st in (e.patches_setting(l) for l in range(e.levels)) if st is not None), None), stripes=True)
         contents = list(content_t) if isinstance(content_t, (list, tuple)) else [content_t]
         styles = list(style_t) if isinstance(style_t, (list, tuple)) else [style_t]
         if blend is not None and styles and isinstance(styles[0], torch.Tensor):

@@ -1,0 +1,148 @@
+"""The MRF style term: every 3x3 patch of a feature map pulled towards its nearest neighbour among the style's patches of
+the same map - Li & Wand, "Combining Markov Random Fields and Convolutional Neural Networks for Image Synthesis" (CVPR
+2016), the loss of CNNMRF and neural-doodle; see nst_level_set_patches in include/nst_hip.h.  The one normaliser of the
+term (neural_style_transfer_mrf(), NeuralStyleTransfer.set_patch_match, StyleEngine.set_patches), kept free of torch:
+everything here raises ValueError before any GPU work."""
+import math
+import numbers
+
+from .taps import DEFAULT_STYLE_INDICES, NUM_MAPS, map_index, map_index_texts
+
+_MAP_TEXTS = map_index_texts("mrf_weight")
+DEFAULT_EPSILON = 1e-5
+DEFAULT_STRIDE = 1
+MAX_STRIDE = 8
+LI_WAND_MAPS = (2, 3)           # relu3_1 and relu4_1: the layers of the paper
+MAP_SCALE = (0, 1, 2, 3, 3, 4)  # log2 of the spatial divisor of each map
+MIN_MAP = 3                     # a map below 3x3 has no patch
+MAX_LEVELS = 8
+
+
+def _weight(v, what):
+    if isinstance(v, bool) or not isinstance(v, numbers.Real):
+        raise ValueError(f"{what} must be a finite number >= 0, not {v!r}")
+    w = float(v)
+    if not math.isfinite(w) or w < 0.0:
+        raise ValueError(f"{what} must be a finite number >= 0, not {v!r}")
+    return w
+
+
+def check_epsilon(epsilon=DEFAULT_EPSILON):
+    if isinstance(epsilon, bool) or not isinstance(epsilon, numbers.Real):
+        raise ValueError(f"mrf_epsilon must be a finite number > 0, not {epsilon!r}")
+    e = float(epsilon)
+    if not math.isfinite(e) or not e > 0.0:
+        raise ValueError(f"mrf_epsilon must be a finite number > 0, not {epsilon!r}")
+    return e
+
+
+def check_stride(stride=DEFAULT_STRIDE):
+    if isinstance(stride, bool) or not isinstance(stride, numbers.Integral) or not 1 <= int(stride) <= MAX_STRIDE:
+        raise ValueError(f"mrf_stride must be an integer 1..{MAX_STRIDE}, not {stride!r}")
+    return int(stride)
+
+
+def normalize_weights(value=None, style_indices=None, use_relu=None):
+    """Six weights >= 0 by map index of Vgg19.layer_names.  `value`: None or 0 (zeros); a number (that weight on those of
+    relu3_1 and relu4_1 - indices 2 and 3, Li & Wand's layers - that are style maps of the job; an error when there are
+    none); a sequence of six numbers; or a dict {map index or name: number} (the rest 0).  `style_indices`: the job's style
+    maps (None: the reference's 0, 1, 2, 3, 5 for a number, and a sequence or a dict is not checked against it);
+    `use_relu`: the flavour whose map names a dict may use (None: either).
+    ValueError for a negative or non-finite number, a wrong length, an unknown map, or a positive weight on a map that is
+    not a style map of the job."""
+    known = style_indices is not None
+    style = sorted(DEFAULT_STYLE_INDICES) if not known else sorted({int(i) for i in style_indices})
+    if value is None:
+        return (0.0,) * NUM_MAPS
+    if isinstance(value, (str, bytes, set, frozenset)):
+        raise ValueError(f"mrf_weight: expected a number, {NUM_MAPS} numbers or a dict, got {value!r}")
+    if isinstance(value, (bool, numbers.Number)):
+        w = _weight(value, "mrf_weight")
+        if w == 0.0:
+            return (0.0,) * NUM_MAPS
+        on = [i for i in LI_WAND_MAPS if i in style]
+        if not on:
+            raise ValueError(f"mrf_weight: neither relu3_1 nor relu4_1 (indices 2 and 3) is a style map of the job {style}; "
+                             f"give the weights by map")
+        return tuple(w if i in on else 0.0 for i in range(NUM_MAPS))
+    if isinstance(value, dict):
+        ws = [0.0] * NUM_MAPS
+        for key, v in value.items():
+            ws[map_index(key, use_relu, _MAP_TEXTS)] = _weight(v, f"mrf_weight of {key!r}")
+    else:
+        try:
+            items = list(value)
+        except TypeError:
+            raise ValueError(f"mrf_weight: expected a number, {NUM_MAPS} numbers or a dict, got {value!r}") from None
+        if len(items) != NUM_MAPS:
+            raise ValueError(f"mrf_weight: expected {NUM_MAPS} numbers (one per feature map), got {len(items)}")
+        ws = [_weight(v, f"mrf_weight entry {i}") for i, v in enumerate(items)]
+    for i, w in enumerate(ws):
+        if known and w > 0.0 and i not in style:
+            raise ValueError(f"mrf_weight: map {i} has a positive weight but is not a style map of the job {style}")
+    return tuple(ws)
+
+
+def normalize_levels(levels=None, levels_num=None):
+    """None (every level), or the sorted tuple of distinct level indices, as StyleEngine numbers them (0 = the full
+    resolution).  `levels_num` (None: not checked beyond 0..7): the job's number of levels."""
+    if levels is None:
+        return None
+    if isinstance(levels, (str, bytes, dict)) or isinstance(levels, (bool, numbers.Number)):
+        raise ValueError(f"mrf_levels: expected None or a collection of level indices, got {levels!r}")
+    try:
+        items = list(levels)
+    except TypeError:
+        raise ValueError(f"mrf_levels: expected None or a collection of level indices, got {levels!r}") from None
+    top = MAX_LEVELS if levels_num is None else int(levels_num)
+    out = set()
+    for v in items:
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not 0 <= int(v) < top:
+            raise ValueError(f"mrf_levels: {v!r} is not a level index 0..{top - 1}")
+        out.add(int(v))
+    if not out:
+        raise ValueError("mrf_levels: the collection is empty (None means every level)")
+    return tuple(sorted(out))
+
+
+def normalize_mrf(mrf_weight=None, mrf_stride=DEFAULT_STRIDE, mrf_epsilon=DEFAULT_EPSILON, mrf_levels=None, style_indices=None,
+                  use_relu=None, levels_num=None):
+    """(weights, stride, epsilon, levels) - six weights by map index, the style stride, epsilon and the levels (None: all) -
+    or None when the term is off (None, 0, all zeros).  Everything is validated, the off setting included."""
+    stride = check_stride(mrf_stride)
+    eps = check_epsilon(mrf_epsilon)
+    levels = normalize_levels(mrf_levels, levels_num)
+    w = normalize_weights(mrf_weight, style_indices, use_relu)
+    if all(v == 0.0 for v in w):
+        return None
+    return w, stride, eps, levels
+
+
+def check_exclusive(setting, regions=None, stripes: bool = False, extra_styles=None) -> None:
+    """The term does not combine with several style images (the union of dictionaries is a follow-up), with spatial
+    control (guided levels) or with stripe sharding."""
+    if setting is None:
+        return
+    if extra_styles:
+        raise ValueError("mrf_weight cannot be combined with extra_styles")
+    if regions is not None:
+        raise ValueError("mrf_weight cannot be combined with content_regions / style_regions")
+    if stripes:
+        raise ValueError("mrf_weight cannot be combined with stripe sharding")
+
+
+def check_sizes(setting, level_shapes, style_shapes) -> None:
+    """Every weighted map is at least 3x3 on every chosen level, on the level image and on the level's style image.
+    `level_shapes`, `style_shapes`: (h, w) per level, in StyleEngine's numbering."""
+    if setting is None:
+        return
+    w, _, _, levels = setting
+    for lv in (range(len(level_shapes)) if levels is None else levels):
+        if lv >= len(level_shapes):
+            raise ValueError(f"mrf_levels: level {lv} is outside the job's {len(level_shapes)} levels")
+        for i, wi in enumerate(w):
+            if not wi > 0.0:
+                continue
+            for what, (h, ww) in (("image", level_shapes[lv]), ("style image", style_shapes[lv])):
+                if (int(h) >> MAP_SCALE[i]) < MIN_MAP or (int(ww) >> MAP_SCALE[i]) < MIN_MAP:
+                    raise ValueError(f"mrf_weight: map {i} of the {what} of level {lv} ({h}x{ww}) pools below {MIN_MAP}x{MIN_MAP}")

@@ -26,6 +26,7 @@ from . import gram_modes as _gram
 from . import laplacian_modes as _lap
 from . import matting_modes as _mat
 from . import moment_modes as _mom
+from . import mrf_modes as _mrf
 
 # ImageNet statistics (reference :22-23)
 IMAGENET_MEAN_255 = [123.675, 116.28, 103.53]
@@ -217,6 +218,7 @@ class _DeviceJob:
                 else:
                     content_t = prepared
                     style_t = lambda img, k=0: prepared(img)                                      # noqa: E731
+                self.style_levels = [(lambda img=s_img: style_t(img)) for s_img in style_imgs]     # set_patch_match: the images the targets are made from
                 for lvl, (c_img, s_img) in enumerate(zip(content_imgs, style_imgs)):
                     if tuple(c_img.shape[:2]) != engine.level_shape(lvl):
                         raise ValueError(f"content level {lvl} is {tuple(c_img.shape[:2])}, expected {engine.level_shape(lvl)}")
@@ -245,6 +247,14 @@ class _DeviceJob:
             for lvl, (a, c) in enumerate(zip(anchor_levels, weight_levels)):
                 if a is not None:
                     self.engine.set_anchor(lvl, a, c, gamma=gamma)
+
+    def set_patch_match(self, weights, stride, epsilon, levels):
+        """The MRF term of the levels (StyleEngine.set_patches; `levels` None: every level): each level gets the style level
+        image its targets were made from - recoloured under "histogram", the matched luminance plane under "luminance"."""
+        with torch.cuda.device(self.dev), torch.cuda.stream(self.job_stream):
+            for lvl, style_of in enumerate(self.style_levels):
+                if levels is None or lvl in levels:
+                    self.engine.set_patches(lvl, style_of(), weights, stride, epsilon)
 
     def step(self, cw, sw, tvw):
         """One optimizer.step(closure) (nst_opt_step).  Runs on a pool thread, whose current stream is its own."""
@@ -321,6 +331,7 @@ class NeuralStyleTransfer:
         self.__optimizer_name = optimizer_name
         self.settings = _job.JobSettings()       # the optional settings of the next `process`: the set_* below update it
         self.__anchor = None                     # set_anchor: data of the next `process`, not a setting
+        self.__patches = None                    # set_patch_match: likewise
 
     def set_feature_maps(self, content_layer=None, style_layers=None, use_relu=True):
         """Extension: the feature maps the losses of the next `process` read - a content map and a set of style maps of
@@ -431,6 +442,21 @@ class NeuralStyleTransfer:
             raise ValueError(f"{len(anchors)} anchor levels but {len(weights)} weight levels")
         self.__anchor = (anchors, weights, g)
 
+    def set_patch_match(self, weights=None, stride=_mrf.DEFAULT_STRIDE, epsilon=_mrf.DEFAULT_EPSILON, levels=None):
+        """Extension: the MRF style term of Li & Wand 2016 (CNNMRF, neural-doodle) in the next `process`: per pyramid level
+        sum_i w_i mrf_i, mrf_i the mean squared distance of the 3x3 patches of map i from their nearest neighbours - by
+        normalised cross-correlation - among the 3x3 patches of the same map of the level's style image (nst_level_set_patches
+        in include/nst_hip.h has the definition).  `weights`: None or 0 (off), a number (that weight on those of relu3_1 and
+        relu4_1 that are style maps of the job), six numbers by map index of Vgg19.layer_names, or a dict {map index or name:
+        number}; `stride`: the stride of the style patches, 1..8 (the search costs 1 / stride^2); `epsilon` > 0; `levels`:
+        None for every level, or the level indices that carry the term (0 = the full resolution).  Data of one job, like the
+        anchor - not one of `settings`.  ValueError for a malformed setting and - in `process`, where the style set and the
+        level sizes are known - for a positive weight on a map that is not a style map, a weighted map that pools below 3x3
+        on a chosen level (on either image), or the term together with regions or several style images."""
+        _mrf.normalize_mrf(weights, stride, epsilon, levels)          # (malformed: here and now; the style set comes with `process`)
+        off = weights is None or (isinstance(weights, (int, float)) and not isinstance(weights, bool) and weights == 0)
+        self.__patches = None if off else (weights, stride, epsilon, levels)
+
     async def process(self, content_imgs, init_img, lr_start, iters_num, content_weight, style_weight, tv_weight,
                       init_img_name):
         # validates the model name exactly as the reference does (ValueError for anything but vgg19)
@@ -456,12 +482,24 @@ class NeuralStyleTransfer:
             if "blend" in resolved:
                 extra, blend = resolved["blend"]
                 resolved["blend"] = ([device_image.recolor_histogram(setup, content_top, [up(s) for s in lv]) for lv in extra], blend)
+        patches = None
+        if self.__patches is not None:
+            style_set, use_relu = resolved["taps"][1:] if "taps" in resolved else (_taps.DEFAULT_STYLE_INDICES, True)
+            patches = _mrf.normalize_mrf(*self.__patches, style_indices=style_set, use_relu=use_relu, levels_num=len(content_imgs))
+            _mrf.check_exclusive(patches, regions=resolved.get("regions"), extra_styles=resolved.get("blend"))
+            _mrf.check_sizes(patches, [tuple(c.shape[:2]) for c in content_imgs], [tuple(s.shape[:2]) for s in style_imgs])
         if self.__anchor is not None and len(self.__anchor[0]) != len(content_imgs):
             raise ValueError(f"{len(self.__anchor[0])} anchor levels for a job of {len(content_imgs)} levels")
         job = _make_job(self.__device, self.__optimizer_name, style_imgs, content_imgs, init_img, lr_start, **resolved)
         if self.__anchor is not None:        # (data of the job, handed over once the job exists: not one of its settings)
             try:
                 job.set_anchor(*self.__anchor)
+            except BaseException:
+                job.close()
+                raise
+        if patches is not None:              # (likewise)
+            try:
+                job.set_patch_match(*patches)
             except BaseException:
                 job.close()
                 raise
@@ -565,16 +603,23 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
 
 def _transfer_from(content_n_style, content_weight, style_weight, tv_weight, optimizer, model, init_method, iters_num, levels_num,
                    noise_factor, noise_levels, noise_levels_central_amplitude, noise_levels_peripheral_amplitude,
-                   noise_levels_dispersion, *, device=None, start=None, **keywords):
+                   noise_levels_dispersion, *, device=None, start=None, patches=None, **keywords):
     """The settings validation of neural_style_transfer() (`keywords`: its keyword-only parameters), here and now - before any
-    GPU work, ValueError - and then the job as an async generator, from the `init_method` image or from `start` (_transfer)."""
+    GPU work, ValueError - and then the job as an async generator, from the `init_method` image or from `start` (_transfer).
+    `patches` (patch_match.py): None, or the arguments of NeuralStyleTransfer.set_patch_match, validated here too."""
     settings = _job.JobSettings(for_job=True, **keywords)
 
     def level_shapes(img):      # (the level sizes follow from the image size: top level first)
         ih, iw = np.shape(img)[:2]
         return [host_image.level_size(ih, iw, lvl) for lvl in range(max(levels_num - 1, 0), -1, -1)]
 
-    settings.resolve(lambda: level_shapes(content_n_style.content[1]), lambda: level_shapes(content_n_style.style[1]))
+    resolved = settings.resolve(lambda: level_shapes(content_n_style.content[1]), lambda: level_shapes(content_n_style.style[1]))
+    if patches is not None:
+        style_set, use_relu = resolved["taps"][1:] if "taps" in resolved else (_taps.DEFAULT_STYLE_INDICES, True)
+        checked = _mrf.normalize_mrf(*patches, style_indices=style_set, use_relu=use_relu, levels_num=max(levels_num, 1))
+        _mrf.check_exclusive(checked, regions=resolved.get("regions"), extra_styles=keywords.get("extra_styles"))
+        _mrf.check_sizes(checked, level_shapes(content_n_style.content[1]), level_shapes(content_n_style.style[1]))
+        patches = patches if checked is not None else None
     extra_styles = keywords.get("extra_styles")
     extra_styles = list(extra_styles) if extra_styles is not None else []
     for img in extra_styles:
@@ -583,16 +628,17 @@ def _transfer_from(content_n_style, content_weight, style_weight, tv_weight, opt
     return _transfer(content_n_style, content_weight, style_weight, tv_weight, optimizer, model, init_method, iters_num, levels_num,
                      noise_factor, noise_levels, noise_levels_central_amplitude, noise_levels_peripheral_amplitude,
                      noise_levels_dispersion, device, settings, keywords.get("preserve_color"), extra_styles,
-                     keywords.get("style_blend"), start)
+                     keywords.get("style_blend"), start, patches)
 
 
 async def _transfer(content_n_style, content_weight, style_weight, tv_weight, optimizer, model, init_method, iters_num, levels_num,
                     noise_factor, noise_levels, noise_levels_central_amplitude, noise_levels_peripheral_amplitude,
-                    noise_levels_dispersion, device, settings, preserve_color, extra_styles, style_blend, start=None):
+                    noise_levels_dispersion, device, settings, preserve_color, extra_styles, style_blend, start=None, patches=None):
     """neural_style_transfer() below its settings validation: `settings` is its validated JobSettings, `extra_styles` its
     checked list.  `start` (video.py): None, or a callable (setup engine, level-0 (h, w)) -> (start image: a device HWC
     tensor the job starts from in place of the `init_method` image, anchor levels, weight levels, gamma) - the arguments of
-    NeuralStyleTransfer.set_anchor - called once the level sizes are known."""
+    NeuralStyleTransfer.set_anchor - called once the level sizes are known.  `patches` (patch_match.py): None, or the checked
+    arguments of NeuralStyleTransfer.set_patch_match."""
     if device is None:
         if not torch.cuda.is_available():
             raise RuntimeError("no GPU visible: the HIP style-transfer engine has no CPU path")
@@ -627,6 +673,8 @@ async def _transfer(content_n_style, content_weight, style_weight, tv_weight, op
     nst = NeuralStyleTransfer(device, model, style_levels, optimizer)
     if anchor is not None:
         nst.set_anchor(*anchor)
+    if patches is not None:
+        nst.set_patch_match(*patches)
     # (the extra styles as their pyramids; "histogram" has recoloured the style levels above)
     settings.update(extra_styles=extra_levels, style_blend=style_blend if extra_levels else None)
     if preserve_color == "histogram":

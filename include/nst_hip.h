@@ -816,6 +816,66 @@ int nst_matting_loss(nst_ctx* ctx, const float* y, const float* guide, int C, in
 int nst_anchor_loss(nst_ctx* ctx, const float* y, const float* anchor, const float* weights /* nullable */, int C, int h, int w,
                     float* value, float* grad /* nullable, overwritten */, void* stream);
 int nst_anchor_geometry(int* blocks, int* block_elems);
+
+/* ---- The MRF style term (Li & Wand, CVPR 2016: CNNMRF, neural-doodle) --------------------------------------------------
+ * Every 3x3 patch of a tapped map is pulled towards its nearest neighbour among the 3x3 patches of the same map of the
+ * style.  For one pyramid level and one tapped map of index i in Vgg19.layer_names:
+ *   F  = the map of the level image, NHWC, h x w x C;  Fs = the same map of the level's style image, hs x ws x C, through
+ *        the network the job uses (its tap flavour, its pooling, its colour mode).
+ * Patches.  A patch is the 3x3xC block around a centre (y, x).  Image patches: 1 <= y <= h-2, 1 <= x <= w-2, n = (h-2)(w-2)
+ *   of them in row-major order.
+ * Dictionary.  Style centres (1 + a s, 1 + b s), a, b >= 0 integers, as long as they stay <= hs-2 and <= ws-2; s = the style
+ *   stride, 1..8.  Entry j = a nb + b; m = na nb entries, na = (hs-3)/s + 1 in integer division, nb likewise.
+ * Match.  score(i, j) = <P_i, Q_j> rq_j, rq_j = (float)(1 / sqrt(|Q_j|^2 + epsilon)), the norm summed in double, epsilon > 0
+ *   (default 1e-5).  nn(i) = the LOWEST j among the maximal scores.  |P_i| does not change the arg-max and is not formed
+ *   (Li & Wand's normalised cross-correlation).  The products run in the f16x2 arithmetic of the convolutions: each operand
+ *   cut into two scaled fp16 pieces, three fp16 MFMAs per product block, fp32 accumulation.
+ * Value.  mrf_i = (float)((1 / (9 C n)) sum_i |P_i - Q_nn(i)|^2), differences and squares formed in double from the fp32
+ *   maps, summed in a fixed two-stage order (not |P|^2 - 2 <P,Q> + |Q|^2).
+ * Loss row.  A level with the term has the total (... + gamma tmp) + sum_i w_i mrf_i: added after the temporal term, in
+ *   ascending map order, every product and sum rounded.  NST_LOSS_ROW stays 4.  The weights w_i are the term's own:
+ *   style_weight does not scale it (as with the moment term).
+ * Gradient, nn held fixed.  dF(y,x,c) = coef_i sum over dy, dx in {-1,0,1} whose patch centre (y-dy, x-dx) exists of
+ *   (F(y,x,c) - Fs(cy+dy, cx+dx, c)), (cy, cx) the centre of Q_nn of that patch, coef_i = (float)((double)w_i 2 / (9 C n)).
+ *   Gather form, taps in the order dy outer, dx inner, ascending; fp32, one rounding per operation.  It reaches the network
+ *   as the addend of the launch below the map: on top of the content gradient when the map is the content map too, beside
+ *   the Gram second source and its row bias when the map carries those.
+ * Between the closure halves the forward half keeps nn (int32 per patch) and the value; the backward half reads nn and the
+ *   maps.  No float atomic takes part: across workgroups the search combines by an integer atomicMax on a 64-bit key (the
+ *   order-preserving bit pattern of the score above ~j), so a closure with the term is bitwise reproducible.
+ *
+ * nst_level_set_patches: the term of one level, data of one job like the anchor (not a setting).  style = device (C,hs,ws)
+ *   image in the job's colour mode (C = 3, or 1 under NST_COLOR_LUMINANCE), NULL: clear the level's term.  weights[6] by
+ *   map index.  The call runs the style image through the network up to the deepest weighted map, keeps the weighted maps,
+ *   prepares their dictionaries (rq, the absmax record, and the PACKED operand: both fp16 pieces of every entry in the
+ *   search kernel's operand order, nine times the entries' share of the map, counted by nst_ctx_bytes) and allocates nn
+ *   and the value partials: a closure allocates nothing.  Life cycle of nst_level_set_anchor: waits for the context's
+ *   work; drops a captured graph, an L-BFGS memo and a pending backward half; a refusal changes nothing;
+ *   nst_job_configure drops the term with the levels; nst_job_set_taps, nst_job_set_pooling and nst_job_set_color drop it
+ *   (the maps are the other network's).
+ *   NST_E_ARG: level out of range; negative or non-finite weights or epsilon (epsilon must be > 0); stride outside 1..8; a
+ *   positive weight on a map that is not a style map of the job; a map or style map below 3x3.
+ *   NST_E_STATE: no configured job; an arithmetic mode other than f16x2; a guided level (nst_level_set_guidance on a level
+ *   with the term refuses likewise); a context with use_graph (the term's launches are not captured).
+ *   The stripe closure returns NST_E_STATE while its level carries the term.
+ * nst_level_patches: the level's setting (all-zero weights: no term).
+ * nst_job_patch_losses: out = device, levels x 6: the unweighted mrf_i of the last closure by map index (zeros: maps
+ *   without the term and levels outside the last level mask).
+ * nst_level_patch_matches: idx_out = device int32, (h-2)(w-2) of the map: the nn of the last closure.  NST_E_STATE: the map
+ *   carries no term on the level.  Both readers of a level return NST_E_ARG for a level out of range.
+ * nst_patch_match: the match alone.  f = device NHWC (h,w,C), fs = device NHWC (hs,ws,C), C = 64, 128, 256 or 512, both
+ *   maps at least 3x3; idx_out (int32, n) and score_out (float, n), either nullable.  Reads no job state.  Synchronous.
+ * nst_patch_term: value and gradient alone at the given idx (entries outside [0, m) are clamped): value_out (device
+ *   scalar, nullable) = mrf; grad_out (nullable, overwritten, NHWC like f) = the gradient with the given coef.  Synchronous. */
+int nst_level_set_patches(nst_ctx* ctx, int level, const float* style /* device (C,hs,ws), or NULL: clear */, int hs, int ws,
+                          const float* weights /* 6, by map index */, int stride, double epsilon, void* stream);
+int nst_level_patches(const nst_ctx* ctx, int level, float* weights /* 6 */, int* stride, double* epsilon);
+int nst_job_patch_losses(nst_ctx* ctx, float* out /* device, levels x 6 */, void* stream);
+int nst_level_patch_matches(nst_ctx* ctx, int level, int map, int* idx_out /* device */, void* stream);
+int nst_patch_match(nst_ctx* ctx, const float* f, int h, int w, int C, const float* fs, int hs, int ws, int stride, double epsilon,
+                    int* idx_out /* nullable */, float* score_out /* nullable */, void* stream);
+int nst_patch_term(nst_ctx* ctx, const float* f, int h, int w, int C, const float* fs, int hs, int ws, int stride, const int* idx,
+                   float coef, float* value_out /* nullable */, float* grad_out /* nullable */, void* stream);
 int nst_warp_bilinear(nst_ctx* ctx, const float* src, const float* flow, int C, int h, int w, float* out,
                       float* valid /* nullable */, void* stream);
 int nst_flow_weights(nst_ctx* ctx, const float* fwd, const float* bwd, int h, int w, float* out, void* stream);

@@ -1,0 +1,756 @@
+"""GPU: the MRF style term (nst_level_set_patches; Li & Wand 2016) - 3x3 feature patches matched to their nearest style patch.
+1. the decisions of the match alone (nst_patch_match) against fp64, held to torch-fp32's own error of the same cosines;
+2. ties, bitwise: the lowest index of equal scores, all-zero patches and all-zero dictionary entries;
+3. value and gradient alone (nst_patch_term) against fp64 autograd at the device's indices;
+4. the closure under equal decisions - the device's nn handed to the oracle as fixed indices - against the oracle with
+   cpu_ref.level_loss and cpu_ref.LevelTargets replaced by test-local ones that add the term (monkeypatch: no oracle edit),
+   at hip_helpers' standing tolerances, over the paths the term's gradient takes;
+5. closure halves, reproducibility, L-BFGS, level masks; 6. the loss row; 7. a cleared term; 8. life cycle and refusals;
+9. a whole job."""
+import asyncio
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from hip_helpers import (CW, SW, TVW, TERMS, check_rows, closure_vs_oracle_under_equal_decisions, dev, levels as _levels,
+                         oracle_targets, rel_l2, report)
+from oracle import cpu_ref
+from test_hip_gram_shift import _bits, _job, prerelu_vgg19_features
+
+pytestmark = pytest.mark.gpu
+
+EPS = 1e-5
+
+
+# ---- the term restated ---------------------------------------------------------------------------------------------------
+def patches(f):
+    """(n, 9C) rows of the 3x3 patches of a (1,C,h,w) map, centres in row-major order."""
+    return F.unfold(f, 3).squeeze(0).t()
+
+
+def dictionary(fs, stride):
+    """(m, 9C): the style patches whose centres are (1 + a s, 1 + b s), entry a nb + b."""
+    hs, ws = fs.shape[-2:]
+    q = patches(fs).reshape(hs - 2, ws - 2, -1)[::stride, ::stride]
+    return q.reshape(-1, q.shape[-1])
+
+
+def cosines(f, fs, stride, eps=EPS):
+    """(n, m) score(i, j) / |P_i| in f's dtype (|P_i| = 0: the scores themselves, which are zero)."""
+    p, q = patches(f), dictionary(fs, stride)
+    rq = 1.0 / torch.sqrt((q * q).sum(dim=1) + eps)
+    pn = torch.sqrt((p * p).sum(dim=1))
+    return (p @ q.t()) * rq[None, :] / torch.where(pn > 0, pn, torch.ones_like(pn))[:, None]
+
+
+def mrf_value(f, fs, nn, stride):
+    """mrf = (1 / (9 C n)) sum_i |P_i - Q_nn(i)|^2 in f's dtype."""
+    return ((patches(f) - dictionary(fs, stride)[nn.reshape(-1).long()]) ** 2).mean()
+
+
+def feature_like(c, h, w, seed):
+    """A seeded randn * 3, then relu(x - 1), every seventh channel zero: (1,C,h,w)."""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.relu(torch.randn((1, c, h, w), generator=g) * 3.0 - 1.0)
+    x[:, ::7] = 0.0
+    return x.contiguous()
+
+
+def nhwc(x):
+    return dev(x.squeeze(0).permute(1, 2, 0))
+
+
+@pytest.fixture(scope="module")
+def eng(vgg_weights):
+    from artstyletransfer_amd.engine import StyleEngine
+    e = StyleEngine(vgg_weights, 0)
+    yield e
+    e.close()
+
+
+@pytest.fixture(scope="module")
+def eng_per_level(vgg_weights):
+    from artstyletransfer_amd.engine import StyleEngine
+    e = StyleEngine(vgg_weights, 0, batched=False)
+    yield e
+    e.close()
+
+
+# ---- 1. decisions against fp64 ---------------------------------------------------------------------------------------------
+MATCH_SHAPES = [(64, 12, 13, 11, 9, 1), (128, 9, 10, 14, 7, 2), (256, 7, 33, 8, 19, 1), (512, 5, 6, 6, 5, 1), (64, 40, 37, 33, 45, 1),
+                (64, 3, 3, 3, 3, 1)]
+_MATCH_CACHE = {}
+
+
+def _match_case(eng, shape):
+    """(f, fs, fp64 cosines, device nn, device score) of one shape, computed once."""
+    if shape not in _MATCH_CACHE:
+        c, h, w, hs, ws, stride = shape
+        f, fs = feature_like(c, h, w, seed=c + h), feature_like(c, hs, ws, seed=c + hs + 100)
+        cos64 = cosines(f.double(), fs.double(), stride)
+        nn, score = eng.patch_match(nhwc(f), nhwc(fs), stride, EPS)
+        _MATCH_CACHE[shape] = (f, fs, cos64, nn.cpu(), score.cpu())
+    return _MATCH_CACHE[shape]
+
+
+@pytest.mark.parametrize("shape", MATCH_SHAPES)
+def test_match_decisions_vs_fp64(eng, shape):
+    """The fp64 cosine of every device choice is within delta of the fp64 best, delta = 4 x the largest error of a torch-fp32
+    evaluation of the same cosines against fp64 on this input (measured here, never taken from the device); at most 1 % of
+    the patches differ from the fp64 arg-max at all.
+
+    Measured on the GPU (profiles/r20_mrf.txt): no patch differs from the fp64 arg-max on any shape; the device's score is
+    1.4e-8 ... 6.8e-7 (relative to the largest score) from fp64, torch fp32's 7.9e-8 ... 2.0e-7."""
+    c, h, w, hs, ws, stride = shape
+    f, fs, cos64, nn, score = _match_case(eng, shape)
+    cos32 = cosines(f, fs, stride).double()
+    delta = 4.0 * float((cos32 - cos64).abs().max())
+    n, m = cos64.shape
+    assert tuple(nn.shape) == (h - 2, w - 2) and n == (h - 2) * (w - 2) and m == ((hs - 3) // stride + 1) * ((ws - 3) // stride + 1)
+    idx = nn.reshape(-1).long()
+    assert int(idx.min()) >= 0 and int(idx.max()) < m
+    best, arg = cos64.max(dim=1)
+    chosen = cos64.gather(1, idx[:, None]).squeeze(1)
+    differ = float((idx != arg).double().mean())
+    # the device's score against the fp64 score of its own choice
+    p64, q64 = patches(f.double()), dictionary(fs.double(), stride)
+    s64 = (p64 * q64[idx]).sum(dim=1) / torch.sqrt((q64[idx] ** 2).sum(dim=1) + EPS)
+    s32 = (patches(f) * dictionary(fs, stride)[idx]).sum(dim=1) / torch.sqrt((dictionary(fs, stride)[idx] ** 2).sum(dim=1) + EPS)
+    scale = float(s64.abs().max())
+    e_dev, e_32 = float((score.reshape(-1).double() - s64).abs().max()) / scale, float((s32.double() - s64).abs().max()) / scale
+    report(f"mrf match C={c} {h}x{w} vs {hs}x{ws} stride {stride}: n={n} m={m}, delta {delta:.2e}, worst shortfall "
+           f"{float((best - chosen).max()):.2e}, patches off the fp64 arg-max {differ:.2%}; score error / largest score: device "
+           f"{e_dev:.2e}, torch fp32 {e_32:.2e}")
+    assert torch.isfinite(score).all()
+    assert bool((chosen >= best - delta).all()), float((best - chosen).max())
+    assert differ <= 0.01, differ
+
+
+# ---- 2. ties, bitwise ---------------------------------------------------------------------------------------------------------
+def test_ties_pick_the_lowest_index(eng):
+    """A style map tiled from a 4x5 block three times in each direction: entry (a, b) repeats at (a + 4, b + 5), bitwise, so
+    every image patch must pick the member (a % 4, b % 5) of its class; an all-zero image patch picks entry 0; an all-zero
+    dictionary entry has rq = 1 / sqrt(epsilon), score 0 and makes nothing non-finite."""
+    c = 64
+    block = feature_like(c, 4, 5, seed=11)
+    fs = block.repeat(1, 1, 3, 3).contiguous()                    # 12 x 15
+    f = feature_like(c, 9, 11, seed=12)
+    f[:, :, 0:3, 0:3] = 0.0                                       # patch 0 is all zero
+    nn, score = eng.patch_match(nhwc(f), nhwc(fs), 1, EPS)
+    nn, score = nn.cpu().long(), score.cpu()
+    nb = 13
+    a, b = nn // nb, nn % nb
+    assert bool((a < 4).all()) and bool((b < 5).all()), (a.max(), b.max())
+    assert int(nn[0, 0]) == 0 and float(score[0, 0]) == 0.0
+    # the classes are the fp64 ones
+    arg = cosines(f.double(), fs.double(), 1).argmax(dim=1).reshape(nn.shape)
+    same = ((arg // nb) % 4 == a) & ((arg % nb) % 5 == b)
+    assert float(same.double().mean()) >= 0.99
+    # stride 2 breaks the period along neither axis evenly: rows repeat every 2 entries (4 / 2), columns every 5
+    nn2, _ = eng.patch_match(nhwc(f), nhwc(fs), 2, EPS)
+    nn2 = nn2.cpu().long()
+    nb2 = (15 - 3) // 2 + 1
+    assert bool((nn2 // nb2 < 2).all()) and bool((nn2 % nb2 < 5).all())
+    # an all-zero dictionary entry
+    fz = feature_like(c, 6, 7, seed=13)
+    fz[:, :, 0:3, 0:3] = 0.0
+    nn3, score3 = eng.patch_match(nhwc(f), nhwc(fz), 1, EPS)
+    assert torch.isfinite(score3).all() and int(nn3.min()) >= 0 and int(nn3.max()) < 4 * 5
+    only_zero = torch.zeros((1, c, 3, 3))
+    nn4, score4 = eng.patch_match(nhwc(f), nhwc(only_zero), 1, EPS)
+    assert not nn4.cpu().any() and not score4.cpu().any()
+    # run to run, bitwise
+    nn5, score5 = eng.patch_match(nhwc(f), nhwc(fs), 1, EPS)
+    assert torch.equal(nn5.cpu().long(), nn) and np.array_equal(_bits(score5), _bits(score))
+
+
+def test_stand_alone_pieces_refuse_what_they_cannot_read(eng):
+    """The pieces take raw pointers: a view that is not contiguous, another dtype, another rank or unequal channel counts
+    are refused before the call, as is an idx of the wrong size or type."""
+    from artstyletransfer_amd._lib import NstError
+    f, fs = nhwc(feature_like(64, 6, 7, seed=1)), nhwc(feature_like(64, 5, 5, seed=2))
+    idx = torch.zeros((4, 5), dtype=torch.int32, device="cuda:0")
+    view = dev(feature_like(64, 6, 7, seed=1)).squeeze(0).permute(1, 2, 0)            # NHWC strides over CHW memory
+    assert not view.is_contiguous()
+    for bad_f, bad_fs in ((view, fs), (f, fs.double()), (f.unsqueeze(0), fs), (f, nhwc(feature_like(128, 5, 5, seed=2)))):
+        with pytest.raises(NstError):
+            eng.patch_match(bad_f, bad_fs)
+        with pytest.raises(NstError):
+            eng.patch_term(bad_f, bad_fs, idx)
+    for bad_idx in (idx.long(), idx[:, :4].contiguous(), idx.cpu()):
+        with pytest.raises(NstError):
+            eng.patch_term(f, fs, bad_idx)
+    val, grad = eng.patch_term(f, fs, idx)
+    assert torch.isfinite(val).all() and torch.isfinite(grad).all()
+
+
+# ---- 3. value and gradient alone ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("shape", MATCH_SHAPES)
+def test_term_vs_fp64_autograd_at_the_device_indices(eng, shape):
+    """mrf and d mrf / dF at the device's nn against fp64 autograd of the definition: each error at most 4 x that of a
+    torch-fp32 evaluation of the same expression on the same input.
+
+    Measured on the GPU (profiles/r20_mrf.txt): value 1.9e-9 ... 2.8e-8 (torch fp32 7.7e-9 ... 7.6e-8), gradient rel-L2
+    2.9e-8 ... 8.0e-8 (torch fp32 2.9e-8 ... 8.0e-8)."""
+    c, h, w, hs, ws, stride = shape
+    f, fs, _, nn, _ = _match_case(eng, shape)
+    out = {}
+    for name, dt in (("fp64", torch.float64), ("fp32", torch.float32)):
+        x = f.to(dt).clone().requires_grad_(True)
+        v = mrf_value(x, fs.to(dt), nn, stride)
+        v.backward()
+        out[name] = (float(v.detach()), x.grad.detach().double())
+    val, grad = eng.patch_term(nhwc(f), nhwc(fs), dev(nn), stride)
+    val, grad = float(val.cpu()), grad.cpu().permute(2, 0, 1).unsqueeze(0).double()
+    v64, g64 = out["fp64"]
+    e_v, e_v32 = abs(val - v64) / v64, abs(out["fp32"][0] - v64) / v64
+    e_g, e_g32 = rel_l2(grad.numpy(), g64.numpy()), rel_l2(out["fp32"][1].numpy(), g64.numpy())
+    report(f"mrf term C={c} {h}x{w} vs {hs}x{ws} stride {stride}: value rel err device {e_v:.2e} / torch fp32 {e_v32:.2e}, "
+           f"gradient rel-L2 device {e_g:.2e} / torch fp32 {e_g32:.2e}")
+    assert e_v <= 4.0 * e_v32, (e_v, e_v32)
+    assert e_g <= 4.0 * e_g32, (e_g, e_g32)
+
+
+# ---- 4. the closure under equal decisions ------------------------------------------------------------------------------------
+class PatchedOracle:
+    """cpu_ref.level_loss and cpu_ref.LevelTargets with the MRF term at FIXED indices: LevelTargets gains the style's maps and
+    its level number (the order the targets are made in), level_loss calls the original, adds sum_i w_i mrf_i (ascending map
+    order) to the total of a level with the term and returns the same four-entry row.  `nn[level][map]`: the device's
+    patch_matches, which the test hands over before the first evaluation.  The term is in EVERY weighting of a closure - its
+    weights are its own, as on the device.  `log` keeps, per level_loss call, (weighted term, {map: mrf_i})."""
+
+    def __init__(self, monkeypatch, w, stride=1, levels=None):
+        self.w, self.stride, self.levels = tuple(w), stride, levels
+        self.level_loss0, self.targets0 = cpu_ref.level_loss, cpu_ref.LevelTargets
+        self.nn, self.log, self.made = {}, [], 0
+        monkeypatch.setattr(cpu_ref, "level_loss", self.level_loss)
+        monkeypatch.setattr(cpu_ref, "LevelTargets", self.targets)
+
+    def targets(self, content_t, style_t, weights):
+        tg = self.targets0(content_t, style_t, weights)
+        with torch.no_grad():
+            sf = cpu_ref.vgg19_features(style_t, weights)
+            tg.mrf_style = {i: sf[i].detach() for i in range(6) if self.w[i] > 0}
+        tg.mrf_level = self.made
+        self.made += 1
+        return tg
+
+    def term(self, feats, tg):
+        l = tg.mrf_level
+        if self.levels is not None and l not in self.levels:
+            return None, {}
+        total, vals = None, {}
+        for i in range(6):
+            if not self.w[i] > 0:
+                continue
+            v = mrf_value(feats[i], tg.mrf_style[i], self.nn[l][i], self.stride)
+            vals[i] = float(v.detach())
+            t = torch.tensor(np.float32(self.w[i])) * v
+            total = t if total is None else total + t
+        return total, vals
+
+    def level_loss(self, x, tg, weights, cw, sw, tvw, decisions=None, record=None):
+        seen = []
+        inner = cpu_ref.vgg19_features
+
+        def keep(*a, **k):
+            seen.append(inner(*a, **k))
+            return seen[-1]
+
+        cpu_ref.vgg19_features = keep             # (the features the original computes, not a second forward pass)
+        try:
+            total, content, style, tv = self.level_loss0(x, tg, weights, cw, sw, tvw, decisions, record)
+        finally:
+            cpu_ref.vgg19_features = inner
+        term, vals = self.term(seen[0], tg)
+        self.log.append((float(term.detach()) if term is not None else 0.0, vals))
+        return (total + term if term is not None else total), content, style, tv
+
+
+NO_TV = TERMS[:3]
+TV_ONLY = TERMS[3:]
+
+
+def _set_patches(e, styles, w, stride=1, levels=None, prep=cpu_ref.prepare_img):
+    for i in range(len(styles)):
+        if levels is None or i in levels:
+            e.set_patches(i, dev(prep(styles[i])), w, stride, EPS)
+
+
+def _setup(e, contents, styles, w, stride=1, levels=None, prepare=None):
+    h, wd = contents[0].shape[:2]
+    e.configure(len(contents), h, wd)
+    if prepare:
+        prepare(e)
+    for i in range(len(contents)):
+        e.set_targets(i, dev(cpu_ref.prepare_img(contents[i])), dev(cpu_ref.prepare_img(styles[i])))
+    _set_patches(e, styles, w, stride, levels)
+
+
+def _hand_over_matches(e, patched, xd, w):
+    """One closure, then the device's nn of every (level, weighted map) into the oracle."""
+    e.closure(xd, CW, SW, TVW)
+    patched.nn = {l: {i: e.patch_matches(l, i).cpu() for i in range(6) if w[i] > 0}
+                  for l in range(e.levels) if e.patches_setting(l) is not None}
+
+
+def _the_term_counts(patched, xt, tg, weights, what, cache=None, lo=0.10, hi=0.60):
+    """On the CPU: the term is between 10 % and 60 % of every level total that carries it - a build that ignores it cannot
+    pass, and it does not drown the rest."""
+    rec = []
+    patched.log.clear()
+    loss, grad, rows = cpu_ref.closure_eval(xt, tg, weights, CW, SW, TVW, record=rec)
+    if cache is not None:
+        cache["all"] = (loss, grad, rows, rec)
+    assert len(patched.log) == len(rows)
+    for l, ((term, vals), row) in enumerate(zip(patched.log, rows)):
+        share = term / row[0]
+        report(f"mrf {what} level {l}: term {term:.4e} of total {row[0]:.4e} = {share:.1%}; mrf_i = {vals}")
+        if vals:
+            assert lo <= share <= hi, (what, l, share)
+
+
+def _additivity(e, xt, what):
+    """The term is in every weighting with its own weights, so the sum of the content, style and tv gradients holds it three
+    times and the weighted sum once; the closure with cw = sw = tvw = 0 is the term alone (same forward pass, same nn):
+    g(all) = g(content) + g(style) + g(tv) - 2 g(0, 0, 0), to hip_helpers' 2e-6."""
+    xd = dev(xt)
+    g = {name: e.closure(xd, *w3)[0].cpu().numpy().astype(np.float64) for name, w3 in TERMS + (("mrf", (0.0, 0.0, 0.0)),)}
+    s = g["content"] + g["style"] + g["tv"] - 2.0 * g["mrf"]
+    add = float(np.linalg.norm(g["all"] - s) / np.linalg.norm(s))
+    share = float(np.linalg.norm(g["mrf"]) / np.linalg.norm(g["all"]))
+    report(f"mrf {what}: |g(all) - (sum of the weightings - 2 g(term alone))| / |.| = {add:.1e}; |g(term alone)| / |g(all)| = {share:.2f}")
+    assert add < 2e-6, (what, add)
+    assert share > 0.01, (what, share)
+
+
+def _held_to_patched_oracle(e, xt, tg, weights, what, cache=None):
+    """Losses 1e-5, rows 2e-5, gradient 2e-5 under the device's decisions (hip_helpers' standing tolerances), additivity 2e-6."""
+    closure_vs_oracle_under_equal_decisions(e, xt, tg, weights, f"mrf {what}", terms=NO_TV, own_cache=cache)
+    closure_vs_oracle_under_equal_decisions(e, xt, tg, weights, f"mrf {what}", terms=TV_ONLY)
+    _additivity(e, xt, what)
+
+
+def _strict(e, monkeypatch, vgg_weights, what, w, stride=1, levels=None, prepare=None, job="64x96_L1"):
+    c, s, xt = _job(job)
+    patched = PatchedOracle(monkeypatch, w, stride, levels)
+    tg = oracle_targets(c, s, vgg_weights)
+    _setup(e, c, s, w, stride, levels, prepare)
+    _hand_over_matches(e, patched, dev(xt), w)
+    cache = {}
+    _the_term_counts(patched, xt, tg, vgg_weights, what, cache)
+    _held_to_patched_oracle(e, xt, tg, vgg_weights, what, cache)
+    return patched
+
+
+# relu3_1 and relu4_1, Li & Wand's layers.  Measured on the CPU (the patched oracle, the tests' synthetic weights): at weights
+# (2, 1) the term is 0.1 % ... 0.3 % of the level totals of the 64x96 two-level job on every path below, so 200 times that
+# puts it between 15 % and 40 %
+W_34 = (0.0, 0.0, 400.0, 200.0, 0.0, 0.0)
+
+
+def test_path_batched_walker(eng, vgg_weights, monkeypatch):
+    _strict(eng, monkeypatch, vgg_weights, "batched walker", W_34)
+
+
+def test_path_per_level_walker(eng_per_level, vgg_weights, monkeypatch):
+    _strict(eng_per_level, monkeypatch, vgg_weights, "per-level walker", W_34)
+
+
+def test_path_stride_two_and_one_level_of_two(eng, vgg_weights, monkeypatch):
+    """mrf_levels naming one level of two (the other level's row and gradient are what they are without the term), at style
+    stride 2."""
+    p = _strict(eng, monkeypatch, vgg_weights, "level 0 of two, stride 2", W_34, stride=2, levels=(0,))
+    assert eng.patches_setting(1) is None and eng.patches_setting(0) == (W_34, 2, EPS)
+    assert not eng.patch_losses().cpu().numpy()[1].any()
+    assert p.log[-1][1] == {}
+
+
+def test_path_average_pooling(eng, vgg_weights, monkeypatch):
+    from test_hip_pooling import avg_vgg19_features
+    monkeypatch.setattr(cpu_ref, "vgg19_features", avg_vgg19_features)
+    try:
+        _strict(eng, monkeypatch, vgg_weights, "avg pooling", W_34, prepare=lambda e: e.set_pooling("avg"))
+    finally:
+        eng.reset_pooling()
+
+
+def test_path_pre_relu_taps(eng, vgg_weights, monkeypatch):
+    monkeypatch.setattr(cpu_ref, "vgg19_features", prerelu_vgg19_features)
+    try:
+        _strict(eng, monkeypatch, vgg_weights, "pre-ReLU taps", W_34, prepare=lambda e: e.set_taps(4, [0, 1, 2, 3, 5], use_relu=False))
+    finally:
+        eng.reset_taps()
+
+
+def test_path_beside_a_centred_gram_and_the_moment_term(eng, vgg_weights, monkeypatch):
+    """The term's addend beside the Gram second source, its row bias (o S of the centred Gram) and the moment term's fold."""
+    from test_hip_gram_shift import MEAN, PatchedGram
+    from test_hip_moments import PatchedOracle as MomentOracle, on_maps as mom_maps
+    monkeypatch.setattr(cpu_ref, "gram_matrix", PatchedGram((MEAN,) * 6))
+    MomentOracle(monkeypatch, mom_maps(1e2), mom_maps(1e2))            # (patched first: the MRF oracle wraps it)
+
+    def prepare(e):
+        e.set_gram_shift("mean")
+        e.set_moments(mom_maps(1e2), mom_maps(1e2))
+
+    _strict(eng, monkeypatch, vgg_weights, "'mean' Gram + moments", W_34, prepare=prepare)
+
+
+# -- taps beyond cpu_ref.level_loss: test_hip_style_blend's restatement with the term added
+def _restated_closure(x, targets, weights, cw, sw, tvw, taps, decisions, w, nn, stride=1):
+    content_i, style_set = taps
+    x = x.detach().clone().requires_grad_(True)
+    lv, total, rows, terms = [x], None, [], []
+    for l, tg in enumerate(targets):
+        if l > 0:
+            lv.append(cpu_ref.bicubic_half(lv[l - 1]))
+        dec = decisions[l] if decisions is not None else None
+        f = cpu_ref.vgg19_features(lv[l], weights, dec)
+        content = F.mse_loss(tg.content, f[content_i].squeeze(0), reduction="mean")
+        style = 0.0
+        for i in style_set:
+            style = style + F.mse_loss(tg.grams[i][0], cpu_ref.gram_matrix(f[i])[0], reduction="mean")
+        style = style / len(style_set)
+        tv = cpu_ref.total_variation(lv[l], dec.tv if dec is not None else None)
+        term = None
+        for i in range(6):
+            if w[i] > 0:
+                t = torch.tensor(np.float32(w[i])) * mrf_value(f[i], tg.mrf_style[i], nn[l][i], stride)
+                term = t if term is None else term + t
+        t = cw * content + sw * style + tvw * tv + term
+        total = t if total is None else 1.0 * total + t
+        rows.append((float(t.detach()), float(content.detach()), float(style.detach()), float(tv.detach())))
+        terms.append(float(term.detach()))
+    total.backward()
+    return total.detach(), x.grad.detach(), rows, terms
+
+
+@pytest.mark.parametrize("case", ["content map is an MRF map", "MRF map at the top of the chain"])
+def test_path_other_taps(eng, vgg_weights, case):
+    """style_mask 0x3F with the term on conv4_2, the content map (content gradient and the term in one addend, beside the Gram
+    second source); and style maps ending at relu4_1 with the term on it: the top-of-chain launch's addend."""
+    from test_hip_style_blend import device_decisions as decisions_of, restated_targets
+    if case.startswith("content"):
+        taps, w = (4, (0, 1, 2, 3, 4, 5)), (0.0, 0.0, 400.0, 0.0, 200.0, 0.0)
+    else:
+        taps, w = (2, (0, 1, 2, 3)), W_34
+    c, s, xt = _job("64x96_L1")
+    prep = cpu_ref.prepare_img
+    try:
+        eng.configure(2, 64, 96)
+        eng.set_taps(taps[0], list(taps[1]))
+        tg = []
+        for i in range(2):
+            eng.set_targets(i, dev(prep(c[i])), dev(prep(s[i])))
+            t = restated_targets(prep(c[i]), [prep(s[i])], ((1.0,) * 6,), vgg_weights, taps)
+            with torch.no_grad():
+                sf = cpu_ref.vgg19_features(prep(s[i]), vgg_weights)
+            t.mrf_style = {k: sf[k].detach() for k in range(6) if w[k] > 0}
+            tg.append(t)
+        _set_patches(eng, s, w)
+        xd = dev(xt)
+        for name, (cw, sw, tvw) in (("style", (0.0, SW, 0.0)), ("all", (CW, SW, TVW))):
+            grad, losses = eng.closure(xd, cw, sw, tvw)
+            dec = decisions_of(eng, xd, vgg_weights, taps)
+            nn = {l: {k: eng.patch_matches(l, k).cpu() for k in range(6) if w[k] > 0} for l in range(2)}
+            losses = losses.cpu().numpy()
+            loss, g_ref, rows, terms = _restated_closure(xt, tg, vgg_weights, cw, sw, tvw, taps, dec, w, nn)
+            e_l = abs(float(losses[-1]) - float(loss)) / abs(float(loss))
+            e_g = rel_l2(grad.cpu().numpy(), g_ref.numpy())
+            shares = [t / r[0] for t, r in zip(terms, rows)]
+            report(f"mrf {case} [{name}]: total rel {e_l:.2e}, gradient rel-L2 under equal decisions {e_g:.2e}; share of the level "
+                   f"totals {[round(v, 3) for v in shares]}")
+            if name == "all":
+                assert all(0.10 <= v <= 0.60 for v in shares), (case, shares)
+            assert e_l < 1e-5, (case, name, e_l)
+            check_rows(losses[:-1].reshape(2, 4), np.array(rows), 2e-5, cw, sw, tvw)
+            assert e_g < 2e-5, (case, name, e_g)
+    finally:
+        eng.reset_taps()
+
+
+def test_path_luminance(eng, vgg_weights, monkeypatch):
+    """The luminance closure with the term = the patched oracle's closure at E(u), gradient summed over the channels; the
+    style's maps are those of the matched luminance plane."""
+    from artstyletransfer_amd import host_image
+    from test_hip_color import expand, lum_decisions, lum_targets, start_u
+    c, s = _levels(64, 96, 2, 1), _levels(70, 110, 2, 2)
+    w = W_34
+    patched = PatchedOracle(monkeypatch, w)
+    try:
+        eng.configure(2, 64, 96)
+        eng.set_color("luminance")
+        alpha, beta = host_image.luminance_params(host_image.color_stats(c[0]), host_image.color_stats(s[0]))
+        cu, su = lum_targets(c, s, alpha, beta)
+        for i in range(2):
+            eng.set_targets(i, dev(torch.from_numpy(cu[i])), dev(torch.from_numpy(su[i])))
+            eng.set_patches(i, dev(torch.from_numpy(su[i])), w, 1, EPS)
+        tg = [cpu_ref.LevelTargets(expand(torch.from_numpy(a)), expand(torch.from_numpy(b)), vgg_weights) for a, b in zip(cu, su)]
+        u = start_u(c[0])
+        ud = dev(u.reshape(1, 1, 64, 96))
+        xt = expand(u)
+        grad, losses = eng.closure(ud, CW, SW, TVW)
+        patched.nn = {l: {i: eng.patch_matches(l, i).cpu() for i in range(6) if w[i] > 0} for l in range(2)}
+        dec = lum_decisions(eng, ud)
+        losses = losses.cpu().numpy()
+        patched.log.clear()
+        loss, _, rows = cpu_ref.closure_eval(xt, tg, vgg_weights, CW, SW, TVW)
+        shares = [m / r[0] for (m, _), r in zip(patched.log, rows)]
+        report(f"mrf luminance: share of the level totals {[round(v, 3) for v in shares]}")
+        assert all(0.10 <= v <= 0.60 for v in shares), shares
+        assert float(losses[-1]) == pytest.approx(float(loss), rel=1e-5)
+        check_rows(losses[:-1].reshape(2, 4), np.array(rows), 1e-5, CW, SW, TVW)
+        _, g_eq, _ = cpu_ref.closure_eval(xt, tg, vgg_weights, CW, SW, TVW, decisions=dec)
+        e_g = rel_l2(grad.cpu().numpy().reshape(64, 96), g_eq.sum(dim=1).numpy().reshape(64, 96))
+        report(f"mrf luminance: gradient rel-L2 under equal decisions {e_g:.2e}")
+        assert e_g < 2e-5
+    finally:
+        eng.reset_color()
+
+
+# ---- 5. halves, reproducibility, L-BFGS, level masks ----------------------------------------------------------------------
+MIXED_W = (0.0, 100.0, 400.0, 200.0, 0.0, 0.0)     # (relu5_1 of the 32x48 level is 2x3: no patch)
+
+
+def _mixed_job(e, name="64x96_L1"):
+    c, s, xt = _job(name)
+    _setup(e, c, s, MIXED_W)
+    return dev(xt), c, s
+
+
+def test_halves_equal_the_whole_and_run_to_run_bitwise(eng):
+    x, _, _ = _mixed_job(eng)
+    g, l = eng.closure(x, CW, SW, TVW)
+    m = eng.patch_losses()
+    nn = [eng.patch_matches(lv, 3).clone() for lv in range(2)]
+    g2, l2 = eng.closure(x, CW, SW, TVW)
+    assert np.array_equal(_bits(g), _bits(g2)) and np.array_equal(_bits(l), _bits(l2))
+    assert np.array_equal(_bits(m), _bits(eng.patch_losses()))
+    assert all(torch.equal(a, eng.patch_matches(lv, 3)) for lv, a in enumerate(nn))
+    lf = eng.closure_forward(x, CW, SW, TVW)
+    assert np.array_equal(_bits(lf), _bits(l))
+    gb = eng.closure_backward(x, CW, SW, TVW)
+    assert np.array_equal(_bits(gb), _bits(g))
+
+
+@pytest.mark.parametrize("which", ["batched", "per_level"])
+def test_level_masks_add_up(eng, eng_per_level, which):
+    e = eng if which == "batched" else eng_per_level
+    x, _, _ = _mixed_job(e)
+    g, l = e.closure(x, CW, SW, TVW)
+    m = e.patch_losses().cpu().numpy()
+    g, l = g.cpu().numpy().astype(np.float64), l.cpu().numpy().astype(np.float64)
+    gs, ls, ms = np.zeros_like(g), np.zeros_like(l), np.zeros_like(m)
+    for mask in (1, 2):
+        gm, lm = e.closure_levels(x, CW, SW, TVW, mask)
+        mm = e.patch_losses().cpu().numpy()
+        assert not mm[[lv for lv in range(2) if not (mask >> lv) & 1]].any()          # zeros for levels outside the mask
+        gs += gm.cpu().numpy()
+        ls += lm.cpu().numpy()
+        ms += mm
+    np.testing.assert_allclose(ls, l, rtol=1e-6)
+    assert np.array_equal(ms, m)
+    err = float(np.linalg.norm(gs - g) / np.linalg.norm(g))
+    report(f"mrf level masks [{which}]: |sum - unsharded| / |.| = {err:.1e}")
+    assert err <= 1e-6
+
+
+def test_lbfgs_is_the_same_with_reuse_and_lazy_backward_on_or_off(eng):
+    from artstyletransfer_amd.engine import PixelOptimizer
+    x0, _, _ = _mixed_job(eng)
+    runs = {}
+    for reuse, lazy in ((False, False), (True, True)):
+        opt = PixelOptimizer(eng, "lbfgs")
+        try:
+            opt.set_closure_reuse(reuse)
+            opt.set_lazy_backward(lazy)
+            x = x0.clone()
+            out = []
+            for _ in range(5):
+                info, rows = opt.step(x, CW, SW, TVW)
+                out.append((info.closures, info.total_closures, info.accepted, info.history, rows.view(np.uint32).copy(), _bits(x)))
+            runs[(reuse, lazy)] = (out, opt.closure_stats(), opt.backward_stats())
+        finally:
+            opt.close()
+    base = runs[(False, False)][0]
+    out, stats, bw = runs[(True, True)]
+    for k, (a, b) in enumerate(zip(out, base)):
+        assert a[:4] == b[:4], (k, a[:4], b[:4])
+        assert np.array_equal(a[4], b[4]) and np.array_equal(a[5], b[5]), k
+    assert np.isfinite(base[-1][4].view(np.float32)).all()
+    assert sum(stats) == base[-1][1], (stats, bw)
+
+
+# ---- 6. the loss row -----------------------------------------------------------------------------------------------------------
+def test_patch_losses_times_the_weights_plus_the_other_terms_are_the_row_totals(eng):
+    """total = ((cw content + sw style) + tvw tv) + w_1 mrf_1 + w_2 mrf_2 ... in ascending map order, every product and sum
+    rounded to fp32: bitwise from what the closure returns; and zeros for the maps without the term."""
+    x, _, _ = _mixed_job(eng)
+    _, l = eng.closure(x, CW, SW, TVW)
+    rows = l.cpu().numpy()[:-1].reshape(2, 4)
+    m = eng.patch_losses().cpu().numpy()
+    on = [i for i in range(6) if MIXED_W[i] > 0]
+    assert m.shape == (2, 6) and not m[:, [0, 4, 5]].any() and (m[:, on] > 0).all()
+    f32 = np.float32
+    for lv in range(2):
+        total = (f32(CW) * rows[lv, 1] + f32(SW) * rows[lv, 2]) + f32(TVW) * rows[lv, 3]
+        for i in on:
+            total = f32(total + f32(MIXED_W[i]) * m[lv, i])
+        assert total == rows[lv, 0], (lv, total, rows[lv, 0])
+
+
+# ---- 7. a cleared term ---------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("batched", [True, False])
+def test_cleared_term_is_bitwise_an_engine_that_never_called_the_setter(vgg_weights, batched):
+    from artstyletransfer_amd.engine import StyleEngine
+    c, s, xt = _job("64x96_L1")
+    out = []
+    for call in (False, True):
+        e = StyleEngine(vgg_weights, 0, batched=batched)
+        try:
+            e.set_timing(2)
+            e.configure(2, 64, 96)
+            for i in range(2):
+                e.set_targets(i, dev(cpu_ref.prepare_img(c[i])), dev(cpu_ref.prepare_img(s[i])))
+            if call:
+                before = e.bytes()
+                _set_patches(e, s, MIXED_W)
+                assert e.bytes() > before
+                e.closure(dev(xt), CW, SW, TVW)
+                e.clear_patches()
+                assert e.bytes() == before
+                assert all(e.patches_setting(i) is None for i in range(2))
+            g, l = e.closure(dev(xt), CW, SW, TVW)
+            assert not e.patch_losses().cpu().numpy().any()
+            out.append((_bits(g), _bits(l), e.last_closure_launches()))
+        finally:
+            e.close()
+    assert np.array_equal(out[0][0], out[1][0]) and np.array_equal(out[0][1], out[1][1])
+    strip = lambda rec: [{k: v for k, v in d.items() if k not in ("ms",)} for d in rec]        # noqa: E731
+    assert strip(out[0][2]) == strip(out[1][2]) and len(out[0][2]) > 0
+
+
+# ---- 8. life cycle and refusals --------------------------------------------------------------------------------------------
+def test_life_cycle_and_refusals(eng, vgg_weights):
+    from artstyletransfer_amd._lib import NstError
+    from artstyletransfer_amd.engine import StyleEngine, _ptr, _stream
+    x, c, s = _mixed_job(eng)
+    g0, l0 = eng.closure(x, CW, SW, TVW)
+    before = [eng.patches_setting(i) for i in range(2)]
+    assert before[0] == (MIXED_W, 1, EPS)
+    style = dev(cpu_ref.prepare_img(s[0]))
+    hs, ws = style.shape[-2:]
+
+    def raw(level=0, w=MIXED_W, stride=1, eps=1e-5, img=style, shape=None):
+        sh = shape or (hs, ws)
+        return eng.lib.nst_level_set_patches(eng.ctx, level, _ptr(img), sh[0], sh[1], (C.c_float * 6)(*w), stride, eps, _stream(eng.device))
+
+    # NST_E_ARG, and a refusal leaves the level as it was
+    assert raw(level=-1) == -1 and raw(level=2) == -1
+    for bad in (-1.0, float("nan"), float("inf")):
+        assert raw(w=(0.0, 0.0, bad, 1.0, 0.0, 0.0)) == -1
+    for eps in (0.0, -1e-5, float("nan"), float("inf")):
+        assert raw(eps=eps) == -1
+    assert raw(stride=0) == -1 and raw(stride=9) == -1
+    assert raw(w=(0.0, 0.0, 0.0, 0.0, 1.0, 0.0)) == -1                 # conv4_2 is no style map under the default taps
+    assert raw(level=1, w=(0.0,) * 5 + (1.0,)) == -1                  # relu5_1 of the 32x48 level is 2x3
+    assert raw(w=(0.0,) * 5 + (1.0,), shape=(40, 40)) == -1           # relu5_1 of a 40x40 style image is 2x2
+    assert [eng.patches_setting(i) for i in range(2)] == before
+    g1, l1 = eng.closure(x, CW, SW, TVW)
+    assert np.array_equal(_bits(g1), _bits(g0)) and np.array_equal(_bits(l1), _bits(l0))
+    # a guided level, in either order of the two calls
+    planes = torch.ones((2, 64, 96), device="cuda:0") * 0.5
+    with pytest.raises(NstError, match=r"\(-2\)"):
+        eng.set_guidance(0, planes)
+    eng.clear_patches(0)
+    eng.set_guidance(0, planes)
+    assert raw() == -2 and eng.patches_setting(0) is None
+    eng.clear_guidance()
+    # a pending backward half goes with a new term
+    _mixed_job(eng)
+    eng.closure_forward(x, CW, SW, TVW)
+    eng.set_patches(0, style, W_34)
+    with pytest.raises(NstError, match=r"\(-2\)"):
+        eng.closure_backward(x, CW, SW, TVW)
+    # configure, set_taps, set_pooling and set_color drop the term
+    for drop, undo in ((lambda: eng.configure(2, 64, 96), None), (lambda: eng.set_taps(4, [0, 1, 2, 3]), eng.reset_taps),
+                       (lambda: eng.set_pooling("avg"), eng.reset_pooling), (lambda: eng.set_color("luminance"), eng.reset_color)):
+        _mixed_job(eng)
+        assert eng.patches_setting(0) is not None
+        drop()
+        try:
+            assert all(eng.patches_setting(i) is None for i in range(2))
+        finally:
+            if undo:
+                undo()
+    # the stripe closure, and the stripe sharding of the optimiser before any stripe engine is made
+    from artstyletransfer_amd.engine import PixelOptimizer
+    e1 = StyleEngine(vgg_weights, 0)
+    try:
+        xs = dev(cpu_ref.prepare_img(cpu_ref.synthetic_image(64, 96, 1)))
+        assert e1.lib.nst_level_set_patches(e1.ctx, 0, _ptr(xs), 64, 96, (C.c_float * 6)(*W_34), 1, 1e-5, _stream(e1.device)) == -2
+        e1.configure(1, 64, 96)
+        e1.set_targets(0, xs, xs)
+        e1.set_patches(0, xs, W_34)
+        with pytest.raises(NstError, match=r"\(-2\)"):
+            e1.window_begin(xs, 0, 64, 64)
+        opt = PixelOptimizer(e1, "lbfgs")
+        try:
+            with pytest.raises(ValueError, match="mrf_weight cannot be combined with stripe sharding"):
+                opt.shard_stripes(0, 2, None, None, None, dist_mod=object())
+        finally:
+            opt.close()
+        # the two readers name a level out of range the same way
+        assert e1.lib.nst_level_patches(e1.ctx, 1, None, None, None) == -1
+        assert e1.lib.nst_level_patch_matches(e1.ctx, 1, 3, _ptr(xs), _stream(e1.device)) == -1
+        e1.clear_patches()
+        e1.window_begin(xs, 0, 64, 64)
+    finally:
+        e1.close()
+
+
+@pytest.mark.parametrize("kw", [{"conv_mode": "f32"}, {"conv_mode": "bf16x3"}, {"use_graph": True}])
+def test_other_arithmetic_modes_and_a_graph_context_refuse_the_term(vgg_weights, kw):
+    from artstyletransfer_amd.engine import StyleEngine, _ptr, _stream
+    e = StyleEngine(vgg_weights, 0, **kw)
+    try:
+        e.configure(1, 64, 96)
+        xs = dev(cpu_ref.prepare_img(cpu_ref.synthetic_image(64, 96, 1)))
+        assert e.lib.nst_level_set_patches(e.ctx, 0, _ptr(xs), 64, 96, (C.c_float * 6)(*W_34), 1, 1e-5, _stream(e.device)) == -2
+        e.clear_patches()                                          # clearing is no setting
+        assert e.patches_setting(0) is None
+    finally:
+        e.close()
+
+
+# ---- 9. a whole job ----------------------------------------------------------------------------------------------------------
+def _run_job(fn, seed=1, **kw):
+    import neural_style_transfer as nst
+    content = cpu_ref.synthetic_image(64, 96, seed=seed)
+    style = cpu_ref.synthetic_image(70, 110, seed=seed + 1)
+    pair = nst.ContentStylePair(("c", content), ("s", style))
+    np.random.seed(1234)
+
+    async def run():
+        return [img async for _, img in fn(pair, CW, SW, TVW, "adam", "vgg19", "content+noise", 3, 1, 0.95, (9, 18, 36, -1, 0),
+                                           (0.3, 0.2, 0.1, 0.2, 0.2), (0.2, 0.3, 0.4, 0.1, 0.0), (0.2, 0.3, 0.4, 0.6, 0.3),
+                                           device=torch.device("cuda", 0), **kw)]
+    return asyncio.run(run())
+
+
+def test_whole_job():
+    """neural_style_transfer_mrf on a 64x96 pair (one level, which the driver resizes to a short edge of 256) yields finite
+    images that the term has moved; with mrf_weight=None it is neural_style_transfer(), bitwise."""
+    from artstyletransfer_amd.neural_style_transfer import neural_style_transfer
+    from artstyletransfer_amd.patch_match import neural_style_transfer_mrf
+    out = _run_job(neural_style_transfer_mrf, mrf_weight=300.0, mrf_stride=2)
+    assert len(out) == 3 and all(np.isfinite(o).all() for o in out)
+    plain = _run_job(neural_style_transfer)
+    off = _run_job(neural_style_transfer_mrf, mrf_weight=None, mrf_stride=2)
+    assert len(plain) == len(off) == 3
+    assert all(np.array_equal(a, b) for a, b in zip(plain, off))
+    assert not np.array_equal(plain[-1], out[-1])                  # (the term moved the result)
