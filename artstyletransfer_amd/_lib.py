@@ -168,6 +168,9 @@ SYMBOLS = {
     "nst_ctx_forward_pack": (C.c_int, [c_void]),
     "nst_ctx_set_gram_pack": (C.c_int, [c_void, C.c_int]),
     "nst_ctx_gram_pack": (C.c_int, [c_void]),
+    "nst_ctx_set_h2_direct_weights": (C.c_int, [c_void, C.c_int]),
+    "nst_ctx_h2_direct_weights": (C.c_int, [c_void]),
+    "nst_ctx_h2_direct_launches": (C.c_longlong, [c_void]),
     "nst_level_image": (C.c_int, [c_void, C.c_int, c_void, c_void]),
     "nst_gram": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, c_void, c_void]),
     "nst_guided_gram_backward": (C.c_int, [c_void, c_void, C.c_size_t, C.c_int, C.c_int, c_void, c_void, c_void, c_void, c_void,

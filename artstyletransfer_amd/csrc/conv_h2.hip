@@ -46,6 +46,10 @@ namespace {
 #ifndef NST_H2_WEIGHT_SETS4
 #define NST_H2_WEIGHT_SETS4 1
 #endif
+// DIRECT K loop (conv_h2_body): fragment sets in the ring; a stage's B fragments are requested RING - 1 stages ahead
+#ifndef NST_H2_DIRECT_RING
+#define NST_H2_DIRECT_RING 3
+#endif
 // Timing-only builds (tools/ablate_conv.sh; never shipped): a set bit gives one stream of the kernel a buffer descriptor
 // with zero records, so the range check drops its loads / stores while the instruction stream, the waits and the
 // barriers stay - the launch then shows what that stream's memory traffic costs.  bit 0: the patch loads of the main
@@ -72,6 +76,12 @@ constexpr float LO_DOWN = 1.f / 2048.f;
 //   <16,  64, 2, 16>  256 threads, 16x16 pixels x  64 channels, 70 KB LDS    the 64-channel layers: TWO workgroups
 //                     per CU, so that one's prologue / epilogue (a large share with K = 576) runs under the other's
 //                     MFMAs; 16-channel chunks keep the double-buffered patch of each within half the LDS
+//   the last two with DIRECT (conv_h2_batch_kernel<..., true>; nst_ctx_set_h2_direct_weights, the default): the FORWARD
+//                     launches of conv2_1 / conv2_2 / conv3_1 and of conv1_2 - no second source, no un-pooling, one tile per
+//                     workgroup.  B fragments come from the layer's fragment-order image through a buffer descriptor (L2 ->
+//                     registers, a ring of NST_H2_DIRECT_RING sets), LDS holds the double-buffered patch alone (30 / 54 KB)
+//                     and the K loop has ONE barrier per chunk (9 stages, 108 MFMAs per wave) instead of one per stage.
+//                     Their input-gradient launches (Gram source, un-pooling) and the persistent form run the loop below.
 // LDS: the halo patch double buffered, the per-tap weight slice triple buffered (see the main K loop); a row holds
 // the two pieces of KC channels (2 x 2 KC bytes) + 16 B pad = 144 / 80 B, an odd multiple of 16 B: 16 consecutive
 // rows start on 16 distinct 16-B slots -> conflict-free ds_read_b128 fragments.
@@ -150,7 +160,7 @@ __device__ __forceinline__ void cut2x4(const f32x4 v, const float s, u32x2& hi, 
 // drain under its first stages.  Per tile of a one-tile-per-workgroup launch that prologue + dispatch + the write burst
 // of 256 CUs finishing in lock-step cost ~11 us (fit over the 72- and 144-stage layers), 6 - 11 % of a launch.
 // The arithmetic of a tile does not depend on how it was reached: both launch forms give bitwise the same tensors.
-template <int TH, int BN, int NTW, int KC, bool UNPOOL, bool M16, class Tiles>
+template <int TH, int BN, int NTW, int KC, bool UNPOOL, bool M16, bool DIRECT, class Tiles>
 __device__ __forceinline__ void conv_h2_body(const Tiles& tiles, const int slot_seed) {
     static_assert(!M16 || KC == 32, "the 16x16x32 form takes a whole 32-channel chunk per MFMA");
     using C = H2Cfg<TH, BN, NTW, KC>;
@@ -159,7 +169,7 @@ __device__ __forceinline__ void conv_h2_body(const Tiles& tiles, const int slot_
     // the three weight-slice buffers first: every fragment address of theirs is then ONE per-lane base + an immediate
     // below 64 KiB (the ds_read offset field), instead of a base register per slice
     unsigned char* ldsB = smem;                          // 3 weight-slice buffers
-    unsigned char* ldsA = smem + 3 * C::B_BYTES;         // 2 patch buffers
+    unsigned char* ldsA = smem + (DIRECT ? 0 : 3 * C::B_BYTES);      // 2 patch buffers (DIRECT: LDS holds nothing else)
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -563,6 +573,114 @@ __device__ __forceinline__ void conv_h2_body(const Tiles& tiles, const int slot_
         };
         auto tap_off = [](int t) { return (t / 3) * C::PROWB + (t % 3) * ROWB; };
 
+        // ---- DIRECT: the K loop without weight slices in LDS.  A wave takes the B fragments of stage g + RING - 1 straight
+        // from the fragment-order image (L2 -> registers, four 16-byte buffer loads per stage: per-lane offset fixed for the
+        // whole loop, one scalar offset per stage) into a ring of RING fragment sets; LDS holds the double-buffered patch
+        // only, and the ONE workgroup barrier left is the one at a chunk boundary, 9 stages = 108 MFMAs per wave apart.
+        // Hazard: the cut of chunk c+1 (taps 3 / 7 of chunk c) writes the buffer that chunk c-1 read; every fragment read of
+        // chunk c-1 was requested before the barrier that ended it (its last stage requests nothing: the first fragments of
+        // the next chunk are requested BEHIND the barrier, from the buffer all waves have then finished cutting).
+        // The MFMAs of an accumulator arrive in the order of the loop below: chunk, tap; cross, main, cross.
+        if constexpr (DIRECT) {
+            static_assert(KC == 16 && NTW == 2 && !UNPOOL && !M16 && !Tiles::REFETCH, "the 16-channel-chunk forward launches, one tile per workgroup");
+            constexpr int RING = NST_H2_DIRECT_RING;
+            constexpr int NB = (RING % 3 == 0) ? 2 : 4;        // chunks per loop body: 9 NB stages, a multiple of RING and of 2
+            static_assert((9 * NB) % RING == 0 && RING >= 2, "the ring position of a stage is a constant of the loop body");
+            const int nct = p.Cout >> 5;                       // 32-channel tiles of the layer
+            const __amdgpu_buffer_rsrc_t rsrc_f = __builtin_amdgcn_make_buffer_rsrc(
+                const_cast<void*>(p.wt_h2_frag), 0, (unsigned)((size_t)9 * nch * nct * 2048) * ABL_W, 0x00020000);
+            // 16-byte units [chunk][tap][32-channel tile][piece][lane]
+            const unsigned f_voff = (unsigned)(lane * 16 + ((n0 >> 5) + wn * NTW) * 2048);
+            struct BF { f16x8 v[NTW][2]; };      // [n tile][piece]
+            struct AF { f16x8 v[2][2]; };        // [m tile][piece]
+            auto load_f = [&](BF& f, const int chunk, const int tap) {
+                const int soff = (chunk * 9 + tap) * nct * 2048;
+#pragma unroll
+                for (int nt = 0; nt < NTW; ++nt)
+#pragma unroll
+                    for (int s = 0; s < 2; ++s)
+                        f.v[nt][s] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(rsrc_f, f_voff + (nt * 2 + s) * 1024, soff, 0));
+            };
+            auto request_a = [&](AF& f, const unsigned char* abase) {
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    f.v[0][s] = *reinterpret_cast<const f16x8*>(abase + a_off0 + s * PIECEB);
+                    f.v[1][s] = *reinterpret_cast<const f16x8*>(abase + a_off1 + s * PIECEB);
+                }
+            };
+            auto multiply_d = [&](const AF& a, const BF& w) {
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                    for (int nt = 0; nt < NTW; ++nt) {
+                        accx[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a.v[mt][1], w.v[nt][0], accx[mt][nt], 0, 0, 0);
+                        accm[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a.v[mt][0], w.v[nt][0], accm[mt][nt], 0, 0, 0);
+                        accx[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a.v[mt][0], w.v[nt][1], accx[mt][nt], 0, 0, 0);
+                    }
+            };
+            // store_a without a branch: a lane whose unit lies beyond the patch (the last unit of the higher lanes) writes its
+            // zeros into the pad behind patch row 0 - a conditional store inside the stage would split it into basic blocks,
+            // and every s_waitcnt behind a join waits for ALL loads in flight
+            static_assert(C::PROWB - C::PW * ROWB >= PIECEB + 8, "the row pitch leaves a pad to drop unused units into");
+            auto store_a_d = [&](unsigned char* dstA, const f32x4* r, const int i0, const int i1, const int to) {
+#pragma unroll
+                for (int i = i0; i < i1; ++i) {
+                    const int off_v = a_lds_of(i, to);
+                    const int off = off_v >= 0 ? off_v : C::PW * ROWB;
+                    u32x2 hi, lo;
+                    cut2x4(r[i - i0], sa, hi, lo);
+                    *reinterpret_cast<u32x2*>(dstA + off) = hi;
+                    *reinterpret_cast<u32x2*>(dstA + off + PIECEB) = lo;
+                }
+            };
+            BF B[RING];
+            AF A[2];
+            // prologue: chunk 0 into patch buffer 0, the fragments of the first RING - 1 stages on their way
+            load_a(ra, here, 0, 0, C::A_PER_T, tid);
+#pragma unroll
+            for (int j = 0; j < RING - 1; ++j) load_f(B[j], j / 9, j % 9);
+            store_a_d(ldsA, ra, 0, C::A_PER_T, tid);
+            __syncthreads();
+            request_a(A[0], ldsA + tap_off(0));
+            constexpr int AP = (C::A_PER_T + 1) / 2;
+            for (int c0 = 0; c0 < nch; c0 += NB) {
+                const int to = opaque(tid);
+#pragma unroll
+                for (int j = 0; j < 9 * NB; ++j) {          // stage j of the body: chunk c, tap t (constants once unrolled)
+                    const int c = c0 + j / 9, t = j % 9;
+                    unsigned char* acur = ldsA + (c & 1) * C::A_BYTES;
+                    unsigned char* anext = ldsA + ((c + 1) & 1) * C::A_BYTES;
+                    // (last chunk: the look-ahead re-loads valid addresses into registers and a buffer nobody reads any more,
+                    // so the body stays branch-free and its s_waitcnt counts exact)
+                    const int cn = (c + 1 < nch) ? c + 1 : c;
+                    {
+                        const int ja = j + RING - 1, ca = c0 + ja / 9;
+                        load_f(B[ja % RING], ca < nch ? ca : nch - 1, ja % 9);
+                    }
+                    if (t == 0) load_a(ra, here, cn, 0, AP, to);
+                    if (t == 4) load_a(ra, here, cn, AP, C::A_PER_T, to);
+                    __builtin_amdgcn_sched_barrier(0);      // (the loads stay at the top of the stage, see the parent's loop below)
+                    if (t == 3) store_a_d(anext, ra, 0, AP, to);
+                    if (t == 7) store_a_d(anext, ra, AP, C::A_PER_T, to);
+                    if (t < 8) {
+                        request_a(A[(j + 1) & 1], acur + tap_off(t + 1));
+                        multiply_d(A[j & 1], B[j % RING]);
+#pragma unroll
+                        for (int g = 0; g < 4; ++g) {
+                            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                        }
+                        __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
+                    } else {
+                        multiply_d(A[j & 1], B[j % RING]);
+                        __syncthreads();
+                        request_a(A[(j + 1) & 1], anext + tap_off(0));
+                    }
+                }
+            }
+            return;
+        }
+
         // prologue: chunk 0 and the slices of stages 0, 1 into LDS, slice 2 into registers - unless the previous tile of
         // this workgroup left exactly that state behind (`primed`)
         if (!primed) {
@@ -720,12 +838,13 @@ __device__ __forceinline__ void conv_h2_body(const Tiles& tiles, const int slot_
 
     // scales of the operand tensors (recorded absmax -> power of two) and of the frozen weights
     // (Cin == 0: a launch of the second source alone, e.g. the Gram backward at the top of the chain, dF = F S)
-    const bool has_main = p.Cin > 0;
+    // (DIRECT: launched for the main source alone - its LDS has no room for the second source's weight stages)
+    const bool has_main = DIRECT || p.Cin > 0;
     float sa1 = 1.f, ia1 = 1.f;
     if (has_main) tensor_scale(p.amax_in, lane, sa1, ia1);
     const float w1_inv = has_main ? p.wt_h2_inv : 1.f;
     const float inv = ia1 * w1_inv;
-    if (p.in2) {
+    if (!DIRECT && p.in2) {
         // The Gram backward rides on this launch with its own scales; it runs first and the accumulators are then
         // re-expressed in the scale of the main source (powers of two: exact).
         float sa2, ia2, sw2, iw2;
@@ -1285,7 +1404,7 @@ struct H2BatchTiles {
         p.tiles_x = im.tiles_x; p.tiles_y = 0; p.partial = nullptr; p.partial_floats = 0; p.ksplit = 1;
         p.in2 = im.in2; p.Cin2 = b.Cin2; p.wt2_bf = nullptr; p.bits_out = im.bits_out; p.bits_in = im.bits_in;
         p.pool_out = im.pool_out;
-        p.wt_h2 = b.wt_h2; p.wt_h2_inv = b.wt_h2_inv; p.wt2_f32 = im.wt2_f32;
+        p.wt_h2 = b.wt_h2; p.wt_h2_inv = b.wt_h2_inv; p.wt2_f32 = im.wt2_f32; p.wt_h2_frag = b.wt_h2_frag;
         p.amax_in = im.amax_in; p.amax_in2 = im.amax_in2; p.amax_w2 = im.amax_w2; p.amax_out = im.amax_out;
         p.pcode_in = im.pcode_in; p.pcode_out = im.pcode_out; p.pool_avg = b.pool_avg;
         p.in2_row0 = im.in2_row0; p.in2_rows = im.in2_rows; p.ty0 = im.ty0;
@@ -1295,10 +1414,16 @@ struct H2BatchTiles {
 };
 
 // One launch = one layer over several images (the pyramid levels of a closure), see conv_bf3.hip.
-template <int TH, int BN, int NTW, int KC, bool UNPOOL, bool M16, bool PERSIST>
+template <int TH, int BN, int NTW, int KC, bool UNPOOL, bool M16, bool PERSIST, bool DIRECT = false>
 __global__ __launch_bounds__((H2Cfg<TH, BN, NTW, KC>::NT), (H2Cfg<TH, BN, NTW, KC>::WAVES_PER_EU)) void conv_h2_batch_kernel(ConvBatch b) {
-    conv_h2_body<TH, BN, NTW, KC, UNPOOL, M16>(H2BatchTiles<PERSIST>{b, b.Cout / BN}, blockIdx.x);
+    conv_h2_body<TH, BN, NTW, KC, UNPOOL, M16, DIRECT>(H2BatchTiles<PERSIST>{b, b.Cout / BN}, blockIdx.x);
 }
+// the shapes the DIRECT K loop is built for (forward launches without a second source, one tile per workgroup), and its LDS:
+// the double-buffered patch alone
+template <int NTW, int KC>
+constexpr bool h2_direct_shape = (KC == 16 && NTW == 2);
+template <int TH, int BN, int NTW, int KC>
+constexpr int h2_direct_lds = 2 * H2Cfg<TH, BN, NTW, KC>::A_BYTES;
 // the shapes the persistent form is built for: the ones whose launches have more tiles than the chip holds workgroups
 template <int TH, int BN, int NTW, int KC>
 constexpr bool h2_persist_shape = (KC == 16) || (TH == 16 && NTW == 2 && KC == 32);
@@ -1315,6 +1440,11 @@ static hipError_t init_form() {
         if (e == hipSuccess)
             e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_h2_batch_kernel<TH, BN, NTW, KC, UNPOOL, false, true>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    }
+    if constexpr (h2_direct_shape<NTW, KC> && !M16 && !UNPOOL) {
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_h2_batch_kernel<TH, BN, NTW, KC, false, false, false, true>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, h2_direct_lds<TH, BN, NTW, KC>);
     }
     return e;
 }
@@ -1398,6 +1528,14 @@ static H2Shape h2_launch_shape(const int* H, const int* W, int n, int Cin, int C
     return sh;
 }
 
+// whether a launch of the decided shape runs the DIRECT K loop: a short-K forward launch that was given the layer's
+// fragment-order image, alone on its K (no second source, no un-pooling), one tile per workgroup, and a chunk count that fills
+// the loop body (two chunks with a ring of three: every Cin the launchers accept, h2_operands_ok)
+static int h2_takes_direct(const ConvBatch& b, const H2Shape& sh) {
+    constexpr int body = ((NST_H2_DIRECT_RING % 3 == 0) ? 2 : 4) * 16;
+    return (sh.chunk == 16 && sh.ntw == 2 && b.wt_h2_frag && !b.unpool && !sh.second && !sh.persist && b.Cin > 0 && b.Cin % body == 0) ? 1 : 0;
+}
+
 template <int TH, int BN, int NTW, int KC>
 static void launch_batch_cfg(const ConvBatch& b, const H2Shape& sh, int blocks, hipStream_t stream) {
     constexpr int lds = H2Cfg<TH, BN, NTW, KC>::LDS_BYTES;
@@ -1406,6 +1544,16 @@ static void launch_batch_cfg(const ConvBatch& b, const H2Shape& sh, int blocks, 
         if (sh.m16) {
             if (b.unpool) hipLaunchKernelGGL((conv_h2_batch_kernel<TH, BN, NTW, KC, true, true, false>), dim3(blocks), dim3(nt), lds, stream, b);
             else hipLaunchKernelGGL((conv_h2_batch_kernel<TH, BN, NTW, KC, false, true, false>), dim3(blocks), dim3(nt), lds, stream, b);
+            return;
+        }
+    }
+    if constexpr (h2_direct_shape<NTW, KC>) {
+        // the forward launches of the short-K shapes with the layer's fragment-order image (nst_ctx_set_h2_direct_weights): B
+        // fragments from L2, no weight slice in LDS.  Input-gradient launches (un-pooling, second source) and the persistent
+        // form stay on the parent's loop (h2_takes_direct, recorded in H2Shape::direct)
+        constexpr int lds_direct = h2_direct_lds<TH, BN, NTW, KC>;
+        if (sh.direct) {
+            hipLaunchKernelGGL((conv_h2_batch_kernel<TH, BN, NTW, KC, false, false, false, true>), dim3(blocks), dim3(nt), lds_direct, stream, b);
             return;
         }
     }
@@ -1457,7 +1605,8 @@ hipError_t launch_conv_h2_batch(const ConvBatch& b0, hipStream_t stream, H2Shape
         second = second || (im.in2 != nullptr);
     }
     int blocks = 0;
-    const H2Shape sh = h2_launch_shape(H, W, b.n, b.Cin, b.Cout, b.unpool != 0, second, b.tile_rows, b.mfma16, b.wg256, b.persist, &blocks);
+    H2Shape sh = h2_launch_shape(H, W, b.n, b.Cin, b.Cout, b.unpool != 0, second, b.tile_rows, b.mfma16, b.wg256, b.persist, &blocks);
+    sh.direct = h2_takes_direct(b, sh);
     int tiles = 0;
     for (int i = 0; i < b.n; ++i) {
         b.img[i].tiles_x = (b.img[i].W + 15) / 16;
@@ -1502,10 +1651,11 @@ hipError_t launch_conv_h2(const ConvParams& p, hipStream_t stream, H2Shape* shap
     b.n = 1;
     b.bias = p.bias;
     b.Cin = p.Cin; b.Cout = p.Cout; b.Cin2 = p.Cin2; b.relu = p.relu;
-    b.wt_h2 = p.wt_h2; b.wt_h2_inv = p.wt_h2_inv;
+    b.wt_h2 = p.wt_h2; b.wt_h2_inv = p.wt_h2_inv; b.wt_h2_frag = p.wt_h2_frag;
     b.unpool = (p.pcode_in != nullptr);
     b.persist = 0;
     b.pool_avg = p.pool_avg;
+    sh.direct = h2_takes_direct(b, sh);
     int bands = 0;
     for (int r0 = 0; r0 < p.H; r0 += band_rows) {
         const int r1 = (r0 + band_rows < p.H) ? r0 + band_rows : p.H;

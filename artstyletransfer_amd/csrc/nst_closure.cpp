@@ -31,6 +31,7 @@ hipError_t launch_conv3(nst_ctx* ctx, const ConvParams& p, Timer& t) {
         H2Shape sh{};
         const hipError_t e = launch_conv_h2(p, s, &sh);
         t.shape(sh);
+        ctx->h2_direct_launches += sh.direct ? sh.bands : 0;
         return e;
     }
     hipError_t e = launch_conv_mfma(p, 9, s);
@@ -47,12 +48,15 @@ bool bf3_unsplit(const nst_ctx* ctx, const ConvParams& p) {
     return !(p.partial && S > 1 && (size_t)S * p.H * p.W * p.Cout <= p.partial_floats);
 }
 
+// nst_ctx_set_h2_direct_weights' bit of layer l's forward launch: 1 = the 64-channel shape, 2 = the 128-channel short-K shape
+static int h2_direct_bit(int l) { return kCout[l] % 128 == 0 ? 2 : 1; }
 // Layer l's weights (dgrad: those of its input-gradient launch), the split-K workspace and the context's f16x2 launch knobs
 void conv_setup(const nst_ctx* ctx, ConvParams& p, const ActSet& a, int l, bool dgrad) {
     p.wt = dgrad ? ctx->wd[l] : ctx->wf[l]; p.wt_bf = dgrad ? ctx->wd_bf[l] : ctx->wf_bf[l];
     p.partial = a.splitk; p.partial_floats = a.splitk_floats;
     if (ctx->conv_mode != 2) return;
     p.wt_h2 = dgrad ? ctx->wd_h2[l] : ctx->wf_h2[l]; p.wt_h2_inv = dgrad ? ctx->wd_h2_inv[l] : ctx->wf_h2_inv[l];
+    p.wt_h2_frag = (!dgrad && (ctx->h2_direct_weights & h2_direct_bit(l))) ? ctx->wf_h2_frag[l] : nullptr;
     p.band_rows = ctx->band_rows; p.mfma16 = ctx->mfma16; p.wg256 = ctx->wg256; p.tile_rows = ctx->tile_rows;
 }
 // The same for one launch per layer; l = 0: a launch without 3x3 weights (the Gram term alone)
@@ -61,6 +65,7 @@ void conv_setup(const nst_ctx* ctx, ConvBatch& b, int l, bool dgrad) {
     if (l < 1) { b.wt_h2_inv = 1.f; return; }
     b.wt_bf = dgrad ? ctx->wd_bf[l] : ctx->wf_bf[l];
     b.wt_h2 = dgrad ? ctx->wd_h2[l] : ctx->wf_h2[l]; b.wt_h2_inv = dgrad ? ctx->wd_h2_inv[l] : ctx->wf_h2_inv[l];
+    b.wt_h2_frag = (!dgrad && (ctx->h2_direct_weights & h2_direct_bit(l))) ? ctx->wf_h2_frag[l] : nullptr;
     b.wt_wino = dgrad ? ctx->wd_wino[l] : ctx->wf_wino[l]; b.wt_wino_inv = dgrad ? ctx->wd_wino_inv[l] : ctx->wf_wino_inv[l];
 }
 // One conv launch for every level, under the caller's timer: the Winograd form where the layer has its weights and the
@@ -72,6 +77,7 @@ int launch_conv_batch(nst_ctx* ctx, const ConvBatch& b, hipStream_t s, Timer* t,
         H2Shape sh{};
         const hipError_t e = launch_conv_h2_batch(b, s, &sh);
         if (t) t->shape(sh);
+        ctx->h2_direct_launches += sh.direct;
         HIPCHK(ctx, e);
     } else HIPCHK(ctx, launch_conv_bf3_batch(b, s));
     return NST_OK;

@@ -178,8 +178,9 @@ static inline float f16_to_f32(uint16_t h) {
 // brings the largest |w| into [2^14, 2^15); *inv = 1 / s (same cut as conv_h2.hip::cut2x4).  kc = channels per K
 // chunk of the kernel shape that consumes these weights: 32 when `rows` (its output channels) is a multiple of
 // 128 and K (its input channels) > NST_H2_SHORTK_CIN, else 16 (conv_h2.hip, shapes in use).
+static int h2_chunk(int rows, int K) { return (rows % 128 == 0 && K > NST_H2_SHORTK_CIN) ? 32 : 16; }
 void make_h2(const float* w, int taps, int rows, int K, std::vector<uint16_t>& out, float* inv) {
-    const int kc = (rows % 128 == 0 && K > NST_H2_SHORTK_CIN) ? 32 : 16;
+    const int kc = h2_chunk(rows, K);
     const size_t n = (size_t)taps * rows * K;
     float mx = 0.f;
     for (size_t i = 0; i < n; ++i) mx = std::max(mx, std::fabs(w[i]));
@@ -198,6 +199,25 @@ void make_h2(const float* w, int taps, int rows, int K, std::vector<uint16_t>& o
                 const size_t base = (((size_t)t * rows + r) * nch + k / kc) * 2 * kc + (k % kc);
                 out[base] = uh; out[base + kc] = ul;
             }
+}
+
+// h2: make_h2's image of a 16-channel-chunk layer, [9][rows][K/16][2][16] fp16  ->  the SAME pieces in the order a lane's
+// v_mfma_f32_32x32x16_f16 B operand wants them (conv_h2.hip, DIRECT): 16-byte units [chunk][tap][rows/32][piece][lane], lane
+// (r = lane & 31, h = lane >> 5) holding input channels chunk*16 + 8 h .. + 7 of output channel tile*32 + r - one 16-byte
+// buffer load per (32-channel tile, piece) yields a fragment, and a wave walks the image front to back.
+void make_h2_frag(const std::vector<uint16_t>& h2, int rows, int K, std::vector<uint16_t>& out) {
+    const int nch = K / 16, nct = rows / 32;
+    out.assign(h2.size(), 0);
+    for (int ch = 0; ch < nch; ++ch)
+        for (int t = 0; t < 9; ++t)
+            for (int ct = 0; ct < nct; ++ct)
+                for (int s = 0; s < 2; ++s)
+                    for (int lane = 0; lane < 64; ++lane) {
+                        const int r = lane & 31, h = lane >> 5;
+                        const uint16_t* src = h2.data() + ((((size_t)t * rows + ct * 32 + r) * nch + ch) * 2 + s) * 16 + 8 * h;
+                        uint16_t* dst = out.data() + ((((((size_t)ch * 9 + t) * nct + ct) * 2 + s) * 64) + lane) * 8;
+                        for (int j = 0; j < 8; ++j) dst[j] = src[j];
+                    }
 }
 
 // w: [9 taps = ky*3 + kx][rows = Cout][K = Cin] fp32  ->  the 1-D Winograd F(2,3) weights of conv_wino.hip: for every ky the
@@ -484,6 +504,7 @@ int nst_ctx_create_ex(int device, const float* const* weights, const float* cons
     ctx->keep_all_maps = env_flag("NST_KEEP_ALL_MAPS", 0) ? 1 : 0;      // (nst_ctx_set_keep_all_maps overrides)
     ctx->forward_pack = env_flag("NST_FORWARD_PACK", 1) ? 1 : 0;        // (nst_ctx_set_forward_pack overrides)
     ctx->gram_pack = env_flag("NST_GRAM_PACK", 1) ? 1 : 0;              // (nst_ctx_set_gram_pack overrides)
+    ctx->h2_direct_weights = env_flag("NST_H2_DIRECT_WEIGHTS", NST_H2_DIRECT_DEFAULT) & 3;      // (nst_ctx_set_h2_direct_weights overrides)
     if (ctx->use_graph && hipStreamCreateWithFlags(&ctx->gstream, hipStreamNonBlocking) != hipSuccess) { ctx->err = "stream creation failed"; return bail(NST_E_HIP); }
     if (e != hipSuccess) { ctx->err = std::string("kernel attribute setup: ") + hipGetErrorString(e); return bail(NST_E_HIP); }
 
@@ -496,7 +517,8 @@ int nst_ctx_create_ex(int device, const float* const* weights, const float* cons
     };
     // tmp = [9][rows][K] cut into the 16-bit pieces of the active arithmetic only (a context is created per job: 0.24 s -
     // tools/time_ctx_create.py - and ~200 MB of weight images)
-    auto pieces = [&](int rows, int K, void*& bf, void*& h2, float& h2_inv, void*& wino, float& wino_inv) -> int {
+    std::vector<uint16_t> frag16;
+    auto pieces = [&](int rows, int K, void*& bf, void*& h2, float& h2_inv, void*& wino, float& wino_inv, void** frag) -> int {
         if (ctx->conv_mode == 1) {
             make_bf3(tmp.data(), 9, rows, K, tmp16);
             return upload(bf, tmp16.data(), tmp16.size() * 2, "weight");
@@ -504,6 +526,11 @@ int nst_ctx_create_ex(int device, const float* const* weights, const float* cons
         if (ctx->conv_mode != 2) return NST_OK;
         make_h2(tmp.data(), 9, rows, K, tmp16, &h2_inv);
         NSTCHK(upload(h2, tmp16.data(), tmp16.size() * 2, "weight"));
+        // (a forward layer on 16-channel chunks: the same pieces once more in fragment order, for its DIRECT launches)
+        if (frag && h2_chunk(rows, K) == 16 && rows % 64 == 0 && K % 16 == 0) {
+            make_h2_frag(tmp16, rows, K, frag16);
+            NSTCHK(upload(*frag, frag16.data(), frag16.size() * 2, "weight"));
+        }
         if (ctx->winograd && K >= 256 && K % 64 == 0 && rows % 128 == 0) {      // (K = 128: no gain measured)
             make_wino(tmp.data(), rows, K, tmp16, &wino_inv);
             NSTCHK(upload(wino, tmp16.data(), tmp16.size() * 2, "weight"));
@@ -536,7 +563,7 @@ int nst_ctx_create_ex(int device, const float* const* weights, const float* cons
             for (int o = 0; o < co; ++o)
                 for (int c = 0; c < ci; ++c) tmp[((size_t)t * co + o) * ci + c] = W[((size_t)o * ci + c) * 9 + t];
         if (int r = upload(ctx->wf[l], tmp.data(), n * 4, "weight")) return bail(r);
-        if (int r = pieces(co, ci, ctx->wf_bf[l], ctx->wf_h2[l], ctx->wf_h2_inv[l], ctx->wf_wino[l], ctx->wf_wino_inv[l])) return bail(r);
+        if (int r = pieces(co, ci, ctx->wf_bf[l], ctx->wf_h2[l], ctx->wf_h2_inv[l], ctx->wf_wino[l], ctx->wf_wino_inv[l], &ctx->wf_h2_frag[l])) return bail(r);
         // input gradient: a conv with "Cout" = ci and "Cin" = co: wd[tap'][ci][co] = W[co][ci][2-ky'][2-kx']
         for (int t = 0; t < 9; ++t) {
             const int ky = 2 - t / 3, kx = 2 - t % 3;
@@ -544,7 +571,7 @@ int nst_ctx_create_ex(int device, const float* const* weights, const float* cons
                 for (int o = 0; o < co; ++o) tmp[((size_t)t * ci + c) * co + o] = W[((size_t)o * ci + c) * 9 + ky * 3 + kx];
         }
         if (int r = upload(ctx->wd[l], tmp.data(), n * 4, "weight")) return bail(r);
-        if (int r = pieces(ci, co, ctx->wd_bf[l], ctx->wd_h2[l], ctx->wd_h2_inv[l], ctx->wd_wino[l], ctx->wd_wino_inv[l])) return bail(r);
+        if (int r = pieces(ci, co, ctx->wd_bf[l], ctx->wd_h2[l], ctx->wd_h2_inv[l], ctx->wd_wino[l], ctx->wd_wino_inv[l], nullptr)) return bail(r);
     }
     if (ctx->level_split) ctx->gram_overlap = 0;      // (one side stream: the two experiments exclude each other)
     if ((ctx->gram_overlap || ctx->level_split) && ctx->conv_mode == 2 &&
@@ -731,6 +758,20 @@ int nst_ctx_set_gram_pack(nst_ctx* ctx, int enabled) {
     return NST_OK;
 }
 int nst_ctx_gram_pack(const nst_ctx* ctx) { return ctx ? ctx->gram_pack : -1; }
+
+// The A/B twin of the DIRECT K loop in one build: 0 = the forward launches of the 16-channel-chunk conv_h2 shapes stage
+// their weight slices through LDS as before.  Results do not depend on it (conv_h2.hip: every accumulator sees the same
+// MFMAs on the same operands in the same order); a captured graph holds the kernels of the setting it was captured under.
+int nst_ctx_set_h2_direct_weights(nst_ctx* ctx, int enabled) {
+    NSTCHK(bind(ctx));
+    ++ctx->ws_seq;
+    drop_closure_state(ctx, false);
+    if (enabled < 0 || enabled > 3) return fail(ctx, NST_E_ARG, "h2_direct_weights must be 0 .. 3");
+    ctx->h2_direct_weights = enabled;
+    return NST_OK;
+}
+int nst_ctx_h2_direct_weights(const nst_ctx* ctx) { return ctx ? ctx->h2_direct_weights : -1; }
+long long nst_ctx_h2_direct_launches(const nst_ctx* ctx) { return ctx ? (long long)ctx->h2_direct_launches : -1; }
 
 int nst_job_map_stats(nst_ctx* ctx, int level, unsigned* stored_mask) {
     NSTCHK(bind(ctx));

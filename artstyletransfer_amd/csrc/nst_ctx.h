@@ -297,6 +297,13 @@ struct nst_ctx {
     // nst_ctx_set_gram_pack: 1 = the fp16-piece Gram kernels skip the blocks below the diagonal of a diagonal tile and a
     // plain batch takes both tile shapes in one launch; 0 = the kernels and the two launches from before
     int gram_pack = 1;
+    // nst_ctx_set_h2_direct_weights: which forward launches of the 16-channel-chunk conv_h2 shapes take their B fragments
+    // from wf_h2_frag (L2 -> registers, one barrier per chunk): bit 0 = <16,64,2,16> (conv1_2), bit 1 = <8,128,2,16>
+    // (conv2_1, conv2_2, conv3_1); 0 = the weight slices go through LDS as before.  The default is decided per shape
+    // (profiles/r21_h2_direct_weights.txt).  The images exist either way (2.2 MB), so the switch works in both directions.
+    int h2_direct_weights = NST_H2_DIRECT_DEFAULT;
+    unsigned long long h2_direct_launches = 0;      // conv_h2 launches that ran the DIRECT K loop (nst_ctx_h2_direct_launches)
+    void* wf_h2_frag[nst::NL] = {};      // wf_h2's pieces in MFMA fragment order (make_h2_frag); nullptr: not a short-K layer
     unsigned long long fwd_pass = 0;     // batched forward passes so far (ActSet::pass)
     hipStream_t side = nullptr; // the Gram launches of the shallow style layers run here, under the deeper forward convolutions
     hipEvent_t side_fork = nullptr, side_join = nullptr;

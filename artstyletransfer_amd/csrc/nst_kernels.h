@@ -53,8 +53,16 @@ struct ConvParams {
     // multi-hot code bit q = (e_q > 0) (launch-uniform: a scalar branch in the epilogues).  The un-pooling loaders test every
     // position's bit on its own and are the same for both; the 1/4 of the average's backward rides on wt_h2_inv.
     int pool_avg;
+    // conv_h2, forward launches of the 16-channel-chunk shapes (nst_ctx_set_h2_direct_weights): the pieces of wt_h2 in MFMA
+    // FRAGMENT order (conv_h2.hip, DIRECT; make_h2_frag has the layout); nullptr: the weight slices go through LDS
+    const void* wt_h2_frag;
 };
 
+// nst_ctx_set_h2_direct_weights' default: the shapes whose forward launches run the DIRECT K loop (bit 0: <16,64,2,16>, bit 1:
+// <8,128,2,16>), decided per shape from the kernel traces of profiles/r21_h2_direct_weights.txt
+#ifndef NST_H2_DIRECT_DEFAULT
+#define NST_H2_DIRECT_DEFAULT 3
+#endif
 constexpr int NST_AMAX_SLOTS = 64;
 // conv_h2: launches with at most this many input channels (K <= 1152) use the 16-channel-chunk shapes, and the
 // host lays their pre-cut weights out in 16-channel chunks (make_h2)
@@ -104,6 +112,7 @@ struct ConvBatch {
     const void* wt_wino;     // conv_wino: the layer's transformed weights in fragment order (nullptr: none)
     float wt_wino_inv;
     int pool_avg;            // see ConvParams
+    const void* wt_h2_frag;  // conv_h2: see ConvParams (nullptr: none)
 };
 
 // conv_wino.hip: forward 3x3 convolution as 1-D Winograd F(2,3) in the f16x2 arithmetic (nst_options.h2_winograd)
@@ -137,6 +146,7 @@ struct H2Shape {
     int persist;                // persistent workgroups (launch_conv_h2_batch only)
     int second, unpool;         // the launch has a second K source / un-pools its input in the loader
     int bands;                  // kernel launches it took (per-level launcher: one one-image batch per row band; else 1)
+    int direct;                 // the DIRECT K loop: B fragments from the layer's fragment-order image (ConvParams::wt_h2_frag)
 };
 hipError_t launch_conv_h2(const ConvParams& p, hipStream_t stream, H2Shape* shape = nullptr);
 hipError_t launch_conv_h2_batch(const ConvBatch& b, hipStream_t stream, H2Shape* shape = nullptr);

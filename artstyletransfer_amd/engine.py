@@ -85,7 +85,8 @@ class StyleEngine:
                  h2_tile_rows: Optional[int] = None, gram_overlap: Optional[bool] = None,
                  h2_persist: Optional[bool] = None, level_split: Optional[bool] = None,
                  h2_winograd: Optional[bool] = None, keep_all_maps: Optional[bool] = None,
-                 forward_pack: Optional[bool] = None, gram_pack: Optional[bool] = None):
+                 forward_pack: Optional[bool] = None, gram_pack: Optional[bool] = None,
+                 h2_direct_weights: Optional[bool] = None):
         """Options (nst_options): None = environment variable (NST_CONV, NST_BATCH, NST_SINGLE_STREAM, NST_GRAPH,
         NST_H2_BAND_ROWS, NST_LBFGS_GRAM, NST_H2_MFMA16; read once, here) and otherwise the default (f16x2, batched, ...).
         keep_all_maps (nst_ctx_set_keep_all_maps; None = env NST_KEEP_ALL_MAPS, default off): every batched forward launch
@@ -93,7 +94,11 @@ class StyleEngine:
         forward_pack (nst_ctx_set_forward_pack; None = env NST_FORWARD_PACK, default on): False = the forward half's front and
         loss terms launched per pyramid level, S also written in bf16 pieces - same results, the A/B twin of the packing.
         gram_pack (nst_ctx_set_gram_pack; None = env NST_GRAM_PACK, default on): False = the Gram partial kernels compute every
-        block of a diagonal tile and a batch launches once per tile shape - same results, the A/B twin of the packed Gram pass."""
+        block of a diagonal tile and a batch launches once per tile shape - same results, the A/B twin of the packed Gram pass.
+        h2_direct_weights (nst_ctx_set_h2_direct_weights; None = env NST_H2_DIRECT_WEIGHTS, default on): False = the forward
+        launches of conv1_2, conv2_1, conv2_2 and conv3_1 stage their weight slices through LDS instead of reading fragments
+        from L2 - same results, the A/B twin of the one-barrier-per-chunk K loop.  True = both kernel shapes; an int is the
+        setter's mask (1 = conv1_2's shape, 2 = the shape of the other three)."""
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise NstError("no GPU visible: the style-transfer hot path runs only on the HIP device")
@@ -129,6 +134,10 @@ class StyleEngine:
             _lib.check(self.ctx, self.lib.nst_ctx_set_forward_pack(self.ctx, int(bool(forward_pack))), "nst_ctx_set_forward_pack")
         if gram_pack is not None:
             _lib.check(self.ctx, self.lib.nst_ctx_set_gram_pack(self.ctx, int(bool(gram_pack))), "nst_ctx_set_gram_pack")
+        if h2_direct_weights is not None:
+            _lib.check(self.ctx, self.lib.nst_ctx_set_h2_direct_weights(
+                self.ctx, 3 if h2_direct_weights is True else int(h2_direct_weights)),
+                       "nst_ctx_set_h2_direct_weights")
         self.weights_id = id(weights)          # which weight set this context carries (neural_nets' engine pool)
         self.levels = 0
         self.shape = None

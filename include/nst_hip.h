@@ -777,6 +777,21 @@ int nst_ctx_forward_pack(const nst_ctx* ctx);
  *     for a null context. */
 int nst_ctx_set_gram_pack(nst_ctx* ctx, int enabled);
 int nst_ctx_gram_pack(const nst_ctx* ctx);
+/* Weight fragments from L2 in the short-K forward launches (on by default).  The forward launches of the f16x2 direct kernel
+ * that run on 16-channel chunks - conv1_2, conv2_1, conv2_2, conv3_1 - read their weight fragments straight from a second
+ * image of the layer's fp16 pieces, laid out in MFMA fragment order when the context is created (2.2 MB, counted in
+ * nst_ctx_bytes), instead of staging a slice per tap through LDS: one workgroup barrier per 16-channel chunk instead of one
+ * per tap.  Every accumulator sees the same products in the same order: all maps, losses and gradients are bitwise the same.
+ * The input-gradient launches of those shapes are not affected.
+ *   nst_ctx_set_h2_direct_weights(ctx, 0): the weight slices go through LDS - the A/B twin in one build.  Otherwise a mask of
+ *     kernel shapes: 1 = the 64-channel shape (conv1_2), 2 = the 128-channel short-K shape (conv2_1, conv2_2, conv3_1), 3 =
+ *     both; NST_E_ARG outside 0 .. 3.  A new context takes env NST_H2_DIRECT_WEIGHTS (read once at creation); the default, 3, is
+ *     the set of shapes that measured faster (profiles/r21_h2_direct_weights.txt).  nst_ctx_h2_direct_weights: the setting, -1
+ *     for a null context.  nst_ctx_h2_direct_launches: conv_h2 launches of this context that ran the new loop so far (-1 for a
+ *     null context) - a launch that quietly stayed on the other loop is one this count misses. */
+int nst_ctx_set_h2_direct_weights(nst_ctx* ctx, int enabled);
+int nst_ctx_h2_direct_weights(const nst_ctx* ctx);
+long long nst_ctx_h2_direct_launches(const nst_ctx* ctx);
 /* The image of pyramid level `level` >= 1 that the last closure evaluated - the bicubic 1/2 chain of x
  * (neural_style_transfer.py:170-176) - as (3,h_l,w_l) planar fp32 to out (device).  The total-variation term takes
  * sign(y_i - y_j) of neighbouring pixels: on flat image regions those differences are rounding noise of the down-sampling,
