@@ -95,6 +95,11 @@ SYMBOLS = {
                                   c_void, c_void]),
     "nst_patch_term": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, C.c_int, C.c_int, C.c_int, c_void, C.c_float,
                                  c_void, c_void, c_void]),
+    "nst_level_set_patch_guidance": (C.c_int, [c_void, C.c_int, C.c_int, c_void, c_void, C.c_float, c_void]),
+    "nst_level_patch_guidance": (C.c_int, [c_void, C.c_int, C.POINTER(C.c_int), c_float_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "nst_patch_descriptors": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, c_void, c_void]),
+    "nst_patch_match_guided": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, C.c_int, C.c_int, C.c_int, C.c_double,
+                                         C.c_int, c_void, c_void, C.c_float, c_void, c_void, c_void]),
     "nst_warp_bilinear": (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, c_void, c_void]),
     "nst_flow_weights": (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, c_void, c_void]),
     "nst_anchor_fold": (C.c_int, [c_void, C.c_int, C.POINTER(c_void), C.POINTER(c_void), C.c_int, C.c_int, C.c_int, c_void, c_void,

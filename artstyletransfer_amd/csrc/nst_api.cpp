@@ -319,6 +319,62 @@ int nst_patch_match(nst_ctx* ctx, const float* f, int h, int w, int C, const flo
     return sc.finish();
 }
 
+// The descriptors of the guided search alone: planes at the MAP's resolution -> (count, 4), count the entries of the
+// stride-`stride` geometry of an hm x wm map.
+int nst_patch_descriptors(nst_ctx* ctx, const float* planes, int R, int hm, int wm, int stride, double epsilon, float* out, void* stream) {
+    NSTCHK(bind(ctx));
+    if (!planes || !out) return fail(ctx, NST_E_ARG, "null argument");
+    if (R < 1 || R > NST_MAX_REGIONS) return fail(ctx, NST_E_ARG, "the number of regions must be 1 .. NST_MAX_REGIONS");
+    if (hm < 3 || wm < 3) return fail(ctx, NST_E_ARG, "the map must be at least 3x3");
+    if (stride < 1 || stride > 8) return fail(ctx, NST_E_ARG, "the style stride must be 1..8");
+    if (!(epsilon > 0.0) || std::isinf(epsilon)) return fail(ctx, NST_E_ARG, "the patch epsilon must be finite and > 0");
+    const long long count = (long long)((hm - 3) / stride + 1) * ((wm - 3) / stride + 1);
+    if (count > (1ll << 30) || (double)R * hm * wm >= 2147483648.0) return fail(ctx, NST_E_ARG, "the map is too large");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIPCHK(ctx, launch_pm_descriptors(planes, R, hm, wm, stride, epsilon, (int)count, out, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return NST_OK;
+}
+
+// nst_patch_match under guidance: the norms of the image patches and a zero-padded copy of e on scratch, then the guided search
+int nst_patch_match_guided(nst_ctx* ctx, const float* f, int h, int w, int C, const float* fs, int hs, int ws, int stride, double epsilon,
+                           int R, const float* d_img, const float* e_dict, float gamma, int* idx_out, float* score_out, void* stream) {
+    NSTCHK(bind(ctx));
+    PatchDict d;
+    NSTCHK(patch_args(ctx, f, h, w, C, fs, hs, ws, stride, &d));
+    if ((!idx_out && !score_out) || !d_img || !e_dict) return fail(ctx, NST_E_ARG, "null argument");
+    if (!(epsilon > 0.0) || std::isinf(epsilon)) return fail(ctx, NST_E_ARG, "the patch epsilon must be finite and > 0");
+    if (R < 1 || R > NST_MAX_REGIONS) return fail(ctx, NST_E_ARG, "the number of regions must be 1 .. NST_MAX_REGIONS");
+    if (!(gamma >= 0.f) || std::isinf(gamma)) return fail(ctx, NST_E_ARG, "the semantic weight must be finite and >= 0");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t n = (size_t)(h - 2) * (w - 2), padded = (size_t)pm_dict_tiles(d.m) * 32;
+    PatchDict own{};
+    own.fs = f;
+    if (!pm_dict_geometry(h, w, C, 1, &own)) return fail(ctx, NST_E_ARG, "bad map geometry");
+    Scratch sc(ctx, s);
+    unsigned* amax = nullptr; float* rq = nullptr; unsigned char* packed = nullptr; unsigned long long* keys = nullptr;
+    float* rp = nullptr; float* ge = nullptr;
+    NSTCHK(sc.alloc(&amax, (size_t)2 * NST_AMAX_SLOTS));
+    NSTCHK(sc.alloc(&rq, padded));
+    NSTCHK(sc.alloc(&packed, pm_packed_bytes(d.m, C)));
+    NSTCHK(sc.alloc(&keys, n));
+    NSTCHK(sc.alloc(&rp, (size_t)pm_dict_tiles((int)n) * 32));
+    NSTCHK(sc.alloc(&ge, padded * 4));
+    HIPCHK(ctx, launch_pm_prepare(d, epsilon, amax, rq, packed, s));
+    d.amax = amax; d.rq = rq; d.packed = packed;
+    unsigned* amax_f = amax + NST_AMAX_SLOTS;
+    HIPCHK(ctx, launch_zero(amax_f, NST_AMAX_SLOTS, s));
+    HIPCHK(ctx, launch_absmax_slots(f, (size_t)h * w * C, amax_f, s));
+    HIPCHK(ctx, launch_pm_norms(own, epsilon, rp, s));
+    HIPCHK(ctx, hipMemsetAsync(ge, 0, padded * 4 * sizeof(float), s));
+    HIPCHK(ctx, hipMemcpyAsync(ge, e_dict, (size_t)d.m * 4 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    PatchSearch p{};
+    p.f = f; p.h = h; p.w = w; p.C = C; p.amax_f = amax_f; p.d = d; p.keys = keys;
+    p.gd = d_img; p.ge = ge; p.rp = rp; p.gamma = gamma;
+    HIPCHK(ctx, launch_pm_search(p, idx_out, score_out, s));
+    return sc.finish();
+}
+
 int nst_patch_term(nst_ctx* ctx, const float* f, int h, int w, int C, const float* fs, int hs, int ws, int stride, const int* idx,
                    float coef, float* value_out, float* grad_out, void* stream) {
     NSTCHK(bind(ctx));

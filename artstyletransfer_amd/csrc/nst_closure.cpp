@@ -274,6 +274,16 @@ int patch_forward(nst_ctx* ctx, LevelWs& L, hipStream_t s) {
         const PatchTerm t = patch_term_of(L, i);
         PatchSearch p{};
         p.f = t.f; p.h = t.h; p.w = t.w; p.C = kCout[l]; p.amax_f = amax_act(L.acts, l); p.d = t.d; p.keys = L.pm.keys[i];
+        if (L.pm.sem.R > 0) {
+            // a guided level (nst_level_set_patch_guidance): the norms of the map's own patches - a stride-1 geometry of the
+            // map has them as its entries - then the guided search
+            Timer tm(ctx, s, K_OTHER, 0, t.h, t.w, kCout[l], 0, 9, 200 + i);      // (layer tag 200 + map index: the rp pass)
+            PatchDict own{};
+            own.fs = t.f;
+            if (!pm_dict_geometry(t.h, t.w, kCout[l], 1, &own)) return fail(ctx, NST_E_STATE, "a guided map has no patch geometry");
+            HIPCHK(ctx, launch_pm_norms(own, L.pm.eps, L.pm.sem.rp[i], s));
+            p.gd = L.pm.sem.gd[i]; p.ge = L.pm.sem.ge[i]; p.rp = L.pm.sem.rp[i]; p.gamma = L.pm.sem.gamma;
+        }
         {
             Timer tm(ctx, s, K_OTHER, 2.0 * (double)(t.h - 2) * (t.w - 2) * (double)t.d.m * 9.0 * kCout[l], t.h, t.w, kCout[l], t.d.m, 9, 100 + i);
             HIPCHK(ctx, launch_pm_search(p, L.pm.nn[i], nullptr, s));

@@ -1114,7 +1114,7 @@ int nst_level_set_patches(nst_ctx* ctx, int level, const float* style, int hs, i
                 return fail(ctx, NST_E_ARG, "a weighted map or its style map is below 3x3");
             deepest = l;
         }
-        g.stride = stride; g.eps = epsilon;
+        g.stride = stride; g.eps = epsilon; g.hs = hs; g.ws = ws;
         Scratch sc(ctx, s);
         NSTCHK(alloc_acts(ctx, sc.acts, hs, ws));
         NSTCHK(forward(ctx, sc.acts, style, hs, ws, s, deepest, ctx->channels));
@@ -1188,6 +1188,83 @@ int nst_level_patch_matches(nst_ctx* ctx, int level, int map, int* idx_out, void
     hipStream_t s = enter(ctx, stream);
     HIPCHK(ctx, hipMemcpyAsync(idx_out, L.pm.nn[map], n * sizeof(int), hipMemcpyDeviceToDevice, s));
     mark(ctx, s);
+    return NST_OK;
+}
+
+// The semantic guidance of a level's MRF term (neural-doodle; include/nst_hip.h has the definition).  The planes of both sides
+// are checked for their range and pooled on scratch; what stays with the level - in PatchGuide's own block, beside the old one
+// until the call has succeeded - are the descriptors of every weighted map and the buffer of the image patches' norms.  The
+// life cycle is that of nst_level_set_patches.  R = 0, gamma = 0 or null planes clear.
+int nst_level_set_patch_guidance(nst_ctx* ctx, int level, int R, const float* content_planes, const float* style_planes, float gamma,
+                                 void* stream) {
+    if (ctx) { ++ctx->closure_epoch; ++ctx->ws_seq; }
+    NSTCHK(bind(ctx));
+    if (ctx->levels < 1) return fail(ctx, NST_E_STATE, "nst_job_configure has not been called");
+    if (level < 0 || level >= ctx->levels) return fail(ctx, NST_E_ARG, "level out of range");
+    if (R < 0 || R > NST_MAX_REGIONS) return fail(ctx, NST_E_ARG, "the number of regions must be 0 .. NST_MAX_REGIONS");
+    if (!(gamma >= 0.f) || std::isinf(gamma)) return fail(ctx, NST_E_ARG, "the semantic weight must be finite and >= 0");
+    LevelWs& L = ctx->lv[level];
+    PatchGuide g;
+    hipStream_t s = enter(ctx, stream);
+    if (R > 0 && gamma > 0.f && content_planes && style_planes) {
+        if (!L.pm.on()) return fail(ctx, NST_E_STATE, "the level carries no MRF term (nst_level_set_patches first)");
+        g.R = R; g.gamma = gamma;
+        int deepest = 0;                               // the deepest network scale among the weighted maps
+        for (int i = 0; i < 6; ++i)
+            if (L.pm.w[i] > 0.f && kScale[kTapLayer[i]] > deepest) deepest = kScale[kTapLayer[i]];
+        Scratch sc(ctx, s);
+        // both pyramids: side 0 the level image's planes, side 1 the style image's; off[k][scale] in floats
+        const float* src[2] = {content_planes, style_planes};
+        const int hh[2] = {L.h, L.pm.hs}, ww[2] = {L.w, L.pm.ws};
+        float* pyr[2] = {};
+        size_t off[2][6];
+        double* dscratch = nullptr;
+        NSTCHK(sc.alloc(&dscratch, ((size_t)R * GUIDE_MASS_BLOCKS + 2 * R) * 2));
+        double* counts = dscratch + (size_t)R * GUIDE_MASS_BLOCKS * 2;
+        for (int k = 0; k < 2; ++k) {
+            off[k][0] = 0;
+            for (int scl = 0; scl < 5; ++scl) off[k][scl + 1] = off[k][scl] + (size_t)R * (hh[k] >> scl) * (ww[k] >> scl);
+            NSTCHK(sc.alloc(&pyr[k], off[k][deepest + 1]));
+            HIPCHK(ctx, hipMemcpyAsync(pyr[k], src[k], (size_t)R * hh[k] * ww[k] * sizeof(float), hipMemcpyDeviceToDevice, s));
+            // (mass, values outside [0,1] or not finite) of every plane: the count is what is asked here - a region may be empty
+            HIPCHK(ctx, launch_guide_mass(pyr[k], R, (size_t)hh[k] * ww[k], dscratch, counts + (size_t)k * R * 2, s));
+            for (int scl = 1; scl <= deepest; ++scl)
+                HIPCHK(ctx, launch_guide_pool(pyr[k] + off[k][scl - 1], R, hh[k] >> (scl - 1), ww[k] >> (scl - 1), pyr[k] + off[k][scl], s));
+        }
+        double host[2 * NST_MAX_REGIONS * 2];
+        HIPCHK(ctx, hipMemcpyAsync(host, counts, (size_t)2 * R * 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+        for (int k = 0; k < 2 * R; ++k)
+            if (host[2 * k + 1] > 0.0) return fail(ctx, NST_E_ARG, "semantic plane values must be finite and in [0,1]");
+        for (int i = 0; i < 6; ++i) {
+            if (!(L.pm.w[i] > 0.f)) continue;
+            const int l = kTapLayer[i], scl = kScale[l];
+            const PatchDict& d = L.pm.d[i];
+            const int hm = L.acts.h[l], wm = L.acts.w[l];
+            const int n = (hm - 2) * (wm - 2), padded = pm_dict_tiles(d.m) * 32;
+            NSTCHK(g.mem.alloc(ctx, &g.gd[i], (size_t)n * 4));
+            NSTCHK(g.mem.alloc(ctx, &g.ge[i], (size_t)padded * 4));
+            NSTCHK(g.mem.alloc(ctx, &g.rp[i], (size_t)pm_dict_tiles(n) * 32));
+            HIPCHK(ctx, launch_pm_descriptors(pyr[0] + off[0][scl], R, hm, wm, 1, L.pm.eps, n, g.gd[i], s));
+            HIPCHK(ctx, launch_pm_descriptors(pyr[1] + off[1][scl], R, d.hs, d.ws, d.stride, L.pm.eps, padded, g.ge[i], s));
+            HIPCHK(ctx, hipMemsetAsync(g.rp[i], 0, (size_t)pm_dict_tiles(n) * 32 * sizeof(float), s));
+        }
+        NSTCHK(sc.finish());       // (synchronises: the caller's planes are free again when this returns)
+    }
+    quiesce(ctx);
+    drop_closure_state(ctx, false);
+    L.pm.sem = std::move(g);
+    return NST_OK;
+}
+
+int nst_level_patch_guidance(const nst_ctx* ctx, int level, int* R, float* gamma, int* hs, int* ws) {
+    if (!ctx) return fail(nullptr, NST_E_ARG, "null context");
+    if (level < 0 || level >= ctx->levels) return fail(nullptr, NST_E_ARG, "level out of range");
+    const PatchGuide& g = ctx->lv[level].pm.sem;
+    if (R) *R = g.R;
+    if (gamma) *gamma = g.gamma;
+    if (hs) *hs = ctx->lv[level].pm.hs;
+    if (ws) *ws = ctx->lv[level].pm.ws;
     return NST_OK;
 }
 

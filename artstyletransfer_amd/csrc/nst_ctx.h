@@ -205,10 +205,26 @@ struct AnchorLevel {
 // keys, nn and the value partials of the last closure, and the unweighted mrf_i (six floats, which the forward half writes
 // and the loss rows read).  Data of one job, not a setting: made by the setter, freed when the level's term is cleared, the
 // taps, the pooling or the colour mode are set or the job is configured again: a closure allocates nothing.
+// The semantic guidance of a level's MRF term (nst_level_set_patch_guidance; include/nst_hip.h has the definition), by map
+// index of the weighted maps: the descriptors of the image patches (n x 4) and of the dictionary entries (32 pm_dict_tiles(m)
+// x 4, zeros behind entry m), both made by the setter from the pooled planes, and the image patches' norms rp (32
+// pm_dict_tiles(n) floats), which the forward half writes before every guided search.  Part of PatchLevel: whatever drops the
+// level's term drops its guidance.
+struct PatchGuide {
+    int R = 0;                  // 0: the level's search is unguided
+    float gamma = 0.f;
+    float* gd[6] = {};
+    float* ge[6] = {};
+    float* rp[6] = {};
+    DevMem mem;
+};
+
 struct PatchLevel {
     float w[6] = {};
     int stride = 1;
     double eps = 1e-5;
+    int hs = 0, ws = 0;         // the style image of nst_level_set_patches: the size of the guidance's style planes
+    PatchGuide sem;
     PatchDict d[6] = {};
     unsigned long long* keys[6] = {};
     int* nn[6] = {};

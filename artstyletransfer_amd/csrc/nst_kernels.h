@@ -514,14 +514,28 @@ __host__ __device__ inline int pm_dict_tiles(int m) { return (m + 31) / 32; }
 size_t pm_packed_bytes(int m, int C);
 bool pm_dict_geometry(int hs, int ws, int C, int stride, PatchDict* d);
 hipError_t launch_pm_prepare(const PatchDict& d, double epsilon, unsigned* amax, float* rq, void* packed, hipStream_t stream);
+// The norms alone: out[j] = (float)(1 / sqrt(|Q_j|^2 + epsilon)) of the 32 pm_dict_tiles(m) entries of the geometry (zeros behind
+// entry m); d.fs and the integers of d are read.  launch_pm_prepare's rq, and - on a stride-1 geometry of the IMAGE map, whose
+// entries are the n image patches - the rp_i of the guided search.
+hipError_t launch_pm_norms(const PatchDict& d, double epsilon, float* out, hipStream_t stream);
+// The semantic descriptors of the guided search (include/nst_hip.h has the definition): planes (R, hm, wm) at the map's
+// resolution, R = 1..4; out = `padded` x 4 floats, the descriptors of the stride-`stride` geometry's entries and zeros behind
+// them (padded >= the entry count: 32 pm_dict_tiles(m) for a dictionary, n for the image).
+hipError_t launch_pm_descriptors(const float* planes, int R, int hm, int wm, int stride, double epsilon, int padded, float* out,
+                                 hipStream_t stream);
 // The search: nn and score of every 3x3 patch of f (NHWC, h x w x C; amax_f: its absmax record) against the dictionary.  keys:
 // (h - 2)(w - 2) 64-bit words of scratch, which the launch clears and the kernel raises by atomicMax; idx / score (nullable):
-// what the keys decode to.  (tiles_x, tiles_y, cshift: the launcher's.)
-struct PatchSearch {
+// what the keys decode to.  (tiles_x, tiles_y, cshift: the launcher's.)  The guidance (all null: the unguided search and its
+// kernels): gd = n x 4 descriptors of the image patches, ge = 32 pm_dict_tiles(m) x 4 of the entries, rp = the image patches'
+// norms (launch_pm_norms), gamma >= 0; the score is then cos(i, j) + gamma <d_i, e_j>.
+struct PatchSearchCore {       // (what the unguided kernels take: their argument block is what it was)
     const float* f; int h, w, C; const unsigned* amax_f;
     PatchDict d;
     unsigned long long* keys;
     int tiles_x, tiles_y, cshift;
+};
+struct PatchSearch : PatchSearchCore {
+    const float* gd; const float* ge; const float* rp; float gamma;
 };
 hipError_t launch_pm_search(const PatchSearch& p, int* idx, float* score, hipStream_t stream);
 // Value and gradient at fixed idx (d.fs and the integers of d are read; entries outside [0, m) are clamped).  The value in two

@@ -6,7 +6,10 @@
 //                      scale of conv_h2.hip) and laid out in the lane order of the MFMA's row operand
 //   pm_search_kernel   the search: an implicit GEMM, rows = dictionary entries, columns = image patches, K = 9 C as
 //                      (tap, 16 channels), on v_mfma_f32_32x32x16_f16 with three MFMAs per product block; the epilogue
-//                      scales a row by rq_j and folds it into a running (score, index) key per column
+//                      scales a row by rq_j and folds it into a running (score, index) key per column; the guided
+//                      instantiation (SEM) also scales by the column's rp_i and adds gamma <d_i, e_j>
+//   pm_desc_kernel     the semantic descriptors of the guided search (nst_level_set_patch_guidance): per patch the nine-tap sums
+//                      of R pooled planes, normalised, as four floats
 //   pm_decode_kernel   keys -> nn (int32) and score
 //   pm_value_kernel    sum_i |P_i - Q_nn(i)|^2 in double, two ordered stages (pm_value_finish_kernel: the second)
 //   pm_grad_kernel     the gradient at fixed nn, in gather form: nine taps per pixel, 16-byte channel runs
@@ -19,6 +22,8 @@
 // bit pattern of the score above ~j), which is independent of arrival order and resolves equal scores to the lowest j.
 // There is no float atomic here.
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "nst_kernels.h"
 
@@ -76,7 +81,8 @@ __device__ __forceinline__ void dict_centre(const PatchDict& d, int j, int& cy, 
 }
 
 // ---- dictionary preparation ---------------------------------------------------------------------------------------------
-// one wave per entry; the padding entries of the last tile get rq = 0
+// one wave per entry; the padding entries of the last tile get rq = 0.  The guided search runs it on the image map too: a
+// stride-1 geometry of the map has exactly the n image patches as its entries, and rp_i is rq_j's formula
 __global__ __launch_bounds__(256) void pm_rq_kernel(PatchDict d, double epsilon, float* __restrict__ rq) {
     const int lane = threadIdx.x & 63;
     const int j = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
@@ -130,6 +136,40 @@ __global__ __launch_bounds__(256) void pm_pack_kernel(PatchDict d, unsigned char
     }
 }
 
+// one thread per entry of a stride-`stride` geometry of the (R, hm, wm) planes, nb entries a row: a[r] = the nine taps of
+// plane r in row-major order, d = (float)(a / sqrt(sum_r a[r]^2 + epsilon)), all in double; entries r >= R and the entries
+// [count, padded) are zero
+__global__ __launch_bounds__(256) void pm_desc_kernel(const float* __restrict__ planes, int R, int hm, int wm, int stride, int nb, int count,
+                                                      int padded, double epsilon, float* __restrict__ out) {
+#pragma clang fp contract(off)
+    const int j = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (j >= padded) return;
+    f32x4 d = {0.f, 0.f, 0.f, 0.f};
+    if (j < count) {
+        const int a = j / nb, b = j - a * nb;
+        const int y0 = a * stride, x0 = b * stride;      // the patch's first pixel: its centre is (1 + a stride, 1 + b stride)
+        double acc[4] = {0.0, 0.0, 0.0, 0.0};
+        double ss = 0.0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            if (r < R) {
+                const float* pl = planes + ((size_t)r * hm + y0) * wm + x0;
+                double t = 0.0;
+#pragma unroll
+                for (int ty = 0; ty < 3; ++ty)
+#pragma unroll
+                    for (int tx = 0; tx < 3; ++tx) t += (double)pl[(size_t)ty * wm + tx];
+                acc[r] = t;
+                ss += t * t;
+            }
+        }
+        const double nrm = sqrt(ss + epsilon);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) d[r] = r < R ? (float)(acc[r] / nrm) : 0.f;
+    }
+    *reinterpret_cast<f32x4*>(out + (size_t)j * 4) = d;
+}
+
 // ---- the search ---------------------------------------------------------------------------------------------------------
 // A workgroup (8 waves) owns 4 x 8 NCT image patches.  It stages their 6 x (8 NCT + 2) halo, all C channels, cut into the two
 // pieces, once in LDS: a pixel's row holds per 8 channels 16 B of hi and 16 B of lo, C / 8 such groups, + 16 B pad (an odd
@@ -138,6 +178,9 @@ __global__ __launch_bounds__(256) void pm_pack_kernel(PatchDict d, unsigned char
 // ...; a tile's row fragments come straight from global memory (two 1-KiB loads per k-step, prefetched PF k-steps ahead), the
 // column fragments from LDS.  Registers per lane: 32 NCT accumulators, 16 PF row fragments in flight, 8 NCT column
 // fragments, 2 NCT key words.
+// SEM (the guided search, include/nst_hip.h): T(i, j) = cos(i, j) + gamma <d_i, e_j>.  The row's e_j is one 16-byte load beside
+// the rq load; the column's d_i and rp_i are fetched in the epilogue, once per tile, and not held over the K loop (NCT = 4 has
+// 206 of 256 VGPRs in use without them).  SEM = false is the unguided kernel as it was.
 template <int NCT>
 struct PmCfg {
     static constexpr int TY = 4, TX = 8 * NCT;
@@ -152,8 +195,8 @@ __device__ __forceinline__ unsigned score_order(float v) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
-template <int NCT>
-__global__ __launch_bounds__(512) void pm_search_kernel(PatchSearch p) {
+template <int NCT, bool SEM>
+__global__ __launch_bounds__(512) void pm_search_kernel(std::conditional_t<SEM, PatchSearch, PatchSearchCore> p) {
     using Cf = PmCfg<NCT>;
     constexpr int PF = Cf::PF;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -254,16 +297,44 @@ __global__ __launch_bounds__(512) void pm_search_kernel(PatchSearch p) {
             // the tile is complete: register e of a lane is row (e & 3) + 8 (e >> 2) + 4 hh, entry j = 32 tile + row
 #pragma clang fp contract(off)
             const int j0 = (g0 + tl * gstride) * 32;
+            // the guided search: d_i and rp_i of this lane's NCT columns (a column outside the map reads the nearest patch's:
+            // its key is never written)
+            f32x4 dcol[SEM ? NCT : 1];
+            float rpcol[SEM ? NCT : 1];
+            if constexpr (SEM) {
+                const int wn = p.w - 2, hn = p.h - 2;
+                const int py = y0 + (r >> 3) < hn ? y0 + (r >> 3) : hn - 1;
+#pragma unroll
+                for (int ct = 0; ct < NCT; ++ct) {
+                    const int px = x0 + ct * 8 + (r & 7) < wn ? x0 + ct * 8 + (r & 7) : wn - 1;
+                    const size_t i = (size_t)py * wn + px;
+                    dcol[ct] = *reinterpret_cast<const f32x4*>(p.gd + i * 4);
+                    rpcol[ct] = p.rp[i];
+                }
+            }
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const f32x4 rq = *reinterpret_cast<const f32x4*>(p.d.rq + j0 + 8 * q + 4 * hh);
+                f32x4 erow[SEM ? 4 : 1];
+                if constexpr (SEM) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) erow[e] = *reinterpret_cast<const f32x4*>(p.ge + (size_t)(j0 + 8 * q + 4 * hh + e) * 4);
+                }
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int j = j0 + 8 * q + 4 * hh + e;
                     const unsigned low = ~(unsigned)j;
 #pragma unroll
                     for (int ct = 0; ct < NCT; ++ct) {
-                        const float sc = ((accm[ct][4 * q + e] + accx[ct][4 * q + e] * LO_DOWN) * inv) * rq[e] + 0.f;      // (+ 0: -0 -> +0)
+                        float sc;
+                        if constexpr (SEM) {
+                            const float feat = (((accm[ct][4 * q + e] + accx[ct][4 * q + e] * LO_DOWN) * inv) * rq[e]) * rpcol[ct];
+                            const float sem = ((dcol[ct][0] * erow[e][0] + dcol[ct][1] * erow[e][1]) + dcol[ct][2] * erow[e][2]) +
+                                              dcol[ct][3] * erow[e][3];
+                            sc = feat + p.gamma * sem + 0.f;
+                        } else {
+                            sc = ((accm[ct][4 * q + e] + accx[ct][4 * q + e] * LO_DOWN) * inv) * rq[e] + 0.f;      // (+ 0: -0 -> +0)
+                        }
                         const unsigned long long key = ((unsigned long long)score_order(sc) << 32) | low;
                         if (j < p.d.m && key > best[ct]) best[ct] = key;
                     }
@@ -382,13 +453,13 @@ __global__ __launch_bounds__(256) void pm_grad_kernel(PatchTerm t, float coef, f
 bool pm_channels_ok(int C) { return C == 64 || C == 128 || C == 256 || C == 512; }
 
 // the dynamic-LDS limit of one shape, for its widest map (C = 512 / NCT)
-template <int NCT>
+template <int NCT, bool SEM>
 hipError_t pm_search_attr() {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_search_kernel<NCT>), hipFuncAttributeMaxDynamicSharedMemorySize,
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_search_kernel<NCT, SEM>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                PmCfg<NCT>::lds_bytes(512 / NCT));
 }
 
-template <int NCT>
+template <int NCT, bool SEM>
 hipError_t pm_search_launch(PatchSearch p, hipStream_t stream) {
     using Cf = PmCfg<NCT>;
     p.tiles_y = (p.h - 2 + Cf::TY - 1) / Cf::TY;
@@ -401,17 +472,25 @@ hipError_t pm_search_launch(PatchSearch p, hipStream_t stream) {
     if (nsplit > cap) nsplit = cap;
     if (nsplit < 1) nsplit = 1;
     if (nsplit > 65535) nsplit = 65535;
-    hipLaunchKernelGGL(pm_search_kernel<NCT>, dim3((unsigned)tiles, (unsigned)nsplit), dim3(512), (size_t)Cf::lds_bytes(p.C), stream, p);
+    hipLaunchKernelGGL((pm_search_kernel<NCT, SEM>), dim3((unsigned)tiles, (unsigned)nsplit), dim3(512), (size_t)Cf::lds_bytes(p.C), stream, p);
     return hipGetLastError();
+}
+
+template <bool SEM>
+hipError_t pm_search_by_channels(const PatchSearch& p, hipStream_t stream) {
+    return p.C == 512 ? pm_search_launch<1, SEM>(p, stream) : (p.C == 256 ? pm_search_launch<2, SEM>(p, stream) : pm_search_launch<4, SEM>(p, stream));
 }
 
 }  // namespace
 
 // once per device, before the first launch there (the search kernels take more than 64 KB of dynamic LDS)
 hipError_t pm_init_device() {
-    hipError_t e = pm_search_attr<1>();
-    if (e == hipSuccess) e = pm_search_attr<2>();
-    if (e == hipSuccess) e = pm_search_attr<4>();
+    hipError_t e = pm_search_attr<1, false>();
+    if (e == hipSuccess) e = pm_search_attr<2, false>();
+    if (e == hipSuccess) e = pm_search_attr<4, false>();
+    if (e == hipSuccess) e = pm_search_attr<1, true>();
+    if (e == hipSuccess) e = pm_search_attr<2, true>();
+    if (e == hipSuccess) e = pm_search_attr<4, true>();
     return e;
 }
 
@@ -428,6 +507,23 @@ bool pm_dict_geometry(int hs, int ws, int C, int stride, PatchDict* d) {
     return true;
 }
 
+hipError_t launch_pm_norms(const PatchDict& d, double epsilon, float* out, hipStream_t stream) {
+    if (!d.fs || !out || d.m < 1 || !pm_channels_ok(d.C) || !(epsilon > 0.0)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pm_rq_kernel, dim3((unsigned)(pm_dict_tiles(d.m) * 8)), dim3(256), 0, stream, d, epsilon, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_pm_descriptors(const float* planes, int R, int hm, int wm, int stride, double epsilon, int padded, float* out,
+                                 hipStream_t stream) {
+    if (!planes || !out || R < 1 || R > 4 || hm < 3 || wm < 3 || stride < 1 || stride > 8 || !(epsilon > 0.0)) return hipErrorInvalidValue;
+    const int na = (hm - 3) / stride + 1, nb = (wm - 3) / stride + 1;
+    const long long count = (long long)na * nb;
+    if (count > (1ll << 30) || padded < count) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pm_desc_kernel, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, stream, planes, R, hm, wm, stride, nb, (int)count,
+                       padded, epsilon, out);
+    return hipGetLastError();
+}
+
 hipError_t launch_pm_prepare(const PatchDict& d, double epsilon, unsigned* amax, float* rq, void* packed, hipStream_t stream) {
     if (!d.fs || !amax || !rq || !packed || d.m < 1 || !pm_channels_ok(d.C) || !(epsilon > 0.0)) return hipErrorInvalidValue;
     hipError_t e = launch_zero(amax, NST_AMAX_SLOTS, stream);
@@ -437,8 +533,7 @@ hipError_t launch_pm_prepare(const PatchDict& d, double epsilon, unsigned* amax,
     PatchDict dd = d;
     dd.amax = amax; dd.rq = rq; dd.packed = packed;
     const int padded = pm_dict_tiles(d.m) * 32;
-    hipLaunchKernelGGL(pm_rq_kernel, dim3((unsigned)(padded / 4)), dim3(256), 0, stream, dd, epsilon, rq);
-    e = hipGetLastError();
+    e = launch_pm_norms(dd, epsilon, rq, stream);
     if (e != hipSuccess) return e;
     const size_t total = (size_t)padded * (9 * d.C / 8);
     const size_t want = (total + 255) / 256;
@@ -451,11 +546,14 @@ hipError_t launch_pm_search(const PatchSearch& p0, int* idx, float* score, hipSt
     if (!p.f || !p.amax_f || !p.keys || !p.d.fs || !p.d.amax || !p.d.rq || !p.d.packed || p.h < 3 || p.w < 3 || p.d.m < 1 ||
         p.C != p.d.C || !pm_channels_ok(p.C))
         return hipErrorInvalidValue;
+    // the guidance: all of gd, ge, rp (and a finite gamma >= 0), or none of them
+    const bool guided = p.gd || p.ge || p.rp;
+    if (guided && (!p.gd || !p.ge || !p.rp || !(p.gamma >= 0.f) || p.gamma > 3.0e38f)) return hipErrorInvalidValue;
     const size_t n = (size_t)(p.h - 2) * (p.w - 2);
     p.cshift = p.C == 64 ? 2 : (p.C == 128 ? 3 : (p.C == 256 ? 4 : 5));
     hipError_t e = launch_zero(p.keys, 2 * n, stream);
     if (e != hipSuccess) return e;
-    e = p.C == 512 ? pm_search_launch<1>(p, stream) : (p.C == 256 ? pm_search_launch<2>(p, stream) : pm_search_launch<4>(p, stream));
+    e = guided ? pm_search_by_channels<true>(p, stream) : pm_search_by_channels<false>(p, stream);
     if (e != hipSuccess) return e;
     if (!idx && !score) return hipSuccess;
     hipLaunchKernelGGL(pm_decode_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, p.keys, n, p.d.m, idx, score);

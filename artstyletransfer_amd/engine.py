@@ -661,6 +661,98 @@ class StyleEngine:
                                                      float(coef), _ptr(val), _ptr(grad), _stream(self.device)), "nst_patch_term")
         return (val, grad) if want_grad else val
 
+    # ---- the MRF term under semantic maps (nst_level_set_patch_guidance; neural-doodle) ----------------------
+    def _semantic_planes(self, planes: torch.Tensor, shape, what: str) -> torch.Tensor:
+        if not (isinstance(planes, torch.Tensor) and planes.dtype == torch.float32 and planes.dim() == 3):
+            raise ValueError(f"{what}: expected a float32 (R,h,w) device tensor")
+        if not 1 <= planes.shape[0] <= _regions.MAX_REGIONS:
+            raise ValueError(f"{what}: {planes.shape[0]} regions, 1 .. {_regions.MAX_REGIONS} allowed")
+        if shape is not None and tuple(planes.shape[1:]) != tuple(shape):
+            raise ValueError(f"{what}: planes of {tuple(planes.shape[1:])}, expected {tuple(shape)}")
+        planes = planes.contiguous()
+        _chk_dev(planes, self.device)
+        return planes
+
+    def set_patch_guidance(self, level: int, content_planes: Optional[torch.Tensor], style_planes: Optional[torch.Tensor],
+                           gamma: float = 1.0) -> None:
+        """Semantic maps steer the patch search of a level that carries the MRF term (nst_level_set_patch_guidance;
+        Champandard 2016): the score of a candidate becomes cos(i,j) + gamma <d_i, e_j>, d and e the normalised nine-tap sums
+        of the pooled planes.  content_planes: device float32 (R,h,w) at the level image's size; style_planes: (R,hs,ws) at the
+        size of the style image given to set_patches; values in [0,1]; R <= 4.  Call it after set_patches: whatever drops the
+        level's term drops its guidance.  None planes or gamma 0 clear the guidance.  ValueError, before the call, for planes
+        of another shape or dtype, mismatched R, or a negative or non-finite gamma."""
+        g = float(gamma)
+        if not np.isfinite(g) or g < 0.0:
+            raise ValueError(f"the semantic weight must be finite and >= 0, got {gamma!r}")
+        if content_planes is None or style_planes is None or g == 0.0:
+            _lib.check(self.ctx, self.lib.nst_level_set_patch_guidance(self.ctx, int(level), 0, None, None, 0.0, _stream(self.device)),
+                       "nst_level_set_patch_guidance")
+            return
+        hs, ws = C.c_int(), C.c_int()
+        _lib.check(self.ctx, self.lib.nst_level_patch_guidance(self.ctx, int(level), None, None, C.byref(hs), C.byref(ws)),
+                   "nst_level_patch_guidance")
+        c = self._semantic_planes(content_planes, self.level_shape(level), "content_planes")
+        # (a level without the term has no style size: the call itself refuses it, NST_E_STATE)
+        s = self._semantic_planes(style_planes, (hs.value, ws.value) if hs.value > 0 else None, "style_planes")
+        if c.shape[0] != s.shape[0]:
+            raise ValueError(f"content_planes has {c.shape[0]} regions, style_planes {s.shape[0]}")
+        _lib.check(self.ctx, self.lib.nst_level_set_patch_guidance(self.ctx, int(level), int(c.shape[0]), _ptr(c), _ptr(s), g,
+                                                                   _stream(self.device)), "nst_level_set_patch_guidance")
+
+    def clear_patch_guidance(self, level: Optional[int] = None) -> None:
+        """An unguided search on one level, or (None) on every configured level."""
+        for l in (range(self.levels) if level is None else (level,)):
+            self.set_patch_guidance(l, None, None)
+
+    def patch_guidance(self, level: int):
+        """(R, gamma) of a level (nst_level_patch_guidance), or None when its search is unguided."""
+        r, g = C.c_int(), C.c_float()
+        _lib.check(self.ctx, self.lib.nst_level_patch_guidance(self.ctx, int(level), C.byref(r), C.byref(g), None, None),
+                   "nst_level_patch_guidance")
+        return None if r.value == 0 else (r.value, float(g.value))
+
+    def patch_descriptors(self, planes: torch.Tensor, stride: int = 1, epsilon: float = _mrf.DEFAULT_EPSILON) -> torch.Tensor:
+        """The semantic descriptors alone (nst_patch_descriptors): planes (R,hm,wm), device float32 at the MAP's resolution
+        (regions.pool_chain restates the pooling) -> (count, 4) float32, count the entries of the stride-`stride` geometry:
+        stride 1 for the image patches, the style stride for a dictionary."""
+        stride, eps = _mrf.check_stride(stride), _mrf.check_epsilon(epsilon)
+        planes = self._semantic_planes(planes, None, "planes")
+        r, hm, wm = planes.shape
+        if hm < 3 or wm < 3:
+            raise ValueError(f"planes: a map of {hm}x{wm} has no 3x3 patch")
+        count = ((hm - 3) // stride + 1) * ((wm - 3) // stride + 1)
+        out = torch.empty((count, 4), dtype=torch.float32, device=self.device)
+        _lib.check(self.ctx, self.lib.nst_patch_descriptors(self.ctx, _ptr(planes), r, hm, wm, stride, eps, _ptr(out),
+                                                            _stream(self.device)), "nst_patch_descriptors")
+        return out
+
+    def patch_match_guided(self, f: torch.Tensor, fs: torch.Tensor, d: torch.Tensor, e: torch.Tensor, gamma: float, stride: int = 1,
+                           epsilon: float = _mrf.DEFAULT_EPSILON):
+        """The guided match alone (nst_patch_match_guided): patch_match's f and fs, the descriptors d (n,4) of the image
+        patches and e (m,4) of the dictionary entries (patch_descriptors) and gamma >= 0 -> (nn (h-2,w-2) int32, T (h-2,w-2)
+        float32), T(i,j) = cos(i,j) + gamma <d_i, e_j>."""
+        stride, eps = _mrf.check_stride(stride), _mrf.check_epsilon(epsilon)
+        g = float(gamma)
+        if not np.isfinite(g) or g < 0.0:
+            raise ValueError(f"the semantic weight must be finite and >= 0, got {gamma!r}")
+        _chk_dev(f, self.device)
+        _chk_dev(fs, self.device)
+        if f.dim() != 3 or fs.dim() != 3 or f.shape[2] != fs.shape[2]:
+            raise NstError("f and fs must be (h,w,C) and (hs,ws,C) with the same C")
+        h, w, c = f.shape
+        n = (h - 2) * (w - 2)
+        m = ((fs.shape[0] - 3) // stride + 1) * ((fs.shape[1] - 3) // stride + 1)
+        for t, rows, what in ((d, n, "d"), (e, m, "e")):
+            _chk_dev(t, self.device)
+            if tuple(t.shape) != (rows, 4):
+                raise NstError(f"{what} must be ({rows},4), got {tuple(t.shape)}")
+        idx = torch.empty((h - 2, w - 2), dtype=torch.int32, device=self.device)
+        score = torch.empty((h - 2, w - 2), dtype=torch.float32, device=self.device)
+        _lib.check(self.ctx, self.lib.nst_patch_match_guided(self.ctx, _ptr(f), h, w, c, _ptr(fs), fs.shape[0], fs.shape[1], stride, eps,
+                                                             _regions.MAX_REGIONS, _ptr(d), _ptr(e), g, _ptr(idx), _ptr(score),
+                                                             _stream(self.device)), "nst_patch_match_guided")
+        return idx, score
+
     def closure(self, x: torch.Tensor, cw: float, sw: float, tvw: float,
                 grad: Optional[torch.Tensor] = None, losses: Optional[torch.Tensor] = None):
         """Asynchronous on the current stream. Returns (grad (C,H,W), losses (4*levels+1,)) device tensors (C = 3, or 1

@@ -146,3 +146,41 @@ def check_sizes(setting, level_shapes, style_shapes) -> None:
             for what, (h, ww) in (("image", level_shapes[lv]), ("style image", style_shapes[lv])):
                 if (int(h) >> MAP_SCALE[i]) < MIN_MAP or (int(ww) >> MAP_SCALE[i]) < MIN_MAP:
                     raise ValueError(f"mrf_weight: map {i} of the {what} of level {lv} ({h}x{ww}) pools below {MIN_MAP}x{MIN_MAP}")
+
+
+DEFAULT_SEMANTIC_WEIGHT = 1.0
+
+
+def normalize_semantic(content=None, style=None, weight=DEFAULT_SEMANTIC_WEIGHT):
+    """The semantic maps that steer the patch search (neural-doodle; nst_level_set_patch_guidance in include/nst_hip.h) ->
+    (content stack (R,H,W), style stack (R,Hs,Ws), weight), float32 stacks as regions.normalize_regions makes them, or None
+    when off: both maps None, or a weight of 0.  Each map is an integer label map (H,W) with labels 0..R-1 or a float stack
+    (R,H,W) in [0,1], at any resolution.  Everything is validated, the off setting included.
+    ValueError for a malformed map, one map without the other, mismatched R, or a weight that is not a finite number >= 0."""
+    from . import regions as _regions
+    w = _weight(weight, "semantic_weight")
+    if content is None and style is None:
+        return None
+    if content is None or style is None:
+        raise ValueError("semantic_content and semantic_style go together: one was given without the other")
+    c = _regions.normalize_regions(content, "semantic_content")
+    s = _regions.normalize_regions(style, "semantic_style")
+    if c.shape[0] != s.shape[0]:
+        raise ValueError(f"semantic_content has {c.shape[0]} regions, semantic_style {s.shape[0]}")
+    if w == 0.0:
+        return None
+    return c, s, w
+
+
+def semantic_level_planes(setting, level_shapes, style_shapes, levels=None):
+    """The stacks of normalize_semantic resized (regions.resize_nearest) to every chosen level of each pyramid: a list, by
+    level, of (content planes (R,h,w), style planes (R,hs,ws)) or None for a level that does not carry the term."""
+    from . import regions as _regions
+    c, s, _ = setting
+    out = []
+    for lv, ((h, w), (hs, ws)) in enumerate(zip(level_shapes, style_shapes)):
+        if levels is not None and lv not in levels:
+            out.append(None)
+        else:
+            out.append((_regions.resize_nearest(c, int(h), int(w)), _regions.resize_nearest(s, int(hs), int(ws))))
+    return out

@@ -256,6 +256,15 @@ class _DeviceJob:
                 if levels is None or lvl in levels:
                     self.engine.set_patches(lvl, style_of(), weights, stride, epsilon)
 
+    def set_patch_semantics(self, level_planes, weight):
+        """The semantic maps of the MRF term's levels (StyleEngine.set_patch_guidance), after set_patch_match: `level_planes`
+        per level (content planes (R,h,w), style planes (R,hs,ws)) as host float32 stacks, or None for a level without."""
+        with torch.cuda.device(self.dev), torch.cuda.stream(self.job_stream):
+            for lvl, planes in enumerate(level_planes):
+                if planes is not None:
+                    self.engine.set_patch_guidance(lvl, torch.from_numpy(planes[0]).to(self.dev), torch.from_numpy(planes[1]).to(self.dev),
+                                                   weight)
+
     def step(self, cw, sw, tvw):
         """One optimizer.step(closure) (nst_opt_step).  Runs on a pool thread, whose current stream is its own."""
         with torch.cuda.stream(self.job_stream):
@@ -332,6 +341,7 @@ class NeuralStyleTransfer:
         self.settings = _job.JobSettings()       # the optional settings of the next `process`: the set_* below update it
         self.__anchor = None                     # set_anchor: data of the next `process`, not a setting
         self.__patches = None                    # set_patch_match: likewise
+        self.__semantics = None                  # set_patch_semantics: likewise
 
     def set_feature_maps(self, content_layer=None, style_layers=None, use_relu=True):
         """Extension: the feature maps the losses of the next `process` read - a content map and a set of style maps of
@@ -457,6 +467,19 @@ class NeuralStyleTransfer:
         off = weights is None or (isinstance(weights, (int, float)) and not isinstance(weights, bool) and weights == 0)
         self.__patches = None if off else (weights, stride, epsilon, levels)
 
+    def set_patch_semantics(self, content_regions=None, style_regions=None, weight=_mrf.DEFAULT_SEMANTIC_WEIGHT):
+        """Extension: semantic maps that steer the patch search of the MRF term (Champandard 2016, neural-doodle) in the next
+        `process`: a patch of region r of the content prefers style patches of region r of the style - the score of a
+        candidate is cos + weight <d, e>, d and e the normalised region descriptors of the two patches
+        (nst_level_set_patch_guidance in include/nst_hip.h has the definition).  Each map is an integer label map (H,W) with
+        labels 0..R-1 or a float stack (R,H,W) in [0,1], at any resolution (it is resized to every level of its pyramid that
+        carries the term, nearest neighbour); R <= 4, equal on the two sides.  `weight`: a finite number >= 0; the cosines
+        of post-ReLU maps lie in [0,1], so from 1 on a candidate of the same region always beats one of another region for
+        one-hot descriptors, and smaller values trade region for feature similarity.  Data of one job, like set_patch_match
+        (which names the maps, the stride and the levels).  None, None or weight 0: off.  ValueError for a malformed
+        argument, one map without the other, mismatched R and - in `process` - semantic maps without the MRF term."""
+        self.__semantics = _mrf.normalize_semantic(content_regions, style_regions, weight)
+
     async def process(self, content_imgs, init_img, lr_start, iters_num, content_weight, style_weight, tv_weight,
                       init_img_name):
         # validates the model name exactly as the reference does (ValueError for anything but vgg19)
@@ -488,6 +511,12 @@ class NeuralStyleTransfer:
             patches = _mrf.normalize_mrf(*self.__patches, style_indices=style_set, use_relu=use_relu, levels_num=len(content_imgs))
             _mrf.check_exclusive(patches, regions=resolved.get("regions"), extra_styles=resolved.get("blend"))
             _mrf.check_sizes(patches, [tuple(c.shape[:2]) for c in content_imgs], [tuple(s.shape[:2]) for s in style_imgs])
+        semantics = None
+        if self.__semantics is not None:
+            if patches is None:
+                raise ValueError("semantic maps steer the MRF term: set_patch_semantics needs set_patch_match (mrf_weight is off)")
+            semantics = _mrf.semantic_level_planes(self.__semantics, [tuple(c.shape[:2]) for c in content_imgs],
+                                                   [tuple(s.shape[:2]) for s in style_imgs], patches[3])
         if self.__anchor is not None and len(self.__anchor[0]) != len(content_imgs):
             raise ValueError(f"{len(self.__anchor[0])} anchor levels for a job of {len(content_imgs)} levels")
         job = _make_job(self.__device, self.__optimizer_name, style_imgs, content_imgs, init_img, lr_start, **resolved)
@@ -500,6 +529,8 @@ class NeuralStyleTransfer:
         if patches is not None:              # (likewise)
             try:
                 job.set_patch_match(*patches)
+                if semantics is not None:
+                    job.set_patch_semantics(semantics, self.__semantics[2])
             except BaseException:
                 job.close()
                 raise
@@ -603,10 +634,11 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
 
 def _transfer_from(content_n_style, content_weight, style_weight, tv_weight, optimizer, model, init_method, iters_num, levels_num,
                    noise_factor, noise_levels, noise_levels_central_amplitude, noise_levels_peripheral_amplitude,
-                   noise_levels_dispersion, *, device=None, start=None, patches=None, **keywords):
+                   noise_levels_dispersion, *, device=None, start=None, patches=None, semantics=None, **keywords):
     """The settings validation of neural_style_transfer() (`keywords`: its keyword-only parameters), here and now - before any
     GPU work, ValueError - and then the job as an async generator, from the `init_method` image or from `start` (_transfer).
-    `patches` (patch_match.py): None, or the arguments of NeuralStyleTransfer.set_patch_match, validated here too."""
+    `patches` (patch_match.py): None, or the arguments of NeuralStyleTransfer.set_patch_match, validated here too;
+    `semantics`: None, or the arguments of NeuralStyleTransfer.set_patch_semantics, likewise (they need `patches`)."""
     settings = _job.JobSettings(for_job=True, **keywords)
 
     def level_shapes(img):      # (the level sizes follow from the image size: top level first)
@@ -620,6 +652,11 @@ def _transfer_from(content_n_style, content_weight, style_weight, tv_weight, opt
         _mrf.check_exclusive(checked, regions=resolved.get("regions"), extra_styles=keywords.get("extra_styles"))
         _mrf.check_sizes(checked, level_shapes(content_n_style.content[1]), level_shapes(content_n_style.style[1]))
         patches = patches if checked is not None else None
+    if semantics is not None:
+        if _mrf.normalize_semantic(*semantics) is None:
+            semantics = None
+        elif patches is None:
+            raise ValueError("semantic_content / semantic_style steer the MRF term: mrf_weight is off")
     extra_styles = keywords.get("extra_styles")
     extra_styles = list(extra_styles) if extra_styles is not None else []
     for img in extra_styles:
@@ -628,17 +665,18 @@ def _transfer_from(content_n_style, content_weight, style_weight, tv_weight, opt
     return _transfer(content_n_style, content_weight, style_weight, tv_weight, optimizer, model, init_method, iters_num, levels_num,
                      noise_factor, noise_levels, noise_levels_central_amplitude, noise_levels_peripheral_amplitude,
                      noise_levels_dispersion, device, settings, keywords.get("preserve_color"), extra_styles,
-                     keywords.get("style_blend"), start, patches)
+                     keywords.get("style_blend"), start, patches, semantics)
 
 
 async def _transfer(content_n_style, content_weight, style_weight, tv_weight, optimizer, model, init_method, iters_num, levels_num,
                     noise_factor, noise_levels, noise_levels_central_amplitude, noise_levels_peripheral_amplitude,
-                    noise_levels_dispersion, device, settings, preserve_color, extra_styles, style_blend, start=None, patches=None):
+                    noise_levels_dispersion, device, settings, preserve_color, extra_styles, style_blend, start=None, patches=None,
+                    semantics=None):
     """neural_style_transfer() below its settings validation: `settings` is its validated JobSettings, `extra_styles` its
     checked list.  `start` (video.py): None, or a callable (setup engine, level-0 (h, w)) -> (start image: a device HWC
     tensor the job starts from in place of the `init_method` image, anchor levels, weight levels, gamma) - the arguments of
     NeuralStyleTransfer.set_anchor - called once the level sizes are known.  `patches` (patch_match.py): None, or the checked
-    arguments of NeuralStyleTransfer.set_patch_match."""
+    arguments of NeuralStyleTransfer.set_patch_match; `semantics`: None, or those of NeuralStyleTransfer.set_patch_semantics."""
     if device is None:
         if not torch.cuda.is_available():
             raise RuntimeError("no GPU visible: the HIP style-transfer engine has no CPU path")
@@ -675,6 +713,8 @@ async def _transfer(content_n_style, content_weight, style_weight, tv_weight, op
         nst.set_anchor(*anchor)
     if patches is not None:
         nst.set_patch_match(*patches)
+    if semantics is not None:
+        nst.set_patch_semantics(*semantics)
     # (the extra styles as their pyramids; "histogram" has recoloured the style levels above)
     settings.update(extra_styles=extra_levels, style_blend=style_blend if extra_levels else None)
     if preserve_color == "histogram":

@@ -891,6 +891,57 @@ int nst_patch_match(nst_ctx* ctx, const float* f, int h, int w, int C, const flo
                     int* idx_out /* nullable */, float* score_out /* nullable */, void* stream);
 int nst_patch_term(nst_ctx* ctx, const float* f, int h, int w, int C, const float* fs, int hs, int ws, int stride, const int* idx,
                    float coef, float* value_out /* nullable */, float* grad_out /* nullable */, void* stream);
+/* ---- The MRF term under semantic maps (Champandard 2016, "Semantic Style Transfer and Turning Two-Bit Doodles into Fine
+ * Artworks": neural-doodle) ---------------------------------------------------------------------------------------------
+ * A pair of semantic maps steers the patch search of a level that carries the MRF term: a patch prefers style patches of
+ * its own region.  Only nn changes; value and gradient of the term are the ones above, at the new nn.
+ * Inputs of a level.  Content planes c: (R,h,w) at the level image's size; style planes s: (R,hs,ws) at the size of the style
+ *   image given to nst_level_set_patches; 1 <= R <= NST_MAX_REGIONS; all plane values in [0,1]; a weight gamma >= 0.
+ * Descriptors.  For a weighted map i both stacks are brought to the map's resolution by the map's network scale (0, 1, 2, 3, 3,
+ *   4 by map index) steps of the 2x2 mean pool of nst_level_set_guidance (floor sizes, ((e00 + e01) + e10) + e11 times 1/4,
+ *   fp32).  The descriptor of a patch centred at (y,x): a[r] = the sum of the nine taps of pooled plane r, in double, taps in
+ *   row-major order; d = (float)(a / sqrt(sum_r a[r]^2 + epsilon)), in double, with the term's own epsilon; stored as four
+ *   floats, entries r >= R zero.  Image patches get d_i, i over all n patches; dictionary entries get e_j at the dictionary's
+ *   centres (1 + a s, 1 + b s); the padding entries of the last dictionary tile are zero.  (An R-vector, not Champandard's
+ *   9R-channel concatenation: 4 multiply-adds per score in the epilogue instead of 36, and for piecewise-constant labels the
+ *   two agree wherever a patch lies inside one region.)
+ * Score.  T(i,j) = cos(i,j) + gamma <d_i, e_j>, cos(i,j) = <P_i,Q_j> rq_j rp_i, rp_i = (float)(1 / sqrt(|P_i|^2 + epsilon)),
+ *   summed in double over the image map and recomputed in every closure (the map changes).  rp_i is new: the unguided score
+ *   omits it because it does not change an arg-max over j; next to an additive term it does.  On the device, without
+ *   contraction:
+ *     feat = (((main + cross * 2^-11) * inv) * rq_j) * rp_i
+ *     sem  = ((d0*e0 + d1*e1) + d2*e2) + d3*e3
+ *     sc   = feat + gamma * sem + 0.f
+ *   The key, the atomicMax, the lowest-j tie rule and bitwise reproducibility are those of the unguided search; nn(i) is the
+ *   arg-max of T.
+ * Value and gradient do not change: mrf_i = sum |P - Q_nn|^2 / (9 C n) and its gather-form gradient at fixed nn - the
+ *   semantic planes are constants, and the matches are held fixed.
+ * Off.  gamma = 0, R = 0 and null planes all clear the guidance; a level without guidance launches the kernels of the
+ *   unguided term and computes the same bits.
+ *
+ * nst_level_set_patch_guidance: the guidance of one level's term.  Both plane stacks are checked and pooled on scratch; the
+ *   descriptors of every weighted map and the buffer of rp stay with the level (counted by nst_ctx_bytes, credited back when
+ *   cleared): a closure allocates nothing.  Life cycle of nst_level_set_patches: waits for the context's work; ends a captured
+ *   graph, an L-BFGS memo and a pending backward half; a refusal changes nothing.  Whatever drops the level's term drops its
+ *   guidance: nst_level_set_patches (again or cleared), nst_job_configure, nst_job_set_taps, nst_job_set_pooling,
+ *   nst_job_set_color.  So the order is patches first.
+ *   NST_E_ARG: level or R out of range; a negative or non-finite gamma; a plane value outside [0,1] or not finite (a region
+ *   may be empty on either side: the mass rule of the guided Gram does not apply).
+ *   NST_E_STATE: no configured job; guidance for a level that carries no MRF term.
+ * nst_level_patch_guidance: R and gamma of the level (zeros: unguided), and the size (hs, ws) the style planes of the level
+ *   must have: that of the style image of nst_level_set_patches (zeros: the level carries no term).  All outputs nullable.
+ * nst_patch_descriptors: the descriptors alone.  planes = device (R,hm,wm) at the MAP's resolution, hm, wm >= 3; out = device
+ *   (count,4), count = ((hm-3)/stride + 1)((wm-3)/stride + 1): stride 1 for image patches, the style stride for a dictionary.
+ * nst_patch_match_guided: nst_patch_match plus R, d (n,4), e (m,4) and gamma (the descriptors are used as given: entries
+ *   r >= R are the caller's zeros); score_out is T.  Both read no job state and are synchronous. */
+int nst_level_set_patch_guidance(nst_ctx* ctx, int level, int R, const float* content_planes /* device (R,h,w) */,
+                                 const float* style_planes /* device (R,hs,ws) */, float gamma, void* stream);
+int nst_level_patch_guidance(const nst_ctx* ctx, int level, int* R, float* gamma, int* hs, int* ws);
+int nst_patch_descriptors(nst_ctx* ctx, const float* planes /* device (R,hm,wm) */, int R, int hm, int wm, int stride, double epsilon,
+                          float* out /* device (count,4) */, void* stream);
+int nst_patch_match_guided(nst_ctx* ctx, const float* f, int h, int w, int C, const float* fs, int hs, int ws, int stride,
+                           double epsilon, int R, const float* d /* device (n,4) */, const float* e /* device (m,4) */, float gamma,
+                           int* idx_out /* nullable */, float* score_out /* nullable */, void* stream);
 int nst_warp_bilinear(nst_ctx* ctx, const float* src, const float* flow, int C, int h, int w, float* out,
                       float* valid /* nullable */, void* stream);
 int nst_flow_weights(nst_ctx* ctx, const float* fwd, const float* bwd, int h, int w, float* out, void* stream);
