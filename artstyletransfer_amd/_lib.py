@@ -100,6 +100,14 @@ SYMBOLS = {
     "nst_patch_descriptors": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, c_void, c_void]),
     "nst_patch_match_guided": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, C.c_int, C.c_int, C.c_int, C.c_double,
                                          C.c_int, c_void, c_void, C.c_float, c_void, c_void, c_void]),
+    "nst_level_set_histograms": (C.c_int, [c_void, C.c_int, c_void, C.c_int, C.c_int, c_float_p, C.c_int, c_void]),
+    "nst_level_histograms": (C.c_int, [c_void, C.c_int, c_float_p, C.POINTER(C.c_int)]),
+    "nst_job_histogram_losses": (C.c_int, [c_void, c_void, c_void]),
+    "nst_level_histogram_tables": (C.c_int, [c_void, C.c_int, C.c_int, c_void, c_void, c_void, c_void]),
+    "nst_level_histogram_style": (C.c_int, [c_void, C.c_int, C.c_int, c_void, c_void, c_void]),
+    "nst_histogram_counts": (C.c_int, [c_void, c_void, C.c_longlong, C.c_int, C.c_int, c_void, c_void, c_void]),
+    "nst_histogram_tables": (C.c_int, [c_void, c_void, c_void, C.c_longlong, c_void, c_void, C.c_longlong, C.c_int, C.c_int, c_void, c_void]),
+    "nst_histogram_term": (C.c_int, [c_void, c_void, C.c_longlong, C.c_int, C.c_int, c_void, c_void, C.c_float, c_void, c_void, c_void]),
     "nst_warp_bilinear": (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, c_void, c_void]),
     "nst_flow_weights": (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, c_void, c_void]),
     "nst_anchor_fold": (C.c_int, [c_void, C.c_int, C.POINTER(c_void), C.POINTER(c_void), C.c_int, C.c_int, C.c_int, c_void, c_void,

@@ -395,6 +395,55 @@ int nst_patch_term(nst_ctx* ctx, const float* f, int h, int w, int C, const floa
     return sc.finish();
 }
 
+// The histogram loss's pieces on their own (include/nst_hip.h has the definition): the kernels of histogram.hip.  Synchronous.
+static int hist_args(nst_ctx* ctx, long long N, int C, int bins) {
+    if (!hist_channels_ok(C)) return fail(ctx, NST_E_ARG, "the histogram loss takes maps of 64, 128, 256 or 512 channels");
+    if (bins < 2 || bins > 1024) return fail(ctx, NST_E_ARG, "the number of bins must be 2..1024");
+    if (N < 1 || (double)N * C >= 2147483648.0) return fail(ctx, NST_E_ARG, "the map must have 1 <= N and N C < 2^31");
+    return NST_OK;
+}
+
+int nst_histogram_counts(nst_ctx* ctx, const float* f, long long N, int C, int bins, float* lo_hi_out, unsigned* counts_out, void* stream) {
+    NSTCHK(bind(ctx));
+    if (!f || !lo_hi_out || !counts_out) return fail(ctx, NST_E_ARG, "null argument");
+    NSTCHK(hist_args(ctx, N, C, bins));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIPCHK(ctx, launch_hist_counts(f, (size_t)N, C, bins, lo_hi_out, counts_out, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return NST_OK;
+}
+
+int nst_histogram_tables(nst_ctx* ctx, const float* lo_hi, const unsigned* counts, long long N, const float* s_lo_hi, const unsigned* s_counts,
+                         long long Ns, int C, int bins, float* ends_out, void* stream) {
+    NSTCHK(bind(ctx));
+    if (!lo_hi || !counts || !s_lo_hi || !s_counts || !ends_out) return fail(ctx, NST_E_ARG, "null argument");
+    NSTCHK(hist_args(ctx, N, C, bins));
+    NSTCHK(hist_args(ctx, Ns, C, bins));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIPCHK(ctx, launch_hist_tables(counts, (size_t)N, s_lo_hi, s_counts, (size_t)Ns, C, bins, ends_out, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return NST_OK;
+}
+
+int nst_histogram_term(nst_ctx* ctx, const float* f, long long N, int C, int bins, const float* lo_hi, const float* ends, float coef,
+                       float* value_out, float* grad_out, void* stream) {
+    NSTCHK(bind(ctx));
+    if (!f || !lo_hi || !ends || (!value_out && !grad_out)) return fail(ctx, NST_E_ARG, "null argument");
+    NSTCHK(hist_args(ctx, N, C, bins));
+    if (!std::isfinite(coef)) return fail(ctx, NST_E_ARG, "the coefficient must be finite");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const HistTerm t{f, (size_t)N, C, bins, lo_hi, ends};
+    Scratch sc(ctx, s);
+    if (value_out) {
+        double* partial = nullptr;
+        NSTCHK(sc.alloc(&partial, (size_t)HIST_VALUE_BLOCKS));
+        HIPCHK(ctx, launch_hist_value_partials(t, partial, s));
+        HIPCHK(ctx, launch_hist_value(partial, (double)C * (double)N, value_out, s));
+    }
+    if (grad_out) HIPCHK(ctx, launch_hist_grad(t, coef, grad_out, 0, s));
+    return sc.finish();
+}
+
 // The warp of a sequence (include/nst_hip.h): out = src sampled bilinearly at p + flow(p), valid (nullable) = the four taps
 // lie inside the image.  Synchronous.
 int nst_warp_bilinear(nst_ctx* ctx, const float* src, const float* flow, int C, int h, int w, float* out, float* valid, void* stream) {

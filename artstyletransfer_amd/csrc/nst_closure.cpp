@@ -306,6 +306,43 @@ bool patch_layer(const LevelWs& L, int m) {
     return i >= 0 && L.pm.w[i] > 0.f;
 }
 
+// ---- the histogram loss (include/nst_hip.h has the definition; kernels: histogram.hip) -----------------------------------
+// map index i of level L: the term's operands on the level's own map, C N, and coef = (float)(2 w / (C N)) formed in double
+HistTerm hist_term_of(const LevelWs& L, int i) {
+    const int l = kTapLayer[i];
+    return HistTerm{L.acts.act[l], (size_t)L.acts.h[l] * L.acts.w[l], kCout[l], L.hist.bins, L.hist.lo_hi[i], L.hist.ends[i]};
+}
+double hist_denom(const LevelWs& L, int i) {
+    const int l = kTapLayer[i];
+    return (double)kCout[l] * (double)L.acts.h[l] * (double)L.acts.w[l];
+}
+float hist_coef(float w, double denom) { return (float)(2.0 * (double)w / denom); }
+// forward part of level L, once its maps exist: per map with a weight the range, the counts, the tables, the value partials
+// and hist_i (a level without the term: no launch)
+int hist_forward(nst_ctx* ctx, LevelWs& L, hipStream_t s) {
+    for (int i = 0; i < 6 && L.hist.on(); ++i) {
+        if (!(L.hist.w[i] > 0.f)) continue;
+        const HistTerm t = hist_term_of(L, i);
+        Timer tm(ctx, s, K_OTHER, 0);
+        HIPCHK(ctx, launch_hist_counts(t.f, t.N, t.C, t.bins, L.hist.lo_hi[i], L.hist.counts[i], s));
+        HIPCHK(ctx, launch_hist_tables(L.hist.counts[i], t.N, L.hist.s_lo_hi[i], L.hist.s_counts[i], L.hist.Ns[i], t.C, t.bins, L.hist.ends[i], s));
+        HIPCHK(ctx, launch_hist_value_partials(t, L.hist.partial[i], s));
+        HIPCHK(ctx, launch_hist_value(L.hist.partial[i], hist_denom(L, i), L.hist.vals + i, s));
+    }
+    return NST_OK;
+}
+// gradient part of map index i: into dst (the map's shape), written or added to what is there
+int hist_backward(nst_ctx* ctx, LevelWs& L, int i, float* dst, int accumulate, hipStream_t s) {
+    Timer tm(ctx, s, K_OTHER, 0);
+    HIPCHK(ctx, launch_hist_grad(hist_term_of(L, i), hist_coef(L.hist.w[i], hist_denom(L, i)), dst, accumulate, s));
+    return NST_OK;
+}
+// conv layer m of level L carries the term
+bool hist_layer(const LevelWs& L, int m) {
+    const int i = tap_index_of(m);
+    return i >= 0 && L.hist.w[i] > 0.f;
+}
+
 // ---- the moment loss (include/nst_hip.h has the definition; kernels: moments.hip) ----------------------------------------
 // style slot q of level L on its map f (N pixels, C channels): the statistics item, and the fold item that follows the Gram
 // finish pass and the row bias of a shifted Gram (r0: that bias, or nullptr)
@@ -393,6 +430,12 @@ int backward(nst_ctx* ctx, ActSet& a, const Inject* inj, const ContentJob* cj, f
             Timer t(ctx, s, K_OTHER, 0);
             HIPCHK(ctx, launch_pm_grad(*inj[l].mrf, inj[l].mrf_coef, oth, content ? 1 : 0, s));
         }
+        // the histogram loss of the top map, after both
+        const bool hist = inj[l].hist && inj[l].S;
+        if (hist) {
+            Timer t(ctx, s, K_OTHER, 0);
+            HIPCHK(ctx, launch_hist_grad(*inj[l].hist, inj[l].hist_coef, oth, (content || mrf) ? 1 : 0, s));
+        }
         if (inj[l].guided) {
             GuidedBwd gb = *inj[l].guided;
             gb.addend = content ? oth : nullptr; gb.out = cur; gb.mask = top_mask ? a.act[l] : nullptr;
@@ -401,7 +444,7 @@ int backward(nst_ctx* ctx, ActSet& a, const Inject* inj, const ContentJob* cj, f
             // (the content gradient, if any, as the addend of the 1x1 Gram launch)
             ConvParams p{};
             p.in = a.act[l]; p.wt = inj[l].S; p.out = cur; p.mask = top_mask ? a.act[l] : nullptr;
-            p.addend = (content || mrf) ? oth : nullptr;
+            p.addend = (content || mrf || hist) ? oth : nullptr;
             p.bias = inj[l].bias;                  // (a shifted Gram: F S + r, then the addend and the mask)
             p.H = a.h[l]; p.W = a.w[l]; p.Cin = kCout[l]; p.Cout = kCout[l];
             Timer t(ctx, s, K_GRAM, conv_flops(p.H, p.W, p.Cin, p.Cout, 1));
@@ -461,6 +504,12 @@ int backward(nst_ctx* ctx, ActSet& a, const Inject* inj, const ContentJob* cj, f
                 // the MRF term of the map: written, or added to the content gradient
                 Timer t(ctx, s, K_OTHER, 0);
                 HIPCHK(ctx, launch_pm_grad(*in.mrf, in.mrf_coef, oth, p.addend == oth ? 1 : 0, s));
+                p.addend = oth;
+            }
+            if (in.hist) {
+                // the histogram loss of the map: written, or added to the content gradient and the MRF term's
+                Timer t(ctx, s, K_OTHER, 0);
+                HIPCHK(ctx, launch_hist_grad(*in.hist, in.hist_coef, oth, p.addend == oth ? 1 : 0, s));
                 p.addend = oth;
             }
             if (in.guided) {
@@ -827,6 +876,16 @@ int batched_backward(nst_ctx* ctx, const float* const* xi, float* const* gi, con
         top_mrf[k] = patch_layer(L, top);
         if (top_mrf[k]) NSTCHK(patch_backward(ctx, L, tap_index_of(top), oth[k], top_content ? 1 : 0, s));
     }
+    // the histogram loss of the top map (nst_level_set_histograms; a level's own), after both; top_add: the launch has an addend
+    bool top_add[NST_MAX_LEVELS] = {};
+    for (int k = 0; k < n; ++k) {
+        LevelWs& L = ctx->lv[lv[k]];
+        top_add[k] = top_content || top_mrf[k];
+        if (top_q >= 0 && hist_layer(L, top)) {
+            NSTCHK(hist_backward(ctx, L, tap_index_of(top), oth[k], top_add[k] ? 1 : 0, s));
+            top_add[k] = true;
+        }
+    }
     const bool guided = guided_levels(ctx, lv, n);
     if (guided && top_q >= 0) {
         // top of the chain of a guided job: the guided Gram backward of each level, which adds the content gradient (when
@@ -854,7 +913,7 @@ int batched_backward(nst_ctx* ctx, const float* const* xi, float* const* gi, con
             im.out = cur[k]; im.H = a.h[l]; im.W = a.w[l];
             im.in2 = a.act[l]; im.wt2_f32 = L.S[top_q]; im.amax_in2 = amax_act(a, l); im.amax_w2 = amax_S(a, top_q);
             im.bits_in = tp.top_mask() ? a.bits[l] : nullptr; im.amax_out = amax_grad(a, l);
-            im.addend = (top_content || top_mrf[k]) ? oth[k] : nullptr;
+            im.addend = top_add[k] ? oth[k] : nullptr;
             im.bias = ctx->row_bias_of(L, top_q);      // (a shifted Gram, the moment term: F S + r, then the addend and the mask)
             if (win) { im.in2_row0 = win_r0(*win, kScale[l]); im.in2_rows = win_nr(*win, kScale[l]); }
             flops += conv_flops(im.H, im.W, b.Cin2, b.Cout, 1);
@@ -870,7 +929,7 @@ int batched_backward(nst_ctx* ctx, const float* const* xi, float* const* gi, con
         if (top_q >= 0) {
             ConvParams p{};
             p.in = a.act[l]; p.wt = L.S[top_q]; p.out = cur[k]; p.mask = tp.top_mask() ? a.act[l] : nullptr;
-            p.addend = top_content ? oth[k] : nullptr;
+            p.addend = top_add[k] ? oth[k] : nullptr;
             p.H = a.h[l]; p.W = a.w[l]; p.Cin = kCout[l]; p.Cout = kCout[l];
             Timer t(ctx, s, K_GRAM, conv_flops(p.H, p.W, p.Cin, p.Cout, 1));
             HIPCHK(ctx, launch_conv_mfma(p, 1, s));
@@ -936,6 +995,11 @@ int batched_backward(nst_ctx* ctx, const float* const* xi, float* const* gi, con
             if (patch_layer(L, m)) {
                 // the MRF term of the map, after the content gradient when the map is the content map too
                 NSTCHK(patch_backward(ctx, L, tap_index_of(m), oth[k], m == tp.content ? 1 : 0, s));
+                im.addend = oth[k];
+            }
+            if (hist_layer(L, m)) {
+                // the histogram loss of the map, after the content gradient and the MRF term where the map has those
+                NSTCHK(hist_backward(ctx, L, tap_index_of(m), oth[k], im.addend == oth[k] ? 1 : 0, s));
                 im.addend = oth[k];
             }
             im.bits_in = a.bits[m];
@@ -1004,6 +1068,7 @@ int closure_batched_forward(nst_ctx* ctx, const float* const* xi, unsigned level
     NSTCHK(batched_gram(ctx, lv, n, sw, s, overlap ? 0x18u : (1u << ctx->taps.nstyle) - 1u));
     if (overlap) HIPCHK(ctx, hipStreamWaitEvent(s, ctx->side_join, 0));
     for (int k = 0; k < n; ++k) NSTCHK(patch_forward(ctx, ctx->lv[lv[k]], s));       // (nst_level_set_patches: the maps exist)
+    for (int k = 0; k < n; ++k) NSTCHK(hist_forward(ctx, ctx->lv[lv[k]], s));        // (nst_level_set_histograms likewise)
     if (loss_terms && ctx->forward_pack && ctx->conv_mode == 2 && !ctx->use_graph && n > 1) {
         // one launch each for all levels; every level keeps its partial buffers and block decomposition
         MseBatch mb{};
@@ -1117,6 +1182,15 @@ int closure_per_level(nst_ctx* ctx, const float* const* xi, float* const* gi, in
         inj[kTapLayer[i]].mrf = &pterm[i];
         inj[kTapLayer[i]].mrf_coef = patch_coef(L.pm.w[i], patch_denom(L, i));
     }
+    // the histogram loss (nst_level_set_histograms): tables and values now, the gradients as addends of the walk
+    NSTCHK(hist_forward(ctx, L, s));
+    HistTerm hterm[6];
+    for (int i = 0; i < 6 && L.hist.on(); ++i) {
+        if (!(L.hist.w[i] > 0.f)) continue;
+        hterm[i] = hist_term_of(L, i);
+        inj[kTapLayer[i]].hist = &hterm[i];
+        inj[kTapLayer[i]].hist_coef = hist_coef(L.hist.w[i], hist_denom(L, i));
+    }
     ContentJob cj{L.content_t, L.content_n, content_coef(cw, (double)L.content_n), L.content_partial};
     NSTCHK(backward(ctx, L.acts, inj, &cj, L.gbuf[0], L.gbuf[1], gi[level], L.h, L.w, s, tp.top, tp.top_mask(), ctx->channels));
     {
@@ -1163,6 +1237,12 @@ LossAssembly fill_loss_assembly(const nst_ctx* ctx, unsigned level_mask, float c
         if (!L.pm.on()) continue;
         la.lv[i].mrf_vals = L.pm.vals;
         for (int k = 0; k < 6; ++k) la.lv[i].mrf_w[k] = L.pm.w[k];
+    }
+    for (int i = 0; i < ctx->levels; ++i) {      // (the histogram loss, a level's own in the same way)
+        const LevelWs& L = ctx->lv[i];
+        if (!L.hist.on()) continue;
+        la.lv[i].hist_vals = L.hist.vals;
+        for (int k = 0; k < 6; ++k) la.lv[i].hist_w[k] = L.hist.w[k];
     }
     return la;
 }
@@ -1339,6 +1419,8 @@ int window_check(nst_ctx* ctx, const float* xs, int row0, int rows, int H0) {
         return fail(ctx, NST_E_STATE, "the stripe closure implements no temporal term (nst_level_set_anchor(ctx, 0, NULL, NULL, 0, stream) clears it)");
     if (L.pm.on())
         return fail(ctx, NST_E_STATE, "the stripe closure implements no MRF term (nst_level_set_patches(ctx, 0, NULL, ...) clears it)");
+    if (L.hist.on())
+        return fail(ctx, NST_E_STATE, "the stripe closure implements no histogram loss (nst_level_set_histograms(ctx, 0, NULL, ...) clears it)");
     if (L.guide.R > 0)
         return fail(ctx, NST_E_STATE, "the stripe closure implements no spatial control (nst_level_set_guidance(ctx, 0, 0, ...) clears it)");
     if (!L.targets) return fail(ctx, NST_E_STATE, "targets of the stripe not set");
@@ -1486,6 +1568,7 @@ int nst_level_set_guidance(nst_ctx* ctx, int level, int R, const float* planes, 
     if (ctx->gs_on()) return fail(ctx, NST_E_STATE, "guided Gram matrices take the plain statistic only (nst_job_set_gram_shift with zeros switches the shift off)");
     if (ctx->mom_on()) return fail(ctx, NST_E_STATE, "guided levels take no moment loss (nst_job_set_moments with zeros switches it off)");
     if (L.pm.on()) return fail(ctx, NST_E_STATE, "a level with the MRF term takes no guidance (nst_level_set_patches(ctx, level, NULL, ...) clears the term)");
+    if (L.hist.on()) return fail(ctx, NST_E_STATE, "a level with the histogram loss takes no guidance (nst_level_set_histograms(ctx, level, NULL, ...) clears the term)");
     if (!planes) return fail(ctx, NST_E_ARG, "null argument");
     float lam[NST_MAX_REGIONS] = {1.f, 1.f, 1.f, 1.f};
     bool positive = lambda == nullptr;

@@ -478,6 +478,7 @@ int nst_ctx_create_ex(int device, const float* const* weights, const float* cons
     if (e == hipSuccess) e = conv_wino_init_device();
     if (e == hipSuccess) e = gram_init_device();
     if (e == hipSuccess) e = pm_init_device();
+    if (e == hipSuccess) e = hist_init_device();
     // options: an explicit argument wins; -1 falls back to the environment (read here, once), then to the default
     if (opts.conv_mode >= 0) {
         if (opts.conv_mode > NST_CONV_F16X2) { ctx->err = "nst_options.conv_mode must be NST_CONV_F32, NST_CONV_BF16X3 or NST_CONV_F16X2"; return bail(NST_E_ARG); }
@@ -682,6 +683,7 @@ int nst_job_set_taps(nst_ctx* ctx, int content_index, unsigned style_mask, int u
         LevelWs& L = ctx->lv[i];
         L.guide = Guidance();           // (sized for the old style set: nst_level_set_guidance again)
         L.pm = PatchLevel();            // (the style's maps of the old taps: nst_level_set_patches again)
+        L.hist = HistLevel();           // (likewise: nst_level_set_histograms again)
         free_tap_buffers(L);
         NSTCHK(alloc_tap_buffers(ctx, L));
     }
@@ -706,6 +708,7 @@ int nst_job_set_color(nst_ctx* ctx, int mode) {
     for (int i = 0; i < ctx->levels && channels != ctx->channels; ++i) ctx->lv[i].anc = AnchorLevel();
     // the MRF term holds maps of the style image as the other mode's network saw it (nst_level_set_patches): dropped
     for (int i = 0; i < ctx->levels; ++i) ctx->lv[i].pm = PatchLevel();
+    for (int i = 0; i < ctx->levels; ++i) ctx->lv[i].hist = HistLevel();     // (the histogram loss's style record likewise)
     ctx->channels = channels;
     return NST_OK;
 }
@@ -721,6 +724,7 @@ int nst_job_set_pooling(nst_ctx* ctx, int mode) {
     quiesce(ctx);
     drop_closure_state(ctx, true);
     for (int i = 0; i < ctx->levels; ++i) ctx->lv[i].pm = PatchLevel();      // (the MRF term's maps are the other network's)
+    for (int i = 0; i < ctx->levels; ++i) ctx->lv[i].hist = HistLevel();     // (and the histogram loss's style record)
     ctx->pool_avg = mode == NST_POOL_AVG ? 1 : 0;
     return NST_OK;
 }
@@ -1189,6 +1193,120 @@ int nst_level_patch_matches(nst_ctx* ctx, int level, int map, int* idx_out, void
     HIPCHK(ctx, hipMemcpyAsync(idx_out, L.pm.nn[map], n * sizeof(int), hipMemcpyDeviceToDevice, s));
     mark(ctx, s);
     return NST_OK;
+}
+
+// The histogram loss of one level (Risser, Wilmot & Barnes 2017; include/nst_hip.h has the definition): the range and counts of
+// the style's weighted maps, and the image side's buffers.  The style's maps live on scratch only.  Life cycle of
+// nst_level_set_patches: everything is made here beside what the level has (a refusal changes nothing), the context's work is
+// waited for before the level's block is replaced, and the captured closure, an optimiser's remembered closure and a pending
+// backward half go.  The targets stay.
+int nst_level_set_histograms(nst_ctx* ctx, int level, const float* style, int hs, int ws, const float* weights, int bins, void* stream) {
+    if (ctx) { ++ctx->closure_epoch; ++ctx->ws_seq; }
+    NSTCHK(bind(ctx));
+    if (ctx->levels < 1) return fail(ctx, NST_E_STATE, "nst_job_configure has not been called");
+    if (level < 0 || level >= ctx->levels) return fail(ctx, NST_E_ARG, "level out of range");
+    LevelWs& L = ctx->lv[level];
+    HistLevel g;
+    bool on = false;
+    if (style) {
+        if (!weights) return fail(ctx, NST_E_ARG, "null argument");
+        for (int i = 0; i < 6; ++i) {
+            if (!(weights[i] >= 0.f) || std::isinf(weights[i])) return fail(ctx, NST_E_ARG, "the histogram weights must be finite and >= 0");
+            g.w[i] = weights[i];
+            on = on || weights[i] > 0.f;
+        }
+        if (bins < 2 || bins > 1024) return fail(ctx, NST_E_ARG, "the number of bins must be 2..1024");
+    }
+    hipStream_t s = enter(ctx, stream);
+    if (on) {
+        if (ctx->use_graph) return fail(ctx, NST_E_STATE, "the histogram loss's launches are not captured: a context with use_graph takes no term");
+        if (L.guide.R > 0) return fail(ctx, NST_E_STATE, "a guided level takes no histogram loss (nst_level_set_guidance(ctx, level, 0, ...) clears the guidance)");
+        if (hs < 16 || ws < 16) return fail(ctx, NST_E_ARG, "style image must be at least 16x16");
+        const unsigned style_mask = style_mask_of(ctx->taps);
+        int deepest = -1;
+        for (int i = 0; i < 6; ++i) {
+            if (!(g.w[i] > 0.f)) continue;
+            if (!((style_mask >> i) & 1u)) return fail(ctx, NST_E_ARG, "a positive histogram weight on a map that is not a style map of the job");
+            deepest = kTapLayer[i];
+        }
+        g.bins = bins;
+        Scratch sc(ctx, s);
+        NSTCHK(alloc_acts(ctx, sc.acts, hs, ws));
+        NSTCHK(forward(ctx, sc.acts, style, hs, ws, s, deepest, ctx->channels));
+        NSTCHK(g.mem.alloc(ctx, &g.vals, 6));
+        HIPCHK(ctx, hipMemsetAsync(g.vals, 0, 6 * sizeof(float), s));
+        for (int i = 0; i < 6; ++i) {
+            if (!(g.w[i] > 0.f)) continue;
+            const int l = kTapLayer[i], C = kCout[l];
+            const size_t cb = (size_t)C * bins;
+            g.Ns[i] = (size_t)sc.acts.h[l] * sc.acts.w[l];
+            NSTCHK(g.mem.alloc(ctx, &g.s_lo_hi[i], (size_t)2 * C));
+            NSTCHK(g.mem.alloc(ctx, &g.s_counts[i], cb));
+            NSTCHK(g.mem.alloc(ctx, &g.lo_hi[i], (size_t)2 * C));
+            NSTCHK(g.mem.alloc(ctx, &g.counts[i], cb));
+            NSTCHK(g.mem.alloc(ctx, &g.ends[i], 2 * cb));
+            NSTCHK(g.mem.alloc(ctx, &g.partial[i], (size_t)HIST_VALUE_BLOCKS));
+            HIPCHK(ctx, launch_hist_counts(sc.acts.act[l], g.Ns[i], C, bins, g.s_lo_hi[i], g.s_counts[i], s));
+            HIPCHK(ctx, hipMemsetAsync(g.lo_hi[i], 0, (size_t)2 * C * sizeof(float), s));
+            HIPCHK(ctx, hipMemsetAsync(g.counts[i], 0, cb * sizeof(unsigned), s));
+            HIPCHK(ctx, hipMemsetAsync(g.ends[i], 0, 2 * cb * sizeof(float), s));
+        }
+        NSTCHK(sc.finish());       // (synchronises: the caller's image is free again when this returns)
+    } else {
+        g = HistLevel();
+    }
+    quiesce(ctx);
+    drop_closure_state(ctx, false);
+    L.hist = std::move(g);
+    return NST_OK;
+}
+
+int nst_level_histograms(const nst_ctx* ctx, int level, float* weights, int* bins) {
+    if (!ctx) return fail(nullptr, NST_E_ARG, "null context");
+    if (level < 0 || level >= ctx->levels) return fail(nullptr, NST_E_ARG, "level out of range");
+    const HistLevel& g = ctx->lv[level].hist;
+    for (int i = 0; i < 6 && weights; ++i) weights[i] = g.w[i];
+    if (bins) *bins = g.bins;
+    return NST_OK;
+}
+
+// the unweighted hist_i of the last closure, levels x 6 by map index (zeros: levels without the term or outside the last level
+// mask, maps without a weight, no closure yet)
+int nst_job_histogram_losses(nst_ctx* ctx, float* out, void* stream) {
+    NSTCHK(bind(ctx));
+    if (ctx->levels < 1) return fail(ctx, NST_E_STATE, "nst_job_configure has not been called");
+    if (!out) return fail(ctx, NST_E_ARG, "null argument");
+    hipStream_t s = enter(ctx, stream);
+    for (int i = 0; i < ctx->levels; ++i) {
+        const HistLevel& g = ctx->lv[i].hist;
+        if (g.on()) HIPCHK(ctx, hipMemcpyAsync(out + 6 * i, g.vals, 6 * sizeof(float), hipMemcpyDeviceToDevice, s));
+        else HIPCHK(ctx, hipMemsetAsync(out + 6 * i, 0, 6 * sizeof(float), s));
+    }
+    mark(ctx, s);
+    return NST_OK;
+}
+
+// one weighted map of a level: the image side of the last closure (zeros before any closure), or the style's record
+static int hist_read(nst_ctx* ctx, int level, int map, bool style, float* lo_hi, unsigned* counts, float* ends, void* stream) {
+    NSTCHK(bind(ctx));
+    if (level < 0 || level >= ctx->levels) return fail(ctx, NST_E_ARG, "level out of range");
+    if (map < 0 || map > 5) return fail(ctx, NST_E_ARG, "bad argument");
+    const HistLevel& g = ctx->lv[level].hist;
+    if (!(g.w[map] > 0.f)) return fail(ctx, NST_E_STATE, "the map carries no histogram loss on this level (nst_level_set_histograms)");
+    const int C = kCout[kTapLayer[map]];
+    const size_t cb = (size_t)C * g.bins;
+    hipStream_t s = enter(ctx, stream);
+    if (lo_hi) HIPCHK(ctx, hipMemcpyAsync(lo_hi, style ? g.s_lo_hi[map] : g.lo_hi[map], (size_t)2 * C * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (counts) HIPCHK(ctx, hipMemcpyAsync(counts, style ? g.s_counts[map] : g.counts[map], cb * sizeof(unsigned), hipMemcpyDeviceToDevice, s));
+    if (ends) HIPCHK(ctx, hipMemcpyAsync(ends, g.ends[map], 2 * cb * sizeof(float), hipMemcpyDeviceToDevice, s));
+    mark(ctx, s);
+    return NST_OK;
+}
+int nst_level_histogram_tables(nst_ctx* ctx, int level, int map, float* lo_hi, unsigned* counts, float* ends, void* stream) {
+    return hist_read(ctx, level, map, false, lo_hi, counts, ends, stream);
+}
+int nst_level_histogram_style(nst_ctx* ctx, int level, int map, float* lo_hi, unsigned* counts, void* stream) {
+    return hist_read(ctx, level, map, true, lo_hi, counts, nullptr, stream);
 }
 
 // The semantic guidance of a level's MRF term (neural-doodle; include/nst_hip.h has the definition).  The planes of both sides

@@ -237,6 +237,29 @@ struct PatchLevel {
     }
 };
 
+// The histogram loss of one level (nst_level_set_histograms; include/nst_hip.h has the definition), by map index: the weight
+// (0: the map has no term), the style's record (s_lo_hi: C x 2, s_counts: C x bins, Ns pixels - the style's maps are not kept),
+// the image side of the last closure (lo_hi, counts, the table ends: C x bins x 2), the value partials, and the unweighted
+// hist_i (six floats, which the forward half writes and the loss rows read).  Data of one job with PatchLevel's life cycle:
+// everything is made by the setter, a closure allocates nothing.
+struct HistLevel {
+    float w[6] = {};
+    int bins = 256;
+    size_t Ns[6] = {};
+    float* s_lo_hi[6] = {};
+    unsigned* s_counts[6] = {};
+    float* lo_hi[6] = {};
+    unsigned* counts[6] = {};
+    float* ends[6] = {};
+    double* partial[6] = {};    // HIST_VALUE_BLOCKS each
+    float* vals = nullptr;
+    DevMem mem;
+    bool on() const {
+        for (float v : w) if (v > 0.f) return true;
+        return false;
+    }
+};
+
 // the level image and its gradient (levels >= 1), planar: channels (nst_job_set_color) x h x w floats each
 struct LevelImage {
     float* xl = nullptr;
@@ -253,6 +276,7 @@ struct LevelWs {
     MomentLevel mom;
     AnchorLevel anc;
     PatchLevel pm;
+    HistLevel hist;
     ActSet acts;
     float* gbuf[2] = {};
     size_t gbuf_floats = 0;
@@ -382,7 +406,7 @@ struct nst_ctx {
         if (mom_on() && mom_slot(q)) return L.mom.row_bias(q);
         return gs_on() ? L.gs.row_bias(q) : nullptr;
     }
-    // bumped on entry to every call that changes what a closure computes (configure, taps, colour, pooling, style weights, Laplacian, matting, Gram shift, moments, targets, a level's anchor, a level's MRF term), failure paths
+    // bumped on entry to every call that changes what a closure computes (configure, taps, colour, pooling, style weights, Laplacian, matting, Gram shift, moments, targets, a level's anchor, a level's MRF term, a level's histogram loss), failure paths
     // included: an optimiser's remembered closure result is valid only under the epoch it was made in (nst_opt.cpp)
     unsigned long long closure_epoch = 0;
     // advanced on entry to every call that reads or writes the level workspaces (nst_closure*, nst_window_*,
@@ -510,6 +534,8 @@ struct Inject {
     const GuidedBwd* guided = nullptr; // guided Gram backward (R, t, S filled in): dF = sum_r t_r^2 F S_r, by a launch of its own
     const PatchTerm* mrf = nullptr;  // the MRF term of the map (nst_level_set_patches): its gradient joins the addend of the launch
     float mrf_coef = 0.f;
+    const HistTerm* hist = nullptr;  // the histogram loss of the map (nst_level_set_histograms): likewise, after the MRF term
+    float hist_coef = 0.f;
 };
 struct ContentJob { const float* target; size_t n; float coef; double* partial; };
 // channels = 1: x is a luminance plane u, conv1_1 sees x_c = u - mean_c (nst_job_set_color)

@@ -378,6 +378,9 @@ struct LevelLossInputs {
     // (nullptr: the level has no term and its row is what it is without it), and the weights (0: the map has no term)
     float* mrf_vals;
     float mrf_w[6];
+    // histogram loss (nst_level_set_histograms), a level's own, in the same form: the six unweighted hist_i and the weights
+    float* hist_vals;
+    float hist_w[6];
 };
 struct LossAssembly {
     LevelLossInputs lv[8];
@@ -546,6 +549,25 @@ struct PatchTerm { const float* f; int h, w; const int* idx; PatchDict d; };
 hipError_t launch_pm_value_partials(const PatchTerm& t, double* partial, hipStream_t stream);
 hipError_t launch_pm_value(const double* partial, double denom, float* out, hipStream_t stream);
 hipError_t launch_pm_grad(const PatchTerm& t, float coef, float* out, int accumulate, hipStream_t stream);
+
+// histogram.hip: the histogram loss (include/nst_hip.h has the definition) --------------------------------------------------
+// Maps are NHWC, N pixels x C channels, C = 64 / 128 / 256 / 512, N C < 2^31; bins = 2..1024.  lo_hi: C x 2 floats (lo_c, hi_c);
+// counts: C x bins uint32; ends: C x bins x 2 floats (start_b, end_b; zeros at empty image bins).
+constexpr int HIST_SLAB = 32;               // channels of one workgroup of the counts pass: bins x 32 words of LDS
+constexpr int HIST_VALUE_BLOCKS = 2048;     // double partials of the value's first stage
+hipError_t hist_init_device();     // raises the dynamic-LDS limit of the counts kernel: once per device, before the first launch there
+bool hist_channels_ok(int C);
+// range, then counts, of f: both outputs are written whole (lo_hi holds the range keys in between)
+hipError_t launch_hist_counts(const float* f, size_t N, int C, int bins, float* lo_hi, unsigned* counts, hipStream_t stream);
+// the two ends of every non-empty image bin from the image's counts and the style's record
+hipError_t launch_hist_tables(const unsigned* counts, size_t N, const float* s_lo_hi, const unsigned* s_counts, size_t Ns, int C, int bins,
+                              float* ends, hipStream_t stream);
+// Value and gradient at fixed tables.  The value in two ordered stages: HIST_VALUE_BLOCKS double partials of sum (F - R)^2, then
+// out = (float)(their sum / denom).  The gradient: out (the map's shape) = coef (F - R), written or (accumulate) added.
+struct HistTerm { const float* f; size_t N; int C, bins; const float* lo_hi; const float* ends; };
+hipError_t launch_hist_value_partials(const HistTerm& t, double* partial, hipStream_t stream);
+hipError_t launch_hist_value(const double* partial, double denom, float* out, hipStream_t stream);
+hipError_t launch_hist_grad(const HistTerm& t, float coef, float* out, int accumulate, hipStream_t stream);
 
 // gram_guided.hip: spatial control (guided Gram matrices; include/nst_hip.h has the definitions) ---------------------
 constexpr int NST_MAX_REGIONS_K = 4;

@@ -654,6 +654,7 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(LossAssembly la) {
         if (la.mom_on && threadIdx.x < 12) la.mom_out[12 * l + threadIdx.x] = 0.f;
         if (in.tmp_gamma > 0.f && threadIdx.x == 0) in.tmp_out[0] = 0.f;
         if (in.mrf_vals && threadIdx.x < 6) in.mrf_vals[threadIdx.x] = 0.f;
+        if (in.hist_vals && threadIdx.x < 6) in.hist_vals[threadIdx.x] = 0.f;
         return;
     }
     double v[7];
@@ -772,6 +773,11 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(LossAssembly la) {
             // (... + gamma tmp) + sum_i w_i mrf_i over the maps with a weight, in ascending map order: every product and sum rounded
             for (int i = 0; i < 6; ++i)
                 if (in.mrf_w[i] > 0.f) total = total + in.mrf_w[i] * in.mrf_vals[i];
+        }
+        if (in.hist_vals) {
+            // (... + sum_i w_i mrf_i) + sum_i w_i hist_i, likewise
+            for (int i = 0; i < 6; ++i)
+                if (in.hist_w[i] > 0.f) total = total + in.hist_w[i] * in.hist_vals[i];
         }
         la.out[4 * l + 0] = total;
         la.out[4 * l + 1] = content;

@@ -19,6 +19,7 @@ from . import laplacian_modes as _lap
 from . import matting_modes as _mat
 from . import flow_modes as _flow
 from . import mrf_modes as _mrf
+from . import hist_modes as _hist
 from ._lib import NST_LOSS_ROW, NstError, StepInfo
 
 TAP_CHANNELS = (64, 128, 256, 512, 512, 512)
@@ -752,6 +753,117 @@ class StyleEngine:
                                                              _regions.MAX_REGIONS, _ptr(d), _ptr(e), g, _ptr(idx), _ptr(score),
                                                              _stream(self.device)), "nst_patch_match_guided")
         return idx, score
+
+    # ---- the histogram loss (nst_level_set_histograms; histogram_loss.py is the driver) ----------------------
+    def set_histograms(self, level: int, style: Optional[torch.Tensor], weights=None, bins: int = _hist.DEFAULT_BINS) -> None:
+        """The histogram loss of one level (nst_level_set_histograms; Risser, Wilmot & Barnes 2017): the level total gains
+        sum_i w_i hist_i, hist_i the mean squared distance of map i from its remap onto the style's per-channel histograms.
+        style: the level's style image, a device float32 (C,hs,ws) tensor (any leading ones; C = 3, or 1 in luminance mode),
+        which is run through the network and of whose weighted maps range and counts are kept; weights: as
+        hist_modes.normalize_weights takes them.  Data of the job, not a setting: configure(), set_taps, set_pooling and
+        set_color drop it.  style None or zero weights clear the level's term."""
+        setting = None if style is None else _hist.normalize_hist(weights, bins, None, self.taps[1])
+        if setting is None:
+            _lib.check(self.ctx, self.lib.nst_level_set_histograms(self.ctx, int(level), None, 0, 0, None, _hist.DEFAULT_BINS,
+                                                                   _stream(self.device)), "nst_level_set_histograms")
+            return
+        w, bins, _ = setting
+        ch = self.channels
+        if style.dim() < 3 or style.numel() != ch * style.shape[-2] * style.shape[-1]:
+            raise NstError(f"the style image of level {level} must have shape ({ch},hs,ws), got {tuple(style.shape)}")
+        style = style.contiguous()
+        _chk_dev(style, self.device)
+        _lib.check(self.ctx, self.lib.nst_level_set_histograms(self.ctx, int(level), _ptr(style), int(style.shape[-2]),
+                                                               int(style.shape[-1]), (C.c_float * 6)(*w), bins, _stream(self.device)),
+                   "nst_level_set_histograms")
+
+    def clear_histograms(self, level: Optional[int] = None) -> None:
+        """No histogram loss on one level, or (None) on any configured level."""
+        for l in (range(self.levels) if level is None else (level,)):
+            self.set_histograms(l, None)
+
+    def histograms_setting(self, level: int):
+        """(weights (6,), bins) of a level (nst_level_histograms), or None when the level has no term."""
+        w, b = (C.c_float * 6)(), C.c_int()
+        _lib.check(self.ctx, self.lib.nst_level_histograms(self.ctx, int(level), w, C.byref(b)), "nst_level_histograms")
+        ws = tuple(float(v) for v in w)
+        return None if all(v == 0.0 for v in ws) else (ws, b.value)
+
+    def histogram_losses(self) -> torch.Tensor:
+        """(levels, 6) device tensor: the unweighted hist_i of the last closure by map index (nst_job_histogram_losses); zeros
+        for maps without the term and levels outside the last level mask."""
+        out = torch.empty((self.levels, 6), dtype=torch.float32, device=self.device)
+        _lib.check(self.ctx, self.lib.nst_job_histogram_losses(self.ctx, _ptr(out), _stream(self.device)), "nst_job_histogram_losses")
+        return out
+
+    def histogram_tables(self, level: int, map: int):
+        """(lo_hi (C,2) float32, counts (C,B) int32, ends (C,B,2) float32) device tensors: the image side of map index `map`
+        of a level as the last closure made it (nst_level_histogram_tables)."""
+        st = self.histograms_setting(level)
+        c, b = TAP_CHANNELS[map], (st[1] if st else _hist.DEFAULT_BINS)
+        lo_hi = torch.empty((c, 2), dtype=torch.float32, device=self.device)
+        counts = torch.empty((c, b), dtype=torch.int32, device=self.device)
+        ends = torch.empty((c, b, 2), dtype=torch.float32, device=self.device)
+        _lib.check(self.ctx, self.lib.nst_level_histogram_tables(self.ctx, int(level), int(map), _ptr(lo_hi), _ptr(counts), _ptr(ends),
+                                                                 _stream(self.device)), "nst_level_histogram_tables")
+        return lo_hi, counts, ends
+
+    def histogram_style(self, level: int, map: int):
+        """(lo_hi (C,2) float32, counts (C,B) int32): the style's record of map index `map` of a level
+        (nst_level_histogram_style)."""
+        st = self.histograms_setting(level)
+        c, b = TAP_CHANNELS[map], (st[1] if st else _hist.DEFAULT_BINS)
+        lo_hi = torch.empty((c, 2), dtype=torch.float32, device=self.device)
+        counts = torch.empty((c, b), dtype=torch.int32, device=self.device)
+        _lib.check(self.ctx, self.lib.nst_level_histogram_style(self.ctx, int(level), int(map), _ptr(lo_hi), _ptr(counts),
+                                                                _stream(self.device)), "nst_level_histogram_style")
+        return lo_hi, counts
+
+    def histogram_counts(self, f: torch.Tensor, bins: int = _hist.DEFAULT_BINS):
+        """Range and counts alone (nst_histogram_counts): f (N,C) or (h,w,C) device float32 in NHWC, C = 64, 128, 256 or 512
+        -> (lo_hi (C,2) float32, counts (C,B) int32)."""
+        bins = _hist.check_bins(bins)
+        _chk_dev(f, self.device)
+        c = f.shape[-1]
+        n = f.numel() // c
+        lo_hi = torch.empty((c, 2), dtype=torch.float32, device=self.device)
+        counts = torch.empty((c, bins), dtype=torch.int32, device=self.device)
+        _lib.check(self.ctx, self.lib.nst_histogram_counts(self.ctx, _ptr(f), n, c, bins, _ptr(lo_hi), _ptr(counts), _stream(self.device)),
+                   "nst_histogram_counts")
+        return lo_hi, counts
+
+    def histogram_table(self, lo_hi: torch.Tensor, counts: torch.Tensor, n: int, s_lo_hi: torch.Tensor, s_counts: torch.Tensor,
+                        ns: int) -> torch.Tensor:
+        """The tables alone (nst_histogram_tables): the image's and the style's range and counts (histogram_counts) and their
+        pixel counts -> ends (C,B,2) float32."""
+        c, bins = counts.shape
+        _chk_dev(lo_hi, self.device, (c, 2))
+        _chk_dev(s_lo_hi, self.device, (c, 2))
+        for t in (counts, s_counts):
+            if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (c, bins)):
+                raise NstError(f"counts must be contiguous int32 CUDA tensors of shape ({c},{bins})")
+        ends = torch.empty((c, bins, 2), dtype=torch.float32, device=self.device)
+        _lib.check(self.ctx, self.lib.nst_histogram_tables(self.ctx, _ptr(lo_hi), _ptr(counts), int(n), _ptr(s_lo_hi), _ptr(s_counts),
+                                                           int(ns), c, bins, _ptr(ends), _stream(self.device)), "nst_histogram_tables")
+        return ends
+
+    def histogram_term(self, f: torch.Tensor, lo_hi: torch.Tensor, ends: torch.Tensor, coef: Optional[float] = None,
+                       want_grad: bool = True):
+        """Value and gradient alone at the given tables (nst_histogram_term): hist (device scalar) and, with want_grad, the
+        gradient in f's shape under `coef` (None: 2 / (C N), the gradient of hist itself)."""
+        _chk_dev(f, self.device)
+        c = f.shape[-1]
+        n = f.numel() // c
+        bins = ends.shape[1]
+        _chk_dev(lo_hi, self.device, (c, 2))
+        _chk_dev(ends, self.device, (c, bins, 2))
+        if coef is None:
+            coef = 2.0 / (float(c) * n)
+        val = torch.empty(1, dtype=torch.float32, device=self.device)
+        grad = torch.empty_like(f) if want_grad else None
+        _lib.check(self.ctx, self.lib.nst_histogram_term(self.ctx, _ptr(f), n, c, bins, _ptr(lo_hi), _ptr(ends), float(coef), _ptr(val),
+                                                         _ptr(grad), _stream(self.device)), "nst_histogram_term")
+        return (val, grad) if want_grad else val
 
     def closure(self, x: torch.Tensor, cw: float, sw: float, tvw: float,
                 grad: Optional[torch.Tensor] = None, losses: Optional[torch.Tensor] = None):
@@ -1493,6 +1605,7 @@ class PixelOptimizer:
         if any(e.anchor(l)[0] > 0 for l in range(e.levels)):
             raise ValueError("a temporal anchor cannot be combined with stripe sharding (clear_anchor())")
         _mrf.check_exclusive(next((st for st in (e.patches_setting(l) for l in range(e.levels)) if st is not None), None), stripes=True)
+        _hist.check_exclusive(next((st for st in (e.histograms_setting(l) for l in range(e.levels)) if st is not None), None), stripes=True)
         contents = list(content_t) if isinstance(content_t, (list, tuple)) else [content_t]
         styles = list(style_t) if isinstance(style_t, (list, tuple)) else [style_t]
         if blend is not None and styles and isinstance(styles[0], torch.Tensor):

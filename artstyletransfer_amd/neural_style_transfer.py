@@ -27,6 +27,7 @@ from . import laplacian_modes as _lap
 from . import matting_modes as _mat
 from . import moment_modes as _mom
 from . import mrf_modes as _mrf
+from . import hist_modes as _hist
 
 # ImageNet statistics (reference :22-23)
 IMAGENET_MEAN_255 = [123.675, 116.28, 103.53]
@@ -265,6 +266,14 @@ class _DeviceJob:
                     self.engine.set_patch_guidance(lvl, torch.from_numpy(planes[0]).to(self.dev), torch.from_numpy(planes[1]).to(self.dev),
                                                    weight)
 
+    def set_histogram_loss(self, weights, bins, levels):
+        """The histogram loss of the levels (StyleEngine.set_histograms; `levels` None: every level): each level gets the style
+        level image its targets were made from, as set_patch_match does."""
+        with torch.cuda.device(self.dev), torch.cuda.stream(self.job_stream):
+            for lvl, style_of in enumerate(self.style_levels):
+                if levels is None or lvl in levels:
+                    self.engine.set_histograms(lvl, style_of(), weights, bins)
+
     def step(self, cw, sw, tvw):
         """One optimizer.step(closure) (nst_opt_step).  Runs on a pool thread, whose current stream is its own."""
         with torch.cuda.stream(self.job_stream):
@@ -342,6 +351,7 @@ class NeuralStyleTransfer:
         self.__anchor = None                     # set_anchor: data of the next `process`, not a setting
         self.__patches = None                    # set_patch_match: likewise
         self.__semantics = None                  # set_patch_semantics: likewise
+        self.__histograms = None                 # set_histogram_loss: likewise
 
     def set_feature_maps(self, content_layer=None, style_layers=None, use_relu=True):
         """Extension: the feature maps the losses of the next `process` read - a content map and a set of style maps of
@@ -480,6 +490,19 @@ class NeuralStyleTransfer:
         argument, one map without the other, mismatched R and - in `process` - semantic maps without the MRF term."""
         self.__semantics = _mrf.normalize_semantic(content_regions, style_regions, weight)
 
+    def set_histogram_loss(self, weights=None, bins=_hist.DEFAULT_BINS, levels=None):
+        """Extension: the histogram loss of Risser, Wilmot & Barnes 2017 in the next `process`: per pyramid level
+        sum_i w_i hist_i, hist_i the mean squared distance of map i from its remap onto the per-channel histograms of the same
+        map of the level's style image (nst_level_set_histograms in include/nst_hip.h has the definition).  `weights`: None or
+        0 (off), a number (that weight on those of relu1_1 and relu4_1 that are style maps of the job), six numbers by map
+        index of Vgg19.layer_names, or a dict {map index or name: number}; `bins`: 2..1024; `levels`: None for every level, or
+        the level indices that carry the term (0 = the full resolution).  Data of one job, like set_patch_match - not one of
+        `settings`.  ValueError for a malformed setting and - in `process`, where the style set is known - for a positive
+        weight on a map that is not a style map, or the term together with regions or several style images."""
+        _hist.normalize_hist(weights, bins, levels)          # (malformed: here and now; the style set comes with `process`)
+        off = weights is None or (isinstance(weights, (int, float)) and not isinstance(weights, bool) and weights == 0)
+        self.__histograms = None if off else (weights, bins, levels)
+
     async def process(self, content_imgs, init_img, lr_start, iters_num, content_weight, style_weight, tv_weight,
                       init_img_name):
         # validates the model name exactly as the reference does (ValueError for anything but vgg19)
@@ -517,6 +540,11 @@ class NeuralStyleTransfer:
                 raise ValueError("semantic maps steer the MRF term: set_patch_semantics needs set_patch_match (mrf_weight is off)")
             semantics = _mrf.semantic_level_planes(self.__semantics, [tuple(c.shape[:2]) for c in content_imgs],
                                                    [tuple(s.shape[:2]) for s in style_imgs], patches[3])
+        histograms = None
+        if self.__histograms is not None:
+            style_set, use_relu = resolved["taps"][1:] if "taps" in resolved else (_taps.DEFAULT_STYLE_INDICES, True)
+            histograms = _hist.normalize_hist(*self.__histograms, style_indices=style_set, use_relu=use_relu, levels_num=len(content_imgs))
+            _hist.check_exclusive(histograms, regions=resolved.get("regions"), extra_styles=resolved.get("blend"))
         if self.__anchor is not None and len(self.__anchor[0]) != len(content_imgs):
             raise ValueError(f"{len(self.__anchor[0])} anchor levels for a job of {len(content_imgs)} levels")
         job = _make_job(self.__device, self.__optimizer_name, style_imgs, content_imgs, init_img, lr_start, **resolved)
@@ -531,6 +559,12 @@ class NeuralStyleTransfer:
                 job.set_patch_match(*patches)
                 if semantics is not None:
                     job.set_patch_semantics(semantics, self.__semantics[2])
+            except BaseException:
+                job.close()
+                raise
+        if histograms is not None:           # (likewise, after the MRF term)
+            try:
+                job.set_histogram_loss(*histograms)
             except BaseException:
                 job.close()
                 raise
@@ -634,11 +668,12 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
 
 def _transfer_from(content_n_style, content_weight, style_weight, tv_weight, optimizer, model, init_method, iters_num, levels_num,
                    noise_factor, noise_levels, noise_levels_central_amplitude, noise_levels_peripheral_amplitude,
-                   noise_levels_dispersion, *, device=None, start=None, patches=None, semantics=None, **keywords):
+                   noise_levels_dispersion, *, device=None, start=None, patches=None, semantics=None, histograms=None, **keywords):
     """The settings validation of neural_style_transfer() (`keywords`: its keyword-only parameters), here and now - before any
     GPU work, ValueError - and then the job as an async generator, from the `init_method` image or from `start` (_transfer).
     `patches` (patch_match.py): None, or the arguments of NeuralStyleTransfer.set_patch_match, validated here too;
-    `semantics`: None, or the arguments of NeuralStyleTransfer.set_patch_semantics, likewise (they need `patches`)."""
+    `semantics`: None, or the arguments of NeuralStyleTransfer.set_patch_semantics, likewise (they need `patches`);
+    `histograms` (histogram_loss.py): None, or the arguments of NeuralStyleTransfer.set_histogram_loss, likewise."""
     settings = _job.JobSettings(for_job=True, **keywords)
 
     def level_shapes(img):      # (the level sizes follow from the image size: top level first)
@@ -657,6 +692,11 @@ def _transfer_from(content_n_style, content_weight, style_weight, tv_weight, opt
             semantics = None
         elif patches is None:
             raise ValueError("semantic_content / semantic_style steer the MRF term: mrf_weight is off")
+    if histograms is not None:
+        style_set, use_relu = resolved["taps"][1:] if "taps" in resolved else (_taps.DEFAULT_STYLE_INDICES, True)
+        checked = _hist.normalize_hist(*histograms, style_indices=style_set, use_relu=use_relu, levels_num=max(levels_num, 1))
+        _hist.check_exclusive(checked, regions=resolved.get("regions"), extra_styles=keywords.get("extra_styles"))
+        histograms = histograms if checked is not None else None
     extra_styles = keywords.get("extra_styles")
     extra_styles = list(extra_styles) if extra_styles is not None else []
     for img in extra_styles:
@@ -665,18 +705,19 @@ def _transfer_from(content_n_style, content_weight, style_weight, tv_weight, opt
     return _transfer(content_n_style, content_weight, style_weight, tv_weight, optimizer, model, init_method, iters_num, levels_num,
                      noise_factor, noise_levels, noise_levels_central_amplitude, noise_levels_peripheral_amplitude,
                      noise_levels_dispersion, device, settings, keywords.get("preserve_color"), extra_styles,
-                     keywords.get("style_blend"), start, patches, semantics)
+                     keywords.get("style_blend"), start, patches, semantics, histograms)
 
 
 async def _transfer(content_n_style, content_weight, style_weight, tv_weight, optimizer, model, init_method, iters_num, levels_num,
                     noise_factor, noise_levels, noise_levels_central_amplitude, noise_levels_peripheral_amplitude,
                     noise_levels_dispersion, device, settings, preserve_color, extra_styles, style_blend, start=None, patches=None,
-                    semantics=None):
+                    semantics=None, histograms=None):
     """neural_style_transfer() below its settings validation: `settings` is its validated JobSettings, `extra_styles` its
     checked list.  `start` (video.py): None, or a callable (setup engine, level-0 (h, w)) -> (start image: a device HWC
     tensor the job starts from in place of the `init_method` image, anchor levels, weight levels, gamma) - the arguments of
     NeuralStyleTransfer.set_anchor - called once the level sizes are known.  `patches` (patch_match.py): None, or the checked
-    arguments of NeuralStyleTransfer.set_patch_match; `semantics`: None, or those of NeuralStyleTransfer.set_patch_semantics."""
+    arguments of NeuralStyleTransfer.set_patch_match; `semantics`: None, or those of NeuralStyleTransfer.set_patch_semantics;
+    `histograms` (histogram_loss.py): None, or those of NeuralStyleTransfer.set_histogram_loss."""
     if device is None:
         if not torch.cuda.is_available():
             raise RuntimeError("no GPU visible: the HIP style-transfer engine has no CPU path")
@@ -715,6 +756,8 @@ async def _transfer(content_n_style, content_weight, style_weight, tv_weight, op
         nst.set_patch_match(*patches)
     if semantics is not None:
         nst.set_patch_semantics(*semantics)
+    if histograms is not None:
+        nst.set_histogram_loss(*histograms)
     # (the extra styles as their pyramids; "histogram" has recoloured the style levels above)
     settings.update(extra_styles=extra_levels, style_blend=style_blend if extra_levels else None)
     if preserve_color == "histogram":

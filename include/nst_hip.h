@@ -942,6 +942,74 @@ int nst_patch_descriptors(nst_ctx* ctx, const float* planes /* device (R,hm,wm) 
 int nst_patch_match_guided(nst_ctx* ctx, const float* f, int h, int w, int C, const float* fs, int hs, int ws, int stride,
                            double epsilon, int R, const float* d /* device (n,4) */, const float* e /* device (m,4) */, float gamma,
                            int* idx_out /* nullable */, float* score_out /* nullable */, void* stream);
+/* ---- The histogram loss (Risser, Wilmot & Barnes 2017, "Stable and Controllable Neural Texture Synthesis and Style Transfer
+ * Using Histogram Losses") ------------------------------------------------------------------------------------------------
+ * Every channel of a tapped map is remapped so that its histogram becomes the style's, and the map is pulled towards its
+ * remap.  For one pyramid level and one tapped map of index i in Vgg19.layer_names:
+ *   F  = the map of the level image, NHWC, N = h w pixels by C channels, fp32;  Fs = the same map of the level's style image
+ *        (Ns pixels), through the network the job uses (its tap flavour, its pooling, its colour mode);  B = the number of
+ *        bins, 2..1024, default 256.
+ * Range.  lo_c = min_p F[p,c], hi_c = max_p F[p,c], exact (-0 counts as +0).  A channel with hi_c == lo_c is FLAT and has no
+ *   term: value 0, gradient 0, no counts.
+ * Bin.  scale_c = (float)((double)B / ((double)hi_c - (double)lo_c));  x = (v - lo_c) scale_c in fp32, the subtraction and
+ *   the product each rounded once;  b = min(B-1, (int)x);  f = min(1, x - (float)b);  counts[c][b] is uint32.
+ * Style side.  slo, shi and scounts likewise from Fs with its own range, once, in the setter.  The style's maps are not
+ *   kept: per map only C (B + 2) numbers are.
+ * Table.  Every non-empty image bin gets two ends.  Per channel cum_b = sum_{b'<b} counts[b'] and scum_j likewise (uint64),
+ *   width = ((double)shi - (double)slo) / B.
+ *   start_b: the smallest j with scounts[j] > 0 and scum_{j+1} N > cum_b Ns;  t = (cum_b Ns - scum_j N) / (scounts[j] N), the
+ *     products compared and subtracted as 64-bit integers, the quotient in double;  start_b = (float)(slo + (j + t) width).
+ *   end_b: the same with cum_{b+1} and >= in place of >.
+ *   A style channel with shi == slo has start = end = slo.  Empty image bins are never read (their ends are stored as zeros).
+ *   Two ends, not one knot per bin edge: a non-empty bin that follows empty bins would otherwise start at the wrong end of the
+ *   flat piece of the style's inverse CDF.  With two ends a map remapped onto its own histogram comes back, the remap is
+ *   monotone per channel and stays inside [slo, shi].
+ * Remap.  R(v) = start_b + f (end_b - start_b), fp32, three roundings.
+ * Value.  hist_i = (float)((1 / (C N)) sum (F - R)^2), differences and squares formed in double from the fp32 numbers, summed
+ *   in a fixed two-stage order.
+ * Gradient, R held fixed.  dF = coef (F - R), coef = (float)(2 w_i / (C N)) formed in double; fp32, one rounding per
+ *   operation.  It reaches the network as the addend of the launch below the map: after the content gradient and after the
+ *   MRF term's addend where the map has those, beside the Gram second source and its row bias.  The launch's ReLU mask then
+ *   applies as to any addend.
+ * Loss row.  A level with the term has the total (... + sum_i w_i mrf_i) + sum_i w_i hist_i: added after the MRF term, in
+ *   ascending map order, every product and sum rounded.  NST_LOSS_ROW stays 4.  The weights are the term's own:
+ *   style_weight does not scale it.
+ * Determinism.  No float atomic takes part: range and counts combine across workgroups by integer atomics only (the range on
+ *   the order-preserving bit pattern the MRF keys use), the value by fixed-order double partials.  A closure with the term is
+ *   bitwise reproducible.  Everything above is reproducible from the map's bits.
+ * The term runs in all three arithmetic modes: the addend is the walkers' own.
+ *
+ * nst_level_set_histograms: the term of one level, data of one job like the MRF term.  style = device (C,hs,ws) image in the
+ *   job's colour mode, NULL: clear the level's term.  weights[6] by map index.  The call runs the style image through the
+ *   network up to the deepest weighted map, keeps range and counts of the weighted maps and allocates the image side (range,
+ *   counts, tables, value partials): a closure allocates nothing.  Life cycle of nst_level_set_patches: waits for the
+ *   context's work; drops a captured graph, an L-BFGS memo and a pending backward half; a refusal changes nothing;
+ *   nst_job_configure drops the term with the levels; nst_job_set_taps, nst_job_set_pooling and nst_job_set_color drop it.
+ *   NST_E_ARG: level out of range; bins outside 2..1024; negative or non-finite weights; a positive weight on a map that is
+ *   not a style map of the job.
+ *   NST_E_STATE: no configured job; a guided level (nst_level_set_guidance on a level with the term refuses likewise); a
+ *   context with use_graph.  The stripe closure returns NST_E_STATE while its level carries the term.
+ * nst_level_histograms: the level's setting (all-zero weights: no term).
+ * nst_job_histogram_losses: out = device, levels x 6: the unweighted hist_i of the last closure by map index (zeros: maps
+ *   without the term and levels outside the last level mask).
+ * nst_level_histogram_tables: the image side of the last closure of one weighted map: lo_hi (C x 2 floats), counts (C x B
+ *   uint32), ends (C x B x 2 floats), each nullable; zeros before any closure.  nst_level_histogram_style: the style's record.
+ *   NST_E_STATE: the map carries no term on the level.  NST_E_ARG: a level or map out of range.
+ * nst_histogram_counts, nst_histogram_tables, nst_histogram_term: the pieces alone, on NHWC device maps of C = 64, 128, 256 or
+ *   512 channels (else NST_E_ARG) with N C < 2^31.  They read no job state.  Synchronous.  nst_histogram_term: value_out
+ *   (device scalar, nullable) = hist; grad_out (nullable, overwritten, NHWC like f) = the gradient with the given coef. */
+int nst_level_set_histograms(nst_ctx* ctx, int level, const float* style /* device (C,hs,ws), or NULL: clear */, int hs, int ws,
+                             const float* weights /* 6, by map index */, int bins, void* stream);
+int nst_level_histograms(const nst_ctx* ctx, int level, float* weights /* 6 */, int* bins);
+int nst_job_histogram_losses(nst_ctx* ctx, float* out /* device, levels x 6 */, void* stream);
+int nst_level_histogram_tables(nst_ctx* ctx, int level, int map, float* lo_hi /* C x 2 */, unsigned* counts /* C x B */,
+                               float* ends /* C x B x 2 */, void* stream);
+int nst_level_histogram_style(nst_ctx* ctx, int level, int map, float* lo_hi /* C x 2 */, unsigned* counts /* C x B */, void* stream);
+int nst_histogram_counts(nst_ctx* ctx, const float* f, long long N, int C, int bins, float* lo_hi_out, unsigned* counts_out, void* stream);
+int nst_histogram_tables(nst_ctx* ctx, const float* lo_hi, const unsigned* counts, long long N, const float* s_lo_hi,
+                         const unsigned* s_counts, long long Ns, int C, int bins, float* ends_out, void* stream);
+int nst_histogram_term(nst_ctx* ctx, const float* f, long long N, int C, int bins, const float* lo_hi, const float* ends, float coef,
+                       float* value_out /* nullable */, float* grad_out /* nullable */, void* stream);
 int nst_warp_bilinear(nst_ctx* ctx, const float* src, const float* flow, int C, int h, int w, float* out,
                       float* valid /* nullable */, void* stream);
 int nst_flow_weights(nst_ctx* ctx, const float* fwd, const float* bwd, int h, int w, float* out, void* stream);
