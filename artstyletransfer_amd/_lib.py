@@ -108,6 +108,16 @@ SYMBOLS = {
     "nst_histogram_counts": (C.c_int, [c_void, c_void, C.c_longlong, C.c_int, C.c_int, c_void, c_void, c_void]),
     "nst_histogram_tables": (C.c_int, [c_void, c_void, c_void, C.c_longlong, c_void, c_void, C.c_longlong, C.c_int, C.c_int, c_void, c_void]),
     "nst_histogram_term": (C.c_int, [c_void, c_void, C.c_longlong, C.c_int, C.c_int, c_void, c_void, C.c_float, c_void, c_void, c_void]),
+    "nst_level_set_remd": (C.c_int, [c_void, C.c_int, c_void, C.c_int, C.c_int, c_float_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_double,
+                                     c_void]),
+    "nst_level_remd": (C.c_int, [c_void, C.c_int, c_float_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double),
+                                 C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "nst_job_remd_losses": (C.c_int, [c_void, c_void, c_void]),
+    "nst_level_remd_matches": (C.c_int, [c_void, C.c_int, C.c_int, c_void, c_void, c_void, c_void]),
+    "nst_remd_match": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, c_void,
+                                 c_void, c_void]),
+    "nst_remd_term": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, c_void,
+                                c_void, C.c_int, C.c_float, c_void, c_void, c_void, c_void]),
     "nst_warp_bilinear": (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, c_void, c_void]),
     "nst_flow_weights": (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, c_void, c_void]),
     "nst_anchor_fold": (C.c_int, [c_void, C.c_int, C.POINTER(c_void), C.POINTER(c_void), C.c_int, C.c_int, C.c_int, c_void, c_void,

@@ -444,6 +444,82 @@ int nst_histogram_term(nst_ctx* ctx, const float* f, long long N, int C, int bin
     return sc.finish();
 }
 
+// The relaxed EMD term's pieces on their own (include/nst_hip.h has the definition): the kernels of remd.hip on scratch buffers.
+// Synchronous.
+static int remd_args(nst_ctx* ctx, const float* f, int h, int w, int C, const float* fs, int hs, int ws, int si, int ss, double epsilon,
+                     RemdSide* x, RemdSide* y) {
+    if (!f || !fs) return fail(ctx, NST_E_ARG, "null argument");
+    if (C != 64 && C != 128 && C != 256 && C != 512) return fail(ctx, NST_E_ARG, "the relaxed EMD term takes maps of 64, 128, 256 or 512 channels");
+    if (h < 1 || w < 1 || hs < 1 || ws < 1) return fail(ctx, NST_E_ARG, "the map and the style map must be at least 1x1");
+    if (si < 1 || si > 256 || ss < 1 || ss > 256) return fail(ctx, NST_E_ARG, "the sample strides must be 1..256");
+    if (!(epsilon > 0.0) || std::isinf(epsilon)) return fail(ctx, NST_E_ARG, "the relaxed EMD epsilon must be finite and > 0");
+    *x = RemdSide{}; *y = RemdSide{};
+    if (!remd_side_geometry(h, w, C, si, x) || !remd_side_geometry(hs, ws, C, ss, y)) return fail(ctx, NST_E_ARG, "the map is too large");
+    x->f = f; y->f = fs;
+    return NST_OK;
+}
+
+int nst_remd_match(nst_ctx* ctx, const float* f, int h, int w, int C, const float* fs, int hs, int ws, int si, int ss, double epsilon,
+                   int* nnA_out, int* nnB_out, void* stream) {
+    NSTCHK(bind(ctx));
+    RemdSide x, y;
+    NSTCHK(remd_args(ctx, f, h, w, C, fs, hs, ws, si, ss, epsilon, &x, &y));
+    if (!nnA_out || !nnB_out) return fail(ctx, NST_E_ARG, "null argument");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Scratch sc(ctx, s);
+    RemdSide* sides[2] = {&x, &y};
+    unsigned* amax = nullptr;
+    NSTCHK(sc.alloc(&amax, (size_t)2 * NST_AMAX_SLOTS));
+    HIPCHK(ctx, launch_zero(amax, (size_t)2 * NST_AMAX_SLOTS, s));
+    for (int k = 0; k < 2; ++k) {
+        RemdSide& d = *sides[k];
+        float* r = nullptr; unsigned char* packed = nullptr;
+        NSTCHK(sc.alloc(&r, (size_t)remd_tiles(d.count) * 32));
+        NSTCHK(sc.alloc(&packed, remd_packed_bytes(d.count, C)));
+        HIPCHK(ctx, launch_absmax_slots(d.f, (size_t)d.h * d.w * C, amax + k * NST_AMAX_SLOTS, s));
+        d.amax = amax + k * NST_AMAX_SLOTS;
+        HIPCHK(ctx, launch_remd_norms(d, epsilon, r, s));
+        HIPCHK(ctx, launch_remd_pack(d, packed, s));
+        d.r = r; d.packed = packed;
+    }
+    unsigned long long* keys = nullptr;
+    NSTCHK(sc.alloc(&keys, (size_t)(x.count > y.count ? x.count : y.count)));
+    HIPCHK(ctx, launch_remd_search(y, x, keys, nnA_out, s));
+    HIPCHK(ctx, launch_remd_search(x, y, keys, nnB_out, s));
+    return sc.finish();
+}
+
+int nst_remd_term(nst_ctx* ctx, const float* f, int h, int w, int C, const float* fs, int hs, int ws, int si, int ss, double epsilon,
+                  const int* nnA, const int* nnB, int side, float coef, float* value_out, int* side_out, float* grad_out, void* stream) {
+    NSTCHK(bind(ctx));
+    RemdSide x, y;
+    NSTCHK(remd_args(ctx, f, h, w, C, fs, hs, ws, si, ss, epsilon, &x, &y));
+    if (!nnA || !nnB || (!value_out && !side_out && !grad_out)) return fail(ctx, NST_E_ARG, "null argument");
+    if (side < -1 || side > 1) return fail(ctx, NST_E_ARG, "side must be 0 (A), 1 (B) or -1 (decide)");
+    if (!std::isfinite(coef)) return fail(ctx, NST_E_ARG, "the coefficient must be finite");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Scratch sc(ctx, s);
+    float* rp = nullptr; float* rq = nullptr; float* cosA = nullptr; float* cosB = nullptr; float* rec = nullptr; int* sd = nullptr;
+    double* partial = nullptr;
+    NSTCHK(sc.alloc(&rp, (size_t)remd_tiles(x.count) * 32));
+    NSTCHK(sc.alloc(&rq, (size_t)remd_tiles(y.count) * 32));
+    NSTCHK(sc.alloc(&cosA, (size_t)x.count));
+    NSTCHK(sc.alloc(&cosB, (size_t)y.count));
+    NSTCHK(sc.alloc(&rec, 4));
+    NSTCHK(sc.alloc(&sd, 4));
+    NSTCHK(sc.alloc(&partial, (size_t)2 * REMD_VALUE_BLOCKS));
+    HIPCHK(ctx, launch_remd_norms(x, epsilon, rp, s));
+    HIPCHK(ctx, launch_remd_norms(y, epsilon, rq, s));
+    x.r = rp; y.r = rq;
+    const RemdTerm t{x, y, nnA, nnB, cosA, cosB, rec, sd};
+    HIPCHK(ctx, launch_remd_value(t, epsilon, side, partial, nullptr, s));
+    if (value_out) HIPCHK(ctx, hipMemcpyAsync(value_out, rec, 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (side_out) HIPCHK(ctx, hipMemcpyAsync(side_out, sd, sizeof(int), hipMemcpyDeviceToDevice, s));
+    if (grad_out)
+        HIPCHK(ctx, launch_remd_grad(t, (float)((double)coef / (double)x.count), (float)((double)coef / (double)y.count), grad_out, 0, s));
+    return sc.finish();
+}
+
 // The warp of a sequence (include/nst_hip.h): out = src sampled bilinearly at p + flow(p), valid (nullable) = the four taps
 // lie inside the image.  Synchronous.
 int nst_warp_bilinear(nst_ctx* ctx, const float* src, const float* flow, int C, int h, int w, float* out, float* valid, void* stream) {

@@ -343,6 +343,61 @@ bool hist_layer(const LevelWs& L, int m) {
     return i >= 0 && L.hist.w[i] > 0.f;
 }
 
+// ---- the relaxed EMD term (include/nst_hip.h has the definition; kernels: remd.hip) ---------------------------------------
+// map index i of level L: the term's operands on the level's own map (the image side: f, the sample grid, the absmax record of
+// the map, rp and the packed operand of this closure), and the coefficients (float)(w / n) and (float)(w / m) formed in double
+RemdSide remd_image_side(const LevelWs& L, int i) {
+    const int l = kTapLayer[i];
+    RemdSide x{};
+    remd_side_geometry(L.acts.h[l], L.acts.w[l], kCout[l], L.remd.si[i], &x);
+    x.f = L.acts.act[l]; x.amax = amax_act(L.acts, l); x.r = L.remd.rp[i]; x.packed = L.remd.xpacked[i];
+    return x;
+}
+RemdTerm remd_term_of(const LevelWs& L, int i) {
+    const RemdLevel& g = L.remd;
+    return RemdTerm{remd_image_side(L, i), g.y[i], g.nnA[i], g.nnB[i], g.cosA[i], g.cosB[i], g.rec[i], g.side[i]};
+}
+float remd_coef(float w, int count) { return (float)((double)w / (double)count); }
+// forward part of level L, once its maps exist: per map with a weight the image side's norms and packed operand, the two
+// searches, the cosines, remd_i and the side (a level without the term: no launch)
+int remd_forward(nst_ctx* ctx, LevelWs& L, hipStream_t s) {
+    for (int i = 0; i < 6 && L.remd.on(); ++i) {
+        if (!(L.remd.w[i] > 0.f)) continue;
+        const RemdTerm t = remd_term_of(L, i);
+        {
+            Timer tm(ctx, s, K_OTHER, 0);
+            HIPCHK(ctx, launch_remd_norms(t.x, L.remd.eps, L.remd.rp[i], s));
+            HIPCHK(ctx, launch_remd_pack(t.x, L.remd.xpacked[i], s));
+        }
+        // two launches of n x m x C (three MFMAs per product block each), timed as "n x 1, cin C, cout m", layer tag 200 + map
+        // for direction A (the style is the dictionary) and 210 + map for direction B (the image is)
+        const double flops = 2.0 * (double)t.x.count * (double)t.y.count * (double)t.x.C;
+        {
+            Timer tm(ctx, s, K_OTHER, flops, t.x.count, 1, t.x.C, t.y.count, 1, 200 + i);
+            HIPCHK(ctx, launch_remd_search(t.y, t.x, L.remd.keysA[i], L.remd.nnA[i], s));
+        }
+        {
+            Timer tm(ctx, s, K_OTHER, flops, t.x.count, 1, t.x.C, t.y.count, 1, 210 + i);
+            HIPCHK(ctx, launch_remd_search(t.x, t.y, L.remd.keysB[i], L.remd.nnB[i], s));
+        }
+        Timer tm(ctx, s, K_OTHER, 0);
+        HIPCHK(ctx, launch_remd_value(t, L.remd.eps, -1, L.remd.partial[i], L.remd.vals + i, s));
+    }
+    return NST_OK;
+}
+// gradient part of map index i: into dst (the map's shape), written or added to what is there
+int remd_backward(nst_ctx* ctx, LevelWs& L, int i, float* dst, int accumulate, hipStream_t s) {
+    Timer tm(ctx, s, K_OTHER, 0);
+    const RemdTerm t = remd_term_of(L, i);
+    HIPCHK(ctx, launch_remd_grad(t, remd_coef(L.remd.w[i], t.x.count), remd_coef(L.remd.w[i], t.y.count), dst, accumulate, s));
+    return NST_OK;
+}
+// conv layer m of level L carries the term
+bool remd_layer(const LevelWs& L, int m) {
+    const int i = tap_index_of(m);
+    return i >= 0 && L.remd.w[i] > 0.f;
+}
+
 // ---- the moment loss (include/nst_hip.h has the definition; kernels: moments.hip) ----------------------------------------
 // style slot q of level L on its map f (N pixels, C channels): the statistics item, and the fold item that follows the Gram
 // finish pass and the row bias of a shifted Gram (r0: that bias, or nullptr)
@@ -436,6 +491,12 @@ int backward(nst_ctx* ctx, ActSet& a, const Inject* inj, const ContentJob* cj, f
             Timer t(ctx, s, K_OTHER, 0);
             HIPCHK(ctx, launch_hist_grad(*inj[l].hist, inj[l].hist_coef, oth, (content || mrf) ? 1 : 0, s));
         }
+        // the relaxed EMD term of the top map, after all three
+        const bool remd = inj[l].remd && inj[l].S;
+        if (remd) {
+            Timer t(ctx, s, K_OTHER, 0);
+            HIPCHK(ctx, launch_remd_grad(*inj[l].remd, inj[l].remd_coefA, inj[l].remd_coefB, oth, (content || mrf || hist) ? 1 : 0, s));
+        }
         if (inj[l].guided) {
             GuidedBwd gb = *inj[l].guided;
             gb.addend = content ? oth : nullptr; gb.out = cur; gb.mask = top_mask ? a.act[l] : nullptr;
@@ -444,7 +505,7 @@ int backward(nst_ctx* ctx, ActSet& a, const Inject* inj, const ContentJob* cj, f
             // (the content gradient, if any, as the addend of the 1x1 Gram launch)
             ConvParams p{};
             p.in = a.act[l]; p.wt = inj[l].S; p.out = cur; p.mask = top_mask ? a.act[l] : nullptr;
-            p.addend = (content || mrf || hist) ? oth : nullptr;
+            p.addend = (content || mrf || hist || remd) ? oth : nullptr;
             p.bias = inj[l].bias;                  // (a shifted Gram: F S + r, then the addend and the mask)
             p.H = a.h[l]; p.W = a.w[l]; p.Cin = kCout[l]; p.Cout = kCout[l];
             Timer t(ctx, s, K_GRAM, conv_flops(p.H, p.W, p.Cin, p.Cout, 1));
@@ -510,6 +571,12 @@ int backward(nst_ctx* ctx, ActSet& a, const Inject* inj, const ContentJob* cj, f
                 // the histogram loss of the map: written, or added to the content gradient and the MRF term's
                 Timer t(ctx, s, K_OTHER, 0);
                 HIPCHK(ctx, launch_hist_grad(*in.hist, in.hist_coef, oth, p.addend == oth ? 1 : 0, s));
+                p.addend = oth;
+            }
+            if (in.remd) {
+                // the relaxed EMD term of the map: written, or added to the gradients before it
+                Timer t(ctx, s, K_OTHER, 0);
+                HIPCHK(ctx, launch_remd_grad(*in.remd, in.remd_coefA, in.remd_coefB, oth, p.addend == oth ? 1 : 0, s));
                 p.addend = oth;
             }
             if (in.guided) {
@@ -885,6 +952,10 @@ int batched_backward(nst_ctx* ctx, const float* const* xi, float* const* gi, con
             NSTCHK(hist_backward(ctx, L, tap_index_of(top), oth[k], top_add[k] ? 1 : 0, s));
             top_add[k] = true;
         }
+        if (top_q >= 0 && remd_layer(L, top)) {      // (the relaxed EMD term, nst_level_set_remd, after all three)
+            NSTCHK(remd_backward(ctx, L, tap_index_of(top), oth[k], top_add[k] ? 1 : 0, s));
+            top_add[k] = true;
+        }
     }
     const bool guided = guided_levels(ctx, lv, n);
     if (guided && top_q >= 0) {
@@ -1002,6 +1073,11 @@ int batched_backward(nst_ctx* ctx, const float* const* xi, float* const* gi, con
                 NSTCHK(hist_backward(ctx, L, tap_index_of(m), oth[k], im.addend == oth[k] ? 1 : 0, s));
                 im.addend = oth[k];
             }
+            if (remd_layer(L, m)) {
+                // the relaxed EMD term of the map, after the gradients before it where the map has those
+                NSTCHK(remd_backward(ctx, L, tap_index_of(m), oth[k], im.addend == oth[k] ? 1 : 0, s));
+                im.addend = oth[k];
+            }
             im.bits_in = a.bits[m];
         }
         {
@@ -1069,6 +1145,7 @@ int closure_batched_forward(nst_ctx* ctx, const float* const* xi, unsigned level
     if (overlap) HIPCHK(ctx, hipStreamWaitEvent(s, ctx->side_join, 0));
     for (int k = 0; k < n; ++k) NSTCHK(patch_forward(ctx, ctx->lv[lv[k]], s));       // (nst_level_set_patches: the maps exist)
     for (int k = 0; k < n; ++k) NSTCHK(hist_forward(ctx, ctx->lv[lv[k]], s));        // (nst_level_set_histograms likewise)
+    for (int k = 0; k < n; ++k) NSTCHK(remd_forward(ctx, ctx->lv[lv[k]], s));        // (nst_level_set_remd likewise)
     if (loss_terms && ctx->forward_pack && ctx->conv_mode == 2 && !ctx->use_graph && n > 1) {
         // one launch each for all levels; every level keeps its partial buffers and block decomposition
         MseBatch mb{};
@@ -1191,6 +1268,16 @@ int closure_per_level(nst_ctx* ctx, const float* const* xi, float* const* gi, in
         inj[kTapLayer[i]].hist = &hterm[i];
         inj[kTapLayer[i]].hist_coef = hist_coef(L.hist.w[i], hist_denom(L, i));
     }
+    // the relaxed EMD term (nst_level_set_remd): matches, values and sides now, the gradients as addends of the walk
+    NSTCHK(remd_forward(ctx, L, s));
+    RemdTerm rterm[6];
+    for (int i = 0; i < 6 && L.remd.on(); ++i) {
+        if (!(L.remd.w[i] > 0.f)) continue;
+        rterm[i] = remd_term_of(L, i);
+        inj[kTapLayer[i]].remd = &rterm[i];
+        inj[kTapLayer[i]].remd_coefA = remd_coef(L.remd.w[i], rterm[i].x.count);
+        inj[kTapLayer[i]].remd_coefB = remd_coef(L.remd.w[i], rterm[i].y.count);
+    }
     ContentJob cj{L.content_t, L.content_n, content_coef(cw, (double)L.content_n), L.content_partial};
     NSTCHK(backward(ctx, L.acts, inj, &cj, L.gbuf[0], L.gbuf[1], gi[level], L.h, L.w, s, tp.top, tp.top_mask(), ctx->channels));
     {
@@ -1243,6 +1330,12 @@ LossAssembly fill_loss_assembly(const nst_ctx* ctx, unsigned level_mask, float c
         if (!L.hist.on()) continue;
         la.lv[i].hist_vals = L.hist.vals;
         for (int k = 0; k < 6; ++k) la.lv[i].hist_w[k] = L.hist.w[k];
+    }
+    for (int i = 0; i < ctx->levels; ++i) {      // (the relaxed EMD term, a level's own in the same way)
+        const LevelWs& L = ctx->lv[i];
+        if (!L.remd.on()) continue;
+        la.lv[i].remd_vals = L.remd.vals;
+        for (int k = 0; k < 6; ++k) la.lv[i].remd_w[k] = L.remd.w[k];
     }
     return la;
 }
@@ -1421,6 +1514,8 @@ int window_check(nst_ctx* ctx, const float* xs, int row0, int rows, int H0) {
         return fail(ctx, NST_E_STATE, "the stripe closure implements no MRF term (nst_level_set_patches(ctx, 0, NULL, ...) clears it)");
     if (L.hist.on())
         return fail(ctx, NST_E_STATE, "the stripe closure implements no histogram loss (nst_level_set_histograms(ctx, 0, NULL, ...) clears it)");
+    if (L.remd.on())
+        return fail(ctx, NST_E_STATE, "the stripe closure implements no relaxed EMD term (nst_level_set_remd(ctx, 0, NULL, ...) clears it)");
     if (L.guide.R > 0)
         return fail(ctx, NST_E_STATE, "the stripe closure implements no spatial control (nst_level_set_guidance(ctx, 0, 0, ...) clears it)");
     if (!L.targets) return fail(ctx, NST_E_STATE, "targets of the stripe not set");
@@ -1569,6 +1664,7 @@ int nst_level_set_guidance(nst_ctx* ctx, int level, int R, const float* planes, 
     if (ctx->mom_on()) return fail(ctx, NST_E_STATE, "guided levels take no moment loss (nst_job_set_moments with zeros switches it off)");
     if (L.pm.on()) return fail(ctx, NST_E_STATE, "a level with the MRF term takes no guidance (nst_level_set_patches(ctx, level, NULL, ...) clears the term)");
     if (L.hist.on()) return fail(ctx, NST_E_STATE, "a level with the histogram loss takes no guidance (nst_level_set_histograms(ctx, level, NULL, ...) clears the term)");
+    if (L.remd.on()) return fail(ctx, NST_E_STATE, "a level with the relaxed EMD term takes no guidance (nst_level_set_remd(ctx, level, NULL, ...) clears the term)");
     if (!planes) return fail(ctx, NST_E_ARG, "null argument");
     float lam[NST_MAX_REGIONS] = {1.f, 1.f, 1.f, 1.f};
     bool positive = lambda == nullptr;

@@ -479,6 +479,7 @@ int nst_ctx_create_ex(int device, const float* const* weights, const float* cons
     if (e == hipSuccess) e = gram_init_device();
     if (e == hipSuccess) e = pm_init_device();
     if (e == hipSuccess) e = hist_init_device();
+    if (e == hipSuccess) e = remd_init_device();
     // options: an explicit argument wins; -1 falls back to the environment (read here, once), then to the default
     if (opts.conv_mode >= 0) {
         if (opts.conv_mode > NST_CONV_F16X2) { ctx->err = "nst_options.conv_mode must be NST_CONV_F32, NST_CONV_BF16X3 or NST_CONV_F16X2"; return bail(NST_E_ARG); }
@@ -684,6 +685,7 @@ int nst_job_set_taps(nst_ctx* ctx, int content_index, unsigned style_mask, int u
         L.guide = Guidance();           // (sized for the old style set: nst_level_set_guidance again)
         L.pm = PatchLevel();            // (the style's maps of the old taps: nst_level_set_patches again)
         L.hist = HistLevel();           // (likewise: nst_level_set_histograms again)
+        L.remd = RemdLevel();           // (likewise: nst_level_set_remd again)
         free_tap_buffers(L);
         NSTCHK(alloc_tap_buffers(ctx, L));
     }
@@ -709,6 +711,7 @@ int nst_job_set_color(nst_ctx* ctx, int mode) {
     // the MRF term holds maps of the style image as the other mode's network saw it (nst_level_set_patches): dropped
     for (int i = 0; i < ctx->levels; ++i) ctx->lv[i].pm = PatchLevel();
     for (int i = 0; i < ctx->levels; ++i) ctx->lv[i].hist = HistLevel();     // (the histogram loss's style record likewise)
+    for (int i = 0; i < ctx->levels; ++i) ctx->lv[i].remd = RemdLevel();     // (and the relaxed EMD term's style maps)
     ctx->channels = channels;
     return NST_OK;
 }
@@ -725,6 +728,7 @@ int nst_job_set_pooling(nst_ctx* ctx, int mode) {
     drop_closure_state(ctx, true);
     for (int i = 0; i < ctx->levels; ++i) ctx->lv[i].pm = PatchLevel();      // (the MRF term's maps are the other network's)
     for (int i = 0; i < ctx->levels; ++i) ctx->lv[i].hist = HistLevel();     // (and the histogram loss's style record)
+    for (int i = 0; i < ctx->levels; ++i) ctx->lv[i].remd = RemdLevel();     // (and the relaxed EMD term's style maps)
     ctx->pool_avg = mode == NST_POOL_AVG ? 1 : 0;
     return NST_OK;
 }
@@ -1307,6 +1311,144 @@ int nst_level_histogram_tables(nst_ctx* ctx, int level, int map, float* lo_hi, u
 }
 int nst_level_histogram_style(nst_ctx* ctx, int level, int map, float* lo_hi, unsigned* counts, void* stream) {
     return hist_read(ctx, level, map, true, lo_hi, counts, nullptr, stream);
+}
+
+// The relaxed EMD term of one level (Kolkin et al. 2019; include/nst_hip.h has the definition): the style's weighted maps with
+// their norms and packed operands, and every buffer the image side needs in a closure.  Life cycle of nst_level_set_patches:
+// everything is made here beside what the level has (a refusal changes nothing), the context's work is waited for before the
+// level's block is replaced, and the captured closure, an optimiser's remembered closure and a pending backward half go.  The
+// targets stay.
+int nst_level_set_remd(nst_ctx* ctx, int level, const float* style, int hs, int ws, const float* weights, const int* image_stride,
+                       const int* style_stride, double epsilon, void* stream) {
+    if (ctx) { ++ctx->closure_epoch; ++ctx->ws_seq; }
+    NSTCHK(bind(ctx));
+    if (ctx->levels < 1) return fail(ctx, NST_E_STATE, "nst_job_configure has not been called");
+    if (level < 0 || level >= ctx->levels) return fail(ctx, NST_E_ARG, "level out of range");
+    LevelWs& L = ctx->lv[level];
+    RemdLevel g;
+    bool on = false;
+    if (style) {
+        if (!weights || !image_stride || !style_stride) return fail(ctx, NST_E_ARG, "null argument");
+        for (int i = 0; i < 6; ++i) {
+            if (!(weights[i] >= 0.f) || std::isinf(weights[i])) return fail(ctx, NST_E_ARG, "the relaxed EMD weights must be finite and >= 0");
+            if (image_stride[i] < 1 || image_stride[i] > 256 || style_stride[i] < 1 || style_stride[i] > 256)
+                return fail(ctx, NST_E_ARG, "the sample strides must be 1..256");
+            g.w[i] = weights[i]; g.si[i] = image_stride[i]; g.ss[i] = style_stride[i];
+            on = on || weights[i] > 0.f;
+        }
+        if (!(epsilon > 0.0) || std::isinf(epsilon)) return fail(ctx, NST_E_ARG, "the relaxed EMD epsilon must be finite and > 0");
+    }
+    hipStream_t s = enter(ctx, stream);
+    if (on) {
+        if (ctx->conv_mode != 2) return fail(ctx, NST_E_STATE, "the relaxed EMD term runs in the f16x2 arithmetic only (NST_CONV unset)");
+        if (ctx->use_graph) return fail(ctx, NST_E_STATE, "the relaxed EMD term's launches are not captured: a context with use_graph takes no term");
+        if (L.guide.R > 0) return fail(ctx, NST_E_STATE, "a guided level takes no relaxed EMD term (nst_level_set_guidance(ctx, level, 0, ...) clears the guidance)");
+        if (hs < 16 || ws < 16) return fail(ctx, NST_E_ARG, "style image must be at least 16x16");
+        const unsigned style_mask = style_mask_of(ctx->taps);
+        int deepest = -1;
+        for (int i = 0; i < 6; ++i) {
+            if (!(g.w[i] > 0.f)) continue;
+            if (!((style_mask >> i) & 1u)) return fail(ctx, NST_E_ARG, "a positive relaxed EMD weight on a map that is not a style map of the job");
+            deepest = kTapLayer[i];
+        }
+        g.eps = epsilon; g.hs = hs; g.ws = ws;
+        Scratch sc(ctx, s);
+        NSTCHK(alloc_acts(ctx, sc.acts, hs, ws));
+        NSTCHK(forward(ctx, sc.acts, style, hs, ws, s, deepest, ctx->channels));
+        NSTCHK(g.mem.alloc(ctx, &g.vals, 6));
+        HIPCHK(ctx, hipMemsetAsync(g.vals, 0, 6 * sizeof(float), s));
+        for (int i = 0; i < 6; ++i) {
+            if (!(g.w[i] > 0.f)) continue;
+            const int l = kTapLayer[i], C = kCout[l], mh = sc.acts.h[l], mw = sc.acts.w[l];
+            RemdSide& y = g.y[i];
+            RemdSide x{};
+            if (!remd_side_geometry(mh, mw, C, g.ss[i], &y) || !remd_side_geometry(L.acts.h[l], L.acts.w[l], C, g.si[i], &x))
+                return fail(ctx, NST_E_ARG, "a weighted map or its style map is too large");
+            const int n = x.count, m = y.count;
+            g.n[i] = n;
+            float* fs = nullptr; unsigned* amax = nullptr; float* rq = nullptr; unsigned char* packed = nullptr;
+            const size_t fs_n = (size_t)mh * mw * C;
+            NSTCHK(g.mem.alloc(ctx, &fs, fs_n));
+            NSTCHK(g.mem.alloc(ctx, &amax, (size_t)NST_AMAX_SLOTS));
+            NSTCHK(g.mem.alloc(ctx, &rq, (size_t)remd_tiles(m) * 32));
+            NSTCHK(g.mem.alloc(ctx, &packed, remd_packed_bytes(m, C)));
+            NSTCHK(g.mem.alloc(ctx, &g.rp[i], (size_t)remd_tiles(n) * 32));
+            NSTCHK(g.mem.alloc(ctx, &g.xpacked[i], remd_packed_bytes(n, C)));
+            NSTCHK(g.mem.alloc(ctx, &g.keysA[i], (size_t)n));
+            NSTCHK(g.mem.alloc(ctx, &g.keysB[i], (size_t)m));
+            NSTCHK(g.mem.alloc(ctx, &g.nnA[i], (size_t)n));
+            NSTCHK(g.mem.alloc(ctx, &g.nnB[i], (size_t)m));
+            NSTCHK(g.mem.alloc(ctx, &g.cosA[i], (size_t)n));
+            NSTCHK(g.mem.alloc(ctx, &g.cosB[i], (size_t)m));
+            NSTCHK(g.mem.alloc(ctx, &g.partial[i], (size_t)2 * REMD_VALUE_BLOCKS));
+            NSTCHK(g.mem.alloc(ctx, &g.rec[i], 3));
+            NSTCHK(g.mem.alloc(ctx, &g.side[i], 1));
+            HIPCHK(ctx, hipMemcpyAsync(fs, sc.acts.act[l], fs_n * sizeof(float), hipMemcpyDeviceToDevice, s));
+            HIPCHK(ctx, hipMemsetAsync(g.nnA[i], 0, (size_t)n * sizeof(int), s));
+            HIPCHK(ctx, hipMemsetAsync(g.nnB[i], 0, (size_t)m * sizeof(int), s));
+            HIPCHK(ctx, hipMemsetAsync(g.rec[i], 0, 3 * sizeof(float), s));
+            HIPCHK(ctx, hipMemsetAsync(g.side[i], 0, sizeof(int), s));
+            y.f = fs;
+            HIPCHK(ctx, launch_zero(amax, NST_AMAX_SLOTS, s));
+            HIPCHK(ctx, launch_absmax_slots(fs, fs_n, amax, s));
+            y.amax = amax;
+            HIPCHK(ctx, launch_remd_norms(y, epsilon, rq, s));
+            HIPCHK(ctx, launch_remd_pack(y, packed, s));
+            y.r = rq; y.packed = packed;
+        }
+        NSTCHK(sc.finish());       // (synchronises: the caller's image is free again when this returns)
+    } else {
+        g = RemdLevel();
+    }
+    quiesce(ctx);
+    drop_closure_state(ctx, false);
+    L.remd = std::move(g);
+    return NST_OK;
+}
+
+int nst_level_remd(const nst_ctx* ctx, int level, float* weights, int* image_stride, int* style_stride, double* epsilon, int* hs, int* ws) {
+    if (!ctx) return fail(nullptr, NST_E_ARG, "null context");
+    if (level < 0 || level >= ctx->levels) return fail(nullptr, NST_E_ARG, "level out of range");
+    const RemdLevel& g = ctx->lv[level].remd;
+    for (int i = 0; i < 6 && weights; ++i) weights[i] = g.w[i];
+    for (int i = 0; i < 6 && image_stride; ++i) image_stride[i] = g.si[i];
+    for (int i = 0; i < 6 && style_stride; ++i) style_stride[i] = g.ss[i];
+    if (epsilon) *epsilon = g.eps;
+    if (hs) *hs = g.hs;
+    if (ws) *ws = g.ws;
+    return NST_OK;
+}
+
+// the unweighted remd_i of the last closure, levels x 6 by map index (zeros: levels without the term or outside the last level
+// mask, maps without a weight, no closure yet)
+int nst_job_remd_losses(nst_ctx* ctx, float* out, void* stream) {
+    NSTCHK(bind(ctx));
+    if (ctx->levels < 1) return fail(ctx, NST_E_STATE, "nst_job_configure has not been called");
+    if (!out) return fail(ctx, NST_E_ARG, "null argument");
+    hipStream_t s = enter(ctx, stream);
+    for (int i = 0; i < ctx->levels; ++i) {
+        const RemdLevel& g = ctx->lv[i].remd;
+        if (g.on()) HIPCHK(ctx, hipMemcpyAsync(out + 6 * i, g.vals, 6 * sizeof(float), hipMemcpyDeviceToDevice, s));
+        else HIPCHK(ctx, hipMemsetAsync(out + 6 * i, 0, 6 * sizeof(float), s));
+    }
+    mark(ctx, s);
+    return NST_OK;
+}
+
+// the matches and the side of the last closure of one weighted map of a level (nnA: n int32, nnB: m int32, side: one int32;
+// zeros before any closure; each nullable)
+int nst_level_remd_matches(nst_ctx* ctx, int level, int map, int* nnA_out, int* nnB_out, int* side_out, void* stream) {
+    NSTCHK(bind(ctx));
+    if (level < 0 || level >= ctx->levels) return fail(ctx, NST_E_ARG, "level out of range");
+    if (map < 0 || map > 5 || (!nnA_out && !nnB_out && !side_out)) return fail(ctx, NST_E_ARG, "bad argument");
+    const RemdLevel& g = ctx->lv[level].remd;
+    if (!(g.w[map] > 0.f)) return fail(ctx, NST_E_STATE, "the map carries no relaxed EMD term on this level (nst_level_set_remd)");
+    hipStream_t s = enter(ctx, stream);
+    if (nnA_out) HIPCHK(ctx, hipMemcpyAsync(nnA_out, g.nnA[map], (size_t)g.n[map] * sizeof(int), hipMemcpyDeviceToDevice, s));
+    if (nnB_out) HIPCHK(ctx, hipMemcpyAsync(nnB_out, g.nnB[map], (size_t)g.y[map].count * sizeof(int), hipMemcpyDeviceToDevice, s));
+    if (side_out) HIPCHK(ctx, hipMemcpyAsync(side_out, g.side[map], sizeof(int), hipMemcpyDeviceToDevice, s));
+    mark(ctx, s);
+    return NST_OK;
 }
 
 // The semantic guidance of a level's MRF term (neural-doodle; include/nst_hip.h has the definition).  The planes of both sides

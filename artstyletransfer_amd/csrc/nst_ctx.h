@@ -260,6 +260,38 @@ struct HistLevel {
     }
 };
 
+// The relaxed EMD term of one level (nst_level_set_remd; include/nst_hip.h has the definition), by map index: the weight (0: the
+// map has no term) and the stride pair; the style side y[i] (the style's map, its absmax record, rq and the packed operand, all
+// made by the setter); the image side's buffers, which the forward half fills every closure (rp and the packed operand; f, the
+// size and the absmax record are the level's own map's); the keys of both directions, nnA, nnB, the stored cosines, the value
+// partials, (remd, rA, rB) and the side flag; and the unweighted remd_i (six floats, which the forward half writes and the loss
+// rows read).  Data of one job with PatchLevel's life cycle: everything is made by the setter, a closure allocates nothing.
+struct RemdLevel {
+    float w[6] = {};
+    int si[6] = {1, 1, 1, 1, 1, 1}, ss[6] = {1, 1, 1, 1, 1, 1};
+    double eps = 1e-5;
+    int hs = 0, ws = 0;         // the style image of nst_level_set_remd
+    RemdSide y[6] = {};
+    int n[6] = {};              // image samples of the map
+    float* rp[6] = {};
+    unsigned char* xpacked[6] = {};
+    unsigned long long* keysA[6] = {};
+    unsigned long long* keysB[6] = {};
+    int* nnA[6] = {};
+    int* nnB[6] = {};
+    float* cosA[6] = {};
+    float* cosB[6] = {};
+    double* partial[6] = {};    // 2 REMD_VALUE_BLOCKS each
+    float* rec[6] = {};         // (remd, rA, rB)
+    int* side[6] = {};
+    float* vals = nullptr;
+    DevMem mem;
+    bool on() const {
+        for (float v : w) if (v > 0.f) return true;
+        return false;
+    }
+};
+
 // the level image and its gradient (levels >= 1), planar: channels (nst_job_set_color) x h x w floats each
 struct LevelImage {
     float* xl = nullptr;
@@ -277,6 +309,7 @@ struct LevelWs {
     AnchorLevel anc;
     PatchLevel pm;
     HistLevel hist;
+    RemdLevel remd;
     ActSet acts;
     float* gbuf[2] = {};
     size_t gbuf_floats = 0;
@@ -406,7 +439,7 @@ struct nst_ctx {
         if (mom_on() && mom_slot(q)) return L.mom.row_bias(q);
         return gs_on() ? L.gs.row_bias(q) : nullptr;
     }
-    // bumped on entry to every call that changes what a closure computes (configure, taps, colour, pooling, style weights, Laplacian, matting, Gram shift, moments, targets, a level's anchor, a level's MRF term, a level's histogram loss), failure paths
+    // bumped on entry to every call that changes what a closure computes (configure, taps, colour, pooling, style weights, Laplacian, matting, Gram shift, moments, targets, a level's anchor, a level's MRF term, a level's histogram loss, a level's relaxed EMD term), failure paths
     // included: an optimiser's remembered closure result is valid only under the epoch it was made in (nst_opt.cpp)
     unsigned long long closure_epoch = 0;
     // advanced on entry to every call that reads or writes the level workspaces (nst_closure*, nst_window_*,
@@ -536,6 +569,8 @@ struct Inject {
     float mrf_coef = 0.f;
     const HistTerm* hist = nullptr;  // the histogram loss of the map (nst_level_set_histograms): likewise, after the MRF term
     float hist_coef = 0.f;
+    const RemdTerm* remd = nullptr;  // the relaxed EMD term of the map (nst_level_set_remd): likewise, after the histogram loss
+    float remd_coefA = 0.f, remd_coefB = 0.f;
 };
 struct ContentJob { const float* target; size_t n; float coef; double* partial; };
 // channels = 1: x is a luminance plane u, conv1_1 sees x_c = u - mean_c (nst_job_set_color)

@@ -381,6 +381,9 @@ struct LevelLossInputs {
     // histogram loss (nst_level_set_histograms), a level's own, in the same form: the six unweighted hist_i and the weights
     float* hist_vals;
     float hist_w[6];
+    // relaxed EMD term (nst_level_set_remd), a level's own, in the same form: the six unweighted remd_i and the weights
+    float* remd_vals;
+    float remd_w[6];
 };
 struct LossAssembly {
     LevelLossInputs lv[8];
@@ -568,6 +571,42 @@ struct HistTerm { const float* f; size_t N; int C, bins; const float* lo_hi; con
 hipError_t launch_hist_value_partials(const HistTerm& t, double* partial, hipStream_t stream);
 hipError_t launch_hist_value(const double* partial, double denom, float* out, hipStream_t stream);
 hipError_t launch_hist_grad(const HistTerm& t, float coef, float* out, int accumulate, hipStream_t stream);
+
+// remd.hip: the relaxed EMD term (include/nst_hip.h has the definition) ------------------------------------------------------
+// One side of the term: the samples of f (NHWC, h x w x C) on the stride grid, sample k = pixel ((k / nb) stride, (k % nb) stride),
+// count = na nb of them.  remd_side_geometry fills the integers (false: an empty map, a stride outside 1..256, a C other than
+// 64 / 128 / 256 / 512, h w C >= 2^31).  amax: the absmax record of f; r: 32 remd_tiles(count) floats, the reciprocal norms
+// (launch_remd_norms; zeros behind the last sample); packed: remd_packed_bytes(count, C) bytes, both fp16 pieces of every sample
+// in the lane order of the search kernel's row operand (launch_remd_pack) - only a side that is searched as a dictionary needs it.
+struct RemdSide {
+    const float* f; int h, w, C, stride, na, nb, count;
+    const unsigned* amax; const float* r; const void* packed;
+};
+hipError_t remd_init_device();   // raises the dynamic-LDS limit of the search kernels: once per device, before the first launch there
+__host__ __device__ inline int remd_tiles(int count) { return (count + 31) / 32; }
+size_t remd_packed_bytes(int count, int C);
+bool remd_side_geometry(int h, int w, int C, int stride, RemdSide* s);
+hipError_t launch_remd_norms(const RemdSide& s, double epsilon, float* r, hipStream_t stream);
+hipError_t launch_remd_pack(const RemdSide& s, void* packed, hipStream_t stream);      // reads s.amax
+// One direction of the search: for every sample of `cols` the lowest index among its best samples of `dict` (dict: amax, r and
+// packed; cols: amax and r).  keys: cols.count 64-bit words, which the launch clears and the kernel raises by atomicMax; nn:
+// cols.count int32, what the keys decode to.
+hipError_t launch_remd_search(const RemdSide& dict, const RemdSide& cols, unsigned long long* keys, int* nn, hipStream_t stream);
+// Value and gradient at fixed matches (x: the image side, y: the style side; f, the integers and r of both are read; matches
+// outside their range are clamped).  The value in two ordered stages: 2 REMD_VALUE_BLOCKS double partials of sum_i a_i and
+// sum_j b_j (the first stage also stores the cosines), then rec = (remd, rA, rB) and *side = 0 (A) or 1 (B); force = 0 / 1 takes
+// that side whatever the values (remd is then its r), -1 decides; val (nullable) also receives remd.  The gradient in gather
+// form, a wave per image sample, reading *side on the device: out (the image map's shape) gets coefA d(i, nnA(i)) or coefB
+// sum_j d(i, j) at the sampled pixels - written, everything else zero, or (accumulate) added.
+constexpr int REMD_VALUE_BLOCKS = 256;
+struct RemdTerm {
+    RemdSide x, y;
+    const int* nnA; const int* nnB;      // x.count and y.count entries
+    float* cosA; float* cosB;            // likewise: (float)a_i and (float)b_j
+    float* rec; int* side;               // 3 floats and 1 int
+};
+hipError_t launch_remd_value(const RemdTerm& t, double epsilon, int force, double* partial, float* val, hipStream_t stream);
+hipError_t launch_remd_grad(const RemdTerm& t, float coefA, float coefB, float* out, int accumulate, hipStream_t stream);
 
 // gram_guided.hip: spatial control (guided Gram matrices; include/nst_hip.h has the definitions) ---------------------
 constexpr int NST_MAX_REGIONS_K = 4;

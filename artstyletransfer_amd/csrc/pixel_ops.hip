@@ -655,6 +655,7 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(LossAssembly la) {
         if (in.tmp_gamma > 0.f && threadIdx.x == 0) in.tmp_out[0] = 0.f;
         if (in.mrf_vals && threadIdx.x < 6) in.mrf_vals[threadIdx.x] = 0.f;
         if (in.hist_vals && threadIdx.x < 6) in.hist_vals[threadIdx.x] = 0.f;
+        if (in.remd_vals && threadIdx.x < 6) in.remd_vals[threadIdx.x] = 0.f;
         return;
     }
     double v[7];
@@ -778,6 +779,11 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(LossAssembly la) {
             // (... + sum_i w_i mrf_i) + sum_i w_i hist_i, likewise
             for (int i = 0; i < 6; ++i)
                 if (in.hist_w[i] > 0.f) total = total + in.hist_w[i] * in.hist_vals[i];
+        }
+        if (in.remd_vals) {
+            // (... + sum_i w_i hist_i) + sum_i w_i remd_i, likewise
+            for (int i = 0; i < 6; ++i)
+                if (in.remd_w[i] > 0.f) total = total + in.remd_w[i] * in.remd_vals[i];
         }
         la.out[4 * l + 0] = total;
         la.out[4 * l + 1] = content;

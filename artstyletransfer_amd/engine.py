@@ -20,6 +20,7 @@ from . import matting_modes as _mat
 from . import flow_modes as _flow
 from . import mrf_modes as _mrf
 from . import hist_modes as _hist
+from . import remd_modes as _remd
 from ._lib import NST_LOSS_ROW, NstError, StepInfo
 
 TAP_CHANNELS = (64, 128, 256, 512, 512, 512)
@@ -865,6 +866,112 @@ class StyleEngine:
                                                          _ptr(grad), _stream(self.device)), "nst_histogram_term")
         return (val, grad) if want_grad else val
 
+    # ---- the relaxed EMD term (nst_level_set_remd; remd_loss.py is the driver) -------------------------------
+    def set_remd(self, level: int, style: Optional[torch.Tensor], weights=None, image_strides=1, style_strides=1,
+                 epsilon: float = _remd.DEFAULT_EPSILON) -> None:
+        """The relaxed EMD term of one level (nst_level_set_remd; Kolkin et al. 2019): the level total gains sum_i w_i remd_i,
+        remd_i the larger of the two mean cosine distances of the two-way nearest-neighbour match between the sampled vectors
+        of map i and of the style's map i.  style: the level's style image, a device float32 (C,hs,ws) tensor (any leading
+        ones; C = 3, or 1 in luminance mode), which is run through the network and whose weighted maps are kept; weights: as
+        remd_modes.normalize_weights takes them; image_strides, style_strides: one integer 1..256 or six by map index
+        (remd_modes.stride_for chooses one for a sample budget).  Data of the job, not a setting: configure(), set_taps,
+        set_pooling and set_color drop it.  style None or zero weights clear the level's term."""
+        setting = None if style is None else _remd.normalize_remd(weights, _remd.DEFAULT_SAMPLES, epsilon, None, self.taps[1])
+        ones = (C.c_int * 6)(*([1] * 6))
+        if setting is None:
+            _lib.check(self.ctx, self.lib.nst_level_set_remd(self.ctx, int(level), None, 0, 0, None, ones, ones, _remd.DEFAULT_EPSILON,
+                                                             _stream(self.device)), "nst_level_set_remd")
+            return
+        w, _, eps, _ = setting
+        si, ss = _remd.check_strides(image_strides, "image_strides"), _remd.check_strides(style_strides, "style_strides")
+        ch = self.channels
+        if style.dim() < 3 or style.numel() != ch * style.shape[-2] * style.shape[-1]:
+            raise NstError(f"the style image of level {level} must have shape ({ch},hs,ws), got {tuple(style.shape)}")
+        style = style.contiguous()
+        _chk_dev(style, self.device)
+        _lib.check(self.ctx, self.lib.nst_level_set_remd(self.ctx, int(level), _ptr(style), int(style.shape[-2]), int(style.shape[-1]),
+                                                         (C.c_float * 6)(*w), (C.c_int * 6)(*si), (C.c_int * 6)(*ss), eps,
+                                                         _stream(self.device)), "nst_level_set_remd")
+
+    def clear_remd(self, level: Optional[int] = None) -> None:
+        """No relaxed EMD term on one level, or (None) on any configured level."""
+        for l in (range(self.levels) if level is None else (level,)):
+            self.set_remd(l, None)
+
+    def remd_setting(self, level: int):
+        """(weights (6,), image strides (6,), style strides (6,), epsilon, (hs, ws) of the style image) of a level
+        (nst_level_remd), or None when the level has no term."""
+        w, si, ss, eps = (C.c_float * 6)(), (C.c_int * 6)(), (C.c_int * 6)(), C.c_double()
+        hs, wd = C.c_int(), C.c_int()
+        _lib.check(self.ctx, self.lib.nst_level_remd(self.ctx, int(level), w, si, ss, C.byref(eps), C.byref(hs), C.byref(wd)),
+                   "nst_level_remd")
+        ws = tuple(float(v) for v in w)
+        if all(v == 0.0 for v in ws):
+            return None
+        return ws, tuple(int(v) for v in si), tuple(int(v) for v in ss), eps.value, (hs.value, wd.value)
+
+    def remd_losses(self) -> torch.Tensor:
+        """(levels, 6) device tensor: the unweighted remd_i of the last closure by map index (nst_job_remd_losses); zeros for
+        maps without the term and levels outside the last level mask."""
+        out = torch.empty((self.levels, 6), dtype=torch.float32, device=self.device)
+        _lib.check(self.ctx, self.lib.nst_job_remd_losses(self.ctx, _ptr(out), _stream(self.device)), "nst_job_remd_losses")
+        return out
+
+    def remd_matches(self, level: int, map: int):
+        """(nnA (n,) int32, nnB (m,) int32, side: 0 = A or 1 = B) of map index `map` of a level as the last closure found them
+        (nst_level_remd_matches): nnA[i] the style sample of image sample i, nnB[j] the image sample of style sample j."""
+        st = self.remd_setting(level)
+        if st is None or not st[0][map] > 0.0:
+            raise NstError(f"map {map} carries no relaxed EMD term on level {level} (set_remd)")
+        h, w = self.level_shape(level)
+        n = _remd.samples_of(h >> TAP_SCALE[map], w >> TAP_SCALE[map], st[1][map])
+        m = _remd.samples_of(st[4][0] >> TAP_SCALE[map], st[4][1] >> TAP_SCALE[map], st[2][map])
+        nna = torch.empty(n, dtype=torch.int32, device=self.device)
+        nnb = torch.empty(m, dtype=torch.int32, device=self.device)
+        side = torch.empty(1, dtype=torch.int32, device=self.device)
+        _lib.check(self.ctx, self.lib.nst_level_remd_matches(self.ctx, int(level), int(map), _ptr(nna), _ptr(nnb), _ptr(side),
+                                                             _stream(self.device)), "nst_level_remd_matches")
+        return nna, nnb, int(side.item())
+
+    def _remd_maps(self, f: torch.Tensor, fs: torch.Tensor, si, ss, epsilon):
+        si, ss, eps = _remd.check_stride(si, "si"), _remd.check_stride(ss, "ss"), _remd.check_epsilon(epsilon)
+        _chk_dev(f, self.device)
+        _chk_dev(fs, self.device)
+        if f.dim() != 3 or fs.dim() != 3 or f.shape[2] != fs.shape[2]:
+            raise NstError("f and fs must be (h,w,C) and (hs,ws,C) with the same C")
+        n = _remd.samples_of(f.shape[0], f.shape[1], si)
+        m = _remd.samples_of(fs.shape[0], fs.shape[1], ss)
+        return si, ss, eps, n, m
+
+    def remd_match(self, f: torch.Tensor, fs: torch.Tensor, si: int = 1, ss: int = 1, epsilon: float = _remd.DEFAULT_EPSILON):
+        """The match alone (nst_remd_match): f (h,w,C) and fs (hs,ws,C) device float32 maps in NHWC, C = 64, 128, 256 or 512,
+        sampled with the strides si and ss -> (nnA (n,) int32, nnB (m,) int32)."""
+        si, ss, eps, n, m = self._remd_maps(f, fs, si, ss, epsilon)
+        nna = torch.empty(n, dtype=torch.int32, device=self.device)
+        nnb = torch.empty(m, dtype=torch.int32, device=self.device)
+        _lib.check(self.ctx, self.lib.nst_remd_match(self.ctx, _ptr(f), f.shape[0], f.shape[1], f.shape[2], _ptr(fs), fs.shape[0],
+                                                     fs.shape[1], si, ss, eps, _ptr(nna), _ptr(nnb), _stream(self.device)), "nst_remd_match")
+        return nna, nnb
+
+    def remd_term(self, f: torch.Tensor, fs: torch.Tensor, nnA: torch.Tensor, nnB: torch.Tensor, si: int = 1, ss: int = 1,
+                  epsilon: float = _remd.DEFAULT_EPSILON, side: int = -1, coef: float = 1.0, want_grad: bool = True):
+        """Value and gradient alone at the given matches (nst_remd_term): ((remd, rA, rB) device float32, side: 0 = A or 1 = B)
+        and, with want_grad, the (h,w,C) gradient of coef remd, zero off the sample grid.  side -1 decides (A when rA >= rB);
+        0 or 1 forces that side, and remd is then its r."""
+        si, ss, eps, n, m = self._remd_maps(f, fs, si, ss, epsilon)
+        if side not in (-1, 0, 1):
+            raise ValueError(f"side must be 0 (A), 1 (B) or -1 (decide), not {side!r}")
+        for t, rows, what in ((nnA, n, "nnA"), (nnB, m, "nnB")):
+            if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == rows and t.device == self.device):
+                raise NstError(f"{what} must be a contiguous int32 CUDA tensor of {rows} entries")
+        val = torch.empty(3, dtype=torch.float32, device=self.device)
+        sd = torch.empty(1, dtype=torch.int32, device=self.device)
+        grad = torch.empty_like(f) if want_grad else None
+        _lib.check(self.ctx, self.lib.nst_remd_term(self.ctx, _ptr(f), f.shape[0], f.shape[1], f.shape[2], _ptr(fs), fs.shape[0],
+                                                    fs.shape[1], si, ss, eps, _ptr(nnA), _ptr(nnB), int(side), float(coef), _ptr(val),
+                                                    _ptr(sd), _ptr(grad), _stream(self.device)), "nst_remd_term")
+        return (val, int(sd.item()), grad) if want_grad else (val, int(sd.item()))
+
     def closure(self, x: torch.Tensor, cw: float, sw: float, tvw: float,
                 grad: Optional[torch.Tensor] = None, losses: Optional[torch.Tensor] = None):
         """Asynchronous on the current stream. Returns (grad (C,H,W), losses (4*levels+1,)) device tensors (C = 3, or 1
@@ -1606,6 +1713,7 @@ class PixelOptimizer:
             raise ValueError("a temporal anchor cannot be combined with stripe sharding (clear_anchor())")
         _mrf.check_exclusive(next((st for st in (e.patches_setting(l) for l in range(e.levels)) if st is not None), None), stripes=True)
         _hist.check_exclusive(next((st for st in (e.histograms_setting(l) for l in range(e.levels)) if st is not None), None), stripes=True)
+        _remd.check_exclusive(next((st for st in (e.remd_setting(l) for l in range(e.levels)) if st is not None), None), stripes=True)
         contents = list(content_t) if isinstance(content_t, (list, tuple)) else [content_t]
         styles = list(style_t) if isinstance(style_t, (list, tuple)) else [style_t]
         if blend is not None and styles and isinstance(styles[0], torch.Tensor):

@@ -28,6 +28,7 @@ from . import matting_modes as _mat
 from . import moment_modes as _mom
 from . import mrf_modes as _mrf
 from . import hist_modes as _hist
+from . import remd_modes as _remd
 
 # ImageNet statistics (reference :22-23)
 IMAGENET_MEAN_255 = [123.675, 116.28, 103.53]
@@ -274,6 +275,15 @@ class _DeviceJob:
                 if levels is None or lvl in levels:
                     self.engine.set_histograms(lvl, style_of(), weights, bins)
 
+    def set_relaxed_emd(self, weights, strides, epsilon):
+        """The relaxed EMD term of the levels (StyleEngine.set_remd; `strides` per level: None for a level without the term, or
+        (image strides, style strides) as remd_modes.level_strides makes them): each level gets the style level image its
+        targets were made from, as set_patch_match does."""
+        with torch.cuda.device(self.dev), torch.cuda.stream(self.job_stream):
+            for lvl, style_of in enumerate(self.style_levels):
+                if strides[lvl] is not None:
+                    self.engine.set_remd(lvl, style_of(), weights, strides[lvl][0], strides[lvl][1], epsilon)
+
     def step(self, cw, sw, tvw):
         """One optimizer.step(closure) (nst_opt_step).  Runs on a pool thread, whose current stream is its own."""
         with torch.cuda.stream(self.job_stream):
@@ -352,6 +362,7 @@ class NeuralStyleTransfer:
         self.__patches = None                    # set_patch_match: likewise
         self.__semantics = None                  # set_patch_semantics: likewise
         self.__histograms = None                 # set_histogram_loss: likewise
+        self.__remd = None                       # set_relaxed_emd: likewise
 
     def set_feature_maps(self, content_layer=None, style_layers=None, use_relu=True):
         """Extension: the feature maps the losses of the next `process` read - a content map and a set of style maps of
@@ -503,6 +514,21 @@ class NeuralStyleTransfer:
         off = weights is None or (isinstance(weights, (int, float)) and not isinstance(weights, bool) and weights == 0)
         self.__histograms = None if off else (weights, bins, levels)
 
+    def set_relaxed_emd(self, weights=None, samples=_remd.DEFAULT_SAMPLES, epsilon=_remd.DEFAULT_EPSILON, levels=None):
+        """Extension: the relaxed EMD style term of Kolkin, Salavon & Shakhnarovich 2019 (STROTSS) in the next `process`: per
+        pyramid level sum_i w_i remd_i, remd_i the larger of the two mean cosine distances of the two-way nearest-neighbour
+        match between the sampled feature vectors of map i and of the same map of the level's style image (nst_level_set_remd
+        in include/nst_hip.h has the definition).  `weights`: None or 0 (off), a number (that weight on those of relu2_1,
+        relu3_1 and relu4_1 that are style maps of the job), six numbers by map index of Vgg19.layer_names, or a dict {map
+        index or name: number}; `samples`: the most samples per side and map (every map gets the smallest stride that keeps
+        to it; the search's cost grows with its square); `epsilon` > 0; `levels`: None for every level, or the level indices
+        that carry the term (0 = the full resolution).  Data of one job, like set_patch_match - not one of `settings`.
+        ValueError for a malformed setting and - in `process`, where the style set and the sizes are known - for a positive
+        weight on a map that is not a style map, a map that needs a stride above 256, or the term together with regions or
+        several style images."""
+        off = _remd.normalize_remd(weights, samples, epsilon, levels) is None       # (malformed: here and now)
+        self.__remd = None if off else (weights, samples, epsilon, levels)
+
     async def process(self, content_imgs, init_img, lr_start, iters_num, content_weight, style_weight, tv_weight,
                       init_img_name):
         # validates the model name exactly as the reference does (ValueError for anything but vgg19)
@@ -545,6 +571,12 @@ class NeuralStyleTransfer:
             style_set, use_relu = resolved["taps"][1:] if "taps" in resolved else (_taps.DEFAULT_STYLE_INDICES, True)
             histograms = _hist.normalize_hist(*self.__histograms, style_indices=style_set, use_relu=use_relu, levels_num=len(content_imgs))
             _hist.check_exclusive(histograms, regions=resolved.get("regions"), extra_styles=resolved.get("blend"))
+        remd = None
+        if self.__remd is not None:
+            style_set, use_relu = resolved["taps"][1:] if "taps" in resolved else (_taps.DEFAULT_STYLE_INDICES, True)
+            remd = _remd.normalize_remd(*self.__remd, style_indices=style_set, use_relu=use_relu, levels_num=len(content_imgs))
+            _remd.check_exclusive(remd, regions=resolved.get("regions"), extra_styles=resolved.get("blend"))
+            remd_strides = _remd.level_strides(remd, [tuple(c.shape[:2]) for c in content_imgs], [tuple(s.shape[:2]) for s in style_imgs])
         if self.__anchor is not None and len(self.__anchor[0]) != len(content_imgs):
             raise ValueError(f"{len(self.__anchor[0])} anchor levels for a job of {len(content_imgs)} levels")
         job = _make_job(self.__device, self.__optimizer_name, style_imgs, content_imgs, init_img, lr_start, **resolved)
@@ -565,6 +597,12 @@ class NeuralStyleTransfer:
         if histograms is not None:           # (likewise, after the MRF term)
             try:
                 job.set_histogram_loss(*histograms)
+            except BaseException:
+                job.close()
+                raise
+        if remd is not None:                 # (likewise, after the histogram loss)
+            try:
+                job.set_relaxed_emd(remd[0], remd_strides, remd[2])
             except BaseException:
                 job.close()
                 raise
@@ -668,12 +706,13 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
 
 def _transfer_from(content_n_style, content_weight, style_weight, tv_weight, optimizer, model, init_method, iters_num, levels_num,
                    noise_factor, noise_levels, noise_levels_central_amplitude, noise_levels_peripheral_amplitude,
-                   noise_levels_dispersion, *, device=None, start=None, patches=None, semantics=None, histograms=None, **keywords):
+                   noise_levels_dispersion, *, device=None, start=None, patches=None, semantics=None, histograms=None, remd=None, **keywords):
     """The settings validation of neural_style_transfer() (`keywords`: its keyword-only parameters), here and now - before any
     GPU work, ValueError - and then the job as an async generator, from the `init_method` image or from `start` (_transfer).
     `patches` (patch_match.py): None, or the arguments of NeuralStyleTransfer.set_patch_match, validated here too;
     `semantics`: None, or the arguments of NeuralStyleTransfer.set_patch_semantics, likewise (they need `patches`);
-    `histograms` (histogram_loss.py): None, or the arguments of NeuralStyleTransfer.set_histogram_loss, likewise."""
+    `histograms` (histogram_loss.py): None, or the arguments of NeuralStyleTransfer.set_histogram_loss, likewise; `remd`
+    (remd_loss.py): None, or the arguments of NeuralStyleTransfer.set_relaxed_emd, likewise."""
     settings = _job.JobSettings(for_job=True, **keywords)
 
     def level_shapes(img):      # (the level sizes follow from the image size: top level first)
@@ -697,6 +736,12 @@ def _transfer_from(content_n_style, content_weight, style_weight, tv_weight, opt
         checked = _hist.normalize_hist(*histograms, style_indices=style_set, use_relu=use_relu, levels_num=max(levels_num, 1))
         _hist.check_exclusive(checked, regions=resolved.get("regions"), extra_styles=keywords.get("extra_styles"))
         histograms = histograms if checked is not None else None
+    if remd is not None:
+        style_set, use_relu = resolved["taps"][1:] if "taps" in resolved else (_taps.DEFAULT_STYLE_INDICES, True)
+        checked = _remd.normalize_remd(*remd, style_indices=style_set, use_relu=use_relu, levels_num=max(levels_num, 1))
+        _remd.check_exclusive(checked, regions=resolved.get("regions"), extra_styles=keywords.get("extra_styles"))
+        _remd.level_strides(checked, level_shapes(content_n_style.content[1]), level_shapes(content_n_style.style[1]))
+        remd = remd if checked is not None else None
     extra_styles = keywords.get("extra_styles")
     extra_styles = list(extra_styles) if extra_styles is not None else []
     for img in extra_styles:
@@ -705,19 +750,20 @@ def _transfer_from(content_n_style, content_weight, style_weight, tv_weight, opt
     return _transfer(content_n_style, content_weight, style_weight, tv_weight, optimizer, model, init_method, iters_num, levels_num,
                      noise_factor, noise_levels, noise_levels_central_amplitude, noise_levels_peripheral_amplitude,
                      noise_levels_dispersion, device, settings, keywords.get("preserve_color"), extra_styles,
-                     keywords.get("style_blend"), start, patches, semantics, histograms)
+                     keywords.get("style_blend"), start, patches, semantics, histograms, remd)
 
 
 async def _transfer(content_n_style, content_weight, style_weight, tv_weight, optimizer, model, init_method, iters_num, levels_num,
                     noise_factor, noise_levels, noise_levels_central_amplitude, noise_levels_peripheral_amplitude,
                     noise_levels_dispersion, device, settings, preserve_color, extra_styles, style_blend, start=None, patches=None,
-                    semantics=None, histograms=None):
+                    semantics=None, histograms=None, remd=None):
     """neural_style_transfer() below its settings validation: `settings` is its validated JobSettings, `extra_styles` its
     checked list.  `start` (video.py): None, or a callable (setup engine, level-0 (h, w)) -> (start image: a device HWC
     tensor the job starts from in place of the `init_method` image, anchor levels, weight levels, gamma) - the arguments of
     NeuralStyleTransfer.set_anchor - called once the level sizes are known.  `patches` (patch_match.py): None, or the checked
     arguments of NeuralStyleTransfer.set_patch_match; `semantics`: None, or those of NeuralStyleTransfer.set_patch_semantics;
-    `histograms` (histogram_loss.py): None, or those of NeuralStyleTransfer.set_histogram_loss."""
+    `histograms` (histogram_loss.py): None, or those of NeuralStyleTransfer.set_histogram_loss; `remd` (remd_loss.py): None,
+    or those of NeuralStyleTransfer.set_relaxed_emd."""
     if device is None:
         if not torch.cuda.is_available():
             raise RuntimeError("no GPU visible: the HIP style-transfer engine has no CPU path")
@@ -758,6 +804,8 @@ async def _transfer(content_n_style, content_weight, style_weight, tv_weight, op
         nst.set_patch_semantics(*semantics)
     if histograms is not None:
         nst.set_histogram_loss(*histograms)
+    if remd is not None:
+        nst.set_relaxed_emd(*remd)
     # (the extra styles as their pyramids; "histogram" has recoloured the style levels above)
     settings.update(extra_styles=extra_levels, style_blend=style_blend if extra_levels else None)
     if preserve_color == "histogram":

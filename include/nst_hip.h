@@ -1010,6 +1010,79 @@ int nst_histogram_tables(nst_ctx* ctx, const float* lo_hi, const unsigned* count
                          const unsigned* s_counts, long long Ns, int C, int bins, float* ends_out, void* stream);
 int nst_histogram_term(nst_ctx* ctx, const float* f, long long N, int C, int bins, const float* lo_hi, const float* ends, float coef,
                        float* value_out /* nullable */, float* grad_out /* nullable */, void* stream);
+/* ---- The relaxed EMD style term (Kolkin, Salavon & Shakhnarovich 2019, "Style Transfer by Relaxed Optimal Transport and
+ * Self-Similarity", STROTSS) ----------------------------------------------------------------------------------------------------
+ * Two-way nearest-neighbour matching of feature vectors: every image vector must have a close style vector (side A), every
+ * style vector a close image vector (side B), and the term is the larger of the two mean cosine distances.  For one pyramid
+ * level and one tapped map of index i in Vgg19.layer_names:
+ *   F  = the map of the level image, NHWC, h x w x C;  Fs = the same map of the level's style image, hs x ws x C, through the
+ *        network the job uses (its tap flavour, its pooling, its colour mode);  C = 64, 128, 256 or 512.
+ * Samples.  The image stride si and the style stride ss are integers in 1..256.  The image samples X_i, n of them, are the
+ *   pixels (a si, b si), a = 0..(h-1)/si, b = 0..(w-1)/si (integer division), in row-major order; the style samples Y_j, m of
+ *   them, likewise with ss.
+ * Norms.  rp_i = (float)(1 / sqrt(|X_i|^2 + epsilon)), rq_j likewise for Y_j; epsilon > 0 (default 1e-5).  The squares are
+ *   formed and summed in double: a wave per sample, lane l adds the squares of its 16-byte channel runs l, l + 64, ... in
+ *   ascending order, the 64 lanes by the xor tree (offsets 32, 16, .., 1).
+ * Matches.  c(i,j) = <X_i, Y_j> rp_i rq_j in the f16x2 arithmetic of the convolutions: each side's samples are scaled by the
+ *   power of two of its map's absmax record and cut into a hi and a lo fp16 piece as in the MRF search; per 16 channels, in
+ *   ascending order, the MFMA accumulates lo_d hi_c, hi_d hi_c, hi_d lo_c (d: the dictionary side, c: the column side) into a
+ *   main (hi hi) and a cross accumulator; then c = (((main + cross 2^-11) inv) r_d) r_c + 0, every operation rounded in fp32,
+ *   inv the product of the two inverse scales.  In direction A the style is the dictionary and the image the columns, in
+ *   direction B the image is the dictionary: the same kernel twice, so r_d is rq in A and rp in B.
+ *   nnA(i) = the lowest j among the maxima of c(i, .);  nnB(j) = the lowest i among the maxima of c(., j).  Scores of -0 count
+ *   as +0.  An all-zero sample has every score +0 and so the match 0.
+ * Value, formed in double from the fp32 maps at the matches, not from the search's scores.
+ *   a_i = <X_i, Y_nnA(i)> / sqrt((|X_i|^2 + eps)(|Y_nnA(i)|^2 + eps));  b_j = the same expression at (nnB(j), j).  The three
+ *   sums of one pair run over the channels in the order of the norms.  rA = 1 - (1/n) sum a_i, rB = 1 - (1/m) sum b_j, both sums
+ *   in a fixed two-stage order (256 blocks of consecutive samples, four waves a block each taking every fourth sample, the waves
+ *   in wave order; then the 256 partials by a tree).  remd_i = (float)max(rA, rB).  The active side is A when rA >= rB, else B.
+ * Loss row.  A level with the term has the total (... + sum_i w_i hist_i) + sum_i w_i remd_i: added after the histogram term, in
+ *   ascending map order, every product and sum rounded.  NST_LOSS_ROW stays 4.  The weights are the term's own: style_weight
+ *   does not scale it.
+ * Gradient of the active side, exact wherever the matches and the side are locally constant.  It reaches sampled pixels only.
+ *   d(i,j) = rp_i ((cos rp_i) X_i - rq_j Y_j) with cos the stored (float)a_i (side A) or (float)b_j (side B), computed as
+ *   t = cos rp_i; u = t X_i; v = rq_j Y_j; d = (u - v) rp_i.
+ *   side A: dX_i = (float)(w/n) d(i, nnA(i));  side B: dX_i = (float)(w/m) sum over the j with nnB(j) = i, in ascending j, of
+ *   d(i,j), the sum starting from +0.  fp32, contraction off, the coefficients formed in double.  It joins the addend of the
+ *   launch below the map, after the content gradient, the MRF term's and the histogram term's where the map has those; at the
+ *   top of the chain it is the addend of the 1x1 Gram launch, as for the MRF term.  The side flag is read on the device.
+ * Determinism.  No float atomic takes part.  Across workgroups the searches combine by the integer atomicMax on the 64-bit key
+ *   (score bits above ~index); side B's sum is formed in ascending j.  A closure with the term is bitwise reproducible.
+ *
+ * nst_level_set_remd: the term of one level, data of one job like the MRF term.  style = device (C,hs,ws) image in the job's
+ *   colour mode, NULL: clear the level's term.  weights[6], image_stride[6], style_stride[6] by map index (all six stride pairs
+ *   are checked).  The call runs the style image through the network up to the deepest weighted map, keeps the weighted maps
+ *   with their absmax record, rq and packed operand, and allocates everything a closure needs.  Life cycle of
+ *   nst_level_set_patches: waits for the context's work; drops a captured graph, an L-BFGS memo and a pending backward half; a
+ *   refusal changes nothing; nst_job_configure drops the term with the levels; nst_job_set_taps, nst_job_set_pooling and
+ *   nst_job_set_color drop it.
+ *   NST_E_ARG: level out of range; negative or non-finite weights; epsilon <= 0 or not finite; a stride outside 1..256; a
+ *   positive weight on a map that is not a style map of the job.
+ *   NST_E_STATE: no configured job; an arithmetic mode other than f16x2; a guided level (nst_level_set_guidance on a level with
+ *   the term refuses likewise); a context with use_graph.  The stripe closure returns NST_E_STATE while its level carries the
+ *   term.
+ * nst_level_remd: the level's setting (all-zero weights: no term; hs, ws: the size of the style image the setter was given);
+ *   every output is nullable.
+ * nst_job_remd_losses: out = device, levels x 6: the unweighted remd_i of the last closure by map index (zeros: maps without the
+ *   term and levels outside the last level mask).
+ * nst_level_remd_matches: nnA (n int32), nnB (m int32) and the side (one int32: 0 = A, 1 = B) of the last closure of one weighted
+ *   map, device pointers, each nullable; zeros before any closure.  NST_E_STATE: the map carries no term on the level.
+ * nst_remd_match, nst_remd_term: the pieces alone, on NHWC device maps.  They read no job state.  Synchronous.
+ *   nst_remd_term: the value and the gradient at given matches.  side = 0 / 1 takes that side whatever the values (remd is then
+ *   that side's r), -1 decides.  coef is the weight w of the definition.  value_out = device, 3 floats (remd, rA, rB); side_out =
+ *   device int32; grad_out = NHWC like f, overwritten (zero off the sample grid); each nullable. */
+int nst_level_set_remd(nst_ctx* ctx, int level, const float* style /* device (C,hs,ws), or NULL: clear */, int hs, int ws,
+                       const float* weights /* 6, by map index */, const int* image_stride /* 6 */, const int* style_stride /* 6 */,
+                       double epsilon, void* stream);
+int nst_level_remd(const nst_ctx* ctx, int level, float* weights /* 6 */, int* image_stride /* 6 */, int* style_stride /* 6 */,
+                   double* epsilon, int* hs, int* ws);
+int nst_job_remd_losses(nst_ctx* ctx, float* out /* device, levels x 6 */, void* stream);
+int nst_level_remd_matches(nst_ctx* ctx, int level, int map, int* nnA_out, int* nnB_out, int* side_out, void* stream);
+int nst_remd_match(nst_ctx* ctx, const float* f, int h, int w, int C, const float* fs, int hs, int ws, int si, int ss, double epsilon,
+                   int* nnA_out /* n */, int* nnB_out /* m */, void* stream);
+int nst_remd_term(nst_ctx* ctx, const float* f, int h, int w, int C, const float* fs, int hs, int ws, int si, int ss, double epsilon,
+                  const int* nnA, const int* nnB, int side, float coef, float* value_out /* 3, nullable */, int* side_out /* nullable */,
+                  float* grad_out /* nullable */, void* stream);
 int nst_warp_bilinear(nst_ctx* ctx, const float* src, const float* flow, int C, int h, int w, float* out,
                       float* valid /* nullable */, void* stream);
 int nst_flow_weights(nst_ctx* ctx, const float* fwd, const float* bwd, int h, int w, float* out, void* stream);
