@@ -294,17 +294,6 @@ int patch_forward(nst_ctx* ctx, LevelWs& L, hipStream_t s) {
     }
     return NST_OK;
 }
-// gradient part of map index i: into dst (the map's shape), written or added to what is there
-int patch_backward(nst_ctx* ctx, LevelWs& L, int i, float* dst, int accumulate, hipStream_t s) {
-    Timer tm(ctx, s, K_OTHER, 0);
-    HIPCHK(ctx, launch_pm_grad(patch_term_of(L, i), patch_coef(L.pm.w[i], patch_denom(L, i)), dst, accumulate, s));
-    return NST_OK;
-}
-// conv layer m of level L carries the term
-bool patch_layer(const LevelWs& L, int m) {
-    const int i = tap_index_of(m);
-    return i >= 0 && L.pm.w[i] > 0.f;
-}
 
 // ---- the histogram loss (include/nst_hip.h has the definition; kernels: histogram.hip) -----------------------------------
 // map index i of level L: the term's operands on the level's own map, C N, and coef = (float)(2 w / (C N)) formed in double
@@ -330,17 +319,6 @@ int hist_forward(nst_ctx* ctx, LevelWs& L, hipStream_t s) {
         HIPCHK(ctx, launch_hist_value(L.hist.partial[i], hist_denom(L, i), L.hist.vals + i, s));
     }
     return NST_OK;
-}
-// gradient part of map index i: into dst (the map's shape), written or added to what is there
-int hist_backward(nst_ctx* ctx, LevelWs& L, int i, float* dst, int accumulate, hipStream_t s) {
-    Timer tm(ctx, s, K_OTHER, 0);
-    HIPCHK(ctx, launch_hist_grad(hist_term_of(L, i), hist_coef(L.hist.w[i], hist_denom(L, i)), dst, accumulate, s));
-    return NST_OK;
-}
-// conv layer m of level L carries the term
-bool hist_layer(const LevelWs& L, int m) {
-    const int i = tap_index_of(m);
-    return i >= 0 && L.hist.w[i] > 0.f;
 }
 
 // ---- the relaxed EMD term (include/nst_hip.h has the definition; kernels: remd.hip) ---------------------------------------
@@ -385,17 +363,37 @@ int remd_forward(nst_ctx* ctx, LevelWs& L, hipStream_t s) {
     }
     return NST_OK;
 }
-// gradient part of map index i: into dst (the map's shape), written or added to what is there
-int remd_backward(nst_ctx* ctx, LevelWs& L, int i, float* dst, int accumulate, hipStream_t s) {
-    Timer tm(ctx, s, K_OTHER, 0);
-    const RemdTerm t = remd_term_of(L, i);
-    HIPCHK(ctx, launch_remd_grad(t, remd_coef(L.remd.w[i], t.x.count), remd_coef(L.remd.w[i], t.y.count), dst, accumulate, s));
+
+// ---- the per-map terms together (MapTerm in nst_ctx.h): MRF, histogram loss, relaxed EMD - always in this order ------------
+// forward parts of the levels lv[0..n), once their maps exist: every level of one term before the next term
+int map_terms_forward(nst_ctx* ctx, const int* lv, int n, hipStream_t s) {
+    for (int k = 0; k < n; ++k) NSTCHK(patch_forward(ctx, ctx->lv[lv[k]], s));
+    for (int k = 0; k < n; ++k) NSTCHK(hist_forward(ctx, ctx->lv[lv[k]], s));
+    for (int k = 0; k < n; ++k) NSTCHK(remd_forward(ctx, ctx->lv[lv[k]], s));
     return NST_OK;
 }
-// conv layer m of level L carries the term
-bool remd_layer(const LevelWs& L, int m) {
+// gradient parts of conv layer m of level L, of the terms the map carries, into dst (the map's shape).  `held`: dst holds an
+// addend already (the content gradient) - the first launch writes unless it does, every later one adds - and on return:
+// it holds one now.  The one place a walker's addend takes these gradients in, at the top of a chain or inside it.
+int map_terms_backward(nst_ctx* ctx, const LevelWs& L, int m, float* dst, bool& held, hipStream_t s) {
     const int i = tap_index_of(m);
-    return i >= 0 && L.remd.w[i] > 0.f;
+    if (L.pm.carries(m)) {
+        Timer tm(ctx, s, K_OTHER, 0);
+        HIPCHK(ctx, launch_pm_grad(patch_term_of(L, i), patch_coef(L.pm.w[i], patch_denom(L, i)), dst, held ? 1 : 0, s));
+        held = true;
+    }
+    if (L.hist.carries(m)) {
+        Timer tm(ctx, s, K_OTHER, 0);
+        HIPCHK(ctx, launch_hist_grad(hist_term_of(L, i), hist_coef(L.hist.w[i], hist_denom(L, i)), dst, held ? 1 : 0, s));
+        held = true;
+    }
+    if (L.remd.carries(m)) {
+        Timer tm(ctx, s, K_OTHER, 0);
+        const RemdTerm t = remd_term_of(L, i);
+        HIPCHK(ctx, launch_remd_grad(t, remd_coef(L.remd.w[i], t.x.count), remd_coef(L.remd.w[i], t.y.count), dst, held ? 1 : 0, s));
+        held = true;
+    }
+    return NST_OK;
 }
 
 // ---- the moment loss (include/nst_hip.h has the definition; kernels: moments.hip) ----------------------------------------
@@ -465,7 +463,7 @@ int forward(nst_ctx* ctx, ActSet& a, const float* x, int h, int w, hipStream_t s
 
 // ---- network backward (nst_ctx.h has the contract) --------------------------------------------------
 int backward(nst_ctx* ctx, ActSet& a, const Inject* inj, const ContentJob* cj, float* gbuf0, float* gbuf1, float* gx,
-             int h, int w, hipStream_t s, int top, bool top_mask, int channels) {
+             int h, int w, hipStream_t s, int top, bool top_mask, int channels, const LevelWs* terms) {
     float* cur = gbuf0;     // holds the gradient w.r.t. the pre-ReLU output of the layer being processed
     float* oth = gbuf1;
     const bool h2 = ctx->conv_mode == 2;
@@ -479,24 +477,9 @@ int backward(nst_ctx* ctx, ActSet& a, const Inject* inj, const ContentJob* cj, f
             Timer t(ctx, s, K_OTHER, 0);
             HIPCHK(ctx, launch_mse_grad(a.act[l], cj->target, cj->n, cj->coef, oth, cj->partial, s));
         }
-        // the MRF term of the top map: onto the content gradient when there is one, the addend of the 1x1 Gram launch
-        const bool mrf = inj[l].mrf && inj[l].S;
-        if (mrf) {
-            Timer t(ctx, s, K_OTHER, 0);
-            HIPCHK(ctx, launch_pm_grad(*inj[l].mrf, inj[l].mrf_coef, oth, content ? 1 : 0, s));
-        }
-        // the histogram loss of the top map, after both
-        const bool hist = inj[l].hist && inj[l].S;
-        if (hist) {
-            Timer t(ctx, s, K_OTHER, 0);
-            HIPCHK(ctx, launch_hist_grad(*inj[l].hist, inj[l].hist_coef, oth, (content || mrf) ? 1 : 0, s));
-        }
-        // the relaxed EMD term of the top map, after all three
-        const bool remd = inj[l].remd && inj[l].S;
-        if (remd) {
-            Timer t(ctx, s, K_OTHER, 0);
-            HIPCHK(ctx, launch_remd_grad(*inj[l].remd, inj[l].remd_coefA, inj[l].remd_coefB, oth, (content || mrf || hist) ? 1 : 0, s));
-        }
+        // the per-map terms of the top map: onto the content gradient when there is one, the addend of the 1x1 Gram launch
+        bool held = content;
+        if (terms && inj[l].S) NSTCHK(map_terms_backward(ctx, *terms, l, oth, held, s));
         if (inj[l].guided) {
             GuidedBwd gb = *inj[l].guided;
             gb.addend = content ? oth : nullptr; gb.out = cur; gb.mask = top_mask ? a.act[l] : nullptr;
@@ -505,7 +488,7 @@ int backward(nst_ctx* ctx, ActSet& a, const Inject* inj, const ContentJob* cj, f
             // (the content gradient, if any, as the addend of the 1x1 Gram launch)
             ConvParams p{};
             p.in = a.act[l]; p.wt = inj[l].S; p.out = cur; p.mask = top_mask ? a.act[l] : nullptr;
-            p.addend = (content || mrf || hist || remd) ? oth : nullptr;
+            p.addend = held ? oth : nullptr;
             p.bias = inj[l].bias;                  // (a shifted Gram: F S + r, then the addend and the mask)
             p.H = a.h[l]; p.W = a.w[l]; p.Cin = kCout[l]; p.Cout = kCout[l];
             Timer t(ctx, s, K_GRAM, conv_flops(p.H, p.W, p.Cin, p.Cout, 1));
@@ -561,24 +544,10 @@ int backward(nst_ctx* ctx, ActSet& a, const Inject* inj, const ContentJob* cj, f
             } else if (in.direct) {
                 p.addend = in.direct;
             }
-            if (in.mrf) {
-                // the MRF term of the map: written, or added to the content gradient
-                Timer t(ctx, s, K_OTHER, 0);
-                HIPCHK(ctx, launch_pm_grad(*in.mrf, in.mrf_coef, oth, p.addend == oth ? 1 : 0, s));
-                p.addend = oth;
-            }
-            if (in.hist) {
-                // the histogram loss of the map: written, or added to the content gradient and the MRF term's
-                Timer t(ctx, s, K_OTHER, 0);
-                HIPCHK(ctx, launch_hist_grad(*in.hist, in.hist_coef, oth, p.addend == oth ? 1 : 0, s));
-                p.addend = oth;
-            }
-            if (in.remd) {
-                // the relaxed EMD term of the map: written, or added to the gradients before it
-                Timer t(ctx, s, K_OTHER, 0);
-                HIPCHK(ctx, launch_remd_grad(*in.remd, in.remd_coefA, in.remd_coefB, oth, p.addend == oth ? 1 : 0, s));
-                p.addend = oth;
-            }
+            // the per-map terms of the map: written, or added to the content gradient
+            bool held = p.addend == oth;
+            if (terms) NSTCHK(map_terms_backward(ctx, *terms, m, oth, held, s));
+            if (held) p.addend = oth;
             if (in.guided) {
                 // the guided Gram backward by its own launch, onto the content gradient when there is one: the addend
                 GuidedBwd gb = *in.guided;
@@ -936,26 +905,11 @@ int batched_backward(nst_ctx* ctx, const float* const* xi, float* const* gi, con
     };
     if (top_content)
         for (int k = 0; k < n; ++k) NSTCHK(content_grad(k, oth[k]));
-    // the MRF term of the top map (nst_level_set_patches; a level's own), written after the content gradient: the launch's addend
-    bool top_mrf[NST_MAX_LEVELS] = {};
-    for (int k = 0; k < n && top_q >= 0; ++k) {
-        LevelWs& L = ctx->lv[lv[k]];
-        top_mrf[k] = patch_layer(L, top);
-        if (top_mrf[k]) NSTCHK(patch_backward(ctx, L, tap_index_of(top), oth[k], top_content ? 1 : 0, s));
-    }
-    // the histogram loss of the top map (nst_level_set_histograms; a level's own), after both; top_add: the launch has an addend
+    // the per-map terms of the top map (a level's own), after the content gradient; top_add: the launch has an addend
     bool top_add[NST_MAX_LEVELS] = {};
     for (int k = 0; k < n; ++k) {
-        LevelWs& L = ctx->lv[lv[k]];
-        top_add[k] = top_content || top_mrf[k];
-        if (top_q >= 0 && hist_layer(L, top)) {
-            NSTCHK(hist_backward(ctx, L, tap_index_of(top), oth[k], top_add[k] ? 1 : 0, s));
-            top_add[k] = true;
-        }
-        if (top_q >= 0 && remd_layer(L, top)) {      // (the relaxed EMD term, nst_level_set_remd, after all three)
-            NSTCHK(remd_backward(ctx, L, tap_index_of(top), oth[k], top_add[k] ? 1 : 0, s));
-            top_add[k] = true;
-        }
+        top_add[k] = top_content;
+        if (top_q >= 0) NSTCHK(map_terms_backward(ctx, ctx->lv[lv[k]], top, oth[k], top_add[k], s));
     }
     const bool guided = guided_levels(ctx, lv, n);
     if (guided && top_q >= 0) {
@@ -1063,21 +1017,10 @@ int batched_backward(nst_ctx* ctx, const float* const* xi, float* const* gi, con
                 NSTCHK(content_grad(k, oth[k]));
                 im.addend = oth[k];
             }
-            if (patch_layer(L, m)) {
-                // the MRF term of the map, after the content gradient when the map is the content map too
-                NSTCHK(patch_backward(ctx, L, tap_index_of(m), oth[k], m == tp.content ? 1 : 0, s));
-                im.addend = oth[k];
-            }
-            if (hist_layer(L, m)) {
-                // the histogram loss of the map, after the content gradient and the MRF term where the map has those
-                NSTCHK(hist_backward(ctx, L, tap_index_of(m), oth[k], im.addend == oth[k] ? 1 : 0, s));
-                im.addend = oth[k];
-            }
-            if (remd_layer(L, m)) {
-                // the relaxed EMD term of the map, after the gradients before it where the map has those
-                NSTCHK(remd_backward(ctx, L, tap_index_of(m), oth[k], im.addend == oth[k] ? 1 : 0, s));
-                im.addend = oth[k];
-            }
+            // the per-map terms of the map, after the content gradient when the map is the content map too
+            bool held = im.addend == oth[k];
+            NSTCHK(map_terms_backward(ctx, L, m, oth[k], held, s));
+            if (held) im.addend = oth[k];
             im.bits_in = a.bits[m];
         }
         {
@@ -1143,9 +1086,7 @@ int closure_batched_forward(nst_ctx* ctx, const float* const* xi, unsigned level
     NSTCHK(batched_forward(ctx, xi, lv, n, s, nullptr, overlap ? sw : -1.f));
     NSTCHK(batched_gram(ctx, lv, n, sw, s, overlap ? 0x18u : (1u << ctx->taps.nstyle) - 1u));
     if (overlap) HIPCHK(ctx, hipStreamWaitEvent(s, ctx->side_join, 0));
-    for (int k = 0; k < n; ++k) NSTCHK(patch_forward(ctx, ctx->lv[lv[k]], s));       // (nst_level_set_patches: the maps exist)
-    for (int k = 0; k < n; ++k) NSTCHK(hist_forward(ctx, ctx->lv[lv[k]], s));        // (nst_level_set_histograms likewise)
-    for (int k = 0; k < n; ++k) NSTCHK(remd_forward(ctx, ctx->lv[lv[k]], s));        // (nst_level_set_remd likewise)
+    NSTCHK(map_terms_forward(ctx, lv, n, s));        // (the per-map terms: the maps exist)
     if (loss_terms && ctx->forward_pack && ctx->conv_mode == 2 && !ctx->use_graph && n > 1) {
         // one launch each for all levels; every level keeps its partial buffers and block decomposition
         MseBatch mb{};
@@ -1250,36 +1191,10 @@ int closure_per_level(nst_ctx* ctx, const float* const* xi, float* const* gi, in
         inj[l].S_amax = h2 ? amax_S(L.acts, k) : nullptr;
     }
     inj[tp.content].content = true;
-    // the MRF term (nst_level_set_patches): nn and the values now, the gradients as addends of the walk
-    NSTCHK(patch_forward(ctx, L, s));
-    PatchTerm pterm[6];
-    for (int i = 0; i < 6 && L.pm.on(); ++i) {
-        if (!(L.pm.w[i] > 0.f)) continue;
-        pterm[i] = patch_term_of(L, i);
-        inj[kTapLayer[i]].mrf = &pterm[i];
-        inj[kTapLayer[i]].mrf_coef = patch_coef(L.pm.w[i], patch_denom(L, i));
-    }
-    // the histogram loss (nst_level_set_histograms): tables and values now, the gradients as addends of the walk
-    NSTCHK(hist_forward(ctx, L, s));
-    HistTerm hterm[6];
-    for (int i = 0; i < 6 && L.hist.on(); ++i) {
-        if (!(L.hist.w[i] > 0.f)) continue;
-        hterm[i] = hist_term_of(L, i);
-        inj[kTapLayer[i]].hist = &hterm[i];
-        inj[kTapLayer[i]].hist_coef = hist_coef(L.hist.w[i], hist_denom(L, i));
-    }
-    // the relaxed EMD term (nst_level_set_remd): matches, values and sides now, the gradients as addends of the walk
-    NSTCHK(remd_forward(ctx, L, s));
-    RemdTerm rterm[6];
-    for (int i = 0; i < 6 && L.remd.on(); ++i) {
-        if (!(L.remd.w[i] > 0.f)) continue;
-        rterm[i] = remd_term_of(L, i);
-        inj[kTapLayer[i]].remd = &rterm[i];
-        inj[kTapLayer[i]].remd_coefA = remd_coef(L.remd.w[i], rterm[i].x.count);
-        inj[kTapLayer[i]].remd_coefB = remd_coef(L.remd.w[i], rterm[i].y.count);
-    }
+    // the per-map terms: matches, tables and values now, the gradients as addends of the walk
+    NSTCHK(map_terms_forward(ctx, &level, 1, s));
     ContentJob cj{L.content_t, L.content_n, content_coef(cw, (double)L.content_n), L.content_partial};
-    NSTCHK(backward(ctx, L.acts, inj, &cj, L.gbuf[0], L.gbuf[1], gi[level], L.h, L.w, s, tp.top, tp.top_mask(), ctx->channels));
+    NSTCHK(backward(ctx, L.acts, inj, &cj, L.gbuf[0], L.gbuf[1], gi[level], L.h, L.w, s, tp.top, tp.top_mask(), ctx->channels, &L));
     {
         Timer t(ctx, s, K_OTHER, 0);
         HIPCHK(ctx, launch_tv_finish(xi[level], ctx->channels, L.h, L.w, L.tv_partial, tvw, gi[level], 1, L.tv_means, s));
@@ -1319,23 +1234,13 @@ LossAssembly fill_loss_assembly(const nst_ctx* ctx, unsigned level_mask, float c
         if (!(L.anc.gamma > 0.f)) continue;
         la.lv[i].tmp_partial = L.anc.partial; la.lv[i].tmp_gamma = L.anc.gamma; la.lv[i].tmp_n = anchor_n(ctx, L); la.lv[i].tmp_out = L.anc.val;
     }
-    for (int i = 0; i < ctx->levels; ++i) {      // (a level's own: la{} left the levels without the MRF term at nullptr)
-        const LevelWs& L = ctx->lv[i];
-        if (!L.pm.on()) continue;
-        la.lv[i].mrf_vals = L.pm.vals;
-        for (int k = 0; k < 6; ++k) la.lv[i].mrf_w[k] = L.pm.w[k];
-    }
-    for (int i = 0; i < ctx->levels; ++i) {      // (the histogram loss, a level's own in the same way)
-        const LevelWs& L = ctx->lv[i];
-        if (!L.hist.on()) continue;
-        la.lv[i].hist_vals = L.hist.vals;
-        for (int k = 0; k < 6; ++k) la.lv[i].hist_w[k] = L.hist.w[k];
-    }
-    for (int i = 0; i < ctx->levels; ++i) {      // (the relaxed EMD term, a level's own in the same way)
-        const LevelWs& L = ctx->lv[i];
-        if (!L.remd.on()) continue;
-        la.lv[i].remd_vals = L.remd.vals;
-        for (int k = 0; k < 6; ++k) la.lv[i].remd_w[k] = L.remd.w[k];
+    for (int i = 0; i < ctx->levels; ++i) {      // (a level's own: la{} left the levels without a per-map term at nullptr)
+        for (int t = 0; t < NST_MAP_TERMS; ++t) {
+            const MapTerm& g = ctx->lv[i].map_term(t);
+            if (!g.on()) continue;
+            la.lv[i].term[t].vals = g.vals;
+            for (int k = 0; k < 6; ++k) la.lv[i].term[t].w[k] = g.w[k];
+        }
     }
     return la;
 }

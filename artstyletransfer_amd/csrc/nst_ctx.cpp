@@ -424,6 +424,84 @@ int replace_term(nst_ctx* ctx, Block LevelWs::*member, Fill fill) {
     return replace_blocks(ctx->lv, ctx->levels, member, fill, [&] { quiesce(ctx); drop_closure_state(ctx, true); });
 }
 
+// ---- what the per-map terms (MapTerm: MRF, histogram loss, relaxed EMD) share outside a closure -----------------------------
+// how the refusals of a term's setter name it ("the <adj> weights", "no <name>"), and what the term asks of the job besides
+struct MapTermWords { const char* adj; const char* name; bool f16x2_only; bool min_3x3; };
+const MapTermWords kMrfWords{"MRF", "MRF term", true, true};
+const MapTermWords kHistWords{"histogram", "histogram loss", false, false};
+const MapTermWords kRemdWords{"relaxed EMD", "relaxed EMD term", true, false};
+
+// every level's per-map terms go (they hold maps of the style image as the job's network saw it: the setters again)
+void drop_map_terms(nst_ctx* ctx) {
+    for (int i = 0; i < ctx->levels; ++i) {
+        ctx->lv[i].pm = PatchLevel();
+        ctx->lv[i].hist = HistLevel();
+        ctx->lv[i].remd = RemdLevel();
+    }
+}
+// weight i of a setter's six into the new block
+int take_weight(nst_ctx* ctx, const MapTermWords& t, const float* weights, int i, MapTerm& g) {
+    if (!(weights[i] >= 0.f) || std::isinf(weights[i]))
+        return fail(ctx, NST_E_ARG, std::string("the ") + t.adj + " weights must be finite and >= 0");
+    g.w[i] = weights[i];
+    return NST_OK;
+}
+// A setter after its own argument checks: orders the stream and, when the new block g has a positive weight, refuses what
+// every term refuses, then runs the style image through the network on scratch up to the deepest weighted map (sc: left
+// open, the setter copies from its maps) and makes the zeroed vals.  No positive weight: sc stays empty.
+int begin_map_term(nst_ctx* ctx, const MapTermWords& t, const LevelWs& L, MapTerm& g, const float* style, int hs, int ws, void* stream,
+                   std::optional<Scratch>& sc) {
+    hipStream_t s = enter(ctx, stream);
+    if (!g.on()) return NST_OK;
+    const std::string name = t.name, adj = t.adj;
+    if (t.f16x2_only && ctx->conv_mode != 2) return fail(ctx, NST_E_STATE, "the " + name + " runs in the f16x2 arithmetic only (NST_CONV unset)");
+    if (ctx->use_graph) return fail(ctx, NST_E_STATE, "the " + name + "'s launches are not captured: a context with use_graph takes no term");
+    if (L.guide.R > 0) return fail(ctx, NST_E_STATE, "a guided level takes no " + name + " (nst_level_set_guidance(ctx, level, 0, ...) clears the guidance)");
+    if (hs < 16 || ws < 16) return fail(ctx, NST_E_ARG, "style image must be at least 16x16");
+    const unsigned style_mask = style_mask_of(ctx->taps);
+    int deepest = -1;
+    for (int i = 0; i < 6; ++i) {
+        if (!(g.w[i] > 0.f)) continue;
+        if (!((style_mask >> i) & 1u)) return fail(ctx, NST_E_ARG, "a positive " + adj + " weight on a map that is not a style map of the job");
+        const int l = kTapLayer[i];
+        if (t.min_3x3 && (L.acts.h[l] < 3 || L.acts.w[l] < 3 || (hs >> kScale[l]) < 3 || (ws >> kScale[l]) < 3))
+            return fail(ctx, NST_E_ARG, "a weighted map or its style map is below 3x3");
+        deepest = l;
+    }
+    sc.emplace(ctx, s);
+    NSTCHK(alloc_acts(ctx, sc->acts, hs, ws));
+    NSTCHK(forward(ctx, sc->acts, style, hs, ws, s, deepest, ctx->channels));
+    NSTCHK(g.mem.alloc(ctx, &g.vals, 6));
+    HIPCHK(ctx, hipMemsetAsync(g.vals, 0, 6 * sizeof(float), s));
+    return NST_OK;
+}
+// A setter's end: the scratch goes (or, no positive weight, g is a cleared block), the context's work is waited for, what a
+// closure remembered goes, and g becomes the level's block
+template <typename Block>
+int commit_map_term(nst_ctx* ctx, std::optional<Scratch>& sc, Block& slot, Block& g) {
+    if (sc) NSTCHK(sc->finish());       // (synchronises: the caller's image is free again when this returns)
+    else g = Block();
+    quiesce(ctx);
+    drop_closure_state(ctx, false);
+    slot = std::move(g);
+    return NST_OK;
+}
+// the unweighted values of term t of the last closure, levels x 6 by map index (zeros: levels without the term or outside the
+// last level mask, maps without a weight, no closure yet)
+int map_term_losses(nst_ctx* ctx, int t, float* out, void* stream) {
+    NSTCHK(bind(ctx));
+    if (ctx->levels < 1) return fail(ctx, NST_E_STATE, "nst_job_configure has not been called");
+    if (!out) return fail(ctx, NST_E_ARG, "null argument");
+    hipStream_t s = enter(ctx, stream);
+    for (int i = 0; i < ctx->levels; ++i) {
+        const MapTerm& g = ctx->lv[i].map_term(t);
+        if (g.on()) HIPCHK(ctx, hipMemcpyAsync(out + 6 * i, g.vals, 6 * sizeof(float), hipMemcpyDeviceToDevice, s));
+        else HIPCHK(ctx, hipMemsetAsync(out + 6 * i, 0, 6 * sizeof(float), s));
+    }
+    mark(ctx, s);
+    return NST_OK;
+}
+
 }  // namespace
 
 // ================================================================================================
@@ -680,12 +758,10 @@ int nst_job_set_taps(nst_ctx* ctx, int content_index, unsigned style_mask, int u
     quiesce(ctx);
     drop_closure_state(ctx, true);
     ctx->taps = tp;
+    drop_map_terms(ctx);                    // (the style's maps of the old taps)
     for (int i = 0; i < ctx->levels; ++i) {
         LevelWs& L = ctx->lv[i];
         L.guide = Guidance();           // (sized for the old style set: nst_level_set_guidance again)
-        L.pm = PatchLevel();            // (the style's maps of the old taps: nst_level_set_patches again)
-        L.hist = HistLevel();           // (likewise: nst_level_set_histograms again)
-        L.remd = RemdLevel();           // (likewise: nst_level_set_remd again)
         free_tap_buffers(L);
         NSTCHK(alloc_tap_buffers(ctx, L));
     }
@@ -708,10 +784,7 @@ int nst_job_set_color(nst_ctx* ctx, int mode) {
                           [&] { drop_closure_state(ctx, true); }));
     // an anchor has the planes of the mode it was set under (nst_level_set_anchor): another mode drops it
     for (int i = 0; i < ctx->levels && channels != ctx->channels; ++i) ctx->lv[i].anc = AnchorLevel();
-    // the MRF term holds maps of the style image as the other mode's network saw it (nst_level_set_patches): dropped
-    for (int i = 0; i < ctx->levels; ++i) ctx->lv[i].pm = PatchLevel();
-    for (int i = 0; i < ctx->levels; ++i) ctx->lv[i].hist = HistLevel();     // (the histogram loss's style record likewise)
-    for (int i = 0; i < ctx->levels; ++i) ctx->lv[i].remd = RemdLevel();     // (and the relaxed EMD term's style maps)
+    drop_map_terms(ctx);                    // (maps of the style image as the other mode's network saw it)
     ctx->channels = channels;
     return NST_OK;
 }
@@ -726,9 +799,7 @@ int nst_job_set_pooling(nst_ctx* ctx, int mode) {
     if (mode != NST_POOL_MAX && mode != NST_POOL_AVG) return fail(ctx, NST_E_ARG, "mode must be NST_POOL_MAX or NST_POOL_AVG");
     quiesce(ctx);
     drop_closure_state(ctx, true);
-    for (int i = 0; i < ctx->levels; ++i) ctx->lv[i].pm = PatchLevel();      // (the MRF term's maps are the other network's)
-    for (int i = 0; i < ctx->levels; ++i) ctx->lv[i].hist = HistLevel();     // (and the histogram loss's style record)
-    for (int i = 0; i < ctx->levels; ++i) ctx->lv[i].remd = RemdLevel();     // (and the relaxed EMD term's style maps)
+    drop_map_terms(ctx);                    // (their style maps are the other network's)
     ctx->pool_avg = mode == NST_POOL_AVG ? 1 : 0;
     return NST_OK;
 }
@@ -1095,42 +1166,20 @@ int nst_level_set_patches(nst_ctx* ctx, int level, const float* style, int hs, i
     if (level < 0 || level >= ctx->levels) return fail(ctx, NST_E_ARG, "level out of range");
     LevelWs& L = ctx->lv[level];
     PatchLevel g;
-    bool on = false;
     if (style) {
         if (!weights) return fail(ctx, NST_E_ARG, "null argument");
-        for (int i = 0; i < 6; ++i) {
-            if (!(weights[i] >= 0.f) || std::isinf(weights[i])) return fail(ctx, NST_E_ARG, "the MRF weights must be finite and >= 0");
-            g.w[i] = weights[i];
-            on = on || weights[i] > 0.f;
-        }
+        for (int i = 0; i < 6; ++i) NSTCHK(take_weight(ctx, kMrfWords, weights, i, g));
         if (!(epsilon > 0.0) || std::isinf(epsilon)) return fail(ctx, NST_E_ARG, "the MRF epsilon must be finite and > 0");
         if (stride < 1 || stride > 8) return fail(ctx, NST_E_ARG, "the style stride must be 1..8");
     }
-    hipStream_t s = enter(ctx, stream);
-    if (on) {
-        if (ctx->conv_mode != 2) return fail(ctx, NST_E_STATE, "the MRF term runs in the f16x2 arithmetic only (NST_CONV unset)");
-        if (ctx->use_graph) return fail(ctx, NST_E_STATE, "the MRF term's launches are not captured: a context with use_graph takes no term");
-        if (L.guide.R > 0) return fail(ctx, NST_E_STATE, "a guided level takes no MRF term (nst_level_set_guidance(ctx, level, 0, ...) clears the guidance)");
-        if (hs < 16 || ws < 16) return fail(ctx, NST_E_ARG, "style image must be at least 16x16");
-        const unsigned style_mask = style_mask_of(ctx->taps);
-        int deepest = -1;
-        for (int i = 0; i < 6; ++i) {
-            if (!(g.w[i] > 0.f)) continue;
-            if (!((style_mask >> i) & 1u)) return fail(ctx, NST_E_ARG, "a positive MRF weight on a map that is not a style map of the job");
-            const int l = kTapLayer[i];
-            if (L.acts.h[l] < 3 || L.acts.w[l] < 3 || (hs >> kScale[l]) < 3 || (ws >> kScale[l]) < 3)
-                return fail(ctx, NST_E_ARG, "a weighted map or its style map is below 3x3");
-            deepest = l;
-        }
+    std::optional<Scratch> sc;
+    NSTCHK(begin_map_term(ctx, kMrfWords, L, g, style, hs, ws, stream, sc));
+    if (sc) {
+        hipStream_t s = sc->s;
         g.stride = stride; g.eps = epsilon; g.hs = hs; g.ws = ws;
-        Scratch sc(ctx, s);
-        NSTCHK(alloc_acts(ctx, sc.acts, hs, ws));
-        NSTCHK(forward(ctx, sc.acts, style, hs, ws, s, deepest, ctx->channels));
-        NSTCHK(g.mem.alloc(ctx, &g.vals, 6));
-        HIPCHK(ctx, hipMemsetAsync(g.vals, 0, 6 * sizeof(float), s));
         for (int i = 0; i < 6; ++i) {
             if (!(g.w[i] > 0.f)) continue;
-            const int l = kTapLayer[i], C = kCout[l], mh = sc.acts.h[l], mw = sc.acts.w[l];
+            const int l = kTapLayer[i], C = kCout[l], mh = sc->acts.h[l], mw = sc->acts.w[l];
             PatchDict& d = g.d[i];
             if (!pm_dict_geometry(mh, mw, C, stride, &d)) return fail(ctx, NST_E_ARG, "a weighted map or its style map is below 3x3");
             float* fs = nullptr; unsigned* amax = nullptr; float* rq = nullptr; unsigned char* packed = nullptr;
@@ -1142,20 +1191,14 @@ int nst_level_set_patches(nst_ctx* ctx, int level, const float* style, int hs, i
             NSTCHK(g.mem.alloc(ctx, &g.keys[i], n));
             NSTCHK(g.mem.alloc(ctx, &g.nn[i], n));
             NSTCHK(g.mem.alloc(ctx, &g.partial[i], (size_t)PM_VALUE_BLOCKS));
-            HIPCHK(ctx, hipMemcpyAsync(fs, sc.acts.act[l], fs_n * sizeof(float), hipMemcpyDeviceToDevice, s));
+            HIPCHK(ctx, hipMemcpyAsync(fs, sc->acts.act[l], fs_n * sizeof(float), hipMemcpyDeviceToDevice, s));
             HIPCHK(ctx, hipMemsetAsync(g.nn[i], 0, n * sizeof(int), s));
             d.fs = fs;
             HIPCHK(ctx, launch_pm_prepare(d, epsilon, amax, rq, packed, s));
             d.amax = amax; d.rq = rq; d.packed = packed;
         }
-        NSTCHK(sc.finish());       // (synchronises: the caller's image is free again when this returns)
-    } else {
-        g = PatchLevel();
     }
-    quiesce(ctx);
-    drop_closure_state(ctx, false);
-    L.pm = std::move(g);
-    return NST_OK;
+    return commit_map_term(ctx, sc, L.pm, g);
 }
 
 int nst_level_patches(const nst_ctx* ctx, int level, float* weights, int* stride, double* epsilon) {
@@ -1168,21 +1211,8 @@ int nst_level_patches(const nst_ctx* ctx, int level, float* weights, int* stride
     return NST_OK;
 }
 
-// the unweighted mrf_i of the last closure, levels x 6 by map index (zeros: levels without the term or outside the last level
-// mask, maps without a weight, no closure yet)
-int nst_job_patch_losses(nst_ctx* ctx, float* out, void* stream) {
-    NSTCHK(bind(ctx));
-    if (ctx->levels < 1) return fail(ctx, NST_E_STATE, "nst_job_configure has not been called");
-    if (!out) return fail(ctx, NST_E_ARG, "null argument");
-    hipStream_t s = enter(ctx, stream);
-    for (int i = 0; i < ctx->levels; ++i) {
-        const PatchLevel& g = ctx->lv[i].pm;
-        if (g.on()) HIPCHK(ctx, hipMemcpyAsync(out + 6 * i, g.vals, 6 * sizeof(float), hipMemcpyDeviceToDevice, s));
-        else HIPCHK(ctx, hipMemsetAsync(out + 6 * i, 0, 6 * sizeof(float), s));
-    }
-    mark(ctx, s);
-    return NST_OK;
-}
+// the unweighted mrf_i of the last closure (map_term_losses)
+int nst_job_patch_losses(nst_ctx* ctx, float* out, void* stream) { return map_term_losses(ctx, T_MRF, out, stream); }
 
 // the nn of the last closure of one weighted map of a level ((h - 2)(w - 2) int32 of the map; zeros before any closure)
 int nst_level_patch_matches(nst_ctx* ctx, int level, int map, int* idx_out, void* stream) {
@@ -1211,58 +1241,34 @@ int nst_level_set_histograms(nst_ctx* ctx, int level, const float* style, int hs
     if (level < 0 || level >= ctx->levels) return fail(ctx, NST_E_ARG, "level out of range");
     LevelWs& L = ctx->lv[level];
     HistLevel g;
-    bool on = false;
     if (style) {
         if (!weights) return fail(ctx, NST_E_ARG, "null argument");
-        for (int i = 0; i < 6; ++i) {
-            if (!(weights[i] >= 0.f) || std::isinf(weights[i])) return fail(ctx, NST_E_ARG, "the histogram weights must be finite and >= 0");
-            g.w[i] = weights[i];
-            on = on || weights[i] > 0.f;
-        }
+        for (int i = 0; i < 6; ++i) NSTCHK(take_weight(ctx, kHistWords, weights, i, g));
         if (bins < 2 || bins > 1024) return fail(ctx, NST_E_ARG, "the number of bins must be 2..1024");
     }
-    hipStream_t s = enter(ctx, stream);
-    if (on) {
-        if (ctx->use_graph) return fail(ctx, NST_E_STATE, "the histogram loss's launches are not captured: a context with use_graph takes no term");
-        if (L.guide.R > 0) return fail(ctx, NST_E_STATE, "a guided level takes no histogram loss (nst_level_set_guidance(ctx, level, 0, ...) clears the guidance)");
-        if (hs < 16 || ws < 16) return fail(ctx, NST_E_ARG, "style image must be at least 16x16");
-        const unsigned style_mask = style_mask_of(ctx->taps);
-        int deepest = -1;
-        for (int i = 0; i < 6; ++i) {
-            if (!(g.w[i] > 0.f)) continue;
-            if (!((style_mask >> i) & 1u)) return fail(ctx, NST_E_ARG, "a positive histogram weight on a map that is not a style map of the job");
-            deepest = kTapLayer[i];
-        }
+    std::optional<Scratch> sc;
+    NSTCHK(begin_map_term(ctx, kHistWords, L, g, style, hs, ws, stream, sc));
+    if (sc) {
+        hipStream_t s = sc->s;
         g.bins = bins;
-        Scratch sc(ctx, s);
-        NSTCHK(alloc_acts(ctx, sc.acts, hs, ws));
-        NSTCHK(forward(ctx, sc.acts, style, hs, ws, s, deepest, ctx->channels));
-        NSTCHK(g.mem.alloc(ctx, &g.vals, 6));
-        HIPCHK(ctx, hipMemsetAsync(g.vals, 0, 6 * sizeof(float), s));
         for (int i = 0; i < 6; ++i) {
             if (!(g.w[i] > 0.f)) continue;
             const int l = kTapLayer[i], C = kCout[l];
             const size_t cb = (size_t)C * bins;
-            g.Ns[i] = (size_t)sc.acts.h[l] * sc.acts.w[l];
+            g.Ns[i] = (size_t)sc->acts.h[l] * sc->acts.w[l];
             NSTCHK(g.mem.alloc(ctx, &g.s_lo_hi[i], (size_t)2 * C));
             NSTCHK(g.mem.alloc(ctx, &g.s_counts[i], cb));
             NSTCHK(g.mem.alloc(ctx, &g.lo_hi[i], (size_t)2 * C));
             NSTCHK(g.mem.alloc(ctx, &g.counts[i], cb));
             NSTCHK(g.mem.alloc(ctx, &g.ends[i], 2 * cb));
             NSTCHK(g.mem.alloc(ctx, &g.partial[i], (size_t)HIST_VALUE_BLOCKS));
-            HIPCHK(ctx, launch_hist_counts(sc.acts.act[l], g.Ns[i], C, bins, g.s_lo_hi[i], g.s_counts[i], s));
+            HIPCHK(ctx, launch_hist_counts(sc->acts.act[l], g.Ns[i], C, bins, g.s_lo_hi[i], g.s_counts[i], s));
             HIPCHK(ctx, hipMemsetAsync(g.lo_hi[i], 0, (size_t)2 * C * sizeof(float), s));
             HIPCHK(ctx, hipMemsetAsync(g.counts[i], 0, cb * sizeof(unsigned), s));
             HIPCHK(ctx, hipMemsetAsync(g.ends[i], 0, 2 * cb * sizeof(float), s));
         }
-        NSTCHK(sc.finish());       // (synchronises: the caller's image is free again when this returns)
-    } else {
-        g = HistLevel();
     }
-    quiesce(ctx);
-    drop_closure_state(ctx, false);
-    L.hist = std::move(g);
-    return NST_OK;
+    return commit_map_term(ctx, sc, L.hist, g);
 }
 
 int nst_level_histograms(const nst_ctx* ctx, int level, float* weights, int* bins) {
@@ -1274,21 +1280,8 @@ int nst_level_histograms(const nst_ctx* ctx, int level, float* weights, int* bin
     return NST_OK;
 }
 
-// the unweighted hist_i of the last closure, levels x 6 by map index (zeros: levels without the term or outside the last level
-// mask, maps without a weight, no closure yet)
-int nst_job_histogram_losses(nst_ctx* ctx, float* out, void* stream) {
-    NSTCHK(bind(ctx));
-    if (ctx->levels < 1) return fail(ctx, NST_E_STATE, "nst_job_configure has not been called");
-    if (!out) return fail(ctx, NST_E_ARG, "null argument");
-    hipStream_t s = enter(ctx, stream);
-    for (int i = 0; i < ctx->levels; ++i) {
-        const HistLevel& g = ctx->lv[i].hist;
-        if (g.on()) HIPCHK(ctx, hipMemcpyAsync(out + 6 * i, g.vals, 6 * sizeof(float), hipMemcpyDeviceToDevice, s));
-        else HIPCHK(ctx, hipMemsetAsync(out + 6 * i, 0, 6 * sizeof(float), s));
-    }
-    mark(ctx, s);
-    return NST_OK;
-}
+// the unweighted hist_i of the last closure (map_term_losses)
+int nst_job_histogram_losses(nst_ctx* ctx, float* out, void* stream) { return map_term_losses(ctx, T_HIST, out, stream); }
 
 // one weighted map of a level: the image side of the last closure (zeros before any closure), or the style's record
 static int hist_read(nst_ctx* ctx, int level, int map, bool style, float* lo_hi, unsigned* counts, float* ends, void* stream) {
@@ -1326,40 +1319,24 @@ int nst_level_set_remd(nst_ctx* ctx, int level, const float* style, int hs, int 
     if (level < 0 || level >= ctx->levels) return fail(ctx, NST_E_ARG, "level out of range");
     LevelWs& L = ctx->lv[level];
     RemdLevel g;
-    bool on = false;
     if (style) {
         if (!weights || !image_stride || !style_stride) return fail(ctx, NST_E_ARG, "null argument");
         for (int i = 0; i < 6; ++i) {
-            if (!(weights[i] >= 0.f) || std::isinf(weights[i])) return fail(ctx, NST_E_ARG, "the relaxed EMD weights must be finite and >= 0");
+            NSTCHK(take_weight(ctx, kRemdWords, weights, i, g));
             if (image_stride[i] < 1 || image_stride[i] > 256 || style_stride[i] < 1 || style_stride[i] > 256)
                 return fail(ctx, NST_E_ARG, "the sample strides must be 1..256");
-            g.w[i] = weights[i]; g.si[i] = image_stride[i]; g.ss[i] = style_stride[i];
-            on = on || weights[i] > 0.f;
+            g.si[i] = image_stride[i]; g.ss[i] = style_stride[i];
         }
         if (!(epsilon > 0.0) || std::isinf(epsilon)) return fail(ctx, NST_E_ARG, "the relaxed EMD epsilon must be finite and > 0");
     }
-    hipStream_t s = enter(ctx, stream);
-    if (on) {
-        if (ctx->conv_mode != 2) return fail(ctx, NST_E_STATE, "the relaxed EMD term runs in the f16x2 arithmetic only (NST_CONV unset)");
-        if (ctx->use_graph) return fail(ctx, NST_E_STATE, "the relaxed EMD term's launches are not captured: a context with use_graph takes no term");
-        if (L.guide.R > 0) return fail(ctx, NST_E_STATE, "a guided level takes no relaxed EMD term (nst_level_set_guidance(ctx, level, 0, ...) clears the guidance)");
-        if (hs < 16 || ws < 16) return fail(ctx, NST_E_ARG, "style image must be at least 16x16");
-        const unsigned style_mask = style_mask_of(ctx->taps);
-        int deepest = -1;
-        for (int i = 0; i < 6; ++i) {
-            if (!(g.w[i] > 0.f)) continue;
-            if (!((style_mask >> i) & 1u)) return fail(ctx, NST_E_ARG, "a positive relaxed EMD weight on a map that is not a style map of the job");
-            deepest = kTapLayer[i];
-        }
+    std::optional<Scratch> sc;
+    NSTCHK(begin_map_term(ctx, kRemdWords, L, g, style, hs, ws, stream, sc));
+    if (sc) {
+        hipStream_t s = sc->s;
         g.eps = epsilon; g.hs = hs; g.ws = ws;
-        Scratch sc(ctx, s);
-        NSTCHK(alloc_acts(ctx, sc.acts, hs, ws));
-        NSTCHK(forward(ctx, sc.acts, style, hs, ws, s, deepest, ctx->channels));
-        NSTCHK(g.mem.alloc(ctx, &g.vals, 6));
-        HIPCHK(ctx, hipMemsetAsync(g.vals, 0, 6 * sizeof(float), s));
         for (int i = 0; i < 6; ++i) {
             if (!(g.w[i] > 0.f)) continue;
-            const int l = kTapLayer[i], C = kCout[l], mh = sc.acts.h[l], mw = sc.acts.w[l];
+            const int l = kTapLayer[i], C = kCout[l], mh = sc->acts.h[l], mw = sc->acts.w[l];
             RemdSide& y = g.y[i];
             RemdSide x{};
             if (!remd_side_geometry(mh, mw, C, g.ss[i], &y) || !remd_side_geometry(L.acts.h[l], L.acts.w[l], C, g.si[i], &x))
@@ -1383,7 +1360,7 @@ int nst_level_set_remd(nst_ctx* ctx, int level, const float* style, int hs, int 
             NSTCHK(g.mem.alloc(ctx, &g.partial[i], (size_t)2 * REMD_VALUE_BLOCKS));
             NSTCHK(g.mem.alloc(ctx, &g.rec[i], 3));
             NSTCHK(g.mem.alloc(ctx, &g.side[i], 1));
-            HIPCHK(ctx, hipMemcpyAsync(fs, sc.acts.act[l], fs_n * sizeof(float), hipMemcpyDeviceToDevice, s));
+            HIPCHK(ctx, hipMemcpyAsync(fs, sc->acts.act[l], fs_n * sizeof(float), hipMemcpyDeviceToDevice, s));
             HIPCHK(ctx, hipMemsetAsync(g.nnA[i], 0, (size_t)n * sizeof(int), s));
             HIPCHK(ctx, hipMemsetAsync(g.nnB[i], 0, (size_t)m * sizeof(int), s));
             HIPCHK(ctx, hipMemsetAsync(g.rec[i], 0, 3 * sizeof(float), s));
@@ -1396,14 +1373,8 @@ int nst_level_set_remd(nst_ctx* ctx, int level, const float* style, int hs, int 
             HIPCHK(ctx, launch_remd_pack(y, packed, s));
             y.r = rq; y.packed = packed;
         }
-        NSTCHK(sc.finish());       // (synchronises: the caller's image is free again when this returns)
-    } else {
-        g = RemdLevel();
     }
-    quiesce(ctx);
-    drop_closure_state(ctx, false);
-    L.remd = std::move(g);
-    return NST_OK;
+    return commit_map_term(ctx, sc, L.remd, g);
 }
 
 int nst_level_remd(const nst_ctx* ctx, int level, float* weights, int* image_stride, int* style_stride, double* epsilon, int* hs, int* ws) {
@@ -1419,21 +1390,8 @@ int nst_level_remd(const nst_ctx* ctx, int level, float* weights, int* image_str
     return NST_OK;
 }
 
-// the unweighted remd_i of the last closure, levels x 6 by map index (zeros: levels without the term or outside the last level
-// mask, maps without a weight, no closure yet)
-int nst_job_remd_losses(nst_ctx* ctx, float* out, void* stream) {
-    NSTCHK(bind(ctx));
-    if (ctx->levels < 1) return fail(ctx, NST_E_STATE, "nst_job_configure has not been called");
-    if (!out) return fail(ctx, NST_E_ARG, "null argument");
-    hipStream_t s = enter(ctx, stream);
-    for (int i = 0; i < ctx->levels; ++i) {
-        const RemdLevel& g = ctx->lv[i].remd;
-        if (g.on()) HIPCHK(ctx, hipMemcpyAsync(out + 6 * i, g.vals, 6 * sizeof(float), hipMemcpyDeviceToDevice, s));
-        else HIPCHK(ctx, hipMemsetAsync(out + 6 * i, 0, 6 * sizeof(float), s));
-    }
-    mark(ctx, s);
-    return NST_OK;
-}
+// the unweighted remd_i of the last closure (map_term_losses)
+int nst_job_remd_losses(nst_ctx* ctx, float* out, void* stream) { return map_term_losses(ctx, T_REMD, out, stream); }
 
 // the matches and the side of the last closure of one weighted map of a level (nnA: n int32, nnB: m int32, side: one int32;
 // zeros before any closure; each nullable)

@@ -200,6 +200,25 @@ struct AnchorLevel {
     DevMem mem;
 };
 
+// What the per-map terms of one level share (PatchLevel, HistLevel, RemdLevel below; always in that order, NST_MAP_TERMS of
+// them): the weights by map index (0: the map has no term), the six unweighted values of the last closure (which the forward
+// half writes and the loss rows read), and the block's memory.
+struct MapTerm {
+    float w[6] = {};
+    float* vals = nullptr;
+    DevMem mem;
+    bool on() const {
+        for (float v : w) if (v > 0.f) return true;
+        return false;
+    }
+    // conv layer m carries the term
+    bool carries(int m) const {
+        const int i = tap_index_of(m);
+        return i >= 0 && w[i] > 0.f;
+    }
+};
+enum MapTermId { T_MRF = 0, T_HIST = 1, T_REMD = 2 };
+
 // The MRF term of one level (nst_level_set_patches; include/nst_hip.h has the definition), by map index: the weight (0: the
 // map has no term), the style's map with its dictionary (d[i]: fs, the absmax record, rq and the packed operand), the search
 // keys, nn and the value partials of the last closure, and the unweighted mrf_i (six floats, which the forward half writes
@@ -219,8 +238,7 @@ struct PatchGuide {
     DevMem mem;
 };
 
-struct PatchLevel {
-    float w[6] = {};
+struct PatchLevel : MapTerm {
     int stride = 1;
     double eps = 1e-5;
     int hs = 0, ws = 0;         // the style image of nst_level_set_patches: the size of the guidance's style planes
@@ -229,12 +247,6 @@ struct PatchLevel {
     unsigned long long* keys[6] = {};
     int* nn[6] = {};
     double* partial[6] = {};    // PM_VALUE_BLOCKS each
-    float* vals = nullptr;
-    DevMem mem;
-    bool on() const {
-        for (float v : w) if (v > 0.f) return true;
-        return false;
-    }
 };
 
 // The histogram loss of one level (nst_level_set_histograms; include/nst_hip.h has the definition), by map index: the weight
@@ -242,8 +254,7 @@ struct PatchLevel {
 // the image side of the last closure (lo_hi, counts, the table ends: C x bins x 2), the value partials, and the unweighted
 // hist_i (six floats, which the forward half writes and the loss rows read).  Data of one job with PatchLevel's life cycle:
 // everything is made by the setter, a closure allocates nothing.
-struct HistLevel {
-    float w[6] = {};
+struct HistLevel : MapTerm {
     int bins = 256;
     size_t Ns[6] = {};
     float* s_lo_hi[6] = {};
@@ -252,12 +263,6 @@ struct HistLevel {
     unsigned* counts[6] = {};
     float* ends[6] = {};
     double* partial[6] = {};    // HIST_VALUE_BLOCKS each
-    float* vals = nullptr;
-    DevMem mem;
-    bool on() const {
-        for (float v : w) if (v > 0.f) return true;
-        return false;
-    }
 };
 
 // The relaxed EMD term of one level (nst_level_set_remd; include/nst_hip.h has the definition), by map index: the weight (0: the
@@ -266,8 +271,7 @@ struct HistLevel {
 // size and the absmax record are the level's own map's); the keys of both directions, nnA, nnB, the stored cosines, the value
 // partials, (remd, rA, rB) and the side flag; and the unweighted remd_i (six floats, which the forward half writes and the loss
 // rows read).  Data of one job with PatchLevel's life cycle: everything is made by the setter, a closure allocates nothing.
-struct RemdLevel {
-    float w[6] = {};
+struct RemdLevel : MapTerm {
     int si[6] = {1, 1, 1, 1, 1, 1}, ss[6] = {1, 1, 1, 1, 1, 1};
     double eps = 1e-5;
     int hs = 0, ws = 0;         // the style image of nst_level_set_remd
@@ -284,12 +288,6 @@ struct RemdLevel {
     double* partial[6] = {};    // 2 REMD_VALUE_BLOCKS each
     float* rec[6] = {};         // (remd, rA, rB)
     int* side[6] = {};
-    float* vals = nullptr;
-    DevMem mem;
-    bool on() const {
-        for (float v : w) if (v > 0.f) return true;
-        return false;
-    }
 };
 
 // the level image and its gradient (levels >= 1), planar: channels (nst_job_set_color) x h x w floats each
@@ -310,6 +308,7 @@ struct LevelWs {
     PatchLevel pm;
     HistLevel hist;
     RemdLevel remd;
+    const MapTerm& map_term(int t) const { return t == T_MRF ? (const MapTerm&)pm : t == T_HIST ? (const MapTerm&)hist : remd; }
     ActSet acts;
     float* gbuf[2] = {};
     size_t gbuf_floats = 0;
@@ -439,7 +438,7 @@ struct nst_ctx {
         if (mom_on() && mom_slot(q)) return L.mom.row_bias(q);
         return gs_on() ? L.gs.row_bias(q) : nullptr;
     }
-    // bumped on entry to every call that changes what a closure computes (configure, taps, colour, pooling, style weights, Laplacian, matting, Gram shift, moments, targets, a level's anchor, a level's MRF term, a level's histogram loss, a level's relaxed EMD term), failure paths
+    // bumped on entry to every call that changes what a closure computes (configure, taps, colour, pooling, style weights, Laplacian, matting, Gram shift, moments, targets, a level's anchor, a level's per-map terms - nst::MapTerm), failure paths
     // included: an optimiser's remembered closure result is valid only under the epoch it was made in (nst_opt.cpp)
     unsigned long long closure_epoch = 0;
     // advanced on entry to every call that reads or writes the level workspaces (nst_closure*, nst_window_*,
@@ -565,12 +564,7 @@ struct Inject {
     bool content = false;            // or the content MSE gradient (closure only)
     const float* bias = nullptr;     // with S, a shifted Gram (nst_job_set_gram_shift) and / or the moment term: the row bias, dF = F * S + r
     const GuidedBwd* guided = nullptr; // guided Gram backward (R, t, S filled in): dF = sum_r t_r^2 F S_r, by a launch of its own
-    const PatchTerm* mrf = nullptr;  // the MRF term of the map (nst_level_set_patches): its gradient joins the addend of the launch
-    float mrf_coef = 0.f;
-    const HistTerm* hist = nullptr;  // the histogram loss of the map (nst_level_set_histograms): likewise, after the MRF term
-    float hist_coef = 0.f;
-    const RemdTerm* remd = nullptr;  // the relaxed EMD term of the map (nst_level_set_remd): likewise, after the histogram loss
-    float remd_coefA = 0.f, remd_coefB = 0.f;
+    // (the per-map terms of a level - MapTerm - are not injected: backward() takes the level and asks it per map)
 };
 struct ContentJob { const float* target; size_t n; float coef; double* partial; };
 // channels = 1: x is a luminance plane u, conv1_1 sees x_c = u - mean_c (nst_job_set_color)
@@ -579,8 +573,10 @@ int forward(nst_ctx* ctx, ActSet& a, const float* x, int h, int w, hipStream_t s
 // inj[l] describes what enters at conv layer l; gbuf: two NHWC scratch buffers of the largest size.  The chain starts at
 // layer `top` (nothing above it is read); `top_mask` = false: the top map is pre-ReLU (its gradient passes unmasked).
 // channels = 1: gx is the gradient of a luminance plane (the sum over the three channels)
+// `terms`: the level (whose maps `a` holds) whose per-map terms join the walk - the gradient of every term a map carries joins
+// the addend of that map's launch; nullptr: none (the stand-alone callers)
 int backward(nst_ctx* ctx, ActSet& a, const Inject* inj, const ContentJob* cj, float* gbuf0, float* gbuf1, float* gx,
-             int h, int w, hipStream_t s, int top = NL - 1, bool top_mask = true, int channels = 3);
+             int h, int w, hipStream_t s, int top = NL - 1, bool top_mask = true, int channels = 3, const LevelWs* terms = nullptr);
 // The Gram of one map, the one recipe of every caller outside the batched closure: the partial products (launch_gram_partial,
 // gram_nsplit(C, N) splits, timed as K_GRAM) and the finish pass over their slabs (timed as K_OTHER).
 struct GramOperand {

@@ -354,6 +354,7 @@ hipError_t launch_flow_tvl1_estimate(const float* from, const float* to, const F
                                      int warps, int iterations, float* flow, float* ws, hipStream_t stream);
 
 // loss assembly -----------------------------------------------------------------------------------
+constexpr int NST_MAP_TERMS = 3;     // the per-map terms of a level: MRF, histogram loss, relaxed EMD - always in this order
 struct LevelLossInputs {
     const double* content_partial;   // MSE_BLOCKS doubles
     size_t content_n;
@@ -374,16 +375,11 @@ struct LevelLossInputs {
     float tmp_gamma;
     double tmp_n;
     float* tmp_out;
-    // MRF term (nst_level_set_patches), a level's own: the six unweighted mrf_i by map index as the forward half left them
-    // (nullptr: the level has no term and its row is what it is without it), and the weights (0: the map has no term)
-    float* mrf_vals;
-    float mrf_w[6];
-    // histogram loss (nst_level_set_histograms), a level's own, in the same form: the six unweighted hist_i and the weights
-    float* hist_vals;
-    float hist_w[6];
-    // relaxed EMD term (nst_level_set_remd), a level's own, in the same form: the six unweighted remd_i and the weights
-    float* remd_vals;
-    float remd_w[6];
+    // the per-map terms, a level's own, in the order the row adds them: MRF (nst_level_set_patches), histogram loss
+    // (nst_level_set_histograms), relaxed EMD (nst_level_set_remd).  Each: the six unweighted values by map index as the
+    // forward half left them (nullptr: the level has no such term and its row is what it is without it), and the weights (0:
+    // the map has no term)
+    struct MapTerm { float* vals; float w[6]; } term[NST_MAP_TERMS];
 };
 struct LossAssembly {
     LevelLossInputs lv[8];

@@ -653,9 +653,8 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(LossAssembly la) {
         if (la.mat_gamma > 0.f && threadIdx.x == 0) la.mat_out[l] = 0.f;
         if (la.mom_on && threadIdx.x < 12) la.mom_out[12 * l + threadIdx.x] = 0.f;
         if (in.tmp_gamma > 0.f && threadIdx.x == 0) in.tmp_out[0] = 0.f;
-        if (in.mrf_vals && threadIdx.x < 6) in.mrf_vals[threadIdx.x] = 0.f;
-        if (in.hist_vals && threadIdx.x < 6) in.hist_vals[threadIdx.x] = 0.f;
-        if (in.remd_vals && threadIdx.x < 6) in.remd_vals[threadIdx.x] = 0.f;
+        for (int t = 0; t < NST_MAP_TERMS; ++t)
+            if (in.term[t].vals && threadIdx.x < 6) in.term[t].vals[threadIdx.x] = 0.f;
         return;
     }
     double v[7];
@@ -770,20 +769,13 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(LossAssembly la) {
             in.tmp_out[0] = tmp;
             total = total + in.tmp_gamma * tmp;
         }
-        if (in.mrf_vals) {
-            // (... + gamma tmp) + sum_i w_i mrf_i over the maps with a weight, in ascending map order: every product and sum rounded
+        for (int t = 0; t < NST_MAP_TERMS; ++t) {
+            // (... + gamma tmp) + sum_i w_i mrf_i + sum_i w_i hist_i + sum_i w_i remd_i: term after term, each over its maps with
+            // a weight in ascending map order, every product and sum rounded
+            const LevelLossInputs::MapTerm& m = in.term[t];
+            if (!m.vals) continue;
             for (int i = 0; i < 6; ++i)
-                if (in.mrf_w[i] > 0.f) total = total + in.mrf_w[i] * in.mrf_vals[i];
-        }
-        if (in.hist_vals) {
-            // (... + sum_i w_i mrf_i) + sum_i w_i hist_i, likewise
-            for (int i = 0; i < 6; ++i)
-                if (in.hist_w[i] > 0.f) total = total + in.hist_w[i] * in.hist_vals[i];
-        }
-        if (in.remd_vals) {
-            // (... + sum_i w_i hist_i) + sum_i w_i remd_i, likewise
-            for (int i = 0; i < 6; ++i)
-                if (in.remd_w[i] > 0.f) total = total + in.remd_w[i] * in.remd_vals[i];
+                if (m.w[i] > 0.f) total = total + m.w[i] * m.vals[i];
         }
         la.out[4 * l + 0] = total;
         la.out[4 * l + 1] = content;

@@ -575,6 +575,25 @@ class StyleEngine:
                    "nst_job_temporal_losses")
         return out
 
+    # ---- what the per-map terms (MRF, histogram loss, relaxed EMD) share --------------------------------------
+    def _level_style(self, level: int, style: torch.Tensor) -> torch.Tensor:
+        """The style image a level's per-map term is made from: checked, contiguous."""
+        ch = self.channels
+        if style.dim() < 3 or style.numel() != ch * style.shape[-2] * style.shape[-1]:
+            raise NstError(f"the style image of level {level} must have shape ({ch},hs,ws), got {tuple(style.shape)}")
+        style = style.contiguous()
+        _chk_dev(style, self.device)
+        return style
+
+    def _map_term_losses(self, symbol: str) -> torch.Tensor:
+        out = torch.empty((self.levels, 6), dtype=torch.float32, device=self.device)
+        _lib.check(self.ctx, getattr(self.lib, symbol)(self.ctx, _ptr(out), _stream(self.device)), symbol)
+        return out
+
+    def _clear_levels(self, setter, level: Optional[int]) -> None:
+        for l in (range(self.levels) if level is None else (level,)):
+            setter(l, None)
+
     # ---- the MRF style term (nst_level_set_patches; patch_match.py is the driver) ---------------------------
     def set_patches(self, level: int, style: Optional[torch.Tensor], weights=None, stride: int = 1,
                     epsilon: float = _mrf.DEFAULT_EPSILON) -> None:
@@ -590,19 +609,14 @@ class StyleEngine:
                                                                 _stream(self.device)), "nst_level_set_patches")
             return
         w, stride, eps, _ = setting
-        ch = self.channels
-        if style.dim() < 3 or style.numel() != ch * style.shape[-2] * style.shape[-1]:
-            raise NstError(f"the style image of level {level} must have shape ({ch},hs,ws), got {tuple(style.shape)}")
-        style = style.contiguous()
-        _chk_dev(style, self.device)
+        style = self._level_style(level, style)
         _lib.check(self.ctx, self.lib.nst_level_set_patches(self.ctx, int(level), _ptr(style), int(style.shape[-2]), int(style.shape[-1]),
                                                             (C.c_float * 6)(*w), stride, eps, _stream(self.device)),
                    "nst_level_set_patches")
 
     def clear_patches(self, level: Optional[int] = None) -> None:
         """No MRF term on one level, or (None) on any configured level."""
-        for l in (range(self.levels) if level is None else (level,)):
-            self.set_patches(l, None)
+        self._clear_levels(self.set_patches, level)
 
     def patches_setting(self, level: int):
         """(weights (6,), stride, epsilon) of a level (nst_level_patches), or None when the level has no term."""
@@ -614,9 +628,7 @@ class StyleEngine:
     def patch_losses(self) -> torch.Tensor:
         """(levels, 6) device tensor: the unweighted mrf_i of the last closure by map index (nst_job_patch_losses); zeros for
         maps without the term and levels outside the last level mask."""
-        out = torch.empty((self.levels, 6), dtype=torch.float32, device=self.device)
-        _lib.check(self.ctx, self.lib.nst_job_patch_losses(self.ctx, _ptr(out), _stream(self.device)), "nst_job_patch_losses")
-        return out
+        return self._map_term_losses("nst_job_patch_losses")
 
     def patch_matches(self, level: int, map: int) -> torch.Tensor:
         """(h-2, w-2) int32 device tensor: the nearest style patch of every patch of map index `map` of a level, as the last
@@ -769,19 +781,14 @@ class StyleEngine:
                                                                    _stream(self.device)), "nst_level_set_histograms")
             return
         w, bins, _ = setting
-        ch = self.channels
-        if style.dim() < 3 or style.numel() != ch * style.shape[-2] * style.shape[-1]:
-            raise NstError(f"the style image of level {level} must have shape ({ch},hs,ws), got {tuple(style.shape)}")
-        style = style.contiguous()
-        _chk_dev(style, self.device)
+        style = self._level_style(level, style)
         _lib.check(self.ctx, self.lib.nst_level_set_histograms(self.ctx, int(level), _ptr(style), int(style.shape[-2]),
                                                                int(style.shape[-1]), (C.c_float * 6)(*w), bins, _stream(self.device)),
                    "nst_level_set_histograms")
 
     def clear_histograms(self, level: Optional[int] = None) -> None:
         """No histogram loss on one level, or (None) on any configured level."""
-        for l in (range(self.levels) if level is None else (level,)):
-            self.set_histograms(l, None)
+        self._clear_levels(self.set_histograms, level)
 
     def histograms_setting(self, level: int):
         """(weights (6,), bins) of a level (nst_level_histograms), or None when the level has no term."""
@@ -793,9 +800,7 @@ class StyleEngine:
     def histogram_losses(self) -> torch.Tensor:
         """(levels, 6) device tensor: the unweighted hist_i of the last closure by map index (nst_job_histogram_losses); zeros
         for maps without the term and levels outside the last level mask."""
-        out = torch.empty((self.levels, 6), dtype=torch.float32, device=self.device)
-        _lib.check(self.ctx, self.lib.nst_job_histogram_losses(self.ctx, _ptr(out), _stream(self.device)), "nst_job_histogram_losses")
-        return out
+        return self._map_term_losses("nst_job_histogram_losses")
 
     def histogram_tables(self, level: int, map: int):
         """(lo_hi (C,2) float32, counts (C,B) int32, ends (C,B,2) float32) device tensors: the image side of map index `map`
@@ -884,19 +889,14 @@ class StyleEngine:
             return
         w, _, eps, _ = setting
         si, ss = _remd.check_strides(image_strides, "image_strides"), _remd.check_strides(style_strides, "style_strides")
-        ch = self.channels
-        if style.dim() < 3 or style.numel() != ch * style.shape[-2] * style.shape[-1]:
-            raise NstError(f"the style image of level {level} must have shape ({ch},hs,ws), got {tuple(style.shape)}")
-        style = style.contiguous()
-        _chk_dev(style, self.device)
+        style = self._level_style(level, style)
         _lib.check(self.ctx, self.lib.nst_level_set_remd(self.ctx, int(level), _ptr(style), int(style.shape[-2]), int(style.shape[-1]),
                                                          (C.c_float * 6)(*w), (C.c_int * 6)(*si), (C.c_int * 6)(*ss), eps,
                                                          _stream(self.device)), "nst_level_set_remd")
 
     def clear_remd(self, level: Optional[int] = None) -> None:
         """No relaxed EMD term on one level, or (None) on any configured level."""
-        for l in (range(self.levels) if level is None else (level,)):
-            self.set_remd(l, None)
+        self._clear_levels(self.set_remd, level)
 
     def remd_setting(self, level: int):
         """(weights (6,), image strides (6,), style strides (6,), epsilon, (hs, ws) of the style image) of a level
@@ -913,9 +913,7 @@ class StyleEngine:
     def remd_losses(self) -> torch.Tensor:
         """(levels, 6) device tensor: the unweighted remd_i of the last closure by map index (nst_job_remd_losses); zeros for
         maps without the term and levels outside the last level mask."""
-        out = torch.empty((self.levels, 6), dtype=torch.float32, device=self.device)
-        _lib.check(self.ctx, self.lib.nst_job_remd_losses(self.ctx, _ptr(out), _stream(self.device)), "nst_job_remd_losses")
-        return out
+        return self._map_term_losses("nst_job_remd_losses")
 
     def remd_matches(self, level: int, map: int):
         """(nnA (n,) int32, nnB (m,) int32, side: 0 = A or 1 = B) of map index `map` of a level as the last closure found them

@@ -6,24 +6,16 @@ here raises ValueError before any GPU work."""
 import math
 import numbers
 
+from . import map_term_modes as _terms
+from .map_term_modes import MAX_LEVELS, _weight  # noqa: F401
 from .mrf_modes import MAP_SCALE
-from .taps import DEFAULT_STYLE_INDICES, NUM_MAPS, map_index, map_index_texts
+from .taps import NUM_MAPS
 
-_MAP_TEXTS = map_index_texts("remd_weight")
 DEFAULT_SAMPLES = 4096          # a setting, not a measurement: the search costs n m C, so cost grows with its square
 DEFAULT_EPSILON = 1e-5
 MAX_STRIDE = 256
 DEFAULT_MAPS = (1, 2, 3)        # relu2_1, relu3_1 and relu4_1: what a plain number weighs
-MAX_LEVELS = 8
-
-
-def _weight(v, what):
-    if isinstance(v, bool) or not isinstance(v, numbers.Real):
-        raise ValueError(f"{what} must be a finite number >= 0, not {v!r}")
-    w = float(v)
-    if not math.isfinite(w) or w < 0.0:
-        raise ValueError(f"{what} must be a finite number >= 0, not {v!r}")
-    return w
+_WORDS = _terms.words("remd_weight", "remd_levels", DEFAULT_MAPS, "none of relu2_1, relu3_1, relu4_1 (indices 1, 2, 3)")
 
 
 def check_samples(samples=DEFAULT_SAMPLES):
@@ -75,66 +67,14 @@ def stride_for(hm, wm, samples=DEFAULT_SAMPLES):
 
 
 def normalize_weights(value=None, style_indices=None, use_relu=None):
-    """Six weights >= 0 by map index of Vgg19.layer_names.  `value`: None or 0 (zeros); a number (that weight on those of
-    relu2_1, relu3_1 and relu4_1 - indices 1, 2, 3 - that are style maps of the job; an error when there are none); a sequence
-    of six numbers; or a dict {map index or name: number} (the rest 0).  `style_indices`: the job's style maps (None: the
-    reference's 0, 1, 2, 3, 5 for a number, and a sequence or a dict is not checked against it); `use_relu`: the flavour whose
-    map names a dict may use (None: either).
-    ValueError for a negative or non-finite number, a wrong length, an unknown map, or a positive weight on a map that is
-    not a style map of the job."""
-    known = style_indices is not None
-    style = sorted(DEFAULT_STYLE_INDICES) if not known else sorted({int(i) for i in style_indices})
-    if value is None:
-        return (0.0,) * NUM_MAPS
-    if isinstance(value, (str, bytes, set, frozenset)):
-        raise ValueError(f"remd_weight: expected a number, {NUM_MAPS} numbers or a dict, got {value!r}")
-    if isinstance(value, (bool, numbers.Number)):
-        w = _weight(value, "remd_weight")
-        if w == 0.0:
-            return (0.0,) * NUM_MAPS
-        on = [i for i in DEFAULT_MAPS if i in style]
-        if not on:
-            raise ValueError(f"remd_weight: none of relu2_1, relu3_1, relu4_1 (indices 1, 2, 3) is a style map of the job {style}; "
-                             f"give the weights by map")
-        return tuple(w if i in on else 0.0 for i in range(NUM_MAPS))
-    if isinstance(value, dict):
-        ws = [0.0] * NUM_MAPS
-        for key, v in value.items():
-            ws[map_index(key, use_relu, _MAP_TEXTS)] = _weight(v, f"remd_weight of {key!r}")
-    else:
-        try:
-            items = list(value)
-        except TypeError:
-            raise ValueError(f"remd_weight: expected a number, {NUM_MAPS} numbers or a dict, got {value!r}") from None
-        if len(items) != NUM_MAPS:
-            raise ValueError(f"remd_weight: expected {NUM_MAPS} numbers (one per feature map), got {len(items)}")
-        ws = [_weight(v, f"remd_weight entry {i}") for i, v in enumerate(items)]
-    for i, w in enumerate(ws):
-        if known and w > 0.0 and i not in style:
-            raise ValueError(f"remd_weight: map {i} has a positive weight but is not a style map of the job {style}")
-    return tuple(ws)
+    """Six weights >= 0 by map index (map_term_modes.normalize_weights has the forms of `value`); a plain number weighs
+    those of relu2_1, relu3_1 and relu4_1 - indices 1, 2, 3 - that are style maps of the job."""
+    return _terms.normalize_weights(_WORDS, value, style_indices, use_relu)
 
 
 def normalize_levels(levels=None, levels_num=None):
-    """None (every level), or the sorted tuple of distinct level indices, as StyleEngine numbers them (0 = the full
-    resolution).  `levels_num` (None: not checked beyond 0..7): the job's number of levels."""
-    if levels is None:
-        return None
-    if isinstance(levels, (str, bytes, dict)) or isinstance(levels, (bool, numbers.Number)):
-        raise ValueError(f"remd_levels: expected None or a collection of level indices, got {levels!r}")
-    try:
-        items = list(levels)
-    except TypeError:
-        raise ValueError(f"remd_levels: expected None or a collection of level indices, got {levels!r}") from None
-    top = MAX_LEVELS if levels_num is None else int(levels_num)
-    out = set()
-    for v in items:
-        if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not 0 <= int(v) < top:
-            raise ValueError(f"remd_levels: {v!r} is not a level index 0..{top - 1}")
-        out.add(int(v))
-    if not out:
-        raise ValueError("remd_levels: the collection is empty (None means every level)")
-    return tuple(sorted(out))
+    """None (every level), or the sorted tuple of distinct level indices (map_term_modes.normalize_levels)."""
+    return _terms.normalize_levels(_WORDS, levels, levels_num)
 
 
 def normalize_remd(remd_weight=None, remd_samples=DEFAULT_SAMPLES, remd_epsilon=DEFAULT_EPSILON, remd_levels=None, style_indices=None,
@@ -154,14 +94,7 @@ def normalize_remd(remd_weight=None, remd_samples=DEFAULT_SAMPLES, remd_epsilon=
 def check_exclusive(setting, regions=None, stripes: bool = False, extra_styles=None) -> None:
     """The term does not combine with several style images (the union of the styles' samples is a follow-up), with spatial
     control (guided levels) or with stripe sharding."""
-    if setting is None:
-        return
-    if extra_styles:
-        raise ValueError("remd_weight cannot be combined with extra_styles")
-    if regions is not None:
-        raise ValueError("remd_weight cannot be combined with content_regions / style_regions")
-    if stripes:
-        raise ValueError("remd_weight cannot be combined with stripe sharding")
+    _terms.check_exclusive(_WORDS, setting, regions, stripes, extra_styles)
 
 
 def level_strides(setting, level_shapes, style_shapes):

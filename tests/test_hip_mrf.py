@@ -429,10 +429,10 @@ def _restated_closure(x, targets, weights, cw, sw, tvw, taps, decisions, w, nn, 
     return total.detach(), x.grad.detach(), rows, terms
 
 
-@pytest.mark.parametrize("case", ["content map is an MRF map", "MRF map at the top of the chain"])
-def test_path_other_taps(eng, vgg_weights, case):
-    """style_mask 0x3F with the term on conv4_2, the content map (content gradient and the term in one addend, beside the Gram
-    second source); and style maps ending at relu4_1 with the term on it: the top-of-chain launch's addend."""
+OTHER_TAPS = ["content map is an MRF map", "MRF map at the top of the chain"]
+
+
+def _path_other_taps(e, vgg_weights, case):
     from test_hip_style_blend import device_decisions as decisions_of, restated_targets
     if case.startswith("content"):
         taps, w = (4, (0, 1, 2, 3, 4, 5)), (0.0, 0.0, 400.0, 0.0, 200.0, 0.0)
@@ -441,22 +441,22 @@ def test_path_other_taps(eng, vgg_weights, case):
     c, s, xt = _job("64x96_L1")
     prep = cpu_ref.prepare_img
     try:
-        eng.configure(2, 64, 96)
-        eng.set_taps(taps[0], list(taps[1]))
+        e.configure(2, 64, 96)
+        e.set_taps(taps[0], list(taps[1]))
         tg = []
         for i in range(2):
-            eng.set_targets(i, dev(prep(c[i])), dev(prep(s[i])))
+            e.set_targets(i, dev(prep(c[i])), dev(prep(s[i])))
             t = restated_targets(prep(c[i]), [prep(s[i])], ((1.0,) * 6,), vgg_weights, taps)
             with torch.no_grad():
                 sf = cpu_ref.vgg19_features(prep(s[i]), vgg_weights)
             t.mrf_style = {k: sf[k].detach() for k in range(6) if w[k] > 0}
             tg.append(t)
-        _set_patches(eng, s, w)
+        _set_patches(e, s, w)
         xd = dev(xt)
         for name, (cw, sw, tvw) in (("style", (0.0, SW, 0.0)), ("all", (CW, SW, TVW))):
-            grad, losses = eng.closure(xd, cw, sw, tvw)
-            dec = decisions_of(eng, xd, vgg_weights, taps)
-            nn = {l: {k: eng.patch_matches(l, k).cpu() for k in range(6) if w[k] > 0} for l in range(2)}
+            grad, losses = e.closure(xd, cw, sw, tvw)
+            dec = decisions_of(e, xd, vgg_weights, taps)
+            nn = {l: {k: e.patch_matches(l, k).cpu() for k in range(6) if w[k] > 0} for l in range(2)}
             losses = losses.cpu().numpy()
             loss, g_ref, rows, terms = _restated_closure(xt, tg, vgg_weights, cw, sw, tvw, taps, dec, w, nn)
             e_l = abs(float(losses[-1]) - float(loss)) / abs(float(loss))
@@ -470,7 +470,21 @@ def test_path_other_taps(eng, vgg_weights, case):
             check_rows(losses[:-1].reshape(2, 4), np.array(rows), 2e-5, cw, sw, tvw)
             assert e_g < 2e-5, (case, name, e_g)
     finally:
-        eng.reset_taps()
+        e.reset_taps()
+
+
+@pytest.mark.parametrize("case", OTHER_TAPS)
+def test_path_other_taps(eng, vgg_weights, case):
+    """style_mask 0x3F with the term on conv4_2, the content map (content gradient and the term in one addend, beside the Gram
+    second source); and style maps ending at relu4_1 with the term on it: the top-of-chain launch's addend."""
+    _path_other_taps(eng, vgg_weights, case)
+
+
+@pytest.mark.parametrize("case", OTHER_TAPS)
+def test_path_other_taps_per_level_walker(eng_per_level, vgg_weights, case):
+    """The same two cases on the per-level walker - its content-map and top-of-chain sites with the term on them - to the
+    same bounds."""
+    _path_other_taps(eng_per_level, vgg_weights, case)
 
 
 def test_path_luminance(eng, vgg_weights, monkeypatch):

@@ -426,10 +426,7 @@ def test_path_pre_relu_taps(eng, vgg_weights, monkeypatch):
         eng.reset_taps()
 
 
-def test_path_beside_the_mrf_and_the_histogram_terms_on_the_same_map(eng, vgg_weights, monkeypatch):
-    """relu4_1 carries all three terms: the MRF term's addend first, the histogram loss added to it, then this term.  The
-    oracles of tests/test_hip_mrf.py and tests/test_hip_hist.py are patched first and handed the device's decisions; this
-    one wraps them, as the loss row adds the term last."""
+def _path_beside_the_mrf_and_the_histogram_terms_on_the_same_map(e, vgg_weights, monkeypatch):
     import test_hip_hist as th
     from test_hip_mrf import PatchedOracle as MrfOracle, W_34
     c, s, xt = _job("64x96_L1")
@@ -439,21 +436,33 @@ def test_path_beside_the_mrf_and_the_histogram_terms_on_the_same_map(eng, vgg_we
     strides = _strides(2)
     patched = PatchedOracle(monkeypatch, W_23, strides)
     tg = oracle_targets(c, s, vgg_weights)
-    _setup(eng, c, s, W_23, strides)
+    _setup(e, c, s, W_23, strides)
     for i in range(2):
-        eng.set_patches(i, dev(cpu_ref.prepare_img(s[i])), W_34, 1, EPS)
-    th._set_histograms(eng, s, w_hist)
+        e.set_patches(i, dev(cpu_ref.prepare_img(s[i])), W_34, 1, EPS)
+    th._set_histograms(e, s, w_hist)
     try:
-        hist.given = th._hand_over(eng, dev(xt), w_hist, th.BINS, "beside remd")
-        mrf.nn = {l: {i: eng.patch_matches(l, i).cpu() for i in range(6) if W_34[i] > 0} for l in range(2)}
-        patched.given = _matches_of(eng, W_23, "beside MRF and hist")
+        hist.given = th._hand_over(e, dev(xt), w_hist, th.BINS, "beside remd")
+        mrf.nn = {l: {i: e.patch_matches(l, i).cpu() for i in range(6) if W_34[i] > 0} for l in range(2)}
+        patched.given = _matches_of(e, W_23, "beside MRF and hist")
         cache = {}
         _the_term_counts(patched, xt, tg, vgg_weights, "beside MRF and hist", cache, lo=0.05)
-        closure_vs_oracle_under_equal_decisions(eng, xt, tg, vgg_weights, "remd beside MRF and hist", terms=NO_TV, own_cache=cache)
-        closure_vs_oracle_under_equal_decisions(eng, xt, tg, vgg_weights, "remd beside MRF and hist", terms=TV_ONLY)
+        closure_vs_oracle_under_equal_decisions(e, xt, tg, vgg_weights, "remd beside MRF and hist", terms=NO_TV, own_cache=cache)
+        closure_vs_oracle_under_equal_decisions(e, xt, tg, vgg_weights, "remd beside MRF and hist", terms=TV_ONLY)
     finally:
-        eng.clear_patches()
-        eng.clear_histograms()
+        e.clear_patches()
+        e.clear_histograms()
+
+
+def test_path_beside_the_mrf_and_the_histogram_terms_on_the_same_map(eng, vgg_weights, monkeypatch):
+    """relu4_1 carries all three terms: the MRF term's addend first, the histogram loss added to it, then this term.  The
+    oracles of tests/test_hip_mrf.py and tests/test_hip_hist.py are patched first and handed the device's decisions; this
+    one wraps them, as the loss row adds the term last."""
+    _path_beside_the_mrf_and_the_histogram_terms_on_the_same_map(eng, vgg_weights, monkeypatch)
+
+
+def test_path_beside_the_mrf_and_the_histogram_terms_on_the_same_map_per_level_walker(eng_per_level, vgg_weights, monkeypatch):
+    """The same on the per-level walker (the mid-chain site with all three terms on one map), to the same bounds."""
+    _path_beside_the_mrf_and_the_histogram_terms_on_the_same_map(eng_per_level, vgg_weights, monkeypatch)
 
 
 # -- taps beyond cpu_ref.level_loss: test_hip_style_blend's restatement with the term added
@@ -486,10 +495,10 @@ def _restated_closure(x, targets, weights, cw, sw, tvw, taps, decisions, w, give
     return total.detach(), x.grad.detach(), rows, terms
 
 
-@pytest.mark.parametrize("case", ["content map is a weighted map", "weighted map at the top of the chain"])
-def test_path_other_taps(eng, vgg_weights, case):
-    """style_mask 0x3F with the term on conv4_2, the content map (content gradient and the term in one addend, beside the Gram
-    second source); and style maps ending at relu4_1 with the term on it: the top-of-chain launch's addend."""
+OTHER_TAPS = ["content map is a weighted map", "weighted map at the top of the chain"]
+
+
+def _path_other_taps(e, vgg_weights, case):
     from test_hip_style_blend import device_decisions as decisions_of, restated_targets
     if case.startswith("content"):
         taps, w = (4, (0, 1, 2, 3, 4, 5)), (0.0, 0.0, 7e4, 0.0, 7e4, 0.0)
@@ -498,22 +507,22 @@ def test_path_other_taps(eng, vgg_weights, case):
     c, s, xt = _job("64x96_L1")
     prep = cpu_ref.prepare_img
     try:
-        eng.configure(2, 64, 96)
-        eng.set_taps(taps[0], list(taps[1]))
+        e.configure(2, 64, 96)
+        e.set_taps(taps[0], list(taps[1]))
         tg = []
         for i in range(2):
-            eng.set_targets(i, dev(prep(c[i])), dev(prep(s[i])))
+            e.set_targets(i, dev(prep(c[i])), dev(prep(s[i])))
             t = restated_targets(prep(c[i]), [prep(s[i])], ((1.0,) * 6,), vgg_weights, taps)
             with torch.no_grad():
                 sf = cpu_ref.vgg19_features(prep(s[i]), vgg_weights)
             t.remd_style = {k: sf[k].detach() for k in range(6) if w[k] > 0}
             tg.append(t)
-        _set_remd(eng, s, w, _strides(2))
+        _set_remd(e, s, w, _strides(2))
         xd = dev(xt)
         for name, (cw, sw, tvw) in (("style", (0.0, SW, 0.0)), ("all", (CW, SW, TVW))):
-            grad, losses = eng.closure(xd, cw, sw, tvw)
-            dec = decisions_of(eng, xd, vgg_weights, taps)
-            given = _matches_of(eng, w, case)
+            grad, losses = e.closure(xd, cw, sw, tvw)
+            dec = decisions_of(e, xd, vgg_weights, taps)
+            given = _matches_of(e, w, case)
             losses = losses.cpu().numpy()
             loss, g_ref, rows, terms = _restated_closure(xt, tg, vgg_weights, cw, sw, tvw, taps, dec, w, given)
             e_l = abs(float(losses[-1]) - float(loss)) / abs(float(loss))
@@ -527,7 +536,21 @@ def test_path_other_taps(eng, vgg_weights, case):
             check_rows(losses[:-1].reshape(2, 4), np.array(rows), 2e-5, cw, sw, tvw)
             assert e_g < 2e-5, (case, name, e_g)
     finally:
-        eng.reset_taps()
+        e.reset_taps()
+
+
+@pytest.mark.parametrize("case", OTHER_TAPS)
+def test_path_other_taps(eng, vgg_weights, case):
+    """style_mask 0x3F with the term on conv4_2, the content map (content gradient and the term in one addend, beside the Gram
+    second source); and style maps ending at relu4_1 with the term on it: the top-of-chain launch's addend."""
+    _path_other_taps(eng, vgg_weights, case)
+
+
+@pytest.mark.parametrize("case", OTHER_TAPS)
+def test_path_other_taps_per_level_walker(eng_per_level, vgg_weights, case):
+    """The same two cases on the per-level walker - its content-map and top-of-chain sites with the term on them - to the
+    same bounds."""
+    _path_other_taps(eng_per_level, vgg_weights, case)
 
 
 def test_path_luminance(eng, vgg_weights, monkeypatch):
