@@ -118,6 +118,13 @@ SYMBOLS = {
                                  c_void, c_void]),
     "nst_remd_term": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, c_void,
                                 c_void, C.c_int, C.c_float, c_void, c_void, c_void, c_void]),
+    "nst_level_set_selfsim": (C.c_int, [c_void, C.c_int, c_void, C.c_int, C.c_int, c_float_p, C.POINTER(C.c_int), C.c_double, c_void]),
+    "nst_level_selfsim": (C.c_int, [c_void, C.c_int, c_float_p, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    "nst_job_selfsim_losses": (C.c_int, [c_void, c_void, c_void]),
+    "nst_level_selfsim_decisions": (C.c_int, [c_void, C.c_int, C.c_int, c_void, c_void, c_void, c_void]),
+    "nst_selfsim_matrix": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, c_void, c_void, c_void]),
+    "nst_selfsim_term": (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_float, c_void, c_void,
+                                   c_void, c_void]),
     "nst_warp_bilinear": (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, c_void, c_void]),
     "nst_flow_weights": (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, c_void, c_void]),
     "nst_anchor_fold": (C.c_int, [c_void, C.c_int, C.POINTER(c_void), C.POINTER(c_void), C.c_int, C.c_int, C.c_int, c_void, c_void,

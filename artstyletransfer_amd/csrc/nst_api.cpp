@@ -520,6 +520,94 @@ int nst_remd_term(nst_ctx* ctx, const float* f, int h, int w, int C, const float
     return sc.finish();
 }
 
+// The self-similarity term's pieces on their own (include/nst_hip.h has the definition): the kernels of selfsim.hip on scratch
+// buffers.  Synchronous.
+// one sample set on scratch: the absmax record, the norms, the packed operand, D, s and q
+struct SelfSimSet { RemdSide x; float* D; double* s; double* q; };
+static int selfsim_args(nst_ctx* ctx, const float* f, int h, int w, int C, int stride, double epsilon, RemdSide* x) {
+    if (!f) return fail(ctx, NST_E_ARG, "null argument");
+    if (C != 64 && C != 128 && C != 256 && C != 512) return fail(ctx, NST_E_ARG, "the self-similarity term takes maps of 64, 128, 256 or 512 channels");
+    if (h < 1 || w < 1) return fail(ctx, NST_E_ARG, "the map must be at least 1x1");
+    if (stride < 1 || stride > 256) return fail(ctx, NST_E_ARG, "the sample stride must be 1..256");
+    if (!(epsilon > 0.0) || std::isinf(epsilon)) return fail(ctx, NST_E_ARG, "the self-similarity epsilon must be finite and > 0");
+    *x = RemdSide{};
+    if (!remd_side_geometry(h, w, C, stride, x)) return fail(ctx, NST_E_ARG, "the map is too large");
+    if (x->count > SELFSIM_MAX_SAMPLES) return fail(ctx, NST_E_ARG, "the stride leaves more than 4096 samples");
+    x->f = f;
+    return NST_OK;
+}
+static int selfsim_set(nst_ctx* ctx, Scratch& sc, const RemdSide& geom, double epsilon, double* part, SelfSimSet* out, hipStream_t s) {
+    RemdSide x = geom;
+    const size_t n = (size_t)x.count;
+    unsigned* amax = nullptr; float* r = nullptr; unsigned char* packed = nullptr;
+    NSTCHK(sc.alloc(&amax, (size_t)NST_AMAX_SLOTS));
+    NSTCHK(sc.alloc(&r, (size_t)remd_tiles(x.count) * 32));
+    NSTCHK(sc.alloc(&packed, remd_packed_bytes(x.count, x.C)));
+    NSTCHK(sc.alloc(&out->D, n * n));
+    NSTCHK(sc.alloc(&out->s, n));
+    NSTCHK(sc.alloc(&out->q, n));
+    HIPCHK(ctx, launch_zero(amax, (size_t)NST_AMAX_SLOTS, s));
+    HIPCHK(ctx, launch_absmax_slots(x.f, (size_t)x.h * x.w * x.C, amax, s));
+    x.amax = amax;
+    HIPCHK(ctx, launch_remd_norms(x, epsilon, r, s));
+    x.r = r;
+    HIPCHK(ctx, launch_remd_pack(x, packed, s));
+    x.packed = packed;
+    HIPCHK(ctx, launch_selfsim_matrix(x, out->D, s));
+    HIPCHK(ctx, launch_selfsim_colsums(out->D, x.count, epsilon, part, out->s, out->q, s));
+    out->x = x;
+    return NST_OK;
+}
+
+int nst_selfsim_matrix(nst_ctx* ctx, const float* f, int h, int w, int C, int stride, double epsilon, float* D_out, double* s_out, void* stream) {
+    NSTCHK(bind(ctx));
+    RemdSide x;
+    NSTCHK(selfsim_args(ctx, f, h, w, C, stride, epsilon, &x));
+    if (!D_out && !s_out) return fail(ctx, NST_E_ARG, "null argument");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Scratch sc(ctx, s);
+    const size_t n = (size_t)x.count;
+    double* part = nullptr;
+    NSTCHK(sc.alloc(&part, (size_t)SELFSIM_ROW_BLOCKS * n));
+    SelfSimSet a{};
+    NSTCHK(selfsim_set(ctx, sc, x, epsilon, part, &a, s));
+    if (D_out) HIPCHK(ctx, hipMemcpyAsync(D_out, a.D, n * n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (s_out) HIPCHK(ctx, hipMemcpyAsync(s_out, a.s, n * sizeof(double), hipMemcpyDeviceToDevice, s));
+    return sc.finish();
+}
+
+int nst_selfsim_term(nst_ctx* ctx, const float* f, const float* fc, int h, int w, int C, int stride, double epsilon, float coef, float* value_out,
+                     signed char* sg_out, float* grad_out, void* stream) {
+    NSTCHK(bind(ctx));
+    RemdSide x, y;
+    NSTCHK(selfsim_args(ctx, f, h, w, C, stride, epsilon, &x));
+    NSTCHK(selfsim_args(ctx, fc, h, w, C, stride, epsilon, &y));
+    if (!value_out && !sg_out && !grad_out) return fail(ctx, NST_E_ARG, "null argument");
+    if (!std::isfinite(coef)) return fail(ctx, NST_E_ARG, "the coefficient must be finite");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Scratch sc(ctx, s);
+    const size_t n = (size_t)x.count;
+    double* part = nullptr; double* t = nullptr; signed char* sg = nullptr; float* val = nullptr;
+    NSTCHK(sc.alloc(&part, (size_t)2 * SELFSIM_ROW_BLOCKS * n));
+    NSTCHK(sc.alloc(&t, n));
+    NSTCHK(sc.alloc(&sg, n * n));
+    NSTCHK(sc.alloc(&val, 4));
+    SelfSimSet a{}, b{};
+    NSTCHK(selfsim_set(ctx, sc, y, epsilon, part, &b, s));
+    NSTCHK(selfsim_set(ctx, sc, x, epsilon, part, &a, s));
+    const SelfSimTerm term{a.D, a.q, b.D, b.q, x.count, sg, part, t, val};
+    HIPCHK(ctx, launch_selfsim_value(term, s));
+    if (value_out) HIPCHK(ctx, hipMemcpyAsync(value_out, val, sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (sg_out) HIPCHK(ctx, hipMemcpyAsync(sg_out, sg, n * n, hipMemcpyDeviceToDevice, s));
+    if (grad_out) {
+        float* W = nullptr; float* U = nullptr;
+        NSTCHK(sc.alloc(&W, n * n));
+        NSTCHK(sc.alloc(&U, n * (size_t)C));
+        HIPCHK(ctx, launch_selfsim_grad(a.x, term, (float)((double)coef / (double)x.count), W, U, grad_out, 0, s));
+    }
+    return sc.finish();
+}
+
 // The warp of a sequence (include/nst_hip.h): out = src sampled bilinearly at p + flow(p), valid (nullable) = the four taps
 // lie inside the image.  Synchronous.
 int nst_warp_bilinear(nst_ctx* ctx, const float* src, const float* flow, int C, int h, int w, float* out, float* valid, void* stream) {

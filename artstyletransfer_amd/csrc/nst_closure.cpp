@@ -364,12 +364,50 @@ int remd_forward(nst_ctx* ctx, LevelWs& L, hipStream_t s) {
     return NST_OK;
 }
 
-// ---- the per-map terms together (MapTerm in nst_ctx.h): MRF, histogram loss, relaxed EMD - always in this order ------------
+// ---- the self-similarity term (include/nst_hip.h has the definition; kernels: selfsim.hip) ----------------------------------
+// map index i of level L: the samples of the level's own map (f, the grid, the absmax record of the map, rp and the packed
+// operand of this closure), the term's arrays, and the coefficient (float)(w / n) formed in double
+RemdSide selfsim_side(const LevelWs& L, int i) {
+    const int l = kTapLayer[i];
+    RemdSide x{};
+    remd_side_geometry(L.acts.h[l], L.acts.w[l], kCout[l], L.selfsim.stride[i], &x);
+    x.f = L.acts.act[l]; x.amax = amax_act(L.acts, l); x.r = L.selfsim.rp[i]; x.packed = L.selfsim.xpacked[i];
+    return x;
+}
+SelfSimTerm selfsim_term_of(const LevelWs& L, int i) {
+    const SelfSimLevel& g = L.selfsim;
+    return SelfSimTerm{g.D[i], g.q[i], g.Dc[i], g.qc[i], g.n[i], g.sg[i], g.partial[i], g.t[i], g.vals + i};
+}
+// forward part of level L, once its maps exist: per map with a weight the norms and the packed operand, the distance matrix
+// (timed as "n x 1, cin C, cout n", layer tag 220 + map), the column sums, the signs and selfsim_k (a level without the term:
+// no launch)
+int selfsim_forward(nst_ctx* ctx, LevelWs& L, hipStream_t s) {
+    for (int i = 0; i < 6 && L.selfsim.on(); ++i) {
+        if (!(L.selfsim.w[i] > 0.f)) continue;
+        const RemdSide x = selfsim_side(L, i);
+        {
+            Timer tm(ctx, s, K_OTHER, 0);
+            HIPCHK(ctx, launch_remd_norms(x, L.selfsim.eps, L.selfsim.rp[i], s));
+            HIPCHK(ctx, launch_remd_pack(x, L.selfsim.xpacked[i], s));
+        }
+        {
+            Timer tm(ctx, s, K_OTHER, 2.0 * (double)x.count * (double)x.count * (double)x.C, x.count, 1, x.C, x.count, 1, 220 + i);
+            HIPCHK(ctx, launch_selfsim_matrix(x, L.selfsim.D[i], s));
+        }
+        Timer tm(ctx, s, K_OTHER, 0, x.count, 1, x.count, x.count, 1, 240 + i);      // (the passes over the n x n arrays: tag 240 + map)
+        HIPCHK(ctx, launch_selfsim_colsums(L.selfsim.D[i], x.count, L.selfsim.eps, L.selfsim.partial[i], L.selfsim.s[i], L.selfsim.q[i], s));
+        HIPCHK(ctx, launch_selfsim_value(selfsim_term_of(L, i), s));
+    }
+    return NST_OK;
+}
+
+// ---- the per-map terms together (MapTerm in nst_ctx.h): MRF, histogram loss, relaxed EMD, self-similarity - always in this order
 // forward parts of the levels lv[0..n), once their maps exist: every level of one term before the next term
 int map_terms_forward(nst_ctx* ctx, const int* lv, int n, hipStream_t s) {
     for (int k = 0; k < n; ++k) NSTCHK(patch_forward(ctx, ctx->lv[lv[k]], s));
     for (int k = 0; k < n; ++k) NSTCHK(hist_forward(ctx, ctx->lv[lv[k]], s));
     for (int k = 0; k < n; ++k) NSTCHK(remd_forward(ctx, ctx->lv[lv[k]], s));
+    for (int k = 0; k < n; ++k) NSTCHK(selfsim_forward(ctx, ctx->lv[lv[k]], s));
     return NST_OK;
 }
 // gradient parts of conv layer m of level L, of the terms the map carries, into dst (the map's shape).  `held`: dst holds an
@@ -391,6 +429,14 @@ int map_terms_backward(nst_ctx* ctx, const LevelWs& L, int m, float* dst, bool& 
         Timer tm(ctx, s, K_OTHER, 0);
         const RemdTerm t = remd_term_of(L, i);
         HIPCHK(ctx, launch_remd_grad(t, remd_coef(L.remd.w[i], t.x.count), remd_coef(L.remd.w[i], t.y.count), dst, held ? 1 : 0, s));
+        held = true;
+    }
+    if (L.selfsim.carries(m)) {
+        // (W, U and the fp32 product g = -W U, n x n x C: timed as "n x 1, cin n, cout C", layer tag 230 + map; no f16 work)
+        const RemdSide x = selfsim_side(L, i);
+        Timer tm(ctx, s, K_OTHER, 0, x.count, 1, x.count, x.C, 1, 230 + i);
+        HIPCHK(ctx, launch_selfsim_grad(x, selfsim_term_of(L, i), remd_coef(L.selfsim.w[i], x.count), L.selfsim.W[i], L.selfsim.U[i], dst,
+                                        held ? 1 : 0, s));
         held = true;
     }
     return NST_OK;
@@ -477,9 +523,10 @@ int backward(nst_ctx* ctx, ActSet& a, const Inject* inj, const ContentJob* cj, f
             Timer t(ctx, s, K_OTHER, 0);
             HIPCHK(ctx, launch_mse_grad(a.act[l], cj->target, cj->n, cj->coef, oth, cj->partial, s));
         }
-        // the per-map terms of the top map: onto the content gradient when there is one, the addend of the 1x1 Gram launch
+        // the per-map terms of the top map: onto the content gradient when there is one, the addend of the 1x1 Gram launch - or,
+        // on a content map that is no style map (the self-similarity term may sit there), of the mask pass below
         bool held = content;
-        if (terms && inj[l].S) NSTCHK(map_terms_backward(ctx, *terms, l, oth, held, s));
+        if (terms && (inj[l].S || content)) NSTCHK(map_terms_backward(ctx, *terms, l, oth, held, s));
         if (inj[l].guided) {
             GuidedBwd gb = *inj[l].guided;
             gb.addend = content ? oth : nullptr; gb.out = cur; gb.mask = top_mask ? a.act[l] : nullptr;
@@ -909,7 +956,8 @@ int batched_backward(nst_ctx* ctx, const float* const* xi, float* const* gi, con
     bool top_add[NST_MAX_LEVELS] = {};
     for (int k = 0; k < n; ++k) {
         top_add[k] = top_content;
-        if (top_q >= 0) NSTCHK(map_terms_backward(ctx, ctx->lv[lv[k]], top, oth[k], top_add[k], s));
+        // (a content map alone at the top - no style slot - may carry the self-similarity term: onto its content gradient)
+        if (top_q >= 0 || top_content) NSTCHK(map_terms_backward(ctx, ctx->lv[lv[k]], top, oth[k], top_add[k], s));
     }
     const bool guided = guided_levels(ctx, lv, n);
     if (guided && top_q >= 0) {
@@ -1421,6 +1469,8 @@ int window_check(nst_ctx* ctx, const float* xs, int row0, int rows, int H0) {
         return fail(ctx, NST_E_STATE, "the stripe closure implements no histogram loss (nst_level_set_histograms(ctx, 0, NULL, ...) clears it)");
     if (L.remd.on())
         return fail(ctx, NST_E_STATE, "the stripe closure implements no relaxed EMD term (nst_level_set_remd(ctx, 0, NULL, ...) clears it)");
+    if (L.selfsim.on())
+        return fail(ctx, NST_E_STATE, "the stripe closure implements no self-similarity term (nst_level_set_selfsim(ctx, 0, NULL, ...) clears it)");
     if (L.guide.R > 0)
         return fail(ctx, NST_E_STATE, "the stripe closure implements no spatial control (nst_level_set_guidance(ctx, 0, 0, ...) clears it)");
     if (!L.targets) return fail(ctx, NST_E_STATE, "targets of the stripe not set");
@@ -1570,6 +1620,7 @@ int nst_level_set_guidance(nst_ctx* ctx, int level, int R, const float* planes, 
     if (L.pm.on()) return fail(ctx, NST_E_STATE, "a level with the MRF term takes no guidance (nst_level_set_patches(ctx, level, NULL, ...) clears the term)");
     if (L.hist.on()) return fail(ctx, NST_E_STATE, "a level with the histogram loss takes no guidance (nst_level_set_histograms(ctx, level, NULL, ...) clears the term)");
     if (L.remd.on()) return fail(ctx, NST_E_STATE, "a level with the relaxed EMD term takes no guidance (nst_level_set_remd(ctx, level, NULL, ...) clears the term)");
+    if (L.selfsim.on()) return fail(ctx, NST_E_STATE, "a level with the self-similarity term takes no guidance (nst_level_set_selfsim(ctx, level, NULL, ...) clears the term)");
     if (!planes) return fail(ctx, NST_E_ARG, "null argument");
     float lam[NST_MAX_REGIONS] = {1.f, 1.f, 1.f, 1.f};
     bool positive = lambda == nullptr;

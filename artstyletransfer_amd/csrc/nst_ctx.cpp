@@ -424,12 +424,15 @@ int replace_term(nst_ctx* ctx, Block LevelWs::*member, Fill fill) {
     return replace_blocks(ctx->lv, ctx->levels, member, fill, [&] { quiesce(ctx); drop_closure_state(ctx, true); });
 }
 
-// ---- what the per-map terms (MapTerm: MRF, histogram loss, relaxed EMD) share outside a closure -----------------------------
+// ---- what the per-map terms (MapTerm: MRF, histogram loss, relaxed EMD, self-similarity) share outside a closure -----------------------------
 // how the refusals of a term's setter name it ("the <adj> weights", "no <name>"), and what the term asks of the job besides
-struct MapTermWords { const char* adj; const char* name; bool f16x2_only; bool min_3x3; };
-const MapTermWords kMrfWords{"MRF", "MRF term", true, true};
-const MapTermWords kHistWords{"histogram", "histogram loss", false, false};
-const MapTermWords kRemdWords{"relaxed EMD", "relaxed EMD term", true, false};
+// (any_used_map: a weight may sit on the job's content map as well as on a style map, and the image the setter is given is
+// the level's content image, not a style image)
+struct MapTermWords { const char* adj; const char* name; bool f16x2_only; bool min_3x3; bool any_used_map; };
+const MapTermWords kMrfWords{"MRF", "MRF term", true, true, false};
+const MapTermWords kHistWords{"histogram", "histogram loss", false, false, false};
+const MapTermWords kRemdWords{"relaxed EMD", "relaxed EMD term", true, false, false};
+const MapTermWords kSelfSimWords{"self-similarity", "self-similarity term", true, false, true};
 
 // every level's per-map terms go (they hold maps of the style image as the job's network saw it: the setters again)
 void drop_map_terms(nst_ctx* ctx) {
@@ -437,6 +440,7 @@ void drop_map_terms(nst_ctx* ctx) {
         ctx->lv[i].pm = PatchLevel();
         ctx->lv[i].hist = HistLevel();
         ctx->lv[i].remd = RemdLevel();
+        ctx->lv[i].selfsim = SelfSimLevel();
     }
 }
 // weight i of a setter's six into the new block
@@ -457,12 +461,15 @@ int begin_map_term(nst_ctx* ctx, const MapTermWords& t, const LevelWs& L, MapTer
     if (t.f16x2_only && ctx->conv_mode != 2) return fail(ctx, NST_E_STATE, "the " + name + " runs in the f16x2 arithmetic only (NST_CONV unset)");
     if (ctx->use_graph) return fail(ctx, NST_E_STATE, "the " + name + "'s launches are not captured: a context with use_graph takes no term");
     if (L.guide.R > 0) return fail(ctx, NST_E_STATE, "a guided level takes no " + name + " (nst_level_set_guidance(ctx, level, 0, ...) clears the guidance)");
-    if (hs < 16 || ws < 16) return fail(ctx, NST_E_ARG, "style image must be at least 16x16");
-    const unsigned style_mask = style_mask_of(ctx->taps);
+    if (t.any_used_map ? (hs != L.h || ws != L.w) : (hs < 16 || ws < 16))
+        return fail(ctx, NST_E_ARG, t.any_used_map ? "the content image must have the level's size" : "style image must be at least 16x16");
+    unsigned used_mask = style_mask_of(ctx->taps);
+    if (t.any_used_map) used_mask |= 1u << tap_index_of(ctx->taps.content);
     int deepest = -1;
     for (int i = 0; i < 6; ++i) {
         if (!(g.w[i] > 0.f)) continue;
-        if (!((style_mask >> i) & 1u)) return fail(ctx, NST_E_ARG, "a positive " + adj + " weight on a map that is not a style map of the job");
+        if (!((used_mask >> i) & 1u))
+            return fail(ctx, NST_E_ARG, "a positive " + adj + " weight on a map that is not " + (t.any_used_map ? "a map the job uses" : "a style map of the job"));
         const int l = kTapLayer[i];
         if (t.min_3x3 && (L.acts.h[l] < 3 || L.acts.w[l] < 3 || (hs >> kScale[l]) < 3 || (ws >> kScale[l]) < 3))
             return fail(ctx, NST_E_ARG, "a weighted map or its style map is below 3x3");
@@ -558,6 +565,7 @@ int nst_ctx_create_ex(int device, const float* const* weights, const float* cons
     if (e == hipSuccess) e = pm_init_device();
     if (e == hipSuccess) e = hist_init_device();
     if (e == hipSuccess) e = remd_init_device();
+    if (e == hipSuccess) e = selfsim_init_device();
     // options: an explicit argument wins; -1 falls back to the environment (read here, once), then to the default
     if (opts.conv_mode >= 0) {
         if (opts.conv_mode > NST_CONV_F16X2) { ctx->err = "nst_options.conv_mode must be NST_CONV_F32, NST_CONV_BF16X3 or NST_CONV_F16X2"; return bail(NST_E_ARG); }
@@ -1405,6 +1413,105 @@ int nst_level_remd_matches(nst_ctx* ctx, int level, int map, int* nnA_out, int* 
     if (nnA_out) HIPCHK(ctx, hipMemcpyAsync(nnA_out, g.nnA[map], (size_t)g.n[map] * sizeof(int), hipMemcpyDeviceToDevice, s));
     if (nnB_out) HIPCHK(ctx, hipMemcpyAsync(nnB_out, g.nnB[map], (size_t)g.y[map].count * sizeof(int), hipMemcpyDeviceToDevice, s));
     if (side_out) HIPCHK(ctx, hipMemcpyAsync(side_out, g.side[map], sizeof(int), hipMemcpyDeviceToDevice, s));
+    mark(ctx, s);
+    return NST_OK;
+}
+
+// The self-similarity term of one level (Kolkin et al. 2019; include/nst_hip.h has the definition): the content image goes
+// through the network on scratch, and per weighted map the content's D and q are made by the launches a closure uses on the
+// image's map - in the level's own D, s and partial buffers, which the first closure overwrites - beside every buffer a closure
+// needs.  Life cycle of nst_level_set_remd.
+int nst_level_set_selfsim(nst_ctx* ctx, int level, const float* content, int h, int w, const float* weights, const int* stride, double epsilon,
+                          void* stream) {
+    if (ctx) { ++ctx->closure_epoch; ++ctx->ws_seq; }
+    NSTCHK(bind(ctx));
+    if (ctx->levels < 1) return fail(ctx, NST_E_STATE, "nst_job_configure has not been called");
+    if (level < 0 || level >= ctx->levels) return fail(ctx, NST_E_ARG, "level out of range");
+    LevelWs& L = ctx->lv[level];
+    SelfSimLevel g;
+    if (content) {
+        if (!weights || !stride) return fail(ctx, NST_E_ARG, "null argument");
+        for (int i = 0; i < 6; ++i) {
+            NSTCHK(take_weight(ctx, kSelfSimWords, weights, i, g));
+            if (stride[i] < 1 || stride[i] > 256) return fail(ctx, NST_E_ARG, "the sample strides must be 1..256");
+            g.stride[i] = stride[i];
+        }
+        if (!(epsilon > 0.0) || std::isinf(epsilon)) return fail(ctx, NST_E_ARG, "the self-similarity epsilon must be finite and > 0");
+        for (int i = 0; i < 6; ++i) {
+            RemdSide x{};
+            const int l = kTapLayer[i];
+            if (g.w[i] > 0.f && remd_side_geometry(L.acts.h[l], L.acts.w[l], kCout[l], g.stride[i], &x) && x.count > SELFSIM_MAX_SAMPLES)
+                return fail(ctx, NST_E_ARG, "a weighted map has more than 4096 samples at its stride");
+        }
+    }
+    std::optional<Scratch> sc;
+    NSTCHK(begin_map_term(ctx, kSelfSimWords, L, g, content, h, w, stream, sc));
+    if (sc) {
+        hipStream_t s = sc->s;
+        g.eps = epsilon;
+        for (int i = 0; i < 6; ++i) {
+            if (!(g.w[i] > 0.f)) continue;
+            const int l = kTapLayer[i], C = kCout[l];
+            RemdSide y{};
+            if (!remd_side_geometry(sc->acts.h[l], sc->acts.w[l], C, g.stride[i], &y) || sc->acts.h[l] != L.acts.h[l] || sc->acts.w[l] != L.acts.w[l])
+                return fail(ctx, NST_E_ARG, "a weighted map is too large");
+            const size_t n = (size_t)y.count;
+            g.n[i] = y.count;
+            NSTCHK(g.mem.alloc(ctx, &g.Dc[i], n * n));
+            NSTCHK(g.mem.alloc(ctx, &g.qc[i], n));
+            NSTCHK(g.mem.alloc(ctx, &g.rp[i], (size_t)remd_tiles(y.count) * 32));
+            NSTCHK(g.mem.alloc(ctx, &g.xpacked[i], remd_packed_bytes(y.count, C)));
+            NSTCHK(g.mem.alloc(ctx, &g.D[i], n * n));
+            NSTCHK(g.mem.alloc(ctx, &g.s[i], n));
+            NSTCHK(g.mem.alloc(ctx, &g.q[i], n));
+            NSTCHK(g.mem.alloc(ctx, &g.sg[i], n * n));
+            NSTCHK(g.mem.alloc(ctx, &g.t[i], n));
+            NSTCHK(g.mem.alloc(ctx, &g.partial[i], (size_t)2 * SELFSIM_ROW_BLOCKS * n));
+            NSTCHK(g.mem.alloc(ctx, &g.W[i], n * n));
+            NSTCHK(g.mem.alloc(ctx, &g.U[i], n * (size_t)C));
+            // the content's side by the closure's launches: norms, pack, matrix, column sums
+            y.f = sc->acts.act[l]; y.amax = amax_act(sc->acts, l);
+            HIPCHK(ctx, launch_remd_norms(y, epsilon, g.rp[i], s));
+            y.r = g.rp[i];
+            HIPCHK(ctx, launch_remd_pack(y, g.xpacked[i], s));
+            y.packed = g.xpacked[i];
+            HIPCHK(ctx, launch_selfsim_matrix(y, g.Dc[i], s));
+            HIPCHK(ctx, launch_selfsim_colsums(g.Dc[i], y.count, epsilon, g.partial[i], g.s[i], g.qc[i], s));
+            // what nst_level_selfsim_decisions reads before any closure
+            HIPCHK(ctx, hipMemsetAsync(g.D[i], 0, n * n * sizeof(float), s));
+            HIPCHK(ctx, hipMemsetAsync(g.s[i], 0, n * sizeof(double), s));
+            HIPCHK(ctx, hipMemsetAsync(g.sg[i], 0, n * n, s));
+        }
+    }
+    return commit_map_term(ctx, sc, L.selfsim, g);
+}
+
+int nst_level_selfsim(const nst_ctx* ctx, int level, float* weights, int* stride, double* epsilon) {
+    if (!ctx) return fail(nullptr, NST_E_ARG, "null context");
+    if (level < 0 || level >= ctx->levels) return fail(nullptr, NST_E_ARG, "level out of range");
+    const SelfSimLevel& g = ctx->lv[level].selfsim;
+    for (int i = 0; i < 6 && weights; ++i) weights[i] = g.w[i];
+    for (int i = 0; i < 6 && stride; ++i) stride[i] = g.stride[i];
+    if (epsilon) *epsilon = g.eps;
+    return NST_OK;
+}
+
+// the unweighted selfsim_k of the last closure (map_term_losses)
+int nst_job_selfsim_losses(nst_ctx* ctx, float* out, void* stream) { return map_term_losses(ctx, T_SELFSIM, out, stream); }
+
+// D (n x n float), s (n double) and sg (n x n int8) of the last closure of one weighted map of a level (zeros before any
+// closure; each nullable)
+int nst_level_selfsim_decisions(nst_ctx* ctx, int level, int map, float* D_out, double* s_out, signed char* sg_out, void* stream) {
+    NSTCHK(bind(ctx));
+    if (level < 0 || level >= ctx->levels) return fail(ctx, NST_E_ARG, "level out of range");
+    if (map < 0 || map > 5 || (!D_out && !s_out && !sg_out)) return fail(ctx, NST_E_ARG, "bad argument");
+    const SelfSimLevel& g = ctx->lv[level].selfsim;
+    if (!(g.w[map] > 0.f)) return fail(ctx, NST_E_STATE, "the map carries no self-similarity term on this level (nst_level_set_selfsim)");
+    const size_t n = (size_t)g.n[map];
+    hipStream_t s = enter(ctx, stream);
+    if (D_out) HIPCHK(ctx, hipMemcpyAsync(D_out, g.D[map], n * n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (s_out) HIPCHK(ctx, hipMemcpyAsync(s_out, g.s[map], n * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (sg_out) HIPCHK(ctx, hipMemcpyAsync(sg_out, g.sg[map], n * n, hipMemcpyDeviceToDevice, s));
     mark(ctx, s);
     return NST_OK;
 }

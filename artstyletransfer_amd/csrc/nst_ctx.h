@@ -200,7 +200,7 @@ struct AnchorLevel {
     DevMem mem;
 };
 
-// What the per-map terms of one level share (PatchLevel, HistLevel, RemdLevel below; always in that order, NST_MAP_TERMS of
+// What the per-map terms of one level share (PatchLevel, HistLevel, RemdLevel, SelfSimLevel below; always in that order, NST_MAP_TERMS of
 // them): the weights by map index (0: the map has no term), the six unweighted values of the last closure (which the forward
 // half writes and the loss rows read), and the block's memory.
 struct MapTerm {
@@ -217,7 +217,7 @@ struct MapTerm {
         return i >= 0 && w[i] > 0.f;
     }
 };
-enum MapTermId { T_MRF = 0, T_HIST = 1, T_REMD = 2 };
+enum MapTermId { T_MRF = 0, T_HIST = 1, T_REMD = 2, T_SELFSIM = 3 };
 
 // The MRF term of one level (nst_level_set_patches; include/nst_hip.h has the definition), by map index: the weight (0: the
 // map has no term), the style's map with its dictionary (d[i]: fs, the absmax record, rq and the packed operand), the search
@@ -290,6 +290,30 @@ struct RemdLevel : MapTerm {
     int* side[6] = {};
 };
 
+// The self-similarity term of one level (nst_level_set_selfsim; include/nst_hip.h has the definition), by map index: the weight
+// (0: the map has no term; any map the job uses may carry one) and the stride; the content's side, made once by the setter (Dc:
+// n x n, qc); the image side's buffers, which the forward half fills every closure (rp, the packed operand, D, s, q, the signs,
+// t and the partials) and the backward half's workspace (W: n x n, U: n x C); and the unweighted selfsim_k (six floats, which
+// the forward half writes and the loss rows read).  Data of one job with PatchLevel's life cycle: everything is made by the
+// setter, a closure allocates nothing.
+struct SelfSimLevel : MapTerm {
+    int stride[6] = {1, 1, 1, 1, 1, 1};
+    double eps = 1e-5;
+    int n[6] = {};              // samples of the map
+    float* Dc[6] = {};
+    double* qc[6] = {};
+    float* rp[6] = {};
+    unsigned char* xpacked[6] = {};
+    float* D[6] = {};
+    double* s[6] = {};
+    double* q[6] = {};
+    signed char* sg[6] = {};
+    double* t[6] = {};
+    double* partial[6] = {};    // 2 SELFSIM_ROW_BLOCKS n each
+    float* W[6] = {};
+    float* U[6] = {};
+};
+
 // the level image and its gradient (levels >= 1), planar: channels (nst_job_set_color) x h x w floats each
 struct LevelImage {
     float* xl = nullptr;
@@ -308,7 +332,10 @@ struct LevelWs {
     PatchLevel pm;
     HistLevel hist;
     RemdLevel remd;
-    const MapTerm& map_term(int t) const { return t == T_MRF ? (const MapTerm&)pm : t == T_HIST ? (const MapTerm&)hist : remd; }
+    SelfSimLevel selfsim;
+    const MapTerm& map_term(int t) const {
+        return t == T_MRF ? (const MapTerm&)pm : t == T_HIST ? (const MapTerm&)hist : t == T_REMD ? (const MapTerm&)remd : selfsim;
+    }
     ActSet acts;
     float* gbuf[2] = {};
     size_t gbuf_floats = 0;

@@ -354,7 +354,7 @@ hipError_t launch_flow_tvl1_estimate(const float* from, const float* to, const F
                                      int warps, int iterations, float* flow, float* ws, hipStream_t stream);
 
 // loss assembly -----------------------------------------------------------------------------------
-constexpr int NST_MAP_TERMS = 3;     // the per-map terms of a level: MRF, histogram loss, relaxed EMD - always in this order
+constexpr int NST_MAP_TERMS = 4;     // the per-map terms of a level: MRF, histogram loss, relaxed EMD, self-similarity - always in this order
 struct LevelLossInputs {
     const double* content_partial;   // MSE_BLOCKS doubles
     size_t content_n;
@@ -376,7 +376,7 @@ struct LevelLossInputs {
     double tmp_n;
     float* tmp_out;
     // the per-map terms, a level's own, in the order the row adds them: MRF (nst_level_set_patches), histogram loss
-    // (nst_level_set_histograms), relaxed EMD (nst_level_set_remd).  Each: the six unweighted values by map index as the
+    // (nst_level_set_histograms), relaxed EMD (nst_level_set_remd), self-similarity (nst_level_set_selfsim).  Each: the six unweighted values by map index as the
     // forward half left them (nullptr: the level has no such term and its row is what it is without it), and the weights (0:
     // the map has no term)
     struct MapTerm { float* vals; float w[6]; } term[NST_MAP_TERMS];
@@ -603,6 +603,27 @@ struct RemdTerm {
 };
 hipError_t launch_remd_value(const RemdTerm& t, double epsilon, int force, double* partial, float* val, hipStream_t stream);
 hipError_t launch_remd_grad(const RemdTerm& t, float coefA, float coefB, float* out, int accumulate, hipStream_t stream);
+
+// selfsim.hip: the self-similarity content term (include/nst_hip.h has the definition) ----------------------------------------
+// The samples are a RemdSide (f, the grid, the absmax record, r from launch_remd_norms, packed from launch_remd_pack) of at
+// most SELFSIM_MAX_SAMPLES samples: the term keeps n x n arrays.
+constexpr int SELFSIM_MAX_SAMPLES = 4096;
+constexpr int SELFSIM_ROW_BLOCKS = 16;
+hipError_t selfsim_init_device();   // raises the dynamic-LDS limit of the matrix kernels: once per device, before the first launch there
+// D (n x n floats, row-major, row = the dictionary role i, column = the column role j): 0 on the diagonal, else max(0, 1 - c(i,j))
+hipError_t launch_selfsim_matrix(const RemdSide& x, float* D, hipStream_t stream);
+// s_j = sum_i D_ij (double, two ordered stages; part: SELFSIM_ROW_BLOCKS n doubles) and q_j = 1 / (s_j + epsilon)
+hipError_t launch_selfsim_colsums(const float* D, int n, double epsilon, double* part, double* s, double* q, hipStream_t stream);
+// Value and decisions: N = D q against M = Dc qc.  sg: n x n int8; part: 2 SELFSIM_ROW_BLOCKS n doubles; t: n doubles; val: one float
+struct SelfSimTerm {
+    const float* D; const double* q; const float* Dc; const double* qc; int n;
+    signed char* sg; double* part; double* t; float* val;
+};
+hipError_t launch_selfsim_value(const SelfSimTerm& t, hipStream_t stream);
+// The gradient at the decisions the value pass left (sg, t): W (n x n floats) and U (n x C floats) are workspace; out (the map's
+// shape) gets coef rp_i (g_i - <g_i, u_i> u_i) at the sampled pixels - written, everything else zero, or (accumulate) added.
+hipError_t launch_selfsim_grad(const RemdSide& x, const SelfSimTerm& t, float coef, float* W, float* U, float* out, int accumulate,
+                               hipStream_t stream);
 
 // gram_guided.hip: spatial control (guided Gram matrices; include/nst_hip.h has the definitions) ---------------------
 constexpr int NST_MAX_REGIONS_K = 4;

@@ -770,7 +770,7 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(LossAssembly la) {
             total = total + in.tmp_gamma * tmp;
         }
         for (int t = 0; t < NST_MAP_TERMS; ++t) {
-            // (... + gamma tmp) + sum_i w_i mrf_i + sum_i w_i hist_i + sum_i w_i remd_i: term after term, each over its maps with
+            // (... + gamma tmp) + sum_i w_i mrf_i + sum_i w_i hist_i + sum_i w_i remd_i + sum_i w_i selfsim_i: term after term, each over its maps with
             // a weight in ascending map order, every product and sum rounded
             const LevelLossInputs::MapTerm& m = in.term[t];
             if (!m.vals) continue;

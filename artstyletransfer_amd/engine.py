@@ -21,6 +21,7 @@ from . import flow_modes as _flow
 from . import mrf_modes as _mrf
 from . import hist_modes as _hist
 from . import remd_modes as _remd
+from . import selfsim_modes as _selfsim
 from ._lib import NST_LOSS_ROW, NstError, StepInfo
 
 TAP_CHANNELS = (64, 128, 256, 512, 512, 512)
@@ -970,6 +971,106 @@ class StyleEngine:
                                                     _ptr(sd), _ptr(grad), _stream(self.device)), "nst_remd_term")
         return (val, int(sd.item()), grad) if want_grad else (val, int(sd.item()))
 
+    # ---- the self-similarity content term (nst_level_set_selfsim; selfsim_loss.py is the driver) --------------
+    def set_selfsim(self, level: int, content: Optional[torch.Tensor], weights=None, strides=1,
+                    epsilon: float = _selfsim.DEFAULT_EPSILON) -> None:
+        """The self-similarity term of one level (nst_level_set_selfsim; Kolkin et al. 2019): the level total gains
+        sum_k w_k selfsim_k, selfsim_k the mean over the sampled positions of the L1 distance between the column-normalised
+        cosine-distance matrices of map k and of the content's map k.  content: the level's content image, a device float32
+        (C,h,w) tensor of the level's size (any leading ones; C = 3, or 1 in luminance mode), which is run through the network;
+        weights: as selfsim_modes.normalize_weights takes them (a number: the job's content map; any map the job uses may
+        carry one); strides: one integer 1..256 or six by map index (selfsim_modes.stride_for chooses one for a sample
+        budget; at most 4096 samples a map).  Data of the job, not a setting: configure(), set_taps, set_pooling and set_color
+        drop it.  content None or zero weights clear the level's term."""
+        setting = None if content is None else _selfsim.normalize_selfsim(weights, _selfsim.DEFAULT_SAMPLES, epsilon, None, self.taps[0],
+                                                                          self.taps[1])
+        if setting is None:
+            ones = (C.c_int * 6)(*([1] * 6))
+            _lib.check(self.ctx, self.lib.nst_level_set_selfsim(self.ctx, int(level), None, 0, 0, None, ones, _selfsim.DEFAULT_EPSILON,
+                                                                _stream(self.device)), "nst_level_set_selfsim")
+            return
+        w, _, eps, _ = setting
+        st = _selfsim.check_strides(strides, "strides")
+        ch = self.channels
+        if content.dim() < 3 or content.numel() != ch * content.shape[-2] * content.shape[-1]:
+            raise NstError(f"the content image of level {level} must have shape ({ch},h,w), got {tuple(content.shape)}")
+        content = content.contiguous()
+        _chk_dev(content, self.device)
+        _lib.check(self.ctx, self.lib.nst_level_set_selfsim(self.ctx, int(level), _ptr(content), int(content.shape[-2]),
+                                                            int(content.shape[-1]), (C.c_float * 6)(*w), (C.c_int * 6)(*st), eps,
+                                                            _stream(self.device)), "nst_level_set_selfsim")
+
+    def clear_selfsim(self, level: Optional[int] = None) -> None:
+        """No self-similarity term on one level, or (None) on any configured level."""
+        self._clear_levels(self.set_selfsim, level)
+
+    def selfsim_setting(self, level: int):
+        """(weights (6,), strides (6,), epsilon) of a level (nst_level_selfsim), or None when the level has no term."""
+        w, st, eps = (C.c_float * 6)(), (C.c_int * 6)(), C.c_double()
+        _lib.check(self.ctx, self.lib.nst_level_selfsim(self.ctx, int(level), w, st, C.byref(eps)), "nst_level_selfsim")
+        ws = tuple(float(v) for v in w)
+        if all(v == 0.0 for v in ws):
+            return None
+        return ws, tuple(int(v) for v in st), eps.value
+
+    def selfsim_losses(self) -> torch.Tensor:
+        """(levels, 6) device tensor: the unweighted selfsim_k of the last closure by map index (nst_job_selfsim_losses); zeros
+        for maps without the term and levels outside the last level mask."""
+        return self._map_term_losses("nst_job_selfsim_losses")
+
+    def selfsim_decisions(self, level: int, map: int):
+        """(D (n,n) float32, s (n,) float64, sg (n,n) int8) of map index `map` of a level as the last closure made them
+        (nst_level_selfsim_decisions): D[i, j] the cosine distance with i in the dictionary and j in the column role, s its
+        column sums, sg the signs of N - M."""
+        st = self.selfsim_setting(level)
+        if st is None or not st[0][map] > 0.0:
+            raise NstError(f"map {map} carries no self-similarity term on level {level} (set_selfsim)")
+        h, w = self.level_shape(level)
+        n = _selfsim.samples_of(h >> TAP_SCALE[map], w >> TAP_SCALE[map], st[1][map])
+        d = torch.empty((n, n), dtype=torch.float32, device=self.device)
+        s = torch.empty(n, dtype=torch.float64, device=self.device)
+        sg = torch.empty((n, n), dtype=torch.int8, device=self.device)
+        _lib.check(self.ctx, self.lib.nst_level_selfsim_decisions(self.ctx, int(level), int(map), _ptr(d), _ptr(s), _ptr(sg),
+                                                                  _stream(self.device)), "nst_level_selfsim_decisions")
+        return d, s, sg
+
+    def _selfsim_map(self, f: torch.Tensor, stride, epsilon):
+        stride, eps = _selfsim.check_stride(stride, "stride"), _selfsim.check_epsilon(epsilon)
+        _chk_dev(f, self.device)
+        if f.dim() != 3:
+            raise NstError("f must be (h,w,C)")
+        n = _selfsim.samples_of(f.shape[0], f.shape[1], stride)
+        if n > _selfsim.MAX_SAMPLES:
+            raise ValueError(f"stride {stride} leaves {n} samples of a {f.shape[0]}x{f.shape[1]} map: at most {_selfsim.MAX_SAMPLES}")
+        return stride, eps, n
+
+    def selfsim_matrix(self, f: torch.Tensor, stride: int = 1, epsilon: float = _selfsim.DEFAULT_EPSILON):
+        """The distance matrix alone (nst_selfsim_matrix): f (h,w,C) device float32 map in NHWC, C = 64, 128, 256 or 512,
+        sampled with the stride -> (D (n,n) float32, s (n,) float64: the column sums)."""
+        stride, eps, n = self._selfsim_map(f, stride, epsilon)
+        d = torch.empty((n, n), dtype=torch.float32, device=self.device)
+        s = torch.empty(n, dtype=torch.float64, device=self.device)
+        _lib.check(self.ctx, self.lib.nst_selfsim_matrix(self.ctx, _ptr(f), f.shape[0], f.shape[1], f.shape[2], stride, eps, _ptr(d),
+                                                         _ptr(s), _stream(self.device)), "nst_selfsim_matrix")
+        return d, s
+
+    def selfsim_term(self, f: torch.Tensor, fc: torch.Tensor, stride: int = 1, epsilon: float = _selfsim.DEFAULT_EPSILON,
+                     coef: float = 1.0, want_grad: bool = True):
+        """Value, decisions and gradient alone (nst_selfsim_term): f against the content's map fc, both (h,w,C) ->
+        (selfsim device scalar, sg (n,n) int8) and, with want_grad, the (h,w,C) gradient of coef selfsim at those decisions,
+        zero off the sample grid."""
+        stride, eps, n = self._selfsim_map(f, stride, epsilon)
+        _chk_dev(fc, self.device)
+        if tuple(fc.shape) != tuple(f.shape):
+            raise NstError("f and fc must have the same (h,w,C) shape")
+        val = torch.empty(1, dtype=torch.float32, device=self.device)
+        sg = torch.empty((n, n), dtype=torch.int8, device=self.device)
+        grad = torch.empty_like(f) if want_grad else None
+        _lib.check(self.ctx, self.lib.nst_selfsim_term(self.ctx, _ptr(f), _ptr(fc), f.shape[0], f.shape[1], f.shape[2], stride, eps,
+                                                       float(coef), _ptr(val), _ptr(sg), _ptr(grad), _stream(self.device)),
+                   "nst_selfsim_term")
+        return (val, sg, grad) if want_grad else (val, sg)
+
     def closure(self, x: torch.Tensor, cw: float, sw: float, tvw: float,
                 grad: Optional[torch.Tensor] = None, losses: Optional[torch.Tensor] = None):
         """Asynchronous on the current stream. Returns (grad (C,H,W), losses (4*levels+1,)) device tensors (C = 3, or 1
@@ -1712,6 +1813,7 @@ class PixelOptimizer:
         _mrf.check_exclusive(next((st for st in (e.patches_setting(l) for l in range(e.levels)) if st is not None), None), stripes=True)
         _hist.check_exclusive(next((st for st in (e.histograms_setting(l) for l in range(e.levels)) if st is not None), None), stripes=True)
         _remd.check_exclusive(next((st for st in (e.remd_setting(l) for l in range(e.levels)) if st is not None), None), stripes=True)
+        _selfsim.check_exclusive(next((st for st in (e.selfsim_setting(l) for l in range(e.levels)) if st is not None), None), stripes=True)
         contents = list(content_t) if isinstance(content_t, (list, tuple)) else [content_t]
         styles = list(style_t) if isinstance(style_t, (list, tuple)) else [style_t]
         if blend is not None and styles and isinstance(styles[0], torch.Tensor):

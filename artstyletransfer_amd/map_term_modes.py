@@ -1,4 +1,4 @@
-"""What the settings of the per-map style terms share - mrf_modes, hist_modes and remd_modes bind these to their own words: six
+"""What the settings of the per-map terms share - mrf_modes, hist_modes, remd_modes and selfsim_modes bind these to their own words: six
 weights by map index of Vgg19.layer_names, the levels that carry the term, and what the term does not combine with.  Kept
 free of torch: everything here raises ValueError before any GPU work."""
 import math
@@ -17,10 +17,11 @@ class Words(NamedTuple):
     default_maps: tuple     # the maps a plain number weighs
     no_default: str         # "... is a style map of the job": said when none of default_maps is one
     map_texts: tuple        # taps.map_index_texts(name)
+    role: str = "a style map"   # what a weighted map must be: "... is not <role> of the job"
 
 
-def words(name, levels_name, default_maps, no_default):
-    return Words(name, levels_name, tuple(default_maps), no_default, map_index_texts(name))
+def words(name, levels_name, default_maps, no_default, role="a style map"):
+    return Words(name, levels_name, tuple(default_maps), no_default, map_index_texts(name), role)
 
 
 def _weight(v, what):
@@ -52,7 +53,7 @@ def normalize_weights(t, value=None, style_indices=None, use_relu=None):
             return (0.0,) * NUM_MAPS
         on = [i for i in t.default_maps if i in style]
         if not on:
-            raise ValueError(f"{t.name}: {t.no_default} is a style map of the job {style}; give the weights by map")
+            raise ValueError(f"{t.name}: {t.no_default} is {t.role} of the job {style}; give the weights by map")
         return tuple(w if i in on else 0.0 for i in range(NUM_MAPS))
     if isinstance(value, dict):
         ws = [0.0] * NUM_MAPS
@@ -68,7 +69,7 @@ def normalize_weights(t, value=None, style_indices=None, use_relu=None):
         ws = [_weight(v, f"{t.name} entry {i}") for i, v in enumerate(items)]
     for i, w in enumerate(ws):
         if known and w > 0.0 and i not in style:
-            raise ValueError(f"{t.name}: map {i} has a positive weight but is not a style map of the job {style}")
+            raise ValueError(f"{t.name}: map {i} has a positive weight but is not {t.role} of the job {style}")
     return tuple(ws)
 
 

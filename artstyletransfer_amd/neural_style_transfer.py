@@ -29,6 +29,7 @@ from . import moment_modes as _mom
 from . import mrf_modes as _mrf
 from . import hist_modes as _hist
 from . import remd_modes as _remd
+from . import selfsim_modes as _selfsim
 
 # ImageNet statistics (reference :22-23)
 IMAGENET_MEAN_255 = [123.675, 116.28, 103.53]
@@ -221,6 +222,7 @@ class _DeviceJob:
                     content_t = prepared
                     style_t = lambda img, k=0: prepared(img)                                      # noqa: E731
                 self.style_levels = [(lambda img=s_img: style_t(img)) for s_img in style_imgs]     # set_patch_match: the images the targets are made from
+                self.content_levels = [(lambda img=c_img: content_t(img)) for c_img in content_imgs]   # set_self_similarity: likewise
                 for lvl, (c_img, s_img) in enumerate(zip(content_imgs, style_imgs)):
                     if tuple(c_img.shape[:2]) != engine.level_shape(lvl):
                         raise ValueError(f"content level {lvl} is {tuple(c_img.shape[:2])}, expected {engine.level_shape(lvl)}")
@@ -283,6 +285,15 @@ class _DeviceJob:
             for lvl, style_of in enumerate(self.style_levels):
                 if strides[lvl] is not None:
                     self.engine.set_remd(lvl, style_of(), weights, strides[lvl][0], strides[lvl][1], epsilon)
+
+    def set_self_similarity(self, weights, strides, epsilon):
+        """The self-similarity term of the levels (StyleEngine.set_selfsim; `strides` per level: None for a level without the
+        term, or six strides as selfsim_modes.level_strides makes them): each level gets the content level image its targets
+        were made from."""
+        with torch.cuda.device(self.dev), torch.cuda.stream(self.job_stream):
+            for lvl, content_of in enumerate(self.content_levels):
+                if strides[lvl] is not None:
+                    self.engine.set_selfsim(lvl, content_of(), weights, strides[lvl], epsilon)
 
     def step(self, cw, sw, tvw):
         """One optimizer.step(closure) (nst_opt_step).  Runs on a pool thread, whose current stream is its own."""
@@ -363,6 +374,7 @@ class NeuralStyleTransfer:
         self.__semantics = None                  # set_patch_semantics: likewise
         self.__histograms = None                 # set_histogram_loss: likewise
         self.__remd = None                       # set_relaxed_emd: likewise
+        self.__selfsim = None                    # set_self_similarity: likewise
 
     def set_feature_maps(self, content_layer=None, style_layers=None, use_relu=True):
         """Extension: the feature maps the losses of the next `process` read - a content map and a set of style maps of
@@ -529,6 +541,22 @@ class NeuralStyleTransfer:
         off = _remd.normalize_remd(weights, samples, epsilon, levels) is None       # (malformed: here and now)
         self.__remd = None if off else (weights, samples, epsilon, levels)
 
+    def set_self_similarity(self, weights=None, samples=_selfsim.DEFAULT_SAMPLES, epsilon=_selfsim.DEFAULT_EPSILON, levels=None):
+        """Extension: the self-similarity content term of Kolkin, Salavon & Shakhnarovich 2019 (STROTSS) in the next `process`:
+        per pyramid level sum_k w_k selfsim_k, selfsim_k the mean over the sampled positions of map k of the L1 distance between
+        the column-normalised matrices of pairwise cosine distances of the image's and of the content's samples
+        (nst_level_set_selfsim in include/nst_hip.h has the definition).  It ties the layout to the content's without tying the
+        feature values: the term to use with a low content weight beside set_relaxed_emd.  `weights`: None or 0 (off), a number
+        (that weight on the job's content map), six numbers by map index of Vgg19.layer_names, or a dict {map index or name:
+        number} - any map the job uses may carry one, its content map or a style map; `samples`: 1..4096, the most samples per
+        map (every map gets the smallest stride that keeps to it; the term keeps samples x samples arrays; 1024 is the
+        paper's count); `epsilon` > 0; `levels`: None for every level, or the level indices that carry the term (0 = the full
+        resolution).  Data of one job, like set_relaxed_emd - not one of `settings`.  ValueError for a malformed setting and -
+        in `process`, where the taps and the sizes are known - for a positive weight on a map the job does not use, a map that
+        needs a stride above 256, or the term together with regions or several style images."""
+        off = _selfsim.normalize_selfsim(weights, samples, epsilon, levels) is None       # (malformed: here and now)
+        self.__selfsim = None if off else (weights, samples, epsilon, levels)
+
     async def process(self, content_imgs, init_img, lr_start, iters_num, content_weight, style_weight, tv_weight,
                       init_img_name):
         # validates the model name exactly as the reference does (ValueError for anything but vgg19)
@@ -577,6 +605,13 @@ class NeuralStyleTransfer:
             remd = _remd.normalize_remd(*self.__remd, style_indices=style_set, use_relu=use_relu, levels_num=len(content_imgs))
             _remd.check_exclusive(remd, regions=resolved.get("regions"), extra_styles=resolved.get("blend"))
             remd_strides = _remd.level_strides(remd, [tuple(c.shape[:2]) for c in content_imgs], [tuple(s.shape[:2]) for s in style_imgs])
+        selfsim = None
+        if self.__selfsim is not None:
+            content_i, style_set, use_relu = resolved.get("taps", (_taps.DEFAULT_CONTENT_INDEX, _taps.DEFAULT_STYLE_INDICES, True))
+            selfsim = _selfsim.normalize_selfsim(*self.__selfsim, content_index=content_i, style_indices=style_set, use_relu=use_relu,
+                                                 levels_num=len(content_imgs))
+            _selfsim.check_exclusive(selfsim, regions=resolved.get("regions"), extra_styles=resolved.get("blend"))
+            selfsim_strides = _selfsim.level_strides(selfsim, [tuple(c.shape[:2]) for c in content_imgs])
         if self.__anchor is not None and len(self.__anchor[0]) != len(content_imgs):
             raise ValueError(f"{len(self.__anchor[0])} anchor levels for a job of {len(content_imgs)} levels")
         job = _make_job(self.__device, self.__optimizer_name, style_imgs, content_imgs, init_img, lr_start, **resolved)
@@ -603,6 +638,12 @@ class NeuralStyleTransfer:
         if remd is not None:                 # (likewise, after the histogram loss)
             try:
                 job.set_relaxed_emd(remd[0], remd_strides, remd[2])
+            except BaseException:
+                job.close()
+                raise
+        if selfsim is not None:              # (likewise, after the relaxed EMD term)
+            try:
+                job.set_self_similarity(selfsim[0], selfsim_strides, selfsim[2])
             except BaseException:
                 job.close()
                 raise
@@ -706,13 +747,15 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
 
 def _transfer_from(content_n_style, content_weight, style_weight, tv_weight, optimizer, model, init_method, iters_num, levels_num,
                    noise_factor, noise_levels, noise_levels_central_amplitude, noise_levels_peripheral_amplitude,
-                   noise_levels_dispersion, *, device=None, start=None, patches=None, semantics=None, histograms=None, remd=None, **keywords):
+                   noise_levels_dispersion, *, device=None, start=None, patches=None, semantics=None, histograms=None, remd=None, selfsim=None,
+                   **keywords):
     """The settings validation of neural_style_transfer() (`keywords`: its keyword-only parameters), here and now - before any
     GPU work, ValueError - and then the job as an async generator, from the `init_method` image or from `start` (_transfer).
     `patches` (patch_match.py): None, or the arguments of NeuralStyleTransfer.set_patch_match, validated here too;
     `semantics`: None, or the arguments of NeuralStyleTransfer.set_patch_semantics, likewise (they need `patches`);
     `histograms` (histogram_loss.py): None, or the arguments of NeuralStyleTransfer.set_histogram_loss, likewise; `remd`
-    (remd_loss.py): None, or the arguments of NeuralStyleTransfer.set_relaxed_emd, likewise."""
+    (remd_loss.py): None, or the arguments of NeuralStyleTransfer.set_relaxed_emd, likewise; `selfsim` (selfsim_loss.py): None, or
+    the arguments of NeuralStyleTransfer.set_self_similarity, likewise."""
     settings = _job.JobSettings(for_job=True, **keywords)
 
     def level_shapes(img):      # (the level sizes follow from the image size: top level first)
@@ -742,6 +785,13 @@ def _transfer_from(content_n_style, content_weight, style_weight, tv_weight, opt
         _remd.check_exclusive(checked, regions=resolved.get("regions"), extra_styles=keywords.get("extra_styles"))
         _remd.level_strides(checked, level_shapes(content_n_style.content[1]), level_shapes(content_n_style.style[1]))
         remd = remd if checked is not None else None
+    if selfsim is not None:
+        content_i, style_set, use_relu = resolved.get("taps", (_taps.DEFAULT_CONTENT_INDEX, _taps.DEFAULT_STYLE_INDICES, True))
+        checked = _selfsim.normalize_selfsim(*selfsim, content_index=content_i, style_indices=style_set, use_relu=use_relu,
+                                             levels_num=max(levels_num, 1))
+        _selfsim.check_exclusive(checked, regions=resolved.get("regions"), extra_styles=keywords.get("extra_styles"))
+        _selfsim.level_strides(checked, level_shapes(content_n_style.content[1]))
+        selfsim = selfsim if checked is not None else None
     extra_styles = keywords.get("extra_styles")
     extra_styles = list(extra_styles) if extra_styles is not None else []
     for img in extra_styles:
@@ -750,20 +800,21 @@ def _transfer_from(content_n_style, content_weight, style_weight, tv_weight, opt
     return _transfer(content_n_style, content_weight, style_weight, tv_weight, optimizer, model, init_method, iters_num, levels_num,
                      noise_factor, noise_levels, noise_levels_central_amplitude, noise_levels_peripheral_amplitude,
                      noise_levels_dispersion, device, settings, keywords.get("preserve_color"), extra_styles,
-                     keywords.get("style_blend"), start, patches, semantics, histograms, remd)
+                     keywords.get("style_blend"), start, patches, semantics, histograms, remd, selfsim)
 
 
 async def _transfer(content_n_style, content_weight, style_weight, tv_weight, optimizer, model, init_method, iters_num, levels_num,
                     noise_factor, noise_levels, noise_levels_central_amplitude, noise_levels_peripheral_amplitude,
                     noise_levels_dispersion, device, settings, preserve_color, extra_styles, style_blend, start=None, patches=None,
-                    semantics=None, histograms=None, remd=None):
+                    semantics=None, histograms=None, remd=None, selfsim=None):
     """neural_style_transfer() below its settings validation: `settings` is its validated JobSettings, `extra_styles` its
     checked list.  `start` (video.py): None, or a callable (setup engine, level-0 (h, w)) -> (start image: a device HWC
     tensor the job starts from in place of the `init_method` image, anchor levels, weight levels, gamma) - the arguments of
     NeuralStyleTransfer.set_anchor - called once the level sizes are known.  `patches` (patch_match.py): None, or the checked
     arguments of NeuralStyleTransfer.set_patch_match; `semantics`: None, or those of NeuralStyleTransfer.set_patch_semantics;
     `histograms` (histogram_loss.py): None, or those of NeuralStyleTransfer.set_histogram_loss; `remd` (remd_loss.py): None,
-    or those of NeuralStyleTransfer.set_relaxed_emd."""
+    or those of NeuralStyleTransfer.set_relaxed_emd; `selfsim` (selfsim_loss.py): None, or those of
+    NeuralStyleTransfer.set_self_similarity."""
     if device is None:
         if not torch.cuda.is_available():
             raise RuntimeError("no GPU visible: the HIP style-transfer engine has no CPU path")
@@ -806,6 +857,8 @@ async def _transfer(content_n_style, content_weight, style_weight, tv_weight, op
         nst.set_histogram_loss(*histograms)
     if remd is not None:
         nst.set_relaxed_emd(*remd)
+    if selfsim is not None:
+        nst.set_self_similarity(*selfsim)
     # (the extra styles as their pyramids; "histogram" has recoloured the style levels above)
     settings.update(extra_styles=extra_levels, style_blend=style_blend if extra_levels else None)
     if preserve_color == "histogram":

@@ -1083,6 +1083,77 @@ int nst_remd_match(nst_ctx* ctx, const float* f, int h, int w, int C, const floa
 int nst_remd_term(nst_ctx* ctx, const float* f, int h, int w, int C, const float* fs, int hs, int ws, int si, int ss, double epsilon,
                   const int* nnA, const int* nnB, int side, float coef, float* value_out /* 3, nullable */, int* side_out /* nullable */,
                   float* grad_out /* nullable */, void* stream);
+/* ---- The self-similarity content term (the content half of Kolkin, Salavon & Shakhnarovich 2019, STROTSS) -------------------
+ * The pattern of pairwise cosine distances between sampled positions of the image must be the content's; the feature vectors
+ * themselves may become anything.  For one pyramid level and one tapped map of index k in Vgg19.layer_names - any map the job
+ * uses, its content map or a style map:
+ *   F  = the map of the level image, NHWC, h x w x C;  Fc = the same map of the level's content image, the same size, through
+ *        the network the job uses (its tap flavour, its pooling, its colour mode);  C = 64, 128, 256 or 512.
+ * Samples.  One stride s in 1..256 per map.  The image samples X_i, i = 0..n-1, are the pixels (a s, b s), a = 0..(h-1)/s,
+ *   b = 0..(w-1)/s (integer division), in row-major order - the relaxed EMD term's rule; the content samples Z_i are the same
+ *   pixels of Fc.  n <= 4096 (the term keeps n x n arrays): a stride that leaves more is refused.
+ * Norms.  rp_i = (float)(1 / sqrt(|X_i|^2 + epsilon)), formed as the relaxed EMD term forms it (double, the same lane and tree
+ *   order); epsilon > 0 (default 1e-5).
+ * Distances.  c(i,j) = <X_i, X_j> rp_i rp_j in the f16x2 arithmetic, exactly the relaxed EMD search's product with the sample set
+ *   on both sides under the one absmax record of the map: i in the dictionary role (the packed operand), j in the column role,
+ *   per 16 channels in ascending order lo_i hi_j, hi_i hi_j, hi_i lo_j into the main and the cross accumulator, then
+ *   c = (((main + cross 2^-11) inv) rp_i) rp_j + 0, every operation rounded in fp32, inv the square of the inverse scale.
+ *   D_ii = 0;  D_ij = max(0, 1 - c(i,j)) otherwise (fp32).  D is used as computed: the two roles accumulate their cross pieces
+ *   in different orders, so D_ij and D_ji need not share bits.
+ * Column normalisation.  s_j = sum_i D_ij in double, in two ordered stages: 16 row blocks of ceil(n / 16) consecutive rows; in
+ *   a block four partial sums, the v-th over the block's rows v, v + 4, ... in ascending order, joined ((p0 + p1) + p2) + p3;
+ *   then the 16 blocks in ascending order, starting from +0.  q_j = 1 / (s_j + epsilon) (double);  N_ij = D_ij q_j (double).
+ *   M is the same thing for the content samples: the setter makes it once by the same launches (it keeps the content's D and
+ *   q), so an image whose maps equal the content's bit for bit has N = M bit for bit.
+ * Value.  selfsim_k = (float)((1/n) sum_ij |N_ij - M_ij|): the mean over the columns of the L1 distance between two
+ *   distributions, which lies in [0, 2] whatever n is - hence the factor 1/n and not the paper's printed 1/n^2, under which
+ *   the term would shrink with the sample count.  The sum in double: per column and row block as for s_j, per column the 16
+ *   blocks in ascending order, then thread u of 256 the columns u, u + 256, ... in ascending order and the 256 threads by a
+ *   tree.  n = 1 gives 0.  A map equal to the content's bit for bit gives exactly 0, constant and all-zero maps included; two
+ *   different constant maps need not (epsilon sits in the norms and in the column sums), only a finite value in [0, 2].
+ * Decisions.  sg_ij = sign(N_ij - M_ij) in {-1, 0, +1}, evaluated on the doubles above and kept as int8; and the clamp: an
+ *   off-diagonal entry with D_ij = 0 passes no gradient.
+ * Gradient, exact wherever the decisions are locally constant.  It reaches sampled pixels only.
+ *   t_j = sum_i sg_ij N_ij (double, in the order of s_j);  E_ij = (sg_ij - t_j) q_j (double), 0 on the diagonal and at clamped
+ *   entries;  W_ij = (float)(E_ij + E_ji);  u_j = rp_j X_j (fp32, one rounding);  g_i = -sum_j W_ij u_j on
+ *   v_mfma_f32_32x32x2_f32 with j ascending from a zero accumulator;  <g_i, u_i> in double (per 32 channels the xor tree with
+ *   offsets 16 .. 1, the 32-channel blocks in ascending order);  dX_i = ((g_i - (float)<g_i, u_i> u_i) rp_i) (float)(w / n),
+ *   fp32, contraction off, the coefficient formed in double.  It joins the addend of the launch below the map after the
+ *   content gradient and the MRF, histogram and relaxed EMD terms' gradients; at the top of the chain it is the addend of the
+ *   1x1 Gram launch, or, on a content map that is no style map, of the mask pass.
+ * Loss row.  A level with the term has the total (... + sum_i w_i remd_i) + sum_k w_k selfsim_k: added after the relaxed EMD
+ *   term, in ascending map order, every product and sum rounded.  NST_LOSS_ROW stays 4.  The weights are the term's own:
+ *   content_weight does not scale it.
+ * Determinism.  No atomic takes part; every reduction has one owner and a fixed order.  A closure with the term is bitwise
+ *   reproducible.
+ *
+ * nst_level_set_selfsim: the term of one level, data of one job like the relaxed EMD term.  content = device (C,h,w) image in
+ *   the job's colour mode, of the level's size, NULL: clear the level's term.  weights[6], stride[6] by map index (all six
+ *   strides are checked).  The call runs the content image through the network up to the deepest weighted map, keeps per
+ *   weighted map the content's D and q, and allocates everything a closure needs.  Life cycle of nst_level_set_remd.
+ *   NST_E_ARG: level out of range; negative or non-finite weights; epsilon <= 0 or not finite; a stride outside 1..256; a
+ *   size other than the level's; a positive weight on a map the job does not use (neither its content map nor a style map);
+ *   more than 4096 samples on a weighted map.
+ *   NST_E_STATE: no configured job; an arithmetic mode other than f16x2; a guided level (nst_level_set_guidance on a level with
+ *   the term refuses likewise); a context with use_graph.  The stripe closure returns NST_E_STATE while its level carries the
+ *   term.
+ * nst_level_selfsim: the level's setting (all-zero weights: no term); every output is nullable.
+ * nst_job_selfsim_losses: out = device, levels x 6: the unweighted selfsim_k of the last closure by map index (zeros: maps
+ *   without the term and levels outside the last level mask).
+ * nst_level_selfsim_decisions: the last closure's D (n x n float), s (n double) and sg (n x n int8) of one weighted map,
+ *   device pointers, each nullable; zeros before any closure.  NST_E_STATE: the map carries no term on the level.
+ * nst_selfsim_matrix, nst_selfsim_term: the pieces alone, on NHWC device maps.  They read no job state.  Synchronous.
+ *   nst_selfsim_term: f against fc (both h x w x C).  coef is the weight w of the definition.  value_out = device float;
+ *   sg_out = device, n x n int8; grad_out = NHWC like f, overwritten (zero off the sample grid); each nullable. */
+int nst_level_set_selfsim(nst_ctx* ctx, int level, const float* content /* device (C,h,w), or NULL: clear */, int h, int w,
+                          const float* weights /* 6, by map index */, const int* stride /* 6 */, double epsilon, void* stream);
+int nst_level_selfsim(const nst_ctx* ctx, int level, float* weights /* 6 */, int* stride /* 6 */, double* epsilon);
+int nst_job_selfsim_losses(nst_ctx* ctx, float* out /* device, levels x 6 */, void* stream);
+int nst_level_selfsim_decisions(nst_ctx* ctx, int level, int map, float* D_out, double* s_out, signed char* sg_out, void* stream);
+int nst_selfsim_matrix(nst_ctx* ctx, const float* f, int h, int w, int C, int stride, double epsilon, float* D_out /* n x n, nullable */,
+                       double* s_out /* n, nullable */, void* stream);
+int nst_selfsim_term(nst_ctx* ctx, const float* f, const float* fc, int h, int w, int C, int stride, double epsilon, float coef,
+                     float* value_out /* nullable */, signed char* sg_out /* nullable */, float* grad_out /* nullable */, void* stream);
 int nst_warp_bilinear(nst_ctx* ctx, const float* src, const float* flow, int C, int h, int w, float* out,
                       float* valid /* nullable */, void* stream);
 int nst_flow_weights(nst_ctx* ctx, const float* fwd, const float* bwd, int h, int w, float* out, void* stream);
