@@ -46,6 +46,16 @@ class StepInfo(C.Structure):
                 ("loss", C.c_float), ("lr", C.c_float), ("t", C.c_float), ("history", C.c_int)]
 
 
+NST_GRAM_BATCH_MAX = 16
+
+
+class GramBatchItem(C.Structure):
+    """nst_gram_batch_item: the inputs of one map of nst_gram_batch and what the call reports back on the host."""
+    _fields_ = [("f", C.c_void_p), ("C", C.c_int), ("h", C.c_int), ("w", C.c_int), ("guide", C.c_void_p), ("target", C.c_void_p),
+                ("coef", C.c_float), ("gram", C.c_void_p), ("S", C.c_void_p), ("S_bf", C.c_void_p), ("mse", C.c_double),
+                ("S_absmax", C.c_float), ("nsplit", C.c_int), ("pix_per_split", C.c_longlong)]
+
+
 class Options(C.Structure):
     """nst_options: -1 = take the environment variable (read once at context creation), else the default."""
     _fields_ = [("struct_size", C.c_int), ("conv_mode", C.c_int), ("batched", C.c_int), ("single_stream", C.c_int),
@@ -146,6 +156,7 @@ SYMBOLS = {
     "nst_job_gram_shift": (C.c_int, [c_void, c_float_p, C.POINTER(C.c_uint)]),
     "nst_level_gram_offsets": (C.c_int, [c_void, C.c_int, C.c_int, c_void, c_void]),
     "nst_gram_shifted": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, c_void, c_void, c_void]),
+    "nst_gram_batch": (C.c_int, [c_void, C.POINTER(GramBatchItem), C.c_int, C.c_int, c_void]),
     "nst_job_set_moments": (C.c_int, [c_void, c_float_p, c_float_p, C.c_float]),
     "nst_job_moments": (C.c_int, [c_void, c_float_p, c_float_p, c_float_p]),
     "nst_job_moment_losses": (C.c_int, [c_void, c_void, c_void]),

@@ -798,7 +798,7 @@ static int gram_nsplit_in_batch(const GramBatch& b, int i) {
 // own partial buffer of nsplit x C x C floats).  Fills nsplit / pix_per_split / the block prefixes.
 // pack (nst_ctx_set_gram_pack): the PACK kernels, and a plain batch's two tile shapes in one grid; 0: the parent's kernels
 // and launch sequence
-hipError_t launch_gram_batch(const GramBatch& b0, hipStream_t stream, int pack) {
+hipError_t launch_gram_batch(const GramBatch& b0, hipStream_t stream, int pack, GramGeometry* geo) {
     if (b0.n < 1 || b0.n > NST_GRAM_BATCH_MAX) return hipErrorInvalidValue;
     // a batch is guided as a whole (every item carries its guidance plane) or not at all
     const bool guided = b0.it[0].guide != nullptr;
@@ -829,6 +829,7 @@ hipError_t launch_gram_batch(const GramBatch& b0, hipStream_t stream, int pack) 
             it.pix_per_split = ((chunks + it.nsplit - 1) / it.nsplit) * kp;
             // 32-bit buffer offsets inside ONE split (the map itself may be larger)
             if (it.pix_per_split * (size_t)it.C * 4 >= 0xFFFFFF00ull) return hipErrorInvalidValue;
+            if (geo) geo[i] = GramGeometry{it.nsplit, it.pix_per_split};
             it.part_end = (b.n ? b.it[b.n - 1].part_end : 0) + pairs * it.nsplit;
             ++b.n;
         }

@@ -118,6 +118,64 @@ int nst_gram_shifted(nst_ctx* ctx, const float* f, int C, int h, int w, int norm
     return sc.finish();
 }
 
+// the closure's batched Gram launch on the caller's maps (one launch_gram_batch under the context's gram_pack), beside nst_gram_shifted
+int nst_gram_batch(nst_ctx* ctx, nst_gram_batch_item* items, int n, int normalize, void* stream) {
+    NSTCHK(bind(ctx));
+    if (!items || n < 1 || n > NST_GRAM_BATCH_MAX) return fail(ctx, NST_E_ARG, "a Gram batch takes 1 .. NST_GRAM_BATCH_MAX items");
+    if (ctx->conv_mode != 2) return fail(ctx, NST_E_STATE, "the Gram batch runs in the f16x2 arithmetic only (NST_CONV unset)");
+    for (int i = 0; i < n; ++i) {
+        const nst_gram_batch_item& a = items[i];
+        if (!a.f || !a.gram || a.h < 1 || a.w < 1) return fail(ctx, NST_E_ARG, "bad argument");
+        if (!(a.C == 64 || (a.C >= 128 && a.C % 128 == 0))) return fail(ctx, NST_E_ARG, "the Gram batch takes C = 64 or a multiple of 128");
+        if ((a.guide != nullptr) != (items[0].guide != nullptr)) return fail(ctx, NST_E_ARG, "a Gram batch is guided as a whole or not at all");
+        if (!a.target && (a.S || a.S_bf)) return fail(ctx, NST_E_ARG, "S and S_bf need a target");
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Scratch sc(ctx, s);
+    GramBatch gb{};
+    gb.n = n;
+    for (int i = 0; i < n; ++i) {
+        const nst_gram_batch_item& a = items[i];
+        const size_t N = (size_t)a.h * a.w;
+        float* nhwc = nullptr; float* part = nullptr; unsigned* amax = nullptr; unsigned* s_amax = nullptr; double* partial = nullptr;
+        NSTCHK(sc.alloc(&nhwc, N * a.C));
+        NSTCHK(sc.alloc(&part, (size_t)gram_nsplit(a.C, N) * a.C * a.C));
+        NSTCHK(sc.alloc(&amax, (size_t)NST_AMAX_SLOTS));
+        if (a.target) {
+            NSTCHK(sc.alloc(&s_amax, (size_t)NST_AMAX_SLOTS));
+            NSTCHK(sc.alloc(&partial, (size_t)gram_finish_blocks(a.C)));
+        }
+        if (launch_chw_to_hwc(a.f, a.C, a.h, a.w, nhwc, s) != hipSuccess) return fail(ctx, NST_E_HIP, "chw_to_hwc launch failed");
+        if (launch_zero(amax, NST_AMAX_SLOTS, s) != hipSuccess || launch_absmax_slots(nhwc, N * a.C, amax, s) != hipSuccess)
+            return fail(ctx, NST_E_HIP, "absmax launch failed");
+        if (s_amax && launch_zero(s_amax, NST_AMAX_SLOTS, s) != hipSuccess) return fail(ctx, NST_E_HIP, "zero launch failed");
+        GramItem& it = gb.it[i];
+        it.f = nhwc; it.N = N; it.C = a.C; it.amax = amax; it.part = part; it.guide = a.guide;
+        it.divisor = normalize ? (float)((double)a.C * a.h * a.w) : 1.f;
+        it.target = a.target; it.coef = a.coef; it.gram_out = a.gram; it.S = a.S; it.S_bf = a.S_bf; it.S_amax = s_amax;
+        it.mse_partial = partial;
+    }
+    GramGeometry geo[NST_GRAM_BATCH_MAX] = {};
+    HIPCHK(ctx, launch_gram_batch(gb, s, ctx->gram_pack, geo));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    std::vector<double> partial;
+    for (int i = 0; i < n; ++i) {
+        nst_gram_batch_item& a = items[i];
+        a.nsplit = geo[i].nsplit;
+        a.pix_per_split = (long long)geo[i].pix_per_split;
+        a.mse = 0.0;
+        a.S_absmax = 0.f;
+        if (!a.target) continue;
+        partial.resize((size_t)gram_finish_blocks(a.C));
+        float words[NST_AMAX_SLOTS];
+        HIPCHK(ctx, hipMemcpy(partial.data(), gb.it[i].mse_partial, partial.size() * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(ctx, hipMemcpy(words, gb.it[i].S_amax, sizeof(words), hipMemcpyDeviceToHost));
+        for (double v : partial) a.mse += v;
+        for (float v : words) a.S_absmax = std::max(a.S_absmax, v);
+    }
+    return sc.finish();
+}
+
 // the moment statistic alone (nst_job_set_moments has the definition), beside nst_gram_shifted: the closure's kernels
 int nst_moments(nst_ctx* ctx, const float* f, int C, int h, int w, float epsilon, float* mean_out, float* std_out, void* stream) {
     NSTCHK(bind(ctx));

@@ -418,7 +418,9 @@ int gram_nslabs(int C, int nsplit);
 // Several Gram matrices in two partial launches (one per tile shape; a plain batch under `pack`: one for both) + one finish
 // launch.  pack (nst_ctx_set_gram_pack): the kernels that skip the below-diagonal blocks of a diagonal tile.  Per item the caller sets
 // f, N, C, amax, part (its own gram_nsplit(C, N) x C x C floats) and the finish arguments; the rest is filled in.
-constexpr int NST_GRAM_BATCH_MAX = 16;
+#ifndef NST_GRAM_BATCH_MAX
+#define NST_GRAM_BATCH_MAX 16      // (include/nst_hip.h states the same number for nst_gram_batch)
+#endif
 struct GramItem {
     const float* f; size_t N; int C; const unsigned* amax; float* part;
     float divisor; const float* target; float coef; float* gram_out; float* S; unsigned short* S_bf; unsigned* S_amax;
@@ -428,7 +430,10 @@ struct GramItem {
     const float* offset;  // shifted Gram (gram_shift.hip): o[C] added to every staged value, `amax` the shifted operand's record; nullptr: plain
 };
 struct GramBatch { GramItem it[NST_GRAM_BATCH_MAX]; int n; };
-hipError_t launch_gram_batch(const GramBatch& b, hipStream_t stream, int pack = 1);
+// what the launcher filled in for item i of the caller's batch: its splits (= slabs) and the pixels of one split
+struct GramGeometry { int nsplit; size_t pix_per_split; };
+// geo (nullable): b.n entries, the geometry of every item as launched
+hipError_t launch_gram_batch(const GramBatch& b, hipStream_t stream, int pack = 1, GramGeometry* geo = nullptr);
 #define NST_GRAM_FINISH_EPB 128      // elements of G a block of the finish pass owns (one partial sum of (G-Gt)^2 each)
 int gram_finish_blocks(int C);
 // S_amax (nullable): NST_AMAX_SLOTS words receiving the absmax of S (atomic max; zero them beforehand).

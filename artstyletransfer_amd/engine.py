@@ -1351,6 +1351,46 @@ class StyleEngine:
                                                        _ptr(g), _ptr(o), _stream(self.device)), "nst_gram_shifted")
         return g, o
 
+    def gram_batch(self, maps, guides=None, targets=None, coefs=None, normalize: bool = True, want_S_bf: bool = False):
+        """The closure's batched Gram launch on the caller's maps (nst_gram_batch): one launch for 1 .. 16 (1,C,h,w) maps, C = 64
+        or a multiple of 128, under the context's gram_pack.  guides: None, or one (h,w) plane in [0,1] per map (the guided
+        form); targets / coefs: None, or per map a (C,C) target or None and its coefficient.  Returns one dict per map: G
+        (1,C,C), nsplit and pix_per_split (the launcher's geometry), and with a target S (C,C), mse (the sum of (G - Gt)^2 in
+        double), S_absmax and, when asked for, S_bf ((C, C/32, 3, 32) int16 words)."""
+        n = len(maps)
+        if not 1 <= n <= _lib.NST_GRAM_BATCH_MAX:
+            raise NstError(f"a Gram batch takes 1 .. {_lib.NST_GRAM_BATCH_MAX} maps")
+        items = (_lib.GramBatchItem * n)()
+        outs = []
+        for i, f in enumerate(maps):
+            _chk_dev(f, self.device)
+            b, c, h, w = f.shape
+            assert b == 1
+            t = targets[i] if targets is not None else None
+            g = guides[i] if guides is not None else None
+            out = {"G": torch.empty((1, c, c), dtype=torch.float32, device=self.device)}
+            if g is not None:
+                _chk_dev(g, self.device, (h, w))
+            if t is not None:
+                _chk_dev(t, self.device, (c, c))
+                out["S"] = torch.empty((c, c), dtype=torch.float32, device=self.device)
+                if want_S_bf:
+                    out["S_bf"] = torch.empty((c, c // 32, 3, 32), dtype=torch.int16, device=self.device)
+            items[i].f, items[i].C, items[i].h, items[i].w = f.data_ptr(), c, h, w
+            items[i].guide = g.data_ptr() if g is not None else None
+            items[i].target = t.data_ptr() if t is not None else None
+            items[i].coef = float(coefs[i]) if (coefs is not None and t is not None) else 0.0
+            items[i].gram = out["G"].data_ptr()
+            items[i].S = out["S"].data_ptr() if "S" in out else None
+            items[i].S_bf = out["S_bf"].data_ptr() if "S_bf" in out else None
+            outs.append(out)
+        _lib.check(self.ctx, self.lib.nst_gram_batch(self.ctx, items, n, int(normalize), _stream(self.device)), "nst_gram_batch")
+        for it, out in zip(items, outs):
+            out["nsplit"], out["pix_per_split"] = int(it.nsplit), int(it.pix_per_split)
+            if "S" in out:
+                out["mse"], out["S_absmax"] = float(it.mse), float(it.S_absmax)
+        return outs
+
     def guided_gram_backward(self, f: torch.Tensor, planes: torch.Tensor, s_mats: torch.Tensor, addend: Optional[torch.Tensor] = None,
                              relu_bits: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, want_absmax: bool = False):
         """The guided Gram backward launch on its own (nst_guided_gram_backward): out (N,C) = addend + sum_r t_r^2 . f . S_r for

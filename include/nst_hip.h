@@ -345,6 +345,43 @@ int nst_level_gram_offsets(nst_ctx* ctx, int level, int slot, float* out, void* 
 int nst_gram_shifted(nst_ctx* ctx, const float* f, int C, int h, int w, int normalize, int center, float shift, float* gram,
                      float* offset_out /* nullable, C floats */, void* stream);
 
+/* nst_gram_batch: the closure's own Gram launch on the caller's maps - what a closure does with the style maps of its
+ * pyramid levels, as a stand-alone call.  n items, 1 <= n <= NST_GRAM_BATCH_MAX; per item the planar map is made
+ * pixel-major and its absmax recorded (as nst_gram does), then ONE batched launch under the context's gram_pack setting:
+ * the partial products of every item - both tile shapes in one grid when packed, a smaller map of a channel count with
+ * fewer splits than a lone map of its size gets - and one finish pass.  Per item:
+ *   f        device (C,h,w); C = 64 or a multiple of 128
+ *   guide    nullable, for ALL items or for none: device h w floats in [0,1], the guided Gram sum_p t(p)^2 F(p) F(p)^T
+ *   target   nullable: device (C,C); with it the finish pass makes S = coef (G - target), one subtraction and one
+ *            multiplication in fp32, the sum of (G - target)^2 in double and the absmax of S
+ *   gram     device (C,C), required: G = (sum of the slabs) / (C h w), or the bare sum with normalize = 0
+ *   S        nullable, device (C,C);  S_bf nullable, device 3 C C 16-bit words: S cut into three bf16 pieces (the truncated
+ *            high 16 bits, then those of each remainder) at [row][col / 32][piece][col % 32]
+ *   outputs on the HOST, written before the call returns: mse (the finish blocks' partial sums added in block order; 0
+ *   without a target), S_absmax (the maximum of the record's words; 0 without a target), nsplit and pix_per_split (the
+ *   geometry the launcher used: splits = slabs, pixels of one split).
+ * NST_E_STATE outside the f16x2 arithmetic (the batch has no other form).  NST_E_ARG: n out of range, a null f or gram,
+ * a C other than 64 or a multiple of 128, guided and unguided items mixed, S or S_bf without a target.  Reads no job
+ * state; every buffer it needs is scratch of the call.  Synchronous on `stream`, as nst_gram. */
+#ifndef NST_GRAM_BATCH_MAX
+#define NST_GRAM_BATCH_MAX 16
+#endif
+typedef struct nst_gram_batch_item {
+    const float* f;
+    int C, h, w;
+    const float* guide;
+    const float* target;
+    float coef;
+    float* gram;
+    float* S;
+    unsigned short* S_bf;
+    double mse;
+    float S_absmax;
+    int nsplit;
+    long long pix_per_split;
+} nst_gram_batch_item;
+int nst_gram_batch(nst_ctx* ctx, nst_gram_batch_item* items, int n, int normalize, void* stream);
+
 /* Moment loss: the channel means and standard deviations of the style maps matched to the style's, a setting of the
  * context.  The reference has no counterpart.  It is the "BN statistics matching" of Li, Wang, Liu & Hou, "Demystifying
  * Neural Style Transfer" (2017), and the style loss of Huang & Belongie, "Arbitrary Style Transfer in Real-time with

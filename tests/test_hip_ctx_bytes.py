@@ -136,6 +136,7 @@ def test_standalone_calls_leave_the_count_where_it_was(eng):
         "nst_gram_shifted (shift)": lambda: eng.gram_shifted(f, shift=0.5),
         "nst_gram_shifted (center)": lambda: eng.gram_shifted(f, center=True),
         "nst_gram_shifted (plain)": lambda: eng.gram_shifted(f),
+        "nst_gram_batch": lambda: eng.gram_batch([f, f], targets=[eng.gram(f)[0].contiguous(), None], coefs=[1.0, 0.0], want_S_bf=True),
         "nst_moments": lambda: eng.moments(f),
         "nst_level_activation (a map the pass left out)": lambda: eng.level_activation(0, 1),
         "nst_level_activation": lambda: eng.level_activation(1, 9),

@@ -52,6 +52,26 @@ def test_options_struct_matches_the_header():
     assert [getattr(o, f[0]) for f in _lib.Options._fields_[1:]] == [-1] * 13
 
 
+def test_gram_batch_item_matches_the_header_and_refuses_without_a_context():
+    """The ctypes mirror of nst_gram_batch_item has the header's fields in the header's order; NST_GRAM_BATCH_MAX is the
+    header's; the entry refuses a null context (NST_E_ARG) before it reads an item.  (The refusals that need a context - the
+    arithmetic, the channel count, mixed guidance - are in tests/test_hip_gram_local.py.)"""
+    from artstyletransfer_amd import _lib
+    text = open(os.path.join(ROOT, "include", "nst_hip.h")).read()
+    body = re.search(r"typedef struct nst_gram_batch_item \{(.*?)\} nst_gram_batch_item;", text, flags=re.S).group(1)
+    names = [n for decl in re.findall(r"[a-z_ ]+\*?\s+\*?([A-Za-z_, ]+);", body) for n in decl.replace(" ", "").split(",")]
+    assert names == [f[0] for f in _lib.GramBatchItem._fields_]
+    assert int(re.search(r"#define NST_GRAM_BATCH_MAX (\d+)", text).group(1)) == _lib.NST_GRAM_BATCH_MAX
+    kernels = open(os.path.join(ROOT, "artstyletransfer_amd", "csrc", "nst_kernels.h")).read()
+    assert int(re.search(r"#define NST_GRAM_BATCH_MAX (\d+)", kernels).group(1)) == _lib.NST_GRAM_BATCH_MAX
+    assert re.search(r"int nst_gram_batch\(nst_ctx\* ctx, nst_gram_batch_item\* items, int n, int normalize, void\* stream\);", text)
+    lib = _lib.load()
+    items = (_lib.GramBatchItem * 2)()
+    assert lib.nst_gram_batch(None, items, 2, 1, None) == -1      # NST_E_ARG
+    assert b"null context" in lib.nst_last_error(None)
+    assert items[0].nsplit == 0 and items[0].mse == 0.0
+
+
 def test_no_gpu_is_an_error_not_a_fallback(vgg_weights):
     import torch
     from artstyletransfer_amd import _lib
