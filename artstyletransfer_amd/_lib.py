@@ -135,6 +135,13 @@ SYMBOLS = {
     "nst_selfsim_matrix": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, c_void, c_void, c_void]),
     "nst_selfsim_term": (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_float, c_void, c_void,
                                    c_void, c_void]),
+    "nst_level_set_xcorr": (C.c_int, [c_void, C.c_int, c_void, C.c_int, C.c_int, c_float_p, C.POINTER(C.c_int), C.c_int, c_void]),
+    "nst_level_xcorr": (C.c_int, [c_void, C.c_int, c_float_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "nst_job_xcorr_losses": (C.c_int, [c_void, c_void, c_void]),
+    "nst_level_xcorr_matrices": (C.c_int, [c_void, C.c_int, C.c_int, c_void, c_void]),
+    "nst_xcorr": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, c_void, C.POINTER(C.c_int), c_void]),
+    "nst_xcorr_term": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, C.POINTER(C.c_int), C.c_int, C.c_float, c_void, c_void,
+                                 c_void]),
     "nst_warp_bilinear": (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, c_void, c_void]),
     "nst_flow_weights": (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, c_void, c_void]),
     "nst_anchor_fold": (C.c_int, [c_void, C.c_int, C.POINTER(c_void), C.POINTER(c_void), C.c_int, C.c_int, C.c_int, c_void, c_void,

@@ -666,6 +666,92 @@ int nst_selfsim_term(nst_ctx* ctx, const float* f, const float* fc, int h, int w
     return sc.finish();
 }
 
+// The long-range style term's pieces on their own (include/nst_hip.h has the definition): the kernels of xcorr.hip on scratch
+// buffers.  Synchronous.
+// the n items of one map on scratch (the absmax record, per shift the slabs); G, and with a target S, St and sq, are the caller's
+static int xcorr_items(nst_ctx* ctx, Scratch& sc, const float* f, int h, int w, int C, const int* shifts, int n, XcorrItem* items,
+                       int* geometry_out, hipStream_t s) {
+    if (!f || !shifts) return fail(ctx, NST_E_ARG, "null argument");
+    if (ctx->conv_mode != 2) return fail(ctx, NST_E_STATE, "the xcorr term runs in the f16x2 arithmetic only (NST_CONV unset)");
+    if (C != 64 && C != 128 && C != 256 && C != 512) return fail(ctx, NST_E_ARG, "the xcorr term takes maps of 64, 128, 256 or 512 channels");
+    if (n < 1 || n > XCORR_MAX_SHIFTS) return fail(ctx, NST_E_ARG, "the xcorr term takes 1..16 shifts");
+    unsigned* amax = nullptr;
+    NSTCHK(sc.alloc(&amax, (size_t)NST_AMAX_SLOTS));
+    HIPCHK(ctx, launch_zero(amax, (size_t)NST_AMAX_SLOTS, s));
+    for (int d = 0; d < n; ++d) {
+        XcorrGeometry geo;
+        if (!xcorr_geometry(C, h, w, shifts[2 * d], shifts[2 * d + 1], &geo))
+            return fail(ctx, NST_E_ARG, "a shift (dx, dy) has 0 <= dx < w, 0 <= dy < h, not both 0 (or the map is too large)");
+        if (geometry_out) { geometry_out[2 * d] = geo.nsplit; geometry_out[2 * d + 1] = geo.pix_per_split; }
+        XcorrItem& it = items[d];
+        it = XcorrItem{};
+        NSTCHK(sc.alloc(&it.part, (size_t)geo.nsplit * C * C));
+        it.f = f; it.amax = amax; it.C = C; it.h = h; it.w = w; it.dx = shifts[2 * d]; it.dy = shifts[2 * d + 1];
+        it.divisor = (float)((double)C * (double)(h - it.dy) * (double)(w - it.dx));
+    }
+    HIPCHK(ctx, launch_absmax_slots(f, (size_t)h * w * C, amax, s));
+    return NST_OK;
+}
+static int xcorr_launch(nst_ctx* ctx, const XcorrItem* items, int n, hipStream_t s) {
+    for (int d0 = 0; d0 < n; d0 += XCORR_BATCH_MAX) {
+        XcorrBatch b{};
+        b.n = std::min(n - d0, XCORR_BATCH_MAX);
+        for (int d = 0; d < b.n; ++d) b.it[d] = items[d0 + d];
+        HIPCHK(ctx, launch_xcorr_batch(b, s));
+    }
+    return NST_OK;
+}
+
+int nst_xcorr(nst_ctx* ctx, const float* f, int h, int w, int C, const int* shifts, int n, float* out, int* geometry_out, void* stream) {
+    NSTCHK(bind(ctx));
+    if (!out) return fail(ctx, NST_E_ARG, "null argument");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Scratch sc(ctx, s);
+    XcorrItem items[XCORR_MAX_SHIFTS];
+    NSTCHK(xcorr_items(ctx, sc, f, h, w, C, shifts, n, items, geometry_out, s));
+    for (int d = 0; d < n; ++d) items[d].G = out + (size_t)d * C * C;
+    NSTCHK(xcorr_launch(ctx, items, n, s));
+    return sc.finish();
+}
+
+int nst_xcorr_term(nst_ctx* ctx, const float* f, int h, int w, int C, const float* gt, const int* shifts, int n, float coef, float* value_out,
+                   float* grad_out, void* stream) {
+    NSTCHK(bind(ctx));
+    if (!gt || (!value_out && !grad_out)) return fail(ctx, NST_E_ARG, "null argument");
+    if (!std::isfinite(coef)) return fail(ctx, NST_E_ARG, "the coefficient must be finite");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Scratch sc(ctx, s);
+    XcorrItem items[XCORR_MAX_SHIFTS];
+    NSTCHK(xcorr_items(ctx, sc, f, h, w, C, shifts, n, items, nullptr, s));
+    const size_t CC = (size_t)C * C;
+    float* S = nullptr; float* St = nullptr; double* sq = nullptr; float* val = nullptr;
+    NSTCHK(sc.alloc(&S, (size_t)n * CC));
+    NSTCHK(sc.alloc(&St, (size_t)n * CC));
+    NSTCHK(sc.alloc(&sq, (size_t)n * xcorr_finish_blocks(C)));
+    NSTCHK(sc.alloc(&val, 4));
+    for (int d = 0; d < n; ++d) {
+        XcorrItem& it = items[d];
+        it.target = gt + d * CC; it.S = S + d * CC; it.St = St + d * CC; it.sq = sq + (size_t)d * xcorr_finish_blocks(C);
+        it.coef = (float)(2.0 * (double)coef / ((double)n * (double)C * (double)C * (double)C * (double)(h - it.dy) * (double)(w - it.dx)));
+    }
+    NSTCHK(xcorr_launch(ctx, items, n, s));
+    if (value_out) {
+        XcorrValueBatch vb{};
+        vb.n = 1;
+        vb.it[0] = XcorrValueItem{sq, n, xcorr_finish_blocks(C), (double)C * (double)C, val};
+        HIPCHK(ctx, launch_xcorr_values(vb, s));
+        HIPCHK(ctx, hipMemcpyAsync(value_out, val, sizeof(float), hipMemcpyDeviceToDevice, s));
+    }
+    if (grad_out) {
+        XcorrGrad g{};
+        g.f = f; g.h = h; g.w = w; g.C = C; g.nd = n;
+        for (int d = 0; d < n; ++d) { g.dx[d] = items[d].dx; g.dy[d] = items[d].dy; }
+        g.S = S; g.St = St; g.out = grad_out; g.accumulate = 0;
+        HIPCHK(ctx, launch_xcorr_grad(g, s));
+    }
+    return sc.finish();
+}
+
 // The warp of a sequence (include/nst_hip.h): out = src sampled bilinearly at p + flow(p), valid (nullable) = the four taps
 // lie inside the image.  Synchronous.
 int nst_warp_bilinear(nst_ctx* ctx, const float* src, const float* flow, int C, int h, int w, float* out, float* valid, void* stream) {

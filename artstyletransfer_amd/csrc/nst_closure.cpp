@@ -401,13 +401,96 @@ int selfsim_forward(nst_ctx* ctx, LevelWs& L, hipStream_t s) {
     return NST_OK;
 }
 
-// ---- the per-map terms together (MapTerm in nst_ctx.h): MRF, histogram loss, relaxed EMD, self-similarity - always in this order
+// ---- the long-range style term (include/nst_hip.h has the definition; kernels: xcorr.hip) -----------------------------------
+// item (map index i, shift d) of level L: the level's own map with its absmax record, the shift's slabs, Z_d, the target and the
+// coefficient 2 w_i / (|D| C^2 Z_d) formed in double, and the places of G_d, S_d, S_d^T and the partial sums of squares
+double xcorr_divisor(int C, int h, int w, int dx, int dy) { return (double)C * (double)(h - dy) * (double)(w - dx); }
+float xcorr_coef(float wgt, int nd, int C, double Z) { return (float)(2.0 * (double)wgt / ((double)nd * (double)C * (double)C * Z)); }
+XcorrItem xcorr_item_of(const LevelWs& L, int i, int d) {
+    const XcorrLevel& g = L.xcorr;
+    const int l = kTapLayer[i], C = kCout[l], h = L.acts.h[l], w = L.acts.w[l];
+    const size_t CC = (size_t)C * C;
+    const double Z = xcorr_divisor(C, h, w, g.dx[d], g.dy[d]);
+    XcorrItem it{};
+    it.f = L.acts.act[l]; it.amax = amax_act(L.acts, l); it.part = g.part[i][d];
+    it.C = C; it.h = h; it.w = w; it.dx = g.dx[d]; it.dy = g.dy[d];
+    it.divisor = (float)Z;
+    it.target = g.Gt[i] + d * CC; it.coef = xcorr_coef(g.w[i], g.nd, C, Z);
+    it.G = g.G[i] + d * CC; it.S = g.S[i] + d * CC; it.St = g.St[i] + d * CC;
+    it.sq = g.sq[i] + (size_t)d * xcorr_finish_blocks(C);
+    return it;
+}
+// forward part of the levels lv[0..n), once their maps exist: every (level, weighted map, shift) in one value launch and one
+// finish launch (XCORR_BATCH_MAX items a launch), then xcorr_i of every (level, weighted map) in one launch (levels without
+// the term: no launch)
+int xcorr_forward(nst_ctx* ctx, const int* lv, int n, hipStream_t s) {
+    XcorrBatch b{};
+    XcorrValueBatch vb{};
+    double flops = 0.0;
+    auto flush = [&]() -> int {
+        if (b.n == 0) return NST_OK;
+        Timer tm(ctx, s, K_OTHER, flops, b.n, 1, 0, 0, 1, 250);      // (timed as a whole, layer tag 250)
+        HIPCHK(ctx, launch_xcorr_batch(b, s));
+        b.n = 0; flops = 0.0;
+        return NST_OK;
+    };
+    for (int k = 0; k < n; ++k) {
+        const LevelWs& L = ctx->lv[lv[k]];
+        for (int i = 0; i < 6 && L.xcorr.on(); ++i) {
+            if (!(L.xcorr.w[i] > 0.f)) continue;
+            const int C = kCout[kTapLayer[i]];
+            for (int d = 0; d < L.xcorr.nd; ++d) {
+                if (b.n == XCORR_BATCH_MAX) NSTCHK(flush());
+                const XcorrItem it = xcorr_item_of(L, i, d);
+                flops += 2.0 * (double)(it.h - it.dy) * (double)(it.w - it.dx) * (double)C * (double)C;
+                b.it[b.n++] = it;
+            }
+            vb.it[vb.n++] = XcorrValueItem{L.xcorr.sq[i], L.xcorr.nd, xcorr_finish_blocks(C), (double)C * (double)C, L.xcorr.vals + i};
+        }
+    }
+    NSTCHK(flush());
+    if (vb.n > 0) {
+        Timer tm(ctx, s, K_OTHER, 0);
+        HIPCHK(ctx, launch_xcorr_values(vb, s));
+    }
+    return NST_OK;
+}
+// the term's share of the loss rows, behind the loss assembly (a closure none of whose levels in the mask carries the term: no
+// launch, and the rows are what that assembly left)
+int xcorr_loss_rows(nst_ctx* ctx, unsigned level_mask, float* losses, hipStream_t s) {
+    XcorrRows r{};
+    r.levels = ctx->levels; r.out = losses;
+    bool any = false;
+    for (int i = 0; i < ctx->levels; ++i) {
+        const XcorrLevel& g = ctx->lv[i].xcorr;
+        r.lv[i].owned = (int)((level_mask >> i) & 1u);
+        if (!g.on()) continue;
+        r.lv[i].vals = g.vals;
+        for (int k = 0; k < 6; ++k) r.lv[i].w[k] = g.w[k];
+        any = true;
+    }
+    if (any) HIPCHK(ctx, launch_xcorr_rows(r, s));
+    return NST_OK;
+}
+// the gradient launch of map index i of level L into dst
+XcorrGrad xcorr_grad_of(const LevelWs& L, int i, float* dst, bool held) {
+    const XcorrLevel& g = L.xcorr;
+    const int l = kTapLayer[i];
+    XcorrGrad x{};
+    x.f = L.acts.act[l]; x.h = L.acts.h[l]; x.w = L.acts.w[l]; x.C = kCout[l]; x.nd = g.nd;
+    for (int d = 0; d < g.nd; ++d) { x.dx[d] = g.dx[d]; x.dy[d] = g.dy[d]; }
+    x.S = g.S[i]; x.St = g.St[i]; x.out = dst; x.accumulate = held ? 1 : 0;
+    return x;
+}
+
+// ---- the per-map terms together (MapTerm in nst_ctx.h): MRF, histogram loss, relaxed EMD, self-similarity, xcorr - always in this order
 // forward parts of the levels lv[0..n), once their maps exist: every level of one term before the next term
 int map_terms_forward(nst_ctx* ctx, const int* lv, int n, hipStream_t s) {
     for (int k = 0; k < n; ++k) NSTCHK(patch_forward(ctx, ctx->lv[lv[k]], s));
     for (int k = 0; k < n; ++k) NSTCHK(hist_forward(ctx, ctx->lv[lv[k]], s));
     for (int k = 0; k < n; ++k) NSTCHK(remd_forward(ctx, ctx->lv[lv[k]], s));
     for (int k = 0; k < n; ++k) NSTCHK(selfsim_forward(ctx, ctx->lv[lv[k]], s));
+    NSTCHK(xcorr_forward(ctx, lv, n, s));
     return NST_OK;
 }
 // gradient parts of conv layer m of level L, of the terms the map carries, into dst (the map's shape).  `held`: dst holds an
@@ -437,6 +520,13 @@ int map_terms_backward(nst_ctx* ctx, const LevelWs& L, int m, float* dst, bool& 
         Timer tm(ctx, s, K_OTHER, 0, x.count, 1, x.count, x.C, 1, 230 + i);
         HIPCHK(ctx, launch_selfsim_grad(x, selfsim_term_of(L, i), remd_coef(L.selfsim.w[i], x.count), L.selfsim.W[i], L.selfsim.U[i], dst,
                                         held ? 1 : 0, s));
+        held = true;
+    }
+    if (L.xcorr.carries(m)) {
+        // (the fp32 product over all shifts, N x 2 C |D| x C: timed as "N x 1, cin 2 C |D|, cout C", layer tag 260 + map)
+        const XcorrGrad x = xcorr_grad_of(L, i, dst, held);
+        Timer tm(ctx, s, K_OTHER, 0, x.h * x.w, 1, 2 * x.C * x.nd, x.C, 1, 260 + i);
+        HIPCHK(ctx, launch_xcorr_grad(x, s));
         held = true;
     }
     return NST_OK;
@@ -1365,6 +1455,7 @@ int closure_record(nst_ctx* ctx, const float* x, float cw, float sw, float tvw, 
                                             gi[i - 1], 1, main));
     }
     if (half != BACKWARD) HIPCHK(ctx, launch_loss_assemble(fill_loss_assembly(ctx, level_mask, cw, sw, tvw, losses), main));
+    if (half != BACKWARD) NSTCHK(xcorr_loss_rows(ctx, level_mask, losses, main));
     return NST_OK;
 }
 
@@ -1471,6 +1562,8 @@ int window_check(nst_ctx* ctx, const float* xs, int row0, int rows, int H0) {
         return fail(ctx, NST_E_STATE, "the stripe closure implements no relaxed EMD term (nst_level_set_remd(ctx, 0, NULL, ...) clears it)");
     if (L.selfsim.on())
         return fail(ctx, NST_E_STATE, "the stripe closure implements no self-similarity term (nst_level_set_selfsim(ctx, 0, NULL, ...) clears it)");
+    if (L.xcorr.on())
+        return fail(ctx, NST_E_STATE, "the stripe closure implements no xcorr term (nst_level_set_xcorr(ctx, 0, NULL, ...) clears it)");
     if (L.guide.R > 0)
         return fail(ctx, NST_E_STATE, "the stripe closure implements no spatial control (nst_level_set_guidance(ctx, 0, 0, ...) clears it)");
     if (!L.targets) return fail(ctx, NST_E_STATE, "targets of the stripe not set");
@@ -1621,6 +1714,7 @@ int nst_level_set_guidance(nst_ctx* ctx, int level, int R, const float* planes, 
     if (L.hist.on()) return fail(ctx, NST_E_STATE, "a level with the histogram loss takes no guidance (nst_level_set_histograms(ctx, level, NULL, ...) clears the term)");
     if (L.remd.on()) return fail(ctx, NST_E_STATE, "a level with the relaxed EMD term takes no guidance (nst_level_set_remd(ctx, level, NULL, ...) clears the term)");
     if (L.selfsim.on()) return fail(ctx, NST_E_STATE, "a level with the self-similarity term takes no guidance (nst_level_set_selfsim(ctx, level, NULL, ...) clears the term)");
+    if (L.xcorr.on()) return fail(ctx, NST_E_STATE, "a level with the xcorr term takes no guidance (nst_level_set_xcorr(ctx, level, NULL, ...) clears the term)");
     if (!planes) return fail(ctx, NST_E_ARG, "null argument");
     float lam[NST_MAX_REGIONS] = {1.f, 1.f, 1.f, 1.f};
     bool positive = lambda == nullptr;

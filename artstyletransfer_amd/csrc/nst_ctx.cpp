@@ -424,7 +424,7 @@ int replace_term(nst_ctx* ctx, Block LevelWs::*member, Fill fill) {
     return replace_blocks(ctx->lv, ctx->levels, member, fill, [&] { quiesce(ctx); drop_closure_state(ctx, true); });
 }
 
-// ---- what the per-map terms (MapTerm: MRF, histogram loss, relaxed EMD, self-similarity) share outside a closure -----------------------------
+// ---- what the per-map terms (MapTerm: MRF, histogram loss, relaxed EMD, self-similarity, xcorr) share outside a closure -----------------------------
 // how the refusals of a term's setter name it ("the <adj> weights", "no <name>"), and what the term asks of the job besides
 // (any_used_map: a weight may sit on the job's content map as well as on a style map, and the image the setter is given is
 // the level's content image, not a style image)
@@ -433,6 +433,7 @@ const MapTermWords kMrfWords{"MRF", "MRF term", true, true, false};
 const MapTermWords kHistWords{"histogram", "histogram loss", false, false, false};
 const MapTermWords kRemdWords{"relaxed EMD", "relaxed EMD term", true, false, false};
 const MapTermWords kSelfSimWords{"self-similarity", "self-similarity term", true, false, true};
+const MapTermWords kXcorrWords{"xcorr", "xcorr term", true, false, false};
 
 // every level's per-map terms go (they hold maps of the style image as the job's network saw it: the setters again)
 void drop_map_terms(nst_ctx* ctx) {
@@ -441,6 +442,7 @@ void drop_map_terms(nst_ctx* ctx) {
         ctx->lv[i].hist = HistLevel();
         ctx->lv[i].remd = RemdLevel();
         ctx->lv[i].selfsim = SelfSimLevel();
+        ctx->lv[i].xcorr = XcorrLevel();
     }
 }
 // weight i of a setter's six into the new block
@@ -566,6 +568,7 @@ int nst_ctx_create_ex(int device, const float* const* weights, const float* cons
     if (e == hipSuccess) e = hist_init_device();
     if (e == hipSuccess) e = remd_init_device();
     if (e == hipSuccess) e = selfsim_init_device();
+    if (e == hipSuccess) e = xcorr_init_device();
     // options: an explicit argument wins; -1 falls back to the environment (read here, once), then to the default
     if (opts.conv_mode >= 0) {
         if (opts.conv_mode > NST_CONV_F16X2) { ctx->err = "nst_options.conv_mode must be NST_CONV_F32, NST_CONV_BF16X3 or NST_CONV_F16X2"; return bail(NST_E_ARG); }
@@ -1512,6 +1515,112 @@ int nst_level_selfsim_decisions(nst_ctx* ctx, int level, int map, float* D_out, 
     if (D_out) HIPCHK(ctx, hipMemcpyAsync(D_out, g.D[map], n * n * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (s_out) HIPCHK(ctx, hipMemcpyAsync(s_out, g.s[map], n * sizeof(double), hipMemcpyDeviceToDevice, s));
     if (sg_out) HIPCHK(ctx, hipMemcpyAsync(sg_out, g.sg[map], n * n, hipMemcpyDeviceToDevice, s));
+    mark(ctx, s);
+    return NST_OK;
+}
+
+// The long-range style term of one level (Berger & Memisevic 2017; include/nst_hip.h has the definition): the style image goes
+// through the network on scratch, and per weighted map the style's G_d stack is made by the launches a closure uses on the
+// image's map, beside every buffer a closure needs.  Life cycle of nst_level_set_remd.
+int nst_level_set_xcorr(nst_ctx* ctx, int level, const float* style, int hs, int ws, const float* weights, const int* shifts, int n,
+                        void* stream) {
+    if (ctx) { ++ctx->closure_epoch; ++ctx->ws_seq; }
+    NSTCHK(bind(ctx));
+    if (ctx->levels < 1) return fail(ctx, NST_E_STATE, "nst_job_configure has not been called");
+    if (level < 0 || level >= ctx->levels) return fail(ctx, NST_E_ARG, "level out of range");
+    LevelWs& L = ctx->lv[level];
+    XcorrLevel g;
+    if (style) {
+        if (!weights || !shifts) return fail(ctx, NST_E_ARG, "null argument");
+        for (int i = 0; i < 6; ++i) NSTCHK(take_weight(ctx, kXcorrWords, weights, i, g));
+        if (n < 1 || n > XCORR_MAX_SHIFTS) return fail(ctx, NST_E_ARG, "the xcorr term takes 1..16 shifts");
+        for (int d = 0; d < n; ++d) {
+            const int dx = shifts[2 * d], dy = shifts[2 * d + 1];
+            if (dx < 0 || dy < 0 || dx > 64 || dy > 64 || (dx == 0 && dy == 0))
+                return fail(ctx, NST_E_ARG, "a shift (dx, dy) has 0 <= dx, dy <= 64, not both 0");
+            for (int e = 0; e < d; ++e)
+                if (g.dx[e] == dx && g.dy[e] == dy) return fail(ctx, NST_E_ARG, "the shifts must be distinct");
+            g.dx[d] = dx; g.dy[d] = dy;
+        }
+        g.nd = n;
+        // a shift must leave a pair on every weighted map, of the level's image and of the style image
+        for (int i = 0; i < 6; ++i) {
+            if (!(g.w[i] > 0.f)) continue;
+            const int l = kTapLayer[i];
+            for (int d = 0; d < n; ++d)
+                if (g.dx[d] >= L.acts.w[l] || g.dy[d] >= L.acts.h[l] || g.dx[d] >= (ws >> kScale[l]) || g.dy[d] >= (hs >> kScale[l]))
+                    return fail(ctx, NST_E_ARG, "a shift is not smaller than a weighted map or its style map");
+        }
+    }
+    std::optional<Scratch> sc;
+    NSTCHK(begin_map_term(ctx, kXcorrWords, L, g, style, hs, ws, stream, sc));
+    if (sc) {
+        hipStream_t s = sc->s;
+        g.hs = hs; g.ws = ws;
+        XcorrBatch b{};
+        auto flush = [&]() -> int {
+            if (b.n > 0) HIPCHK(ctx, launch_xcorr_batch(b, s));
+            b.n = 0;
+            return NST_OK;
+        };
+        for (int i = 0; i < 6; ++i) {
+            if (!(g.w[i] > 0.f)) continue;
+            const int l = kTapLayer[i], C = kCout[l], mh = sc->acts.h[l], mw = sc->acts.w[l];
+            const size_t CC = (size_t)C * C, stack = (size_t)g.nd * CC;
+            NSTCHK(g.mem.alloc(ctx, &g.Gt[i], stack));
+            NSTCHK(g.mem.alloc(ctx, &g.G[i], stack));
+            NSTCHK(g.mem.alloc(ctx, &g.S[i], stack));
+            NSTCHK(g.mem.alloc(ctx, &g.St[i], stack));
+            NSTCHK(g.mem.alloc(ctx, &g.sq[i], (size_t)g.nd * xcorr_finish_blocks(C)));
+            // what nst_level_xcorr_matrices reads before any closure
+            HIPCHK(ctx, hipMemsetAsync(g.G[i], 0, stack * sizeof(float), s));
+            for (int d = 0; d < g.nd; ++d) {
+                XcorrGeometry own, sty;
+                if (!xcorr_geometry(C, L.acts.h[l], L.acts.w[l], g.dx[d], g.dy[d], &own) || !xcorr_geometry(C, mh, mw, g.dx[d], g.dy[d], &sty))
+                    return fail(ctx, NST_E_ARG, "a weighted map or its style map is too large, or a shift is not smaller than it");
+                NSTCHK(g.mem.alloc(ctx, &g.part[i][d], (size_t)own.nsplit * CC));
+                // the style's G_d by the closure's launches, its slabs on scratch
+                float* part = nullptr;
+                NSTCHK(sc->alloc(&part, (size_t)sty.nsplit * CC));
+                if (b.n == XCORR_BATCH_MAX) NSTCHK(flush());
+                XcorrItem& it = b.it[b.n++];
+                it = XcorrItem{};
+                it.f = sc->acts.act[l]; it.amax = amax_act(sc->acts, l); it.part = part;
+                it.C = C; it.h = mh; it.w = mw; it.dx = g.dx[d]; it.dy = g.dy[d];
+                it.divisor = (float)((double)C * (double)(mh - g.dy[d]) * (double)(mw - g.dx[d]));
+                it.G = g.Gt[i] + d * CC;
+            }
+        }
+        NSTCHK(flush());
+    }
+    return commit_map_term(ctx, sc, L.xcorr, g);
+}
+
+int nst_level_xcorr(const nst_ctx* ctx, int level, float* weights, int* shifts, int* n, int* hs, int* ws) {
+    if (!ctx) return fail(nullptr, NST_E_ARG, "null context");
+    if (level < 0 || level >= ctx->levels) return fail(nullptr, NST_E_ARG, "level out of range");
+    const XcorrLevel& g = ctx->lv[level].xcorr;
+    for (int i = 0; i < 6 && weights; ++i) weights[i] = g.w[i];
+    for (int d = 0; d < XCORR_MAX_SHIFTS && shifts; ++d) { shifts[2 * d] = d < g.nd ? g.dx[d] : 0; shifts[2 * d + 1] = d < g.nd ? g.dy[d] : 0; }
+    if (n) *n = g.nd;
+    if (hs) *hs = g.hs;
+    if (ws) *ws = g.ws;
+    return NST_OK;
+}
+
+// the unweighted xcorr_i of the last closure (map_term_losses)
+int nst_job_xcorr_losses(nst_ctx* ctx, float* out, void* stream) { return map_term_losses(ctx, T_XCORR, out, stream); }
+
+// the G_d stack (|D| x C x C floats) of the last closure of one weighted map of a level (zeros before any closure)
+int nst_level_xcorr_matrices(nst_ctx* ctx, int level, int map, float* G_out, void* stream) {
+    NSTCHK(bind(ctx));
+    if (level < 0 || level >= ctx->levels) return fail(ctx, NST_E_ARG, "level out of range");
+    if (map < 0 || map > 5 || !G_out) return fail(ctx, NST_E_ARG, "bad argument");
+    const XcorrLevel& g = ctx->lv[level].xcorr;
+    if (!(g.w[map] > 0.f)) return fail(ctx, NST_E_STATE, "the map carries no xcorr term on this level (nst_level_set_xcorr)");
+    const size_t C = (size_t)kCout[kTapLayer[map]];
+    hipStream_t s = enter(ctx, stream);
+    HIPCHK(ctx, hipMemcpyAsync(G_out, g.G[map], (size_t)g.nd * C * C * sizeof(float), hipMemcpyDeviceToDevice, s));
     mark(ctx, s);
     return NST_OK;
 }

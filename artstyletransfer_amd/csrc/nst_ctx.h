@@ -200,8 +200,8 @@ struct AnchorLevel {
     DevMem mem;
 };
 
-// What the per-map terms of one level share (PatchLevel, HistLevel, RemdLevel, SelfSimLevel below; always in that order, NST_MAP_TERMS of
-// them): the weights by map index (0: the map has no term), the six unweighted values of the last closure (which the forward
+// What the per-map terms of one level share (PatchLevel, HistLevel, RemdLevel, SelfSimLevel, XcorrLevel below; always in that order; the
+// loss assembly adds the rows of the first NST_MAP_TERMS of them, xcorr_loss_rows those of the last): the weights by map index (0: the map has no term), the six unweighted values of the last closure (which the forward
 // half writes and the loss rows read), and the block's memory.
 struct MapTerm {
     float w[6] = {};
@@ -217,7 +217,7 @@ struct MapTerm {
         return i >= 0 && w[i] > 0.f;
     }
 };
-enum MapTermId { T_MRF = 0, T_HIST = 1, T_REMD = 2, T_SELFSIM = 3 };
+enum MapTermId { T_MRF = 0, T_HIST = 1, T_REMD = 2, T_SELFSIM = 3, T_XCORR = 4 };
 
 // The MRF term of one level (nst_level_set_patches; include/nst_hip.h has the definition), by map index: the weight (0: the
 // map has no term), the style's map with its dictionary (d[i]: fs, the absmax record, rq and the packed operand), the search
@@ -314,6 +314,25 @@ struct SelfSimLevel : MapTerm {
     float* U[6] = {};
 };
 
+// The long-range style term of one level (nst_level_set_xcorr; include/nst_hip.h has the definition): the shifts (nd of them, at
+// most XCORR_MAX_SHIFTS, the same for every map of the level) and the style image's size; by map index the weight (0: the map
+// has no term), the style's G_d stack (Gt: nd x C x C, made once by the setter), the image side's stacks, which the forward half
+// fills every closure (G, S = coef (G - Gt) and its transpose St), per shift the slabs of the value pass, the finish pass's
+// partial sums of squares (sq: nd x xcorr_finish_blocks(C)), and the unweighted xcorr_i (six floats, which the forward half
+// writes and the loss rows read).  Data of one job with PatchLevel's life cycle: everything is made by the setter, a closure
+// allocates nothing.
+struct XcorrLevel : MapTerm {
+    int nd = 0;
+    int dx[XCORR_MAX_SHIFTS] = {}, dy[XCORR_MAX_SHIFTS] = {};
+    int hs = 0, ws = 0;         // the style image of nst_level_set_xcorr
+    float* Gt[6] = {};
+    float* G[6] = {};
+    float* S[6] = {};
+    float* St[6] = {};
+    float* part[6][XCORR_MAX_SHIFTS] = {};
+    double* sq[6] = {};
+};
+
 // the level image and its gradient (levels >= 1), planar: channels (nst_job_set_color) x h x w floats each
 struct LevelImage {
     float* xl = nullptr;
@@ -333,8 +352,10 @@ struct LevelWs {
     HistLevel hist;
     RemdLevel remd;
     SelfSimLevel selfsim;
+    XcorrLevel xcorr;
     const MapTerm& map_term(int t) const {
-        return t == T_MRF ? (const MapTerm&)pm : t == T_HIST ? (const MapTerm&)hist : t == T_REMD ? (const MapTerm&)remd : selfsim;
+        return t == T_MRF ? (const MapTerm&)pm : t == T_HIST ? (const MapTerm&)hist : t == T_REMD ? (const MapTerm&)remd
+             : t == T_SELFSIM ? (const MapTerm&)selfsim : xcorr;
     }
     ActSet acts;
     float* gbuf[2] = {};

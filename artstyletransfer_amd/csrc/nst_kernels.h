@@ -630,6 +630,50 @@ hipError_t launch_selfsim_value(const SelfSimTerm& t, hipStream_t stream);
 hipError_t launch_selfsim_grad(const RemdSide& x, const SelfSimTerm& t, float coef, float* W, float* U, float* out, int accumulate,
                                hipStream_t stream);
 
+// xcorr.hip: the long-range style term, Gram matrices of spatially shifted maps (include/nst_hip.h has the definition) ---------
+constexpr int XCORR_MAX_SHIFTS = 16;     // (include/nst_hip.h states the same number for nst_level_set_xcorr)
+constexpr int XCORR_BATCH_MAX = 32;      // (level, map, shift) items of one launch
+constexpr int XCORR_VALUE_MAX = 48;      // (level, map) items of one value launch: NST_MAX_LEVELS x 6
+constexpr int XCORR_KP = 32;             // pairs per staged chunk
+constexpr int XCORR_FINISH_EPB = 1024;   // elements of G_d per block of the finish pass
+hipError_t xcorr_init_device();   // raises the dynamic-LDS limit of the value kernel: once per device, before the first launch there
+// How the pairs of one shift are dealt to workgroups: nsplit slabs of pix_per_split consecutive pixels p (whole chunks), a
+// function of the shape alone.  false: C other than 64 / 128 / 256 / 512, a shift outside 0 <= dx < w, 0 <= dy < h or (0,0),
+// h w C >= 2^31.
+struct XcorrGeometry { int nsplit; int pix_per_split; };
+bool xcorr_geometry(int C, int h, int w, int dx, int dy, XcorrGeometry* g);
+inline int xcorr_finish_blocks(int C) { return C * C / XCORR_FINISH_EPB; }
+// One (map, shift): f NHWC with its absmax record; part: nsplit x C x C floats (the slabs); divisor Z_d; G (nullable) gets G_d;
+// with a target also S = coef (G_d - target), St its transpose and sq (xcorr_finish_blocks(C) doubles) the partial sums of
+// (G_d - target)^2.  launch_xcorr_batch fills the geometry and the block prefixes: one value launch and one finish launch.
+struct XcorrItem {
+    const float* f; const unsigned* amax; float* part;
+    int C, h, w, dx, dy;
+    int nsplit, pix_per_split, part_end;
+    float divisor;
+    const float* target; float coef; float* G; float* S; float* St; double* sq;
+    int finish_end;
+};
+struct XcorrBatch { XcorrItem it[XCORR_BATCH_MAX]; int n; };
+hipError_t launch_xcorr_batch(const XcorrBatch& b, hipStream_t stream);
+// xcorr_i of a map from its shifts' partials (sq: nd x nblk doubles, cc = C^2): out = (float)((1/nd) sum_d (sum sq_d) / cc)
+struct XcorrValueItem { const double* sq; int nd; int nblk; double cc; float* out; };
+struct XcorrValueBatch { XcorrValueItem it[XCORR_VALUE_MAX]; int n; };
+hipError_t launch_xcorr_values(const XcorrValueBatch& b, hipStream_t stream);
+// the term's share of the loss rows, after launch_loss_assemble (NST_MAP_TERMS counts the four terms whose rows that launch adds):
+// per level with the term out[4 l] = (out[4 l] + w_1 xcorr_1) + ... in ascending map order, every product and sum rounded, and
+// the grand total out[4 levels] formed again from the owned levels' totals in level order, as launch_loss_assemble forms it
+// (owned: the level is in the closure's mask; the six values of a level with the term outside it are zeroed)
+struct XcorrRows { struct Level { float* vals; float w[6]; int owned; } lv[8]; int levels; float* out; };
+hipError_t launch_xcorr_rows(const XcorrRows& r, hipStream_t stream);
+// The gradient of one map over all its shifts: S and St are the nd x C x C stacks the finish pass left; out (the map's shape) is
+// written, or (accumulate) added to.
+struct XcorrGrad {
+    const float* f; int h, w, C; int nd; int dx[XCORR_MAX_SHIFTS], dy[XCORR_MAX_SHIFTS];
+    const float* S; const float* St; float* out; int accumulate;
+};
+hipError_t launch_xcorr_grad(const XcorrGrad& g, hipStream_t stream);
+
 // gram_guided.hip: spatial control (guided Gram matrices; include/nst_hip.h has the definitions) ---------------------
 constexpr int NST_MAX_REGIONS_K = 4;
 constexpr int GUIDE_MASS_BLOCKS = 64;

@@ -22,6 +22,7 @@ from . import mrf_modes as _mrf
 from . import hist_modes as _hist
 from . import remd_modes as _remd
 from . import selfsim_modes as _selfsim
+from . import xcorr_modes as _xcorr
 from ._lib import NST_LOSS_ROW, NstError, StepInfo
 
 TAP_CHANNELS = (64, 128, 256, 512, 512, 512)
@@ -1071,6 +1072,99 @@ class StyleEngine:
                    "nst_selfsim_term")
         return (val, sg, grad) if want_grad else (val, sg)
 
+    # ---- the long-range style term, xcorr (nst_level_set_xcorr; xcorr_loss.py is the driver) -------------------
+    def set_xcorr(self, level: int, style: Optional[torch.Tensor], weights=None, shifts=_xcorr.DEFAULT_SHIFTS) -> None:
+        """The long-range style term of one level (nst_level_set_xcorr; Berger & Memisevic 2017): the level total gains
+        sum_i w_i xcorr_i, xcorr_i the mean over the shifts d of the mean squared difference between G_d = (1/Z_d) sum_p
+        F(p + d) F(p)^T of map i and the same statistic of the style's map.  style: the level's style image, a device float32
+        (C,hs,ws) tensor (any leading ones; C = 3, or 1 in luminance mode), which is run through the network; weights: as
+        xcorr_modes.normalize_weights takes them; shifts: as xcorr_modes.normalize_shifts takes them (an int k: (k, 0) and
+        (0, k); a pair (dx, dy) passes through; at most 16 after expansion), each smaller than every weighted map of the level
+        and of the style image.  Data of the job, not a setting: configure(), set_taps, set_pooling and set_color drop it.
+        style None or zero weights clear the level's term."""
+        setting = None if style is None else _xcorr.normalize_xcorr(weights, shifts, None, self.taps[1])
+        if setting is None:
+            _lib.check(self.ctx, self.lib.nst_level_set_xcorr(self.ctx, int(level), None, 0, 0, None, None, 0, _stream(self.device)),
+                       "nst_level_set_xcorr")
+            return
+        w, sh, _ = setting
+        style = self._level_style(level, style)
+        _xcorr.level_carries(setting, [self.level_shape(level)], [(int(style.shape[-2]), int(style.shape[-1]))])
+        flat = [v for d in sh for v in d]
+        _lib.check(self.ctx, self.lib.nst_level_set_xcorr(self.ctx, int(level), _ptr(style), int(style.shape[-2]), int(style.shape[-1]),
+                                                          (C.c_float * 6)(*w), (C.c_int * len(flat))(*flat), len(sh),
+                                                          _stream(self.device)), "nst_level_set_xcorr")
+
+    def clear_xcorr(self, level: Optional[int] = None) -> None:
+        """No xcorr term on one level, or (None) on any configured level."""
+        self._clear_levels(self.set_xcorr, level)
+
+    def xcorr_setting(self, level: int):
+        """(weights (6,), shifts ((dx, dy), ...), (hs, ws) of the style image) of a level (nst_level_xcorr), or None when the
+        level has no term."""
+        w, sh, n = (C.c_float * 6)(), (C.c_int * (2 * _xcorr.MAX_SHIFTS))(), C.c_int()
+        hs, wd = C.c_int(), C.c_int()
+        _lib.check(self.ctx, self.lib.nst_level_xcorr(self.ctx, int(level), w, sh, C.byref(n), C.byref(hs), C.byref(wd)), "nst_level_xcorr")
+        ws = tuple(float(v) for v in w)
+        if all(v == 0.0 for v in ws):
+            return None
+        return ws, tuple((int(sh[2 * d]), int(sh[2 * d + 1])) for d in range(n.value)), (hs.value, wd.value)
+
+    def xcorr_losses(self) -> torch.Tensor:
+        """(levels, 6) device tensor: the unweighted xcorr_i of the last closure by map index (nst_job_xcorr_losses); zeros for
+        maps without the term and levels outside the last level mask."""
+        return self._map_term_losses("nst_job_xcorr_losses")
+
+    def xcorr_matrices(self, level: int, map: int) -> torch.Tensor:
+        """(|D|, C, C) device float32: the G_d stack of map index `map` of a level as the last closure made it
+        (nst_level_xcorr_matrices); zeros before any closure."""
+        st = self.xcorr_setting(level)
+        if st is None or not st[0][map] > 0.0:
+            raise NstError(f"map {map} carries no xcorr term on level {level} (set_xcorr)")
+        ch = TAP_CHANNELS[map]
+        out = torch.empty((len(st[1]), ch, ch), dtype=torch.float32, device=self.device)
+        _lib.check(self.ctx, self.lib.nst_level_xcorr_matrices(self.ctx, int(level), int(map), _ptr(out), _stream(self.device)),
+                   "nst_level_xcorr_matrices")
+        return out
+
+    def _xcorr_map(self, f: torch.Tensor, shifts):
+        _chk_dev(f, self.device)
+        if f.dim() != 3:
+            raise NstError("f must be (h,w,C)")
+        sh = _xcorr.normalize_shifts(shifts)
+        _xcorr.check_map(f.shape[0], f.shape[1], sh)
+        flat = [v for d in sh for v in d]
+        return sh, (C.c_int * len(flat))(*flat)
+
+    def xcorr(self, f: torch.Tensor, shifts=_xcorr.DEFAULT_SHIFTS, want_geometry: bool = False):
+        """The statistic alone (nst_xcorr): f (h,w,C) device float32 map in NHWC, C = 64, 128, 256 or 512 -> the (|D|, C, C)
+        stack of G_d, d in the order of xcorr_modes.normalize_shifts(shifts); with want_geometry also ((nsplit, pix_per_split),
+        ...) per shift: how the device dealt the pairs to its partial sums."""
+        sh, arr = self._xcorr_map(f, shifts)
+        f = f.contiguous()
+        out = torch.empty((len(sh), f.shape[2], f.shape[2]), dtype=torch.float32, device=self.device)
+        geo = (C.c_int * (2 * len(sh)))()
+        _lib.check(self.ctx, self.lib.nst_xcorr(self.ctx, _ptr(f), f.shape[0], f.shape[1], f.shape[2], arr, len(sh), _ptr(out), geo,
+                                                _stream(self.device)), "nst_xcorr")
+        if want_geometry:
+            return out, tuple((int(geo[2 * d]), int(geo[2 * d + 1])) for d in range(len(sh)))
+        return out
+
+    def xcorr_term(self, f: torch.Tensor, gt: torch.Tensor, shifts=_xcorr.DEFAULT_SHIFTS, coef: float = 1.0, want_grad: bool = True):
+        """Value and gradient alone (nst_xcorr_term): f (h,w,C) against the targets gt (|D|, C, C) -> the unweighted xcorr as a
+        device scalar and, with want_grad, the (h,w,C) gradient of coef xcorr."""
+        sh, arr = self._xcorr_map(f, shifts)
+        f = f.contiguous()
+        _chk_dev(gt, self.device)
+        if tuple(gt.shape) != (len(sh), f.shape[2], f.shape[2]):
+            raise NstError(f"gt must be ({len(sh)},{f.shape[2]},{f.shape[2]}), got {tuple(gt.shape)}")
+        gt = gt.contiguous()
+        val = torch.empty(1, dtype=torch.float32, device=self.device)
+        grad = torch.empty_like(f) if want_grad else None
+        _lib.check(self.ctx, self.lib.nst_xcorr_term(self.ctx, _ptr(f), f.shape[0], f.shape[1], f.shape[2], _ptr(gt), arr, len(sh),
+                                                     float(coef), _ptr(val), _ptr(grad), _stream(self.device)), "nst_xcorr_term")
+        return (val, grad) if want_grad else val
+
     def closure(self, x: torch.Tensor, cw: float, sw: float, tvw: float,
                 grad: Optional[torch.Tensor] = None, losses: Optional[torch.Tensor] = None):
         """Asynchronous on the current stream. Returns (grad (C,H,W), losses (4*levels+1,)) device tensors (C = 3, or 1
@@ -1854,6 +1948,7 @@ class PixelOptimizer:
         _hist.check_exclusive(next((st for st in (e.histograms_setting(l) for l in range(e.levels)) if st is not None), None), stripes=True)
         _remd.check_exclusive(next((st for st in (e.remd_setting(l) for l in range(e.levels)) if st is not None), None), stripes=True)
         _selfsim.check_exclusive(next((st for st in (e.selfsim_setting(l) for l in range(e.levels)) if st is not None), None), stripes=True)
+        _xcorr.check_exclusive(next((st for st in (e.xcorr_setting(l) for l in range(e.levels)) if st is not None), None), stripes=True)
         contents = list(content_t) if isinstance(content_t, (list, tuple)) else [content_t]
         styles = list(style_t) if isinstance(style_t, (list, tuple)) else [style_t]
         if blend is not None and styles and isinstance(styles[0], torch.Tensor):

@@ -30,6 +30,7 @@ from . import mrf_modes as _mrf
 from . import hist_modes as _hist
 from . import remd_modes as _remd
 from . import selfsim_modes as _selfsim
+from . import xcorr_modes as _xcorr
 
 # ImageNet statistics (reference :22-23)
 IMAGENET_MEAN_255 = [123.675, 116.28, 103.53]
@@ -295,6 +296,14 @@ class _DeviceJob:
                 if strides[lvl] is not None:
                     self.engine.set_selfsim(lvl, content_of(), weights, strides[lvl], epsilon)
 
+    def set_shifted_gram(self, weights, shifts, carries):
+        """The xcorr term of the levels (StyleEngine.set_xcorr; `carries` per level: whether it carries the term, as
+        xcorr_modes.level_carries makes it): each level gets the style level image its targets were made from."""
+        with torch.cuda.device(self.dev), torch.cuda.stream(self.job_stream):
+            for lvl, style_of in enumerate(self.style_levels):
+                if carries[lvl]:
+                    self.engine.set_xcorr(lvl, style_of(), weights, shifts)
+
     def step(self, cw, sw, tvw):
         """One optimizer.step(closure) (nst_opt_step).  Runs on a pool thread, whose current stream is its own."""
         with torch.cuda.stream(self.job_stream):
@@ -375,6 +384,7 @@ class NeuralStyleTransfer:
         self.__histograms = None                 # set_histogram_loss: likewise
         self.__remd = None                       # set_relaxed_emd: likewise
         self.__selfsim = None                    # set_self_similarity: likewise
+        self.__xcorr = None                      # set_shifted_gram: likewise
 
     def set_feature_maps(self, content_layer=None, style_layers=None, use_relu=True):
         """Extension: the feature maps the losses of the next `process` read - a content map and a set of style maps of
@@ -557,6 +567,22 @@ class NeuralStyleTransfer:
         off = _selfsim.normalize_selfsim(weights, samples, epsilon, levels) is None       # (malformed: here and now)
         self.__selfsim = None if off else (weights, samples, epsilon, levels)
 
+    def set_shifted_gram(self, weights=None, shifts=_xcorr.DEFAULT_SHIFTS, levels=None):
+        """Extension: the long-range style term of Berger & Memisevic 2017 ("xcorr") in the next `process`: per pyramid level
+        sum_i w_i xcorr_i, xcorr_i the mean over the shifts d of the mean squared difference between the cross-correlation of
+        map i with its copy shifted by d, G_d = (1/Z_d) sum_p F(p + d) F(p)^T, and the same statistic of the level's style
+        image (nst_level_set_xcorr in include/nst_hip.h has the definition).  It carries a texture's regular structure - a
+        lattice, hatching at a fixed pitch - which every summed statistic is blind to.  `weights`: None or 0 (off), a number
+        (that weight on those of relu2_1, relu3_1, relu4_1 that are style maps of the job), six numbers by map index of
+        Vgg19.layer_names, or a dict {map index or name: number}; `shifts`: integers k (the axis shifts (k, 0) and (0, k)) or
+        pairs (dx, dy), 0..64, at most 16 after expansion, in map pixels; `levels`: None for every level, or the level indices
+        that carry the term (0 = the full resolution).  Data of one job, like set_relaxed_emd - not one of `settings`.
+        ValueError for a malformed setting and - in `process`, where the taps and the sizes are known - for a positive weight on
+        a map that is not a style map, a shift that is not smaller than a weighted map of a carrying level, of either image, or
+        the term together with regions or several style images."""
+        off = _xcorr.normalize_xcorr(weights, shifts, levels) is None       # (malformed: here and now)
+        self.__xcorr = None if off else (weights, shifts, levels)
+
     async def process(self, content_imgs, init_img, lr_start, iters_num, content_weight, style_weight, tv_weight,
                       init_img_name):
         # validates the model name exactly as the reference does (ValueError for anything but vgg19)
@@ -612,6 +638,12 @@ class NeuralStyleTransfer:
                                                  levels_num=len(content_imgs))
             _selfsim.check_exclusive(selfsim, regions=resolved.get("regions"), extra_styles=resolved.get("blend"))
             selfsim_strides = _selfsim.level_strides(selfsim, [tuple(c.shape[:2]) for c in content_imgs])
+        xcorr = None
+        if self.__xcorr is not None:
+            _, style_set, use_relu = resolved.get("taps", (_taps.DEFAULT_CONTENT_INDEX, _taps.DEFAULT_STYLE_INDICES, True))
+            xcorr = _xcorr.normalize_xcorr(*self.__xcorr, style_indices=style_set, use_relu=use_relu, levels_num=len(content_imgs))
+            _xcorr.check_exclusive(xcorr, regions=resolved.get("regions"), extra_styles=resolved.get("blend"))
+            xcorr_carries = _xcorr.level_carries(xcorr, [tuple(c.shape[:2]) for c in content_imgs], [tuple(s.shape[:2]) for s in style_imgs])
         if self.__anchor is not None and len(self.__anchor[0]) != len(content_imgs):
             raise ValueError(f"{len(self.__anchor[0])} anchor levels for a job of {len(content_imgs)} levels")
         job = _make_job(self.__device, self.__optimizer_name, style_imgs, content_imgs, init_img, lr_start, **resolved)
@@ -644,6 +676,12 @@ class NeuralStyleTransfer:
         if selfsim is not None:              # (likewise, after the relaxed EMD term)
             try:
                 job.set_self_similarity(selfsim[0], selfsim_strides, selfsim[2])
+            except BaseException:
+                job.close()
+                raise
+        if xcorr is not None:                # (likewise, after the self-similarity term)
+            try:
+                job.set_shifted_gram(xcorr[0], xcorr[1], xcorr_carries)
             except BaseException:
                 job.close()
                 raise
@@ -748,14 +786,15 @@ async def neural_style_transfer(content_n_style: ContentStylePair,
 def _transfer_from(content_n_style, content_weight, style_weight, tv_weight, optimizer, model, init_method, iters_num, levels_num,
                    noise_factor, noise_levels, noise_levels_central_amplitude, noise_levels_peripheral_amplitude,
                    noise_levels_dispersion, *, device=None, start=None, patches=None, semantics=None, histograms=None, remd=None, selfsim=None,
-                   **keywords):
+                   xcorr=None, **keywords):
     """The settings validation of neural_style_transfer() (`keywords`: its keyword-only parameters), here and now - before any
     GPU work, ValueError - and then the job as an async generator, from the `init_method` image or from `start` (_transfer).
     `patches` (patch_match.py): None, or the arguments of NeuralStyleTransfer.set_patch_match, validated here too;
     `semantics`: None, or the arguments of NeuralStyleTransfer.set_patch_semantics, likewise (they need `patches`);
     `histograms` (histogram_loss.py): None, or the arguments of NeuralStyleTransfer.set_histogram_loss, likewise; `remd`
     (remd_loss.py): None, or the arguments of NeuralStyleTransfer.set_relaxed_emd, likewise; `selfsim` (selfsim_loss.py): None, or
-    the arguments of NeuralStyleTransfer.set_self_similarity, likewise."""
+    the arguments of NeuralStyleTransfer.set_self_similarity, likewise; `xcorr` (xcorr_loss.py): None, or the arguments of
+    NeuralStyleTransfer.set_shifted_gram, likewise."""
     settings = _job.JobSettings(for_job=True, **keywords)
 
     def level_shapes(img):      # (the level sizes follow from the image size: top level first)
@@ -792,6 +831,12 @@ def _transfer_from(content_n_style, content_weight, style_weight, tv_weight, opt
         _selfsim.check_exclusive(checked, regions=resolved.get("regions"), extra_styles=keywords.get("extra_styles"))
         _selfsim.level_strides(checked, level_shapes(content_n_style.content[1]))
         selfsim = selfsim if checked is not None else None
+    if xcorr is not None:
+        _, style_set, use_relu = resolved.get("taps", (_taps.DEFAULT_CONTENT_INDEX, _taps.DEFAULT_STYLE_INDICES, True))
+        checked = _xcorr.normalize_xcorr(*xcorr, style_indices=style_set, use_relu=use_relu, levels_num=max(levels_num, 1))
+        _xcorr.check_exclusive(checked, regions=resolved.get("regions"), extra_styles=keywords.get("extra_styles"))
+        _xcorr.level_carries(checked, level_shapes(content_n_style.content[1]), level_shapes(content_n_style.style[1]))
+        xcorr = xcorr if checked is not None else None
     extra_styles = keywords.get("extra_styles")
     extra_styles = list(extra_styles) if extra_styles is not None else []
     for img in extra_styles:
@@ -800,13 +845,14 @@ def _transfer_from(content_n_style, content_weight, style_weight, tv_weight, opt
     return _transfer(content_n_style, content_weight, style_weight, tv_weight, optimizer, model, init_method, iters_num, levels_num,
                      noise_factor, noise_levels, noise_levels_central_amplitude, noise_levels_peripheral_amplitude,
                      noise_levels_dispersion, device, settings, keywords.get("preserve_color"), extra_styles,
-                     keywords.get("style_blend"), start, patches, semantics, histograms, remd, selfsim)
+                     keywords.get("style_blend"), start, patches, semantics, histograms, remd, selfsim,
+                     **({} if xcorr is None else {"xcorr": xcorr}))        # (by name, and only when set: `selfsim` stays the last positional)
 
 
 async def _transfer(content_n_style, content_weight, style_weight, tv_weight, optimizer, model, init_method, iters_num, levels_num,
                     noise_factor, noise_levels, noise_levels_central_amplitude, noise_levels_peripheral_amplitude,
                     noise_levels_dispersion, device, settings, preserve_color, extra_styles, style_blend, start=None, patches=None,
-                    semantics=None, histograms=None, remd=None, selfsim=None):
+                    semantics=None, histograms=None, remd=None, selfsim=None, xcorr=None):
     """neural_style_transfer() below its settings validation: `settings` is its validated JobSettings, `extra_styles` its
     checked list.  `start` (video.py): None, or a callable (setup engine, level-0 (h, w)) -> (start image: a device HWC
     tensor the job starts from in place of the `init_method` image, anchor levels, weight levels, gamma) - the arguments of
@@ -814,7 +860,7 @@ async def _transfer(content_n_style, content_weight, style_weight, tv_weight, op
     arguments of NeuralStyleTransfer.set_patch_match; `semantics`: None, or those of NeuralStyleTransfer.set_patch_semantics;
     `histograms` (histogram_loss.py): None, or those of NeuralStyleTransfer.set_histogram_loss; `remd` (remd_loss.py): None,
     or those of NeuralStyleTransfer.set_relaxed_emd; `selfsim` (selfsim_loss.py): None, or those of
-    NeuralStyleTransfer.set_self_similarity."""
+    NeuralStyleTransfer.set_self_similarity; `xcorr` (xcorr_loss.py): None, or those of NeuralStyleTransfer.set_shifted_gram."""
     if device is None:
         if not torch.cuda.is_available():
             raise RuntimeError("no GPU visible: the HIP style-transfer engine has no CPU path")
@@ -859,6 +905,8 @@ async def _transfer(content_n_style, content_weight, style_weight, tv_weight, op
         nst.set_relaxed_emd(*remd)
     if selfsim is not None:
         nst.set_self_similarity(*selfsim)
+    if xcorr is not None:
+        nst.set_shifted_gram(*xcorr)
     # (the extra styles as their pyramids; "histogram" has recoloured the style levels above)
     settings.update(extra_styles=extra_levels, style_blend=style_blend if extra_levels else None)
     if preserve_color == "histogram":

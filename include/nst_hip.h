@@ -1191,6 +1191,64 @@ int nst_selfsim_matrix(nst_ctx* ctx, const float* f, int h, int w, int C, int st
                        double* s_out /* n, nullable */, void* stream);
 int nst_selfsim_term(nst_ctx* ctx, const float* f, const float* fc, int h, int w, int C, int stride, double epsilon, float coef,
                      float* value_out /* nullable */, signed char* sg_out /* nullable */, float* grad_out /* nullable */, void* stream);
+/* ---- The long-range style term, "xcorr": Gram matrices of spatially shifted maps (Berger & Memisevic, ICLR 2017) ---------------
+ * Every summed style statistic is blind to arrangement; this one is not: the cross-correlation of a map with a shifted copy of
+ * itself carries a texture's regular structure (a lattice, hatching at a fixed pitch).  ("Gram shift" is the activation shift of
+ * nst_job_set_gram_shift; this term is called xcorr everywhere.)  For one pyramid level, one style map of index i in
+ * Vgg19.layer_names and one shift d = (dx, dy), dx, dy >= 0, not both 0, dx < w, dy < h:
+ *   F = the map of the level image, NHWC, h x w x C, the raw map whatever gram_shift is;  C = 64, 128, 256 or 512.
+ *   G_d[c][e] = (1/Z_d) sum over y < h - dy, x < w - dx of F(y + dy, x + dx)[c] F(y, x)[e];   Z_d = C (h - dy)(w - dx): the Gram
+ *     divisor with the pair count in place of the pixel count.  G_d is not symmetric.  A pixel at x >= w - dx is never paired
+ *     with the next row's.
+ *   Gt_d = the same statistic of the same map of the level's style image, which has its own size and hence its own Z_d.
+ * Per map.  xcorr_i = (1/|D|) sum_d mean_{c,e} (G_d - Gt_d)^2 over the level's shift list D (1..16 distinct shifts, each
+ *   component 0..64): the MEAN over the shifts, not the paper's sum, so that a weight means the same whatever the list is.
+ * Arithmetic.  G_d in the f16x2 arithmetic of the Gram pass: both operands are windows of the same map under its one recorded
+ *   absmax, two fp16 pieces each, per 16 pairs lo hi, hi hi, hi lo into a main and a cross accumulator (three
+ *   v_mfma_f32_32x32x16_f16 per 32x32x16 block), joined as (main + cross 2^-11) inv^2.  The pairs are dealt to nsplit slabs of
+ *   pix_per_split consecutive pixels p = y w + x < (h - dy) w - dx (whole chunks of 32; a function of the shape alone, which
+ *   nst_xcorr reports); the slabs are added in slab order, then divided by (float)Z_d.  The value: (G_d - Gt_d)^2 in double,
+ *   1024 consecutive elements a block joined by a fixed tree, the blocks of a shift likewise, the shifts in ascending order;
+ *   xcorr_i = (float) of that.
+ * Gradient.  S_d = (float)(2 w_i / (|D| C^2 Z_d)) (G_d - Gt_d), the coefficient formed in double;
+ *   dF(q) = sum_d ( [x >= dx, y >= dy] F(q - d) S_d^T + [x < w - dx, y < h - dy] F(q + d) S_d )
+ *   on v_mfma_f32_32x32x2_f32 with fp32 operands: per pixel and channel one chain over the shifts in list order, per shift the
+ *   F(q - d) part before the F(q + d) part, channels ascending.  It joins the addend of the launch below the map after the
+ *   self-similarity term's gradient: written unless an addend is held already, else added.
+ * Loss row.  A level with the term has the total (... + sum_k w_k selfsim_k) + sum_i w_i xcorr_i: added after the
+ *   self-similarity term, in ascending map order, every product and sum rounded.  NST_LOSS_ROW stays 4.  The weights are the
+ *   term's own: style_weight and style_layer_weights do not scale it.
+ * Determinism.  No float atomic takes part; every reduction has one owner and a fixed order.  A closure with the term is bitwise
+ *   reproducible.
+ *
+ * nst_level_set_xcorr: the term of one level, data of one job like the relaxed EMD term.  style = device (C,hs,ws) image in the
+ *   job's colour mode, NULL: clear the level's term.  weights[6] by map index; shifts = host, n x 2 ints (dx, dy), the same for
+ *   every map of the level.  The call runs the style image through the network up to the deepest weighted map, keeps per
+ *   weighted map the style's G_d stack, and allocates everything a closure needs.  Life cycle of nst_level_set_remd.
+ *   NST_E_ARG: level out of range; negative or non-finite weights; n outside 1..16; a shift component outside 0..64, a (0,0)
+ *   shift or a repeated one; a shift that is not smaller than a weighted map of the level or of the style image; a style image
+ *   below 16x16; a positive weight on a map that is not a style map of the job.
+ *   NST_E_STATE: no configured job; an arithmetic mode other than f16x2; a guided level (nst_level_set_guidance on a level with
+ *   the term refuses likewise); a context with use_graph.  The stripe closure returns NST_E_STATE while its level carries the
+ *   term.
+ * nst_level_xcorr: the level's setting (all-zero weights: no term); shifts takes 16 x 2 ints; every output is nullable.
+ * nst_job_xcorr_losses: out = device, levels x 6: the unweighted xcorr_i of the last closure by map index (zeros: maps without
+ *   the term and levels outside the last level mask).
+ * nst_level_xcorr_matrices: the last closure's G_d stack (|D| x C x C floats, device) of one weighted map; zeros before any
+ *   closure.  NST_E_STATE: the map carries no term on the level.
+ * nst_xcorr, nst_xcorr_term: the pieces alone, on an NHWC device map.  They read no job state.  Synchronous.
+ *   nst_xcorr: out = device, n x C x C; geometry_out = host, n x 2 ints (nsplit, pix_per_split) per shift, nullable.
+ *   nst_xcorr_term: f against the targets gt (device, n x C x C).  coef is the weight w of the definition.  value_out = device
+ *   float (the unweighted xcorr); grad_out = NHWC like f, overwritten; each nullable. */
+int nst_level_set_xcorr(nst_ctx* ctx, int level, const float* style /* device (C,hs,ws), or NULL: clear */, int hs, int ws,
+                        const float* weights /* 6, by map index */, const int* shifts /* host, n x 2 */, int n, void* stream);
+int nst_level_xcorr(const nst_ctx* ctx, int level, float* weights /* 6 */, int* shifts /* 16 x 2 */, int* n, int* hs, int* ws);
+int nst_job_xcorr_losses(nst_ctx* ctx, float* out /* device, levels x 6 */, void* stream);
+int nst_level_xcorr_matrices(nst_ctx* ctx, int level, int map, float* G_out /* device, |D| x C x C */, void* stream);
+int nst_xcorr(nst_ctx* ctx, const float* f, int h, int w, int C, const int* shifts /* host, n x 2 */, int n, float* out /* n x C x C */,
+              int* geometry_out /* host, n x 2, nullable */, void* stream);
+int nst_xcorr_term(nst_ctx* ctx, const float* f, int h, int w, int C, const float* gt /* n x C x C */, const int* shifts /* host, n x 2 */,
+                   int n, float coef, float* value_out /* nullable */, float* grad_out /* nullable */, void* stream);
 int nst_warp_bilinear(nst_ctx* ctx, const float* src, const float* flow, int C, int h, int w, float* out,
                       float* valid /* nullable */, void* stream);
 int nst_flow_weights(nst_ctx* ctx, const float* fwd, const float* bwd, int h, int w, float* out, void* stream);
